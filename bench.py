@@ -14,9 +14,13 @@ reservoir layout for a shared GPU) is `lsm_speech_classifier_amd.pipeline.HotPat
 drop-in scripts use.  With --gpus N > 1 and no launcher environment it starts N fresh rank processes
 itself (before anything touches the GPU) and exits with their status.
 
-Prints ONE JSON line on rank 0 with the contract keys plus `roofline` (reservoir kernel, algorithmic
-bytes of SURVEY.md §8(d) / measured HIP-event time; `dominant_kernel_by_time` = the float64 filterbank)
-and, at N=1, `cpu_baseline` (the C oracle timed on the host cores on a bounded sample of the workload).
+Prints ONE JSON line on rank 0 with the contract keys.  A plain run does only what they need: set-up, the
+warm-up steps, the K timed steps (and, with --dump-outputs DIR, DIR/<name>.npy of what the last timed step
+computed).  --full adds everything else the benchmark measures: a first, unprimed pass (`unprimed`), HIP events
+around every reservoir launch of the timed region, idle-GPU launches after it and `roofline` (reservoir kernel,
+algorithmic bytes of SURVEY.md §8(d) / measured HIP-event time; `dominant_kernel_by_time` = the float64
+filterbank), at N=1 `cpu_baseline` (the C oracle timed on the host cores on a bounded sample of the workload), and
+with several ranks the digest of the exchanged rows.
 """
 import argparse
 import json
@@ -62,6 +66,7 @@ def gather_ceiling_gbs(table_bytes):
         return 7400.0, "table <= 256 MiB, served by the Infinity Cache: 7.4 TB/s (151 MB measurement)"
     return 6000.0, "table beyond the Infinity Cache, served by HBM: 6.0 TB/s"
 F64_UNFUSED_PEAK_TOPS = 39.3   # one float64 operation per lane and instruction, all 1024 SIMDs (exp/ubench_f64.hip)
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
 
 
 def parse_args(argv=None):
@@ -75,7 +80,13 @@ def parse_args(argv=None):
                     help="reservoir layout (default: the library chooses, knowing whether steps overlap)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "dense", "ring", "ring-pairs", "ring-quads", "sparse"])
     ap.add_argument("--stage", default="full", choices=["full", "reservoir", "frontend"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: unprimed pass, roofline, CPU baseline, "
+                         "exchange digest (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; "
+                         f"a fixed sample of clips when it exceeds {DUMP_LIMIT_BYTES // 10**6} MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no `cpu_baseline`")
     ap.add_argument("--from-host", action="store_true",
                     help="every step first copies its audio batch from pinned host memory (PCIe-inclusive "
                          "rate; never the contract's `value`, which is quoted on HBM-resident inputs)")
@@ -100,9 +111,12 @@ def parse_args(argv=None):
                     help="the last this-many timed steps are submitted with HotPath.submit(tail=True), as HotPath.run() does "
                          "for the last batches of a finite list (default: the pipeline's TAIL_STEPS; 0 = none)")
     ap.add_argument("--no-unprimed", action="store_true",
-                    help="skip the first, unprimed pass (one step per stream, W warm-up steps, K timed steps: the "
-                         "round-2 protocol) whose figure the line reports as `unprimed` beside the headline")
-    return ap.parse_args(argv)
+                    help="with --full: skip the first, unprimed pass (one step per stream, W warm-up steps, K timed "
+                         "steps: the round-2 protocol) whose figure the line reports as `unprimed` beside the headline")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------ launcher ----
@@ -261,6 +275,22 @@ def cpu_baseline(cfg, audio, res, seconds_budget=24.0):
     }
 
 
+def dump_outputs(out_dir, name, rows):
+    """--dump-outputs: `rows` (first axis = clips) as out_dir/<name>.npy in float32.  Above DUMP_LIMIT_BYTES a fixed
+    sample of clips (seed 0, ascending) is written instead, and their indices as out_dir/<name>_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = rows.shape[0]
+    row_bytes = 4 * (rows[0].numel() if n else 0)
+    if n and n * row_bytes > DUMP_LIMIT_BYTES:
+        k = max(1, (DUMP_LIMIT_BYTES - 1024) // (row_bytes + 8))        # 1 KiB for the two .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+        rows = rows[torch.from_numpy(idx).to(rows.device)]
+    np.save(os.path.join(out_dir, f"{name}.npy"), rows.float().cpu().numpy())
+
+
 def run_rank(args):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("LSM_BENCH_FORCE_DIST") == "1":
         # 5 front-end + 6 reservoir streams + the default stream fill the package's 12 hardware queues; the exchange
@@ -335,7 +365,7 @@ def run_rank(args):
 
     n_streams = args.streams or DEFAULT_STREAMS
     hp = HotPath(fe, net, FEATURE_SET, streams=n_streams, waves_per_clip=args.waves_per_clip,
-                 time_reservoir=True, fe_streams=args.fe_streams)
+                 time_reservoir=args.full, fe_streams=args.fe_streams)
     lay = net.layout(B, fe.n_steps, hp.waves_per_clip)
     audio_pinned = torch.from_numpy(audio_np).pin_memory() if args.from_host else None
     per_step = use_dist and args.exchange == "per-step"
@@ -497,10 +527,10 @@ def run_rank(args):
                            "end_barrier_ms": round(end_fence[0], 4), "end_synchronize_ms": round(end_fence[1], 4)}}
 
     # the 40 ms of HotPath.prime() are a measurement-protocol choice (the clock governor at its working
-    # point, profiles/r03_clock_ramp.txt).  The first pass keeps round 2's protocol -- one step per stream, W warm-up
-    # steps, K timed steps -- and its figure is reported as `unprimed`; the second pass is the headline.
+    # point, profiles/r03_clock_ramp.txt).  With --full a first pass keeps round 2's protocol -- one step per stream, W
+    # warm-up steps, K timed steps -- and its figure is reported as `unprimed`; the second pass is the headline.
     unprimed = None
-    if world == 1 and not use_dist and not args.no_unprimed and args.prime_ms > 0:
+    if args.full and world == 1 and not use_dist and not args.no_unprimed and args.prime_ms > 0:
         u = timed_pass(0.0)
         unprimed = {"value": round(B * args.steps / u["elapsed"], 2), "ms_per_step": round(u["elapsed"] / args.steps * 1e3, 4),
                     "protocol": f"first pass of this run: {u['primed']} untimed steps (one per stream) + {args.warmup} "
@@ -515,6 +545,14 @@ def run_rank(args):
         exchange_ms = float(t.item())
     hp.reservoir_events[:] = res_pass["ev_pairs"]
     ev_pairs = list(hp.reservoir_events)
+    if args.dump_outputs and rank == 0:
+        if gathered is not None:               # what the exchange delivered: every rank's rows of the last step
+            by_rank = lsm_dist.rows_by_rank(gathered[: world * args.steps * B], world, args.steps, chunk, B)
+            last = torch.cat([r[(args.steps - 1) * B:] for r in by_rank])
+            del by_rank
+        else:                                  # this rank's rows (a per-step exchange: every rank's), or its rasters
+            last = out
+        dump_outputs(args.dump_outputs, "rasters" if args.stage == "frontend" else "features", last)
 
     def median_ms(fn, reps=5):
         times = []
@@ -531,16 +569,16 @@ def run_rank(args):
     # outside the timed region, on an otherwise idle GPU: the front end alone, the reservoir launch in the
     # pipeline's layout, and a lone launch in the layout the library picks for that
     fe_ms = gt_ms = serial_ms = lone_ms = None
-    if rank == 0 and args.stage != "reservoir":
+    if args.full and rank == 0 and args.stage != "reservoir":
         fe_ms = median_ms(lambda: fe.encode(audio))
         if cfg["filterbank"] == "gammatone":
             gt_ms = median_ms(lambda: fe.spectrogram_db(audio))
-    if rank == 0 and args.stage != "frontend":
+    if args.full and rank == 0 and args.stage != "frontend":
         lone_ms = median_ms(lambda: net.run_batch(rasters0, FEATURE_SET, waves_per_clip=0))
         serial_ms = median_ms(lambda: net.run_batch(rasters0, FEATURE_SET, waves_per_clip=hp.waves_per_clip))
 
     spikes_per_clip = spikes_total = None
-    if rank == 0 and args.stage != "frontend":
+    if args.full and rank == 0 and args.stage != "frontend":
         st = torch.empty((B, 2), dtype=torch.int32, device=dev)       # untimed: reservoir spikes of the batch
         net.run_batch(rasters0, FEATURE_SET, stats_out=st)
         spikes_total = int(st[:, 1].sum())
@@ -548,7 +586,7 @@ def run_rank(args):
         rows = local_rows[args.steps - 1] if local_rows is not None else out[:B]
         spikes_per_clip = float(rows.float()[:, :cfg["n_out"]].sum(dim=1).mean())
     exchange_digest = None
-    if gathered is not None and args.stage != "frontend":
+    if args.full and gathered is not None and args.stage != "frontend":
         # the gathered block holds every rank's rows, chunk by chunk: put them back into (rank, step, clip) order --
         # this rank's rows must come back unchanged, and the digest of the whole block is the same number whatever the
         # exchange mode (tests/test_gpu_hotpath.py compares 'once' and 'chunked')
@@ -620,7 +658,7 @@ def run_rank(args):
                 "note": "exchange_ms = exposed tail: from the moment the last step's kernels finished to the end of the "
                         "exchange (HIP events, max over ranks), inside the timed region; exchange_bytes = what every "
                         "rank holds afterwards"}
-        if ev_pairs:
+        if args.full and ev_pairs:
             lif_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / len(ev_pairs)
             w_bytes = res.csr_bytes()
             per_clip = fe.n_channels * fe.n_steps + n_feat * 4 + fe.n_steps * w_bytes / B
@@ -736,7 +774,7 @@ def run_rank(args):
                             "the overlapped path runs at the socket's power limit (1380-1390 of 1400 W, shader clock throttled "
                             "to 2.29-2.33 GHz: profiles/r04_clock_power_under_load.txt, not measured in this run)",
                 }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, audio_np, res)
         print(json.dumps(line), flush=True)
     if use_dist:

@@ -9,7 +9,7 @@ rm -rf "$OUT" && mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for P in "valu SQ_INSTS_VALU SQ_INSTS_SALU" "mem SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "smem SQ_INSTS_SMEM SQ_INSTS_VMEM_WR" "waves SQ_WAVES SQ_WAVE_CYCLES" "busy SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU" "lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   set -- $P; name=$1; shift
-  if rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python3 $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --streams 1 ${SQ_EXTRA} > $OUT/$name.json 2> $OUT/$name.err; then
+  if rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python3 $ROOT/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --streams 1 ${SQ_EXTRA} > $OUT/$name.json 2> $OUT/$name.err; then
     echo "pass $name done"
   else
     echo "pass $name FAILED (see $name.err)"

@@ -5,7 +5,7 @@ for V in base new base new; do
   LIB=/root/repo/lsm-speech-classifier_amd/liblsm_hip_$V.so
   [ $V = new ] && LIB=/root/repo/lsm-speech-classifier_amd/liblsm_hip.so
   for A in "--stage frontend --streams 1 --steps 30 --warmup 5" "--steps 20 --warmup 5" "--steps 200 --warmup 12"; do
-  LSM_HIP_LIB=$LIB python3 bench.py $A --no-cpu-baseline 2>/dev/null | python3 -c "
+  LSM_HIP_LIB=$LIB python3 bench.py --full $A --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 r = d.get('roofline', {}); g = r.get('dominant_kernel_by_time', {})

@@ -4,12 +4,12 @@
 OUT=gpurun_out/r03_clock.txt
 : > $OUT
 for N in 1 2 3 4; do
-  python3 bench.py --stage frontend --streams $N --fe-streams 0 --steps 60 --warmup 8 --no-cpu-baseline 2>/dev/null | python3 -c "
+  python3 bench.py --full --stage frontend --streams $N --fe-streams 0 --steps 60 --warmup 8 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('front ends in flight $N: ms/step', d['ms_per_step'], '-> per launch', round(d['ms_per_step'] * $N, 4), 'ms')" | tee -a $OUT
 done
-( python3 bench.py --stage frontend --streams 4 --fe-streams 0 --steps 4000 --warmup 8 --no-cpu-baseline > /dev/null 2>&1 ) &
+( python3 bench.py --full --stage frontend --streams 4 --fe-streams 0 --steps 4000 --warmup 8 --no-cpu-baseline > /dev/null 2>&1 ) &
 BP=$!
 sleep 6
 for i in 1 2 3 4 5; do

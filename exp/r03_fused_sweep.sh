@@ -18,8 +18,8 @@ MODE=${1:-all}
 if [ $MODE = ab ] || [ $MODE = all ]; then
   for rep in 1 2; do
     for A in "--steps 20 --warmup 5" "--steps 200 --warmup 12"; do
-      run "split $A" LSM_FRONTEND_SPLIT=1 python3 bench.py $A --no-cpu-baseline
-      run "fused $A" python3 bench.py $A --no-cpu-baseline
+      run "split $A" LSM_FRONTEND_SPLIT=1 python3 bench.py --full $A --no-cpu-baseline
+      run "fused $A" python3 bench.py --full $A --no-cpu-baseline
     done
   done
 fi
@@ -27,7 +27,7 @@ if [ $MODE = sweep ] || [ $MODE = all ]; then
   for CFG in ${CFGS:-"2 4 82944" "2 4 0" "2 4 41000" "2 2 82944" "2 2 41000" "2 1 82944" "2 1 41000" "2 1 20000" "2 8 82944" "1 4 82944" "1 4 41000" "1 8 82944"}; do
     set -- $CFG
     for A in "--steps 20 --warmup 5" "--steps 200 --warmup 12"; do
-      run "nch $1 wpb $2 lds $3 $A" LSM_HIP_LIB=$HOOKS LSM_GTF_NCH=$1 LSM_GTF_WPB=$2 LSM_GTF_LDS=$3 python3 bench.py $A --no-cpu-baseline
+      run "nch $1 wpb $2 lds $3 $A" LSM_HIP_LIB=$HOOKS LSM_GTF_NCH=$1 LSM_GTF_WPB=$2 LSM_GTF_LDS=$3 python3 bench.py --full $A --no-cpu-baseline
     done
   done
 fi

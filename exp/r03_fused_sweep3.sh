@@ -13,13 +13,13 @@ print('$label', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lif in-
 " | tee -a $OUT
 }
 for A in "--steps 20 --warmup 5" "--steps 200 --warmup 12"; do
-  run "split streams 6 $A" LSM_FRONTEND_SPLIT=1 python3 bench.py $A --no-cpu-baseline
+  run "split streams 6 $A" LSM_FRONTEND_SPLIT=1 python3 bench.py --full $A --no-cpu-baseline
 done
 for CFG in ${CFGS:-"2 4 82944" "2 4 41000" "2 2 41000" "2 1 20000" "1 4 82944" "1 4 41000" "1 8 82944"}; do
   set -- $CFG
   for A in "--stage frontend --steps 100 --warmup 12" "--steps 20 --warmup 5" "--steps 200 --warmup 12"; do
     for ST in ${STS:-6 10}; do
-      run "nch $1 wpb $2 lds $3 streams $ST $A" LSM_HIP_LIB=$HOOKS LSM_GTF_NCH=$1 LSM_GTF_WPB=$2 LSM_GTF_LDS=$3 python3 bench.py $A --streams $ST --no-cpu-baseline
+      run "nch $1 wpb $2 lds $3 streams $ST $A" LSM_HIP_LIB=$HOOKS LSM_GTF_NCH=$1 LSM_GTF_WPB=$2 LSM_GTF_LDS=$3 python3 bench.py --full $A --streams $ST --no-cpu-baseline
     done
   done
 done

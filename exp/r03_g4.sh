@@ -16,12 +16,12 @@ print('$label', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lif in-
 for rep in 1 2 3; do
   for V in g8 g4; do
     L="LSM_X=0"; [ $V = g4 ] && L="LSM_HIP_LIB=$G4"
-    run "$V --steps 20 --warmup 5" $L python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    run "$V --steps 20 --warmup 5" $L python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   done
 done
 for rep in 1 2; do
   for V in g8 g4; do
     L="LSM_X=0"; [ $V = g4 ] && L="LSM_HIP_LIB=$G4"
-    run "$V --steps 200 --warmup 12" $L python3 bench.py --steps 200 --warmup 12 --no-cpu-baseline
+    run "$V --steps 200 --warmup 12" $L python3 bench.py --full --steps 200 --warmup 12 --no-cpu-baseline
   done
 done

@@ -13,11 +13,11 @@ print('$label', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lif in-
 }
 for rep in 1 2 3 4; do
   for W in 0 1; do
-    run "pool $W --steps 20 --warmup 5" LSM_HOTPATH_POOL=$W python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    run "pool $W --steps 20 --warmup 5" LSM_HOTPATH_POOL=$W python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   done
 done
 for rep in 1 2; do
   for W in 0 1; do
-    run "pool $W --steps 200 --warmup 12" LSM_HOTPATH_POOL=$W python3 bench.py --steps 200 --warmup 12 --no-cpu-baseline
+    run "pool $W --steps 200 --warmup 12" LSM_HOTPATH_POOL=$W python3 bench.py --full --steps 200 --warmup 12 --no-cpu-baseline
   done
 done

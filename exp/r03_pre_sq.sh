@@ -7,10 +7,10 @@ cd /tmp && export TMPDIR=/tmp
 for V in prev new; do
   if [ $V = prev ]; then export LSM_HIP_LIB=$ROOT/lsm-speech-classifier_amd/liblsm_hip_prev.so; else unset LSM_HIP_LIB; fi
   A="--stage frontend --streams 1 --steps 6 --warmup 2 --no-cpu-baseline"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${V}_stats -- python3 $ROOT/bench.py $A > $OUT/${V}_stats.json 2> $OUT/${V}_stats.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${V}_stats -- python3 $ROOT/bench.py --full $A > $OUT/${V}_stats.json 2> $OUT/${V}_stats.err || exit 1
   for P in "valu SQ_INSTS_VALU SQ_INSTS_SALU" "smem SQ_INSTS_SMEM SQ_INSTS_VMEM_RD" "waves SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "wait SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" "wait2 SQ_WAIT_ANY SQ_INST_CYCLES_SALU"; do
     set -- $P; name=$1; shift
-    rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/${V}_$name -- python3 $ROOT/bench.py $A > $OUT/${V}_$name.json 2> $OUT/${V}_$name.err || exit 1
+    rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/${V}_$name -- python3 $ROOT/bench.py --full $A > $OUT/${V}_$name.json 2> $OUT/${V}_$name.err || exit 1
   done
   echo "$V done"
 done

@@ -17,7 +17,7 @@ for LIB in hooks hooks_noprio; do
     for TOPO in "4 6" "0 6"; do
       set -- $TOPO
       for A in "--steps 20 --warmup 5" "--steps 200 --warmup 12"; do
-        run "lib $LIB fe_prio $PR fe_streams $1 streams $2 $A" LSM_HIP_LIB=/root/repo/lsm-speech-classifier_amd/liblsm_hip_$LIB.so LSM_GTF_PRIO=$PR python3 bench.py $A --fe-streams $1 --streams $2 --no-cpu-baseline
+        run "lib $LIB fe_prio $PR fe_streams $1 streams $2 $A" LSM_HIP_LIB=$PWD/lsm-speech-classifier_amd/liblsm_hip_$LIB.so LSM_GTF_PRIO=$PR python3 bench.py --full $A --fe-streams $1 --streams $2 --no-cpu-baseline
       done
     done
   done

@@ -16,12 +16,12 @@ print('$label', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; kernel'
 for rep in 1 2; do
   for V in prev new; do
     L=""; [ $V = prev ] && L="LSM_HIP_LIB=$PREV"
-    run "$V cfg4 B1024 reservoir" $L python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline
-    run "$V cfg5 B512 reservoir" $L python3 bench.py --config cfg5 --batch 512 --stage reservoir --streams 1 --steps 6 --warmup 2 --no-cpu-baseline
+    run "$V cfg4 B1024 reservoir" $L python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline
+    run "$V cfg5 B512 reservoir" $L python3 bench.py --full --config cfg5 --batch 512 --stage reservoir --streams 1 --steps 6 --warmup 2 --no-cpu-baseline
   done
 done
 for V in prev new; do
   L=""; [ $V = prev ] && L="LSM_HIP_LIB=$PREV"
-  run "$V cfg5 B4096 reservoir" $L python3 bench.py --config cfg5 --stage reservoir --streams 1 --steps 3 --warmup 1 --no-cpu-baseline
-  run "$V cfg4 whole path" $L python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline
+  run "$V cfg5 B4096 reservoir" $L python3 bench.py --full --config cfg5 --stage reservoir --streams 1 --steps 3 --warmup 1 --no-cpu-baseline
+  run "$V cfg4 whole path" $L python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline
 done

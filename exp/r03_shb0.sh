@@ -7,7 +7,7 @@ for rep in 1 2 3; do
   for V in prev new; do
     L="LSM_X=0"; [ $V = prev ] && L="LSM_HIP_LIB=$PREV"
     for ARGS in "--stage frontend --steps 200 --warmup 12" "--steps 200 --warmup 12" "--steps 20 --warmup 5"; do
-      env $L python3 bench.py $ARGS --no-cpu-baseline 2>/dev/null | python3 -c "
+      env $L python3 bench.py --full $ARGS --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$V $ARGS ->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step')" | tee -a $OUT

@@ -14,13 +14,13 @@ print('$label', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lif in-
 }
 for rep in 1 2 3 4; do
   for W in 0 1; do
-    run "wide_when_idle $W --steps 20 --warmup 5" LSM_FE_WIDE_WHEN_IDLE=$W python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    run "wide_when_idle $W --steps 20 --warmup 5" LSM_FE_WIDE_WHEN_IDLE=$W python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   done
 done
 for rep in 1 2; do
   for W in 0 1; do
-    run "wide_when_idle $W --steps 200 --warmup 12" LSM_FE_WIDE_WHEN_IDLE=$W python3 bench.py --steps 200 --warmup 12 --no-cpu-baseline
+    run "wide_when_idle $W --steps 200 --warmup 12" LSM_FE_WIDE_WHEN_IDLE=$W python3 bench.py --full --steps 200 --warmup 12 --no-cpu-baseline
   done
 done
-run "split rotation --steps 20 --warmup 5" LSM_FRONTEND_SPLIT=1 python3 bench.py --steps 20 --warmup 5 --fe-streams 0 --no-cpu-baseline
-run "split rotation --steps 20 --warmup 5" LSM_FRONTEND_SPLIT=1 python3 bench.py --steps 20 --warmup 5 --fe-streams 0 --no-cpu-baseline
+run "split rotation --steps 20 --warmup 5" LSM_FRONTEND_SPLIT=1 python3 bench.py --full --steps 20 --warmup 5 --fe-streams 0 --no-cpu-baseline
+run "split rotation --steps 20 --warmup 5" LSM_FRONTEND_SPLIT=1 python3 bench.py --full --steps 20 --warmup 5 --fe-streams 0 --no-cpu-baseline

@@ -12,9 +12,9 @@ print('$label', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lif in-
 }
 for rep in 1 2 3; do
   for W in 1 2 3; do
-    run "wide_below $W --steps 20 --warmup 5" LSM_FE_WIDE_BELOW=$W python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    run "wide_below $W --steps 20 --warmup 5" LSM_FE_WIDE_BELOW=$W python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   done
 done
 for W in 1 2 3; do
-  run "wide_below $W --steps 200 --warmup 12" LSM_FE_WIDE_BELOW=$W python3 bench.py --steps 200 --warmup 12 --no-cpu-baseline
+  run "wide_below $W --steps 200 --warmup 12" LSM_FE_WIDE_BELOW=$W python3 bench.py --full --steps 200 --warmup 12 --no-cpu-baseline
 done

@@ -17,13 +17,13 @@ V=exp/variants
 for rep in 1 2; do
   for C in "before $V/liblsm_hooks.so 0" "masks_P4_inreg $V/liblsm_hooks_new.so 0" "masks_P4_streamed $V/liblsm_hooks_new.so 1" "masks_P6_inreg $V/liblsm_ring_p6.so 0" "masks_P6_streamed $V/liblsm_ring_p6.so 1" "masks_P8_streamed $V/liblsm_ring_p8.so 1"; do
     set -- $C
-    LSM_HIP_LIB=$2 LSM_RING_NO_INREG=$3 python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir $1" >> $O/ring_p.txt
+    LSM_HIP_LIB=$2 LSM_RING_NO_INREG=$3 python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir $1" >> $O/ring_p.txt
   done
 done
 for C in "before $V/liblsm_hooks.so 0" "masks_P4 $V/liblsm_hooks_new.so 0" "masks_P6 $V/liblsm_ring_p6.so 0" "masks_P8 $V/liblsm_ring_p8.so 0"; do
   set -- $C
-  LSM_HIP_LIB=$2 python3 bench.py --config cfg5 --batch 512 --stage reservoir --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B512 reservoir $1" >> $O/ring_p.txt
-  LSM_HIP_LIB=$2 python3 bench.py --config cfg5 --stage reservoir --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B4096 reservoir $1" >> $O/ring_p.txt
-  LSM_HIP_LIB=$2 LSM_RING_NO_INREG=1 python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path $1 (streamed)" >> $O/ring_p.txt
+  LSM_HIP_LIB=$2 python3 bench.py --full --config cfg5 --batch 512 --stage reservoir --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B512 reservoir $1" >> $O/ring_p.txt
+  LSM_HIP_LIB=$2 python3 bench.py --full --config cfg5 --stage reservoir --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B4096 reservoir $1" >> $O/ring_p.txt
+  LSM_HIP_LIB=$2 LSM_RING_NO_INREG=1 python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path $1 (streamed)" >> $O/ring_p.txt
 done
 cat $O/ring_p.txt

@@ -16,11 +16,11 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 H=exp/variants/liblsm_hooks.so
 for rep in 1 2 3; do
   for V in 1 0; do
-    LSM_HIP_LIB=$H LSM_RING_NO_INMASK=$V python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir no_inmask=$V" >> $O/ring_mask.txt
+    LSM_HIP_LIB=$H LSM_RING_NO_INMASK=$V python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir no_inmask=$V" >> $O/ring_mask.txt
   done
 done
 for V in 1 0; do
-  LSM_HIP_LIB=$H LSM_RING_NO_INMASK=$V python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path no_inmask=$V" >> $O/ring_mask.txt
-  LSM_HIP_LIB=$H LSM_RING_NO_INMASK=$V python3 bench.py --config cfg4 --batch 256 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 B256 reservoir no_inmask=$V" >> $O/ring_mask.txt
+  LSM_HIP_LIB=$H LSM_RING_NO_INMASK=$V python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path no_inmask=$V" >> $O/ring_mask.txt
+  LSM_HIP_LIB=$H LSM_RING_NO_INMASK=$V python3 bench.py --full --config cfg4 --batch 256 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 B256 reservoir no_inmask=$V" >> $O/ring_mask.txt
 done
 cat $O/ring_mask.txt

@@ -13,12 +13,12 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 for rep in 1 2; do
   for P in 0 1 2 3; do
     L=exp/variants/liblsm_ring_prio$P.so; [ $P = 0 ] && L=
-    LSM_HIP_LIB=$L python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path ring prio $P" >> $O/prio.txt
+    LSM_HIP_LIB=$L python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path ring prio $P" >> $O/prio.txt
   done
 done
 for P in 0 1 2 3; do
   L=exp/variants/liblsm_ring_prio$P.so; [ $P = 0 ] && L=
-  LSM_HIP_LIB=$L python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir alone ring prio $P" >> $O/prio.txt
-  LSM_HIP_LIB=$L python3 bench.py --config cfg5 --steps 4 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 whole path ring prio $P" >> $O/prio.txt
+  LSM_HIP_LIB=$L python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir alone ring prio $P" >> $O/prio.txt
+  LSM_HIP_LIB=$L python3 bench.py --full --config cfg5 --steps 4 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 whole path ring prio $P" >> $O/prio.txt
 done
 cat $O/prio.txt

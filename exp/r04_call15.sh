@@ -14,8 +14,8 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 H=exp/variants/liblsm_hooks.so
 run() {  # label, env..., -- bench args
   local label="$1"; shift
-  env "$@" LSM_HIP_LIB=$H python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed $EXTRA 2>/dev/null | line "$label driver" >> $O/fe1.txt
-  env "$@" LSM_HIP_LIB=$H python3 bench.py --no-cpu-baseline --no-unprimed $EXTRA 2>/dev/null | line "$label 200steps" >> $O/fe1.txt
+  env "$@" LSM_HIP_LIB=$H python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed $EXTRA 2>/dev/null | line "$label driver" >> $O/fe1.txt
+  env "$@" LSM_HIP_LIB=$H python3 bench.py --full --no-cpu-baseline --no-unprimed $EXTRA 2>/dev/null | line "$label 200steps" >> $O/fe1.txt
 }
 EXTRA="" run "product layout (nch 2, 82944), fe_streams 5" LSM_X=0
 for LDS in 82944 41000 33000; do for FS in 3 4 5 6; do

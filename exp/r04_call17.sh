@@ -12,10 +12,10 @@ d = json.loads(ls[-1]); x = d.get('exchange') or {}
 print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; exchange', {k: x.get(k) for k in ('mode', 'exchange_ms', 'exchange_bytes', 'collectives')}, 'hw queues', d.get('config', {}).get('hw_queues'))
 "; }
 for rep in 1 2 3; do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain N=1 (12 queues)" >> $O/x.txt
-  GPU_MAX_HW_QUEUES=16 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain N=1, 16 queues" >> $O/x.txt
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain N=1 (12 queues)" >> $O/x.txt
+  GPU_MAX_HW_QUEUES=16 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain N=1, 16 queues" >> $O/x.txt
   for M in chunked once per-step; do
-    RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 LSM_BENCH_FORCE_DIST=1 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange $M 2>$O/err_$M.txt | line "one RCCL rank, exchange $M" >> $O/x.txt
+    RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 LSM_BENCH_FORCE_DIST=1 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange $M 2>$O/err_$M.txt | line "one RCCL rank, exchange $M" >> $O/x.txt
   done
 done
 cat $O/x.txt

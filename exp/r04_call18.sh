@@ -13,12 +13,12 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; fences', d.
 "; }
 D="RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 LSM_BENCH_FORCE_DIST=1"
 for rep in 1 2 3; do if false; then
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain" >> $O/x.txt
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain" >> $O/x.txt
   for I in 0.2 0.5 1 3; do
-    LSM_BENCH_DIAG_IDLE_MS=$I python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain, idle $I ms before the region" >> $O/x.txt
+    LSM_BENCH_DIAG_IDLE_MS=$I python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "plain, idle $I ms before the region" >> $O/x.txt
   done
-  fi; env $D python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange once 2>/dev/null | line "one RCCL rank, once" >> $O/x.txt
-  env $D python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange chunked 2>/dev/null | line "one RCCL rank, chunked" >> $O/x.txt
-  env $D LSM_BENCH_BACKEND=gloo python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange once 2>/dev/null | line "one gloo rank, once" >> $O/x.txt
+  fi; env $D python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange once 2>/dev/null | line "one RCCL rank, once" >> $O/x.txt
+  env $D python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange chunked 2>/dev/null | line "one RCCL rank, chunked" >> $O/x.txt
+  env $D LSM_BENCH_BACKEND=gloo python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --exchange once 2>/dev/null | line "one gloo rank, once" >> $O/x.txt
 done
 cat $O/x.txt

@@ -15,19 +15,19 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 H=exp/variants/liblsm_hooks.so
 for rep in 1 2 3; do
   for V in 1 0; do
-    LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line "no_refm=$V driver" >> $O/refm_ab.txt
-    LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V 200steps" >> $O/refm_ab.txt
+    LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | line "no_refm=$V driver" >> $O/refm_ab.txt
+    LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --full --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V 200steps" >> $O/refm_ab.txt
   done
 done
 for V in 1 0; do
-  LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --stage reservoir --streams 1 --steps 40 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V reservoir alone (8 waves)" >> $O/refm_ab.txt
-  LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --stage reservoir --steps 200 --warmup 12 --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V reservoir stage, pipeline topology" >> $O/refm_ab.txt
-  LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --config cfg1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V cfg1" >> $O/refm_ab.txt
+  LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --full --stage reservoir --streams 1 --steps 40 --warmup 5 --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V reservoir alone (8 waves)" >> $O/refm_ab.txt
+  LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --full --stage reservoir --steps 200 --warmup 12 --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V reservoir stage, pipeline topology" >> $O/refm_ab.txt
+  LSM_HIP_LIB=$H LSM_DENSE_NO_REFM=$V python3 bench.py --full --config cfg1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "no_refm=$V cfg1" >> $O/refm_ab.txt
 done
 cat $O/refm_ab.txt
 for rep in 1 2; do
   for L in "" exp/variants/liblsm_ring_input_twice.so exp/variants/liblsm_ring_nofeat.so; do
-    LSM_HIP_LIB=$L python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir lib=${L:-product}" >> $O/ring_ablate.txt
+    LSM_HIP_LIB=$L python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir lib=${L:-product}" >> $O/ring_ablate.txt
   done
 done
 cat $O/ring_ablate.txt

@@ -15,22 +15,22 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 H=exp/variants/liblsm_hooks.so
 for rep in 1 2; do
   for V in 1 0; do
-    LSM_HIP_LIB=$H LSM_RING_NO_INREG=$V python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir no_inreg=$V" >> $O/ring_ab.txt
+    LSM_HIP_LIB=$H LSM_RING_NO_INREG=$V python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir no_inreg=$V" >> $O/ring_ab.txt
   done
-  LSM_HIP_LIB=exp/variants/liblsm_ring_input_twice.so python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir input drive twice" >> $O/ring_ab.txt
+  LSM_HIP_LIB=exp/variants/liblsm_ring_input_twice.so python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir input drive twice" >> $O/ring_ab.txt
 done
-python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path" >> $O/ring_ab.txt
-python3 bench.py --config cfg5 --batch 512 --stage reservoir --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B512 reservoir" >> $O/ring_ab.txt
-python3 bench.py --config cfg5 --stage reservoir --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B4096 reservoir" >> $O/ring_ab.txt
+python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path" >> $O/ring_ab.txt
+python3 bench.py --full --config cfg5 --batch 512 --stage reservoir --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B512 reservoir" >> $O/ring_ab.txt
+python3 bench.py --full --config cfg5 --stage reservoir --streams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 B4096 reservoir" >> $O/ring_ab.txt
 cat $O/ring_ab.txt
 for rep in 1 2 3; do
   for TS in 0 1 2 3 4; do
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed --tail-steps $TS 2>/dev/null | line "tail_steps=$TS driver" >> $O/tail.txt
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed --tail-steps $TS 2>/dev/null | line "tail_steps=$TS driver" >> $O/tail.txt
   done
 done
 for TS in 0 1 2; do
-  LSM_TAIL_LONE_LAYOUT=0 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed --tail-steps $TS 2>/dev/null | line "tail_steps=$TS driver, reservoir layout unchanged" >> $O/tail.txt
-  python3 bench.py --no-cpu-baseline --no-unprimed --tail-steps $TS 2>/dev/null | line "tail_steps=$TS 200steps" >> $O/tail.txt
+  LSM_TAIL_LONE_LAYOUT=0 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed --tail-steps $TS 2>/dev/null | line "tail_steps=$TS driver, reservoir layout unchanged" >> $O/tail.txt
+  python3 bench.py --full --no-cpu-baseline --no-unprimed --tail-steps $TS 2>/dev/null | line "tail_steps=$TS 200steps" >> $O/tail.txt
 done
 cat $O/tail.txt
 for W in 8 4; do LSM_HIP_LIB=exp/variants/liblsm_stamp.so python3 exp/stamp_run.py $W 256 >> $O/stamps.txt 2>&1; done

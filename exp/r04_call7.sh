@@ -14,13 +14,13 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step')
 "; }
 H=exp/variants/liblsm_hooks.so
 for rep in 1 2; do
-  LSM_HIP_LIB=$H LSM_FRONTEND_SPLIT=1 python3 bench.py --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 whole path, split route" >> $O/mel_ab.txt
-  LSM_HIP_LIB=$H LSM_FRONTEND_SPLIT=1 python3 bench.py --config cfg1 --stage frontend --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front ends alone, split route" >> $O/mel_ab.txt
-  LSM_HIP_LIB=$H LSM_FRONTEND_SPLIT=1 python3 bench.py --config cfg1 --stage frontend --streams 1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front end, one stream, split route" >> $O/mel_ab.txt
+  LSM_HIP_LIB=$H LSM_FRONTEND_SPLIT=1 python3 bench.py --full --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 whole path, split route" >> $O/mel_ab.txt
+  LSM_HIP_LIB=$H LSM_FRONTEND_SPLIT=1 python3 bench.py --full --config cfg1 --stage frontend --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front ends alone, split route" >> $O/mel_ab.txt
+  LSM_HIP_LIB=$H LSM_FRONTEND_SPLIT=1 python3 bench.py --full --config cfg1 --stage frontend --streams 1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front end, one stream, split route" >> $O/mel_ab.txt
   for G in 1 4 8 16 32 101; do
-    LSM_HIP_LIB=$H LSM_MEL_FRAMES_PER_WG=$G python3 bench.py --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 whole path, one launch, $G frames per workgroup" >> $O/mel_ab.txt
-    LSM_HIP_LIB=$H LSM_MEL_FRAMES_PER_WG=$G python3 bench.py --config cfg1 --stage frontend --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front ends alone, one launch, $G frames per workgroup" >> $O/mel_ab.txt
-    LSM_HIP_LIB=$H LSM_MEL_FRAMES_PER_WG=$G python3 bench.py --config cfg1 --stage frontend --streams 1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front end, one stream, one launch, $G frames per workgroup" >> $O/mel_ab.txt
+    LSM_HIP_LIB=$H LSM_MEL_FRAMES_PER_WG=$G python3 bench.py --full --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 whole path, one launch, $G frames per workgroup" >> $O/mel_ab.txt
+    LSM_HIP_LIB=$H LSM_MEL_FRAMES_PER_WG=$G python3 bench.py --full --config cfg1 --stage frontend --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front ends alone, one launch, $G frames per workgroup" >> $O/mel_ab.txt
+    LSM_HIP_LIB=$H LSM_MEL_FRAMES_PER_WG=$G python3 bench.py --full --config cfg1 --stage frontend --streams 1 --steps 60 --warmup 8 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg1 front end, one stream, one launch, $G frames per workgroup" >> $O/mel_ab.txt
   done
 done
 cat $O/mel_ab.txt

@@ -18,16 +18,16 @@ for rep in 1 2; do
   for V in "4 -1" "4 0" "2 -1" "1 -1"; do
     set -- $V
     E="LSM_GTF_WPB=$1"; [ "$2" != "-1" ] && E="$E LSM_GTF_LDS=$2"
-    env LSM_HIP_LIB=$H $E python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path, fe waves per workgroup $1, reservation ${2}" >> $O/cfg4_fe_lds.txt
+    env LSM_HIP_LIB=$H $E python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path, fe waves per workgroup $1, reservation ${2}" >> $O/cfg4_fe_lds.txt
   done
   for FS in 2 3; do
-    env LSM_HIP_LIB=$H python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed --fe-streams $FS --streams 3 2>/dev/null | line "cfg4 whole path, fe_streams $FS, streams 3" >> $O/cfg4_fe_lds.txt
+    env LSM_HIP_LIB=$H python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed --fe-streams $FS --streams 3 2>/dev/null | line "cfg4 whole path, fe_streams $FS, streams 3" >> $O/cfg4_fe_lds.txt
   done
-  env LSM_HIP_LIB=$H python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed --fe-streams 0 --streams 3 2>/dev/null | line "cfg4 whole path, rotation over 3 streams" >> $O/cfg4_fe_lds.txt
+  env LSM_HIP_LIB=$H python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed --fe-streams 0 --streams 3 2>/dev/null | line "cfg4 whole path, rotation over 3 streams" >> $O/cfg4_fe_lds.txt
 done
 cat $O/cfg4_fe_lds.txt
 for V in "4 -1" "1 -1"; do
   set -- $V
-  env LSM_HIP_LIB=$H LSM_GTF_WPB=$1 python3 bench.py --config cfg5 --steps 4 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 whole path, fe waves per workgroup $1" >> $O/cfg5_fe_lds.txt
+  env LSM_HIP_LIB=$H LSM_GTF_WPB=$1 python3 bench.py --full --config cfg5 --steps 4 --warmup 1 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg5 whole path, fe waves per workgroup $1" >> $O/cfg5_fe_lds.txt
 done
 cat $O/cfg5_fe_lds.txt

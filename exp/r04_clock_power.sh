@@ -5,9 +5,9 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r04_clock_power; mkdir -p $O
 sample() {   # label, bench args...
   local label="$1"; shift
-  ( python3 bench.py "$@" --no-cpu-baseline --no-unprimed > $O/line.json 2>/dev/null ) &
+  ( python3 bench.py --full "$@" --no-cpu-baseline --no-unprimed > $O/line.json 2>/dev/null ) &
   local BP=$!
-  echo "## $label: python3 bench.py $*" >> $O/out.txt
+  echo "## $label: python3 bench.py --full $*" >> $O/out.txt
   local t0=$(date +%s.%N)
   while kill -0 $BP 2>/dev/null; do
     local s=$(rocm-smi --showclocks --showpower 2>/dev/null | grep -E "sclk|Power" | sed -E 's/.*\((.*Mhz)\).*/\1/; s/.*Power \(W\): //' | tr '\n' ' ')

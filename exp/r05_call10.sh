@@ -15,8 +15,8 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 "; }
 for rep in 1 2; do
   for K in ring ring-pairs-rowlists ring-quads; do
-    timeout -k 10 300 python3 bench.py --config cfg4 --kernel $K --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_$K.txt | line "cfg4 reservoir $K" | tee -a $O/pairs.txt
+    timeout -k 10 300 python3 bench.py --full --config cfg4 --kernel $K --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_$K.txt | line "cfg4 reservoir $K" | tee -a $O/pairs.txt
   done
 done
-timeout -k 10 300 python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path (auto)" | tee -a $O/pairs.txt
+timeout -k 10 300 python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path (auto)" | tee -a $O/pairs.txt
 LSM_HIP_LIB=exp/variants/lib_pair_phases.so timeout -k 10 300 python3 exp/r03_ring_phases.py cfg4 1024 > $O/phases.txt 2>&1; tail -14 $O/phases.txt

@@ -13,7 +13,7 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 "; }
 for rep in 1 2 3; do
   for K in ring ring-pairs-rowlists ring-quads; do
-    timeout -k 10 300 python3 bench.py --config cfg4 --kernel $K --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>$O/err_$K.txt | line "cfg4 whole path $K" | tee -a $O/whole.txt
+    timeout -k 10 300 python3 bench.py --full --config cfg4 --kernel $K --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>$O/err_$K.txt | line "cfg4 whole path $K" | tee -a $O/whole.txt
   done
 done
 timeout -k 10 600 python3 -m pytest tests/test_gpu_parity.py -m gpu -q -k "full_size or mel or nan" > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log

@@ -16,12 +16,12 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 H=exp/variants/liblsm_hooks.so
 for rep in 1 2; do
   for V in 0 1; do
-    LSM_HIP_LIB=$H LSM_PAIR_NO_FEATG=$V timeout -k 10 300 python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_r$V.txt | line "cfg4 reservoir no_featg=$V" | tee -a $O/featg.txt
+    LSM_HIP_LIB=$H LSM_PAIR_NO_FEATG=$V timeout -k 10 300 python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_r$V.txt | line "cfg4 reservoir no_featg=$V" | tee -a $O/featg.txt
   done
 done
 for rep in 1 2; do
   for V in 0 1; do
-    LSM_HIP_LIB=$H LSM_PAIR_NO_FEATG=$V timeout -k 10 300 python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>$O/err_w$V.txt | line "cfg4 whole path no_featg=$V" | tee -a $O/featg.txt
+    LSM_HIP_LIB=$H LSM_PAIR_NO_FEATG=$V timeout -k 10 300 python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>$O/err_w$V.txt | line "cfg4 whole path no_featg=$V" | tee -a $O/featg.txt
   done
 done
 LSM_HIP_LIB=exp/variants/lib_pair_phases.so timeout -k 10 300 python3 exp/r03_ring_phases.py cfg4 1024 > $O/phases.txt 2>&1; tail -14 $O/phases.txt

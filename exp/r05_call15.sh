@@ -16,6 +16,6 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 for rep in 1 2; do
 for S in "5 6" "4 6" "6 6" "3 6" "5 4" "5 8" "4 4" "6 8"; do
   set -- $S
-  timeout -k 10 300 python3 bench.py --config cfg4 --fe-streams $1 --streams $2 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path fe-streams=$1 streams=$2" | tee -a $O/streams.txt
+  timeout -k 10 300 python3 bench.py --full --config cfg4 --fe-streams $1 --streams $2 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path fe-streams=$1 streams=$2" | tee -a $O/streams.txt
 done
 done

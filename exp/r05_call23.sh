@@ -14,8 +14,8 @@ d = json.loads(ls[-1]); r = d.get('roofline', {})
 print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.get('kernel_ms'))
 "; }
 for rep in 1 2 3; do
-  timeout -k 10 300 python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err.txt | line "cfg4 reservoir chunk64" | tee -a $O/chunk.txt
+  timeout -k 10 300 python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err.txt | line "cfg4 reservoir chunk64" | tee -a $O/chunk.txt
 done
 for rep in 1 2; do
-  timeout -k 10 300 python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>$O/err_full.txt | line "cfg4 whole path chunk64" | tee -a $O/chunk.txt
+  timeout -k 10 300 python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>$O/err_full.txt | line "cfg4 whole path chunk64" | tee -a $O/chunk.txt
 done

@@ -12,9 +12,9 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 "; }
 for rep in 1 2; do
 for K in dense ring-pairs ring-quads; do
-  timeout -k 10 300 python3 bench.py --config cfg2 --kernel $K --stage reservoir --streams 1 --steps 40 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_$K.txt | line "cfg2 reservoir $K" | tee -a $O/cfg2.txt
+  timeout -k 10 300 python3 bench.py --full --config cfg2 --kernel $K --stage reservoir --streams 1 --steps 40 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_$K.txt | line "cfg2 reservoir $K" | tee -a $O/cfg2.txt
 done
 done
 for K in dense ring-pairs; do
-  timeout -k 10 300 python3 bench.py --config cfg2 --kernel $K --steps 200 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_full_$K.txt | line "cfg2 whole path 200 steps $K" | tee -a $O/cfg2.txt
+  timeout -k 10 300 python3 bench.py --full --config cfg2 --kernel $K --steps 200 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_full_$K.txt | line "cfg2 whole path 200 steps $K" | tee -a $O/cfg2.txt
 done

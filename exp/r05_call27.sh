@@ -9,11 +9,11 @@ tail -15 $O/pytest.log | tee -a $O/summary.txt
 cd /tmp && export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py"
 O=$GRAFT_REPO_ROOT/$O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_fe -- $B --config cfg1 --stage frontend --steps 40 --warmup 5 --streams 1 --no-cpu-baseline --no-unprimed > $O/fe.json 2> $O/fe.err && echo "front-end stats done"
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_fe -- $B --full --config cfg1 --stage frontend --steps 40 --warmup 5 --streams 1 --no-cpu-baseline --no-unprimed > $O/fe.json 2> $O/fe.err && echo "front-end stats done"
 c=$(find $O/stats_fe -name "*kernel_stats.csv" | head -1); head -5 $c | cut -c1-220
-$B --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline > $O/cfg1.json 2> $O/cfg1.err && python3 -c "
+$B --full --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline > $O/cfg1.json 2> $O/cfg1.err && python3 -c "
 import json
 d=json.loads([l for l in open('$O/cfg1.json') if l.startswith('{')][-1]); print('cfg1', d['value'], d['ms_per_step'], 'unprimed', d['unprimed']['value'])"
-$B --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline > $O/cfg1b.json 2> $O/cfg1b.err && python3 -c "
+$B --full --config cfg1 --steps 60 --warmup 8 --no-cpu-baseline > $O/cfg1b.json 2> $O/cfg1b.err && python3 -c "
 import json
 d=json.loads([l for l in open('$O/cfg1b.json') if l.startswith('{')][-1]); print('cfg1', d['value'], d['ms_per_step'], 'unprimed', d['unprimed']['value'])"

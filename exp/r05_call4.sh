@@ -16,10 +16,10 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 for rep in 1 2; do
   for V in product pair_p2 pair_p6; do
     if [ $V = product ]; then L=""; else L=exp/variants/lib_$V.so; fi
-    LSM_HIP_LIB=$L timeout -k 10 300 python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_$V.txt | line "cfg4 reservoir $V" >> $O/pairs.txt
+    LSM_HIP_LIB=$L timeout -k 10 300 python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_$V.txt | line "cfg4 reservoir $V" >> $O/pairs.txt
   done
 done
-timeout -k 10 300 python3 bench.py --config cfg4 --kernel ring-quads --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir ring-quads" >> $O/pairs.txt
-timeout -k 10 300 python3 bench.py --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path (auto)" >> $O/pairs.txt
+timeout -k 10 300 python3 bench.py --full --config cfg4 --kernel ring-quads --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 reservoir ring-quads" >> $O/pairs.txt
+timeout -k 10 300 python3 bench.py --full --config cfg4 --steps 24 --warmup 4 --no-cpu-baseline --no-unprimed 2>/dev/null | line "cfg4 whole path (auto)" >> $O/pairs.txt
 cat $O/pairs.txt
 LSM_HIP_LIB=exp/variants/lib_pair_phases.so timeout -k 10 300 python3 exp/r03_ring_phases.py cfg4 1024 > $O/phases.txt 2>&1; tail -14 $O/phases.txt

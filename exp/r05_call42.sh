@@ -10,7 +10,7 @@ B="python3 $ROOT/bench.py"
 for P in "fetch FETCH_SIZE" "write WRITE_SIZE" "l2 TCC_HIT_sum TCC_MISS_sum"; do
   set -- $P; name=$1; shift
   D=$OUT/pmc_cfg1_B200_auto_$name
-  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $D -- $B --config cfg1 --batch 200 --kernel auto --stage reservoir --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-unprimed --prime-ms 0 > $D.json 2> $D.err && echo "pmc cfg1 $name done"
+  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $D -- $B --full --config cfg1 --batch 200 --kernel auto --stage reservoir --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-unprimed --prime-ms 0 > $D.json 2> $D.err && echo "pmc cfg1 $name done"
 done
 cd $ROOT
 python3 exp/r05_summarise.py $OUT > $OUT/summarise.log 2>&1 || { tail -20 $OUT/summarise.log; exit 1; }
@@ -23,7 +23,7 @@ print({k: v for k, v in old.items() if k.startswith("cfg1")})
 PY
 export LSM_TRAFFIC_FILE=$OUT/summary/lif_traffic.json
 cd /tmp
-$B --config cfg1 --steps 60 --warmup 8 > $OUT/summary/r05_cfg1.json 2> $OUT/cfg1.err && python3 -c "
+$B --full --config cfg1 --steps 60 --warmup 8 > $OUT/summary/r05_cfg1.json 2> $OUT/cfg1.err && python3 -c "
 import json
 p='$OUT/summary/r05_cfg1.json'
 d=json.loads([l for l in open(p) if l.startswith('{')][-1]); json.dump(d, open(p,'w'), indent=1); r=d['roofline']

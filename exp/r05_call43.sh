@@ -16,16 +16,16 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 for rep in 1 2; do
 for V in product prev; do
   if [ $V = product ]; then export LSM_HIP_LIB=; else export LSM_HIP_LIB=$GRAFT_REPO_ROOT/exp/variants/lib_$V.so; fi
-  timeout -k 10 300 python3 bench.py --config cfg2 --stage reservoir --streams 1 --steps 60 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_$V.txt | line "cfg2 reservoir $V" | tee -a $O/pack.txt
+  timeout -k 10 300 python3 bench.py --full --config cfg2 --stage reservoir --streams 1 --steps 60 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_$V.txt | line "cfg2 reservoir $V" | tee -a $O/pack.txt
 done
 done
 for rep in 1 2 3; do
 for V in product prev; do
   if [ $V = product ]; then export LSM_HIP_LIB=; else export LSM_HIP_LIB=$GRAFT_REPO_ROOT/exp/variants/lib_$V.so; fi
-  timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_d_$V.txt | line "cfg2 driver command $V" | tee -a $O/pack.txt
+  timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-unprimed 2>$O/err_d_$V.txt | line "cfg2 driver command $V" | tee -a $O/pack.txt
 done
 done
 for V in product prev; do
   if [ $V = product ]; then export LSM_HIP_LIB=; else export LSM_HIP_LIB=$GRAFT_REPO_ROOT/exp/variants/lib_$V.so; fi
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-unprimed 2>$O/err_l_$V.txt | line "cfg2 200 steps $V" | tee -a $O/pack.txt
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-unprimed 2>$O/err_l_$V.txt | line "cfg2 200 steps $V" | tee -a $O/pack.txt
 done

@@ -14,7 +14,7 @@ print('$1', '->', d['value'], 'clips/s', d['ms_per_step'], 'ms/step; lone', r.ge
 for rep in 1 2; do
   for V in product lsm_pair_dummy_salu_8 lsm_pair_dummy_valu_8 lsm_pair_dummy_lds_2 lsm_pair_dummy_vmem_2 lsm_pair_own_dump_1; do
     if [ $V = product ]; then L=""; else L=exp/variants/lib_$V.so; fi
-    LSM_HIP_LIB=$L timeout -k 10 300 python3 bench.py --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_$V.txt | line "cfg4 reservoir $V" >> $O/ports.txt
+    LSM_HIP_LIB=$L timeout -k 10 300 python3 bench.py --full --config cfg4 --stage reservoir --streams 1 --steps 12 --warmup 3 --no-cpu-baseline --no-unprimed 2>$O/err_$V.txt | line "cfg4 reservoir $V" >> $O/ports.txt
   done
 done
 cat $O/ports.txt

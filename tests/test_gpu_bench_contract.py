@@ -1,19 +1,20 @@
-"""bench.py's driver contract on the GPU box: one JSON line with the required keys, the roofline and
-cpu_baseline objects, and sane values (tiny K so the test stays short)."""
+"""bench.py's driver contract on the GPU box: one JSON line with the required keys and sane values, the roofline and
+cpu_baseline objects of --full, the outputs of --dump-outputs (tiny K so the test stays short)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", *extra],
-                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+def _run(*extra, full=True):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2",
+                          *(["--full"] if full else []), *extra], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -82,6 +83,25 @@ def test_bench_line_contract():
     assert d["value"] / c["value"] > 100           # north star: >= 100x the CPU reference at 1 GPU
 
 
+def test_plain_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the run does only what the headline needs: no unprimed pass, roofline or CPU baseline in the line.
+    --dump-outputs writes the feature rows of the last timed step; the inputs are seeded, so the serial path (one
+    stream) writes the same rows as the overlapped one."""
+    d = _run("--batch", "64", "--dump-outputs", str(tmp_path / "overlapped"), full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "clips/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    assert not {"unprimed", "roofline", "cpu_baseline"} & set(d)
+    assert "unprimed pass" not in d["config"]["prime"]
+    feats = np.load(tmp_path / "overlapped" / "features.npy")
+    assert feats.dtype == np.float32 and feats.shape == (64, 5 * 400) and np.isfinite(feats).all()
+    assert abs(feats[:, :400].sum(axis=1).mean() - d["config"]["mean_output_spikes_per_clip"]) < 1e-3
+    assert sorted(os.listdir(tmp_path / "overlapped")) == ["features.npy"]
+    _run("--batch", "64", "--streams", "1", "--dump-outputs", str(tmp_path / "serial"), full=False)
+    np.testing.assert_array_equal(np.load(tmp_path / "serial" / "features.npy"), feats)
+
+
 def test_bench_line_names_the_committed_traffic_file_at_the_headline_shape():
     d = _run("--no-cpu-baseline")                       # cfg2 at its own batch: the shape profiles/lif_traffic.json holds
     r = d["roofline"]
@@ -138,8 +158,8 @@ def test_a_rank_started_by_the_launcher_inherits_what_rccl_needs():
                                                             "WORLD_SIZE", "LOCAL_RANK")}
     env.update(LSM_BENCH_FORCE_SPAWN="1", LSM_BENCH_FORCE_DIST="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                          "--batch", "64", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT,
-                         env=env)
+                          "--batch", "64", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+                         cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -165,8 +185,8 @@ def test_chunked_exchange_over_two_gpus_equals_the_single_exchange():
     digests = {}
     for mode in ("once", "chunked"):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                              "--batch", "64", "--no-cpu-baseline", "--exchange", mode], capture_output=True, text=True,
-                             timeout=900, cwd=ROOT)
+                              "--batch", "64", "--full", "--no-cpu-baseline", "--exchange", mode], capture_output=True,
+                             text=True, timeout=900, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
         assert d["n_gpus"] == 2 and d["exchange"]["mode"] == mode

@@ -150,7 +150,7 @@ def _bench_two_ranks(exchange, *extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(LSM_BENCH_SHARE_GPU="1", LSM_BENCH_BACKEND="gloo")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-                        "--batch", "64", "--no-cpu-baseline", "--exchange", exchange, *extra], env=env,
+                        "--batch", "64", "--full", "--no-cpu-baseline", "--exchange", exchange, *extra], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -194,7 +194,8 @@ def test_bench_rccl_code_path_with_one_rank():
     env.pop("LSM_BENCH_BACKEND", None)
     env.pop("GPU_MAX_HW_QUEUES", None)        # this process's package import set 12; a fresh process under a launcher chooses
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                        "--no-cpu-baseline", "--exchange", "chunked"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--exchange", "chunked"], env=env, capture_output=True, text=True,
+                       timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["value"] > 1e4 and d["steps"] == 6
