@@ -77,9 +77,16 @@ int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_samples, const
  *               half a CU's LDS so that overlapping launches spread one workgroup per CU; beside a kernel whose
  *               workgroups need most of the LDS themselves (the ring-row reservoir kernel) the caller sets this bit and
  *               the launch asks for what it uses (27 KB per 4-wave workgroup at 4 thresholds x 100 bins).
- *               Results do not depend on the flags.  0 = the throughput layout with the reservation.
+ *               Results do not depend on the flags.  0 = the throughput layout with the reservation.  Where the
+ *               lane pair applies (lsm_gammatone_spikes_layout() == 0) bit 0 changes nothing and no LDS is reserved.
  * Returns LSM_ERR_UNSUPPORTED for more than 1024 filters (use the two split entry points). */
 long lsm_gammatone_spikes_workspace(int n_clips, int n_filters, int ncols);
+/* The layout lsm_gammatone_spikes_f64 launches for n_clips x n_filters with these launch_flags on the current device and
+ * this process's hardware queues (GPU_MAX_HW_QUEUES, 4 where unset): 0 = lane pair (32 channels per wave, filter
+ * sections 1-2 and 3-4 on the two halves of a wave; 2..256 filters with at most 4 queues, unless the batch fills every
+ * SIMD without it), 1 / 2 = one / two 64-channel groups per lane.  LSM_ERR_ARG for a bad shape, LSM_ERR_UNSUPPORTED where
+ * lsm_gammatone_spikes_f64 refuses.  Informational: results do not depend on the layout. */
+int lsm_gammatone_spikes_layout(int n_clips, int n_filters, int launch_flags);
 int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samples, const double *coefs_dev,
                              int n_filters, int nwin, int hop, int ncols, int time_bins,
                              const double *thr_on, const double *thr_off, int n_thr, int redundancy,

@@ -22,6 +22,7 @@ _SIGS = {
     "lsm_gammatone_spec_f64": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_int,
                                        c_void, c_void, c_int, c_void]),
     "lsm_gammatone_spikes_workspace": (C.c_long, [c_int, c_int, c_int]),
+    "lsm_gammatone_spikes_layout": (c_int, [c_int, c_int, c_int]),
     "lsm_gammatone_spikes_f64": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_int, c_int,
                                          c_void, c_void, c_int, c_int, c_void, c_void, C.c_long, c_int, c_int, c_void]),
     "lsm_spec_to_spikes_f64": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void,

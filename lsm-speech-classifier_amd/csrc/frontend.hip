@@ -10,6 +10,7 @@
 #include "lsm_common.h"
 #include "spikes_body.h"
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <type_traits>
 
@@ -182,11 +183,20 @@ __global__ __launch_bounds__(LSM_SPK_THREADS) void spec_to_spikes_kernel(const S
 //     order of spec_to_spikes_kernel<double>; the raster rows of a wave are staged bit-packed in LDS and
 //     leave as coalesced 4-byte stores.
 // Waves beyond the batch (last workgroup) skip the filter loop but keep the barriers.
+//
+// PAIR (lane-pair layout, NCH = 1): a wave carries 32 channels of its clip, channel j in lanes j (head) and j + 32
+// (tail), so at 128 filters a clip is 4 waves and a 256-clip launch puts a wave on every SIMD.  In the iteration of
+// sample n the head runs sections 1-2 on sample n + 1 and the tail sections 3-4 on sample n, fed with the head's
+// section-2 output of sample n, which v_permlane32_swap moves from lane j to lane j + 32 at the top of the iteration.
+// Both halves run the same two-section code with their own section coefficients and state.  The division, the
+// square and the window sums run on both halves (one instruction stream) but only the tail's feed the dB columns,
+// the max/min and the epilogue.  Every float64 operation of a channel and its order are those of the other layouts:
+// the skew only changes when section 3 sees a value, and the hand-off moves bits.
 // ---------------------------------------------------------------------------------------------
 struct FusedArgs {
     const float *audio;
     const double *coefs;
-    double *ws;                 // (n_clips, ncols, groups*NCH*64) float64 scratch
+    double *ws;                 // (n_clips, ncols, groups*NCH*64) float64 scratch (32 channels per group in the lane pair)
     uint8_t *raster;            // (n_clips, n_filters*redundancy, time_bins*n_thr)
     int n_clips, n_samples, n_filters, nwin, hop, ncols;
     int time_bins, n_thr, redundancy, groups;
@@ -195,12 +205,32 @@ struct FusedArgs {
     double on[MAX_THR], off[MAX_THR];
 };
 
+// Head lanes (0-31) keep `lo`, tail lanes (32-63) receive v of lane - 32: v_permlane32_swap exchanges lanes 32-63 of
+// its first operand with lanes 0-31 of its second; one swap per 32-bit half.
+__device__ __forceinline__ double pair_up(double lo, double v)
+{
+    const unsigned long long a = (unsigned long long)__double_as_longlong(lo);
+    const unsigned long long c = (unsigned long long)__double_as_longlong(v);
+    const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)c, false, false);
+    const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)(a >> 32), (unsigned)(c >> 32), false, false);
+    return __longlong_as_double((long long)(((unsigned long long)rh[0] << 32) | rl[0]));
+}
+
+__device__ __forceinline__ double uniform_f64(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // SHB0: every channel has the same first-section gain b0 = A0/B0 (the host verified it, coef_flags bit 2: this filter
 // design has A0 = 1/fs and B0 = 1 everywhere), so the product b0*x of a sample is formed once per lane and feeds both
 // chains: 70 instead of 71 instructions per sample and lane.
-template <int NW, bool FAST, int NCH, bool SHB0 = false>
+template <int NW, bool FAST, int NCH, bool SHB0 = false, bool PAIR = false>
 __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const FusedArgs a)
 {
+    static_assert(!PAIR || NCH == 1, "the lane pair carries one chain per lane pair");
+    constexpr int CPW = PAIR ? 32 : 64;                                   // channels of a chain group (of a wave)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *xch = reinterpret_cast<double *>(smem);                       // 2 * GT_MAX_WPB doubles
     uint32_t *stage_all = reinterpret_cast<uint32_t *>(smem + 2 * GT_MAX_WPB * sizeof(double));
@@ -214,13 +244,15 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     const int b = valid ? b_raw : a.n_clips - 1;
     const int g = wid - b_raw * groups;
     const int F = a.n_filters, nwin = a.nwin, hop = a.hop, ncols = a.ncols, n_samples = a.n_samples;
-    const int NG = groups * NCH;                                          // 64-channel groups per clip (padded)
+    const int NG = groups * NCH;                                          // chain groups per clip (padded)
+    const int cl = PAIR ? (lane & 31) : lane;                             // this lane's channel within its group
+    const bool owner = !PAIR || lane >= 32;                               // the lane whose output is the channel's
 
     bool live[NCH];
     double b0[NCH], b11[NCH], b12[NCH], b13[NCH], b14[NCH], b2[NCH], a1[NCH], a2[NCH], gain[NCH], rgain[NCH];
 #pragma unroll
     for (int q = 0; q < NCH; ++q) {
-        const int chl = (g * NCH + q) * 64 + lane;
+        const int chl = (g * NCH + q) * CPW + cl;
         live[q] = chl < F;
         const double *k = a.coefs + (size_t)(live[q] ? chl : F - 1) * 10;
         const double a0 = k[6];
@@ -243,6 +275,29 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         mx[q] = -INFINITY; mn[q] = INFINITY;
     }
 
+    // PAIR: this half's section coefficients (head: sections 1-2, tail: 3-4) and its last section-2 output.  With SHB0
+    // the one b0 of the table is channel 0's, read once per wave (scalar registers).
+    const double bp1 = owner ? b13[0] : b11[0], bp2 = owner ? b14[0] : b12[0];
+    const double b0p = SHB0 ? uniform_f64(a.coefs[0] / a.coefs[6]) : b0[0];
+    double u2 = 0.0;
+    auto pfilt = [&](double x0) __attribute__((always_inline)) -> double {
+        const double u = pair_up(x0, u2);               // head: the next sample; tail: the head's y2 of its sample
+        const double y1 = z01[0] + b0p * u;
+        z01[0] = (z11[0] + u * bp1) - y1 * a1[0];
+        z11[0] = FAST ? -(y1 * a2[0]) : u * b2[0] - y1 * a2[0];
+        const double y2 = z02[0] + b0p * y1;
+        z02[0] = (z12[0] + y1 * bp2) - y2 * a1[0];
+        z12[0] = FAST ? -(y2 * a2[0]) : y1 * b2[0] - y2 * a2[0];
+        u2 = y2;
+        double o;
+        if (FAST) {
+            const double q0 = y2 * rgain[0];
+            o = __builtin_fma(__builtin_fma(-q0, gain[0], y2), rgain[0], q0);
+        } else {
+            o = y2 / gain[0];
+        }
+        return o * o;
+    };
     auto filt = [&](int q, double x0, double bx) __attribute__((always_inline)) -> double {
         const double y1 = z01[q] + (SHB0 ? bx : b0[q] * x0);
         z01[q] = (z11[q] + x0 * b11[q]) - y1 * a1[q];
@@ -294,8 +349,32 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         }                                                                           \
     }
 
-    // scratch of this wave: column c, chain q at wsw[(c * NG + q) * 64]
-    double *wsw = a.ws + ((size_t)b * ncols * NG + (size_t)g * NCH) * 64 + lane;
+    // PAIR: the tail processes sample n while the head takes x[n + 1] (clamped inside the clip: the head's output of
+    // the sample past the last one is never used); full chunks stop where x[n + 8] would leave the clip
+#define LSM_RUNP(n_to, NACT)                                                        \
+    {                                                                               \
+        const int n_blk = min((n_to), n_samples - 1);                               \
+        if (n + 8 <= n_blk) {                                                       \
+            float xs[8], nx[8];                                                     \
+            _Pragma("unroll") for (int u = 0; u < 8; ++u) xs[u] = x[n + 1 + u];     \
+            for (; n + 8 <= n_blk; n += 8) {                                        \
+                const float *pn = x + 1 + min(n + 8, n_samples - 9);                \
+                _Pragma("unroll") for (int u = 0; u < 8; ++u) nx[u] = pn[u];        \
+                _Pragma("unroll") for (int u = 0; u < 8; ++u) {                     \
+                    const double e = pfilt((double)xs[u]);                          \
+                    _Pragma("unroll") for (int w = 0; w < (NACT); ++w) win[0][w] += e; \
+                }                                                                   \
+                _Pragma("unroll") for (int u = 0; u < 8; ++u) xs[u] = nx[u];        \
+            }                                                                       \
+        }                                                                           \
+        for (; n < (n_to); ++n) {                                                   \
+            const double e = pfilt((double)x[min(n + 1, n_samples - 1)]);           \
+            _Pragma("unroll") for (int w = 0; w < (NACT); ++w) win[0][w] += e;      \
+        }                                                                           \
+    }
+
+    // scratch of this wave: column c, chain q at wsw[(c * NG + q) * CPW]
+    double *wsw = a.ws + ((size_t)b * ncols * NG + (size_t)g * NCH) * CPW + cl;
     // The filter loop is the throughput-critical stream of the pipeline: a wave alone on its SIMD issues a float64
     // operation every 5.0 cycles, which leaves the reservoir waves sharing the SIMD one issue slot in five -- about
     // what they need.  At the default priority the reservoir kernel's raised-priority phases (lif_dense.h) take
@@ -307,19 +386,25 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         const int pos = nwin - (NW - 1) * hop;
         const int n_end = (ncols - 1) * hop + nwin;
         const double dn = (double)nwin;
+        if (PAIR) {
+            // the head's sample 0; the tail ran on a zero input, and its state restarts at +0 (all it held were
+            // signed zeros)
+            (void)pfilt((double)x[0]);
+            if (owner) z01[0] = z11[0] = z02[0] = z12[0] = 0.0;
+        }
         int n = 0;
         for (int h = 0; n < n_end; ++h) {
             const int base = h * hop;
             const int mid = min(base + pos, n_end);
-            LSM_RUNF(mid, NW)
+            if (PAIR) LSM_RUNP(mid, NW) else LSM_RUNF(mid, NW)
             const int c = h - (NW - 1);
             if (n == base + pos && c >= 0 && c < ncols) {
 #pragma unroll
                 for (int q = 0; q < NCH; ++q) {
                     const double y = sqrt(win[q][NW - 1] / dn);
                     const double v = 20 * log10(y + 1e-9);
-                    wsw[((size_t)c * NG + q) * 64] = v;
-                    if (live[q]) {
+                    if (owner) wsw[((size_t)c * NG + q) * CPW] = v;
+                    if (live[q] && owner) {
                         mx[q] = v > mx[q] ? v : mx[q];
                         mn[q] = v < mn[q] ? v : mn[q];
                         nan_seen |= v != v;
@@ -327,7 +412,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
                 }
             }
             const int stop = min(base + hop, n_end);
-            LSM_RUNF(stop, NW - 1)
+            if (PAIR) LSM_RUNP(stop, NW - 1) else LSM_RUNF(stop, NW - 1)
 #pragma unroll
             for (int q = 0; q < NCH; ++q) {
 #pragma unroll
@@ -337,6 +422,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         }
     }
 #undef LSM_RUNF
+#undef LSM_RUNP
 
     __builtin_amdgcn_s_setprio(0);
 #if LSM_EXPERIMENT_HOOKS
@@ -401,8 +487,8 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     const int JPW = 16 / FBH;                           // bins per 32-bit word (4 or 2)
     const int NG4 = (Tb + JPW - 1) / JPW;               // groups of JPW bins
     const int RW = (row_bits + 31) >> 5;                // words per staged raster row
-    uint32_t *stage = stage_all + (size_t)wave * (NCH * 64) * RW;
-    const size_t cs = (size_t)NG * 64;                  // doubles between two columns of the scratch
+    uint32_t *stage = stage_all + (size_t)wave * (NCH * CPW) * RW;
+    const size_t cs = (size_t)NG * CPW;                 // doubles between two columns of the scratch
     // straight-line variants (fast division or not, <= 4 thresholds or not, resize or not): one uniform choice
     // per wave instead of uniform branches inside the loop, which would keep the compiler from batching the loads
     auto pass_a = [&](auto fast_c, auto nt_c, auto zoom_c) __attribute__((always_inline)) {
@@ -445,7 +531,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
                 const int f1 = two[u] ? f + 1 : f;
 #pragma unroll
                 for (int q = 0; q < NCH; ++q) {
-                    const double *col = wsw + (size_t)q * 64;
+                    const double *col = wsw + (size_t)q * CPW;
                     x0[u][q] = col[(size_t)f * cs];
                     if (ZOOM) x1[u][q] = col[(size_t)f1 * cs];
                 }
@@ -491,7 +577,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
                     if (fill >= 32) {
 #pragma unroll
                         for (int q = 0; q < NCH; ++q) {
-                            stage[(q * 64 + lane) * RW + wout] = (uint32_t)acc[q];
+                            if (owner) stage[(q * CPW + cl) * RW + wout] = (uint32_t)acc[q];
                             acc[q] >>= 32;
                         }
                         ++wout;
@@ -502,7 +588,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         }
         if (fill > 0) {
 #pragma unroll
-            for (int q = 0; q < NCH; ++q) stage[(q * 64 + lane) * RW + wout] = (uint32_t)acc[q];
+            for (int q = 0; q < NCH; ++q) if (owner) stage[(q * CPW + cl) * RW + wout] = (uint32_t)acc[q];
         }
     };
     {
@@ -523,8 +609,8 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     if (valid) {
         // create_pure_redundancy: output row c reads filter row c / redundancy
         const int R = a.redundancy;
-        const int fbase = g * NCH * 64;
-        const int rows_out = min(NCH * 64, F - fbase) * R;
+        const int fbase = g * NCH * CPW;
+        const int rows_out = min(NCH * CPW, F - fbase) * R;
         const int row_bytes = row_bits;
         uint8_t *dst = a.raster + ((size_t)b * F + fbase) * R * row_bytes;
         if ((row_bytes & 3) == 0) {
@@ -767,36 +853,75 @@ LSM_API int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_sample
 
 constexpr int GTF_DEFAULT_PRIO = 0;
 
-// Layout of the fused launch for `n_filters`: chains per lane, waves per clip, waves per workgroup.
-struct FusedPlan { int nch, groups, wpb; };
-static bool fused_plan(int n_filters, int launch_flags, FusedPlan *p)
+// Layout of the fused launch for `n_filters` x `n_clips`: chains per lane, lane pair or not, waves per clip, waves per
+// workgroup.
+struct FusedPlan { int nch, groups, wpb; bool pair; };
+
+// Hardware queues HIP gives this process: GPU_MAX_HW_QUEUES, or the runtime's default of 4 where it is unset (the package
+// sets 12 before HIP starts unless the user chose a value).  Read at every plan, like the variable itself a per-process
+// setting.
+static int hw_queues()
 {
-    // two chains per lane above 64 filters (fewest CU-cycles per clip), unless the caller asks for the low-latency
-    // layout: one chain per lane = twice the waves, each half as long (1.47 against 2.43 ms for 256 clips x 128
-    // filters on an idle GPU, for 12 % more CU time)
+    const char *e = getenv("GPU_MAX_HW_QUEUES");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : 4;
+}
+
+static bool fused_plan(int n_filters, int n_clips, int launch_flags, FusedPlan *p)
+{
+    // The lane pair for 2..256 filters, whatever the low-latency flag says, where queues are scarce: at 128 filters a clip
+    // is 4 waves of 0.4 times the two-chain wave's time, so one 256-clip launch covers all 1024 SIMDs and the pipeline
+    // needs no five launches in flight.  Its cost: 25 issue slots per 32 channel-samples (22 float64, 2 swaps, 1 move),
+    // i.e. 100 per 128 against the two-chain layout's 70 (+43 %).  So
+    //   * with more than 4 hardware queues the two-chain launches overlap enough to fill the chip and win (cfg2, 12 queues,
+    //     medians of 5: profiles/r06_lane_pair_ab.txt); values between 5 and 11 are not measured;
+    //   * a launch that the two-chain layout alone spreads over every SIMD (n_clips x groups >= 4 x CUs: cfg4's 1024
+    //     clips) keeps the layouts below.
+    const DevInfo di = dev_info();
+    bool pair = n_filters <= 32 * GT_MAX_WPB && hw_queues() <= 4 &&
+                (di.cus <= 0 || (long)n_clips * ((n_filters + 127) / 128) < 4L * di.cus);
+    // otherwise two chains per lane above 64 filters (fewest CU-cycles per clip), unless the caller asks for the
+    // low-latency layout: one chain per lane = twice the waves, each half as long (1.47 against 2.43 ms for 256 clips x
+    // 128 filters on an idle GPU, for 12 % more CU time)
     int nch = (n_filters > 64 && !(launch_flags & 1)) ? 2 : 1;       // (bit 1 of the flags concerns the LDS reservation only)
 #if LSM_EXPERIMENT_HOOKS
+    // A/B runs on one library: LSM_GTF_NCH=1 / 2 forces the one- / two-chain layout; LSM_GTF_PAIR=0 never takes the lane
+    // pair (the layouts as before it existed), =1 takes it wherever it applies (<= 256 filters), whatever the queues
     static const int nch_env = [] { const char *e = getenv("LSM_GTF_NCH"); return e ? atoi(e) : 0; }();
-    if (nch_env == 1 || nch_env == 2) nch = nch_env;
+    static const int pair_env = [] { const char *e = getenv("LSM_GTF_PAIR"); return e ? atoi(e) : -1; }();
+    if (pair_env == 0) pair = false;
+    if (pair_env == 1) pair = n_filters <= 32 * GT_MAX_WPB;
+    if (nch_env == 1 || nch_env == 2) { nch = nch_env; pair = false; }
 #endif
+    if (pair) nch = 1;
     // the low-latency flag is a layout hint, never a reason to refuse: 513..1024 filters need more than GT_MAX_WPB
     // one-chain waves per clip, so they keep the two-chain layout whatever the flag says
     if (nch == 1 && (n_filters + 63) / 64 > GT_MAX_WPB) nch = 2;
-    const int groups = (n_filters + 64 * nch - 1) / (64 * nch);
+    const int cpw = pair ? 32 : 64;                              // channels per chain group
+    const int groups = (n_filters + cpw * nch - 1) / (cpw * nch);
     if (groups > GT_MAX_WPB) return false;
     int wpb = groups >= 4 ? groups : groups * (4 / groups);     // a multiple of `groups`, about 4 waves
 #if LSM_EXPERIMENT_HOOKS
     static const int wpb_env = [] { const char *e = getenv("LSM_GTF_WPB"); return e ? atoi(e) : 0; }();
     if (wpb_env >= 1 && wpb_env <= GT_MAX_WPB && wpb_env % groups == 0) wpb = wpb_env;
 #endif
-    p->nch = nch; p->groups = groups; p->wpb = wpb;
+    p->nch = nch; p->groups = groups; p->wpb = wpb; p->pair = pair;
     return true;
+}
+
+LSM_API int lsm_gammatone_spikes_layout(int n_clips, int n_filters, int launch_flags)
+{
+    FusedPlan pl;
+    if (n_clips < 1 || n_filters < 1) return LSM_ERR_ARG;
+    if (!fused_plan(n_filters, n_clips, launch_flags, &pl)) return LSM_ERR_UNSUPPORTED;
+    return pl.pair ? 0 : pl.nch;
 }
 
 LSM_API long lsm_gammatone_spikes_workspace(int n_clips, int n_filters, int ncols)
 {
     if (n_clips < 0 || n_filters < 1 || ncols < 1) return 0;
-    // 64-channel groups padded to an even number: covers both the one- and the two-chain layout
+    // 64-channel groups padded to an even number: covers the one- and the two-chain layout and the lane pair (32-channel
+    // groups)
     return (long)n_clips * ncols * (((n_filters + 127) / 128) * 2) * 64 * (long)sizeof(double);
 }
 
@@ -829,7 +954,7 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     LSM_REQUIRE((row_bytes & 3) != 0 || ((uintptr_t)raster & 3u) == 0,
                 "the raster must be 4-byte aligned when a row is a multiple of 4 bytes");
     FusedPlan pl;
-    if (!fused_plan(n_filters, launch_flags, &pl)) {
+    if (!fused_plan(n_filters, n_clips, launch_flags, &pl)) {
         lsm_set_error("gammatone_spikes: %d filters need more than %d waves per clip; use the split entry points",
                       n_filters, GT_MAX_WPB);
         return LSM_ERR_UNSUPPORTED;
@@ -854,7 +979,7 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     // per lane row: the comparison fields of pass A (4 bins per word up to 4 thresholds, else 2), reused for the raster bits
     // per lane row: the raster bits of the channel (time_bins * n_thr bits), staged for the coalesced write-out
     const int RW = (time_bins * n_thr + 31) / 32;
-    long lds = 2 * GT_MAX_WPB * (long)sizeof(double) + (long)pl.wpb * pl.nch * 64 * RW * 4;
+    long lds = 2 * GT_MAX_WPB * (long)sizeof(double) + (long)pl.wpb * pl.nch * (pl.pair ? 32 : 64) * RW * 4;
     LSM_REQUIRE(lds <= 160 * 1024, "raster stage of %ld bytes exceeds one CU's LDS", lds);
     // CU-exclusive placement of small launches, as in lsm_gammatone_spec_f64
     {
@@ -867,26 +992,35 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
         // launch_flags bit 1: the caller runs LDS-hungry workgroups of another kernel beside this launch (the ring-row
         // reservoir kernel: 64-74 KB per clip, two per CU) -- no reservation then: the launch asks for what it uses
         // (27 KB per 4-wave workgroup at 4 thresholds x 100 bins) and fits beside such a pair
-        if (!(launch_flags & 2) && di.cus > 0 && n_wgs <= di.cus && di.lds_per_cu >= 4096 && resv > lds && resv <= di.lds_per_cu)
+        // The lane pair takes none: its launch already has a wave on every SIMD, and the reservation would only keep the
+        // next step's launch off the CUs until this one has left (cfg2, 4 hardware queues, medians of 3 runs: 1.10 -> 1.00
+        // ms/step at 20 steps, 1.11 -> 0.98 at 200; 12 queues, one run each: 1.03 -> 1.00 and 0.98 -> 0.86;
+        // profiles/r06_lane_pair_placement.txt)
+        if (!pl.pair && !(launch_flags & 2) && di.cus > 0 && n_wgs <= di.cus && di.lds_per_cu >= 4096 && resv > lds &&
+            resv <= di.lds_per_cu)
             lds = resv;
     }
     const dim3 grid((unsigned)n_wgs), block((unsigned)(64 * pl.wpb));
     const bool fast = (coef_flags & 3) == 3;
-    const bool shb0 = fast && (coef_flags & 4) != 0;       // one b0 for every channel: shared between the two chains
+    const bool shb0 = fast && (coef_flags & 4) != 0;       // one b0 for every channel: shared between the two chains,
+                                                           // wave-uniform in the lane pair
     const int nw = (nwin + hop - 1) / hop;
-#define LSM_GTF2(NW, FAST, NCH, SHB0)                                                         \
+#define LSM_GTF2(NW, FAST, NCH, SHB0, PAIR)                                                   \
     {                                                                                         \
-        auto fn = gammatone_spikes_kernel<NW, FAST, NCH, SHB0>;                               \
+        auto fn = gammatone_spikes_kernel<NW, FAST, NCH, SHB0, PAIR>;                         \
         if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));           \
         hipLaunchKernelGGL(fn, grid, block, (size_t)lds, (hipStream_t)stream, a);             \
     }
 #define LSM_GTF(NW)                                                                           \
     {                                                                                         \
         if (fast) {                                                                           \
-            if (pl.nch == 2) { if (shb0) LSM_GTF2(NW, true, 2, true) else LSM_GTF2(NW, true, 2, false) } \
-            else LSM_GTF2(NW, true, 1, false)                                                 \
+            if (pl.pair) { if (shb0) LSM_GTF2(NW, true, 1, true, true) else LSM_GTF2(NW, true, 1, false, true) } \
+            else if (pl.nch == 2) { if (shb0) LSM_GTF2(NW, true, 2, true, false) else LSM_GTF2(NW, true, 2, false, false) } \
+            else LSM_GTF2(NW, true, 1, false, false)                                          \
         } else {                                                                              \
-            if (pl.nch == 2) LSM_GTF2(NW, false, 2, false) else LSM_GTF2(NW, false, 1, false) \
+            if (pl.pair) LSM_GTF2(NW, false, 1, false, true)                                  \
+            else if (pl.nch == 2) LSM_GTF2(NW, false, 2, false, false)                        \
+            else LSM_GTF2(NW, false, 1, false, false)                                         \
         }                                                                                     \
     }
     switch (nw) {
