@@ -181,8 +181,10 @@ int lsm_reservoir_destroy(lsm_reservoir *h);
  * (for a reservoir that mode 0 serves with ring rows the dense table is built by THIS call: it allocates and
  * synchronises, once),
  * 3 = ring rows (refused when the reservoir is not ring-like or has fewer than ~700 neurons), 4 = ring rows
- * restricted to the layouts with contiguous quad ownership (tests; 3 prefers the strided ones).  All produce
- * bit-identical results (SPEC.md §3).  num_neurons <= 8192. */
+ * restricted to the layouts with contiguous quad ownership (tests; 3 prefers the strided ones), 5 = ring rows in pair
+ * blocks only (128-neuron blocks, two neurons per lane; refused when the reservoir has no pair-block layout: more than
+ * 128 channels, or no block count and window that fit 4, 8 or 16 waves), 6 = ring rows in quads only (never pair
+ * blocks).  All produce bit-identical results (SPEC.md §3).  num_neurons <= 8192. */
 int lsm_reservoir_set_kernel(lsm_reservoir *h, int mode);
 
 /* The kernel lsm_reservoir_run would launch for this handle now: 1 sparse, 2 dense rows, 3 ring rows -- for the
@@ -263,10 +265,6 @@ int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, i
 int lsm_debug_pair_layout(int num_neurons, const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w, int wpc,
                           unsigned long long band_addr, unsigned long long rem_addr, long *band_floats, long *n_list_entries,
                           int *pitch_bytes, float *band_out, uint32_t *rem_out, uint32_t *rec_out);
-
-/* Diagnostic builds (-DLSM_STAMP=1) only: per-phase s_memtime sums of the reservoir kernel
- * (out8: 8 counters, HOST memory); all zeros in the shipped build. */
-int lsm_debug_lif_stamps(unsigned long long *out8, int reset);
 
 #ifdef __cplusplus
 }

@@ -58,7 +58,6 @@ _SIGS = {
     "lsm_reservoir_input_mode": (c_int, [c_void, c_int, c_int, c_int]),
     "lsm_debug_pair_layout": (c_int, [c_int, c_void, c_void, c_void, c_int, C.c_ulonglong, C.c_ulonglong,
                                       C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(c_int), c_void, c_void, c_void]),
-    "lsm_debug_lif_stamps": (c_int, [c_void, c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

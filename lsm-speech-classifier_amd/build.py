@@ -18,10 +18,13 @@ LIB_NAME = "liblsm_hip.so"
 # -ffp-contract=off: the kernels must round every float operation exactly like the CPU oracle.
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
           "-std=c++17"]
+# The only switch a build may set: the pair kernel's phase clock (lif_pair.h; its output replaces the features, so such a
+# build is never the in-tree library).
+ALLOWED_DEFINES = {"LSM_PAIR_PHASES"}
 
 
 def lib_path() -> str:
-    # LSM_HIP_LIB: load another build of the same library (diagnostic/ablation builds)
+    # LSM_HIP_LIB: load another build of the same library (a diagnostic build, written outside the package)
     return os.environ.get("LSM_HIP_LIB") or os.path.join(PKG_DIR, LIB_NAME)
 
 
@@ -74,8 +77,25 @@ def needs_build(out: str | None = None) -> bool:
     return built_id(out) != source_id()
 
 
+def _check_defines(defines, out: str | None) -> None:
+    """A diagnostic build names only ALLOWED_DEFINES and goes to a library outside the package directory: the in-tree
+    library is always a product build, so its build id (the hash of the sources) says what it computes."""
+    for d in defines:
+        name = d.split("=", 1)[0]
+        if name not in ALLOWED_DEFINES:
+            raise ValueError(f"-D{d}: not a switch of these sources (allowed: {sorted(ALLOWED_DEFINES)})")
+    if defines:
+        if out is None:
+            raise ValueError(f"-D{' -D'.join(defines)}: a diagnostic build needs an output path outside {PKG_DIR}")
+        if os.path.commonpath([os.path.realpath(out), os.path.realpath(PKG_DIR)]) == os.path.realpath(PKG_DIR):
+            raise ValueError(f"{out}: a diagnostic build must not be written inside {PKG_DIR}")
+
+
 def build(force: bool = False, verbose: bool = False, defines=(), out: str | None = None) -> str:
-    """Compile every translation unit (in parallel) and link liblsm_hip.so in-tree."""
+    """Compile every translation unit (in parallel) and link liblsm_hip.so in-tree, or a diagnostic build (`defines`
+    from ALLOWED_DEFINES) to `out` outside the package."""
+    defines = list(defines)
+    _check_defines(defines, out)
     out = out or os.path.join(PKG_DIR, LIB_NAME)
     if not force and not needs_build(out):
         return out
@@ -94,7 +114,8 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str | Non
         return obj
 
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    jobs = int(os.environ.get("MAX_JOBS") or 16)
+    with ThreadPoolExecutor(max_workers=max(1, min(len(SOURCES), jobs))) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out + ".tmp"] + objs
     if verbose:

@@ -152,15 +152,13 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_kernel(
 using lsm_fe::MAX_THR;
 using lsm_fe::SpikeArgs;
 
-#ifndef LSM_SPK_THREADS
-#define LSM_SPK_THREADS 256     // threads of a spec_to_spikes_kernel workgroup (one clip).  Alone on the GPU sixteen waves are faster than
-                                // four (21.5 against 32.7 us per 200 clips: with one wave per SIMD every dependent instruction waits out
-                                // its latency), inside the overlapped pipeline the small workgroup is (cfg1: 1.26-1.29 M clips/s with 256
-                                // threads, 1.22-1.26 M with 512, 1.13-1.15 M with 1024, which must find a whole CU's wave slots free;
-                                // profiles/r05_mel_wave_per_frame.txt)
-#endif
+// Threads of a spec_to_spikes_kernel workgroup (one clip).  Alone on the GPU sixteen waves are faster than four (21.5 against
+// 32.7 us per 200 clips: with one wave per SIMD every dependent instruction waits out its latency), inside the overlapped
+// pipeline the small workgroup is (cfg1: 1.26-1.29 M clips/s with 256 threads, 1.22-1.26 M with 512, 1.13-1.15 M with 1024,
+// which must find a whole CU's wave slots free; profiles/r05_mel_wave_per_frame.txt)
+constexpr int SPK_THREADS = 256;
 template <typename T>
-__global__ __launch_bounds__(LSM_SPK_THREADS) void spec_to_spikes_kernel(const SpikeArgs<T> a)
+__global__ __launch_bounds__(SPK_THREADS) void spec_to_spikes_kernel(const SpikeArgs<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     lsm_fe::spec_to_spikes_body<T>(a, (int)blockIdx.x, smem);
@@ -200,8 +198,8 @@ struct FusedArgs {
     uint8_t *raster;            // (n_clips, n_filters*redundancy, time_bins*n_thr)
     int n_clips, n_samples, n_filters, nwin, hop, ncols;
     int time_bins, n_thr, redundancy, groups;
-    int skip_epilogue;          // diagnostic builds (LSM_EXPERIMENT_HOOKS) only: time the filter loop alone
-    int prio;                   // wave priority of the filter loop (s_setprio 0..3)
+    int unused_;                // (keeps the argument layout, and with it the filter loop's code, of the measured build)
+    int prio;                   // wave priority of the filter loop: 0 (see the kernel)
     double on[MAX_THR], off[MAX_THR];
 };
 
@@ -378,7 +376,9 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     // The filter loop is the throughput-critical stream of the pipeline: a wave alone on its SIMD issues a float64
     // operation every 5.0 cycles, which leaves the reservoir waves sharing the SIMD one issue slot in five -- about
     // what they need.  At the default priority the reservoir kernel's raised-priority phases (lif_dense.h) take
-    // slots from it instead.
+    // slots from it instead, so it runs at priority 0 (priorities 0-3: profiles/r03_priorities_and_stream_counts.txt).
+    // The untaken branches below stay: without them the compiler allocates the filter loop differently (fewer vector
+    // registers, e.g. 238 -> 168 in one layout) and the pipeline ran 4 % slower at cfg4, 3 % at cfg2.
     if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
     else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
     else if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
@@ -425,9 +425,6 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
 #undef LSM_RUNP
 
     __builtin_amdgcn_s_setprio(0);
-#if LSM_EXPERIMENT_HOOKS
-    if (a.skip_epilogue) return;
-#endif
     // ---- the clip's max / min -----------------------------------------------------------------
     double hi = mx[0], lo = mn[0];
 #pragma unroll
@@ -505,16 +502,13 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
             }
             return d / den;
         };
-#ifndef LSM_GTF_PASS_A_UNROLL
-#define LSM_GTF_PASS_A_UNROLL 1
-#endif
         uint32_t act[NCH];
         unsigned long long acc[NCH];
 #pragma unroll
         for (int q = 0; q < NCH; ++q) { act[q] = 0u; acc[q] = 0ull; }
         int fill = 0, wout = 0;                         // the same for every chain of the lane
         const uint32_t tmask_a = (1u << n_thr) - 1u;
-#pragma unroll LSM_GTF_PASS_A_UNROLL
+#pragma unroll 1
         for (int jw = 0; jw < NG4; ++jw) {
             double x0[G][NCH], x1[G][NCH], w0[G], w1[G];
             bool two[G];
@@ -681,7 +675,7 @@ int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, in
     LSM_REQUIRE(lds <= 160 * 1024, "latch bit rows of %zu bytes (time_bins x thresholds) exceed one CU's LDS", lds);
     auto fn = spec_to_spikes_kernel<T>;
     if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
-    hipLaunchKernelGGL(fn, dim3(n_clips), dim3(LSM_SPK_THREADS), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(fn, dim3(n_clips), dim3(SPK_THREADS), lds, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
@@ -792,21 +786,7 @@ LSM_API int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_sample
     LSM_REQUIRE((long)(ncols - 1) * hop + nwin <= n_samples, "columns exceed the clip");
     LSM_REQUIRE(n_samples >= 8, "clips shorter than 8 samples are not supported");
     const long n_waves = (long)((n_filters + 63) / 64) * n_clips;
-#if LSM_EXPERIMENT_HOOKS                                // diagnostic builds only (exp/wpb_sweep.sh, exp/resv_sweep.sh)
-    static const int wpb_env = [] {
-        const char *e = getenv("LSM_GT_WPB");
-        const int v = e ? atoi(e) : 0;
-        return v >= 1 && v <= GT_MAX_WPB ? v : 0;
-    }();
-    const int wpb = wpb_env ? wpb_env : 4;
-    static const int lds_env = [] {
-        const char *e = getenv("LSM_GT_LDS");
-        const int v = e ? atoi(e) : -1;
-        return v >= 0 && v <= 160 * 1024 ? v : -1;
-    }();
-#else
-    constexpr int wpb = 4, lds_env = -1;
-#endif
+    constexpr int wpb = 4;
     // CU-exclusive placement for small launches.  The kernel uses no LDS; the reservation (half of
     // a CU's LDS plus 1 KB) only caps the dispatcher at ONE gammatone workgroup per CU, so launches
     // that overlap on other streams spread over the free CUs instead of stacking their waves on the
@@ -821,7 +801,6 @@ LSM_API int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_sample
         if (di.cus > 0 && n_wgs <= di.cus && di.lds_per_cu >= 4096)
             lds = (int)(di.lds_per_cu / 2 + 1024);
     }
-    if (lds_env >= 0) lds = lds_env;
     LSM_REQUIRE((n_waves + wpb - 1) / wpb <= 0x7fffffffL, "too many clips for one launch");
     const dim3 grid((unsigned)((n_waves + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
     const bool fast = (coef_flags & 3) == 3;       // both properties verified by the host
@@ -850,8 +829,6 @@ LSM_API int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_sample
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
-
-constexpr int GTF_DEFAULT_PRIO = 0;
 
 // Layout of the fused launch for `n_filters` x `n_clips`: chains per lane, lane pair or not, waves per clip, waves per
 // workgroup.
@@ -884,15 +861,6 @@ static bool fused_plan(int n_filters, int n_clips, int launch_flags, FusedPlan *
     // low-latency layout: one chain per lane = twice the waves, each half as long (1.47 against 2.43 ms for 256 clips x
     // 128 filters on an idle GPU, for 12 % more CU time)
     int nch = (n_filters > 64 && !(launch_flags & 1)) ? 2 : 1;       // (bit 1 of the flags concerns the LDS reservation only)
-#if LSM_EXPERIMENT_HOOKS
-    // A/B runs on one library: LSM_GTF_NCH=1 / 2 forces the one- / two-chain layout; LSM_GTF_PAIR=0 never takes the lane
-    // pair (the layouts as before it existed), =1 takes it wherever it applies (<= 256 filters), whatever the queues
-    static const int nch_env = [] { const char *e = getenv("LSM_GTF_NCH"); return e ? atoi(e) : 0; }();
-    static const int pair_env = [] { const char *e = getenv("LSM_GTF_PAIR"); return e ? atoi(e) : -1; }();
-    if (pair_env == 0) pair = false;
-    if (pair_env == 1) pair = n_filters <= 32 * GT_MAX_WPB;
-    if (nch_env == 1 || nch_env == 2) { nch = nch_env; pair = false; }
-#endif
     if (pair) nch = 1;
     // the low-latency flag is a layout hint, never a reason to refuse: 513..1024 filters need more than GT_MAX_WPB
     // one-chain waves per clip, so they keep the two-chain layout whatever the flag says
@@ -900,11 +868,7 @@ static bool fused_plan(int n_filters, int n_clips, int launch_flags, FusedPlan *
     const int cpw = pair ? 32 : 64;                              // channels per chain group
     const int groups = (n_filters + cpw * nch - 1) / (cpw * nch);
     if (groups > GT_MAX_WPB) return false;
-    int wpb = groups >= 4 ? groups : groups * (4 / groups);     // a multiple of `groups`, about 4 waves
-#if LSM_EXPERIMENT_HOOKS
-    static const int wpb_env = [] { const char *e = getenv("LSM_GTF_WPB"); return e ? atoi(e) : 0; }();
-    if (wpb_env >= 1 && wpb_env <= GT_MAX_WPB && wpb_env % groups == 0) wpb = wpb_env;
-#endif
+    const int wpb = groups >= 4 ? groups : groups * (4 / groups);   // a multiple of `groups`, about 4 waves
     p->nch = nch; p->groups = groups; p->wpb = wpb; p->pair = pair;
     return true;
 }
@@ -963,14 +927,7 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     a.audio = audio; a.coefs = coefs; a.ws = static_cast<double *>(workspace); a.raster = raster;
     a.n_clips = n_clips; a.n_samples = n_samples; a.n_filters = n_filters; a.nwin = nwin; a.hop = hop;
     a.ncols = ncols; a.time_bins = time_bins; a.n_thr = n_thr; a.redundancy = redundancy; a.groups = pl.groups;
-    a.skip_epilogue = 0;
-    a.prio = GTF_DEFAULT_PRIO;
-#if LSM_EXPERIMENT_HOOKS
-    static const int prio_env = [] { const char *e = getenv("LSM_GTF_PRIO"); return e ? atoi(e) : -1; }();
-    if (prio_env >= 0 && prio_env <= 3) a.prio = prio_env;
-    static const int skip_env = [] { const char *e = getenv("LSM_GTF_SKIP_EPILOGUE"); return e ? atoi(e) : 0; }();
-    a.skip_epilogue = skip_env;
-#endif
+    a.prio = 0;
     // unused table entries never fire: nothing is > +inf or < -inf (the kernel compares 4 or 8 thresholds)
     for (int q = 0; q < MAX_THR; ++q) { a.on[q] = q < n_thr ? thr_on[q] : INFINITY; a.off[q] = q < n_thr ? thr_off[q] : -INFINITY; }
     const long n_waves = (long)pl.groups * n_clips;
@@ -984,11 +941,7 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     // CU-exclusive placement of small launches, as in lsm_gammatone_spec_f64
     {
         const DevInfo di = dev_info();
-        long resv = di.lds_per_cu / 2 + 1024;
-#if LSM_EXPERIMENT_HOOKS
-        static const long lds_env = [] { const char *e = getenv("LSM_GTF_LDS"); return e ? atol(e) : -1L; }();
-        if (lds_env >= 0) resv = lds_env;
-#endif
+        const long resv = di.lds_per_cu / 2 + 1024;
         // launch_flags bit 1: the caller runs LDS-hungry workgroups of another kernel beside this launch (the ring-row
         // reservoir kernel: 64-74 KB per clip, two per CU) -- no reservation then: the launch asks for what it uses
         // (27 KB per 4-wave workgroup at 4 thresholds x 100 bins) and fits beside such a pair

@@ -21,25 +21,12 @@
 #pragma once
 #include "lif_kernel.h"
 
-#ifndef LSM_ABLATE
-#define LSM_ABLATE 0        // diagnostic builds only (results are WRONG): 1 = no recurrent rows, 2 = no input
-#endif                      // drive, 4 = no step barrier, 8 = no feature updates, 16 = no loads (adds kept),
-                            // 32 = rows folded onto the first 256 (1 MB footprint), 64 = non-temporal raster reads
-
-// Row fetch, same-box A/B at 128 filters / 1000 neurons / 256 clips (profiles/r02_dense_row_chain_ab.txt):
-// LSM_DENSE_BUF=1 issues the row loads as MUBUF `buffer_load ... offen` with the row offset as scalar operand
-// (no per-row vector address add) - and the launch takes 0.60 ms instead of 0.53: with eight waves of a CU
-// issuing dword gathers, buffer loads run at 3/4 of the rate of global loads (exp/ubench_vmem.hip,
-// profiles/r02_ubench_global_vs_buffer_loads.txt).  Kept as a switch so that the measurement can be repeated.
-// LSM_DENSE_BITSET: clear the consumed list bit with one s_bitset0_b64 instead of the three-instruction
-// `todo &= todo - 1`; with the row offsets premultiplied once per 64 entries a row costs 9 instructions per
-// wave instead of 12 (0.532 -> 0.519 ms).
-#ifndef LSM_DENSE_BUF
-#define LSM_DENSE_BUF 0
-#endif
-#ifndef LSM_DENSE_BITSET
-#define LSM_DENSE_BITSET 1
-#endif
+// Row fetch, same-box A/B at 128 filters / 1000 neurons / 256 clips (profiles/r02_dense_row_chain_ab.txt): global loads.
+// MUBUF `buffer_load ... offen` with the row offset as scalar operand (no per-row vector address add) took 0.60 ms
+// instead of 0.53: with eight waves of a CU issuing dword gathers, buffer loads run at 3/4 of the rate of global loads
+// (exp/ubench_vmem.hip, profiles/r02_ubench_global_vs_buffer_loads.txt).  The consumed list bit is cleared with one
+// s_bitset0_b64 instead of the three-instruction `todo &= todo - 1`; with the row offsets premultiplied once per 64
+// entries a row costs 9 instructions per wave instead of 12 (0.532 -> 0.519 ms).
 namespace lsm_lif {
 
 struct DenseArgs {
@@ -72,17 +59,6 @@ struct DenseArgs {
 //      feeding one neuron differ in their position mod 32: the four masked words of a neuron are disjoint and ONE
 //      popcount of their union counts them -- 5 vector instructions per neuron and step instead of 9
 // (Ring-like reservoirs whose dense table no longer fits the caches run on lif_ring.h instead: window + list rows.)
-// LSM_DENSE_MAX_VGPR: register cap of the kernel (0 = the compiler's choice).  Inside the pipeline a reservoir wave
-// shares its SIMD with a front-end wave of 160-168 registers: at <= 112 registers THREE reservoir workgroups fit beside
-// it (168 + 3 x 112 <= 512), at the compiler's 113 (allocated in steps of 8: 120) only two.
-#ifndef LSM_DENSE_MAX_VGPR
-#define LSM_DENSE_MAX_VGPR 0
-#endif
-#if LSM_DENSE_MAX_VGPR
-#define LSM_DENSE_VGPR_ATTR __attribute__((amdgpu_waves_per_eu(512 / LSM_DENSE_MAX_VGPR)))
-#else
-#define LSM_DENSE_VGPR_ATTR
-#endif
 // REFM: the refractory countdown of the reference's period (REFRACTORY_PERIOD = 2, extract_lsm_features.py:13) lives in
 // SCALAR registers -- two 64-bit lane masks per slot, h2 = "fired at the last step" and h1 = "fired the step before" --
 // instead of one vector register per neuron.  The fire condition comes out of v_cmp as a lane mask, `held` = h1 | h2
@@ -93,7 +69,7 @@ struct DenseArgs {
 // vector-instruction issue, and scalar instructions issue beside it.  Other periods keep the vector
 // countdown (REFM = false).
 template <int SL, int WPC, int INMODE, bool REFM>
-__global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel(const DenseArgs a)
+__global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
 {
     constexpr bool INREG = INMODE == 1;
     constexpr bool INMASK = INMODE >= 2;
@@ -102,11 +78,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
     constexpr int NPAD = NPW * WPC;
     constexpr int NT = WPC * 64;
     constexpr int R = 64 / WPC;            // fixed-region list entries per producer wave
-#ifndef LSM_DENSE_G4
-#define LSM_DENSE_G4 8
-#endif
-    // rows in flight per group (<= 32 registers of weights; LSM_DENSE_G4: the SL = 4 value, see LSM_DENSE_MAX_VGPR's note)
-    constexpr int G = SL == 1 ? 16 : (SL == 4 ? LSM_DENSE_G4 : 32 / SL);
+    constexpr int G = SL == 1 ? 16 : 32 / SL;   // rows in flight per group (<= 32 registers of weights)
     constexpr bool FEATREG = SL <= 4;           // feature accumulators in registers (4 per neuron) instead of LDS
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -135,7 +107,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
             const uint32_t *clip4 = reinterpret_cast<const uint32_t *>(clip);
             const int nd = a.C * T / 4;
             for (int q = tid; q < nd; q += NT) {
-                const uint32_t v = (LSM_ABLATE & 64) ? __builtin_nontemporal_load(clip4 + q) : clip4[q];
+                const uint32_t v = clip4[q];
                 if (v == 0) continue;
                 const int c = (q * 4) / T;
                 const int t0 = (q * 4) - c * T;
@@ -195,10 +167,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
     const bool trace = a.spike_matrix != nullptr || a.v_trace != nullptr;
     // weight of presynaptic j onto my target r: byte offset j*ld*4 (scalar, 32 bits are enough:
     // N*ld*4 <= 2^28 for N <= 8192) + my lane's byte offset (vector) + r*256 (immediate)
-    // (a buffer load takes the row offset as its scalar operand: no per-row vector address arithmetic)
     const char *wt_bytes = reinterpret_cast<const char *>(a.wt);
-    const __amdgpu_buffer_rsrc_t wt_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(a.wt), 0, (int)((uint32_t)N * (uint32_t)a.ld * 4u), 0x00020000);
     const uint32_t ld_bytes = (uint32_t)a.ld * 4u;
     const uint32_t lane_off = (uint32_t)(w * NPW + lane) * 4u;
     uint4 fr[FEATREG ? SL : 1];        // FEATREG: {n | bursts << 16, first | last << 16, sum t, sum isi^2} per neuron
@@ -210,7 +179,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
 
     // input drive of step `ts`: count the active channels feeding each target (integer atomics)
     auto input_drive = [&](int ts) {
-        if (INMASK || (LSM_ABLATE & 2)) return;
+        if (INMASK) return;
         const uint32_t *row = bits + ts * CW;
         if (INREG) {
 #pragma unroll
@@ -232,20 +201,13 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
         }
     };
 
-#if LSM_STAMP                         // diagnostic builds only: per-phase s_memtime sums of wave 0 of each clip
-    unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-    const unsigned long long st_loop0 = st_last, st_real0 = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = 0; t < T; ++t) {
         // The step list read and the row fetch are the latency-critical part of a step: they issue at
         // raised priority so that waves of other kernels sharing the SIMD (the float64 filterbank in the
         // pipeline) do not delay the loads; the update below runs at normal priority in their stall slots.
         // Measured inside the pipeline: launch duration 1.31 -> 1.11 ms at unchanged throughput (raising
         // the priority for the whole step gives 0.67 ms but costs 4 % of the pipeline's throughput).
-#ifndef LSM_LIF_NO_PRIO                  // diagnostic builds: same-box A/B of the priority phases
         __builtin_amdgcn_s_setprio(1);
-#endif
         const int cur = t & 1, prv = cur ^ 1;
         const uint16_t *list_prev = wlist + prv * NPAD;
         uint16_t *list_cur = wlist + cur * NPAD + w * NPW;
@@ -254,7 +216,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
 #pragma unroll
         for (int r = 0; r < SL; ++r) cin[r] = 0.0f;
         uint32_t rowbits[4] = {0u, 0u, 0u, 0u};          // INMASK: this step's input bit row (wave-uniform)
-        if (INMASK && !(LSM_ABLATE & 2)) {
+        if (INMASK) {
             if (CW == 4) {
                 const uint4 q4 = *reinterpret_cast<const uint4 *>(bits + t * 4);
                 rowbits[0] = q4.x; rowbits[1] = q4.y; rowbits[2] = q4.z; rowbits[3] = q4.w;
@@ -268,10 +230,8 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
         // are in flight; nested "one more?" tests make a group cost one taken branch.
         bool drove = false;
         auto add_rows = [&](unsigned long long todo, uint32_t jl) {
-            if (LSM_ABLATE & 1) todo = 0ull;
-            if (LSM_ABLATE & 4) jl = min(jl, (uint32_t)(N - 1));
             // entry -> byte offset of its row, once per 64 entries (N*ld*4 <= 2^28 for N <= 8192)
-            const uint32_t jo = ((LSM_ABLATE & 32) ? (jl & 255u) : jl) * ld_bytes;
+            const uint32_t jo = jl * ld_bytes;
             while (todo != 0ull) {
                 const int n8 = min((int)__builtin_popcountll(todo), G);
                 float wv[16][SL];                   // only the first G rows are ever live
@@ -279,16 +239,9 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
     {                                                                               \
         const int sk = __builtin_ctzll(todo);                                       \
         const uint32_t j = __builtin_amdgcn_readlane(jo, sk);                       \
-        if (LSM_DENSE_BITSET) asm volatile("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(sk)); \
-        else todo &= todo - 1ull;                                                   \
-        {                                                                           \
-            const int so = (int)j;                                                  \
-            _Pragma("unroll") for (int r = 0; r < SL; ++r)                          \
-                wv[k][r] = (LSM_ABLATE & 16) ? __uint_as_float(j + r)               \
-                         : LSM_DENSE_BUF ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(    \
-                               wt_rsrc, (int)lane_off + r * 256, so, 0))            \
-                         : *reinterpret_cast<const float *>(wt_bytes + j + lane_off + r * 256); \
-        }                                                                           \
+        asm volatile("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(sk));               \
+        _Pragma("unroll") for (int r = 0; r < SL; ++r)                              \
+            wv[k][r] = *reinterpret_cast<const float *>(wt_bytes + j + lane_off + r * 256); \
     }
                 // the load chain tests the remaining-entries mask itself (one scalar 64-bit compare per row)
                 LSM_LD(0)
@@ -308,7 +261,6 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
                 if (G > 14 && todo) { LSM_LD(14)
                 if (G > 15 && todo) { LSM_LD(15) } } } } } } } } } } } } } } }
 #undef LSM_LD
-                STAMP(1);
                 if (!drove) {                     // the input counts fill the load latency
                     input_drive(t);
                     drove = true;
@@ -334,14 +286,12 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
                 if (n8 > 14) { LSM_ADD(14)
                 if (n8 > 15) { LSM_ADD(15) } } } } } } } } } } } } } } }
 #undef LSM_ADD
-                STAMP(2);
             }
         };
 
         // ---- spiking neurons of step t-1 ----
         const uint32_t pcnt = wcnt[prv * 16 + lane / R];            // spikes of producer wave lane/R
         const uint32_t jfix = flist[prv * 64 + lane];               // its (lane%R)-th spiking neuron
-        STAMP(0);
         // a producer with more than R spikes does not fit its fixed region: the counts themselves say so
         if (__ballot(pcnt > (uint32_t)R) == 0ull) {
             add_rows(__ballot((uint32_t)(lane % R) < pcnt), jfix);
@@ -370,9 +320,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
         if (!drove) input_drive(t);
         if (!INMASK) wave_lds_fence();
 
-#if !defined(LSM_LIF_NO_PRIO) && !defined(LSM_LIF_PRIO_WHOLE)   // (PRIO_WHOLE: diagnostic build, raised for the whole step)
         __builtin_amdgcn_s_setprio(0);
-#endif
         // ---- neuron update ----
         unsigned long long bal[SL];
         unsigned long long any_fire = 0ull;
@@ -416,7 +364,6 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
             }
             any_fire |= bal[r];
         }
-        STAMP(3);
         int nspk = 0;
         if (any_fire != 0ull) {                  // one branch per wave and step
 #pragma unroll
@@ -429,7 +376,7 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
                     list_cur[rank] = me;
                     if (rank < R) flist[cur * 64 + w * R + rank] = me;
                     hf |= 1u << r;
-                    if ((FEATREG || os[r] >= 0) && !(LSM_ABLATE & 8)) {
+                    if (FEATREG || os[r] >= 0) {
                         // FEATREG: the accumulators of EVERY neuron of the lane sit in registers (no LDS round
                         // trip in the fire path, which all other waves wait for at the barrier); they are parked
                         // in the LDS array once, after the last step
@@ -465,16 +412,8 @@ __global__ __launch_bounds__(WPC * 64) LSM_DENSE_VGPR_ATTR void lif_dense_kernel
                 }
             }
         }
-        STAMP(4);
-        if (!(LSM_ABLATE & 4)) __syncthreads();
-        STAMP(5);
+        __syncthreads();
     }
-#if LSM_STAMP
-    st_sum[6] = st_last - st_loop0;                                   // shader cycles in the step loop
-    st_sum[7] = __builtin_amdgcn_s_memrealtime() - st_real0;          // 100 MHz ticks in the step loop
-    if (tid == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_lif_stamps[k], st_sum[k]);
-#endif
 
     if (FEATREG) {
 #pragma unroll
@@ -567,9 +506,5 @@ dense_fn_t pick_dense_0(int sl, int wpc, bool refm);      // lif_dense_0.hip (IN
 dense_fn_t pick_dense_1(int sl, int wpc, bool refm);      // lif_dense_1.hip (INMODE 1: entries in registers)
 dense_fn_t pick_dense_2(int sl, int wpc, bool refm);      // lif_dense_2.hip (INMODE 2: channel masks, C <= 128, SL <= 4)
 dense_fn_t pick_dense_3(int sl, int wpc, bool refm);      // lif_dense_3.hip (INMODE 3: channel masks at coloured positions)
-#if LSM_STAMP
-int read_lif_stamps_d2(unsigned long long *o, int r);   // stamps of the INMODE-2 unit
-int read_lif_stamps_d3(unsigned long long *o, int r);   // stamps of the INMODE-3 unit (the cfg2 kernel)
-#endif
 
 }  // namespace lsm_lif

@@ -4,7 +4,4 @@
 
 namespace lsm_lif {
 dense_fn_t pick_dense_3(int sl, int wpc, bool refm) { return pick_dense_sl<3>(sl, wpc, refm); }
-#if LSM_STAMP
-LSM_DEFINE_STAMP_READER(read_lif_stamps_d3)
-#endif
 }  // namespace lsm_lif

@@ -38,24 +38,6 @@
 
 namespace lsm_lif {
 
-#ifndef LSM_STAMP
-#define LSM_STAMP 0         // diagnostic builds only: per-phase s_memtime sums (wave 0 of each clip)
-#endif
-#if LSM_STAMP
-namespace { __device__ unsigned long long g_lif_stamps[8]; }   // one copy per translation unit
-#define STAMP(k)                                                                             \
-    do {                                                                                     \
-        unsigned long long _t;                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory"); \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        st_sum[k] += _t - st_last;                                                           \
-        st_last = _t;                                                                        \
-    } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-
 constexpr int IN_REG_SLOTS = 6;       // input-map entries per lane kept in registers
 constexpr int SPIKE_GROUP = 8;        // spiking neurons whose synapse loads are in flight together
 
@@ -214,11 +196,6 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         }
     };
 
-#if LSM_STAMP
-    unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-    const unsigned long long st_loop0 = st_last, st_real0 = __builtin_amdgcn_s_memrealtime();
-#endif
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1;
         const uint16_t *list_prev = wlist + (cur ^ 1) * NPAD;
@@ -232,7 +209,6 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         for (int q = 0; q < WPC; ++q) pre[q + 1] = pre[q] + __builtin_amdgcn_readlane(cv, q);
         const uint32_t total = pre[WPC];
         bool drove = false;
-        STAMP(0);
 
         for (uint32_t l0 = 0; l0 < total; l0 += 64) {
             const uint32_t l = l0 + lane;
@@ -284,12 +260,10 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
                 if (n8 > 6) { LSM_LD(6)
                 if (n8 > 7) { LSM_LD(7) } } } } } } }
 #undef LSM_LD
-                STAMP(1);
                 if (!drove) {                     // ---- c. fill the load latency ----
                     input_drive(t);
                     drove = true;
                 }
-                STAMP(2);
                 // ---- d. ordered read+add+write, one spiking neuron after the other ----
 #define LSM_RMW(k)                                                                  \
     if (gb[k] + lane < ge[k]) acc[ent[k].x] = acc[ent[k].x] + __uint_as_float(ent[k].y); \
@@ -325,12 +299,10 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
                 }
 #undef LSM_RMW
 #undef LSM_RMW_LONG
-                STAMP(3);
             }
         }
         if (!drove) input_drive(t);
         wave_lds_fence();
-        STAMP(2);
 
         // ---- e. neuron update ----
         float cin[SL];
@@ -401,16 +373,8 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
                 }
             }
         }
-        STAMP(4);
         __syncthreads();
-        STAMP(5);
     }
-#if LSM_STAMP
-    st_sum[6] = st_last - st_loop0;                                   // shader cycles in the step loop
-    st_sum[7] = __builtin_amdgcn_s_memrealtime() - st_real0;          // 100 MHz ticks in the step loop
-    if (tid == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_lif_stamps[k], st_sum[k]);
-#endif
 
     // ---- epilogue: health statistics (the count array is idle and all zero after the last step), then
     //      SPEC.md §4 features from the integer accumulators (float64, then float32) ----
@@ -484,23 +448,5 @@ lif_fn_t pick_lif_00(int sl, int wpc);
 lif_fn_t pick_lif_01(int sl, int wpc);
 lif_fn_t pick_lif_10(int sl, int wpc);
 lif_fn_t pick_lif_11(int sl, int wpc);
-#if LSM_STAMP
-int read_lif_stamps(int unit, unsigned long long *out8, int reset);   // reservoir.hip sums the four units
-int read_lif_stamps_00(unsigned long long *o, int r);
-int read_lif_stamps_01(unsigned long long *o, int r);
-int read_lif_stamps_10(unsigned long long *o, int r);
-int read_lif_stamps_11(unsigned long long *o, int r);
-#define LSM_DEFINE_STAMP_READER(NAME)                                               \
-    int NAME(unsigned long long *o, int r)                                          \
-    {                                                                               \
-        LSM_CHECK_HIP(hipDeviceSynchronize());                                      \
-        LSM_CHECK_HIP(hipMemcpyFromSymbol(o, HIP_SYMBOL(g_lif_stamps), 64));        \
-        if (r) {                                                                    \
-            unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};                     \
-            LSM_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_lif_stamps), z, 64));      \
-        }                                                                           \
-        return LSM_OK;                                                              \
-    }
-#endif
 
 }  // namespace lsm_lif

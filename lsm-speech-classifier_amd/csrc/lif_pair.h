@@ -33,70 +33,14 @@
 
 namespace lsm_lif {
 
-#ifndef LSM_PAIR_P
-#define LSM_PAIR_P 4        // rows in flight (5 registers each; 6 rows: the lone launch 1.5 % faster, the whole path 3.5 % slower:
-                            // profiles/r05_pair_rows_in_flight.txt)
-#endif
-#ifndef LSM_PAIR_PRE
-#define LSM_PAIR_PRE 0      // where a step's input counts and leak terms (they do not depend on the recurrent sums) are computed: 0 = in the
-#endif                      // update; 1 = while the first chunk's row records are fetched; 2 = while its first rows are fetched (both 1-2 %
-                            // SLOWER at cfg4: the other waves of the CU fill those waits already; profiles/r05_pair_rows_in_flight.txt)
-#ifndef LSM_PAIR_PRIO
-#define LSM_PAIR_PRIO 1     // wave priority of the step loop (as lif_ring.h: profiles/r04_ring_priority.txt)
-#endif
-#ifndef LSM_PAIR_ABLATE
-#define LSM_PAIR_ABLATE 0   // diagnostic builds only (WRONG results): 1 = no window loads, 2 = no accumulator read-modify-write,
-#endif                      // 8 = no list loads, 32 = no feature updates, 64 = no accumulator reads, 128 = the window piece summed in a
-                            // register (no block switches), 256 = the list entries summed in a register (profiles/r05_pair_rmw_ablation.txt)
-
 #ifndef LSM_PAIR_PHASES
 #define LSM_PAIR_PHASES 0   // diagnostic builds only: every wave sums the core-clock cycles of its step phases and writes them OVER
-#endif                      // the feature rows (exp/r03_ring_phases.py reads them back), as LSM_RING_PHASES of lif_ring.h
+#endif                      // the feature rows (exp/r03_ring_phases.py reads them back)
 #if LSM_PAIR_PHASES
 #define LSM_PAIR_MARK(k) { const uint64_t now_ = __builtin_amdgcn_s_memtime(); ph_[k] += (uint32_t)(now_ - last_); last_ = now_; }
 #else
 #define LSM_PAIR_MARK(k)
 #endif
-
-// Diagnostic builds only (results stay right): extra work per row and wave, to see which port the row loop is bound by
-// (profiles/r05_pair_issue_ports.txt): scalar / vector instructions, LDS stores to the lane's own dump word, buffer loads
-// whose descriptor holds zero bytes (they pass through the texture-address unit and touch no memory).
-#ifndef LSM_PAIR_DUMMY_SALU
-#define LSM_PAIR_DUMMY_SALU 0
-#endif
-#ifndef LSM_PAIR_DUMMY_VALU
-#define LSM_PAIR_DUMMY_VALU 0
-#endif
-#ifndef LSM_PAIR_DUMMY_LDS
-#define LSM_PAIR_DUMMY_LDS 0
-#endif
-#ifndef LSM_PAIR_DUMMY_VMEM
-#define LSM_PAIR_DUMMY_VMEM 0
-#endif
-#ifndef LSM_PAIR_DUMMY_VMEM_LANES
-#define LSM_PAIR_DUMMY_VMEM_LANES 64
-#endif
-#ifndef LSM_PAIR_OWN_DUMP
-#define LSM_PAIR_OWN_DUMP 0     // 1: a lane without a list entry adds its zero to a dump word of its own (lane*4), not to word 0
-#endif
-// Time-only ablation builds (VERDICT r4 #1a: "predict before building"; exp/r05_residency.py).  REPLAY: the update takes every
-// neuron's spike from a RECORDED spike matrix (the `spike_matrix` argument, read instead of written: a correct run's
-// output), so the rows of every step are those of the real run whatever else the build leaves out; features are garbage.
-// LEAN (with REPLAY): no input masks, no refractory/slot register, no feature records -- the registers and the LDS a
-// kernel would have with the input counts precomputed and the features accumulated outside LDS.
-#ifndef LSM_PAIR_REPLAY
-#define LSM_PAIR_REPLAY 0
-#endif
-#ifndef LSM_PAIR_LEAN
-#define LSM_PAIR_LEAN 0
-#endif
-#ifndef LSM_PAIR_WAVES_PER_EU
-#define LSM_PAIR_WAVES_PER_EU 4
-#endif
-#ifndef LSM_PAIR_LDS_PAD
-#define LSM_PAIR_LDS_PAD 0      // extra LDS bytes per clip (host side): pins the clips per compute unit of an ablation build
-#endif
-#define LSM_PAIR_DUMMIES (LSM_PAIR_DUMMY_SALU || LSM_PAIR_DUMMY_VALU || LSM_PAIR_DUMMY_LDS || LSM_PAIR_DUMMY_VMEM)
 
 struct PairArgs {
     int N, C, T, B;
@@ -123,7 +67,7 @@ typedef float pair_f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t pair_u2 __attribute__((ext_vector_type(2)));
 typedef uint32_t pair_u4 __attribute__((ext_vector_type(4)));
 // LDS accesses of the row loop by ABSOLUTE byte address (the kernel has no static LDS: its dynamic LDS starts at 0, checked
-// once per launch): `smem + offset` costs a vector add per access that the compiler does not fold.
+// by the host once per kernel): `smem + offset` costs a vector add per access that the compiler does not fold.
 typedef __attribute__((address_space(3))) pair_f2 pair_lds_f2;
 typedef __attribute__((address_space(3))) float pair_lds_f1;
 #define LSM_PAIR_LDS_F2(addr) (*reinterpret_cast<pair_lds_f2 *>((uintptr_t)(uint32_t)(addr)))
@@ -224,14 +168,15 @@ __device__ __forceinline__ uint32_t pair_input_count(const uint32_t (&im)[4], co
 // LEAKV: a leak coefficient per neuron in registers (the reference's --leak-variance-divisor, extract_lsm_features.py:174,
 // 182-183) instead of one for all (its default).
 template <int BL, int WPC, int INMASK, bool LEAKV = false>
-__global__ __launch_bounds__(WPC * 64) __attribute__((amdgpu_waves_per_eu(LSM_PAIR_WAVES_PER_EU)))
+__global__ __launch_bounds__(WPC * 64) __attribute__((amdgpu_waves_per_eu(4)))
 void lif_pair_kernel(const PairArgs a)
 {
     constexpr int SL = 2 * BL;
     constexpr int NBP = BL * WPC;                   // blocks of the padded layout
     constexpr int NPAD = NBP * 128;
     constexpr int NT = WPC * 64;
-    constexpr int P = LSM_PAIR_P;
+    constexpr int P = 4;                            // rows in flight (5 registers each; 6 rows: the lone launch 1.5 % faster, the
+                                                    // whole path 3.5 % slower: profiles/r05_pair_rows_in_flight.txt)
     constexpr int CH = PAIR_CHUNK;
     constexpr uint32_t RSRC_FLAGS = 0x00020000u;    // raw dword buffer, gfx9 family
     static_assert(NBP <= PAIR_MAX_BLOCKS, "at most 8192 neurons");
@@ -241,8 +186,8 @@ void lif_pair_kernel(const PairArgs a)
     uint32_t *marks = reinterpret_cast<uint32_t *>(smem + PAIR_DUMP_BYTES + NPAD * 4);    // 64 words per wave
     uint8_t *wlist = reinterpret_cast<uint8_t *>(marks + WPC * 64);                       // 2*NPAD: 128 per block
     uint32_t *wcnt = reinterpret_cast<uint32_t *>(wlist + 2 * NPAD);                      // 2*64 block counts + stats
-    uint4 *feat = reinterpret_cast<uint4 *>(wcnt + PAIR_WCNT_WORDS);                      // n_out (none in a LEAN ablation build)
-    uint32_t *bits = reinterpret_cast<uint32_t *>(feat + (LSM_PAIR_LEAN ? 0 : a.n_out)); // T*CW
+    uint4 *feat = reinterpret_cast<uint4 *>(wcnt + PAIR_WCNT_WORDS);                      // n_out
+    uint32_t *bits = reinterpret_cast<uint32_t *>(feat + a.n_out);                        // T*CW
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -251,14 +196,10 @@ void lif_pair_kernel(const PairArgs a)
     const int N = a.N, T = a.T, CW = a.CW;
 #define LSM_PAIR_GB(q) ((q) * WPC + w)              // global block of my register block q
 
-    // the row loop addresses LDS absolutely (LSM_PAIR_LDS_F2): the dynamic LDS must start at 0
-    if ((uintptr_t)((__attribute__((address_space(3))) unsigned char *)smem) != 0) __builtin_trap();
-
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
     for (int i = tid; i < (PAIR_DUMP_BYTES + NPAD * 4 + WPC * 256) / 4; i += NT) reinterpret_cast<uint32_t *>(smem)[i] = 0u;
     for (int i = tid; i < PAIR_WCNT_WORDS; i += NT) wcnt[i] = 0u;
-    if (!LSM_PAIR_LEAN)
-        for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
     for (int i = tid; i < T * CW; i += NT) bits[i] = 0u;
     __syncthreads();
     {
@@ -292,8 +233,8 @@ void lif_pair_kernel(const PairArgs a)
     // oref[r] = (output slot + 1) | (refractory countdown << 16), as in lif_ring.h
     float v[SL];
     float lam[LEAKV ? SL : 1];
-    uint32_t oref[LSM_PAIR_LEAN ? 1 : SL];
-    uint32_t im[LSM_PAIR_LEAN ? 1 : SL][4];         // channels 0..127 feeding my neuron r
+    uint32_t oref[SL];
+    uint32_t im[SL][4];                             // channels 0..127 feeding my neuron r
     const float lam_u = a.leak_u;
 #pragma unroll
     for (int q = 0; q < BL; ++q) {
@@ -309,26 +250,19 @@ void lif_pair_kernel(const PairArgs a)
             // padding neurons (i >= N) start with a NaN potential: it stays NaN through every update and never fires
             // (a window that wraps past the ring's end may deliver weights of real blocks to them)
             v[2 * q + h] = (i0 + h) < N ? 0.0f : __builtin_nanf("");
-            if (!LSM_PAIR_LEAN) {
-                oref[2 * q + h] = (uint32_t)(o[h] + 1);
-                const uint4 m = reinterpret_cast<const uint4 *>(a.inmask)[i0 + h];
-                im[2 * q + h][0] = m.x; im[2 * q + h][1] = m.y; im[2 * q + h][2] = m.z; im[2 * q + h][3] = m.w;
-            }
+            oref[2 * q + h] = (uint32_t)(o[h] + 1);
+            const uint4 m = reinterpret_cast<const uint4 *>(a.inmask)[i0 + h];
+            im[2 * q + h][0] = m.x; im[2 * q + h][1] = m.y; im[2 * q + h][2] = m.z; im[2 * q + h][3] = m.w;
         }
     }
     uint32_t ref_set_v = (uint32_t)a.refractory << 16;             // (vector registers: a VOP3 select takes no literal)
     uint32_t minus_one_v = 0xFFFF0000u;
     asm volatile("" : "+v"(ref_set_v), "+v"(minus_one_v));
     const float theta = a.theta, w_in = a.w_in;
-    const bool trace = !LSM_PAIR_REPLAY && (a.spike_matrix != nullptr || a.v_trace != nullptr);
-#if LSM_PAIR_REPLAY
-    const uint8_t *rec_row = a.spike_matrix + (size_t)b * a.T * a.N;      // recorded spikes of step t (read, not written)
-    unsigned long long never64 = 0ull;
-    asm volatile("" : "+s"(never64));
-#endif
+    const bool trace = a.spike_matrix != nullptr || a.v_trace != nullptr;
     // row t of the clip's optional (T, N) outputs: advanced by N per step (the per-block form of the address, a 64-bit
     // product, was computed by every block of every step, traced or not)
-    uint8_t *sm_row = (a.spike_matrix && !LSM_PAIR_REPLAY) ? a.spike_matrix + (size_t)b * T * N : nullptr;
+    uint8_t *sm_row = a.spike_matrix ? a.spike_matrix + (size_t)b * T * N : nullptr;
     float *vt_row = a.v_trace ? a.v_trace + (size_t)b * T * N : nullptr;
     const uint32_t lane8 = (uint32_t)lane * 8u;
     const uint32_t accl = (uint32_t)PAIR_DUMP_BYTES + lane8;       // my pair of block g: accl + g*512
@@ -349,28 +283,7 @@ void lif_pair_kernel(const PairArgs a)
     last_ = __builtin_amdgcn_s_memtime();
 #endif
 
-    // The part of a step's update that does not wait for the recurrent sums -- the count of spiking input channels of every
-    // neuron and the leak d = v - lambda * v -- is computed while the step's first loads are in the air (LSM_PAIR_PRE); the
-    // update then forms sum + w_in * count and d + that: the same operations in the same order (SPEC.md 3).
-    uint32_t npk[(LSM_PAIR_PRE && !LSM_PAIR_LEAN) ? (SL + 3) / 4 : 1];     // input counts (<= 128 channels), a byte per neuron
-#define LSM_PAIR_PRE_UPDATE                                                                             \
-    {                                                                                                   \
-        uint32_t rowbits[4];                                    /* this step's input bit row (wave-uniform) */ \
-        if (CW == 4) {                                                                                  \
-            const uint4 q4 = *reinterpret_cast<const uint4 *>(bits + t * 4);                            \
-            rowbits[0] = q4.x; rowbits[1] = q4.y; rowbits[2] = q4.z; rowbits[3] = q4.w;                 \
-        } else {                                                                                        \
-            _Pragma("unroll") for (int k = 0; k < 4; ++k) rowbits[k] = k < CW ? bits[t * CW + k] : 0u;  \
-        }                                                                                               \
-        _Pragma("unroll") for (int r = 0; r < SL; ++r) {                                                \
-            const uint32_t nn_ = pair_input_count<INMASK>(im[r], rowbits);                              \
-            npk[r >> 2] = (r & 3) ? (npk[r >> 2] | (nn_ << (8 * (r & 3)))) : nn_;                       \
-            const float m_ = (LEAKV ? lam[r] : lam_u) * v[r];                                           \
-            v[r] = v[r] - m_;                                                                           \
-        }                                                                                               \
-    }
-
-    if (LSM_PAIR_PRIO) __builtin_amdgcn_s_setprio(LSM_PAIR_PRIO);
+    __builtin_amdgcn_s_setprio(1);     // wave priority of the step loop (as lif_ring.h: profiles/r04_ring_priority.txt)
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, prv = cur ^ 1;
         const uint8_t *list_prev = wlist + prv * NPAD;
@@ -407,7 +320,6 @@ void lif_pair_kernel(const PairArgs a)
             // no scalar arithmetic (an extra scalar instruction per row costs the launch five times what a vector one does:
             // profiles/r05_ring_issue_ports.txt).
             const uint4 rc = my_rec[(size_t)jl * WPC];
-            if (LSM_PAIR_PRE == 1 && !LSM_PAIR_LEAN && l0 == 0) LSM_PAIR_PRE_UPDATE
             const uint32_t rx = rc.x, rw = rc.w;
             const uint32_t r_so = (uint32_t)(int)(int16_t)(rc.y & 0xFFFFu);        // my block's byte offset in the row (signed)
             const uint32_t r_lo = rc.y >> 16;                                      // LDS offset of its accumulators
@@ -424,39 +336,6 @@ void lif_pair_kernel(const PairArgs a)
             // the accumulators under the row being applied are fetched one row ahead: two sets, by the row's parity
             pair_f2 old[2];                      // under the window piece
             float oldl[2];                       // under my list entry
-#if LSM_PAIR_DUMMIES
-            uint32_t dummy_s_ = 0u, dummy_v_ = 0u;
-            pair_u2 dummy_m_[LSM_PAIR_P][LSM_PAIR_DUMMY_VMEM ? LSM_PAIR_DUMMY_VMEM : 1] = {};
-#define LSM_PAIR_DUMMY_WORK                                                                                     \
-    {                                                                                                           \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_PAIR_DUMMY_SALU; ++d_)                                      \
-            asm volatile("s_add_u32 %0, %0, 1" : "+s"(dummy_s_) : : "scc");                                     \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_PAIR_DUMMY_VALU; ++d_)                                      \
-            asm volatile("v_add_u32 %0, 1, %0" : "+v"(dummy_v_));                                               \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_PAIR_DUMMY_LDS; ++d_)                                       \
-            asm volatile("ds_write_b32 %0, %1" : : "v"(lane8 >> 1), "v"(dummy_v_) : "memory"); /* dump bytes */ \
-    }
-            // the zero-byte loads take a buffer of the row pipeline like the real ones (issued with the row, consumed when the
-            // row is applied): waiting for one at once would drain the pipeline and measure that instead
-#define LSM_PAIR_DUMMY_LOADS(p)                                                                                 \
-    {                                                                                                           \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_PAIR_DUMMY_VMEM; ++d_) {                                    \
-            const __amdgpu_buffer_rsrc_t rd_ = __builtin_amdgcn_make_buffer_rsrc(                               \
-                reinterpret_cast<void *>(band_hi | (uint64_t)sx), 0, 0, RSRC_FLAGS);                            \
-            /* LSM_PAIR_DUMMY_VMEM_LANES: only that many lanes take part (exec mask): does a load's cost follow its lanes? */ \
-            if (LSM_PAIR_DUMMY_VMEM_LANES >= 64 || lane < LSM_PAIR_DUMMY_VMEM_LANES)                            \
-                dummy_m_[p][d_] = __builtin_amdgcn_raw_buffer_load_b64(rd_, (int)lane8, 0, 0);                  \
-        }                                                                                                       \
-    }
-#define LSM_PAIR_DUMMY_USE(p)                                                                                   \
-    {                                                                                                           \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_PAIR_DUMMY_VMEM; ++d_) asm volatile("" : : "v"(dummy_m_[p][d_])); \
-    }
-#else
-#define LSM_PAIR_DUMMY_WORK
-#define LSM_PAIR_DUMMY_LOADS(p)
-#define LSM_PAIR_DUMMY_USE(p)
-#endif
             // SEL(m): the six fields of the chunk's row m into scalar registers.  It runs AHEAD of the row's loads, with the
             // previous row's accumulator update between them: a buffer load that reads a scalar register written by
             // v_readlane needs five wait states, which were three s_nop per row when the loads followed at once.
@@ -475,7 +354,6 @@ void lif_pair_kernel(const PairArgs a)
             // ISSUE(p): request the selected row's window piece and list entry into buffer p
 #define LSM_PAIR_ISSUE(p)                                                                       \
     {                                                                                           \
-        LSM_PAIR_DUMMY_WORK                                                                     \
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(                    \
             reinterpret_cast<void *>(band_hi | (uint64_t)sx), 0, (int)snb, RSRC_FLAGS);         \
         wa[p] = lane8 + slo;                                                                    \
@@ -483,17 +361,11 @@ void lif_pair_kernel(const PairArgs a)
         /* instruction's immediate), so a lane in front of the row is a huge unsigned offset        */ \
         uint32_t so_ = so;                                                                      \
         asm volatile("" : "+s"(so_));                                                           \
-        if (LSM_PAIR_ABLATE & 1) {                                                              \
-            wv[p] = (pair_f2){0.0f, 0.0f};                                                      \
-        } else {                                                                                \
-            const pair_u2 x = __builtin_amdgcn_raw_buffer_load_b64(rb, (int)(lane8 + so_), 0, 0); \
-            wv[p] = (pair_f2){__uint_as_float(x.x), __uint_as_float(x.y)};                      \
-        }                                                                                       \
+        const pair_u2 x = __builtin_amdgcn_raw_buffer_load_b64(rb, (int)(lane8 + so_), 0, 0);   \
+        wv[p] = (pair_f2){__uint_as_float(x.x), __uint_as_float(x.y)};                          \
         const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(                    \
             reinterpret_cast<void *>(rem_hi | (uint64_t)sw), 0, (int)sln, RSRC_FLAGS);          \
-        if (LSM_PAIR_ABLATE & 8) re[p] = (pair_u2){0u, 0u};                                     \
-        else re[p] = __builtin_amdgcn_raw_buffer_load_b64(rr, (int)lane8, 0, 0);                \
-        LSM_PAIR_DUMMY_LOADS(p)                                                                 \
+        re[p] = __builtin_amdgcn_raw_buffer_load_b64(rr, (int)lane8, 0, 0);                     \
         __builtin_amdgcn_sched_barrier(0);                                                      \
     }
             // READ(p): fetch the accumulators the row in buffer p adds to: the pair under its window piece and the word
@@ -501,11 +373,8 @@ void lif_pair_kernel(const PairArgs a)
             // such lane rewrites with the same value, old + 0 -- same-address lanes of one LDS instruction do not conflict)
 #define LSM_PAIR_READ(p)                                                                        \
     {                                                                                           \
-        if (LSM_PAIR_ABLATE & (64 | 128)) old[(p) & 1] = (pair_f2){0.0f, 0.0f};                 \
-        else old[(p) & 1] = LSM_PAIR_LDS_F2(wa[p] + PAIR_DUMP_BYTES);                           \
-        if (LSM_PAIR_OWN_DUMP) re[p].x = max(re[p].x, lane8 >> 1);                              \
-        if (LSM_PAIR_ABLATE & (64 | 256)) oldl[(p) & 1] = 0.0f;                                 \
-        else oldl[(p) & 1] = LSM_PAIR_LDS_F1(re[p].x);                                          \
+        old[(p) & 1] = LSM_PAIR_LDS_F2(wa[p] + PAIR_DUMP_BYTES);                                \
+        oldl[(p) & 1] = LSM_PAIR_LDS_F1(re[p].x);                                               \
         __builtin_amdgcn_sched_barrier(0);                                                      \
     }
             // APPLY(p): add row p and write back -- the window pair first, the list word after it (a list target may sit in
@@ -513,23 +382,16 @@ void lif_pair_kernel(const PairArgs a)
             // old + weight from the list write, in that order).  Rows are applied in ascending j = the order of these calls.
 #define LSM_PAIR_APPLY(p)                                                                       \
     {                                                                                           \
-        LSM_PAIR_DUMMY_USE(p)                                                                   \
-        if (!(LSM_PAIR_ABLATE & 2)) {                                                           \
-            /* the list sum first: its read was issued last, so ONE wait covers both reads */   \
-            float newl = oldl[(p) & 1] + __uint_as_float(re[p].y);                              \
-            asm volatile("" : "+v"(newl));                                                      \
-            if (LSM_PAIR_ABLATE & 128) abl_cur_ = abl_cur_ + wv[p];                             \
-            else LSM_PAIR_LDS_F2(wa[p] + PAIR_DUMP_BYTES) = old[(p) & 1] + wv[p];               \
-            asm volatile("" ::: "memory");                                                      \
-            if (LSM_PAIR_ABLATE & 256) abl_l_ += newl;                                          \
-            else LSM_PAIR_LDS_F1(re[p].x) = newl;                                               \
-            asm volatile("" ::: "memory");                                                      \
-        }                                                                                       \
+        /* the list sum first: its read was issued last, so ONE wait covers both reads */       \
+        float newl = oldl[(p) & 1] + __uint_as_float(re[p].y);                                  \
+        asm volatile("" : "+v"(newl));                                                          \
+        LSM_PAIR_LDS_F2(wa[p] + PAIR_DUMP_BYTES) = old[(p) & 1] + wv[p];                        \
+        asm volatile("" ::: "memory");                                                          \
+        LSM_PAIR_LDS_F1(re[p].x) = newl;                                                        \
+        asm volatile("" ::: "memory");                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                      \
     }
             static_assert(P % 2 == 0, "the look-ahead sets alternate by the row's parity");
-            pair_f2 abl_cur_ = {0.0f, 0.0f};       // LSM_PAIR_ABLATE & 128 / 256 only
-            float abl_l_ = 0.0f;
             // Exactly the chunk's n rows are requested (a buffer load holds the texture-address path about 11 cycles whether
             // or not its descriptor has bytes: profiles/r05_residency_ablation.txt).  n >= P: P rows requested, whole turns
             // of P rows while the P rows requested in a turn all exist, one last turn that requests the n % P rows left, then
@@ -541,7 +403,6 @@ void lif_pair_kernel(const PairArgs a)
                     LSM_PAIR_ISSUE(p)
                 }
                 LSM_PAIR_MARK(2)       // first P rows requested
-                if (LSM_PAIR_PRE == 2 && !LSM_PAIR_LEAN && l0 == 0) LSM_PAIR_PRE_UPDATE
                 LSM_PAIR_READ(0)
                 int m = 0;
                 for (; m + 2 * P <= n; m += P) {
@@ -579,7 +440,6 @@ void lif_pair_kernel(const PairArgs a)
                         LSM_PAIR_ISSUE(p)
                     }
                 LSM_PAIR_MARK(2)
-                if (LSM_PAIR_PRE == 2 && !LSM_PAIR_LEAN && l0 == 0) LSM_PAIR_PRE_UPDATE
 #pragma unroll
                 for (int p = 0; p < P - 1; ++p)
                     if (p < n) {
@@ -587,21 +447,17 @@ void lif_pair_kernel(const PairArgs a)
                         LSM_PAIR_APPLY(p)
                     }
             }
-            if (LSM_PAIR_ABLATE & (128 | 256)) LSM_PAIR_LDS_F2(lane8 + PAIR_DUMP_BYTES) = abl_cur_ + (pair_f2){abl_l_, 0.0f};
 #undef LSM_PAIR_SEL
 #undef LSM_PAIR_ISSUE
-#undef LSM_PAIR_DUMMY_WORK
-#undef LSM_PAIR_DUMMY_LOADS
-#undef LSM_PAIR_DUMMY_USE
 #undef LSM_PAIR_READ
 #undef LSM_PAIR_APPLY
             LSM_PAIR_MARK(3)           // rows applied (waits for the row loads included)
         }
         wave_lds_fence();
-#if LSM_PAIR_PRE && !LSM_PAIR_LEAN
-        if (total == 0u) LSM_PAIR_PRE_UPDATE                    // a step without rows
-#else
-        uint32_t rowbits[4];                                    // this step's input bit row (wave-uniform)
+        // this step's input bit row (wave-uniform).  The input counts and the leak are computed in the update: computing them
+        // while the step's first loads are in the air was 1-2 % SLOWER at cfg4 (the other waves of the CU fill those waits
+        // already; profiles/r05_pair_rows_in_flight.txt)
+        uint32_t rowbits[4];
         if (CW == 4) {
             const uint4 q4 = *reinterpret_cast<const uint4 *>(bits + t * 4);
             rowbits[0] = q4.x; rowbits[1] = q4.y; rowbits[2] = q4.z; rowbits[3] = q4.w;
@@ -609,7 +465,6 @@ void lif_pair_kernel(const PairArgs a)
 #pragma unroll
             for (int k = 0; k < 4; ++k) rowbits[k] = k < CW ? bits[t * CW + k] : 0u;
         }
-#endif
 
         // ---- neuron update, block by block: leak/integrate/threshold by select, then (only if a neuron of the
         //      block fired) its entries of the block's spike list and the feature accumulators ----
@@ -623,43 +478,24 @@ void lif_pair_kernel(const PairArgs a)
             *reinterpret_cast<pair_f2 *>(smem + accl + (uint32_t)gb * 512u) = (pair_f2){0.0f, 0.0f};
             float ci[2] = {cq.x, cq.y};
             unsigned long long bq[2];
-#if LSM_PAIR_REPLAY
-            uint32_t rec2 = 0u;                                     // my two neurons' recorded spikes of this step
-            if (gb * 128 + lane * 2 + 1 < N) rec2 = *reinterpret_cast<const uint16_t *>(rec_row + gb * 128 + lane * 2);
-#endif
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int r = 2 * q + h;
-#if LSM_PAIR_PRE && !LSM_PAIR_LEAN
-                ci[h] = ci[h] + w_in * (float)((npk[r >> 2] >> (8 * (r & 3))) & 0xFFu);    // SPEC.md §3: input term after the recurrent sum
-                const float vn = v[r] + ci[h];             // v[r] holds d = v - lambda * v since LSM_PAIR_PRE_UPDATE
-#else
-                const uint32_t nn = LSM_PAIR_LEAN ? 0u : pair_input_count<INMASK>(im[r], rowbits);
+                const uint32_t nn = pair_input_count<INMASK>(im[r], rowbits);
                 ci[h] = ci[h] + w_in * (float)nn;          // SPEC.md §3: input term after the recurrent sum
                 const float m = (LEAKV ? lam[r] : lam_u) * v[r];
                 const float d = v[r] - m;
                 const float vn = d + ci[h];
-#endif
-#if LSM_PAIR_REPLAY
-                const unsigned long long held = LSM_PAIR_LEAN ? 0ull : __builtin_amdgcn_uicmp(oref[r], 0x10000u, 35);
-                const unsigned long long ge = __builtin_amdgcn_fcmpf(vn, theta, 3 /* ordered >= */);
-                // (the membrane arithmetic stays alive through a mask the compiler cannot see is empty)
-                const unsigned long long fire = __builtin_amdgcn_uicmp((rec2 >> (8 * h)) & 0xFFu, 0u, 33 /* != */) |
-                                                (ge & ~held & never64);
-#else
                 const unsigned long long held = __builtin_amdgcn_uicmp(oref[r], 0x10000u, 35 /* unsigned >= */);
                 const unsigned long long ge = __builtin_amdgcn_fcmpf(vn, theta, 3 /* ordered >= */);
                 const unsigned long long fire = ge & ~held;
-#endif
                 v[r] = __builtin_amdgcn_inverse_ballot_w64(ge | held) ? 0.0f : vn;
                 // countdown: -1 while held, set on fire -- two selects on the lane masks and an add (written out: the
                 // compiler turned the nested select into an exec-masked region of six instructions)
-                if (!LSM_PAIR_LEAN) {
-                    uint32_t dlt;
-                    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(dlt) : "v"(ref_set_v), "s"(fire));
-                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dlt) : "v"(dlt), "v"(minus_one_v), "s"(held));
-                    oref[r] += dlt;
-                }
+                uint32_t dlt;
+                asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(dlt) : "v"(ref_set_v), "s"(fire));
+                asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(dlt) : "v"(dlt), "v"(minus_one_v), "s"(held));
+                oref[r] += dlt;
                 bq[h] = fire;
             }
             int nq = 0;
@@ -673,8 +509,8 @@ void lif_pair_kernel(const PairArgs a)
                         list_cur[gb * 128 + rank] = (uint8_t)(lane * 2 + h);
                         rank += 1;
                         hf |= 1u << r;
-                        const int osl = LSM_PAIR_LEAN ? -1 : (int)(oref[r] & 0xFFFFu) - 1;
-                        if (osl >= 0 && !(LSM_PAIR_ABLATE & 32)) {
+                        const int osl = (int)(oref[r] & 0xFFFFu) - 1;
+                        if (osl >= 0) {
                             uint4 f = feat[osl];
                             uint32_t nf = f.x & 0xFFFFu, bursts = f.x >> 16;
                             uint32_t first = f.y & 0xFFFFu, last = f.y >> 16;
@@ -707,9 +543,6 @@ void lif_pair_kernel(const PairArgs a)
             }
         }
         if (lane < BL) wcnt[cur * PAIR_MAX_BLOCKS + lane * WPC + w] = cntv;      // block lane*WPC + w is my block `lane`
-#if LSM_PAIR_REPLAY
-        rec_row += N;
-#endif
         if (trace) {
             if (sm_row) sm_row += N;
             if (vt_row) vt_row += N;
@@ -720,7 +553,7 @@ void lif_pair_kernel(const PairArgs a)
         LSM_PAIR_MARK(6)               // barrier
     }
 #undef LSM_PAIR_GB
-    if (LSM_PAIR_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
     if (a.stats) {
@@ -733,7 +566,7 @@ void lif_pair_kernel(const PairArgs a)
         }
     }
     const int nf = a.n_keys * a.n_out;
-    for (int idx = tid; idx < (LSM_PAIR_LEAN ? 0 : nf); idx += NT) {
+    for (int idx = tid; idx < nf; idx += NT) {
         const int kq = idx / a.n_out;
         const int o = idx - kq * a.n_out;
         const uint4 f = feat[o];

@@ -47,56 +47,6 @@ namespace lsm_lif {
 
 #define LSM_RING_ADD4(a, b) a = a + b;      // four floats: two v_pk_add_f32 (four v_add_f32 measured equal)
 
-#ifndef LSM_RING_PHASES
-#define LSM_RING_PHASES 0   // diagnostic builds only: 1 = every wave sums the core-clock cycles of its step phases and writes them
-#endif                      // OVER the feature rows (exp/r03_ring_phases.py reads them back); results are not features.
-#if LSM_RING_PHASES         // A mark is not free: s_memtime returns through lgkmcnt (it waits for the wave's outstanding LDS
-                            // operations) and the compiler moves no memory operation across it -- phases that the product build
-                            // overlaps (e.g. the input-map fetch with the last rows) show up serialised here.
-#define LSM_RING_MARK(k) { const uint64_t now_ = __builtin_amdgcn_s_memtime(); ph_[k] += (uint32_t)(now_ - last_); last_ = now_; }
-#else
-#define LSM_RING_MARK(k)
-#endif
-
-#ifndef LSM_RING_PRIO
-#define LSM_RING_PRIO 1         // wave priority of the step loop (s_setprio 0..3; profiles/r04_ring_priority.txt)
-#endif
-#ifndef LSM_RING_DRIVE_AT
-#define LSM_RING_DRIVE_AT 0     // 0 = at the top of the step (product: 6.09 ms at cfg4), 1 = behind the first row loads of the step
-#endif                          // (6.13 ms and seven spilled registers: profiles/r04_ring_input_drive.txt)
-
-#ifndef LSM_RING_DRIVE_ALL_LANES
-#define LSM_RING_DRIVE_ALL_LANES 0
-#endif
-// Diagnostic builds only (results stay right): extra scalar / vector / LDS instructions per row and wave, to see which
-// issue port the row loop is bound by (profiles/r05_ring_issue_ports.txt).
-#ifndef LSM_RING_DUMMY_SALU
-#define LSM_RING_DUMMY_SALU 0
-#endif
-#ifndef LSM_RING_DUMMY_VALU
-#define LSM_RING_DUMMY_VALU 0
-#endif
-#ifndef LSM_RING_DUMMY_LDS
-#define LSM_RING_DUMMY_LDS 0
-#endif
-#if LSM_RING_DUMMY_SALU || LSM_RING_DUMMY_VALU || LSM_RING_DUMMY_LDS
-#define LSM_RING_DUMMY_WORK                                                                                     \
-    {                                                                                                           \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_RING_DUMMY_SALU; ++d_)                                      \
-            asm volatile("s_add_u32 %0, %0, 1" : "+s"(dummy_s_) : : "scc");                                     \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_RING_DUMMY_VALU; ++d_)                                      \
-            asm volatile("v_add_u32 %0, 1, %0" : "+v"(dummy_v_));                                               \
-        _Pragma("unroll") for (int d_ = 0; d_ < LSM_RING_DUMMY_LDS; ++d_)                                       \
-            asm volatile("ds_write_b32 %0, %1" : : "v"(lane4), "v"(dummy_v_) : "memory");  /* my dump word */   \
-    }
-#else
-#define LSM_RING_DUMMY_WORK
-#endif
-#ifndef LSM_RING_ABLATE
-#define LSM_RING_ABLATE 0   // diagnostic builds only (1, 2, 8, 16, 32 give WRONG results): 1 = no window loads, 2 = no
-#endif                      // accumulator read-modify-write, 8 = no list loads, 16 = no input drive, 32 = no feature updates;
-                            // 64 = the input drive issued TWICE, the second pass adding zeros (results stay right: its time is the drive's cost)
-
 struct RingArgs {
     int N, C, T, B;
     int n_out, CW, EinW, refractory, burst_isi_max;
@@ -174,16 +124,10 @@ void lif_ring_kernel(const RingArgs a)
     constexpr int NPAD = NQP * 256;
     constexpr int NT = WPC * 64;
     constexpr int WL = STRIDED ? 1 : QL;            // window loads per row and wave
-#ifndef LSM_RING_P                                  // experiment switches: rows in flight (strided / contiguous)
-#define LSM_RING_P 4
-#endif
-#ifndef LSM_RING_PC
-#define LSM_RING_PC (QL >= 4 ? 4 : 8)
-#endif
     // rows in flight (WL*4 + 2 registers each), even.  Round 4, after the update's lane masks freed registers: four quads per
     // wave (N = 8000) take 6 -- 142 registers, still three waves per SIMD: cfg5 163.2 -> 160.4 ms --, two quads keep 4
     // (N = 4000 with 6: 6.02 -> 6.23 ms; profiles/r04_ring_masks_and_rows_in_flight.txt)
-    constexpr int P = STRIDED ? (QL == 4 && LSM_RING_P == 4 ? 6 : LSM_RING_P) : LSM_RING_PC;
+    constexpr int P = STRIDED ? (QL == 4 ? 6 : 4) : (QL >= 4 ? 4 : 8);
     constexpr uint32_t RSRC_FLAGS = 0x00020000u;    // raw dword buffer, gfx9 family
     static_assert(NQP <= RING_MAX_QUADS, "at most 8192 neurons");
 
@@ -282,14 +226,6 @@ void lif_ring_kernel(const RingArgs a)
     const uint64_t band_base = reinterpret_cast<uint64_t>(a.band);
     const uint64_t rem_base = reinterpret_cast<uint64_t>(a.rem);
     const int H = a.H, NQ = a.NQ;
-#if LSM_RING_PHASES
-    uint32_t ph_[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    uint32_t rows_ = 0u;
-    uint64_t last_ = 0;
-#endif
-#if LSM_RING_DUMMY_SALU || LSM_RING_DUMMY_VALU || LSM_RING_DUMMY_LDS
-    uint32_t dummy_s_ = 0u, dummy_v_ = 0u;
-#endif
     uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
     uint32_t tot_spk = 0u;             // spikes of my wave (stats)
     __syncthreads();
@@ -301,7 +237,7 @@ void lif_ring_kernel(const RingArgs a)
     // put it at 1.49 of cfg4's 6.44 ms (profiles/r04_ring_input_drive.txt).  A wave's entries only ever touch the counts
     // of its own neurons, which it cleared itself in the previous update: the drive needs no barrier and can run anywhere
     // between two updates of its wave.
-    auto drive_block = [&](const uint32_t *row, const uint32_t (&x)[EPL], uint32_t keep) __attribute__((always_inline)) {
+    auto drive_block = [&](const uint32_t *row, const uint32_t (&x)[EPL]) __attribute__((always_inline)) {
         uint32_t rw[EPL];
 #pragma unroll
         for (int u = 0; u < EPL; ++u) rw[u] = row[x[u] >> 21];
@@ -313,15 +249,10 @@ void lif_ring_kernel(const RingArgs a)
         for (int u = 0; u < EPL; ++u) {
             const uint32_t bit = (rw[u] >> ((x[u] >> 16) & 31u)) & 1u;
             const uint32_t inc = bit << ((x[u] >> 11) & 16u);
-#if LSM_RING_DRIVE_ALL_LANES                       // diagnostic builds: every lane adds (zeros included)
-            atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(cnt) + (x[u] & 0x7FFFu)), inc & keep);
-#else
-            if (bit & keep)
-                atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(cnt) + (x[u] & 0x7FFFu)), inc);
-#endif
+            if (bit) atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(cnt) + (x[u] & 0x7FFFu)), inc);
         }
     };
-    auto input_drive = [&](int ts, uint32_t keep = 0xFFFFFFFFu) {
+    auto input_drive = [&](int ts) {
         if (INMASK) return;                       // counted in the update, from the masks
         const uint32_t *row = bits + ts * CW;
         if (INREG) {
@@ -330,45 +261,32 @@ void lif_ring_kernel(const RingArgs a)
                 uint32_t x[EPL];
 #pragma unroll
                 for (int u = 0; u < EPL; ++u) x[u] = ent_reg[q * EPL + u];
-                drive_block(row, x, keep);
+                drive_block(row, x);
             }
         } else {
             for (int e0 = 0; e0 < a.EinW; e0 += RING_ENT_BLOCK) {
                 uint32_t x[EPL];
 #pragma unroll
                 for (int u = 0; u < EPL; ++u) x[u] = my_ent[e0 + u * 64 + lane];
-                drive_block(row, x, keep);
+                drive_block(row, x);
             }
         }
     };
 
-#if LSM_RING_PHASES
-    last_ = __builtin_amdgcn_s_memtime();
-#endif
     // Inside the pipeline the ring kernel is the stage that bounds the step (cfg4: 5.1 ms of reservoir against 2.5 ms of front
     // end per 1024 clips), and a float64 filterbank wave shares every SIMD with its waves for 40 % of the time: the step loop runs
     // at raised wave priority so that its latency chain is not stretched by the front end's issue slots.
-    if (LSM_RING_PRIO) __builtin_amdgcn_s_setprio(LSM_RING_PRIO);
+    // (s_setprio 1; profiles/r04_ring_priority.txt)
+    __builtin_amdgcn_s_setprio(1);
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1, prv = cur ^ 1;
         const uint16_t *list_prev = wlist + prv * NPAD;
         uint16_t *list_cur = wlist + cur * NPAD;
 
         // The input drive is independent of the rows (see input_drive): it is issued once per step, at the top (behind
-        // the first row loads of the step -- LSM_RING_DRIVE_AT=1, diagnostic builds -- it measured 0.7 % slower).
-        bool drove = false;
-        auto drive_once = [&]() __attribute__((always_inline)) {
-            if (drove) return;
-            drove = true;
-            if (!(LSM_RING_ABLATE & 16)) input_drive(t);
-            if (LSM_RING_ABLATE & 64) {
-                uint32_t zero = 0u;
-                asm volatile("" : "+s"(zero));      // opaque: the second pass is not folded away
-                input_drive(t, zero);
-            }
-        };
-        if (LSM_RING_DRIVE_AT == 0) drive_once();
-        LSM_RING_MARK(4)               // input counts issued (the fetch of streamed input-map entries included)
+        // the first row loads of the step it measured 0.7 % slower: 6.13 against 6.09 ms at cfg4, and seven spilled
+        // registers; profiles/r04_ring_input_drive.txt).
+        input_drive(t);
 
         // ---- spiking neurons of step t-1: prefix of the per-quad counts, lane l <- l-th neuron ----
         const uint32_t cv = wcnt[prv * 32 + (lane & 31)];
@@ -376,10 +294,6 @@ void lif_ring_kernel(const RingArgs a)
 #pragma unroll
         for (int g = 0; g < NQP; ++g) total += __builtin_amdgcn_readlane(cv, g);
 
-        LSM_RING_MARK(0)               // quad counts read, total known
-#if LSM_RING_PHASES
-        rows_ += total;
-#endif
         for (uint32_t l0 = 0; l0 < total; l0 += 64) {
             const uint32_t l = l0 + lane;
             uint32_t gsel = 0u, pbase = 0u, run = 0u;      // (the prefix is formed again per chunk: it would
@@ -428,10 +342,6 @@ void lif_ring_kernel(const RingArgs a)
             const uint32_t p_a = (uint32_t)jl | ((p_nrec >> 4) << 16);
             const uint32_t p_c = r0 | ((r1 - r0) << 24);                // host: fewer than 2^24 list entries per layout
             const int n = (int)min(64u, total - l0);
-#if LSM_RING_PHASES
-            asm volatile("" : : "v"(p_a), "v"(p_c), "v"(p_soff));      // the row words (and the pointer loads) have arrived
-#endif
-            LSM_RING_MARK(1)           // chunk set-up: prefix, list read, geometry, list pointers
             ring_f4 wv[P][WL];
             ring_u2 re[P];
             ring_f4 old[WL];                     // accumulators under the window load of the row being applied
@@ -443,7 +353,6 @@ void lif_ring_kernel(const RingArgs a)
             // exist: their num_records is 0, every load is out of range and returns zeros without traffic.
 #define LSM_RING_LOADW(p, m)                                                                    \
     {                                                                                           \
-        LSM_RING_DUMMY_WORK                                                                     \
         const int mm = (m) & 63;                                                                \
         const uint32_t live = (uint32_t) - (int)((m) < n);                                      \
         const uint32_t ra = __builtin_amdgcn_readlane(p_a, mm);                                 \
@@ -459,13 +368,9 @@ void lif_ring_kernel(const RingArgs a)
             /* out of range whatever the address adder does with a carry                                  */ \
             uint32_t so = (STRIDED ? (soff & ~15u) : soff) + (uint32_t)q * 1024u;               \
             asm volatile("" : "+s"(so));                                                        \
-            if (LSM_RING_ABLATE & 1) {                                                          \
-                wv[p][q] = (ring_f4){0.0f, 0.0f, 0.0f, 0.0f};                                   \
-            } else {                                                                            \
-                const ring_u4 x = __builtin_amdgcn_raw_buffer_load_b128(rb, (int)(lane16 + so), 0, 0); \
-                wv[p][q] = (ring_f4){__uint_as_float(x.x), __uint_as_float(x.y),                \
-                                     __uint_as_float(x.z), __uint_as_float(x.w)};               \
-            }                                                                                   \
+            const ring_u4 x = __builtin_amdgcn_raw_buffer_load_b128(rb, (int)(lane16 + so), 0, 0); \
+            wv[p][q] = (ring_f4){__uint_as_float(x.x), __uint_as_float(x.y),                    \
+                                 __uint_as_float(x.z), __uint_as_float(x.w)};                   \
         }                                                                                       \
     }
 #define LSM_RING_LOADL(p, m)                                                                    \
@@ -477,8 +382,7 @@ void lif_ring_kernel(const RingArgs a)
         const uint64_t raddr = rem_base + (uint64_t)((rc & 0xFFFFFFu) << 3);                    \
         const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(                    \
             reinterpret_cast<void *>(raddr), 0, (int)rnrec, RSRC_FLAGS);                        \
-        if (LSM_RING_ABLATE & 8) re[p] = (ring_u2){0u, 0u};                                     \
-        else re[p] = __builtin_amdgcn_raw_buffer_load_b64(rr, (int)lane8, 0, 0);                \
+        re[p] = __builtin_amdgcn_raw_buffer_load_b64(rr, (int)lane8, 0, 0);                     \
         __builtin_amdgcn_sched_barrier(0);                                                      \
     }
             // READ(p): fetch the accumulators the row in buffer p adds to: the quad(s) under its window load and
@@ -499,15 +403,13 @@ void lif_ring_kernel(const RingArgs a)
             // ascending j = the order of these calls; LDS keeps a wave's accesses in program order.
 #define LSM_RING_APPLY(p)                                                                       \
     {                                                                                           \
-        if (!(LSM_RING_ABLATE & 2)) {                                                           \
-            _Pragma("unroll") for (int q = 0; q < WL; ++q) {                                    \
-                LSM_RING_ADD4(old[q], wv[p][q])                                                 \
-                *reinterpret_cast<ring_f4 *>(smem + wa[q]) = old[q];                            \
-            }                                                                                   \
-            asm volatile("" ::: "memory");                                                      \
-            *reinterpret_cast<float *>(smem + pa) = oldl + __uint_as_float(re[p].y);            \
-            asm volatile("" ::: "memory");                                                      \
+        _Pragma("unroll") for (int q = 0; q < WL; ++q) {                                        \
+            LSM_RING_ADD4(old[q], wv[p][q])                                                     \
+            *reinterpret_cast<ring_f4 *>(smem + wa[q]) = old[q];                                \
         }                                                                                       \
+        asm volatile("" ::: "memory");                                                          \
+        *reinterpret_cast<float *>(smem + pa) = oldl + __uint_as_float(re[p].y);                \
+        asm volatile("" ::: "memory");                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                      \
     }
             // software pipeline: P rows of loads in flight; the accumulator reads of row m+1 are issued right
@@ -517,8 +419,6 @@ void lif_ring_kernel(const RingArgs a)
                 LSM_RING_LOADW(p, p)
                 LSM_RING_LOADL(p, p)
             }
-            LSM_RING_MARK(2)           // first P rows requested
-            if (LSM_RING_DRIVE_AT == 1) drive_once();
             LSM_RING_READ(0)
             for (int m = 0; m < n; m += P) {
 #pragma unroll
@@ -529,13 +429,11 @@ void lif_ring_kernel(const RingArgs a)
                     LSM_RING_LOADL(p, m + p + P)
                 }
             }
-            LSM_RING_MARK(3)           // rows applied (waits for the row loads included)
 #undef LSM_RING_LOADW
 #undef LSM_RING_LOADL
 #undef LSM_RING_READ
 #undef LSM_RING_APPLY
         }
-        drive_once();                  // a step without reservoir spikes: no rows to hide behind
         wave_lds_fence();
         uint32_t rowbits[4] = {0u, 0u, 0u, 0u};              // INMASK: this step's input bit row (wave-uniform)
         if (INMASK) {
@@ -610,7 +508,7 @@ void lif_ring_kernel(const RingArgs a)
                         rank += 1;
                         hf |= 1u << r;
                         const int osl = (int)(oref[r] & 0xFFFFu) - 1;
-                        if (osl >= 0 && !(LSM_RING_ABLATE & 32)) {
+                        if (osl >= 0) {
                             uint4 f = feat[osl];
                             uint32_t nf = f.x & 0xFFFFu, bursts = f.x >> 16;
                             uint32_t first = f.y & 0xFFFFu, last = f.y >> 16;
@@ -644,12 +542,10 @@ void lif_ring_kernel(const RingArgs a)
             }
         }
         tot_spk += (uint32_t)nspk;
-        LSM_RING_MARK(5)               // neuron update, spike lists, feature accumulators
         __syncthreads();
-        LSM_RING_MARK(6)               // barrier
     }
 #undef LSM_RING_GQ
-    if (LSM_RING_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
     if (a.stats) {
@@ -686,13 +582,6 @@ void lif_ring_kernel(const RingArgs a)
         }
         a.features[(size_t)b * nf + idx] = (float)val;
     }
-#if LSM_RING_PHASES
-    __syncthreads();
-    float out_ = (float)rows_;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) out_ = lane == k ? (float)ph_[k] : out_;
-    if (lane < 8 && nf >= WPC * 8) a.features[(size_t)b * nf + w * 8 + lane] = out_;
-#endif
 }
 
 typedef void (*ring_fn_t)(const RingArgs);

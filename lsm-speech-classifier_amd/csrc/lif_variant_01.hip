@@ -4,7 +4,4 @@
 
 namespace lsm_lif {
 lif_fn_t pick_lif_01(int sl, int wpc) { return pick_sl<false, true>(sl, wpc); }
-#if LSM_STAMP
-LSM_DEFINE_STAMP_READER(read_lif_stamps_01)
-#endif
 }  // namespace lsm_lif

@@ -4,7 +4,4 @@
 
 namespace lsm_lif {
 lif_fn_t pick_lif_10(int sl, int wpc) { return pick_sl<true, false>(sl, wpc); }
-#if LSM_STAMP
-LSM_DEFINE_STAMP_READER(read_lif_stamps_10)
-#endif
 }  // namespace lsm_lif

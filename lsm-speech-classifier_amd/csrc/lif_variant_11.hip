@@ -4,7 +4,4 @@
 
 namespace lsm_lif {
 lif_fn_t pick_lif_11(int sl, int wpc) { return pick_sl<true, true>(sl, wpc); }
-#if LSM_STAMP
-LSM_DEFINE_STAMP_READER(read_lif_stamps_11)
-#endif
 }  // namespace lsm_lif

@@ -15,10 +15,6 @@
 
 namespace {
 
-#ifndef LSM_MEL_ABLATE
-#define LSM_MEL_ABLATE 0    // diagnostic builds only (WRONG results): 1 = no FFT passes, 2 = no mel projection (every filter gets
-#endif                      // its first bin), 4 = no unpack / power (profiles/r05_mel_power_parts.txt: where the kernel's time goes)
-
 constexpr int NFFT = 2048;
 constexpr int N2 = NFFT / 2;                 // the real frame is transformed as N2 complex points
 constexpr int NBINS = NFFT / 2 + 1;
@@ -136,54 +132,49 @@ __device__ __forceinline__ void mel_frame_wave(const MelArgs &a, double2 *z, con
         const double2 wn = *reinterpret_cast<const double2 *>(window + 2 * n);
         u[s] = make_double2(wn.x * v0, wn.y * v1);
     }
-    if (!(LSM_MEL_ABLATE & 1)) {
-        constexpr double C1 = 0.92387953251128673848, S1 = 0.38268343236508978178, H = 0.70710678118654752440;
-        // p = 1: i = lane, k = 0, j = 16 lane
-        bfly16(u);
+    constexpr double C1 = 0.92387953251128673848, S1 = 0.38268343236508978178, H = 0.70710678118654752440;
+    // p = 1: i = lane, k = 0, j = 16 lane
+    bfly16(u);
 #pragma unroll
-        for (int s = 0; s < 16; ++s) z[zpad(16 * lane + (s >> 2) + 4 * (s & 3))] = u[s];
-        mel_wave_fence();
-        // p = 16: i = lane, k = lane mod 16, j = (lane - k) 16 + k; twiddles W_256^(q k) = W_2048^(8 q k)
+    for (int s = 0; s < 16; ++s) z[zpad(16 * lane + (s >> 2) + 4 * (s & 3))] = u[s];
+    mel_wave_fence();
+    // p = 16: i = lane, k = lane mod 16, j = (lane - k) 16 + k; twiddles W_256^(q k) = W_2048^(8 q k)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) u[s] = z[zpad(lane + 64 * s)];
-        {
-            const double2 w3 = cmul(wb2, wb1), w5 = cmul(wb4, wb1), w6 = cmul(wb4, wb2), w7 = cmul(wb4, w3);
-            u[1] = cmul(u[1], wb1); u[2] = cmul(u[2], wb2); u[3] = cmul(u[3], w3); u[4] = cmul(u[4], wb4);
-            u[5] = cmul(u[5], w5); u[6] = cmul(u[6], w6); u[7] = cmul(u[7], w7); u[8] = cmul(u[8], wb8);
-            u[9] = cmul(u[9], cmul(wb8, wb1)); u[10] = cmul(u[10], cmul(wb8, wb2)); u[11] = cmul(u[11], cmul(wb8, w3));
-            u[12] = cmul(u[12], cmul(wb8, wb4)); u[13] = cmul(u[13], cmul(wb8, w5)); u[14] = cmul(u[14], cmul(wb8, w6));
-            u[15] = cmul(u[15], cmul(wb8, w7));
+    for (int s = 0; s < 16; ++s) u[s] = z[zpad(lane + 64 * s)];
+    {
+        const double2 w3 = cmul(wb2, wb1), w5 = cmul(wb4, wb1), w6 = cmul(wb4, wb2), w7 = cmul(wb4, w3);
+        u[1] = cmul(u[1], wb1); u[2] = cmul(u[2], wb2); u[3] = cmul(u[3], w3); u[4] = cmul(u[4], wb4);
+        u[5] = cmul(u[5], w5); u[6] = cmul(u[6], w6); u[7] = cmul(u[7], w7); u[8] = cmul(u[8], wb8);
+        u[9] = cmul(u[9], cmul(wb8, wb1)); u[10] = cmul(u[10], cmul(wb8, wb2)); u[11] = cmul(u[11], cmul(wb8, w3));
+        u[12] = cmul(u[12], cmul(wb8, wb4)); u[13] = cmul(u[13], cmul(wb8, w5)); u[14] = cmul(u[14], cmul(wb8, w6));
+        u[15] = cmul(u[15], cmul(wb8, w7));
+    }
+    bfly16(u);
+    mel_wave_fence();                       // every lane has read its points before any is overwritten
+    const int j = (lane - k) * 16 + k;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) z[zpad(j + 16 * ((s >> 2) + 4 * (s & 3)))] = u[s];
+    mel_wave_fence();
+    // p = 256, radix 4: butterflies i = lane + 64 c, k = i, j = i; twiddles W_1024^(q k) = W_1024^(q lane) W_16^(q c)
+#pragma unroll
+    for (int s = 0; s < 16; ++s) u[s] = z[zpad(lane + 64 * s)];
+    mel_wave_fence();
+    const double2 w16[10] = {make_double2(1.0, 0.0), make_double2(C1, -S1), make_double2(H, -H), make_double2(S1, -C1),
+                             make_double2(0.0, -1.0), make_double2(0.0, 0.0), make_double2(-H, -H), make_double2(0.0, 0.0),
+                             make_double2(0.0, 0.0), make_double2(-C1, S1)};        // W_16^m for m = q c
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int kk = lane + 64 * c;
+        if (c == 0) {
+            u[4] = cmul(u[4], wc1); u[8] = cmul(u[8], wc2); u[12] = cmul(u[12], wc3);
+        } else {
+            u[c + 4] = cmul(u[c + 4], cmul(wc1, w16[c]));
+            u[c + 8] = cmul(u[c + 8], cmul(wc2, w16[2 * c]));
+            u[c + 12] = cmul(u[c + 12], cmul(wc3, w16[3 * c]));
         }
-        bfly16(u);
-        mel_wave_fence();                       // every lane has read its points before any is overwritten
-        const int j = (lane - k) * 16 + k;
+        bfly4(u[c], u[c + 4], u[c + 8], u[c + 12]);
 #pragma unroll
-        for (int s = 0; s < 16; ++s) z[zpad(j + 16 * ((s >> 2) + 4 * (s & 3)))] = u[s];
-        mel_wave_fence();
-        // p = 256, radix 4: butterflies i = lane + 64 c, k = i, j = i; twiddles W_1024^(q k) = W_1024^(q lane) W_16^(q c)
-#pragma unroll
-        for (int s = 0; s < 16; ++s) u[s] = z[zpad(lane + 64 * s)];
-        mel_wave_fence();
-        const double2 w16[10] = {make_double2(1.0, 0.0), make_double2(C1, -S1), make_double2(H, -H), make_double2(S1, -C1),
-                                 make_double2(0.0, -1.0), make_double2(0.0, 0.0), make_double2(-H, -H), make_double2(0.0, 0.0),
-                                 make_double2(0.0, 0.0), make_double2(-C1, S1)};        // W_16^m for m = q c
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int kk = lane + 64 * c;
-            if (c == 0) {
-                u[4] = cmul(u[4], wc1); u[8] = cmul(u[8], wc2); u[12] = cmul(u[12], wc3);
-            } else {
-                u[c + 4] = cmul(u[c + 4], cmul(wc1, w16[c]));
-                u[c + 8] = cmul(u[c + 8], cmul(wc2, w16[2 * c]));
-                u[c + 12] = cmul(u[c + 12], cmul(wc3, w16[3 * c]));
-            }
-            bfly4(u[c], u[c + 4], u[c + 8], u[c + 12]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) z[zpad(kk + 256 * r)] = u[c + 4 * r];
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) z[zpad(lane + 64 * s)] = u[s];
+        for (int r = 0; r < 4; ++r) z[zpad(kk + 256 * r)] = u[c + 4 * r];
     }
     mel_wave_fence();
     // The 1025 power values go where the points were (`pw` aliases `z`): every lane forms its seventeen first, then they are stored.
@@ -192,7 +183,7 @@ __device__ __forceinline__ void mel_frame_wave(const MelArgs &a, double2 *z, con
     for (int i = 0; i <= 16; ++i) {
         const int f = lane + 64 * i;
         pv[i] = 0.0f;
-        if (!(LSM_MEL_ABLATE & 4) && (i < 16 || lane == 0)) {
+        if (i < 16 || lane == 0) {
             const double2 zk = z[zpad(f & (N2 - 1))];
             const double2 zr = z[zpad((N2 - f) & (N2 - 1))];
             const double2 E = make_double2(0.5 * (zk.x + zr.x), 0.5 * (zk.y - zr.y));    // (Zk + conj Zr)/2
@@ -216,7 +207,7 @@ __device__ __forceinline__ void mel_frame_wave(const MelArgs &a, double2 *z, con
         float acc = 0.0f;
         if (m < n_mels) {
             const float *row = basis + (size_t)m * NBINS;
-            const int h = (LSM_MEL_ABLATE & 2) ? lo[m] + 1 : hi[m];
+            const int h = hi[m];
             int f = lo[m] + q;
             for (; f + 28 < h; f += 32) {       // eight terms at a time, their loads together; the additions keep their order
                 float r[8], pq[8];
@@ -418,10 +409,6 @@ LSM_API int lsm_mel_spikes_f32(const float *audio, int n_clips, int n_samples, i
     // (101) 0.30 / 0.90; the three split launches 0.28 / 0.33.  A batch that gives every other CU a clip takes the whole
     // clip per workgroup (best throughput when launches overlap), smaller batches 32 frames (more workgroups).
     int fpw = n_clips >= 128 ? n_frames : 32;
-#if LSM_EXPERIMENT_HOOKS
-    static const int fpw_env = [] { const char *e = getenv("LSM_MEL_FRAMES_PER_WG"); return e ? atoi(e) : 0; }();
-    if (fpw_env >= 1) fpw = fpw_env;
-#endif
     fpw = fpw > n_frames ? n_frames : fpw;
     a.frames_per_wg = fpw;
     // The per-clip arrival counters are zeroed HERE, on the launch stream (4 bytes per clip; a memset node when captured): the

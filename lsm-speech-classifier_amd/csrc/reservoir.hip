@@ -9,6 +9,8 @@
 #include <climits>
 #include <cstdint>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <vector>
 
 using lsm_lif::LifArgs;
@@ -22,22 +24,6 @@ lif_fn_t pick_kernel(int sl, int wpc, bool inreg, bool seglds)
     if (inreg) return seglds ? lsm_lif::pick_lif_11(sl, wpc) : lsm_lif::pick_lif_10(sl, wpc);
     return seglds ? lsm_lif::pick_lif_01(sl, wpc) : lsm_lif::pick_lif_00(sl, wpc);
 }
-
-#if LSM_STAMP
-}  // namespace
-namespace lsm_lif {
-int read_lif_stamps(int unit, unsigned long long *o, int r)
-{
-    switch (unit) {
-    case 0: return read_lif_stamps_00(o, r);
-    case 1: return read_lif_stamps_01(o, r);
-    case 2: return read_lif_stamps_10(o, r);
-    default: return read_lif_stamps_11(o, r);
-    }
-}
-}  // namespace lsm_lif
-namespace {
-#endif
 
 struct Variant {            // per waves-per-clip layout
     int wpc = 0, sl = 0, einw = 0;
@@ -491,12 +477,7 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
 
     // coloured bit positions for the input masks of the dense kernel (one assignment per reservoir)
     std::vector<uint8_t> inperm;
-#if LSM_EXPERIMENT_HOOKS
-    static const bool no_incol = [] { const char *e = getenv("LSM_DENSE_NO_INCOL"); return e && atoi(e) != 0; }();
-#else
-    constexpr bool no_incol = false;
-#endif
-    const bool coloured = !no_incol && colour_input_channels(N, C, in_tgt, in_fanout, &inperm);
+    const bool coloured = colour_input_channels(N, C, in_tgt, in_fanout, &inperm);
     if (coloured && (rc = upload(&h->inperm, inperm))) { free_reservoir(h); return rc; }
     h->leak_uniform = true;
     h->leak_u = leak[0];
@@ -664,12 +645,7 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                         return rc;
                     }
                     // INMASK form of the kernel (lif_ring.h): per-neuron channel masks in registers instead of the entry drive
-#if LSM_EXPERIMENT_HOOKS
-                    static const bool no_ring_mask = [] { const char *e = getenv("LSM_RING_NO_INMASK"); return e && atoi(e) != 0; }();
-#else
-                    constexpr bool no_ring_mask = false;
-#endif
-                    if (!no_ring_mask && C <= 128 && h->leak_uniform && strided && ql <= 2) {
+                    if (C <= 128 && h->leak_uniform && strided && ql <= 2) {
                         std::vector<uint32_t> im((size_t)npad * 4, 0u);
                         bool distinct = true;
                         for (int c = 0; c < C; ++c)
@@ -691,14 +667,9 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                 // w, w+wpc, ...: the residues must survive the ring's wrap (2*NQ % wpc == 0), a window must not touch more
                 // than wpc blocks, a wave at most four blocks (8 neurons per lane).  The kernel counts the input drive from
                 // per-neuron channel masks only: C <= 128.
-#if LSM_EXPERIMENT_HOOKS
-                static const bool no_pairs = [] { const char *e = getenv("LSM_RING_NO_PAIRS"); return e && atoi(e) != 0; }();
-#else
-                constexpr bool no_pairs = false;
-#endif
                 const int NB = 2 * NQ;
                 const int pwpcs[3] = {4, 8, 16};
-                for (int vi = 0; vi < 3 && !no_pairs && C <= 128; ++vi) {
+                for (int vi = 0; vi < 3 && C <= 128; ++vi) {
                     const int wpc = pwpcs[vi];
                     std::vector<uint32_t> rptr;
                     std::vector<uint2> rem;
@@ -791,12 +762,7 @@ static bool ring_inreg(const RingVariant &rv)
 {
     // the wave's input map stays in registers when it is one block (8 registers) AND the layout has few neurons per
     // lane: with three or four quads per wave the extra registers would cost a wave per SIMD
-    bool inreg = rv.einw <= lsm_lif::RING_ENT_BLOCK * lsm_lif::RING_ENT_REG_BLOCKS && rv.ql <= 2 && rv.strided;
-#if LSM_EXPERIMENT_HOOKS
-    static const bool no_inreg = [] { const char *e = getenv("LSM_RING_NO_INREG"); return e && atoi(e) != 0; }();
-    if (no_inreg) inreg = false;
-#endif
-    return inreg;
+    return rv.einw <= lsm_lif::RING_ENT_BLOCK * lsm_lif::RING_ENT_REG_BLOCKS && rv.ql <= 2 && rv.strided;
 }
 
 
@@ -842,8 +808,24 @@ static size_t pair_lds_bytes(const lsm_reservoir *h, const PairVariant &v, int T
     // dump words, float32 accumulators, 64 scratch words per wave, two step lists of bytes, block counts, feature
     // accumulators, the clip's input bits
     return (size_t)lsm_lif::PAIR_DUMP_BYTES + npad * 4 + (size_t)v.wpc * 256 + 2 * npad +
-           (size_t)lsm_lif::PAIR_WCNT_WORDS * 4 + (LSM_PAIR_LEAN ? 0 : (size_t)h->n_out * 16) + (size_t)T * cw * 4 +
-           (size_t)LSM_PAIR_LDS_PAD;
+           (size_t)lsm_lif::PAIR_WCNT_WORDS * 4 + (size_t)h->n_out * 16 + (size_t)T * cw * 4;
+}
+
+// Static LDS bytes of a pair-block kernel, asked once per kernel for the life of the process.  lif_pair.h addresses LDS
+// by absolute byte address, which holds only while the kernel has no static LDS (its dynamic LDS then starts at 0).
+static int pair_static_lds(const void *fn, size_t *bytes)
+{
+    static std::mutex mu;
+    static std::map<const void *, size_t> known;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = known.find(fn);
+    if (it == known.end()) {
+        hipFuncAttributes fa;
+        LSM_CHECK_HIP(hipFuncGetAttributes(&fa, fn));
+        it = known.emplace(fn, fa.sharedSizeBytes).first;
+    }
+    *bytes = it->second;
+    return LSM_OK;
 }
 
 // Pair-block layout for a batch: the requested waves per clip, else the fewest waves (every wave repeats the per-row work).
@@ -1100,6 +1082,15 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                                  : pv->bl == 3 ? lsm_lif::pick_pair_3(pv->wpc, inmask, leakv)
                                                : lsm_lif::pick_pair_4(pv->wpc, inmask, leakv);
         LSM_REQUIRE(pfn != nullptr, "no pair-block ring kernel for BL=%d WPC=%d", pv->bl, pv->wpc);
+        size_t static_lds = 0;
+        const int src = pair_static_lds(reinterpret_cast<const void *>(pfn), &static_lds);
+        if (src != LSM_OK) return src;
+        if (static_lds != 0) {
+            lsm_set_error("pair-block ring kernel BL=%d WPC=%d has %zu bytes of static LDS: its row loop addresses LDS "
+                          "absolutely and needs its dynamic LDS to start at byte 0 (defective build)", pv->bl, pv->wpc,
+                          static_lds);
+            return LSM_ERR_UNSUPPORTED;
+        }
         lsm_lif::PairArgs r;
         r.N = h->N; r.C = h->C; r.T = n_steps; r.B = n_clips;
         r.n_out = h->n_out; r.CW = (int)cw;
@@ -1149,13 +1140,8 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
     }
     const Variant *v = plan.v;
     if (plan.kernel == 2) {
-        // the reference's refractory period (2 steps) counts down in scalar lane masks (lif_dense.h, REFM);
-        // LSM_DENSE_NO_REFM (diagnostic builds) keeps the vector-register countdown for same-box A/B runs
-        bool refm = h->refractory == lsm_lif::DENSE_REFM_REFRACTORY;
-#if LSM_EXPERIMENT_HOOKS
-        static const bool no_refm = [] { const char *e = getenv("LSM_DENSE_NO_REFM"); return e && atoi(e) != 0; }();
-        if (no_refm) refm = false;
-#endif
+        // the reference's refractory period (2 steps) counts down in scalar lane masks (lif_dense.h, REFM)
+        const bool refm = h->refractory == lsm_lif::DENSE_REFM_REFRACTORY;
         lsm_lif::dense_fn_t dfn = v->inmask       ? (v->incol ? lsm_lif::pick_dense_3(v->sl, v->wpc, refm)
                                                               : lsm_lif::pick_dense_2(v->sl, v->wpc, refm))
                                   : lif_inreg(*v) ? lsm_lif::pick_dense_1(v->sl, v->wpc, refm)
@@ -1314,23 +1300,4 @@ int lsm_reservoir_kernel_in_use(const lsm_reservoir *h)
     RunPlan p;
     if (make_plan(h, 1, 400, 0, &p) != LSM_OK) return want_ring(h) ? 3 : (use_dense(h) ? 2 : 1);
     return p.kernel;
-}
-
-// Diagnostic builds (-DLSM_STAMP=1) only: per-phase cycle sums of the LIF kernel; zeros otherwise.
-extern "C" __attribute__((visibility("default")))
-int lsm_debug_lif_stamps(unsigned long long *out8, int reset)
-{
-    for (int k = 0; k < 8; ++k) out8[k] = 0;
-#if LSM_STAMP
-    for (int q = 0; q < 6; ++q) {                 // the four sparse-kernel units + the dense kernel's INMODE-2 and -3 units
-        unsigned long long part[8];
-        int rc = q < 4 ? lsm_lif::read_lif_stamps(q, part, reset)
-                       : (q == 4 ? lsm_lif::read_lif_stamps_d2(part, reset) : lsm_lif::read_lif_stamps_d3(part, reset));
-        if (rc) return rc;
-        for (int k = 0; k < 8; ++k) out8[k] += part[k];
-    }
-#else
-    (void)reset;
-#endif
-    return LSM_OK;
 }

@@ -38,9 +38,6 @@ __device__ __forceinline__ T block_reduce(T v, bool is_max, T *scratch)
     return r;
 }
 
-#ifndef LSM_SPK_ABLATE
-#define LSM_SPK_ABLATE 0    // diagnostic builds only (WRONG results): 1 = no minimum/maximum pass, 2 = no values / comparison bits,
-#endif                      // 4 = no latches, 8 = no raster bytes (profiles/r05_mel_wave_per_frame.txt)
 constexpr int SPK_ROWS = 64;               // spectrogram rows (filters) a workgroup encodes at a time
 
 // LDS bytes of spec_to_spikes_body: 128 of reduction scratch (sixteen waves) + two bit arrays (value above the on-threshold / below the
@@ -75,7 +72,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
     T mx = -INFINITY, mn = INFINITY;
     int nan_seen = 0;
 #pragma unroll 8
-    for (int i = tid; i < ((LSM_SPK_ABLATE & 1) ? 0 : n); i += blockDim.x) {
+    for (int i = tid; i < n; i += blockDim.x) {
         const T v = db[i];
         mx = v > mx ? v : mx;
         mn = v < mn ? v : mn;
@@ -102,7 +99,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
         const int rows = min(SPK_ROWS, F - r0);
         // ---- 1. values and comparison bits: a wave takes (row, 64 time bins) pieces four at a time, their loads together ----
         const int nh = (Tb + 63) >> 6, npiece = rows * nh;
-        for (int p0 = wv; p0 < ((LSM_SPK_ABLATE & 2) ? 0 : npiece); p0 += 4 * nwv) {
+        for (int p0 = wv; p0 < npiece; p0 += 4 * nwv) {
             T x0[4], x1[4];
             double w0[4], w1[4];
             bool two[4];
@@ -166,7 +163,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
         __syncthreads();
         // ---- 2. the latches: where above and below exclude each other (off <= on), active' = above | (active & ~below) is the
         //      carry chain of an addition: generate = above, propagate = ~below, so a word of 32 time bins is one 64-bit add ----
-        for (int i = tid; i < ((LSM_SPK_ABLATE & 4) ? 0 : rows * nq); i += blockDim.x) {
+        for (int i = tid; i < rows * nq; i += blockDim.x) {
             uint32_t *o = onb + (size_t)i * W;
             const uint32_t *d = offb + (size_t)i * W;
             uint64_t active = 0u;
@@ -191,7 +188,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
         }
         __syncthreads();
         // ---- 3. raster bytes of the group's rows (create_pure_redundancy: output row c reads filter row c / redundancy) ----
-        if (dst && !(LSM_SPK_ABLATE & 8)) {
+        if (dst) {
             const int c0 = r0 * a.redundancy, nrow = rows * a.redundancy;
             if ((row_bytes & 3) == 0) {
                 const int rw = row_bytes / 4;

@@ -233,6 +233,39 @@ def test_a_stale_library_is_refused_with_a_rebuild_message(monkeypatch):
         _lib.load()
 
 
+def test_every_switch_of_the_sources_is_one_a_build_may_set():
+    """Every LSM_* macro that csrc/ tests with #if / #ifdef / #ifndef / defined() is either written by build.py itself
+    (the version and the build id) or a diagnostic switch build() accepts: no code arm that only an unchecked -D reaches."""
+    from lsm_speech_classifier_amd import build
+    csrc = os.path.join(ROOT, "lsm-speech-classifier_amd", "csrc")
+    tested = set()
+    for name in os.listdir(csrc):
+        with open(os.path.join(csrc, name)) as f:
+            for line in f:
+                m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+                if m:
+                    tested |= set(re.findall(r"\b(LSM_[A-Z0-9_]+)\b", m.group(1)))
+    assert "LSM_PAIR_PHASES" in tested
+    assert tested <= {"LSM_VERSION_NUMBER", "LSM_BUILD_ID_STRING"} | build.ALLOWED_DEFINES, sorted(tested)
+
+
+def test_build_refuses_unknown_and_in_tree_diagnostic_defines(monkeypatch, tmp_path):
+    """build() takes only ALLOWED_DEFINES, and only for a library outside the package: the in-tree library is always a
+    product build.  Both refusals come before any compiler runs."""
+    from lsm_speech_classifier_amd import build
+
+    def no_compiler(*a, **k):
+        raise AssertionError("a compiler ran")
+    monkeypatch.setattr(build.subprocess, "check_call", no_compiler)
+    with pytest.raises(ValueError, match="not a switch"):
+        build.build(force=True, defines=["LSM_PAIR_ABLATE=1"], out=str(tmp_path / "x.so"))
+    with pytest.raises(ValueError, match="outside"):
+        build.build(force=True, defines=["LSM_PAIR_PHASES=1"])
+    with pytest.raises(ValueError, match="inside"):
+        build.build(force=True, defines=["LSM_PAIR_PHASES=1"], out=os.path.join(build.PKG_DIR, "diag.so"))
+    assert not os.path.exists(os.path.join(build.PKG_DIR, "diag.so"))
+
+
 def test_train_test_split_permutation_is_the_pinned_one(golden_dir):
     """extract_lsm_features.py:160-162 splits with train_test_split(test_size=.2, random_state=42,
     stratify=y) and the first <= 500 training clips set w_critico (:40) -- the permutation is pinned for the class
