@@ -167,7 +167,14 @@ typedef struct lsm_reservoir lsm_reservoir;
  * wiring (built on the host per SPEC.md §2) to the current device.  All arrays are HOST memory.
  *   csc_ptr (N+1), csc_post (nnz, ascending within a column), csc_w (nnz): synapses grouped by
  *           PRESYNAPTIC neuron j;  leak (N);  in_tgt (n_channels, in_fanout) target neurons of
- *           each input channel;  out_idx (n_out) strictly ascending output neurons. */
+ *           each input channel;  out_idx (n_out) strictly ascending output neurons.
+ * Limits: num_neurons <= 8192, n_channels <= 65535, n_out <= num_neurons, every in_tgt entry in [0, num_neurons).
+ *   refractory     any value >= 0; stored as min(refractory, 65535), which is the same simulation for the at most 65535
+ *                  steps of a run (a neuron that fires is held through the end of the clip either way) and fits the
+ *                  16-bit countdown of the ring-row kernels
+ *   burst_isi_max  any int (an interval counts as a burst when it is <= burst_isi_max: none does for a value <= 0)
+ *   in_tgt         a channel may name a neuron more than once: every entry adds w_in.  Such a map is served from the
+ *                  input-entry lists (no channel masks), so it has no pair-block layout (set_kernel mode 5 is refused). */
 int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                          const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w,
                          const float *leak, const int32_t *in_tgt, int in_fanout, float w_in,
@@ -208,7 +215,9 @@ int lsm_reservoir_kernel_in_use(const lsm_reservoir *h);
  *                    the GPU with other kernels of an overlapped pipeline; else 1, 2, 4, 8 or 16
  * Fails (LSM_ERR, "no ... layout") when no layout's per-clip LDS image fits a CU's 160 KB: roughly
  * 10*N + 16*n_out + n_steps*ceil(n_channels/32)*4 bytes for ring rows (e.g. N = 8000 with more than ~4500 output
- * neurons); every BASELINE configuration fits (N = 8000, n_out = 3200, 256 channels: 145 KB). */
+ * neurons); every BASELINE configuration fits (N = 8000, n_out = 3200, 256 channels: 145 KB).  n_steps <= 65535 (the
+ * feature records hold spike counts and times in 16 bits); the LDS image grows by 4 * ceil(n_channels / 32) bytes per step,
+ * so long clips of many channels are refused the same way well before that (lsm_reservoir_plan tells without launching). */
 int lsm_reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
                       const int32_t *key_ids, int n_keys, float *features_out,
                       uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,

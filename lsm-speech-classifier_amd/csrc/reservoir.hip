@@ -421,6 +421,10 @@ int lsm_debug_pair_layout(int num_neurons, const int32_t *csc_ptr, const int32_t
     return bl;
 }
 
+// Any refractory period >= 0 is accepted and stored as min(refractory, 65535): a run has at most 65535 steps, so a neuron
+// that fires at step t is held through the end of the clip either way -- the same simulation -- and the ring and pair kernels
+// keep the countdown in the upper 16 bits of a register (lif_ring.h, lif_pair.h).  An input map may name a neuron more than
+// once in one channel (every entry counts); such a map has no channel-mask form, hence no pair-block layout.
 extern "C" __attribute__((visibility("default")))
 int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                          const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w,
@@ -456,7 +460,7 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
         LSM_REQUIRE(in_tgt[e] >= 0 && in_tgt[e] < N, "in_tgt[%d] out of range", e);
 
     lsm_reservoir *h = new lsm_reservoir();
-    h->N = N; h->C = C; h->n_out = n_out; h->refractory = refractory;
+    h->N = N; h->C = C; h->n_out = n_out; h->refractory = std::min(refractory, 65535);
     h->burst_isi_max = burst_isi_max; h->theta = theta; h->w_in = w_in; h->nnz = nnz;
     (void)hipGetDevice(&h->device);
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) {
@@ -742,8 +746,9 @@ int lsm_reservoir_set_kernel(lsm_reservoir *h, int mode)
     LSM_REQUIRE(mode >= 0 && mode <= 6, "mode must be 0 (auto), 1 (sparse), 2 (dense), 3 (ring), 4 (ring, contiguous quads), "
                 "5 (ring, pair blocks) or 6 (ring, quads)");
     LSM_REQUIRE(mode < 3 || has_ring(h), "this reservoir has no ring-row format (not ring-like, or too small)");
-    LSM_REQUIRE(mode != 5 || has_pairs(h), "this reservoir has no pair-block ring layout (needs at most 128 channels, a block "
-                "count that is a multiple of 4, 8 or 16 waves and a window of at most that many blocks)");
+    LSM_REQUIRE(mode != 5 || has_pairs(h), "this reservoir has no pair-block ring layout (needs at most 128 channels, an input map "
+                "that names no neuron twice in one channel, a block count that is a multiple of 4, 8 or 16 waves and a window of "
+                "at most that many blocks)");
     if (mode == 2) {                       // an explicit request builds the table a ring-served reservoir deferred
         const int rc = ensure_dense_rows(h);
         if (rc) return rc;
