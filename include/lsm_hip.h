@@ -174,7 +174,8 @@ typedef struct lsm_reservoir lsm_reservoir;
  *                  16-bit countdown of the ring-row kernels
  *   burst_isi_max  any int (an interval counts as a burst when it is <= burst_isi_max: none does for a value <= 0)
  *   in_tgt         a channel may name a neuron more than once: every entry adds w_in.  Such a map is served from the
- *                  input-entry lists (no channel masks), so it has no pair-block layout (set_kernel mode 5 is refused). */
+ *                  input-entry lists (no channel masks or bit planes), so it has no pair-block layout (set_kernel mode 5
+ *                  is refused). */
 int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                          const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w,
                          const float *leak, const int32_t *in_tgt, int in_fanout, float w_in,
@@ -190,8 +191,11 @@ int lsm_reservoir_destroy(lsm_reservoir *h);
  * 3 = ring rows (refused when the reservoir is not ring-like or has fewer than ~700 neurons), 4 = ring rows
  * restricted to the layouts with contiguous quad ownership (tests; 3 prefers the strided ones), 5 = ring rows in pair
  * blocks only (128-neuron blocks, two neurons per lane; refused when the reservoir has no pair-block layout: more than
- * 128 channels, or no block count and window that fit 4, 8 or 16 waves), 6 = ring rows in quads only (never pair
- * blocks).  All produce bit-identical results (SPEC.md §3).  num_neurons <= 8192. */
+ * 256 channels; 129 to 256 channels without bit positions in which the channels feeding one neuron differ mod 32 (e.g.
+ * more than 32 channels onto one neuron); a channel that names a neuron twice; or no block count and window that fit 4, 8
+ * or 16 waves), 6 = ring rows in quads only (never pair blocks).  Modes 0 and 3 take pair blocks where they were measured
+ * faster: at least three blocks per wave and at most 128 channels; above 128 channels pair blocks run by name (5) only
+ * (DESIGN.md 3c).  All produce bit-identical results (SPEC.md §3).  num_neurons <= 8192. */
 int lsm_reservoir_set_kernel(lsm_reservoir *h, int mode);
 
 /* The kernel lsm_reservoir_run would launch for this handle now: 1 sparse, 2 dense rows, 3 ring rows -- for the
@@ -259,11 +263,17 @@ int lsm_reservoir_row_request_bytes(const lsm_reservoir *h, int n_clips, int n_s
 /* How the planned kernel forms the input drive (introspection for tests): dense rows 0 = input-map entries streamed
  * from global memory + LDS atomics, 1 = entries in registers + LDS atomics, 2 = per-neuron channel masks, four
  * popcounts, 3 = channel masks at coloured bit positions, one popcount (C <= 128 and an assignment exists in which
- * the channels feeding one neuron differ mod 32); ring rows 10 = packed entries streamed, 11 = packed entries in
- * registers, 12 / 13 = per-neuron channel masks at natural / coloured positions (C <= 128, every neuron the same leak
+ * the channels feeding one neuron differ mod 32); ring rows 10 = packed entries streamed, 11 = entries in registers: in
+ * quads the wave's packed input-map entries, in pair blocks (129 to 256 channels) one (bit position -> row word) entry per
+ * coloured bit of a neuron, held as a position mask and three bit planes and resolved by bitwise selects,
+ * 12 / 13 = per-neuron channel masks at natural / coloured positions (C <= 128, every neuron the same leak
  * coefficient, strided quad ownership with at most two quads per wave), 14 / 15 = the same masks in the pair-block form of the
  * ring rows (C <= 128; any leak coefficients); sparse kernel 20. */
 int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip);
+
+/* Which form of the ring rows the planned kernel is (the same decision as lsm_reservoir_plan): 0 = the planned kernel is
+ * not ring rows, 1 = quads with contiguous ownership, 2 = quads with strided ownership, 3 = pair blocks; < 0 on error. */
+int lsm_reservoir_ring_form(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip);
 
 /* Host-only (no GPU, no HIP call): the ring-window table, the pair-block lists ({LDS byte offset of the target's accumulator,
  * weight bits} per entry) and the 16-byte row records lsm_reservoir_create would build for these CSC arrays and `wpc` (4, 8, 16)
@@ -274,6 +284,17 @@ int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, i
 int lsm_debug_pair_layout(int num_neurons, const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w, int wpc,
                           unsigned long long band_addr, unsigned long long rem_addr, long *band_floats, long *n_list_entries,
                           int *pitch_bytes, float *band_out, uint32_t *rem_out, uint32_t *rec_out);
+
+/* Host-only (no GPU, no HIP call): what lsm_reservoir_create would upload for the pair-block kernel's input drive with `wpc`
+ * (4, 8, 16) waves per clip: perm_out[n_channels], the bit position of every channel in a step's input bit row (word * 32 +
+ * colour; the channel's own number where the masks keep the natural positions), and words_out[4 * NPAD], NPAD = 256 *
+ * ceil(num_neurons / 256), four words per neuron: up to 128 channels the channel masks (bit `position`), from 129 to 256
+ * channels {posmask, P0, P1, P2} -- bit p of posmask: a channel at a position = p mod 32 feeds the neuron; bit p of Pj: bit j
+ * of that channel's word.  Either array may be NULL.  Returns 1 (masks, natural positions), 2 (masks, coloured positions) or
+ * 3 (bit planes); 0 when the map has no such form (more than 256 channels, no colouring above 128, a channel naming a neuron
+ * twice) or the blocks do not share out over `wpc` waves; < 0 on a bad argument. */
+int lsm_debug_pair_inputs(int num_neurons, int n_channels, const int32_t *in_tgt, int in_fanout, int wpc, uint8_t *perm_out,
+                          uint32_t *words_out);
 
 #ifdef __cplusplus
 }

@@ -56,8 +56,10 @@ _SIGS = {
                                    C.POINTER(c_int), C.POINTER(c_int), C.POINTER(C.c_long)]),
     "lsm_reservoir_row_request_bytes": (c_int, [c_void, c_int, c_int, c_int, C.POINTER(C.c_double)]),
     "lsm_reservoir_input_mode": (c_int, [c_void, c_int, c_int, c_int]),
+    "lsm_reservoir_ring_form": (c_int, [c_void, c_int, c_int, c_int]),
     "lsm_debug_pair_layout": (c_int, [c_int, c_void, c_void, c_void, c_int, C.c_ulonglong, C.c_ulonglong,
                                       C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(c_int), c_void, c_void, c_void]),
+    "lsm_debug_pair_inputs": (c_int, [c_int, c_int, c_void, c_int, c_int, c_void, c_void]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

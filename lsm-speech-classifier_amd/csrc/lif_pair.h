@@ -25,7 +25,8 @@
 // address-path time of every request -- not the accumulator read-modify-write through LDS, not residency.
 // Arithmetic, order of the float32 additions (rows ascending, a target gets a row's weight from the window or from
 // the list, never both, the other term is +0.0) and results are those of lif_ring.h: bit-identical to the oracle.
-// The kernel exists for the input drive counted from per-neuron channel masks (C <= 128: the reference's 128 filters), with
+// The kernel exists for the input drive counted from four registers per neuron: channel masks (C <= 128: the reference's 128
+// filters) or, for 129..256 channels, one (position -> row word) entry per coloured bit in bit planes (INMASK 3 below), with
 // one leak coefficient for every neuron (its default) or one per neuron in registers (LEAKV: --leak-variance-divisor);
 // other reservoirs keep lif_ring.h.
 #pragma once
@@ -52,7 +53,7 @@ struct PairArgs {
     const uint2 *rem;          // list entries {LDS byte offset of the target's accumulator, weight bits}, (row, wave) major
     const float *leak;         // LEAKV: (NPAD) leak coefficient per neuron, neuron order (else null: leak_u for every neuron)
     const int *oslot;          // (NPAD) output slot or -1, neuron order
-    const uint32_t *inmask;    // (NPAD, 4) input-channel bit mask per neuron
+    const uint32_t *inmask;    // (NPAD, 4) input-channel bit mask per neuron; INMASK 3: {posmask, P0, P1, P2} (pair_input_planes)
     const uint8_t *inperm;     // coloured positions: (C) bit position of channel c in the input bit row, else null
     int n_keys;
     int key_ids[8];
@@ -163,8 +164,41 @@ __device__ __forceinline__ uint32_t pair_input_count(const uint32_t (&im)[4], co
     return __popc(im[0] & rowbits[0]) + __popc(im[1] & rowbits[1]) + __popc(im[2] & rowbits[2]) + __popc(im[3] & rowbits[3]);
 }
 
+// The same count for 129..256 channels (INMASK 3), still from four registers per neuron.  The channels sit at coloured
+// positions word * 32 + colour of the step's bit row (at most 8 words), and the channels feeding one neuron all differ in
+// colour: a neuron has at most ONE channel per bit position p, and all it needs to know about it is the word it sits in.
+// im = {posmask, P0, P1, P2}: bit p of posmask = a channel of colour p feeds the neuron, bit p of plane Pj = bit j of that
+// channel's word.  A bitwise 8:1 select of the row words by the planes (v_bfi_b32: (S & A) | (~S & B)) puts that channel's
+// row bit at position p; seven selects, one and, one popcount per neuron and step.  A gfx9 VALU instruction reads at most
+// one scalar register, so of the two row words of a first-level select the ODD one stays in a vector register and the even
+// one (rowlo[q] = word 2q) is wave-uniform in a scalar register: four vector registers for the row, as the masks have --
+// eight made the LEAKV form of four blocks per wave spill.
+__device__ __forceinline__ uint32_t pair_bfi(uint32_t sel, uint32_t one, uint32_t zero)
+{
+    uint32_t d;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(sel), "v"(one), "v"(zero));
+    return d;
+}
+__device__ __forceinline__ uint32_t pair_bfi_s(uint32_t sel, uint32_t one, uint32_t zero_uniform)
+{
+    uint32_t d;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(sel), "v"(one), "s"(zero_uniform));
+    return d;
+}
+__device__ __forceinline__ uint32_t pair_input_planes(const uint32_t (&im)[4], const uint32_t (&rowhi)[4], const uint32_t (&rowlo)[4])
+{
+    const uint32_t a0 = pair_bfi_s(im[1], rowhi[0], rowlo[0]);
+    const uint32_t a1 = pair_bfi_s(im[1], rowhi[1], rowlo[1]);
+    const uint32_t b0 = pair_bfi(im[2], a1, a0);
+    const uint32_t a2 = pair_bfi_s(im[1], rowhi[2], rowlo[2]);
+    const uint32_t a3 = pair_bfi_s(im[1], rowhi[3], rowlo[3]);
+    const uint32_t b1 = pair_bfi(im[2], a3, a2);
+    return __popc(pair_bfi(im[3], b1, b0) & im[0]);
+}
+
 // BL: blocks (128 neurons, 2 per lane) per wave; WPC: waves per clip; INMASK: 1 = natural bit positions of the input
-// channels, 2 = coloured positions (lif_dense.h, INMODE 3).
+// channels, 2 = coloured positions (lif_dense.h, INMODE 3), 3 = coloured positions of 129..256 channels in bit planes
+// (pair_input_planes; 5..8 row words).
 // LEAKV: a leak coefficient per neuron in registers (the reference's --leak-variance-divisor, extract_lsm_features.py:174,
 // 182-183) instead of one for all (its default).
 template <int BL, int WPC, int INMASK, bool LEAKV = false>
@@ -212,7 +246,7 @@ void lif_pair_kernel(const PairArgs a)
                 if (v == 0) continue;
                 const int c = (q * 4) / T;
                 const int t0 = (q * 4) - c * T;
-                const int pc = INMASK == 2 ? (int)a.inperm[c] : c;      // the channel's place in the bit row
+                const int pc = INMASK >= 2 ? (int)a.inperm[c] : c;      // the channel's place in the bit row
                 const uint32_t bit = 1u << (pc & 31);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
@@ -223,7 +257,7 @@ void lif_pair_kernel(const PairArgs a)
             for (int q = tid; q < nb; q += NT)
                 if (clip[q]) {
                     const int c = q / T;
-                    const int pc = INMASK == 2 ? (int)a.inperm[c] : c;
+                    const int pc = INMASK >= 2 ? (int)a.inperm[c] : c;
                     atomicOr(&bits[(q - c * T) * CW + (pc >> 5)], 1u << (pc & 31));
                 }
         }
@@ -234,7 +268,7 @@ void lif_pair_kernel(const PairArgs a)
     float v[SL];
     float lam[LEAKV ? SL : 1];
     uint32_t oref[SL];
-    uint32_t im[SL][4];                             // channels 0..127 feeding my neuron r
+    uint32_t im[SL][4];                             // channels 0..127 feeding my neuron r (INMASK 3: its bit planes)
     const float lam_u = a.leak_u;
 #pragma unroll
     for (int q = 0; q < BL; ++q) {
@@ -457,8 +491,19 @@ void lif_pair_kernel(const PairArgs a)
         // this step's input bit row (wave-uniform).  The input counts and the leak are computed in the update: computing them
         // while the step's first loads are in the air was 1-2 % SLOWER at cfg4 (the other waves of the CU fill those waits
         // already; profiles/r05_pair_rows_in_flight.txt)
+        // INMASK 3: 5..8 words; rowbits = the odd words, rowlo = the even ones, uniform.  No set bit of a neuron's posmask
+        // selects a word past CW (a channel's word is < CW), so those words need no zero-fill: they are read from inside the
+        // image (the last word of the clip at the latest) and whatever they hold is masked away.
         uint32_t rowbits[4];
-        if (CW == 4) {
+        uint32_t rowlo[INMASK == 3 ? 4 : 1];
+        if (INMASK == 3) {
+            const int w0 = t * CW, wlast = T * CW - 1;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                rowlo[k] = __builtin_amdgcn_readfirstlane(bits[2 * k < 5 ? w0 + 2 * k : min(w0 + 2 * k, wlast)]);
+                rowbits[k] = bits[2 * k + 1 < 5 ? w0 + 2 * k + 1 : min(w0 + 2 * k + 1, wlast)];
+            }
+        } else if (CW == 4) {
             const uint4 q4 = *reinterpret_cast<const uint4 *>(bits + t * 4);
             rowbits[0] = q4.x; rowbits[1] = q4.y; rowbits[2] = q4.z; rowbits[3] = q4.w;
         } else {
@@ -481,7 +526,9 @@ void lif_pair_kernel(const PairArgs a)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int r = 2 * q + h;
-                const uint32_t nn = pair_input_count<INMASK>(im[r], rowbits);
+                uint32_t nn;
+                if constexpr (INMASK == 3) nn = pair_input_planes(im[r], rowbits, rowlo);
+                else nn = pair_input_count<INMASK>(im[r], rowbits);
                 ci[h] = ci[h] + w_in * (float)nn;          // SPEC.md §3: input term after the recurrent sum
                 const float m = (LEAKV ? lam[r] : lam_u) * v[r];
                 const float d = v[r] - m;
@@ -602,10 +649,20 @@ pair_fn_t pick_pair(int wpc, int inmask, bool leakv)
     return inmask == 2 ? pick_pair_wpc<BL, 2, false>(wpc) : pick_pair_wpc<BL, 1, false>(wpc);
 }
 
-// one definition per translation unit lif_pair_<bl>.hip
+template <int BL>
+pair_fn_t pick_pair_wide(int wpc, bool leakv)
+{
+    return leakv ? pick_pair_wpc<BL, 3, true>(wpc) : pick_pair_wpc<BL, 3, false>(wpc);
+}
+
+// one definition per translation unit lif_pair_<bl>.hip (INMASK 1, 2) and lif_pair_wide_<bl>.hip (INMASK 3)
 pair_fn_t pick_pair_1(int wpc, int inmask, bool leakv);
 pair_fn_t pick_pair_2(int wpc, int inmask, bool leakv);
 pair_fn_t pick_pair_3(int wpc, int inmask, bool leakv);
 pair_fn_t pick_pair_4(int wpc, int inmask, bool leakv);
+pair_fn_t pick_pair_wide_1(int wpc, bool leakv);
+pair_fn_t pick_pair_wide_2(int wpc, bool leakv);
+pair_fn_t pick_pair_wide_3(int wpc, bool leakv);
+pair_fn_t pick_pair_wide_4(int wpc, bool leakv);
 
 }  // namespace lsm_lif

@@ -1,0 +1,7 @@
+// Pair-block ring LIF kernel instantiations for 129..256 input channels (INMASK 3: bit planes) with 4 block(s)
+// (= 8 neurons per lane) per wave (see lif_pair.h).
+#include "lif_pair.h"
+
+namespace lsm_lif {
+pair_fn_t pick_pair_wide_4(int wpc, bool leakv) { return pick_pair_wide<4>(wpc, leakv); }
+}  // namespace lsm_lif

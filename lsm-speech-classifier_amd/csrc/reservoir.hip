@@ -57,8 +57,9 @@ struct PairVariant {        // per waves-per-clip layout of the pair-block ring 
     uint2 *rem = nullptr;            // {LDS byte offset of the accumulator, weight bits}, (row, wave) major
     int *oslot = nullptr;
     float *leak = nullptr;           // (npad) leak coefficients when they differ between neurons, else null
-    uint32_t *inmask = nullptr;      // (npad, 4) input-channel masks in neuron order
-    bool incol = false;              // the masks use the coloured bit positions of lsm_reservoir::inperm
+    uint32_t *inmask = nullptr;      // (npad, 4) input-channel masks in neuron order, or {posmask, P0, P1, P2} (inform 3)
+    int inform = 0;                  // the kernel's INMASK: 1 masks at natural positions, 2 at the coloured positions of
+                                     // lsm_reservoir::inperm, 3 bit planes over coloured positions (129..256 channels)
 };
 
 }  // namespace
@@ -102,7 +103,7 @@ struct lsm_reservoir {
                             // (lif_pair.h), 6 ring rows in quads only (lif_ring.h, either ownership)
     Variant var[5];         // wpc = 1, 2, 4, 8, 16 (wpc == 0: not available)
     RingVariant rvar[8];    // wpc = 2, 4, 8, 16, contiguous [0..3] and strided [4..7] quad ownership
-    PairVariant pvar[3];    // wpc = 4, 8, 16: pair blocks (lif_pair.h), uniform leak and C <= 128 only
+    PairVariant pvar[3];    // wpc = 4, 8, 16: pair blocks (lif_pair.h), C <= 256 (above 128 only with a colouring)
 };
 
 static int free_reservoir(lsm_reservoir *h)
@@ -196,17 +197,19 @@ static int upload(T **dst, const std::vector<T> &src)
     return LSM_OK;
 }
 
-// Bit positions for the input channels of the dense kernel's INMODE 3 (C <= 128): position p = word * 32 + bit with
+// Bit positions for the input channels of the dense kernel's INMODE 3 (C <= 128) and of the pair-block kernel's bit
+// planes (C <= 256, lif_pair.h INMASK 3): position p = word * 32 + bit with
 // word < ceil(C / 32), such that the channels feeding ONE neuron all have different `bit`s.  Then the words
 // (mask_w & row_w) of a neuron have no set bit in common and popcount(m0&r0) + ... + popcount(m3&r3) =
 // popcount((m0&r0) | (m1&r1) | (m2&r2) | (m3&r3)): one v_and, three v_and_or and one v_bcnt per neuron and step
 // instead of four v_and, four v_bcnt and an add.  This is an equitable colouring of the channels' conflict graph
 // (two channels conflict when they share a target) with 32 colours of ceil(C/32) places each; greedy by conflict
-// degree with a one-move repair finds one for every input map tried (N = 256..4000, C = 32..128).  Returns false
-// when it does not: the caller keeps the natural positions (INMODE 2).
+// degree with a one-move repair finds one for every input map tried (N = 256..4000, C = 32..128; N = 1024..8000,
+// C = 129..256, where C = 256 forces exactly 8 channels per colour).  Returns false when it does not: the caller keeps
+// the natural positions (INMODE 2; above 128 channels there is then no pair-block layout).
 static bool colour_input_channels(int N, int C, const int32_t *in_tgt, int in_fanout, std::vector<uint8_t> *perm)
 {
-    if (C > 128) return false;
+    if (C > 256) return false;
     const int cap = (C + 31) / 32;
     std::vector<std::vector<int>> chans_of(N);
     for (int c = 0; c < C; ++c)
@@ -421,10 +424,69 @@ int lsm_debug_pair_layout(int num_neurons, const int32_t *csc_ptr, const int32_t
     return bl;
 }
 
+// The pair-block kernel's four input words per neuron (lif_pair.h), (npad, 4) in neuron order, for channels at the positions
+// `inperm` (coloured) or at their natural ones.  Returns the kernel's INMASK form: 1 = channel masks at the natural positions
+// (C <= 128, no colouring), 2 = masks at coloured positions (C <= 128), 3 = {posmask, P0, P1, P2} over coloured positions
+// (129..256 channels: bit p of posmask = a channel of colour p feeds the neuron, bit p of Pj = bit j of that channel's
+// word), 0 = no such form: more than 256 channels, more than 128 without a colouring, or a channel that names a neuron
+// twice (the words hold one bit per (channel, neuron) pair).  Host arithmetic only.
+static int pair_input_words(int C, const int32_t *in_tgt, int in_fanout, int npad, bool coloured,
+                            const std::vector<uint8_t> &inperm, std::vector<uint32_t> *im)
+{
+    if (C > 256 || (C > 128 && !coloured)) return 0;
+    im->assign((size_t)npad * 4, 0u);
+    for (int c = 0; c < C; ++c)
+        for (int d = 0; d < in_fanout; ++d) {
+            const int tgt = in_tgt[(size_t)c * in_fanout + d];
+            const int pc = coloured ? inperm[c] : c;          // bit position of channel c in the input bit row
+            const uint32_t bit = 1u << (pc & 31);
+            uint32_t *m = im->data() + (size_t)tgt * 4;
+            if (C <= 128) {
+                if (m[pc >> 5] & bit) return 0;
+                m[pc >> 5] |= bit;
+            } else {
+                // channels that share a neuron differ in colour: a bit met twice is the SAME channel naming the neuron again
+                if (m[0] & bit) return 0;
+                m[0] |= bit;
+                for (int j = 0; j < 3; ++j)
+                    if (((pc >> 5) >> j) & 1) m[1 + j] |= bit;
+            }
+        }
+    return C > 128 ? 3 : (coloured ? 2 : 1);
+}
+
+// Host-only (no GPU, no HIP call): the channel positions (perm_out[n_channels]; the identity where the masks keep the natural
+// positions) and the per-neuron input words (words_out[4 * NPAD], NPAD = 256 * ceil(num_neurons / 256)) lsm_reservoir_create
+// would upload for the pair-block kernel with `wpc` (4, 8, 16) waves per clip.  Either output may be null.  Returns the
+// input form (pair_input_words: 1, 2 or 3), 0 when the map has none or the blocks do not divide into 1..4 for each of `wpc`
+// waves, < 0 on a bad argument.  tests/test_pair_inputs_host.py decodes the words back into the map, on the CPU.
+extern "C" __attribute__((visibility("default")))
+int lsm_debug_pair_inputs(int num_neurons, int n_channels, const int32_t *in_tgt, int in_fanout, int wpc, uint8_t *perm_out,
+                          uint32_t *words_out)
+{
+    LSM_REQUIRE(num_neurons >= 1 && num_neurons <= 8192 && n_channels >= 1 && n_channels <= 65535 && in_tgt &&
+                in_fanout >= 1 && in_fanout <= num_neurons, "lsm_debug_pair_inputs: bad argument");
+    LSM_REQUIRE(wpc == 4 || wpc == 8 || wpc == 16, "lsm_debug_pair_inputs: wpc must be 4, 8 or 16");
+    const int N = num_neurons, C = n_channels;
+    for (size_t e = 0; e < (size_t)C * in_fanout; ++e)
+        LSM_REQUIRE(in_tgt[e] >= 0 && in_tgt[e] < N, "lsm_debug_pair_inputs: in_tgt[%zu] out of range", e);
+    const int NB = 2 * ((N + 255) / 256);
+    if (NB % wpc != 0 || NB / wpc > 4) return 0;
+    std::vector<uint8_t> inperm;
+    const bool coloured = colour_input_channels(N, C, in_tgt, in_fanout, &inperm);
+    std::vector<uint32_t> im;
+    const int form = pair_input_words(C, in_tgt, in_fanout, NB * 128, coloured, inperm, &im);
+    if (!form) return 0;
+    if (perm_out)
+        for (int c = 0; c < C; ++c) perm_out[c] = coloured ? inperm[c] : (uint8_t)c;
+    if (words_out) std::memcpy(words_out, im.data(), im.size() * sizeof(uint32_t));
+    return form;
+}
+
 // Any refractory period >= 0 is accepted and stored as min(refractory, 65535): a run has at most 65535 steps, so a neuron
 // that fires at step t is held through the end of the clip either way -- the same simulation -- and the ring and pair kernels
 // keep the countdown in the upper 16 bits of a register (lif_ring.h, lif_pair.h).  An input map may name a neuron more than
-// once in one channel (every entry counts); such a map has no channel-mask form, hence no pair-block layout.
+// once in one channel (every entry counts); such a map has no channel-mask or bit-plane form, hence no pair-block layout.
 extern "C" __attribute__((visibility("default")))
 int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                          const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w,
@@ -479,7 +541,7 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
     std::vector<uint32_t> rowptr(csc_ptr, csc_ptr + N + 1);
     if ((rc = upload(&h->rowptr, rowptr))) { free_reservoir(h); return rc; }
 
-    // coloured bit positions for the input masks of the dense kernel (one assignment per reservoir)
+    // coloured bit positions for the input masks of the dense kernel and the pair blocks (one assignment per reservoir)
     std::vector<uint8_t> inperm;
     const bool coloured = colour_input_channels(N, C, in_tgt, in_fanout, &inperm);
     if (coloured && (rc = upload(&h->inperm, inperm))) { free_reservoir(h); return rc; }
@@ -670,10 +732,12 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                 // Pair blocks (lif_pair.h): the same windows shared out in 128-neuron blocks, wave w owning the blocks
                 // w, w+wpc, ...: the residues must survive the ring's wrap (2*NQ % wpc == 0), a window must not touch more
                 // than wpc blocks, a wave at most four blocks (8 neurons per lane).  The kernel counts the input drive from
-                // per-neuron channel masks only: C <= 128.
+                // four registers per neuron only (pair_input_words): C <= 128, or C <= 256 with a colouring.
                 const int NB = 2 * NQ;
                 const int pwpcs[3] = {4, 8, 16};
-                for (int vi = 0; vi < 3 && C <= 128; ++vi) {
+                std::vector<uint32_t> im;
+                const int inform = pair_input_words(C, in_tgt, in_fanout, NB * 128, coloured, inperm, &im);
+                for (int vi = 0; vi < 3 && inform != 0; ++vi) {
                     const int wpc = pwpcs[vi];
                     std::vector<uint32_t> rptr;
                     std::vector<uint2> rem;
@@ -695,17 +759,6 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                     pair_records(N, wpc, geo, rptr, band_a, rem_a, &rec);
                     std::vector<int> os(npad, -1);
                     for (int o = 0; o < n_out; ++o) os[out_idx[o]] = o;
-                    std::vector<uint32_t> im((size_t)npad * 4, 0u);
-                    bool distinct = true;
-                    for (int c = 0; c < C; ++c)
-                        for (int d = 0; d < in_fanout; ++d) {
-                            const int tgt = in_tgt[(size_t)c * in_fanout + d];
-                            const int pc = coloured ? inperm[c] : c;
-                            uint32_t &word = im[(size_t)tgt * 4 + (pc >> 5)];
-                            distinct = distinct && !(word & (1u << (pc & 31)));
-                            word |= 1u << (pc & 31);
-                        }
-                    if (!distinct) { (void)hipFree(v.rem); v.rem = nullptr; continue; }
                     if ((rc = upload(&v.rec, rec)) || (rc = upload(&v.oslot, os)) || (rc = upload(&v.inmask, im))) {
                         free_reservoir(h);
                         return rc;
@@ -715,7 +768,7 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
                         for (int i = 0; i < N; ++i) lk[i] = leak[i];
                         if ((rc = upload(&v.leak, lk))) { free_reservoir(h); return rc; }
                     }
-                    v.incol = coloured;
+                    v.inform = inform;
                     v.wpc = wpc; v.bl = bl; v.n_rem = rptr.back();
                 }
             }
@@ -746,9 +799,10 @@ int lsm_reservoir_set_kernel(lsm_reservoir *h, int mode)
     LSM_REQUIRE(mode >= 0 && mode <= 6, "mode must be 0 (auto), 1 (sparse), 2 (dense), 3 (ring), 4 (ring, contiguous quads), "
                 "5 (ring, pair blocks) or 6 (ring, quads)");
     LSM_REQUIRE(mode < 3 || has_ring(h), "this reservoir has no ring-row format (not ring-like, or too small)");
-    LSM_REQUIRE(mode != 5 || has_pairs(h), "this reservoir has no pair-block ring layout (needs at most 128 channels, an input map "
-                "that names no neuron twice in one channel, a block count that is a multiple of 4, 8 or 16 waves and a window of "
-                "at most that many blocks)");
+    LSM_REQUIRE(mode != 5 || has_pairs(h), "this reservoir has no pair-block ring layout (needs at most 256 channels -- above 128 "
+                "with bit positions in which the channels feeding one neuron differ mod 32, so at most 32 channels per neuron --, "
+                "an input map that names no neuron twice in one channel, a block count that is a multiple of 4, 8 or 16 waves and "
+                "a window of at most that many blocks)");
     if (mode == 2) {                       // an explicit request builds the table a ring-served reservoir deferred
         const int rc = ensure_dense_rows(h);
         if (rc) return rc;
@@ -833,6 +887,12 @@ static int pair_static_lds(const void *fn, size_t *bytes)
     return LSM_OK;
 }
 
+// Whether auto and "ring" take the bit-plane form of the pair blocks (129..256 channels) where the rule below allows it.
+// The form has not been timed against the quads yet (profiles/pair_wide_channels.txt: the comparison exp/pair_wide_channels.py
+// makes is not on record), and the default changes only on a measured gain beyond the run-to-run spread: until then such
+// reservoirs keep the kernel they had, and the pair blocks are there by name (mode 5).
+constexpr bool PAIR_WIDE_AUTO = false;
+
 // Pair-block layout for a batch: the requested waves per clip, else the fewest waves (every wave repeats the per-row work).
 static const PairVariant *choose_pair(const lsm_reservoir *h, int T, int requested)
 {
@@ -846,6 +906,10 @@ static const PairVariant *choose_pair(const lsm_reservoir *h, int T, int request
         // but N = 2048 (2 blocks, 8 waves) 2.46 against 2.19: with few neurons per lane the per-wave work per row dominates
         // and the quads' four fat waves win.
         if (h->mode != 5 && v.bl < 3 && has_ring(h)) continue;
+        // Above 128 channels (bit planes, inform 3): by name only while PAIR_WIDE_AUTO is off, and never by default where the
+        // layout needs 16 waves (N = 8000 with 256 filters: the quads run at 99 % of the gather ceiling there, 16 waves repeat
+        // the per-row work of 8: N = 8000 strided quads, 8 waves 29.0 ms, 16 waves 36.8 ms).
+        if (h->mode != 5 && v.inform == 3 && (v.wpc == 16 || !PAIR_WIDE_AUTO)) continue;
         return &v;
     }
     return nullptr;
@@ -1080,12 +1144,18 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
     }
     if (plan.kernel == 3 && plan.pv) {
         const PairVariant *pv = plan.pv;
-        const int inmask = pv->incol ? 2 : 1;
+        const int inmask = pv->inform;
         const bool leakv = pv->leak != nullptr;
-        lsm_lif::pair_fn_t pfn = pv->bl == 1 ? lsm_lif::pick_pair_1(pv->wpc, inmask, leakv)
+        lsm_lif::pair_fn_t pfn = inmask == 3 ? (pv->bl == 1 ? lsm_lif::pick_pair_wide_1(pv->wpc, leakv)
+                                                : pv->bl == 2 ? lsm_lif::pick_pair_wide_2(pv->wpc, leakv)
+                                                : pv->bl == 3 ? lsm_lif::pick_pair_wide_3(pv->wpc, leakv)
+                                                              : lsm_lif::pick_pair_wide_4(pv->wpc, leakv))
+                                 : pv->bl == 1 ? lsm_lif::pick_pair_1(pv->wpc, inmask, leakv)
                                  : pv->bl == 2 ? lsm_lif::pick_pair_2(pv->wpc, inmask, leakv)
                                  : pv->bl == 3 ? lsm_lif::pick_pair_3(pv->wpc, inmask, leakv)
                                                : lsm_lif::pick_pair_4(pv->wpc, inmask, leakv);
+        // (bit planes: 5..8 row words, and the whole input image is T * cw words -- pair_lds_bytes)
+        LSM_REQUIRE(inmask != 3 || (cw >= 5 && cw <= 8), "pair-block bit planes with %zu row words", cw);
         LSM_REQUIRE(pfn != nullptr, "no pair-block ring kernel for BL=%d WPC=%d", pv->bl, pv->wpc);
         size_t static_lds = 0;
         const int src = pair_static_lds(reinterpret_cast<const void *>(pfn), &static_lds);
@@ -1102,7 +1172,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
         r.refractory = h->refractory; r.burst_isi_max = h->burst_isi_max;
         r.theta = h->theta; r.w_in = h->w_in; r.leak_u = h->leak_u;
         r.raster = spikes_u8; r.band = h->band; r.rec = pv->rec; r.rem = pv->rem;
-        r.oslot = pv->oslot; r.leak = pv->leak; r.inmask = pv->inmask; r.inperm = pv->incol ? h->inperm : nullptr;
+        r.oslot = pv->oslot; r.leak = pv->leak; r.inmask = pv->inmask; r.inperm = pv->inform >= 2 ? h->inperm : nullptr;
         r.n_keys = n_keys;
         for (int k = 0; k < 8; ++k) r.key_ids[k] = k < n_keys ? key_ids[k] : 0;
         r.features = features_out; r.spike_matrix = spike_matrix_out; r.v_trace = v_trace_out;
@@ -1261,10 +1331,22 @@ int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, i
     if (h == nullptr) return LSM_ERR_ARG;
     RunPlan p;
     if (make_plan(h, n_clips, n_steps, waves_per_clip, &p) != LSM_OK) return LSM_ERR_UNSUPPORTED;
-    if (p.kernel == 3 && p.pv) return p.pv->incol ? 15 : 14;
+    if (p.kernel == 3 && p.pv) return p.pv->inform == 3 ? 11 : (p.pv->inform == 2 ? 15 : 14);
     if (p.kernel == 3) return p.rv->inmask ? (p.rv->incol ? 13 : 12) : (ring_inreg(*p.rv) ? 11 : 10);
     if (p.kernel == 1) return 20;
     return p.v->inmask ? (p.v->incol ? 3 : 2) : (lif_inreg(*p.v) ? 1 : 0);
+}
+
+// Which ring-row form the planned kernel is: 0 not ring rows, 1 quads with contiguous ownership, 2 strided quads (lif_ring.h),
+// 3 pair blocks (lif_pair.h).
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_ring_form(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip)
+{
+    if (h == nullptr) return LSM_ERR_ARG;
+    RunPlan p;
+    if (make_plan(h, n_clips, n_steps, waves_per_clip, &p) != LSM_OK) return LSM_ERR_UNSUPPORTED;
+    if (p.kernel != 3) return 0;
+    return p.pv ? 3 : (p.rv->strided ? 2 : 1);
 }
 
 extern "C" __attribute__((visibility("default")))

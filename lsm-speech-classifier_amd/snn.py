@@ -165,7 +165,7 @@ class SNN:
 
     # 'band': round-1 name of 'ring'; 'ring-contiguous': ring rows with contiguous quad ownership only (tests)
     # 'ring-pairs' / 'ring-quads': ring rows shared out in 128-neuron pair blocks (csrc/lif_pair.h) / in 256-neuron quads
-    # (csrc/lif_ring.h) only -- 'ring' takes pair blocks where the reservoir has them (tests, same-box A/B runs)
+    # (csrc/lif_ring.h) only -- 'ring' takes pair blocks where the reservoir has them and they pay (tests, same-box A/B runs)
     KERNEL_MODES = {"auto": 0, "sparse": 1, "dense": 2, "ring": 3, "band": 3, "ring-contiguous": 4, "ring-pairs": 5,
                     "ring-quads": 6}
 
@@ -187,7 +187,9 @@ class SNN:
     def plan(self, n_clips: int, n_steps: int, waves_per_clip: int = 0) -> dict:
         """What `run_batch` would launch for this batch: kernel, layout, LDS bytes per clip and the bytes of the
         weight table that kernel gathers from (`lsm_reservoir_plan`), plus the bytes one spike requests from it, mean
-        over the presynaptic neurons (`lsm_reservoir_row_request_bytes`)."""
+        over the presynaptic neurons (`lsm_reservoir_row_request_bytes`).  ``ring_form``: how ring rows are shared out --
+        ``"quads-contiguous"``, ``"quads"`` (strided ownership) or ``"pairs"`` (pair blocks) -- and ``None`` for the other
+        kernels (`lsm_reservoir_ring_form`)."""
         k, wpc, sl, lds, tab = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_long()
         _lib.check(self.lib.lsm_reservoir_plan(self._handle, n_clips, n_steps, waves_per_clip, C.byref(k),
                                                C.byref(wpc), C.byref(sl), C.byref(lds), C.byref(tab)),
@@ -198,7 +200,16 @@ class SNN:
         return {"kernel": {1: "sparse", 2: "dense", 3: "ring"}[k.value], "waves_per_clip": wpc.value,
                 "slots_per_lane": sl.value, "lds_bytes": lds.value, "table_bytes": tab.value,
                 "row_request_bytes": rb.value,
-                "input_mode": self._input_mode(n_clips, n_steps, waves_per_clip)}
+                "input_mode": self._input_mode(n_clips, n_steps, waves_per_clip),
+                "ring_form": self._ring_form(n_clips, n_steps, waves_per_clip)}
+
+    RING_FORMS = {0: None, 1: "quads-contiguous", 2: "quads", 3: "pairs"}
+
+    def _ring_form(self, n_clips: int, n_steps: int, waves_per_clip: int):
+        form = int(self.lib.lsm_reservoir_ring_form(self._handle, n_clips, n_steps, waves_per_clip))
+        if form < 0:
+            _lib.check(form, "lsm_reservoir_ring_form")
+        return self.RING_FORMS[form]
 
     def _input_mode(self, n_clips: int, n_steps: int, waves_per_clip: int) -> int:
         mode = int(self.lib.lsm_reservoir_input_mode(self._handle, n_clips, n_steps, waves_per_clip))
