@@ -19,7 +19,7 @@
 // when a producer has more than R spikes (its count says so) the consumers merge the per-wave lists for that
 // step instead (scalar prefix over the counts + compare chain).
 #pragma once
-#include "lif_kernel.h"
+#include "lif_common.h"
 
 // Row fetch, same-box A/B at 128 filters / 1000 neurons / 256 clips (profiles/r02_dense_row_chain_ab.txt): global loads.
 // MUBUF `buffer_load ... offen` with the row offset as scalar operand (no per-row vector address add) took 0.60 ms
@@ -96,6 +96,8 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     const int N = a.N, T = a.T, CW = a.CW;
 
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
+    // (zero_features_and_bits, pack_raster_bits and write_features of lif_common.h stay written out here: each call moves the
+    //  registers of some form -- <4, 16, 2, REFM> 115 VGPRs for 114, <16, *, 0> two SGPR spills fewer)
     for (int i = tid; i < NPAD; i += NT) icnt[i] = 0u;
     if (tid < 64) wcnt[tid] = 0u;
     for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
@@ -424,15 +426,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     // ---- epilogue: health statistics (/root/reference/extract_lsm_features.py:119-133 derives them from the
     //      (T, N) spike matrix; here they come from one flag per neuron and one count per wave), then
     //      SPEC.md §4 features from the integer accumulators (float64, then float32) ----
-    if (a.stats) {
-        atomicAdd(&wcnt[32], (uint32_t)__popc(hf));
-        if (lane == 0) atomicAdd(&wcnt[33], tot_spk);
-        __syncthreads();
-        if (tid == 0) {
-            a.stats[2 * b] = (int32_t)wcnt[32];
-            a.stats[2 * b + 1] = (int32_t)wcnt[33];
-        }
-    }
+    if (a.stats) write_stats(a.stats, b, &wcnt[32], &wcnt[33], hf, tot_spk, lane, tid);
     const int nf = a.n_keys * a.n_out;
     for (int idx = tid; idx < nf; idx += NT) {
         const int kq = idx / a.n_out;

@@ -34,11 +34,10 @@
 //      (LDS) touched only inside one "any lane of this wave fired" branch; one barrier.
 // No MFMA: the update is sparse and integer/byte dominated.
 #pragma once
-#include "lsm_common.h"
+#include "lif_common.h"
 
 namespace lsm_lif {
 
-constexpr int IN_REG_SLOTS = 6;       // input-map entries per lane kept in registers
 constexpr int SPIKE_GROUP = 8;        // spiking neurons whose synapse loads are in flight together
 
 struct LifArgs {
@@ -61,19 +60,6 @@ struct LifArgs {
     int32_t *stats;            // (B, 2) {neurons that fired at least once, spikes of the whole reservoir} or null
     const int32_t *order;      // (B) clip of workgroup g, or null (g): lsm_reservoir_run_ordered starts long clips first
 };
-
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int lane_rank(unsigned long long mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                          __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 // INREG: the wave's input-map entries fit IN_REG_SLOTS registers per lane (else they are streamed
 // from global memory every step: static addresses, L2-resident).
@@ -106,8 +92,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
     // ---- prologue: zero LDS state, stage tables, bit-pack the clip's raster time-major ----
     for (int i = tid; i < NPAD; i += NT) { acc[i] = 0.0f; icnt[i] = 0u; }
     if (tid < 32) wcnt[tid] = 0u;
-    for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
-    for (int i = tid; i < T * CW; i += NT) bits[i] = 0u;
+    zero_features_and_bits<NT>(feat, a.n_out, bits, T * CW, tid);
     if (SEGLDS) {
         for (int i = tid; i < N + 1; i += NT) lrow[i] = a.rowptr[i];
         const uint32_t *so32 = reinterpret_cast<const uint32_t *>(a.segoff);
@@ -115,6 +100,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         for (int i = tid; i < (N * (WPC + 1) + 1) / 2; i += NT) lso32[i] = so32[i];
     }
     __syncthreads();
+    // pack_raster_bits<NT, false> written out: the call changes this kernel's SGPR spills (SL >= 8 with the segments in LDS)
     {
         const uint8_t *clip = a.raster + (size_t)b * a.C * T;
         if ((T & 3) == 0) {
@@ -378,15 +364,8 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
 
     // ---- epilogue: health statistics (the count array is idle and all zero after the last step), then
     //      SPEC.md §4 features from the integer accumulators (float64, then float32) ----
-    if (a.stats) {
-        atomicAdd(&icnt[0], (uint32_t)__popc(hf));
-        if (lane == 0) atomicAdd(&icnt[1], tot_spk);
-        __syncthreads();
-        if (tid == 0) {
-            a.stats[2 * b] = (int32_t)icnt[0];
-            a.stats[2 * b + 1] = (int32_t)icnt[1];
-        }
-    }
+    if (a.stats) write_stats(a.stats, b, &icnt[0], &icnt[1], hf, tot_spk, lane, tid);
+    // write_features<NT> written out: with the call the one-slot forms allocate 101 registers instead of 77 (4 waves per SIMD, not 6)
     const int nf = a.n_keys * a.n_out;
     for (int idx = tid; idx < nf; idx += NT) {
         const int kq = idx / a.n_out;

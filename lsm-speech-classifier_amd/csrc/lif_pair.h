@@ -30,7 +30,7 @@
 // one leak coefficient for every neuron (its default) or one per neuron in registers (LEAKV: --leak-variance-divisor);
 // other reservoirs keep lif_ring.h.
 #pragma once
-#include "lif_kernel.h"
+#include "lif_common.h"
 
 namespace lsm_lif {
 
@@ -126,30 +126,6 @@ __device__ __forceinline__ uint32_t pair_scan_max(uint32_t v)
     return v;
 }
 
-// SPEC.md 4: one feature of an output neuron from its exact integers (n spikes, first / last spike time, S1 = sum of the
-// spike times, Q = sum of the squared inter-spike intervals, bursts), evaluated in float64 and rounded to float32.
-__device__ __forceinline__ float pair_feature_value(int key, int n, int bursts, int first, int last, uint32_t s1, uint32_t q2,
-                                                    int T)
-{
-    double val = 0.0;
-    switch (key) {
-    case 0: val = (double)n; break;
-    case 1: { const double p = (double)n / (double)T; val = p * (1.0 - p); } break;
-    case 2: val = n >= 1 ? (double)s1 / (double)n : 0.0; break;
-    case 3: val = n >= 1 ? (double)first : 0.0; break;
-    case 4: val = n >= 1 ? (double)last : 0.0; break;
-    case 5: val = n >= 2 ? (double)(last - first) / (double)(n - 1) : 0.0; break;
-    case 6:
-        if (n >= 2) {
-            const double m = (double)(last - first) / (double)(n - 1);
-            val = (double)q2 / (double)(n - 1) - m * m;
-        }
-        break;
-    default: val = (double)bursts; break;
-    }
-    return (float)val;
-}
-
 // spiking input channels of one neuron in this step: its channel masks against the step's input bit row
 template <int INMASK>
 __device__ __forceinline__ uint32_t pair_input_count(const uint32_t (&im)[4], const uint32_t (&rowbits)[4])
@@ -233,35 +209,9 @@ void lif_pair_kernel(const PairArgs a)
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
     for (int i = tid; i < (PAIR_DUMP_BYTES + NPAD * 4 + WPC * 256) / 4; i += NT) reinterpret_cast<uint32_t *>(smem)[i] = 0u;
     for (int i = tid; i < PAIR_WCNT_WORDS; i += NT) wcnt[i] = 0u;
-    for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
-    for (int i = tid; i < T * CW; i += NT) bits[i] = 0u;
+    zero_features_and_bits<NT>(feat, a.n_out, bits, T * CW, tid);
     __syncthreads();
-    {
-        const uint8_t *clip = a.raster + (size_t)b * a.C * T;
-        if ((T & 3) == 0) {
-            const uint32_t *clip4 = reinterpret_cast<const uint32_t *>(clip);
-            const int nd = a.C * T / 4;
-            for (int q = tid; q < nd; q += NT) {
-                const uint32_t v = clip4[q];
-                if (v == 0) continue;
-                const int c = (q * 4) / T;
-                const int t0 = (q * 4) - c * T;
-                const int pc = INMASK >= 2 ? (int)a.inperm[c] : c;      // the channel's place in the bit row
-                const uint32_t bit = 1u << (pc & 31);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if ((v >> (8 * k)) & 0xFFu) atomicOr(&bits[(t0 + k) * CW + (pc >> 5)], bit);
-            }
-        } else {
-            const int nb = a.C * T;
-            for (int q = tid; q < nb; q += NT)
-                if (clip[q]) {
-                    const int c = q / T;
-                    const int pc = INMASK >= 2 ? (int)a.inperm[c] : c;
-                    atomicOr(&bits[(q - c * T) * CW + (pc >> 5)], 1u << (pc & 31));
-                }
-        }
-    }
+    pack_raster_bits<NT, (INMASK >= 2)>(a.raster, a.inperm, b, a.C, T, CW, bits, tid);
 
     // my neurons: register r = 2*q + h  <->  neuron GB(q)*128 + lane*2 + h
     // oref[r] = (output slot + 1) | (refractory countdown << 16), as in lif_ring.h
@@ -603,26 +553,11 @@ void lif_pair_kernel(const PairArgs a)
     __builtin_amdgcn_s_setprio(0);
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
-    if (a.stats) {
-        atomicAdd(&wcnt[2 * PAIR_MAX_BLOCKS], (uint32_t)__popc(hf));
-        if (lane == 0) atomicAdd(&wcnt[2 * PAIR_MAX_BLOCKS + 1], tot_spk);
-        __syncthreads();
-        if (tid == 0) {
-            a.stats[2 * b] = (int32_t)wcnt[2 * PAIR_MAX_BLOCKS];
-            a.stats[2 * b + 1] = (int32_t)wcnt[2 * PAIR_MAX_BLOCKS + 1];
-        }
-    }
-    const int nf = a.n_keys * a.n_out;
-    for (int idx = tid; idx < nf; idx += NT) {
-        const int kq = idx / a.n_out;
-        const int o = idx - kq * a.n_out;
-        const uint4 f = feat[o];
-        const int n = (int)(f.x & 0xFFFFu), bursts = (int)(f.x >> 16);
-        const int first = (int)(f.y & 0xFFFFu), last = (int)(f.y >> 16);
-        a.features[(size_t)b * nf + idx] = pair_feature_value(a.key_ids[kq], n, bursts, first, last, f.z, f.w, T);
-    }
+    if (a.stats) write_stats(a.stats, b, &wcnt[2 * PAIR_MAX_BLOCKS], &wcnt[2 * PAIR_MAX_BLOCKS + 1], hf, tot_spk, lane, tid);
+    write_features<NT>(a.features, feat, a.key_ids, a.n_keys, a.n_out, b, T, tid);
 #if LSM_PAIR_PHASES
     __syncthreads();
+    const int nf = a.n_keys * a.n_out;
     float out_ = (float)rows_;
 #pragma unroll
     for (int k = 0; k < 7; ++k) out_ = lane == k ? (float)ph_[k] : out_;

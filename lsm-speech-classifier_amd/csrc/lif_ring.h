@@ -41,7 +41,7 @@
 // Rows are pipelined: P rows' loads are in flight while the oldest is applied, and the accumulator reads of row
 // m+1 are issued right after the writes of row m, ahead of the scalar work that launches row m+P.
 #pragma once
-#include "lif_kernel.h"
+#include "lif_common.h"
 
 namespace lsm_lif {
 
@@ -151,35 +151,9 @@ void lif_ring_kernel(const RingArgs a)
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
     for (int i = tid; i < RING_DUMP_WORDS + NPAD + CNT_WORDS; i += NT) reinterpret_cast<uint32_t *>(smem)[i] = 0u;
     for (int i = tid; i < 128; i += NT) wcnt[i] = 0u;
-    for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
-    for (int i = tid; i < T * CW; i += NT) bits[i] = 0u;
+    zero_features_and_bits<NT>(feat, a.n_out, bits, T * CW, tid);
     __syncthreads();
-    {
-        const uint8_t *clip = a.raster + (size_t)b * a.C * T;
-        if ((T & 3) == 0) {
-            const uint32_t *clip4 = reinterpret_cast<const uint32_t *>(clip);
-            const int nd = a.C * T / 4;
-            for (int q = tid; q < nd; q += NT) {
-                const uint32_t v = clip4[q];
-                if (v == 0) continue;
-                const int c = (q * 4) / T;
-                const int t0 = (q * 4) - c * T;
-                const int pc = INMASK == 2 ? (int)a.inperm[c] : c;      // the channel's place in the bit row
-                const uint32_t bit = 1u << (pc & 31);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if ((v >> (8 * k)) & 0xFFu) atomicOr(&bits[(t0 + k) * CW + (pc >> 5)], bit);
-            }
-        } else {
-            const int nb = a.C * T;
-            for (int q = tid; q < nb; q += NT)
-                if (clip[q]) {
-                    const int c = q / T;
-                    const int pc = INMASK == 2 ? (int)a.inperm[c] : c;
-                    atomicOr(&bits[(q - c * T) * CW + (pc >> 5)], 1u << (pc & 31));
-                }
-        }
-    }
+    pack_raster_bits<NT, INMASK == 2>(a.raster, a.inperm, b, a.C, T, CW, bits, tid);
 
     // my neurons: register r = 4*q + h  <->  neuron GQ(q)*256 + lane*4 + h
     // oref[r] = (output slot + 1) | (refractory countdown << 16): one register for both, "held" is one
@@ -548,40 +522,8 @@ void lif_ring_kernel(const RingArgs a)
     __builtin_amdgcn_s_setprio(0);
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
-    if (a.stats) {
-        atomicAdd(&wcnt[64], (uint32_t)__popc(hf));
-        if (lane == 0) atomicAdd(&wcnt[65], tot_spk);
-        __syncthreads();
-        if (tid == 0) {
-            a.stats[2 * b] = (int32_t)wcnt[64];
-            a.stats[2 * b + 1] = (int32_t)wcnt[65];
-        }
-    }
-    const int nf = a.n_keys * a.n_out;
-    for (int idx = tid; idx < nf; idx += NT) {
-        const int kq = idx / a.n_out;
-        const int o = idx - kq * a.n_out;
-        const uint4 f = feat[o];
-        const int n = (int)(f.x & 0xFFFFu), bursts = (int)(f.x >> 16);
-        const int first = (int)(f.y & 0xFFFFu), last = (int)(f.y >> 16);
-        double val = 0.0;
-        switch (a.key_ids[kq]) {
-        case 0: val = (double)n; break;
-        case 1: { const double p = (double)n / (double)T; val = p * (1.0 - p); } break;
-        case 2: val = n >= 1 ? (double)f.z / (double)n : 0.0; break;
-        case 3: val = n >= 1 ? (double)first : 0.0; break;
-        case 4: val = n >= 1 ? (double)last : 0.0; break;
-        case 5: val = n >= 2 ? (double)(last - first) / (double)(n - 1) : 0.0; break;
-        case 6:
-            if (n >= 2) {
-                const double m = (double)(last - first) / (double)(n - 1);
-                val = (double)f.w / (double)(n - 1) - m * m;
-            }
-            break;
-        default: val = (double)bursts; break;
-        }
-        a.features[(size_t)b * nf + idx] = (float)val;
-    }
+    if (a.stats) write_stats(a.stats, b, &wcnt[64], &wcnt[65], hf, tot_spk, lane, tid);
+    write_features<NT>(a.features, feat, a.key_ids, a.n_keys, a.n_out, b, T, tid);
 }
 
 typedef void (*ring_fn_t)(const RingArgs);

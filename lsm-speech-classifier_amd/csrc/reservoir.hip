@@ -1,6 +1,8 @@
-// Host side of the reservoir C ABI (include/lsm_hip.h): handle creation (CSC upload, per-layout
-// segment tables), layout choice and kernel launch.  The kernel itself lives in lif_kernel.h and
-// is instantiated by the four lif_variant_*.hip translation units.
+// Host side of the reservoir C ABI (include/lsm_hip.h): handle creation (CSC upload, per-layout tables), layout choice and
+// kernel launch.  The kernels live in lif_kernel.h (sparse CSC scatter), lif_dense.h (dense rows), lif_ring.h (ring rows in
+// quads) and lif_pair.h (ring rows in pair blocks), what they share in lif_common.h; the lif_variant_*, lif_dense_*,
+// lif_ring_*, lif_pair_* and lif_pair_wide_*.hip translation units instantiate them.
+#include "lif_kernel.h"
 #include "lif_dense.h"
 #include "lif_ring.h"
 #include "lif_pair.h"
@@ -10,6 +12,7 @@
 #include <cstdint>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -19,20 +22,32 @@ using lsm_lif::IN_REG_SLOTS;
 
 namespace {
 
+// The numbers of the ABI: lsm_reservoir_set_kernel's mode, and the kernel lsm_reservoir_plan / _kernel_in_use report.
+enum KernelMode { MODE_AUTO = 0, MODE_SPARSE = 1, MODE_DENSE = 2, MODE_RING = 3, MODE_RING_CONTIGUOUS = 4, MODE_RING_PAIRS = 5,
+                  MODE_RING_QUADS = 6 };
+enum PlannedKernel { KERNEL_NONE = 0, KERNEL_SPARSE = 1, KERNEL_DENSE = 2, KERNEL_RING = 3 };
+
 lif_fn_t pick_kernel(int sl, int wpc, bool inreg, bool seglds)
 {
     if (inreg) return seglds ? lsm_lif::pick_lif_11(sl, wpc) : lsm_lif::pick_lif_10(sl, wpc);
     return seglds ? lsm_lif::pick_lif_01(sl, wpc) : lsm_lif::pick_lif_00(sl, wpc);
 }
 
+// Owning device pointer: move-only, hipFree when it goes.  Every table of a handle is one.
+struct DevFree {
+    void operator()(void *p) const { (void)hipFree(p); }
+};
+template <typename T>
+using DevPtr = std::unique_ptr<T, DevFree>;
+
 struct Variant {            // per waves-per-clip layout
     int wpc = 0, sl = 0, einw = 0;
-    uint32_t *seg = nullptr;
-    uint16_t *segoff = nullptr;
-    float *leak = nullptr;
-    int *oslot = nullptr;
-    uint32_t *in_ent = nullptr;
-    uint32_t *inmask = nullptr;      // (npad, 4) input-channel masks, only when C <= 128 and sl <= 4
+    DevPtr<uint32_t> seg;
+    DevPtr<uint16_t> segoff;
+    DevPtr<float> leak;
+    DevPtr<int> oslot;
+    DevPtr<uint32_t> in_ent;
+    DevPtr<uint32_t> inmask;         // (npad, 4) input-channel masks, only when C <= 128 and sl <= 4
     bool incol = false;              // the masks use the coloured bit positions of lsm_reservoir::inperm (INMODE 3)
 };
 
@@ -40,12 +55,12 @@ struct RingVariant {        // per waves-per-clip layout of the ring-row kernel 
     int wpc = 0, ql = 0, einw = 0;
     bool strided = false;            // quad ownership: wave w owns quads w, w+wpc, ... (else w*ql .. w*ql+ql-1)
     size_t n_rem = 0;                // list entries (synapses outside the ring window)
-    uint32_t *rem_ptr = nullptr;     // (N*wpc + 1) first list entry of (row, wave)
-    uint2 *rem = nullptr;            // synapses outside the ring window: {LDS byte offset of the accumulator, weight bits}
-    float *leak = nullptr;
-    int *oslot = nullptr;
-    uint32_t *in_ent = nullptr;      // (wpc, einw) packed input-map entries (lsm_lif::ring_pack_entry)
-    uint32_t *inmask = nullptr;      // (npad, 4) input-channel masks in neuron order: the INMASK kernel form (C <= 128, uniform
+    DevPtr<uint32_t> rem_ptr;        // (N*wpc + 1) first list entry of (row, wave)
+    DevPtr<uint2> rem;               // synapses outside the ring window: {LDS byte offset of the accumulator, weight bits}
+    DevPtr<float> leak;
+    DevPtr<int> oslot;
+    DevPtr<uint32_t> in_ent;         // (wpc, einw) packed input-map entries (lsm_lif::ring_pack_entry)
+    DevPtr<uint32_t> inmask;         // (npad, 4) input-channel masks in neuron order: the INMASK kernel form (C <= 128, uniform
                                      // leak, strided ownership, <= 2 quads per wave), else null
     bool incol = false;              // the masks use the coloured bit positions of lsm_reservoir::inperm
 };
@@ -53,11 +68,11 @@ struct RingVariant {        // per waves-per-clip layout of the ring-row kernel 
 struct PairVariant {        // per waves-per-clip layout of the pair-block ring kernel (lif_pair.h)
     int wpc = 0, bl = 0;             // wave w owns the 128-neuron blocks w, w+wpc, ...: bl of them
     size_t n_rem = 0;                // list entries (synapses outside the ring window)
-    uint4 *rec = nullptr;            // (N*wpc) row records (lsm_lif::pair_record)
-    uint2 *rem = nullptr;            // {LDS byte offset of the accumulator, weight bits}, (row, wave) major
-    int *oslot = nullptr;
-    float *leak = nullptr;           // (npad) leak coefficients when they differ between neurons, else null
-    uint32_t *inmask = nullptr;      // (npad, 4) input-channel masks in neuron order, or {posmask, P0, P1, P2} (inform 3)
+    DevPtr<uint4> rec;               // (N*wpc) row records (lsm_lif::pair_record)
+    DevPtr<uint2> rem;               // {LDS byte offset of the accumulator, weight bits}, (row, wave) major
+    DevPtr<int> oslot;
+    DevPtr<float> leak;              // (npad) leak coefficients when they differ between neurons, else null
+    DevPtr<uint32_t> inmask;         // (npad, 4) input-channel masks in neuron order, or {posmask, P0, P1, P2} (inform 3)
     int inform = 0;                  // the kernel's INMASK: 1 masks at natural positions, 2 at the coloured positions of
                                      // lsm_reservoir::inperm, 3 bit planes over coloured positions (129..256 channels)
 };
@@ -82,64 +97,29 @@ struct lsm_reservoir {
     int device = 0;
     int cus = 0;            // compute units of that device
     size_t nnz = 0;
-    uint2 *syn = nullptr;
-    uint32_t *rowptr = nullptr;
-    float *wt = nullptr;    // dense rows by presynaptic neuron (N, ld), small reservoirs only
+    DevPtr<uint2> syn;
+    DevPtr<uint32_t> rowptr;
+    DevPtr<float> wt;       // dense rows by presynaptic neuron (N, ld), small reservoirs only
     int ld = 0;
     // ring rows (lif_ring.h): per presynaptic neuron the dense ring window from the 256-aligned start of
     // j-H up to j+H, plus per-layout lists of the synapses outside it
-    float *band = nullptr;
+    DevPtr<float> band;
     uint32_t band_pitch = 0;
     double band_bytes_sum = 0;       // sum over rows of the window bytes that exist (what a spike's window loads can touch)
     int band_h = 0, band_nq = 0, band_wsq = 0;
     // INMODE 3 of the dense kernel: bit position of every input channel in the step's input bit row such that the
     // channels feeding one neuron sit at different positions mod 32 (colour_input_channels); null when no such
     // assignment was found (then the masks keep the natural positions, INMODE 2)
-    uint8_t *inperm = nullptr;
+    DevPtr<uint8_t> inperm;
     bool leak_uniform = false;       // every neuron has the same leak coefficient (leak_u): the reference's default
     float leak_u = 0.0f;
-    int mode = 0;           // 0 auto, 1 sparse (CSC scatter through LDS), 2 dense rows, 3 ring rows,
-                            // 4 ring rows with contiguous quad ownership only (tests), 5 ring rows in pair blocks only
-                            // (lif_pair.h), 6 ring rows in quads only (lif_ring.h, either ownership)
+    KernelMode mode = MODE_AUTO;     // MODE_RING_CONTIGUOUS: ring rows with contiguous quad ownership only (tests);
+                                     // MODE_RING_PAIRS: pair blocks only (lif_pair.h); MODE_RING_QUADS: quads only (lif_ring.h,
+                                     // either ownership)
     Variant var[5];         // wpc = 1, 2, 4, 8, 16 (wpc == 0: not available)
     RingVariant rvar[8];    // wpc = 2, 4, 8, 16, contiguous [0..3] and strided [4..7] quad ownership
     PairVariant pvar[3];    // wpc = 4, 8, 16: pair blocks (lif_pair.h), C <= 256 (above 128 only with a colouring)
 };
-
-static int free_reservoir(lsm_reservoir *h)
-{
-    if (!h) return LSM_OK;
-    if (h->syn) (void)hipFree(h->syn);
-    if (h->rowptr) (void)hipFree(h->rowptr);
-    if (h->wt) (void)hipFree(h->wt);
-    if (h->band) (void)hipFree(h->band);
-    if (h->inperm) (void)hipFree(h->inperm);
-    for (auto &v : h->var) {
-        if (v.seg) (void)hipFree(v.seg);
-        if (v.segoff) (void)hipFree(v.segoff);
-        if (v.leak) (void)hipFree(v.leak);
-        if (v.oslot) (void)hipFree(v.oslot);
-        if (v.in_ent) (void)hipFree(v.in_ent);
-        if (v.inmask) (void)hipFree(v.inmask);
-    }
-    for (auto &v : h->rvar) {
-        if (v.rem_ptr) (void)hipFree(v.rem_ptr);
-        if (v.rem) (void)hipFree(v.rem);
-        if (v.inmask) (void)hipFree(v.inmask);
-        if (v.leak) (void)hipFree(v.leak);
-        if (v.oslot) (void)hipFree(v.oslot);
-        if (v.in_ent) (void)hipFree(v.in_ent);
-    }
-    for (auto &v : h->pvar) {
-        if (v.rec) (void)hipFree(v.rec);
-        if (v.rem) (void)hipFree(v.rem);
-        if (v.oslot) (void)hipFree(v.oslot);
-        if (v.leak) (void)hipFree(v.leak);
-        if (v.inmask) (void)hipFree(v.inmask);
-    }
-    delete h;
-    return LSM_OK;
-}
 
 static size_t ring_lds_bytes(const lsm_reservoir *h, const RingVariant &v, int T);
 
@@ -161,6 +141,17 @@ static bool has_pairs(const lsm_reservoir *h)
 // format moves a quarter (N = 4000: window 3.6 KB + list 0.6 KB against 16 KB per row)
 constexpr size_t RING_AUTO_MIN_DENSE_BYTES = (size_t)32 << 20;
 
+template <typename T>
+static int upload(DevPtr<T> *dst, const std::vector<T> &src)
+{
+    T *p = nullptr;
+    LSM_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(1, src.size()) * sizeof(T)));
+    dst->reset(p);
+    if (!src.empty())
+        LSM_CHECK_HIP(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return LSM_OK;
+}
+
 // Allocate and fill the dense row table of a handle that does not have it yet (synchronous: handle set-up, not a
 // launch function).
 static int ensure_dense_rows(lsm_reservoir *h)
@@ -171,29 +162,20 @@ static int ensure_dense_rows(lsm_reservoir *h)
     LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d",
                 h->device, dev_now);
     const size_t bytes = (size_t)h->N * (size_t)h->ld * sizeof(float);
-    float *wt = nullptr;
-    LSM_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&wt), bytes));
-    hipError_t e = hipMemset(wt, 0, bytes);
+    float *p = nullptr;
+    LSM_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(&p), bytes));
+    DevPtr<float> wt(p);
+    hipError_t e = hipMemset(p, 0, bytes);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(build_dense_rows_kernel, dim3(h->N), dim3(256), 0, nullptr, h->rowptr, h->syn, h->ld, wt);
+        hipLaunchKernelGGL(build_dense_rows_kernel, dim3(h->N), dim3(256), 0, nullptr, h->rowptr.get(), h->syn.get(), h->ld, p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
-        (void)hipFree(wt);
         lsm_set_error("building the dense row table failed: %s", hipGetErrorString(e));
         return LSM_ERR_HIP;
     }
-    h->wt = wt;
-    return LSM_OK;
-}
-
-template <typename T>
-static int upload(T **dst, const std::vector<T> &src)
-{
-    LSM_CHECK_HIP(hipMalloc(reinterpret_cast<void **>(dst), std::max<size_t>(1, src.size()) * sizeof(T)));
-    if (!src.empty())
-        LSM_CHECK_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    h->wt = std::move(wt);
     return LSM_OK;
 }
 
@@ -275,6 +257,89 @@ static bool colour_input_channels(int N, int C, const int32_t *in_tgt, int in_fa
     return true;
 }
 
+// What lsm_reservoir_create is given to build tables from (lsm_debug_pair_layout and lsm_debug_pair_inputs fill in the part
+// their tables need).
+struct Network {
+    int N = 0, C = 0;
+    const int32_t *csc_ptr = nullptr, *csc_post = nullptr;
+    const float *csc_w = nullptr, *leak = nullptr;
+    const int32_t *in_tgt = nullptr;
+    int in_fanout = 0;
+    const int32_t *out_idx = nullptr;
+    int n_out = 0;
+    size_t nnz = 0;
+    const uint8_t *perm = nullptr;      // (C) coloured bit position of every channel (colour_input_channels), null: natural
+};
+
+static uint32_t weight_bits(float w)
+{
+    uint32_t bits;
+    std::memcpy(&bits, &w, 4);
+    return bits;
+}
+
+// (npad) leak coefficients / output slots in neuron order; padding neurons leak 0 and have no slot (-1)
+static std::vector<float> padded_leak(const Network &net, int npad)
+{
+    std::vector<float> lk(npad, 0.0f);
+    std::copy(net.leak, net.leak + net.N, lk.begin());
+    return lk;
+}
+static std::vector<int> output_slots(const Network &net, int npad)
+{
+    std::vector<int> os(npad, -1);
+    for (int o = 0; o < net.n_out; ++o) os[net.out_idx[o]] = o;
+    return os;
+}
+
+// Per-neuron channel masks (npad, 4) in neuron order, C <= 128: bit p of neuron i's four words = the channel at position p
+// (net.perm, else its own number) feeds neuron i -- INMODE 2 / 3 of the dense kernel, INMASK 1 / 2 of the ring and pair
+// kernels.  Returns `distinct`: no channel names a neuron twice (SPEC.md 2.4 draws targets without replacement); the words
+// hold one bit per (channel, neuron) pair, so a map that does has no mask form and `im` is not to be used.
+static bool channel_masks(const Network &net, int npad, std::vector<uint32_t> *im)
+{
+    im->assign((size_t)npad * 4, 0u);
+    for (int c = 0; c < net.C; ++c)
+        for (int d = 0; d < net.in_fanout; ++d) {
+            const int tgt = net.in_tgt[(size_t)c * net.in_fanout + d];
+            const int pc = net.perm ? net.perm[c] : c;          // bit position of channel c in the input bit row
+            uint32_t &word = (*im)[(size_t)tgt * 4 + (pc >> 5)];
+            if (word & (1u << (pc & 31))) return false;
+            word |= 1u << (pc & 31);
+        }
+    return true;
+}
+
+// The channel masks of a layout, uploaded when the map has them (channel_masks); *incol: at the coloured positions.
+static int upload_channel_masks(const Network &net, int npad, DevPtr<uint32_t> *inmask, bool *incol)
+{
+    std::vector<uint32_t> im;
+    if (!channel_masks(net, npad, &im)) return LSM_OK;
+    *incol = net.perm != nullptr;
+    return upload(inmask, im);
+}
+
+// The input map shared out by owner wave: (wpc, einw) words, entry(c, i) for every (channel c -> neuron i) pair of wave
+// wave_of(i) in channel order, every wave's part padded with pad(index) to einw, a multiple of `block`.  Returns einw.
+template <typename WaveOf, typename Entry, typename Pad>
+static int wave_entries(const Network &net, int wpc, int block, WaveOf wave_of, Entry entry, Pad pad, std::vector<uint32_t> *ent)
+{
+    std::vector<std::vector<uint32_t>> per(wpc);
+    for (int c = 0; c < net.C; ++c)
+        for (int d = 0; d < net.in_fanout; ++d) {
+            const int tgt = net.in_tgt[(size_t)c * net.in_fanout + d];
+            per[wave_of(tgt)].push_back(entry(c, tgt));
+        }
+    size_t mx = 1;
+    for (auto &pp : per) mx = std::max(mx, pp.size());
+    const int einw = (int)((mx + block - 1) / block * block);
+    ent->resize((size_t)wpc * einw);
+    for (size_t e = 0; e < ent->size(); ++e) (*ent)[e] = pad(e);
+    for (int w = 0; w < wpc; ++w)
+        std::copy(per[w].begin(), per[w].end(), ent->begin() + (size_t)w * einw);
+    return einw;
+}
+
 // ---- ring-row geometry and the pair-block tables: host arithmetic only (no HIP call), shared by lsm_reservoir_create and
 // lsm_debug_pair_layout, which lets a CPU test apply every row from the tables alone (tests/test_pair_layout.py) ----
 struct RingGeometry {
@@ -293,15 +358,17 @@ struct RingGeometry {
 // Window half-width H = half the mean out-degree (k/2 of a small-world graph).  Row j covers the targets from the
 // 32-aligned start of (j-H) mod N up to (j+H) mod N along the ring padded to NQ quads of 256.  False when the reservoir is
 // not ring-like enough for the format (the plain window must hold most of the synapses and be a real saving).
-static bool ring_geometry(int N, const int32_t *csc_ptr, const int32_t *csc_post, size_t nnz, RingGeometry *g)
+static bool ring_geometry(const Network &net, RingGeometry *g)
 {
+    const int N = net.N;
+    const size_t nnz = net.nnz;
     const int H = (int)((nnz / (size_t)N + 1) / 2);
     const int wd = 2 * H + 1;
     const int NQ = (N + 255) / 256;
     size_t inside = 0;
     for (int j = 0; j < N; ++j)
-        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e) {
-            int q = csc_post[e] - (j - H);
+        for (int e = net.csc_ptr[j]; e < net.csc_ptr[j + 1]; ++e) {
+            int q = net.csc_post[e] - (j - H);
             q = q < 0 ? q + N : (q >= N ? q - N : q);
             inside += q < wd;
         }
@@ -326,48 +393,63 @@ static bool ring_geometry(int N, const int32_t *csc_ptr, const int32_t *csc_post
     return wsq < NQ;
 }
 
-static void ring_windows(int N, const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w, const RingGeometry &g,
-                         std::vector<float> *band)
+static void ring_windows(const Network &net, const RingGeometry &g, std::vector<float> *band)
 {
-    band->assign((size_t)N * (g.pitch / 4), 0.0f);
-    for (int j = 0; j < N; ++j)
-        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e) {
-            const long off = g.win_off(j, csc_post[e]);
-            if (off >= 0) (*band)[(size_t)j * (g.pitch / 4) + (size_t)(off / 4)] = csc_w[e];
+    band->assign((size_t)net.N * (g.pitch / 4), 0.0f);
+    for (int j = 0; j < net.N; ++j)
+        for (int e = net.csc_ptr[j]; e < net.csc_ptr[j + 1]; ++e) {
+            const long off = g.win_off(j, net.csc_post[e]);
+            if (off >= 0) (*band)[(size_t)j * (g.pitch / 4) + (size_t)(off / 4)] = net.csc_w[e];
         }
 }
 
-// Pair blocks (lif_pair.h): the windows shared out in 128-neuron blocks, wave w owning the blocks w, w+wpc, ...: the
-// residues must survive the ring's wrap (2*NQ % wpc == 0), a window must not touch more than wpc blocks, a wave at most
-// four blocks (8 neurons per lane), a (row, wave) list at most 64 entries.  Returns the blocks per wave, 0 = no layout.
-static int pair_lists(int N, int wpc, const int32_t *csc_ptr, const int32_t *csc_post, const float *csc_w,
-                      const RingGeometry &g, std::vector<uint32_t> *rptr, std::vector<uint2> *rem)
+// The synapses outside the ring windows as lists per (row j, wave w), unpadded: rptr[j*wpc + w] = first entry of the list,
+// entries {acc_byte(target), weight bits} in ascending target order.  wave_of(i): the wave that owns neuron i in the layout;
+// acc_byte(i): LDS byte offset of its accumulator.  Returns the longest list (the kernels give a list entry a lane: the
+// callers refuse more than 64).
+template <typename WaveOf, typename AccByte>
+static int outside_lists(const Network &net, int wpc, const RingGeometry &g, WaveOf wave_of, AccByte acc_byte,
+                         std::vector<uint32_t> *rptr, std::vector<uint2> *rem)
 {
-    const int NB = 2 * g.NQ;
-    int wsb = 0;
-    for (int j = 0; j < N; ++j) wsb = std::max(wsb, (((g.a4v[j] & 127) + (g.nbytes[j] / 4 - 1)) >> 7) + 1);
-    if (NB % wpc != 0 || wsb > wpc) return 0;
-    const int bl = NB / wpc;
-    if (bl < 1 || bl > 4) return 0;
-    rptr->assign((size_t)N * wpc + 1, 0u);
+    rptr->assign((size_t)net.N * wpc + 1, 0u);
     int emax = 0;
-    for (int j = 0; j < N; ++j)
-        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e)
-            if (g.win_off(j, csc_post[e]) < 0)
-                emax = std::max(emax, (int)++(*rptr)[(size_t)j * wpc + lsm_lif::pair_wave_of_block(csc_post[e] >> 7, wpc) + 1]);
-    if (emax > 64) return 0;                                 // one lane per list entry
+    for (int j = 0; j < net.N; ++j)
+        for (int e = net.csc_ptr[j]; e < net.csc_ptr[j + 1]; ++e)
+            if (g.win_off(j, net.csc_post[e]) < 0)
+                emax = std::max(emax, (int)++(*rptr)[(size_t)j * wpc + wave_of(net.csc_post[e]) + 1]);
     for (size_t q = 1; q < rptr->size(); ++q) (*rptr)[q] += (*rptr)[q - 1];
-    if ((uint64_t)rptr->back() * 8u >= (1ull << 32)) return 0;
     rem->assign(std::max<size_t>(1, rptr->back()), make_uint2(0u, 0u));
     std::vector<uint32_t> fill(rptr->begin(), rptr->end() - 1);
-    for (int j = 0; j < N; ++j)
-        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e) {
-            const int i = csc_post[e];
-            if (g.win_off(j, i) >= 0) continue;
-            uint32_t bits;
-            std::memcpy(&bits, &csc_w[e], 4);
-            (*rem)[fill[(size_t)j * wpc + lsm_lif::pair_wave_of_block(i >> 7, wpc)]++] = make_uint2(lsm_lif::pair_acc_byte(i), bits);
+    for (int j = 0; j < net.N; ++j)
+        for (int e = net.csc_ptr[j]; e < net.csc_ptr[j + 1]; ++e) {
+            const int i = net.csc_post[e];
+            if (g.win_off(j, i) < 0)
+                (*rem)[fill[(size_t)j * wpc + wave_of(i)]++] = make_uint2(acc_byte(i), weight_bits(net.csc_w[e]));
         }
+    return emax;
+}
+
+// Blocks per wave of a pair-block layout with `wpc` waves: the 2*NQ blocks of 128 neurons shared out evenly (the residues
+// must survive the ring's wrap), a wave at most four blocks (8 neurons per lane).  0 = no such layout.
+static int pair_blocks_per_wave(int NQ, int wpc)
+{
+    const int NB = 2 * NQ;
+    return (NB % wpc == 0 && NB / wpc <= 4) ? NB / wpc : 0;
+}
+
+// Pair blocks (lif_pair.h): the windows shared out in 128-neuron blocks, wave w owning the blocks w, w+wpc, ...
+// (pair_blocks_per_wave), a window must not touch more than wpc blocks, a (row, wave) list at most 64 entries.  Returns the
+// blocks per wave, 0 = no layout.
+static int pair_lists(const Network &net, int wpc, const RingGeometry &g, std::vector<uint32_t> *rptr, std::vector<uint2> *rem)
+{
+    int wsb = 0;
+    for (int j = 0; j < net.N; ++j) wsb = std::max(wsb, (((g.a4v[j] & 127) + (g.nbytes[j] / 4 - 1)) >> 7) + 1);
+    const int bl = pair_blocks_per_wave(g.NQ, wpc);
+    if (!bl || wsb > wpc) return 0;
+    const int emax = outside_lists(net, wpc, g, [&](int i) { return lsm_lif::pair_wave_of_block(i >> 7, wpc); },
+                                   [](int i) { return lsm_lif::pair_acc_byte(i); }, rptr, rem);
+    if (emax > 64) return 0;                                 // one lane per list entry
+    if ((uint64_t)rptr->back() * 8u >= (1ull << 32)) return 0;     // a record holds the low 32 bits of a list's address
     return bl;
 }
 
@@ -400,59 +482,54 @@ int lsm_debug_pair_layout(int num_neurons, const int32_t *csc_ptr, const int32_t
 {
     LSM_REQUIRE(num_neurons >= 1 && num_neurons <= 8192 && csc_ptr && csc_post && csc_w, "lsm_debug_pair_layout: bad argument");
     LSM_REQUIRE(wpc == 4 || wpc == 8 || wpc == 16, "lsm_debug_pair_layout: wpc must be 4, 8 or 16");
-    const int N = num_neurons;
+    Network net;
+    net.N = num_neurons; net.csc_ptr = csc_ptr; net.csc_post = csc_post; net.csc_w = csc_w; net.nnz = (size_t)csc_ptr[net.N];
     RingGeometry g;
-    if (!ring_geometry(N, csc_ptr, csc_post, (size_t)csc_ptr[N], &g)) return 0;
+    if (!ring_geometry(net, &g)) return 0;
     std::vector<uint32_t> rptr;
     std::vector<uint2> rem;
-    const int bl = pair_lists(N, wpc, csc_ptr, csc_post, csc_w, g, &rptr, &rem);
+    const int bl = pair_lists(net, wpc, g, &rptr, &rem);
     if (!bl) return 0;
-    if (band_floats) *band_floats = (long)N * (g.pitch / 4);
+    if (band_floats) *band_floats = (long)net.N * (g.pitch / 4);
     if (n_list_entries) *n_list_entries = (long)rptr.back();
     if (pitch_bytes) *pitch_bytes = (int)g.pitch;
     if (band_out) {
         std::vector<float> band;
-        ring_windows(N, csc_ptr, csc_post, csc_w, g, &band);
+        ring_windows(net, g, &band);
         std::memcpy(band_out, band.data(), band.size() * sizeof(float));
     }
     if (rem_out) std::memcpy(rem_out, rem.data(), (size_t)rptr.back() * sizeof(uint2));
     if (rec_out) {
         std::vector<uint4> rec;
-        pair_records(N, wpc, g, rptr, band_addr, rem_addr, &rec);
+        pair_records(net.N, wpc, g, rptr, band_addr, rem_addr, &rec);
         std::memcpy(rec_out, rec.data(), rec.size() * sizeof(uint4));
     }
     return bl;
 }
 
 // The pair-block kernel's four input words per neuron (lif_pair.h), (npad, 4) in neuron order, for channels at the positions
-// `inperm` (coloured) or at their natural ones.  Returns the kernel's INMASK form: 1 = channel masks at the natural positions
+// net.perm (coloured) or at their natural ones.  Returns the kernel's INMASK form: 1 = channel masks at the natural positions
 // (C <= 128, no colouring), 2 = masks at coloured positions (C <= 128), 3 = {posmask, P0, P1, P2} over coloured positions
 // (129..256 channels: bit p of posmask = a channel of colour p feeds the neuron, bit p of Pj = bit j of that channel's
 // word), 0 = no such form: more than 256 channels, more than 128 without a colouring, or a channel that names a neuron
 // twice (the words hold one bit per (channel, neuron) pair).  Host arithmetic only.
-static int pair_input_words(int C, const int32_t *in_tgt, int in_fanout, int npad, bool coloured,
-                            const std::vector<uint8_t> &inperm, std::vector<uint32_t> *im)
+static int pair_input_words(const Network &net, int npad, std::vector<uint32_t> *im)
 {
-    if (C > 256 || (C > 128 && !coloured)) return 0;
+    if (net.C > 256 || (net.C > 128 && !net.perm)) return 0;
+    if (net.C <= 128) return channel_masks(net, npad, im) ? (net.perm ? 2 : 1) : 0;
     im->assign((size_t)npad * 4, 0u);
-    for (int c = 0; c < C; ++c)
-        for (int d = 0; d < in_fanout; ++d) {
-            const int tgt = in_tgt[(size_t)c * in_fanout + d];
-            const int pc = coloured ? inperm[c] : c;          // bit position of channel c in the input bit row
+    for (int c = 0; c < net.C; ++c)
+        for (int d = 0; d < net.in_fanout; ++d) {
+            const int pc = net.perm[c];
             const uint32_t bit = 1u << (pc & 31);
-            uint32_t *m = im->data() + (size_t)tgt * 4;
-            if (C <= 128) {
-                if (m[pc >> 5] & bit) return 0;
-                m[pc >> 5] |= bit;
-            } else {
-                // channels that share a neuron differ in colour: a bit met twice is the SAME channel naming the neuron again
-                if (m[0] & bit) return 0;
-                m[0] |= bit;
-                for (int j = 0; j < 3; ++j)
-                    if (((pc >> 5) >> j) & 1) m[1 + j] |= bit;
-            }
+            uint32_t *m = im->data() + (size_t)net.in_tgt[(size_t)c * net.in_fanout + d] * 4;
+            // channels that share a neuron differ in colour: a bit met twice is the SAME channel naming the neuron again
+            if (m[0] & bit) return 0;
+            m[0] |= bit;
+            for (int j = 0; j < 3; ++j)
+                if (((pc >> 5) >> j) & 1) m[1 + j] |= bit;
         }
-    return C > 128 ? 3 : (coloured ? 2 : 1);
+    return 3;
 }
 
 // Host-only (no GPU, no HIP call): the channel positions (perm_out[n_channels]; the identity where the masks keep the natural
@@ -467,20 +544,194 @@ int lsm_debug_pair_inputs(int num_neurons, int n_channels, const int32_t *in_tgt
     LSM_REQUIRE(num_neurons >= 1 && num_neurons <= 8192 && n_channels >= 1 && n_channels <= 65535 && in_tgt &&
                 in_fanout >= 1 && in_fanout <= num_neurons, "lsm_debug_pair_inputs: bad argument");
     LSM_REQUIRE(wpc == 4 || wpc == 8 || wpc == 16, "lsm_debug_pair_inputs: wpc must be 4, 8 or 16");
-    const int N = num_neurons, C = n_channels;
-    for (size_t e = 0; e < (size_t)C * in_fanout; ++e)
-        LSM_REQUIRE(in_tgt[e] >= 0 && in_tgt[e] < N, "lsm_debug_pair_inputs: in_tgt[%zu] out of range", e);
-    const int NB = 2 * ((N + 255) / 256);
-    if (NB % wpc != 0 || NB / wpc > 4) return 0;
+    Network net;
+    net.N = num_neurons; net.C = n_channels; net.in_tgt = in_tgt; net.in_fanout = in_fanout;
+    for (size_t e = 0; e < (size_t)net.C * in_fanout; ++e)
+        LSM_REQUIRE(in_tgt[e] >= 0 && in_tgt[e] < net.N, "lsm_debug_pair_inputs: in_tgt[%zu] out of range", e);
+    const int NQ = (net.N + 255) / 256;
+    if (!pair_blocks_per_wave(NQ, wpc)) return 0;
     std::vector<uint8_t> inperm;
-    const bool coloured = colour_input_channels(N, C, in_tgt, in_fanout, &inperm);
+    if (colour_input_channels(net.N, net.C, in_tgt, in_fanout, &inperm)) net.perm = inperm.data();
     std::vector<uint32_t> im;
-    const int form = pair_input_words(C, in_tgt, in_fanout, NB * 128, coloured, inperm, &im);
+    const int form = pair_input_words(net, NQ * 256, &im);
     if (!form) return 0;
     if (perm_out)
-        for (int c = 0; c < C; ++c) perm_out[c] = coloured ? inperm[c] : (uint8_t)c;
+        for (int c = 0; c < net.C; ++c) perm_out[c] = net.perm ? net.perm[c] : (uint8_t)c;
     if (words_out) std::memcpy(words_out, im.data(), im.size() * sizeof(uint32_t));
     return form;
+}
+
+static int check_network(const Network &net, float theta, int refractory)
+{
+    const int N = net.N, C = net.C;
+    // 8192: beyond that the per-clip LDS image (counts, spike lists, features, input bits) of neither kernel
+    // fits the 160 KB of a CU
+    LSM_REQUIRE(N >= 1 && N <= 8192, "num_neurons=%d outside [1, 8192]", N);
+    LSM_REQUIRE(C >= 1 && C <= 65535, "n_channels=%d outside [1, 65535]", C);
+    LSM_REQUIRE(net.n_out >= 1 && net.n_out <= N, "num_output_neurons=%d outside [1, %d]", net.n_out, N);
+    LSM_REQUIRE(theta > 0.0f, "membrane_threshold must be > 0");
+    LSM_REQUIRE(refractory >= 0 && net.in_fanout >= 1 && net.in_fanout <= N, "bad refractory/in_fanout");
+    LSM_REQUIRE(net.csc_ptr && net.csc_post && net.csc_w && net.leak && net.in_tgt && net.out_idx, "null array argument");
+    LSM_REQUIRE(net.csc_ptr[0] == 0, "csc_ptr[0] must be 0");
+    for (int j = 0; j < N; ++j) {
+        LSM_REQUIRE(net.csc_ptr[j + 1] >= net.csc_ptr[j], "csc_ptr not monotone at %d", j);
+        for (int e = net.csc_ptr[j]; e < net.csc_ptr[j + 1]; ++e) {
+            LSM_REQUIRE(net.csc_post[e] >= 0 && net.csc_post[e] < N, "csc_post[%d] out of range", e);
+            LSM_REQUIRE(e == net.csc_ptr[j] || net.csc_post[e] > net.csc_post[e - 1],
+                        "csc_post not strictly ascending within column %d", j);
+        }
+    }
+    for (int o = 0; o < net.n_out; ++o)
+        LSM_REQUIRE(net.out_idx[o] >= 0 && net.out_idx[o] < N && (o == 0 || net.out_idx[o] > net.out_idx[o - 1]),
+                    "out_idx must be strictly ascending in [0, N)");
+    for (int e = 0; e < C * net.in_fanout; ++e)
+        LSM_REQUIRE(net.in_tgt[e] >= 0 && net.in_tgt[e] < N, "in_tgt[%d] out of range", e);
+    return LSM_OK;
+}
+
+static int upload_csc(lsm_reservoir *h, const Network &net)
+{
+    std::vector<uint2> syn(net.nnz);
+    for (size_t e = 0; e < net.nnz; ++e) syn[e] = make_uint2((uint32_t)net.csc_post[e], weight_bits(net.csc_w[e]));
+    const int rc = upload(&h->syn, syn);
+    if (rc) return rc;
+    return upload(&h->rowptr, std::vector<uint32_t>(net.csc_ptr, net.csc_ptr + net.N + 1));
+}
+
+// Layout vi of the sparse and dense kernels: wpc = 1, 2, 4, 8, 16 waves per clip, wave w owning the neurons
+// [w*sl*64, (w+1)*sl*64).  Left unavailable (wpc == 0) when a wave would own more than 16 slots of 64.
+static int build_variant(lsm_reservoir *h, const Network &net, int vi)
+{
+    const int N = net.N, wpc = 1 << vi;
+    const int need = ((N + wpc - 1) / wpc + 63) / 64;      // 64-neuron slots per wave
+    int sl = 1;
+    while (sl < need) sl <<= 1;
+    if (sl > 16) return LSM_OK;
+    const int npw = sl * 64, npad = npw * wpc;
+    Variant &v = h->var[vi];
+    // segment table: entry (j, w) = first synapse of column j whose target belongs to wave w;
+    // the segment ends where entry (j, w+1) -- or column j+1 -- begins.
+    std::vector<uint32_t> seg((size_t)N * wpc + 1);
+    for (int j = 0; j < N; ++j) {
+        int e = net.csc_ptr[j];
+        for (int w = 0; w < wpc; ++w) {
+            seg[(size_t)j * wpc + w] = (uint32_t)e;
+            const int hi = (w + 1) * npw;
+            while (e < net.csc_ptr[j + 1] && net.csc_post[e] < hi) ++e;
+        }
+    }
+    seg[(size_t)N * wpc] = (uint32_t)net.nnz;
+    // packed form for LDS: u16 offsets relative to the row start, WPC + 1 per neuron
+    std::vector<uint16_t> segoff((size_t)N * (wpc + 1) + 2, 0);
+    for (int j = 0; j < N; ++j) {
+        for (int w = 0; w < wpc; ++w)
+            segoff[(size_t)j * (wpc + 1) + w] = (uint16_t)(seg[(size_t)j * wpc + w] - (uint32_t)net.csc_ptr[j]);
+        segoff[(size_t)j * (wpc + 1) + wpc] = (uint16_t)(net.csc_ptr[j + 1] - net.csc_ptr[j]);
+    }
+    std::vector<uint32_t> ent;              // (channel << 16) | target, whole rows of 64, 0xFFFFFFFF = padding
+    const int einw = wave_entries(net, wpc, 64, [&](int i) { return i / npw; },
+                                  [](int c, int i) { return ((uint32_t)c << 16) | (uint32_t)i; },
+                                  [](size_t) { return 0xFFFFFFFFu; }, &ent);
+    int rc;
+    if ((rc = upload(&v.seg, seg)) || (rc = upload(&v.segoff, segoff)) || (rc = upload(&v.leak, padded_leak(net, npad))) ||
+        (rc = upload(&v.oslot, output_slots(net, npad))) || (rc = upload(&v.in_ent, ent)))
+        return rc;
+    // INMODE 2 / 3 of the dense kernel: channel masks in registers
+    if (net.C <= 128 && sl <= 4 && (rc = upload_channel_masks(net, npad, &v.inmask, &v.incol))) return rc;
+    v.wpc = wpc; v.sl = sl; v.einw = einw;
+    return LSM_OK;
+}
+
+// Layout vi of the ring-row kernel in quads (lif_ring.h): wpc = 2, 4, 8, 16 waves, contiguous (vi < 4) or strided quad
+// ownership.  Left unavailable when the geometry does not allow it.
+static int build_quads(lsm_reservoir *h, const Network &net, const RingGeometry &geo, int vi)
+{
+    const int N = net.N, wpc = 2 << (vi & 3);
+    const bool strided = vi >= 4;
+    int ql = 0;
+    if (strided) {
+        // every wave gets exactly one window quad per row: the residues mod wpc must survive the
+        // ring's wrap (NQ % wpc == 0) and a window must not be wider than wpc quads
+        if (geo.NQ % wpc != 0 || geo.wsq > wpc) return LSM_OK;
+        ql = geo.NQ / wpc;
+        if (ql < 1 || ql > 4) return LSM_OK;
+    } else {
+        for (int cand : {1, 2, 3, 4})
+            if (!ql && wpc * cand * 256 >= N) ql = cand;
+        // a wave must never hold both ends of a (wrapped) window: window quads + QL <= NQ
+        if (!ql || geo.wsq + ql > geo.NQ) return LSM_OK;
+    }
+    const int npad = wpc * ql * 256;
+    auto wave_of = [&](int i) { return lsm_lif::ring_wave_of_quad(i >> 8, ql, wpc, strided); };
+    std::vector<uint32_t> rptr;
+    std::vector<uint2> rem;
+    const int emax = outside_lists(net, wpc, geo, wave_of, [](int i) { return (uint32_t)lsm_lif::ring_acc_word(i) * 4u; },
+                                   &rptr, &rem);
+    if (emax > 64) return LSM_OK;                            // one lane per list entry
+    if (rptr.back() >= (1u << 24)) return LSM_OK;            // the kernel packs a list's start into 24 bits
+    // input map per owner wave, packed (lsm_lif::ring_pack_entry), padded to whole blocks of RING_ENT_BLOCK so that the
+    // kernel's drive needs no guards.  Padding entry at index e: channel 0 into dump word e % 64 -- every lane its OWN dump
+    // word (64 lanes adding to one LDS word serialise: zero-padding cost cfg4 5 ms, profiles/r04_ring_input_drive.txt)
+    std::vector<uint32_t> ent;
+    const int einw = wave_entries(net, wpc, lsm_lif::RING_ENT_BLOCK, wave_of,
+                                  [](int c, int i) { return lsm_lif::ring_pack_entry(c, i); },
+                                  [](size_t e) { return (uint32_t)((e % 64) * 4); }, &ent);
+    RingVariant &v = h->rvar[vi];
+    int rc;
+    if ((rc = upload(&v.rem_ptr, rptr)) || (rc = upload(&v.rem, rem)) || (rc = upload(&v.leak, padded_leak(net, npad))) ||
+        (rc = upload(&v.oslot, output_slots(net, npad))) || (rc = upload(&v.in_ent, ent)))
+        return rc;
+    // INMASK form of the kernel (lif_ring.h): per-neuron channel masks in registers instead of the entry drive
+    if (net.C <= 128 && h->leak_uniform && strided && ql <= 2 && (rc = upload_channel_masks(net, npad, &v.inmask, &v.incol)))
+        return rc;
+    v.wpc = wpc; v.ql = ql; v.einw = einw; v.strided = strided; v.n_rem = rptr.back();
+    return LSM_OK;
+}
+
+// Layout vi of the ring-row kernel in pair blocks (lif_pair.h): wpc = 4, 8, 16 waves (pair_lists).  The kernel counts the
+// input drive from four registers per neuron only: `im` in the form `inform` (pair_input_words).
+static int build_pairs(lsm_reservoir *h, const Network &net, const RingGeometry &geo, int vi, int inform,
+                       const std::vector<uint32_t> &im)
+{
+    const int N = net.N, wpc = 4 << vi, npad = geo.NQ * 256;
+    std::vector<uint32_t> rptr;
+    std::vector<uint2> rem;
+    const int bl = pair_lists(net, wpc, geo, &rptr, &rem);
+    if (!bl) return LSM_OK;
+    // the records carry device addresses (low halves): upload the lists first; a table that crosses a 4 GB
+    // line (the kernel takes the high address bits from the table pointer) cannot serve this layout
+    PairVariant &v = h->pvar[vi];
+    int rc;
+    if ((rc = upload(&v.rem, rem))) return rc;
+    const uint64_t band_a = reinterpret_cast<uint64_t>(h->band.get()), rem_a = reinterpret_cast<uint64_t>(v.rem.get());
+    if ((band_a >> 32) != ((band_a + (uint64_t)N * geo.pitch) >> 32) ||
+        (rem_a >> 32) != ((rem_a + (uint64_t)rem.size() * 8u) >> 32)) {
+        v.rem.reset();
+        return LSM_OK;
+    }
+    std::vector<uint4> rec;
+    pair_records(N, wpc, geo, rptr, band_a, rem_a, &rec);
+    if ((rc = upload(&v.rec, rec)) || (rc = upload(&v.oslot, output_slots(net, npad))) || (rc = upload(&v.inmask, im)))
+        return rc;
+    // a coefficient per neuron (LEAKV form of the kernel)
+    if (!h->leak_uniform && (rc = upload(&v.leak, padded_leak(net, npad)))) return rc;
+    v.inform = inform;
+    v.wpc = wpc; v.bl = bl; v.n_rem = rptr.back();
+    return LSM_OK;
+}
+
+// Dense rows at creation, unless auto mode will serve this reservoir with ring rows: the table exceeds the L2 caches, ring
+// rows exist AND one of their layouts fits a CU's LDS with room to spare (probed at 1024 time steps; the
+// reference runs 400).  Then the 64-262 MB table and its upload would be dead weight next to the ring table
+// (ADVICE r2); lsm_reservoir_set_kernel(2) still builds it on request.  When no ring layout fits (e.g. N = 8000
+// with 5000 output neurons) the dense kernel is auto mode's fallback and needs its table from the start.
+static bool ring_serves_auto(const lsm_reservoir *h)
+{
+    if (!has_ring(h) || (size_t)h->N * (size_t)h->ld * 4 <= RING_AUTO_MIN_DENSE_BYTES) return false;
+    // (a pair-block layout implies strided quad layouts of the same table exist; the quads decide)
+    for (const auto &v : h->rvar)
+        if (v.wpc && ring_lds_bytes(h, v, 1024) <= 160 * 1024) return true;
+    return false;
 }
 
 // Any refractory period >= 0 is accepted and stored as min(refractory, 65535): a run has at most 65535 steps, so a neuron
@@ -496,298 +747,64 @@ int lsm_reservoir_create(lsm_reservoir **out, int num_neurons, int n_channels,
 {
     LSM_REQUIRE(out != nullptr, "lsm_reservoir_create: out is null");
     *out = nullptr;
-    const int N = num_neurons, C = n_channels;
-    // 8192: beyond that the per-clip LDS image (counts, spike lists, features, input bits) of neither kernel
-    // fits the 160 KB of a CU
-    LSM_REQUIRE(N >= 1 && N <= 8192, "num_neurons=%d outside [1, 8192]", N);
-    LSM_REQUIRE(C >= 1 && C <= 65535, "n_channels=%d outside [1, 65535]", C);
-    LSM_REQUIRE(n_out >= 1 && n_out <= N, "num_output_neurons=%d outside [1, %d]", n_out, N);
-    LSM_REQUIRE(theta > 0.0f, "membrane_threshold must be > 0");
-    LSM_REQUIRE(refractory >= 0 && in_fanout >= 1 && in_fanout <= N, "bad refractory/in_fanout");
-    LSM_REQUIRE(csc_ptr && csc_post && csc_w && leak && in_tgt && out_idx, "null array argument");
-    LSM_REQUIRE(csc_ptr[0] == 0, "csc_ptr[0] must be 0");
-    const size_t nnz = (size_t)csc_ptr[N];
-    for (int j = 0; j < N; ++j) {
-        LSM_REQUIRE(csc_ptr[j + 1] >= csc_ptr[j], "csc_ptr not monotone at %d", j);
-        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e) {
-            LSM_REQUIRE(csc_post[e] >= 0 && csc_post[e] < N, "csc_post[%d] out of range", e);
-            LSM_REQUIRE(e == csc_ptr[j] || csc_post[e] > csc_post[e - 1],
-                        "csc_post not strictly ascending within column %d", j);
-        }
-    }
-    for (int o = 0; o < n_out; ++o)
-        LSM_REQUIRE(out_idx[o] >= 0 && out_idx[o] < N && (o == 0 || out_idx[o] > out_idx[o - 1]),
-                    "out_idx must be strictly ascending in [0, N)");
-    for (int e = 0; e < C * in_fanout; ++e)
-        LSM_REQUIRE(in_tgt[e] >= 0 && in_tgt[e] < N, "in_tgt[%d] out of range", e);
+    Network net;
+    net.N = num_neurons; net.C = n_channels; net.csc_ptr = csc_ptr; net.csc_post = csc_post; net.csc_w = csc_w;
+    net.leak = leak; net.in_tgt = in_tgt; net.in_fanout = in_fanout; net.out_idx = out_idx; net.n_out = n_out;
+    int rc = check_network(net, theta, refractory);
+    if (rc) return rc;
+    const int N = net.N;
+    net.nnz = (size_t)csc_ptr[N];
 
-    lsm_reservoir *h = new lsm_reservoir();
-    h->N = N; h->C = C; h->n_out = n_out; h->refractory = std::min(refractory, 65535);
-    h->burst_isi_max = burst_isi_max; h->theta = theta; h->w_in = w_in; h->nnz = nnz;
+    std::unique_ptr<lsm_reservoir> h(new lsm_reservoir());
+    h->N = N; h->C = net.C; h->n_out = n_out; h->refractory = std::min(refractory, 65535);
+    h->burst_isi_max = burst_isi_max; h->theta = theta; h->w_in = w_in; h->nnz = net.nnz;
     (void)hipGetDevice(&h->device);
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) {
         (void)hipGetLastError();
         h->cus = 0;
     }
-
-    std::vector<uint2> syn(nnz);
-    for (size_t e = 0; e < nnz; ++e) {
-        uint32_t bits;
-        std::memcpy(&bits, &csc_w[e], 4);
-        syn[e] = make_uint2((uint32_t)csc_post[e], bits);
-    }
-    int rc = upload(&h->syn, syn);
-    if (rc) { free_reservoir(h); return rc; }
-    std::vector<uint32_t> rowptr(csc_ptr, csc_ptr + N + 1);
-    if ((rc = upload(&h->rowptr, rowptr))) { free_reservoir(h); return rc; }
+    if ((rc = upload_csc(h.get(), net))) return rc;
 
     // coloured bit positions for the input masks of the dense kernel and the pair blocks (one assignment per reservoir)
     std::vector<uint8_t> inperm;
-    const bool coloured = colour_input_channels(N, C, in_tgt, in_fanout, &inperm);
-    if (coloured && (rc = upload(&h->inperm, inperm))) { free_reservoir(h); return rc; }
+    if (colour_input_channels(N, net.C, in_tgt, in_fanout, &inperm)) {
+        net.perm = inperm.data();
+        if ((rc = upload(&h->inperm, inperm))) return rc;
+    }
     h->leak_uniform = true;
     h->leak_u = leak[0];
     for (int i = 1; i < N; ++i)
         if (std::memcmp(&leak[i], &leak[0], sizeof(float)) != 0) { h->leak_uniform = false; break; }
 
-    const int wpcs[5] = {1, 2, 4, 8, 16};
-    for (int vi = 0; vi < 5; ++vi) {
-        const int wpc = wpcs[vi];
-        const int need = ((N + wpc - 1) / wpc + 63) / 64;      // 64-neuron slots per wave
-        int sl = 1;
-        while (sl < need) sl <<= 1;
-        if (sl > 16) continue;
-        const int npw = sl * 64, npad = npw * wpc;
-        Variant &v = h->var[vi];
-        // segment table: entry (j, w) = first synapse of column j whose target belongs to wave w;
-        // the segment ends where entry (j, w+1) -- or column j+1 -- begins.
-        std::vector<uint32_t> seg((size_t)N * wpc + 1);
-        for (int j = 0; j < N; ++j) {
-            int e = csc_ptr[j];
-            for (int w = 0; w < wpc; ++w) {
-                seg[(size_t)j * wpc + w] = (uint32_t)e;
-                const int hi = (w + 1) * npw;
-                while (e < csc_ptr[j + 1] && csc_post[e] < hi) ++e;
-            }
-        }
-        seg[(size_t)N * wpc] = (uint32_t)nnz;
-        // packed form for LDS: u16 offsets relative to the row start, WPC + 1 per neuron
-        std::vector<uint16_t> segoff((size_t)N * (wpc + 1) + 2, 0);
-        for (int j = 0; j < N; ++j) {
-            for (int w = 0; w < wpc; ++w)
-                segoff[(size_t)j * (wpc + 1) + w] = (uint16_t)(seg[(size_t)j * wpc + w] - (uint32_t)csc_ptr[j]);
-            segoff[(size_t)j * (wpc + 1) + wpc] = (uint16_t)(csc_ptr[j + 1] - csc_ptr[j]);
-        }
-        std::vector<float> lk(npad, 0.0f);
-        std::vector<int> os(npad, -1);
-        for (int i = 0; i < N; ++i) lk[i] = leak[i];
-        for (int o = 0; o < n_out; ++o) os[out_idx[o]] = o;
-        std::vector<std::vector<uint32_t>> per(wpc);
-        for (int c = 0; c < C; ++c)
-            for (int d = 0; d < in_fanout; ++d) {
-                const int tgt = in_tgt[(size_t)c * in_fanout + d];
-                per[tgt / npw].push_back(((uint32_t)c << 16) | (uint32_t)tgt);
-            }
-        size_t mx = 1;
-        for (auto &p : per) mx = std::max(mx, p.size());
-        const int einw = (int)((mx + 63) / 64 * 64);
-        std::vector<uint32_t> ent((size_t)wpc * einw, 0xFFFFFFFFu);
-        for (int w = 0; w < wpc; ++w)
-            std::copy(per[w].begin(), per[w].end(), ent.begin() + (size_t)w * einw);
-        if ((rc = upload(&v.seg, seg)) || (rc = upload(&v.segoff, segoff)) || (rc = upload(&v.leak, lk)) || (rc = upload(&v.oslot, os)) ||
-            (rc = upload(&v.in_ent, ent))) {
-            free_reservoir(h);
-            return rc;
-        }
-        if (C <= 128 && sl <= 4) {
-            // INMODE 2 of the dense kernel: bit c of neuron i's mask = channel c feeds neuron i (each
-            // (channel, neuron) pair occurs at most once: SPEC.md 2.4 draws targets without replacement)
-            std::vector<uint32_t> im((size_t)npad * 4, 0u);
-            bool distinct = true;
-            for (int c = 0; c < C; ++c)
-                for (int d = 0; d < in_fanout; ++d) {
-                    const int tgt = in_tgt[(size_t)c * in_fanout + d];
-                    const int pc = coloured ? inperm[c] : c;          // bit position of channel c in the input bit row
-                    uint32_t &word = im[(size_t)tgt * 4 + (pc >> 5)];
-                    distinct = distinct && !(word & (1u << (pc & 31)));
-                    word |= 1u << (pc & 31);
-                }
-            if (distinct && (rc = upload(&v.inmask, im))) {
-                free_reservoir(h);
-                return rc;
-            }
-            v.incol = distinct && coloured;
-        }
-        v.wpc = wpc; v.sl = sl; v.einw = einw;
-    }
+    for (int vi = 0; vi < 5; ++vi)
+        if ((rc = build_variant(h.get(), net, vi))) return rc;
     // dense presynaptic rows for the register-accumulating kernel (lif_dense.h): N x ld floats (4 MB at N = 1000:
-    // L2; 64 MB at N = 4000 and 262 MB at N = 8000).  Built further down, and only when auto mode can run them
-    // (ensure_dense_rows); a reservoir that auto mode serves with ring rows gets them on lsm_reservoir_set_kernel(2).
+    // L2; 64 MB at N = 4000 and 262 MB at N = 8000).  Built at the end, and only when auto mode can run them
+    // (ring_serves_auto); a reservoir that auto mode serves with ring rows gets them on lsm_reservoir_set_kernel(2).
     for (const auto &v : h->var)
         if (v.wpc) h->ld = std::max(h->ld, v.sl * 64 * v.wpc);
-    // Ring rows for ring-like graphs (lif_ring.h, lif_pair.h): ring_geometry / ring_windows above.
-    {
-        // (the ring kernel counts a neuron's active input entries of a step in 16 bits)
-        std::vector<uint32_t> fanin(N, 0u);
-        uint32_t max_fanin = 0;
-        for (size_t e = 0; e < (size_t)C * in_fanout; ++e) max_fanin = std::max(max_fanin, ++fanin[in_tgt[e]]);
-        RingGeometry geo;
-        if (max_fanin <= 65535u && ring_geometry(N, csc_ptr, csc_post, nnz, &geo)) {
-            {
-                const int H = geo.H, NQ = geo.NQ, wsq = geo.wsq;
-                const uint32_t pitch = geo.pitch;
-                const std::vector<int> &nbytes = geo.nbytes;
-                auto win_off = [&](int j, int i) -> long { return geo.win_off(j, i); };
-                std::vector<float> band;
-                ring_windows(N, csc_ptr, csc_post, csc_w, geo, &band);
-                if ((rc = upload(&h->band, band))) { free_reservoir(h); return rc; }
-                h->band_pitch = pitch; h->band_h = H; h->band_nq = NQ; h->band_wsq = wsq;
-                for (int j = 0; j < N; ++j) h->band_bytes_sum += nbytes[j];
-                const int rwpcs[4] = {2, 4, 8, 16};
-                for (int vi = 0; vi < 8; ++vi) {
-                    const int wpc = rwpcs[vi & 3];
-                    const bool strided = vi >= 4;
-                    int ql = 0;
-                    if (strided) {
-                        // every wave gets exactly one window quad per row: the residues mod wpc must survive the
-                        // ring's wrap (NQ % wpc == 0) and a window must not be wider than wpc quads
-                        if (NQ % wpc != 0 || wsq > wpc) continue;
-                        ql = NQ / wpc;
-                        if (ql < 1 || ql > 4) continue;
-                    } else {
-                        for (int cand : {1, 2, 3, 4})
-                            if (!ql && wpc * cand * 256 >= N) ql = cand;
-                        // a wave must never hold both ends of a (wrapped) window: window quads + QL <= NQ
-                        if (!ql || wsq + ql > NQ) continue;
-                    }
-                    const int npad = wpc * ql * 256;
-                    auto wave_of = [&](int i) { return lsm_lif::ring_wave_of_quad(i >> 8, ql, wpc, strided); };
-                    std::vector<uint32_t> rptr((size_t)N * wpc + 1, 0u);
-                    int emax = 0;
-                    for (int j = 0; j < N; ++j)
-                        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e)
-                            if (win_off(j, csc_post[e]) < 0)
-                                emax = std::max(emax, (int)++rptr[(size_t)j * wpc + wave_of(csc_post[e]) + 1]);
-                    if (emax > 64) continue;                             // one lane per list entry
-                    for (size_t q = 1; q < rptr.size(); ++q) rptr[q] += rptr[q - 1];
-                    if (rptr.back() >= (1u << 24)) continue;             // the kernel packs a list's start into 24 bits
-                    std::vector<uint2> rem(std::max<size_t>(1, rptr.back()));
-                    std::vector<uint32_t> fill(rptr.begin(), rptr.end() - 1);
-                    for (int j = 0; j < N; ++j)
-                        for (int e = csc_ptr[j]; e < csc_ptr[j + 1]; ++e) {
-                            const int i = csc_post[e];
-                            if (win_off(j, i) >= 0) continue;
-                            uint32_t bits;
-                            std::memcpy(&bits, &csc_w[e], 4);
-                            rem[fill[(size_t)j * wpc + wave_of(i)]++] =
-                                make_uint2((uint32_t)lsm_lif::ring_acc_word(i) * 4u, bits);
-                        }
-                    std::vector<float> lk(npad, 0.0f);
-                    std::vector<int> os(npad, -1);
-                    for (int i = 0; i < N; ++i) lk[i] = leak[i];
-                    for (int o = 0; o < n_out; ++o) os[out_idx[o]] = o;
-                    // input map per owner wave, packed (lsm_lif::ring_pack_entry), padded with zero entries to whole
-                    // blocks of RING_ENT_BLOCK so that the kernel's drive needs no guards
-                    std::vector<std::vector<uint32_t>> per(wpc);
-                    for (int c = 0; c < C; ++c)
-                        for (int d = 0; d < in_fanout; ++d) {
-                            const int tgt = in_tgt[(size_t)c * in_fanout + d];
-                            per[wave_of(tgt)].push_back(lsm_lif::ring_pack_entry(c, tgt));
-                        }
-                    size_t mx = 1;
-                    for (auto &pp : per) mx = std::max(mx, pp.size());
-                    const int blk = lsm_lif::RING_ENT_BLOCK;
-                    const int einw = (int)((mx + blk - 1) / blk * blk);
-                    // padding entry at index e: channel 0 into dump word e % 64 -- every lane its OWN dump word (64 lanes
-                    // adding to one LDS word serialise: zero-padding cost cfg4 5 ms, profiles/r04_ring_input_drive.txt)
-                    std::vector<uint32_t> ent((size_t)wpc * einw);
-                    for (size_t e = 0; e < ent.size(); ++e) ent[e] = (uint32_t)((e % 64) * 4);
-                    for (int w = 0; w < wpc; ++w)
-                        std::copy(per[w].begin(), per[w].end(), ent.begin() + (size_t)w * einw);
-                    RingVariant &v = h->rvar[vi];
-                    if ((rc = upload(&v.rem_ptr, rptr)) || (rc = upload(&v.rem, rem)) || (rc = upload(&v.leak, lk)) ||
-                        (rc = upload(&v.oslot, os)) || (rc = upload(&v.in_ent, ent))) {
-                        free_reservoir(h);
-                        return rc;
-                    }
-                    // INMASK form of the kernel (lif_ring.h): per-neuron channel masks in registers instead of the entry drive
-                    if (C <= 128 && h->leak_uniform && strided && ql <= 2) {
-                        std::vector<uint32_t> im((size_t)npad * 4, 0u);
-                        bool distinct = true;
-                        for (int c = 0; c < C; ++c)
-                            for (int d = 0; d < in_fanout; ++d) {
-                                const int tgt = in_tgt[(size_t)c * in_fanout + d];
-                                const int pc = coloured ? inperm[c] : c;
-                                uint32_t &word = im[(size_t)tgt * 4 + (pc >> 5)];
-                                distinct = distinct && !(word & (1u << (pc & 31)));
-                                word |= 1u << (pc & 31);
-                            }
-                        if (distinct) {
-                            if ((rc = upload(&v.inmask, im))) { free_reservoir(h); return rc; }
-                            v.incol = coloured;
-                        }
-                    }
-                    v.wpc = wpc; v.ql = ql; v.einw = einw; v.strided = strided; v.n_rem = rptr.back();
-                }
-                // Pair blocks (lif_pair.h): the same windows shared out in 128-neuron blocks, wave w owning the blocks
-                // w, w+wpc, ...: the residues must survive the ring's wrap (2*NQ % wpc == 0), a window must not touch more
-                // than wpc blocks, a wave at most four blocks (8 neurons per lane).  The kernel counts the input drive from
-                // four registers per neuron only (pair_input_words): C <= 128, or C <= 256 with a colouring.
-                const int NB = 2 * NQ;
-                const int pwpcs[3] = {4, 8, 16};
-                std::vector<uint32_t> im;
-                const int inform = pair_input_words(C, in_tgt, in_fanout, NB * 128, coloured, inperm, &im);
-                for (int vi = 0; vi < 3 && inform != 0; ++vi) {
-                    const int wpc = pwpcs[vi];
-                    std::vector<uint32_t> rptr;
-                    std::vector<uint2> rem;
-                    const int bl = pair_lists(N, wpc, csc_ptr, csc_post, csc_w, geo, &rptr, &rem);
-                    if (!bl) continue;
-                    const int npad = NB * 128;
-                    // the records carry device addresses (low halves): upload the lists first; a table that crosses a 4 GB
-                    // line (the kernel takes the high address bits from the table pointer) cannot serve this layout
-                    PairVariant &v = h->pvar[vi];
-                    if ((rc = upload(&v.rem, rem))) { free_reservoir(h); return rc; }
-                    const uint64_t band_a = reinterpret_cast<uint64_t>(h->band), rem_a = reinterpret_cast<uint64_t>(v.rem);
-                    if ((band_a >> 32) != ((band_a + (uint64_t)N * pitch) >> 32) ||
-                        (rem_a >> 32) != ((rem_a + (uint64_t)rem.size() * 8u) >> 32)) {
-                        (void)hipFree(v.rem);
-                        v.rem = nullptr;
-                        continue;
-                    }
-                    std::vector<uint4> rec;
-                    pair_records(N, wpc, geo, rptr, band_a, rem_a, &rec);
-                    std::vector<int> os(npad, -1);
-                    for (int o = 0; o < n_out; ++o) os[out_idx[o]] = o;
-                    if ((rc = upload(&v.rec, rec)) || (rc = upload(&v.oslot, os)) || (rc = upload(&v.inmask, im))) {
-                        free_reservoir(h);
-                        return rc;
-                    }
-                    if (!h->leak_uniform) {                              // a coefficient per neuron (LEAKV form of the kernel)
-                        std::vector<float> lk(npad, 0.0f);
-                        for (int i = 0; i < N; ++i) lk[i] = leak[i];
-                        if ((rc = upload(&v.leak, lk))) { free_reservoir(h); return rc; }
-                    }
-                    v.inform = inform;
-                    v.wpc = wpc; v.bl = bl; v.n_rem = rptr.back();
-                }
-            }
-        }
+
+    // Ring rows for ring-like graphs (lif_ring.h, lif_pair.h).  (The ring kernel counts a neuron's active input entries of
+    // a step in 16 bits.)
+    std::vector<uint32_t> fanin(N, 0u);
+    uint32_t max_fanin = 0;
+    for (size_t e = 0; e < (size_t)net.C * in_fanout; ++e) max_fanin = std::max(max_fanin, ++fanin[in_tgt[e]]);
+    RingGeometry geo;
+    if (max_fanin <= 65535u && ring_geometry(net, &geo)) {
+        std::vector<float> band;
+        ring_windows(net, geo, &band);
+        if ((rc = upload(&h->band, band))) return rc;
+        h->band_pitch = geo.pitch; h->band_h = geo.H; h->band_nq = geo.NQ; h->band_wsq = geo.wsq;
+        for (int j = 0; j < N; ++j) h->band_bytes_sum += geo.nbytes[j];
+        for (int vi = 0; vi < 8; ++vi)
+            if ((rc = build_quads(h.get(), net, geo, vi))) return rc;
+        std::vector<uint32_t> im;
+        const int inform = pair_input_words(net, geo.NQ * 256, &im);
+        for (int vi = 0; vi < 3 && inform != 0; ++vi)
+            if ((rc = build_pairs(h.get(), net, geo, vi, inform, im))) return rc;
     }
-    // dense rows now, unless auto mode will serve this reservoir with ring rows: the table exceeds the L2 caches, ring
-    // rows exist AND one of their layouts fits a CU's LDS with room to spare (probed at 1024 time steps; the
-    // reference runs 400).  Then the 64-262 MB table and its upload would be dead weight next to the ring table
-    // (ADVICE r2); lsm_reservoir_set_kernel(2) still builds it on request.  When no ring layout fits (e.g. N = 8000
-    // with 5000 output neurons) the dense kernel is auto mode's fallback and needs its table from the start.
-    {
-        bool ring_serves = false;
-        if (has_ring(h) && (size_t)N * (size_t)h->ld * 4 > RING_AUTO_MIN_DENSE_BYTES)
-            for (const auto &v : h->rvar)
-                if (v.wpc && ring_lds_bytes(h, v, 1024) <= 160 * 1024) ring_serves = true;
-        // (a pair-block layout implies strided quad layouts of the same table exist; the quads decide)
-        if (!ring_serves && (rc = ensure_dense_rows(h))) { free_reservoir(h); return rc; }
-    }
-    *out = h;
+    if (!ring_serves_auto(h.get()) && (rc = ensure_dense_rows(h.get()))) return rc;
+    *out = h.release();
     return LSM_OK;
 }
 
@@ -796,24 +813,28 @@ extern "C" __attribute__((visibility("default")))
 int lsm_reservoir_set_kernel(lsm_reservoir *h, int mode)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_set_kernel: null handle");
-    LSM_REQUIRE(mode >= 0 && mode <= 6, "mode must be 0 (auto), 1 (sparse), 2 (dense), 3 (ring), 4 (ring, contiguous quads), "
+    LSM_REQUIRE(mode >= MODE_AUTO && mode <= MODE_RING_QUADS, "mode must be 0 (auto), 1 (sparse), 2 (dense), 3 (ring), 4 (ring, contiguous quads), "
                 "5 (ring, pair blocks) or 6 (ring, quads)");
-    LSM_REQUIRE(mode < 3 || has_ring(h), "this reservoir has no ring-row format (not ring-like, or too small)");
-    LSM_REQUIRE(mode != 5 || has_pairs(h), "this reservoir has no pair-block ring layout (needs at most 256 channels -- above 128 "
+    LSM_REQUIRE(mode < MODE_RING || has_ring(h), "this reservoir has no ring-row format (not ring-like, or too small)");
+    LSM_REQUIRE(mode != MODE_RING_PAIRS || has_pairs(h), "this reservoir has no pair-block ring layout (needs at most 256 channels -- above 128 "
                 "with bit positions in which the channels feeding one neuron differ mod 32, so at most 32 channels per neuron --, "
                 "an input map that names no neuron twice in one channel, a block count that is a multiple of 4, 8 or 16 waves and "
                 "a window of at most that many blocks)");
-    if (mode == 2) {                       // an explicit request builds the table a ring-served reservoir deferred
+    if (mode == MODE_DENSE) {                       // an explicit request builds the table a ring-served reservoir deferred
         const int rc = ensure_dense_rows(h);
         if (rc) return rc;
         LSM_REQUIRE(h->wt != nullptr, "this reservoir has no dense row table");
     }
-    h->mode = mode;
+    h->mode = static_cast<KernelMode>(mode);
     return LSM_OK;
 }
 
 extern "C" __attribute__((visibility("default")))
-int lsm_reservoir_destroy(lsm_reservoir *h) { return free_reservoir(h); }
+int lsm_reservoir_destroy(lsm_reservoir *h)
+{
+    delete h;
+    return LSM_OK;
+}
 
 static bool lif_inreg(const Variant &v) { return v.einw <= IN_REG_SLOTS * 64; }
 
@@ -824,12 +845,16 @@ static bool ring_inreg(const RingVariant &rv)
     return rv.einw <= lsm_lif::RING_ENT_BLOCK * lsm_lif::RING_ENT_REG_BLOCKS && rv.ql <= 2 && rv.strided;
 }
 
+// words of a step's input bit row
+static size_t input_words(const lsm_reservoir *h) { return (size_t)(h->C + 31) / 32; }
+
+// What every kernel keeps in LDS behind its own arrays: the feature accumulators and the clip's input bits.
+static size_t lds_tail_bytes(const lsm_reservoir *h, int T) { return (size_t)h->n_out * 16 + (size_t)T * input_words(h) * 4; }
 
 static size_t lif_lds_core(const lsm_reservoir *h, const Variant &v, int T)
 {
     const size_t npad = (size_t)v.sl * 64 * v.wpc;
-    const size_t cw = (size_t)(h->C + 31) / 32;
-    return npad * 4 + npad * 4 + 2 * npad * 2 + 128 + (size_t)h->n_out * 16 + (size_t)T * cw * 4;
+    return npad * 4 + npad * 4 + 2 * npad * 2 + 128 + lds_tail_bytes(h, T);
 }
 
 static size_t lif_seg_bytes(const lsm_reservoir *h, const Variant &v)
@@ -852,22 +877,20 @@ static size_t lif_lds_bytes(const lsm_reservoir *h, const Variant &v, int T)
 static size_t ring_lds_bytes(const lsm_reservoir *h, const RingVariant &v, int T)
 {
     const size_t npad = (size_t)v.ql * 256 * v.wpc;
-    const size_t cw = (size_t)(h->C + 31) / 32;
     // float32 accumulators + 16-bit input counts (each behind 64 dump words; no counts when the kernel counts from
     // per-neuron masks, INMASK), two step lists, quad counts, feature accumulators, the clip's input bits
     const size_t cnt_words = v.inmask ? 0 : (size_t)lsm_lif::RING_DUMP_WORDS + npad / 2;
     return ((size_t)lsm_lif::RING_DUMP_WORDS + npad + cnt_words) * 4 +
-           2 * npad * 2 + 512 + (size_t)h->n_out * 16 + (size_t)T * cw * 4;
+           2 * npad * 2 + 512 + lds_tail_bytes(h, T);
 }
 
 static size_t pair_lds_bytes(const lsm_reservoir *h, const PairVariant &v, int T)
 {
     const size_t npad = (size_t)v.bl * 128 * v.wpc;
-    const size_t cw = (size_t)(h->C + 31) / 32;
     // dump words, float32 accumulators, 64 scratch words per wave, two step lists of bytes, block counts, feature
     // accumulators, the clip's input bits
     return (size_t)lsm_lif::PAIR_DUMP_BYTES + npad * 4 + (size_t)v.wpc * 256 + 2 * npad +
-           (size_t)lsm_lif::PAIR_WCNT_WORDS * 4 + (size_t)h->n_out * 16 + (size_t)T * cw * 4;
+           (size_t)lsm_lif::PAIR_WCNT_WORDS * 4 + lds_tail_bytes(h, T);
 }
 
 // Static LDS bytes of a pair-block kernel, asked once per kernel for the life of the process.  lif_pair.h addresses LDS
@@ -896,7 +919,7 @@ constexpr bool PAIR_WIDE_AUTO = false;
 // Pair-block layout for a batch: the requested waves per clip, else the fewest waves (every wave repeats the per-row work).
 static const PairVariant *choose_pair(const lsm_reservoir *h, int T, int requested)
 {
-    if (h->mode != 0 && h->mode != 3 && h->mode != 5) return nullptr;
+    if (h->mode != MODE_AUTO && h->mode != MODE_RING && h->mode != MODE_RING_PAIRS) return nullptr;
     for (const auto &v : h->pvar) {
         if (!v.wpc || pair_lds_bytes(h, v, T) > 160 * 1024) continue;
         if (requested > 0 && v.wpc != requested) continue;
@@ -905,11 +928,11 @@ static const PairVariant *choose_pair(const lsm_reservoir *h, int T, int request
         // against 2.95 in quads, N = 4000 (4 blocks) 4.17 against 5.10, N = 3072 (3 blocks, 8 waves) 3.47 against 3.45 --
         // but N = 2048 (2 blocks, 8 waves) 2.46 against 2.19: with few neurons per lane the per-wave work per row dominates
         // and the quads' four fat waves win.
-        if (h->mode != 5 && v.bl < 3 && has_ring(h)) continue;
+        if (h->mode != MODE_RING_PAIRS && v.bl < 3 && has_ring(h)) continue;
         // Above 128 channels (bit planes, inform 3): by name only while PAIR_WIDE_AUTO is off, and never by default where the
         // layout needs 16 waves (N = 8000 with 256 filters: the quads run at 99 % of the gather ceiling there, 16 waves repeat
         // the per-row work of 8: N = 8000 strided quads, 8 waves 29.0 ms, 16 waves 36.8 ms).
-        if (h->mode != 5 && v.inform == 3 && (v.wpc == 16 || !PAIR_WIDE_AUTO)) continue;
+        if (h->mode != MODE_RING_PAIRS && v.inform == 3 && (v.wpc == 16 || !PAIR_WIDE_AUTO)) continue;
         return &v;
     }
     return nullptr;
@@ -929,10 +952,10 @@ static const RingVariant *choose_ring(const lsm_reservoir *h, int T, int request
         if (v4 != b4) return v4;
         return v4 ? v.wpc < b.wpc : v.wpc > b.wpc;
     };
-    if (h->mode == 5) return nullptr;             // pair blocks only
+    if (h->mode == MODE_RING_PAIRS) return nullptr;
     for (const auto &v : h->rvar) {
         if (!v.wpc || ring_lds_bytes(h, v, T) > 160 * 1024) continue;
-        if (v.strided && h->mode == 4) continue;
+        if (v.strided && h->mode == MODE_RING_CONTIGUOUS) continue;
         if (requested > 0 && v.wpc != requested) continue;
         if (!best || better(v, *best)) best = &v;
     }
@@ -942,16 +965,15 @@ static const RingVariant *choose_ring(const lsm_reservoir *h, int T, int request
 static bool want_ring(const lsm_reservoir *h)
 {
     if (!has_ring(h)) return false;
-    if (h->mode >= 3) return true;
-    return h->mode == 0 && (size_t)h->N * (size_t)h->ld * 4 > RING_AUTO_MIN_DENSE_BYTES;
+    if (h->mode >= MODE_RING) return true;
+    return h->mode == MODE_AUTO && (size_t)h->N * (size_t)h->ld * 4 > RING_AUTO_MIN_DENSE_BYTES;
 }
-static bool use_dense(const lsm_reservoir *h) { return h->wt != nullptr && h->mode != 1; }
+static bool use_dense(const lsm_reservoir *h) { return h->wt != nullptr && h->mode != MODE_SPARSE; }
 
 static size_t dense_lds_bytes(const lsm_reservoir *h, const Variant &v, int T)
 {
     const size_t npad = (size_t)v.sl * 64 * v.wpc;
-    const size_t cw = (size_t)(h->C + 31) / 32;
-    return npad * 4 + 2 * npad * 2 + 512 + (size_t)h->n_out * 16 + (size_t)T * cw * 4;
+    return npad * 4 + 2 * npad * 2 + 512 + lds_tail_bytes(h, T);
 }
 
 // Pick the waves-per-clip layout.  Measured on MI355X at N=1000 (profiles/): the best layout has
@@ -1074,9 +1096,9 @@ __global__ __launch_bounds__(256) void clip_rank_kernel(const int32_t *keys, int
 // large ring-like reservoirs but FALLS THROUGH to the dense (else sparse) kernel when no ring layout fits -- the
 // per-clip LDS image exceeds 160 KB (e.g. N = 8000 with 5000 output neurons: 175.7 KB as ring rows, 158.8 KB
 // for the dense/sparse layouts) or the reservoir's ring layouts lack the requested waves per clip.
-// Only an explicit ring request (modes 3, 4) is a hard error then.
+// Only an explicit ring request (MODE_RING and above) is a hard error then.
 struct RunPlan {
-    int kernel = 0;                   // 1 sparse, 2 dense rows, 3 ring rows
+    PlannedKernel kernel = KERNEL_NONE;
     const PairVariant *pv = nullptr;  // ring rows in pair blocks (lif_pair.h) when set, else
     const RingVariant *rv = nullptr;
     const Variant *v = nullptr;
@@ -1087,17 +1109,137 @@ static int make_plan(const lsm_reservoir *h, int n_clips, int n_steps, int waves
     if (want_ring(h)) {
         // pair blocks where the reservoir has them (cfg4: 5.1 -> see profiles/r05_*), else quads
         p->pv = choose_pair(h, n_steps, waves_per_clip > 0 ? waves_per_clip : 0);
-        if (p->pv) { p->kernel = 3; return LSM_OK; }
+        if (p->pv) { p->kernel = KERNEL_RING; return LSM_OK; }
         p->rv = choose_ring(h, n_steps, waves_per_clip > 0 ? waves_per_clip : 0);
-        if (p->rv) { p->kernel = 3; return LSM_OK; }
-        LSM_REQUIRE(h->mode < 3, "no ring-row layout for waves_per_clip=%d (N=%d, n_out=%d, T=%d): none fits a CU's "
+        if (p->rv) { p->kernel = KERNEL_RING; return LSM_OK; }
+        LSM_REQUIRE(h->mode < MODE_RING, "no ring-row layout for waves_per_clip=%d (N=%d, n_out=%d, T=%d): none fits a CU's "
                     "160 KB of LDS or has that many waves", waves_per_clip, h->N, h->n_out, n_steps);
     }
     p->v = choose_variant(h, n_clips, n_steps, waves_per_clip);
     LSM_REQUIRE(p->v != nullptr, "no reservoir layout for waves_per_clip=%d (N=%d, n_out=%d, T=%d)",
                 waves_per_clip, h->N, h->n_out, n_steps);
-    p->kernel = use_dense(h) ? 2 : 1;
+    p->kernel = use_dense(h) ? KERNEL_DENSE : KERNEL_SPARSE;
     return LSM_OK;
+}
+
+struct RunArgs {                // what one run is given, as the launch functions below pass it on
+    const uint8_t *raster;
+    int n_clips, n_steps, n_keys;
+    const int32_t *key_ids, *order;     // order: clip of workgroup g (longest clips first), or null
+    float *features, *v_trace;
+    uint8_t *spike_matrix;
+    int32_t *stats;
+    void *stream;
+};
+
+// The fields LifArgs, DenseArgs, RingArgs and PairArgs have in common.
+template <typename Args>
+static void set_common_args(Args *a, const lsm_reservoir *h, const RunArgs &r)
+{
+    a->N = h->N; a->C = h->C; a->T = r.n_steps; a->B = r.n_clips;
+    a->n_out = h->n_out; a->CW = (int)input_words(h);
+    a->refractory = h->refractory; a->burst_isi_max = h->burst_isi_max;
+    a->theta = h->theta; a->w_in = h->w_in;
+    a->raster = r.raster;
+    a->n_keys = r.n_keys;
+    for (int k = 0; k < 8; ++k) a->key_ids[k] = k < r.n_keys ? r.key_ids[k] : 0;
+    a->features = r.features; a->spike_matrix = r.spike_matrix; a->v_trace = r.v_trace;
+    a->stats = r.stats; a->order = r.order;
+}
+
+// One workgroup of wpc waves per clip, `lds` bytes of dynamic LDS.
+template <typename Args>
+static int launch(void (*fn)(const Args), const Args &a, const RunArgs &r, int wpc, size_t lds)
+{
+    if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+    hipLaunchKernelGGL(fn, dim3(r.n_clips), dim3(wpc * 64), lds, (hipStream_t)r.stream, a);
+    LSM_CHECK_HIP(hipGetLastError());
+    return LSM_OK;
+}
+
+static int run_pairs(const lsm_reservoir *h, const PairVariant &pv, const RunArgs &r)
+{
+    const int inmask = pv.inform;
+    const bool leakv = pv.leak != nullptr;
+    static lsm_lif::pair_fn_t (*const wide[4])(int, bool) = {lsm_lif::pick_pair_wide_1, lsm_lif::pick_pair_wide_2,
+                                                             lsm_lif::pick_pair_wide_3, lsm_lif::pick_pair_wide_4};
+    static lsm_lif::pair_fn_t (*const masks[4])(int, int, bool) = {lsm_lif::pick_pair_1, lsm_lif::pick_pair_2,
+                                                                   lsm_lif::pick_pair_3, lsm_lif::pick_pair_4};
+    lsm_lif::pair_fn_t pfn = inmask == 3 ? wide[pv.bl - 1](pv.wpc, leakv) : masks[pv.bl - 1](pv.wpc, inmask, leakv);
+    // (bit planes: 5..8 row words, and the whole input image is T * cw words -- pair_lds_bytes)
+    const size_t cw = input_words(h);
+    LSM_REQUIRE(inmask != 3 || (cw >= 5 && cw <= 8), "pair-block bit planes with %zu row words", cw);
+    LSM_REQUIRE(pfn != nullptr, "no pair-block ring kernel for BL=%d WPC=%d", pv.bl, pv.wpc);
+    size_t static_lds = 0;
+    const int src = pair_static_lds(reinterpret_cast<const void *>(pfn), &static_lds);
+    if (src != LSM_OK) return src;
+    if (static_lds != 0) {
+        lsm_set_error("pair-block ring kernel BL=%d WPC=%d has %zu bytes of static LDS: its row loop addresses LDS "
+                      "absolutely and needs its dynamic LDS to start at byte 0 (defective build)", pv.bl, pv.wpc,
+                      static_lds);
+        return LSM_ERR_UNSUPPORTED;
+    }
+    lsm_lif::PairArgs a;
+    set_common_args(&a, h, r);
+    a.leak_u = h->leak_u;
+    a.band = h->band.get(); a.rec = pv.rec.get(); a.rem = pv.rem.get();
+    a.oslot = pv.oslot.get(); a.leak = pv.leak.get(); a.inmask = pv.inmask.get();
+    a.inperm = pv.inform >= 2 ? h->inperm.get() : nullptr;
+    return launch(pfn, a, r, pv.wpc, pair_lds_bytes(h, pv, r.n_steps));
+}
+
+static int run_quads(const lsm_reservoir *h, const RingVariant &rv, const RunArgs &r)
+{
+    const bool inreg = ring_inreg(rv);
+    const bool inmask = rv.inmask != nullptr;
+    lsm_lif::ring_fn_t rfn = inmask ? (rv.ql == 1 ? lsm_lif::pick_ring_mask_1(rv.wpc, rv.incol ? 2 : 1)
+                                                  : lsm_lif::pick_ring_mask_2(rv.wpc, rv.incol ? 2 : 1))
+                             : rv.ql == 1 ? lsm_lif::pick_ring_1(rv.wpc, inreg, rv.strided)
+                             : rv.ql == 2 ? lsm_lif::pick_ring_2(rv.wpc, inreg, rv.strided)
+                             : rv.ql == 3 ? lsm_lif::pick_ring_3(rv.wpc, inreg, rv.strided)
+                                          : lsm_lif::pick_ring_4(rv.wpc, inreg, rv.strided);
+    LSM_REQUIRE(rfn != nullptr, "no ring kernel for QL=%d WPC=%d", rv.ql, rv.wpc);
+    lsm_lif::RingArgs a;
+    set_common_args(&a, h, r);
+    a.EinW = rv.einw;
+    a.H = h->band_h; a.NQ = h->band_nq; a.pitch = h->band_pitch;
+    a.band = h->band.get(); a.rem_ptr = rv.rem_ptr.get(); a.rem = rv.rem.get();
+    a.leak = rv.leak.get(); a.oslot = rv.oslot.get(); a.in_ent = rv.in_ent.get();
+    a.inmask = rv.inmask.get(); a.inperm = (inmask && rv.incol) ? h->inperm.get() : nullptr; a.leak_u = h->leak_u;
+    return launch(rfn, a, r, rv.wpc, ring_lds_bytes(h, rv, r.n_steps));
+}
+
+static int run_dense(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
+{
+    // the reference's refractory period (2 steps) counts down in scalar lane masks (lif_dense.h, REFM)
+    const bool refm = h->refractory == lsm_lif::DENSE_REFM_REFRACTORY;
+    lsm_lif::dense_fn_t dfn = v.inmask      ? (v.incol ? lsm_lif::pick_dense_3(v.sl, v.wpc, refm)
+                                                       : lsm_lif::pick_dense_2(v.sl, v.wpc, refm))
+                              : lif_inreg(v) ? lsm_lif::pick_dense_1(v.sl, v.wpc, refm)
+                                             : lsm_lif::pick_dense_0(v.sl, v.wpc, refm);
+    LSM_REQUIRE(dfn != nullptr, "no dense kernel for SL=%d WPC=%d", v.sl, v.wpc);
+    lsm_lif::DenseArgs a;
+    set_common_args(&a, h, r);
+    a.EinW = v.einw; a.ld = h->ld;
+    a.wt = h->wt.get(); a.leak = v.leak.get(); a.oslot = v.oslot.get(); a.in_ent = v.in_ent.get();
+    a.inmask = v.inmask.get();
+    a.inperm = v.incol ? h->inperm.get() : nullptr;
+    const size_t lds = dense_lds_bytes(h, v, r.n_steps);
+    LSM_REQUIRE(lds <= 160 * 1024, "dense layout needs %zu bytes of LDS", lds);
+    return launch(dfn, a, r, v.wpc, lds);
+}
+
+static int run_sparse(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
+{
+    lif_fn_t fn = pick_kernel(v.sl, v.wpc, lif_inreg(v), lif_seg_in_lds(h, v, r.n_steps));
+    LSM_REQUIRE(fn != nullptr, "no kernel for SL=%d WPC=%d", v.sl, v.wpc);
+    LifArgs a;
+    set_common_args(&a, h, r);
+    a.EinW = v.einw;
+    a.rowptr = h->rowptr.get(); a.segoff = v.segoff.get();
+    a.seg = v.seg.get(); a.syn = h->syn.get(); a.leak = v.leak.get(); a.oslot = v.oslot.get();
+    a.in_ent = v.in_ent.get();
+    return launch(fn, a, r, v.wpc, lif_lds_bytes(h, v, r.n_steps));
 }
 
 static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
@@ -1117,13 +1259,10 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                 h->device, dev_now);
     for (int k = 0; k < n_keys; ++k)
         LSM_REQUIRE(key_ids[k] >= 0 && key_ids[k] < 8, "key id %d out of range", key_ids[k]);
-    const size_t cw = (size_t)(h->C + 31) / 32;
 
     RunPlan plan;
-    {
-        const int prc = make_plan(h, n_clips, n_steps, waves_per_clip, &plan);
-        if (prc) return prc;
-    }
+    const int prc = make_plan(h, n_clips, n_steps, waves_per_clip, &plan);
+    if (prc) return prc;
     // longest clips first, when the launch has more workgroups than the chip has CUs (else every clip starts at once)
     const int32_t *order = nullptr;
     if (workspace) {
@@ -1142,127 +1281,13 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
             order = ord;
         }
     }
-    if (plan.kernel == 3 && plan.pv) {
-        const PairVariant *pv = plan.pv;
-        const int inmask = pv->inform;
-        const bool leakv = pv->leak != nullptr;
-        lsm_lif::pair_fn_t pfn = inmask == 3 ? (pv->bl == 1 ? lsm_lif::pick_pair_wide_1(pv->wpc, leakv)
-                                                : pv->bl == 2 ? lsm_lif::pick_pair_wide_2(pv->wpc, leakv)
-                                                : pv->bl == 3 ? lsm_lif::pick_pair_wide_3(pv->wpc, leakv)
-                                                              : lsm_lif::pick_pair_wide_4(pv->wpc, leakv))
-                                 : pv->bl == 1 ? lsm_lif::pick_pair_1(pv->wpc, inmask, leakv)
-                                 : pv->bl == 2 ? lsm_lif::pick_pair_2(pv->wpc, inmask, leakv)
-                                 : pv->bl == 3 ? lsm_lif::pick_pair_3(pv->wpc, inmask, leakv)
-                                               : lsm_lif::pick_pair_4(pv->wpc, inmask, leakv);
-        // (bit planes: 5..8 row words, and the whole input image is T * cw words -- pair_lds_bytes)
-        LSM_REQUIRE(inmask != 3 || (cw >= 5 && cw <= 8), "pair-block bit planes with %zu row words", cw);
-        LSM_REQUIRE(pfn != nullptr, "no pair-block ring kernel for BL=%d WPC=%d", pv->bl, pv->wpc);
-        size_t static_lds = 0;
-        const int src = pair_static_lds(reinterpret_cast<const void *>(pfn), &static_lds);
-        if (src != LSM_OK) return src;
-        if (static_lds != 0) {
-            lsm_set_error("pair-block ring kernel BL=%d WPC=%d has %zu bytes of static LDS: its row loop addresses LDS "
-                          "absolutely and needs its dynamic LDS to start at byte 0 (defective build)", pv->bl, pv->wpc,
-                          static_lds);
-            return LSM_ERR_UNSUPPORTED;
-        }
-        lsm_lif::PairArgs r;
-        r.N = h->N; r.C = h->C; r.T = n_steps; r.B = n_clips;
-        r.n_out = h->n_out; r.CW = (int)cw;
-        r.refractory = h->refractory; r.burst_isi_max = h->burst_isi_max;
-        r.theta = h->theta; r.w_in = h->w_in; r.leak_u = h->leak_u;
-        r.raster = spikes_u8; r.band = h->band; r.rec = pv->rec; r.rem = pv->rem;
-        r.oslot = pv->oslot; r.leak = pv->leak; r.inmask = pv->inmask; r.inperm = pv->inform >= 2 ? h->inperm : nullptr;
-        r.n_keys = n_keys;
-        for (int k = 0; k < 8; ++k) r.key_ids[k] = k < n_keys ? key_ids[k] : 0;
-        r.features = features_out; r.spike_matrix = spike_matrix_out; r.v_trace = v_trace_out;
-        r.stats = stats_out; r.order = order;
-        const size_t lds = pair_lds_bytes(h, *pv, n_steps);
-        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(pfn));
-        hipLaunchKernelGGL(pfn, dim3(n_clips), dim3(pv->wpc * 64), lds, (hipStream_t)stream, r);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
-    }
-    if (plan.kernel == 3) {
-        const RingVariant *rv = plan.rv;
-        const bool inreg = ring_inreg(*rv);
-        const bool inmask = rv->inmask != nullptr;
-        lsm_lif::ring_fn_t rfn = inmask ? (rv->ql == 1 ? lsm_lif::pick_ring_mask_1(rv->wpc, rv->incol ? 2 : 1)
-                                                       : lsm_lif::pick_ring_mask_2(rv->wpc, rv->incol ? 2 : 1))
-                                 : rv->ql == 1 ? lsm_lif::pick_ring_1(rv->wpc, inreg, rv->strided)
-                                 : rv->ql == 2 ? lsm_lif::pick_ring_2(rv->wpc, inreg, rv->strided)
-                                 : rv->ql == 3 ? lsm_lif::pick_ring_3(rv->wpc, inreg, rv->strided)
-                                               : lsm_lif::pick_ring_4(rv->wpc, inreg, rv->strided);
-        LSM_REQUIRE(rfn != nullptr, "no ring kernel for QL=%d WPC=%d", rv->ql, rv->wpc);
-        lsm_lif::RingArgs r;
-        r.N = h->N; r.C = h->C; r.T = n_steps; r.B = n_clips;
-        r.n_out = h->n_out; r.CW = (int)cw; r.EinW = rv->einw;
-        r.refractory = h->refractory; r.burst_isi_max = h->burst_isi_max;
-        r.H = h->band_h; r.NQ = h->band_nq; r.pitch = h->band_pitch;
-        r.theta = h->theta; r.w_in = h->w_in;
-        r.raster = spikes_u8; r.band = h->band; r.rem_ptr = rv->rem_ptr; r.rem = rv->rem;
-        r.leak = rv->leak; r.oslot = rv->oslot; r.in_ent = rv->in_ent;
-        r.inmask = rv->inmask; r.inperm = (inmask && rv->incol) ? h->inperm : nullptr; r.leak_u = h->leak_u;
-        r.n_keys = n_keys;
-        for (int k = 0; k < 8; ++k) r.key_ids[k] = k < n_keys ? key_ids[k] : 0;
-        r.features = features_out; r.spike_matrix = spike_matrix_out; r.v_trace = v_trace_out;
-        r.stats = stats_out; r.order = order;
-        const size_t lds = ring_lds_bytes(h, *rv, n_steps);
-        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(rfn));
-        hipLaunchKernelGGL(rfn, dim3(n_clips), dim3(rv->wpc * 64), lds, (hipStream_t)stream, r);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
-    }
-    const Variant *v = plan.v;
-    if (plan.kernel == 2) {
-        // the reference's refractory period (2 steps) counts down in scalar lane masks (lif_dense.h, REFM)
-        const bool refm = h->refractory == lsm_lif::DENSE_REFM_REFRACTORY;
-        lsm_lif::dense_fn_t dfn = v->inmask       ? (v->incol ? lsm_lif::pick_dense_3(v->sl, v->wpc, refm)
-                                                              : lsm_lif::pick_dense_2(v->sl, v->wpc, refm))
-                                  : lif_inreg(*v) ? lsm_lif::pick_dense_1(v->sl, v->wpc, refm)
-                                                  : lsm_lif::pick_dense_0(v->sl, v->wpc, refm);
-        LSM_REQUIRE(dfn != nullptr, "no dense kernel for SL=%d WPC=%d", v->sl, v->wpc);
-        lsm_lif::DenseArgs d;
-        d.N = h->N; d.C = h->C; d.T = n_steps; d.B = n_clips;
-        d.n_out = h->n_out; d.CW = (int)cw; d.EinW = v->einw;
-        d.refractory = h->refractory; d.burst_isi_max = h->burst_isi_max; d.ld = h->ld;
-        d.theta = h->theta; d.w_in = h->w_in;
-        d.raster = spikes_u8; d.wt = h->wt; d.leak = v->leak; d.oslot = v->oslot; d.in_ent = v->in_ent;
-        d.inmask = v->inmask;
-        d.inperm = v->incol ? h->inperm : nullptr;
-        d.n_keys = n_keys;
-        for (int k = 0; k < 8; ++k) d.key_ids[k] = k < n_keys ? key_ids[k] : 0;
-        d.features = features_out; d.spike_matrix = spike_matrix_out; d.v_trace = v_trace_out;
-        d.stats = stats_out; d.order = order;
-        const size_t dlds = dense_lds_bytes(h, *v, n_steps);
-        LSM_REQUIRE(dlds <= 160 * 1024, "dense layout needs %zu bytes of LDS", dlds);
-        if (dlds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(dfn));
-        hipLaunchKernelGGL(dfn, dim3(n_clips), dim3(v->wpc * 64), dlds, (hipStream_t)stream, d);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
-    }
-    lif_fn_t fn = pick_kernel(v->sl, v->wpc, lif_inreg(*v), lif_seg_in_lds(h, *v, n_steps));
-    LSM_REQUIRE(fn != nullptr, "no kernel for SL=%d WPC=%d", v->sl, v->wpc);
-
-    LifArgs a;
-    a.N = h->N; a.C = h->C; a.T = n_steps; a.B = n_clips;
-    a.n_out = h->n_out; a.CW = (int)cw; a.EinW = v->einw;
-    a.refractory = h->refractory; a.burst_isi_max = h->burst_isi_max;
-    a.theta = h->theta; a.w_in = h->w_in;
-    a.rowptr = h->rowptr; a.segoff = v->segoff;
-    a.raster = spikes_u8; a.seg = v->seg; a.syn = h->syn; a.leak = v->leak; a.oslot = v->oslot;
-    a.in_ent = v->in_ent;
-    a.n_keys = n_keys;
-    for (int k = 0; k < 8; ++k) a.key_ids[k] = k < n_keys ? key_ids[k] : 0;
-    a.features = features_out; a.spike_matrix = spike_matrix_out; a.v_trace = v_trace_out;
-    a.stats = stats_out; a.order = order;
-
-    const size_t lds = lif_lds_bytes(h, *v, n_steps);
-    if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
-    hipLaunchKernelGGL(fn, dim3(n_clips), dim3(v->wpc * 64), lds, (hipStream_t)stream, a);
-    LSM_CHECK_HIP(hipGetLastError());
-    return LSM_OK;
+    const RunArgs r = {spikes_u8, n_clips, n_steps, n_keys, key_ids, order, features_out, v_trace_out, spike_matrix_out, stats_out,
+                       stream};
+    if (plan.pv) return run_pairs(h, *plan.pv, r);
+    if (plan.rv) return run_quads(h, *plan.rv, r);
+    return plan.kernel == KERNEL_DENSE ? run_dense(h, *plan.v, r) : run_sparse(h, *plan.v, r);
 }
+
 
 extern "C" __attribute__((visibility("default")))
 int lsm_reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
@@ -1298,7 +1323,7 @@ int lsm_reservoir_plan(const lsm_reservoir *h, int n_clips, int n_steps, int wav
     const int rc = make_plan(h, n_clips, n_steps, waves_per_clip, &p);
     if (rc) return rc;
     if (kernel_out) *kernel_out = p.kernel;
-    if (p.kernel == 3 && p.pv) {
+    if (p.pv) {
         if (wpc_out) *wpc_out = p.pv->wpc;
         if (slots_out) *slots_out = p.pv->bl * 2;
         if (lds_bytes_out) *lds_bytes_out = (int)pair_lds_bytes(h, *p.pv, n_steps);
@@ -1306,7 +1331,7 @@ int lsm_reservoir_plan(const lsm_reservoir *h, int n_clips, int n_steps, int wav
             *table_bytes_out = (long)((size_t)h->N * h->band_pitch + p.pv->n_rem * 8 + (size_t)h->N * p.pv->wpc * 16);
         return LSM_OK;
     }
-    if (p.kernel == 3) {
+    if (p.rv) {
         if (wpc_out) *wpc_out = p.rv->wpc;
         if (slots_out) *slots_out = p.rv->ql * 4;
         if (lds_bytes_out) *lds_bytes_out = (int)ring_lds_bytes(h, *p.rv, n_steps);
@@ -1319,9 +1344,9 @@ int lsm_reservoir_plan(const lsm_reservoir *h, int n_clips, int n_steps, int wav
     if (wpc_out) *wpc_out = p.v->wpc;
     if (slots_out) *slots_out = p.v->sl;
     if (lds_bytes_out)
-        *lds_bytes_out = (int)(p.kernel == 2 ? dense_lds_bytes(h, *p.v, n_steps) : lif_lds_bytes(h, *p.v, n_steps));
+        *lds_bytes_out = (int)(p.kernel == KERNEL_DENSE ? dense_lds_bytes(h, *p.v, n_steps) : lif_lds_bytes(h, *p.v, n_steps));
     if (table_bytes_out)
-        *table_bytes_out = p.kernel == 2 ? (long)((size_t)h->N * h->ld * 4) : (long)(h->nnz * 8 + ((size_t)h->N + 1) * 4);
+        *table_bytes_out = p.kernel == KERNEL_DENSE ? (long)((size_t)h->N * h->ld * 4) : (long)(h->nnz * 8 + ((size_t)h->N + 1) * 4);
     return LSM_OK;
 }
 
@@ -1331,9 +1356,9 @@ int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, i
     if (h == nullptr) return LSM_ERR_ARG;
     RunPlan p;
     if (make_plan(h, n_clips, n_steps, waves_per_clip, &p) != LSM_OK) return LSM_ERR_UNSUPPORTED;
-    if (p.kernel == 3 && p.pv) return p.pv->inform == 3 ? 11 : (p.pv->inform == 2 ? 15 : 14);
-    if (p.kernel == 3) return p.rv->inmask ? (p.rv->incol ? 13 : 12) : (ring_inreg(*p.rv) ? 11 : 10);
-    if (p.kernel == 1) return 20;
+    if (p.pv) return p.pv->inform == 3 ? 11 : (p.pv->inform == 2 ? 15 : 14);
+    if (p.rv) return p.rv->inmask ? (p.rv->incol ? 13 : 12) : (ring_inreg(*p.rv) ? 11 : 10);
+    if (p.kernel == KERNEL_SPARSE) return 20;
     return p.v->inmask ? (p.v->incol ? 3 : 2) : (lif_inreg(*p.v) ? 1 : 0);
 }
 
@@ -1345,7 +1370,7 @@ int lsm_reservoir_ring_form(const lsm_reservoir *h, int n_clips, int n_steps, in
     if (h == nullptr) return LSM_ERR_ARG;
     RunPlan p;
     if (make_plan(h, n_clips, n_steps, waves_per_clip, &p) != LSM_OK) return LSM_ERR_UNSUPPORTED;
-    if (p.kernel != 3) return 0;
+    if (p.kernel != KERNEL_RING) return 0;
     return p.pv ? 3 : (p.rv->strided ? 2 : 1);
 }
 
@@ -1360,11 +1385,11 @@ int lsm_reservoir_row_request_bytes(const lsm_reservoir *h, int n_clips, int n_s
     const int rc = make_plan(h, n_clips, n_steps, waves_per_clip, &p);
     if (rc) return rc;
     const double n = (double)h->N;
-    if (p.kernel == 3 && p.pv)
+    if (p.pv)
         *mean_bytes_out = (h->band_bytes_sum + (double)p.pv->n_rem * 8.0) / n + p.pv->wpc * 16.0;
-    else if (p.kernel == 3)
+    else if (p.rv)
         *mean_bytes_out = (h->band_bytes_sum + (double)p.rv->n_rem * 8.0) / n + (p.rv->wpc + 1) * 4.0;
-    else if (p.kernel == 2)
+    else if (p.kernel == KERNEL_DENSE)
         *mean_bytes_out = (double)h->ld * 4.0;
     else
         *mean_bytes_out = (double)h->nnz * 8.0 / n + 8.0;
@@ -1385,6 +1410,6 @@ int lsm_reservoir_kernel_in_use(const lsm_reservoir *h)
 {
     if (h == nullptr) return LSM_ERR_ARG;
     RunPlan p;
-    if (make_plan(h, 1, 400, 0, &p) != LSM_OK) return want_ring(h) ? 3 : (use_dense(h) ? 2 : 1);
+    if (make_plan(h, 1, 400, 0, &p) != LSM_OK) return want_ring(h) ? KERNEL_RING : (use_dense(h) ? KERNEL_DENSE : KERNEL_SPARSE);
     return p.kernel;
 }
