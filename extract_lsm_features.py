@@ -115,8 +115,10 @@ def extract_all_features(lsm, spike_data, feature_keys, desc=""):
             print(f"{desc}: {n} clips" + (f" over {world} GPUs" if world > 1 else ""))
         rows = []
         for a in range(lo, hi, RUN_BATCH):
-            feats, _, _ = lsm.run_batch(np.ascontiguousarray(spike_data[a:min(hi, a + RUN_BATCH)]),
-                                        feature_keys)
+            batch = np.ascontiguousarray(spike_data[a:min(hi, a + RUN_BATCH)])
+            # clips longer than one launch holds on chip (the plan refuses them) run as launches that hand their state on
+            chunked = hasattr(lsm, "run_chunked") and batch.ndim == 3 and batch.shape[2] > lsm.max_steps(len(batch))
+            feats, _, _ = (lsm.run_chunked if chunked else lsm.run_batch)(batch, feature_keys)
             rows.append(feats)
         # an empty shard still takes part in the gather: its row width comes from an empty launch-free call,
         # so it is whatever run_batch makes of these keys (unknown keys are dropped there)

@@ -240,6 +240,44 @@ int lsm_reservoir_run_ordered(const lsm_reservoir *h, const uint8_t *spikes_u8, 
                               uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                               int waves_per_clip, void *workspace, long workspace_bytes, void *stream);
 
+/* Continuation (SPEC.md §4a): a launch that starts from a saved state and saves its own, so that a run split at any step
+ * gives, bit for bit, what the unsplit run gives -- clips longer than one launch's LDS image holds, and streams taken
+ * window by window.  lsm_reservoir_run and lsm_reservoir_run_ordered are untouched by it (an implicit reset() per launch).
+ *
+ * State: per clip one block of lsm_reservoir_state_bytes(h) bytes (a multiple of 16), clip b at byte b * that, DEVICE
+ * memory owned by the caller, 16-byte aligned.  With NP = num_neurons rounded up to 64:
+ *     uint32 header[4]          {spikes of the whole reservoir so far, 0, 0, 0}
+ *     float  v[NP]              membrane potentials (entries past num_neurons: 0)
+ *     uint16 ref[NP]            refractory countdowns
+ *     uint32 last_spikes[NP/32] bit i: neuron i fired at the last step done
+ *     uint32 ever_fired[NP/32]  bit i: neuron i fired at least once
+ *     uint32 feat[n_out][4]     per output neuron {n | bursts << 16, first | last << 16, S1, Q} (SPEC.md §4, absolute times)
+ * The layout does not depend on the kernel, the waves per clip or the layout a launch ran with: consecutive launches may
+ * differ in all of them.  ALL ZEROS IS reset().
+ *
+ * lsm_reservoir_run_from runs steps [first_step, first_step + n_steps) of every clip:
+ *   first_step   HOST value: the steps done before (what the state holds); the library never reads device memory to check it
+ *   state_in     state after step first_step - 1, or NULL: reset (first_step must then be 0)
+ *   state_out    receives the state after step first_step + n_steps - 1, or NULL; may equal state_in (each clip's block is
+ *                read at the start and written at the end of the same workgroup)
+ *   features_out features of steps [0, first_step + n_steps) -- spike times are absolute, spike_variances uses
+ *                T = first_step + n_steps --, or NULL with n_keys = 0
+ *   spike_matrix_out, v_trace_out   (n_clips, n_steps, N): this launch's steps only
+ *   stats_out    totals of [0, first_step + n_steps)
+ *   order_workspace   NULL: clips start in index order; else as lsm_reservoir_run_ordered's workspace
+ * Everything else as lsm_reservoir_run, including the refusals of the plan for n_steps (lsm_reservoir_max_steps gives the
+ * longest launch the plan accepts: chunks of at most that serve any clip).  LSM_ERR_ARG for first_step < 0,
+ * first_step + n_steps > 65535, first_step > 0 without state_in, a state pointer that is not 16-byte aligned.  With both
+ * states NULL it is lsm_reservoir_run. */
+long lsm_reservoir_state_bytes(const lsm_reservoir *h);
+int lsm_reservoir_run_from(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                           int first_step, const void *state_in, void *state_out,
+                           const int32_t *key_ids, int n_keys, float *features_out,
+                           uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                           int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream);
+/* Largest n_steps lsm_reservoir_plan accepts for (n_clips, waves_per_clip), at most 65535; < 0 when it accepts none. */
+int lsm_reservoir_max_steps(const lsm_reservoir *h, int n_clips, int waves_per_clip);
+
 /* Layout that lsm_reservoir_run would use: waves per clip, 64-neuron slots per lane, LDS bytes. */
 int lsm_reservoir_layout(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip,
                          int *wpc_out, int *slots_out, int *lds_bytes_out);

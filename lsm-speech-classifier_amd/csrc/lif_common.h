@@ -118,4 +118,111 @@ __device__ __forceinline__ void write_features(float *features, const uint4 *fea
     }
 }
 
+// ---- continuation (SPEC.md §4a, include/lsm_hip.h: lsm_reservoir_run_from) ----------------------------------------------
+// One block per clip, the same for every kernel and layout, all zeros = reset():
+//   uint32 header[4] {spikes of the whole reservoir so far, 0, 0, 0} | float v[NP] | uint16 ref[NP] |
+//   uint32 last_spikes[NP/32] | uint32 ever_fired[NP/32] | uint4 feat[n_out],     NP = N rounded up to 64.
+// The ST forms of the kernels (template parameter, off in every stateless form) convert it into their own registers and
+// step lists in the prologue and back in the epilogue; the step loops run on local times 0 .. T-1 either way.
+struct StateArgs {
+    const unsigned char *in;   // (B, stride) state after step t0-1, or null: reset
+    unsigned char *out;        // (B, stride) receives the state after step t0+T-1, or null; may be `in`
+    long stride;               // bytes per clip: state_bytes(N, n_out)
+    int t0;                    // steps done before this launch
+};
+
+__host__ __device__ inline int state_np(int N) { return (N + 63) & ~63; }
+__host__ __device__ inline long state_off_v() { return 16; }
+__host__ __device__ inline long state_off_ref(int NP) { return 16 + 4L * NP; }
+__host__ __device__ inline long state_off_last(int NP) { return 16 + 6L * NP; }
+__host__ __device__ inline long state_off_ever(int NP) { return 16 + 6L * NP + NP / 8; }
+__host__ __device__ inline long state_off_feat(int NP) { return 16 + 6L * NP + NP / 4; }
+__host__ __device__ inline long state_bytes(int N, int n_out) { return state_off_feat(state_np(N)) + 16L * n_out; }
+
+// Words of LDS scratch the ST epilogue needs (last-step bits, ever-fired bits, one spike total); every kernel has an idle
+// accumulator array of at least its padded neuron count in words behind the last step.
+__host__ __device__ inline int state_scratch_words(int NP) { return NP / 16 + 1; }
+
+// Prologue: neuron i (< N) of the clip whose block starts at `sin`.
+__device__ __forceinline__ void state_load_neuron(const unsigned char *sin, int NP, int i, float *v, uint32_t *ref, bool *last,
+                                                  bool *ever)
+{
+    *v = reinterpret_cast<const float *>(sin + state_off_v())[i];
+    *ref = reinterpret_cast<const uint16_t *>(sin + state_off_ref(NP))[i];
+    *last = (reinterpret_cast<const uint32_t *>(sin + state_off_last(NP))[i >> 5] >> (i & 31)) & 1u;
+    *ever = (reinterpret_cast<const uint32_t *>(sin + state_off_ever(NP))[i >> 5] >> (i & 31)) & 1u;
+}
+
+__device__ __forceinline__ uint32_t state_load_total(const unsigned char *sin) { return *reinterpret_cast<const uint32_t *>(sin); }
+
+// Epilogue, between state_begin and state_finish: neuron i (< NP; a padding neuron N <= i stores zeros) and the neurons
+// of the last step's spike lists.
+__device__ __forceinline__ void state_store_neuron(unsigned char *sout, uint32_t *scratch, int NP, int N, int i, float v,
+                                                   uint32_t ref, bool ever)
+{
+    if (i >= NP) return;
+    const bool real = i < N;
+    if (sout) {
+        reinterpret_cast<float *>(sout + state_off_v())[i] = real ? v : 0.0f;
+        reinterpret_cast<uint16_t *>(sout + state_off_ref(NP))[i] = (uint16_t)(real ? ref : 0u);
+    }
+    if (real && ever) atomicOr(&scratch[NP / 32 + (i >> 5)], 1u << (i & 31));
+}
+__device__ __forceinline__ void state_mark_last(uint32_t *scratch, int j) { atomicOr(&scratch[j >> 5], 1u << (j & 31)); }
+
+// Epilogue, first: the scratch words start at zero.  Contains a barrier.
+template <int NT>
+__device__ __forceinline__ void state_begin(uint32_t *scratch, int NP, int tid)
+{
+    for (int i = tid; i < state_scratch_words(NP); i += NT) scratch[i] = 0u;
+    __syncthreads();
+}
+
+// SPEC.md §4a: the record of [0, t0) and the record of this launch's steps on local times make the record of [0, t0 + n).
+__device__ __forceinline__ uint4 merge_feature_records(uint4 f1, uint4 f2, uint32_t t0, int burst_isi_max)
+{
+    const uint32_t n1 = f1.x & 0xFFFFu, b1 = f1.x >> 16, n2 = f2.x & 0xFFFFu, b2 = f2.x >> 16;
+    if (n2 == 0u) return f1;
+    const uint32_t first2 = (f2.y & 0xFFFFu) + t0, last2 = (f2.y >> 16) + t0;
+    uint4 m;
+    m.z = f1.z + f2.z + n2 * t0;
+    if (n1 == 0u) {
+        m.x = n2 | (b2 << 16);
+        m.y = first2 | (last2 << 16);
+        m.w = f2.w;
+        return m;
+    }
+    const uint32_t first1 = f1.y & 0xFFFFu, last1 = f1.y >> 16;
+    const uint32_t isi = first2 - last1;                 // the interval that straddles the cut
+    m.x = (n1 + n2) | ((b1 + b2 + ((int)isi <= burst_isi_max ? 1u : 0u)) << 16);
+    m.y = first1 | (last2 << 16);
+    m.w = f1.w + f2.w + isi * isi;
+    return m;
+}
+
+// Epilogue, last: every wave has stored its neurons and added its spikes to the total (lane 0, state_add_total).  Writes the
+// bit fields and the header, merges the feature records (LDS `feat` holds this launch's on entry and the whole run's on
+// return, as does the state).  Contains barriers; `in` and `out` may be the same block: every word is read before it is
+// written, by the same thread.
+__device__ __forceinline__ void state_add_total(uint32_t *scratch, int NP, uint32_t tot_spk) { atomicAdd(&scratch[NP / 16], tot_spk); }
+
+template <int NT>
+__device__ __forceinline__ void state_finish(const unsigned char *sin, unsigned char *sout, uint32_t *scratch, uint4 *feat,
+                                             int NP, int n_out, uint32_t t0, int burst_isi_max, int tid)
+{
+    __syncthreads();
+    if (sout) {
+        uint32_t *bitsout = reinterpret_cast<uint32_t *>(sout + state_off_last(NP));      // last, then ever: NP/16 words
+        for (int i = tid; i < NP / 16; i += NT) bitsout[i] = scratch[i];
+        if (tid == 0) *reinterpret_cast<uint4 *>(sout) = make_uint4(scratch[NP / 16], 0u, 0u, 0u);
+    }
+    for (int o = tid; o < n_out; o += NT) {
+        uint4 f = feat[o];
+        if (sin) f = merge_feature_records(reinterpret_cast<const uint4 *>(sin + state_off_feat(NP))[o], f, t0, burst_isi_max);
+        feat[o] = f;
+        if (sout) reinterpret_cast<uint4 *>(sout + state_off_feat(NP))[o] = f;
+    }
+    __syncthreads();
+}
+
 }  // namespace lsm_lif

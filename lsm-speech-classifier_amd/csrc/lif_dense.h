@@ -47,6 +47,7 @@ struct DenseArgs {
     float *v_trace;            // (B, T, N) or null
     int32_t *stats;            // (B, 2) {neurons that fired at least once, spikes of the whole reservoir} or null
     const int32_t *order;      // (B) clip of workgroup g, or null (g): lsm_reservoir_run_ordered starts long clips first
+    StateArgs st;              // ST forms only (lsm_reservoir_run_from)
 };
 
 // INMODE: how the input drive m_i(t) = #{active channels feeding neuron i} is formed.
@@ -68,7 +69,9 @@ struct DenseArgs {
 // selects, decrement, select).  The arithmetic on v is untouched.  Inside the pipeline the chip is bound by
 // vector-instruction issue, and scalar instructions issue beside it.  Other periods keep the vector
 // countdown (REFM = false).
-template <int SL, int WPC, int INMODE, bool REFM>
+// ST: the launch continues from a saved state and / or saves its own (lif_common.h); prologue and epilogue only.  REFM: the
+// state's countdown 2 / 1 is the lane mask h2 / h1.
+template <int SL, int WPC, int INMODE, bool REFM, bool ST = false>
 __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
 {
     constexpr bool INREG = INMODE == 1;
@@ -177,6 +180,34 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     for (int r = 0; r < (FEATREG ? SL : 1); ++r) fr[r] = make_uint4(0, 0, 0, 0);
     uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
     uint32_t tot_spk = 0u;             // spikes of my wave (stats)
+    if constexpr (ST) {
+        if (a.st.in) {
+            // the state after step t0-1: potentials, countdowns, and the spike lists of that step as the update leaves them
+            const unsigned char *sin = a.st.in + (size_t)b * a.st.stride;
+            const int NP = state_np(N);
+            uint16_t *list_last = wlist + NPAD + w * NPW;
+            int nspk = 0;
+#pragma unroll
+            for (int r = 0; r < SL; ++r) {
+                const int i = (w * SL + r) * 64 + lane;
+                bool last = false, ever = false;
+                uint32_t rf = 0u;
+                if (i < N) state_load_neuron(sin, NP, i, &v[r], &rf, &last, &ever);
+                if (REFM) { h2[r] = __ballot(rf == 2u); h1[r] = __ballot(rf == 1u); }
+                else ref[r] = (int)rf;
+                hf |= (ever ? 1u : 0u) << r;
+                const unsigned long long bal = __ballot(last);
+                if (last) {
+                    const int rank = nspk + lane_rank(bal);
+                    list_last[rank] = (uint16_t)i;
+                    if (rank < R) flist[64 + w * R + rank] = (uint16_t)i;
+                }
+                nspk += __popcll(bal);
+            }
+            if (lane == 0) wcnt[16 + w] = (uint32_t)nspk;
+            tot_spk = w == 0 ? state_load_total(sin) : 0u;
+        }
+    }
     __syncthreads();
 
     // input drive of step `ts`: count the active channels feeding each target (integer atomics)
@@ -426,6 +457,26 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     // ---- epilogue: health statistics (/root/reference/extract_lsm_features.py:119-133 derives them from the
     //      (T, N) spike matrix; here they come from one flag per neuron and one count per wave), then
     //      SPEC.md §4 features from the integer accumulators (float64, then float32) ----
+    if constexpr (ST) {
+        // the state after the last step (the count array is idle: scratch), and the feature records of the whole run
+        const unsigned char *sin = a.st.in ? a.st.in + (size_t)b * a.st.stride : nullptr;
+        unsigned char *sout = a.st.out ? a.st.out + (size_t)b * a.st.stride : nullptr;
+        uint32_t *scratch = icnt;
+        const int NP = state_np(N);
+        state_begin<NT>(scratch, NP, tid);
+#pragma unroll
+        for (int r = 0; r < SL; ++r) {
+            const uint32_t rf = REFM ? (((h2[r] >> lane) & 1ull) ? 2u : (uint32_t)((h1[r] >> lane) & 1ull)) : (uint32_t)ref[REFM ? 0 : r];
+            state_store_neuron(sout, scratch, NP, N, (w * SL + r) * 64 + lane, v[r], rf, (hf >> r) & 1u);
+        }
+        const int lastbuf = (T - 1) & 1;
+        const uint16_t *list_last = wlist + lastbuf * NPAD + w * NPW;
+        const int nlast = (int)wcnt[lastbuf * 16 + w];
+        for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
+        if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
+    }
+    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
     if (a.stats) write_stats(a.stats, b, &wcnt[32], &wcnt[33], hf, tot_spk, lane, tid);
     const int nf = a.n_keys * a.n_out;
     for (int idx = tid; idx < nf; idx += NT) {
@@ -437,7 +488,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
         double val = 0.0;
         switch (a.key_ids[kq]) {
         case 0: val = (double)n; break;
-        case 1: { const double p = (double)n / (double)T; val = p * (1.0 - p); } break;
+        case 1: { const double p = (double)n / (double)Tf; val = p * (1.0 - p); } break;
         case 2: val = n >= 1 ? (double)f.z / (double)n : 0.0; break;
         case 3: val = n >= 1 ? (double)first : 0.0; break;
         case 4: val = n >= 1 ? (double)last : 0.0; break;
@@ -461,44 +512,51 @@ typedef void (*dense_fn_t)(const DenseArgs);
 constexpr int DENSE_REFM_MAX_SL = 4;
 constexpr int DENSE_REFM_REFRACTORY = 2;        // the one period the mask form is written for (the reference's)
 
-template <int SL, int INMODE, bool REFM>
+template <int SL, int INMODE, bool REFM, bool ST>
 dense_fn_t pick_dense_wpc(int wpc)
 {
     switch (wpc) {
-    case 1: return lif_dense_kernel<SL, 1, INMODE, REFM>;
-    case 2: return lif_dense_kernel<SL, 2, INMODE, REFM>;
-    case 4: return lif_dense_kernel<SL, 4, INMODE, REFM>;
-    case 8: return lif_dense_kernel<SL, 8, INMODE, REFM>;
-    case 16: return lif_dense_kernel<SL, 16, INMODE, REFM>;
+    case 1: return lif_dense_kernel<SL, 1, INMODE, REFM, ST>;
+    case 2: return lif_dense_kernel<SL, 2, INMODE, REFM, ST>;
+    case 4: return lif_dense_kernel<SL, 4, INMODE, REFM, ST>;
+    case 8: return lif_dense_kernel<SL, 8, INMODE, REFM, ST>;
+    case 16: return lif_dense_kernel<SL, 16, INMODE, REFM, ST>;
     default: return nullptr;
     }
 }
 
-template <int INMODE>
-dense_fn_t pick_dense_sl(int sl, int wpc, bool refm)
+template <int INMODE, bool ST>
+dense_fn_t pick_dense_sl_st(int sl, int wpc, bool refm)
 {
     if (refm && sl <= DENSE_REFM_MAX_SL) {
         switch (sl) {
-        case 1: return pick_dense_wpc<1, INMODE, true>(wpc);
-        case 2: return pick_dense_wpc<2, INMODE, true>(wpc);
-        case 4: return pick_dense_wpc<4, INMODE, true>(wpc);
+        case 1: return pick_dense_wpc<1, INMODE, true, ST>(wpc);
+        case 2: return pick_dense_wpc<2, INMODE, true, ST>(wpc);
+        case 4: return pick_dense_wpc<4, INMODE, true, ST>(wpc);
         default: return nullptr;
         }
     }
     switch (sl) {
-    case 1: return pick_dense_wpc<1, INMODE, false>(wpc);
-    case 2: return pick_dense_wpc<2, INMODE, false>(wpc);
-    case 4: return pick_dense_wpc<4, INMODE, false>(wpc);
-    case 8: if (INMODE >= 2) return nullptr; else return pick_dense_wpc<INMODE >= 2 ? 4 : 8, INMODE, false>(wpc);
-    case 16: if (INMODE >= 2) return nullptr; else return pick_dense_wpc<INMODE >= 2 ? 4 : 16, INMODE, false>(wpc);
+    case 1: return pick_dense_wpc<1, INMODE, false, ST>(wpc);
+    case 2: return pick_dense_wpc<2, INMODE, false, ST>(wpc);
+    case 4: return pick_dense_wpc<4, INMODE, false, ST>(wpc);
+    case 8: if (INMODE >= 2) return nullptr; else return pick_dense_wpc<INMODE >= 2 ? 4 : 8, INMODE, false, ST>(wpc);
+    case 16: if (INMODE >= 2) return nullptr; else return pick_dense_wpc<INMODE >= 2 ? 4 : 16, INMODE, false, ST>(wpc);
     default: return nullptr;
     }
 }
 
+// state: the ST form (continuation)
+template <int INMODE>
+dense_fn_t pick_dense_sl(int sl, int wpc, bool refm, bool state)
+{
+    return state ? pick_dense_sl_st<INMODE, true>(sl, wpc, refm) : pick_dense_sl_st<INMODE, false>(sl, wpc, refm);
+}
+
 // refm: the caller checked a.refractory == DENSE_REFM_REFRACTORY (else the countdown stays in vector registers)
-dense_fn_t pick_dense_0(int sl, int wpc, bool refm);      // lif_dense_0.hip (INMODE 0: entries from global memory)
-dense_fn_t pick_dense_1(int sl, int wpc, bool refm);      // lif_dense_1.hip (INMODE 1: entries in registers)
-dense_fn_t pick_dense_2(int sl, int wpc, bool refm);      // lif_dense_2.hip (INMODE 2: channel masks, C <= 128, SL <= 4)
-dense_fn_t pick_dense_3(int sl, int wpc, bool refm);      // lif_dense_3.hip (INMODE 3: channel masks at coloured positions)
+dense_fn_t pick_dense_0(int sl, int wpc, bool refm, bool state);      // lif_dense_0.hip (INMODE 0: entries from global memory)
+dense_fn_t pick_dense_1(int sl, int wpc, bool refm, bool state);      // lif_dense_1.hip (INMODE 1: entries in registers)
+dense_fn_t pick_dense_2(int sl, int wpc, bool refm, bool state);      // lif_dense_2.hip (INMODE 2: channel masks, C <= 128, SL <= 4)
+dense_fn_t pick_dense_3(int sl, int wpc, bool refm, bool state);      // lif_dense_3.hip (INMODE 3: channel masks at coloured positions)
 
 }  // namespace lsm_lif

@@ -3,5 +3,5 @@
 #include "lif_dense.h"
 
 namespace lsm_lif {
-dense_fn_t pick_dense_3(int sl, int wpc, bool refm) { return pick_dense_sl<3>(sl, wpc, refm); }
+dense_fn_t pick_dense_3(int sl, int wpc, bool refm, bool state) { return pick_dense_sl<3>(sl, wpc, refm, state); }
 }  // namespace lsm_lif

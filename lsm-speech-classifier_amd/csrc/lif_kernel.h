@@ -59,6 +59,7 @@ struct LifArgs {
     float *v_trace;            // (B, T, N) or null
     int32_t *stats;            // (B, 2) {neurons that fired at least once, spikes of the whole reservoir} or null
     const int32_t *order;      // (B) clip of workgroup g, or null (g): lsm_reservoir_run_ordered starts long clips first
+    StateArgs st;              // ST forms only (lsm_reservoir_run_from)
 };
 
 // INREG: the wave's input-map entries fit IN_REG_SLOTS registers per lane (else they are streamed
@@ -66,7 +67,8 @@ struct LifArgs {
 // SEGLDS: the segment table is staged in LDS (else read from global memory).  Both are template
 // parameters so that every access keeps its own address space: a run-time choice between an LDS
 // and a global pointer compiles to flat loads, whose waits serialise the row loads behind them.
-template <int SL, int WPC, bool INREG, bool SEGLDS>
+// ST: the launch continues from a saved state and / or saves its own (lif_common.h); prologue and epilogue only.
+template <int SL, int WPC, bool INREG, bool SEGLDS, bool ST = false>
 __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
 {
     constexpr int NPW = SL * 64;
@@ -136,6 +138,31 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         lam[r] = a.leak[i];
         os[r] = a.oslot[i];
     }
+    uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
+    uint32_t tot_spk = 0u;             // spikes of my wave (stats)
+    if constexpr (ST) {
+        if (a.st.in) {
+            // the state after step t0-1: potentials, countdowns, and the spike list of that step as the update leaves it
+            const unsigned char *sin = a.st.in + (size_t)b * a.st.stride;
+            const int NP = state_np(N);
+            uint16_t *list_last = wlist + NPAD + w * NPW;
+            int nspk = 0;
+#pragma unroll
+            for (int r = 0; r < SL; ++r) {
+                const int i = (w * SL + r) * 64 + lane;
+                bool last = false, ever = false;
+                uint32_t rf = 0u;
+                if (i < N) state_load_neuron(sin, NP, i, &v[r], &rf, &last, &ever);
+                ref[r] = (int)rf;
+                hf |= (ever ? 1u : 0u) << r;
+                const unsigned long long bal = __ballot(last);
+                if (last) list_last[nspk + lane_rank(bal)] = (uint16_t)i;
+                nspk += __popcll(bal);
+            }
+            if (lane == 0) wcnt[16 + w] = (uint32_t)nspk;
+            tot_spk = w == 0 ? state_load_total(sin) : 0u;
+        }
+    }
     // input-map entries of this wave: word offset of the channel bit, its mask, target neuron.
     // Padding entries get mask 0 and a target of their own (this lane's first neuron): they add 0,
     // and never pile up on one LDS address (same-address atomics serialise).
@@ -155,8 +182,6 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
     const float theta = a.theta, w_in = a.w_in;
     const uint32_t *my_ent = a.in_ent + (size_t)w * a.EinW;   // !INREG: streamed from L2 each step
     const bool trace = a.spike_matrix != nullptr || a.v_trace != nullptr;
-    uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
-    uint32_t tot_spk = 0u;             // spikes of my wave (stats)
     __syncthreads();
 
     // input drive of step `ts`: count the active channels feeding each target (integer atomics,
@@ -364,6 +389,24 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
 
     // ---- epilogue: health statistics (the count array is idle and all zero after the last step), then
     //      SPEC.md §4 features from the integer accumulators (float64, then float32) ----
+    if constexpr (ST) {
+        // the state after the last step (the accumulators are idle: scratch), and the feature records of the whole run
+        const unsigned char *sin = a.st.in ? a.st.in + (size_t)b * a.st.stride : nullptr;
+        unsigned char *sout = a.st.out ? a.st.out + (size_t)b * a.st.stride : nullptr;
+        uint32_t *scratch = reinterpret_cast<uint32_t *>(acc);
+        const int NP = state_np(N);
+        state_begin<NT>(scratch, NP, tid);
+#pragma unroll
+        for (int r = 0; r < SL; ++r)
+            state_store_neuron(sout, scratch, NP, N, (w * SL + r) * 64 + lane, v[r], (uint32_t)ref[r], (hf >> r) & 1u);
+        const int lastbuf = (T - 1) & 1;
+        const uint16_t *list_last = wlist + lastbuf * NPAD + w * NPW;
+        const int nlast = (int)wcnt[lastbuf * 16 + w];
+        for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
+        if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
+    }
+    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
     if (a.stats) write_stats(a.stats, b, &icnt[0], &icnt[1], hf, tot_spk, lane, tid);
     // write_features<NT> written out: with the call the one-slot forms allocate 101 registers instead of 77 (4 waves per SIMD, not 6)
     const int nf = a.n_keys * a.n_out;
@@ -376,7 +419,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         double val = 0.0;
         switch (a.key_ids[kq]) {
         case 0: val = (double)n; break;
-        case 1: { const double p = (double)n / (double)T; val = p * (1.0 - p); } break;
+        case 1: { const double p = (double)n / (double)Tf; val = p * (1.0 - p); } break;
         case 2: val = n >= 1 ? (double)f.z / (double)n : 0.0; break;
         case 3: val = n >= 1 ? (double)first : 0.0; break;
         case 4: val = n >= 1 ? (double)last : 0.0; break;
@@ -396,36 +439,43 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
 
 typedef void (*lif_fn_t)(const LifArgs);
 
-template <int SL, bool INREG, bool SEGLDS>
+template <int SL, bool INREG, bool SEGLDS, bool ST>
 lif_fn_t pick_wpc(int wpc)
 {
     switch (wpc) {
-    case 1: return lif_kernel<SL, 1, INREG, SEGLDS>;
-    case 2: return lif_kernel<SL, 2, INREG, SEGLDS>;
-    case 4: return lif_kernel<SL, 4, INREG, SEGLDS>;
-    case 8: return lif_kernel<SL, 8, INREG, SEGLDS>;
-    case 16: return lif_kernel<SL, 16, INREG, SEGLDS>;
+    case 1: return lif_kernel<SL, 1, INREG, SEGLDS, ST>;
+    case 2: return lif_kernel<SL, 2, INREG, SEGLDS, ST>;
+    case 4: return lif_kernel<SL, 4, INREG, SEGLDS, ST>;
+    case 8: return lif_kernel<SL, 8, INREG, SEGLDS, ST>;
+    case 16: return lif_kernel<SL, 16, INREG, SEGLDS, ST>;
     default: return nullptr;
     }
 }
 
-template <bool INREG, bool SEGLDS>
-lif_fn_t pick_sl(int sl, int wpc)
+template <bool INREG, bool SEGLDS, bool ST>
+lif_fn_t pick_sl_st(int sl, int wpc)
 {
     switch (sl) {
-    case 1: return pick_wpc<1, INREG, SEGLDS>(wpc);
-    case 2: return pick_wpc<2, INREG, SEGLDS>(wpc);
-    case 4: return pick_wpc<4, INREG, SEGLDS>(wpc);
-    case 8: return pick_wpc<8, INREG, SEGLDS>(wpc);
-    case 16: return pick_wpc<16, INREG, SEGLDS>(wpc);
+    case 1: return pick_wpc<1, INREG, SEGLDS, ST>(wpc);
+    case 2: return pick_wpc<2, INREG, SEGLDS, ST>(wpc);
+    case 4: return pick_wpc<4, INREG, SEGLDS, ST>(wpc);
+    case 8: return pick_wpc<8, INREG, SEGLDS, ST>(wpc);
+    case 16: return pick_wpc<16, INREG, SEGLDS, ST>(wpc);
     default: return nullptr;
     }
+}
+
+// state: the ST form (continuation)
+template <bool INREG, bool SEGLDS>
+lif_fn_t pick_sl(int sl, int wpc, bool state)
+{
+    return state ? pick_sl_st<INREG, SEGLDS, true>(sl, wpc) : pick_sl_st<INREG, SEGLDS, false>(sl, wpc);
 }
 
 // one definition per translation unit lif_variant_<inreg><seglds>.hip
-lif_fn_t pick_lif_00(int sl, int wpc);
-lif_fn_t pick_lif_01(int sl, int wpc);
-lif_fn_t pick_lif_10(int sl, int wpc);
-lif_fn_t pick_lif_11(int sl, int wpc);
+lif_fn_t pick_lif_00(int sl, int wpc, bool state);
+lif_fn_t pick_lif_01(int sl, int wpc, bool state);
+lif_fn_t pick_lif_10(int sl, int wpc, bool state);
+lif_fn_t pick_lif_11(int sl, int wpc, bool state);
 
 }  // namespace lsm_lif

@@ -62,6 +62,7 @@ struct PairArgs {
     float *v_trace;            // (B, T, N) or null
     int32_t *stats;            // (B, 2) or null
     const int32_t *order;      // (B) clip of workgroup g, or null
+    StateArgs st;              // ST forms only (lsm_reservoir_run_from)
 };
 
 typedef float pair_f2 __attribute__((ext_vector_type(2)));
@@ -177,7 +178,8 @@ __device__ __forceinline__ uint32_t pair_input_planes(const uint32_t (&im)[4], c
 // (pair_input_planes; 5..8 row words).
 // LEAKV: a leak coefficient per neuron in registers (the reference's --leak-variance-divisor, extract_lsm_features.py:174,
 // 182-183) instead of one for all (its default).
-template <int BL, int WPC, int INMASK, bool LEAKV = false>
+// ST: the launch continues from a saved state and / or saves its own (lif_common.h); prologue and epilogue only.
+template <int BL, int WPC, int INMASK, bool LEAKV = false, bool ST = false>
 __global__ __launch_bounds__(WPC * 64) __attribute__((amdgpu_waves_per_eu(4)))
 void lif_pair_kernel(const PairArgs a)
 {
@@ -262,6 +264,40 @@ void lif_pair_kernel(const PairArgs a)
     uint32_t rows_ = 0u;
     uint64_t last_ = 0;
 #endif
+    if constexpr (ST) {
+        if (a.st.in) {
+            // the state after step t0-1: potentials, countdowns, and the block lists of that step as the update leaves them
+            const unsigned char *sin = a.st.in + (size_t)b * a.st.stride;
+            const int NP = state_np(N);
+            uint8_t *list_last = wlist + NPAD;
+#pragma unroll
+            for (int q = 0; q < BL; ++q) {
+                const int gb = LSM_PAIR_GB(q);
+                unsigned long long bq[2];
+                bool last[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int r = 2 * q + h, i = gb * 128 + lane * 2 + h;
+                    bool ever = false;
+                    uint32_t rf = 0u;
+                    last[h] = false;
+                    if (i < N) state_load_neuron(sin, NP, i, &v[r], &rf, &last[h], &ever);
+                    oref[r] |= rf << 16;
+                    hf |= (ever ? 1u : 0u) << r;
+                    bq[h] = __ballot(last[h]);
+                }
+                int rank = lane_rank(bq[0]) + lane_rank(bq[1]);
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    if (last[h]) {
+                        list_last[gb * 128 + rank] = (uint8_t)(lane * 2 + h);
+                        rank += 1;
+                    }
+                if (lane == 0) wcnt[PAIR_MAX_BLOCKS + gb] = (uint32_t)(__popcll(bq[0]) + __popcll(bq[1]));
+            }
+            tot_spk = w == 0 ? state_load_total(sin) : 0u;
+        }
+    }
     __syncthreads();
 #if LSM_PAIR_PHASES
     last_ = __builtin_amdgcn_s_memtime();
@@ -549,12 +585,36 @@ void lif_pair_kernel(const PairArgs a)
         __syncthreads();
         LSM_PAIR_MARK(6)               // barrier
     }
-#undef LSM_PAIR_GB
     __builtin_amdgcn_s_setprio(0);
+
+    if constexpr (ST) {
+        // the state after the last step (the accumulators are idle: scratch), and the feature records of the whole run
+        const unsigned char *sin = a.st.in ? a.st.in + (size_t)b * a.st.stride : nullptr;
+        unsigned char *sout = a.st.out ? a.st.out + (size_t)b * a.st.stride : nullptr;
+        uint32_t *scratch = reinterpret_cast<uint32_t *>(smem + PAIR_DUMP_BYTES);
+        const int NP = state_np(N);
+        state_begin<NT>(scratch, NP, tid);
+        const int lastbuf = (T - 1) & 1;
+#pragma unroll
+        for (int q = 0; q < BL; ++q) {
+            const int gb = LSM_PAIR_GB(q);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                state_store_neuron(sout, scratch, NP, N, gb * 128 + lane * 2 + h, v[2 * q + h], oref[2 * q + h] >> 16,
+                                   (hf >> (2 * q + h)) & 1u);
+            const uint8_t *list_last = wlist + lastbuf * NPAD + gb * 128;
+            const int nlast = (int)wcnt[lastbuf * PAIR_MAX_BLOCKS + gb];
+            for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, gb * 128 + (int)list_last[l]);
+        }
+        if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
+    }
+#undef LSM_PAIR_GB
+    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
     if (a.stats) write_stats(a.stats, b, &wcnt[2 * PAIR_MAX_BLOCKS], &wcnt[2 * PAIR_MAX_BLOCKS + 1], hf, tot_spk, lane, tid);
-    write_features<NT>(a.features, feat, a.key_ids, a.n_keys, a.n_out, b, T, tid);
+    write_features<NT>(a.features, feat, a.key_ids, a.n_keys, a.n_out, b, Tf, tid);
 #if LSM_PAIR_PHASES
     __syncthreads();
     const int nf = a.n_keys * a.n_out;
@@ -567,37 +627,44 @@ void lif_pair_kernel(const PairArgs a)
 
 typedef void (*pair_fn_t)(const PairArgs);
 
-template <int BL, int INMASK, bool LEAKV>
+template <int BL, int INMASK, bool LEAKV, bool ST>
 pair_fn_t pick_pair_wpc(int wpc)
 {
     switch (wpc) {
-    case 4: return lif_pair_kernel<BL, 4, INMASK, LEAKV>;
-    case 8: return lif_pair_kernel<BL, 8, INMASK, LEAKV>;
-    case 16: return lif_pair_kernel<BL, 16, INMASK, LEAKV>;
+    case 4: return lif_pair_kernel<BL, 4, INMASK, LEAKV, ST>;
+    case 8: return lif_pair_kernel<BL, 8, INMASK, LEAKV, ST>;
+    case 16: return lif_pair_kernel<BL, 16, INMASK, LEAKV, ST>;
     default: return nullptr;
     }
 }
-template <int BL>
-pair_fn_t pick_pair(int wpc, int inmask, bool leakv)
+template <int BL, bool ST>
+pair_fn_t pick_pair_st(int wpc, int inmask, bool leakv)
 {
-    if (leakv) return inmask == 2 ? pick_pair_wpc<BL, 2, true>(wpc) : pick_pair_wpc<BL, 1, true>(wpc);
-    return inmask == 2 ? pick_pair_wpc<BL, 2, false>(wpc) : pick_pair_wpc<BL, 1, false>(wpc);
+    if (leakv) return inmask == 2 ? pick_pair_wpc<BL, 2, true, ST>(wpc) : pick_pair_wpc<BL, 1, true, ST>(wpc);
+    return inmask == 2 ? pick_pair_wpc<BL, 2, false, ST>(wpc) : pick_pair_wpc<BL, 1, false, ST>(wpc);
+}
+// state: the ST form (continuation)
+template <int BL>
+pair_fn_t pick_pair(int wpc, int inmask, bool leakv, bool state)
+{
+    return state ? pick_pair_st<BL, true>(wpc, inmask, leakv) : pick_pair_st<BL, false>(wpc, inmask, leakv);
 }
 
 template <int BL>
-pair_fn_t pick_pair_wide(int wpc, bool leakv)
+pair_fn_t pick_pair_wide(int wpc, bool leakv, bool state)
 {
-    return leakv ? pick_pair_wpc<BL, 3, true>(wpc) : pick_pair_wpc<BL, 3, false>(wpc);
+    if (state) return leakv ? pick_pair_wpc<BL, 3, true, true>(wpc) : pick_pair_wpc<BL, 3, false, true>(wpc);
+    return leakv ? pick_pair_wpc<BL, 3, true, false>(wpc) : pick_pair_wpc<BL, 3, false, false>(wpc);
 }
 
 // one definition per translation unit lif_pair_<bl>.hip (INMASK 1, 2) and lif_pair_wide_<bl>.hip (INMASK 3)
-pair_fn_t pick_pair_1(int wpc, int inmask, bool leakv);
-pair_fn_t pick_pair_2(int wpc, int inmask, bool leakv);
-pair_fn_t pick_pair_3(int wpc, int inmask, bool leakv);
-pair_fn_t pick_pair_4(int wpc, int inmask, bool leakv);
-pair_fn_t pick_pair_wide_1(int wpc, bool leakv);
-pair_fn_t pick_pair_wide_2(int wpc, bool leakv);
-pair_fn_t pick_pair_wide_3(int wpc, bool leakv);
-pair_fn_t pick_pair_wide_4(int wpc, bool leakv);
+pair_fn_t pick_pair_1(int wpc, int inmask, bool leakv, bool state);
+pair_fn_t pick_pair_2(int wpc, int inmask, bool leakv, bool state);
+pair_fn_t pick_pair_3(int wpc, int inmask, bool leakv, bool state);
+pair_fn_t pick_pair_4(int wpc, int inmask, bool leakv, bool state);
+pair_fn_t pick_pair_wide_1(int wpc, bool leakv, bool state);
+pair_fn_t pick_pair_wide_2(int wpc, bool leakv, bool state);
+pair_fn_t pick_pair_wide_3(int wpc, bool leakv, bool state);
+pair_fn_t pick_pair_wide_4(int wpc, bool leakv, bool state);
 
 }  // namespace lsm_lif

@@ -2,5 +2,5 @@
 #include "lif_pair.h"
 
 namespace lsm_lif {
-pair_fn_t pick_pair_3(int wpc, int inmask, bool leakv) { return pick_pair<3>(wpc, inmask, leakv); }
+pair_fn_t pick_pair_3(int wpc, int inmask, bool leakv, bool state) { return pick_pair<3>(wpc, inmask, leakv, state); }
 }  // namespace lsm_lif

@@ -3,5 +3,5 @@
 #include "lif_pair.h"
 
 namespace lsm_lif {
-pair_fn_t pick_pair_wide_1(int wpc, bool leakv) { return pick_pair_wide<1>(wpc, leakv); }
+pair_fn_t pick_pair_wide_1(int wpc, bool leakv, bool state) { return pick_pair_wide<1>(wpc, leakv, state); }
 }  // namespace lsm_lif

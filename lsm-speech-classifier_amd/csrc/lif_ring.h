@@ -71,6 +71,7 @@ struct RingArgs {
     float *v_trace;            // (B, T, N) or null
     int32_t *stats;            // (B, 2) {neurons that fired at least once, spikes of the whole reservoir} or null
     const int32_t *order;      // (B) clip of workgroup g, or null (g): lsm_reservoir_run_ordered starts long clips first
+    StateArgs st;              // ST forms only (lsm_reservoir_run_from)
 };
 
 typedef float ring_f4 __attribute__((ext_vector_type(4)));
@@ -115,7 +116,8 @@ __host__ __device__ inline int ring_cnt_word(int i) { return RING_DUMP_WORDS + (
 // no input-map entries, no LDS atomics, no count array on the step's critical path (the entry drive cost ~1.0 of cfg4's 6.0 ms,
 // profiles/r04_ring_input_drive.txt).  The 4 x SL registers exist only when the leak coefficients do not need SL of their own:
 // offered for UNIFORM leaks (the reference's default, leak_variance_divisor = None), C <= 128 and at most two quads per wave.
-template <int QL, int WPC, bool INREG, bool STRIDED, int INMASK = 0>
+// ST: the launch continues from a saved state and / or saves its own (lif_common.h); prologue and epilogue only.
+template <int QL, int WPC, bool INREG, bool STRIDED, int INMASK = 0, bool ST = false>
 __global__ __launch_bounds__(WPC * 64) __attribute__((amdgpu_waves_per_eu((QL <= 2 && STRIDED) ? 4 : 1)))
 void lif_ring_kernel(const RingArgs a)
 {
@@ -202,6 +204,40 @@ void lif_ring_kernel(const RingArgs a)
     const int H = a.H, NQ = a.NQ;
     uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
     uint32_t tot_spk = 0u;             // spikes of my wave (stats)
+    if constexpr (ST) {
+        if (a.st.in) {
+            // the state after step t0-1: potentials, countdowns, and the quad lists of that step as the update leaves them
+            const unsigned char *sin = a.st.in + (size_t)b * a.st.stride;
+            const int NP = state_np(N);
+            uint16_t *list_last = wlist + NPAD;
+#pragma unroll
+            for (int q = 0; q < QL; ++q) {
+                const int gq = LSM_RING_GQ(q);
+                unsigned long long bq[4];
+                bool last[4];
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const int r = 4 * q + h, i = gq * 256 + lane * 4 + h;
+                    bool ever = false;
+                    uint32_t rf = 0u;
+                    last[h] = false;
+                    if (i < N) state_load_neuron(sin, NP, i, &v[r], &rf, &last[h], &ever);
+                    oref[r] |= rf << 16;
+                    hf |= (ever ? 1u : 0u) << r;
+                    bq[h] = __ballot(last[h]);
+                }
+                int rank = lane_rank(bq[0]) + lane_rank(bq[1]) + lane_rank(bq[2]) + lane_rank(bq[3]);
+#pragma unroll
+                for (int h = 0; h < 4; ++h)
+                    if (last[h]) {
+                        list_last[gq * 256 + rank] = (uint16_t)(gq * 256 + lane * 4 + h);
+                        rank += 1;
+                    }
+                if (lane == 0) wcnt[32 + gq] = (uint32_t)(__popcll(bq[0]) + __popcll(bq[1]) + __popcll(bq[2]) + __popcll(bq[3]));
+            }
+            tot_spk = w == 0 ? state_load_total(sin) : 0u;
+        }
+    }
     __syncthreads();
 
     // Input drive of step `ts`: every entry looks its channel up in the step's bit row and adds the bit to its target's
@@ -518,63 +554,94 @@ void lif_ring_kernel(const RingArgs a)
         tot_spk += (uint32_t)nspk;
         __syncthreads();
     }
-#undef LSM_RING_GQ
     __builtin_amdgcn_s_setprio(0);
+
+    if constexpr (ST) {
+        // the state after the last step (the accumulators are idle: scratch), and the feature records of the whole run
+        const unsigned char *sin = a.st.in ? a.st.in + (size_t)b * a.st.stride : nullptr;
+        unsigned char *sout = a.st.out ? a.st.out + (size_t)b * a.st.stride : nullptr;
+        uint32_t *scratch = reinterpret_cast<uint32_t *>(acc + RING_DUMP_WORDS);
+        const int NP = state_np(N);
+        state_begin<NT>(scratch, NP, tid);
+        const int lastbuf = (T - 1) & 1;
+#pragma unroll
+        for (int q = 0; q < QL; ++q) {
+            const int gq = LSM_RING_GQ(q);
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+                state_store_neuron(sout, scratch, NP, N, gq * 256 + lane * 4 + h, v[4 * q + h], oref[4 * q + h] >> 16,
+                                   (hf >> (4 * q + h)) & 1u);
+            const uint16_t *list_last = wlist + lastbuf * NPAD + gq * 256;
+            const int nlast = (int)wcnt[lastbuf * 32 + gq];
+            for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
+        }
+        if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
+    }
+#undef LSM_RING_GQ
+    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
     if (a.stats) write_stats(a.stats, b, &wcnt[64], &wcnt[65], hf, tot_spk, lane, tid);
-    write_features<NT>(a.features, feat, a.key_ids, a.n_keys, a.n_out, b, T, tid);
+    write_features<NT>(a.features, feat, a.key_ids, a.n_keys, a.n_out, b, Tf, tid);
 }
 
 typedef void (*ring_fn_t)(const RingArgs);
 
-template <int QL, bool INREG, bool STRIDED>
+template <int QL, bool INREG, bool STRIDED, bool ST>
 ring_fn_t pick_ring_wpc(int wpc)
 {
     switch (wpc) {
-    case 2: return lif_ring_kernel<QL, 2, INREG, STRIDED>;
-    case 4: return lif_ring_kernel<QL, 4, INREG, STRIDED>;
-    case 8: return lif_ring_kernel<QL, 8, INREG, STRIDED>;
+    case 2: return lif_ring_kernel<QL, 2, INREG, STRIDED, 0, ST>;
+    case 4: return lif_ring_kernel<QL, 4, INREG, STRIDED, 0, ST>;
+    case 8: return lif_ring_kernel<QL, 8, INREG, STRIDED, 0, ST>;
     case 16:
-        if constexpr (QL * 16 <= RING_MAX_QUADS) return lif_ring_kernel<QL, 16, INREG, STRIDED>;   // N <= 8192 = 16 waves x 2 quads
+        if constexpr (QL * 16 <= RING_MAX_QUADS) return lif_ring_kernel<QL, 16, INREG, STRIDED, 0, ST>;   // N <= 8192 = 16 waves x 2 quads
         else return nullptr;
     default: return nullptr;
     }
 }
 
-template <int QL>
-ring_fn_t pick_ring(int wpc, bool inreg, bool strided)
+template <int QL, bool ST>
+ring_fn_t pick_ring_st(int wpc, bool inreg, bool strided)
 {
-    if (strided) return inreg ? pick_ring_wpc<QL, true, true>(wpc) : pick_ring_wpc<QL, false, true>(wpc);
-    return inreg ? pick_ring_wpc<QL, true, false>(wpc) : pick_ring_wpc<QL, false, false>(wpc);
+    if (strided) return inreg ? pick_ring_wpc<QL, true, true, ST>(wpc) : pick_ring_wpc<QL, false, true, ST>(wpc);
+    return inreg ? pick_ring_wpc<QL, true, false, ST>(wpc) : pick_ring_wpc<QL, false, false, ST>(wpc);
+}
+// state: the ST form (continuation)
+template <int QL>
+ring_fn_t pick_ring(int wpc, bool inreg, bool strided, bool state)
+{
+    return state ? pick_ring_st<QL, true>(wpc, inreg, strided) : pick_ring_st<QL, false>(wpc, inreg, strided);
 }
 
 // INMASK forms: strided ownership, at most two quads per wave (lif_ring_1.hip, lif_ring_2.hip); inmask = 1 natural / 2 coloured
-template <int QL, int INMASK>
+template <int QL, int INMASK, bool ST>
 ring_fn_t pick_ring_mask_wpc(int wpc)
 {
     switch (wpc) {
-    case 2: return lif_ring_kernel<QL, 2, false, true, INMASK>;
-    case 4: return lif_ring_kernel<QL, 4, false, true, INMASK>;
-    case 8: return lif_ring_kernel<QL, 8, false, true, INMASK>;
+    case 2: return lif_ring_kernel<QL, 2, false, true, INMASK, ST>;
+    case 4: return lif_ring_kernel<QL, 4, false, true, INMASK, ST>;
+    case 8: return lif_ring_kernel<QL, 8, false, true, INMASK, ST>;
     case 16:
-        if constexpr (QL * 16 <= RING_MAX_QUADS) return lif_ring_kernel<QL, 16, false, true, INMASK>;
+        if constexpr (QL * 16 <= RING_MAX_QUADS) return lif_ring_kernel<QL, 16, false, true, INMASK, ST>;
         else return nullptr;
     default: return nullptr;
     }
 }
 template <int QL>
-ring_fn_t pick_ring_mask(int wpc, int inmask)
+ring_fn_t pick_ring_mask(int wpc, int inmask, bool state)
 {
-    return inmask == 2 ? pick_ring_mask_wpc<QL, 2>(wpc) : pick_ring_mask_wpc<QL, 1>(wpc);
+    if (state) return inmask == 2 ? pick_ring_mask_wpc<QL, 2, true>(wpc) : pick_ring_mask_wpc<QL, 1, true>(wpc);
+    return inmask == 2 ? pick_ring_mask_wpc<QL, 2, false>(wpc) : pick_ring_mask_wpc<QL, 1, false>(wpc);
 }
 
 // one definition per translation unit lif_ring_<ql>.hip
-ring_fn_t pick_ring_1(int wpc, bool inreg, bool strided);
-ring_fn_t pick_ring_2(int wpc, bool inreg, bool strided);
-ring_fn_t pick_ring_3(int wpc, bool inreg, bool strided);
-ring_fn_t pick_ring_4(int wpc, bool inreg, bool strided);
-ring_fn_t pick_ring_mask_1(int wpc, int inmask);
-ring_fn_t pick_ring_mask_2(int wpc, int inmask);
+ring_fn_t pick_ring_1(int wpc, bool inreg, bool strided, bool state);
+ring_fn_t pick_ring_2(int wpc, bool inreg, bool strided, bool state);
+ring_fn_t pick_ring_3(int wpc, bool inreg, bool strided, bool state);
+ring_fn_t pick_ring_4(int wpc, bool inreg, bool strided, bool state);
+ring_fn_t pick_ring_mask_1(int wpc, int inmask, bool state);
+ring_fn_t pick_ring_mask_2(int wpc, int inmask, bool state);
 
 }  // namespace lsm_lif

@@ -3,5 +3,5 @@
 #include "lif_ring.h"
 
 namespace lsm_lif {
-ring_fn_t pick_ring_3(int wpc, bool inreg, bool strided) { return pick_ring<3>(wpc, inreg, strided); }
+ring_fn_t pick_ring_3(int wpc, bool inreg, bool strided, bool state) { return pick_ring<3>(wpc, inreg, strided, state); }
 }  // namespace lsm_lif

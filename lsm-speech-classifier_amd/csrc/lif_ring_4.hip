@@ -2,5 +2,5 @@
 #include "lif_ring.h"
 
 namespace lsm_lif {
-ring_fn_t pick_ring_4(int wpc, bool inreg, bool strided) { return pick_ring<4>(wpc, inreg, strided); }
+ring_fn_t pick_ring_4(int wpc, bool inreg, bool strided, bool state) { return pick_ring<4>(wpc, inreg, strided, state); }
 }  // namespace lsm_lif

@@ -3,5 +3,5 @@
 #include "lif_kernel.h"
 
 namespace lsm_lif {
-lif_fn_t pick_lif_01(int sl, int wpc) { return pick_sl<false, true>(sl, wpc); }
+lif_fn_t pick_lif_01(int sl, int wpc, bool state) { return pick_sl<false, true>(sl, wpc, state); }
 }  // namespace lsm_lif

@@ -27,10 +27,10 @@ enum KernelMode { MODE_AUTO = 0, MODE_SPARSE = 1, MODE_DENSE = 2, MODE_RING = 3,
                   MODE_RING_QUADS = 6 };
 enum PlannedKernel { KERNEL_NONE = 0, KERNEL_SPARSE = 1, KERNEL_DENSE = 2, KERNEL_RING = 3 };
 
-lif_fn_t pick_kernel(int sl, int wpc, bool inreg, bool seglds)
+lif_fn_t pick_kernel(int sl, int wpc, bool inreg, bool seglds, bool state)
 {
-    if (inreg) return seglds ? lsm_lif::pick_lif_11(sl, wpc) : lsm_lif::pick_lif_10(sl, wpc);
-    return seglds ? lsm_lif::pick_lif_01(sl, wpc) : lsm_lif::pick_lif_00(sl, wpc);
+    if (inreg) return seglds ? lsm_lif::pick_lif_11(sl, wpc, state) : lsm_lif::pick_lif_10(sl, wpc, state);
+    return seglds ? lsm_lif::pick_lif_01(sl, wpc, state) : lsm_lif::pick_lif_00(sl, wpc, state);
 }
 
 // Owning device pointer: move-only, hipFree when it goes.  Every table of a handle is one.
@@ -1130,6 +1130,12 @@ struct RunArgs {                // what one run is given, as the launch function
     uint8_t *spike_matrix;
     int32_t *stats;
     void *stream;
+    // continuation (lsm_reservoir_run_from): the state blocks read / written and the steps done before this launch.  Either
+    // pointer set selects the kernels' ST forms; lsm_reservoir_run and _run_ordered leave them null.
+    const void *state_in = nullptr;
+    void *state_out = nullptr;
+    int first_step = 0;
+    bool stateful() const { return state_in != nullptr || state_out != nullptr; }
 };
 
 // The fields LifArgs, DenseArgs, RingArgs and PairArgs have in common.
@@ -1145,6 +1151,8 @@ static void set_common_args(Args *a, const lsm_reservoir *h, const RunArgs &r)
     for (int k = 0; k < 8; ++k) a->key_ids[k] = k < r.n_keys ? r.key_ids[k] : 0;
     a->features = r.features; a->spike_matrix = r.spike_matrix; a->v_trace = r.v_trace;
     a->stats = r.stats; a->order = r.order;
+    a->st.in = static_cast<const unsigned char *>(r.state_in); a->st.out = static_cast<unsigned char *>(r.state_out);
+    a->st.stride = lsm_lif::state_bytes(h->N, h->n_out); a->st.t0 = r.first_step;
 }
 
 // One workgroup of wpc waves per clip, `lds` bytes of dynamic LDS.
@@ -1161,11 +1169,12 @@ static int run_pairs(const lsm_reservoir *h, const PairVariant &pv, const RunArg
 {
     const int inmask = pv.inform;
     const bool leakv = pv.leak != nullptr;
-    static lsm_lif::pair_fn_t (*const wide[4])(int, bool) = {lsm_lif::pick_pair_wide_1, lsm_lif::pick_pair_wide_2,
+    static lsm_lif::pair_fn_t (*const wide[4])(int, bool, bool) = {lsm_lif::pick_pair_wide_1, lsm_lif::pick_pair_wide_2,
                                                              lsm_lif::pick_pair_wide_3, lsm_lif::pick_pair_wide_4};
-    static lsm_lif::pair_fn_t (*const masks[4])(int, int, bool) = {lsm_lif::pick_pair_1, lsm_lif::pick_pair_2,
+    static lsm_lif::pair_fn_t (*const masks[4])(int, int, bool, bool) = {lsm_lif::pick_pair_1, lsm_lif::pick_pair_2,
                                                                    lsm_lif::pick_pair_3, lsm_lif::pick_pair_4};
-    lsm_lif::pair_fn_t pfn = inmask == 3 ? wide[pv.bl - 1](pv.wpc, leakv) : masks[pv.bl - 1](pv.wpc, inmask, leakv);
+    const bool st = r.stateful();
+    lsm_lif::pair_fn_t pfn = inmask == 3 ? wide[pv.bl - 1](pv.wpc, leakv, st) : masks[pv.bl - 1](pv.wpc, inmask, leakv, st);
     // (bit planes: 5..8 row words, and the whole input image is T * cw words -- pair_lds_bytes)
     const size_t cw = input_words(h);
     LSM_REQUIRE(inmask != 3 || (cw >= 5 && cw <= 8), "pair-block bit planes with %zu row words", cw);
@@ -1192,12 +1201,13 @@ static int run_quads(const lsm_reservoir *h, const RingVariant &rv, const RunArg
 {
     const bool inreg = ring_inreg(rv);
     const bool inmask = rv.inmask != nullptr;
-    lsm_lif::ring_fn_t rfn = inmask ? (rv.ql == 1 ? lsm_lif::pick_ring_mask_1(rv.wpc, rv.incol ? 2 : 1)
-                                                  : lsm_lif::pick_ring_mask_2(rv.wpc, rv.incol ? 2 : 1))
-                             : rv.ql == 1 ? lsm_lif::pick_ring_1(rv.wpc, inreg, rv.strided)
-                             : rv.ql == 2 ? lsm_lif::pick_ring_2(rv.wpc, inreg, rv.strided)
-                             : rv.ql == 3 ? lsm_lif::pick_ring_3(rv.wpc, inreg, rv.strided)
-                                          : lsm_lif::pick_ring_4(rv.wpc, inreg, rv.strided);
+    const bool st = r.stateful();
+    lsm_lif::ring_fn_t rfn = inmask ? (rv.ql == 1 ? lsm_lif::pick_ring_mask_1(rv.wpc, rv.incol ? 2 : 1, st)
+                                                  : lsm_lif::pick_ring_mask_2(rv.wpc, rv.incol ? 2 : 1, st))
+                             : rv.ql == 1 ? lsm_lif::pick_ring_1(rv.wpc, inreg, rv.strided, st)
+                             : rv.ql == 2 ? lsm_lif::pick_ring_2(rv.wpc, inreg, rv.strided, st)
+                             : rv.ql == 3 ? lsm_lif::pick_ring_3(rv.wpc, inreg, rv.strided, st)
+                                          : lsm_lif::pick_ring_4(rv.wpc, inreg, rv.strided, st);
     LSM_REQUIRE(rfn != nullptr, "no ring kernel for QL=%d WPC=%d", rv.ql, rv.wpc);
     lsm_lif::RingArgs a;
     set_common_args(&a, h, r);
@@ -1213,10 +1223,11 @@ static int run_dense(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
 {
     // the reference's refractory period (2 steps) counts down in scalar lane masks (lif_dense.h, REFM)
     const bool refm = h->refractory == lsm_lif::DENSE_REFM_REFRACTORY;
-    lsm_lif::dense_fn_t dfn = v.inmask      ? (v.incol ? lsm_lif::pick_dense_3(v.sl, v.wpc, refm)
-                                                       : lsm_lif::pick_dense_2(v.sl, v.wpc, refm))
-                              : lif_inreg(v) ? lsm_lif::pick_dense_1(v.sl, v.wpc, refm)
-                                             : lsm_lif::pick_dense_0(v.sl, v.wpc, refm);
+    const bool st = r.stateful();
+    lsm_lif::dense_fn_t dfn = v.inmask      ? (v.incol ? lsm_lif::pick_dense_3(v.sl, v.wpc, refm, st)
+                                                       : lsm_lif::pick_dense_2(v.sl, v.wpc, refm, st))
+                              : lif_inreg(v) ? lsm_lif::pick_dense_1(v.sl, v.wpc, refm, st)
+                                             : lsm_lif::pick_dense_0(v.sl, v.wpc, refm, st);
     LSM_REQUIRE(dfn != nullptr, "no dense kernel for SL=%d WPC=%d", v.sl, v.wpc);
     lsm_lif::DenseArgs a;
     set_common_args(&a, h, r);
@@ -1231,7 +1242,7 @@ static int run_dense(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
 
 static int run_sparse(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
 {
-    lif_fn_t fn = pick_kernel(v.sl, v.wpc, lif_inreg(v), lif_seg_in_lds(h, v, r.n_steps));
+    lif_fn_t fn = pick_kernel(v.sl, v.wpc, lif_inreg(v), lif_seg_in_lds(h, v, r.n_steps), r.stateful());
     LSM_REQUIRE(fn != nullptr, "no kernel for SL=%d WPC=%d", v.sl, v.wpc);
     LifArgs a;
     set_common_args(&a, h, r);
@@ -1245,14 +1256,27 @@ static int run_sparse(const lsm_reservoir *h, const Variant &v, const RunArgs &r
 static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
                          const int32_t *key_ids, int n_keys, float *features_out,
                          uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
-                         int waves_per_clip, void *workspace, long workspace_bytes, void *stream)
+                         int waves_per_clip, void *workspace, long workspace_bytes, void *stream,
+                         int first_step = 0, const void *state_in = nullptr, void *state_out = nullptr, bool from = false)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_run: null handle");
     LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
-    LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+    if (from) {
+        LSM_REQUIRE(first_step >= 0, "first_step=%d must be >= 0", first_step);
+        LSM_REQUIRE((long)first_step + n_steps <= 65535, "first_step + n_steps = %ld exceeds 65535 (the feature records hold "
+                    "spike times in 16 bits)", (long)first_step + n_steps);
+        LSM_REQUIRE(first_step == 0 || state_in != nullptr, "first_step=%d needs state_in (a run from reset starts at 0)",
+                    first_step);
+        LSM_REQUIRE((reinterpret_cast<uintptr_t>(state_in) & 15) == 0 && (reinterpret_cast<uintptr_t>(state_out) & 15) == 0,
+                    "state_in / state_out must be 16-byte aligned");
+        LSM_REQUIRE(n_keys >= 0 && n_keys <= 8 && (n_keys == 0 || key_ids), "n_keys must be in [0, 8]");
+        LSM_REQUIRE(n_keys == 0 || features_out, "null features_out with n_keys=%d", n_keys);
+    } else {
+        LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+    }
     LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
     if (n_clips == 0) return LSM_OK;            // empty batch: nothing to read or write
-    LSM_REQUIRE(spikes_u8 && features_out, "null buffer");
+    LSM_REQUIRE(spikes_u8 && (features_out || from), "null buffer");
     int dev_now = -1;
     LSM_CHECK_HIP(hipGetDevice(&dev_now));
     LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d",
@@ -1281,8 +1305,9 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
             order = ord;
         }
     }
-    const RunArgs r = {spikes_u8, n_clips, n_steps, n_keys, key_ids, order, features_out, v_trace_out, spike_matrix_out, stats_out,
-                       stream};
+    RunArgs r = {spikes_u8, n_clips, n_steps, n_keys, key_ids, order, features_out, v_trace_out, spike_matrix_out, stats_out,
+                 stream};
+    r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
     if (plan.pv) return run_pairs(h, *plan.pv, r);
     if (plan.rv) return run_quads(h, *plan.rv, r);
     return plan.kernel == KERNEL_DENSE ? run_dense(h, *plan.v, r) : run_sparse(h, *plan.v, r);
@@ -1308,6 +1333,47 @@ int lsm_reservoir_run_ordered(const lsm_reservoir *h, const uint8_t *spikes_u8, 
     LSM_REQUIRE(workspace != nullptr || n_clips == 0, "lsm_reservoir_run_ordered: null workspace");
     return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
                          stats_out, waves_per_clip, workspace, workspace_bytes, stream);
+}
+
+extern "C" __attribute__((visibility("default")))
+long lsm_reservoir_state_bytes(const lsm_reservoir *h)
+{
+    return h ? lsm_lif::state_bytes(h->N, h->n_out) : (long)LSM_ERR_ARG;
+}
+
+// lsm_reservoir_run / _run_ordered from a saved state and into one: the same plan, the same tables, the ST forms of the
+// kernels (lif_common.h).  With neither state it is lsm_reservoir_run.
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_run_from(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                           int first_step, const void *state_in, void *state_out,
+                           const int32_t *key_ids, int n_keys, float *features_out,
+                           uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                           int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
+{
+    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
+                         stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
+                         state_out, true);
+}
+
+// Largest n_steps make_plan accepts for this batch and waves_per_clip: every layout's LDS image grows with the steps, so
+// the accepted lengths are 1 .. that.
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_max_steps(const lsm_reservoir *h, int n_clips, int waves_per_clip)
+{
+    LSM_REQUIRE(h != nullptr, "lsm_reservoir_max_steps: null handle");
+    LSM_REQUIRE(n_clips >= 0, "bad n_clips");
+    LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
+    RunPlan p;
+    const int rc = make_plan(h, n_clips, 1, waves_per_clip, &p);
+    if (rc) return rc;                           // not even one step: the plan's own error
+    int lo = 1, hi = 65535;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        RunPlan q;
+        if (make_plan(h, n_clips, mid, waves_per_clip, &q) == LSM_OK) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
 }
 
 // Introspection for tests and the bench: kernel and layout chosen for a batch, LDS bytes per workgroup, bytes of the

@@ -340,3 +340,24 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     with torch.cuda.device(hp.device):
         feats = hp.run(pinned[lo:lo + batch] for lo in range(0, len(pinned), batch))
     return feats if device_out else feats.cpu().numpy()
+
+
+def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = True):
+    """A recording taken window by window: ``audio`` (n, W * fe.n_samples) float32 -> (n, W, n_feat) float32 device
+    tensor.  The front end runs on the n * W windows as independent clips (its normalisation is per clip, as the
+    reference's); the reservoir then takes window after window and, with ``carry_state``, keeps its membrane, refractory
+    and spike state between them (``SNN.run_batch(state=...)``): row w holds the features of steps [0, (w + 1) * T) of
+    the recording, what one run over the concatenated rasters gives.  ``carry_state=False``: every window from
+    ``reset()``, W independent ``run_batch`` calls."""
+    if isinstance(audio, np.ndarray):
+        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    ns = int(fe.n_samples)
+    if audio.dim() != 2 or audio.shape[1] < ns or audio.shape[1] % ns:
+        raise ValueError(f"audio must be (n, W * {ns}), got {tuple(audio.shape)}")
+    n, W = int(audio.shape[0]), int(audio.shape[1]) // ns
+    with torch.cuda.device(net.device):
+        x = audio.to(net.device, dtype=torch.float32).reshape(n * W, ns).contiguous()
+        rasters = fe.encode(x).reshape(n, W, fe.n_channels, -1)
+        state = net.new_state(n) if carry_state else None
+        rows = [net.run_batch(rasters[:, w].contiguous(), feature_keys, state=state)[0] for w in range(W)]
+        return torch.stack(rows, dim=1)

@@ -22,7 +22,62 @@ from .reservoir import Reservoir, SimulationParams, build_reservoir
 FEATURE_KEYS = ['spike_counts', 'spike_variances', 'mean_spike_times', 'first_spike_times',
                 'last_spike_times', 'mean_isi', 'isi_variances', 'burst_counts']
 
-__all__ = ["SNN", "SimulationParams", "FEATURE_KEYS"]
+MAX_STEPS = 65535                    # steps of one run, launches of a continued run added up (16-bit spike times)
+
+__all__ = ["SNN", "SimulationParams", "FEATURE_KEYS", "ReservoirState", "split_steps", "MAX_STEPS"]
+
+
+def split_steps(n_steps: int, max_steps: int) -> list:
+    """Cut a run of ``n_steps`` into consecutive launches of at most ``max_steps``: [(first_step, steps), ...], every
+    launch but the last one full."""
+    n_steps, max_steps = int(n_steps), int(max_steps)
+    if n_steps < 0 or max_steps < 1:
+        raise ValueError(f"split_steps({n_steps}, {max_steps}): need n_steps >= 0 and max_steps >= 1")
+    return [(t0, min(max_steps, n_steps - t0)) for t0 in range(0, n_steps, max_steps)]
+
+
+class ReservoirState:
+    """What a reservoir carries from one launch to the next (SPEC.md §4a, ``lsm_reservoir_run_from``): ``data``, a
+    (B, state_bytes) uint8 device tensor in the library's layout -- all zeros is ``reset()`` --, and ``steps_done``, the
+    host's count of the steps it holds.  ``SNN.run_batch(..., state=...)`` updates both in place."""
+
+    def __init__(self, data: torch.Tensor, num_neurons: int, num_output_neurons: int, steps_done: int = 0):
+        self.data = data
+        self.num_neurons = int(num_neurons)
+        self.num_output_neurons = int(num_output_neurons)
+        self.steps_done = int(steps_done)
+        self._np = (self.num_neurons + 63) // 64 * 64
+
+    def clone(self) -> "ReservoirState":
+        return ReservoirState(self.data.clone(), self.num_neurons, self.num_output_neurons, self.steps_done)
+
+    def _field(self, offset: int, nbytes: int, dtype) -> torch.Tensor:
+        return self.data[:, offset:offset + nbytes].contiguous().view(dtype)
+
+    def _bits(self, offset: int) -> torch.Tensor:
+        words = self._field(offset, self._np // 8, torch.int32)                       # (B, NP/32), bit i%32 of word i/32
+        shifts = torch.arange(32, device=words.device, dtype=torch.int32)
+        return ((words[:, :, None] >> shifts) & 1).reshape(words.shape[0], -1)[:, :self.num_neurons].bool()
+
+    def spike_total(self) -> torch.Tensor:
+        """(B,) spikes of the whole reservoir so far."""
+        return self._field(0, 4, torch.int32)[:, 0]
+
+    def membrane(self) -> torch.Tensor:
+        """(B, N) float32 membrane potentials after the last step done."""
+        return self._field(16, 4 * self._np, torch.float32)[:, :self.num_neurons]
+
+    def refractory(self) -> torch.Tensor:
+        """(B, N) int32 refractory countdowns after the last step done."""
+        return self._field(16 + 4 * self._np, 2 * self._np, torch.int16)[:, :self.num_neurons].to(torch.int32) & 0xFFFF
+
+    def last_spikes(self) -> torch.Tensor:
+        """(B, N) bool: fired at the last step done."""
+        return self._bits(16 + 6 * self._np)
+
+    def ever_fired(self) -> torch.Tensor:
+        """(B, N) bool: fired at least once so far."""
+        return self._bits(16 + 6 * self._np + self._np // 8)
 
 
 def _dev(t):
@@ -79,7 +134,8 @@ class SNN:
     # ---- batched path -------------------------------------------------------------------
     def run_batch(self, spikes, feature_keys=None, want_spike_matrix=False, want_v_trace=False,
                   waves_per_clip: int = 0, packed_time_steps: int = 0, stats_out=None, features_out=None,
-                  longest_first: bool | None = None):
+                  longest_first: bool | None = None, state: ReservoirState | None = None,
+                  state_out: ReservoirState | None = None):
         """spikes: uint8 (B, C, T) torch tensor on this device (or NumPy, copied).  Returns
         (features float32 (B, n_keys*N_out) device tensor, spike_matrix or None, v_trace or None);
         NaN entries are already 0 and keys are concatenated in the given order
@@ -94,7 +150,12 @@ class SNN:
         ``longest_first``: start the clips with the most input spikes first (``lsm_reservoir_run_ordered``: a
         clip's time grows with its activity, and a launch of several rounds is otherwise as long as whichever
         clip starts last); results are the same either way.  Default: on when the batch has more clips than the
-        GPU has compute units (``LSM_RESERVOIR_ORDER=0`` turns the default off)."""
+        GPU has compute units (``LSM_RESERVOIR_ORDER=0`` turns the default off).
+        ``state``: a ``ReservoirState`` (``new_state(B)``) to continue from: the launch runs steps
+        ``[state.steps_done, state.steps_done + T)``, updates the state in place and returns the features of the whole run
+        so far (absolute spike times); ``spike_matrix`` / ``v_trace`` cover this launch's T steps, ``stats_out`` the run so
+        far.  A run cut at any step gives what the uncut run gives, bit for bit (``lsm_reservoir_run_from``).
+        ``state_out``: with ``state``, write the new state there and leave ``state`` as it is."""
         if isinstance(spikes, np.ndarray):
             spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
         spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
@@ -125,9 +186,24 @@ class SNN:
             raise ValueError(f"stats_out must be a contiguous int32 ({B}, 2) tensor on {spikes.device}")
         if longest_first is None:
             longest_first = self.longest_first_default(B)
+        if state is not None:
+            self._check_state(state, B)
+            if state_out is not None:
+                self._check_state(state_out, B)
+        elif state_out is not None:
+            raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            if longest_first:
+            if state is not None:
+                need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
+                ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
+                _lib.check(self.lib.lsm_reservoir_run_from(
+                    self._handle, _dev(spikes), B, T, state.steps_done, _dev(state.data),
+                    _dev((state_out or state).data),
+                    _host(key_ids), len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out), int(waves_per_clip),
+                    _dev(ws), need, stream), "lsm_reservoir_run_from")
+                (state_out or state).steps_done = state.steps_done + T
+            elif longest_first:
                 # scratch of this call alone: the caching allocator hands a block back to the stream it was taken on
                 need = self.lib.lsm_reservoir_order_workspace(B)
                 ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device)
@@ -141,6 +217,57 @@ class SNN:
                     _dev(vt), _dev(stats_out), int(waves_per_clip), stream),
                     "lsm_reservoir_run")
         return feats, sm, vt
+
+    # ---- continuation -------------------------------------------------------------------
+    def state_bytes(self) -> int:
+        """Bytes of one clip's state block (``lsm_reservoir_state_bytes``)."""
+        return int(self.lib.lsm_reservoir_state_bytes(self._handle))
+
+    def new_state(self, n_clips: int) -> ReservoirState:
+        """The state of ``n_clips`` reservoirs after ``reset()``: zeros, no step done."""
+        data = torch.zeros((int(n_clips), self.state_bytes()), dtype=torch.uint8, device=self.device)
+        return ReservoirState(data, self.num_neurons, self.num_output_neurons, 0)
+
+    def _check_state(self, state, n_clips: int) -> None:
+        if not isinstance(state, ReservoirState):
+            raise _lib.LsmHipError(f"state must be a ReservoirState (SNN.new_state), got {type(state).__name__}")
+        d = state.data
+        if (d.dtype != torch.uint8 or tuple(d.shape) != (n_clips, self.state_bytes()) or not d.is_contiguous()
+                or d.device != self.device):
+            raise _lib.LsmHipError(f"state must hold a contiguous uint8 ({n_clips}, {self.state_bytes()}) tensor on "
+                                   f"{self.device}, got {d.dtype} {tuple(d.shape)} on {d.device}")
+
+    def max_steps(self, n_clips: int, waves_per_clip: int = 0) -> int:
+        """Largest T ``plan(n_clips, T, waves_per_clip)`` accepts (``lsm_reservoir_max_steps``)."""
+        n = int(self.lib.lsm_reservoir_max_steps(self._handle, int(n_clips), int(waves_per_clip)))
+        if n < 0:
+            _lib.check(n, "lsm_reservoir_max_steps")
+        return n
+
+    def run_chunked(self, spikes, feature_keys=None, chunk_steps: int | None = None, want_spike_matrix=False,
+                    want_v_trace=False, waves_per_clip: int = 0, stats_out=None, longest_first: bool | None = None):
+        """``run_batch`` for clips of any length up to 65535 steps: the run is cut into launches of ``chunk_steps`` (default:
+        the longest launch the plan accepts, ``max_steps``) that hand their state on.  Same returns and the same values as
+        one launch over the whole clip would give; ``spike_matrix`` / ``v_trace`` are assembled over the launches."""
+        if isinstance(spikes, np.ndarray):
+            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
+        spikes = spikes.to(self.device, dtype=torch.uint8)
+        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
+            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        B, _, T = spikes.shape
+        if T < 1 or T > MAX_STEPS:
+            raise _lib.LsmHipError(f"n_steps = {T} outside [1, {MAX_STEPS}]")
+        if chunk_steps is None:
+            chunk_steps = self.max_steps(B, waves_per_clip)
+        state = self.new_state(B)
+        feats, sms, vts = None, [], []
+        for t0, n in split_steps(T, chunk_steps):
+            feats, sm, vt = self.run_batch(spikes[:, :, t0:t0 + n], feature_keys, want_spike_matrix, want_v_trace,
+                                           waves_per_clip, stats_out=stats_out, longest_first=longest_first, state=state)
+            sms.append(sm)
+            vts.append(vt)
+        return (feats, torch.cat(sms, dim=1) if want_spike_matrix else None,
+                torch.cat(vts, dim=1) if want_v_trace else None)
 
     def longest_first_default(self, n_clips: int) -> bool:
         """Whether ``run_batch`` starts the clips of a batch of this size longest first by default."""
