@@ -101,10 +101,19 @@ def load_spike_dataset(filename=DATASET_FILE):
     return X_spikes, y_labels
 
 
+def check_time_segments(n_steps: int, time_segments: int) -> int:
+    """``--time-segments K``: the clips' T steps are read in K equal segments; the segment length T // K.  K must divide T."""
+    K = int(time_segments)
+    if K < 1 or int(n_steps) % K != 0:
+        raise ValueError(f"--time-segments {time_segments}: must be >= 1 and divide the clips' {n_steps} time steps")
+    return int(n_steps) // K
+
+
 def extract_all_features(lsm, spike_data, feature_keys, desc=""):
     """(n, C, T) uint8 -> (n, len(keys) * N_out) features, NaN -> 0, keys in the given order.
     Batched on the GPU (and sharded across ranks under torchrun) when ``lsm`` offers ``run_batch``;
-    otherwise the reference's one-clip-at-a-time object protocol is used."""
+    otherwise the reference's one-clip-at-a-time object protocol is used.  (The reference's four parameters, pinned;
+    ``extract_all_segment_features`` reads the clips per time segment.)"""
     if hasattr(lsm, "run_batch"):
         import torch
         from lsm_speech_classifier_amd import dist as lsm_dist
@@ -132,6 +141,35 @@ def extract_all_features(lsm, spike_data, feature_keys, desc=""):
         feats = lsm.extract_features_from_spikes()
         rows.append(np.concatenate([np.nan_to_num(feats[k].copy()) for k in feature_keys if k in feats]))
     return np.array(rows)
+
+
+def extract_all_segment_features(lsm, spike_data, feature_keys, desc="", time_segments=1):
+    """extract_all_features per time segment: every clip is read in K = ``time_segments`` equal segments
+    (``SNN.run_segments``, SPEC.md 4b) and its row is the K segment rows side by side -- (n, K * len(keys) * N_out),
+    segment-major, then key-major.  The same batching, sharding and gather; K = 1 is extract_all_features itself."""
+    if time_segments == 1:
+        return extract_all_features(lsm, spike_data, feature_keys, desc)
+    import torch
+    from lsm_speech_classifier_amd import dist as lsm_dist
+    if not hasattr(lsm, "run_segments"):
+        raise ValueError("--time-segments needs a reservoir with run_segments (lsm_speech_classifier_amd.snn.SNN)")
+    spike_data = np.asarray(spike_data)
+    if spike_data.ndim != 3:
+        raise ValueError(f"--time-segments needs clips of one length, got an array of shape {spike_data.shape}")
+    seg = check_time_segments(spike_data.shape[2], time_segments)
+    rank, world = lsm_dist.group_world()
+    n = len(spike_data)
+    lo, hi = lsm_dist.shard_range(n, rank, world) if world > 1 else (0, n)
+    if desc and rank == 0:
+        print(f"{desc}: {n} clips in {time_segments} time segments" + (f" over {world} GPUs" if world > 1 else ""))
+    rows = [lsm.run_segments(np.ascontiguousarray(spike_data[a:min(hi, a + RUN_BATCH)]), seg, feature_keys)
+            .reshape(min(hi, a + RUN_BATCH) - a, -1) for a in range(lo, hi, RUN_BATCH)]
+    if rows:
+        local = torch.cat(rows)
+    else:               # an empty shard still takes part in the gather, with the row width of the others
+        width = lsm.run_batch(np.ascontiguousarray(spike_data[:0]), feature_keys)[0].shape[1] * int(time_segments)
+        local = torch.empty((0, width), dtype=torch.float32, device=lsm.device)
+    return lsm_dist.gather_rows(local, n).cpu().numpy()
 
 
 def run_network_diagnostics(lsm, X_sample_batch):
@@ -173,7 +211,8 @@ def run_network_diagnostics(lsm, X_sample_batch):
 
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
-                    num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None):
+                    num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
+                    time_segments=1):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -190,7 +229,10 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     extract_lsm_features.py:199-212 -> train_classifier.py:27-45): the gathered rows never leave the device --
     `readout.StandardScaler` -> the PyTorch readout -> predictions, all on rank 0's GPU; File 2 is still written
     (ONE device-to-host copy of the scaled arrays, schema unchanged) and the report train_classifier.py prints is
-    printed here.  Returns the test accuracy then (None otherwise, like the reference's main())."""
+    printed here.  Returns the test accuracy then (None otherwise, like the reference's main()).
+
+    `time_segments` = K > 1: every clip is read in K equal time segments (`pipeline.HotPath(time_segments=K)`); File 2
+    keeps its keys, the feature arrays get K times the columns."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
@@ -211,6 +253,7 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
         np.arange(len(audio)), labels, test_size=0.2, random_state=42, stratify=labels)
     dev = lsm_dist.local_device() if world > 1 else None
     fe = frontend.SpikeFrontEnd(n_filters, filterbank, device=dev)
+    check_time_segments(fe.n_steps, time_segments)                  # refused with the reason before any work is done
     head = fe.encode(audio[idx_train[:500]]).cpu().numpy()          # what w_critico and the diagnostics look at
     params = _simulation_params(head[0], leak_variance_divisor, num_neurons, num_output_neurons, small_world_k, seed)
     with _rank0_only(rank):
@@ -231,7 +274,8 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     def split_features(idx):
         """(len(idx), n_feat) float32 rows in dataset order, STILL ON THE DEVICE (every rank holds all of them)."""
         lo, hi = lsm_dist.shard_range(len(idx), rank, world)
-        local = pipeline.features_from_audio(audio[idx[lo:hi]], fe, lsm, keys, batch=batch, device_out=True)
+        local = pipeline.features_from_audio(audio[idx[lo:hi]], fe, lsm, keys, batch=batch, device_out=True,
+                                             time_segments=time_segments)
         return lsm_dist.gather_rows(local, len(idx))
 
     X_train_dev = split_features(idx_train)
@@ -276,9 +320,11 @@ def _device_readout(X_train_dev, X_test_dev, y_train, y_test, readout, feature_s
 
 
 def main(feature_set: str, multiplier: float, leak_variance_divisor: float = None, *, num_neurons=None,
-         num_output_neurons=None, small_world_k=None, seed=None):
+         num_output_neurons=None, small_world_k=None, seed=None, time_segments=None):
     """The reference's three arguments; the keyword-only ones expose the module constants the reference
-    hard-codes (NUM_NEURONS, NUM_OUTPUT_NEURONS, SMALL_WORLD_K, the NumPy seed), None = the reference's value."""
+    hard-codes (NUM_NEURONS, NUM_OUTPUT_NEURONS, SMALL_WORLD_K, the NumPy seed), None = the reference's value.
+    `time_segments` = K > 1: features per time segment, K times the columns (None or 1 = the reference's whole-clip rows)."""
+    time_segments = 1 if time_segments is None else int(time_segments)
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist
@@ -292,6 +338,8 @@ def main(feature_set: str, multiplier: float, leak_variance_divisor: float = Non
         return
     X_train, X_test, y_train, y_test = train_test_split(
         X_spikes, y_labels, test_size=0.2, random_state=42, stratify=y_labels)
+    if time_segments != 1:
+        check_time_segments(np.asarray(X_train[0]).shape[1], time_segments)      # refused before the reservoir is built
 
     params = _simulation_params(X_train[0], leak_variance_divisor, num_neurons, num_output_neurons, small_world_k, seed)
     with _rank0_only(rank):
@@ -310,8 +358,12 @@ def main(feature_set: str, multiplier: float, leak_variance_divisor: float = Non
     keys = FEATURE_SETS[feature_set]
     if rank == 0:
         print(f"Extracting feature set: '{feature_set}'")
-    X_train_feat = extract_all_features(lsm, X_train, keys, "Training")
-    X_test_feat = extract_all_features(lsm, X_test, keys, "Testing")
+    if time_segments == 1:
+        X_train_feat = extract_all_features(lsm, X_train, keys, "Training")
+        X_test_feat = extract_all_features(lsm, X_test, keys, "Testing")
+    else:
+        X_train_feat = extract_all_segment_features(lsm, X_train, keys, "Training", time_segments)
+        X_test_feat = extract_all_segment_features(lsm, X_test, keys, "Testing", time_segments)
     lsm_dist.finish()
     if rank != 0:
         return
@@ -336,13 +388,20 @@ def add_reservoir_flags(ap):
     ap.add_argument("--seed", type=int, default=None, help="Seed of the reservoir wiring (default 42).")
 
 
+def add_time_segments_flag(ap):
+    ap.add_argument("--time-segments", type=int, default=1,
+                    help="Read every clip in K equal time segments: K feature rows per clip side by side (K must divide the "
+                         "clips' time steps; default 1 = one row over the whole clip).")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="Extract features from a spike train dataset using an LSM.")
     ap.add_argument("--feature-set", type=str, default="original", choices=FEATURE_SETS.keys())
     ap.add_argument("--multiplier", type=float, default=0.6)
     ap.add_argument("--leak-variance-divisor", type=float, default=None)
     add_reservoir_flags(ap)
+    add_time_segments_flag(ap)
     a = ap.parse_args()
     main(feature_set=a.feature_set, multiplier=a.multiplier, leak_variance_divisor=a.leak_variance_divisor,
          num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons, small_world_k=a.small_world_k,
-         seed=a.seed)
+         seed=a.seed, time_segments=a.time_segments)

@@ -275,6 +275,36 @@ int lsm_reservoir_run_from(const lsm_reservoir *h, const uint8_t *spikes_u8, int
                            const int32_t *key_ids, int n_keys, float *features_out,
                            uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                            int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream);
+
+/* Segments and windows (SPEC.md §4b): lsm_reservoir_run_from with the feature bookkeeping cut every segment_steps steps.
+ * Segment g of the launch covers its steps [g * segment_steps, (g + 1) * segment_steps); records_out receives, per clip,
+ * segment and output neuron, the record of the state block's packing {n | bursts << 16, first | last << 16, S1, Q} over
+ * the neuron's spikes inside that segment, on times local to the segment (0 .. segment_steps - 1):
+ *   records_out  (n_clips, n_steps / segment_steps, n_out) x 16 bytes, DEVICE memory owned by the caller, 16-byte
+ *                aligned, required
+ * The dynamics are one uncut run: state_out, the cumulative features_out (absolute times; NULL with n_keys = 0),
+ * stats_out, the spike matrix and the membrane trace are lsm_reservoir_run_from's, bit for bit.  Records of consecutive
+ * launches cut at a segment boundary concatenate along the segment axis.  lsm_reservoir_plan and lsm_reservoir_max_steps
+ * answer for a segmented launch as for an unsegmented one (the LDS image is the same).  LSM_ERR_ARG for
+ * segment_steps < 1, n_steps % segment_steps != 0, a NULL or misaligned records_out, and lsm_reservoir_run_from's refusals.
+ *
+ * lsm_segment_features turns records into feature rows: window w of window_segments segments starts at segment
+ * w * hop_segments, there are W = (n_segments - window_segments) / hop_segments + 1 of them, and a window's row is, bit for
+ * bit, the feature row of the (window_segments * segment_steps, N) slice of the spike matrix it covers (§4a's merge folded
+ * over its records, then §4's features with T = window_segments * segment_steps):
+ *   records       (n_clips, n_segments, n_out) x 16 bytes as written above (launches concatenated along the segment axis)
+ *   features_out  (n_clips, W, n_keys * n_out) float32, key-major rows
+ * LSM_ERR_ARG for segment_steps < 1, window_segments < 1 or > n_segments, hop_segments < 1,
+ * window_segments * segment_steps > 65535, n_keys outside [1, 8], a misaligned records pointer. */
+int lsm_reservoir_run_segments(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                               int segment_steps, int first_step, const void *state_in, void *state_out, void *records_out,
+                               const int32_t *key_ids, int n_keys, float *features_out,
+                               uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                               int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream);
+int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clips, int n_segments, int segment_steps,
+                         int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
+                         void *stream);
+
 /* Largest n_steps lsm_reservoir_plan accepts for (n_clips, waves_per_clip), at most 65535; < 0 when it accepts none. */
 int lsm_reservoir_max_steps(const lsm_reservoir *h, int n_clips, int waves_per_clip);
 

@@ -53,6 +53,9 @@ _SIGS = {
     "lsm_reservoir_state_bytes": (C.c_long, [c_void]),
     "lsm_reservoir_run_from": (c_int, [c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_int, c_void,
                                        c_void, c_void, c_void, c_int, c_void, C.c_long, c_void]),
+    "lsm_reservoir_run_segments": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_void,
+                                           c_int, c_void, c_void, c_void, c_void, c_int, c_void, C.c_long, c_void]),
+    "lsm_segment_features": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_void]),
     "lsm_reservoir_max_steps": (c_int, [c_void, c_int, c_int]),
     "lsm_reservoir_layout": (c_int, [c_void, c_int, c_int, c_int, C.POINTER(c_int),
                                      C.POINTER(c_int), C.POINTER(c_int)]),

@@ -129,6 +129,8 @@ struct StateArgs {
     unsigned char *out;        // (B, stride) receives the state after step t0+T-1, or null; may be `in`
     long stride;               // bytes per clip: state_bytes(N, n_out)
     int t0;                    // steps done before this launch
+    int seg;                   // SPEC.md §4b: steps per segment (divides T), 0 = the launch is not segmented
+    uint4 *rec;                // seg > 0: (B, T / seg, n_out) segment records
 };
 
 __host__ __device__ inline int state_np(int N) { return (N + 63) & ~63; }
@@ -198,6 +200,74 @@ __device__ __forceinline__ uint4 merge_feature_records(uint4 f1, uint4 f2, uint3
     m.y = first1 | (last2 << 16);
     m.w = f1.w + f2.w + isi * isi;
     return m;
+}
+
+// ---- segments (SPEC.md §4b, include/lsm_hip.h: lsm_reservoir_run_segments; ST forms with StateArgs::seg > 0) ------------
+// The step loops keep their records on launch-local times.  After the update of the last step of a segment the lane that
+// owns an output neuron -- the only writer of its record -- closes it: rebased to the segment's own times, stored, zeroed.
+// No barrier is involved: the next write of the record is the same lane's.
+struct SegmentCursor {
+    uint4 *rec;                // records of the open segment of this clip
+    uint32_t t_begin;          // its first step (launch-local)
+    uint32_t t_end;            // the step after its last; 0 = not segmented (no step t has t + 1 == 0)
+};
+
+__device__ __forceinline__ SegmentCursor segment_cursor(const StateArgs &st, int b, int T, int n_out)
+{
+    SegmentCursor c;
+    c.rec = st.seg > 0 ? st.rec + (size_t)b * (size_t)(T / st.seg) * (size_t)n_out : nullptr;
+    c.t_begin = 0u;
+    c.t_end = st.seg > 0 ? (uint32_t)st.seg : 0u;
+    return c;
+}
+
+// Workgroup-uniform: step t was the last of the open segment.
+__device__ __forceinline__ bool segment_ends(const SegmentCursor &c, int t) { return (uint32_t)(t + 1) == c.t_end; }
+
+// The record of output slot o over the open segment, on segment-local times: first and last lose t_begin, S1 loses
+// n * t_begin; the intervals (Q, bursts) do not depend on the origin.  An empty record stays all zeros.
+__device__ __forceinline__ void segment_close(const SegmentCursor &c, int o, uint4 f)
+{
+    const uint32_t n = f.x & 0xFFFFu;
+    if (n != 0u) {
+        f.y -= c.t_begin | (c.t_begin << 16);
+        f.z -= n * c.t_begin;
+    }
+    c.rec[o] = f;
+}
+
+// The LDS-held record of output slot o (-1: the neuron is no output neuron): closed and zeroed by its owner.  The callers
+// read the slots of their neurons again from the layout's table, in a loop that is not unrolled: a segment end is rare,
+// and the step loop's registers stay what they are.
+__device__ __forceinline__ void segment_close_lds(const SegmentCursor &c, uint4 *feat, int o)
+{
+    if (o >= 0) {
+        segment_close(c, o, feat[o]);
+        feat[o] = make_uint4(0, 0, 0, 0);
+    }
+}
+
+__device__ __forceinline__ void segment_next(SegmentCursor *c, int seg, int n_out)
+{
+    c->rec += n_out;
+    c->t_begin = c->t_end;
+    c->t_end += (uint32_t)seg;
+}
+
+// Epilogue, before state_finish and behind a barrier that follows the last close: the launch-wide record of every output
+// neuron is the left fold of §4a's merge over the clip's own segment records, read back from the records buffer (the
+// workgroup's own stores, ordered by that barrier) -- no second LDS record array.
+template <int NT>
+__device__ __forceinline__ void segment_fold(const StateArgs &st, int b, int T, uint4 *feat, int n_out, int burst_isi_max, int tid)
+{
+    const int G = T / st.seg;
+    const uint4 *rec = st.rec + (size_t)b * (size_t)G * (size_t)n_out;
+    for (int o = tid; o < n_out; o += NT) {
+        uint4 f = make_uint4(0, 0, 0, 0);
+        for (int g = 0; g < G; ++g)
+            f = merge_feature_records(f, rec[(size_t)g * n_out + o], (uint32_t)(g * st.seg), burst_isi_max);
+        feat[o] = f;
+    }
 }
 
 // Epilogue, last: every wave has stored its neurons and added its spikes to the total (lane 0, state_add_total).  Writes the

@@ -180,6 +180,8 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     for (int r = 0; r < (FEATREG ? SL : 1); ++r) fr[r] = make_uint4(0, 0, 0, 0);
     uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
     uint32_t tot_spk = 0u;             // spikes of my wave (stats)
+    SegmentCursor sc = {nullptr, 0u, 0u};       // ST: the open segment (SPEC.md §4b)
+    if constexpr (ST) sc = segment_cursor(a.st, b, T, a.n_out);
     if constexpr (ST) {
         if (a.st.in) {
             // the state after step t0-1: potentials, countdowns, and the spike lists of that step as the update leaves them
@@ -434,6 +436,21 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
         }
         tot_spk += (uint32_t)nspk;
         if (lane == 0) wcnt[cur * 16 + w] = (uint32_t)nspk;   // > R: next step's consumers merge the lists
+        if constexpr (ST) {
+            if (segment_ends(sc, t)) {           // the owners close their records (FEATREG: straight from the registers)
+                if constexpr (FEATREG) {
+#pragma unroll
+                    for (int r = 0; r < SL; ++r) {
+                        if (os[r] >= 0) segment_close(sc, os[r], fr[r]);
+                        fr[r] = make_uint4(0, 0, 0, 0);
+                    }
+                } else {
+#pragma unroll 1
+                    for (int r = 0; r < SL; ++r) segment_close_lds(sc, feat, a.oslot[(w * SL + r) * 64 + lane]);
+                }
+                segment_next(&sc, a.st.seg, a.n_out);
+            }
+        }
         if (trace) {
 #pragma unroll
             for (int r = 0; r < SL; ++r) {
@@ -474,6 +491,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
         const int nlast = (int)wcnt[lastbuf * 16 + w];
         for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
     const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)

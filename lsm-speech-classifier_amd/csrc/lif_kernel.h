@@ -182,6 +182,8 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
     const float theta = a.theta, w_in = a.w_in;
     const uint32_t *my_ent = a.in_ent + (size_t)w * a.EinW;   // !INREG: streamed from L2 each step
     const bool trace = a.spike_matrix != nullptr || a.v_trace != nullptr;
+    SegmentCursor sc = {nullptr, 0u, 0u};       // ST: the open segment (SPEC.md §4b)
+    if constexpr (ST) sc = segment_cursor(a.st, b, T, a.n_out);
     __syncthreads();
 
     // input drive of step `ts`: count the active channels feeding each target (integer atomics,
@@ -373,6 +375,13 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         }
         tot_spk += (uint32_t)nspk;
         if (lane == 0) wcnt[cur * 16 + w] = (uint32_t)nspk;
+        if constexpr (ST) {
+            if (segment_ends(sc, t)) {           // the owners close their records: stored on segment-local times, zeroed
+#pragma unroll 1
+                for (int r = 0; r < SL; ++r) segment_close_lds(sc, feat, a.oslot[(w * SL + r) * 64 + lane]);
+                segment_next(&sc, a.st.seg, a.n_out);
+            }
+        }
         if (trace) {
 #pragma unroll
             for (int r = 0; r < SL; ++r) {
@@ -404,6 +413,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         const int nlast = (int)wcnt[lastbuf * 16 + w];
         for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
     const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)

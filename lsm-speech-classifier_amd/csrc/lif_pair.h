@@ -259,6 +259,8 @@ void lif_pair_kernel(const PairArgs a)
     uint32_t *mymarks = marks + w * 64;
     uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
     uint32_t tot_spk = 0u;             // spikes of my wave (stats)
+    SegmentCursor sc = {nullptr, 0u, 0u};       // ST: the open segment (SPEC.md §4b)
+    if constexpr (ST) sc = segment_cursor(a.st, b, T, a.n_out);
 #if LSM_PAIR_PHASES
     uint32_t ph_[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     uint32_t rows_ = 0u;
@@ -581,6 +583,17 @@ void lif_pair_kernel(const PairArgs a)
             if (vt_row) vt_row += N;
         }
         tot_spk += (uint32_t)nspk;
+        if constexpr (ST) {
+            if (segment_ends(sc, t)) {           // the owners close their records: stored on segment-local times, zeroed
+#pragma unroll 1
+                for (int q = 0; q < BL; ++q) {
+                    const int2 o2 = *reinterpret_cast<const int2 *>(a.oslot + LSM_PAIR_GB(q) * 128 + lane * 2);
+                    segment_close_lds(sc, feat, o2.x);
+                    segment_close_lds(sc, feat, o2.y);
+                }
+                segment_next(&sc, a.st.seg, a.n_out);
+            }
+        }
         LSM_PAIR_MARK(5)               // neuron update, spike lists, feature accumulators
         __syncthreads();
         LSM_PAIR_MARK(6)               // barrier
@@ -607,6 +620,7 @@ void lif_pair_kernel(const PairArgs a)
             for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, gb * 128 + (int)list_last[l]);
         }
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
 #undef LSM_PAIR_GB

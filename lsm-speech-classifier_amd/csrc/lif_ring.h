@@ -204,6 +204,8 @@ void lif_ring_kernel(const RingArgs a)
     const int H = a.H, NQ = a.NQ;
     uint32_t hf = 0u;                  // bit r: my neuron r fired at least once (stats)
     uint32_t tot_spk = 0u;             // spikes of my wave (stats)
+    SegmentCursor sc = {nullptr, 0u, 0u};       // ST: the open segment (SPEC.md §4b)
+    if constexpr (ST) sc = segment_cursor(a.st, b, T, a.n_out);
     if constexpr (ST) {
         if (a.st.in) {
             // the state after step t0-1: potentials, countdowns, and the quad lists of that step as the update leaves them
@@ -552,6 +554,19 @@ void lif_ring_kernel(const RingArgs a)
             }
         }
         tot_spk += (uint32_t)nspk;
+        if constexpr (ST) {
+            if (segment_ends(sc, t)) {           // the owners close their records: stored on segment-local times, zeroed
+#pragma unroll 1
+                for (int q = 0; q < QL; ++q) {
+                    const int4 o4 = *reinterpret_cast<const int4 *>(a.oslot + LSM_RING_GQ(q) * 256 + lane * 4);
+                    segment_close_lds(sc, feat, o4.x);
+                    segment_close_lds(sc, feat, o4.y);
+                    segment_close_lds(sc, feat, o4.z);
+                    segment_close_lds(sc, feat, o4.w);
+                }
+                segment_next(&sc, a.st.seg, a.n_out);
+            }
+        }
         __syncthreads();
     }
     __builtin_amdgcn_s_setprio(0);
@@ -576,6 +591,7 @@ void lif_ring_kernel(const RingArgs a)
             for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         }
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
 #undef LSM_RING_GQ

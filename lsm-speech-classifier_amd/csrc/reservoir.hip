@@ -1135,7 +1135,10 @@ struct RunArgs {                // what one run is given, as the launch function
     const void *state_in = nullptr;
     void *state_out = nullptr;
     int first_step = 0;
-    bool stateful() const { return state_in != nullptr || state_out != nullptr; }
+    // segments (lsm_reservoir_run_segments): steps per segment and the records buffer; the ST forms close the records
+    int segment_steps = 0;
+    void *records = nullptr;
+    bool stateful() const { return state_in != nullptr || state_out != nullptr || segment_steps > 0; }
 };
 
 // The fields LifArgs, DenseArgs, RingArgs and PairArgs have in common.
@@ -1153,6 +1156,7 @@ static void set_common_args(Args *a, const lsm_reservoir *h, const RunArgs &r)
     a->stats = r.stats; a->order = r.order;
     a->st.in = static_cast<const unsigned char *>(r.state_in); a->st.out = static_cast<unsigned char *>(r.state_out);
     a->st.stride = lsm_lif::state_bytes(h->N, h->n_out); a->st.t0 = r.first_step;
+    a->st.seg = r.segment_steps; a->st.rec = static_cast<uint4 *>(r.records);
 }
 
 // One workgroup of wpc waves per clip, `lds` bytes of dynamic LDS.
@@ -1257,10 +1261,17 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                          const int32_t *key_ids, int n_keys, float *features_out,
                          uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                          int waves_per_clip, void *workspace, long workspace_bytes, void *stream,
-                         int first_step = 0, const void *state_in = nullptr, void *state_out = nullptr, bool from = false)
+                         int first_step = 0, const void *state_in = nullptr, void *state_out = nullptr, bool from = false,
+                         bool segmented = false, int segment_steps = 0, void *records = nullptr)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_run: null handle");
     LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
+    if (segmented) {
+        LSM_REQUIRE(segment_steps >= 1, "segment_steps=%d must be >= 1", segment_steps);
+        LSM_REQUIRE(n_steps % segment_steps == 0, "n_steps=%d is not a multiple of segment_steps=%d", n_steps, segment_steps);
+        LSM_REQUIRE(records != nullptr || n_clips == 0, "null records_out");
+        LSM_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "records_out must be 16-byte aligned");
+    }
     if (from) {
         LSM_REQUIRE(first_step >= 0, "first_step=%d must be >= 0", first_step);
         LSM_REQUIRE((long)first_step + n_steps <= 65535, "first_step + n_steps = %ld exceeds 65535 (the feature records hold "
@@ -1308,6 +1319,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
     RunArgs r = {spikes_u8, n_clips, n_steps, n_keys, key_ids, order, features_out, v_trace_out, spike_matrix_out, stats_out,
                  stream};
     r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
+    if (segmented) { r.segment_steps = segment_steps; r.records = records; }
     if (plan.pv) return run_pairs(h, *plan.pv, r);
     if (plan.rv) return run_quads(h, *plan.rv, r);
     return plan.kernel == KERNEL_DENSE ? run_dense(h, *plan.v, r) : run_sparse(h, *plan.v, r);
@@ -1353,6 +1365,86 @@ int lsm_reservoir_run_from(const lsm_reservoir *h, const uint8_t *spikes_u8, int
     return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
                          stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
                          state_out, true);
+}
+
+// lsm_reservoir_run_from with the feature bookkeeping cut every segment_steps steps (SPEC.md §4b): always the ST forms,
+// which close each output neuron's record into records_out at the segment ends (lif_common.h, segment_close).
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_run_segments(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                               int segment_steps, int first_step, const void *state_in, void *state_out, void *records_out,
+                               const int32_t *key_ids, int n_keys, float *features_out,
+                               uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                               int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
+{
+    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
+                         stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
+                         state_out, true, true, segment_steps, records_out);
+}
+
+// One thread per (clip, window, output neuron): §4a's merge folded over the window's records, then the neuron's n_keys
+// features (key-major rows, as write_features writes them).
+struct SegmentFeatureArgs {
+    const uint4 *rec;          // (B, G, n_out)
+    float *features;           // (B, W, n_keys * n_out)
+    int B, G, S, K, H, W, n_out, n_keys, burst_isi_max;
+    int key_ids[8];
+};
+
+__global__ __launch_bounds__(256) void segment_features_kernel(const SegmentFeatureArgs a)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.B * a.W * a.n_out;
+    if (idx >= total) return;
+    const int o = (int)(idx % a.n_out);
+    const long bw = idx / a.n_out;
+    const int wdw = (int)(bw % a.W);
+    const int b = (int)(bw / a.W);
+    const uint4 *rec = a.rec + ((size_t)b * a.G + (size_t)wdw * a.H) * a.n_out + o;
+    uint4 f = make_uint4(0, 0, 0, 0);
+    for (int j = 0; j < a.K; ++j)
+        f = lsm_lif::merge_feature_records(f, rec[(size_t)j * a.n_out], (uint32_t)(j * a.S), a.burst_isi_max);
+    const int n = (int)(f.x & 0xFFFFu), bursts = (int)(f.x >> 16);
+    const int first = (int)(f.y & 0xFFFFu), last = (int)(f.y >> 16);
+    float *row = a.features + (size_t)bw * a.n_keys * a.n_out + o;
+    for (int k = 0; k < a.n_keys; ++k)
+        row[(size_t)k * a.n_out] = lsm_lif::feature_value(a.key_ids[k], n, bursts, first, last, f.z, f.w, a.K * a.S);
+}
+
+extern "C" __attribute__((visibility("default")))
+int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clips, int n_segments, int segment_steps,
+                         int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
+                         void *stream)
+{
+    LSM_REQUIRE(h != nullptr, "lsm_segment_features: null handle");
+    LSM_REQUIRE(n_clips >= 0 && n_segments >= 1, "bad n_clips/n_segments");
+    LSM_REQUIRE(segment_steps >= 1, "segment_steps=%d must be >= 1", segment_steps);
+    LSM_REQUIRE(window_segments >= 1 && window_segments <= n_segments, "window_segments=%d must be in [1, n_segments=%d]",
+                window_segments, n_segments);
+    LSM_REQUIRE(hop_segments >= 1, "hop_segments=%d must be >= 1", hop_segments);
+    LSM_REQUIRE((long)window_segments * segment_steps <= 65535, "a window of %d segments of %d steps exceeds 65535 steps "
+                "(the feature records hold spike times in 16 bits)", window_segments, segment_steps);
+    LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+    for (int k = 0; k < n_keys; ++k)
+        LSM_REQUIRE(key_ids[k] >= 0 && key_ids[k] < 8, "key id %d out of range", key_ids[k]);
+    LSM_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "records must be 16-byte aligned");
+    if (n_clips == 0) return LSM_OK;
+    LSM_REQUIRE(records && features_out, "null buffer");
+    int dev_now = -1;
+    LSM_CHECK_HIP(hipGetDevice(&dev_now));
+    LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d",
+                h->device, dev_now);
+    SegmentFeatureArgs a;
+    a.rec = static_cast<const uint4 *>(records); a.features = features_out;
+    a.B = n_clips; a.G = n_segments; a.S = segment_steps; a.K = window_segments; a.H = hop_segments;
+    a.W = (n_segments - window_segments) / hop_segments + 1;
+    a.n_out = h->n_out; a.n_keys = n_keys; a.burst_isi_max = h->burst_isi_max;
+    for (int k = 0; k < 8; ++k) a.key_ids[k] = k < n_keys ? key_ids[k] : 0;
+    const long total = (long)a.B * a.W * a.n_out;
+    LSM_REQUIRE((total + 255) / 256 <= 0x7FFFFFFFL, "too many (clip, window, output neuron) triples: %ld", total);
+    if (total == 0) return LSM_OK;
+    hipLaunchKernelGGL(segment_features_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    LSM_CHECK_HIP(hipGetLastError());
+    return LSM_OK;
 }
 
 // Largest n_steps make_plan accepts for this batch and waves_per_clip: every layout's LDS image grows with the steps, so

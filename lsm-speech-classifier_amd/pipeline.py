@@ -51,11 +51,13 @@ def configure_hardware_queues(n: int = DEFAULT_HW_QUEUES) -> int:
 class HotPath:
     """fe: frontend.SpikeFrontEnd, net: snn.SNN (same device).  `streams` = reservoir streams (1 = serial:
     everything on the current stream); `fe_streams` = front-end streams of their own (0 = rotation: a step keeps to
-    one of the `streams`; None = DEFAULT_FE_STREAMS)."""
+    one of the `streams`; None = DEFAULT_FE_STREAMS).  `time_segments` = K > 1: a step's reservoir launch is the segmented
+    one (`SNN.run_segments`, K segments of T // K steps, SPEC.md §4b) and a clip's row is its K segment rows side by side
+    (segment-major, then key-major: K times the columns); 1 = the whole-clip row, the calls of a pipeline without it."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
-                 fe_streams: int | None = None):
+                 fe_streams: int | None = None, time_segments: int = 1):
         def norm(d):      # a tensor's device always carries its index, `torch.device("cuda")` does not
             return d if d.index is not None or d.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
         if norm(fe.device) != norm(net.device):
@@ -65,6 +67,9 @@ class HotPath:
         self.fe, self.net = fe, net
         self.device = norm(fe.device)     # so that a device-resident batch is recognised as such (not copied again)
         self.feature_keys = feature_keys
+        self.time_segments = int(time_segments)
+        if self.time_segments < 1 or fe.n_steps % self.time_segments:
+            raise ValueError(f"time_segments = {time_segments} must be >= 1 and divide the front end's {fe.n_steps} steps")
         self.n_streams = max(1, int(streams))
         # inside the rotation the reservoir launch shares the chip: let the library pick for that case
         self.waves_per_clip = (-1 if self.n_streams > 1 else 0) if waves_per_clip is None else int(waves_per_clip)
@@ -117,8 +122,14 @@ class HotPath:
             e0.record()
         # a tail step's reservoir launch meets a draining GPU: the layout of a lone launch (more, thinner waves)
         wpc = 0 if (tail and self.waves_per_clip == -1 and self.tail_lone_layout) else self.waves_per_clip
-        feats, _, _ = self.net.run_batch(rasters, self.feature_keys, waves_per_clip=wpc,
-                                         stats_out=stats_out, features_out=out)
+        if self.time_segments > 1:
+            K, B = self.time_segments, int(rasters.shape[0])
+            feats = self.net.run_segments(rasters, int(rasters.shape[2]) // K, self.feature_keys, waves_per_clip=wpc,
+                                          stats_out=stats_out,
+                                          features_out=out.view(B, K, -1) if out is not None else None).view(B, -1)
+        else:
+            feats, _, _ = self.net.run_batch(rasters, self.feature_keys, waves_per_clip=wpc,
+                                             stats_out=stats_out, features_out=out)
         if self.time_reservoir:
             e1.record()
             self.reservoir_events.append((e0, e1))
@@ -317,7 +328,8 @@ class HotPath:
         self.synchronize()
         if not parts:
             n_keys = len(self.feature_keys) if self.feature_keys is not None else 8
-            return torch.empty((0, n_keys * self.net.num_output_neurons), dtype=torch.float32, device=self.device)
+            return torch.empty((0, self.time_segments * n_keys * self.net.num_output_neurons), dtype=torch.float32,
+                               device=self.device)
         if out is None:
             return torch.cat(parts)
         torch.cat(parts, out=out)
@@ -325,12 +337,13 @@ class HotPath:
 
 
 def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1024,
-                        streams: int = DEFAULT_STREAMS, device_out: bool = False):
+                        streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1):
     """Host convenience for the drop-in scripts' in-memory path: (n, n_samples) float32 on the host ->
     (n, n_feat) float32 on the host (or, `device_out`, still on the GPU for a gather), batches of `batch` clips
     through the overlapped pipeline (pinned staging, uploads on the steps' streams).  n = 0 (an empty shard)
-    gives an empty (0, n_feat) block."""
-    hp = HotPath(fe, net, feature_keys, streams=streams)
+    gives an empty (0, n_feat) block.  `time_segments` = K > 1: K segment rows per clip side by side (`HotPath`), n_feat is
+    K times as wide."""
+    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments)
     pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
     if len(pinned):
         try:
@@ -361,3 +374,31 @@ def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = T
         state = net.new_state(n) if carry_state else None
         rows = [net.run_batch(rasters[:, w].contiguous(), feature_keys, state=state)[0] for w in range(W)]
         return torch.stack(rows, dim=1)
+
+
+def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps: int, window_segments: int,
+                                     hop_segments: int = 1):
+    """Features of sliding windows over a recording: ``audio`` (n, W * fe.n_samples) float32 -> (n, Wn, n_feat) float32
+    device tensor.  The front end runs on the n * W audio windows as independent clips, as in
+    ``features_from_long_audio``; the reservoir takes them one after the other with its state carried, one segmented
+    launch per audio window (``segment_steps`` divides ``fe.n_steps``), and the records of all launches, concatenated, go
+    through one ``lsm_segment_features`` call: row w is the feature row of steps
+    ``[w * hop_segments * segment_steps, (w * hop_segments + window_segments) * segment_steps)`` of the recording's one
+    uncut run -- windows may straddle the audio windows."""
+    if isinstance(audio, np.ndarray):
+        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    ns = int(fe.n_samples)
+    if audio.dim() != 2 or audio.shape[1] < ns or audio.shape[1] % ns:
+        raise ValueError(f"audio must be (n, W * {ns}), got {tuple(audio.shape)}")
+    S = int(segment_steps)
+    if S < 1 or fe.n_steps % S:
+        raise ValueError(f"segment_steps = {segment_steps} must be >= 1 and divide the front end's {fe.n_steps} steps")
+    n, W = int(audio.shape[0]), int(audio.shape[1]) // ns
+    net.segment_windows(W * (fe.n_steps // S), window_segments, hop_segments)     # refuse before anything is launched
+    with torch.cuda.device(net.device):
+        x = audio.to(net.device, dtype=torch.float32).reshape(n * W, ns).contiguous()
+        rasters = fe.encode(x).reshape(n, W, fe.n_channels, -1)
+        state = net.new_state(n)
+        records = torch.cat([net.run_segment_records(rasters[:, w].contiguous(), S, state=state)[0] for w in range(W)],
+                            dim=1)
+        return net.segment_features(records, S, feature_keys, window_segments, hop_segments)

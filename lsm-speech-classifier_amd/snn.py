@@ -121,6 +121,7 @@ class SNN:
         self._input = None
         self.spike_matrix = None
         self._features = None
+        self._max_steps = {}             # (n_clips, waves_per_clip) -> max_steps, until set_kernel changes the plans
 
     def __del__(self):
         try:
@@ -244,6 +245,12 @@ class SNN:
             _lib.check(n, "lsm_reservoir_max_steps")
         return n
 
+    def _max_steps_cached(self, n_clips: int, waves_per_clip: int = 0) -> int:
+        key = (int(n_clips), int(waves_per_clip))
+        if key not in self._max_steps:
+            self._max_steps[key] = self.max_steps(*key)
+        return self._max_steps[key]
+
     def run_chunked(self, spikes, feature_keys=None, chunk_steps: int | None = None, want_spike_matrix=False,
                     want_v_trace=False, waves_per_clip: int = 0, stats_out=None, longest_first: bool | None = None):
         """``run_batch`` for clips of any length up to 65535 steps: the run is cut into launches of ``chunk_steps`` (default:
@@ -268,6 +275,139 @@ class SNN:
             vts.append(vt)
         return (feats, torch.cat(sms, dim=1) if want_spike_matrix else None,
                 torch.cat(vts, dim=1) if want_v_trace else None)
+
+    # ---- segments and windows (SPEC.md §4b) ---------------------------------------------
+    def run_segment_records(self, spikes, segment_steps: int, feature_keys=(), want_spike_matrix=False,
+                            want_v_trace=False, waves_per_clip: int = 0, stats_out=None,
+                            longest_first: bool | None = None, state: ReservoirState | None = None,
+                            state_out: ReservoirState | None = None):
+        """One segmented launch (``lsm_reservoir_run_segments``): ``run_batch(state=...)`` whose feature bookkeeping is cut
+        every ``segment_steps`` steps.  Returns ``(records, features, spike_matrix, v_trace)``: ``records`` is the
+        (B, T // segment_steps, N_out, 4) int32 device tensor of the segments' integer records (times local to the
+        segment), the other three are ``run_batch``'s for the same launch (``features`` cumulative, ``None`` without
+        ``feature_keys``).  Without ``state`` the launch starts from ``reset()``."""
+        if isinstance(spikes, np.ndarray):
+            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
+        spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
+        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
+            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        B, _, T = spikes.shape
+        S = int(segment_steps)
+        if S < 1 or T % S != 0:
+            raise _lib.LsmHipError(f"segment_steps = {S} must be >= 1 and divide the launch's {T} steps")
+        keys = [k for k in (feature_keys or ()) if k in FEATURE_KEYS]
+        key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+        feats = (torch.empty((B, len(keys) * self.num_output_neurons), dtype=torch.float32, device=self.device)
+                 if keys else None)
+        sm = torch.empty((B, T, self.num_neurons), dtype=torch.uint8, device=self.device) if want_spike_matrix else None
+        vt = torch.empty((B, T, self.num_neurons), dtype=torch.float32, device=self.device) if want_v_trace else None
+        if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (B, 2)
+                                      or not stats_out.is_contiguous() or stats_out.device != spikes.device):
+            raise ValueError(f"stats_out must be a contiguous int32 ({B}, 2) tensor on {spikes.device}")
+        if state is not None:
+            self._check_state(state, B)
+            if state_out is not None:
+                self._check_state(state_out, B)
+        elif state_out is not None:
+            raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
+        if longest_first is None:
+            longest_first = self.longest_first_default(B)
+        records = torch.empty((B, T // S, self.num_output_neurons, 4), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
+            ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
+            _lib.check(self.lib.lsm_reservoir_run_segments(
+                self._handle, _dev(spikes), B, T, S, state.steps_done if state is not None else 0,
+                _dev(state.data) if state is not None else None,
+                _dev((state_out or state).data) if state is not None else None, _dev(records),
+                _host(key_ids) if keys else None, len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out),
+                int(waves_per_clip), _dev(ws), need, stream), "lsm_reservoir_run_segments")
+        if state is not None:
+            (state_out or state).steps_done = state.steps_done + T
+        return records, feats, sm, vt
+
+    @staticmethod
+    def segment_windows(n_segments: int, window_segments: int = 1, hop_segments: int = 1) -> int:
+        """Number of windows of ``window_segments`` segments, ``hop_segments`` apart, in ``n_segments`` segments."""
+        G, K, H = int(n_segments), int(window_segments), int(hop_segments)
+        if K < 1 or K > G or H < 1:
+            raise _lib.LsmHipError(f"window_segments = {K} must be in [1, {G}] and hop_segments = {H} >= 1")
+        return (G - K) // H + 1
+
+    def segment_features(self, records, segment_steps: int, feature_keys=None, window_segments: int = 1,
+                         hop_segments: int = 1, features_out=None):
+        """Feature rows of sliding windows over segment records (``lsm_segment_features``): ``records`` (B, G, N_out, 4)
+        int32 as ``run_segment_records`` returns them (launches concatenated along dim 1).  Returns float32
+        (B, W, n_keys*N_out); window w covers segments ``[w*hop, w*hop + window_segments)`` and its row is the feature row
+        of that slice of the spike matrix."""
+        if (records.dtype != torch.int32 or records.dim() != 4 or tuple(records.shape[2:]) != (self.num_output_neurons, 4)
+                or records.device != self.device):
+            raise ValueError(f"records must be an int32 (B, G, {self.num_output_neurons}, 4) tensor on {self.device}")
+        records = records.contiguous()
+        B, G = int(records.shape[0]), int(records.shape[1])
+        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
+        key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+        W = self.segment_windows(G, window_segments, hop_segments)
+        shape = (B, W, len(keys) * self.num_output_neurons)
+        if features_out is not None:
+            if (features_out.dtype != torch.float32 or tuple(features_out.shape) != shape
+                    or not features_out.is_contiguous() or features_out.device != self.device):
+                raise ValueError(f"features_out must be a contiguous float32 {shape} tensor on {self.device}")
+            feats = features_out
+        else:
+            feats = torch.empty(shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self.lib.lsm_segment_features(
+                self._handle, _dev(records), B, G, int(segment_steps), int(window_segments), int(hop_segments),
+                _host(key_ids), len(keys), _dev(feats), stream), "lsm_segment_features")
+        return feats
+
+    def run_segments(self, spikes, segment_steps: int, feature_keys=None, window_segments: int = 1,
+                     hop_segments: int = 1, state: ReservoirState | None = None,
+                     state_out: ReservoirState | None = None, waves_per_clip: int = 0,
+                     longest_first: bool | None = None, want_records: bool = False, features_out=None,
+                     stats_out=None):
+        """Features per time segment or sliding window: float32 (B, W, n_keys*N_out) on the device, and with
+        ``want_records`` the (B, G, N_out, 4) records tensor as well.  The reservoir runs once over the clip (from
+        ``state``, else from ``reset()``); every ``segment_steps`` steps the integer feature records are closed, and
+        window w folds those of segments ``[w*hop_segments, w*hop_segments + window_segments)``: its row is, bit for
+        bit, the feature row of that slice of the spike matrix (``window_segments=1``: one row per segment).  Clips
+        longer than ``max_steps`` are cut at segment boundaries into launches that hand their state on.  ``features_out`` /
+        ``stats_out``: as ``run_batch``'s (a contiguous (B, W, n_keys*N_out) tensor; the statistics of the run so far)."""
+        if isinstance(spikes, np.ndarray):
+            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
+        spikes = spikes.to(self.device, dtype=torch.uint8)
+        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
+            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        B, _, T = spikes.shape
+        S = int(segment_steps)
+        if S < 1 or T < 1 or T % S != 0:
+            raise _lib.LsmHipError(f"segment_steps = {S} must be >= 1 and divide the clip's {T} steps")
+        self.segment_windows(T // S, window_segments, hop_segments)      # refuse before anything is launched
+        if int(window_segments) * S > MAX_STEPS:
+            raise _lib.LsmHipError(f"a window of {window_segments} segments of {S} steps exceeds {MAX_STEPS} steps")
+        longest = self._max_steps_cached(B, waves_per_clip)
+        chunk = longest // S * S
+        if chunk < 1:
+            raise _lib.LsmHipError(f"segment_steps = {S} exceeds the longest launch the plan accepts for {B} clips "
+                                   f"({longest} steps)")
+        parts = split_steps(T, chunk)
+        if state is None and len(parts) > 1:
+            state = self.new_state(B)                                     # carried between the launches only
+            state_out = None
+        recs = []
+        for i, (t0, n) in enumerate(parts):
+            # the caller's state stays as it is when state_out is given: the first launch moves over to state_out
+            r, _, _, _ = self.run_segment_records(spikes[:, :, t0:t0 + n], S, (), False, False, waves_per_clip,
+                                                  stats_out, longest_first, state, state_out)
+            if state_out is not None:
+                state, state_out = state_out, None
+            recs.append(r)
+        records = recs[0] if len(recs) == 1 else torch.cat(recs, dim=1)
+        feats = self.segment_features(records, S, feature_keys, window_segments, hop_segments, features_out)
+        return (feats, records) if want_records else feats
 
     def longest_first_default(self, n_clips: int) -> bool:
         """Whether ``run_batch`` starts the clips of a batch of this size longest first by default."""
@@ -305,6 +445,7 @@ class SNN:
             return self._set_kernel(mode)
 
     def _set_kernel(self, mode: str = "auto"):
+        self._max_steps.clear()
         _lib.check(self.lib.lsm_reservoir_set_kernel(self._handle, self.KERNEL_MODES[mode]),
                    "lsm_reservoir_set_kernel")
 

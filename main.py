@@ -45,7 +45,7 @@ STAGES = (
      + _corpus_args(a) + (["--packed"] if a.packed else [])),
     ("Step 2: Extracting LSM Features",
      lambda a: ["extract_lsm_features.py", "--feature-set", a.feature_set, "--multiplier", str(a.multiplier)]
-     + _reservoir_args(a)),
+     + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])),
     ("Step 3: Training and Evaluating Classifier",
      lambda a: ["train_classifier.py"] + (["--readout", a.readout] if a.readout else [])
      + (["--commands", a.commands] if a.commands else [])
@@ -60,7 +60,7 @@ audio, labels = cd.collect_audio(commands=cd.commands_from_args(a), dataset_root
 ex.main_from_audio(audio, labels, a.n_filters, a.filterbank, a.feature_set, a.multiplier,
                    num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons,
                    small_world_k=a.small_world_k, seed=a.seed, readout=a.device_readout,
-                   class_names=cd.commands_from_args(a))
+                   class_names=cd.commands_from_args(a), time_segments=a.time_segments)
 """
 
 
@@ -82,12 +82,12 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     except that a PyTorch readout (`readout="torch-ridge"` / `"torch-logistic"`) runs inside that process on the
     feature rows still on the GPU and prints the final report itself (no stage 3 process, no File 2 reload).
     `extra`: the forwarded constants (commands, commands_file, dataset_root, max_per_class, synthetic_per_class,
-    packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc)."""
+    packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc, time_segments)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
                               packed=False, num_neurons=None, num_output_neurons=None, small_world_k=None, seed=None,
-                              readout=None, nproc=1)
+                              readout=None, nproc=1, time_segments=1)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -149,10 +149,12 @@ if __name__ == "__main__":
                     help="Readout of stage 3 (default: scikit-learn logistic regression, or LSM_READOUT).")
     ap.add_argument("--nproc", type=int, default=int(os.environ.get("LSM_NPROC", "1")),
                     help="Ranks (one per GPU) for stages 1 and 2.")
+    ap.add_argument("--time-segments", type=int, default=1,
+                    help="Read every clip in K equal time segments, K feature rows side by side (stage 2; default 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
                  dataset_root=a.dataset_root, max_per_class=a.max_per_class,
                  synthetic_per_class=a.synthetic_per_class, packed=a.packed, num_neurons=a.num_neurons,
                  num_output_neurons=a.num_output_neurons, small_world_k=a.small_world_k, seed=a.seed,
-                 readout=a.readout, nproc=a.nproc)
+                 readout=a.readout, nproc=a.nproc, time_segments=a.time_segments)
