@@ -305,6 +305,31 @@ int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clip
                          int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
                          void *stream);
 
+/* Ragged batches (SPEC.md §4c): lsm_reservoir_run_from whose clips run a number of steps of their own.  n_steps is the row
+ * stride of the launch -- spikes_u8 is (n_clips, C, n_steps), the spike matrix and the membrane trace (n_clips, n_steps, N) --
+ * and clip b runs L_b = clamp(clip_steps[b], 0, n_steps) steps: it is, bit for bit, lsm_reservoir_run_from over steps
+ * [first_step, first_step + L_b) of that clip alone.
+ *   clip_steps   (n_clips) int32, DEVICE memory, 4-byte aligned, or NULL: every clip runs n_steps (the call is then
+ *                lsm_reservoir_run_from).  The kernels clamp every value into [0, n_steps], so no value can address outside
+ *                the launch's buffers; the library never reads device memory to check one (as with first_step)
+ *   first_step   HOST value, one for the whole launch
+ *   features_out clip b: features of steps [0, first_step + L_b), spike_variances with T = first_step + L_b
+ *   stats_out, state_out   clip b: after step first_step + L_b - 1
+ *   spike_matrix_out, v_trace_out   clip b: rows 0 .. L_b - 1 are written, rows from L_b on are left as they are
+ *   order_workspace   as lsm_reservoir_run_from's; the clips are ranked by their input spikes at t < L_b
+ * Input bytes at t >= L_b influence nothing.  A clip with L_b = 0 is not touched: its feature row, statistics row and
+ * matrix rows keep what they held, and its state_out block receives its state_in block byte for byte (zeros when state_in
+ * is NULL; nothing happens when state_out == state_in).  A clip that ran fewer than n_steps steps has ended: later launches
+ * of the same run must give it 0 steps (the library cannot check that; SNN.run_batch(lengths=...) does).
+ * The plan and the LDS image are those of n_steps: lsm_reservoir_plan and lsm_reservoir_max_steps answer as for an unragged
+ * launch, and every refusal of lsm_reservoir_run_from applies unchanged; LSM_ERR_ARG also for a clip_steps pointer that is
+ * not 4-byte aligned.  Segments (§4b) are not offered on this entry. */
+int lsm_reservoir_run_ragged(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                             const int32_t *clip_steps, int first_step, const void *state_in, void *state_out,
+                             const int32_t *key_ids, int n_keys, float *features_out,
+                             uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                             int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream);
+
 /* Largest n_steps lsm_reservoir_plan accepts for (n_clips, waves_per_clip), at most 65535; < 0 when it accepts none. */
 int lsm_reservoir_max_steps(const lsm_reservoir *h, int n_clips, int waves_per_clip);
 

@@ -53,6 +53,8 @@ _SIGS = {
     "lsm_reservoir_state_bytes": (C.c_long, [c_void]),
     "lsm_reservoir_run_from": (c_int, [c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_int, c_void,
                                        c_void, c_void, c_void, c_int, c_void, C.c_long, c_void]),
+    "lsm_reservoir_run_ragged": (c_int, [c_void, c_void, c_int, c_int, c_void, c_int, c_void, c_void, c_void, c_int, c_void,
+                                         c_void, c_void, c_void, c_int, c_void, C.c_long, c_void]),
     "lsm_reservoir_run_segments": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_void,
                                            c_int, c_void, c_void, c_void, c_void, c_int, c_void, C.c_long, c_void]),
     "lsm_segment_features": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_void]),

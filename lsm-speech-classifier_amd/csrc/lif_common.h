@@ -33,9 +33,11 @@ __device__ __forceinline__ void zero_features_and_bits(uint4 *feat, int n_out, u
 // Prologue: bit-pack clip b of the (B, C, T) uint8 raster time-major into `bits` (T rows of CW words, zeroed before):
 // bit p of row t = channel c spikes at step t, p = inperm[c] (PERM: the coloured positions chosen by the host) or c.
 // Four steps per load when a channel's T bytes are whole dwords.
-template <int NT, bool PERM>
+// LIM (ST forms, SPEC.md §4c): only the steps t < Tb of every channel row are packed -- a dword that straddles Tb loses its
+// bytes at t >= Tb, a byte at t >= Tb is skipped -- and only the rows below Tb need to be zero.  T stays the row stride.
+template <int NT, bool PERM, bool LIM = false>
 __device__ __forceinline__ void pack_raster_bits(const uint8_t *raster, const uint8_t *inperm, int b, int C, int T, int CW,
-                                                 uint32_t *bits, int tid)
+                                                 uint32_t *bits, int tid, int Tb = 0)
 {
     const uint8_t *clip = raster + (size_t)b * C * T;
     if ((T & 3) == 0) {
@@ -46,17 +48,19 @@ __device__ __forceinline__ void pack_raster_bits(const uint8_t *raster, const ui
             if (v == 0) continue;
             const int c = (q * 4) / T;
             const int t0 = (q * 4) - c * T;
+            if (LIM && t0 >= Tb) continue;
             const int pc = PERM ? (int)inperm[c] : c;        // the channel's place in the bit row
             const uint32_t bit = 1u << (pc & 31);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if ((v >> (8 * k)) & 0xFFu) atomicOr(&bits[(t0 + k) * CW + (pc >> 5)], bit);
+                if (((v >> (8 * k)) & 0xFFu) && (!LIM || t0 + k < Tb)) atomicOr(&bits[(t0 + k) * CW + (pc >> 5)], bit);
         }
     } else {
         const int nb = C * T;
         for (int q = tid; q < nb; q += NT)
             if (clip[q]) {
                 const int c = q / T;
+                if (LIM && q - c * T >= Tb) continue;
                 const int pc = PERM ? (int)inperm[c] : c;
                 atomicOr(&bits[(q - c * T) * CW + (pc >> 5)], 1u << (pc & 31));
             }
@@ -131,7 +135,44 @@ struct StateArgs {
     int t0;                    // steps done before this launch
     int seg;                   // SPEC.md §4b: steps per segment (divides T), 0 = the launch is not segmented
     uint4 *rec;                // seg > 0: (B, T / seg, n_out) segment records
+    const int *steps;          // SPEC.md §4c: (B) steps every clip runs in this launch (clamped into [0, T]), or null: T
 };
+
+// SPEC.md §4c: the steps clip b runs in a launch of T (Tb).  b is workgroup-uniform, so this is one scalar load; T stays the
+// row stride of the raster, the spike matrix and the trace and the size of the LDS image.
+__device__ __forceinline__ int clip_step_count(const StateArgs &st, int b, int T)
+{
+    return st.steps ? min(max(st.steps[b], 0), T) : T;
+}
+
+// A clip of zero steps (SPEC.md §4c): its state block passes through -- out receives in byte for byte (zeros without in;
+// nothing when they are the same block), 16 bytes per move (the stride and both bases are multiples of 16) -- and nothing
+// else of the clip is touched.  Called before the first barrier and before any LDS write, under a workgroup-uniform test;
+// the workgroup returns behind it.
+// st_offset: offsetof(<the kernel's argument struct>, st).  The block reads StateArgs from the kernel-argument segment (the
+// argument struct is the kernel's only parameter: offset 0) through a pointer the optimiser cannot see through, NOT as
+// `a.st`: loads of a.st.in / out / stride at the top of the kernel are merged with those of the state prologue and epilogue
+// and stay live across the step loop -- lif_dense_kernel<2, 1, 0, false, true> then took 101 registers for 81 (4 waves per
+// SIMD for 5), <16, 16, 0, false, true> 100 bytes of scratch for 84 (profiles/ragged_batches.txt).
+template <int NT>
+__device__ __forceinline__ void state_pass_through(int b, int tid, size_t st_offset)
+{
+    typedef __attribute__((address_space(4))) const unsigned char *karg_t;
+    karg_t ka = (karg_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    ka += st_offset;
+    typedef const unsigned char *in_t;
+    typedef unsigned char *out_t;
+    const in_t in = *reinterpret_cast<__attribute__((address_space(4))) const in_t *>(ka + offsetof(StateArgs, in));
+    const out_t out = *reinterpret_cast<__attribute__((address_space(4))) const out_t *>(ka + offsetof(StateArgs, out));
+    const long stride = *reinterpret_cast<__attribute__((address_space(4))) const long *>(ka + offsetof(StateArgs, stride));
+    if (!out || out == in) return;
+    const size_t off = (size_t)b * stride;
+    uint4 *dst = reinterpret_cast<uint4 *>(out + off);
+    const uint4 *src = in ? reinterpret_cast<const uint4 *>(in + off) : nullptr;
+    const int n16 = (int)(stride >> 4);
+    for (int i = tid; i < n16; i += NT) dst[i] = src ? src[i] : make_uint4(0u, 0u, 0u, 0u);
+}
 
 __host__ __device__ inline int state_np(int N) { return (N + 63) & ~63; }
 __host__ __device__ inline long state_off_v() { return 16; }
@@ -257,6 +298,7 @@ __device__ __forceinline__ void segment_next(SegmentCursor *c, int seg, int n_ou
 // Epilogue, before state_finish and behind a barrier that follows the last close: the launch-wide record of every output
 // neuron is the left fold of §4a's merge over the clip's own segment records, read back from the records buffer (the
 // workgroup's own stores, ordered by that barrier) -- no second LDS record array.
+// (The kernels pass their Tb for T: a segmented launch is never ragged, so Tb == T, and T need not outlive the step loop.)
 template <int NT>
 __device__ __forceinline__ void segment_fold(const StateArgs &st, int b, int T, uint4 *feat, int n_out, int burst_isi_max, int tid)
 {

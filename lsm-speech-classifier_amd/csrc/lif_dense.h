@@ -97,6 +97,15 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;      // wave-uniform
     const int N = a.N, T = a.T, CW = a.CW;
+    // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
+    // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
+    const int Tb = ST ? clip_step_count(a.st, b, T) : T;
+    if constexpr (ST) {
+        if (Tb == 0) {
+            state_pass_through<NT>(b, tid, offsetof(DenseArgs, st));
+            return;
+        }
+    }
 
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
     // (zero_features_and_bits, pack_raster_bits and write_features of lif_common.h stay written out here: each call moves the
@@ -104,7 +113,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
     for (int i = tid; i < NPAD; i += NT) icnt[i] = 0u;
     if (tid < 64) wcnt[tid] = 0u;
     for (int i = tid; i < a.n_out; i += NT) feat[i] = make_uint4(0, 0, 0, 0);
-    for (int i = tid; i < T * CW; i += NT) bits[i] = 0u;
+    for (int i = tid; i < Tb * CW; i += NT) bits[i] = 0u;
     __syncthreads();
     {
         const uint8_t *clip = a.raster + (size_t)b * a.C * T;
@@ -116,17 +125,19 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
                 if (v == 0) continue;
                 const int c = (q * 4) / T;
                 const int t0 = (q * 4) - c * T;
+                if (ST && t0 >= Tb) continue;                       // ST: only the steps t < Tb are packed
                 const int pc = INCOL ? (int)a.inperm[c] : c;        // the channel's place in the bit row
                 const uint32_t bit = 1u << (pc & 31);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if ((v >> (8 * k)) & 0xFFu) atomicOr(&bits[(t0 + k) * CW + (pc >> 5)], bit);
+                    if (((v >> (8 * k)) & 0xFFu) && (!ST || t0 + k < Tb)) atomicOr(&bits[(t0 + k) * CW + (pc >> 5)], bit);
             }
         } else {
             const int nb = a.C * T;
             for (int q = tid; q < nb; q += NT)
                 if (clip[q]) {
                     const int c = q / T;
+                    if (ST && q - c * T >= Tb) continue;
                     const int pc = INCOL ? (int)a.inperm[c] : c;
                     atomicOr(&bits[(q - c * T) * CW + (pc >> 5)], 1u << (pc & 31));
                 }
@@ -236,7 +247,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
         }
     };
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < Tb; ++t) {
         // The step list read and the row fetch are the latency-critical part of a step: they issue at
         // raised priority so that waves of other kernels sharing the SIMD (the float64 filterbank in the
         // pipeline) do not delay the loads; the update below runs at normal priority in their stall slots.
@@ -486,15 +497,15 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
             const uint32_t rf = REFM ? (((h2[r] >> lane) & 1ull) ? 2u : (uint32_t)((h1[r] >> lane) & 1ull)) : (uint32_t)ref[REFM ? 0 : r];
             state_store_neuron(sout, scratch, NP, N, (w * SL + r) * 64 + lane, v[r], rf, (hf >> r) & 1u);
         }
-        const int lastbuf = (T - 1) & 1;
+        const int lastbuf = (Tb - 1) & 1;
         const uint16_t *list_last = wlist + lastbuf * NPAD + w * NPW;
         const int nlast = (int)wcnt[lastbuf * 16 + w];
         for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
-        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
-    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
+    const int Tf = ST ? Tb + a.st.t0 : T;           // the features are those of [0, t0 + Tb)
     if (a.stats) write_stats(a.stats, b, &wcnt[32], &wcnt[33], hf, tot_spk, lane, tid);
     const int nf = a.n_keys * a.n_out;
     for (int idx = tid; idx < nf; idx += NT) {

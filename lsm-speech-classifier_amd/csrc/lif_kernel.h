@@ -90,11 +90,20 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;      // wave-uniform
     const int N = a.N, T = a.T, CW = a.CW;
+    // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
+    // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
+    const int Tb = ST ? clip_step_count(a.st, b, T) : T;
+    if constexpr (ST) {
+        if (Tb == 0) {
+            state_pass_through<NT>(b, tid, offsetof(LifArgs, st));
+            return;
+        }
+    }
 
     // ---- prologue: zero LDS state, stage tables, bit-pack the clip's raster time-major ----
     for (int i = tid; i < NPAD; i += NT) { acc[i] = 0.0f; icnt[i] = 0u; }
     if (tid < 32) wcnt[tid] = 0u;
-    zero_features_and_bits<NT>(feat, a.n_out, bits, T * CW, tid);
+    zero_features_and_bits<NT>(feat, a.n_out, bits, Tb * CW, tid);
     if (SEGLDS) {
         for (int i = tid; i < N + 1; i += NT) lrow[i] = a.rowptr[i];
         const uint32_t *so32 = reinterpret_cast<const uint32_t *>(a.segoff);
@@ -113,16 +122,18 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
                 if (v == 0) continue;
                 const int c = (q * 4) / T;
                 const int t0 = (q * 4) - c * T;
+                if (ST && t0 >= Tb) continue;                    // ST: only the steps t < Tb are packed
                 const uint32_t bit = 1u << (c & 31);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if ((v >> (8 * k)) & 0xFFu) atomicOr(&bits[(t0 + k) * CW + (c >> 5)], bit);
+                    if (((v >> (8 * k)) & 0xFFu) && (!ST || t0 + k < Tb)) atomicOr(&bits[(t0 + k) * CW + (c >> 5)], bit);
             }
         } else {
             const int nb = a.C * T;
             for (int q = tid; q < nb; q += NT)
                 if (clip[q]) {
                     const int c = q / T;
+                    if (ST && q - c * T >= Tb) continue;
                     atomicOr(&bits[(q - c * T) * CW + (c >> 5)], 1u << (c & 31));
                 }
         }
@@ -209,7 +220,7 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         }
     };
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < Tb; ++t) {
         const int cur = t & 1;
         const uint16_t *list_prev = wlist + (cur ^ 1) * NPAD;
         uint16_t *list_cur = wlist + cur * NPAD + w * NPW;
@@ -408,15 +419,15 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
 #pragma unroll
         for (int r = 0; r < SL; ++r)
             state_store_neuron(sout, scratch, NP, N, (w * SL + r) * 64 + lane, v[r], (uint32_t)ref[r], (hf >> r) & 1u);
-        const int lastbuf = (T - 1) & 1;
+        const int lastbuf = (Tb - 1) & 1;
         const uint16_t *list_last = wlist + lastbuf * NPAD + w * NPW;
         const int nlast = (int)wcnt[lastbuf * 16 + w];
         for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
-        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
-    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
+    const int Tf = ST ? Tb + a.st.t0 : T;           // the features are those of [0, t0 + Tb)
     if (a.stats) write_stats(a.stats, b, &icnt[0], &icnt[1], hf, tot_spk, lane, tid);
     // write_features<NT> written out: with the call the one-slot forms allocate 101 registers instead of 77 (4 waves per SIMD, not 6)
     const int nf = a.n_keys * a.n_out;

@@ -206,14 +206,23 @@ void lif_pair_kernel(const PairArgs a)
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;      // wave-uniform
     const int N = a.N, T = a.T, CW = a.CW;
+    // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
+    // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
+    const int Tb = ST ? clip_step_count(a.st, b, T) : T;
+    if constexpr (ST) {
+        if (Tb == 0) {
+            state_pass_through<NT>(b, tid, offsetof(PairArgs, st));
+            return;
+        }
+    }
 #define LSM_PAIR_GB(q) ((q) * WPC + w)              // global block of my register block q
 
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
     for (int i = tid; i < (PAIR_DUMP_BYTES + NPAD * 4 + WPC * 256) / 4; i += NT) reinterpret_cast<uint32_t *>(smem)[i] = 0u;
     for (int i = tid; i < PAIR_WCNT_WORDS; i += NT) wcnt[i] = 0u;
-    zero_features_and_bits<NT>(feat, a.n_out, bits, T * CW, tid);
+    zero_features_and_bits<NT>(feat, a.n_out, bits, Tb * CW, tid);
     __syncthreads();
-    pack_raster_bits<NT, (INMASK >= 2)>(a.raster, a.inperm, b, a.C, T, CW, bits, tid);
+    pack_raster_bits<NT, (INMASK >= 2), ST>(a.raster, a.inperm, b, a.C, T, CW, bits, tid, Tb);
 
     // my neurons: register r = 2*q + h  <->  neuron GB(q)*128 + lane*2 + h
     // oref[r] = (output slot + 1) | (refractory countdown << 16), as in lif_ring.h
@@ -306,7 +315,7 @@ void lif_pair_kernel(const PairArgs a)
 #endif
 
     __builtin_amdgcn_s_setprio(1);     // wave priority of the step loop (as lif_ring.h: profiles/r04_ring_priority.txt)
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < Tb; ++t) {
         const int cur = t & 1, prv = cur ^ 1;
         const uint8_t *list_prev = wlist + prv * NPAD;
         uint8_t *list_cur = wlist + cur * NPAD;
@@ -607,7 +616,7 @@ void lif_pair_kernel(const PairArgs a)
         uint32_t *scratch = reinterpret_cast<uint32_t *>(smem + PAIR_DUMP_BYTES);
         const int NP = state_np(N);
         state_begin<NT>(scratch, NP, tid);
-        const int lastbuf = (T - 1) & 1;
+        const int lastbuf = (Tb - 1) & 1;
 #pragma unroll
         for (int q = 0; q < BL; ++q) {
             const int gb = LSM_PAIR_GB(q);
@@ -620,11 +629,11 @@ void lif_pair_kernel(const PairArgs a)
             for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, gb * 128 + (int)list_last[l]);
         }
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
-        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
 #undef LSM_PAIR_GB
-    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
+    const int Tf = ST ? Tb + a.st.t0 : T;           // the features are those of [0, t0 + Tb)
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
     if (a.stats) write_stats(a.stats, b, &wcnt[2 * PAIR_MAX_BLOCKS], &wcnt[2 * PAIR_MAX_BLOCKS + 1], hf, tot_spk, lane, tid);

@@ -147,15 +147,24 @@ void lif_ring_kernel(const RingArgs a)
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;      // wave-uniform
     const int N = a.N, T = a.T, CW = a.CW;
+    // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
+    // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
+    const int Tb = ST ? clip_step_count(a.st, b, T) : T;
+    if constexpr (ST) {
+        if (Tb == 0) {
+            state_pass_through<NT>(b, tid, offsetof(RingArgs, st));
+            return;
+        }
+    }
     // global quad of my register quad q
 #define LSM_RING_GQ(q) (STRIDED ? (q) * WPC + w : w * QL + (q))
 
     // ---- prologue: zero LDS state, bit-pack the clip's raster time-major ----
     for (int i = tid; i < RING_DUMP_WORDS + NPAD + CNT_WORDS; i += NT) reinterpret_cast<uint32_t *>(smem)[i] = 0u;
     for (int i = tid; i < 128; i += NT) wcnt[i] = 0u;
-    zero_features_and_bits<NT>(feat, a.n_out, bits, T * CW, tid);
+    zero_features_and_bits<NT>(feat, a.n_out, bits, Tb * CW, tid);
     __syncthreads();
-    pack_raster_bits<NT, INMASK == 2>(a.raster, a.inperm, b, a.C, T, CW, bits, tid);
+    pack_raster_bits<NT, INMASK == 2, ST>(a.raster, a.inperm, b, a.C, T, CW, bits, tid, Tb);
 
     // my neurons: register r = 4*q + h  <->  neuron GQ(q)*256 + lane*4 + h
     // oref[r] = (output slot + 1) | (refractory countdown << 16): one register for both, "held" is one
@@ -290,7 +299,7 @@ void lif_ring_kernel(const RingArgs a)
     // at raised wave priority so that its latency chain is not stretched by the front end's issue slots.
     // (s_setprio 1; profiles/r04_ring_priority.txt)
     __builtin_amdgcn_s_setprio(1);
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < Tb; ++t) {
         const int cur = t & 1, prv = cur ^ 1;
         const uint16_t *list_prev = wlist + prv * NPAD;
         uint16_t *list_cur = wlist + cur * NPAD;
@@ -578,7 +587,7 @@ void lif_ring_kernel(const RingArgs a)
         uint32_t *scratch = reinterpret_cast<uint32_t *>(acc + RING_DUMP_WORDS);
         const int NP = state_np(N);
         state_begin<NT>(scratch, NP, tid);
-        const int lastbuf = (T - 1) & 1;
+        const int lastbuf = (Tb - 1) & 1;
 #pragma unroll
         for (int q = 0; q < QL; ++q) {
             const int gq = LSM_RING_GQ(q);
@@ -591,11 +600,11 @@ void lif_ring_kernel(const RingArgs a)
             for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         }
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
-        if (a.st.seg > 0) segment_fold<NT>(a.st, b, T, feat, a.n_out, a.burst_isi_max, tid);
+        if (a.st.seg > 0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
 #undef LSM_RING_GQ
-    const int Tf = ST ? T + a.st.t0 : T;            // the features are those of [0, t0 + T)
+    const int Tf = ST ? Tb + a.st.t0 : T;           // the features are those of [0, t0 + Tb)
 
     // ---- epilogue: health statistics, then SPEC.md §4 features from the integer accumulators ----
     if (a.stats) write_stats(a.stats, b, &wcnt[64], &wcnt[65], hf, tot_spk, lane, tid);

@@ -1056,6 +1056,44 @@ __global__ __launch_bounds__(256) void clip_keys_kernel(const uint8_t *raster, l
     if (threadIdx.x == 0) keys[b] = (int32_t)(part[0] + part[1] + part[2] + part[3]);
 }
 
+// The same key for a ragged launch (lsm_reservoir_run_ragged, SPEC.md §4c): clip b's non-zero bytes at t < L_b of every
+// channel row, L_b = clip_steps[b] clamped into [0, n_steps] -- bytes behind a clip's length are neither read nor counted,
+// and a clip of no steps gets key 0 and starts last.  One wave per channel row at a time (rows c = wave, wave + 4, ...):
+// the row's valid prefix is read 16 bytes per lane from its first 16-byte-aligned address on, its head and tail by bytes.
+__global__ __launch_bounds__(256) void clip_keys_ragged_kernel(const uint8_t *raster, int n_channels, int n_steps,
+                                                               const int32_t *clip_steps, int n_clips, int32_t *keys)
+{
+    const int b = blockIdx.x;
+    const int len = min(max(clip_steps[b], 0), n_steps);                // workgroup-uniform
+    const uint8_t *clip = raster + (size_t)b * (size_t)n_channels * (size_t)n_steps;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t sum = 0;
+    for (int c = wave; c < n_channels; c += 4) {
+        const uint8_t *row = clip + (size_t)c * (size_t)n_steps;
+        // [0, head) and [body_end, len) by bytes, [head, body_end) in 16-byte groups
+        const int head = min(len, (int)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u));
+        const int body_end = head + ((len - head) & ~15);
+        for (int t = head + lane * 16; t < body_end; t += 64 * 16) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(row + t);
+            const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                uint32_t nz = w4[k] | (w4[k] >> 4);
+                nz |= nz >> 2; nz |= nz >> 1;
+                sum += __popc(nz & 0x01010101u);
+            }
+        }
+        if (lane < head) sum += row[lane] != 0;                          // head < 16
+        if (body_end + lane < len) sum += row[body_end + lane] != 0;     // len - body_end < 16
+    }
+    __shared__ uint32_t part[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor((int)sum, off, 64);
+    if (lane == 0) part[wave] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) keys[b] = (int32_t)(part[0] + part[1] + part[2] + part[3]);
+}
+
 constexpr int ORDER_WINDOW = 4096;      // clips ranked against each other (bounds the quadratic ranking)
 static_assert(ORDER_WINDOW % 256 == 0, "a ranking workgroup stays inside one window");
 
@@ -1138,7 +1176,14 @@ struct RunArgs {                // what one run is given, as the launch function
     // segments (lsm_reservoir_run_segments): steps per segment and the records buffer; the ST forms close the records
     int segment_steps = 0;
     void *records = nullptr;
-    bool stateful() const { return state_in != nullptr || state_out != nullptr || segment_steps > 0; }
+    // ragged launch (lsm_reservoir_run_ragged, SPEC.md §4c): device array of the steps every clip runs, or null: n_steps.
+    // The entry always takes the ST forms (`ragged`), with or without lengths.
+    const int32_t *clip_steps = nullptr;
+    bool ragged = false;
+    bool stateful() const
+    {
+        return state_in != nullptr || state_out != nullptr || segment_steps > 0 || clip_steps != nullptr || ragged;
+    }
 };
 
 // The fields LifArgs, DenseArgs, RingArgs and PairArgs have in common.
@@ -1157,6 +1202,7 @@ static void set_common_args(Args *a, const lsm_reservoir *h, const RunArgs &r)
     a->st.in = static_cast<const unsigned char *>(r.state_in); a->st.out = static_cast<unsigned char *>(r.state_out);
     a->st.stride = lsm_lif::state_bytes(h->N, h->n_out); a->st.t0 = r.first_step;
     a->st.seg = r.segment_steps; a->st.rec = static_cast<uint4 *>(r.records);
+    a->st.steps = r.clip_steps;
 }
 
 // One workgroup of wpc waves per clip, `lds` bytes of dynamic LDS.
@@ -1262,7 +1308,8 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                          uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                          int waves_per_clip, void *workspace, long workspace_bytes, void *stream,
                          int first_step = 0, const void *state_in = nullptr, void *state_out = nullptr, bool from = false,
-                         bool segmented = false, int segment_steps = 0, void *records = nullptr)
+                         bool segmented = false, int segment_steps = 0, void *records = nullptr, bool ragged = false,
+                         const int32_t *clip_steps = nullptr)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_run: null handle");
     LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
@@ -1285,6 +1332,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
     } else {
         LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
     }
+    LSM_REQUIRE((reinterpret_cast<uintptr_t>(clip_steps) & 3) == 0, "clip_steps must be 4-byte aligned");
     LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
     if (n_clips == 0) return LSM_OK;            // empty batch: nothing to read or write
     LSM_REQUIRE(spikes_u8 && (features_out || from), "null buffer");
@@ -1308,8 +1356,12 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
         if (h->cus > 0 && n_clips > h->cus) {
             int32_t *keys = static_cast<int32_t *>(workspace);
             int32_t *ord = keys + n_clips;
-            hipLaunchKernelGGL(clip_keys_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
-                               (long)h->C * n_steps, n_clips, keys);
+            if (clip_steps)         // the bytes inside every clip's own length
+                hipLaunchKernelGGL(clip_keys_ragged_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
+                                   h->C, n_steps, clip_steps, n_clips, keys);
+            else
+                hipLaunchKernelGGL(clip_keys_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
+                                   (long)h->C * n_steps, n_clips, keys);
             hipLaunchKernelGGL(clip_rank_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                                keys, n_clips, ord);
             LSM_CHECK_HIP(hipGetLastError());
@@ -1320,6 +1372,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                  stream};
     r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
     if (segmented) { r.segment_steps = segment_steps; r.records = records; }
+    r.ragged = ragged; r.clip_steps = clip_steps;
     if (plan.pv) return run_pairs(h, *plan.pv, r);
     if (plan.rv) return run_quads(h, *plan.rv, r);
     return plan.kernel == KERNEL_DENSE ? run_dense(h, *plan.v, r) : run_sparse(h, *plan.v, r);
@@ -1379,6 +1432,20 @@ int lsm_reservoir_run_segments(const lsm_reservoir *h, const uint8_t *spikes_u8,
     return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
                          stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
                          state_out, true, true, segment_steps, records_out);
+}
+
+// lsm_reservoir_run_from whose clips run clip_steps[b] (clamped into [0, n_steps]) steps each (SPEC.md §4c): the same
+// refusals, the plan and the LDS image of n_steps, always the ST forms; the kernels read the count once per workgroup.
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_run_ragged(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                             const int32_t *clip_steps, int first_step, const void *state_in, void *state_out,
+                             const int32_t *key_ids, int n_keys, float *features_out,
+                             uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                             int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
+{
+    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
+                         stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
+                         state_out, true, false, 0, nullptr, true, clip_steps);
 }
 
 // One thread per (clip, window, output neuron): §4a's merge folded over the window's records, then the neuron's n_keys

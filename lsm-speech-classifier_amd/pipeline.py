@@ -376,6 +376,45 @@ def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = T
         return torch.stack(rows, dim=1)
 
 
+def features_from_recordings(recordings, fe, net, feature_keys):
+    """Recordings of different lengths in one batch: ``recordings``, a list of n 1-D float32 arrays of ``W_r *
+    fe.n_samples`` samples each (W_r >= 1 whole windows), -> (n, n_feat) float32 device tensor.  Row r holds the features of
+    recording r's one uncut run over its ``W_r * fe.n_steps`` steps, what ``features_from_long_audio`` gives for that
+    recording alone in its last row.  The front end runs once on all windows of all recordings as independent clips (its
+    normalisation is per window, as the reference's); the rasters are scattered into (n, W_max, C, T), and the reservoir
+    takes W_max ragged launches with its state carried (``SNN.run_batch(lengths=...)``, SPEC.md §4c): in launch w a
+    recording that still has a window runs its T steps, one that has ended rides along with 0 and keeps its row."""
+    ns = int(fe.n_samples)
+    arrays, windows = [], []
+    for r, rec in enumerate(recordings):
+        a = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
+        if a.ndim != 1 or a.shape[0] < ns or a.shape[0] % ns:
+            raise ValueError(f"recording {r} must be a 1-D array of a whole number (at least 1) of windows of {ns} samples, "
+                             f"got shape {tuple(a.shape)}")
+        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
+        windows.append(a.shape[0] // ns)
+    if not arrays:
+        raise ValueError("features_from_recordings needs at least one recording")
+    n, w_max = len(arrays), max(windows)
+    windows = np.asarray(windows, dtype=np.int64)
+    with torch.cuda.device(net.device):
+        x = torch.from_numpy(np.concatenate(arrays).reshape(-1, ns)).to(net.device)
+        enc = fe.encode(x)                                              # (sum of W_r, C, T), recording-major
+        T = int(enc.shape[2])
+        rec_of = torch.from_numpy(np.repeat(np.arange(n), windows)).to(net.device)
+        win_of = torch.from_numpy(np.concatenate([np.arange(w) for w in windows])).to(net.device)
+        rasters = torch.zeros((n, w_max, fe.n_channels, T), dtype=torch.uint8, device=net.device)
+        rasters[rec_of, win_of] = enc
+        from .snn import FEATURE_KEYS
+        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
+        feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
+        state = net.new_state(n)
+        for w in range(w_max):
+            net.run_batch(rasters[:, w].contiguous(), feature_keys, features_out=feats, state=state,
+                          lengths=np.where(windows > w, T, 0))
+        return feats
+
+
 def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps: int, window_segments: int,
                                      hop_segments: int = 1):
     """Features of sliding windows over a recording: ``audio`` (n, W * fe.n_samples) float32 -> (n, Wn, n_feat) float32

@@ -24,7 +24,7 @@ FEATURE_KEYS = ['spike_counts', 'spike_variances', 'mean_spike_times', 'first_sp
 
 MAX_STEPS = 65535                    # steps of one run, launches of a continued run added up (16-bit spike times)
 
-__all__ = ["SNN", "SimulationParams", "FEATURE_KEYS", "ReservoirState", "split_steps", "MAX_STEPS"]
+__all__ = ["SNN", "SimulationParams", "FEATURE_KEYS", "ReservoirState", "split_steps", "ragged_chunks", "MAX_STEPS"]
 
 
 def split_steps(n_steps: int, max_steps: int) -> list:
@@ -36,20 +36,38 @@ def split_steps(n_steps: int, max_steps: int) -> list:
     return [(t0, min(max_steps, n_steps - t0)) for t0 in range(0, n_steps, max_steps)]
 
 
+def ragged_chunks(lengths, chunk_steps: int) -> list:
+    """Cut the runs of clips of ``lengths[b]`` steps into consecutive ragged launches of at most ``chunk_steps``
+    (SPEC.md §4c): [(first_step, n_steps, clip_steps), ...] with ``first_step = k * chunk_steps``, ``n_steps =
+    min(chunk_steps, max(lengths) - first_step)`` and ``clip_steps = clip(lengths - first_step, 0, n_steps)`` (int32), one
+    launch per ``chunk_steps`` of the longest clip -- none when every length is 0.  A clip that has ended rides along with
+    0 steps."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    chunk_steps = int(chunk_steps)
+    if chunk_steps < 1 or (lengths < 0).any():
+        raise ValueError(f"ragged_chunks: need chunk_steps >= 1 (got {chunk_steps}) and lengths >= 0")
+    longest = int(lengths.max()) if len(lengths) else 0
+    return [(t0, n, np.clip(lengths - t0, 0, n).astype(np.int32)) for t0, n in split_steps(longest, chunk_steps)]
+
+
 class ReservoirState:
     """What a reservoir carries from one launch to the next (SPEC.md §4a, ``lsm_reservoir_run_from``): ``data``, a
     (B, state_bytes) uint8 device tensor in the library's layout -- all zeros is ``reset()`` --, and ``steps_done``, the
-    host's count of the steps it holds.  ``SNN.run_batch(..., state=...)`` updates both in place."""
+    host's count of the steps it holds.  ``SNN.run_batch(..., state=...)`` updates both in place.  ``ended`` (host, (B,) bool): clip b ran fewer steps than a ragged
+    launch's ``n_steps`` (``run_batch(lengths=...)``, SPEC.md §4c) -- its run is over, later launches must give it 0 steps;
+    ``steps_done`` keeps advancing by every launch's ``n_steps`` (the one ``first_step`` of the next launch)."""
 
-    def __init__(self, data: torch.Tensor, num_neurons: int, num_output_neurons: int, steps_done: int = 0):
+    def __init__(self, data: torch.Tensor, num_neurons: int, num_output_neurons: int, steps_done: int = 0, ended=None):
         self.data = data
         self.num_neurons = int(num_neurons)
         self.num_output_neurons = int(num_output_neurons)
         self.steps_done = int(steps_done)
+        self.ended = (np.zeros(int(data.shape[0]), dtype=bool) if ended is None
+                      else np.array(ended, dtype=bool).reshape(-1))
         self._np = (self.num_neurons + 63) // 64 * 64
 
     def clone(self) -> "ReservoirState":
-        return ReservoirState(self.data.clone(), self.num_neurons, self.num_output_neurons, self.steps_done)
+        return ReservoirState(self.data.clone(), self.num_neurons, self.num_output_neurons, self.steps_done, self.ended)
 
     def _field(self, offset: int, nbytes: int, dtype) -> torch.Tensor:
         return self.data[:, offset:offset + nbytes].contiguous().view(dtype)
@@ -136,7 +154,7 @@ class SNN:
     def run_batch(self, spikes, feature_keys=None, want_spike_matrix=False, want_v_trace=False,
                   waves_per_clip: int = 0, packed_time_steps: int = 0, stats_out=None, features_out=None,
                   longest_first: bool | None = None, state: ReservoirState | None = None,
-                  state_out: ReservoirState | None = None):
+                  state_out: ReservoirState | None = None, lengths=None):
         """spikes: uint8 (B, C, T) torch tensor on this device (or NumPy, copied).  Returns
         (features float32 (B, n_keys*N_out) device tensor, spike_matrix or None, v_trace or None);
         NaN entries are already 0 and keys are concatenated in the given order
@@ -156,7 +174,14 @@ class SNN:
         ``[state.steps_done, state.steps_done + T)``, updates the state in place and returns the features of the whole run
         so far (absolute spike times); ``spike_matrix`` / ``v_trace`` cover this launch's T steps, ``stats_out`` the run so
         far.  A run cut at any step gives what the uncut run gives, bit for bit (``lsm_reservoir_run_from``).
-        ``state_out``: with ``state``, write the new state there and leave ``state`` as it is."""
+        ``state_out``: with ``state``, write the new state there and leave ``state`` as it is.
+        ``lengths``: the steps every clip runs in this launch (``lsm_reservoir_run_ragged``, SPEC.md §4c) -- a sequence, a
+        NumPy array or an int32 tensor of B values in [0, T]; T stays the row stride of ``spikes`` and of the (B, T, N)
+        outputs.  Clip b's results are those of a launch over ``spikes[b, :, :lengths[b]]`` alone; input at
+        ``t >= lengths[b]`` influences nothing, and a clip of 0 steps keeps its feature row, statistics and state.  The
+        outputs allocated here start as zeros, so rows past a clip's length read as zeros.  Host values outside [0, T]
+        raise ``ValueError`` (values of a device tensor are not read back: the kernels clamp them).  With ``state``, a
+        clip given fewer than T steps is marked ``state.ended`` and may only be given 0 steps from then on."""
         if isinstance(spikes, np.ndarray):
             spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
         spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
@@ -169,6 +194,12 @@ class SNN:
         B, _, T = spikes.shape
         keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
         key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+        ragged = lengths is not None
+        host_lengths = self._host_lengths(lengths, B, T) if ragged else None
+        if ragged and state is not None and host_lengths is not None and (host_lengths[state.ended] > 0).any():
+            raise ValueError(f"clips {np.nonzero(state.ended & (host_lengths > 0))[0].tolist()} have ended (they ran fewer "
+                             f"steps than an earlier launch's n_steps) and can only be given 0 steps")
+        alloc = torch.zeros if ragged else torch.empty          # ragged: what a clip does not write reads as zeros
         if features_out is not None:
             if (features_out.dtype != torch.float32 or tuple(features_out.shape) != (B, len(keys) * self.num_output_neurons)
                     or not features_out.is_contiguous() or features_out.device != spikes.device):
@@ -176,11 +207,10 @@ class SNN:
                                  f"tensor on {spikes.device}")
             feats = features_out
         else:
-            feats = torch.empty((B, len(keys) * self.num_output_neurons), dtype=torch.float32,
-                                device=self.device)
-        sm = (torch.empty((B, T, self.num_neurons), dtype=torch.uint8, device=self.device)
+            feats = alloc((B, len(keys) * self.num_output_neurons), dtype=torch.float32, device=self.device)
+        sm = (alloc((B, T, self.num_neurons), dtype=torch.uint8, device=self.device)
               if want_spike_matrix else None)
-        vt = (torch.empty((B, T, self.num_neurons), dtype=torch.float32, device=self.device)
+        vt = (alloc((B, T, self.num_neurons), dtype=torch.float32, device=self.device)
               if want_v_trace else None)
         if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (B, 2)
                                       or not stats_out.is_contiguous() or stats_out.device != spikes.device):
@@ -195,7 +225,24 @@ class SNN:
             raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            if state is not None:
+            if ragged:
+                if isinstance(lengths, torch.Tensor):
+                    steps = lengths.to(self.device, dtype=torch.int32).contiguous()
+                else:
+                    steps = torch.from_numpy(host_lengths.astype(np.int32)).to(self.device)
+                need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
+                ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
+                dst = (state_out or state) if state is not None else None
+                _lib.check(self.lib.lsm_reservoir_run_ragged(
+                    self._handle, _dev(spikes), B, T, _dev(steps), state.steps_done if state is not None else 0,
+                    _dev(state.data) if state is not None else None, _dev(dst.data) if dst is not None else None,
+                    _host(key_ids), len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out), int(waves_per_clip),
+                    _dev(ws), need, stream), "lsm_reservoir_run_ragged")
+                if state is not None:
+                    ended = state.ended | (host_lengths < T) if host_lengths is not None else state.ended.copy()
+                    dst.steps_done = state.steps_done + T
+                    dst.ended = ended
+            elif state is not None:
                 need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
                 ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
                 _lib.check(self.lib.lsm_reservoir_run_from(
@@ -218,6 +265,25 @@ class SNN:
                     _dev(vt), _dev(stats_out), int(waves_per_clip), stream),
                     "lsm_reservoir_run")
         return feats, sm, vt
+
+    @staticmethod
+    def _host_lengths(lengths, n_clips: int, n_steps: int):
+        """``run_batch``'s ``lengths`` as an int64 host array, checked against [0, n_steps]; ``None`` for a device tensor
+        (never read back: the kernels clamp its values)."""
+        if isinstance(lengths, torch.Tensor):
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n_clips,):
+                raise ValueError(f"lengths must hold {n_clips} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
+            if lengths.is_cuda:
+                return None
+            lengths = lengths.numpy()
+        arr = np.asarray(lengths)
+        if arr.shape != (n_clips,) or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"lengths must be {n_clips} integers, got {arr.dtype} {arr.shape}")
+        arr = arr.astype(np.int64)
+        if ((arr < 0) | (arr > n_steps)).any():
+            bad = np.nonzero((arr < 0) | (arr > n_steps))[0]
+            raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {n_steps}]")
+        return arr
 
     # ---- continuation -------------------------------------------------------------------
     def state_bytes(self) -> int:
@@ -252,10 +318,17 @@ class SNN:
         return self._max_steps[key]
 
     def run_chunked(self, spikes, feature_keys=None, chunk_steps: int | None = None, want_spike_matrix=False,
-                    want_v_trace=False, waves_per_clip: int = 0, stats_out=None, longest_first: bool | None = None):
+                    want_v_trace=False, waves_per_clip: int = 0, stats_out=None, longest_first: bool | None = None,
+                    lengths=None, want_state: bool = False):
         """``run_batch`` for clips of any length up to 65535 steps: the run is cut into launches of ``chunk_steps`` (default:
         the longest launch the plan accepts, ``max_steps``) that hand their state on.  Same returns and the same values as
-        one launch over the whole clip would give; ``spike_matrix`` / ``v_trace`` are assembled over the launches."""
+        one launch over the whole clip would give; ``spike_matrix`` / ``v_trace`` are assembled over the launches.
+        ``lengths``: host integers, the steps of every clip (SPEC.md §4c; ``ragged_chunks``): clip b's results are those of
+        the uncut run over ``spikes[b, :, :lengths[b]]`` alone.  One features and one statistics buffer serve all launches,
+        so a clip keeps the row of the launch it ended in; rows of ``spike_matrix`` / ``v_trace`` past a clip's length,
+        and everything of a clip of length 0, are zeros.
+        ``want_state``: return the ``ReservoirState`` after the last launch as a fourth value (each clip's state after its
+        own last step)."""
         if isinstance(spikes, np.ndarray):
             spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
         spikes = spikes.to(self.device, dtype=torch.uint8)
@@ -266,6 +339,9 @@ class SNN:
             raise _lib.LsmHipError(f"n_steps = {T} outside [1, {MAX_STEPS}]")
         if chunk_steps is None:
             chunk_steps = self.max_steps(B, waves_per_clip)
+        if lengths is not None:
+            return self._run_chunked_ragged(spikes, lengths, feature_keys, int(chunk_steps), want_spike_matrix, want_v_trace,
+                                            waves_per_clip, stats_out, longest_first, want_state)
         state = self.new_state(B)
         feats, sms, vts = None, [], []
         for t0, n in split_steps(T, chunk_steps):
@@ -273,8 +349,30 @@ class SNN:
                                            waves_per_clip, stats_out=stats_out, longest_first=longest_first, state=state)
             sms.append(sm)
             vts.append(vt)
-        return (feats, torch.cat(sms, dim=1) if want_spike_matrix else None,
-                torch.cat(vts, dim=1) if want_v_trace else None)
+        out = (feats, torch.cat(sms, dim=1) if want_spike_matrix else None,
+               torch.cat(vts, dim=1) if want_v_trace else None)
+        return out + (state,) if want_state else out
+
+    def _run_chunked_ragged(self, spikes, lengths, feature_keys, chunk_steps, want_spike_matrix, want_v_trace,
+                            waves_per_clip, stats_out, longest_first, want_state):
+        B, _, T = spikes.shape
+        if isinstance(lengths, torch.Tensor):
+            lengths = lengths.cpu().numpy()
+        lengths = self._host_lengths(lengths, B, T)
+        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
+        feats = torch.zeros((B, len(keys) * self.num_output_neurons), dtype=torch.float32, device=self.device)
+        sm = torch.zeros((B, T, self.num_neurons), dtype=torch.uint8, device=self.device) if want_spike_matrix else None
+        vt = torch.zeros((B, T, self.num_neurons), dtype=torch.float32, device=self.device) if want_v_trace else None
+        state = self.new_state(B)
+        for t0, n, steps in ragged_chunks(lengths, chunk_steps):
+            _, sm_k, vt_k = self.run_batch(spikes[:, :, t0:t0 + n], feature_keys, want_spike_matrix, want_v_trace,
+                                           waves_per_clip, stats_out=stats_out, features_out=feats,
+                                           longest_first=longest_first, state=state, lengths=steps)
+            if want_spike_matrix:
+                sm[:, t0:t0 + n] = sm_k
+            if want_v_trace:
+                vt[:, t0:t0 + n] = vt_k
+        return (feats, sm, vt, state) if want_state else (feats, sm, vt)
 
     # ---- segments and windows (SPEC.md §4b) ---------------------------------------------
     def run_segment_records(self, spikes, segment_steps: int, feature_keys=(), want_spike_matrix=False,
