@@ -73,6 +73,15 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
+# include/lsm_hip_streams.h (SPEC.md §4d): bound beside the table above, which stays the mirror of include/lsm_hip.h
+STREAM_SIGS = {
+    "lsm_reservoir_run_stream": (c_int, [c_void, c_void, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void,
+                                         c_void, c_void, c_int, c_void, C.c_long, c_void]),
+    "lsm_segment_features_ragged": (c_int, [c_void, c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_void, c_int,
+                                            c_void, c_void]),
+}
+STREAM_SYMBOLS = tuple(STREAM_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -120,7 +129,7 @@ def load():
         raise LsmHipError(
             f"{path} was built from other sources than this tree's (build id {_build.built_id(path)}, sources "
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(STREAM_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,7 @@ SOURCES = ["lsm_api.hip", "frontend.hip", "mel.hip", "reservoir.hip", "lif_varia
            "lif_pair_1.hip", "lif_pair_2.hip", "lif_pair_3.hip", "lif_pair_4.hip",
            "lif_pair_wide_1.hip", "lif_pair_wide_2.hip", "lif_pair_wide_3.hip", "lif_pair_wide_4.hip"]
 HEADERS = ["lsm_common.h", "lif_common.h", "lif_kernel.h", "lif_dense.h", "lif_ring.h", "lif_pair.h", "spikes_body.h"]
+PUBLIC_HEADERS = ["lsm_hip.h", "lsm_hip_streams.h"]        # include/: the C ABI
 LIB_NAME = "liblsm_hip.so"
 # -ffp-contract=off: the kernels must round every float operation exactly like the CPU oracle.
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
@@ -41,13 +42,15 @@ def version_number() -> int:
     return a * 10000 + b * 100 + c
 
 
-def source_id() -> str:
-    """Identity of what a build of this tree compiles: every source and header under csrc/, include/lsm_hip.h, the
-    compiler flags and the version, hashed.  build() links it into the library (lsm_build_id()); _lib.load() refuses a
+def source_id(include_dir: str | None = None) -> str:
+    """Identity of what a build of this tree compiles: every source and header under csrc/, the public headers of include/
+    (``include_dir``: read them from another directory), the compiler flags and the version, hashed.  build() links it into the library (lsm_build_id()); _lib.load() refuses a
     library that carries another one, and needs_build() compares it instead of trusting file times -- a stale binary
     that merely looks newer than the sources cannot pass for a build of them (VERDICT r4 weak #9)."""
     h = hashlib.sha256()
-    files = sorted(os.path.join(PKG_DIR, "csrc", f) for f in SOURCES + HEADERS) + [os.path.join(ROOT, "include", "lsm_hip.h")]
+    include_dir = include_dir or os.path.join(ROOT, "include")
+    files = sorted(os.path.join(PKG_DIR, "csrc", f) for f in SOURCES + HEADERS) + [os.path.join(include_dir, f)
+                                                                                  for f in PUBLIC_HEADERS]
     for path in files:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:

@@ -136,13 +136,52 @@ struct StateArgs {
     int seg;                   // SPEC.md §4b: steps per segment (divides T), 0 = the launch is not segmented
     uint4 *rec;                // seg > 0: (B, T / seg, n_out) segment records
     const int *steps;          // SPEC.md §4c: (B) steps every clip runs in this launch (clamped into [0, T]), or null: T
+    // SPEC.md §4d, stream launch (seg > 0): t0 is STREAM_T0 -- no cumulative record is kept, the feat block of `in` is not
+    // read and that of `out` is written as zeros --, and `steps` counts whole segments: clip b runs
+    // clamp(steps[b], 0, count_limit) * count_steps steps.  Every other launch: count_limit = T, count_steps = 1.
+    int count_limit, count_steps;
 };
+constexpr int STREAM_T0 = -1;          // StateArgs::t0 of a stream launch: it has no position (every real first step is >= 0)
+
+// count_limit and count_steps of the launch, read from the kernel-argument segment through a pointer the optimiser cannot see
+// through (st_offset: offsetof(<the kernel's argument struct>, st), as state_pass_through below): scalar loads of the
+// prologue that are not merged with the other loads of a.st and do not stay live across the step loop.
+__device__ __forceinline__ int2 state_count_scale(size_t st_offset)
+{
+    typedef __attribute__((address_space(4))) const unsigned char *karg_t;
+    karg_t ka = (karg_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    ka += st_offset;
+    return make_int2(*reinterpret_cast<__attribute__((address_space(4))) const int *>(ka + offsetof(StateArgs, count_limit)),
+                     *reinterpret_cast<__attribute__((address_space(4))) const int *>(ka + offsetof(StateArgs, count_steps)));
+}
 
 // SPEC.md §4c: the steps clip b runs in a launch of T (Tb).  b is workgroup-uniform, so this is one scalar load; T stays the
 // row stride of the raster, the spike matrix and the trace and the size of the LDS image.
-__device__ __forceinline__ int clip_step_count(const StateArgs &st, int b, int T)
+// Stream launch (SPEC.md §4d): the count is in whole segments, clamped into [0, T / seg]; Tb is a multiple of seg, so the
+// clip's last step closes its last record and no clip ends inside a segment.
+// The same value in two forms, because the ST kernels' register allocation follows the form (profiles/stream_segments.txt:
+// with either form alone some kernels gain scratch or lose a wave per SIMD, with each kernel on its form none does):
+//   clip_step_count           the §4c count, then min(., count_limit) * count_steps, the two scale fields read apart from a.st
+//                             (lif_ring.h, lif_pair.h, lif_dense.h but for INMODE 1);
+//   clip_step_count_unscaled  the §4c count alone, and behind the zero-step exit stream_step_scale: a count n > 0 of whole
+//                             segments becomes min(n * seg, T) steps (lif_kernel.h, lif_dense.h with INMODE 1).  n <= T <=
+//                             65535 and seg <= 65535, so the product stays below 2^32: the compare is unsigned.
+__device__ __forceinline__ int clip_step_count_unscaled(const StateArgs &st, int b, int T)
 {
     return st.steps ? min(max(st.steps[b], 0), T) : T;
+}
+
+__device__ __forceinline__ int clip_step_count(const StateArgs &st, int b, int T, size_t st_offset)
+{
+    const int n = clip_step_count_unscaled(st, b, T);
+    const int2 scale = state_count_scale(st_offset);         // {T, 1}, stream launch {T / seg, seg}
+    return min(n, scale.x) * scale.y;
+}
+
+__device__ __forceinline__ int stream_step_scale(const StateArgs &st, int n, int T)
+{
+    return st.t0 == STREAM_T0 ? (int)min((uint32_t)n * (uint32_t)st.seg, (uint32_t)T) : n;
 }
 
 // A clip of zero steps (SPEC.md §4c): its state block passes through -- out receives in byte for byte (zeros without in;
@@ -298,7 +337,9 @@ __device__ __forceinline__ void segment_next(SegmentCursor *c, int seg, int n_ou
 // Epilogue, before state_finish and behind a barrier that follows the last close: the launch-wide record of every output
 // neuron is the left fold of §4a's merge over the clip's own segment records, read back from the records buffer (the
 // workgroup's own stores, ordered by that barrier) -- no second LDS record array.
-// (The kernels pass their Tb for T: a segmented launch is never ragged, so Tb == T, and T need not outlive the step loop.)
+// (The kernels pass their Tb for T: a segmented launch that keeps a cumulative record is never ragged, so Tb == T, and T
+// need not outlive the step loop.  The ragged segmented launch is the stream launch of SPEC.md §4d, which keeps no cumulative
+// record and skips this fold: nothing reads its records back.)
 template <int NT>
 __device__ __forceinline__ void segment_fold(const StateArgs &st, int b, int T, uint4 *feat, int n_out, int burst_isi_max, int tid)
 {
@@ -316,6 +357,8 @@ __device__ __forceinline__ void segment_fold(const StateArgs &st, int b, int T, 
 // bit fields and the header, merges the feature records (LDS `feat` holds this launch's on entry and the whole run's on
 // return, as does the state).  Contains barriers; `in` and `out` may be the same block: every word is read before it is
 // written, by the same thread.
+// Stream launch (t0 == STREAM_T0, SPEC.md §4d): no cumulative record exists -- nothing is merged, the feat block of `sin` is
+// not read, and that of `sout` (and LDS `feat`, which nobody reads: the launch has no feature keys) receives zeros.
 __device__ __forceinline__ void state_add_total(uint32_t *scratch, int NP, uint32_t tot_spk) { atomicAdd(&scratch[NP / 16], tot_spk); }
 
 template <int NT>
@@ -330,7 +373,8 @@ __device__ __forceinline__ void state_finish(const unsigned char *sin, unsigned 
     }
     for (int o = tid; o < n_out; o += NT) {
         uint4 f = feat[o];
-        if (sin) f = merge_feature_records(reinterpret_cast<const uint4 *>(sin + state_off_feat(NP))[o], f, t0, burst_isi_max);
+        if ((int)t0 == STREAM_T0) f = make_uint4(0u, 0u, 0u, 0u);
+        else if (sin) f = merge_feature_records(reinterpret_cast<const uint4 *>(sin + state_off_feat(NP))[o], f, t0, burst_isi_max);
         feat[o] = f;
         if (sout) reinterpret_cast<uint4 *>(sout + state_off_feat(NP))[o] = f;
     }

@@ -92,12 +92,13 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
     const int N = a.N, T = a.T, CW = a.CW;
     // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
     // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
-    const int Tb = ST ? clip_step_count(a.st, b, T) : T;
+    int Tb = ST ? clip_step_count_unscaled(a.st, b, T) : T;
     if constexpr (ST) {
         if (Tb == 0) {
             state_pass_through<NT>(b, tid, offsetof(LifArgs, st));
             return;
         }
+        Tb = stream_step_scale(a.st, Tb, T);        // a stream launch counts whole segments (lif_common.h on the two forms)
     }
 
     // ---- prologue: zero LDS state, stage tables, bit-pack the clip's raster time-major ----
@@ -424,7 +425,8 @@ __global__ __launch_bounds__(WPC * 64) void lif_kernel(const LifArgs a)
         const int nlast = (int)wcnt[lastbuf * 16 + w];
         for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
-        if (a.st.seg > 0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
+        // (a stream launch, SPEC.md §4d, keeps no cumulative record: no fold, and state_finish does not merge)
+        if (a.st.seg > 0 && a.st.t0 != STREAM_T0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
     const int Tf = ST ? Tb + a.st.t0 : T;           // the features are those of [0, t0 + Tb)

@@ -149,7 +149,7 @@ void lif_ring_kernel(const RingArgs a)
     const int N = a.N, T = a.T, CW = a.CW;
     // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
     // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
-    const int Tb = ST ? clip_step_count(a.st, b, T) : T;
+    const int Tb = ST ? clip_step_count(a.st, b, T, offsetof(RingArgs, st)) : T;
     if constexpr (ST) {
         if (Tb == 0) {
             state_pass_through<NT>(b, tid, offsetof(RingArgs, st));
@@ -600,7 +600,8 @@ void lif_ring_kernel(const RingArgs a)
             for (int l = lane; l < nlast; l += 64) state_mark_last(scratch, list_last[l]);
         }
         if (lane == 0) state_add_total(scratch, NP, tot_spk);
-        if (a.st.seg > 0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
+        // (a stream launch, SPEC.md §4d, keeps no cumulative record: no fold, and state_finish does not merge)
+        if (a.st.seg > 0 && a.st.t0 != STREAM_T0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
 #undef LSM_RING_GQ

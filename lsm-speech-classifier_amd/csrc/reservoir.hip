@@ -1060,11 +1060,14 @@ __global__ __launch_bounds__(256) void clip_keys_kernel(const uint8_t *raster, l
 // channel row, L_b = clip_steps[b] clamped into [0, n_steps] -- bytes behind a clip's length are neither read nor counted,
 // and a clip of no steps gets key 0 and starts last.  One wave per channel row at a time (rows c = wave, wave + 4, ...):
 // the row's valid prefix is read 16 bytes per lane from its first 16-byte-aligned address on, its head and tail by bytes.
+// seg > 0 (stream launch, SPEC.md §4d): clip_steps counts whole segments of seg steps, L_b = clamp(clip_steps[b], 0,
+// n_steps / seg) * seg -- the same arithmetic as clip_step_count (lif_common.h).
 __global__ __launch_bounds__(256) void clip_keys_ragged_kernel(const uint8_t *raster, int n_channels, int n_steps,
-                                                               const int32_t *clip_steps, int n_clips, int32_t *keys)
+                                                               const int32_t *clip_steps, int n_clips, int32_t *keys, int seg)
 {
     const int b = blockIdx.x;
-    const int len = min(max(clip_steps[b], 0), n_steps);                // workgroup-uniform
+    const int len = seg > 0 ? min(max(clip_steps[b], 0), n_steps / seg) * seg
+                            : min(max(clip_steps[b], 0), n_steps);      // workgroup-uniform
     const uint8_t *clip = raster + (size_t)b * (size_t)n_channels * (size_t)n_steps;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t sum = 0;
@@ -1180,6 +1183,8 @@ struct RunArgs {                // what one run is given, as the launch function
     // The entry always takes the ST forms (`ragged`), with or without lengths.
     const int32_t *clip_steps = nullptr;
     bool ragged = false;
+    // stream launch (lsm_reservoir_run_stream, SPEC.md §4d): segmented, clip_steps counts whole segments, no cumulative record
+    bool streamed = false;
     bool stateful() const
     {
         return state_in != nullptr || state_out != nullptr || segment_steps > 0 || clip_steps != nullptr || ragged;
@@ -1200,9 +1205,10 @@ static void set_common_args(Args *a, const lsm_reservoir *h, const RunArgs &r)
     a->features = r.features; a->spike_matrix = r.spike_matrix; a->v_trace = r.v_trace;
     a->stats = r.stats; a->order = r.order;
     a->st.in = static_cast<const unsigned char *>(r.state_in); a->st.out = static_cast<unsigned char *>(r.state_out);
-    a->st.stride = lsm_lif::state_bytes(h->N, h->n_out); a->st.t0 = r.first_step;
+    a->st.stride = lsm_lif::state_bytes(h->N, h->n_out); a->st.t0 = r.streamed ? lsm_lif::STREAM_T0 : r.first_step;
     a->st.seg = r.segment_steps; a->st.rec = static_cast<uint4 *>(r.records);
-    a->st.steps = r.clip_steps;
+    a->st.steps = r.clip_steps; a->st.count_limit = r.streamed ? r.n_steps / r.segment_steps : r.n_steps;
+    a->st.count_steps = r.streamed ? r.segment_steps : 1;
 }
 
 // One workgroup of wpc waves per clip, `lds` bytes of dynamic LDS.
@@ -1309,7 +1315,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                          int waves_per_clip, void *workspace, long workspace_bytes, void *stream,
                          int first_step = 0, const void *state_in = nullptr, void *state_out = nullptr, bool from = false,
                          bool segmented = false, int segment_steps = 0, void *records = nullptr, bool ragged = false,
-                         const int32_t *clip_steps = nullptr)
+                         const int32_t *clip_steps = nullptr, bool streamed = false)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_run: null handle");
     LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
@@ -1332,7 +1338,8 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
     } else {
         LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
     }
-    LSM_REQUIRE((reinterpret_cast<uintptr_t>(clip_steps) & 3) == 0, "clip_steps must be 4-byte aligned");
+    LSM_REQUIRE((reinterpret_cast<uintptr_t>(clip_steps) & 3) == 0, "%s must be 4-byte aligned",
+                streamed ? "clip_segments" : "clip_steps");
     LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
     if (n_clips == 0) return LSM_OK;            // empty batch: nothing to read or write
     LSM_REQUIRE(spikes_u8 && (features_out || from), "null buffer");
@@ -1358,7 +1365,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
             int32_t *ord = keys + n_clips;
             if (clip_steps)         // the bytes inside every clip's own length
                 hipLaunchKernelGGL(clip_keys_ragged_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
-                                   h->C, n_steps, clip_steps, n_clips, keys);
+                                   h->C, n_steps, clip_steps, n_clips, keys, streamed ? segment_steps : 0);
             else
                 hipLaunchKernelGGL(clip_keys_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
                                    (long)h->C * n_steps, n_clips, keys);
@@ -1372,7 +1379,7 @@ static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n
                  stream};
     r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
     if (segmented) { r.segment_steps = segment_steps; r.records = records; }
-    r.ragged = ragged; r.clip_steps = clip_steps;
+    r.ragged = ragged; r.clip_steps = clip_steps; r.streamed = streamed;
     if (plan.pv) return run_pairs(h, *plan.pv, r);
     if (plan.rv) return run_quads(h, *plan.rv, r);
     return plan.kernel == KERNEL_DENSE ? run_dense(h, *plan.v, r) : run_sparse(h, *plan.v, r);
@@ -1455,17 +1462,12 @@ struct SegmentFeatureArgs {
     float *features;           // (B, W, n_keys * n_out)
     int B, G, S, K, H, W, n_out, n_keys, burst_isi_max;
     int key_ids[8];
+    const int32_t *valid;      // lsm_segment_features_ragged (SPEC.md §4d): (B) valid segments of every clip, clamped into [0, G]
 };
 
-__global__ __launch_bounds__(256) void segment_features_kernel(const SegmentFeatureArgs a)
+// The row of window wdw of clip b for output neuron o (bw = b * W + wdw): both kernels below.
+__device__ __forceinline__ void segment_window_row(const SegmentFeatureArgs &a, int b, int wdw, long bw, int o)
 {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    const long total = (long)a.B * a.W * a.n_out;
-    if (idx >= total) return;
-    const int o = (int)(idx % a.n_out);
-    const long bw = idx / a.n_out;
-    const int wdw = (int)(bw % a.W);
-    const int b = (int)(bw / a.W);
     const uint4 *rec = a.rec + ((size_t)b * a.G + (size_t)wdw * a.H) * a.n_out + o;
     uint4 f = make_uint4(0, 0, 0, 0);
     for (int j = 0; j < a.K; ++j)
@@ -1477,10 +1479,35 @@ __global__ __launch_bounds__(256) void segment_features_kernel(const SegmentFeat
         row[(size_t)k * a.n_out] = lsm_lif::feature_value(a.key_ids[k], n, bursts, first, last, f.z, f.w, a.K * a.S);
 }
 
-extern "C" __attribute__((visibility("default")))
-int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clips, int n_segments, int segment_steps,
-                         int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
-                         void *stream)
+__global__ __launch_bounds__(256) void segment_features_kernel(const SegmentFeatureArgs a)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.B * a.W * a.n_out;
+    if (idx >= total) return;
+    const int o = (int)(idx % a.n_out);
+    const long bw = idx / a.n_out;
+    segment_window_row(a, (int)(bw / a.W), (int)(bw % a.W), bw, o);
+}
+
+// The same over records of which clip b has Gv_b = clamp(valid[b], 0, G) (SPEC.md §4d): a thread whose window is not
+// complete -- wdw * H + K > Gv_b -- returns without storing, so rows at w >= W_b keep what they held.
+__global__ __launch_bounds__(256) void segment_features_ragged_kernel(const SegmentFeatureArgs a)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)a.B * a.W * a.n_out;
+    if (idx >= total) return;
+    const int o = (int)(idx % a.n_out);
+    const long bw = idx / a.n_out;
+    const int wdw = (int)(bw % a.W);
+    const int b = (int)(bw / a.W);
+    const int gv = min(max(a.valid[b], 0), a.G);
+    if ((long)wdw * a.H + a.K > gv) return;
+    segment_window_row(a, b, wdw, bw, o);
+}
+
+static int segment_features(const lsm_reservoir *h, const void *records, int n_clips, int n_segments, int segment_steps,
+                            int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
+                            void *stream, bool ragged, const int32_t *clip_segments)
 {
     LSM_REQUIRE(h != nullptr, "lsm_segment_features: null handle");
     LSM_REQUIRE(n_clips >= 0 && n_segments >= 1, "bad n_clips/n_segments");
@@ -1494,8 +1521,10 @@ int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clip
     for (int k = 0; k < n_keys; ++k)
         LSM_REQUIRE(key_ids[k] >= 0 && key_ids[k] < 8, "key id %d out of range", key_ids[k]);
     LSM_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "records must be 16-byte aligned");
+    LSM_REQUIRE((reinterpret_cast<uintptr_t>(clip_segments) & 3) == 0, "clip_segments must be 4-byte aligned");
     if (n_clips == 0) return LSM_OK;
     LSM_REQUIRE(records && features_out, "null buffer");
+    LSM_REQUIRE(!ragged || clip_segments, "null clip_segments");
     int dev_now = -1;
     LSM_CHECK_HIP(hipGetDevice(&dev_now));
     LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d",
@@ -1506,12 +1535,48 @@ int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clip
     a.W = (n_segments - window_segments) / hop_segments + 1;
     a.n_out = h->n_out; a.n_keys = n_keys; a.burst_isi_max = h->burst_isi_max;
     for (int k = 0; k < 8; ++k) a.key_ids[k] = k < n_keys ? key_ids[k] : 0;
+    a.valid = clip_segments;
     const long total = (long)a.B * a.W * a.n_out;
     LSM_REQUIRE((total + 255) / 256 <= 0x7FFFFFFFL, "too many (clip, window, output neuron) triples: %ld", total);
     if (total == 0) return LSM_OK;
-    hipLaunchKernelGGL(segment_features_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ragged ? segment_features_ragged_kernel : segment_features_kernel, dim3((unsigned)((total + 255) / 256)),
+                       dim3(256), 0, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
+}
+
+extern "C" __attribute__((visibility("default")))
+int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clips, int n_segments, int segment_steps,
+                         int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
+                         void *stream)
+{
+    return segment_features(h, records, n_clips, n_segments, segment_steps, window_segments, hop_segments, key_ids, n_keys,
+                            features_out, stream, false, nullptr);
+}
+
+// ---- streams (SPEC.md §4d, include/lsm_hip_streams.h) --------------------------------------------------------------------
+// lsm_reservoir_run_segments whose clips run clip_segments[b] whole segments each and which keeps no cumulative record: no
+// first_step (nothing in the launch depends on a clip's position on its own timeline), no features, the feat block of
+// state_in is not read and that of state_out is written as zeros.  Always the ST forms.
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_run_stream(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
+                             int segment_steps, const int32_t *clip_segments, const void *state_in, void *state_out,
+                             void *records_out, uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
+                             int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
+{
+    return reservoir_run(h, spikes_u8, n_clips, n_steps, nullptr, 0, nullptr, spike_matrix_out, v_trace_out, stats_out,
+                         waves_per_clip, order_workspace, order_workspace_bytes, stream, 0, state_in, state_out, true, true,
+                         segment_steps, records_out, true, clip_segments, true);
+}
+
+// lsm_segment_features over records of which every clip has a valid count of its own.
+extern "C" __attribute__((visibility("default")))
+int lsm_segment_features_ragged(const lsm_reservoir *h, const void *records, int n_clips, int n_segments,
+                                const int32_t *clip_segments, int segment_steps, int window_segments, int hop_segments,
+                                const int32_t *key_ids, int n_keys, float *features_out, void *stream)
+{
+    return segment_features(h, records, n_clips, n_segments, segment_steps, window_segments, hop_segments, key_ids, n_keys,
+                            features_out, stream, true, clip_segments);
 }
 
 // Largest n_steps make_plan accepts for this batch and waves_per_clip: every layout's LDS image grows with the steps, so

@@ -441,3 +441,156 @@ def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps
         records = torch.cat([net.run_segment_records(rasters[:, w].contiguous(), S, state=state)[0] for w in range(W)],
                             dim=1)
         return net.segment_features(records, S, feature_keys, window_segments, hop_segments)
+
+
+# ---- open-ended streams (SPEC.md §4d) -------------------------------------------------------------------------------------
+def stream_window_plan(seen, new, window_segments: int, hop_segments: int = 1):
+    """The bookkeeping of one push into a stream, host integers only.  Window w of a stream covers its segments
+    ``[w * H, w * H + K)`` counted from the stream's start, and is complete once the stream has seen ``w * H + K`` segments.
+    A stream that had seen ``seen`` segments and receives ``new`` more completes ``n_windows`` windows and must keep its last
+    ``keep`` records for the windows still open: those from the start of the next window on, at most ``K - 1`` of them
+    (``H <= K`` is required: with a larger hop whole segments would be skipped, not kept).  Scalars or arrays of equal
+    shape; returns ``(n_windows, keep)`` as ints or int64 arrays."""
+    K, H = int(window_segments), int(hop_segments)
+    if K < 1 or H < 1 or H > K:
+        raise ValueError(f"window_segments = {K} must be >= 1 and hop_segments = {H} in [1, {K}]")
+    seen_a, new_a = np.asarray(seen, dtype=np.int64), np.asarray(new, dtype=np.int64)
+    if (seen_a < 0).any() or (new_a < 0).any():
+        raise ValueError("stream_window_plan: seen and new must be >= 0")
+
+    def complete(n):
+        return np.where(n >= K, (n - K) // H + 1, 0)
+
+    total = seen_a + new_a
+    n_windows = complete(total) - complete(seen_a)
+    keep = total - complete(total) * H              # 0 <= keep <= K - 1 for H <= K
+    if np.ndim(seen) == 0 and np.ndim(new) == 0:
+        return int(n_windows), int(keep)
+    return n_windows, keep
+
+
+class StreamBank:
+    """``n_streams`` open-ended streams served by one reservoir: every ``push`` takes whatever whole segments each stream
+    has delivered since the last one -- any number, 0 included, the streams anywhere on their own timelines -- through one
+    ragged stream launch (``SNN.run_stream_records``) and returns the sliding-window feature rows the push completed.
+    Window w of a stream covers its segments ``[w * hop_segments, w * hop_segments + window_segments)``, counted from the
+    stream's start or last ``reset``; its row is the feature row of that slice of the stream's one uncut run.  The bank holds
+    the reservoir state, per stream the trailing records still needed (at most ``window_segments - 1``) and a host count of
+    the segments seen; a stream has no length limit."""
+
+    def __init__(self, net, n_streams: int, segment_steps: int, window_segments: int, hop_segments: int = 1,
+                 feature_keys=None):
+        self.net = net
+        self.n_streams = int(n_streams)
+        self.S, self.K, self.H = int(segment_steps), int(window_segments), int(hop_segments)
+        if self.n_streams < 1 or self.S < 1:
+            raise ValueError(f"StreamBank needs n_streams >= 1 and segment_steps >= 1, got {n_streams}, {segment_steps}")
+        stream_window_plan(0, 0, self.K, self.H)                         # H <= K
+        if self.K * self.S > 65535:
+            raise ValueError(f"a window of {self.K} segments of {self.S} steps exceeds 65535 steps")
+        self.feature_keys = feature_keys
+        self.state = net.new_state(self.n_streams)
+        self.seen = np.zeros(self.n_streams, dtype=np.int64)             # segments since the stream's start
+        self.tail_count = np.zeros(self.n_streams, dtype=np.int64)       # records kept in `tail`, left-aligned
+        self.tail = torch.zeros((self.n_streams, self.K - 1, net.num_output_neurons, 4), dtype=torch.int32,
+                                device=net.device)
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: state block, tail and count back to zero."""
+        slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
+        if ((slots < 0) | (slots >= self.n_streams)).any():
+            raise ValueError(f"slots {slots.tolist()} outside [0, {self.n_streams})")
+        idx = torch.from_numpy(slots).to(self.net.device)
+        self.state.data[idx] = 0
+        self.tail[idx] = 0
+        self.seen[slots] = 0
+        self.tail_count[slots] = 0
+
+    def push(self, rasters, segments):
+        """``rasters`` (n_streams, C, G * S) uint8: stream b's new steps are the first ``segments[b] * S`` columns of its
+        row; ``segments``: n_streams host integers in [0, G].  Returns ``(rows, counts)``: ``rows`` float32
+        (n_streams, W, n_feat) on the device and ``counts`` (int64, host) -- ``rows[b, j]`` for ``j < counts[b]`` are the
+        windows of stream b this push completed, in order; rows past a count are zeros.  A push longer than the longest
+        launch the plan accepts is cut at segment boundaries."""
+        net, S, K, H = self.net, self.S, self.K, self.H
+        if isinstance(rasters, np.ndarray):
+            rasters = torch.from_numpy(np.ascontiguousarray(rasters, dtype=np.uint8))
+        if rasters.dim() != 3 or rasters.shape[0] != self.n_streams or rasters.shape[2] % S:
+            raise ValueError(f"rasters must be ({self.n_streams}, C, G * {S}), got {tuple(rasters.shape)}")
+        Gp = int(rasters.shape[2]) // S
+        new = net._host_segments(np.asarray(segments), self.n_streams, Gp)
+        counts, keep = stream_window_plan(self.seen, new, K, H)
+        from .snn import FEATURE_KEYS, ragged_chunks
+        keys = FEATURE_KEYS if self.feature_keys is None else [k for k in self.feature_keys if k in FEATURE_KEYS]
+        n_feat = len(keys) * net.num_output_neurons
+        if Gp == 0 or int(new.max()) == 0:
+            return torch.zeros((self.n_streams, 0, n_feat), dtype=torch.float32, device=net.device), counts
+        chunk = net._max_steps_cached(self.n_streams) // S * S
+        if chunk < 1:
+            raise ValueError(f"segment_steps = {S} exceeds the longest launch the plan accepts for {self.n_streams} streams")
+        with torch.cuda.device(net.device):
+            rasters = rasters.to(net.device, dtype=torch.uint8)
+            fresh = torch.zeros((self.n_streams, Gp, net.num_output_neurons, 4), dtype=torch.int32, device=net.device)
+            for t0, n, steps in ragged_chunks(new * S, chunk):
+                rec, _, _ = net.run_stream_records(rasters[:, :, t0:t0 + n], S, segments=steps // S, state=self.state)
+                fresh[:, t0 // S:(t0 + n) // S] = rec
+            # per stream: its kept records, then the new ones, contiguous from column 0 (the start of its next window)
+            have = self.tail_count + new
+            both = torch.cat([self.tail, fresh], dim=1)
+            j = np.arange(K - 1 + Gp, dtype=np.int64)[None, :]
+            src = np.where(j < self.tail_count[:, None], j, np.minimum(K - 1 + j - self.tail_count[:, None], K - 2 + Gp))
+            rows_of = torch.arange(self.n_streams, device=net.device)[:, None]
+            joined = both[rows_of, torch.from_numpy(src).to(net.device)].contiguous()
+            rows = net.segment_features(joined, S, self.feature_keys, K, H, segments=have)
+            if K > 1:
+                jk = np.arange(K - 1, dtype=np.int64)[None, :]
+                src = np.clip(have[:, None] - keep[:, None] + jk, 0, K - 2 + Gp)
+                kept = joined[rows_of, torch.from_numpy(src).to(net.device)]
+                live = torch.from_numpy(jk < keep[:, None]).to(net.device)
+                self.tail = torch.where(live[:, :, None, None], kept, torch.zeros_like(kept)).contiguous()
+        self.seen += new
+        self.tail_count = keep.copy()
+        return rows, counts
+
+
+def sliding_features_from_recordings(recordings, fe, net, feature_keys, segment_steps: int, window_segments: int,
+                                     hop_segments: int = 1):
+    """``sliding_features_from_long_audio`` for recordings of different lengths in one batch: ``recordings``, a list of n
+    1-D float32 arrays of ``W_r * fe.n_samples`` samples each (W_r >= 1 whole audio windows), -> ``(rows, counts)``: ``rows``
+    float32 (n, Wn, n_feat) on the device, ``counts`` (int64, host).  ``rows[r, :counts[r]]`` are the sliding-window rows of
+    recording r alone; rows past a count are zeros.  The front end and the scatter are ``features_from_recordings``'; the
+    reservoir takes W_max stream launches with its state carried (``SNN.run_stream_records``, SPEC.md §4d): in launch w a
+    recording that still has an audio window runs all its segments, one that has ended rides along with 0."""
+    ns = int(fe.n_samples)
+    S = int(segment_steps)
+    if S < 1 or fe.n_steps % S:
+        raise ValueError(f"segment_steps = {segment_steps} must be >= 1 and divide the front end's {fe.n_steps} steps")
+    arrays, windows = [], []
+    for r, rec in enumerate(recordings):
+        a = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
+        if a.ndim != 1 or a.shape[0] < ns or a.shape[0] % ns:
+            raise ValueError(f"recording {r} must be a 1-D array of a whole number (at least 1) of windows of {ns} samples, "
+                             f"got shape {tuple(a.shape)}")
+        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
+        windows.append(a.shape[0] // ns)
+    if not arrays:
+        raise ValueError("sliding_features_from_recordings needs at least one recording")
+    n, w_max = len(arrays), max(windows)
+    windows = np.asarray(windows, dtype=np.int64)
+    Gt = fe.n_steps // S                                                # segments per audio window
+    K, H = int(window_segments), int(hop_segments)
+    net.segment_windows(w_max * Gt, K, H)                               # refuse before anything is launched
+    valid = windows * Gt
+    counts = np.where(valid >= K, (valid - K) // H + 1, 0)
+    with torch.cuda.device(net.device):
+        x = torch.from_numpy(np.concatenate(arrays).reshape(-1, ns)).to(net.device)
+        enc = fe.encode(x)                                              # (sum of W_r, C, T), recording-major
+        T = int(enc.shape[2])
+        rec_of = torch.from_numpy(np.repeat(np.arange(n), windows)).to(net.device)
+        win_of = torch.from_numpy(np.concatenate([np.arange(w) for w in windows])).to(net.device)
+        rasters = torch.zeros((n, w_max, fe.n_channels, T), dtype=torch.uint8, device=net.device)
+        rasters[rec_of, win_of] = enc
+        state = net.new_state(n)
+        records = torch.cat([net.run_stream_records(rasters[:, w].contiguous(), S, segments=np.where(windows > w, Gt, 0),
+                                                    state=state)[0] for w in range(w_max)], dim=1)
+        return net.segment_features(records, S, feature_keys, K, H, segments=valid), counts

@@ -425,6 +425,82 @@ class SNN:
             (state_out or state).steps_done = state.steps_done + T
         return records, feats, sm, vt
 
+    # ---- streams (SPEC.md §4d) ----------------------------------------------------------
+    @staticmethod
+    def _host_segments(segments, n_clips: int, n_segments: int):
+        """``segments`` as an int64 host array, checked against [0, n_segments]; ``None`` for a device tensor (never read
+        back: the kernels clamp its values)."""
+        if isinstance(segments, torch.Tensor):
+            if segments.dtype != torch.int32 or tuple(segments.shape) != (n_clips,):
+                raise ValueError(f"segments must hold {n_clips} int32 values, got {segments.dtype} {tuple(segments.shape)}")
+            if segments.is_cuda:
+                return None
+            segments = segments.numpy()
+        arr = np.asarray(segments)
+        if arr.shape != (n_clips,) or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"segments must be {n_clips} integers, got {arr.dtype} {arr.shape}")
+        arr = arr.astype(np.int64)
+        if ((arr < 0) | (arr > n_segments)).any():
+            bad = np.nonzero((arr < 0) | (arr > n_segments))[0]
+            raise ValueError(f"segments {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {n_segments}]")
+        return arr
+
+    def _device_segments(self, segments, host_segments):
+        if host_segments is None:
+            return segments.to(self.device, dtype=torch.int32).contiguous()
+        return torch.from_numpy(host_segments.astype(np.int32)).to(self.device)
+
+    def run_stream_records(self, spikes, segment_steps: int, segments=None, state: ReservoirState | None = None,
+                           state_out: ReservoirState | None = None, want_spike_matrix=False, want_v_trace=False,
+                           waves_per_clip: int = 0, stats_out=None, longest_first: bool | None = None):
+        """One stream launch (``lsm_reservoir_run_stream``, SPEC.md §4d): a segmented launch that keeps no cumulative
+        feature record, so that it needs no position -- streams anywhere on their own timelines share it, and a stream has
+        no length limit.  ``spikes`` is (B, C, T) with ``T % segment_steps == 0``; ``segments``: a sequence, a NumPy array or
+        an int32 tensor of B values in [0, T // segment_steps], the whole segments every clip runs (default: all).  Clip b
+        runs the first ``segments[b] * segment_steps`` columns of its row from ``state`` (else from ``reset()``); a clip of 0
+        segments keeps its state, statistics and rows.  Returns ``(records, spike_matrix, v_trace)``: ``records``
+        (B, T // segment_steps, N_out, 4) int32 as ``run_segment_records`` gives them, valid at ``g < segments[b]``.  The
+        tensors allocated here start as zeros, so unwritten records and rows read as zeros.  Host values out of range raise
+        ``ValueError`` (a device tensor is not read back: the kernels clamp).  ``state.data`` is updated in place (or
+        ``state_out.data`` written) with its feature-record block zeroed; ``steps_done`` and ``ended`` are not touched -- a
+        stream has neither."""
+        if isinstance(spikes, np.ndarray):
+            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
+        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
+            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        B, _, T = spikes.shape
+        S = int(segment_steps)
+        if S < 1 or T < 1 or T % S != 0:
+            raise ValueError(f"segment_steps = {S} must be >= 1 and divide the launch's {T} steps")
+        G = T // S
+        host_segments = self._host_segments(segments, B, G) if segments is not None else None
+        spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
+        if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (B, 2)
+                                      or not stats_out.is_contiguous() or stats_out.device != spikes.device):
+            raise ValueError(f"stats_out must be a contiguous int32 ({B}, 2) tensor on {spikes.device}")
+        if state is not None:
+            self._check_state(state, B)
+            if state_out is not None:
+                self._check_state(state_out, B)
+        elif state_out is not None:
+            raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
+        if longest_first is None:
+            longest_first = self.longest_first_default(B)
+        records = torch.zeros((B, G, self.num_output_neurons, 4), dtype=torch.int32, device=self.device)
+        sm = torch.zeros((B, T, self.num_neurons), dtype=torch.uint8, device=self.device) if want_spike_matrix else None
+        vt = torch.zeros((B, T, self.num_neurons), dtype=torch.float32, device=self.device) if want_v_trace else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            counts = self._device_segments(segments, host_segments) if segments is not None else None
+            need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
+            ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
+            dst = (state_out or state) if state is not None else None
+            _lib.check(self.lib.lsm_reservoir_run_stream(
+                self._handle, _dev(spikes), B, T, S, _dev(counts), _dev(state.data) if state is not None else None,
+                _dev(dst.data) if dst is not None else None, _dev(records), _dev(sm), _dev(vt), _dev(stats_out),
+                int(waves_per_clip), _dev(ws), need, stream), "lsm_reservoir_run_stream")
+        return records, sm, vt
+
     @staticmethod
     def segment_windows(n_segments: int, window_segments: int = 1, hop_segments: int = 1) -> int:
         """Number of windows of ``window_segments`` segments, ``hop_segments`` apart, in ``n_segments`` segments."""
@@ -434,11 +510,15 @@ class SNN:
         return (G - K) // H + 1
 
     def segment_features(self, records, segment_steps: int, feature_keys=None, window_segments: int = 1,
-                         hop_segments: int = 1, features_out=None):
+                         hop_segments: int = 1, features_out=None, segments=None):
         """Feature rows of sliding windows over segment records (``lsm_segment_features``): ``records`` (B, G, N_out, 4)
         int32 as ``run_segment_records`` returns them (launches concatenated along dim 1).  Returns float32
         (B, W, n_keys*N_out); window w covers segments ``[w*hop, w*hop + window_segments)`` and its row is the feature row
-        of that slice of the spike matrix."""
+        of that slice of the spike matrix.
+        ``segments``: the valid records of every clip (``lsm_segment_features_ragged``, SPEC.md §4d) -- B values as
+        ``run_stream_records`` takes them, in [0, G].  Clip b then has ``(segments[b] - window_segments) // hop_segments + 1``
+        rows (none below ``window_segments``); the rows past them are zeros, or in a caller's ``features_out`` left as they
+        are."""
         if (records.dtype != torch.int32 or records.dim() != 4 or tuple(records.shape[2:]) != (self.num_output_neurons, 4)
                 or records.device != self.device):
             raise ValueError(f"records must be an int32 (B, G, {self.num_output_neurons}, 4) tensor on {self.device}")
@@ -448,15 +528,23 @@ class SNN:
         key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
         W = self.segment_windows(G, window_segments, hop_segments)
         shape = (B, W, len(keys) * self.num_output_neurons)
+        ragged = segments is not None
+        host_segments = self._host_segments(segments, B, G) if ragged else None
         if features_out is not None:
             if (features_out.dtype != torch.float32 or tuple(features_out.shape) != shape
                     or not features_out.is_contiguous() or features_out.device != self.device):
                 raise ValueError(f"features_out must be a contiguous float32 {shape} tensor on {self.device}")
             feats = features_out
         else:
-            feats = torch.empty(shape, dtype=torch.float32, device=self.device)
+            feats = (torch.zeros if ragged else torch.empty)(shape, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if ragged:
+                counts = self._device_segments(segments, host_segments)
+                _lib.check(self.lib.lsm_segment_features_ragged(
+                    self._handle, _dev(records), B, G, _dev(counts), int(segment_steps), int(window_segments),
+                    int(hop_segments), _host(key_ids), len(keys), _dev(feats), stream), "lsm_segment_features_ragged")
+                return feats
             _lib.check(self.lib.lsm_segment_features(
                 self._handle, _dev(records), B, G, int(segment_steps), int(window_segments), int(hop_segments),
                 _host(key_ids), len(keys), _dev(feats), stream), "lsm_segment_features")
