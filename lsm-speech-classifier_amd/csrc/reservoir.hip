@@ -1023,6 +1023,15 @@ long lsm_reservoir_order_workspace(int n_clips)
 // long as the clip that happens to start last: 8.8 ms for 1024 clips whose work fills the chip for 5.1 ms.  Workgroups
 // are dispatched in index order, so handing workgroup g the clip with the g-th most input spikes is the classic
 // longest-processing-time-first schedule.  Results do not depend on it: every clip is simulated on its own.
+// The non-zero bytes among the four of w: raster bytes are 0 or 1, and anything else counts as a spike in the LIF kernels too.
+// (Per word, so that both key kernels keep adding the four counts of a 16-byte group straight into their sum.)
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w)
+{
+    uint32_t nz = w | (w >> 4);
+    nz |= nz >> 2; nz |= nz >> 1;
+    return __popc(nz & 0x01010101u);
+}
+
 __global__ __launch_bounds__(256) void clip_keys_kernel(const uint8_t *raster, long bytes_per_clip, int n_clips,
                                                         int32_t *keys)
 {
@@ -1033,14 +1042,9 @@ __global__ __launch_bounds__(256) void clip_keys_kernel(const uint8_t *raster, l
     if ((reinterpret_cast<uintptr_t>(clip) & 15) == 0) {
         for (; i + 16 <= bytes_per_clip; i += 256 * 16L) {
             const uint4 v = *reinterpret_cast<const uint4 *>(clip + i);
-            // bytes are 0 or 1 (anything else counts as a spike in the LIF kernels too: count non-zero bytes)
             const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t nz = w4[k] | (w4[k] >> 4);
-                nz |= nz >> 2; nz |= nz >> 1;
-                sum += __popc(nz & 0x01010101u);
-            }
+            for (int k = 0; k < 4; ++k) sum += nonzero_bytes(w4[k]);
         }
         // the bytes behind the last full 16-byte group of the whole clip
         if (threadIdx.x == 0)
@@ -1080,11 +1084,7 @@ __global__ __launch_bounds__(256) void clip_keys_ragged_kernel(const uint8_t *ra
             const uint4 v = *reinterpret_cast<const uint4 *>(row + t);
             const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t nz = w4[k] | (w4[k] >> 4);
-                nz |= nz >> 2; nz |= nz >> 1;
-                sum += __popc(nz & 0x01010101u);
-            }
+            for (int k = 0; k < 4; ++k) sum += nonzero_bytes(w4[k]);
         }
         if (lane < head) sum += row[lane] != 0;                          // head < 16
         if (body_end + lane < len) sum += row[body_end + lane] != 0;     // len - body_end < 16
@@ -1163,20 +1163,32 @@ static int make_plan(const lsm_reservoir *h, int n_clips, int n_steps, int waves
     return LSM_OK;
 }
 
-struct RunArgs {                // what one run is given, as the launch functions below pass it on
-    const uint8_t *raster;
-    int n_clips, n_steps, n_keys;
-    const int32_t *key_ids, *order;     // order: clip of workgroup g (longest clips first), or null
-    float *features, *v_trace;
-    uint8_t *spike_matrix;
-    int32_t *stats;
-    void *stream;
-    // continuation (lsm_reservoir_run_from): the state blocks read / written and the steps done before this launch.  Either
-    // pointer set selects the kernels' ST forms; lsm_reservoir_run and _run_ordered leave them null.
+// One launch: every run export fills its members by name, reservoir_run and the launch functions below read them.  The four
+// flags say which refusals apply (check_run); which kernel forms run follows from the values (stateful, set_common_args).
+struct RunArgs {
+    const uint8_t *raster = nullptr;
+    int n_clips = 0, n_steps = 0, n_keys = 0;
+    const int32_t *key_ids = nullptr;
+    float *features = nullptr, *v_trace = nullptr;
+    uint8_t *spike_matrix = nullptr;
+    int32_t *stats = nullptr;
+    int waves_per_clip = 0;
+    // longest clips first: the caller's workspace (lsm_reservoir_order_workspace), or null: clips start in index order.
+    // order_clips fills `order`, the clip of workgroup g, when the launch has more workgroups than the chip has CUs.
+    void *workspace = nullptr;
+    long workspace_bytes = 0;
+    const int32_t *order = nullptr;
+    void *stream = nullptr;
+    // continuation (`from`: lsm_reservoir_run_from and every export after it): the state blocks read / written and the
+    // steps done before this launch.  Either pointer set selects the kernels' ST forms; lsm_reservoir_run and _run_ordered
+    // leave them null, and a run_from call with neither is lsm_reservoir_run.
+    bool from = false;
     const void *state_in = nullptr;
     void *state_out = nullptr;
     int first_step = 0;
-    // segments (lsm_reservoir_run_segments): steps per segment and the records buffer; the ST forms close the records
+    // segments (`segmented`: lsm_reservoir_run_segments, _run_stream): steps per segment and the records buffer; the ST
+    // forms close the records
+    bool segmented = false;
     int segment_steps = 0;
     void *records = nullptr;
     // ragged launch (lsm_reservoir_run_ragged, SPEC.md §4c): device array of the steps every clip runs, or null: n_steps.
@@ -1309,82 +1321,102 @@ static int run_sparse(const lsm_reservoir *h, const Variant &v, const RunArgs &r
     return launch(fn, a, r, v.wpc, lif_lds_bytes(h, v, r.n_steps));
 }
 
-static int reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
-                         const int32_t *key_ids, int n_keys, float *features_out,
-                         uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
-                         int waves_per_clip, void *workspace, long workspace_bytes, void *stream,
-                         int first_step = 0, const void *state_in = nullptr, void *state_out = nullptr, bool from = false,
-                         bool segmented = false, int segment_steps = 0, void *records = nullptr, bool ragged = false,
-                         const int32_t *clip_steps = nullptr, bool streamed = false)
+// Step 1 of a launch: what it refuses, in the order that decides which reason a caller with two bad arguments reads, and
+// the plan (made before the workspace is looked at).  An empty batch is accepted before its buffers are.
+static int check_run(const lsm_reservoir *h, const RunArgs &r, RunPlan *plan)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_run: null handle");
-    LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
-    if (segmented) {
-        LSM_REQUIRE(segment_steps >= 1, "segment_steps=%d must be >= 1", segment_steps);
-        LSM_REQUIRE(n_steps % segment_steps == 0, "n_steps=%d is not a multiple of segment_steps=%d", n_steps, segment_steps);
-        LSM_REQUIRE(records != nullptr || n_clips == 0, "null records_out");
-        LSM_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15) == 0, "records_out must be 16-byte aligned");
+    LSM_REQUIRE(r.n_clips >= 0 && r.n_steps >= 1 && r.n_steps <= 65535, "bad n_clips/n_steps");
+    if (r.segmented) {
+        LSM_REQUIRE(r.segment_steps >= 1, "segment_steps=%d must be >= 1", r.segment_steps);
+        LSM_REQUIRE(r.n_steps % r.segment_steps == 0, "n_steps=%d is not a multiple of segment_steps=%d", r.n_steps,
+                    r.segment_steps);
+        LSM_REQUIRE(r.records != nullptr || r.n_clips == 0, "null records_out");
+        LSM_REQUIRE((reinterpret_cast<uintptr_t>(r.records) & 15) == 0, "records_out must be 16-byte aligned");
     }
-    if (from) {
-        LSM_REQUIRE(first_step >= 0, "first_step=%d must be >= 0", first_step);
-        LSM_REQUIRE((long)first_step + n_steps <= 65535, "first_step + n_steps = %ld exceeds 65535 (the feature records hold "
-                    "spike times in 16 bits)", (long)first_step + n_steps);
-        LSM_REQUIRE(first_step == 0 || state_in != nullptr, "first_step=%d needs state_in (a run from reset starts at 0)",
-                    first_step);
-        LSM_REQUIRE((reinterpret_cast<uintptr_t>(state_in) & 15) == 0 && (reinterpret_cast<uintptr_t>(state_out) & 15) == 0,
+    if (r.from) {
+        LSM_REQUIRE(r.first_step >= 0, "first_step=%d must be >= 0", r.first_step);
+        LSM_REQUIRE((long)r.first_step + r.n_steps <= 65535, "first_step + n_steps = %ld exceeds 65535 (the feature records hold "
+                    "spike times in 16 bits)", (long)r.first_step + r.n_steps);
+        LSM_REQUIRE(r.first_step == 0 || r.state_in != nullptr, "first_step=%d needs state_in (a run from reset starts at 0)",
+                    r.first_step);
+        LSM_REQUIRE((reinterpret_cast<uintptr_t>(r.state_in) & 15) == 0 && (reinterpret_cast<uintptr_t>(r.state_out) & 15) == 0,
                     "state_in / state_out must be 16-byte aligned");
-        LSM_REQUIRE(n_keys >= 0 && n_keys <= 8 && (n_keys == 0 || key_ids), "n_keys must be in [0, 8]");
-        LSM_REQUIRE(n_keys == 0 || features_out, "null features_out with n_keys=%d", n_keys);
+        LSM_REQUIRE(r.n_keys >= 0 && r.n_keys <= 8 && (r.n_keys == 0 || r.key_ids), "n_keys must be in [0, 8]");
+        LSM_REQUIRE(r.n_keys == 0 || r.features, "null features_out with n_keys=%d", r.n_keys);
     } else {
-        LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+        LSM_REQUIRE(r.n_keys >= 1 && r.n_keys <= 8 && r.key_ids, "n_keys must be in [1, 8]");
     }
-    LSM_REQUIRE((reinterpret_cast<uintptr_t>(clip_steps) & 3) == 0, "%s must be 4-byte aligned",
-                streamed ? "clip_segments" : "clip_steps");
-    LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
-    if (n_clips == 0) return LSM_OK;            // empty batch: nothing to read or write
-    LSM_REQUIRE(spikes_u8 && (features_out || from), "null buffer");
+    LSM_REQUIRE((reinterpret_cast<uintptr_t>(r.clip_steps) & 3) == 0, "%s must be 4-byte aligned",
+                r.streamed ? "clip_segments" : "clip_steps");
+    LSM_REQUIRE(r.waves_per_clip >= -1 && r.waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
+    if (r.n_clips == 0) return LSM_OK;          // empty batch: nothing to read or write
+    LSM_REQUIRE(r.raster && (r.features || r.from), "null buffer");
     int dev_now = -1;
     LSM_CHECK_HIP(hipGetDevice(&dev_now));
     LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d",
                 h->device, dev_now);
-    for (int k = 0; k < n_keys; ++k)
-        LSM_REQUIRE(key_ids[k] >= 0 && key_ids[k] < 8, "key id %d out of range", key_ids[k]);
-
-    RunPlan plan;
-    const int prc = make_plan(h, n_clips, n_steps, waves_per_clip, &plan);
+    for (int k = 0; k < r.n_keys; ++k)
+        LSM_REQUIRE(r.key_ids[k] >= 0 && r.key_ids[k] < 8, "key id %d out of range", r.key_ids[k]);
+    const int prc = make_plan(h, r.n_clips, r.n_steps, r.waves_per_clip, plan);
     if (prc) return prc;
-    // longest clips first, when the launch has more workgroups than the chip has CUs (else every clip starts at once)
-    const int32_t *order = nullptr;
-    if (workspace) {
-        LSM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "workspace must be 4-byte aligned");
-        LSM_REQUIRE(workspace_bytes >= lsm_reservoir_order_workspace(n_clips),
-                    "workspace of %ld bytes, need %ld (lsm_reservoir_order_workspace)", workspace_bytes,
-                    lsm_reservoir_order_workspace(n_clips));
-        if (h->cus > 0 && n_clips > h->cus) {
-            int32_t *keys = static_cast<int32_t *>(workspace);
-            int32_t *ord = keys + n_clips;
-            if (clip_steps)         // the bytes inside every clip's own length
-                hipLaunchKernelGGL(clip_keys_ragged_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
-                                   h->C, n_steps, clip_steps, n_clips, keys, streamed ? segment_steps : 0);
-            else
-                hipLaunchKernelGGL(clip_keys_kernel, dim3(n_clips), dim3(256), 0, (hipStream_t)stream, spikes_u8,
-                                   (long)h->C * n_steps, n_clips, keys);
-            hipLaunchKernelGGL(clip_rank_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                               keys, n_clips, ord);
-            LSM_CHECK_HIP(hipGetLastError());
-            order = ord;
-        }
+    if (r.workspace) {
+        LSM_REQUIRE((reinterpret_cast<uintptr_t>(r.workspace) & 3) == 0, "workspace must be 4-byte aligned");
+        LSM_REQUIRE(r.workspace_bytes >= lsm_reservoir_order_workspace(r.n_clips),
+                    "workspace of %ld bytes, need %ld (lsm_reservoir_order_workspace)", r.workspace_bytes,
+                    lsm_reservoir_order_workspace(r.n_clips));
     }
-    RunArgs r = {spikes_u8, n_clips, n_steps, n_keys, key_ids, order, features_out, v_trace_out, spike_matrix_out, stats_out,
-                 stream};
-    r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
-    if (segmented) { r.segment_steps = segment_steps; r.records = records; }
-    r.ragged = ragged; r.clip_steps = clip_steps; r.streamed = streamed;
+    return LSM_OK;
+}
+
+// Step 2: longest clips first, when the caller gave a workspace and the launch has more workgroups than the chip has CUs
+// (else every clip starts at once).
+static int order_clips(const lsm_reservoir *h, RunArgs *r)
+{
+    if (!r->workspace || h->cus <= 0 || r->n_clips <= h->cus) return LSM_OK;
+    int32_t *keys = static_cast<int32_t *>(r->workspace);
+    int32_t *ord = keys + r->n_clips;
+    if (r->clip_steps)      // the bytes inside every clip's own length
+        hipLaunchKernelGGL(clip_keys_ragged_kernel, dim3(r->n_clips), dim3(256), 0, (hipStream_t)r->stream, r->raster,
+                           h->C, r->n_steps, r->clip_steps, r->n_clips, keys, r->streamed ? r->segment_steps : 0);
+    else
+        hipLaunchKernelGGL(clip_keys_kernel, dim3(r->n_clips), dim3(256), 0, (hipStream_t)r->stream, r->raster,
+                           (long)h->C * r->n_steps, r->n_clips, keys);
+    hipLaunchKernelGGL(clip_rank_kernel, dim3((r->n_clips + 255) / 256), dim3(256), 0, (hipStream_t)r->stream,
+                       keys, r->n_clips, ord);
+    LSM_CHECK_HIP(hipGetLastError());
+    r->order = ord;
+    return LSM_OK;
+}
+
+// Step 3: the planned kernel.
+static int dispatch(const lsm_reservoir *h, const RunPlan &plan, const RunArgs &r)
+{
     if (plan.pv) return run_pairs(h, *plan.pv, r);
     if (plan.rv) return run_quads(h, *plan.rv, r);
     return plan.kernel == KERNEL_DENSE ? run_dense(h, *plan.v, r) : run_sparse(h, *plan.v, r);
 }
 
+// Every run export ends here with the request it filled.
+static int reservoir_run(const lsm_reservoir *h, RunArgs *r)
+{
+    RunPlan plan;
+    int rc = check_run(h, *r, &plan);
+    if (rc != LSM_OK || r->n_clips == 0) return rc;    // refused, or an empty batch: accepted, but no plan was made for it
+    rc = order_clips(h, r);
+    return rc != LSM_OK ? rc : dispatch(h, plan, *r);
+}
+
+// What all six run exports are given: the clips, the outputs of every step, the layout request and the stream.
+static RunArgs run_args(const uint8_t *spikes_u8, int n_clips, int n_steps, uint8_t *spike_matrix_out, float *v_trace_out,
+                        int32_t *stats_out, int waves_per_clip, void *stream)
+{
+    RunArgs r;
+    r.raster = spikes_u8; r.n_clips = n_clips; r.n_steps = n_steps;
+    r.spike_matrix = spike_matrix_out; r.v_trace = v_trace_out; r.stats = stats_out;
+    r.waves_per_clip = waves_per_clip; r.stream = stream;
+    return r;
+}
 
 extern "C" __attribute__((visibility("default")))
 int lsm_reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_clips, int n_steps,
@@ -1392,8 +1424,9 @@ int lsm_reservoir_run(const lsm_reservoir *h, const uint8_t *spikes_u8, int n_cl
                       uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                       int waves_per_clip, void *stream)
 {
-    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
-                         stats_out, waves_per_clip, nullptr, 0, stream);
+    RunArgs r = run_args(spikes_u8, n_clips, n_steps, spike_matrix_out, v_trace_out, stats_out, waves_per_clip, stream);
+    r.key_ids = key_ids; r.n_keys = n_keys; r.features = features_out;
+    return reservoir_run(h, &r);
 }
 
 extern "C" __attribute__((visibility("default")))
@@ -1403,8 +1436,10 @@ int lsm_reservoir_run_ordered(const lsm_reservoir *h, const uint8_t *spikes_u8, 
                               int waves_per_clip, void *workspace, long workspace_bytes, void *stream)
 {
     LSM_REQUIRE(workspace != nullptr || n_clips == 0, "lsm_reservoir_run_ordered: null workspace");
-    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
-                         stats_out, waves_per_clip, workspace, workspace_bytes, stream);
+    RunArgs r = run_args(spikes_u8, n_clips, n_steps, spike_matrix_out, v_trace_out, stats_out, waves_per_clip, stream);
+    r.key_ids = key_ids; r.n_keys = n_keys; r.features = features_out;
+    r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+    return reservoir_run(h, &r);
 }
 
 extern "C" __attribute__((visibility("default")))
@@ -1422,9 +1457,11 @@ int lsm_reservoir_run_from(const lsm_reservoir *h, const uint8_t *spikes_u8, int
                            uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                            int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
 {
-    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
-                         stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
-                         state_out, true);
+    RunArgs r = run_args(spikes_u8, n_clips, n_steps, spike_matrix_out, v_trace_out, stats_out, waves_per_clip, stream);
+    r.key_ids = key_ids; r.n_keys = n_keys; r.features = features_out;
+    r.workspace = order_workspace; r.workspace_bytes = order_workspace_bytes;
+    r.from = true; r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
+    return reservoir_run(h, &r);
 }
 
 // lsm_reservoir_run_from with the feature bookkeeping cut every segment_steps steps (SPEC.md §4b): always the ST forms,
@@ -1436,9 +1473,12 @@ int lsm_reservoir_run_segments(const lsm_reservoir *h, const uint8_t *spikes_u8,
                                uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                                int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
 {
-    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
-                         stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
-                         state_out, true, true, segment_steps, records_out);
+    RunArgs r = run_args(spikes_u8, n_clips, n_steps, spike_matrix_out, v_trace_out, stats_out, waves_per_clip, stream);
+    r.key_ids = key_ids; r.n_keys = n_keys; r.features = features_out;
+    r.workspace = order_workspace; r.workspace_bytes = order_workspace_bytes;
+    r.from = true; r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
+    r.segmented = true; r.segment_steps = segment_steps; r.records = records_out;
+    return reservoir_run(h, &r);
 }
 
 // lsm_reservoir_run_from whose clips run clip_steps[b] (clamped into [0, n_steps]) steps each (SPEC.md §4c): the same
@@ -1450,9 +1490,12 @@ int lsm_reservoir_run_ragged(const lsm_reservoir *h, const uint8_t *spikes_u8, i
                              uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                              int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
 {
-    return reservoir_run(h, spikes_u8, n_clips, n_steps, key_ids, n_keys, features_out, spike_matrix_out, v_trace_out,
-                         stats_out, waves_per_clip, order_workspace, order_workspace_bytes, stream, first_step, state_in,
-                         state_out, true, false, 0, nullptr, true, clip_steps);
+    RunArgs r = run_args(spikes_u8, n_clips, n_steps, spike_matrix_out, v_trace_out, stats_out, waves_per_clip, stream);
+    r.key_ids = key_ids; r.n_keys = n_keys; r.features = features_out;
+    r.workspace = order_workspace; r.workspace_bytes = order_workspace_bytes;
+    r.from = true; r.state_in = state_in; r.state_out = state_out; r.first_step = first_step;
+    r.ragged = true; r.clip_steps = clip_steps;
+    return reservoir_run(h, &r);
 }
 
 // One thread per (clip, window, output neuron): §4a's merge folded over the window's records, then the neuron's n_keys
@@ -1505,9 +1548,11 @@ __global__ __launch_bounds__(256) void segment_features_ragged_kernel(const Segm
     segment_window_row(a, b, wdw, bw, o);
 }
 
+enum SegmentCounts { ALL_SEGMENTS, CLIP_SEGMENTS };     // every clip has all n_segments records / clip_segments[b] of them
+
 static int segment_features(const lsm_reservoir *h, const void *records, int n_clips, int n_segments, int segment_steps,
                             int window_segments, int hop_segments, const int32_t *key_ids, int n_keys, float *features_out,
-                            void *stream, bool ragged, const int32_t *clip_segments)
+                            void *stream, SegmentCounts counts, const int32_t *clip_segments)
 {
     LSM_REQUIRE(h != nullptr, "lsm_segment_features: null handle");
     LSM_REQUIRE(n_clips >= 0 && n_segments >= 1, "bad n_clips/n_segments");
@@ -1524,7 +1569,7 @@ static int segment_features(const lsm_reservoir *h, const void *records, int n_c
     LSM_REQUIRE((reinterpret_cast<uintptr_t>(clip_segments) & 3) == 0, "clip_segments must be 4-byte aligned");
     if (n_clips == 0) return LSM_OK;
     LSM_REQUIRE(records && features_out, "null buffer");
-    LSM_REQUIRE(!ragged || clip_segments, "null clip_segments");
+    LSM_REQUIRE(counts == ALL_SEGMENTS || clip_segments, "null clip_segments");
     int dev_now = -1;
     LSM_CHECK_HIP(hipGetDevice(&dev_now));
     LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d",
@@ -1539,8 +1584,8 @@ static int segment_features(const lsm_reservoir *h, const void *records, int n_c
     const long total = (long)a.B * a.W * a.n_out;
     LSM_REQUIRE((total + 255) / 256 <= 0x7FFFFFFFL, "too many (clip, window, output neuron) triples: %ld", total);
     if (total == 0) return LSM_OK;
-    hipLaunchKernelGGL(ragged ? segment_features_ragged_kernel : segment_features_kernel, dim3((unsigned)((total + 255) / 256)),
-                       dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(counts == CLIP_SEGMENTS ? segment_features_ragged_kernel : segment_features_kernel,
+                       dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
@@ -1551,7 +1596,7 @@ int lsm_segment_features(const lsm_reservoir *h, const void *records, int n_clip
                          void *stream)
 {
     return segment_features(h, records, n_clips, n_segments, segment_steps, window_segments, hop_segments, key_ids, n_keys,
-                            features_out, stream, false, nullptr);
+                            features_out, stream, ALL_SEGMENTS, nullptr);
 }
 
 // ---- streams (SPEC.md §4d, include/lsm_hip_streams.h) --------------------------------------------------------------------
@@ -1564,9 +1609,12 @@ int lsm_reservoir_run_stream(const lsm_reservoir *h, const uint8_t *spikes_u8, i
                              void *records_out, uint8_t *spike_matrix_out, float *v_trace_out, int32_t *stats_out,
                              int waves_per_clip, void *order_workspace, long order_workspace_bytes, void *stream)
 {
-    return reservoir_run(h, spikes_u8, n_clips, n_steps, nullptr, 0, nullptr, spike_matrix_out, v_trace_out, stats_out,
-                         waves_per_clip, order_workspace, order_workspace_bytes, stream, 0, state_in, state_out, true, true,
-                         segment_steps, records_out, true, clip_segments, true);
+    RunArgs r = run_args(spikes_u8, n_clips, n_steps, spike_matrix_out, v_trace_out, stats_out, waves_per_clip, stream);
+    r.workspace = order_workspace; r.workspace_bytes = order_workspace_bytes;
+    r.from = true; r.state_in = state_in; r.state_out = state_out;
+    r.segmented = true; r.segment_steps = segment_steps; r.records = records_out;
+    r.ragged = true; r.clip_steps = clip_segments; r.streamed = true;
+    return reservoir_run(h, &r);
 }
 
 // lsm_segment_features over records of which every clip has a valid count of its own.
@@ -1576,7 +1624,15 @@ int lsm_segment_features_ragged(const lsm_reservoir *h, const void *records, int
                                 const int32_t *key_ids, int n_keys, float *features_out, void *stream)
 {
     return segment_features(h, records, n_clips, n_segments, segment_steps, window_segments, hop_segments, key_ids, n_keys,
-                            features_out, stream, true, clip_segments);
+                            features_out, stream, CLIP_SEGMENTS, clip_segments);
+}
+
+// The plan for lsm_reservoir_plan and _row_request_bytes, behind the two refusals they share.
+static int plan_request(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip, RunPlan *p)
+{
+    LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
+    LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
+    return make_plan(h, n_clips, n_steps, waves_per_clip, p);
 }
 
 // Largest n_steps make_plan accepts for this batch and waves_per_clip: every layout's LDS image grows with the steps, so
@@ -1600,89 +1656,65 @@ int lsm_reservoir_max_steps(const lsm_reservoir *h, int n_clips, int waves_per_c
     return lo;
 }
 
-// Introspection for tests and the bench: kernel and layout chosen for a batch, LDS bytes per workgroup, bytes of the
-// weight table the kernel gathers its rows from.
+// Introspection for tests and the bench, read off a made plan: the layout chosen for a batch (waves per clip, neuron slots
+// per lane), LDS bytes per workgroup, bytes of the weight table the kernel gathers its rows from and the mean bytes one row
+// request moves, the kernel's input form (lsm_reservoir_input_mode) and which ring-row form it is: 0 not ring rows, 1 quads
+// with contiguous ownership, 2 strided quads (lif_ring.h), 3 pair blocks (lif_pair.h).
+struct PlanFacts {
+    int wpc, slots, input_mode, ring_form;
+    size_t lds_bytes, table_bytes;
+    double row_request_bytes;
+};
+
+static PlanFacts plan_facts(const lsm_reservoir *h, const RunPlan &p, int n_steps)
+{
+    const double n = (double)h->N;
+    PlanFacts f;
+    if (p.pv) {
+        const PairVariant &v = *p.pv;
+        f.wpc = v.wpc; f.slots = v.bl * 2;
+        f.lds_bytes = pair_lds_bytes(h, v, n_steps);
+        // ring windows + this layout's lists + its row records
+        f.table_bytes = (size_t)h->N * h->band_pitch + v.n_rem * 8 + (size_t)h->N * v.wpc * 16;
+        f.row_request_bytes = (h->band_bytes_sum + (double)v.n_rem * 8.0) / n + v.wpc * 16.0;
+        f.input_mode = v.inform == 3 ? 11 : (v.inform == 2 ? 15 : 14);
+        f.ring_form = 3;
+    } else if (p.rv) {
+        const RingVariant &v = *p.rv;
+        f.wpc = v.wpc; f.slots = v.ql * 4;
+        f.lds_bytes = ring_lds_bytes(h, v, n_steps);
+        // ring windows + this layout's lists of the synapses outside them + their row pointers
+        f.table_bytes = (size_t)h->N * h->band_pitch + v.n_rem * 8 + ((size_t)h->N * v.wpc + 1) * 4;
+        f.row_request_bytes = (h->band_bytes_sum + (double)v.n_rem * 8.0) / n + (v.wpc + 1) * 4.0;
+        f.input_mode = v.inmask ? (v.incol ? 13 : 12) : (ring_inreg(v) ? 11 : 10);
+        f.ring_form = v.strided ? 2 : 1;
+    } else {
+        const Variant &v = *p.v;
+        const bool dense = p.kernel == KERNEL_DENSE;
+        f.wpc = v.wpc; f.slots = v.sl;
+        f.lds_bytes = dense ? dense_lds_bytes(h, v, n_steps) : lif_lds_bytes(h, v, n_steps);
+        f.table_bytes = dense ? (size_t)h->N * h->ld * 4 : h->nnz * 8 + ((size_t)h->N + 1) * 4;
+        f.row_request_bytes = dense ? (double)h->ld * 4.0 : (double)h->nnz * 8.0 / n + 8.0;
+        f.input_mode = !dense ? 20 : v.inmask ? (v.incol ? 3 : 2) : (lif_inreg(v) ? 1 : 0);
+        f.ring_form = 0;
+    }
+    return f;
+}
+
 extern "C" __attribute__((visibility("default")))
 int lsm_reservoir_plan(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip, int *kernel_out,
                        int *wpc_out, int *slots_out, int *lds_bytes_out, long *table_bytes_out)
 {
     LSM_REQUIRE(h != nullptr, "lsm_reservoir_plan: null handle");
-    LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
-    LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
     RunPlan p;
-    const int rc = make_plan(h, n_clips, n_steps, waves_per_clip, &p);
+    const int rc = plan_request(h, n_clips, n_steps, waves_per_clip, &p);
     if (rc) return rc;
+    const PlanFacts f = plan_facts(h, p, n_steps);
     if (kernel_out) *kernel_out = p.kernel;
-    if (p.pv) {
-        if (wpc_out) *wpc_out = p.pv->wpc;
-        if (slots_out) *slots_out = p.pv->bl * 2;
-        if (lds_bytes_out) *lds_bytes_out = (int)pair_lds_bytes(h, *p.pv, n_steps);
-        if (table_bytes_out)    // ring windows + this layout's lists + its row records
-            *table_bytes_out = (long)((size_t)h->N * h->band_pitch + p.pv->n_rem * 8 + (size_t)h->N * p.pv->wpc * 16);
-        return LSM_OK;
-    }
-    if (p.rv) {
-        if (wpc_out) *wpc_out = p.rv->wpc;
-        if (slots_out) *slots_out = p.rv->ql * 4;
-        if (lds_bytes_out) *lds_bytes_out = (int)ring_lds_bytes(h, *p.rv, n_steps);
-        if (table_bytes_out) {
-            // ring windows + this layout's lists of the synapses outside them + their row pointers
-            *table_bytes_out = (long)((size_t)h->N * h->band_pitch + p.rv->n_rem * 8 + ((size_t)h->N * p.rv->wpc + 1) * 4);
-        }
-        return LSM_OK;
-    }
-    if (wpc_out) *wpc_out = p.v->wpc;
-    if (slots_out) *slots_out = p.v->sl;
-    if (lds_bytes_out)
-        *lds_bytes_out = (int)(p.kernel == KERNEL_DENSE ? dense_lds_bytes(h, *p.v, n_steps) : lif_lds_bytes(h, *p.v, n_steps));
-    if (table_bytes_out)
-        *table_bytes_out = p.kernel == KERNEL_DENSE ? (long)((size_t)h->N * h->ld * 4) : (long)(h->nnz * 8 + ((size_t)h->N + 1) * 4);
-    return LSM_OK;
-}
-
-extern "C" __attribute__((visibility("default")))
-int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip)
-{
-    if (h == nullptr) return LSM_ERR_ARG;
-    RunPlan p;
-    if (make_plan(h, n_clips, n_steps, waves_per_clip, &p) != LSM_OK) return LSM_ERR_UNSUPPORTED;
-    if (p.pv) return p.pv->inform == 3 ? 11 : (p.pv->inform == 2 ? 15 : 14);
-    if (p.rv) return p.rv->inmask ? (p.rv->incol ? 13 : 12) : (ring_inreg(*p.rv) ? 11 : 10);
-    if (p.kernel == KERNEL_SPARSE) return 20;
-    return p.v->inmask ? (p.v->incol ? 3 : 2) : (lif_inreg(*p.v) ? 1 : 0);
-}
-
-// Which ring-row form the planned kernel is: 0 not ring rows, 1 quads with contiguous ownership, 2 strided quads (lif_ring.h),
-// 3 pair blocks (lif_pair.h).
-extern "C" __attribute__((visibility("default")))
-int lsm_reservoir_ring_form(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip)
-{
-    if (h == nullptr) return LSM_ERR_ARG;
-    RunPlan p;
-    if (make_plan(h, n_clips, n_steps, waves_per_clip, &p) != LSM_OK) return LSM_ERR_UNSUPPORTED;
-    if (p.kernel != KERNEL_RING) return 0;
-    return p.pv ? 3 : (p.rv->strided ? 2 : 1);
-}
-
-extern "C" __attribute__((visibility("default")))
-int lsm_reservoir_row_request_bytes(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip,
-                                    double *mean_bytes_out)
-{
-    LSM_REQUIRE(h != nullptr && mean_bytes_out != nullptr, "lsm_reservoir_row_request_bytes: null argument");
-    LSM_REQUIRE(n_clips >= 0 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
-    LSM_REQUIRE(waves_per_clip >= -1 && waves_per_clip <= 16, "waves_per_clip must be -1 (pipelined), 0 (choose) or 1..16");
-    RunPlan p;
-    const int rc = make_plan(h, n_clips, n_steps, waves_per_clip, &p);
-    if (rc) return rc;
-    const double n = (double)h->N;
-    if (p.pv)
-        *mean_bytes_out = (h->band_bytes_sum + (double)p.pv->n_rem * 8.0) / n + p.pv->wpc * 16.0;
-    else if (p.rv)
-        *mean_bytes_out = (h->band_bytes_sum + (double)p.rv->n_rem * 8.0) / n + (p.rv->wpc + 1) * 4.0;
-    else if (p.kernel == KERNEL_DENSE)
-        *mean_bytes_out = (double)h->ld * 4.0;
-    else
-        *mean_bytes_out = (double)h->nnz * 8.0 / n + 8.0;
+    if (wpc_out) *wpc_out = f.wpc;
+    if (slots_out) *slots_out = f.slots;
+    if (lds_bytes_out) *lds_bytes_out = (int)f.lds_bytes;
+    if (table_bytes_out) *table_bytes_out = (long)f.table_bytes;
     return LSM_OK;
 }
 
@@ -1691,6 +1723,41 @@ int lsm_reservoir_layout(const lsm_reservoir *h, int n_clips, int n_steps, int w
                          int *wpc_out, int *slots_out, int *lds_bytes_out)
 {
     return lsm_reservoir_plan(h, n_clips, n_steps, waves_per_clip, nullptr, wpc_out, slots_out, lds_bytes_out, nullptr);
+}
+
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_row_request_bytes(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip,
+                                    double *mean_bytes_out)
+{
+    LSM_REQUIRE(h != nullptr && mean_bytes_out != nullptr, "lsm_reservoir_row_request_bytes: null argument");
+    RunPlan p;
+    const int rc = plan_request(h, n_clips, n_steps, waves_per_clip, &p);
+    if (rc) return rc;
+    *mean_bytes_out = plan_facts(h, p, n_steps).row_request_bytes;
+    return LSM_OK;
+}
+
+// The plan for lsm_reservoir_input_mode and _ring_form, which refuse only a null handle and leave no message.
+static int quiet_plan(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip, RunPlan *p)
+{
+    if (h == nullptr) return LSM_ERR_ARG;
+    return make_plan(h, n_clips, n_steps, waves_per_clip, p) == LSM_OK ? LSM_OK : LSM_ERR_UNSUPPORTED;
+}
+
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_input_mode(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip)
+{
+    RunPlan p;
+    const int rc = quiet_plan(h, n_clips, n_steps, waves_per_clip, &p);
+    return rc ? rc : plan_facts(h, p, n_steps).input_mode;
+}
+
+extern "C" __attribute__((visibility("default")))
+int lsm_reservoir_ring_form(const lsm_reservoir *h, int n_clips, int n_steps, int waves_per_clip)
+{
+    RunPlan p;
+    const int rc = quiet_plan(h, n_clips, n_steps, waves_per_clip, &p);
+    return rc ? rc : plan_facts(h, p, n_steps).ring_form;
 }
 
 // Which kernel lsm_reservoir_run would launch for this handle: 1 sparse, 2 dense rows, 3 ring rows -- for the

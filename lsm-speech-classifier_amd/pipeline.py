@@ -355,6 +355,54 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     return feats if device_out else feats.cpu().numpy()
 
 
+def _audio_windows(audio, fe):
+    """``audio`` (n, W * fe.n_samples) float32, tensor or NumPy (copied), checked: ``(audio tensor, n, W)``."""
+    if isinstance(audio, np.ndarray):
+        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    ns = int(fe.n_samples)
+    if audio.dim() != 2 or audio.shape[1] < ns or audio.shape[1] % ns:
+        raise ValueError(f"audio must be (n, W * {ns}), got {tuple(audio.shape)}")
+    return audio, int(audio.shape[0]), int(audio.shape[1]) // ns
+
+
+def _encode_audio_windows(audio, n: int, W: int, fe, net):
+    """The rasters (n, W, C, T) of ``_audio_windows``' audio: the front end runs on the n * W windows as independent clips.
+    Called on ``net.device``."""
+    x = audio.to(net.device, dtype=torch.float32).reshape(n * W, int(fe.n_samples)).contiguous()
+    return fe.encode(x).reshape(n, W, fe.n_channels, -1)
+
+
+def _recording_windows(recordings, fe, caller: str):
+    """``recordings`` (1-D arrays or tensors of whole windows of fe.n_samples samples) as contiguous float32 arrays, and
+    their window counts W_r (int64); ``caller`` is the public function's name, for the refusal of an empty list."""
+    ns = int(fe.n_samples)
+    arrays, windows = [], []
+    for r, rec in enumerate(recordings):
+        a = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
+        if a.ndim != 1 or a.shape[0] < ns or a.shape[0] % ns:
+            raise ValueError(f"recording {r} must be a 1-D array of a whole number (at least 1) of windows of {ns} samples, "
+                             f"got shape {tuple(a.shape)}")
+        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
+        windows.append(a.shape[0] // ns)
+    if not arrays:
+        raise ValueError(f"{caller} needs at least one recording")
+    return arrays, np.asarray(windows, dtype=np.int64)
+
+
+def _scatter_recording_windows(arrays, windows, fe, net):
+    """The rasters (n, W_max, C, T) of ``_recording_windows``' recordings: the front end runs once on all windows of all
+    recordings as independent clips, window w of recording r lands at [r, w], and what lies past a recording's W_r windows
+    is zeros.  Called on ``net.device``."""
+    n, w_max = len(arrays), int(windows.max())
+    x = torch.from_numpy(np.concatenate(arrays).reshape(-1, int(fe.n_samples))).to(net.device)
+    enc = fe.encode(x)                                                  # (sum of W_r, C, T), recording-major
+    rec_of = torch.from_numpy(np.repeat(np.arange(n), windows)).to(net.device)
+    win_of = torch.from_numpy(np.concatenate([np.arange(w) for w in windows])).to(net.device)
+    rasters = torch.zeros((n, w_max, fe.n_channels, int(enc.shape[2])), dtype=torch.uint8, device=net.device)
+    rasters[rec_of, win_of] = enc
+    return rasters
+
+
 def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = True):
     """A recording taken window by window: ``audio`` (n, W * fe.n_samples) float32 -> (n, W, n_feat) float32 device
     tensor.  The front end runs on the n * W windows as independent clips (its normalisation is per clip, as the
@@ -362,15 +410,9 @@ def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = T
     and spike state between them (``SNN.run_batch(state=...)``): row w holds the features of steps [0, (w + 1) * T) of
     the recording, what one run over the concatenated rasters gives.  ``carry_state=False``: every window from
     ``reset()``, W independent ``run_batch`` calls."""
-    if isinstance(audio, np.ndarray):
-        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-    ns = int(fe.n_samples)
-    if audio.dim() != 2 or audio.shape[1] < ns or audio.shape[1] % ns:
-        raise ValueError(f"audio must be (n, W * {ns}), got {tuple(audio.shape)}")
-    n, W = int(audio.shape[0]), int(audio.shape[1]) // ns
+    audio, n, W = _audio_windows(audio, fe)
     with torch.cuda.device(net.device):
-        x = audio.to(net.device, dtype=torch.float32).reshape(n * W, ns).contiguous()
-        rasters = fe.encode(x).reshape(n, W, fe.n_channels, -1)
+        rasters = _encode_audio_windows(audio, n, W, fe, net)
         state = net.new_state(n) if carry_state else None
         rows = [net.run_batch(rasters[:, w].contiguous(), feature_keys, state=state)[0] for w in range(W)]
         return torch.stack(rows, dim=1)
@@ -384,32 +426,16 @@ def features_from_recordings(recordings, fe, net, feature_keys):
     normalisation is per window, as the reference's); the rasters are scattered into (n, W_max, C, T), and the reservoir
     takes W_max ragged launches with its state carried (``SNN.run_batch(lengths=...)``, SPEC.md §4c): in launch w a
     recording that still has a window runs its T steps, one that has ended rides along with 0 and keeps its row."""
-    ns = int(fe.n_samples)
-    arrays, windows = [], []
-    for r, rec in enumerate(recordings):
-        a = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
-        if a.ndim != 1 or a.shape[0] < ns or a.shape[0] % ns:
-            raise ValueError(f"recording {r} must be a 1-D array of a whole number (at least 1) of windows of {ns} samples, "
-                             f"got shape {tuple(a.shape)}")
-        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
-        windows.append(a.shape[0] // ns)
-    if not arrays:
-        raise ValueError("features_from_recordings needs at least one recording")
-    n, w_max = len(arrays), max(windows)
-    windows = np.asarray(windows, dtype=np.int64)
+    arrays, windows = _recording_windows(recordings, fe, "features_from_recordings")
+    n = len(arrays)
     with torch.cuda.device(net.device):
-        x = torch.from_numpy(np.concatenate(arrays).reshape(-1, ns)).to(net.device)
-        enc = fe.encode(x)                                              # (sum of W_r, C, T), recording-major
-        T = int(enc.shape[2])
-        rec_of = torch.from_numpy(np.repeat(np.arange(n), windows)).to(net.device)
-        win_of = torch.from_numpy(np.concatenate([np.arange(w) for w in windows])).to(net.device)
-        rasters = torch.zeros((n, w_max, fe.n_channels, T), dtype=torch.uint8, device=net.device)
-        rasters[rec_of, win_of] = enc
-        from .snn import FEATURE_KEYS
-        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
+        rasters = _scatter_recording_windows(arrays, windows, fe, net)
+        T = int(rasters.shape[3])
+        from .snn import _select_keys
+        keys, _ = _select_keys(feature_keys)
         feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
         state = net.new_state(n)
-        for w in range(w_max):
+        for w in range(rasters.shape[1]):
             net.run_batch(rasters[:, w].contiguous(), feature_keys, features_out=feats, state=state,
                           lengths=np.where(windows > w, T, 0))
         return feats
@@ -424,19 +450,13 @@ def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps
     through one ``lsm_segment_features`` call: row w is the feature row of steps
     ``[w * hop_segments * segment_steps, (w * hop_segments + window_segments) * segment_steps)`` of the recording's one
     uncut run -- windows may straddle the audio windows."""
-    if isinstance(audio, np.ndarray):
-        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-    ns = int(fe.n_samples)
-    if audio.dim() != 2 or audio.shape[1] < ns or audio.shape[1] % ns:
-        raise ValueError(f"audio must be (n, W * {ns}), got {tuple(audio.shape)}")
+    audio, n, W = _audio_windows(audio, fe)
     S = int(segment_steps)
     if S < 1 or fe.n_steps % S:
         raise ValueError(f"segment_steps = {segment_steps} must be >= 1 and divide the front end's {fe.n_steps} steps")
-    n, W = int(audio.shape[0]), int(audio.shape[1]) // ns
     net.segment_windows(W * (fe.n_steps // S), window_segments, hop_segments)     # refuse before anything is launched
     with torch.cuda.device(net.device):
-        x = audio.to(net.device, dtype=torch.float32).reshape(n * W, ns).contiguous()
-        rasters = fe.encode(x).reshape(n, W, fe.n_channels, -1)
+        rasters = _encode_audio_windows(audio, n, W, fe, net)
         state = net.new_state(n)
         records = torch.cat([net.run_segment_records(rasters[:, w].contiguous(), S, state=state)[0] for w in range(W)],
                             dim=1)
@@ -520,9 +540,8 @@ class StreamBank:
         Gp = int(rasters.shape[2]) // S
         new = net._host_segments(np.asarray(segments), self.n_streams, Gp)
         counts, keep = stream_window_plan(self.seen, new, K, H)
-        from .snn import FEATURE_KEYS, ragged_chunks
-        keys = FEATURE_KEYS if self.feature_keys is None else [k for k in self.feature_keys if k in FEATURE_KEYS]
-        n_feat = len(keys) * net.num_output_neurons
+        from .snn import _select_keys, ragged_chunks
+        n_feat = len(_select_keys(self.feature_keys)[0]) * net.num_output_neurons
         if Gp == 0 or int(new.max()) == 0:
             return torch.zeros((self.n_streams, 0, n_feat), dtype=torch.float32, device=net.device), counts
         chunk = net._max_steps_cached(self.n_streams) // S * S
@@ -561,35 +580,18 @@ def sliding_features_from_recordings(recordings, fe, net, feature_keys, segment_
     recording r alone; rows past a count are zeros.  The front end and the scatter are ``features_from_recordings``'; the
     reservoir takes W_max stream launches with its state carried (``SNN.run_stream_records``, SPEC.md §4d): in launch w a
     recording that still has an audio window runs all its segments, one that has ended rides along with 0."""
-    ns = int(fe.n_samples)
     S = int(segment_steps)
     if S < 1 or fe.n_steps % S:
         raise ValueError(f"segment_steps = {segment_steps} must be >= 1 and divide the front end's {fe.n_steps} steps")
-    arrays, windows = [], []
-    for r, rec in enumerate(recordings):
-        a = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else np.asarray(rec)
-        if a.ndim != 1 or a.shape[0] < ns or a.shape[0] % ns:
-            raise ValueError(f"recording {r} must be a 1-D array of a whole number (at least 1) of windows of {ns} samples, "
-                             f"got shape {tuple(a.shape)}")
-        arrays.append(np.ascontiguousarray(a, dtype=np.float32))
-        windows.append(a.shape[0] // ns)
-    if not arrays:
-        raise ValueError("sliding_features_from_recordings needs at least one recording")
-    n, w_max = len(arrays), max(windows)
-    windows = np.asarray(windows, dtype=np.int64)
+    arrays, windows = _recording_windows(recordings, fe, "sliding_features_from_recordings")
+    n, w_max = len(arrays), int(windows.max())
     Gt = fe.n_steps // S                                                # segments per audio window
     K, H = int(window_segments), int(hop_segments)
     net.segment_windows(w_max * Gt, K, H)                               # refuse before anything is launched
     valid = windows * Gt
     counts = np.where(valid >= K, (valid - K) // H + 1, 0)
     with torch.cuda.device(net.device):
-        x = torch.from_numpy(np.concatenate(arrays).reshape(-1, ns)).to(net.device)
-        enc = fe.encode(x)                                              # (sum of W_r, C, T), recording-major
-        T = int(enc.shape[2])
-        rec_of = torch.from_numpy(np.repeat(np.arange(n), windows)).to(net.device)
-        win_of = torch.from_numpy(np.concatenate([np.arange(w) for w in windows])).to(net.device)
-        rasters = torch.zeros((n, w_max, fe.n_channels, T), dtype=torch.uint8, device=net.device)
-        rasters[rec_of, win_of] = enc
+        rasters = _scatter_recording_windows(arrays, windows, fe, net)
         state = net.new_state(n)
         records = torch.cat([net.run_stream_records(rasters[:, w].contiguous(), S, segments=np.where(windows > w, Gt, 0),
                                                     state=state)[0] for w in range(w_max)], dim=1)

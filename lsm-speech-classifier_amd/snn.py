@@ -102,6 +102,19 @@ def _dev(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _select_keys(feature_keys):
+    """``(keys, key_ids)``: the names of ``feature_keys`` that are FEATURE_KEYS, in the given order (``None``: all of them),
+    and their ids in the C ABI as an int32 array."""
+    keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
+    return keys, np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+
+
+def _check_stats_out(stats_out, n_clips: int, device) -> None:
+    if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (n_clips, 2)
+                                  or not stats_out.is_contiguous() or stats_out.device != device):
+        raise ValueError(f"stats_out must be a contiguous int32 ({n_clips}, 2) tensor on {device}")
+
+
 def _host(a):
     return C.c_void_p(a.ctypes.data)
 
@@ -182,20 +195,11 @@ class SNN:
         outputs allocated here start as zeros, so rows past a clip's length read as zeros.  Host values outside [0, T]
         raise ``ValueError`` (values of a device tensor are not read back: the kernels clamp them).  With ``state``, a
         clip given fewer than T steps is marked ``state.ended`` and may only be given 0 steps from then on."""
-        if isinstance(spikes, np.ndarray):
-            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
-        spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
-        if packed_time_steps:
-            from .frontend import unpack_raster
-            with torch.cuda.device(self.device):
-                spikes = unpack_raster(spikes, int(packed_time_steps))
-        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
-            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        spikes = self._spikes(spikes, packed_time_steps).to(self.device, dtype=torch.uint8).contiguous()
         B, _, T = spikes.shape
-        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
-        key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+        keys, key_ids = _select_keys(feature_keys)
         ragged = lengths is not None
-        host_lengths = self._host_lengths(lengths, B, T) if ragged else None
+        host_lengths = self._host_counts(lengths, B, T, "lengths") if ragged else None
         if ragged and state is not None and host_lengths is not None and (host_lengths[state.ended] > 0).any():
             raise ValueError(f"clips {np.nonzero(state.ended & (host_lengths > 0))[0].tolist()} have ended (they ran fewer "
                              f"steps than an earlier launch's n_steps) and can only be given 0 steps")
@@ -212,78 +216,99 @@ class SNN:
               if want_spike_matrix else None)
         vt = (alloc((B, T, self.num_neurons), dtype=torch.float32, device=self.device)
               if want_v_trace else None)
-        if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (B, 2)
-                                      or not stats_out.is_contiguous() or stats_out.device != spikes.device):
-            raise ValueError(f"stats_out must be a contiguous int32 ({B}, 2) tensor on {spikes.device}")
-        if longest_first is None:
-            longest_first = self.longest_first_default(B)
-        if state is not None:
-            self._check_state(state, B)
-            if state_out is not None:
-                self._check_state(state_out, B)
-        elif state_out is not None:
-            raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
+        _check_stats_out(stats_out, B, spikes.device)
+        first_step, src, dst = self._continuation(state, state_out, B)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            ws, need = self._order_workspace(B, longest_first)
+            clips = (self._handle, _dev(spikes), B, T)
+            outputs = (_host(key_ids), len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out), int(waves_per_clip))
             if ragged:
-                if isinstance(lengths, torch.Tensor):
-                    steps = lengths.to(self.device, dtype=torch.int32).contiguous()
-                else:
-                    steps = torch.from_numpy(host_lengths.astype(np.int32)).to(self.device)
-                need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
-                ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
-                dst = (state_out or state) if state is not None else None
-                _lib.check(self.lib.lsm_reservoir_run_ragged(
-                    self._handle, _dev(spikes), B, T, _dev(steps), state.steps_done if state is not None else 0,
-                    _dev(state.data) if state is not None else None, _dev(dst.data) if dst is not None else None,
-                    _host(key_ids), len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out), int(waves_per_clip),
-                    _dev(ws), need, stream), "lsm_reservoir_run_ragged")
-                if state is not None:
-                    ended = state.ended | (host_lengths < T) if host_lengths is not None else state.ended.copy()
-                    dst.steps_done = state.steps_done + T
-                    dst.ended = ended
+                steps = self._device_counts(lengths, host_lengths)
+                _lib.check(self.lib.lsm_reservoir_run_ragged(*clips, _dev(steps), first_step, _dev(src), _dev(dst), *outputs,
+                                                             _dev(ws), need, stream), "lsm_reservoir_run_ragged")
             elif state is not None:
-                need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
-                ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
-                _lib.check(self.lib.lsm_reservoir_run_from(
-                    self._handle, _dev(spikes), B, T, state.steps_done, _dev(state.data),
-                    _dev((state_out or state).data),
-                    _host(key_ids), len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out), int(waves_per_clip),
-                    _dev(ws), need, stream), "lsm_reservoir_run_from")
-                (state_out or state).steps_done = state.steps_done + T
-            elif longest_first:
-                # scratch of this call alone: the caching allocator hands a block back to the stream it was taken on
-                need = self.lib.lsm_reservoir_order_workspace(B)
-                ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device)
-                _lib.check(self.lib.lsm_reservoir_run_ordered(
-                    self._handle, _dev(spikes), B, T, _host(key_ids), len(keys), _dev(feats), _dev(sm),
-                    _dev(vt), _dev(stats_out), int(waves_per_clip), _dev(ws), need, stream),
-                    "lsm_reservoir_run_ordered")
+                _lib.check(self.lib.lsm_reservoir_run_from(*clips, first_step, _dev(src), _dev(dst), *outputs,
+                                                           _dev(ws), need, stream), "lsm_reservoir_run_from")
+            elif ws is not None:
+                _lib.check(self.lib.lsm_reservoir_run_ordered(*clips, *outputs, _dev(ws), need, stream),
+                           "lsm_reservoir_run_ordered")
             else:
-                _lib.check(self.lib.lsm_reservoir_run(
-                    self._handle, _dev(spikes), B, T, _host(key_ids), len(keys), _dev(feats), _dev(sm),
-                    _dev(vt), _dev(stats_out), int(waves_per_clip), stream),
-                    "lsm_reservoir_run")
+                _lib.check(self.lib.lsm_reservoir_run(*clips, *outputs, stream), "lsm_reservoir_run")
+        if state is not None:
+            done = state_out or state
+            if ragged:
+                done.ended = state.ended | (host_lengths < T) if host_lengths is not None else state.ended.copy()
+            done.steps_done = state.steps_done + T
         return feats, sm, vt
 
+    # ---- the argument steps the launch methods share ------------------------------------
+    def _spikes(self, spikes, packed_time_steps: int = 0):
+        """A launch's ``spikes`` (tensor, or NumPy: copied) as a (B, C, T) tensor, unpacked on the GPU first when
+        ``packed_time_steps`` says they are bit-packed; another shape is refused.  The caller moves it to the device."""
+        if isinstance(spikes, np.ndarray):
+            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
+        if packed_time_steps:
+            from .frontend import unpack_raster
+            with torch.cuda.device(self.device):
+                spikes = unpack_raster(spikes.to(self.device, dtype=torch.uint8).contiguous(), int(packed_time_steps))
+        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
+            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        return spikes
+
     @staticmethod
-    def _host_lengths(lengths, n_clips: int, n_steps: int):
-        """``run_batch``'s ``lengths`` as an int64 host array, checked against [0, n_steps]; ``None`` for a device tensor
-        (never read back: the kernels clamp its values)."""
-        if isinstance(lengths, torch.Tensor):
-            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n_clips,):
-                raise ValueError(f"lengths must hold {n_clips} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
-            if lengths.is_cuda:
+    def _host_counts(counts, n_clips: int, limit: int, noun: str):
+        """A launch's per-clip ``lengths`` or ``segments`` (``noun``) as an int64 host array, checked against [0, limit];
+        ``None`` for a device tensor (never read back: the kernels clamp its values)."""
+        if isinstance(counts, torch.Tensor):
+            if counts.dtype != torch.int32 or tuple(counts.shape) != (n_clips,):
+                raise ValueError(f"{noun} must hold {n_clips} int32 values, got {counts.dtype} {tuple(counts.shape)}")
+            if counts.is_cuda:
                 return None
-            lengths = lengths.numpy()
-        arr = np.asarray(lengths)
+            counts = counts.numpy()
+        arr = np.asarray(counts)
         if arr.shape != (n_clips,) or not np.issubdtype(arr.dtype, np.integer):
-            raise ValueError(f"lengths must be {n_clips} integers, got {arr.dtype} {arr.shape}")
+            raise ValueError(f"{noun} must be {n_clips} integers, got {arr.dtype} {arr.shape}")
         arr = arr.astype(np.int64)
-        if ((arr < 0) | (arr > n_steps)).any():
-            bad = np.nonzero((arr < 0) | (arr > n_steps))[0]
-            raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {n_steps}]")
+        if ((arr < 0) | (arr > limit)).any():
+            bad = np.nonzero((arr < 0) | (arr > limit))[0]
+            raise ValueError(f"{noun} {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {limit}]")
         return arr
+
+    @staticmethod
+    def _host_segments(segments, n_clips: int, n_segments: int):
+        """``_host_counts`` of a launch's ``segments``: what ``pipeline.StreamBank`` asks of its net."""
+        return SNN._host_counts(segments, n_clips, n_segments, "segments")
+
+    def _device_counts(self, counts, host_counts):
+        """The int32 device tensor of per-clip counts a launch reads: from ``_host_counts``' array, else the caller's device
+        tensor."""
+        if host_counts is None:
+            return counts.to(self.device, dtype=torch.int32).contiguous()
+        return torch.from_numpy(host_counts.astype(np.int32)).to(self.device)
+
+    def _continuation(self, state, state_out, n_clips: int):
+        """``(first_step, state_in, state_out)`` of a launch as tensors: from ``state`` into ``state_out`` or back into
+        ``state``; without ``state`` the launch starts from ``reset()`` and keeps nothing: (0, None, None)."""
+        if state is None:
+            if state_out is not None:
+                raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
+            return 0, None, None
+        self._check_state(state, n_clips)
+        if state_out is not None:
+            self._check_state(state_out, n_clips)
+        return state.steps_done, state.data, (state_out or state).data
+
+    def _order_workspace(self, n_clips: int, longest_first):
+        """``(workspace, bytes)`` of a launch that starts its clips longest first (``longest_first``, ``None``: the default
+        for a batch of this size), else ``(None, 0)``.  Scratch of this call alone: the caching allocator hands a block back
+        to the stream it was taken on."""
+        if longest_first is None:
+            longest_first = self.longest_first_default(n_clips)
+        if not longest_first:
+            return None, 0
+        need = self.lib.lsm_reservoir_order_workspace(n_clips)
+        return torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device), need
 
     # ---- continuation -------------------------------------------------------------------
     def state_bytes(self) -> int:
@@ -329,11 +354,7 @@ class SNN:
         and everything of a clip of length 0, are zeros.
         ``want_state``: return the ``ReservoirState`` after the last launch as a fourth value (each clip's state after its
         own last step)."""
-        if isinstance(spikes, np.ndarray):
-            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
-        spikes = spikes.to(self.device, dtype=torch.uint8)
-        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
-            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        spikes = self._spikes(spikes).to(self.device, dtype=torch.uint8)
         B, _, T = spikes.shape
         if T < 1 or T > MAX_STEPS:
             raise _lib.LsmHipError(f"n_steps = {T} outside [1, {MAX_STEPS}]")
@@ -358,8 +379,8 @@ class SNN:
         B, _, T = spikes.shape
         if isinstance(lengths, torch.Tensor):
             lengths = lengths.cpu().numpy()
-        lengths = self._host_lengths(lengths, B, T)
-        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
+        lengths = self._host_counts(lengths, B, T, "lengths")
+        keys, _ = _select_keys(feature_keys)
         feats = torch.zeros((B, len(keys) * self.num_output_neurons), dtype=torch.float32, device=self.device)
         sm = torch.zeros((B, T, self.num_neurons), dtype=torch.uint8, device=self.device) if want_spike_matrix else None
         vt = torch.zeros((B, T, self.num_neurons), dtype=torch.float32, device=self.device) if want_v_trace else None
@@ -384,41 +405,24 @@ class SNN:
         (B, T // segment_steps, N_out, 4) int32 device tensor of the segments' integer records (times local to the
         segment), the other three are ``run_batch``'s for the same launch (``features`` cumulative, ``None`` without
         ``feature_keys``).  Without ``state`` the launch starts from ``reset()``."""
-        if isinstance(spikes, np.ndarray):
-            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
-        spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
-        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
-            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        spikes = self._spikes(spikes).to(self.device, dtype=torch.uint8).contiguous()
         B, _, T = spikes.shape
         S = int(segment_steps)
         if S < 1 or T % S != 0:
             raise _lib.LsmHipError(f"segment_steps = {S} must be >= 1 and divide the launch's {T} steps")
-        keys = [k for k in (feature_keys or ()) if k in FEATURE_KEYS]
-        key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+        keys, key_ids = _select_keys(feature_keys or ())
         feats = (torch.empty((B, len(keys) * self.num_output_neurons), dtype=torch.float32, device=self.device)
                  if keys else None)
         sm = torch.empty((B, T, self.num_neurons), dtype=torch.uint8, device=self.device) if want_spike_matrix else None
         vt = torch.empty((B, T, self.num_neurons), dtype=torch.float32, device=self.device) if want_v_trace else None
-        if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (B, 2)
-                                      or not stats_out.is_contiguous() or stats_out.device != spikes.device):
-            raise ValueError(f"stats_out must be a contiguous int32 ({B}, 2) tensor on {spikes.device}")
-        if state is not None:
-            self._check_state(state, B)
-            if state_out is not None:
-                self._check_state(state_out, B)
-        elif state_out is not None:
-            raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
-        if longest_first is None:
-            longest_first = self.longest_first_default(B)
+        _check_stats_out(stats_out, B, spikes.device)
+        first_step, src, dst = self._continuation(state, state_out, B)
         records = torch.empty((B, T // S, self.num_output_neurons, 4), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
-            ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
+            ws, need = self._order_workspace(B, longest_first)
             _lib.check(self.lib.lsm_reservoir_run_segments(
-                self._handle, _dev(spikes), B, T, S, state.steps_done if state is not None else 0,
-                _dev(state.data) if state is not None else None,
-                _dev((state_out or state).data) if state is not None else None, _dev(records),
+                self._handle, _dev(spikes), B, T, S, first_step, _dev(src), _dev(dst), _dev(records),
                 _host(key_ids) if keys else None, len(keys), _dev(feats), _dev(sm), _dev(vt), _dev(stats_out),
                 int(waves_per_clip), _dev(ws), need, stream), "lsm_reservoir_run_segments")
         if state is not None:
@@ -426,30 +430,6 @@ class SNN:
         return records, feats, sm, vt
 
     # ---- streams (SPEC.md §4d) ----------------------------------------------------------
-    @staticmethod
-    def _host_segments(segments, n_clips: int, n_segments: int):
-        """``segments`` as an int64 host array, checked against [0, n_segments]; ``None`` for a device tensor (never read
-        back: the kernels clamp its values)."""
-        if isinstance(segments, torch.Tensor):
-            if segments.dtype != torch.int32 or tuple(segments.shape) != (n_clips,):
-                raise ValueError(f"segments must hold {n_clips} int32 values, got {segments.dtype} {tuple(segments.shape)}")
-            if segments.is_cuda:
-                return None
-            segments = segments.numpy()
-        arr = np.asarray(segments)
-        if arr.shape != (n_clips,) or not np.issubdtype(arr.dtype, np.integer):
-            raise ValueError(f"segments must be {n_clips} integers, got {arr.dtype} {arr.shape}")
-        arr = arr.astype(np.int64)
-        if ((arr < 0) | (arr > n_segments)).any():
-            bad = np.nonzero((arr < 0) | (arr > n_segments))[0]
-            raise ValueError(f"segments {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {n_segments}]")
-        return arr
-
-    def _device_segments(self, segments, host_segments):
-        if host_segments is None:
-            return segments.to(self.device, dtype=torch.int32).contiguous()
-        return torch.from_numpy(host_segments.astype(np.int32)).to(self.device)
-
     def run_stream_records(self, spikes, segment_steps: int, segments=None, state: ReservoirState | None = None,
                            state_out: ReservoirState | None = None, want_spike_matrix=False, want_v_trace=False,
                            waves_per_clip: int = 0, stats_out=None, longest_first: bool | None = None):
@@ -464,10 +444,7 @@ class SNN:
         ``ValueError`` (a device tensor is not read back: the kernels clamp).  ``state.data`` is updated in place (or
         ``state_out.data`` written) with its feature-record block zeroed; ``steps_done`` and ``ended`` are not touched -- a
         stream has neither."""
-        if isinstance(spikes, np.ndarray):
-            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
-        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
-            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        spikes = self._spikes(spikes)                   # every refusal below comes before the library or a device is touched
         B, _, T = spikes.shape
         S = int(segment_steps)
         if S < 1 or T < 1 or T % S != 0:
@@ -475,30 +452,18 @@ class SNN:
         G = T // S
         host_segments = self._host_segments(segments, B, G) if segments is not None else None
         spikes = spikes.to(self.device, dtype=torch.uint8).contiguous()
-        if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (B, 2)
-                                      or not stats_out.is_contiguous() or stats_out.device != spikes.device):
-            raise ValueError(f"stats_out must be a contiguous int32 ({B}, 2) tensor on {spikes.device}")
-        if state is not None:
-            self._check_state(state, B)
-            if state_out is not None:
-                self._check_state(state_out, B)
-        elif state_out is not None:
-            raise ValueError("state_out needs state (SNN.new_state(B) is the state after reset())")
-        if longest_first is None:
-            longest_first = self.longest_first_default(B)
+        _check_stats_out(stats_out, B, spikes.device)
+        _, src, dst = self._continuation(state, state_out, B)
         records = torch.zeros((B, G, self.num_output_neurons, 4), dtype=torch.int32, device=self.device)
         sm = torch.zeros((B, T, self.num_neurons), dtype=torch.uint8, device=self.device) if want_spike_matrix else None
         vt = torch.zeros((B, T, self.num_neurons), dtype=torch.float32, device=self.device) if want_v_trace else None
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            counts = self._device_segments(segments, host_segments) if segments is not None else None
-            need = self.lib.lsm_reservoir_order_workspace(B) if longest_first else 0
-            ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=self.device) if longest_first else None
-            dst = (state_out or state) if state is not None else None
+            counts = self._device_counts(segments, host_segments) if segments is not None else None
+            ws, need = self._order_workspace(B, longest_first)
             _lib.check(self.lib.lsm_reservoir_run_stream(
-                self._handle, _dev(spikes), B, T, S, _dev(counts), _dev(state.data) if state is not None else None,
-                _dev(dst.data) if dst is not None else None, _dev(records), _dev(sm), _dev(vt), _dev(stats_out),
-                int(waves_per_clip), _dev(ws), need, stream), "lsm_reservoir_run_stream")
+                self._handle, _dev(spikes), B, T, S, _dev(counts), _dev(src), _dev(dst), _dev(records), _dev(sm), _dev(vt),
+                _dev(stats_out), int(waves_per_clip), _dev(ws), need, stream), "lsm_reservoir_run_stream")
         return records, sm, vt
 
     @staticmethod
@@ -524,8 +489,7 @@ class SNN:
             raise ValueError(f"records must be an int32 (B, G, {self.num_output_neurons}, 4) tensor on {self.device}")
         records = records.contiguous()
         B, G = int(records.shape[0]), int(records.shape[1])
-        keys = FEATURE_KEYS if feature_keys is None else [k for k in feature_keys if k in FEATURE_KEYS]
-        key_ids = np.array([FEATURE_KEYS.index(k) for k in keys], dtype=np.int32)
+        keys, key_ids = _select_keys(feature_keys)
         W = self.segment_windows(G, window_segments, hop_segments)
         shape = (B, W, len(keys) * self.num_output_neurons)
         ragged = segments is not None
@@ -540,7 +504,7 @@ class SNN:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             if ragged:
-                counts = self._device_segments(segments, host_segments)
+                counts = self._device_counts(segments, host_segments)
                 _lib.check(self.lib.lsm_segment_features_ragged(
                     self._handle, _dev(records), B, G, _dev(counts), int(segment_steps), int(window_segments),
                     int(hop_segments), _host(key_ids), len(keys), _dev(feats), stream), "lsm_segment_features_ragged")
@@ -562,11 +526,7 @@ class SNN:
         bit, the feature row of that slice of the spike matrix (``window_segments=1``: one row per segment).  Clips
         longer than ``max_steps`` are cut at segment boundaries into launches that hand their state on.  ``features_out`` /
         ``stats_out``: as ``run_batch``'s (a contiguous (B, W, n_keys*N_out) tensor; the statistics of the run so far)."""
-        if isinstance(spikes, np.ndarray):
-            spikes = torch.from_numpy(np.ascontiguousarray(spikes, dtype=np.uint8))
-        spikes = spikes.to(self.device, dtype=torch.uint8)
-        if spikes.dim() != 3 or spikes.shape[1] != self.n_channels:
-            raise ValueError(f"spikes must be (B, {self.n_channels}, T), got {tuple(spikes.shape)}")
+        spikes = self._spikes(spikes).to(self.device, dtype=torch.uint8)
         B, _, T = spikes.shape
         S = int(segment_steps)
         if S < 1 or T < 1 or T % S != 0:

@@ -152,6 +152,35 @@ def test_run_stream_records_checks_its_arguments_on_the_host():
         net.segment_features(records, 8, segments=(4, 0, 0))
 
 
+def test_launch_methods_keep_their_own_refusals_on_the_host():
+    """What the launch methods' shared argument steps must not blur: the noun in a count's refusal, which exception a bad
+    ``segment_steps`` raises from which method, and the ``state_out`` / ``stats_out`` refusals of all three launch
+    methods -- each before the library is called (``_NoLibrary`` fails the test otherwise)."""
+    import torch
+    from lsm_speech_classifier_amd import _lib
+    net = _net_without_a_gpu()
+    spikes = np.zeros((3, 4, 24), dtype=np.uint8)
+    for lengths in ((25, 0, 0), (0, -1, 0), (1, 2), (1, 2, 3, 0), (1.0, 2.0, 3.0), torch.tensor([1, 2, 3]),
+                    torch.tensor([1, 2], dtype=torch.int32)):
+        with pytest.raises(ValueError, match="lengths"):
+            net.run_batch(spikes, lengths=lengths, longest_first=False)
+    for S in (0, 5, 48):
+        with pytest.raises(_lib.LsmHipError, match="segment_steps"):
+            net.run_segment_records(spikes, S)
+        with pytest.raises(_lib.LsmHipError, match="segment_steps"):
+            net.run_segments(spikes, S)
+        with pytest.raises(ValueError, match="segment_steps"):
+            net.run_stream_records(spikes, S)
+    launches = (lambda **kw: net.run_batch(spikes, longest_first=False, **kw),
+                lambda **kw: net.run_segment_records(spikes, 8, **kw),
+                lambda **kw: net.run_stream_records(spikes, 8, **kw))
+    for launch in launches:
+        with pytest.raises(ValueError, match="state_out needs state"):
+            launch(state_out=object())
+        with pytest.raises(ValueError, match="stats_out must be"):
+            launch(stats_out=torch.zeros((3, 3), dtype=torch.int32))
+
+
 # ---- NumPy restatement: ragged records, merge fold, feature_value ----------------------------------------------------------
 def test_ragged_records_fold_to_the_oracles_rows_on_slices(oracle_c):
     """Per-clip counts: clip b's G_b records are the records of its first G_b * S steps (what it ran), window w < W_b folds
