@@ -14,7 +14,8 @@ SOURCES = ["lsm_api.hip", "frontend.hip", "mel.hip", "reservoir.hip", "lif_varia
            "lif_ring_1.hip", "lif_ring_2.hip", "lif_ring_3.hip", "lif_ring_4.hip",
            "lif_pair_1.hip", "lif_pair_2.hip", "lif_pair_3.hip", "lif_pair_4.hip",
            "lif_pair_wide_1.hip", "lif_pair_wide_2.hip", "lif_pair_wide_3.hip", "lif_pair_wide_4.hip"]
-HEADERS = ["lsm_common.h", "lif_common.h", "lif_kernel.h", "lif_dense.h", "lif_ring.h", "lif_pair.h", "spikes_body.h"]
+HEADERS = ["lsm_common.h", "lif_common.h", "lif_kernel.h", "lif_dense.h", "lif_ring.h", "lif_pair.h", "spikes_body.h",
+           "gammatone_body.h"]
 PUBLIC_HEADERS = ["lsm_hip.h", "lsm_hip_streams.h"]        # include/: the C ABI
 LIB_NAME = "liblsm_hip.so"
 # -ffp-contract=off: the kernels must round every float operation exactly like the CPU oracle.

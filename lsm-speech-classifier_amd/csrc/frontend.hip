@@ -8,6 +8,7 @@
 // with -ffp-contract=off so that results equal the CPU oracle bit for bit (log10 excepted: no
 // two libms agree on its last bit).
 #include "lsm_common.h"
+#include "gammatone_body.h"
 #include "spikes_body.h"
 #include <cstdlib>
 #include <cstring>
@@ -26,12 +27,8 @@ namespace {
 // registers that shift by one at every hop boundary.  Serial in time, parallel over clips x
 // channels: bound by float64 VALU issue (~36 operations per sample), not by memory.
 //
-// Exactness notes.  (1) A2 == 0 for every channel of this filter design, so x*b2 is a signed zero
-// and z1 = x*b2 - y*a2 equals -(y*a2) up to the sign of an exact zero, which can never reach a
-// non-zero value downstream; B2ZERO drops that product.  (2) y/gain is evaluated as
-// q = y*r, q' = fma(fma(-q, gain, y), r, q) with r = RN(1/gain): Markstein's sequence returns the
-// correctly rounded quotient (= the IEEE division the reference performs) unless gain's significand
-// is all ones, which the host checks before choosing this path.
+// The coefficient load, the section step, the quotient by a reciprocal and the exactness notes (B2ZERO, FASTDIV) are in
+// gammatone_body.h.
 // ---------------------------------------------------------------------------------------------
 constexpr int NWIN_MAX = 4;
 constexpr int GT_MAX_WPB = 8;           // waves per workgroup, at most
@@ -57,12 +54,9 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_kernel(
     const int chl = (wid - b * groups) * 64 + (int)(threadIdx.x & 63);
     const bool live = chl < n_filters;
     const int ch = live ? chl : n_filters - 1;
-    const double *k = coefs + (size_t)ch * 10;
-    const double a0 = k[6];
-    const double b0 = k[0] / a0, b2 = k[5] / a0;
-    const double b11 = k[1] / a0, b12 = k[2] / a0, b13 = k[3] / a0, b14 = k[4] / a0;
-    const double a1 = k[7] / a0, a2 = k[8] / a0, gain = k[9];
-    const double rgain = 1.0 / gain;
+    const lsm_gt::Sections s = lsm_gt::load_sections(coefs, ch);
+    const double b0 = s.b0, b2 = s.b2, b11 = s.b1[0], b12 = s.b1[1], b13 = s.b1[2], b14 = s.b1[3];
+    const double a1 = s.a1, a2 = s.a2, gain = s.gain, rgain = s.rgain;
     const float *__restrict__ x = audio + (size_t)b * n_samples;      // wave-uniform
 
     double z01 = 0, z11 = 0, z02 = 0, z12 = 0, z03 = 0, z13 = 0, z04 = 0, z14 = 0;
@@ -72,25 +66,12 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_kernel(
 
     auto filt = [&](float xf) -> double {
         const double x0 = (double)xf;
-        const double y1 = z01 + b0 * x0;
-        z01 = (z11 + x0 * b11) - y1 * a1;
-        z11 = B2ZERO ? -(y1 * a2) : x0 * b2 - y1 * a2;
-        const double y2 = z02 + b0 * y1;
-        z02 = (z12 + y1 * b12) - y2 * a1;
-        z12 = B2ZERO ? -(y2 * a2) : y1 * b2 - y2 * a2;
-        const double y3 = z03 + b0 * y2;
-        z03 = (z13 + y2 * b13) - y3 * a1;
-        z13 = B2ZERO ? -(y3 * a2) : y2 * b2 - y3 * a2;
-        const double y4 = z04 + b0 * y3;
-        z04 = (z14 + y3 * b14) - y4 * a1;
-        z14 = B2ZERO ? -(y4 * a2) : y3 * b2 - y4 * a2;
+        const double y1 = lsm_gt::section<B2ZERO>(z01, b0, x0, z11, b11, a1, a2, b2);
+        const double y2 = lsm_gt::section<B2ZERO>(z02, b0, y1, z12, b12, a1, a2, b2);
+        const double y3 = lsm_gt::section<B2ZERO>(z03, b0, y2, z13, b13, a1, a2, b2);
+        const double y4 = lsm_gt::section<B2ZERO>(z04, b0, y3, z14, b14, a1, a2, b2);
         double o;
-        if (FASTDIV) {
-            const double q0 = y4 * rgain;
-            o = __builtin_fma(__builtin_fma(-q0, gain, y4), rgain, q0);
-        } else {
-            o = y4 / gain;
-        }
+        lsm_gt::quot<FASTDIV>(o, y4, gain, rgain);
         return o * o;
     };
     // samples [n, n_to) with the NACT youngest windows accumulating; the scalar load of the next
@@ -252,12 +233,9 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     for (int q = 0; q < NCH; ++q) {
         const int chl = (g * NCH + q) * CPW + cl;
         live[q] = chl < F;
-        const double *k = a.coefs + (size_t)(live[q] ? chl : F - 1) * 10;
-        const double a0 = k[6];
-        b0[q] = k[0] / a0; b2[q] = k[5] / a0;
-        b11[q] = k[1] / a0; b12[q] = k[2] / a0; b13[q] = k[3] / a0; b14[q] = k[4] / a0;
-        a1[q] = k[7] / a0; a2[q] = k[8] / a0; gain[q] = k[9];
-        rgain[q] = 1.0 / gain[q];
+        const lsm_gt::Sections s = lsm_gt::load_sections(a.coefs, live[q] ? chl : F - 1);
+        b0[q] = s.b0; b2[q] = s.b2; b11[q] = s.b1[0]; b12[q] = s.b1[1]; b13[q] = s.b1[2]; b14[q] = s.b1[3];
+        a1[q] = s.a1; a2[q] = s.a2; gain[q] = s.gain; rgain[q] = s.rgain;
     }
     const float *__restrict__ x = a.audio + (size_t)b * n_samples;        // wave-uniform
 
@@ -280,22 +258,15 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     double u2 = 0.0;
     auto pfilt = [&](double x0) __attribute__((always_inline)) -> double {
         const double u = pair_up(x0, u2);               // head: the next sample; tail: the head's y2 of its sample
-        const double y1 = z01[0] + b0p * u;
-        z01[0] = (z11[0] + u * bp1) - y1 * a1[0];
-        z11[0] = FAST ? -(y1 * a2[0]) : u * b2[0] - y1 * a2[0];
-        const double y2 = z02[0] + b0p * y1;
-        z02[0] = (z12[0] + y1 * bp2) - y2 * a1[0];
-        z12[0] = FAST ? -(y2 * a2[0]) : y1 * b2[0] - y2 * a2[0];
+        const double y1 = lsm_gt::section<FAST>(z01[0], b0p, u, z11[0], bp1, a1[0], a2[0], b2[0]);
+        const double y2 = lsm_gt::section<FAST>(z02[0], b0p, y1, z12[0], bp2, a1[0], a2[0], b2[0]);
         u2 = y2;
         double o;
-        if (FAST) {
-            const double q0 = y2 * rgain[0];
-            o = __builtin_fma(__builtin_fma(-q0, gain[0], y2), rgain[0], q0);
-        } else {
-            o = y2 / gain[0];
-        }
+        lsm_gt::quot<FAST>(o, y2, gain[0], rgain[0]);
         return o * o;
     };
+    // lsm_gt::section four times, written out: called through section() this cascade compiles to other code, whatever the
+    // form of the call (profiles/frontend_shared_filter.txt); the split kernel's cascade and pfilt do call it
     auto filt = [&](int q, double x0, double bx) __attribute__((always_inline)) -> double {
         const double y1 = z01[q] + (SHB0 ? bx : b0[q] * x0);
         z01[q] = (z11[q] + x0 * b11[q]) - y1 * a1[q];
@@ -310,12 +281,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         z04[q] = (z14[q] + y3 * b14[q]) - y4 * a1[q];
         z14[q] = FAST ? -(y4 * a2[q]) : y3 * b2[q] - y4 * a2[q];
         double o;
-        if (FAST) {
-            const double q0 = y4 * rgain[q];
-            o = __builtin_fma(__builtin_fma(-q0, gain[q], y4), rgain[q], q0);
-        } else {
-            o = y4 / gain[q];
-        }
+        lsm_gt::quot<FAST>(o, y4, gain[q], rgain[q]);
         return o * o;
     };
 #define LSM_RUNF(n_to, NACT)                                                        \
@@ -495,12 +461,9 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         constexpr int H = NT <= 4 ? 4 : 8, G = 16 / H;  // = FBH, JPW
         auto norm1 = [&](double v) __attribute__((always_inline)) -> double {
             v = v > fl ? v : fl;
-            const double d = v - lo;
-            if (FD) {
-                const double q0 = d * rden;
-                return __builtin_fma(__builtin_fma(-q0, den, d), rden, q0);
-            }
-            return d / den;
+            double q;
+            lsm_gt::quot<FD>(q, v - lo, den, rden);
+            return q;
         };
         uint32_t act[NCH];
         unsigned long long acc[NCH];
@@ -654,6 +617,16 @@ __global__ __launch_bounds__(64) void encode_kernel(const T *__restrict__ spec, 
     }
 }
 
+// The kernels' threshold tables from the caller's n_thr entries; the entries beyond them take the pad values.
+template <typename T>
+void fill_thresholds(T (&on)[MAX_THR], T (&off)[MAX_THR], const T *thr_on, const T *thr_off, int n_thr, T pad_on, T pad_off)
+{
+    for (int q = 0; q < MAX_THR; ++q) {
+        on[q] = q < n_thr ? thr_on[q] : pad_on;
+        off[q] = q < n_thr ? thr_off[q] : pad_off;
+    }
+}
+
 template <typename T>
 int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, int time_bins,
                           int apply_floor, const T *thr_on, const T *thr_off, int n_thr,
@@ -670,7 +643,7 @@ int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, in
     a.db = db; a.n_clips = n_clips; a.n_filters = n_filters; a.ncols = ncols;
     a.time_bins = time_bins; a.apply_floor = apply_floor; a.n_thr = n_thr;
     a.redundancy = redundancy; a.raster = raster; a.norm_out = norm_out;
-    for (int q = 0; q < MAX_THR; ++q) { a.on[q] = q < n_thr ? thr_on[q] : (T)0; a.off[q] = q < n_thr ? thr_off[q] : (T)0; }
+    fill_thresholds<T>(a.on, a.off, thr_on, thr_off, n_thr, (T)0, (T)0);
     const size_t lds = lsm_fe::spikes_lds_bytes(time_bins, n_thr);
     LSM_REQUIRE(lds <= 160 * 1024, "latch bit rows of %zu bytes (time_bins x thresholds) exceed one CU's LDS", lds);
     auto fn = spec_to_spikes_kernel<T>;
@@ -689,7 +662,7 @@ int launch_encode(const T *spec, int n_rows, int n_bins, const T *thr_on, const 
     if (n_rows == 0) return LSM_OK;
     LSM_REQUIRE(spec && out && thr_on && thr_off, "encode: null buffer");
     SpikeArgs<T> a{};
-    for (int q = 0; q < MAX_THR; ++q) { a.on[q] = q < n_thr ? thr_on[q] : (T)0; a.off[q] = q < n_thr ? thr_off[q] : (T)0; }
+    fill_thresholds<T>(a.on, a.off, thr_on, thr_off, n_thr, (T)0, (T)0);
     hipLaunchKernelGGL(encode_kernel<T>, dim3((n_rows + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        spec, n_rows, n_bins, n_thr, a, out);
     LSM_CHECK_HIP(hipGetLastError());
@@ -768,64 +741,74 @@ static DevInfo dev_info()
 
 #define LSM_API extern "C" __attribute__((visibility("default")))
 
+// tags that pick a kernel instantiation (as pass_a does on the device)
+template <int N> using Int = std::integral_constant<int, N>;
+
+// SPEC.md 1.1: one channel would take NumPy's pairwise window sums in the reference; these kernels sum element by element
+static const char NEED_TWO_FILTERS[] =
+    "the gammatone filterbank needs n_filters >= 2 (one channel: NumPy's pairwise window sums, SPEC.md 1.1)";
+
+// What the filter loop asks of the windows, refused in this order by both gammatone entry points
+static int check_windows(int n_samples, int nwin, int hop, int ncols)
+{
+    LSM_REQUIRE(nwin <= NWIN_MAX * hop, "nwin=%d needs more than %d overlapping windows of hop=%d",
+                nwin, NWIN_MAX, hop);
+    LSM_REQUIRE((long)(ncols - 1) * hop + nwin <= n_samples, "columns exceed the clip");
+    LSM_REQUIRE(n_samples >= 8, "clips shorter than 8 samples are not supported");
+    return LSM_OK;
+}
+
+// CU-exclusive placement for small launches: the dynamic LDS to request for a launch of `n_wgs` workgroups that use
+// `used_bytes` each.  The reservation (half of a CU's LDS plus 1 KB) only caps the dispatcher at ONE gammatone
+// workgroup per CU, so launches that overlap on other streams spread over the free CUs instead of stacking their waves
+// on the SIMDs an earlier launch already occupies (measured at 256 clips x 128 filters, 3 streams: 0.85 -> 0.68 ms per
+// launch, whole pipeline 1.18 -> 0.95 ms).  The other half of the LDS stays free for the reservoir workgroups (21.5 KB
+// each at cfg2; two or three per CU is best).  Launches with more workgroups than CUs need several per CU and get no
+// reservation, nor do those that use more than the reservation themselves.
+static long cu_exclusive_lds(long n_wgs, long used_bytes)
+{
+    const DevInfo di = dev_info();
+    const long resv = di.lds_per_cu / 2 + 1024;
+    if (di.cus > 0 && n_wgs <= di.cus && di.lds_per_cu >= 4096 && resv > used_bytes && resv <= di.lds_per_cu)
+        return resv;
+    return used_bytes;
+}
+
 LSM_API int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_samples,
                                    const double *coefs, int n_filters, int nwin, int hop,
                                    int ncols, double *spec_out, double *db_out, int coef_flags,
                                    void *stream)
 {
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && n_samples >= 1, "bad shape");
-    // SPEC.md 1.1: one channel would take NumPy's pairwise window sums in the reference; these kernels sum element by element
-    LSM_REQUIRE(n_filters >= 2, "the gammatone filterbank needs n_filters >= 2 (one channel: NumPy's pairwise window sums, "
-                "SPEC.md 1.1)");
+    LSM_REQUIRE(n_filters >= 2, "%s", NEED_TWO_FILTERS);
     if (n_clips == 0) return LSM_OK;
     LSM_REQUIRE(audio && coefs, "gammatone: null input");
     LSM_REQUIRE(spec_out || db_out, "gammatone: both outputs null");
     LSM_REQUIRE(nwin >= 1 && hop >= 1 && ncols >= 1, "bad window");
-    LSM_REQUIRE(nwin <= NWIN_MAX * hop, "nwin=%d needs more than %d overlapping windows of hop=%d",
-                nwin, NWIN_MAX, hop);
-    LSM_REQUIRE((long)(ncols - 1) * hop + nwin <= n_samples, "columns exceed the clip");
-    LSM_REQUIRE(n_samples >= 8, "clips shorter than 8 samples are not supported");
-    const long n_waves = (long)((n_filters + 63) / 64) * n_clips;
+    if (const int rc = check_windows(n_samples, nwin, hop, ncols)) return rc;
     constexpr int wpb = 4;
-    // CU-exclusive placement for small launches.  The kernel uses no LDS; the reservation (half of
-    // a CU's LDS plus 1 KB) only caps the dispatcher at ONE gammatone workgroup per CU, so launches
-    // that overlap on other streams spread over the free CUs instead of stacking their waves on the
-    // SIMDs an earlier launch already occupies (measured at 256 clips x 128 filters, 3 streams:
-    // 0.85 -> 0.68 ms per launch, whole pipeline 1.18 -> 0.95 ms).  The other half of the LDS
-    // stays free for the reservoir workgroups (21.5 KB each at cfg2; two or three per CU is best).  Launches with more workgroups than CUs need several
-    // per CU and get no reservation.
-    int lds = 0;
-    {
-        const DevInfo di = dev_info();
-        const long n_wgs = (n_waves + wpb - 1) / wpb;
-        if (di.cus > 0 && n_wgs <= di.cus && di.lds_per_cu >= 4096)
-            lds = (int)(di.lds_per_cu / 2 + 1024);
-    }
-    LSM_REQUIRE((n_waves + wpb - 1) / wpb <= 0x7fffffffL, "too many clips for one launch");
-    const dim3 grid((unsigned)((n_waves + wpb - 1) / wpb)), block((unsigned)(64 * wpb));
+    const long n_wgs = ((long)((n_filters + 63) / 64) * n_clips + wpb - 1) / wpb;
+    const long lds = cu_exclusive_lds(n_wgs, 0);          // the kernel itself uses no LDS
+    LSM_REQUIRE(n_wgs <= 0x7fffffffL, "too many clips for one launch");
+    const dim3 grid((unsigned)n_wgs), block((unsigned)(64 * wpb));
     const bool fast = (coef_flags & 3) == 3;       // both properties verified by the host
     const int nw = (nwin + hop - 1) / hop;
-#define LSM_GT(NW)                                                                            \
-    {                                                                                         \
-        if (lds > 64 * 1024)                                                                  \
-            lsm_allow_big_lds(fast ? reinterpret_cast<const void *>(&gammatone_kernel<NW, true, true>)   \
-                                   : reinterpret_cast<const void *>(&gammatone_kernel<NW, false, false>)); \
-        if (fast)                                                                             \
-            hipLaunchKernelGGL((gammatone_kernel<NW, true, true>), grid, block, lds,          \
-                               (hipStream_t)stream, audio, n_clips, n_samples, coefs,         \
-                               n_filters, nwin, hop, ncols, spec_out, db_out);                \
-        else                                                                                  \
-            hipLaunchKernelGGL((gammatone_kernel<NW, false, false>), grid, block, lds,        \
-                               (hipStream_t)stream, audio, n_clips, n_samples, coefs,         \
-                               n_filters, nwin, hop, ncols, spec_out, db_out);                \
-    }
+    auto launch = [&](auto nw_c, auto fast_c) {
+        constexpr bool FAST = decltype(fast_c)::value;
+        auto fn = gammatone_kernel<decltype(nw_c)::value, FAST, FAST>;
+        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+        hipLaunchKernelGGL(fn, grid, block, (size_t)lds, (hipStream_t)stream, audio, n_clips, n_samples, coefs,
+                           n_filters, nwin, hop, ncols, spec_out, db_out);
+    };
+    auto launch_nw = [&](auto nw_c) {
+        if (fast) launch(nw_c, std::true_type{}); else launch(nw_c, std::false_type{});
+    };
     switch (nw) {
-    case 1: LSM_GT(1) break;
-    case 2: LSM_GT(2) break;
-    case 3: LSM_GT(3) break;
-    default: LSM_GT(4) break;
+    case 1: launch_nw(Int<1>{}); break;
+    case 2: launch_nw(Int<2>{}); break;
+    case 3: launch_nw(Int<3>{}); break;
+    default: launch_nw(Int<4>{}); break;
     }
-#undef LSM_GT
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
@@ -897,14 +880,9 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
 {
     LSM_REQUIRE((launch_flags & ~3) == 0, "launch_flags: only bit 0 (low-latency layout) and bit 1 (no LDS reservation) are defined");
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && n_samples >= 1, "bad shape");
-    // SPEC.md 1.1: one channel would take NumPy's pairwise window sums in the reference; these kernels sum element by element
-    LSM_REQUIRE(n_filters >= 2, "the gammatone filterbank needs n_filters >= 2 (one channel: NumPy's pairwise window sums, "
-                "SPEC.md 1.1)");
+    LSM_REQUIRE(n_filters >= 2, "%s", NEED_TWO_FILTERS);
     LSM_REQUIRE(nwin >= 1 && hop >= 1 && ncols >= 2 && time_bins >= 2, "bad window");
-    LSM_REQUIRE(nwin <= NWIN_MAX * hop, "nwin=%d needs more than %d overlapping windows of hop=%d",
-                nwin, NWIN_MAX, hop);
-    LSM_REQUIRE((long)(ncols - 1) * hop + nwin <= n_samples, "columns exceed the clip");
-    LSM_REQUIRE(n_samples >= 8, "clips shorter than 8 samples are not supported");
+    if (const int rc = check_windows(n_samples, nwin, hop, ncols)) return rc;
     LSM_REQUIRE(n_thr >= 1 && n_thr <= MAX_THR, "n_thr=%d outside [1, %d]", n_thr, MAX_THR);
     LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
     LSM_REQUIRE(thr_on && thr_off, "null threshold table");
@@ -929,61 +907,54 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     a.ncols = ncols; a.time_bins = time_bins; a.n_thr = n_thr; a.redundancy = redundancy; a.groups = pl.groups;
     a.prio = 0;
     // unused table entries never fire: nothing is > +inf or < -inf (the kernel compares 4 or 8 thresholds)
-    for (int q = 0; q < MAX_THR; ++q) { a.on[q] = q < n_thr ? thr_on[q] : INFINITY; a.off[q] = q < n_thr ? thr_off[q] : -INFINITY; }
+    fill_thresholds<double>(a.on, a.off, thr_on, thr_off, n_thr, INFINITY, -INFINITY);
     const long n_waves = (long)pl.groups * n_clips;
     const long n_wgs = (n_waves + pl.wpb - 1) / pl.wpb;
     LSM_REQUIRE(n_wgs <= 0x7fffffffL, "too many clips for one launch");
-    // per lane row: the comparison fields of pass A (4 bins per word up to 4 thresholds, else 2), reused for the raster bits
     // per lane row: the raster bits of the channel (time_bins * n_thr bits), staged for the coalesced write-out
     const int RW = (time_bins * n_thr + 31) / 32;
     long lds = 2 * GT_MAX_WPB * (long)sizeof(double) + (long)pl.wpb * pl.nch * (pl.pair ? 32 : 64) * RW * 4;
     LSM_REQUIRE(lds <= 160 * 1024, "raster stage of %ld bytes exceeds one CU's LDS", lds);
-    // CU-exclusive placement of small launches, as in lsm_gammatone_spec_f64
-    {
-        const DevInfo di = dev_info();
-        const long resv = di.lds_per_cu / 2 + 1024;
-        // launch_flags bit 1: the caller runs LDS-hungry workgroups of another kernel beside this launch (the ring-row
-        // reservoir kernel: 64-74 KB per clip, two per CU) -- no reservation then: the launch asks for what it uses
-        // (27 KB per 4-wave workgroup at 4 thresholds x 100 bins) and fits beside such a pair
-        // The lane pair takes none: its launch already has a wave on every SIMD, and the reservation would only keep the
-        // next step's launch off the CUs until this one has left (cfg2, 4 hardware queues, medians of 3 runs: 1.10 -> 1.00
-        // ms/step at 20 steps, 1.11 -> 0.98 at 200; 12 queues, one run each: 1.03 -> 1.00 and 0.98 -> 0.86;
-        // profiles/r06_lane_pair_placement.txt)
-        if (!pl.pair && !(launch_flags & 2) && di.cus > 0 && n_wgs <= di.cus && di.lds_per_cu >= 4096 && resv > lds &&
-            resv <= di.lds_per_cu)
-            lds = resv;
-    }
+    // CU-exclusive placement of small launches (cu_exclusive_lds), with two exceptions.
+    // launch_flags bit 1: the caller runs LDS-hungry workgroups of another kernel beside this launch (the ring-row
+    // reservoir kernel: 64-74 KB per clip, two per CU) -- no reservation then: the launch asks for what it uses
+    // (27 KB per 4-wave workgroup at 4 thresholds x 100 bins) and fits beside such a pair
+    // The lane pair takes none: its launch already has a wave on every SIMD, and the reservation would only keep the
+    // next step's launch off the CUs until this one has left (cfg2, 4 hardware queues, medians of 3 runs: 1.10 -> 1.00
+    // ms/step at 20 steps, 1.11 -> 0.98 at 200; 12 queues, one run each: 1.03 -> 1.00 and 0.98 -> 0.86;
+    // profiles/r06_lane_pair_placement.txt)
+    if (!pl.pair && !(launch_flags & 2)) lds = cu_exclusive_lds(n_wgs, lds);
     const dim3 grid((unsigned)n_wgs), block((unsigned)(64 * pl.wpb));
     const bool fast = (coef_flags & 3) == 3;
     const bool shb0 = fast && (coef_flags & 4) != 0;       // one b0 for every channel: shared between the two chains,
                                                            // wave-uniform in the lane pair
     const int nw = (nwin + hop - 1) / hop;
-#define LSM_GTF2(NW, FAST, NCH, SHB0, PAIR)                                                   \
-    {                                                                                         \
-        auto fn = gammatone_spikes_kernel<NW, FAST, NCH, SHB0, PAIR>;                         \
-        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));           \
-        hipLaunchKernelGGL(fn, grid, block, (size_t)lds, (hipStream_t)stream, a);             \
-    }
-#define LSM_GTF(NW)                                                                           \
-    {                                                                                         \
-        if (fast) {                                                                           \
-            if (pl.pair) { if (shb0) LSM_GTF2(NW, true, 1, true, true) else LSM_GTF2(NW, true, 1, false, true) } \
-            else if (pl.nch == 2) { if (shb0) LSM_GTF2(NW, true, 2, true, false) else LSM_GTF2(NW, true, 2, false, false) } \
-            else LSM_GTF2(NW, true, 1, false, false)                                          \
-        } else {                                                                              \
-            if (pl.pair) LSM_GTF2(NW, false, 1, false, true)                                  \
-            else if (pl.nch == 2) LSM_GTF2(NW, false, 2, false, false)                        \
-            else LSM_GTF2(NW, false, 1, false, false)                                         \
-        }                                                                                     \
-    }
+    auto launch = [&](auto nw_c, auto fast_c, auto nch_c, auto shb0_c, auto pair_c) {
+        auto fn = gammatone_spikes_kernel<decltype(nw_c)::value, decltype(fast_c)::value, decltype(nch_c)::value,
+                                          decltype(shb0_c)::value, decltype(pair_c)::value>;
+        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+        hipLaunchKernelGGL(fn, grid, block, (size_t)lds, (hipStream_t)stream, a);
+    };
+    // the eight forms of a kernel: the shared b0 exists on the fast path only, and not with one chain per lane
+    auto launch_nw = [&](auto nw_c) {
+        using T = std::true_type;
+        using F = std::false_type;
+        if (fast) {
+            if (pl.pair) { if (shb0) launch(nw_c, T{}, Int<1>{}, T{}, T{}); else launch(nw_c, T{}, Int<1>{}, F{}, T{}); }
+            else if (pl.nch == 2) { if (shb0) launch(nw_c, T{}, Int<2>{}, T{}, F{}); else launch(nw_c, T{}, Int<2>{}, F{}, F{}); }
+            else launch(nw_c, T{}, Int<1>{}, F{}, F{});
+        } else {
+            if (pl.pair) launch(nw_c, F{}, Int<1>{}, F{}, T{});
+            else if (pl.nch == 2) launch(nw_c, F{}, Int<2>{}, F{}, F{});
+            else launch(nw_c, F{}, Int<1>{}, F{}, F{});
+        }
+    };
     switch (nw) {
-    case 1: LSM_GTF(1) break;
-    case 2: LSM_GTF(2) break;
-    case 3: LSM_GTF(3) break;
-    default: LSM_GTF(4) break;
+    case 1: launch_nw(Int<1>{}); break;
+    case 2: launch_nw(Int<2>{}); break;
+    case 3: launch_nw(Int<3>{}); break;
+    default: launch_nw(Int<4>{}); break;
     }
-#undef LSM_GTF
-#undef LSM_GTF2
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
@@ -1020,41 +991,33 @@ LSM_API int lsm_encode_hysteresis_f32(const float *spec, int n_rows, int n_bins,
     return launch_encode<float>(spec, n_rows, n_bins, thr_on, thr_off, n_thr, out, stream);
 }
 
-static int check_bits_args(const void *a, const void *b, const void *raster, long n_rows, int T,
-                           const char *what)
+// Launch of pack_bits_kernel or unpack_bits_kernel (same parameters): `src` -> `dst`, one of which is `raster`.
+static int launch_bits(void (*kernel)(const uint8_t *, long, int, int, uint8_t *), const uint8_t *src, uint8_t *dst,
+                       const uint8_t *raster, long n_rows, int T, const char *what, void *stream)
 {
     LSM_REQUIRE(n_rows >= 0 && T >= 1, "%s: bad shape", what);
-    if (n_rows == 0) return 1;
-    LSM_REQUIRE(a && b, "%s: null buffer", what);
+    if (n_rows == 0) return LSM_OK;                     // nothing to do
+    LSM_REQUIRE(src && dst, "%s: null buffer", what);
     // rows of a multiple of 8 steps move as 64-bit words; other lengths go byte by byte
     LSM_REQUIRE((T & 7) != 0 || ((uintptr_t)raster & 7u) == 0,
                 "%s: the raster must be 8-byte aligned when n_steps is a multiple of 8", what);
-    LSM_REQUIRE(n_rows * (long)((T + 7) / 8) <= 0x7fffffffL * 256L, "%s: too many rows", what);
+    const int TP = (T + 7) / 8;
+    LSM_REQUIRE(n_rows * (long)TP <= 0x7fffffffL * 256L, "%s: too many rows", what);
+    const long n = n_rows * TP;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, n_rows, T, TP,
+                       dst);
+    LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
 
 LSM_API int lsm_raster_pack_bits(const uint8_t *raster, long n_rows, int n_steps, uint8_t *packed,
                                  void *stream)
 {
-    const int rc = check_bits_args(raster, packed, raster, n_rows, n_steps, "pack_bits");
-    if (rc != LSM_OK) return rc == 1 ? LSM_OK : rc;
-    const int TP = (n_steps + 7) / 8;
-    const long n = n_rows * TP;
-    hipLaunchKernelGGL(pack_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, raster, n_rows, n_steps, TP, packed);
-    LSM_CHECK_HIP(hipGetLastError());
-    return LSM_OK;
+    return launch_bits(pack_bits_kernel, raster, packed, raster, n_rows, n_steps, "pack_bits", stream);
 }
 
 LSM_API int lsm_raster_unpack_bits(const uint8_t *packed, long n_rows, int n_steps, uint8_t *raster,
                                    void *stream)
 {
-    const int rc = check_bits_args(packed, raster, raster, n_rows, n_steps, "unpack_bits");
-    if (rc != LSM_OK) return rc == 1 ? LSM_OK : rc;
-    const int TP = (n_steps + 7) / 8;
-    const long n = n_rows * TP;
-    hipLaunchKernelGGL(unpack_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, packed, n_rows, n_steps, TP, raster);
-    LSM_CHECK_HIP(hipGetLastError());
-    return LSM_OK;
+    return launch_bits(unpack_bits_kernel, packed, raster, raster, n_rows, n_steps, "unpack_bits", stream);
 }
