@@ -82,6 +82,16 @@ STREAM_SIGS = {
 }
 STREAM_SYMBOLS = tuple(STREAM_SIGS)
 
+# include/lsm_hip_audio.h (SPEC.md §1.6): the streamed gammatone front end, a table of its own likewise
+c_double = C.c_double
+AUDIO_SIGS = {
+    "lsm_gammatone_stream_state_bytes": (C.c_long, [c_int, c_int, c_int]),
+    "lsm_gammatone_stream_f64": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_void, c_double, c_double,
+                                         c_void, c_void, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_int,
+                                         c_void]),
+}
+AUDIO_SYMBOLS = tuple(AUDIO_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -129,7 +139,7 @@ def load():
         raise LsmHipError(
             f"{path} was built from other sources than this tree's (build id {_build.built_id(path)}, sources "
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
-    for name, (res, args) in list(_SIGS.items()) + list(STREAM_SIGS.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items()):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

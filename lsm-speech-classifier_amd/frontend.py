@@ -307,6 +307,146 @@ class SpikeFrontEnd:
         return raster
 
 
+    def db_range(self, audio):
+        """Calibration range for `GammatoneStream` from a batch of calibration clips (B, n_samples): ``(lo, hi)`` Python
+        floats, the minimum and maximum of the split path's dB values over the whole batch after the 80 dB floor below the
+        maximum (``lo = max(min, hi - 80)``)."""
+        if self.filterbank != "gammatone":
+            raise ValueError("db_range calibrates the streamed gammatone front end; this front end is a mel filterbank")
+        db, _ = self.spectrogram_db(audio)
+        hi = db.max()
+        lo = torch.maximum(db.min(), hi - 80.0)
+        return float(lo), float(hi)
+
+
+# ---- streamed gammatone front end (SPEC.md §1.6, include/lsm_hip_audio.h) ----------------------------------------------
+STREAM_NWIN = 400           # 25 ms at 16 kHz
+STREAM_HOP = 160            # 10 ms: 100 columns per second, one time bin each
+
+
+def _check_stream_strides(nwin: int, hop: int) -> None:
+    if hop < 1 or nwin < hop or nwin > 4 * hop:
+        raise ValueError(f"nwin = {nwin} and hop = {hop}: need hop >= 1 and hop <= nwin <= 4 * hop")
+
+
+def stream_column_plan(seen_hops, new_hops, nwin: int = STREAM_NWIN, hop: int = STREAM_HOP):
+    """The columns one push completes, host integers only.  Column c of a stream covers its samples
+    ``[c * hop, c * hop + nwin)`` counted from the stream's start, and a stream that has seen n whole hops has
+    ``complete(n) = 0 if n * hop < nwin else (n * hop - nwin) // hop + 1`` of them.  A stream that had seen ``seen_hops``
+    hops and receives ``new_hops`` more completes ``complete(seen + new) - complete(seen)`` columns.  Scalars or arrays of
+    equal shape; returns an int or an int64 array."""
+    nwin, hop = int(nwin), int(hop)
+    _check_stream_strides(nwin, hop)
+    seen_a, new_a = np.asarray(seen_hops, dtype=np.int64), np.asarray(new_hops, dtype=np.int64)
+    if (seen_a < 0).any() or (new_a < 0).any():
+        raise ValueError("stream_column_plan: seen_hops and new_hops must be >= 0")
+
+    def complete(n):
+        return np.where(n * hop >= nwin, (n * hop - nwin) // hop + 1, 0)
+
+    cols = complete(seen_a + new_a) - complete(seen_a)
+    return int(cols) if np.ndim(seen_hops) == 0 and np.ndim(new_hops) == 0 else cols
+
+
+class GammatoneStream:
+    """``n_streams`` open-ended audio streams through one gammatone -> dB -> fixed-range normalise -> hysteresis encoder
+    kernel (`lsm_gammatone_stream_f64`, SPEC.md §1.6).  Every ``push`` advances each stream by the whole hops it delivers --
+    any number, 0 included -- from the state the bank holds (filter state, open window sums, latches), and returns the
+    raster columns those hops completed: one time bin per column, normalised with the calibration range ``db_range``
+    (``SpikeFrontEnd.db_range``) fixed for the streams' lives.  A stream cut into pushes at any hop boundaries gives, bit for
+    bit, the raster of its uncut run."""
+    filterbank = "gammatone"
+
+    def __init__(self, n_filters: int, n_streams: int, db_range, thresholds=None, gap: float = HYSTERESIS_GAP,
+                 redundancy: int = REDUNDANCY_FACTOR, device=None, nwin: int = STREAM_NWIN, hop: int = STREAM_HOP):
+        self.n_filters, self.n_streams = int(n_filters), int(n_streams)
+        self.nwin, self.hop, self.redundancy = int(nwin), int(hop), int(redundancy)
+        if self.n_filters < 2:
+            raise ValueError("the gammatone branch needs n_filters >= 2 (SPEC.md 1.1)")
+        if self.n_streams < 1 or self.redundancy < 1:
+            raise ValueError(f"GammatoneStream needs n_streams >= 1 and redundancy >= 1, got {n_streams}, {redundancy}")
+        _check_stream_strides(self.nwin, self.hop)
+        self.db_lo, self.db_hi = (float(v) for v in db_range)
+        if not (np.isfinite(self.db_lo) and np.isfinite(self.db_hi) and self.db_lo < self.db_hi):
+            raise ValueError(f"db_range = ({self.db_lo}, {self.db_hi}) must be finite with lo < hi")
+        self.thresholds = list(SPIKE_THRESHOLDS if thresholds is None else thresholds)
+        self.gap = float(gap)
+        self.on, self.off = threshold_tables(self.thresholds, self.gap, np.float64)
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        tab = gammatone_filter_table(SAMPLE_RATE, self.n_filters, GT_F_MIN)
+        self.coefs = torch.from_numpy(tab).to(self.device)
+        self.coef_flags = coef_flags(tab)
+        self.state_bytes = int(self.lib.lsm_gammatone_stream_state_bytes(self.n_filters, self.nwin, self.hop))
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self.seen = np.zeros(self.n_streams, dtype=np.int64)            # hops since the stream's start
+
+    @property
+    def n_thr(self) -> int:
+        return len(self.on)
+
+    @property
+    def n_channels(self) -> int:
+        return self.n_filters * self.redundancy
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: state block and hop count back to zero."""
+        slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
+        if ((slots < 0) | (slots >= self.n_streams)).any():
+            raise ValueError(f"slots {slots.tolist()} outside [0, {self.n_streams})")
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+        self.seen[slots] = 0
+
+    def _out(self, t, shape, dtype, name):
+        if t is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {self.device}")
+        return t
+
+    def push(self, audio, hops=None, want_db: bool = False, want_spec: bool = False, raster_out=None, db_out=None,
+             spec_out=None):
+        """``audio`` (n_streams, H * hop) float32: stream b's new samples are the first ``hops[b] * hop`` of its row;
+        ``hops``: n_streams host integers in [0, H], or None for H everywhere.  Returns ``(raster, cols)``: ``raster`` uint8
+        (n_streams, C, H * n_thr) on the device and ``cols`` (int64, host) -- the first ``cols[b] * n_thr`` steps of stream
+        b's rows are the columns this push completed (`stream_column_plan`); what lies behind them is zeros, or what a
+        caller-owned ``raster_out`` held.  With ``want_db`` / ``want_spec`` (or caller-owned ``db_out`` / ``spec_out``) the
+        return is ``(raster, cols, db, spec)``: float64 (n_streams, F, H), written like the raster, None where not asked."""
+        if isinstance(audio, np.ndarray):
+            audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+        audio = audio.to(self.device, dtype=torch.float32).contiguous()
+        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % self.hop or audio.shape[1] < self.hop:
+            raise ValueError(f"audio must be ({self.n_streams}, H * {self.hop}) with H >= 1, got {tuple(audio.shape)}")
+        H = int(audio.shape[1]) // self.hop
+        if hops is None:
+            new = np.full(self.n_streams, H, dtype=np.int64)
+        else:
+            new = np.asarray(hops)
+            if new.shape != (self.n_streams,) or new.dtype.kind not in "iu" or (new < 0).any() or (new > H).any():
+                raise ValueError(f"hops must be {self.n_streams} integers in [0, {H}], got {hops!r}")
+            new = new.astype(np.int64)
+        cols = stream_column_plan(self.seen, new, self.nwin, self.hop)
+        with torch.cuda.device(self.device):
+            raster = self._out(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
+            shape = (self.n_streams, self.n_filters, H)
+            db = self._out(db_out, shape, torch.float64, "db_out") if (want_db or db_out is not None) else None
+            spec = self._out(spec_out, shape, torch.float64, "spec_out") if (want_spec or spec_out is not None) else None
+            counts = None if hops is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            _lib.check(self.lib.lsm_gammatone_stream_f64(
+                _dev(audio), self.n_streams, H, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
+                _dev(counts) if counts is not None else None, self.db_lo, self.db_hi, _host(self.on), _host(self.off),
+                self.n_thr, self.redundancy, _dev(self.state), _dev(self.state), _dev(raster),
+                _dev(spec) if spec is not None else None, _dev(db) if db is not None else None, self.coef_flags,
+                torch.cuda.current_stream(self.device).cuda_stream), "lsm_gammatone_stream_f64")
+        self.seen += new
+        if db is not None or spec is not None:
+            return raster, cols, db, spec
+        return raster, cols
+
+
 _FRONT_ENDS: dict = {}
 
 

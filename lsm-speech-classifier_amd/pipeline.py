@@ -572,6 +572,69 @@ class StreamBank:
         return rows, counts
 
 
+class AudioStreamBank:
+    """``StreamBank`` fed with audio: ``gt_stream`` (``frontend.GammatoneStream``) turns every push of whole hops into the
+    raster columns it completed, the bank keeps each stream's columns that do not yet fill a segment (fewer than
+    ``segment_steps / n_thr`` of them) and forwards whole segments to an inner ``StreamBank`` over ``net``.  Both halves
+    continue from saved state, so the rows are those of each stream's one uncut run, audio to features."""
+
+    def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None):
+        # the refusals come before anything touches a device
+        if getattr(gt_stream, "filterbank", None) != "gammatone" or not hasattr(gt_stream, "push"):
+            raise ValueError("AudioStreamBank needs a frontend.GammatoneStream: the mel front end normalises every window by "
+                             "its own maximum and keeps no state between launches, so it cannot be streamed")
+        S, n_thr = int(segment_steps), int(gt_stream.n_thr)
+        if S < 1 or S % n_thr:
+            raise ValueError(f"segment_steps = {segment_steps} must be a positive multiple of the front end's {n_thr} "
+                             f"thresholds: a column is {n_thr} steps and is never split over two segments")
+        stream_window_plan(0, 0, int(window_segments), int(hop_segments))        # hop_segments <= window_segments
+        if net.n_channels != gt_stream.n_channels:
+            raise ValueError(f"the front end has {gt_stream.n_channels} channels, the reservoir {net.n_channels}")
+        self.gt, self.net, self.S, self.n_thr = gt_stream, net, S, n_thr
+        self.n_streams = int(gt_stream.n_streams)
+        self.bank = StreamBank(net, self.n_streams, S, window_segments, hop_segments, feature_keys)
+        self.pending_steps = np.zeros(self.n_streams, dtype=np.int64)    # steps kept in `pending`, left-aligned, < S
+        self.pending = torch.zeros((self.n_streams, S - n_thr, gt_stream.n_channels), dtype=torch.uint8, device=net.device)
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: both halves and the pending columns."""
+        self.gt.reset(slots)
+        self.bank.reset(slots)
+        slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
+        self.pending[torch.from_numpy(slots).to(self.net.device)] = 0
+        self.pending_steps[slots] = 0
+
+    def push(self, audio, hops=None):
+        """``audio`` (n_streams, H * hop) float32 and ``hops`` as ``GammatoneStream.push`` takes them.  Returns
+        ``(rows, counts)`` with ``StreamBank.push``'s meaning: the sliding-window rows this push completed."""
+        S, P = self.S, self.S - self.n_thr
+        raster, cols = self.gt.push(audio, hops)
+        dev = self.net.device
+        total = self.pending_steps + cols * self.n_thr
+        segs = total // S
+        keep = total - segs * S
+        L = int(segs.max()) * S
+        with torch.cuda.device(dev):
+            # time-major: per stream its pending steps, then the new ones, contiguous from step 0
+            both = torch.cat([self.pending, raster.to(dev).transpose(1, 2)], dim=1)
+            rows_of = torch.arange(self.n_streams, device=dev)[:, None]
+            last = both.shape[1] - 1
+
+            def take(first, n):
+                """Steps first[b] .. first[b] + n - 1 of every stream's joined run, (n_streams, n, C)."""
+                j = first[:, None] + np.arange(n, dtype=np.int64)[None, :]
+                src = np.where(j < self.pending_steps[:, None], j, P + j - self.pending_steps[:, None])
+                return both[rows_of, torch.from_numpy(np.clip(src, 0, last)).to(dev)]
+
+            joined = take(np.zeros(self.n_streams, dtype=np.int64), L).transpose(1, 2).contiguous()
+            if P:
+                live = torch.from_numpy(np.arange(P, dtype=np.int64)[None, :] < keep[:, None]).to(dev)
+                kept = take(segs * S, P)
+                self.pending = torch.where(live[:, :, None], kept, torch.zeros_like(kept)).contiguous()
+        self.pending_steps = keep
+        return self.bank.push(joined, segs)
+
+
 def sliding_features_from_recordings(recordings, fe, net, feature_keys, segment_steps: int, window_segments: int,
                                      hop_segments: int = 1):
     """``sliding_features_from_long_audio`` for recordings of different lengths in one batch: ``recordings``, a list of n
