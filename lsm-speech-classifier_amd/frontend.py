@@ -112,6 +112,28 @@ def _host(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
+def indexed_device(device=None) -> torch.device:
+    """``device`` (None = "cuda") with its index: a tensor's device always carries one, ``torch.device("cuda")`` does not,
+    and means whatever device is current when it is used."""
+    d = torch.device(device if device is not None else "cuda")
+    return d if d.index is not None or d.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
+
+
+def as_float32(audio) -> torch.Tensor:
+    """NumPy array (copied) or tensor -> contiguous float32 tensor, on the device it is on."""
+    if isinstance(audio, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    return audio.to(torch.float32).contiguous()
+
+
+def checked_slots(slots, n_streams: int) -> np.ndarray:
+    """The stream slots a ``reset`` names, as an int64 array; refused when one lies outside ``[0, n_streams)``."""
+    slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
+    if ((slots < 0) | (slots >= n_streams)).any():
+        raise ValueError(f"slots {slots.tolist()} outside [0, {n_streams})")
+    return slots
+
+
 class SpikeFrontEnd:
     """Batched filterbank -> dB -> normalise -> resize -> hysteresis encoder on one GPU."""
 
@@ -131,9 +153,7 @@ class SpikeFrontEnd:
                              "--filterbank mel for one filter")
         _lib.require_gpu()
         self.lib = _lib.load()
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type == "cuda" and self.device.index is None:      # pin the device NOW: later calls may
-            self.device = torch.device("cuda", torch.cuda.current_device())   # come under another current device
+        self.device = indexed_device(device)        # pin the device NOW: later calls may come under another current device
         self.n_filters = int(n_filters)
         self.filterbank = filterbank
         self.redundancy = int(redundancy)
@@ -167,10 +187,6 @@ class SpikeFrontEnd:
         """The current stream of THIS front end's device (not of whatever device is current)."""
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _indexed_device(self) -> torch.device:
-        d = self.device                 # pinned by __init__; an instance built without it may still say "cuda"
-        return d if d.index is not None or d.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
-
     def workspace_elems(self, n_clips: int) -> int:
         """float64 elements of the fused launch's scratch for a batch of `n_clips` (0 for the mel branch)."""
         if self.filterbank != "gammatone":
@@ -200,9 +216,7 @@ class SpikeFrontEnd:
         return torch.empty((self.workspace_elems(n_clips),), dtype=torch.float64, device=self.device)
 
     def _audio(self, audio) -> torch.Tensor:
-        if isinstance(audio, np.ndarray):
-            audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-        audio = audio.to(self.device, dtype=torch.float32).contiguous()
+        audio = as_float32(audio).to(self.device)
         if audio.dim() == 1:
             audio = audio[None]
         if audio.shape[1] != self.n_samples:
@@ -232,7 +246,7 @@ class SpikeFrontEnd:
         f64 = db.dtype == torch.float64
         np_dt = np.float64 if f64 else np.float32
         on, off = threshold_tables(self.thresholds, self.gap, np_dt)
-        if db.device != self._indexed_device():
+        if db.device != indexed_device(self.device):      # pinned by __init__; an instance built without it may still say "cuda"
             raise ValueError(f"spectrogram on {db.device}, front end on {self.device}")
         db = db.contiguous()
         with torch.cuda.device(self.device):
@@ -374,9 +388,7 @@ class GammatoneStream:
         self.on, self.off = threshold_tables(self.thresholds, self.gap, np.float64)
         _lib.require_gpu()
         self.lib = _lib.load()
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = indexed_device(device)
         tab = gammatone_filter_table(SAMPLE_RATE, self.n_filters, GT_F_MIN)
         self.coefs = torch.from_numpy(tab).to(self.device)
         self.coef_flags = coef_flags(tab)
@@ -394,9 +406,7 @@ class GammatoneStream:
 
     def reset(self, slots) -> None:
         """The streams in ``slots`` have ended and new ones take their places: state block and hop count back to zero."""
-        slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
-        if ((slots < 0) | (slots >= self.n_streams)).any():
-            raise ValueError(f"slots {slots.tolist()} outside [0, {self.n_streams})")
+        slots = checked_slots(slots, self.n_streams)
         self.state[torch.from_numpy(slots).to(self.device)] = 0
         self.seen[slots] = 0
 
@@ -415,9 +425,7 @@ class GammatoneStream:
         b's rows are the columns this push completed (`stream_column_plan`); what lies behind them is zeros, or what a
         caller-owned ``raster_out`` held.  With ``want_db`` / ``want_spec`` (or caller-owned ``db_out`` / ``spec_out``) the
         return is ``(raster, cols, db, spec)``: float64 (n_streams, F, H), written like the raster, None where not asked."""
-        if isinstance(audio, np.ndarray):
-            audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-        audio = audio.to(self.device, dtype=torch.float32).contiguous()
+        audio = as_float32(audio).to(self.device)
         if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % self.hop or audio.shape[1] < self.hop:
             raise ValueError(f"audio must be ({self.n_streams}, H * {self.hop}) with H >= 1, got {tuple(audio.shape)}")
         H = int(audio.shape[1]) // self.hop

@@ -15,10 +15,10 @@ kernel (a launch that shares the chip with other kernels prefers fewer, fatter w
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
+
+from .frontend import as_float32, checked_slots, indexed_device
 
 DEFAULT_STREAMS = 6
 # front-end streams of their own (0 = rotation: every step keeps to one stream).  Measured at 128 filters / 1000
@@ -27,12 +27,12 @@ DEFAULT_STREAMS = 6
 # streams 0.70 / 0.86-0.90 on the same box -- a rotation stream cannot issue its next front end before its own
 # reservoir kernel has finished; four one-launch front ends (64 workgroups each, one per CU) cover the chip and the
 # fifth is already queued when the first CUs come free.  5 + 6 + the default stream = the 12 hardware queues.
-DEFAULT_FE_STREAMS = int(os.environ.get("LSM_FE_STREAMS", "5"))
+DEFAULT_FE_STREAMS = 5
 DEFAULT_HW_QUEUES = 12
 RASTER_DEPTH = 4                     # raster buffers per front-end stream (two-stage topology)
 # the last batches of a finite list take the low-latency layouts (HotPath.submit(tail=True)); measured at cfg2,
 # 20-step bursts (profiles/r04_tail_steps.txt)
-TAIL_STEPS = int(os.environ.get("LSM_TAIL_STEPS", "2"))
+TAIL_STEPS = 2
 STAGES = ("full", "frontend", "reservoir")
 
 
@@ -48,6 +48,34 @@ def configure_hardware_queues(n: int = DEFAULT_HW_QUEUES) -> int:
     return int(EFFECTIVE_HW_QUEUES)
 
 
+class RasterRing:
+    """What one front-end slot of the two-stage topology owns for batches of `n_clips`: RASTER_DEPTH raster buffers
+    handed round behind events -- a buffer is written again only after the reservoir launch that read it has finished (a
+    GPU-side wait of the front-end stream, never a host wait) -- and the slot's front-end scratch.  Built on the
+    front-end stream, so that the allocator counts the buffers as that stream's."""
+
+    def __init__(self, fe, n_clips: int, device):
+        self.buffers = [torch.empty((n_clips, fe.n_channels, fe.n_steps), dtype=torch.uint8, device=device)
+                        for _ in range(RASTER_DEPTH)]
+        self.free = [None] * RASTER_DEPTH               # per buffer: the event of its last reader
+        self.next = 0
+        self.workspace = fe.new_workspace(n_clips)      # one per front-end stream
+
+    def acquire(self, fe_stream) -> torch.Tensor:
+        """The next buffer, once `fe_stream` has been made to wait for that buffer's last reader."""
+        bi = self.next
+        self.next = (bi + 1) % RASTER_DEPTH
+        if self.free[bi] is not None:
+            fe_stream.wait_event(self.free[bi])
+        return self.buffers[bi]
+
+    def release(self, reader_stream) -> None:
+        """The launch just issued on `reader_stream` is the last reader of the buffer `acquire` handed out last."""
+        bi = (self.next - 1) % RASTER_DEPTH
+        self.free[bi] = torch.cuda.Event()
+        self.free[bi].record(reader_stream)
+
+
 class HotPath:
     """fe: frontend.SpikeFrontEnd, net: snn.SNN (same device).  `streams` = reservoir streams (1 = serial:
     everything on the current stream); `fe_streams` = front-end streams of their own (0 = rotation: a step keeps to
@@ -58,14 +86,12 @@ class HotPath:
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
                  fe_streams: int | None = None, time_segments: int = 1):
-        def norm(d):      # a tensor's device always carries its index, `torch.device("cuda")` does not
-            return d if d.index is not None or d.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
-        if norm(fe.device) != norm(net.device):
+        if indexed_device(fe.device) != indexed_device(net.device):
             raise ValueError(f"front end on {fe.device}, reservoir on {net.device}")
         if fe.n_channels != net.n_channels:
             raise ValueError(f"front end has {fe.n_channels} channels, reservoir expects {net.n_channels}")
         self.fe, self.net = fe, net
-        self.device = norm(fe.device)     # so that a device-resident batch is recognised as such (not copied again)
+        self.device = indexed_device(fe.device)   # so that a device-resident batch is recognised as such (not copied again)
         self.feature_keys = feature_keys
         self.time_segments = int(time_segments)
         if self.time_segments < 1 or fe.n_steps % self.time_segments:
@@ -84,29 +110,18 @@ class HotPath:
             self.streams = ([torch.cuda.Stream(device=self.device) for _ in range(self.n_streams)]
                             if self.n_streams > 1 else [None])
             self.fe_streams = [torch.cuda.Stream(device=self.device) for _ in range(self.n_fe_streams)]
-        # A front end that meets an idle GPU (none of this pipeline's front ends still in flight: the first step
-        # after a synchronisation, or a caller that submits rarely) is launched in the low-latency layout: it is done
-        # after 1.47 instead of 2.43 ms, and -- what matters for a short burst of steps -- the burst's front ends no
-        # longer run in lockstep rounds of four that all end, and all release their reservoir launches, together.
-        self.wide_when_idle = os.environ.get("LSM_FE_WIDE_WHEN_IDLE", "1") != "0"
-        self.tail_lone_layout = os.environ.get("LSM_TAIL_LONE_LAYOUT", "1") != "0"   # diagnostic: tail steps' reservoir layout
-        self._wide_below = int(os.environ.get("LSM_FE_WIDE_BELOW", "1"))     # diagnostic: front ends in flight below which the wide layout goes out
         self._fe_done = []                  # events of the front ends issued, newest last (two-stage topology)
         # Back-pressure: the host enqueues a step in ~0.1 ms, the GPU runs it in ~0.64: without a bound a long run is
         # enqueued thousands of steps ahead and everything a step allocates stays reserved until the GPU gets there
         # (measured before the pipeline owned its raster buffers: 12 GB after 3000 steps).  submit() therefore waits
         # for step s - max_ahead before it issues step s; the GPU keeps max_ahead steps queued, far more than it overlaps.
         self.max_ahead = max(16, 4 * (self.n_streams + self.n_fe_streams))
-        # Two-stage topology: the rasters and the front end's scratch live in buffers the pipeline owns, RASTER_DEPTH
-        # rasters and one scratch per front-end stream, handed round behind events -- a raster buffer is written again
-        # only after the reservoir launch that read it has finished (a GPU-side wait of the front-end stream, never
-        # a host wait).  Allocating them per step from torch's allocator needs the block of step s to stay reserved
-        # until its reservoir launch has finished on ANOTHER stream (`record_stream`): memory then grows with the
-        # steps enqueued ahead and a burst allocates inside the timed path.  Throughput is the same either way
-        # (profiles/r03_pipeline_buffer_pool.txt); the pool makes the steady path free of allocator calls.
-        self.pool = os.environ.get("LSM_HOTPATH_POOL", "1") != "0"
-        self._rasters = {}                  # (front-end slot, batch size) -> [buffers], [events "free again"], next index
-        self._ws = {}                       # (front-end slot, batch size) -> scratch
+        # Two-stage topology: a fused full step's raster and front-end scratch live in buffers the pipeline owns, one
+        # `RasterRing` per front-end stream.  Allocating them per step from torch's allocator needs the block of step s to
+        # stay reserved until its reservoir launch has finished on ANOTHER stream (`record_stream`): memory then grows with
+        # the steps enqueued ahead and a burst allocates inside the timed path.  Throughput is the same either way
+        # (profiles/r03_pipeline_buffer_pool.txt); the rings make the steady path free of allocator calls.
+        self._rasters = {}                  # (front-end slot, batch size) -> RasterRing
         self._in_flight = []                # one event per submitted step, on the stream its last launch went to
         self._step = 0
         self.reservoir_events = []          # (start, end) HIP event pairs, one per submitted step (time_reservoir)
@@ -114,14 +129,15 @@ class HotPath:
 
     # ---- one step ---------------------------------------------------------------------------
     def _one(self, x, stats_out, out, stage, tail=False):
-        if stage == "frontend":
-            return self.fe.encode(x)
         rasters = x if stage == "reservoir" else self.fe.encode(x)
+        if stage == "frontend":
+            return rasters
         if self.time_reservoir:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        # a tail step's reservoir launch meets a draining GPU: the layout of a lone launch (more, thinner waves)
-        wpc = 0 if (tail and self.waves_per_clip == -1 and self.tail_lone_layout) else self.waves_per_clip
+        # a tail step's reservoir launch meets a draining GPU: the layout of a lone launch (more, thinner waves) when the
+        # choice is the library's (profiles/r04_tail_steps.txt)
+        wpc = 0 if (tail and self.waves_per_clip == -1) else self.waves_per_clip
         if self.time_segments > 1:
             K, B = self.time_segments, int(rasters.shape[0])
             feats = self.net.run_segments(rasters, int(rasters.shape[2]) // K, self.feature_keys, waves_per_clip=wpc,
@@ -166,90 +182,90 @@ class HotPath:
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
         slot = self._step % self.n_streams
-        st = self.streams[slot]
         self._step += 1
         while len(self._in_flight) >= self.max_ahead:
             self._in_flight.pop(0).synchronize()
+        if self.n_streams == 1:
+            topology = self._submit_serial
+        elif self.n_fe_streams and stage != "reservoir":
+            topology = self._submit_two_stages
+        else:
+            topology = self._submit_rotation
+        return topology(slot, audio, stats_out, after, out, stage, tail)
+
+    def _wait_for_input(self, stream, cur, audio, after) -> None:
+        """The ordering of a device input (`submit`): `stream` waits for `after`, or for what `cur` has issued so far."""
+        if after is not None:
+            stream.wait_event(after)
+        elif torch.is_tensor(audio) and audio.device == self.device:
+            stream.wait_stream(cur)
+
+    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail):
+        """Everything on the current stream."""
         cur = torch.cuda.current_stream(self.device)
-        on_device = torch.is_tensor(audio) and audio.device == self.device
-        if st is None:
-            if after is not None:
-                cur.wait_event(after)
-            with torch.cuda.device(self.device):
-                x = audio if stage == "reservoir" else self._to_device(audio, slot)
-                return self._one(x, stats_out, out, stage, tail), cur
-        if self.n_fe_streams and stage != "reservoir":
-            # two stages: front end on its own stream, the reservoir launch behind an event on another
-            fslot = (self._step - 1) % self.n_fe_streams
-            fst = self.fe_streams[fslot]
-            with torch.cuda.device(self.device):
-                with torch.cuda.stream(fst):
-                    if after is not None:
-                        fst.wait_event(after)
-                    elif on_device:
-                        fst.wait_stream(cur)
-                    self._fe_done = [ev for ev in self._fe_done[-8:] if not ev.query()]
-                    # the front end's own decision (mel branch, > 1024 filters and LSM_FRONTEND_SPLIT=1 take the split
-                    # route, which allocates its raster on the front-end stream): only the fused launch writes
-                    # into the pipeline's rings, everything else goes through record_stream below
-                    fuses = bool(getattr(self.fe, "will_fuse", lambda: False)())
-                    idle = fuses and ((self.wide_when_idle and len(self._fe_done) < self._wide_below) or tail)
-                    x = self._to_device(audio, ("fe", fslot))
-                    pooled = self.pool and stage == "full" and fuses
-                    if pooled:
-                        key = (fslot, int(x.shape[0]))
-                        ring = self._rasters.get(key)
-                        if ring is None:
-                            ring = self._rasters[key] = [
-                                [torch.empty((x.shape[0], self.fe.n_channels, self.fe.n_steps), dtype=torch.uint8,
-                                             device=self.device) for _ in range(RASTER_DEPTH)],
-                                [None] * RASTER_DEPTH, 0]
-                            self._ws[key] = self.fe.new_workspace(x.shape[0])        # one per front-end stream
-                        bi = ring[2]
-                        ring[2] = (bi + 1) % RASTER_DEPTH
-                        if ring[1][bi] is not None:
-                            fst.wait_event(ring[1][bi])          # its last reader (a reservoir launch) has finished
-                        gt = self.fe.filterbank == "gammatone"
-                        rasters = self.fe.encode(x, low_latency=idle and gt, raster_out=ring[0][bi], workspace=self._ws[key],
-                                                 share_lds=gt and self._share_lds(int(x.shape[0])))
-                    else:
-                        lowlat = idle and getattr(self.fe, "filterbank", "") == "gammatone"
-                        rasters = self.fe.encode(x, low_latency=True) if lowlat else self.fe.encode(x)
-                        pooled = False
-                    done = torch.cuda.Event()
-                    done.record(fst)
-                    self._fe_done.append(done)
-                    if stage == "frontend":
-                        return rasters, fst
-                if not pooled:
-                    rasters.record_stream(st)      # allocated on the front-end stream, read on the reservoir stream
-                with torch.cuda.stream(st):
-                    st.wait_event(done)
-                    feats = self._one(rasters, stats_out, out, "reservoir", tail)
-                    if pooled:
-                        free = torch.cuda.Event()
-                        free.record(st)
-                        ring[1][bi] = free
-                    return feats, st
+        if after is not None:
+            cur.wait_event(after)
+        with torch.cuda.device(self.device):
+            x = audio if stage == "reservoir" else self._to_device(audio, slot)
+            return self._one(x, stats_out, out, stage, tail), cur
+
+    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail):
+        """The step keeps to reservoir stream `slot`: its front end, then its reservoir launch."""
+        st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
-            if after is not None:
-                st.wait_event(after)
-            elif on_device:
-                st.wait_stream(cur)
+            self._wait_for_input(st, cur, audio, after)
             x = audio if stage == "reservoir" else self._to_device(audio, slot)
             return self._one(x, stats_out, out, stage, tail), st
 
-    def _share_lds(self, n_clips: int) -> bool:
-        """Whether the fused front end gives up its LDS reservation (`encode(share_lds=True)`).  Measured and NOT taken by
-        default: beside the ring-row kernel at 4000 neurons (64 KB per clip, two per CU; the front end needs 27 KB per
-        workgroup since round 4) the whole path runs 6.37-6.40 ms per step without the reservation against 6.26-6.28 with
-        it -- without it the dispatcher stacks several front-end workgroups on one CU
-        (profiles/r04_cfg4_frontend_lds_placement.txt).  LSM_FE_SHARE_LDS=1 switches it on for A/B runs."""
-        return os.environ.get("LSM_FE_SHARE_LDS") == "1"
+    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail):
+        """The front end on the next front-end stream, the reservoir launch on reservoir stream `slot` behind an event."""
+        fslot = (self._step - 1) % self.n_fe_streams
+        st, fst, cur = self.streams[slot], self.fe_streams[fslot], torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            with torch.cuda.stream(fst):
+                self._wait_for_input(fst, cur, audio, after)
+                low_latency = self._low_latency(tail)
+                x = self._to_device(audio, ("fe", fslot))
+                # the front end's own decision (mel branch, > 1024 filters and LSM_FRONTEND_SPLIT=1 take the split
+                # route, which allocates its raster on the front-end stream): only the fused launch of a full step
+                # writes into the pipeline's rings, everything else goes through record_stream below (ADVICE r3)
+                ring, owned = None, {}
+                if stage == "full" and self.fe.will_fuse():
+                    key = (fslot, int(x.shape[0]))
+                    ring = self._rasters.get(key)
+                    if ring is None:
+                        ring = self._rasters[key] = RasterRing(self.fe, key[1], self.device)
+                    owned = dict(raster_out=ring.acquire(fst), workspace=ring.workspace)
+                # `share_lds` stays off: beside the ring-row kernel at 4000 neurons (64 KB of LDS per clip, two per CU)
+                # the whole path runs 6.37-6.40 ms per step without the front end's LDS reservation against 6.26-6.28
+                # with it (profiles/r04_cfg4_frontend_lds_placement.txt)
+                rasters = self.fe.encode(x, low_latency=low_latency, **owned)
+                done = torch.cuda.Event()
+                done.record(fst)
+                self._fe_done.append(done)
+                if stage == "frontend":
+                    return rasters, fst
+            if ring is None:
+                rasters.record_stream(st)      # allocated on the front-end stream, read on the reservoir stream
+            with torch.cuda.stream(st):
+                st.wait_event(done)
+                feats = self._one(rasters, stats_out, out, "reservoir", tail)
+                if ring is not None:
+                    ring.release(st)
+                return feats, st
+
+    def _low_latency(self, tail: bool) -> bool:
+        """Whether this step's fused gammatone front end goes out in the low-latency layout: on a tail step, and when it
+        meets an idle GPU -- none of this pipeline's front ends still in flight: the first step after a synchronisation,
+        or a caller that submits rarely.  It is then done after 1.47 instead of 2.43 ms, and -- what matters for a short
+        burst of steps -- the burst's front ends no longer run in lockstep rounds of four that all end, and all release
+        their reservoir launches, together (profiles/r03_low_latency_layout_when_idle.txt)."""
+        self._fe_done = [ev for ev in self._fe_done[-8:] if not ev.query()]
+        return self.fe.filterbank == "gammatone" and self.fe.will_fuse() and (tail or not self._fe_done)
 
     def _to_device(self, audio, slot):
         if isinstance(audio, np.ndarray):
-            audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+            audio = as_float32(audio)
         if audio.device == self.device:
             return audio
         # host batch: asynchronous copy on the step's stream into this rotation slot's own buffer
@@ -357,8 +373,7 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
 
 def _audio_windows(audio, fe):
     """``audio`` (n, W * fe.n_samples) float32, tensor or NumPy (copied), checked: ``(audio tensor, n, W)``."""
-    if isinstance(audio, np.ndarray):
-        audio = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    audio = as_float32(audio)
     ns = int(fe.n_samples)
     if audio.dim() != 2 or audio.shape[1] < ns or audio.shape[1] % ns:
         raise ValueError(f"audio must be (n, W * {ns}), got {tuple(audio.shape)}")
@@ -368,7 +383,7 @@ def _audio_windows(audio, fe):
 def _encode_audio_windows(audio, n: int, W: int, fe, net):
     """The rasters (n, W, C, T) of ``_audio_windows``' audio: the front end runs on the n * W windows as independent clips.
     Called on ``net.device``."""
-    x = audio.to(net.device, dtype=torch.float32).reshape(n * W, int(fe.n_samples)).contiguous()
+    x = audio.to(net.device).reshape(n * W, int(fe.n_samples))
     return fe.encode(x).reshape(n, W, fe.n_channels, -1)
 
 
@@ -464,6 +479,13 @@ def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps
 
 
 # ---- open-ended streams (SPEC.md §4d) -------------------------------------------------------------------------------------
+def completed_windows(n_segments, window_segments: int, hop_segments: int):
+    """How many windows ``[w * H, w * H + K)`` lie wholly inside the first ``n_segments`` segments (an int or an array of
+    them): none below K, then one more every H segments."""
+    K, H = int(window_segments), int(hop_segments)
+    return np.where(n_segments >= K, (n_segments - K) // H + 1, 0)
+
+
 def stream_window_plan(seen, new, window_segments: int, hop_segments: int = 1):
     """The bookkeeping of one push into a stream, host integers only.  Window w of a stream covers its segments
     ``[w * H, w * H + K)`` counted from the stream's start, and is complete once the stream has seen ``w * H + K`` segments.
@@ -477,16 +499,50 @@ def stream_window_plan(seen, new, window_segments: int, hop_segments: int = 1):
     seen_a, new_a = np.asarray(seen, dtype=np.int64), np.asarray(new, dtype=np.int64)
     if (seen_a < 0).any() or (new_a < 0).any():
         raise ValueError("stream_window_plan: seen and new must be >= 0")
-
-    def complete(n):
-        return np.where(n >= K, (n - K) // H + 1, 0)
-
     total = seen_a + new_a
-    n_windows = complete(total) - complete(seen_a)
-    keep = total - complete(total) * H              # 0 <= keep <= K - 1 for H <= K
+    n_windows = completed_windows(total, K, H) - completed_windows(seen_a, K, H)
+    keep = total - completed_windows(total, K, H) * H              # 0 <= keep <= K - 1 for H <= K
     if np.ndim(seen) == 0 and np.ndim(new) == 0:
         return int(n_windows), int(keep)
     return n_windows, keep
+
+
+class CarryBuffer:
+    """What ``n_streams`` streams carry from one push to the next: per stream up to ``cap`` trailing items (records, raster
+    steps -- tensors of shape ``item``) in ``kept`` (n_streams, cap, *item), left-aligned and zero-padded, and how many of
+    them, in the host array ``count``.  A push first joins the kept items with the new ones into one run per stream, then
+    keeps the tail of that run.  Lives on ``device``, CPU included; ``cap`` may be 0."""
+
+    def __init__(self, n_streams: int, cap: int, item, dtype, device):
+        self.kept = torch.zeros((n_streams, cap, *item), dtype=dtype, device=device)
+        self.count = np.zeros(n_streams, dtype=np.int64)
+
+    def _gather(self, run, src):
+        """``run[b, src[b, j]]`` with the indices clipped to the run's width: (n_streams, src.shape[1], *item)."""
+        src = torch.from_numpy(np.clip(src, 0, max(run.shape[1] - 1, 0))).to(run.device)
+        return run[torch.arange(run.shape[0], device=run.device)[:, None], src]
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` (an int64 array) carry nothing any more."""
+        self.kept[torch.from_numpy(slots).to(self.kept.device)] = 0
+        self.count[slots] = 0
+
+    def join(self, new, counts):
+        """``new`` (n_streams, G, *item): stream b delivers its first ``counts[b]`` items.  Returns ``(run, have)``: ``run``
+        (n_streams, cap + G, *item) holds per stream its kept items, then the new ones, contiguous from position 0;
+        ``have = count + counts`` of them are valid, what lies behind is never to be read."""
+        cap = self.kept.shape[1]
+        j = np.arange(cap + new.shape[1], dtype=np.int64)[None, :]
+        src = np.where(j < self.count[:, None], j, cap + j - self.count[:, None])
+        return self._gather(torch.cat([self.kept, new], dim=1), src).contiguous(), self.count + counts
+
+    def keep(self, run, have, keep) -> None:
+        """The last ``keep[b] <= cap`` of the ``have[b]`` items of ``join``'s ``run`` are what stream b carries on."""
+        j = np.arange(self.kept.shape[1], dtype=np.int64)[None, :]
+        kept = self._gather(run, (have - keep)[:, None] + j)
+        live = torch.from_numpy(j < keep[:, None]).to(run.device).reshape(kept.shape[:2] + (1,) * (kept.dim() - 2))
+        self.kept = torch.where(live, kept, torch.zeros_like(kept)).contiguous()
+        self.count = np.array(keep, dtype=np.int64)
 
 
 class StreamBank:
@@ -511,20 +567,19 @@ class StreamBank:
         self.feature_keys = feature_keys
         self.state = net.new_state(self.n_streams)
         self.seen = np.zeros(self.n_streams, dtype=np.int64)             # segments since the stream's start
-        self.tail_count = np.zeros(self.n_streams, dtype=np.int64)       # records kept in `tail`, left-aligned
-        self.tail = torch.zeros((self.n_streams, self.K - 1, net.num_output_neurons, 4), dtype=torch.int32,
-                                device=net.device)
+        self.tail = CarryBuffer(self.n_streams, self.K - 1, (net.num_output_neurons, 4), torch.int32, net.device)
+
+    @property
+    def tail_count(self) -> np.ndarray:
+        """Records kept per stream for the windows still open."""
+        return self.tail.count
 
     def reset(self, slots) -> None:
         """The streams in ``slots`` have ended and new ones take their places: state block, tail and count back to zero."""
-        slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
-        if ((slots < 0) | (slots >= self.n_streams)).any():
-            raise ValueError(f"slots {slots.tolist()} outside [0, {self.n_streams})")
-        idx = torch.from_numpy(slots).to(self.net.device)
-        self.state.data[idx] = 0
-        self.tail[idx] = 0
+        slots = checked_slots(slots, self.n_streams)
+        self.state.data[torch.from_numpy(slots).to(self.net.device)] = 0
+        self.tail.reset(slots)
         self.seen[slots] = 0
-        self.tail_count[slots] = 0
 
     def push(self, rasters, segments):
         """``rasters`` (n_streams, C, G * S) uint8: stream b's new steps are the first ``segments[b] * S`` columns of its
@@ -554,21 +609,10 @@ class StreamBank:
                 rec, _, _ = net.run_stream_records(rasters[:, :, t0:t0 + n], S, segments=steps // S, state=self.state)
                 fresh[:, t0 // S:(t0 + n) // S] = rec
             # per stream: its kept records, then the new ones, contiguous from column 0 (the start of its next window)
-            have = self.tail_count + new
-            both = torch.cat([self.tail, fresh], dim=1)
-            j = np.arange(K - 1 + Gp, dtype=np.int64)[None, :]
-            src = np.where(j < self.tail_count[:, None], j, np.minimum(K - 1 + j - self.tail_count[:, None], K - 2 + Gp))
-            rows_of = torch.arange(self.n_streams, device=net.device)[:, None]
-            joined = both[rows_of, torch.from_numpy(src).to(net.device)].contiguous()
+            joined, have = self.tail.join(fresh, new)
             rows = net.segment_features(joined, S, self.feature_keys, K, H, segments=have)
-            if K > 1:
-                jk = np.arange(K - 1, dtype=np.int64)[None, :]
-                src = np.clip(have[:, None] - keep[:, None] + jk, 0, K - 2 + Gp)
-                kept = joined[rows_of, torch.from_numpy(src).to(net.device)]
-                live = torch.from_numpy(jk < keep[:, None]).to(net.device)
-                self.tail = torch.where(live[:, :, None, None], kept, torch.zeros_like(kept)).contiguous()
+            self.tail.keep(joined, have, keep)
         self.seen += new
-        self.tail_count = keep.copy()
         return rows, counts
 
 
@@ -593,45 +637,32 @@ class AudioStreamBank:
         self.gt, self.net, self.S, self.n_thr = gt_stream, net, S, n_thr
         self.n_streams = int(gt_stream.n_streams)
         self.bank = StreamBank(net, self.n_streams, S, window_segments, hop_segments, feature_keys)
-        self.pending_steps = np.zeros(self.n_streams, dtype=np.int64)    # steps kept in `pending`, left-aligned, < S
-        self.pending = torch.zeros((self.n_streams, S - n_thr, gt_stream.n_channels), dtype=torch.uint8, device=net.device)
+        # time-major: an item is one raster step, (C,)
+        self.pending = CarryBuffer(self.n_streams, S - n_thr, (gt_stream.n_channels,), torch.uint8, net.device)
+
+    @property
+    def pending_steps(self) -> np.ndarray:
+        """Raster steps kept per stream that do not yet fill a segment (fewer than ``segment_steps``)."""
+        return self.pending.count
 
     def reset(self, slots) -> None:
         """The streams in ``slots`` have ended and new ones take their places: both halves and the pending columns."""
         self.gt.reset(slots)
         self.bank.reset(slots)
-        slots = np.atleast_1d(np.asarray(slots, dtype=np.int64))
-        self.pending[torch.from_numpy(slots).to(self.net.device)] = 0
-        self.pending_steps[slots] = 0
+        self.pending.reset(checked_slots(slots, self.n_streams))
 
     def push(self, audio, hops=None):
         """``audio`` (n_streams, H * hop) float32 and ``hops`` as ``GammatoneStream.push`` takes them.  Returns
         ``(rows, counts)`` with ``StreamBank.push``'s meaning: the sliding-window rows this push completed."""
-        S, P = self.S, self.S - self.n_thr
+        S = self.S
         raster, cols = self.gt.push(audio, hops)
         dev = self.net.device
-        total = self.pending_steps + cols * self.n_thr
-        segs = total // S
-        keep = total - segs * S
-        L = int(segs.max()) * S
         with torch.cuda.device(dev):
-            # time-major: per stream its pending steps, then the new ones, contiguous from step 0
-            both = torch.cat([self.pending, raster.to(dev).transpose(1, 2)], dim=1)
-            rows_of = torch.arange(self.n_streams, device=dev)[:, None]
-            last = both.shape[1] - 1
-
-            def take(first, n):
-                """Steps first[b] .. first[b] + n - 1 of every stream's joined run, (n_streams, n, C)."""
-                j = first[:, None] + np.arange(n, dtype=np.int64)[None, :]
-                src = np.where(j < self.pending_steps[:, None], j, P + j - self.pending_steps[:, None])
-                return both[rows_of, torch.from_numpy(np.clip(src, 0, last)).to(dev)]
-
-            joined = take(np.zeros(self.n_streams, dtype=np.int64), L).transpose(1, 2).contiguous()
-            if P:
-                live = torch.from_numpy(np.arange(P, dtype=np.int64)[None, :] < keep[:, None]).to(dev)
-                kept = take(segs * S, P)
-                self.pending = torch.where(live[:, :, None], kept, torch.zeros_like(kept)).contiguous()
-        self.pending_steps = keep
+            # per stream its pending steps, then the new ones, contiguous from step 0; whole segments go on
+            run, total = self.pending.join(raster.to(dev).transpose(1, 2), cols * self.n_thr)
+            segs = total // S
+            self.pending.keep(run, total, total - segs * S)
+            joined = run[:, :int(segs.max()) * S].transpose(1, 2).contiguous()
         return self.bank.push(joined, segs)
 
 
@@ -652,7 +683,7 @@ def sliding_features_from_recordings(recordings, fe, net, feature_keys, segment_
     K, H = int(window_segments), int(hop_segments)
     net.segment_windows(w_max * Gt, K, H)                               # refuse before anything is launched
     valid = windows * Gt
-    counts = np.where(valid >= K, (valid - K) // H + 1, 0)
+    counts = completed_windows(valid, K, H)
     with torch.cuda.device(net.device):
         rasters = _scatter_recording_windows(arrays, windows, fe, net)
         state = net.new_state(n)

@@ -71,6 +71,77 @@ def test_run_gives_the_last_batches_of_a_finite_list_the_low_latency_layouts():
     assert seen_fe[1:-n].count(True) <= 1 and set(seen_wpc[:-n]) == {-1}
 
 
+def test_every_launch_of_a_step_lands_on_its_stream_with_its_buffers():
+    """The launch trace of 19 steps of distinct audio in the three stream topologies: which stream each front end and each
+    reservoir launch goes to, which pipeline-owned raster and workspace the front end writes, that the reservoir launch
+    reads exactly that raster, and the layout hint.  Every step's rows equal the serial path's bit for bit, so a raster
+    buffer written again before its reader had finished would show."""
+    import torch
+    from lsm_speech_classifier_amd import frontend, pipeline, reservoir as R, snn, synth
+    n_steps, depth = 19, pipeline.RASTER_DEPTH
+    fe = frontend.SpikeFrontEnd(64, "gammatone")
+    net = snn.SNN(R.SimulationParams(num_neurons=256, num_output_neurons=32, small_world_graph_k=16, mean_weight=0.02),
+                  n_channels=64)
+    batches = [torch.from_numpy(synth.class_chirps([s % 12, (s + 5) % 12, (s + 7) % 12], seed=300 + s)).cuda()
+               for s in range(n_steps)]
+    want = torch.cat([net.run_batch(fe.encode(b), KEYS)[0] for b in batches])
+    assert len({want[3 * s:3 * s + 3].cpu().numpy().tobytes() for s in range(n_steps)}) == n_steps     # distinct steps
+    torch.cuda.synchronize()
+    real_encode, real_run = fe.encode, net.run_batch
+
+    def trace(hp):
+        fes, res = [], []
+
+        def encode(x, **kw):
+            out = real_encode(x, **kw)
+            fes.append((torch.cuda.current_stream(hp.device), kw.get("raster_out"), kw.get("workspace"), out))
+            return out
+
+        def run_batch(r, keys=None, **kw):
+            res.append((torch.cuda.current_stream(hp.device), r.data_ptr(), kw.get("waves_per_clip")))
+            return real_run(r, keys, **kw)
+
+        fe.encode, net.run_batch = encode, run_batch
+        try:
+            got = hp.run(batches)
+        finally:
+            fe.encode, net.run_batch = real_encode, real_run
+        assert torch.equal(got, want)
+        assert len(fes) == len(res) == n_steps
+        for s in range(n_steps):
+            assert res[s][1] == fes[s][3].data_ptr(), s                   # the reservoir launch reads this step's raster
+        return fes, res
+
+    # two stages: front ends on streams of their own, rasters from the rings, reservoir launches behind events
+    hp = pipeline.HotPath(fe, net, KEYS, streams=3, fe_streams=2)
+    fes, res = trace(hp)
+    tail = pipeline.TAIL_STEPS
+    for s in range(n_steps):
+        st, raster_out, ws, out = fes[s]
+        assert st == hp.fe_streams[s % 2] and out is raster_out and raster_out is not None, s
+        assert ws is fes[s % 2][2] and ws is not None, s                  # one workspace per front-end slot
+        for back in range(1, depth):
+            assert s < 2 * back or raster_out is not fes[s - 2 * back][1], (s, back)
+        assert s < 2 * depth or raster_out is fes[s - 2 * depth][1], s
+        assert res[s][0] == hp.streams[s % 3], s
+        assert res[s][2] == (0 if s >= n_steps - tail else -1), s
+    assert fes[0][2] is not fes[1][2]
+    # rotation: a step keeps to one stream, rasters from the allocator
+    hp = pipeline.HotPath(fe, net, KEYS, streams=3, fe_streams=0)
+    fes, res = trace(hp)
+    for s in range(n_steps):
+        assert fes[s][0] == hp.streams[s % 3] and res[s][0] == hp.streams[s % 3], s
+        assert fes[s][1] is None and fes[s][2] is None, s
+        assert res[s][2] == (0 if s >= n_steps - tail else -1), s
+    # serial: everything on the current stream
+    hp = pipeline.HotPath(fe, net, KEYS, streams=1)
+    cur = torch.cuda.current_stream(hp.device)
+    fes, res = trace(hp)
+    for s in range(n_steps):
+        assert fes[s][0] == cur and res[s][0] == cur and fes[s][1] is None, s
+        assert res[s][2] == 0, s
+
+
 def test_in_memory_route_writes_the_same_file_2(tmp_path, monkeypatch):
     import create_dataset as cd
     import extract_lsm_features as ex

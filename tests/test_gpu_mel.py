@@ -199,6 +199,6 @@ def test_hotpath_with_the_mel_front_end_equals_the_serial_path(monkeypatch, one_
             assert torch.equal(hp.run(batches), serial), (streams, fes, rep)
     assert fe.will_fuse() == one_launch
     if one_launch:
-        assert len({w.data_ptr() for w in hp._ws.values()}) == len(hp._ws) >= 2
+        assert len({ring.workspace.data_ptr() for ring in hp._rasters.values()}) == len(hp._rasters) >= 2
     else:
-        assert not hp._ws
+        assert not hp._rasters

@@ -1,6 +1,6 @@
 """Open-ended streams (SPEC.md 4d): what can be checked without a GPU -- the new public header and its ctypes table, the
 build identity, `pipeline.stream_window_plan` against a brute-force enumeration of windows, the argument checks of
-`SNN.run_stream_records`, and a NumPy restatement of "ragged records -> merge fold -> feature_value" against the oracle's
+`SNN.run_stream_records`, `pipeline.CarryBuffer` against a list per stream, and a NumPy restatement of "ragged records -> merge fold -> feature_value" against the oracle's
 `feature_row` on slices of one oracle spike matrix."""
 import ctypes
 import os
@@ -295,3 +295,42 @@ def test_stream_bank_hands_every_window_its_own_records(K, H, monkeypatch):
     for b in range(n_streams):
         n_w = (seen[b] - K) // H + 1 if seen[b] >= K else 0
         assert got[b] == [[float(w * H + j + 1) for j in range(K)] for w in range(n_w)], f"stream {b}"
+
+
+# ---- CarryBuffer alone: join and keep against a plain list per stream ------------------------------------------------------
+@pytest.mark.parametrize("item,dtype", [((2,), "int32"), ((5,), "uint8")])
+@pytest.mark.parametrize("G", [0, 1, 4])
+@pytest.mark.parametrize("cap", [0, 1, 3])
+def test_carry_buffer_joins_and_keeps_like_a_list_per_stream(cap, G, item, dtype):
+    """12 consecutive pushes on CPU tensors: after every push the joined run is the model's list (kept items, then the new
+    ones), the kept buffer is the list's tail, left-aligned, and everything past ``keep[b]`` is zero; one slot is reset in
+    the middle."""
+    import torch
+    from lsm_speech_classifier_amd import pipeline
+    n_streams, tdtype = 3, getattr(torch, dtype)
+    rng = np.random.RandomState(1000 * cap + 10 * G + len(item))
+    carry = pipeline.CarryBuffer(n_streams, cap, item, tdtype, torch.device("cpu"))
+    assert carry.kept.shape == (n_streams, cap, *item) and carry.kept.dtype == tdtype and not carry.count.any()
+    model = [[] for _ in range(n_streams)]
+    for push in range(12):
+        counts = rng.randint(0, G + 1, size=n_streams).astype(np.int64)
+        new = rng.randint(1, 200, size=(n_streams, G, *item)).astype(dtype)      # non-zero, also behind a stream's count
+        run, have = carry.join(torch.from_numpy(new), counts)
+        assert run.shape == (n_streams, cap + G, *item) and run.dtype == tdtype and run.is_contiguous()
+        for b in range(n_streams):
+            model[b] += [new[b, g].tolist() for g in range(counts[b])]
+            assert have[b] == len(model[b])
+            assert run[b, :have[b]].tolist() == model[b], (push, b)
+        keep = np.array([rng.randint(0, min(cap, len(m)) + 1) for m in model], dtype=np.int64)
+        carry.keep(run, have, keep)
+        assert carry.kept.shape == (n_streams, cap, *item) and carry.kept.dtype == tdtype and carry.kept.is_contiguous()
+        assert carry.count.tolist() == keep.tolist() and carry.count is not keep
+        for b in range(n_streams):
+            model[b] = model[b][len(model[b]) - keep[b]:]
+            assert carry.kept[b, :keep[b]].tolist() == model[b], (push, b)
+            assert not carry.kept[b, keep[b]:].any(), (push, b)
+        if push == 5:                                                   # stream 1 ends, a new one takes its slot
+            carry.reset(np.array([1], dtype=np.int64))
+            model[1] = []
+            assert carry.count[1] == 0 and not carry.kept[1].any()
+            assert carry.count[0] == keep[0] and carry.kept[0, :keep[0]].tolist() == model[0]
