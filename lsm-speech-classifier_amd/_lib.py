@@ -92,6 +92,16 @@ AUDIO_SIGS = {
 }
 AUDIO_SYMBOLS = tuple(AUDIO_SIGS)
 
+# include/lsm_hip_mel_stream.h (SPEC.md §1.7): the streamed mel front end
+MEL_STREAM_SIGS = {
+    "lsm_mel_stream_state_bytes": (C.c_long, [c_int, c_int, c_int]),
+    "lsm_mel_stream_workspace": (C.c_long, [c_int, c_int, c_int]),
+    "lsm_mel_stream_f32": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_int,
+                                   c_void, c_double, c_double, c_void, c_void, c_int, c_int, c_void, c_void, c_void,
+                                   c_void, c_void, c_void, C.c_long, c_void]),
+}
+MEL_STREAM_SYMBOLS = tuple(MEL_STREAM_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -139,7 +149,8 @@ def load():
         raise LsmHipError(
             f"{path} was built from other sources than this tree's (build id {_build.built_id(path)}, sources "
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
-    for name, (res, args) in list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items()):
+    for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
+                              + list(MEL_STREAM_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

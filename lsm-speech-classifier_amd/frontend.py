@@ -332,6 +332,20 @@ class SpikeFrontEnd:
         lo = torch.maximum(db.min(), hi - 80.0)
         return float(lo), float(hi)
 
+    def mel_db_range(self, audio):
+        """Calibration range for `MelStream` from a batch of calibration clips (B, n_samples): ``(lo, hi)`` Python floats in
+        ABSOLUTE dB (no per-clip reference level): ``hi = 10 * log10(max(amin, max S))`` over the mel power values
+        (`MelSpectrogram.power`) of the whole batch and ``lo = max(10 * log10(max(amin, min S)), hi - 80)``."""
+        if self.filterbank != "mel":
+            raise ValueError("mel_db_range calibrates the streamed mel front end; this front end is a gammatone filterbank "
+                             "(use db_range)")
+        from . import mel as _mel
+        with torch.cuda.device(self.device):
+            S = self._mel.power(self._audio(audio))
+            db = 10.0 * torch.log10(torch.clamp(torch.stack([S.min(), S.max()]), min=_mel.AMIN))
+        lo, hi = (float(v) for v in db.cpu())
+        return max(lo, hi - _mel.TOP_DB), hi
+
 
 # ---- streamed gammatone front end (SPEC.md §1.6, include/lsm_hip_audio.h) ----------------------------------------------
 STREAM_NWIN = 400           # 25 ms at 16 kHz
@@ -362,7 +376,48 @@ def stream_column_plan(seen_hops, new_hops, nwin: int = STREAM_NWIN, hop: int = 
     return int(cols) if np.ndim(seen_hops) == 0 and np.ndim(new_hops) == 0 else cols
 
 
-class GammatoneStream:
+class _AudioStreamBase:
+    """What the streamed front ends share: ``n_streams`` state blocks on the device, the hops each stream has seen, and the
+    checks of a push's arguments.  A subclass sets n_filters, n_streams, hop, redundancy, on, device, state and seen."""
+
+    @property
+    def n_thr(self) -> int:
+        return len(self.on)
+
+    @property
+    def n_channels(self) -> int:
+        return self.n_filters * self.redundancy
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: state block and hop count back to zero."""
+        slots = checked_slots(slots, self.n_streams)
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+        self.seen[slots] = 0
+
+    def _out(self, t, shape, dtype, name):
+        if t is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {self.device}")
+        return t
+
+    def _pushed(self, audio, hops):
+        """A push's arguments checked: (audio on the device, H, the new hops per stream as int64)."""
+        audio = as_float32(audio).to(self.device)
+        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % self.hop or audio.shape[1] < self.hop:
+            raise ValueError(f"audio must be ({self.n_streams}, H * {self.hop}) with H >= 1, got {tuple(audio.shape)}")
+        H = int(audio.shape[1]) // self.hop
+        if hops is None:
+            new = np.full(self.n_streams, H, dtype=np.int64)
+        else:
+            new = np.asarray(hops)
+            if new.shape != (self.n_streams,) or new.dtype.kind not in "iu" or (new < 0).any() or (new > H).any():
+                raise ValueError(f"hops must be {self.n_streams} integers in [0, {H}], got {hops!r}")
+            new = new.astype(np.int64)
+        return audio, H, new
+
+
+class GammatoneStream(_AudioStreamBase):
     """``n_streams`` open-ended audio streams through one gammatone -> dB -> fixed-range normalise -> hysteresis encoder
     kernel (`lsm_gammatone_stream_f64`, SPEC.md §1.6).  Every ``push`` advances each stream by the whole hops it delivers --
     any number, 0 included -- from the state the bank holds (filter state, open window sums, latches), and returns the
@@ -396,27 +451,6 @@ class GammatoneStream:
         self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
         self.seen = np.zeros(self.n_streams, dtype=np.int64)            # hops since the stream's start
 
-    @property
-    def n_thr(self) -> int:
-        return len(self.on)
-
-    @property
-    def n_channels(self) -> int:
-        return self.n_filters * self.redundancy
-
-    def reset(self, slots) -> None:
-        """The streams in ``slots`` have ended and new ones take their places: state block and hop count back to zero."""
-        slots = checked_slots(slots, self.n_streams)
-        self.state[torch.from_numpy(slots).to(self.device)] = 0
-        self.seen[slots] = 0
-
-    def _out(self, t, shape, dtype, name):
-        if t is None:
-            return torch.zeros(shape, dtype=dtype, device=self.device)
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
-            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {self.device}")
-        return t
-
     def push(self, audio, hops=None, want_db: bool = False, want_spec: bool = False, raster_out=None, db_out=None,
              spec_out=None):
         """``audio`` (n_streams, H * hop) float32: stream b's new samples are the first ``hops[b] * hop`` of its row;
@@ -425,17 +459,7 @@ class GammatoneStream:
         b's rows are the columns this push completed (`stream_column_plan`); what lies behind them is zeros, or what a
         caller-owned ``raster_out`` held.  With ``want_db`` / ``want_spec`` (or caller-owned ``db_out`` / ``spec_out``) the
         return is ``(raster, cols, db, spec)``: float64 (n_streams, F, H), written like the raster, None where not asked."""
-        audio = as_float32(audio).to(self.device)
-        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % self.hop or audio.shape[1] < self.hop:
-            raise ValueError(f"audio must be ({self.n_streams}, H * {self.hop}) with H >= 1, got {tuple(audio.shape)}")
-        H = int(audio.shape[1]) // self.hop
-        if hops is None:
-            new = np.full(self.n_streams, H, dtype=np.int64)
-        else:
-            new = np.asarray(hops)
-            if new.shape != (self.n_streams,) or new.dtype.kind not in "iu" or (new < 0).any() or (new > H).any():
-                raise ValueError(f"hops must be {self.n_streams} integers in [0, {H}], got {hops!r}")
-            new = new.astype(np.int64)
+        audio, H, new = self._pushed(audio, hops)
         cols = stream_column_plan(self.seen, new, self.nwin, self.hop)
         with torch.cuda.device(self.device):
             raster = self._out(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
@@ -452,6 +476,109 @@ class GammatoneStream:
         self.seen += new
         if db is not None or spec is not None:
             return raster, cols, db, spec
+        return raster, cols
+
+
+# ---- streamed mel front end (SPEC.md §1.7, include/lsm_hip_mel_stream.h) ------------------------------------------------
+MEL_N_FFT = 2048
+
+
+def _check_mel_hop(hop: int, n_fft: int) -> None:
+    if n_fft != MEL_N_FFT:
+        raise ValueError(f"n_fft = {n_fft}: the mel kernels transform {MEL_N_FFT}-sample frames only")
+    if hop < n_fft // 16 or hop > n_fft // 2:
+        raise ValueError(f"hop = {hop} outside [{n_fft // 16}, {n_fft // 2}] (n_fft / 16 .. n_fft / 2)")
+
+
+def mel_stream_frame_plan(seen_hops, new_hops, hop: int = STREAM_HOP, n_fft: int = MEL_N_FFT):
+    """The frames one push completes, host integers only.  Frame t of a stream is centred on its sample ``t * hop`` and is
+    complete once the stream holds ``t * hop + n_fft / 2`` samples (no frame touches an end padding), so a stream that has
+    seen n whole hops has ``complete(n) = max(0, n - Lg + 1)`` of them, ``Lg = ceil((n_fft / 2) / hop)``.  A stream that
+    had seen ``seen_hops`` hops and receives ``new_hops`` more completes ``complete(seen + new) - complete(seen)`` frames.
+    Scalars or arrays of equal shape; returns an int or an int64 array."""
+    hop, n_fft = int(hop), int(n_fft)
+    _check_mel_hop(hop, n_fft)
+    seen_a, new_a = np.asarray(seen_hops, dtype=np.int64), np.asarray(new_hops, dtype=np.int64)
+    if (seen_a < 0).any() or (new_a < 0).any():
+        raise ValueError("mel_stream_frame_plan: seen_hops and new_hops must be >= 0")
+    lg = -(-(n_fft // 2) // hop)
+
+    def complete(n):
+        return np.maximum(n - lg + 1, 0)
+
+    cols = complete(seen_a + new_a) - complete(seen_a)
+    return int(cols) if np.ndim(seen_hops) == 0 and np.ndim(new_hops) == 0 else cols
+
+
+class MelStream(_AudioStreamBase):
+    """``n_streams`` open-ended audio streams through the streamed mel front end (`lsm_mel_stream_f32`, SPEC.md §1.7):
+    centred STFT frames -> mel power -> absolute dB -> fixed-range normalise -> hysteresis encoder.  Every ``push`` advances
+    each stream by the whole hops it delivers -- any number, 0 included -- from the state the bank holds (the tail of samples
+    the next frames reach back into, the latches, a hop count), and returns the raster columns of the frames those hops
+    completed: one time bin per frame, normalised with the calibration range ``db_range`` (``SpikeFrontEnd.mel_db_range``)
+    fixed for the streams' lives.  A stream cut into pushes at any hop boundaries gives, byte for byte, the raster of its
+    uncut run.  The interface is `GammatoneStream`'s."""
+    filterbank = "mel"
+    streamed = True
+
+    def __init__(self, n_filters: int, n_streams: int, db_range, thresholds=None, gap: float = HYSTERESIS_GAP,
+                 redundancy: int = REDUNDANCY_FACTOR, device=None, hop: int = STREAM_HOP):
+        self.n_filters, self.n_streams = int(n_filters), int(n_streams)
+        self.hop, self.redundancy = int(hop), int(redundancy)
+        if self.n_filters < 1:
+            raise ValueError(f"n_filters must be >= 1, got {n_filters}")
+        if self.n_streams < 1 or self.redundancy < 1:
+            raise ValueError(f"MelStream needs n_streams >= 1 and redundancy >= 1, got {n_streams}, {redundancy}")
+        _check_mel_hop(self.hop, MEL_N_FFT)
+        self.db_lo, self.db_hi = (float(v) for v in db_range)
+        lo32, hi32 = np.float32(self.db_lo), np.float32(self.db_hi)     # the kernel's values: rounded to float32 once
+        if not (np.isfinite(lo32) and np.isfinite(hi32) and lo32 < hi32):
+            raise ValueError(f"db_range = ({self.db_lo}, {self.db_hi}) must be finite with lo < hi (as float32 values)")
+        self.thresholds = list(SPIKE_THRESHOLDS if thresholds is None else thresholds)
+        self.gap = float(gap)
+        self.on, self.off = threshold_tables(self.thresholds, self.gap, np.float32)
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        from . import mel as _mel
+        self.window, self.twiddle, self.basis, self.lo, self.hi = _mel.device_tables(self.n_filters, self.device)
+        self.state_bytes = int(self.lib.lsm_mel_stream_state_bytes(self.n_filters, MEL_N_FFT, self.hop))
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self.seen = np.zeros(self.n_streams, dtype=np.int64)            # hops since the stream's start
+        self._ws = None                                                 # scratch of the launches, grown on demand
+
+    def push(self, audio, hops=None, want_db: bool = False, want_power: bool = False, raster_out=None, db_out=None,
+             power_out=None):
+        """``audio`` (n_streams, H * hop) float32: stream b's new samples are the first ``hops[b] * hop`` of its row;
+        ``hops``: n_streams host integers in [0, H], or None for H everywhere.  Returns ``(raster, cols)``: ``raster`` uint8
+        (n_streams, C, H * n_thr) on the device and ``cols`` (int64, host) -- the first ``cols[b] * n_thr`` steps of stream
+        b's rows are the frames this push completed (`mel_stream_frame_plan`); what lies behind them is zeros, or what a
+        caller-owned ``raster_out`` held.  With ``want_db`` / ``want_power`` (or caller-owned ``db_out`` / ``power_out``) the
+        return is ``(raster, cols, db, power)``: float32 (n_streams, F, H), written like the raster, None where not asked;
+        ``db`` holds the un-floored ``10 * log10(max(1e-10, power))``."""
+        audio, H, new = self._pushed(audio, hops)
+        cols = mel_stream_frame_plan(self.seen, new, self.hop)
+        with torch.cuda.device(self.device):
+            raster = self._out(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
+            shape = (self.n_streams, self.n_filters, H)
+            db = self._out(db_out, shape, torch.float32, "db_out") if (want_db or db_out is not None) else None
+            power = self._out(power_out, shape, torch.float32, "power_out") if (want_power or power_out is not None) else None
+            counts = None if hops is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            need = int(self.lib.lsm_mel_stream_workspace(self.n_streams, self.n_filters, H))
+            if self._ws is None or self._ws.numel() < need:
+                # launches of one bank run in order on the current stream and may share the scratch; the caching allocator
+                # keeps a replaced one alive until the launches that used it have run
+                self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.lsm_mel_stream_f32(
+                _dev(audio), self.n_streams, H, MEL_N_FFT, self.hop, _dev(self.window), _dev(self.twiddle), _dev(self.basis),
+                _dev(self.lo), _dev(self.hi), self.n_filters, _dev(counts) if counts is not None else None, self.db_lo,
+                self.db_hi, _host(self.on), _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state),
+                _dev(raster), _dev(power) if power is not None else None, _dev(db) if db is not None else None,
+                _dev(self._ws), int(self._ws.numel()), torch.cuda.current_stream(self.device).cuda_stream),
+                "lsm_mel_stream_f32")
+        self.seen += new
+        if db is not None or power is not None:
+            return raster, cols, db, power
         return raster, cols
 
 

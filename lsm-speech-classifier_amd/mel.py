@@ -52,6 +52,22 @@ def mel_basis(sr: float, n_fft: int, n_mels: int):
     return w32, lo, hi
 
 
+def stft_tables():
+    """Periodic Hann window (N_FFT float64) and the twiddle table W_2048^k, k < 1024, as (cos, -sin) rows."""
+    n = np.arange(N_FFT)
+    window = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / N_FFT)           # periodic Hann, float64
+    k = np.arange(N_FFT // 2)
+    tw = np.stack([np.cos(2.0 * np.pi * k / N_FFT), -np.sin(2.0 * np.pi * k / N_FFT)], axis=1)
+    return window, tw
+
+
+def device_tables(n_mels: int, device):
+    """The five parameter tables of the mel kernels on ``device``: (window, twiddle, basis, lo, hi)."""
+    window, tw = stft_tables()
+    basis, lo, hi = mel_basis(SAMPLE_RATE, N_FFT, int(n_mels))
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (window, tw, basis, lo, hi))
+
+
 class MelSpectrogram:
     def __init__(self, n_mels: int, n_samples: int, time_bins: int, device):
         self.lib = _lib.load()
@@ -60,14 +76,7 @@ class MelSpectrogram:
         self.n_samples = int(n_samples)
         self.hop = max(1, int(n_samples / time_bins))              # create_dataset.py:44
         self.n_frames = 1 + n_samples // self.hop                  # centred: 1 + floor(L / hop)
-        n = np.arange(N_FFT)
-        window = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / N_FFT)       # periodic Hann, float64
-        k = np.arange(N_FFT // 2)
-        tw = np.stack([np.cos(2.0 * np.pi * k / N_FFT), -np.sin(2.0 * np.pi * k / N_FFT)], axis=1)
-        basis, lo, hi = mel_basis(SAMPLE_RATE, N_FFT, self.n_mels)
-        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        self.window, self.twiddle = to(window), to(tw)
-        self.basis, self.lo, self.hi = to(basis), to(lo), to(hi)
+        self.window, self.twiddle, self.basis, self.lo, self.hi = device_tables(self.n_mels, self.device)
         # scratch of the one-launch front end per (batch size, stream).  A workspace carries the clips' arrival counters,
         # so two launches that may overlap (different streams) must not share one; pipeline.HotPath owns one per stream.
         self._ws = {}

@@ -617,16 +617,18 @@ class StreamBank:
 
 
 class AudioStreamBank:
-    """``StreamBank`` fed with audio: ``gt_stream`` (``frontend.GammatoneStream``) turns every push of whole hops into the
+    """``StreamBank`` fed with audio: ``gt_stream`` (``frontend.GammatoneStream`` or ``frontend.MelStream``) turns every push of whole hops into the
     raster columns it completed, the bank keeps each stream's columns that do not yet fill a segment (fewer than
     ``segment_steps / n_thr`` of them) and forwards whole segments to an inner ``StreamBank`` over ``net``.  Both halves
     continue from saved state, so the rows are those of each stream's one uncut run, audio to features."""
 
     def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None):
         # the refusals come before anything touches a device
-        if getattr(gt_stream, "filterbank", None) != "gammatone" or not hasattr(gt_stream, "push"):
-            raise ValueError("AudioStreamBank needs a frontend.GammatoneStream: the mel front end normalises every window by "
-                             "its own maximum and keeps no state between launches, so it cannot be streamed")
+        streamed = getattr(gt_stream, "filterbank", None) == "gammatone" or getattr(gt_stream, "streamed", None) is True
+        if not streamed or not hasattr(gt_stream, "push"):
+            raise ValueError("AudioStreamBank needs a streamed front end, frontend.GammatoneStream or frontend.MelStream: the "
+                             "batch mel front end (SpikeFrontEnd) normalises every window by its own maximum and keeps no "
+                             "state between launches, so it cannot be streamed; frontend.MelStream is the streamed one")
         S, n_thr = int(segment_steps), int(gt_stream.n_thr)
         if S < 1 or S % n_thr:
             raise ValueError(f"segment_steps = {segment_steps} must be a positive multiple of the front end's {n_thr} "
