@@ -34,33 +34,43 @@ def _frontend():
     return frontend
 
 
+def _decode_wav(filepath: Path):
+    """One PCM wav file as (rate, mono float32 at the file's own rate)."""
+    from scipy.io import wavfile
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        rate, data = wavfile.read(str(filepath))
+    if data.dtype.kind == "i":
+        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
+    elif data.dtype.kind == "u":
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    else:
+        data = data.astype(np.float32)
+    if data.ndim == 2:
+        data = data.mean(axis=1)
+    return int(rate), data
+
+
+def _one_second(data: np.ndarray) -> np.ndarray:
+    want = int(SAMPLE_RATE * DURATION)
+    data = data[:want]
+    if len(data) < want:
+        data = np.pad(data, (0, want - len(data)))
+    return np.ascontiguousarray(data, dtype=np.float32)
+
+
 def load_audio_file(filepath: Path):
     """One wav file as mono float32 at 16 kHz, padded/trimmed to exactly one second; None (with a
     message) when the file cannot be read.  PCM wav only (scipy.io.wavfile); other rates are
     resampled polyphase."""
-    from scipy.io import wavfile
     try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            rate, data = wavfile.read(str(filepath))
-        if data.dtype.kind == "i":
-            data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
-        elif data.dtype.kind == "u":
-            data = (data.astype(np.float32) - 128.0) / 128.0
-        else:
-            data = data.astype(np.float32)
-        if data.ndim == 2:
-            data = data.mean(axis=1)
+        rate, data = _decode_wav(filepath)
         if rate != SAMPLE_RATE:
             from math import gcd
             from scipy.signal import resample_poly
             g = gcd(int(rate), SAMPLE_RATE)
             data = resample_poly(data, SAMPLE_RATE // g, int(rate) // g).astype(np.float32)
-        want = int(SAMPLE_RATE * DURATION)
-        data = data[:want]
-        if len(data) < want:
-            data = np.pad(data, (0, want - len(data)))
-        return np.ascontiguousarray(data, dtype=np.float32)
+        return _one_second(data)
     except Exception as exc:
         print(f"Error loading {filepath}: {exc}")
         return None
@@ -109,6 +119,46 @@ def _load_listing(listing):
     return clips, labels
 
 
+def _load_listing_device(listing, device=None):
+    """`_load_listing` with the resampling on the GPU (`--resample device`): the files are decoded to mono at their own
+    rates on the host, grouped by rate, every group padded with zeros to a common length and resampled in one launch
+    (`frontend.Resampler`, SPEC.md 1.8).  Returns ``(clips, labels)``: a float32 (n, 16000) DEVICE tensor in listing order
+    (None when nothing could be read) and the labels of its rows."""
+    import torch
+    fe = _frontend()
+    want = int(SAMPLE_RATE * DURATION)
+    decoded, labels = [], []
+    for f, label in listing:
+        try:
+            decoded.append(_decode_wav(f))
+            labels.append(label)
+        except Exception as exc:
+            print(f"Error loading {f}: {exc}")
+    if not decoded:
+        return None, labels
+    dev = fe.indexed_device(device)
+    clips = torch.zeros((len(decoded), want), dtype=torch.float32, device=dev)
+    for rate in sorted({r for r, _ in decoded}):
+        rows = [i for i, (r, _) in enumerate(decoded) if r == rate]
+        if rate == SAMPLE_RATE:
+            group = np.stack([_one_second(decoded[i][1]) for i in rows])
+            clips[torch.tensor(rows, device=dev)] = torch.from_numpy(group).to(dev)
+            continue
+        rs = fe.Resampler(rate, SAMPLE_RATE, device=dev)
+        # an output below 16000 reads no input past rate * DURATION + Hs
+        length = min(max(len(decoded[i][1]) for i in rows), int(rate * DURATION) + rs.history + 1)
+        group = np.zeros((len(rows), max(length, 1)), dtype=np.float32)
+        for q, i in enumerate(rows):
+            x = decoded[i][1][:length]
+            group[q, :len(x)] = x
+        out = rs.resample(group, n_out=want)
+        # resample_poly ends a clip after ceil(n * up / down) samples: what the filter's tail adds behind is dropped
+        ends = torch.tensor([rs.default_length(len(decoded[i][1])) for i in rows], device=dev)
+        out.masked_fill_(torch.arange(want, device=dev)[None, :] >= ends[:, None], 0.0)
+        clips[torch.tensor(rows, device=dev)] = out
+    return clips, labels
+
+
 def _collect_audio(commands, root: Path, per_class: int):
     return _load_listing(_list_files(commands, root, per_class))
 
@@ -143,16 +193,19 @@ def collect_audio(commands=None, dataset_root=None, max_per_class: int = MAX_SAM
 
 def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
-                   output_file: str = OUTPUT_FILE, packed: bool = False):
+                   output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host"):
     """Build File 1.  The first two arguments are the reference's; the keyword arguments expose
     what the reference hard-codes (class list, corpus folder, per-class cap) plus a synthetic
     corpus for machines without Speech Commands.  ``packed=True`` writes the bit-packed schema of
     ``lsm_speech_classifier_amd.spikefile`` (rasters packed on the GPU, 8x fewer bytes off the
-    device and on disk); the default is the reference's uint8 schema.
+    device and on disk); the default is the reference's uint8 schema.  ``resample="device"`` resamples files that are not
+    at 16 kHz on the GPU (`_load_listing_device`) instead of one by one on the host.
 
     Under a launcher (torchrun: RANK / WORLD_SIZE) the clip loop of create_dataset.py:143 shards: rank r reads
     and encodes the r-th contiguous block of the file listing on its own GPU, the raster blocks are all-gathered
     in rank order (= the single-process order) and rank 0 writes the file -- the same bytes as one process."""
+    if resample not in ("host", "device"):
+        raise ValueError(f"resample must be 'host' or 'device', got {resample!r}")
     from lsm_speech_classifier_amd import dist as lsm_dist
     rank, _, world = lsm_dist.init()
     commands = list(COMMANDS if commands is None else commands)
@@ -167,8 +220,12 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     else:
         listing = _list_files(commands, root, max_per_class, verbose=rank == 0)
         lo, hi = lsm_dist.shard_range(len(listing), rank, world)
-        clips, labels = _load_listing(listing[lo:hi])
-    if not clips and world == 1:
+        if resample == "device":
+            clips, labels = _load_listing_device(listing[lo:hi], lsm_dist.local_device() if world > 1 else None)
+            clips = [] if clips is None else clips
+        else:
+            clips, labels = _load_listing(listing[lo:hi])
+    if not len(clips) and world == 1:
         print("\nERROR: No audio files were successfully processed.")
         return
 
@@ -180,7 +237,9 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     from lsm_speech_classifier_amd import spikefile
     parts, n_spikes = [], 0
     for a in range(0, len(clips), ENCODE_BATCH):
-        batch = np.stack(clips[a:a + ENCODE_BATCH])
+        batch = clips[a:a + ENCODE_BATCH]
+        if not torch.is_tensor(batch):
+            batch = np.stack(batch)
         raster = fe.encode(batch)
         n_spikes += int(raster.count_nonzero())
         part = _frontend().pack_raster(raster) if packed else raster
@@ -248,7 +307,10 @@ if __name__ == "__main__":
     ap.add_argument("--packed", action="store_true",
                     default=os.environ.get("LSM_PACKED_DATASET", "0") == "1",
                     help="Write the bit-packed File 1 schema (8x fewer raster bytes).")
+    ap.add_argument("--resample", type=str, default="host", choices=["host", "device"],
+                    help="Where files that are not at 16 kHz are resampled: one by one on the host (default), or grouped by "
+                         "rate on the GPU.")
     a = ap.parse_args()
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,
-                   synthetic_per_class=a.synthetic_per_class, packed=a.packed)
+                   synthetic_per_class=a.synthetic_per_class, packed=a.packed, resample=a.resample)

@@ -102,6 +102,15 @@ MEL_STREAM_SIGS = {
 }
 MEL_STREAM_SYMBOLS = tuple(MEL_STREAM_SIGS)
 
+# include/lsm_hip_resample.h (SPEC.md §1.8): the polyphase resampler, batch and streamed
+RESAMPLE_SIGS = {
+    "lsm_resample_state_bytes": (C.c_long, [c_int, c_int]),
+    "lsm_resample_f32": (c_int, [c_void, c_int, c_int, c_int, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
+    "lsm_resample_stream_f32": (c_int, [c_void, c_int, c_int, c_int, c_void, c_int, c_int, c_int, c_void, c_void, c_void,
+                                        c_void, c_void]),
+}
+RESAMPLE_SYMBOLS = tuple(RESAMPLE_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -150,7 +159,7 @@ def load():
             f"{path} was built from other sources than this tree's (build id {_build.built_id(path)}, sources "
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
-                              + list(MEL_STREAM_SIGS.items())):
+                              + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from math import gcd
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -580,6 +582,203 @@ class MelStream(_AudioStreamBase):
         if db is not None or power is not None:
             return raster, cols, db, power
         return raster, cols
+
+
+# ---- polyphase resampler (SPEC.md §1.8, include/lsm_hip_resample.h) -----------------------------------------------------
+RESAMPLE_HALF_WIDTH = 10            # scipy.signal.resample_poly: half = 10 * max(up, down)
+RESAMPLE_KAISER_BETA = 5.0          # its default window, ('kaiser', 5.0)
+RESAMPLE_LDS_BYTES = 160 * 1024     # the tap table laid out by phase must fit a CU's LDS
+
+
+class ResampleTable(NamedTuple):
+    """The design of one rate pair: ``taps`` is hp, the prototype filter behind its ``pre`` leading zeros (float64, K
+    values); ``delay`` D the batch form's shift in output samples; ``history`` Hs the input samples a stream carries."""
+    up: int
+    down: int
+    taps: np.ndarray
+    delay: int
+    history: int
+    pre: int
+
+
+def _checked_rates(rate_in, rate_out):
+    for name, r in (("rate_in", rate_in), ("rate_out", rate_out)):
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or int(r) < 1:
+            raise ValueError(f"{name} must be a positive integer number of samples per second, got {r!r}")
+    return int(rate_in), int(rate_out)
+
+
+def resample_table(rate_in: int, rate_out: int = SAMPLE_RATE) -> ResampleTable:
+    """The polyphase filter of SPEC.md §1.8 for ``rate_in`` -> ``rate_out``, on the host in float64 with NumPy only:
+    ``scipy.signal.firwin(2 * half + 1, 1 / mr, window=('kaiser', 5.0)) * up`` restated, ``mr = max(up, down)``,
+    ``half = 10 * mr``, behind ``pre = down - half % down`` zeros as ``resample_poly`` places it."""
+    rate_in, rate_out = _checked_rates(rate_in, rate_out)
+    if rate_in == rate_out:
+        raise ValueError(f"rate_in == rate_out ({rate_in}): there is nothing to design")
+    g = gcd(rate_in, rate_out)
+    up, down = rate_out // g, rate_in // g
+    mr = max(up, down)
+    half = RESAMPLE_HALF_WIDTH * mr
+    n = np.arange(2 * half + 1, dtype=np.float64)
+    h = (1.0 / mr) * np.sinc((n - half) / mr) * np.kaiser(2 * half + 1, RESAMPLE_KAISER_BETA)
+    h = h / h.sum() * up
+    pre = down - half % down
+    taps = np.concatenate([np.zeros(pre, dtype=np.float64), h])
+    table_bytes = up * (-(-len(taps) // up) | 1) * 8            # [phase][tap] with an odd row stride (csrc/resample_body.h)
+    if table_bytes > RESAMPLE_LDS_BYTES:
+        raise ValueError(f"{rate_in} -> {rate_out} Hz needs {len(taps)} taps in {up} phases: {table_bytes} bytes laid out by "
+                         f"phase, over the {RESAMPLE_LDS_BYTES} of a compute unit's LDS (lsm_resample_f32 refuses it)")
+    return ResampleTable(up, down, taps, (half + pre) // down, (len(taps) - 1) // up, pre)
+
+
+def resample_units(up: int, down: int, hop: int = STREAM_HOP):
+    """The smallest push of a resampled stream that is a whole number of front-end hops: ``(unit_blocks, unit_in,
+    unit_hops)`` -- ``unit_blocks = hop / gcd(up, hop)`` blocks of ``down`` input samples, which are ``unit_in`` samples in
+    and ``unit_blocks * up = unit_hops * hop`` out."""
+    g = gcd(int(up), int(hop))
+    return hop // g, hop // g * int(down), int(up) // g
+
+
+def checked_pcm(audio, n_rows: int | None = None, multiple: int = 1, what: str = "audio"):
+    """Mono PCM rows as the resampler takes them: a 2-D float32 or int16 NumPy array (copied) or tensor, ``n_rows`` rows when
+    given, a positive multiple of ``multiple`` samples each.  Returns ``(contiguous tensor on the device it is on,
+    sample_format)``, 0 for float32 and 1 for int16; refuses everything else with a ValueError."""
+    if isinstance(audio, np.ndarray):
+        if audio.dtype not in (np.float32, np.int16):
+            raise ValueError(f"{what} must be float32 or int16, got {audio.dtype}")
+        audio = torch.from_numpy(np.ascontiguousarray(audio))
+    elif not torch.is_tensor(audio) or audio.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"{what} must be a float32 or int16 NumPy array or tensor, got "
+                         f"{audio.dtype if torch.is_tensor(audio) else type(audio).__name__}")
+    shape = tuple(audio.shape)
+    if audio.dim() != 2 or (n_rows is not None and shape[0] != n_rows) or shape[1] < multiple or shape[1] % multiple:
+        rows = "n" if n_rows is None else str(n_rows)
+        cols = "L >= 1" if multiple == 1 else f"G * {multiple} with G >= 1"
+        raise ValueError(f"{what} must be ({rows}, {cols}), got {shape}")
+    return audio.contiguous(), 1 if audio.dtype == torch.int16 else 0
+
+
+def checked_counts(counts, n_streams: int, limit: int, what: str = "blocks") -> np.ndarray:
+    """Per-stream counts of a push as an int64 array: ``n_streams`` integers in ``[0, limit]``, or None for ``limit``
+    everywhere."""
+    if counts is None:
+        return np.full(n_streams, limit, dtype=np.int64)
+    new = np.asarray(counts)
+    if new.shape != (n_streams,) or new.dtype.kind not in "iu" or (new < 0).any() or (new > limit).any():
+        raise ValueError(f"{what} must be {n_streams} integers in [0, {limit}], got {counts!r}")
+    return new.astype(np.int64)
+
+
+class _ResampleBase:
+    """The design of a rate pair on the host, then -- unless the rates are equal -- the library and the taps on the device."""
+
+    def __init__(self, rate_in, rate_out, device):
+        self.rate_in, self.rate_out = _checked_rates(rate_in, rate_out)
+        self.identity = self.rate_in == self.rate_out
+        table = (ResampleTable(1, 1, np.ones(1, dtype=np.float64), 0, 0, 0) if self.identity
+                 else resample_table(self.rate_in, self.rate_out))
+        self.up, self.down, self.taps, self.delay, self.history, _ = table
+        self.table = table
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        self.taps_dev = torch.from_numpy(self.taps).to(self.device)
+
+    def _as_float(self, audio: torch.Tensor) -> torch.Tensor:
+        """Equal rates: the samples as the kernels widen them, float32, an int16 sample times 2^-15."""
+        return audio.to(torch.float32) * (1.0 / 32768.0) if audio.dtype == torch.int16 else audio.clone()
+
+
+class Resampler(_ResampleBase):
+    """Batches of mono clips from ``rate_in`` to ``rate_out`` in one launch (`lsm_resample_f32`, SPEC.md §1.8): the samples
+    of ``scipy.signal.resample_poly(x, up, down)`` computed in float64 and rounded once to float32, zeros outside a clip.
+    ``up``, ``down``, ``delay``, ``taps`` and ``history`` are the design (`resample_table`).  Equal rates are the identity."""
+    MAX_ROWS = 65535                    # rows of one launch
+
+    def __init__(self, rate_in: int, rate_out: int = SAMPLE_RATE, device=None):
+        super().__init__(rate_in, rate_out, device)
+
+    def default_length(self, n_in: int) -> int:
+        """``ceil(n_in * up / down)``, `resample_poly`'s output length."""
+        return -(-int(n_in) * self.up // self.down)
+
+    def resample(self, audio, n_out: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``audio`` (n, L) float32 or int16, NumPy or tensor -> float32 (n, n_out) on the device.  ``n_out`` defaults to
+        ``ceil(L * up / down)``; a smaller one gives the first samples of the same result, a larger one continues over the
+        zeros behind the clips.  ``out``: a caller-owned contiguous float32 (n, n_out) tensor on the device."""
+        audio, fmt = checked_pcm(audio)
+        n, L = (int(v) for v in audio.shape)
+        n_out = self.default_length(L) if n_out is None else int(n_out)
+        if n_out < 1:
+            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) or not out.is_contiguous()
+                                or out.device != self.device):
+            raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            if out is None:
+                out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+            if self.identity:
+                out.zero_()
+                out[:, :min(L, n_out)] = self._as_float(audio[:, :n_out])
+                return out
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for r0 in range(0, n, self.MAX_ROWS):
+                rows = min(self.MAX_ROWS, n - r0)
+                _lib.check(self.lib.lsm_resample_f32(
+                    _dev(audio[r0:]), fmt, rows, L, _dev(self.taps_dev), len(self.taps), self.up, self.down, self.delay,
+                    n_out, _dev(out[r0:]), stream), "lsm_resample_f32")
+        return out
+
+
+class ResampleStream(_ResampleBase):
+    """``n_streams`` open-ended PCM streams from ``rate_in`` to ``rate_out`` (`lsm_resample_stream_f32`, SPEC.md §1.8): every
+    ``push`` advances each stream by the whole blocks of ``down`` input samples it delivers -- any number, 0 included -- from
+    the history the bank holds (the stream's last ``history`` samples) and returns ``up`` samples per block: the next samples
+    of the stream's causal run, which lags `Resampler`'s alignment by ``delay`` samples.  A stream cut into pushes at any
+    block boundaries gives, byte for byte, the samples of its uncut run.  ``unit_blocks`` blocks (``unit_in`` samples) are the
+    smallest push that is a whole number, ``unit_hops``, of front-end hops (`resample_units`)."""
+
+    def __init__(self, rate_in: int, n_streams: int, rate_out: int = SAMPLE_RATE, device=None):
+        self.n_streams = int(n_streams)
+        if self.n_streams < 1 or self.n_streams > Resampler.MAX_ROWS:
+            raise ValueError(f"ResampleStream needs n_streams in [1, {Resampler.MAX_ROWS}], got {n_streams}")
+        super().__init__(rate_in, rate_out, device)
+        self.unit_blocks, self.unit_in, self.unit_hops = resample_units(self.up, self.down)
+        self.state_bytes = int(self.lib.lsm_resample_state_bytes(len(self.taps), self.up))
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: their history back to zeros."""
+        slots = checked_slots(slots, self.n_streams)
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+
+    def push(self, audio, blocks=None, out: torch.Tensor | None = None):
+        """``audio`` (n_streams, G * down) float32 or int16: stream b's new samples are the first ``blocks[b] * down`` of its
+        row; ``blocks``: n_streams host integers in [0, G], or None for G everywhere.  Returns ``(out, counts)``: ``out``
+        float32 (n_streams, G * up) on the device and ``counts = blocks * up`` (int64, host) -- the first ``counts[b]``
+        samples of row b are the stream's next ones; what lies behind them is zeros, or what a caller-owned ``out`` held."""
+        audio, fmt = checked_pcm(audio, self.n_streams, self.down)
+        G = int(audio.shape[1]) // self.down
+        new = checked_counts(blocks, self.n_streams, G)
+        shape = (self.n_streams, G * self.up)
+        if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()
+                                or out.device != self.device):
+            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            if out is None:
+                out = torch.zeros(shape, dtype=torch.float32, device=self.device)
+            if self.identity:
+                live = torch.from_numpy(np.arange(G)[None, :] < new[:, None]).to(self.device)
+                out[live] = self._as_float(audio)[live]
+                return out, new * self.up
+            counts = None if blocks is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            _lib.check(self.lib.lsm_resample_stream_f32(
+                _dev(audio), fmt, self.n_streams, G, _dev(self.taps_dev), len(self.taps), self.up, self.down,
+                _dev(counts) if counts is not None else None, _dev(self.state), _dev(self.state), _dev(out),
+                torch.cuda.current_stream(self.device).cuda_stream), "lsm_resample_stream_f32")
+        return out, new * self.up
 
 
 _FRONT_ENDS: dict = {}

@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .frontend import as_float32, checked_slots, indexed_device
+from .frontend import as_float32, checked_counts, checked_pcm, checked_slots, indexed_device
 
 DEFAULT_STREAMS = 6
 # front-end streams of their own (0 = rotation: every step keeps to one stream).  Measured at 128 filters / 1000
@@ -620,9 +620,11 @@ class AudioStreamBank:
     """``StreamBank`` fed with audio: ``gt_stream`` (``frontend.GammatoneStream`` or ``frontend.MelStream``) turns every push of whole hops into the
     raster columns it completed, the bank keeps each stream's columns that do not yet fill a segment (fewer than
     ``segment_steps / n_thr`` of them) and forwards whole segments to an inner ``StreamBank`` over ``net``.  Both halves
-    continue from saved state, so the rows are those of each stream's one uncut run, audio to features."""
+    continue from saved state, so the rows are those of each stream's one uncut run, audio to features.  With a ``resampler``
+    (``frontend.ResampleStream``) in front, the streams arrive as PCM at its input rate, in whole units (SPEC.md §1.8)."""
 
-    def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None):
+    def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None,
+                 resampler=None):
         # the refusals come before anything touches a device
         streamed = getattr(gt_stream, "filterbank", None) == "gammatone" or getattr(gt_stream, "streamed", None) is True
         if not streamed or not hasattr(gt_stream, "push"):
@@ -634,9 +636,15 @@ class AudioStreamBank:
             raise ValueError(f"segment_steps = {segment_steps} must be a positive multiple of the front end's {n_thr} "
                              f"thresholds: a column is {n_thr} steps and is never split over two segments")
         stream_window_plan(0, 0, int(window_segments), int(hop_segments))        # hop_segments <= window_segments
+        if resampler is not None:
+            if int(resampler.n_streams) != int(gt_stream.n_streams):
+                raise ValueError(f"the resampler serves {resampler.n_streams} streams, the front end {gt_stream.n_streams}")
+            if resampler.unit_blocks * resampler.up != resampler.unit_hops * int(gt_stream.hop):
+                raise ValueError(f"a unit of the resampler is {resampler.unit_blocks * resampler.up} samples, not "
+                                 f"{resampler.unit_hops} hops of the front end's {gt_stream.hop}")
         if net.n_channels != gt_stream.n_channels:
             raise ValueError(f"the front end has {gt_stream.n_channels} channels, the reservoir {net.n_channels}")
-        self.gt, self.net, self.S, self.n_thr = gt_stream, net, S, n_thr
+        self.gt, self.net, self.S, self.n_thr, self.resampler = gt_stream, net, S, n_thr, resampler
         self.n_streams = int(gt_stream.n_streams)
         self.bank = StreamBank(net, self.n_streams, S, window_segments, hop_segments, feature_keys)
         # time-major: an item is one raster step, (C,)
@@ -649,14 +657,21 @@ class AudioStreamBank:
 
     def reset(self, slots) -> None:
         """The streams in ``slots`` have ended and new ones take their places: both halves and the pending columns."""
+        if self.resampler is not None:
+            self.resampler.reset(slots)
         self.gt.reset(slots)
         self.bank.reset(slots)
         self.pending.reset(checked_slots(slots, self.n_streams))
 
     def push(self, audio, hops=None):
         """``audio`` (n_streams, H * hop) float32 and ``hops`` as ``GammatoneStream.push`` takes them.  Returns
-        ``(rows, counts)`` with ``StreamBank.push``'s meaning: the sliding-window rows this push completed."""
+        ``(rows, counts)`` with ``StreamBank.push``'s meaning: the sliding-window rows this push completed.
+        With a ``resampler`` (``frontend.ResampleStream``): ``audio`` (n_streams, U * unit_in) float32 or int16 at the
+        resampler's input rate and ``hops`` per-stream UNIT counts in [0, U] (None: U everywhere); stream b's first
+        ``hops[b] * unit_in`` samples are resampled and reach the front end as ``hops[b] * unit_hops`` hops."""
         S = self.S
+        if self.resampler is not None:
+            audio, hops = self._resampled(audio, hops)
         raster, cols = self.gt.push(audio, hops)
         dev = self.net.device
         with torch.cuda.device(dev):
@@ -666,6 +681,15 @@ class AudioStreamBank:
             self.pending.keep(run, total, total - segs * S)
             joined = run[:, :int(segs.max()) * S].transpose(1, 2).contiguous()
         return self.bank.push(joined, segs)
+
+
+    def _resampled(self, audio, units):
+        """A push at the resampler's input rate -> ``(samples, hops)`` as the front end takes them."""
+        rs = self.resampler
+        audio, _ = checked_pcm(audio, self.n_streams, rs.unit_in)
+        units = checked_counts(units, self.n_streams, int(audio.shape[1]) // rs.unit_in, "units")
+        samples, _ = rs.push(audio, units * rs.unit_blocks)
+        return samples, units * rs.unit_hops
 
 
 def sliding_features_from_recordings(recordings, fe, net, feature_keys, segment_steps: int, window_segments: int,
