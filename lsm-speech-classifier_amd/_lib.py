@@ -111,6 +111,16 @@ RESAMPLE_SIGS = {
 }
 RESAMPLE_SYMBOLS = tuple(RESAMPLE_SIGS)
 
+# include/lsm_hip_adaptive.h (SPEC.md §1.9): the adaptive-range encoder behind the streamed front ends' dB columns
+_ADAPTIVE_ENCODE = (c_int, [c_void, c_int, c_int, c_int, c_void, c_int, c_void, c_void, c_int, c_int, c_void, c_void, c_void,
+                            c_void, c_void, c_void])
+ADAPTIVE_SIGS = {
+    "lsm_adaptive_state_bytes": (C.c_long, [c_int, c_int, c_int]),
+    "lsm_adaptive_encode_f64": _ADAPTIVE_ENCODE,
+    "lsm_adaptive_encode_f32": _ADAPTIVE_ENCODE,
+}
+ADAPTIVE_SYMBOLS = tuple(ADAPTIVE_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -159,7 +169,7 @@ def load():
             f"{path} was built from other sources than this tree's (build id {_build.built_id(path)}, sources "
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
-                              + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items())):
+                              + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

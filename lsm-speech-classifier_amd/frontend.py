@@ -584,6 +584,160 @@ class MelStream(_AudioStreamBase):
         return raster, cols
 
 
+# ---- adaptive normalisation range (SPEC.md §1.9, include/lsm_hip_adaptive.h) ---------------------------------------------
+ADAPTIVE_WINDOW_COLS = 100          # columns of STREAM_HOP samples: one second, the reference's own window
+ADAPTIVE_MAX_WINDOW = 4096
+_ADAPTIVE_DTYPES = {torch.float64: np.float64, torch.float32: np.float32}
+
+
+class AdaptiveEncoder:
+    """The spike encoder with a sliding normalisation range (`lsm_adaptive_encode_f64` / `_f32`, SPEC.md §1.9): dB columns
+    of ``n_streams`` streams in, raster columns out.  Column c is normalised with the minimum and maximum of the stream's
+    columns ``max(0, c - window_cols + 1) .. c`` after the 80 dB floor -- the reference's per-clip rule made causal -- and
+    goes through the hysteresis latches, which the encoder carries over pushes together with the extrema of the last
+    ``window_cols - 1`` columns.  A stream cut into pushes anywhere gives, byte for byte, the raster of its uncut run.
+    ``dtype``: torch.float64 (the gammatone stream's dB) or torch.float32 (the mel stream's)."""
+
+    def __init__(self, n_filters: int, n_streams: int, dtype, window_cols: int = ADAPTIVE_WINDOW_COLS, thresholds=None,
+                 gap: float = HYSTERESIS_GAP, redundancy: int = REDUNDANCY_FACTOR, device=None):
+        self.n_filters, self.n_streams = int(n_filters), int(n_streams)
+        self.window_cols, self.redundancy = int(window_cols), int(redundancy)
+        if isinstance(dtype, torch.dtype):
+            if dtype not in _ADAPTIVE_DTYPES:
+                raise ValueError(f"dtype must be float64 or float32, got {dtype}")
+            self.dtype = dtype
+        else:
+            if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+                raise ValueError(f"dtype must be float64 or float32, got {dtype!r}")
+            self.dtype = torch.float64 if np.dtype(dtype) == np.dtype(np.float64) else torch.float32
+        if self.n_filters < 1:
+            raise ValueError(f"n_filters must be >= 1, got {n_filters}")
+        if self.n_streams < 1 or self.redundancy < 1:
+            raise ValueError(f"AdaptiveEncoder needs n_streams >= 1 and redundancy >= 1, got {n_streams}, {redundancy}")
+        if not 1 <= self.window_cols <= ADAPTIVE_MAX_WINDOW:
+            raise ValueError(f"window_cols = {window_cols} outside [1, {ADAPTIVE_MAX_WINDOW}]")
+        self.thresholds = list(SPIKE_THRESHOLDS if thresholds is None else thresholds)
+        self.gap = float(gap)
+        self.on, self.off = threshold_tables(self.thresholds, self.gap, _ADAPTIVE_DTYPES[self.dtype])
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        self._encode = self.lib.lsm_adaptive_encode_f64 if self.dtype == torch.float64 else self.lib.lsm_adaptive_encode_f32
+        elem = 8 if self.dtype == torch.float64 else 4
+        self.state_bytes = int(self.lib.lsm_adaptive_state_bytes(self.n_filters, self.window_cols, elem))
+        if self.state_bytes < 1:
+            raise ValueError(f"the encoder refuses n_filters = {n_filters} with window_cols = {window_cols}")
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+
+    @property
+    def n_thr(self) -> int:
+        return len(self.on)
+
+    @property
+    def n_channels(self) -> int:
+        return self.n_filters * self.redundancy
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: no carried columns, latches off."""
+        slots = checked_slots(slots, self.n_streams)
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+
+    def push_db(self, db, cols=None, raster_out=None, want_range: bool = False):
+        """``db`` (n_streams, n_filters, H) of the encoder's dtype: stream b's new columns are the first ``cols[b]`` of its
+        rows; ``cols``: n_streams host integers in [0, H], or None for H everywhere.  Returns ``raster`` uint8 (n_streams, C,
+        H * n_thr) on the device -- the first ``cols[b] * n_thr`` steps of stream b's rows; what lies behind them is zeros,
+        or what a caller-owned ``raster_out`` held -- or, with ``want_range``, ``(raster, lo, hi)``: the range every column
+        was normalised with, (n_streams, H) of the encoder's dtype, written like the raster."""
+        if isinstance(db, np.ndarray):
+            db = torch.from_numpy(np.ascontiguousarray(db))
+        if not torch.is_tensor(db) or db.dtype != self.dtype or db.dim() != 3 \
+                or tuple(db.shape[:2]) != (self.n_streams, self.n_filters) or db.shape[2] < 1:
+            raise ValueError(f"db must be a {self.dtype} ({self.n_streams}, {self.n_filters}, H) array with H >= 1, got "
+                             f"{getattr(db, 'dtype', type(db).__name__)} {tuple(getattr(db, 'shape', ()))}")
+        H = int(db.shape[2])
+        new = checked_counts(cols, self.n_streams, H, "cols")
+        shape = (self.n_streams, self.n_channels, H * self.n_thr)
+        if raster_out is not None and (raster_out.dtype != torch.uint8 or tuple(raster_out.shape) != shape
+                                       or not raster_out.is_contiguous() or raster_out.device != self.device):
+            raise ValueError(f"raster_out must be a contiguous uint8 {shape} tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            db = db.to(self.device).contiguous()
+            raster = torch.zeros(shape, dtype=torch.uint8, device=self.device) if raster_out is None else raster_out
+            lo = hi = None
+            if want_range:
+                lo = torch.zeros((self.n_streams, H), dtype=self.dtype, device=self.device)
+                hi = torch.zeros((self.n_streams, H), dtype=self.dtype, device=self.device)
+            counts = None if cols is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            _lib.check(self._encode(
+                _dev(db), self.n_streams, H, self.n_filters, _dev(counts) if counts is not None else None, self.window_cols,
+                _host(self.on), _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state),
+                _dev(raster), _dev(lo) if lo is not None else None, _dev(hi) if hi is not None else None,
+                torch.cuda.current_stream(self.device).cuda_stream), "lsm_adaptive_encode")
+        return (raster, lo, hi) if want_range else raster
+
+
+class AdaptiveStream:
+    """A streamed front end (`GammatoneStream` or `MelStream`) whose columns are normalised with the range of the stream's
+    last ``window_cols`` columns instead of a calibration range (SPEC.md §1.9): every ``push`` runs ``inner``'s push for its
+    dB columns and then `AdaptiveEncoder.push_db` on them.  The raster no longer depends on the recording level, and no
+    calibration batch is needed: ``inner``'s ``db_range`` is a placeholder -- any valid range will do, it only feeds
+    ``inner``'s own raster, which goes to a scratch buffer and is not used.  Thresholds, gap and redundancy are ``inner``'s.
+    ``window_cols = 100`` columns of 10 ms are one second, the clip the reference normalises over: a stream that has held at
+    most ``window_cols`` columns is normalised exactly like the reference's clip of those columns.  The interface is
+    `GammatoneStream`'s, so `pipeline.AudioStreamBank` takes it in ``inner``'s place."""
+    streamed = True
+
+    def __init__(self, inner, window_cols: int = ADAPTIVE_WINDOW_COLS):
+        if getattr(inner, "filterbank", None) not in ("gammatone", "mel") or not isinstance(inner, _AudioStreamBase):
+            raise ValueError("AdaptiveStream wraps a streamed front end: frontend.GammatoneStream or frontend.MelStream")
+        self.inner = inner
+        self.filterbank = inner.filterbank
+        self.n_filters, self.n_streams, self.hop = inner.n_filters, inner.n_streams, inner.hop
+        self.redundancy, self.device = inner.redundancy, inner.device
+        self.db_dtype = torch.float64 if inner.filterbank == "gammatone" else torch.float32
+        self.encoder = AdaptiveEncoder(inner.n_filters, inner.n_streams, self.db_dtype, window_cols, inner.thresholds,
+                                       inner.gap, inner.redundancy, inner.device)
+        self.window_cols = self.encoder.window_cols
+        self._scratch = None                                            # (H, inner raster, dB) of the last push's shape
+
+    @property
+    def n_thr(self) -> int:
+        return self.encoder.n_thr
+
+    @property
+    def n_channels(self) -> int:
+        return self.encoder.n_channels
+
+    @property
+    def seen(self) -> np.ndarray:
+        """Hops since each stream's start: ``inner``'s count."""
+        return self.inner.seen
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: both halves start over."""
+        checked_slots(slots, self.n_streams)
+        self.inner.reset(slots)
+        self.encoder.reset(slots)
+
+    def push(self, audio, hops=None, raster_out=None, want_db: bool = False):
+        """``audio`` and ``hops`` as `GammatoneStream.push` takes them.  Returns ``(raster, cols)`` with its meaning -- the
+        first ``cols[b] * n_thr`` steps of stream b's rows are the columns this push completed -- or, with ``want_db``,
+        ``(raster, cols, db)``: ``inner``'s dB columns (n_streams, F, H), float64 for gammatone and float32 for mel."""
+        audio, H, _ = self.inner._pushed(audio, hops)
+        with torch.cuda.device(self.device):
+            if self._scratch is None or self._scratch[0] != H:
+                self._scratch = (H, torch.zeros((self.n_streams, self.n_channels, H * self.n_thr), dtype=torch.uint8,
+                                                device=self.device),
+                                 torch.zeros((self.n_streams, self.n_filters, H), dtype=self.db_dtype, device=self.device))
+            _, unused, db = self._scratch
+            if want_db:                                                 # the caller keeps it: not the buffer of the next push
+                db = torch.zeros_like(db)
+            _, cols, db, _ = self.inner.push(audio, hops, raster_out=unused, db_out=db)
+            # every stream completed all H columns (the steady state): no count array to upload
+            raster = self.encoder.push_db(db, None if (cols == H).all() else cols, raster_out=raster_out)
+        return (raster, cols, db) if want_db else (raster, cols)
+
+
 # ---- polyphase resampler (SPEC.md §1.8, include/lsm_hip_resample.h) -----------------------------------------------------
 RESAMPLE_HALF_WIDTH = 10            # scipy.signal.resample_poly: half = 10 * max(up, down)
 RESAMPLE_KAISER_BETA = 5.0          # its default window, ('kaiser', 5.0)
