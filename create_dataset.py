@@ -109,17 +109,20 @@ def _list_files(commands, root: Path, per_class: int, verbose: bool = True):
     return listing
 
 
-def _load_listing(listing):
+def _load_listing(listing, kept=None):
+    """``kept``, when given, receives the positions in ``listing`` of the files that could be read."""
     clips, labels = [], []
-    for f, label in listing:
+    for at, (f, label) in enumerate(listing):
         audio = load_audio_file(f)
         if audio is not None:
             clips.append(audio)
             labels.append(label)
+            if kept is not None:
+                kept.append(at)
     return clips, labels
 
 
-def _load_listing_device(listing, device=None):
+def _load_listing_device(listing, device=None, kept=None):
     """`_load_listing` with the resampling on the GPU (`--resample device`): the files are decoded to mono at their own
     rates on the host, grouped by rate, every group padded with zeros to a common length and resampled in one launch
     (`frontend.Resampler`, SPEC.md 1.8).  Returns ``(clips, labels)``: a float32 (n, 16000) DEVICE tensor in listing order
@@ -128,10 +131,12 @@ def _load_listing_device(listing, device=None):
     fe = _frontend()
     want = int(SAMPLE_RATE * DURATION)
     decoded, labels = [], []
-    for f, label in listing:
+    for at, (f, label) in enumerate(listing):
         try:
             decoded.append(_decode_wav(f))
             labels.append(label)
+            if kept is not None:
+                kept.append(at)
         except Exception as exc:
             print(f"Error loading {f}: {exc}")
     if not decoded:
@@ -161,6 +166,47 @@ def _load_listing_device(listing, device=None):
 
 def _collect_audio(commands, root: Path, per_class: int):
     return _load_listing(_list_files(commands, root, per_class))
+
+
+# ---- corruption on the device (SPEC.md 1.10): --noise-dir, --snr-db, --time-shift-ms, --level-db, --augment-seed --------
+SYNTHETIC_NOISE_ROWS = 4
+SYNTHETIC_NOISE_SECONDS = 4
+DEFAULT_SNR_DB = 10.0
+
+
+def load_noise_bank(noise_dir, seed: int = 42) -> np.ndarray:
+    """The noise bank (M, L) float32 at 16 kHz: every wav under ``noise_dir`` in sorted order, read through `_decode_wav`
+    and resampled like a clip, a shorter file repeated up to the longest one's length (the mixer wraps a row anyway);
+    ``"synthetic"``: `synth.coloured_noise`.  None: one silent sample, for a shift or a level without noise."""
+    if noise_dir is None:
+        return np.zeros((1, 1), dtype=np.float32)
+    if str(noise_dir) == "synthetic":
+        from lsm_speech_classifier_amd import synth
+        return synth.coloured_noise(SYNTHETIC_NOISE_ROWS, SYNTHETIC_NOISE_SECONDS * SAMPLE_RATE, seed=seed)
+    rows = []
+    for f in sorted(Path(noise_dir).glob("*.wav")):
+        rate, data = _decode_wav(f)
+        if rate != SAMPLE_RATE:
+            from math import gcd
+            from scipy.signal import resample_poly
+            g = gcd(int(rate), SAMPLE_RATE)
+            data = resample_poly(data, SAMPLE_RATE // g, int(rate) // g).astype(np.float32)
+        if len(data):
+            rows.append(np.ascontiguousarray(data, dtype=np.float32))
+    if not rows:
+        raise ValueError(f"--noise-dir {noise_dir}: no readable wav file")
+    longest = max(len(r) for r in rows)
+    return np.stack([np.resize(r, longest) for r in rows])
+
+
+def corruption(augment, n_listed: int):
+    """``augment`` (`augment_from_args`) -> ``(noise bank, frontend.MixPlan of all n_listed clips in listing order)``."""
+    bank = load_noise_bank(augment["noise_dir"], augment["seed"])
+    snr = augment["snr_db"] if augment["noise_dir"] is not None else np.inf
+    plan = _frontend().mix_plan(n_listed, bank.shape[0], bank.shape[1], DEFAULT_SNR_DB if snr is None else snr,
+                                max_shift=int(round(augment["time_shift_ms"] * SAMPLE_RATE / 1000.0)),
+                                level_db=augment["level_db"], seed=augment["seed"])
+    return bank, plan
 
 
 def _synthetic_audio(commands, per_class: int):
@@ -193,13 +239,15 @@ def collect_audio(commands=None, dataset_root=None, max_per_class: int = MAX_SAM
 
 def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
-                   output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host"):
+                   output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host", augment=None):
     """Build File 1.  The first two arguments are the reference's; the keyword arguments expose
     what the reference hard-codes (class list, corpus folder, per-class cap) plus a synthetic
     corpus for machines without Speech Commands.  ``packed=True`` writes the bit-packed schema of
     ``lsm_speech_classifier_amd.spikefile`` (rasters packed on the GPU, 8x fewer bytes off the
     device and on disk); the default is the reference's uint8 schema.  ``resample="device"`` resamples files that are not
-    at 16 kHz on the GPU (`_load_listing_device`) instead of one by one on the host.
+    at 16 kHz on the GPU (`_load_listing_device`) instead of one by one on the host.  ``augment`` (`augment_from_args`):
+    every clip is shifted, scaled and mixed with noise on the GPU before the front end (SPEC.md 1.10), by a plan drawn for
+    the whole listing in listing order -- a shard takes its slice, so any number of ranks writes the same bytes.
 
     Under a launcher (torchrun: RANK / WORLD_SIZE) the clip loop of create_dataset.py:143 shards: rank r reads
     and encodes the r-th contiguous block of the file listing on its own GPU, the raster blocks are all-gathered
@@ -213,18 +261,22 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     if rank == 0:
         print(f"Creating dataset with filterbank: {filterbank}, filters: {n_filters}"
               + (f" ({world} ranks)" if world > 1 else ""))
+    kept = [] if augment else None          # positions in the shard's part of the listing of the clips that were read
     if synthetic_per_class > 0:
         clips, labels = _synthetic_audio(commands, synthetic_per_class)
+        n_listed = len(clips)
         lo, hi = lsm_dist.shard_range(len(clips), rank, world)
         clips, labels = clips[lo:hi], labels[lo:hi]
+        kept = list(range(hi - lo)) if augment else None
     else:
         listing = _list_files(commands, root, max_per_class, verbose=rank == 0)
+        n_listed = len(listing)
         lo, hi = lsm_dist.shard_range(len(listing), rank, world)
         if resample == "device":
-            clips, labels = _load_listing_device(listing[lo:hi], lsm_dist.local_device() if world > 1 else None)
+            clips, labels = _load_listing_device(listing[lo:hi], lsm_dist.local_device() if world > 1 else None, kept)
             clips = [] if clips is None else clips
         else:
-            clips, labels = _load_listing(listing[lo:hi])
+            clips, labels = _load_listing(listing[lo:hi], kept)
     if not len(clips) and world == 1:
         print("\nERROR: No audio files were successfully processed.")
         return
@@ -235,11 +287,18 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
                                    thresholds=SPIKE_THRESHOLDS, gap=HYSTERESIS_GAP,
                                    time_bins=TIME_BINS, n_samples=int(SAMPLE_RATE * DURATION))
     from lsm_speech_classifier_amd import spikefile
+    mixer = plan = None
+    if augment:
+        bank, plan = corruption(augment, n_listed)
+        plan = plan.take(lo + np.asarray(kept, dtype=np.int64))
+        mixer = _frontend().NoiseMixer(bank, device=dev)
     parts, n_spikes = [], 0
     for a in range(0, len(clips), ENCODE_BATCH):
         batch = clips[a:a + ENCODE_BATCH]
         if not torch.is_tensor(batch):
             batch = np.stack(batch)
+        if mixer is not None:
+            batch = mixer.mix(batch, *plan.part(a, a + ENCODE_BATCH))
         raster = fe.encode(batch)
         n_spikes += int(raster.count_nonzero())
         part = _frontend().pack_raster(raster) if packed else raster
@@ -290,6 +349,42 @@ def add_corpus_flags(ap):
                     help="Generate this many synthetic clips per class instead of reading wav files.")
 
 
+def _number_or_range(text, flag):
+    """"A" or "A,B" -> a float or a (lo, hi) tuple."""
+    try:
+        values = [float(v) for v in str(text).split(",")]
+    except ValueError:
+        values = []
+    if len(values) not in (1, 2):
+        raise SystemExit(f"{flag} takes a number or two separated by a comma, got {text!r}")
+    return values[0] if len(values) == 1 else (min(values), max(values))
+
+
+def add_augment_flags(ap):
+    """The corruption flags (shared with main.py, which forwards them).  Without any of them nothing changes."""
+    ap.add_argument("--noise-dir", type=str, default=None,
+                    help="Folder of background-noise wav files mixed into every clip on the GPU, or 'synthetic'.")
+    ap.add_argument("--snr-db", type=str, default=None,
+                    help=f"Signal-to-noise ratio in dB, A or a range A,B drawn per clip (default {DEFAULT_SNR_DB:g}).")
+    ap.add_argument("--time-shift-ms", type=float, default=0.0,
+                    help="Shift every clip by up to this many milliseconds either way, zero filled.")
+    ap.add_argument("--level-db", type=str, default=None, help="Level change in dB, A or a range A,B drawn per clip.")
+    ap.add_argument("--augment-seed", type=int, default=42, help="Seed of the per-clip draws.")
+
+
+def augment_from_args(a):
+    """None when no corruption flag is given, else what create_dataset(augment=...) takes."""
+    if a.noise_dir is None and not a.time_shift_ms and a.level_db is None:
+        if a.snr_db is not None:
+            raise SystemExit("--snr-db needs --noise-dir")
+        return None
+    if a.time_shift_ms < 0:
+        raise SystemExit("--time-shift-ms must be >= 0")
+    return dict(noise_dir=a.noise_dir, snr_db=None if a.snr_db is None else _number_or_range(a.snr_db, "--snr-db"),
+                time_shift_ms=float(a.time_shift_ms),
+                level_db=0.0 if a.level_db is None else _number_or_range(a.level_db, "--level-db"), seed=int(a.augment_seed))
+
+
 def commands_from_args(a):
     if a.commands_file:
         return read_commands_file(a.commands_file)
@@ -310,7 +405,9 @@ if __name__ == "__main__":
     ap.add_argument("--resample", type=str, default="host", choices=["host", "device"],
                     help="Where files that are not at 16 kHz are resampled: one by one on the host (default), or grouped by "
                          "rate on the GPU.")
+    add_augment_flags(ap)
     a = ap.parse_args()
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,
-                   synthetic_per_class=a.synthetic_per_class, packed=a.packed, resample=a.resample)
+                   synthetic_per_class=a.synthetic_per_class, packed=a.packed, resample=a.resample,
+                   augment=augment_from_args(a))

@@ -212,7 +212,7 @@ def run_network_diagnostics(lsm, X_sample_batch):
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
                     num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
-                    time_segments=1):
+                    time_segments=1, corrupt=None):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -232,7 +232,11 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     printed here.  Returns the test accuracy then (None otherwise, like the reference's main()).
 
     `time_segments` = K > 1: every clip is read in K equal time segments (`pipeline.HotPath(time_segments=K)`); File 2
-    keeps its keys, the feature arrays get K times the columns."""
+    keeps its keys, the feature arrays get K times the columns.
+
+    `corrupt` = ``(noise bank (M, L) float32, frontend.MixPlan of the n clips)``: every clip is shifted, scaled and mixed
+    with noise on the GPU before its front end (SPEC.md 1.10), the clips w_critico looks at included; a rank corrupts its
+    clips with their entries of the one plan."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
@@ -254,7 +258,13 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     dev = lsm_dist.local_device() if world > 1 else None
     fe = frontend.SpikeFrontEnd(n_filters, filterbank, device=dev)
     check_time_segments(fe.n_steps, time_segments)                  # refused with the reason before any work is done
-    head = fe.encode(audio[idx_train[:500]]).cpu().numpy()          # what w_critico and the diagnostics look at
+    mixer = plan = None
+    if corrupt is not None:
+        mixer, plan = frontend.NoiseMixer(corrupt[0], device=dev), corrupt[1]
+    head_audio = audio[idx_train[:500]]
+    if mixer is not None:
+        head_audio = mixer.mix(head_audio, *plan.take(idx_train[:500]))
+    head = fe.encode(head_audio).cpu().numpy()                      # what w_critico and the diagnostics look at
     params = _simulation_params(head[0], leak_variance_divisor, num_neurons, num_output_neurons, small_world_k, seed)
     with _rank0_only(rank):
         optimal_weight = calculate_theoretical_w_critico(params, head) * multiplier
@@ -275,7 +285,8 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
         """(len(idx), n_feat) float32 rows in dataset order, STILL ON THE DEVICE (every rank holds all of them)."""
         lo, hi = lsm_dist.shard_range(len(idx), rank, world)
         local = pipeline.features_from_audio(audio[idx[lo:hi]], fe, lsm, keys, batch=batch, device_out=True,
-                                             time_segments=time_segments)
+                                             time_segments=time_segments,
+                                             corrupt=(mixer, plan.take(idx[lo:hi])) if mixer is not None else None)
         return lsm_dist.gather_rows(local, len(idx))
 
     X_train_dev = split_features(idx_train)

@@ -121,6 +121,16 @@ ADAPTIVE_SIGS = {
 }
 ADAPTIVE_SYMBOLS = tuple(ADAPTIVE_SIGS)
 
+# include/lsm_hip_mix.h (SPEC.md §1.10): the noise mixer in front of the front ends, batch and streamed
+MIX_SIGS = {
+    "lsm_mix_power_f32": (c_int, [c_void, c_int, c_int, c_void, c_void]),
+    "lsm_mix_f32": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_void,
+                            c_void, c_void, c_void]),
+    "lsm_mix_stream_f32": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_void, c_void, c_void, c_void, c_void,
+                                   c_void, c_void, c_void]),
+}
+MIX_SYMBOLS = tuple(MIX_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -169,7 +179,8 @@ def load():
             f"{path} was built from other sources than this tree's (build id {_build.built_id(path)}, sources "
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
-                              + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())):
+                              + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
+                              + list(MIX_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

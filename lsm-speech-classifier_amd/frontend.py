@@ -935,6 +935,263 @@ class ResampleStream(_ResampleBase):
         return out, new * self.up
 
 
+# ---- noise mixer (SPEC.md §1.10, include/lsm_hip_mix.h) -----------------------------------------------------------------
+MIX_MAX_SAMPLES = 1 << 24
+
+
+class MixPlan(NamedTuple):
+    """Per-clip corruption parameters (`mix_plan`), host arrays of one length: ``snr_db`` float64 (+inf = clean), ``rows``
+    and ``offsets`` into the noise bank and ``shift`` in samples (int32), ``scale`` float32."""
+    snr_db: np.ndarray
+    rows: np.ndarray
+    offsets: np.ndarray
+    shift: np.ndarray
+    scale: np.ndarray
+
+    def part(self, lo: int, hi: int) -> "MixPlan":
+        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
+        return MixPlan(*(a[lo:hi] for a in self))
+
+    def take(self, idx) -> "MixPlan":
+        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
+        return MixPlan(*(a[np.asarray(idx, dtype=np.int64)] for a in self))
+
+
+def _range_draw(value, u: np.ndarray, name: str) -> np.ndarray:
+    """A scalar, or ``lo + (hi - lo) * u`` for a ``(lo, hi)`` range; float64."""
+    v = np.asarray(value, dtype=np.float64)
+    if v.shape == ():
+        return np.full(len(u), float(v), dtype=np.float64)
+    if v.shape != (2,) or not v[0] <= v[1]:
+        raise ValueError(f"{name} must be a number or a (lo, hi) range with lo <= hi, got {value!r}")
+    return v[0] + (v[1] - v[0]) * u
+
+
+def mix_plan(n_clips: int, n_noise_rows: int, noise_len: int, snr_db, max_shift: int = 0, level_db=0.0,
+             seed: int = 42) -> MixPlan:
+    """The corruption of every clip of a listing, drawn from ``np.random.RandomState(seed)`` for ALL ``n_clips`` clips in
+    listing order -- noise rows, noise offsets, shifts in [-max_shift, max_shift], then the SNRs and the levels -- so that
+    a shard or a batch takes its slice (`MixPlan.part`) and a multi-rank run corrupts every clip exactly as one process
+    does.  ``snr_db`` and ``level_db`` are a number or a ``(lo, hi)`` range drawn uniformly in dB; the draws are made in
+    either form, so a scalar changes no other array.  ``scale = float32(10 ** (level_db / 20))``."""
+    n, M, L, S = int(n_clips), int(n_noise_rows), int(noise_len), int(max_shift)
+    if n < 0 or M < 1 or L < 1 or S < 0:
+        raise ValueError(f"mix_plan needs n_clips >= 0, n_noise_rows >= 1, noise_len >= 1 and max_shift >= 0, got "
+                         f"{n_clips}, {n_noise_rows}, {noise_len}, {max_shift}")
+    rs = np.random.RandomState(int(seed))
+    rows = rs.randint(0, M, size=n).astype(np.int32)
+    offsets = rs.randint(0, L, size=n).astype(np.int32)
+    shift = rs.randint(-S, S + 1, size=n).astype(np.int32)
+    snr = _range_draw(snr_db, rs.random_sample(n), "snr_db")
+    level = _range_draw(level_db, rs.random_sample(n), "level_db")
+    snr_ratio(snr, n)                                            # refuses NaN and -inf
+    return MixPlan(snr, rows, offsets, shift, (10.0 ** (level / 20.0)).astype(np.float32))
+
+
+def snr_ratio(snr_db, n_clips: int) -> np.ndarray:
+    """``10 ** (-snr_db / 10)`` per clip in float64, the ``ratio`` of SPEC.md §1.10: ``snr_db`` a number or ``n_clips`` of
+    them; +inf means clean (ratio 0).  NaN, -inf and an SNR whose ratio overflows are refused."""
+    snr = np.asarray(snr_db, dtype=np.float64)
+    if snr.shape not in ((), (int(n_clips),)):
+        raise ValueError(f"snr_db must be a number or {n_clips} of them, got shape {snr.shape}")
+    with np.errstate(over="ignore"):
+        ratio = np.float64(10.0) ** (-snr / 10.0)
+    if np.isnan(snr).any() or not np.isfinite(ratio).all():
+        raise ValueError(f"snr_db must be a number above -3000 dB or +inf (clean); NaN and -inf are refused, got {snr_db!r}")
+    return np.broadcast_to(ratio, (int(n_clips),)).copy()
+
+
+def _per_clip(value, n: int, dtype, name: str):
+    """None, or a scalar or ``n`` values as a contiguous array of ``dtype``; integers must fit int32."""
+    if value is None:
+        return None
+    if torch.is_tensor(value):
+        value = value.cpu().numpy()
+    v = np.asarray(value)
+    if v.shape not in ((), (n,)):
+        raise ValueError(f"{name} must be a number or {n} of them, got shape {v.shape}")
+    if dtype == np.int32:
+        if v.dtype.kind not in "iu" or (v < -2 ** 31).any() or (v >= 2 ** 31).any():
+            raise ValueError(f"{name} must be integers that fit int32, got {value!r}")
+    elif v.dtype.kind not in "fiu":
+        raise ValueError(f"{name} must be numbers, got {v.dtype}")
+    return np.broadcast_to(v.astype(dtype), (n,)).copy()
+
+
+def checked_noise_bank(noise_bank) -> torch.Tensor:
+    """A noise bank as the mixer takes it: (M, L) float32 with M, L >= 1, NumPy (copied) or tensor; a 1-D array is one row."""
+    if isinstance(noise_bank, np.ndarray):
+        noise_bank = torch.from_numpy(np.array(noise_bank))
+    if not torch.is_tensor(noise_bank) or noise_bank.dtype != torch.float32:
+        raise ValueError("the noise bank must be a float32 NumPy array or tensor")
+    if noise_bank.dim() == 1:
+        noise_bank = noise_bank[None, :]
+    if noise_bank.dim() != 2 or noise_bank.shape[0] < 1 or noise_bank.shape[1] < 1 or noise_bank.shape[1] >= 2 ** 31:
+        raise ValueError(f"the noise bank must be (M, L) with M >= 1 and 1 <= L < 2^31, got {tuple(noise_bank.shape)}")
+    return noise_bank.contiguous()
+
+
+def mix_arguments(audio, snr_db, rows=None, offsets=None, shift=None, scale=None, out=None):
+    """The arguments of `NoiseMixer.mix` checked on the host, before anything touches a device: ``(audio tensor, ratio,
+    rows, offsets, shift, scale)``, the per-clip ones as host arrays (None where not given).  Raises ValueError."""
+    if isinstance(audio, np.ndarray):
+        if audio.dtype != np.float32:
+            raise ValueError(f"audio must be float32, got {audio.dtype}")
+        audio = torch.from_numpy(np.ascontiguousarray(audio))
+    if not torch.is_tensor(audio) or audio.dtype != torch.float32 or audio.dim() != 2 or audio.shape[1] < 1 \
+            or audio.shape[1] > MIX_MAX_SAMPLES:
+        raise ValueError(f"audio must be (n, L) float32 with 1 <= L <= {MIX_MAX_SAMPLES}, NumPy or tensor, got "
+                         f"{tuple(audio.shape) if hasattr(audio, 'shape') else type(audio).__name__}")
+    audio = audio.contiguous()
+    n = int(audio.shape[0])
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != tuple(audio.shape) \
+                or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 {tuple(audio.shape)} tensor")
+        if out is audio or (n and out.data_ptr() == audio.data_ptr()):
+            raise ValueError("out must not be audio: a shift reads across what it would write")
+    return (audio, snr_ratio(snr_db, n), _per_clip(rows, n, np.int32, "rows"), _per_clip(offsets, n, np.int32, "offsets"),
+            _per_clip(shift, n, np.int32, "shift"), _per_clip(scale, n, np.float32, "scale"))
+
+
+class NoiseMixer:
+    """A noise bank ``(M, L)`` float32 on the device and the mixer kernels over it (SPEC.md §1.10): `mix` shifts, scales and
+    adds a bank row at a requested SNR to every clip of a batch in one launch (`lsm_mix_f32`); `power` is the row power the
+    SNR is defined with (`lsm_mix_power_f32`); `MixStream` is the streamed form."""
+
+    def __init__(self, noise_bank, device=None):
+        bank = checked_noise_bank(noise_bank)
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        self.noise = bank.to(self.device)
+        self.n_rows, self.noise_len = (int(v) for v in bank.shape)
+        self._row_power = None
+
+    def _up(self, a):
+        return None if a is None else torch.from_numpy(a).to(self.device, non_blocking=True)
+
+    def power(self, x) -> torch.Tensor:
+        """``x`` (R, n) float32 -> the row powers P, float64 (R,) on the device."""
+        x = as_float32(x)
+        if x.dim() != 2 or x.shape[1] < 1 or x.shape[1] > MIX_MAX_SAMPLES:
+            raise ValueError(f"x must be (R, n) with 1 <= n <= {MIX_MAX_SAMPLES}, got {tuple(x.shape)}")
+        with torch.cuda.device(self.device):
+            x = x.to(self.device)
+            out = torch.empty(int(x.shape[0]), dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.lsm_mix_power_f32(_dev(x), int(x.shape[0]), int(x.shape[1]), _dev(out),
+                                                  torch.cuda.current_stream(self.device).cuda_stream), "lsm_mix_power_f32")
+        return out
+
+    @property
+    def row_power(self) -> np.ndarray:
+        """P of every bank row over its L samples, float64 on the host (computed once; the first use synchronises)."""
+        if self._row_power is None:
+            self._row_power = self.power(self.noise).cpu().numpy()
+        return self._row_power
+
+    def mix(self, audio, snr_db, rows=None, offsets=None, shift=None, scale=None, out=None, want_gain: bool = False):
+        """``audio`` (n, L) float32, NumPy or tensor -> the corrupted clips, float32 (n, L) on the device.  Per clip (a number
+        or n of them): ``snr_db`` (+inf = clean; NaN and -inf are refused), ``rows`` and ``offsets`` into the bank (a row
+        outside the bank is clamped, an offset taken modulo the row length; the row wraps), ``shift`` in samples (zero
+        filled, clamped to the clip) and ``scale``; None is 0, 0, 0 and 1.  ``out``: a caller-owned contiguous float32
+        (n, L) tensor on the device, never ``audio``.  ``want_gain``: returns ``(out, gain (n), powers (n, 2))``, float64 on
+        the device -- g and {Px, Pv} of SPEC.md §1.10."""
+        audio, ratio, rows, offsets, shift, scale = mix_arguments(audio, snr_db, rows, offsets, shift, scale, out)
+        n, L = (int(v) for v in audio.shape)
+        if out is not None and out.device != self.device:
+            raise ValueError(f"out must be on {self.device}")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            if out is None:
+                out = torch.empty((n, L), dtype=torch.float32, device=self.device)
+            gain = torch.empty(n, dtype=torch.float64, device=self.device) if want_gain else None
+            powers = torch.empty((n, 2), dtype=torch.float64, device=self.device) if want_gain else None
+            args = [self._up(a) for a in (rows, offsets, shift, scale, ratio)]
+            _lib.check(self.lib.lsm_mix_f32(
+                _dev(audio), n, L, _dev(self.noise), self.n_rows, self.noise_len,
+                *(_dev(a) if a is not None else None for a in args), _dev(out),
+                _dev(gain) if want_gain else None, _dev(powers) if want_gain else None,
+                torch.cuda.current_stream(self.device).cuda_stream), "lsm_mix_f32")
+        return (out, gain, powers) if want_gain else out
+
+
+class MixStream:
+    """``n_streams`` open-ended streams through the mixer's streamed form (`lsm_mix_stream_f32`): every `push` scales each
+    stream's new samples and adds the next samples of its noise row, from the position the bank holds -- a stream's whole
+    state.  A stream cut into pushes anywhere gives, byte for byte, the samples of its uncut run.  A stream has no clip to
+    take a power of, so `set` computes its gain on the host from the speech power the caller states.  Until `set`, a stream
+    passes unchanged (gain 0, scale 1)."""
+
+    def __init__(self, mixer: NoiseMixer, n_streams: int):
+        self.mixer, self.n_streams, self.device = mixer, int(n_streams), mixer.device
+        if self.n_streams < 1:
+            raise ValueError(f"MixStream needs n_streams >= 1, got {n_streams}")
+        self.pos = torch.zeros(self.n_streams, dtype=torch.int32, device=self.device)
+        self.gain = torch.zeros(self.n_streams, dtype=torch.float64, device=self.device)
+        self.scale = torch.ones(self.n_streams, dtype=torch.float32, device=self.device)
+        self.rows = torch.zeros(self.n_streams, dtype=torch.int32, device=self.device)
+
+    def set(self, slots, snr_db, speech_power, rows=0, scale=1.0) -> np.ndarray:
+        """The corruption of the streams in ``slots`` from here on: ``speech_power`` is the mean square per sample of the
+        stream as it arrives (before ``scale``), ``rows`` the bank row (refused outside the bank).  The gain is
+        ``sqrt(scale^2 * speech_power * ratio / (P(row) / L))`` in float64 on the host, 0 for a clean stream or a silent
+        row; it is returned.  The noise positions stay where they are."""
+        slots = checked_slots(slots, self.n_streams)
+        k, mixer = len(slots), self.mixer
+        ratio = snr_ratio(snr_db, k)
+        sp = _per_clip(speech_power, k, np.float64, "speech_power")
+        rows = _per_clip(rows, k, np.int32, "rows")
+        sc = _per_clip(scale, k, np.float32, "scale")
+        if not (np.isfinite(sp).all() and (sp >= 0).all()):
+            raise ValueError(f"speech_power must be finite and >= 0, got {speech_power!r}")
+        if ((rows < 0) | (rows >= mixer.n_rows)).any():
+            raise ValueError(f"rows {rows.tolist()} outside [0, {mixer.n_rows})")
+        per_sample = mixer.row_power[rows] / mixer.noise_len
+        noisy = (ratio > 0) & (per_sample > 0)
+        a = sc.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            gain = np.where(noisy, np.sqrt(a * a * sp * ratio / np.where(noisy, per_sample, 1.0)), 0.0)
+        at = torch.from_numpy(slots).to(self.device)
+        self.gain[at] = torch.from_numpy(gain).to(self.device)
+        self.scale[at] = torch.from_numpy(sc).to(self.device)
+        self.rows[at] = torch.from_numpy(rows).to(self.device)
+        return gain
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: their noise positions back to 0."""
+        slots = checked_slots(slots, self.n_streams)
+        self.pos[torch.from_numpy(slots).to(self.device)] = 0
+
+    def push(self, audio, counts=None, out: torch.Tensor | None = None):
+        """``audio`` (n_streams, H) float32: stream b's new samples are the first ``counts[b]`` of its row; ``counts``:
+        n_streams host integers in [0, H], or None for H everywhere.  Returns ``(out, counts)``: float32 (n_streams, H) on
+        the device, whose first ``counts[b]`` samples of row b are mixed; behind them lies what ``audio`` held, or what a
+        caller-owned ``out`` held.  ``out`` may be ``audio`` (a device tensor): the mix is then in place."""
+        audio = as_float32(audio)
+        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] < 1 or audio.shape[1] > MIX_MAX_SAMPLES:
+            raise ValueError(f"audio must be ({self.n_streams}, H) with 1 <= H <= {MIX_MAX_SAMPLES}, got {tuple(audio.shape)}")
+        H = int(audio.shape[1])
+        new = checked_counts(counts, self.n_streams, H, "counts")
+        if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (self.n_streams, H)
+                                or not out.is_contiguous() or out.device != self.device):
+            raise ValueError(f"out must be a contiguous float32 {(self.n_streams, H)} tensor on {self.device}")
+        mixer = self.mixer
+        with torch.cuda.device(self.device):
+            if out is None:                                     # a copy of the rows, mixed in place
+                out = audio.to(self.device, copy=True)
+                audio = out
+            else:
+                audio = audio.to(self.device)
+            cnt = None if counts is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            _lib.check(mixer.lib.lsm_mix_stream_f32(
+                _dev(audio), self.n_streams, H, _dev(mixer.noise), mixer.n_rows, mixer.noise_len,
+                _dev(cnt) if cnt is not None else None, _dev(self.gain), _dev(self.scale), _dev(self.rows),
+                _dev(self.pos), _dev(self.pos), _dev(out), torch.cuda.current_stream(self.device).cuda_stream),
+                "lsm_mix_stream_f32")
+        return out, new
+
+
 _FRONT_ENDS: dict = {}
 
 

@@ -81,13 +81,19 @@ class HotPath:
     everything on the current stream); `fe_streams` = front-end streams of their own (0 = rotation: a step keeps to
     one of the `streams`; None = DEFAULT_FE_STREAMS).  `time_segments` = K > 1: a step's reservoir launch is the segmented
     one (`SNN.run_segments`, K segments of T // K steps, SPEC.md §4b) and a clip's row is its K segment rows side by side
-    (segment-major, then key-major: K times the columns); 1 = the whole-clip row, the calls of a pipeline without it."""
+    (segment-major, then key-major: K times the columns); 1 = the whole-clip row, the calls of a pipeline without it.
+    `mixer` = a `frontend.NoiseMixer`: a step submitted with `mix=` (a `frontend.MixPlan` of its clips) is corrupted on the
+    device before its front end (SPEC.md §1.10); without `mix` a step launches what it launches without a mixer."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
-                 fe_streams: int | None = None, time_segments: int = 1):
+                 fe_streams: int | None = None, time_segments: int = 1, mixer=None):
         if indexed_device(fe.device) != indexed_device(net.device):
             raise ValueError(f"front end on {fe.device}, reservoir on {net.device}")
+        if mixer is not None and indexed_device(mixer.device) != indexed_device(fe.device):
+            raise ValueError(f"mixer on {mixer.device}, front end on {fe.device}")
+        self.mixer = mixer                  # frontend.NoiseMixer or None: submit(mix=...) corrupts a step's clips with it
+        self._mixed = {}                    # (rotation slot, batch shape) -> the mix launch's output buffer
         if fe.n_channels != net.n_channels:
             raise ValueError(f"front end has {fe.n_channels} channels, reservoir expects {net.n_channels}")
         self.fe, self.net = fe, net
@@ -151,7 +157,7 @@ class HotPath:
             self.reservoir_events.append((e0, e1))
         return feats
 
-    def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False):
+    def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None):
         """Issue one step on the next stream of the rotation.  `audio`: (B, n_samples) float32 -- device tensor,
         or pinned/pageable host tensor / NumPy array, uploaded on the step's own stream.  Returns (features
         (B, n_keys*N_out) device tensor, stream it is produced on); the caller waits (`stream.synchronize()`,
@@ -169,15 +175,20 @@ class HotPath:
         with one chain per lane (twice the waves, each half as long), the reservoir launch as a lone launch would be laid
         out.  At the end of a burst the last front end otherwise runs alone on a quarter of the chip for ~2 ms while the
         rest drains (profiles/r04_tail_steps.txt); inside a long run the normal layouts use fewer CU-cycles.
+        `mix`: a `frontend.MixPlan` of this step's B clips (needs the pipeline's `mixer`): one more launch on the stream
+        that runs the step's front end, between the upload and `encode`, into a buffer the rotation slot owns; no host
+        synchronisation.
         Back-pressure: when `max_ahead` earlier steps have not finished, submit() first waits for the oldest."""
-        res, st = self._submit(audio, stats_out, after, out, stage, tail)
+        if mix is not None and (self.mixer is None or stage == "reservoir"):
+            raise ValueError("submit(mix=...) needs a HotPath built with a mixer and a step that has a front end")
+        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix)
         if st is not None and self.n_streams > 1:
             ev = torch.cuda.Event()
             ev.record(st)
             self._in_flight.append(ev)
         return res, st
 
-    def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False):
+    def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None):
         """submit() without the in-flight bookkeeping."""
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
@@ -191,7 +202,7 @@ class HotPath:
             topology = self._submit_two_stages
         else:
             topology = self._submit_rotation
-        return topology(slot, audio, stats_out, after, out, stage, tail)
+        return topology(slot, audio, stats_out, after, out, stage, tail, mix)
 
     def _wait_for_input(self, stream, cur, audio, after) -> None:
         """The ordering of a device input (`submit`): `stream` waits for `after`, or for what `cur` has issued so far."""
@@ -200,24 +211,24 @@ class HotPath:
         elif torch.is_tensor(audio) and audio.device == self.device:
             stream.wait_stream(cur)
 
-    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail):
+    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None):
         """Everything on the current stream."""
         cur = torch.cuda.current_stream(self.device)
         if after is not None:
             cur.wait_event(after)
         with torch.cuda.device(self.device):
-            x = audio if stage == "reservoir" else self._to_device(audio, slot)
+            x = audio if stage == "reservoir" else self._mix(self._to_device(audio, slot), mix, slot)
             return self._one(x, stats_out, out, stage, tail), cur
 
-    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail):
+    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None):
         """The step keeps to reservoir stream `slot`: its front end, then its reservoir launch."""
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             self._wait_for_input(st, cur, audio, after)
-            x = audio if stage == "reservoir" else self._to_device(audio, slot)
+            x = audio if stage == "reservoir" else self._mix(self._to_device(audio, slot), mix, slot)
             return self._one(x, stats_out, out, stage, tail), st
 
-    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail):
+    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None):
         """The front end on the next front-end stream, the reservoir launch on reservoir stream `slot` behind an event."""
         fslot = (self._step - 1) % self.n_fe_streams
         st, fst, cur = self.streams[slot], self.fe_streams[fslot], torch.cuda.current_stream(self.device)
@@ -225,7 +236,7 @@ class HotPath:
             with torch.cuda.stream(fst):
                 self._wait_for_input(fst, cur, audio, after)
                 low_latency = self._low_latency(tail)
-                x = self._to_device(audio, ("fe", fslot))
+                x = self._mix(self._to_device(audio, ("fe", fslot)), mix, ("fe", fslot))
                 # the front end's own decision (mel branch, > 1024 filters and LSM_FRONTEND_SPLIT=1 take the split
                 # route, which allocates its raster on the front-end stream): only the fused launch of a full step
                 # writes into the pipeline's rings, everything else goes through record_stream below
@@ -275,6 +286,16 @@ class HotPath:
                                                                       device=self.device)
         buf.copy_(audio, non_blocking=True)
         return buf
+
+    def _mix(self, x, mix, slot):
+        """The step's clips corrupted by `mix` on the current stream (the one that runs its front end), or `x` itself."""
+        if mix is None:
+            return x
+        key = (slot, tuple(x.shape))
+        buf = self._mixed.get(key)
+        if buf is None:
+            buf = self._mixed[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+        return self.mixer.mix(x, mix.snr_db, mix.rows, mix.offsets, mix.shift, mix.scale, out=buf)
 
     def prime(self, audio, stage: str = "full", min_ms: float = 0.0):
         """One untimed step on EVERY stream of the pipeline, then a synchronisation: each stream's first use
@@ -326,21 +347,25 @@ class HotPath:
         torch.cuda.current_stream(self.device).synchronize()
 
     # ---- many steps -------------------------------------------------------------------------
-    def run(self, audio_batches, out: torch.Tensor | None = None) -> torch.Tensor:
+    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None) -> torch.Tensor:
         """Feature rows of every batch, in order, as one (n_clips, n_feat) device tensor.  `audio_batches`
-        is an iterable of (B_i, n_samples) arrays/tensors (host or device)."""
+        is an iterable of (B_i, n_samples) arrays/tensors (host or device); `mixes`, when given, an iterable of one
+        `frontend.MixPlan` per batch (`submit(mix=...)`)."""
         self.fork_from_current()
         # The last TAIL_STEPS batches are submitted in the low-latency layouts: that needs a look-ahead of TAIL_STEPS
         # batches, not the whole list -- a lazily produced stream of (pinned or device) batches is consumed as it comes and
         # never held in full (ADVICE r4).
         from collections import deque
         parts, ahead, it = [], deque(), iter(audio_batches)
+        plans = iter(mixes) if mixes is not None else None
         for a in it:
-            ahead.append(a)
+            ahead.append((a, next(plans) if plans is not None else None))
             if len(ahead) > TAIL_STEPS:
-                parts.append(self.submit(ahead.popleft(), tail=False)[0])
+                a0, m0 = ahead.popleft()
+                parts.append(self.submit(a0, tail=False, mix=m0)[0])
         while ahead:
-            parts.append(self.submit(ahead.popleft(), tail=True)[0])
+            a0, m0 = ahead.popleft()
+            parts.append(self.submit(a0, tail=True, mix=m0)[0])
         self.synchronize()
         if not parts:
             n_keys = len(self.feature_keys) if self.feature_keys is not None else 8
@@ -353,13 +378,17 @@ class HotPath:
 
 
 def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1024,
-                        streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1):
+                        streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1, corrupt=None):
     """Host convenience for the drop-in scripts' in-memory path: (n, n_samples) float32 on the host ->
     (n, n_feat) float32 on the host (or, `device_out`, still on the GPU for a gather), batches of `batch` clips
     through the overlapped pipeline (pinned staging, uploads on the steps' streams).  n = 0 (an empty shard)
     gives an empty (0, n_feat) block.  `time_segments` = K > 1: K segment rows per clip side by side (`HotPath`), n_feat is
-    K times as wide."""
-    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments)
+    K times as wide.  `corrupt` = ``(frontend.NoiseMixer, frontend.MixPlan of the n clips)``: every batch is corrupted on
+    the device with its slice of the plan before its front end (SPEC.md §1.10)."""
+    mixer, plan = corrupt if corrupt is not None else (None, None)
+    if plan is not None and len(plan.rows) != len(audio):
+        raise ValueError(f"the plan covers {len(plan.rows)} clips, audio has {len(audio)}")
+    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer)
     pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
     if len(pinned):
         try:
@@ -367,7 +396,8 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
         except RuntimeError:
             pass
     with torch.cuda.device(hp.device):
-        feats = hp.run(pinned[lo:lo + batch] for lo in range(0, len(pinned), batch))
+        feats = hp.run((pinned[lo:lo + batch] for lo in range(0, len(pinned), batch)),
+                       mixes=(plan.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if plan is not None else None)
     return feats if device_out else feats.cpu().numpy()
 
 
@@ -621,10 +651,12 @@ class AudioStreamBank:
     raster columns it completed, the bank keeps each stream's columns that do not yet fill a segment (fewer than
     ``segment_steps / n_thr`` of them) and forwards whole segments to an inner ``StreamBank`` over ``net``.  Both halves
     continue from saved state, so the rows are those of each stream's one uncut run, audio to features.  With a ``resampler``
-    (``frontend.ResampleStream``) in front, the streams arrive as PCM at its input rate, in whole units (SPEC.md §1.8)."""
+    (``frontend.ResampleStream``) in front, the streams arrive as PCM at its input rate, in whole units (SPEC.md §1.8).  With a
+    ``mixer`` (``frontend.MixStream``), every stream's new samples are corrupted on the device (SPEC.md §1.10) behind the
+    resampler and in front of the front end."""
 
     def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None,
-                 resampler=None):
+                 resampler=None, mixer=None):
         # the refusals come before anything touches a device
         streamed = getattr(gt_stream, "filterbank", None) == "gammatone" or getattr(gt_stream, "streamed", None) is True
         if not streamed or not hasattr(gt_stream, "push"):
@@ -642,9 +674,12 @@ class AudioStreamBank:
             if resampler.unit_blocks * resampler.up != resampler.unit_hops * int(gt_stream.hop):
                 raise ValueError(f"a unit of the resampler is {resampler.unit_blocks * resampler.up} samples, not "
                                  f"{resampler.unit_hops} hops of the front end's {gt_stream.hop}")
+        if mixer is not None and int(mixer.n_streams) != int(gt_stream.n_streams):
+            raise ValueError(f"the mixer serves {mixer.n_streams} streams, the front end {gt_stream.n_streams}")
         if net.n_channels != gt_stream.n_channels:
             raise ValueError(f"the front end has {gt_stream.n_channels} channels, the reservoir {net.n_channels}")
         self.gt, self.net, self.S, self.n_thr, self.resampler = gt_stream, net, S, n_thr, resampler
+        self.mixer = mixer                  # frontend.MixStream or None: behind the resampler, in front of the front end
         self.n_streams = int(gt_stream.n_streams)
         self.bank = StreamBank(net, self.n_streams, S, window_segments, hop_segments, feature_keys)
         # time-major: an item is one raster step, (C,)
@@ -659,6 +694,8 @@ class AudioStreamBank:
         """The streams in ``slots`` have ended and new ones take their places: both halves and the pending columns."""
         if self.resampler is not None:
             self.resampler.reset(slots)
+        if self.mixer is not None:
+            self.mixer.reset(slots)
         self.gt.reset(slots)
         self.bank.reset(slots)
         self.pending.reset(checked_slots(slots, self.n_streams))
@@ -672,6 +709,8 @@ class AudioStreamBank:
         S = self.S
         if self.resampler is not None:
             audio, hops = self._resampled(audio, hops)
+        if self.mixer is not None:
+            audio = self._mixed(audio, hops)
         raster, cols = self.gt.push(audio, hops)
         dev = self.net.device
         with torch.cuda.device(dev):
@@ -682,6 +721,15 @@ class AudioStreamBank:
             joined = run[:, :int(segs.max()) * S].transpose(1, 2).contiguous()
         return self.bank.push(joined, segs)
 
+
+    def _mixed(self, audio, hops):
+        """The first ``hops[b]`` hops of every row through the mixer; the rows keep their length."""
+        hop = int(self.gt.hop)
+        audio = as_float32(audio)
+        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % hop or audio.shape[1] < hop:
+            raise ValueError(f"audio must be ({self.n_streams}, H * {hop}) with H >= 1, got {tuple(audio.shape)}")
+        new = checked_counts(hops, self.n_streams, int(audio.shape[1]) // hop, "hops")
+        return self.mixer.push(audio, None if hops is None else new * hop)[0]
 
     def _resampled(self, audio, units):
         """A push at the resampler's input rate -> ``(samples, hops)`` as the front end takes them."""

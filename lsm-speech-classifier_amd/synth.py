@@ -4,6 +4,7 @@
 * ``class_chirps``: class-structured, speech-like 1 s clips (three amplitude-modulated chirps per
   class + noise) so that accuracy-equality checks have something learnable.
 * ``bernoulli_raster``: reservoir-only timing input, uint8 (B, C, T) at a given density.
+* ``coloured_noise``: a small noise bank for the mixer (SPEC.md §1.10) where no ``_background_noise_`` folder exists.
 """
 from __future__ import annotations
 
@@ -50,6 +51,20 @@ def class_chirps(labels, seed: int = 1234, n_samples: int = CLIP_SAMPLES) -> np.
         x *= 0.5 / max(1e-9, np.abs(x).max())
         x += 0.04 * srng.standard_normal(n_samples)
         out[n] = x.astype(np.float32)
+    return out
+
+
+def coloured_noise(n_rows: int, n_samples: int = 4 * CLIP_SAMPLES, seed: int = 1234) -> np.ndarray:
+    """A noise bank (n_rows, n_samples) float32 with a peak of 0.5: white noise shaped in the frequency domain to a power
+    spectrum of 1 / f^r for row r -- white, pink, brown, ... -- so that the rows differ the way the hum, hiss and rumble of
+    a background-noise folder do."""
+    rng = np.random.default_rng(seed)
+    f = np.fft.rfftfreq(n_samples)
+    f[0] = f[1] if n_samples > 1 else 1.0
+    out = np.empty((n_rows, n_samples), dtype=np.float32)
+    for r in range(n_rows):
+        x = np.fft.irfft(np.fft.rfft(rng.standard_normal(n_samples)) * f ** (-0.5 * r), n=n_samples)
+        out[r] = (x * (0.5 / max(1e-30, np.abs(x).max()))).astype(np.float32)
     return out
 
 

@@ -30,6 +30,18 @@ def _corpus_args(a):
     return out
 
 
+def _augment_args(a):
+    out = []
+    for flag, v in (("--noise-dir", a.noise_dir), ("--snr-db", a.snr_db), ("--level-db", a.level_db)):
+        if v is not None:
+            out += [flag, str(v)]
+    if a.time_shift_ms:
+        out += ["--time-shift-ms", str(a.time_shift_ms)]
+    if out:
+        out += ["--augment-seed", str(a.augment_seed)]
+    return out
+
+
 def _reservoir_args(a):
     out = []
     for flag, v in (("--num-neurons", a.num_neurons), ("--num-output-neurons", a.num_output_neurons),
@@ -42,7 +54,7 @@ def _reservoir_args(a):
 STAGES = (
     ("Step 1: Creating Spike Train Dataset",
      lambda a: ["create_dataset.py", "--n-filters", str(a.n_filters), "--filterbank", a.filterbank]
-     + _corpus_args(a) + (["--packed"] if a.packed else [])),
+     + _corpus_args(a) + (["--packed"] if a.packed else []) + _augment_args(a)),
     ("Step 2: Extracting LSM Features",
      lambda a: ["extract_lsm_features.py", "--feature-set", a.feature_set, "--multiplier", str(a.multiplier)]
      + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])),
@@ -54,13 +66,15 @@ STAGES = (
 
 IN_MEMORY = """import argparse, sys, create_dataset as cd, extract_lsm_features as ex
 a = argparse.Namespace(**{ns!r})
+augment = cd.augment_from_args(a)
 audio, labels = cd.collect_audio(commands=cd.commands_from_args(a), dataset_root=a.dataset_root,
                                  max_per_class=cd.MAX_SAMPLES_PER_CLASS if a.max_per_class is None else a.max_per_class,
                                  synthetic_per_class=a.synthetic_per_class)
+corrupt = cd.corruption(augment, len(audio)) if augment else None
 ex.main_from_audio(audio, labels, a.n_filters, a.filterbank, a.feature_set, a.multiplier,
                    num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons,
                    small_world_k=a.small_world_k, seed=a.seed, readout=a.device_readout,
-                   class_names=cd.commands_from_args(a), time_segments=a.time_segments)
+                   class_names=cd.commands_from_args(a), time_segments=a.time_segments, corrupt=corrupt)
 """
 
 
@@ -82,12 +96,14 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     except that a PyTorch readout (`readout="torch-ridge"` / `"torch-logistic"`) runs inside that process on the
     feature rows still on the GPU and prints the final report itself (no stage 3 process, no File 2 reload).
     `extra`: the forwarded constants (commands, commands_file, dataset_root, max_per_class, synthetic_per_class,
-    packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc, time_segments)."""
+    packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc, time_segments, and the corruption flags
+    noise_dir, snr_db, time_shift_ms, level_db, augment_seed: applied to stage 1 and to the in-memory route)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
                               packed=False, num_neurons=None, num_output_neurons=None, small_world_k=None, seed=None,
-                              readout=None, nproc=1, time_segments=1)
+                              readout=None, nproc=1, time_segments=1, noise_dir=None, snr_db=None, time_shift_ms=0.0,
+                              level_db=None, augment_seed=42)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -151,10 +167,17 @@ if __name__ == "__main__":
                     help="Ranks (one per GPU) for stages 1 and 2.")
     ap.add_argument("--time-segments", type=int, default=1,
                     help="Read every clip in K equal time segments, K feature rows side by side (stage 2; default 1).")
+    ap.add_argument("--noise-dir", type=str, default=None,
+                    help="Folder of background-noise wav files mixed into every clip on the GPU, or 'synthetic' (stage 1).")
+    ap.add_argument("--snr-db", type=str, default=None, help="SNR in dB, A or a range A,B drawn per clip (stage 1).")
+    ap.add_argument("--time-shift-ms", type=float, default=0.0, help="Random time shift of up to this many ms (stage 1).")
+    ap.add_argument("--level-db", type=str, default=None, help="Level change in dB, A or a range A,B (stage 1).")
+    ap.add_argument("--augment-seed", type=int, default=42, help="Seed of the per-clip corruption draws (stage 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
                  dataset_root=a.dataset_root, max_per_class=a.max_per_class,
                  synthetic_per_class=a.synthetic_per_class, packed=a.packed, num_neurons=a.num_neurons,
                  num_output_neurons=a.num_output_neurons, small_world_k=a.small_world_k, seed=a.seed,
-                 readout=a.readout, nproc=a.nproc, time_segments=a.time_segments)
+                 readout=a.readout, nproc=a.nproc, time_segments=a.time_segments, noise_dir=a.noise_dir, snr_db=a.snr_db,
+                 time_shift_ms=a.time_shift_ms, level_db=a.level_db, augment_seed=a.augment_seed)
