@@ -209,6 +209,61 @@ def corruption(augment, n_listed: int):
     return bank, plan
 
 
+# ---- reverberation on the device (SPEC.md 1.11): --rir-dir, --rir-prob, --rir-max-ms; the seed is --augment-seed -----------
+SYNTHETIC_RIR_ROWS = 4
+DEFAULT_RIR_MAX_MS = 500.0
+
+
+def _cut_response(data: np.ndarray, max_taps: int):
+    """One impulse response as a bank row: from its largest-magnitude sample (the direct path, so no delay is added) at
+    most ``max_taps`` samples, divided in float64 by that sample's value (h[0] = 1) and rounded to float32, trailing zeros
+    dropped.  None for a file without a non-zero sample."""
+    data = np.asarray(data, dtype=np.float32)
+    if not len(data) or not np.abs(data).max() > 0:
+        return None
+    at = int(np.argmax(np.abs(data)))
+    h = (data[at:at + max_taps].astype(np.float64) / np.float64(data[at])).astype(np.float32)
+    return h[:int(np.flatnonzero(h)[-1]) + 1]
+
+
+def load_rir_bank(rir_dir, max_ms: float = DEFAULT_RIR_MAX_MS, seed: int = 42):
+    """The bank of room impulse responses ``(bank (M, K) float32, lengths (M,) int32)`` at 16 kHz: every wav under
+    ``rir_dir`` in sorted order, read through `_decode_wav` and resampled like a clip, cut by `_cut_response` to at most
+    ``max_ms`` milliseconds and zero-padded to the longest row; ``lengths`` says where each ends.  ``"synthetic"``:
+    `synth.room_responses`, cut to ``max_ms`` likewise."""
+    max_taps = int(max_ms * SAMPLE_RATE / 1000.0)
+    if not 1 <= max_taps <= 16384:
+        raise ValueError(f"--rir-max-ms {max_ms}: a row must have 1 to 16384 taps at {SAMPLE_RATE} Hz")
+    if str(rir_dir) == "synthetic":
+        from lsm_speech_classifier_amd import synth
+        bank, lengths = synth.room_responses(SYNTHETIC_RIR_ROWS, seed=seed)
+        rows = [bank[r, :n] for r, n in enumerate(lengths)]
+    else:
+        rows = []
+        for f in sorted(Path(rir_dir).glob("*.wav")):
+            rate, data = _decode_wav(f)
+            if rate != SAMPLE_RATE:
+                from math import gcd
+                from scipy.signal import resample_poly
+                g = gcd(int(rate), SAMPLE_RATE)
+                data = resample_poly(data, SAMPLE_RATE // g, int(rate) // g).astype(np.float32)
+            rows.append(data)
+    rows = [h for h in (_cut_response(r, max_taps) for r in rows) if h is not None]
+    if not rows:
+        raise ValueError(f"--rir-dir {rir_dir}: no readable wav file with a non-zero sample")
+    lengths = np.array([len(h) for h in rows], dtype=np.int32)
+    bank = np.zeros((len(rows), int(lengths.max())), dtype=np.float32)
+    for r, h in enumerate(rows):
+        bank[r, :len(h)] = h
+    return bank, lengths
+
+
+def reverberation(reverb, n_listed: int):
+    """``reverb`` (`reverb_from_args`) -> ``(bank, lengths, frontend.ReverbPlan of all n_listed clips in listing order)``."""
+    bank, lengths = load_rir_bank(reverb["rir_dir"], reverb["max_ms"], reverb["seed"])
+    return bank, lengths, _frontend().reverb_plan(n_listed, bank.shape[0], prob=reverb["prob"], seed=reverb["seed"])
+
+
 def _synthetic_audio(commands, per_class: int):
     from lsm_speech_classifier_amd import synth
     labels = np.repeat(np.arange(len(commands)), per_class)
@@ -239,7 +294,8 @@ def collect_audio(commands=None, dataset_root=None, max_per_class: int = MAX_SAM
 
 def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
-                   output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host", augment=None):
+                   output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host", augment=None,
+                   reverb=None):
     """Build File 1.  The first two arguments are the reference's; the keyword arguments expose
     what the reference hard-codes (class list, corpus folder, per-class cap) plus a synthetic
     corpus for machines without Speech Commands.  ``packed=True`` writes the bit-packed schema of
@@ -248,6 +304,8 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     at 16 kHz on the GPU (`_load_listing_device`) instead of one by one on the host.  ``augment`` (`augment_from_args`):
     every clip is shifted, scaled and mixed with noise on the GPU before the front end (SPEC.md 1.10), by a plan drawn for
     the whole listing in listing order -- a shard takes its slice, so any number of ranks writes the same bytes.
+    ``reverb`` (`reverb_from_args`): every clip is first convolved on the GPU with a room impulse response (SPEC.md 1.11),
+    by a plan drawn for the whole listing likewise.
 
     Under a launcher (torchrun: RANK / WORLD_SIZE) the clip loop of create_dataset.py:143 shards: rank r reads
     and encodes the r-th contiguous block of the file listing on its own GPU, the raster blocks are all-gathered
@@ -261,13 +319,14 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     if rank == 0:
         print(f"Creating dataset with filterbank: {filterbank}, filters: {n_filters}"
               + (f" ({world} ranks)" if world > 1 else ""))
-    kept = [] if augment else None          # positions in the shard's part of the listing of the clips that were read
+    planned = bool(augment) or bool(reverb)
+    kept = [] if planned else None          # positions in the shard's part of the listing of the clips that were read
     if synthetic_per_class > 0:
         clips, labels = _synthetic_audio(commands, synthetic_per_class)
         n_listed = len(clips)
         lo, hi = lsm_dist.shard_range(len(clips), rank, world)
         clips, labels = clips[lo:hi], labels[lo:hi]
-        kept = list(range(hi - lo)) if augment else None
+        kept = list(range(hi - lo)) if planned else None
     else:
         listing = _list_files(commands, root, max_per_class, verbose=rank == 0)
         n_listed = len(listing)
@@ -292,11 +351,18 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
         bank, plan = corruption(augment, n_listed)
         plan = plan.take(lo + np.asarray(kept, dtype=np.int64))
         mixer = _frontend().NoiseMixer(bank, device=dev)
+    reverberator = rooms = None
+    if reverb:
+        rir, rir_lengths, rooms = reverberation(reverb, n_listed)
+        rooms = rooms.take(lo + np.asarray(kept, dtype=np.int64))
+        reverberator = _frontend().Reverberator(rir, rir_lengths, device=dev)
     parts, n_spikes = [], 0
     for a in range(0, len(clips), ENCODE_BATCH):
         batch = clips[a:a + ENCODE_BATCH]
         if not torch.is_tensor(batch):
             batch = np.stack(batch)
+        if reverberator is not None:
+            batch = reverberator.reverb(batch, rooms.part(a, a + ENCODE_BATCH).rows)
         if mixer is not None:
             batch = mixer.mix(batch, *plan.part(a, a + ENCODE_BATCH))
         raster = fe.encode(batch)
@@ -385,6 +451,27 @@ def augment_from_args(a):
                 level_db=0.0 if a.level_db is None else _number_or_range(a.level_db, "--level-db"), seed=int(a.augment_seed))
 
 
+def add_reverb_flags(ap):
+    """The reverberation flags (shared with main.py, which forwards them).  Without --rir-dir nothing changes.  The seed of
+    the per-clip draws is --augment-seed (`add_augment_flags`)."""
+    ap.add_argument("--rir-dir", type=str, default=None,
+                    help="Folder of room-impulse-response wav files convolved with every clip on the GPU, or 'synthetic'.")
+    ap.add_argument("--rir-prob", type=float, default=1.0, help="Share of the clips that are reverberated (default 1).")
+    ap.add_argument("--rir-max-ms", type=float, default=DEFAULT_RIR_MAX_MS,
+                    help=f"Cut every response to this many milliseconds (default {DEFAULT_RIR_MAX_MS:g}).")
+
+
+def reverb_from_args(a):
+    """None without --rir-dir, else what create_dataset(reverb=...) takes."""
+    if a.rir_dir is None:
+        return None
+    if not 0.0 <= a.rir_prob <= 1.0:
+        raise SystemExit("--rir-prob must lie in [0, 1]")
+    if not a.rir_max_ms > 0:
+        raise SystemExit("--rir-max-ms must be > 0")
+    return dict(rir_dir=a.rir_dir, prob=float(a.rir_prob), max_ms=float(a.rir_max_ms), seed=int(a.augment_seed))
+
+
 def commands_from_args(a):
     if a.commands_file:
         return read_commands_file(a.commands_file)
@@ -406,8 +493,9 @@ if __name__ == "__main__":
                     help="Where files that are not at 16 kHz are resampled: one by one on the host (default), or grouped by "
                          "rate on the GPU.")
     add_augment_flags(ap)
+    add_reverb_flags(ap)
     a = ap.parse_args()
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,
                    synthetic_per_class=a.synthetic_per_class, packed=a.packed, resample=a.resample,
-                   augment=augment_from_args(a))
+                   augment=augment_from_args(a), reverb=reverb_from_args(a))

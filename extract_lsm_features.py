@@ -212,7 +212,7 @@ def run_network_diagnostics(lsm, X_sample_batch):
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
                     num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
-                    time_segments=1, corrupt=None):
+                    time_segments=1, corrupt=None, reverb=None):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -236,7 +236,10 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
 
     `corrupt` = ``(noise bank (M, L) float32, frontend.MixPlan of the n clips)``: every clip is shifted, scaled and mixed
     with noise on the GPU before its front end (SPEC.md 1.10), the clips w_critico looks at included; a rank corrupts its
-    clips with their entries of the one plan."""
+    clips with their entries of the one plan.
+
+    `reverb` = ``(bank (M, K) float32, lengths, frontend.ReverbPlan of the n clips)``: every clip is first convolved with
+    its room impulse response on the GPU (SPEC.md 1.11), ahead of `corrupt`."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
@@ -261,7 +264,12 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     mixer = plan = None
     if corrupt is not None:
         mixer, plan = frontend.NoiseMixer(corrupt[0], device=dev), corrupt[1]
+    rv = rooms = None
+    if reverb is not None:
+        rv, rooms = frontend.Reverberator(reverb[0], reverb[1], device=dev), reverb[2]
     head_audio = audio[idx_train[:500]]
+    if rv is not None:
+        head_audio = rv.reverb(head_audio, rooms.take(idx_train[:500]).rows)
     if mixer is not None:
         head_audio = mixer.mix(head_audio, *plan.take(idx_train[:500]))
     head = fe.encode(head_audio).cpu().numpy()                      # what w_critico and the diagnostics look at
@@ -286,7 +294,8 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
         lo, hi = lsm_dist.shard_range(len(idx), rank, world)
         local = pipeline.features_from_audio(audio[idx[lo:hi]], fe, lsm, keys, batch=batch, device_out=True,
                                              time_segments=time_segments,
-                                             corrupt=(mixer, plan.take(idx[lo:hi])) if mixer is not None else None)
+                                             corrupt=(mixer, plan.take(idx[lo:hi])) if mixer is not None else None,
+                                             reverb=(rv, rooms.take(idx[lo:hi])) if rv is not None else None)
         return lsm_dist.gather_rows(local, len(idx))
 
     X_train_dev = split_features(idx_train)

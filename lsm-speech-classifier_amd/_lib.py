@@ -131,6 +131,15 @@ MIX_SIGS = {
 }
 MIX_SYMBOLS = tuple(MIX_SIGS)
 
+# include/lsm_hip_reverb.h (SPEC.md §1.11): reverberation in front of the mixer, batch and streamed
+REVERB_SIGS = {
+    "lsm_reverb_state_bytes": (C.c_long, [c_int]),
+    "lsm_reverb_f32": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_void, c_void, c_int, c_void, c_void]),
+    "lsm_reverb_stream_f32": (c_int, [c_void, c_int, c_int, c_void, c_int, c_int, c_void, c_void, c_void, c_void, c_void,
+                                      c_void, c_void]),
+}
+REVERB_SYMBOLS = tuple(REVERB_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -180,7 +189,7 @@ def load():
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
-                              + list(MIX_SIGS.items())):
+                              + list(MIX_SIGS.items()) + list(REVERB_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -1192,6 +1192,175 @@ class MixStream:
         return out, new
 
 
+# ---- reverberation (SPEC.md §1.11, include/lsm_hip_reverb.h) ------------------------------------------------------------
+REVERB_MAX_TAPS = 16384
+REVERB_MAX_ROWS = 65535                 # rows of one launch
+
+
+class ReverbPlan(NamedTuple):
+    """Per-clip rows of a bank of room impulse responses (`reverb_plan`): ``rows`` int32 on the host, -1 = a dry clip."""
+    rows: np.ndarray
+
+    def part(self, lo: int, hi: int) -> "ReverbPlan":
+        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
+        return ReverbPlan(self.rows[lo:hi])
+
+    def take(self, idx) -> "ReverbPlan":
+        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
+        return ReverbPlan(self.rows[np.asarray(idx, dtype=np.int64)])
+
+
+def reverb_plan(n_clips: int, n_rir_rows: int, prob: float = 1.0, seed: int = 42) -> ReverbPlan:
+    """The room of every clip of a listing, drawn from ``np.random.RandomState([seed, 1])`` -- a generator of its own, so
+    `mix_plan`'s draws for the same seed stay as they are -- for ALL ``n_clips`` clips in listing order: the rows
+    (``randint(0, M)``), then ``u = random_sample``; a clip with ``u >= prob`` is dry (row -1)."""
+    n, M, p = int(n_clips), int(n_rir_rows), float(prob)
+    if n < 0 or M < 1 or not 0.0 <= p <= 1.0:
+        raise ValueError(f"reverb_plan needs n_clips >= 0, n_rir_rows >= 1 and prob in [0, 1], got {n_clips}, {n_rir_rows}, "
+                         f"{prob}")
+    rs = np.random.RandomState([int(seed), 1])
+    rows = rs.randint(0, M, size=n).astype(np.int32)
+    u = rs.random_sample(n)
+    rows[u >= p] = -1
+    return ReverbPlan(rows)
+
+
+def checked_rir_bank(rir_bank, lengths=None):
+    """A bank of impulse responses as the kernels take it: ``(bank (M, K) float32 tensor, lengths (M,) int32 array or
+    None)`` with M >= 1 and 1 <= K <= 16384; a 1-D array is one row; ``lengths`` must lie in [1, K]."""
+    if isinstance(rir_bank, np.ndarray):
+        rir_bank = torch.from_numpy(np.array(rir_bank))
+    if not torch.is_tensor(rir_bank) or rir_bank.dtype != torch.float32:
+        raise ValueError("the bank of impulse responses must be a float32 NumPy array or tensor")
+    if rir_bank.dim() == 1:
+        rir_bank = rir_bank[None, :]
+    if rir_bank.dim() != 2 or rir_bank.shape[0] < 1 or not 1 <= rir_bank.shape[1] <= REVERB_MAX_TAPS:
+        raise ValueError(f"the bank of impulse responses must be (M, K) with M >= 1 and 1 <= K <= {REVERB_MAX_TAPS}, got "
+                         f"{tuple(rir_bank.shape)}")
+    M, K = (int(v) for v in rir_bank.shape)
+    if lengths is not None:
+        lengths = _per_clip(lengths, M, np.int32, "lengths")
+        if ((lengths < 1) | (lengths > K)).any():
+            raise ValueError(f"lengths must lie in [1, {K}], got {lengths.tolist()}")
+    return rir_bank.contiguous(), lengths
+
+
+def _reverb_audio(audio, n_rows=None, what="audio"):
+    """(n, L) float32 with 1 <= L <= 2^24, NumPy (float32 only) or tensor -> contiguous tensor."""
+    if isinstance(audio, np.ndarray):
+        if audio.dtype != np.float32:
+            raise ValueError(f"{what} must be float32, got {audio.dtype}")
+        audio = torch.from_numpy(np.ascontiguousarray(audio))
+    if not torch.is_tensor(audio) or audio.dtype != torch.float32 or audio.dim() != 2 or audio.shape[1] < 1 \
+            or audio.shape[1] > MIX_MAX_SAMPLES or (n_rows is not None and audio.shape[0] != n_rows):
+        raise ValueError(f"{what} must be ({'n' if n_rows is None else n_rows}, L) float32 with 1 <= L <= {MIX_MAX_SAMPLES}, "
+                         f"NumPy or tensor, got {tuple(audio.shape) if hasattr(audio, 'shape') else type(audio).__name__}")
+    return audio.contiguous()
+
+
+class Reverberator:
+    """A bank ``(M, K)`` float32 of room impulse responses on the device and the convolution kernels over it (SPEC.md
+    §1.11): `reverb` convolves every clip of a batch with its row in one launch (`lsm_reverb_f32`); `ReverbStream` is the
+    streamed form.  ``lengths`` (M integers in [1, K]) says where each row ends; None: K everywhere."""
+
+    def __init__(self, rir_bank, lengths=None, device=None):
+        bank, lengths = checked_rir_bank(rir_bank, lengths)
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        self.rir = bank.to(self.device)
+        self.n_rows, self.n_taps = (int(v) for v in bank.shape)
+        self.lengths = lengths
+        self.lengths_dev = None if lengths is None else torch.from_numpy(lengths).to(self.device)
+
+    def reverb(self, audio, rows=None, n_out: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``audio`` (n, L) float32, NumPy or tensor -> float32 (n, n_out) on the device.  ``rows``: a number or n of them
+        (None: row 0); a row below 0 is dry -- the clip's bits -- and one at or above M is clamped.  ``n_out`` defaults to
+        L, the recipe's ``convolve(x, h)[:L]``; ``L + K - 1`` is the full tail.  ``out``: a caller-owned contiguous
+        float32 (n, n_out) tensor on the device, never ``audio``."""
+        audio = _reverb_audio(audio)
+        n, L = (int(v) for v in audio.shape)
+        n_out = L if n_out is None else int(n_out)
+        if n_out < 1:
+            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        rows = _per_clip(rows, n, np.int32, "rows")
+        if out is not None:
+            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) \
+                    or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
+            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
+                raise ValueError("out must not be audio: an output reads the samples in front of it")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            if out is None:
+                out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+            rows_dev = None if rows is None else torch.from_numpy(rows).to(self.device, non_blocking=True)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for r0 in range(0, n, REVERB_MAX_ROWS):
+                k = min(REVERB_MAX_ROWS, n - r0)
+                _lib.check(self.lib.lsm_reverb_f32(
+                    _dev(audio[r0:]), k, L, _dev(self.rir), self.n_rows, self.n_taps,
+                    _dev(self.lengths_dev) if self.lengths_dev is not None else None,
+                    _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out, _dev(out[r0:]), stream), "lsm_reverb_f32")
+        return out
+
+
+class ReverbStream:
+    """``n_streams`` open-ended streams through the reverberator's streamed form (`lsm_reverb_stream_f32`): every `push`
+    convolves each stream's new samples -- any number, 0 included -- behind the history the bank holds, the stream's last
+    K - 1 input samples.  A stream cut into pushes anywhere gives, byte for byte, the samples of its uncut run.  Until `set`,
+    every stream uses row 0; row -1 is dry.  The history is kept at the bank's K, so `set` may change a stream's row between
+    pushes."""
+
+    def __init__(self, reverberator: Reverberator, n_streams: int):
+        self.reverberator, self.n_streams, self.device = reverberator, int(n_streams), reverberator.device
+        if self.n_streams < 1 or self.n_streams > REVERB_MAX_ROWS:
+            raise ValueError(f"ReverbStream needs n_streams in [1, {REVERB_MAX_ROWS}], got {n_streams}")
+        self.state_bytes = int(reverberator.lib.lsm_reverb_state_bytes(reverberator.n_taps))
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self.rows = torch.zeros(self.n_streams, dtype=torch.int32, device=self.device)
+
+    def set(self, slots, rows) -> None:
+        """The rows of the streams in ``slots`` from here on (below 0: dry; refused at or above M).  The histories stay."""
+        slots = checked_slots(slots, self.n_streams)
+        rows = _per_clip(rows, len(slots), np.int32, "rows")
+        if (rows >= self.reverberator.n_rows).any():
+            raise ValueError(f"rows {rows.tolist()} outside the bank's {self.reverberator.n_rows} rows")
+        self.rows[torch.from_numpy(slots).to(self.device)] = torch.from_numpy(rows).to(self.device)
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: their histories back to zeros."""
+        slots = checked_slots(slots, self.n_streams)
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+
+    def push(self, audio, counts=None, out: torch.Tensor | None = None):
+        """``audio`` (n_streams, H) float32: stream b's new samples are the first ``counts[b]`` of its row; ``counts``:
+        n_streams host integers in [0, H], or None for H everywhere.  Returns ``(out, counts)``: float32 (n_streams, H) on
+        the device, whose first ``counts[b]`` samples of row b are the stream's next ones; behind them lie zeros, or what a
+        caller-owned ``out`` held.  ``out`` is never ``audio``."""
+        audio = _reverb_audio(audio, self.n_streams)
+        H = int(audio.shape[1])
+        new = checked_counts(counts, self.n_streams, H, "counts")
+        if out is not None:
+            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (self.n_streams, H) \
+                    or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"out must be a contiguous float32 {(self.n_streams, H)} tensor on {self.device}")
+            if out is audio or out.data_ptr() == audio.data_ptr():
+                raise ValueError("out must not be audio: an output reads the samples in front of it")
+        rv = self.reverberator
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            if out is None:
+                out = torch.zeros((self.n_streams, H), dtype=torch.float32, device=self.device)
+            cnt = None if counts is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            _lib.check(rv.lib.lsm_reverb_stream_f32(
+                _dev(audio), self.n_streams, H, _dev(rv.rir), rv.n_rows, rv.n_taps,
+                _dev(rv.lengths_dev) if rv.lengths_dev is not None else None, _dev(self.rows),
+                _dev(cnt) if cnt is not None else None, _dev(self.state), _dev(self.state), _dev(out),
+                torch.cuda.current_stream(self.device).cuda_stream), "lsm_reverb_stream_f32")
+        return out, new
+
+
 _FRONT_ENDS: dict = {}
 
 

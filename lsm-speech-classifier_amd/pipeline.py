@@ -83,17 +83,23 @@ class HotPath:
     one (`SNN.run_segments`, K segments of T // K steps, SPEC.md §4b) and a clip's row is its K segment rows side by side
     (segment-major, then key-major: K times the columns); 1 = the whole-clip row, the calls of a pipeline without it.
     `mixer` = a `frontend.NoiseMixer`: a step submitted with `mix=` (a `frontend.MixPlan` of its clips) is corrupted on the
-    device before its front end (SPEC.md §1.10); without `mix` a step launches what it launches without a mixer."""
+    device before its front end (SPEC.md §1.10); without `mix` a step launches what it launches without a mixer.
+    `reverb` = a `frontend.Reverberator`: a step submitted with `reverb=` (a `frontend.ReverbPlan` of its clips) is convolved
+    with its rooms on the device (SPEC.md §1.11) ahead of the mixer; without it nothing more is launched."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
-                 fe_streams: int | None = None, time_segments: int = 1, mixer=None):
+                 fe_streams: int | None = None, time_segments: int = 1, mixer=None, reverb=None):
         if indexed_device(fe.device) != indexed_device(net.device):
             raise ValueError(f"front end on {fe.device}, reservoir on {net.device}")
         if mixer is not None and indexed_device(mixer.device) != indexed_device(fe.device):
             raise ValueError(f"mixer on {mixer.device}, front end on {fe.device}")
         self.mixer = mixer                  # frontend.NoiseMixer or None: submit(mix=...) corrupts a step's clips with it
         self._mixed = {}                    # (rotation slot, batch shape) -> the mix launch's output buffer
+        if reverb is not None and indexed_device(reverb.device) != indexed_device(fe.device):
+            raise ValueError(f"reverberator on {reverb.device}, front end on {fe.device}")
+        self.reverb = reverb                # frontend.Reverberator or None: submit(reverb=...) convolves a step's clips with it
+        self._reverbed = {}                 # (rotation slot, batch shape) -> the reverb launch's output buffer
         if fe.n_channels != net.n_channels:
             raise ValueError(f"front end has {fe.n_channels} channels, reservoir expects {net.n_channels}")
         self.fe, self.net = fe, net
@@ -157,7 +163,8 @@ class HotPath:
             self.reservoir_events.append((e0, e1))
         return feats
 
-    def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None):
+    def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
+               reverb=None):
         """Issue one step on the next stream of the rotation.  `audio`: (B, n_samples) float32 -- device tensor,
         or pinned/pageable host tensor / NumPy array, uploaded on the step's own stream.  Returns (features
         (B, n_keys*N_out) device tensor, stream it is produced on); the caller waits (`stream.synchronize()`,
@@ -178,17 +185,22 @@ class HotPath:
         `mix`: a `frontend.MixPlan` of this step's B clips (needs the pipeline's `mixer`): one more launch on the stream
         that runs the step's front end, between the upload and `encode`, into a buffer the rotation slot owns; no host
         synchronisation.
+        `reverb`: a `frontend.ReverbPlan` of this step's B clips (needs the pipeline's `reverb`): one more launch on the same
+        stream ahead of the mixer's, into a buffer the rotation slot owns.
         Back-pressure: when `max_ahead` earlier steps have not finished, submit() first waits for the oldest."""
         if mix is not None and (self.mixer is None or stage == "reservoir"):
             raise ValueError("submit(mix=...) needs a HotPath built with a mixer and a step that has a front end")
-        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix)
+        if reverb is not None and (self.reverb is None or stage == "reservoir"):
+            raise ValueError("submit(reverb=...) needs a HotPath built with a reverberator and a step that has a front end")
+        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix, reverb)
         if st is not None and self.n_streams > 1:
             ev = torch.cuda.Event()
             ev.record(st)
             self._in_flight.append(ev)
         return res, st
 
-    def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None):
+    def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
+                reverb=None):
         """submit() without the in-flight bookkeeping."""
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
@@ -202,7 +214,7 @@ class HotPath:
             topology = self._submit_two_stages
         else:
             topology = self._submit_rotation
-        return topology(slot, audio, stats_out, after, out, stage, tail, mix)
+        return topology(slot, audio, stats_out, after, out, stage, tail, mix, reverb)
 
     def _wait_for_input(self, stream, cur, audio, after) -> None:
         """The ordering of a device input (`submit`): `stream` waits for `after`, or for what `cur` has issued so far."""
@@ -211,24 +223,24 @@ class HotPath:
         elif torch.is_tensor(audio) and audio.device == self.device:
             stream.wait_stream(cur)
 
-    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None):
+    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None):
         """Everything on the current stream."""
         cur = torch.cuda.current_stream(self.device)
         if after is not None:
             cur.wait_event(after)
         with torch.cuda.device(self.device):
-            x = audio if stage == "reservoir" else self._mix(self._to_device(audio, slot), mix, slot)
+            x = audio if stage == "reservoir" else self._mix(self._reverb(self._to_device(audio, slot), reverb, slot), mix, slot)
             return self._one(x, stats_out, out, stage, tail), cur
 
-    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None):
+    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None):
         """The step keeps to reservoir stream `slot`: its front end, then its reservoir launch."""
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             self._wait_for_input(st, cur, audio, after)
-            x = audio if stage == "reservoir" else self._mix(self._to_device(audio, slot), mix, slot)
+            x = audio if stage == "reservoir" else self._mix(self._reverb(self._to_device(audio, slot), reverb, slot), mix, slot)
             return self._one(x, stats_out, out, stage, tail), st
 
-    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None):
+    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None):
         """The front end on the next front-end stream, the reservoir launch on reservoir stream `slot` behind an event."""
         fslot = (self._step - 1) % self.n_fe_streams
         st, fst, cur = self.streams[slot], self.fe_streams[fslot], torch.cuda.current_stream(self.device)
@@ -236,7 +248,7 @@ class HotPath:
             with torch.cuda.stream(fst):
                 self._wait_for_input(fst, cur, audio, after)
                 low_latency = self._low_latency(tail)
-                x = self._mix(self._to_device(audio, ("fe", fslot)), mix, ("fe", fslot))
+                x = self._mix(self._reverb(self._to_device(audio, ("fe", fslot)), reverb, ("fe", fslot)), mix, ("fe", fslot))
                 # the front end's own decision (mel branch, > 1024 filters and LSM_FRONTEND_SPLIT=1 take the split
                 # route, which allocates its raster on the front-end stream): only the fused launch of a full step
                 # writes into the pipeline's rings, everything else goes through record_stream below
@@ -297,6 +309,16 @@ class HotPath:
             buf = self._mixed[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
         return self.mixer.mix(x, mix.snr_db, mix.rows, mix.offsets, mix.shift, mix.scale, out=buf)
 
+    def _reverb(self, x, plan, slot):
+        """The step's clips convolved with the rooms of `plan` on the current stream (ahead of `_mix`), or `x` itself."""
+        if plan is None:
+            return x
+        key = (slot, tuple(x.shape))
+        buf = self._reverbed.get(key)
+        if buf is None:
+            buf = self._reverbed[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+        return self.reverb.reverb(x, plan.rows, out=buf)
+
     def prime(self, audio, stage: str = "full", min_ms: float = 0.0):
         """One untimed step on EVERY stream of the pipeline, then a synchronisation: each stream's first use
         pays for its allocator pool (torch caches device memory per stream: the first `encode` on a stream
@@ -347,10 +369,10 @@ class HotPath:
         torch.cuda.current_stream(self.device).synchronize()
 
     # ---- many steps -------------------------------------------------------------------------
-    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None) -> torch.Tensor:
+    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None, reverbs=None) -> torch.Tensor:
         """Feature rows of every batch, in order, as one (n_clips, n_feat) device tensor.  `audio_batches`
         is an iterable of (B_i, n_samples) arrays/tensors (host or device); `mixes`, when given, an iterable of one
-        `frontend.MixPlan` per batch (`submit(mix=...)`)."""
+        `frontend.MixPlan` per batch (`submit(mix=...)`); `reverbs` likewise one `frontend.ReverbPlan` per batch."""
         self.fork_from_current()
         # The last TAIL_STEPS batches are submitted in the low-latency layouts: that needs a look-ahead of TAIL_STEPS
         # batches, not the whole list -- a lazily produced stream of (pinned or device) batches is consumed as it comes and
@@ -358,14 +380,15 @@ class HotPath:
         from collections import deque
         parts, ahead, it = [], deque(), iter(audio_batches)
         plans = iter(mixes) if mixes is not None else None
+        rooms = iter(reverbs) if reverbs is not None else None
         for a in it:
-            ahead.append((a, next(plans) if plans is not None else None))
+            ahead.append((a, next(plans) if plans is not None else None, next(rooms) if rooms is not None else None))
             if len(ahead) > TAIL_STEPS:
-                a0, m0 = ahead.popleft()
-                parts.append(self.submit(a0, tail=False, mix=m0)[0])
+                a0, m0, r0 = ahead.popleft()
+                parts.append(self.submit(a0, tail=False, mix=m0, reverb=r0)[0])
         while ahead:
-            a0, m0 = ahead.popleft()
-            parts.append(self.submit(a0, tail=True, mix=m0)[0])
+            a0, m0, r0 = ahead.popleft()
+            parts.append(self.submit(a0, tail=True, mix=m0, reverb=r0)[0])
         self.synchronize()
         if not parts:
             n_keys = len(self.feature_keys) if self.feature_keys is not None else 8
@@ -378,17 +401,22 @@ class HotPath:
 
 
 def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1024,
-                        streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1, corrupt=None):
+                        streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1, corrupt=None,
+                        reverb=None):
     """Host convenience for the drop-in scripts' in-memory path: (n, n_samples) float32 on the host ->
     (n, n_feat) float32 on the host (or, `device_out`, still on the GPU for a gather), batches of `batch` clips
     through the overlapped pipeline (pinned staging, uploads on the steps' streams).  n = 0 (an empty shard)
     gives an empty (0, n_feat) block.  `time_segments` = K > 1: K segment rows per clip side by side (`HotPath`), n_feat is
     K times as wide.  `corrupt` = ``(frontend.NoiseMixer, frontend.MixPlan of the n clips)``: every batch is corrupted on
-    the device with its slice of the plan before its front end (SPEC.md §1.10)."""
+    the device with its slice of the plan before its front end (SPEC.md §1.10).  `reverb` = ``(frontend.Reverberator,
+    frontend.ReverbPlan of the n clips)``: every batch is convolved with its rooms ahead of that (SPEC.md §1.11)."""
+    rv, rooms = reverb if reverb is not None else (None, None)
+    if rooms is not None and len(rooms.rows) != len(audio):
+        raise ValueError(f"the reverb plan covers {len(rooms.rows)} clips, audio has {len(audio)}")
     mixer, plan = corrupt if corrupt is not None else (None, None)
     if plan is not None and len(plan.rows) != len(audio):
         raise ValueError(f"the plan covers {len(plan.rows)} clips, audio has {len(audio)}")
-    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer)
+    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer, reverb=rv)
     pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
     if len(pinned):
         try:
@@ -397,7 +425,8 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
             pass
     with torch.cuda.device(hp.device):
         feats = hp.run((pinned[lo:lo + batch] for lo in range(0, len(pinned), batch)),
-                       mixes=(plan.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if plan is not None else None)
+                       mixes=(plan.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if plan is not None else None,
+                       reverbs=(rooms.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if rooms is not None else None)
     return feats if device_out else feats.cpu().numpy()
 
 
@@ -653,10 +682,11 @@ class AudioStreamBank:
     continue from saved state, so the rows are those of each stream's one uncut run, audio to features.  With a ``resampler``
     (``frontend.ResampleStream``) in front, the streams arrive as PCM at its input rate, in whole units (SPEC.md §1.8).  With a
     ``mixer`` (``frontend.MixStream``), every stream's new samples are corrupted on the device (SPEC.md §1.10) behind the
-    resampler and in front of the front end."""
+    resampler and in front of the front end.  With a ``reverb`` (``frontend.ReverbStream``), they are convolved with the
+    stream's room first (SPEC.md §1.11): behind the resampler, in front of the mixer."""
 
     def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None,
-                 resampler=None, mixer=None):
+                 resampler=None, mixer=None, reverb=None):
         # the refusals come before anything touches a device
         streamed = getattr(gt_stream, "filterbank", None) == "gammatone" or getattr(gt_stream, "streamed", None) is True
         if not streamed or not hasattr(gt_stream, "push"):
@@ -676,8 +706,11 @@ class AudioStreamBank:
                                  f"{resampler.unit_hops} hops of the front end's {gt_stream.hop}")
         if mixer is not None and int(mixer.n_streams) != int(gt_stream.n_streams):
             raise ValueError(f"the mixer serves {mixer.n_streams} streams, the front end {gt_stream.n_streams}")
+        if reverb is not None and int(reverb.n_streams) != int(gt_stream.n_streams):
+            raise ValueError(f"the reverberator serves {reverb.n_streams} streams, the front end {gt_stream.n_streams}")
         if net.n_channels != gt_stream.n_channels:
             raise ValueError(f"the front end has {gt_stream.n_channels} channels, the reservoir {net.n_channels}")
+        self.reverb = reverb                # frontend.ReverbStream or None: behind the resampler, in front of the mixer
         self.gt, self.net, self.S, self.n_thr, self.resampler = gt_stream, net, S, n_thr, resampler
         self.mixer = mixer                  # frontend.MixStream or None: behind the resampler, in front of the front end
         self.n_streams = int(gt_stream.n_streams)
@@ -694,6 +727,8 @@ class AudioStreamBank:
         """The streams in ``slots`` have ended and new ones take their places: both halves and the pending columns."""
         if self.resampler is not None:
             self.resampler.reset(slots)
+        if self.reverb is not None:
+            self.reverb.reset(slots)
         if self.mixer is not None:
             self.mixer.reset(slots)
         self.gt.reset(slots)
@@ -709,6 +744,8 @@ class AudioStreamBank:
         S = self.S
         if self.resampler is not None:
             audio, hops = self._resampled(audio, hops)
+        if self.reverb is not None:
+            audio = self._mixed(audio, hops, self.reverb)
         if self.mixer is not None:
             audio = self._mixed(audio, hops)
         raster, cols = self.gt.push(audio, hops)
@@ -722,14 +759,15 @@ class AudioStreamBank:
         return self.bank.push(joined, segs)
 
 
-    def _mixed(self, audio, hops):
-        """The first ``hops[b]`` hops of every row through the mixer; the rows keep their length."""
+    def _mixed(self, audio, hops, stage=None):
+        """The first ``hops[b]`` hops of every row through the mixer (or ``stage``, the reverberator); the rows keep their
+        length."""
         hop = int(self.gt.hop)
         audio = as_float32(audio)
         if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % hop or audio.shape[1] < hop:
             raise ValueError(f"audio must be ({self.n_streams}, H * {hop}) with H >= 1, got {tuple(audio.shape)}")
         new = checked_counts(hops, self.n_streams, int(audio.shape[1]) // hop, "hops")
-        return self.mixer.push(audio, None if hops is None else new * hop)[0]
+        return (stage or self.mixer).push(audio, None if hops is None else new * hop)[0]
 
     def _resampled(self, audio, units):
         """A push at the resampler's input rate -> ``(samples, hops)`` as the front end takes them."""

@@ -5,6 +5,7 @@
   class + noise) so that accuracy-equality checks have something learnable.
 * ``bernoulli_raster``: reservoir-only timing input, uint8 (B, C, T) at a given density.
 * ``coloured_noise``: a small noise bank for the mixer (SPEC.md §1.10) where no ``_background_noise_`` folder exists.
+* ``room_responses``: a small bank of room impulse responses for the reverberator (SPEC.md §1.11).
 """
 from __future__ import annotations
 
@@ -66,6 +67,29 @@ def coloured_noise(n_rows: int, n_samples: int = 4 * CLIP_SAMPLES, seed: int = 1
         x = np.fft.irfft(np.fft.rfft(rng.standard_normal(n_samples)) * f ** (-0.5 * r), n=n_samples)
         out[r] = (x * (0.5 / max(1e-30, np.abs(x).max()))).astype(np.float32)
     return out
+
+
+REVERB_TAIL_GAIN = 0.05                 # the noise tail's amplitude at its start, against the direct path's 1
+
+
+def room_responses(n_rows: int, rt60=(0.2, 0.8), seed: int = 1234, fs: int = SAMPLE_RATE):
+    """A bank of room impulse responses ``(bank (n_rows, K) float32, lengths (n_rows,) int32)``: exponentially decaying
+    Gaussian noise behind a direct path of 1 (SPEC.md §1.11).  Row r has the reverberation time ``rt60[0] + (rt60[1] -
+    rt60[0]) * r / max(1, n_rows - 1)`` seconds (``rt60`` a number: every row) and ends at its -60 dB point,
+    ``len_r = int(rt60_r * fs)`` taps: ``h[0] = 1`` and ``h[k] = 0.05 * g[k] * 10 ** (-3 * k / len_r)`` with ``g`` the row's
+    ``len_r`` draws of ``np.random.RandomState(seed).standard_normal``, rows in order; float64 rounded to float32, zeros
+    behind a row's end, K the longest row."""
+    lo, hi = (float(rt60), float(rt60)) if np.ndim(rt60) == 0 else (float(rt60[0]), float(rt60[1]))
+    if n_rows < 1 or not 0 < lo <= hi or int(lo * fs) < 1:
+        raise ValueError(f"room_responses needs n_rows >= 1 and 0 < rt60[0] <= rt60[1] with at least one tap, got {n_rows}, {rt60!r}")
+    rs = np.random.RandomState(int(seed))
+    lengths = np.array([int((lo + (hi - lo) * r / max(1, n_rows - 1)) * fs) for r in range(n_rows)], dtype=np.int32)
+    bank = np.zeros((n_rows, int(lengths.max())), dtype=np.float32)
+    for r, n in enumerate(lengths):
+        h = REVERB_TAIL_GAIN * rs.standard_normal(int(n)) * 10.0 ** (-3.0 * np.arange(int(n), dtype=np.float64) / float(n))
+        h[0] = 1.0
+        bank[r, :n] = h.astype(np.float32)
+    return bank, lengths
 
 
 def bernoulli_raster(n_clips: int, n_channels: int, n_steps: int = 400, density: float = 0.2,
