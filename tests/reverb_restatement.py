@@ -10,6 +10,11 @@ def row_length(lengths, r, K):
     return K if lengths is None else int(np.clip(int(lengths[r]), 1, K))
 
 
+def push_count(counts, b, n_cols):
+    """c_b = clamp(count[b], 0, n_cols): the samples of stream b that a push of ``n_cols`` columns takes; None means n_cols."""
+    return n_cols if counts is None else int(np.clip(int(counts[b]), 0, n_cols))
+
+
 def convolve(x, h, n_out=None, history=None):
     """One signal ``x`` (1-D float32) against taps ``h`` (1-D float32, all of them used) -> float32 (n_out,).  ``history``:
     float32 samples in front of x[0] (the last one is x[-1]); further back, and at or past the end of x, +0.0."""

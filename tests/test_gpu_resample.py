@@ -1,7 +1,8 @@
 """Polyphase resampler on the GPU (SPEC.md 1.8; `lsm_resample_f32`, `lsm_resample_stream_f32`, `frontend.Resampler`,
 `frontend.ResampleStream`, `pipeline.AudioStreamBank(resampler=...)`, `create_dataset(resample="device")`): bit for bit
 against the NumPy restatement (tests/resample_restatement.py) run with the package's own tap table, within the float32
-rounding of `scipy.signal.resample_poly` in float64, and cut against uncut byte for byte."""
+rounding of `scipy.signal.resample_poly` in float64, per output within the derived bound of the definition
+(tests/fir_definition.py), and cut against uncut byte for byte -- at every packaged design of test_resample_host.DESIGNS."""
 import ctypes as C
 import os
 import sys
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fir_definition as D  # noqa: E402
 import resample_restatement as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -17,9 +19,13 @@ pytestmark = pytest.mark.gpu
 FILL = 0xAA
 # rate -> (n_in, n_out): lengths that are no multiples of anything; 44100: all 160 phases over several waves; 11025: the
 # table over 64 KB, and more than one tile of 2048 outputs
-BATCH = {48000: (1501, 501), 44100: (1340, 487), 8000: (403, 806), 11025: (2700, 3919)}
-# blocks of an uncut stream run: more than one tile of 2048 outputs per stream
-STREAM_BLOCKS = {48000: 2200, 44100: 14}
+BATCH = {48000: (1501, 501), 44100: (1340, 487), 8000: (403, 806), 11025: (2700, 3919), 22050: (1340, 973), 32000: (1501, 751),
+         96000: (3005, 501)}
+# blocks of an uncut stream run: a stream's outputs cross one tile of 2048 by an uneven remainder and no further.  8 kHz is
+# the streamed kernel with up > down, 11.025 kHz with a table over 64 KB (the big-LDS opt-in) as well.
+STREAM_BLOCKS = {48000: 2200, 44100: 14, 8000: 1100, 11025: 4, 22050: 7, 32000: 2200, 96000: 2200}
+# blocks of the run with a NaN in it: two pushes, the second longer than the history
+NAN_BLOCKS = {48000: 100, 44100: 6, 8000: 100, 11025: 4, 22050: 6, 32000: 100, 96000: 100}
 _CACHE = {}
 
 
@@ -73,6 +79,9 @@ def test_batch_equals_the_restatement_and_resample_poly(torch_cuda, rate, dtype)
         err, bound = np.abs(got[b] - ref).max(), 2.0 ** -23 * np.abs(ref).max()
         print(f"{rate} Hz {np.dtype(dtype).name} clip {b}: max |y - resample_poly| = {err:.3e}, {err / bound:.2f} of the bound")
         assert ref.shape == (n_out,) and err <= bound
+        # per output, against the definition: a quiet stretch of a clip is held to its own level
+        ref, S = D.resample(x[b], t, t.delay, n_out)
+        D.check(got[b], ref, D.resample_bound(ref, S, t), f"resample batch {rate} Hz {np.dtype(dtype).name} clip {b}")
     # a tensor on the device gives the same samples
     assert rs.resample(torch.from_numpy(x).cuda()).cpu().numpy().tobytes() == want.tobytes()
     # a smaller n_out is the prefix, and nothing is written past it: the rows of a caller-owned output lie in a buffer
@@ -121,22 +130,28 @@ def _history(rs):
 
 def _push_cut(rs, x, plan, done=None):
     """Push ``x`` (n, G * down) in the pieces of ``plan`` (rows of per-stream block counts); the space behind a stream's
-    blocks holds 7s that must never be read.  Returns the samples per stream, concatenated."""
+    blocks holds 7s that must never be read, and the outputs behind a stream's count keep the canary of the caller-owned
+    ``out``.  Returns the samples per stream, concatenated."""
+    import torch
     n = x.shape[0]
     done = np.zeros(n, dtype=np.int64) if done is None else done
     got = [[] for _ in range(n)]
-    for new in plan:
+    for i, new in enumerate(plan):
         new = np.asarray(new, dtype=np.int64)
         G = max(int(new.max()), 1)
         chunk = np.full((n, G * rs.down), 7, dtype=x.dtype)
         for b in range(n):
             chunk[b, :new[b] * rs.down] = x[b, done[b] * rs.down:(done[b] + new[b]) * rs.down]
-        out, counts = rs.push(chunk, new)
+        # every other push into a caller-owned `out` full of canaries, the rest into the zeros that `push` allocates
+        mine = None if i % 2 else torch.full((n, G * rs.up * 4), FILL, dtype=torch.uint8, device="cuda").view(torch.float32)
+        out, counts = rs.push(chunk, new, out=mine)
         assert counts.tolist() == (new * rs.up).tolist() and tuple(out.shape) == (n, G * rs.up)
+        assert mine is None or out is mine
         out = out.cpu().numpy()
         for b in range(n):
             got[b].append(out[b, :counts[b]])
-            assert not out[b, counts[b]:].any(), "written behind a stream's samples"
+            behind = out[b, counts[b]:].view(np.uint8)
+            assert not behind.any() if mine is None else (behind == FILL).all(), "written behind a stream's samples"
         done += new
     return [np.concatenate(g) for g in got]
 
@@ -149,11 +164,20 @@ def test_streams_uncut_and_cut(torch_cuda, rate, dtype):
     G = STREAM_BLOCKS[rate]
     x, z = _uncut(rate, dtype)
     rs = frontend.ResampleStream(rate, 3)
-    assert (rs.unit_blocks, rs.unit_in, rs.unit_hops) == {48000: (160, 480, 1), 44100: (1, 441, 1)}[rate]
+    assert (rs.unit_blocks, rs.unit_in, rs.unit_hops) == frontend.resample_units(t.up, t.down)
+    assert rs.unit_blocks == 160 // np.gcd(t.up, 160) and rs.unit_in == rs.unit_blocks * t.down
+    assert rs.unit_blocks * t.up == rs.unit_hops * 160              # a unit is a whole number of front-end hops
+    known = {48000: (160, 480, 1), 44100: (1, 441, 1), 8000: (80, 80, 1), 11025: (1, 441, 4)}
+    assert rate not in known or (rs.unit_blocks, rs.unit_in, rs.unit_hops) == known[rate]
+    assert 2048 < G * t.up < 2 * 2048                               # one tile and a part of the second
     assert rs.state_bytes % 16 == 0 and rs.state_bytes >= 4 * t.history and not rs.state.any()
     out, counts = rs.push(x)
     assert counts.tolist() == [G * t.up] * 3
-    assert out.cpu().numpy().tobytes() == z.tobytes(), "the uncut run differs from the restatement"
+    out = out.cpu().numpy()
+    assert out.tobytes() == z.tobytes(), "the uncut run differs from the restatement"
+    for b in range(3):
+        ref, S = D.resample(x[b], t, 0, G * t.up)
+        D.check(out[b], ref, D.resample_bound(ref, S, t), f"resample streamed {rate} Hz {np.dtype(dtype).name} stream {b}")
     final = _history(rs).copy()
     want_hist = np.stack([R.widen(row).astype(np.float32)[-t.history:] for row in x])
     assert final.tobytes() == want_hist.tobytes()
@@ -161,6 +185,8 @@ def test_streams_uncut_and_cut(torch_cuda, rate, dtype):
     # state always in place
     a, c = G // 3, G // 5
     plan = [(1, 1, 1), (2, 0, 1), (0, 0, 0), (a, c, 1), (1, a, c), (c, 1, 0)]
+    if G < 10:                                                      # 11.025 and 22.05 kHz: 4 and 7 blocks in all
+        plan = [(1, 1, 1), (1, 0, 1), (0, 0, 0), (1, 1, 0)]
     plan.append(tuple(G - sum(p[b] for p in plan) for b in range(3)))
     assert min(plan[-1]) > 0
     rs2 = frontend.ResampleStream(rate, 3)
@@ -185,7 +211,7 @@ def test_streams_uncut_and_cut(torch_cuda, rate, dtype):
 def test_a_nan_sample_costs_the_outputs_whose_taps_cover_it(torch_cuda, rate):
     from lsm_speech_classifier_amd import frontend
     t = _table(rate)
-    G = {48000: 100, 44100: 6}[rate]
+    G = NAN_BLOCKS[rate]
     x = _uncut(rate, np.float32)[0][:, :G * t.down].copy()
     cut = G // 2
     at = cut * t.down - 10                                           # in the history of the second push

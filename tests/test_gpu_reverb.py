@@ -1,6 +1,8 @@
 """Reverberation on the GPU (SPEC.md 1.11; `lsm_reverb_f32`, `lsm_reverb_stream_f32`, `frontend.Reverberator`,
 `frontend.ReverbStream`, `HotPath(reverb=...)`, `features_from_audio(reverb=...)`, `AudioStreamBank(reverb=...)`): byte for
-byte against the NumPy restatement (tests/reverb_restatement.py), cut against uncut byte for byte, the refusals."""
+byte against the NumPy restatement (tests/reverb_restatement.py), cut against uncut byte for byte, the refusals; at the edges
+of the tap loop -- its groups of 8, its chunks of 1024, one tap short of the 16384 a row can hold -- also per output within the
+derived bound of the definition (tests/fir_definition.py)."""
 import ctypes as C
 import os
 import re
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fir_definition as D  # noqa: E402
 import mix_restatement as M  # noqa: E402
 import reverb_restatement as RR  # noqa: E402
 
@@ -241,6 +244,229 @@ def test_reverb_stream_set_reset_and_a_row_changed_between_pushes(torch_cuda):
     with pytest.raises(ValueError, match="out must not be audio"):
         a = o1.clone()
         rs.push(a, out=a)
+
+
+# ---- the edges of the tap loop and of the ABI's ranges, through the C ABI ---------------------------------------------------
+def _ptr(tensor):
+    return None if tensor is None else C.c_void_p(tensor.data_ptr())
+
+
+def _dev_ints(torch, values):
+    return None if values is None else torch.from_numpy(np.asarray(values, dtype=np.int32)).cuda()
+
+
+def _abi_batch(torch, audio, bank, lengths, rows, n_out):
+    """`lsm_reverb_f32` into a buffer with canaries behind it -> (B, n_out) float32.  ``lengths`` and ``rows`` go as they
+    are: nothing in front of the kernel looks at them."""
+    from lsm_speech_classifier_amd import _lib
+    lib = _lib.load()
+    (B, n), (M_, K) = audio.shape, bank.shape
+    a, h = torch.from_numpy(audio).cuda(), torch.from_numpy(bank).cuda()
+    ln, rw = _dev_ints(torch, lengths), _dev_ints(torch, rows)
+    buf = torch.full((B * n_out + 64,), float(CANARY), dtype=torch.float32, device="cuda")
+    rc = lib.lsm_reverb_f32(_void(a.data_ptr()), B, n, _void(h.data_ptr()), M_, K, _ptr(ln),
+                            _ptr(rw), n_out, _void(buf.data_ptr()),
+                            torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.lsm_last_error()
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert (got[B * n_out:] == CANARY).all(), "the launch wrote behind out"
+    return got[:B * n_out].reshape(B, n_out)
+
+
+def _abi_stream(torch, chunk, bank, lengths, rows, counts, state_in, state_out):
+    """`lsm_reverb_stream_f32` -> the whole of out (S, n_cols), the canaries behind every count included."""
+    from lsm_speech_classifier_amd import _lib
+    lib = _lib.load()
+    (S, H), (M_, K) = chunk.shape, bank.shape
+    a, h = torch.from_numpy(chunk).cuda(), torch.from_numpy(bank).cuda()
+    ln, rw, cn = _dev_ints(torch, lengths), _dev_ints(torch, rows), _dev_ints(torch, counts)
+    out = torch.full((S, H), float(CANARY), dtype=torch.float32, device="cuda")
+    rc = lib.lsm_reverb_stream_f32(_void(a.data_ptr()), S, H, _void(h.data_ptr()), M_, K, _ptr(ln),
+                                   _ptr(rw), _ptr(cn),
+                                   _ptr(state_in),
+                                   _ptr(state_out), _void(out.data_ptr()),
+                                   torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.lsm_last_error()
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _push_all(torch, x, bank, lengths, rows, table, in_place, start=None, pad=0):
+    """Push ``x`` (S, total) in the pieces of ``table`` (pushes, S) -> (samples per stream, the final state blocks as
+    bytes).  Out of place every call writes a fresh block prefilled with 0x5A; the first one reads ``start`` (None: NULL)."""
+    S, K = x.shape[0], bank.shape[1]
+    sb = max(16, (4 * (K - 1) + 15) // 16 * 16)
+    state = None if start is None else torch.from_numpy(start).cuda()
+    if in_place and state is None:
+        state = torch.zeros((S, sb), dtype=torch.uint8, device="cuda")
+    got, at = [[] for _ in range(S)], np.zeros(S, dtype=np.int64)
+    for new in np.asarray(table, dtype=np.int64):
+        H = max(1, int(new.max()))
+        chunk = np.full((S, H), 7.0, dtype=np.float32)
+        for b in range(S):
+            chunk[b, :new[b]] = x[b, at[b]:at[b] + new[b]]
+        nxt = state if in_place else torch.full((S, sb), 0x5A, dtype=torch.uint8, device="cuda")
+        o = _abi_stream(torch, chunk, bank, lengths, rows, new, state, nxt)
+        state = nxt
+        for b in range(S):
+            got[b].append(o[b, :new[b]])
+            assert (o[b, new[b]:] == CANARY).all(), "samples of out behind count were written"
+        at += new
+    assert at.tolist() == [x.shape[1]] * S
+    return [np.concatenate(g) for g in got], state.cpu().numpy()
+
+
+def _edges():
+    """The bank of `fir_definition.reverb_edge_bank`, one clip per row, the restatement and the definition with its bound."""
+    if "edges" not in _CACHE:
+        bank, lengths = D.reverb_edge_bank()
+        audio = D.reverb_edge_audio()
+        rows = np.arange(len(lengths), dtype=np.int32)
+        want = RR.reverb(audio, bank, lengths, rows, D.REVERB_N_OUT)
+        refs = [D.reverb(audio[r], bank[r, :lengths[r]], D.REVERB_N_OUT) for r in rows]
+        bounds = [D.reverb_bound(ref, S, lengths[r]) for r, (ref, S) in enumerate(refs)]
+        _CACHE["edges"] = (bank, lengths, audio, rows, want, [ref for ref, _ in refs], bounds)
+    return _CACHE["edges"]
+
+
+def test_row_lengths_at_the_edges_of_the_tap_loop_batch(torch_cuda):
+    """Rows that end a tap in front of, at and behind a group of 8 and a chunk of 1024 -- 1025: a second chunk of one tap,
+    nothing but the remainder group -- and one tap short of MAX_TAPS, 1e30 behind each row's length.  With the whole tail
+    behind the clips, so that the last tap of the longest row meets a sample."""
+    bank, lengths, audio, rows, want, refs, bounds = _edges()
+    assert bank.shape == (12, 16384) and audio.shape == (12, 2100) and lengths.tolist() == list(D.REVERB_LENGTHS)
+    got = _abi_batch(torch_cuda, audio, bank, lengths, rows, D.REVERB_N_OUT)
+    worst = 0.0
+    for r, n in enumerate(lengths):
+        assert _same(got[r], want[r]), f"len {n}: max |diff| = {np.abs(got[r] - want[r]).max():.3e}"
+        w = D.worst(got[r], refs[r], bounds[r])
+        print(f"reverb batch len {n}: worst err / bound = {w:.4f}")
+        worst = max(worst, w)
+        assert got[r, D.REVERB_N + n - 2] != 0 and not got[r, D.REVERB_N + n - 1:].any()
+    print(f"reverb batch: worst err / bound = {worst:.4f}")
+    assert worst <= 1.0
+    assert np.isfinite(got).all() and np.abs(got).max() < 1e3, "a tap behind a row's length reached the output"
+    # n_out = n, the recipe's length, is the prefix
+    short = _abi_batch(torch_cuda, audio, bank, lengths, rows, D.REVERB_N)
+    assert _same(short, want[:, :D.REVERB_N])
+
+
+def test_row_lengths_at_the_edges_of_the_tap_loop_streamed(torch_cuda):
+    """The same clips as streams cut at 1, 2047 and the rest, then a push of zeros as long as the tail: the deepest taps
+    of the longest row read the clip out of the history."""
+    bank, lengths, audio, rows, want, refs, bounds = _edges()
+    K, N = bank.shape[1], D.REVERB_N_OUT
+    x = np.concatenate([audio, np.zeros((len(rows), N - D.REVERB_N), dtype=np.float32)], axis=1)
+    cuts = list(D.REVERB_CUTS) + [N - D.REVERB_N]
+    table = np.repeat(np.array(cuts, dtype=np.int64)[:, None], len(rows), axis=1)
+    got, state = _push_all(torch_cuda, x, bank, lengths, rows, table, in_place=True)
+    worst = 0.0
+    assert state.shape == (12, 65536)
+    for r, n in enumerate(lengths):
+        assert _same(got[r], want[r]), f"len {n}: max |diff| = {np.abs(got[r] - want[r]).max():.3e}"
+        w = D.worst(got[r], refs[r], bounds[r])
+        print(f"reverb streamed len {n}: worst err / bound = {w:.4f}")
+        worst = max(worst, w)
+        assert _same(state[r, :4 * (K - 1)].view(np.float32), x[r, N - (K - 1):]) and not state[r, 4 * (K - 1):].any()
+    print(f"reverb streamed: worst err / bound = {worst:.4f}")
+    assert worst <= 1.0
+    y, st = RR.stream_cut(x[9], bank, cuts, lengths, 9)
+    assert _same(y, got[9]) and _same(st, state[9, :4 * (K - 1)].view(np.float32))
+
+
+def test_rir_len_outside_its_range_is_clamped(torch_cuda):
+    """`rir_len` of 0, -3 and K + 5 behaves as 1, 1 and K (the Python layer refuses such lengths; the ABI clamps them)."""
+    K, n = 40, 2100
+    bank, audio = _rir(3, K, 81), _noise(3, n, 82)
+    bank[:2, 1:] = np.float32(1e30)                                   # rows 0 and 1 end behind their first tap
+    raw, rule = np.array([0, -3, K + 5], dtype=np.int32), np.array([1, 1, K], dtype=np.int32)
+    rows = np.array([0, 1, 2], dtype=np.int32)
+    assert [RR.row_length(raw, r, K) for r in range(3)] == rule.tolist()
+    want = RR.reverb(audio, bank, raw, rows, n + K)
+    assert np.isfinite(want).all() and want.any(axis=1).all()
+    for lengths in (raw, rule):
+        assert _same(_abi_batch(torch_cuda, audio, bank, lengths, rows, n + K), want)
+        got, state = _push_all(torch_cuda, audio, bank, lengths, rows, [[700] * 3, [1400] * 3], in_place=False)
+        assert all(_same(got[b], want[b, :n]) for b in range(3))
+        assert _same(state[:, :4 * (K - 1)].copy().view(np.float32), audio[:, n - (K - 1):])
+
+
+@pytest.mark.parametrize("in_place", [True, False], ids=["in-place", "out-of-place"])
+def test_count_outside_its_range_is_clamped(torch_cuda, in_place):
+    """`count` of -1 and n_cols + 9 behaves as 0 and n_cols.  For 0 nothing is written to the row, and the state block
+    stays as it is in place and is copied out of place."""
+    torch = torch_cuda
+    K, H, S = 40, 300, 3
+    bank, x = _rir(1, K, 83), _noise(S, H, 84)
+    sb = 160
+    start = np.full((S, sb), 0x3C, dtype=np.uint8)                    # a word of padding behind the 39 samples
+    start[:, :4 * (K - 1)] = _noise(S, K - 1, 85).view(np.uint8)
+    raw, rule = [-1, H + 9, 5], [0, H, 5]
+    assert [RR.push_count(raw, b, H) for b in range(S)] == rule
+    results = []
+    for counts in (raw, rule):
+        state = torch.from_numpy(start).cuda()
+        nxt = state if in_place else torch.full((S, sb), 0x5A, dtype=torch.uint8, device="cuda")
+        out = _abi_stream(torch, x, bank, None, None, counts, state, nxt)
+        assert in_place or state.cpu().numpy().tobytes() == start.tobytes(), "state_in was written"
+        results.append((out, nxt.cpu().numpy()))
+    (out, state), (out_rule, state_rule) = results
+    assert _same(out, out_rule) and state.tobytes() == state_rule.tobytes()
+    assert (out[0] == CANARY).all() and state[0].tobytes() == start[0].tobytes()
+    for b in (1, 2):
+        c = rule[b]
+        y, st = RR.stream(x[b, :c], bank, start[b, :4 * (K - 1)].view(np.float32))
+        assert _same(out[b, :c], y) and (out[b, c:] == CANARY).all()
+        assert _same(state[b, :4 * (K - 1)].view(np.float32), st) and (state[b, 4 * (K - 1):] == 0x3C).all()
+
+
+@pytest.mark.parametrize("in_place", [True, False], ids=["in-place", "out-of-place"])
+def test_streams_of_one_tap(torch_cuda, in_place):
+    """K = 1: no history, `have_hist` false, a state block of 16 bytes that is all padding."""
+    torch = torch_cuda
+    from lsm_speech_classifier_amd import _lib
+    S, total = 3, 2500
+    bank = np.array([[0.75], [-1.5]], dtype=np.float32)
+    rows = np.array([0, 1, -1], dtype=np.int32)
+    x = _noise(S, total, 86)
+    x[2, 5] = np.float32(-0.0)
+    assert _lib.load().lsm_reverb_state_bytes(1) == 16
+    table = [[0, 0, 0], [1, 2100, 0], [2049, 0, 7], [450, 400, 2493]]
+    start = np.full((S, 16), 0x3C, dtype=np.uint8)
+    got, state = _push_all(torch, x, bank, None, rows, table, in_place, start=start)
+    assert (state == 0x3C).all(), "the padding of a state block changed"
+    for b in range(S):
+        y, _ = RR.stream_cut(x[b], bank, [total], None, int(rows[b]))
+        assert _same(got[b], y), b
+    assert _same(got[0], x[0] * np.float32(0.75)) and _same(got[2], x[2])
+    # every stream starts (state_in NULL): out of place the block is zeros
+    got, state = _push_all(torch, x, bank, None, rows, [[total] * 3], in_place=False)
+    assert not state.any() and _same(got[1], x[1] * np.float32(-1.5))
+    # and no state at all
+    out = _abi_stream(torch, x, bank, None, rows, None, None, None)
+    assert all(_same(out[b], got[b]) for b in range(S))
+
+
+def test_counts_that_end_inside_a_tile(torch_cuda):
+    """513: the second wave owns one output; 2041: the last lane of the tile stores one of its 8; 2049: a second tile for one
+    output.  Behind each count the canary stays."""
+    torch = torch_cuda
+    K, H = 130, 2100
+    counts = [513, 2041, 2049]
+    bank, x = _rir(2, K, 87), _noise(3, H, 88)
+    rows = np.array([0, 1, 0], dtype=np.int32)
+    sb = 528
+    for in_place in (True, False):
+        state = torch.zeros((3, sb), dtype=torch.uint8, device="cuda")
+        nxt = state if in_place else torch.full((3, sb), 0x5A, dtype=torch.uint8, device="cuda")
+        out = _abi_stream(torch, x, bank, None, rows, counts, state, nxt)
+        state = nxt.cpu().numpy()
+        for b, c in enumerate(counts):
+            y, st = RR.stream(x[b, :c], bank, RR.new_state(K), None, int(rows[b]))
+            assert _same(out[b, :c], y), f"count {c}"
+            assert (out[b, c:] == CANARY).all(), f"count {c}: written behind it"
+            assert _same(state[b, :4 * (K - 1)].view(np.float32), st) and not state[b, 4 * (K - 1):].any()
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------
