@@ -212,7 +212,7 @@ def run_network_diagnostics(lsm, X_sample_batch):
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
                     num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
-                    time_segments=1, corrupt=None, reverb=None):
+                    time_segments=1, corrupt=None, reverb=None, speed=None):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -239,7 +239,10 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     clips with their entries of the one plan.
 
     `reverb` = ``(bank (M, K) float32, lengths, frontend.ReverbPlan of the n clips)``: every clip is first convolved with
-    its room impulse response on the GPU (SPEC.md 1.11), ahead of `corrupt`."""
+    its room impulse response on the GPU (SPEC.md 1.11), ahead of `corrupt`.
+
+    `speed` = ``(factors, frontend.SpeedPlan of the n clips)``: every clip is first played at its speed among ``factors`` on
+    the GPU (SPEC.md 1.12), ahead of `reverb`."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
@@ -267,7 +270,12 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     rv = rooms = None
     if reverb is not None:
         rv, rooms = frontend.Reverberator(reverb[0], reverb[1], device=dev), reverb[2]
+    sp = paces = None
+    if speed is not None:
+        sp, paces = frontend.SpeedPerturber(speed[0], device=dev), speed[1]
     head_audio = audio[idx_train[:500]]
+    if sp is not None:
+        head_audio = sp.perturb(head_audio, paces.take(idx_train[:500]).choice)
     if rv is not None:
         head_audio = rv.reverb(head_audio, rooms.take(idx_train[:500]).rows)
     if mixer is not None:
@@ -295,7 +303,8 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
         local = pipeline.features_from_audio(audio[idx[lo:hi]], fe, lsm, keys, batch=batch, device_out=True,
                                              time_segments=time_segments,
                                              corrupt=(mixer, plan.take(idx[lo:hi])) if mixer is not None else None,
-                                             reverb=(rv, rooms.take(idx[lo:hi])) if rv is not None else None)
+                                             reverb=(rv, rooms.take(idx[lo:hi])) if rv is not None else None,
+                                             speed=(sp, paces.take(idx[lo:hi])) if sp is not None else None)
         return lsm_dist.gather_rows(local, len(idx))
 
     X_train_dev = split_features(idx_train)

@@ -140,6 +140,13 @@ REVERB_SIGS = {
 }
 REVERB_SYMBOLS = tuple(REVERB_SIGS)
 
+# include/lsm_hip_speed.h (SPEC.md §1.12): speed perturbation in front of the reverberation, a bank of resampler designs
+SPEED_SIGS = {
+    "lsm_speed_lds_bytes": (C.c_long, [c_void, c_int]),
+    "lsm_speed_f32": (c_int, [c_void, c_int, c_int, c_int, c_void, c_int, c_void, c_int, c_void, c_int, c_void, c_void]),
+}
+SPEED_SYMBOLS = tuple(SPEED_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -189,7 +196,7 @@ def load():
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
-                              + list(MIX_SIGS.items()) + list(REVERB_SIGS.items())):
+                              + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from fractions import Fraction
 from math import gcd
 from typing import NamedTuple
 
@@ -1359,6 +1360,154 @@ class ReverbStream:
                 _dev(cnt) if cnt is not None else None, _dev(self.state), _dev(self.state), _dev(out),
                 torch.cuda.current_stream(self.device).cuda_stream), "lsm_reverb_stream_f32")
         return out, new
+
+
+# ---- speed perturbation (SPEC.md §1.12, include/lsm_hip_speed.h) --------------------------------------------------------
+SPEED_MAX_DESIGNS = 16
+SPEED_MAX_ROWS = 65535                  # rows of one launch
+
+
+def _speed_fraction(factor) -> Fraction:
+    """A speed factor as an exact fraction: an int, a Fraction, a string such as "11/10" or "1.1"; a float through its
+    shortest decimal form (``Fraction(str(x))``: 1.1 is 11/10, not the binary value next to it)."""
+    if isinstance(factor, bool):
+        raise ValueError(f"a speed factor must be a number or a string, got {factor!r}")
+    try:
+        if isinstance(factor, (float, np.floating)):
+            return Fraction(str(float(factor)))
+        if isinstance(factor, (int, np.integer)):
+            return Fraction(int(factor))
+        if isinstance(factor, (Fraction, str)):
+            return Fraction(factor)
+    except (ValueError, ZeroDivisionError, OverflowError) as e:
+        raise ValueError(f"{factor!r} is no speed factor: {e}") from None
+    raise ValueError(f"a speed factor must be an int, a Fraction, a float or a string, got {type(factor).__name__}")
+
+
+def speed_design(factor) -> ResampleTable | None:
+    """The design of playing a clip ``factor`` times faster (SPEC.md §1.12): ``resample_table(int(16000 * factor), 16000)``,
+    or None for 1, the identity.  ``factor`` must lie in [1/2, 2] and make ``16000 * factor`` an integer rate."""
+    s = _speed_fraction(factor)
+    if not Fraction(1, 2) <= s <= 2:
+        raise ValueError(f"speed factor {factor!r} outside [1/2, 2]")
+    rate = SAMPLE_RATE * s
+    if rate.denominator != 1:
+        raise ValueError(f"speed factor {factor!r}: {SAMPLE_RATE} * factor = {float(rate):.6g} is no integer sample rate")
+    return None if s == 1 else resample_table(int(rate), SAMPLE_RATE)
+
+
+class SpeedPlan(NamedTuple):
+    """Per-clip choices among a list of speed factors (`speed_plan`): ``choice`` int32 on the host, an index into the list,
+    -1 = an unperturbed clip."""
+    choice: np.ndarray
+
+    def part(self, lo: int, hi: int) -> "SpeedPlan":
+        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
+        return SpeedPlan(self.choice[lo:hi])
+
+    def take(self, idx) -> "SpeedPlan":
+        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
+        return SpeedPlan(self.choice[np.asarray(idx, dtype=np.int64)])
+
+
+def speed_plan(n_clips: int, n_factors: int, prob: float = 1.0, seed: int = 42) -> SpeedPlan:
+    """The speed of every clip of a listing, drawn from ``np.random.RandomState([seed, 2])`` -- a generator of its own, so
+    `mix_plan`'s and `reverb_plan`'s draws for the same seed stay as they are -- for ALL ``n_clips`` clips in listing order:
+    the choices (``randint(0, n_factors)``), then ``u = random_sample``; a clip with ``u >= prob`` is unperturbed (-1)."""
+    n, M, p = int(n_clips), int(n_factors), float(prob)
+    if n < 0 or M < 1 or not 0.0 <= p <= 1.0:
+        raise ValueError(f"speed_plan needs n_clips >= 0, n_factors >= 1 and prob in [0, 1], got {n_clips}, {n_factors}, "
+                         f"{prob}")
+    rs = np.random.RandomState([int(seed), 2])
+    choice = rs.randint(0, M, size=n).astype(np.int32)
+    u = rs.random_sample(n)
+    choice[u >= p] = -1
+    return SpeedPlan(choice)
+
+
+def speed_bank(factors):
+    """``factors`` -> ``(tables, row_of_choice)``: the designs of the non-unit factors in the list's order (`speed_design`,
+    at most 16, all distinct) and, per factor, its row among them as int32, -1 for a unit factor."""
+    factors = list(factors)
+    if not factors:
+        raise ValueError("a list of speed factors must name at least one")
+    seen, tables, row_of_choice = {}, [], []
+    for f in factors:
+        s = _speed_fraction(f)
+        if s in seen:
+            raise ValueError(f"speed factor {f!r} is named twice")
+        table = speed_design(f)
+        seen[s] = -1 if table is None else len(tables)
+        row_of_choice.append(seen[s])
+        if table is not None:
+            tables.append(table)
+    if len(tables) > SPEED_MAX_DESIGNS:
+        raise ValueError(f"{len(tables)} speed factors other than 1: one launch serves at most {SPEED_MAX_DESIGNS} designs")
+    return tables, np.asarray(row_of_choice, dtype=np.int32)
+
+
+class SpeedPerturber:
+    """Clips played at per-clip speeds in one launch (`lsm_speed_f32`, SPEC.md §1.12).  ``factors``: the speeds a plan's
+    choices index (`speed_design`), up to 16 distinct ones other than 1 and at least one; a factor of 1 maps to row -1, the
+    unperturbed copy.  ``tables`` are the designs, ``designs`` their (n, 5) int32 rows of up, down, n_taps, delay and
+    tap_offset on the host, ``taps_dev`` their taps one behind the other on the device, ``row_of_choice`` the design row of
+    every factor."""
+
+    def __init__(self, factors, device=None):
+        self.factors = list(factors)
+        self.tables, self.row_of_choice = speed_bank(self.factors)
+        if not self.tables:
+            raise ValueError("every speed factor is 1: there is nothing to perturb")
+        offsets = np.cumsum([0] + [len(t.taps) for t in self.tables])
+        self.designs = np.ascontiguousarray(
+            [[t.up, t.down, len(t.taps), t.delay, int(o)] for t, o in zip(self.tables, offsets)], dtype=np.int32)
+        self.n_taps_total = int(offsets[-1])
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        self.taps_dev = torch.from_numpy(np.concatenate([t.taps for t in self.tables])).to(self.device)
+        self.lds_bytes = int(self.lib.lsm_speed_lds_bytes(_host(self.designs), len(self.designs)))
+
+    def rows_of(self, choice, n: int):
+        """``choice`` (a number or ``n`` of them, indices into ``factors``, below 0 = unperturbed; None: factor 0
+        everywhere) -> the design rows as int32, or None where every clip takes row 0."""
+        if choice is None:
+            return None if self.row_of_choice[0] == 0 else np.full(n, self.row_of_choice[0], dtype=np.int32)
+        choice = _per_clip(choice, n, np.int32, "choice")
+        if (choice >= len(self.factors)).any():
+            raise ValueError(f"choice {choice.tolist()} outside the {len(self.factors)} speed factors")
+        return np.where(choice < 0, np.int32(-1), self.row_of_choice[np.maximum(choice, 0)]).astype(np.int32)
+
+    def perturb(self, audio, choice=None, n_out: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``audio`` (n, L) float32 or int16, NumPy or tensor -> float32 (n, n_out) on the device, clip c played at
+        ``factors[choice[c]]`` (`rows_of`).  ``n_out`` defaults to L: a faster clip is padded with what the filter rings
+        out and zeros, a slower one trimmed, to the clip length.  ``out``: a caller-owned contiguous float32 (n, n_out)
+        tensor on the device, never ``audio``."""
+        audio, fmt = checked_pcm(audio)
+        n, L = (int(v) for v in audio.shape)
+        n_out = L if n_out is None else int(n_out)
+        if n_out < 1:
+            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        rows = self.rows_of(choice, n)
+        if out is not None:
+            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) \
+                    or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
+            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
+                raise ValueError("out must not be audio: an output reads the samples around it")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            if out is None:
+                out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+            rows_dev = None if rows is None else torch.from_numpy(rows).to(self.device, non_blocking=True)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for r0 in range(0, n, SPEED_MAX_ROWS):
+                k = min(SPEED_MAX_ROWS, n - r0)
+                _lib.check(self.lib.lsm_speed_f32(
+                    _dev(audio[r0:]), fmt, k, L, _dev(self.taps_dev), self.n_taps_total, _host(self.designs),
+                    len(self.designs), _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out, _dev(out[r0:]),
+                    stream), "lsm_speed_f32")
+        return out
 
 
 _FRONT_ENDS: dict = {}

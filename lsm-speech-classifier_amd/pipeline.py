@@ -85,11 +85,13 @@ class HotPath:
     `mixer` = a `frontend.NoiseMixer`: a step submitted with `mix=` (a `frontend.MixPlan` of its clips) is corrupted on the
     device before its front end (SPEC.md §1.10); without `mix` a step launches what it launches without a mixer.
     `reverb` = a `frontend.Reverberator`: a step submitted with `reverb=` (a `frontend.ReverbPlan` of its clips) is convolved
-    with its rooms on the device (SPEC.md §1.11) ahead of the mixer; without it nothing more is launched."""
+    with its rooms on the device (SPEC.md §1.11) ahead of the mixer; without it nothing more is launched.
+    `speed` = a `frontend.SpeedPerturber`: a step submitted with `speed=` (a `frontend.SpeedPlan` of its clips) is played at
+    its clips' speeds on the device (SPEC.md §1.12) ahead of the reverberator: speed, reverb, mixer, front end."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
-                 fe_streams: int | None = None, time_segments: int = 1, mixer=None, reverb=None):
+                 fe_streams: int | None = None, time_segments: int = 1, mixer=None, reverb=None, speed=None):
         if indexed_device(fe.device) != indexed_device(net.device):
             raise ValueError(f"front end on {fe.device}, reservoir on {net.device}")
         if mixer is not None and indexed_device(mixer.device) != indexed_device(fe.device):
@@ -100,6 +102,10 @@ class HotPath:
             raise ValueError(f"reverberator on {reverb.device}, front end on {fe.device}")
         self.reverb = reverb                # frontend.Reverberator or None: submit(reverb=...) convolves a step's clips with it
         self._reverbed = {}                 # (rotation slot, batch shape) -> the reverb launch's output buffer
+        if speed is not None and indexed_device(speed.device) != indexed_device(fe.device):
+            raise ValueError(f"speed perturber on {speed.device}, front end on {fe.device}")
+        self.speed = speed                  # frontend.SpeedPerturber or None: submit(speed=...) plays a step's clips through it
+        self._sped = {}                     # (rotation slot, batch shape) -> the speed launch's output buffer
         if fe.n_channels != net.n_channels:
             raise ValueError(f"front end has {fe.n_channels} channels, reservoir expects {net.n_channels}")
         self.fe, self.net = fe, net
@@ -164,7 +170,7 @@ class HotPath:
         return feats
 
     def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
-               reverb=None):
+               reverb=None, speed=None):
         """Issue one step on the next stream of the rotation.  `audio`: (B, n_samples) float32 -- device tensor,
         or pinned/pageable host tensor / NumPy array, uploaded on the step's own stream.  Returns (features
         (B, n_keys*N_out) device tensor, stream it is produced on); the caller waits (`stream.synchronize()`,
@@ -187,12 +193,16 @@ class HotPath:
         synchronisation.
         `reverb`: a `frontend.ReverbPlan` of this step's B clips (needs the pipeline's `reverb`): one more launch on the same
         stream ahead of the mixer's, into a buffer the rotation slot owns.
+        `speed`: a `frontend.SpeedPlan` of this step's B clips (needs the pipeline's `speed`): one more launch on the same
+        stream ahead of the reverberator's, into a buffer the rotation slot owns.
         Back-pressure: when `max_ahead` earlier steps have not finished, submit() first waits for the oldest."""
         if mix is not None and (self.mixer is None or stage == "reservoir"):
             raise ValueError("submit(mix=...) needs a HotPath built with a mixer and a step that has a front end")
         if reverb is not None and (self.reverb is None or stage == "reservoir"):
             raise ValueError("submit(reverb=...) needs a HotPath built with a reverberator and a step that has a front end")
-        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix, reverb)
+        if speed is not None and (self.speed is None or stage == "reservoir"):
+            raise ValueError("submit(speed=...) needs a HotPath built with a speed perturber and a step that has a front end")
+        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix, reverb, speed)
         if st is not None and self.n_streams > 1:
             ev = torch.cuda.Event()
             ev.record(st)
@@ -200,7 +210,7 @@ class HotPath:
         return res, st
 
     def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
-                reverb=None):
+                reverb=None, speed=None):
         """submit() without the in-flight bookkeeping."""
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
@@ -214,7 +224,7 @@ class HotPath:
             topology = self._submit_two_stages
         else:
             topology = self._submit_rotation
-        return topology(slot, audio, stats_out, after, out, stage, tail, mix, reverb)
+        return topology(slot, audio, stats_out, after, out, stage, tail, mix, reverb, speed)
 
     def _wait_for_input(self, stream, cur, audio, after) -> None:
         """The ordering of a device input (`submit`): `stream` waits for `after`, or for what `cur` has issued so far."""
@@ -223,24 +233,24 @@ class HotPath:
         elif torch.is_tensor(audio) and audio.device == self.device:
             stream.wait_stream(cur)
 
-    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None):
+    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None):
         """Everything on the current stream."""
         cur = torch.cuda.current_stream(self.device)
         if after is not None:
             cur.wait_event(after)
         with torch.cuda.device(self.device):
-            x = audio if stage == "reservoir" else self._mix(self._reverb(self._to_device(audio, slot), reverb, slot), mix, slot)
+            x = audio if stage == "reservoir" else self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
             return self._one(x, stats_out, out, stage, tail), cur
 
-    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None):
+    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None):
         """The step keeps to reservoir stream `slot`: its front end, then its reservoir launch."""
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             self._wait_for_input(st, cur, audio, after)
-            x = audio if stage == "reservoir" else self._mix(self._reverb(self._to_device(audio, slot), reverb, slot), mix, slot)
+            x = audio if stage == "reservoir" else self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
             return self._one(x, stats_out, out, stage, tail), st
 
-    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None):
+    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None):
         """The front end on the next front-end stream, the reservoir launch on reservoir stream `slot` behind an event."""
         fslot = (self._step - 1) % self.n_fe_streams
         st, fst, cur = self.streams[slot], self.fe_streams[fslot], torch.cuda.current_stream(self.device)
@@ -248,7 +258,7 @@ class HotPath:
             with torch.cuda.stream(fst):
                 self._wait_for_input(fst, cur, audio, after)
                 low_latency = self._low_latency(tail)
-                x = self._mix(self._reverb(self._to_device(audio, ("fe", fslot)), reverb, ("fe", fslot)), mix, ("fe", fslot))
+                x = self._augmented(self._to_device(audio, ("fe", fslot)), speed, reverb, mix, ("fe", fslot))
                 # the front end's own decision (mel branch, > 1024 filters and LSM_FRONTEND_SPLIT=1 take the split
                 # route, which allocates its raster on the front-end stream): only the fused launch of a full step
                 # writes into the pipeline's rings, everything else goes through record_stream below
@@ -319,6 +329,20 @@ class HotPath:
             buf = self._reverbed[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
         return self.reverb.reverb(x, plan.rows, out=buf)
 
+    def _speed(self, x, plan, slot):
+        """The step's clips played at the speeds of `plan` on the current stream (ahead of `_reverb`), or `x` itself."""
+        if plan is None:
+            return x
+        key = (slot, tuple(x.shape))
+        buf = self._sped.get(key)
+        if buf is None:
+            buf = self._sped[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+        return self.speed.perturb(x, plan.choice, out=buf)
+
+    def _augmented(self, x, speed, reverb, mix, slot):
+        """The augmentation chain in front of the front end, in the recipe's order: speed, reverberation, mixer."""
+        return self._mix(self._reverb(self._speed(x, speed, slot), reverb, slot), mix, slot)
+
     def prime(self, audio, stage: str = "full", min_ms: float = 0.0):
         """One untimed step on EVERY stream of the pipeline, then a synchronisation: each stream's first use
         pays for its allocator pool (torch caches device memory per stream: the first `encode` on a stream
@@ -369,10 +393,11 @@ class HotPath:
         torch.cuda.current_stream(self.device).synchronize()
 
     # ---- many steps -------------------------------------------------------------------------
-    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None, reverbs=None) -> torch.Tensor:
+    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None, reverbs=None, speeds=None) -> torch.Tensor:
         """Feature rows of every batch, in order, as one (n_clips, n_feat) device tensor.  `audio_batches`
         is an iterable of (B_i, n_samples) arrays/tensors (host or device); `mixes`, when given, an iterable of one
-        `frontend.MixPlan` per batch (`submit(mix=...)`); `reverbs` likewise one `frontend.ReverbPlan` per batch."""
+        `frontend.MixPlan` per batch (`submit(mix=...)`); `reverbs` likewise one `frontend.ReverbPlan` per batch, `speeds` one
+        `frontend.SpeedPlan` per batch."""
         self.fork_from_current()
         # The last TAIL_STEPS batches are submitted in the low-latency layouts: that needs a look-ahead of TAIL_STEPS
         # batches, not the whole list -- a lazily produced stream of (pinned or device) batches is consumed as it comes and
@@ -381,14 +406,16 @@ class HotPath:
         parts, ahead, it = [], deque(), iter(audio_batches)
         plans = iter(mixes) if mixes is not None else None
         rooms = iter(reverbs) if reverbs is not None else None
+        paces = iter(speeds) if speeds is not None else None
         for a in it:
-            ahead.append((a, next(plans) if plans is not None else None, next(rooms) if rooms is not None else None))
+            ahead.append((a, next(plans) if plans is not None else None, next(rooms) if rooms is not None else None,
+                          next(paces) if paces is not None else None))
             if len(ahead) > TAIL_STEPS:
-                a0, m0, r0 = ahead.popleft()
-                parts.append(self.submit(a0, tail=False, mix=m0, reverb=r0)[0])
+                a0, m0, r0, s0 = ahead.popleft()
+                parts.append(self.submit(a0, tail=False, mix=m0, reverb=r0, speed=s0)[0])
         while ahead:
-            a0, m0, r0 = ahead.popleft()
-            parts.append(self.submit(a0, tail=True, mix=m0, reverb=r0)[0])
+            a0, m0, r0, s0 = ahead.popleft()
+            parts.append(self.submit(a0, tail=True, mix=m0, reverb=r0, speed=s0)[0])
         self.synchronize()
         if not parts:
             n_keys = len(self.feature_keys) if self.feature_keys is not None else 8
@@ -402,21 +429,26 @@ class HotPath:
 
 def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1024,
                         streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1, corrupt=None,
-                        reverb=None):
+                        reverb=None, speed=None):
     """Host convenience for the drop-in scripts' in-memory path: (n, n_samples) float32 on the host ->
     (n, n_feat) float32 on the host (or, `device_out`, still on the GPU for a gather), batches of `batch` clips
     through the overlapped pipeline (pinned staging, uploads on the steps' streams).  n = 0 (an empty shard)
     gives an empty (0, n_feat) block.  `time_segments` = K > 1: K segment rows per clip side by side (`HotPath`), n_feat is
     K times as wide.  `corrupt` = ``(frontend.NoiseMixer, frontend.MixPlan of the n clips)``: every batch is corrupted on
     the device with its slice of the plan before its front end (SPEC.md §1.10).  `reverb` = ``(frontend.Reverberator,
-    frontend.ReverbPlan of the n clips)``: every batch is convolved with its rooms ahead of that (SPEC.md §1.11)."""
+    frontend.ReverbPlan of the n clips)``: every batch is convolved with its rooms ahead of that (SPEC.md §1.11).  `speed` =
+    ``(frontend.SpeedPerturber, frontend.SpeedPlan of the n clips)``: every batch is played at its clips' speeds ahead of
+    both (SPEC.md §1.12)."""
+    sp, paces = speed if speed is not None else (None, None)
+    if paces is not None and len(paces.choice) != len(audio):
+        raise ValueError(f"the speed plan covers {len(paces.choice)} clips, audio has {len(audio)}")
     rv, rooms = reverb if reverb is not None else (None, None)
     if rooms is not None and len(rooms.rows) != len(audio):
         raise ValueError(f"the reverb plan covers {len(rooms.rows)} clips, audio has {len(audio)}")
     mixer, plan = corrupt if corrupt is not None else (None, None)
     if plan is not None and len(plan.rows) != len(audio):
         raise ValueError(f"the plan covers {len(plan.rows)} clips, audio has {len(audio)}")
-    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer, reverb=rv)
+    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer, reverb=rv, speed=sp)
     pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
     if len(pinned):
         try:
@@ -426,7 +458,8 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     with torch.cuda.device(hp.device):
         feats = hp.run((pinned[lo:lo + batch] for lo in range(0, len(pinned), batch)),
                        mixes=(plan.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if plan is not None else None,
-                       reverbs=(rooms.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if rooms is not None else None)
+                       reverbs=(rooms.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if rooms is not None else None,
+                       speeds=(paces.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if paces is not None else None)
     return feats if device_out else feats.cpu().numpy()
 
 

@@ -50,6 +50,14 @@ def _reverb_args(a):
     return out if _augment_args(a) else out + ["--augment-seed", str(a.augment_seed)]
 
 
+def _speed_args(a):
+    """Nothing without --speed-factors; the seed goes along unless the corruption or reverberation flags already carry it."""
+    if a.speed_factors is None:
+        return []
+    out = ["--speed-factors", str(a.speed_factors), "--speed-prob", str(a.speed_prob)]
+    return out if _augment_args(a) or _reverb_args(a) else out + ["--augment-seed", str(a.augment_seed)]
+
+
 def _reservoir_args(a):
     out = []
     for flag, v in (("--num-neurons", a.num_neurons), ("--num-output-neurons", a.num_output_neurons),
@@ -62,7 +70,8 @@ def _reservoir_args(a):
 STAGES = (
     ("Step 1: Creating Spike Train Dataset",
      lambda a: ["create_dataset.py", "--n-filters", str(a.n_filters), "--filterbank", a.filterbank]
-     + _corpus_args(a) + (["--packed"] if a.packed else []) + _augment_args(a) + _reverb_args(a)),
+     + _corpus_args(a) + (["--packed"] if a.packed else []) + _augment_args(a) + _reverb_args(a)
+     + _speed_args(a)),
     ("Step 2: Extracting LSM Features",
      lambda a: ["extract_lsm_features.py", "--feature-set", a.feature_set, "--multiplier", str(a.multiplier)]
      + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])),
@@ -81,10 +90,13 @@ audio, labels = cd.collect_audio(commands=cd.commands_from_args(a), dataset_root
 corrupt = cd.corruption(augment, len(audio)) if augment else None
 room = cd.reverb_from_args(a)
 reverb = cd.reverberation(room, len(audio)) if room else None
+pace = cd.speed_from_args(a)
+speed = cd.speeds(pace, len(audio)) if pace else None
 ex.main_from_audio(audio, labels, a.n_filters, a.filterbank, a.feature_set, a.multiplier,
                    num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons,
                    small_world_k=a.small_world_k, seed=a.seed, readout=a.device_readout,
-                   class_names=cd.commands_from_args(a), time_segments=a.time_segments, corrupt=corrupt, reverb=reverb)
+                   class_names=cd.commands_from_args(a), time_segments=a.time_segments, corrupt=corrupt, reverb=reverb,
+                   speed=speed)
 """
 
 
@@ -107,14 +119,15 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     feature rows still on the GPU and prints the final report itself (no stage 3 process, no File 2 reload).
     `extra`: the forwarded constants (commands, commands_file, dataset_root, max_per_class, synthetic_per_class,
     packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc, time_segments, and the corruption flags
-    noise_dir, snr_db, time_shift_ms, level_db, augment_seed and the reverberation flags rir_dir, rir_prob, rir_max_ms:
-    applied to stage 1 and to the in-memory route)."""
+    noise_dir, snr_db, time_shift_ms, level_db, augment_seed, the reverberation flags rir_dir, rir_prob, rir_max_ms and the
+    speed flags speed_factors, speed_prob: applied to stage 1 and to the in-memory route)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
                               packed=False, num_neurons=None, num_output_neurons=None, small_world_k=None, seed=None,
                               readout=None, nproc=1, time_segments=1, noise_dir=None, snr_db=None, time_shift_ms=0.0,
-                              level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0)
+                              level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0,
+                              speed_factors=None, speed_prob=1.0)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -189,6 +202,9 @@ if __name__ == "__main__":
                          "(stage 1).")
     ap.add_argument("--rir-prob", type=float, default=1.0, help="Share of the clips that are reverberated (stage 1).")
     ap.add_argument("--rir-max-ms", type=float, default=500.0, help="Cut every response to this many ms (stage 1).")
+    ap.add_argument("--speed-factors", type=str, default=None,
+                    help="Comma-separated playback speeds drawn per clip on the GPU, e.g. 0.9,1.0,1.1 (stage 1).")
+    ap.add_argument("--speed-prob", type=float, default=1.0, help="Share of the clips whose speed is drawn (stage 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
@@ -197,4 +213,5 @@ if __name__ == "__main__":
                  num_output_neurons=a.num_output_neurons, small_world_k=a.small_world_k, seed=a.seed,
                  readout=a.readout, nproc=a.nproc, time_segments=a.time_segments, noise_dir=a.noise_dir, snr_db=a.snr_db,
                  time_shift_ms=a.time_shift_ms, level_db=a.level_db, augment_seed=a.augment_seed,
-                 rir_dir=a.rir_dir, rir_prob=a.rir_prob, rir_max_ms=a.rir_max_ms)
+                 rir_dir=a.rir_dir, rir_prob=a.rir_prob, rir_max_ms=a.rir_max_ms, speed_factors=a.speed_factors,
+                 speed_prob=a.speed_prob)
