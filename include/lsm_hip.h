@@ -100,7 +100,14 @@ int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samples, con
  *   thr_on  n_thr ON thresholds sorted DESCENDING, thr_off the matching `thr - gap` values, both
  *           already rounded to the spectrogram dtype by the caller (HOST memory, <= 8 entries)
  *   raster  (n_clips, n_filters*redundancy, time_bins*n_thr) uint8 or NULL
- *   norm_out (n_clips, n_filters, time_bins) or NULL: the normalised, resized spectrogram */
+ *   norm_out (n_clips, n_filters, time_bins) or NULL: the normalised, resized spectrogram
+ * The resize (taken when ncols != time_bins) is scipy.ndimage.zoom's, its boundary included: where the last bin's
+ * coordinate (double)(time_bins-1) * zf, zf = (double)(ncols-1) / (double)(time_bins-1), is greater than (double)(ncols-1),
+ * it lies outside the input and the last bin's normalised value is +0.0 for every row, NaN rows included, before the
+ * threshold comparisons (SPEC.md 1.2; e.g. 105 or 58 columns to 100 bins).  The one-launch entry points
+ * (lsm_gammatone_spikes_f64, lsm_mel_spikes_f32) do the same.
+ * LSM_ERR_ARG when the latch bit rows (64 rows x max(n_thr, 1) x ceil(time_bins / 32) words, twice, + 128 bytes) exceed
+ * 160 KB of LDS: 8 thresholds fit up to 1248 time bins. */
 int lsm_spec_to_spikes_f64(const double *db, int n_clips, int n_filters, int ncols, int time_bins,
                            int apply_floor, const double *thr_on, const double *thr_off, int n_thr,
                            int redundancy, uint8_t *raster, double *norm_out, void *stream);

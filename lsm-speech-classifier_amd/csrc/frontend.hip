@@ -428,6 +428,8 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
     const int Tb = a.time_bins, n_thr = a.n_thr;
     const int row_bits = Tb * n_thr;
     const double zf = (double)(ncols - 1) / (double)(Tb - 1);
+    // the bin whose coordinate lies outside the input and is +0.0 (spikes_body.h, SPEC.md 1.2): the last one or none (-1)
+    const int jz = (ncols != Tb && (double)(Tb - 1) * zf > (double)(ncols - 1)) ? Tb - 1 : -1;
     // (x - lo) / den for 2 x 100 values per channel: den is wave-uniform, so its correctly rounded reciprocal is
     // computed once and every quotient is q = x*r, q' = fma(fma(-q, den, x), r, q) -- Markstein's sequence, the
     // correctly rounded quotient (= the IEEE division spec_to_spikes_kernel performs) unless den's significand is
@@ -471,8 +473,10 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
         for (int q = 0; q < NCH; ++q) { act[q] = 0u; acc[q] = 0ull; }
         int fill = 0, wout = 0;                         // the same for every chain of the lane
         const uint32_t tmask_a = (1u << n_thr) - 1u;
-#pragma unroll 1
-        for (int jw = 0; jw < NG4; ++jw) {
+        // one group of G bins; LAST: the group that holds the last bin, the only one the zero rule (jz) can touch -- it is
+        // peeled off the loop, whose groups then carry no test for it
+        auto group = [&](const int jw, auto last_c) __attribute__((always_inline)) {
+            constexpr bool LAST = decltype(last_c)::value;
             double x0[G][NCH], x1[G][NCH], w0[G], w1[G];
             bool two[G];
 #pragma unroll
@@ -505,11 +509,12 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
                     if (ZOOM) {
                         const double n1 = norm1(x1[u][q]);
                         const double acc = n0 * w0[u];
-                        // the last column has no right neighbour; its weight w1 is 0 there and, on the fast path,
-                        // n1 is finite and acc >= +0, so acc + n1*0 == acc bit for bit: no branch needed
+                        // the last column has no right neighbour (two == false: cc >= ncols-1).  Either cc == ncols-1, then
+                        // its weight w1 is 0 and, on the fast path, n1 is finite and acc >= +0, so acc + n1*0 == acc bit
+                        // for bit: no branch needed; or cc > ncols-1, then the bin is jz and the value is replaced below
                         val = (FD || two[u]) ? acc + n1 * w1[u] : acc;
                     }
-                    val = flat ? 0.0 : val;
+                    val = (flat || (LAST && ZOOM && jw * G + u == jz)) ? 0.0 : val;     // (a scalar condition: one select)
                     uint32_t field = 0u;
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
@@ -542,7 +547,10 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const
                     }
                 }
             }
-        }
+        };
+#pragma unroll 1
+        for (int jw = 0; jw < NG4 - 1; ++jw) group(jw, std::false_type{});
+        group(NG4 - 1, std::true_type{});
         if (fill > 0) {
 #pragma unroll
             for (int q = 0; q < NCH; ++q) if (owner) stage[(q * CPW + cl) * RW + wout] = (uint32_t)acc[q];

@@ -92,6 +92,10 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
     const T den = (hi - lo) + (T)1e-8;
     const int row_bytes = Tb * nq;
     const double zf = (double)(nc - 1) / (double)(Tb - 1);
+    // Where the last bin's coordinate (Tb-1)*zf rounds to a double ABOVE nc-1 it lies outside the input, and SciPy's constant
+    // boundary mode answers cval = +0.0 for that bin, whatever the row holds (SPEC.md 1.2).  The overshoot is an ulp, so no
+    // earlier bin has it: one uniform test per launch, jz = the bin that is zero (-1: none).
+    const int jz = (nc != Tb && (double)(Tb - 1) * zf > (double)(nc - 1)) ? Tb - 1 : -1;
     const int C = F * a.redundancy;
     uint8_t *dst = a.raster ? a.raster + (size_t)b * C * row_bytes : nullptr;
 
@@ -145,6 +149,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
                     }
                     val = (T)acc;
                 }
+                val = j == jz ? (T)0 : val;
                 if (a.norm_out && valid) a.norm_out[((size_t)b * F + r0 + rl) * Tb + j] = val;
 #pragma unroll
                 for (int q = 0; q < MAX_THR; ++q) {

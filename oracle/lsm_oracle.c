@@ -132,7 +132,7 @@ ORC_API int orc_normalise_resize_f64(const double *db, int n_filters, int ncols,
         return 0;
     }
     /* scipy.ndimage.zoom(order=1) along time; output length round(ncols*(time_bins/ncols)) is
-     * time_bins for every ncols used here, then [:, :time_bins]. */
+     * time_bins (tests/test_encoder_host.py sweeps it), then [:, :time_bins]. */
     const double zf = (double)(ncols - 1) / (double)(time_bins - 1);
     for (int j = 0; j < time_bins; ++j) {
         const double cc = (double)j * zf;
@@ -148,6 +148,9 @@ ORC_API int orc_normalise_resize_f64(const double *db, int n_filters, int ncols,
             out[(size_t)r * time_bins + j] = v;
         }
     }
+    /* a last coordinate that rounds above ncols-1 lies outside the input: SciPy's constant mode answers cval = +0.0 */
+    if ((double)(time_bins - 1) * zf > (double)(ncols - 1))
+        for (int r = 0; r < n_filters; ++r) out[(size_t)r * time_bins + time_bins - 1] = 0.0;
     return 0;
 }
 
@@ -186,6 +189,9 @@ ORC_API int orc_normalise_resize_f32(const float *db, int n_filters, int ncols, 
             out[(size_t)r * time_bins + j] = (float)v;
         }
     }
+    /* the zero rule of the float64 function */
+    if ((double)(time_bins - 1) * zf > (double)(ncols - 1))
+        for (int r = 0; r < n_filters; ++r) out[(size_t)r * time_bins + time_bins - 1] = 0.0f;
     return 0;
 }
 
