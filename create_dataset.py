@@ -264,6 +264,16 @@ def reverberation(reverb, n_listed: int):
     return bank, lengths, _frontend().reverb_plan(n_listed, bank.shape[0], prob=reverb["prob"], seed=reverb["seed"])
 
 
+# ---- masks inside the spike encoder (SPEC.md 1.13): --freq-masks, --freq-mask-width, --time-masks, --time-mask-width,
+# ---- --mask-prob; the seed is --augment-seed
+def masks(mask, n_listed: int, fe):
+    """``mask`` (`mask_from_args`) -> the frontend.MaskPlan of all n_listed clips in listing order, for front end ``fe``."""
+    try:
+        return _frontend().mask_plan(n_listed, fe.n_filters, fe.time_bins, **mask)
+    except ValueError as e:
+        raise SystemExit(f"mask flags: {e}")
+
+
 # ---- speed perturbation on the device (SPEC.md 1.12): --speed-factors, --speed-prob; the seed is --augment-seed ---------------
 def speeds(speed, n_listed: int):
     """``speed`` (`speed_from_args`) -> ``(factors, frontend.SpeedPlan of all n_listed clips in listing order)``."""
@@ -302,7 +312,7 @@ def collect_audio(commands=None, dataset_root=None, max_per_class: int = MAX_SAM
 def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
                    output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host", augment=None,
-                   reverb=None, speed=None):
+                   reverb=None, speed=None, mask=None):
     """Build File 1.  The first two arguments are the reference's; the keyword arguments expose
     what the reference hard-codes (class list, corpus folder, per-class cap) plus a synthetic
     corpus for machines without Speech Commands.  ``packed=True`` writes the bit-packed schema of
@@ -313,7 +323,9 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     the whole listing in listing order -- a shard takes its slice, so any number of ranks writes the same bytes.
     ``reverb`` (`reverb_from_args`): every clip is first convolved on the GPU with a room impulse response (SPEC.md 1.11),
     by a plan drawn for the whole listing likewise.  ``speed`` (`speed_from_args`): ahead of both, every clip is played at a
-    speed drawn from a list of factors on the GPU (SPEC.md 1.12) and padded or trimmed to the clip length.
+    speed drawn from a list of factors on the GPU (SPEC.md 1.12) and padded or trimmed to the clip length.  ``mask``
+    (`mask_from_args`): frequency bands and time spans of every clip's normalised spectrogram are zeroed inside the spike
+    encoder (SPEC.md 1.13), by a plan drawn for the whole listing likewise.
 
     Under a launcher (torchrun: RANK / WORLD_SIZE) the clip loop of create_dataset.py:143 shards: rank r reads
     and encodes the r-th contiguous block of the file listing on its own GPU, the raster blocks are all-gathered
@@ -327,7 +339,7 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
     if rank == 0:
         print(f"Creating dataset with filterbank: {filterbank}, filters: {n_filters}"
               + (f" ({world} ranks)" if world > 1 else ""))
-    planned = bool(augment) or bool(reverb) or bool(speed)
+    planned = bool(augment) or bool(reverb) or bool(speed) or bool(mask)
     kept = [] if planned else None          # positions in the shard's part of the listing of the clips that were read
     if synthetic_per_class > 0:
         clips, labels = _synthetic_audio(commands, synthetic_per_class)
@@ -369,6 +381,9 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
         factors, paces = speeds(speed, n_listed)
         paces = paces.take(lo + np.asarray(kept, dtype=np.int64))
         perturber = _frontend().SpeedPerturber(factors, device=dev)
+    veils = None
+    if mask:
+        veils = masks(mask, n_listed, fe).take(lo + np.asarray(kept, dtype=np.int64))
     parts, n_spikes = [], 0
     for a in range(0, len(clips), ENCODE_BATCH):
         batch = clips[a:a + ENCODE_BATCH]
@@ -380,7 +395,7 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
             batch = reverberator.reverb(batch, rooms.part(a, a + ENCODE_BATCH).rows)
         if mixer is not None:
             batch = mixer.mix(batch, *plan.part(a, a + ENCODE_BATCH))
-        raster = fe.encode(batch)
+        raster = fe.encode(batch) if veils is None else fe.encode(batch, mask=veils.part(a, a + ENCODE_BATCH))
         n_spikes += int(raster.count_nonzero())
         part = _frontend().pack_raster(raster) if packed else raster
         parts.append(part if world > 1 else part.cpu().numpy())
@@ -487,6 +502,30 @@ def reverb_from_args(a):
     return dict(rir_dir=a.rir_dir, prob=float(a.rir_prob), max_ms=float(a.rir_max_ms), seed=int(a.augment_seed))
 
 
+def add_mask_flags(ap):
+    """The mask flags (shared with main.py, which forwards them).  Without a mask count and width nothing changes.  The seed
+    of the per-clip draws is --augment-seed (`add_augment_flags`)."""
+    ap.add_argument("--freq-masks", type=int, default=0, help="Frequency bands zeroed per clip inside the encoder (default 0).")
+    ap.add_argument("--freq-mask-width", type=int, default=0, help="Largest width of a frequency band, in filters.")
+    ap.add_argument("--time-masks", type=int, default=0, help="Time spans zeroed per clip inside the encoder (default 0).")
+    ap.add_argument("--time-mask-width", type=int, default=0, help="Largest width of a time span, in time bins.")
+    ap.add_argument("--mask-prob", type=float, default=1.0, help="Share of the clips that are masked (default 1).")
+
+
+def mask_from_args(a):
+    """None unless a kind of mask has both a count and a width, else what create_dataset(mask=...) takes."""
+    for flag, v in (("--freq-masks", a.freq_masks), ("--freq-mask-width", a.freq_mask_width), ("--time-masks", a.time_masks),
+                    ("--time-mask-width", a.time_mask_width)):
+        if v < 0:
+            raise SystemExit(f"{flag} must be >= 0")
+    if not 0.0 <= a.mask_prob <= 1.0:
+        raise SystemExit("--mask-prob must lie in [0, 1]")
+    if not (a.freq_masks and a.freq_mask_width) and not (a.time_masks and a.time_mask_width):
+        return None
+    return dict(freq_masks=int(a.freq_masks), freq_width=int(a.freq_mask_width), time_masks=int(a.time_masks),
+                time_width=int(a.time_mask_width), prob=float(a.mask_prob), seed=int(a.augment_seed))
+
+
 def add_speed_flags(ap):
     """The speed flags (shared with main.py, which forwards them).  Without --speed-factors nothing changes.  The seed of the
     per-clip draws is --augment-seed (`add_augment_flags`)."""
@@ -534,8 +573,10 @@ if __name__ == "__main__":
     add_augment_flags(ap)
     add_reverb_flags(ap)
     add_speed_flags(ap)
+    add_mask_flags(ap)
     a = ap.parse_args()
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,
                    synthetic_per_class=a.synthetic_per_class, packed=a.packed, resample=a.resample,
-                   augment=augment_from_args(a), reverb=reverb_from_args(a), speed=speed_from_args(a))
+                   augment=augment_from_args(a), reverb=reverb_from_args(a), speed=speed_from_args(a),
+                   mask=mask_from_args(a))

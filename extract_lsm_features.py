@@ -212,7 +212,7 @@ def run_network_diagnostics(lsm, X_sample_batch):
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
                     num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
-                    time_segments=1, corrupt=None, reverb=None, speed=None):
+                    time_segments=1, corrupt=None, reverb=None, speed=None, mask=None):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -242,7 +242,10 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     its room impulse response on the GPU (SPEC.md 1.11), ahead of `corrupt`.
 
     `speed` = ``(factors, frontend.SpeedPlan of the n clips)``: every clip is first played at its speed among ``factors`` on
-    the GPU (SPEC.md 1.12), ahead of `reverb`."""
+    the GPU (SPEC.md 1.12), ahead of `reverb`.
+
+    `mask` = what `create_dataset.mask_from_args` returns: frequency bands and time spans of every clip's normalised spectrogram
+    are zeroed inside the spike encoder (SPEC.md 1.13), by a plan drawn for all n clips in listing order."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
@@ -273,6 +276,9 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     sp = paces = None
     if speed is not None:
         sp, paces = frontend.SpeedPerturber(speed[0], device=dev), speed[1]
+    veils = None
+    if mask:
+        veils = frontend.mask_plan(len(audio), fe.n_filters, fe.time_bins, **mask)
     head_audio = audio[idx_train[:500]]
     if sp is not None:
         head_audio = sp.perturb(head_audio, paces.take(idx_train[:500]).choice)
@@ -280,7 +286,7 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
         head_audio = rv.reverb(head_audio, rooms.take(idx_train[:500]).rows)
     if mixer is not None:
         head_audio = mixer.mix(head_audio, *plan.take(idx_train[:500]))
-    head = fe.encode(head_audio).cpu().numpy()                      # what w_critico and the diagnostics look at
+    head = fe.encode(head_audio, **({} if veils is None else {"mask": veils.take(idx_train[:500])})).cpu().numpy()                      # what w_critico and the diagnostics look at
     params = _simulation_params(head[0], leak_variance_divisor, num_neurons, num_output_neurons, small_world_k, seed)
     with _rank0_only(rank):
         optimal_weight = calculate_theoretical_w_critico(params, head) * multiplier
@@ -304,7 +310,8 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
                                              time_segments=time_segments,
                                              corrupt=(mixer, plan.take(idx[lo:hi])) if mixer is not None else None,
                                              reverb=(rv, rooms.take(idx[lo:hi])) if rv is not None else None,
-                                             speed=(sp, paces.take(idx[lo:hi])) if sp is not None else None)
+                                             speed=(sp, paces.take(idx[lo:hi])) if sp is not None else None,
+                                             **({} if veils is None else {"mask": veils.take(idx[lo:hi])}))
         return lsm_dist.gather_rows(local, len(idx))
 
     X_train_dev = split_features(idx_train)

@@ -147,6 +147,21 @@ SPEED_SIGS = {
 }
 SPEED_SYMBOLS = tuple(SPEED_SIGS)
 
+# include/lsm_hip_mask.h (SPEC.md §1.13): the masked spike encoders -- each its twin's list with freq_mask, time_mask before
+# the stream
+def _masked(twin: str):
+    res, args = _SIGS[twin]
+    return res, args[:-1] + [c_void, c_void] + args[-1:]
+
+
+MASK_SIGS = {
+    "lsm_spec_to_spikes_masked_f64": _masked("lsm_spec_to_spikes_f64"),
+    "lsm_spec_to_spikes_masked_f32": _masked("lsm_spec_to_spikes_f32"),
+    "lsm_gammatone_spikes_masked_f64": _masked("lsm_gammatone_spikes_f64"),
+    "lsm_mel_spikes_masked_f32": _masked("lsm_mel_spikes_f32"),
+}
+MASK_SYMBOLS = tuple(MASK_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -196,7 +211,8 @@ def load():
             f"{_build.source_id()}): rebuild the extension (`python -c \"import __graft_entry__ as g; g.build()\"`).")
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
-                              + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())):
+                              + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
+                              + list(MASK_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

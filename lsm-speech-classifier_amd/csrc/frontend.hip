@@ -10,6 +10,7 @@
 #include "lsm_common.h"
 #include "gammatone_body.h"
 #include "spikes_body.h"
+#include "gammatone_spikes_body.h"
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -30,8 +31,7 @@ namespace {
 // The coefficient load, the section step, the quotient by a reciprocal and the exactness notes (B2ZERO, FASTDIV) are in
 // gammatone_body.h.
 // ---------------------------------------------------------------------------------------------
-constexpr int NWIN_MAX = 4;
-constexpr int GT_MAX_WPB = 8;           // waves per workgroup, at most
+// (NWIN_MAX and GT_MAX_WPB, the waves per workgroup at most: gammatone_spikes_body.h)
 
 // NW = ceil(nwin / hop) windows are live at any sample.  In every hop block exactly one window
 // completes: the one of age NW-1, after sample number pos = nwin - (NW-1)*hop of the block.  So a
@@ -145,457 +145,7 @@ __global__ __launch_bounds__(SPK_THREADS) void spec_to_spikes_kernel(const Spike
     lsm_fe::spec_to_spikes_body<T>(a, (int)blockIdx.x, smem);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Fused front end: filterbank -> dB -> floor/min-max normalise -> linear resize -> hysteresis encoder ->
-// uint8 raster in ONE launch (create_dataset.py:49-104 per clip).  The filter loop is the one of
-// gammatone_kernel; what differs:
-//   * a wave carries NCH channel groups of its clip (NCH = 2: 128 channels, two independent float64
-//     dependency chains per lane that share the scalar sample loads and the float32 -> float64
-//     conversion), so at 128 filters ONE WAVE IS ONE CLIP and the clip's max/min need no other wave;
-//   * the clip's dB columns go to a private scratch, column-major per wave (64 consecutive doubles per
-//     store); the lane that wrote a value is the only one that reads it back, after the last window, when
-//     the clip's maximum is known.  A row's 98 float64 values do not fit the registers next to the filter
-//     state of two chains and 100 KB per clip do not fit the LDS four times per CU;
-//   * max/min: running per lane, xor-shuffles per wave, one LDS exchange when a clip spans several waves
-//     (the waves of a clip always share a workgroup);
-//   * normalise / SciPy-exact resize / 4-threshold latch: one lane per channel, arithmetic and comparison
-//     order of spec_to_spikes_kernel<double>; the raster rows of a wave are staged bit-packed in LDS and
-//     leave as coalesced 4-byte stores.
-// Waves beyond the batch (last workgroup) skip the filter loop but keep the barriers.
-//
-// PAIR (lane-pair layout, NCH = 1): a wave carries 32 channels of its clip, channel j in lanes j (head) and j + 32
-// (tail), so at 128 filters a clip is 4 waves and a 256-clip launch puts a wave on every SIMD.  In the iteration of
-// sample n the head runs sections 1-2 on sample n + 1 and the tail sections 3-4 on sample n, fed with the head's
-// section-2 output of sample n, which v_permlane32_swap moves from lane j to lane j + 32 at the top of the iteration.
-// Both halves run the same two-section code with their own section coefficients and state.  The division, the
-// square and the window sums run on both halves (one instruction stream) but only the tail's feed the dB columns,
-// the max/min and the epilogue.  Every float64 operation of a channel and its order are those of the other layouts:
-// the skew only changes when section 3 sees a value, and the hand-off moves bits.
-// ---------------------------------------------------------------------------------------------
-struct FusedArgs {
-    const float *audio;
-    const double *coefs;
-    double *ws;                 // (n_clips, ncols, groups*NCH*64) float64 scratch (32 channels per group in the lane pair)
-    uint8_t *raster;            // (n_clips, n_filters*redundancy, time_bins*n_thr)
-    int n_clips, n_samples, n_filters, nwin, hop, ncols;
-    int time_bins, n_thr, redundancy, groups;
-    int unused_;                // (keeps the argument layout, and with it the filter loop's code, of the measured build)
-    int prio;                   // wave priority of the filter loop: 0 (see the kernel)
-    double on[MAX_THR], off[MAX_THR];
-};
-
-// Head lanes (0-31) keep `lo`, tail lanes (32-63) receive v of lane - 32: v_permlane32_swap exchanges lanes 32-63 of
-// its first operand with lanes 0-31 of its second; one swap per 32-bit half.
-__device__ __forceinline__ double pair_up(double lo, double v)
-{
-    const unsigned long long a = (unsigned long long)__double_as_longlong(lo);
-    const unsigned long long c = (unsigned long long)__double_as_longlong(v);
-    const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)c, false, false);
-    const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)(a >> 32), (unsigned)(c >> 32), false, false);
-    return __longlong_as_double((long long)(((unsigned long long)rh[0] << 32) | rl[0]));
-}
-
-__device__ __forceinline__ double uniform_f64(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// SHB0: every channel has the same first-section gain b0 = A0/B0 (the host verified it, coef_flags bit 2: this filter
-// design has A0 = 1/fs and B0 = 1 everywhere), so the product b0*x of a sample is formed once per lane and feeds both
-// chains: 70 instead of 71 instructions per sample and lane.
-template <int NW, bool FAST, int NCH, bool SHB0 = false, bool PAIR = false>
-__global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_spikes_kernel(const FusedArgs a)
-{
-    static_assert(!PAIR || NCH == 1, "the lane pair carries one chain per lane pair");
-    constexpr int CPW = PAIR ? 32 : 64;                                   // channels of a chain group (of a wave)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *xch = reinterpret_cast<double *>(smem);                       // 2 * GT_MAX_WPB doubles
-    uint32_t *stage_all = reinterpret_cast<uint32_t *>(smem + 2 * GT_MAX_WPB * sizeof(double));
-    const int lane = (int)(threadIdx.x & 63);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wpb = (int)(blockDim.x >> 6);
-    const int groups = a.groups;                                          // waves per clip
-    const int wid = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb)) + wave;
-    const int b_raw = wid / groups;
-    const bool valid = b_raw < a.n_clips;
-    const int b = valid ? b_raw : a.n_clips - 1;
-    const int g = wid - b_raw * groups;
-    const int F = a.n_filters, nwin = a.nwin, hop = a.hop, ncols = a.ncols, n_samples = a.n_samples;
-    const int NG = groups * NCH;                                          // chain groups per clip (padded)
-    const int cl = PAIR ? (lane & 31) : lane;                             // this lane's channel within its group
-    const bool owner = !PAIR || lane >= 32;                               // the lane whose output is the channel's
-
-    bool live[NCH];
-    double b0[NCH], b11[NCH], b12[NCH], b13[NCH], b14[NCH], b2[NCH], a1[NCH], a2[NCH], gain[NCH], rgain[NCH];
-#pragma unroll
-    for (int q = 0; q < NCH; ++q) {
-        const int chl = (g * NCH + q) * CPW + cl;
-        live[q] = chl < F;
-        const lsm_gt::Sections s = lsm_gt::load_sections(a.coefs, live[q] ? chl : F - 1);
-        b0[q] = s.b0; b2[q] = s.b2; b11[q] = s.b1[0]; b12[q] = s.b1[1]; b13[q] = s.b1[2]; b14[q] = s.b1[3];
-        a1[q] = s.a1; a2[q] = s.a2; gain[q] = s.gain; rgain[q] = s.rgain;
-    }
-    const float *__restrict__ x = a.audio + (size_t)b * n_samples;        // wave-uniform
-
-    double z01[NCH], z11[NCH], z02[NCH], z12[NCH], z03[NCH], z13[NCH], z04[NCH], z14[NCH];
-    double win[NCH][NW];
-    double mx[NCH], mn[NCH];
-    bool nan_seen = false;                              // a NaN among my dB values (the comparisons below skip it)
-#pragma unroll
-    for (int q = 0; q < NCH; ++q) {
-        z01[q] = z11[q] = z02[q] = z12[q] = z03[q] = z13[q] = z04[q] = z14[q] = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) win[q][w] = 0.0;
-        mx[q] = -INFINITY; mn[q] = INFINITY;
-    }
-
-    // PAIR: this half's section coefficients (head: sections 1-2, tail: 3-4) and its last section-2 output.  With SHB0
-    // the one b0 of the table is channel 0's, read once per wave (scalar registers).
-    const double bp1 = owner ? b13[0] : b11[0], bp2 = owner ? b14[0] : b12[0];
-    const double b0p = SHB0 ? uniform_f64(a.coefs[0] / a.coefs[6]) : b0[0];
-    double u2 = 0.0;
-    auto pfilt = [&](double x0) __attribute__((always_inline)) -> double {
-        const double u = pair_up(x0, u2);               // head: the next sample; tail: the head's y2 of its sample
-        const double y1 = lsm_gt::section<FAST>(z01[0], b0p, u, z11[0], bp1, a1[0], a2[0], b2[0]);
-        const double y2 = lsm_gt::section<FAST>(z02[0], b0p, y1, z12[0], bp2, a1[0], a2[0], b2[0]);
-        u2 = y2;
-        double o;
-        lsm_gt::quot<FAST>(o, y2, gain[0], rgain[0]);
-        return o * o;
-    };
-    // lsm_gt::section four times, written out: called through section() this cascade compiles to other code, whatever the
-    // form of the call (profiles/frontend_shared_filter.txt); the split kernel's cascade and pfilt do call it
-    auto filt = [&](int q, double x0, double bx) __attribute__((always_inline)) -> double {
-        const double y1 = z01[q] + (SHB0 ? bx : b0[q] * x0);
-        z01[q] = (z11[q] + x0 * b11[q]) - y1 * a1[q];
-        z11[q] = FAST ? -(y1 * a2[q]) : x0 * b2[q] - y1 * a2[q];
-        const double y2 = z02[q] + b0[q] * y1;
-        z02[q] = (z12[q] + y1 * b12[q]) - y2 * a1[q];
-        z12[q] = FAST ? -(y2 * a2[q]) : y1 * b2[q] - y2 * a2[q];
-        const double y3 = z03[q] + b0[q] * y2;
-        z03[q] = (z13[q] + y2 * b13[q]) - y3 * a1[q];
-        z13[q] = FAST ? -(y3 * a2[q]) : y2 * b2[q] - y3 * a2[q];
-        const double y4 = z04[q] + b0[q] * y3;
-        z04[q] = (z14[q] + y3 * b14[q]) - y4 * a1[q];
-        z14[q] = FAST ? -(y4 * a2[q]) : y3 * b2[q] - y4 * a2[q];
-        double o;
-        lsm_gt::quot<FAST>(o, y4, gain[q], rgain[q]);
-        return o * o;
-    };
-#define LSM_RUNF(n_to, NACT)                                                        \
-    {                                                                               \
-        if (n + 8 <= (n_to)) {                                                      \
-            float xs[8], nx[8];                                                     \
-            _Pragma("unroll") for (int u = 0; u < 8; ++u) xs[u] = x[n + u];         \
-            for (; n + 8 <= (n_to); n += 8) {                                       \
-                const float *pn = x + min(n + 8, n_samples - 8);                    \
-                _Pragma("unroll") for (int u = 0; u < 8; ++u) nx[u] = pn[u];        \
-                _Pragma("unroll") for (int u = 0; u < 8; ++u) {                     \
-                    const double x0 = (double)xs[u];                                \
-                    const double bx = b0[0] * x0;                                   \
-                    _Pragma("unroll") for (int q = 0; q < NCH; ++q) {               \
-                        const double e = filt(q, x0, bx);                           \
-                        _Pragma("unroll") for (int w = 0; w < (NACT); ++w) win[q][w] += e; \
-                    }                                                               \
-                }                                                                   \
-                _Pragma("unroll") for (int u = 0; u < 8; ++u) xs[u] = nx[u];        \
-            }                                                                       \
-        }                                                                           \
-        for (; n < (n_to); ++n) {                                                   \
-            const double x0 = (double)x[n];                                         \
-            const double bx = b0[0] * x0;                                           \
-            _Pragma("unroll") for (int q = 0; q < NCH; ++q) {                       \
-                const double e = filt(q, x0, bx);                                   \
-                _Pragma("unroll") for (int w = 0; w < (NACT); ++w) win[q][w] += e;  \
-            }                                                                       \
-        }                                                                           \
-    }
-
-    // PAIR: the tail processes sample n while the head takes x[n + 1] (clamped inside the clip: the head's output of
-    // the sample past the last one is never used); full chunks stop where x[n + 8] would leave the clip
-#define LSM_RUNP(n_to, NACT)                                                        \
-    {                                                                               \
-        const int n_blk = min((n_to), n_samples - 1);                               \
-        if (n + 8 <= n_blk) {                                                       \
-            float xs[8], nx[8];                                                     \
-            _Pragma("unroll") for (int u = 0; u < 8; ++u) xs[u] = x[n + 1 + u];     \
-            for (; n + 8 <= n_blk; n += 8) {                                        \
-                const float *pn = x + 1 + min(n + 8, n_samples - 9);                \
-                _Pragma("unroll") for (int u = 0; u < 8; ++u) nx[u] = pn[u];        \
-                _Pragma("unroll") for (int u = 0; u < 8; ++u) {                     \
-                    const double e = pfilt((double)xs[u]);                          \
-                    _Pragma("unroll") for (int w = 0; w < (NACT); ++w) win[0][w] += e; \
-                }                                                                   \
-                _Pragma("unroll") for (int u = 0; u < 8; ++u) xs[u] = nx[u];        \
-            }                                                                       \
-        }                                                                           \
-        for (; n < (n_to); ++n) {                                                   \
-            const double e = pfilt((double)x[min(n + 1, n_samples - 1)]);           \
-            _Pragma("unroll") for (int w = 0; w < (NACT); ++w) win[0][w] += e;      \
-        }                                                                           \
-    }
-
-    // scratch of this wave: column c, chain q at wsw[(c * NG + q) * CPW]
-    double *wsw = a.ws + ((size_t)b * ncols * NG + (size_t)g * NCH) * CPW + cl;
-    // The filter loop is the throughput-critical stream of the pipeline: a wave alone on its SIMD issues a float64
-    // operation every 5.0 cycles, which leaves the reservoir waves sharing the SIMD one issue slot in five -- about
-    // what they need.  At the default priority the reservoir kernel's raised-priority phases (lif_dense.h) take
-    // slots from it instead, so it runs at priority 0 (priorities 0-3: profiles/r03_priorities_and_stream_counts.txt).
-    // The untaken branches below stay: without them the compiler allocates the filter loop differently (fewer vector
-    // registers, e.g. 238 -> 168 in one layout) and the pipeline ran 4 % slower at cfg4, 3 % at cfg2.
-    if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
-    if (valid) {
-        const int pos = nwin - (NW - 1) * hop;
-        const int n_end = (ncols - 1) * hop + nwin;
-        const double dn = (double)nwin;
-        if (PAIR) {
-            // the head's sample 0; the tail ran on a zero input, and its state restarts at +0 (all it held were
-            // signed zeros)
-            (void)pfilt((double)x[0]);
-            if (owner) z01[0] = z11[0] = z02[0] = z12[0] = 0.0;
-        }
-        int n = 0;
-        for (int h = 0; n < n_end; ++h) {
-            const int base = h * hop;
-            const int mid = min(base + pos, n_end);
-            if (PAIR) LSM_RUNP(mid, NW) else LSM_RUNF(mid, NW)
-            const int c = h - (NW - 1);
-            if (n == base + pos && c >= 0 && c < ncols) {
-#pragma unroll
-                for (int q = 0; q < NCH; ++q) {
-                    const double y = sqrt(win[q][NW - 1] / dn);
-                    const double v = 20 * log10(y + 1e-9);
-                    if (owner) wsw[((size_t)c * NG + q) * CPW] = v;
-                    if (live[q] && owner) {
-                        mx[q] = v > mx[q] ? v : mx[q];
-                        mn[q] = v < mn[q] ? v : mn[q];
-                        nan_seen |= v != v;
-                    }
-                }
-            }
-            const int stop = min(base + hop, n_end);
-            if (PAIR) LSM_RUNP(stop, NW - 1) else LSM_RUNF(stop, NW - 1)
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) {
-#pragma unroll
-                for (int w = NW - 1; w > 0; --w) win[q][w] = win[q][w - 1];
-                win[q][0] = 0.0;
-            }
-        }
-    }
-#undef LSM_RUNF
-#undef LSM_RUNP
-
-    __builtin_amdgcn_s_setprio(0);
-    // ---- the clip's max / min -----------------------------------------------------------------
-    double hi = mx[0], lo = mn[0];
-#pragma unroll
-    for (int q = 1; q < NCH; ++q) {
-        hi = mx[q] > hi ? mx[q] : hi;
-        lo = mn[q] < lo ? mn[q] : lo;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double oh = __shfl_xor(hi, off), ol = __shfl_xor(lo, off);
-        hi = oh > hi ? oh : hi;
-        lo = ol < lo ? ol : lo;
-    }
-    // spec_db.max() / .min() / np.maximum (create_dataset.py:59-63) propagate NaN: one NaN among the clip's dB values makes
-    // max, floor and min NaN -- every normalised value NaN, the raster all zeros (tests/golden/postfilter_nonfinite.npz)
-    if (__builtin_amdgcn_ballot_w64(nan_seen) != 0ull) hi = lo = (double)NAN;
-    if (groups > 1) {                                   // uniform over the launch
-        if (lane == 0) { xch[2 * wave] = hi; xch[2 * wave + 1] = lo; }
-        __syncthreads();
-        const int w0 = wave - g;                        // first wave of this clip in the workgroup
-        hi = xch[2 * w0]; lo = xch[2 * w0 + 1];
-        bool nan_any = hi != hi;
-        for (int i = 1; i < groups; ++i) {
-            const double oh = xch[2 * (w0 + i)], ol = xch[2 * (w0 + i) + 1];
-            hi = oh > hi ? oh : hi;
-            lo = ol < lo ? ol : lo;
-            nan_any = nan_any || oh != oh;
-        }
-        if (nan_any) hi = lo = (double)NAN;
-    }
-    // create_dataset.py:60 floors at max-80 before the min is taken: min' = max(min, max-80)
-    const double fl = hi - 80.0;
-    lo = lo > fl ? lo : fl;                             // (NaN: fl)
-    const bool flat = (hi - lo) < 1e-8;
-    const double den = (hi - lo) + 1e-8;
-    const int Tb = a.time_bins, n_thr = a.n_thr;
-    const int row_bits = Tb * n_thr;
-    const double zf = (double)(ncols - 1) / (double)(Tb - 1);
-    // the bin whose coordinate lies outside the input and is +0.0 (spikes_body.h, SPEC.md 1.2): the last one or none (-1)
-    const int jz = (ncols != Tb && (double)(Tb - 1) * zf > (double)(ncols - 1)) ? Tb - 1 : -1;
-    // (x - lo) / den for 2 x 100 values per channel: den is wave-uniform, so its correctly rounded reciprocal is
-    // computed once and every quotient is q = x*r, q' = fma(fma(-q, den, x), r, q) -- Markstein's sequence, the
-    // correctly rounded quotient (= the IEEE division spec_to_spikes_kernel performs) unless den's significand is
-    // all ones or den leaves the normal range (broken audio: inf/NaN); those clips take the true division.  The
-    // numerators need no check of their own: every x is clamped into [lo, hi] (NaN and -inf become the floor), so
-    // 0 <= x - lo <= hi - lo < den, a difference of two dB values: zero or far above the denormal range.
-    const double rden = 1.0 / den;
-    const unsigned long long den_bits = (unsigned long long)__double_as_longlong(den);
-    const bool fastdiv = den > 1e-200 && den < 1e200 &&
-                         (den_bits & 0x000FFFFFFFFFFFFFull) != 0x000FFFFFFFFFFFFFull;
-    // Per group of JPW bins (no dependency between the bins of a group, the loads of the whole group in flight together):
-    // per bin j and threshold t the two comparisons the latch needs, S = val > on[t] in bit t and R = val < off[t] in bit
-    // FBH + t of the bin's field; then -- round 4: in the same iteration, from registers -- the set/reset latches of all
-    // thresholds at once, A = (S & ~A) | (A & ~R), and the raster bits appended to a 64-bit accumulator that is stored to
-    // the lane's LDS row a word at a time.  The first version staged the FIELDS of all bins in LDS (pass A) and ran the
-    // latch as a second pass over them (pass B): 100 bytes of stage per channel instead of 50, i.e. 51 KB instead of
-    // 27 KB per 4-wave workgroup -- which mattered once a ring-kernel clip pair (2 x 64 KB) had to fit beside it on a CU.
-    // The only state carried from group to group is the latch (4-8 bits per chain) and the bit accumulator.
-    const int FBH = n_thr <= 4 ? 4 : 8;                 // bits per half field
-    const int JPW = 16 / FBH;                           // bins per 32-bit word (4 or 2)
-    const int NG4 = (Tb + JPW - 1) / JPW;               // groups of JPW bins
-    const int RW = (row_bits + 31) >> 5;                // words per staged raster row
-    uint32_t *stage = stage_all + (size_t)wave * (NCH * CPW) * RW;
-    const size_t cs = (size_t)NG * CPW;                 // doubles between two columns of the scratch
-    // straight-line variants (fast division or not, <= 4 thresholds or not, resize or not): one uniform choice
-    // per wave instead of uniform branches inside the loop, which would keep the compiler from batching the loads
-    auto pass_a = [&](auto fast_c, auto nt_c, auto zoom_c) __attribute__((always_inline)) {
-        constexpr bool FD = decltype(fast_c)::value;
-        constexpr int NT = decltype(nt_c)::value;       // thresholds compared (tables are padded with +inf / -inf)
-        constexpr bool ZOOM = decltype(zoom_c)::value;
-        constexpr int H = NT <= 4 ? 4 : 8, G = 16 / H;  // = FBH, JPW
-        auto norm1 = [&](double v) __attribute__((always_inline)) -> double {
-            v = v > fl ? v : fl;
-            double q;
-            lsm_gt::quot<FD>(q, v - lo, den, rden);
-            return q;
-        };
-        uint32_t act[NCH];
-        unsigned long long acc[NCH];
-#pragma unroll
-        for (int q = 0; q < NCH; ++q) { act[q] = 0u; acc[q] = 0ull; }
-        int fill = 0, wout = 0;                         // the same for every chain of the lane
-        const uint32_t tmask_a = (1u << n_thr) - 1u;
-        // one group of G bins; LAST: the group that holds the last bin, the only one the zero rule (jz) can touch -- it is
-        // peeled off the loop, whose groups then carry no test for it
-        auto group = [&](const int jw, auto last_c) __attribute__((always_inline)) {
-            constexpr bool LAST = decltype(last_c)::value;
-            double x0[G][NCH], x1[G][NCH], w0[G], w1[G];
-            bool two[G];
-#pragma unroll
-            for (int u = 0; u < G; ++u) {
-                const int j = min(jw * G + u, Tb - 1);
-                // scipy.ndimage.zoom(order=1): double coordinate and weights, w1 = 1 - w0
-                const double cc = (double)j * zf;
-                const double fc = floor(cc);
-                const int f = ZOOM ? (int)fc : j;
-                w0[u] = 1.0 - (cc - fc);
-                w1[u] = 1.0 - w0[u];
-                two[u] = f + 1 <= ncols - 1;
-                const int f1 = two[u] ? f + 1 : f;
-#pragma unroll
-                for (int q = 0; q < NCH; ++q) {
-                    const double *col = wsw + (size_t)q * CPW;
-                    x0[u][q] = col[(size_t)f * cs];
-                    if (ZOOM) x1[u][q] = col[(size_t)f1 * cs];
-                }
-            }
-            uint32_t fw[NCH];
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) fw[q] = 0u;
-#pragma unroll
-            for (int u = 0; u < G; ++u) {
-#pragma unroll
-                for (int q = 0; q < NCH; ++q) {
-                    const double n0 = norm1(x0[u][q]);
-                    double val = n0;
-                    if (ZOOM) {
-                        const double n1 = norm1(x1[u][q]);
-                        const double acc = n0 * w0[u];
-                        // the last column has no right neighbour (two == false: cc >= ncols-1).  Either cc == ncols-1, then
-                        // its weight w1 is 0 and, on the fast path, n1 is finite and acc >= +0, so acc + n1*0 == acc bit
-                        // for bit: no branch needed; or cc > ncols-1, then the bin is jz and the value is replaced below
-                        val = (FD || two[u]) ? acc + n1 * w1[u] : acc;
-                    }
-                    val = (flat || (LAST && ZOOM && jw * G + u == jz)) ? 0.0 : val;     // (a scalar condition: one select)
-                    uint32_t field = 0u;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        field |= (val > a.on[t] ? 1u : 0u) << t;
-                        field |= (val < a.off[t] ? 1u : 0u) << (H + t);
-                    }
-                    fw[q] |= field << (u * 2 * H);
-                }
-            }
-            // the latches of this group's bins, in bin order (bins past the last one repeat it and are skipped)
-#pragma unroll
-            for (int u = 0; u < G; ++u) {
-                if (jw * G + u < Tb) {                  // wave-uniform
-#pragma unroll
-                    for (int q = 0; q < NCH; ++q) {
-                        const uint32_t field = fw[q] >> (u * 2 * H);
-                        const uint32_t S = field & tmask_a, R = (field >> H) & tmask_a;
-                        act[q] = (S & ~act[q]) | (act[q] & ~R);     // create_dataset.py:90-95 (both from the old latch)
-                        acc[q] |= (unsigned long long)act[q] << fill;
-                    }
-                    fill += n_thr;
-                    if (fill >= 32) {
-#pragma unroll
-                        for (int q = 0; q < NCH; ++q) {
-                            if (owner) stage[(q * CPW + cl) * RW + wout] = (uint32_t)acc[q];
-                            acc[q] >>= 32;
-                        }
-                        ++wout;
-                        fill -= 32;
-                    }
-                }
-            }
-        };
-#pragma unroll 1
-        for (int jw = 0; jw < NG4 - 1; ++jw) group(jw, std::false_type{});
-        group(NG4 - 1, std::true_type{});
-        if (fill > 0) {
-#pragma unroll
-            for (int q = 0; q < NCH; ++q) if (owner) stage[(q * CPW + cl) * RW + wout] = (uint32_t)acc[q];
-        }
-    };
-    {
-        using T = std::true_type;
-        using F = std::false_type;
-        using N4 = std::integral_constant<int, 4>;
-        using N8 = std::integral_constant<int, MAX_THR>;
-        const bool zoom = ncols != Tb;
-        if (n_thr <= 4) {
-            if (fastdiv) { if (zoom) pass_a(T{}, N4{}, T{}); else pass_a(T{}, N4{}, F{}); }
-            else         { if (zoom) pass_a(F{}, N4{}, T{}); else pass_a(F{}, N4{}, F{}); }
-        } else {
-            if (fastdiv) { if (zoom) pass_a(T{}, N8{}, T{}); else pass_a(T{}, N8{}, F{}); }
-            else         { if (zoom) pass_a(F{}, N8{}, T{}); else pass_a(F{}, N8{}, F{}); }
-        }
-    }
-    __syncthreads();                                    // the wave's own staged rows (and a uniform barrier count)
-    if (valid) {
-        // create_pure_redundancy: output row c reads filter row c / redundancy
-        const int R = a.redundancy;
-        const int fbase = g * NCH * CPW;
-        const int rows_out = min(NCH * CPW, F - fbase) * R;
-        const int row_bytes = row_bits;
-        uint8_t *dst = a.raster + ((size_t)b * F + fbase) * R * row_bytes;
-        if ((row_bytes & 3) == 0) {
-            const int rw = row_bytes >> 2;
-            uint32_t *d4 = reinterpret_cast<uint32_t *>(dst);
-            for (int i = lane; i < rows_out * rw; i += 64) {
-                const int c = i / rw;
-                const int p = (i - c * rw) * 4;
-                const uint32_t nib = (stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 0xFu;
-                d4[i] = (nib * 0x00204081u) & 0x01010101u;
-            }
-        } else {
-            for (int i = lane; i < rows_out * row_bytes; i += 64) {
-                const int c = i / row_bytes;
-                const int p = i - c * row_bytes;
-                dst[i] = (uint8_t)((stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 1u);
-            }
-        }
-    }
-}
+// The fused front end (gammatone_spikes_kernel: filterbank to raster in one launch) has its body in gammatone_spikes_body.h.
 
 // Stand-alone encoder on an already normalised spectrogram (B, F, n_bins): one lane per channel.
 template <typename T>
@@ -635,10 +185,18 @@ void fill_thresholds(T (&on)[MAX_THR], T (&off)[MAX_THR], const T *thr_on, const
     }
 }
 
+// The masked entry points' own refusal, after their twins' (include/lsm_hip_mask.h)
+int check_masks(const uint32_t *freq_mask, const uint32_t *time_mask)
+{
+    LSM_REQUIRE((((uintptr_t)freq_mask | (uintptr_t)time_mask) & 3u) == 0, "freq_mask and time_mask must be 4-byte aligned");
+    return LSM_OK;
+}
+
 template <typename T>
 int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, int time_bins,
                           int apply_floor, const T *thr_on, const T *thr_off, int n_thr,
-                          int redundancy, uint8_t *raster, T *norm_out, void *stream)
+                          int redundancy, uint8_t *raster, T *norm_out, void *stream,
+                          const uint32_t *freq_mask = nullptr, const uint32_t *time_mask = nullptr)
 {
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && ncols >= 2 && time_bins >= 2, "bad shape");
     LSM_REQUIRE(db != nullptr || n_clips == 0, "spec_to_spikes: null input");
@@ -654,6 +212,12 @@ int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, in
     fill_thresholds<T>(a.on, a.off, thr_on, thr_off, n_thr, (T)0, (T)0);
     const size_t lds = lsm_fe::spikes_lds_bytes(time_bins, n_thr);
     LSM_REQUIRE(lds <= 160 * 1024, "latch bit rows of %zu bytes (time_bins x thresholds) exceed one CU's LDS", lds);
+    if (const int rc = check_masks(freq_mask, time_mask)) return rc;
+    if (freq_mask || time_mask) {                       // SPEC.md 1.13; without a mask the launch below is the twin's
+        lsm_fe::launch_spec_to_spikes_masked<T>(a, lsm_fe::MaskArgs{freq_mask, time_mask}, SPK_THREADS, lds, stream);
+        LSM_CHECK_HIP(hipGetLastError());
+        return LSM_OK;
+    }
     auto fn = spec_to_spikes_kernel<T>;
     if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
     hipLaunchKernelGGL(fn, dim3(n_clips), dim3(SPK_THREADS), lds, (hipStream_t)stream, a);
@@ -880,11 +444,14 @@ LSM_API long lsm_gammatone_spikes_workspace(int n_clips, int n_filters, int ncol
     return (long)n_clips * ncols * (((n_filters + 127) / 128) * 2) * 64 * (long)sizeof(double);
 }
 
-LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samples,
-                                     const double *coefs, int n_filters, int nwin, int hop, int ncols,
-                                     int time_bins, const double *thr_on, const double *thr_off, int n_thr,
-                                     int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
-                                     int coef_flags, int launch_flags, void *stream)
+// lsm_gammatone_spikes_f64 and its masked twin (include/lsm_hip_mask.h): the same refusals, plan and launch geometry; with a
+// mask the kernel is the masked instantiation (mask.hip), without one exactly the unmasked launch.
+static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
+                            const double *coefs, int n_filters, int nwin, int hop, int ncols,
+                            int time_bins, const double *thr_on, const double *thr_off, int n_thr,
+                            int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
+                            int coef_flags, int launch_flags, const uint32_t *freq_mask, const uint32_t *time_mask,
+                            void *stream)
 {
     LSM_REQUIRE((launch_flags & ~3) == 0, "launch_flags: only bit 0 (low-latency layout) and bit 1 (no LDS reservation) are defined");
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && n_samples >= 1, "bad shape");
@@ -937,6 +504,13 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     const bool shb0 = fast && (coef_flags & 4) != 0;       // one b0 for every channel: shared between the two chains,
                                                            // wave-uniform in the lane pair
     const int nw = (nwin + hop - 1) / hop;
+    if (const int rc = check_masks(freq_mask, time_mask)) return rc;
+    if (freq_mask || time_mask) {                       // SPEC.md 1.13
+        const lsm_fe::FusedLaunch l{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
+        lsm_fe::launch_gammatone_spikes_masked(l, &a, lsm_fe::MaskArgs{freq_mask, time_mask}, stream);
+        LSM_CHECK_HIP(hipGetLastError());
+        return LSM_OK;
+    }
     auto launch = [&](auto nw_c, auto fast_c, auto nch_c, auto shb0_c, auto pair_c) {
         auto fn = gammatone_spikes_kernel<decltype(nw_c)::value, decltype(fast_c)::value, decltype(nch_c)::value,
                                           decltype(shb0_c)::value, decltype(pair_c)::value>;
@@ -965,6 +539,48 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
     }
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
+}
+
+LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samples,
+                                     const double *coefs, int n_filters, int nwin, int hop, int ncols,
+                                     int time_bins, const double *thr_on, const double *thr_off, int n_thr,
+                                     int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
+                                     int coef_flags, int launch_flags, void *stream)
+{
+    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                            redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, nullptr, nullptr, stream);
+}
+
+LSM_API int lsm_gammatone_spikes_masked_f64(const float *audio, int n_clips, int n_samples,
+                                            const double *coefs, int n_filters, int nwin, int hop, int ncols,
+                                            int time_bins, const double *thr_on, const double *thr_off, int n_thr,
+                                            int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
+                                            int coef_flags, int launch_flags, const uint32_t *freq_mask,
+                                            const uint32_t *time_mask, void *stream)
+{
+    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                            redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, freq_mask, time_mask,
+                            stream);
+}
+
+LSM_API int lsm_spec_to_spikes_masked_f64(const double *db, int n_clips, int n_filters, int ncols,
+                                          int time_bins, int apply_floor, const double *thr_on,
+                                          const double *thr_off, int n_thr, int redundancy,
+                                          uint8_t *raster, double *norm_out, const uint32_t *freq_mask,
+                                          const uint32_t *time_mask, void *stream)
+{
+    return launch_spec_to_spikes<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor,
+                                         thr_on, thr_off, n_thr, redundancy, raster, norm_out, stream, freq_mask, time_mask);
+}
+
+LSM_API int lsm_spec_to_spikes_masked_f32(const float *db, int n_clips, int n_filters, int ncols,
+                                          int time_bins, int apply_floor, const float *thr_on,
+                                          const float *thr_off, int n_thr, int redundancy,
+                                          uint8_t *raster, float *norm_out, const uint32_t *freq_mask,
+                                          const uint32_t *time_mask, void *stream)
+{
+    return launch_spec_to_spikes<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor,
+                                        thr_on, thr_off, n_thr, redundancy, raster, norm_out, stream, freq_mask, time_mask);
 }
 
 LSM_API int lsm_spec_to_spikes_f64(const double *db, int n_clips, int n_filters, int ncols,

@@ -1,0 +1,103 @@
+// gammatone_spikes_body.h -- the fused gammatone front end (filterbank -> dB -> normalise -> resize -> hysteresis encoder ->
+// raster in ONE launch): its argument type, its helpers and the kernel that frontend.hip launches.  The kernel's text is
+// gammatone_spikes_kernel.inc; the masked kernel (mask.hip, SPEC.md 1.13) is the same text with MASK = true, in a
+// translation unit of its own, compiled beside frontend.hip.
+// Everything here sits in an unnamed namespace, as it did inside frontend.hip: the kernels' symbols carry that
+// namespace and FusedArgs in their names, and those names stay what they were.
+#pragma once
+#include "lsm_common.h"
+#include "gammatone_body.h"
+#include "spikes_body.h"
+#include <type_traits>
+
+namespace {
+
+constexpr int NWIN_MAX = 4;
+constexpr int GT_MAX_WPB = 8;           // waves per workgroup, at most
+using lsm_fe::MAX_THR;
+
+// ---------------------------------------------------------------------------------------------
+// Fused front end: filterbank -> dB -> floor/min-max normalise -> linear resize -> hysteresis encoder ->
+// uint8 raster in ONE launch (create_dataset.py:49-104 per clip).  The filter loop is the one of
+// gammatone_kernel; what differs:
+//   * a wave carries NCH channel groups of its clip (NCH = 2: 128 channels, two independent float64
+//     dependency chains per lane that share the scalar sample loads and the float32 -> float64
+//     conversion), so at 128 filters ONE WAVE IS ONE CLIP and the clip's max/min need no other wave;
+//   * the clip's dB columns go to a private scratch, column-major per wave (64 consecutive doubles per
+//     store); the lane that wrote a value is the only one that reads it back, after the last window, when
+//     the clip's maximum is known.  A row's 98 float64 values do not fit the registers next to the filter
+//     state of two chains and 100 KB per clip do not fit the LDS four times per CU;
+//   * max/min: running per lane, xor-shuffles per wave, one LDS exchange when a clip spans several waves
+//     (the waves of a clip always share a workgroup);
+//   * normalise / SciPy-exact resize / 4-threshold latch: one lane per channel, arithmetic and comparison
+//     order of spec_to_spikes_kernel<double>; the raster rows of a wave are staged bit-packed in LDS and
+//     leave as coalesced 4-byte stores.
+// Waves beyond the batch (last workgroup) skip the filter loop but keep the barriers.
+//
+// PAIR (lane-pair layout, NCH = 1): a wave carries 32 channels of its clip, channel j in lanes j (head) and j + 32
+// (tail), so at 128 filters a clip is 4 waves and a 256-clip launch puts a wave on every SIMD.  In the iteration of
+// sample n the head runs sections 1-2 on sample n + 1 and the tail sections 3-4 on sample n, fed with the head's
+// section-2 output of sample n, which v_permlane32_swap moves from lane j to lane j + 32 at the top of the iteration.
+// Both halves run the same two-section code with their own section coefficients and state.  The division, the
+// square and the window sums run on both halves (one instruction stream) but only the tail's feed the dB columns,
+// the max/min and the epilogue.  Every float64 operation of a channel and its order are those of the other layouts:
+// the skew only changes when section 3 sees a value, and the hand-off moves bits.
+// ---------------------------------------------------------------------------------------------
+struct FusedArgs {
+    const float *audio;
+    const double *coefs;
+    double *ws;                 // (n_clips, ncols, groups*NCH*64) float64 scratch (32 channels per group in the lane pair)
+    uint8_t *raster;            // (n_clips, n_filters*redundancy, time_bins*n_thr)
+    int n_clips, n_samples, n_filters, nwin, hop, ncols;
+    int time_bins, n_thr, redundancy, groups;
+    int unused_;                // (keeps the argument layout, and with it the filter loop's code, of the measured build)
+    int prio;                   // wave priority of the filter loop: 0 (see the kernel)
+    double on[MAX_THR], off[MAX_THR];
+};
+
+// Head lanes (0-31) keep `lo`, tail lanes (32-63) receive v of lane - 32: v_permlane32_swap exchanges lanes 32-63 of
+// its first operand with lanes 0-31 of its second; one swap per 32-bit half.
+__device__ __forceinline__ double pair_up(double lo, double v)
+{
+    const unsigned long long a = (unsigned long long)__double_as_longlong(lo);
+    const unsigned long long c = (unsigned long long)__double_as_longlong(v);
+    const auto rl = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)c, false, false);
+    const auto rh = __builtin_amdgcn_permlane32_swap((unsigned)(a >> 32), (unsigned)(c >> 32), false, false);
+    return __longlong_as_double((long long)(((unsigned long long)rh[0] << 32) | rl[0]));
+}
+
+__device__ __forceinline__ double uniform_f64(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// The unmasked kernel: the text of gammatone_spikes_kernel.inc with MASK = false
+#define LSM_FUSED_KERNEL gammatone_spikes_kernel
+#define LSM_FUSED_PARAMS const FusedArgs a
+#define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
+#include "gammatone_spikes_kernel.inc"
+#undef LSM_FUSED_KERNEL
+#undef LSM_FUSED_PARAMS
+#undef LSM_FUSED_MASK
+
+}  // namespace
+
+namespace lsm_fe {
+
+// What the host needs to launch one of the kernel's forms: chosen by fused_plan and the entry point's checks (frontend.hip)
+struct FusedLaunch {
+    int nw, nch;                // live windows (1..4), chains per lane
+    bool fast, shb0, pair;
+    unsigned grid, block;
+    size_t lds;
+};
+
+// The masked twins of the launches in frontend.hip, defined in mask.hip (their kernels are a translation unit of their own).
+// `fused_args`: a FusedArgs -- the type lives in each unit's unnamed namespace, so it crosses between them as bytes.
+void launch_gammatone_spikes_masked(const FusedLaunch &l, const void *fused_args, const MaskArgs &m, void *stream);
+template <typename T>
+void launch_spec_to_spikes_masked(const SpikeArgs<T> &a, const MaskArgs &m, int threads, size_t lds, void *stream);
+
+}  // namespace lsm_fe

@@ -110,41 +110,20 @@ struct MelSpikeArgs {
 
 constexpr size_t MEL_SPIKES_LDS = 4 * sizeof(double2) * ZPAD + 32;
 
-__global__ __launch_bounds__(256) void mel_spikes_kernel(const MelSpikeArgs a)
-{
-    // four waves, a point buffer each (dynamic: 68 KB); the finishing workgroup reuses them as the raster stage
-    extern __shared__ __attribute__((aligned(16))) unsigned char mel_lds[];
-    double2 *buf = reinterpret_cast<double2 *>(mel_lds);
-    float *red = reinterpret_cast<float *>(mel_lds + 4 * sizeof(double2) * ZPAD);       // 4 floats
-    int &last = *reinterpret_cast<int *>(red + 4);
-    const int b = blockIdx.y, tid = threadIdx.x, w = tid >> 6;
-    // A workgroup takes `frames_per_wg` consecutive frames, its four waves one frame each at a time: the release fence below
-    // writes the XCD's dirty L2 lines back (the eight L2s are not coherent with each other), which costs about a microsecond,
-    // so it is paid once per group of frames, not once per frame (one frame per workgroup: 2.4 instead of 0.3 ms per
-    // 200 clips, profiles/r04_mel_one_launch_ab.txt).
-    const int t0 = (int)blockIdx.x * a.frames_per_wg;
-    const int t1 = min(t0 + a.frames_per_wg, a.mel.n_frames);
-    for (int t = t0 + w; t < t1; t += 4) {
-        mel_clip_frame(a.mel, buf + w * ZPAD, b, t);
-        mel_wave_fence();                       // the wave's LDS buffers are free again
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // my power values are visible device-wide before my count is
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned int prev = atomicAdd(a.counters + b, 1u);
-        last = prev == gridDim.x - 1u;
-        if (last) a.counters[b] = 0u;           // every workgroup of the clip has counted: reset for the next launch
-    }
-    __syncthreads();
-    if (!last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the other workgroups' values, not whatever this CU may have cached
-    const int n = a.mel.n_mels * a.mel.n_frames;
-    float *db = const_cast<float *>(a.sp.db) + (size_t)b * n;
-    power_to_db_body(a.mel.power_out + (size_t)b * n, db, n, a.amin, a.top_db, red);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // dB values written by other threads of this workgroup
-    __syncthreads();
-    lsm_fe::spec_to_spikes_body<float>(a.sp, b, mel_lds);
-}
+#define LSM_MEL_KERNEL mel_spikes_kernel
+#define LSM_MEL_PARAMS const MelSpikeArgs a
+#define LSM_MEL_ENCODE lsm_fe::spec_to_spikes_body<float>(a.sp, b, mel_lds)
+#include "mel_spikes_kernel.inc"
+#undef LSM_MEL_KERNEL
+#undef LSM_MEL_PARAMS
+#undef LSM_MEL_ENCODE
+#define LSM_MEL_KERNEL mel_spikes_masked_kernel
+#define LSM_MEL_PARAMS const MelSpikeArgs a, const lsm_fe::MaskArgs m
+#define LSM_MEL_ENCODE lsm_fe::spec_to_spikes_body<float, true>(a.sp, b, mel_lds, m)
+#include "mel_spikes_kernel.inc"
+#undef LSM_MEL_KERNEL
+#undef LSM_MEL_PARAMS
+#undef LSM_MEL_ENCODE
 
 }  // namespace
 
@@ -178,11 +157,14 @@ LSM_API long lsm_mel_spikes_workspace(int n_clips, int n_mels, int n_frames)
     return (long)(((size_t)n_clips * 4 + 255) / 256 * 256) + 2L * n_clips * n_mels * n_frames * (long)sizeof(float);
 }
 
-LSM_API int lsm_mel_spikes_f32(const float *audio, int n_clips, int n_samples, int n_fft, int hop, int n_frames,
-                               const double *window_dev, const double *twiddle_dev, const float *basis_dev,
-                               const int32_t *lo_dev, const int32_t *hi_dev, int n_mels, float amin, float top_db,
-                               int time_bins, const float *thr_on, const float *thr_off, int n_thr, int redundancy,
-                               uint8_t *raster, void *workspace, long workspace_bytes, void *stream)
+// lsm_mel_spikes_f32 and its masked twin (include/lsm_hip_mask.h): the same refusals and launch geometry; with a mask the
+// kernel is the masked one, without one exactly the unmasked launch.
+static int mel_spikes(const float *audio, int n_clips, int n_samples, int n_fft, int hop, int n_frames,
+                      const double *window_dev, const double *twiddle_dev, const float *basis_dev,
+                      const int32_t *lo_dev, const int32_t *hi_dev, int n_mels, float amin, float top_db,
+                      int time_bins, const float *thr_on, const float *thr_off, int n_thr, int redundancy,
+                      uint8_t *raster, void *workspace, long workspace_bytes, const uint32_t *freq_mask,
+                      const uint32_t *time_mask, void *stream)
 {
     LSM_REQUIRE(n_clips >= 0 && n_samples >= 1 && hop >= 1 && n_frames >= 2 && n_mels >= 1 && time_bins >= 2, "bad shape");
     LSM_REQUIRE(n_fft == NFFT, "n_fft must be %d (librosa's default), got %d", NFFT, n_fft);
@@ -208,6 +190,7 @@ LSM_API int lsm_mel_spikes_f32(const float *audio, int n_clips, int n_samples, i
                       4 * sizeof(double2) * ZPAD);
         return LSM_ERR_UNSUPPORTED;
     }
+    LSM_REQUIRE((((uintptr_t)freq_mask | (uintptr_t)time_mask) & 3u) == 0, "freq_mask and time_mask must be 4-byte aligned");
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     const size_t cbytes = ((size_t)n_clips * 4 + 255) / 256 * 256;
     float *power = reinterpret_cast<float *>(ws + cbytes);
@@ -233,10 +216,40 @@ LSM_API int lsm_mel_spikes_f32(const float *audio, int n_clips, int n_samples, i
     // kernel resets a counter only when a clip's last workgroup arrives, so a launch that failed, or a workspace the caller
     // did not zero, would otherwise leave every later launch without a finishing workgroup.
     LSM_CHECK_HIP(hipMemsetAsync(a.counters, 0, (size_t)n_clips * sizeof(unsigned int), (hipStream_t)stream));
+    if (freq_mask || time_mask) {               // SPEC.md 1.13
+        lsm_allow_big_lds(reinterpret_cast<const void *>(mel_spikes_masked_kernel));
+        hipLaunchKernelGGL(mel_spikes_masked_kernel, dim3((n_frames + fpw - 1) / fpw, n_clips), dim3(256), MEL_SPIKES_LDS,
+                           (hipStream_t)stream, a, lsm_fe::MaskArgs{freq_mask, time_mask});
+        LSM_CHECK_HIP(hipGetLastError());
+        return LSM_OK;
+    }
     lsm_allow_big_lds(reinterpret_cast<const void *>(mel_spikes_kernel));       // 68 KB of dynamic LDS
     hipLaunchKernelGGL(mel_spikes_kernel, dim3((n_frames + fpw - 1) / fpw, n_clips), dim3(256), MEL_SPIKES_LDS, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
+}
+
+LSM_API int lsm_mel_spikes_f32(const float *audio, int n_clips, int n_samples, int n_fft, int hop, int n_frames,
+                               const double *window_dev, const double *twiddle_dev, const float *basis_dev,
+                               const int32_t *lo_dev, const int32_t *hi_dev, int n_mels, float amin, float top_db,
+                               int time_bins, const float *thr_on, const float *thr_off, int n_thr, int redundancy,
+                               uint8_t *raster, void *workspace, long workspace_bytes, void *stream)
+{
+    return mel_spikes(audio, n_clips, n_samples, n_fft, hop, n_frames, window_dev, twiddle_dev, basis_dev, lo_dev, hi_dev,
+                      n_mels, amin, top_db, time_bins, thr_on, thr_off, n_thr, redundancy, raster, workspace, workspace_bytes,
+                      nullptr, nullptr, stream);
+}
+
+LSM_API int lsm_mel_spikes_masked_f32(const float *audio, int n_clips, int n_samples, int n_fft, int hop, int n_frames,
+                                      const double *window_dev, const double *twiddle_dev, const float *basis_dev,
+                                      const int32_t *lo_dev, const int32_t *hi_dev, int n_mels, float amin, float top_db,
+                                      int time_bins, const float *thr_on, const float *thr_off, int n_thr, int redundancy,
+                                      uint8_t *raster, void *workspace, long workspace_bytes, const uint32_t *freq_mask,
+                                      const uint32_t *time_mask, void *stream)
+{
+    return mel_spikes(audio, n_clips, n_samples, n_fft, hop, n_frames, window_dev, twiddle_dev, basis_dev, lo_dev, hi_dev,
+                      n_mels, amin, top_db, time_bins, thr_on, thr_off, n_thr, redundancy, raster, workspace, workspace_bytes,
+                      freq_mask, time_mask, stream);
 }
 
 LSM_API int lsm_power_to_db_f32(const float *power, int n_clips, int n_per_clip, float amin,

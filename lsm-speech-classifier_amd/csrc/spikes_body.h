@@ -21,6 +21,13 @@ struct SpikeArgs {
     T *norm_out;            // (B, F, time_bins) or null
 };
 
+// SpecAugment-style masks of a batch (SPEC.md 1.13), the masked kernels' argument beside their twins' own: one bit per filter
+// row / time bin and clip, bit i in bit i & 31 of word i >> 5; either pointer may be null (no mask of that kind)
+struct MaskArgs {
+    const uint32_t *freq;   // (n_clips, ceil(n_filters / 32)) or null
+    const uint32_t *time;   // (n_clips, ceil(time_bins / 32)) or null
+};
+
 template <typename T>
 __device__ __forceinline__ T block_reduce(T v, bool is_max, T *scratch)
 {
@@ -57,8 +64,11 @@ __host__ __device__ inline size_t spikes_lds_bytes(int time_bins, int n_thr)
 //   2. one thread per (row, threshold) runs the latch over the bits: active' = active ? !below : above
 //      (create_dataset.py:88-96: rising and falling are both taken from the latch before the update), 32 bins per addition;
 //   3. the raster bytes, four per store, from the latch bits.
-template <typename T>
-__device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const int b, unsigned char *smem)
+// MASK (SPEC.md 1.13): a value whose row or time bin is masked becomes +0.0 where the zero bin's does, after maximum, floor,
+// minimum and resize.  The row is wave-uniform (its bit is a scalar), the 64 time bits of a piece are one 64-bit scalar.
+template <typename T, bool MASK = false>
+__device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const int b, unsigned char *smem,
+                                                    const MaskArgs m = MaskArgs{nullptr, nullptr})
 {
     T *scratch = reinterpret_cast<T *>(smem);                 // 16 entries: one per wave of up to 1024 threads
     const int F = a.n_filters, nc = a.ncols, Tb = a.time_bins, nq = a.n_thr;
@@ -98,6 +108,11 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
     const int jz = (nc != Tb && (double)(Tb - 1) * zf > (double)(nc - 1)) ? Tb - 1 : -1;
     const int C = F * a.redundancy;
     uint8_t *dst = a.raster ? a.raster + (size_t)b * C * row_bytes : nullptr;
+    const uint32_t *fmc = nullptr, *tmc = nullptr;            // this clip's mask words
+    if constexpr (MASK) {
+        fmc = m.freq ? m.freq + (size_t)b * ((F + 31) >> 5) : nullptr;
+        tmc = m.time ? m.time + (size_t)b * W : nullptr;
+    }
 
     for (int r0 = 0; r0 < F; r0 += SPK_ROWS) {
         const int rows = min(SPK_ROWS, F - r0);
@@ -150,6 +165,13 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
                     val = (T)acc;
                 }
                 val = j == jz ? (T)0 : val;
+                if constexpr (MASK) {
+                    const int f = r0 + rl, w = j0 >> 5;           // wave-uniform: scalar loads
+                    const uint32_t rowm = fmc ? (fmc[f >> 5] >> (f & 31)) & 1u : 0u;
+                    unsigned long long tb = 0ull;                 // the piece's 64 time bits (words past the row: clear)
+                    if (tmc) tb = (unsigned long long)tmc[w] | (w + 1 < W ? (unsigned long long)tmc[w + 1] << 32 : 0ull);
+                    val = (rowm || ((tb >> lane) & 1ull)) ? (T)0 : val;
+                }
                 if (a.norm_out && valid) a.norm_out[((size_t)b * F + r0 + rl) * Tb + j] = val;
 #pragma unroll
                 for (int q = 0; q < MAX_THR; ++q) {

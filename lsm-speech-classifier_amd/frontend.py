@@ -243,8 +243,10 @@ class SpikeFrontEnd:
                 "lsm_gammatone_spec_f64")
         return db, spec
 
-    def spikes_from_db(self, db: torch.Tensor, want_norm: bool = False, want_raster: bool = True):
-        """dB spectrogram -> (uint8 raster (B, C, n_steps), normalised spectrogram or None)."""
+    def spikes_from_db(self, db: torch.Tensor, want_norm: bool = False, want_raster: bool = True, mask=None):
+        """dB spectrogram -> (uint8 raster (B, C, n_steps), normalised spectrogram or None).  ``mask``: a `MaskPlan` of the
+        batch's clips (SPEC.md 1.13): the masked entry point encodes -- and, with ``want_norm``, shows -- the masked
+        spectrogram; None makes exactly the unmasked call."""
         B = db.shape[0]
         f64 = db.dtype == torch.float64
         np_dt = np.float64 if f64 else np.float32
@@ -257,16 +259,21 @@ class SpikeFrontEnd:
                       if want_raster else None)
             norm = (torch.empty((B, self.n_filters, self.time_bins), dtype=db.dtype, device=self.device)
                     if want_norm else None)
-            fn = self.lib.lsm_spec_to_spikes_f64 if f64 else self.lib.lsm_spec_to_spikes_f32
-            _lib.check(fn(_dev(db), B, self.n_filters, db.shape[2], self.time_bins,
-                          1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on),
-                          self.redundancy, _dev(raster) if want_raster else None,
-                          _dev(norm) if want_norm else None, self._stream()), "lsm_spec_to_spikes")
+            args = (_dev(db), B, self.n_filters, db.shape[2], self.time_bins,
+                    1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on),
+                    self.redundancy, _dev(raster) if want_raster else None, _dev(norm) if want_norm else None)
+            if mask is None:
+                fn = self.lib.lsm_spec_to_spikes_f64 if f64 else self.lib.lsm_spec_to_spikes_f32
+                _lib.check(fn(*args, self._stream()), "lsm_spec_to_spikes")
+            else:
+                fm, tm = upload_mask(mask, B, self.n_filters, self.time_bins, self.device)
+                fn = self.lib.lsm_spec_to_spikes_masked_f64 if f64 else self.lib.lsm_spec_to_spikes_masked_f32
+                _lib.check(fn(*args, _dev(fm), _dev(tm), self._stream()), "lsm_spec_to_spikes_masked")
         return raster, norm
 
     def encode(self, audio, fused: bool | None = None, low_latency: bool = False,
                raster_out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
-               share_lds: bool = False) -> torch.Tensor:
+               share_lds: bool = False, mask=None) -> torch.Tensor:
         """audio (B, n_samples) -> uint8 spike raster (B, C, n_steps) on the device.  The gammatone branch is one
         launch (`lsm_gammatone_spikes_f64`); `fused=False` takes the split entry points (identical rasters), which is
         also what the mel branch takes by default (its one-launch route, `fused=True` -> `lsm_mel_spikes_f32`, measured
@@ -278,9 +285,13 @@ class SpikeFrontEnd:
         launches, `lsm_gammatone_spikes_f64` flag bit 1).  `raster_out` / `workspace`
         (fused launch only): caller-owned uint8 (B, C, n_steps) output and scratch from `new_workspace(B)` (gammatone:
         float64, at least `workspace_elems(B)` elements; mel: zero-initialised bytes), so that a steady stream of
-        batches makes no allocator call at all."""
+        batches makes no allocator call at all.  ``mask``: a `MaskPlan` of the batch's clips (SPEC.md 1.13), applied inside
+        the encoder of whichever route is taken (the masked entry points of include/lsm_hip_mask.h); its words are uploaded on
+        the current stream; None makes exactly the unmasked calls."""
         if fused is None:
             fused = self.will_fuse()
+        if mask is not None:
+            checked_mask(mask, 1 if getattr(audio, "ndim", 2) == 1 else len(audio), self.n_filters, self.time_bins)
         if not fused:
             if raster_out is not None or workspace is not None:
                 # the split route allocates its own outputs on the current stream: a caller that owns the raster
@@ -288,7 +299,7 @@ class SpikeFrontEnd:
                 raise ValueError("raster_out / workspace belong to the fused launch; this front end takes the split "
                                  "route (mel branch, > 1024 filters or LSM_FRONTEND_SPLIT=1)")
             db, _ = self.spectrogram_db(audio)
-            raster, _ = self.spikes_from_db(db)
+            raster, _ = self.spikes_from_db(db, mask=mask)
             return raster
         audio = self._audio(audio)
         B = audio.shape[0]
@@ -297,7 +308,8 @@ class SpikeFrontEnd:
                 raise ValueError(f"{self.n_filters} mel filters do not fit the one-launch front end; use fused=False")
             on32, off32 = threshold_tables(self.thresholds, self.gap, np.float32)
             with torch.cuda.device(self.device):
-                return self._mel.spikes(audio, on32, off32, self.time_bins, self.redundancy, raster_out, workspace)
+                masks = None if mask is None else upload_mask(mask, B, self.n_filters, self.time_bins, self.device)
+                return self._mel.spikes(audio, on32, off32, self.time_bins, self.redundancy, raster_out, workspace, masks)
         on, off = threshold_tables(self.thresholds, self.gap, np.float64)
         with torch.cuda.device(self.device):
             shape = (B, self.n_channels, self.n_steps)
@@ -316,11 +328,15 @@ class SpikeFrontEnd:
                 ws = workspace
             else:
                 ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
-            _lib.check(self.lib.lsm_gammatone_spikes_f64(
-                _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
-                self.ncols, self.time_bins, _host(on), _host(off), len(on), self.redundancy, _dev(raster),
-                _dev(ws), ws_bytes, self.coef_flags, (1 if low_latency else 0) | (2 if share_lds else 0), self._stream()),
-                "lsm_gammatone_spikes_f64")
+            args = (_dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
+                    self.ncols, self.time_bins, _host(on), _host(off), len(on), self.redundancy, _dev(raster),
+                    _dev(ws), ws_bytes, self.coef_flags, (1 if low_latency else 0) | (2 if share_lds else 0))
+            if mask is None:
+                _lib.check(self.lib.lsm_gammatone_spikes_f64(*args, self._stream()), "lsm_gammatone_spikes_f64")
+            else:
+                fm, tm = upload_mask(mask, B, self.n_filters, self.time_bins, self.device)
+                _lib.check(self.lib.lsm_gammatone_spikes_masked_f64(*args, _dev(fm), _dev(tm), self._stream()),
+                           "lsm_gammatone_spikes_masked_f64")
         return raster
 
 
@@ -1508,6 +1524,97 @@ class SpeedPerturber:
                     len(self.designs), _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out, _dev(out[r0:]),
                     stream), "lsm_speed_f32")
         return out
+
+
+# ---- SpecAugment-style masks inside the spike encoders (SPEC.md §1.13, include/lsm_hip_mask.h) ---------------------------
+
+def mask_words(starts, widths, n_bits: int) -> np.ndarray:
+    """Bands -> mask words: ``starts`` and ``widths`` are ``(n_clips, k)`` integers (k bands per clip, a width of 0 is no
+    band); returns ``(n_clips, ceil(n_bits / 32))`` uint32 with bit ``i & 31`` of word ``i >> 5`` set where a band of the clip
+    covers index ``i``.  Every band must lie inside ``[0, n_bits)``."""
+    starts, widths = np.asarray(starts), np.asarray(widths)
+    if starts.ndim != 2 or starts.shape != widths.shape or starts.dtype.kind not in "iu" or widths.dtype.kind not in "iu":
+        raise ValueError(f"starts and widths must be integer arrays of one (n_clips, k) shape, got {starts.shape}, {widths.shape}")
+    n_bits = int(n_bits)
+    if n_bits < 1:
+        raise ValueError(f"n_bits must be >= 1, got {n_bits}")
+    starts, widths = starts.astype(np.int64), widths.astype(np.int64)
+    if (starts < 0).any() or (widths < 0).any() or (starts + widths > n_bits).any():
+        raise ValueError(f"a band lies outside [0, {n_bits})")
+    i = np.arange(n_bits, dtype=np.int64)
+    bits = ((i >= starts[:, :, None]) & (i < (starts + widths)[:, :, None])).any(axis=1)        # (n_clips, n_bits)
+    n_words = (n_bits + 31) // 32
+    padded = np.zeros((len(starts), n_words * 32), dtype=np.uint64)
+    padded[:, :n_bits] = bits
+    return (padded.reshape(len(starts), n_words, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+
+
+class MaskPlan(NamedTuple):
+    """Per-clip frequency and time masks (`mask_plan`, `mask_words`), host arrays of uint32 words, one row per clip: ``freq``
+    ``(n, ceil(n_filters / 32))`` over the filter rows before redundancy, ``time`` ``(n, ceil(time_bins / 32))`` over the
+    time bins."""
+    freq: np.ndarray
+    time: np.ndarray
+
+    def part(self, lo: int, hi: int) -> "MaskPlan":
+        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
+        return MaskPlan(self.freq[lo:hi], self.time[lo:hi])
+
+    def take(self, idx) -> "MaskPlan":
+        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
+        idx = np.asarray(idx, dtype=np.int64)
+        return MaskPlan(self.freq[idx], self.time[idx])
+
+
+def mask_plan(n_clips: int, n_filters: int, time_bins: int, freq_masks: int = 0, freq_width: int = 0, time_masks: int = 0,
+              time_width: int = 0, prob: float = 1.0, seed: int = 42) -> MaskPlan:
+    """The masks of every clip of a listing, drawn from ``np.random.RandomState([seed, 3])`` -- a generator of its own, so
+    `mix_plan`'s, `reverb_plan`'s and `speed_plan`'s draws for the same seed stay as they are -- for ALL ``n_clips`` clips in
+    listing order.  The draws, in this order: (1) the frequency widths, ``randint(0, freq_width + 1, (n, freq_masks))``;
+    (2) the frequency positions, ``floor(random_sample((n, freq_masks)) * (n_filters - width + 1))``; (3) the time widths,
+    ``randint(0, time_width + 1, (n, time_masks))``, and (4) the time positions, ``floor(random_sample((n, time_masks)) *
+    (time_bins - width + 1))``; (5) ``u = random_sample(n)``: a clip with ``u >= prob`` gets no mask.  Band ``k`` of a clip
+    covers ``[position, position + width)``."""
+    n, F, Tb, p = int(n_clips), int(n_filters), int(time_bins), float(prob)
+    nf, wf, nt, wt = int(freq_masks), int(freq_width), int(time_masks), int(time_width)
+    if n < 0 or F < 1 or Tb < 1 or nf < 0 or nt < 0 or wf < 0 or wt < 0 or not 0.0 <= p <= 1.0:
+        raise ValueError(f"mask_plan needs n_clips >= 0, n_filters and time_bins >= 1, counts and widths >= 0 and prob in "
+                         f"[0, 1], got {n_clips}, {n_filters}, {time_bins}, {freq_masks}, {freq_width}, {time_masks}, "
+                         f"{time_width}, {prob}")
+    if wf > F or wt > Tb:
+        raise ValueError(f"a mask cannot be wider than its axis: freq_width {wf} of {F} filters, time_width {wt} of {Tb} bins")
+    rs = np.random.RandomState([int(seed), 3])
+    f_w = rs.randint(0, wf + 1, size=(n, nf)).astype(np.int64)
+    f_p = np.floor(rs.random_sample((n, nf)) * (F - f_w + 1)).astype(np.int64)
+    t_w = rs.randint(0, wt + 1, size=(n, nt)).astype(np.int64)
+    t_p = np.floor(rs.random_sample((n, nt)) * (Tb - t_w + 1)).astype(np.int64)
+    u = rs.random_sample(n)
+    freq, time = mask_words(f_p, f_w, F), mask_words(t_p, t_w, Tb)
+    freq[u >= p] = 0
+    time[u >= p] = 0
+    return MaskPlan(freq, time)
+
+
+def checked_mask(mask, n_clips: int, n_filters: int, time_bins: int):
+    """A `MaskPlan` for a batch of ``n_clips`` as the entry points take it: ``(freq, time)`` contiguous uint32 host arrays of
+    the shapes the ABI reads.  Raises ValueError."""
+    if not isinstance(mask, MaskPlan):
+        raise ValueError(f"mask must be a frontend.MaskPlan, got {type(mask).__name__}")
+    out = []
+    for name, a, bits in (("freq", mask.freq, n_filters), ("time", mask.time, time_bins)):
+        a = np.asarray(a)
+        shape = (int(n_clips), (int(bits) + 31) // 32)
+        if a.dtype != np.uint32 or a.shape != shape:
+            raise ValueError(f"mask.{name} must be uint32 {shape} (one row of words per clip), got {a.dtype} {a.shape}")
+        out.append(np.ascontiguousarray(a))
+    return tuple(out)
+
+
+def upload_mask(mask, n_clips: int, n_filters: int, time_bins: int, device):
+    """`checked_mask`, then the two word arrays on ``device`` (int32 tensors holding the uint32 bits), copied on the current
+    stream without waiting, the way the mixer's per-clip arrays travel.  A plan of zero clips uploads nothing."""
+    freq, time = checked_mask(mask, n_clips, n_filters, time_bins)
+    return tuple(torch.from_numpy(a.view(np.int32)).to(device, non_blocking=True) for a in (freq, time))
 
 
 _FRONT_ENDS: dict = {}

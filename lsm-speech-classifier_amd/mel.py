@@ -105,9 +105,10 @@ class MelSpectrogram:
         return 128 + 2 * 64 * max(n_thr, 1) * ((time_bins + 31) // 32) * 4 <= 4 * 17408
 
     def spikes(self, audio: torch.Tensor, on: np.ndarray, off: np.ndarray, time_bins: int, redundancy: int,
-               raster_out: torch.Tensor | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+               raster_out: torch.Tensor | None = None, workspace: torch.Tensor | None = None, masks=None) -> torch.Tensor:
         """(B, n_samples) float32 -> uint8 raster (B, n_mels*redundancy, time_bins*len(on)) in ONE launch
-        (`lsm_mel_spikes_f32`): mel power -> dB -> normalise -> resize -> hysteresis encoder."""
+        (`lsm_mel_spikes_f32`): mel power -> dB -> normalise -> resize -> hysteresis encoder.  ``masks``: the frequency and the
+        time mask words of the batch on the device (SPEC.md 1.13, `lsm_mel_spikes_masked_f32`); None: the unmasked call."""
         B = audio.shape[0]
         shape = (B, self.n_mels * redundancy, time_bins * len(on))
         raster = raster_out if raster_out is not None else torch.empty(shape, dtype=torch.uint8, device=self.device)
@@ -132,10 +133,13 @@ class MelSpectrogram:
         h = lambda a: C.c_void_p(a.ctypes.data)
         on = np.ascontiguousarray(on, dtype=np.float32)
         off = np.ascontiguousarray(off, dtype=np.float32)
-        _lib.check(self.lib.lsm_mel_spikes_f32(
-            p(audio), B, self.n_samples, N_FFT, self.hop, self.n_frames, p(self.window), p(self.twiddle),
-            p(self.basis), p(self.lo), p(self.hi), self.n_mels, C.c_float(AMIN), C.c_float(TOP_DB), int(time_bins),
-            h(on), h(off), len(on), int(redundancy), p(raster), p(ws), int(ws.numel()), stream), "lsm_mel_spikes_f32")
+        args = (p(audio), B, self.n_samples, N_FFT, self.hop, self.n_frames, p(self.window), p(self.twiddle),
+                p(self.basis), p(self.lo), p(self.hi), self.n_mels, C.c_float(AMIN), C.c_float(TOP_DB), int(time_bins),
+                h(on), h(off), len(on), int(redundancy), p(raster), p(ws), int(ws.numel()))
+        if masks is None:
+            _lib.check(self.lib.lsm_mel_spikes_f32(*args, stream), "lsm_mel_spikes_f32")
+        else:
+            _lib.check(self.lib.lsm_mel_spikes_masked_f32(*args, p(masks[0]), p(masks[1]), stream), "lsm_mel_spikes_masked_f32")
         return raster
 
     def power_db(self, audio: torch.Tensor) -> torch.Tensor:

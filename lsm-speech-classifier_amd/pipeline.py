@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .frontend import as_float32, checked_counts, checked_pcm, checked_slots, indexed_device
+from .frontend import as_float32, checked_counts, checked_mask, checked_pcm, checked_slots, indexed_device
 
 DEFAULT_STREAMS = 6
 # front-end streams of their own (0 = rotation: every step keeps to one stream).  Measured at 128 filters / 1000
@@ -146,8 +146,8 @@ class HotPath:
         self._h2d = {}
 
     # ---- one step ---------------------------------------------------------------------------
-    def _one(self, x, stats_out, out, stage, tail=False):
-        rasters = x if stage == "reservoir" else self.fe.encode(x)
+    def _one(self, x, stats_out, out, stage, tail=False, mask=None):
+        rasters = x if stage == "reservoir" else self.fe.encode(x, **({} if mask is None else {"mask": mask}))
         if stage == "frontend":
             return rasters
         if self.time_reservoir:
@@ -170,7 +170,7 @@ class HotPath:
         return feats
 
     def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
-               reverb=None, speed=None):
+               reverb=None, speed=None, mask=None):
         """Issue one step on the next stream of the rotation.  `audio`: (B, n_samples) float32 -- device tensor,
         or pinned/pageable host tensor / NumPy array, uploaded on the step's own stream.  Returns (features
         (B, n_keys*N_out) device tensor, stream it is produced on); the caller waits (`stream.synchronize()`,
@@ -195,6 +195,10 @@ class HotPath:
         stream ahead of the mixer's, into a buffer the rotation slot owns.
         `speed`: a `frontend.SpeedPlan` of this step's B clips (needs the pipeline's `speed`): one more launch on the same
         stream ahead of the reverberator's, into a buffer the rotation slot owns.
+        `mask`: a `frontend.MaskPlan` of this step's B clips (SPEC.md §1.13): the step's front end is the masked entry point
+        -- the mask acts inside the encoder, behind every corruption of the audio -- and still writes into the pipeline's
+        raster rings; the words are uploaded on the front end's stream, no host synchronisation.  A step without it launches
+        what it always did.
         Back-pressure: when `max_ahead` earlier steps have not finished, submit() first waits for the oldest."""
         if mix is not None and (self.mixer is None or stage == "reservoir"):
             raise ValueError("submit(mix=...) needs a HotPath built with a mixer and a step that has a front end")
@@ -202,7 +206,11 @@ class HotPath:
             raise ValueError("submit(reverb=...) needs a HotPath built with a reverberator and a step that has a front end")
         if speed is not None and (self.speed is None or stage == "reservoir"):
             raise ValueError("submit(speed=...) needs a HotPath built with a speed perturber and a step that has a front end")
-        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix, reverb, speed)
+        if mask is not None:
+            if stage == "reservoir":
+                raise ValueError("submit(mask=...) needs a step that has a front end")
+            checked_mask(mask, len(audio), self.fe.n_filters, self.fe.time_bins)
+        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix, reverb, speed, mask)
         if st is not None and self.n_streams > 1:
             ev = torch.cuda.Event()
             ev.record(st)
@@ -210,7 +218,7 @@ class HotPath:
         return res, st
 
     def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
-                reverb=None, speed=None):
+                reverb=None, speed=None, mask=None):
         """submit() without the in-flight bookkeeping."""
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
@@ -224,7 +232,7 @@ class HotPath:
             topology = self._submit_two_stages
         else:
             topology = self._submit_rotation
-        return topology(slot, audio, stats_out, after, out, stage, tail, mix, reverb, speed)
+        return topology(slot, audio, stats_out, after, out, stage, tail, mix, reverb, speed, mask)
 
     def _wait_for_input(self, stream, cur, audio, after) -> None:
         """The ordering of a device input (`submit`): `stream` waits for `after`, or for what `cur` has issued so far."""
@@ -233,24 +241,27 @@ class HotPath:
         elif torch.is_tensor(audio) and audio.device == self.device:
             stream.wait_stream(cur)
 
-    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None):
+    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None,
+                       mask=None):
         """Everything on the current stream."""
         cur = torch.cuda.current_stream(self.device)
         if after is not None:
             cur.wait_event(after)
         with torch.cuda.device(self.device):
             x = audio if stage == "reservoir" else self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
-            return self._one(x, stats_out, out, stage, tail), cur
+            return self._one(x, stats_out, out, stage, tail, mask), cur
 
-    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None):
+    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None,
+                         mask=None):
         """The step keeps to reservoir stream `slot`: its front end, then its reservoir launch."""
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             self._wait_for_input(st, cur, audio, after)
             x = audio if stage == "reservoir" else self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
-            return self._one(x, stats_out, out, stage, tail), st
+            return self._one(x, stats_out, out, stage, tail, mask), st
 
-    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None):
+    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None,
+                           mask=None):
         """The front end on the next front-end stream, the reservoir launch on reservoir stream `slot` behind an event."""
         fslot = (self._step - 1) % self.n_fe_streams
         st, fst, cur = self.streams[slot], self.fe_streams[fslot], torch.cuda.current_stream(self.device)
@@ -272,6 +283,8 @@ class HotPath:
                 # `share_lds` stays off: beside the ring-row kernel at 4000 neurons (64 KB of LDS per clip, two per CU)
                 # the whole path runs 6.37-6.40 ms per step without the front end's LDS reservation against 6.26-6.28
                 # with it (profiles/r04_cfg4_frontend_lds_placement.txt)
+                if mask is not None:
+                    owned["mask"] = mask
                 rasters = self.fe.encode(x, low_latency=low_latency, **owned)
                 done = torch.cuda.Event()
                 done.record(fst)
@@ -393,11 +406,12 @@ class HotPath:
         torch.cuda.current_stream(self.device).synchronize()
 
     # ---- many steps -------------------------------------------------------------------------
-    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None, reverbs=None, speeds=None) -> torch.Tensor:
+    def run(self, audio_batches, out: torch.Tensor | None = None, mixes=None, reverbs=None, speeds=None,
+            masks=None) -> torch.Tensor:
         """Feature rows of every batch, in order, as one (n_clips, n_feat) device tensor.  `audio_batches`
         is an iterable of (B_i, n_samples) arrays/tensors (host or device); `mixes`, when given, an iterable of one
         `frontend.MixPlan` per batch (`submit(mix=...)`); `reverbs` likewise one `frontend.ReverbPlan` per batch, `speeds` one
-        `frontend.SpeedPlan` per batch."""
+        `frontend.SpeedPlan` per batch, `masks` one `frontend.MaskPlan` per batch (`submit(mask=...)`)."""
         self.fork_from_current()
         # The last TAIL_STEPS batches are submitted in the low-latency layouts: that needs a look-ahead of TAIL_STEPS
         # batches, not the whole list -- a lazily produced stream of (pinned or device) batches is consumed as it comes and
@@ -407,15 +421,19 @@ class HotPath:
         plans = iter(mixes) if mixes is not None else None
         rooms = iter(reverbs) if reverbs is not None else None
         paces = iter(speeds) if speeds is not None else None
+        veils = iter(masks) if masks is not None else None
+
+        def step(a0, m0, r0, s0, k0, tail):
+            extra = {} if k0 is None else {"mask": k0}        # a step without a mask is submitted as it always was
+            return self.submit(a0, tail=tail, mix=m0, reverb=r0, speed=s0, **extra)[0]
+
         for a in it:
             ahead.append((a, next(plans) if plans is not None else None, next(rooms) if rooms is not None else None,
-                          next(paces) if paces is not None else None))
+                          next(paces) if paces is not None else None, next(veils) if veils is not None else None))
             if len(ahead) > TAIL_STEPS:
-                a0, m0, r0, s0 = ahead.popleft()
-                parts.append(self.submit(a0, tail=False, mix=m0, reverb=r0, speed=s0)[0])
+                parts.append(step(*ahead.popleft(), False))
         while ahead:
-            a0, m0, r0, s0 = ahead.popleft()
-            parts.append(self.submit(a0, tail=True, mix=m0, reverb=r0, speed=s0)[0])
+            parts.append(step(*ahead.popleft(), True))
         self.synchronize()
         if not parts:
             n_keys = len(self.feature_keys) if self.feature_keys is not None else 8
@@ -429,7 +447,7 @@ class HotPath:
 
 def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1024,
                         streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1, corrupt=None,
-                        reverb=None, speed=None):
+                        reverb=None, speed=None, mask=None):
     """Host convenience for the drop-in scripts' in-memory path: (n, n_samples) float32 on the host ->
     (n, n_feat) float32 on the host (or, `device_out`, still on the GPU for a gather), batches of `batch` clips
     through the overlapped pipeline (pinned staging, uploads on the steps' streams).  n = 0 (an empty shard)
@@ -438,7 +456,10 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     the device with its slice of the plan before its front end (SPEC.md §1.10).  `reverb` = ``(frontend.Reverberator,
     frontend.ReverbPlan of the n clips)``: every batch is convolved with its rooms ahead of that (SPEC.md §1.11).  `speed` =
     ``(frontend.SpeedPerturber, frontend.SpeedPlan of the n clips)``: every batch is played at its clips' speeds ahead of
-    both (SPEC.md §1.12)."""
+    both (SPEC.md §1.12).  `mask` = a ``frontend.MaskPlan`` of the n clips: every batch's front end masks its slice of the
+    plan inside the encoder (SPEC.md §1.13)."""
+    if mask is not None and not (len(mask.freq) == len(mask.time) == len(audio)):
+        raise ValueError(f"the mask plan covers {len(mask.freq)} / {len(mask.time)} clips, audio has {len(audio)}")
     sp, paces = speed if speed is not None else (None, None)
     if paces is not None and len(paces.choice) != len(audio):
         raise ValueError(f"the speed plan covers {len(paces.choice)} clips, audio has {len(audio)}")
@@ -459,7 +480,9 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
         feats = hp.run((pinned[lo:lo + batch] for lo in range(0, len(pinned), batch)),
                        mixes=(plan.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if plan is not None else None,
                        reverbs=(rooms.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if rooms is not None else None,
-                       speeds=(paces.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if paces is not None else None)
+                       speeds=(paces.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if paces is not None else None,
+                       **({} if mask is None else
+                          {"masks": (mask.part(lo, lo + batch) for lo in range(0, len(pinned), batch))}))
     return feats if device_out else feats.cpu().numpy()
 
 

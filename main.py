@@ -58,6 +58,15 @@ def _speed_args(a):
     return out if _augment_args(a) or _reverb_args(a) else out + ["--augment-seed", str(a.augment_seed)]
 
 
+def _mask_args(a):
+    """Nothing unless a kind of mask has a count and a width; the seed goes along unless other flags already carry it."""
+    if not (a.freq_masks and a.freq_mask_width) and not (a.time_masks and a.time_mask_width):
+        return []
+    out = ["--freq-masks", str(a.freq_masks), "--freq-mask-width", str(a.freq_mask_width), "--time-masks", str(a.time_masks),
+           "--time-mask-width", str(a.time_mask_width), "--mask-prob", str(a.mask_prob)]
+    return out if _augment_args(a) or _reverb_args(a) or _speed_args(a) else out + ["--augment-seed", str(a.augment_seed)]
+
+
 def _reservoir_args(a):
     out = []
     for flag, v in (("--num-neurons", a.num_neurons), ("--num-output-neurons", a.num_output_neurons),
@@ -71,7 +80,7 @@ STAGES = (
     ("Step 1: Creating Spike Train Dataset",
      lambda a: ["create_dataset.py", "--n-filters", str(a.n_filters), "--filterbank", a.filterbank]
      + _corpus_args(a) + (["--packed"] if a.packed else []) + _augment_args(a) + _reverb_args(a)
-     + _speed_args(a)),
+     + _speed_args(a) + _mask_args(a)),
     ("Step 2: Extracting LSM Features",
      lambda a: ["extract_lsm_features.py", "--feature-set", a.feature_set, "--multiplier", str(a.multiplier)]
      + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])),
@@ -96,7 +105,7 @@ ex.main_from_audio(audio, labels, a.n_filters, a.filterbank, a.feature_set, a.mu
                    num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons,
                    small_world_k=a.small_world_k, seed=a.seed, readout=a.device_readout,
                    class_names=cd.commands_from_args(a), time_segments=a.time_segments, corrupt=corrupt, reverb=reverb,
-                   speed=speed)
+                   speed=speed, **({{}} if cd.mask_from_args(a) is None else {{"mask": cd.mask_from_args(a)}}))
 """
 
 
@@ -120,14 +129,16 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     `extra`: the forwarded constants (commands, commands_file, dataset_root, max_per_class, synthetic_per_class,
     packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc, time_segments, and the corruption flags
     noise_dir, snr_db, time_shift_ms, level_db, augment_seed, the reverberation flags rir_dir, rir_prob, rir_max_ms and the
-    speed flags speed_factors, speed_prob: applied to stage 1 and to the in-memory route)."""
+    speed flags speed_factors, speed_prob and the mask flags freq_masks, freq_mask_width, time_masks, time_mask_width,
+    mask_prob: applied to stage 1 and to the in-memory route)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
                               packed=False, num_neurons=None, num_output_neurons=None, small_world_k=None, seed=None,
                               readout=None, nproc=1, time_segments=1, noise_dir=None, snr_db=None, time_shift_ms=0.0,
                               level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0,
-                              speed_factors=None, speed_prob=1.0)
+                              speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
+                              time_mask_width=0, mask_prob=1.0)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -205,6 +216,11 @@ if __name__ == "__main__":
     ap.add_argument("--speed-factors", type=str, default=None,
                     help="Comma-separated playback speeds drawn per clip on the GPU, e.g. 0.9,1.0,1.1 (stage 1).")
     ap.add_argument("--speed-prob", type=float, default=1.0, help="Share of the clips whose speed is drawn (stage 1).")
+    ap.add_argument("--freq-masks", type=int, default=0, help="Frequency bands zeroed per clip inside the encoder (stage 1).")
+    ap.add_argument("--freq-mask-width", type=int, default=0, help="Largest width of a frequency band, in filters (stage 1).")
+    ap.add_argument("--time-masks", type=int, default=0, help="Time spans zeroed per clip inside the encoder (stage 1).")
+    ap.add_argument("--time-mask-width", type=int, default=0, help="Largest width of a time span, in time bins (stage 1).")
+    ap.add_argument("--mask-prob", type=float, default=1.0, help="Share of the clips that are masked (stage 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
@@ -214,4 +230,5 @@ if __name__ == "__main__":
                  readout=a.readout, nproc=a.nproc, time_segments=a.time_segments, noise_dir=a.noise_dir, snr_db=a.snr_db,
                  time_shift_ms=a.time_shift_ms, level_db=a.level_db, augment_seed=a.augment_seed,
                  rir_dir=a.rir_dir, rir_prob=a.rir_prob, rir_max_ms=a.rir_max_ms, speed_factors=a.speed_factors,
-                 speed_prob=a.speed_prob)
+                 speed_prob=a.speed_prob, freq_masks=a.freq_masks, freq_mask_width=a.freq_mask_width,
+                 time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob)
