@@ -309,6 +309,89 @@ def collect_audio(commands=None, dataset_root=None, max_per_class: int = MAX_SAM
     return np.stack(clips).astype(np.float32, copy=False), np.asarray(labels, dtype=np.int32)
 
 
+# ---- utterances of their own lengths (SPEC.md 1.14): --variable-length, --max-seconds ----------------------------------------
+BINS_PER_SECOND = 100        # one time bin per 160 samples, the reference's TIME_BINS / DURATION
+MIN_UTTERANCE_SAMPLES = 321  # three time bins: the shortest clip the ragged front end takes
+
+
+def load_utterance_file(filepath: Path, max_seconds: float = DURATION):
+    """One wav file as mono float32 at 16 kHz at its OWN length: not padded to a second, trimmed at ``max_seconds``, and
+    zero-padded only where it is shorter than three time bins; None (with a message) when the file cannot be read."""
+    try:
+        rate, data = _decode_wav(filepath)
+        if rate != SAMPLE_RATE:
+            from math import gcd
+            from scipy.signal import resample_poly
+            g = gcd(int(rate), SAMPLE_RATE)
+            data = resample_poly(data, SAMPLE_RATE // g, int(rate) // g).astype(np.float32)
+        data = np.ascontiguousarray(data[:max_bins_of(max_seconds) * (SAMPLE_RATE // BINS_PER_SECOND)], dtype=np.float32)
+        if len(data) < MIN_UTTERANCE_SAMPLES:
+            data = np.pad(data, (0, MIN_UTTERANCE_SAMPLES - len(data)))
+        return data
+    except Exception as exc:
+        print(f"Error loading {filepath}: {exc}")
+        return None
+
+
+def max_bins_of(max_seconds: float) -> int:
+    bins = int(round(float(max_seconds) * BINS_PER_SECOND))
+    if bins < 3:
+        raise SystemExit(f"--max-seconds {max_seconds}: a clip has at least 3 time bins of 10 ms")
+    return bins
+
+
+def _synthetic_utterances(commands, per_class: int, max_bins: int):
+    """The synthetic corpus cut to seeded lengths between 0.3 and 1.0 of the longest clip (one second at most)."""
+    clips, labels = _synthetic_audio(commands, per_class)
+    hop = SAMPLE_RATE // BINS_PER_SECOND
+    top = min(max_bins * hop, int(SAMPLE_RATE * DURATION))
+    lengths = np.random.RandomState(4321).randint(max(MIN_UTTERANCE_SAMPLES, int(0.3 * top)), top + 1, size=len(clips))
+    return [np.ascontiguousarray(c[:n]) for c, n in zip(clips, lengths)], labels
+
+
+def create_variable_length_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
+                                   max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
+                                   output_file: str = OUTPUT_FILE, max_seconds: float = DURATION):
+    """File 1 with every clip at its own length (`--variable-length`, SPEC.md 1.14): the wav files are not padded to one
+    second, only trimmed at ``max_seconds``, and go through the ragged front end (`SpikeFrontEnd.encode_ragged`) in batches,
+    longest first.  ``X_spikes`` keeps its schema at the stride ``100 * max_seconds * n_thr`` steps -- clip r's rows hold its
+    ``n_steps[r]`` steps and zeros behind them -- and the file gains the key ``n_steps`` (n,) int32, which
+    extract_lsm_features.py hands to the reservoir as the clips' lengths.  One process, no augmentation chain."""
+    from lsm_speech_classifier_amd import spikefile
+    commands = list(COMMANDS if commands is None else commands)
+    root = Path(DATASET_ROOT if dataset_root is None else dataset_root)
+    max_bins = max_bins_of(max_seconds)
+    print(f"Creating variable-length dataset with filterbank: {filterbank}, filters: {n_filters}, up to {max_bins} time bins")
+    if synthetic_per_class > 0:
+        clips, labels = _synthetic_utterances(commands, synthetic_per_class, max_bins)
+    else:
+        clips, labels = [], []
+        for f, label in _list_files(commands, root, max_per_class):
+            audio = load_utterance_file(f, max_seconds)
+            if audio is not None:
+                clips.append(audio)
+                labels.append(label)
+    if not clips:
+        print("\nERROR: No audio files were successfully processed.")
+        return
+    fr = _frontend()
+    fe = fr.SpikeFrontEnd(n_filters, filterbank, redundancy=REDUNDANCY_FACTOR, thresholds=SPIKE_THRESHOLDS,
+                          gap=HYSTERESIS_GAP, time_bins=max_bins, n_samples=max_bins * fr.RAGGED_HOP)
+    audio, bins = fr.pack_utterances(clips, max_bins)
+    X = np.zeros((len(clips), fe.n_channels, fe.n_steps), dtype=np.uint8)
+    order = np.argsort(-bins.astype(np.int64), kind="stable")
+    for a in range(0, len(order), ENCODE_BATCH):
+        idx = order[a:a + ENCODE_BATCH]
+        raster, _ = fe.encode_ragged(audio[idx], bins[idx])
+        X[idx] = raster.cpu().numpy()
+    n_steps = (bins.astype(np.int64) * len(SPIKE_THRESHOLDS)).astype(np.int32)
+    print("\nDataset created successfully.")
+    print(f"  Shape: {X.shape}, clips of {int(n_steps.min())} to {int(n_steps.max())} steps")
+    print(f"  Avg spikes per sample: {int(X.sum(dtype=np.int64)) / len(X):.1f}")
+    spikefile.save(output_file, X_spikes=X, y_labels=np.asarray(labels, dtype=np.int32), n_steps=n_steps)
+    print(f"Saved to '{output_file}'")
+
+
 def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
                    output_file: str = OUTPUT_FILE, packed: bool = False, resample: str = "host", augment=None,
@@ -550,6 +633,28 @@ def speed_from_args(a):
     return dict(factors=factors, prob=float(a.speed_prob), seed=int(a.augment_seed))
 
 
+def add_variable_length_flags(ap):
+    """The variable-length flags (shared with main.py, which forwards them).  Without --variable-length nothing changes."""
+    ap.add_argument("--variable-length", action="store_true",
+                    help="Keep every clip at its own length (ragged front end) instead of padding it to one second; File 1 "
+                         "gains the key n_steps.")
+    ap.add_argument("--max-seconds", type=float, default=DURATION,
+                    help=f"With --variable-length: trim clips at this many seconds (default {DURATION:g}); sets the row stride.")
+
+
+def check_variable_length_args(a):
+    """--variable-length is a route of its own: refuse the flags it does not take instead of ignoring them."""
+    max_bins_of(a.max_seconds)
+    taken = [flag for flag, on in (("--packed", getattr(a, "packed", False)), ("--resample device", getattr(a, "resample", "host") == "device"),
+                                   ("the corruption flags", augment_from_args(a) is not None),
+                                   ("--rir-dir", reverb_from_args(a) is not None), ("--speed-factors", a.speed_factors is not None),
+                                   ("the mask flags", mask_from_args(a) is not None)) if on]
+    if taken:
+        raise SystemExit(f"--variable-length does not combine with {', '.join(taken)}")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--variable-length runs in one process")
+
+
 def commands_from_args(a):
     if a.commands_file:
         return read_commands_file(a.commands_file)
@@ -574,7 +679,14 @@ if __name__ == "__main__":
     add_reverb_flags(ap)
     add_speed_flags(ap)
     add_mask_flags(ap)
+    add_variable_length_flags(ap)
     a = ap.parse_args()
+    if a.variable_length:
+        check_variable_length_args(a)
+        create_variable_length_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
+                                       dataset_root=a.dataset_root, max_per_class=a.max_per_class,
+                                       synthetic_per_class=a.synthetic_per_class, max_seconds=a.max_seconds)
+        raise SystemExit(0)
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,
                    synthetic_per_class=a.synthetic_per_class, packed=a.packed, resample=a.resample,

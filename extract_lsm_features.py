@@ -143,6 +143,32 @@ def extract_all_features(lsm, spike_data, feature_keys, desc=""):
     return np.array(rows)
 
 
+def clip_views(spike_data, n_steps):
+    """The clips of a variable-length File 1 (SPEC.md 1.14) as per-clip views ``X[b][:, :n_steps[b]]``: what
+    `calculate_theoretical_w_critico`, which sums per-sample shapes, takes in place of the (n, C, T) array."""
+    return [clip[:, :int(t)] for clip, t in zip(spike_data, n_steps)]
+
+
+def extract_all_ragged_features(lsm, spike_data, n_steps, feature_keys, desc=""):
+    """`extract_all_features` for a variable-length File 1: clip b runs its own ``n_steps[b]`` steps of the (n, C, T) rows
+    (``SNN.run_batch(lengths=...)``, SPEC.md 4c; in chunks where T exceeds one launch).  One process."""
+    import torch
+    n = len(spike_data)
+    n_steps = np.asarray(n_steps, dtype=np.int64)
+    if n_steps.shape != (n,):
+        raise ValueError(f"n_steps must hold one value per clip, got {n_steps.shape} for {n} clips")
+    if desc:
+        print(f"{desc}: {n} clips of {int(n_steps.min()) if n else 0} to {int(n_steps.max()) if n else 0} steps")
+    rows = []
+    for a in range(0, n, RUN_BATCH):
+        batch = np.ascontiguousarray(spike_data[a:a + RUN_BATCH])
+        chunked = batch.shape[2] > lsm.max_steps(len(batch))
+        feats, _, _ = (lsm.run_chunked if chunked else lsm.run_batch)(batch, feature_keys, lengths=n_steps[a:a + RUN_BATCH])
+        rows.append(feats)
+    local = torch.cat(rows) if rows else lsm.run_batch(np.ascontiguousarray(spike_data[:0]), feature_keys)[0]
+    return local.cpu().numpy()
+
+
 def extract_all_segment_features(lsm, spike_data, feature_keys, desc="", time_segments=1):
     """extract_all_features per time segment: every clip is read in K = ``time_segments`` equal segments
     (``SNN.run_segments``, SPEC.md 4b) and its row is the K segment rows side by side -- (n, K * len(keys) * N_out),
@@ -372,14 +398,24 @@ def main(feature_set: str, multiplier: float, leak_variance_divisor: float = Non
     if X_spikes is None:
         lsm_dist.finish()                     # every rank took this branch (same file system): leave the group together
         return
-    X_train, X_test, y_train, y_test = train_test_split(
-        X_spikes, y_labels, test_size=0.2, random_state=42, stratify=y_labels)
+    from lsm_speech_classifier_amd import spikefile
+    n_steps = spikefile.load_steps(DATASET_FILE)          # a variable-length File 1 (SPEC.md 1.14), else None
+    steps_train = steps_test = None
+    if n_steps is not None:
+        if world > 1 or time_segments != 1:
+            raise SystemExit("a variable-length dataset (key n_steps) runs in one process and without --time-segments")
+        X_train, X_test, y_train, y_test, steps_train, steps_test = train_test_split(
+            X_spikes, y_labels, n_steps, test_size=0.2, random_state=42, stratify=y_labels)
+    else:
+        X_train, X_test, y_train, y_test = train_test_split(
+            X_spikes, y_labels, test_size=0.2, random_state=42, stratify=y_labels)
     if time_segments != 1:
         check_time_segments(np.asarray(X_train[0]).shape[1], time_segments)      # refused before the reservoir is built
 
     params = _simulation_params(X_train[0], leak_variance_divisor, num_neurons, num_output_neurons, small_world_k, seed)
     with _rank0_only(rank):
-        optimal_weight = calculate_theoretical_w_critico(params, X_train) * multiplier
+        optimal_weight = calculate_theoretical_w_critico(
+            params, X_train if steps_train is None else clip_views(X_train, steps_train)) * multiplier
         print(f"Using weight: {optimal_weight:.8f} (multiplier: {multiplier:.2f})")
         if leak_variance_divisor:
             print(f"Using Heterogeneous Leak. Divisor: {leak_variance_divisor}")
@@ -394,7 +430,10 @@ def main(feature_set: str, multiplier: float, leak_variance_divisor: float = Non
     keys = FEATURE_SETS[feature_set]
     if rank == 0:
         print(f"Extracting feature set: '{feature_set}'")
-    if time_segments == 1:
+    if steps_train is not None:
+        X_train_feat = extract_all_ragged_features(lsm, X_train, steps_train, keys, "Training")
+        X_test_feat = extract_all_ragged_features(lsm, X_test, steps_test, keys, "Testing")
+    elif time_segments == 1:
         X_train_feat = extract_all_features(lsm, X_train, keys, "Training")
         X_test_feat = extract_all_features(lsm, X_test, keys, "Testing")
     else:

@@ -163,6 +163,24 @@ MASK_SIGS = {
 MASK_SYMBOLS = tuple(MASK_SIGS)
 
 
+# include/lsm_hip_ragged.h (SPEC.md §1.14): the ragged front end -- each spike encoder its twin's list with the per-clip DEVICE
+# counts after time_bins (and clip_steps_out after the fused launch's raster)
+def _ragged_encoder(twin: str):
+    res, args = _SIGS[twin]
+    return res, args[:5] + [c_void, c_void] + args[5:]
+
+
+RAGGED_SIGS = {
+    "lsm_spec_to_spikes_ragged_f64": _ragged_encoder("lsm_spec_to_spikes_f64"),
+    "lsm_spec_to_spikes_ragged_f32": _ragged_encoder("lsm_spec_to_spikes_f32"),
+    "lsm_power_to_db_ragged_f32": (c_int, [c_void, c_int, c_int, c_int, c_void, c_float, c_float, c_void, c_void]),
+    "lsm_gammatone_spikes_ragged_f64": (c_int, _SIGS["lsm_gammatone_spikes_f64"][1][:9] + [c_void]
+                                        + _SIGS["lsm_gammatone_spikes_f64"][1][9:14] + [c_void]
+                                        + _SIGS["lsm_gammatone_spikes_f64"][1][14:]),
+}
+RAGGED_SYMBOLS = tuple(RAGGED_SIGS)
+
+
 class LsmHipError(RuntimeError):
     pass
 
@@ -212,7 +230,7 @@ def load():
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
-                              + list(MASK_SIGS.items())):
+                              + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

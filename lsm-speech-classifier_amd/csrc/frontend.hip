@@ -192,11 +192,25 @@ int check_masks(const uint32_t *freq_mask, const uint32_t *time_mask)
     return LSM_OK;
 }
 
+// The ragged entry points' own refusals, after their twins' (include/lsm_hip_ragged.h): the count arrays, then the strides
+int check_ragged(const void *counts_a, const void *counts_b, int time_bins, long n_samples, long hop)
+{
+    LSM_REQUIRE(counts_a != nullptr && counts_b != nullptr, "ragged: null per-clip count array");
+    LSM_REQUIRE((((uintptr_t)counts_a | (uintptr_t)counts_b) & 3u) == 0, "ragged: per-clip count arrays must be 4-byte aligned");
+    LSM_REQUIRE(time_bins >= 3, "ragged: time_bins=%d, a clip has at least 3 time bins", time_bins);
+    LSM_REQUIRE(n_samples >= hop * time_bins, "ragged: rows of %ld samples, need hop * time_bins = %ld", n_samples,
+                hop * time_bins);
+    return LSM_OK;
+}
+
+// `ragged`: the launch of lsm_spec_to_spikes_ragged_* (SPEC.md 1.14), ncols and time_bins the strides, clip_cols / clip_bins
+// the DEVICE counts
 template <typename T>
 int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, int time_bins,
                           int apply_floor, const T *thr_on, const T *thr_off, int n_thr,
                           int redundancy, uint8_t *raster, T *norm_out, void *stream,
-                          const uint32_t *freq_mask = nullptr, const uint32_t *time_mask = nullptr)
+                          const uint32_t *freq_mask = nullptr, const uint32_t *time_mask = nullptr,
+                          bool ragged = false, const int32_t *clip_cols = nullptr, const int32_t *clip_bins = nullptr)
 {
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && ncols >= 2 && time_bins >= 2, "bad shape");
     LSM_REQUIRE(db != nullptr || n_clips == 0, "spec_to_spikes: null input");
@@ -215,6 +229,12 @@ int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, in
     if (const int rc = check_masks(freq_mask, time_mask)) return rc;
     if (freq_mask || time_mask) {                       // SPEC.md 1.13; without a mask the launch below is the twin's
         lsm_fe::launch_spec_to_spikes_masked<T>(a, lsm_fe::MaskArgs{freq_mask, time_mask}, SPK_THREADS, lds, stream);
+        LSM_CHECK_HIP(hipGetLastError());
+        return LSM_OK;
+    }
+    if (ragged) {                                       // SPEC.md 1.14
+        if (const int rc = check_ragged(clip_cols, clip_bins, time_bins, 0, 0)) return rc;
+        lsm_fe::launch_spec_to_spikes_ragged<T>(a, lsm_fe::RaggedCounts{clip_cols, clip_bins}, SPK_THREADS, lds, stream);
         LSM_CHECK_HIP(hipGetLastError());
         return LSM_OK;
     }
@@ -451,7 +471,8 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
                             int time_bins, const double *thr_on, const double *thr_off, int n_thr,
                             int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
                             int coef_flags, int launch_flags, const uint32_t *freq_mask, const uint32_t *time_mask,
-                            void *stream)
+                            void *stream, bool ragged = false, const int32_t *clip_bins = nullptr,
+                            int32_t *clip_steps_out = nullptr)
 {
     LSM_REQUIRE((launch_flags & ~3) == 0, "launch_flags: only bit 0 (low-latency layout) and bit 1 (no LDS reservation) are defined");
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && n_samples >= 1, "bad shape");
@@ -511,6 +532,14 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
         LSM_CHECK_HIP(hipGetLastError());
         return LSM_OK;
     }
+    if (ragged) {                                       // SPEC.md 1.14: ncols and time_bins are strides, n_samples the row's
+        if (const int rc = check_ragged(clip_bins, clip_bins, time_bins, n_samples, hop)) return rc;
+        LSM_REQUIRE(((uintptr_t)clip_steps_out & 3u) == 0, "ragged: clip_steps_out must be 4-byte aligned");
+        const lsm_fe::FusedLaunch l{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
+        lsm_fe::launch_gammatone_spikes_ragged(l, &a, lsm_fe::RaggedArgs{clip_bins, clip_steps_out}, stream);
+        LSM_CHECK_HIP(hipGetLastError());
+        return LSM_OK;
+    }
     auto launch = [&](auto nw_c, auto fast_c, auto nch_c, auto shb0_c, auto pair_c) {
         auto fn = gammatone_spikes_kernel<decltype(nw_c)::value, decltype(fast_c)::value, decltype(nch_c)::value,
                                           decltype(shb0_c)::value, decltype(pair_c)::value>;
@@ -561,6 +590,37 @@ LSM_API int lsm_gammatone_spikes_masked_f64(const float *audio, int n_clips, int
     return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
                             redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, freq_mask, time_mask,
                             stream);
+}
+
+// include/lsm_hip_ragged.h (SPEC.md 1.14): the twins' parameters with per-clip DEVICE counts; kernels in ragged_frontend.hip
+LSM_API int lsm_gammatone_spikes_ragged_f64(const float *audio, int n_clips, int n_samples,
+                                            const double *coefs, int n_filters, int nwin, int hop, int ncols,
+                                            int time_bins, const int32_t *clip_bins, const double *thr_on,
+                                            const double *thr_off, int n_thr, int redundancy, uint8_t *raster,
+                                            int32_t *clip_steps_out, void *workspace, long workspace_bytes,
+                                            int coef_flags, int launch_flags, void *stream)
+{
+    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                            redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, nullptr, nullptr, stream,
+                            true, clip_bins, clip_steps_out);
+}
+
+LSM_API int lsm_spec_to_spikes_ragged_f64(const double *db, int n_clips, int n_filters, int ncols, int time_bins,
+                                          const int32_t *clip_cols, const int32_t *clip_bins, int apply_floor,
+                                          const double *thr_on, const double *thr_off, int n_thr, int redundancy,
+                                          uint8_t *raster, double *norm_out, void *stream)
+{
+    return launch_spec_to_spikes<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                         redundancy, raster, norm_out, stream, nullptr, nullptr, true, clip_cols, clip_bins);
+}
+
+LSM_API int lsm_spec_to_spikes_ragged_f32(const float *db, int n_clips, int n_filters, int ncols, int time_bins,
+                                          const int32_t *clip_cols, const int32_t *clip_bins, int apply_floor,
+                                          const float *thr_on, const float *thr_off, int n_thr, int redundancy,
+                                          uint8_t *raster, float *norm_out, void *stream)
+{
+    return launch_spec_to_spikes<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                        redundancy, raster, norm_out, stream, nullptr, nullptr, true, clip_cols, clip_bins);
 }
 
 LSM_API int lsm_spec_to_spikes_masked_f64(const double *db, int n_clips, int n_filters, int ncols,

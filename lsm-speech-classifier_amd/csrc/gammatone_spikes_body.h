@@ -77,10 +77,12 @@ __device__ __forceinline__ double uniform_f64(double v)
 #define LSM_FUSED_KERNEL gammatone_spikes_kernel
 #define LSM_FUSED_PARAMS const FusedArgs a
 #define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
+#define LSM_FUSED_RAGGED constexpr bool RAGGED = false; const lsm_fe::RaggedArgs rg{nullptr, nullptr};
 #include "gammatone_spikes_kernel.inc"
 #undef LSM_FUSED_KERNEL
 #undef LSM_FUSED_PARAMS
 #undef LSM_FUSED_MASK
+#undef LSM_FUSED_RAGGED
 
 }  // namespace
 
@@ -99,5 +101,10 @@ struct FusedLaunch {
 void launch_gammatone_spikes_masked(const FusedLaunch &l, const void *fused_args, const MaskArgs &m, void *stream);
 template <typename T>
 void launch_spec_to_spikes_masked(const SpikeArgs<T> &a, const MaskArgs &m, int threads, size_t lds, void *stream);
+
+// The ragged twins (SPEC.md 1.14), defined in ragged_frontend.hip, likewise a translation unit of its own
+void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args, const RaggedArgs &rg, void *stream);
+template <typename T>
+void launch_spec_to_spikes_ragged(const SpikeArgs<T> &a, const RaggedCounts &rc, int threads, size_t lds, void *stream);
 
 }  // namespace lsm_fe

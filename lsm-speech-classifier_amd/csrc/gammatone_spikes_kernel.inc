@@ -1,7 +1,8 @@
 // gammatone_spikes_kernel.inc -- the text of the fused gammatone kernel, included once per form: the includer defines the
 // kernel's name (LSM_FUSED_KERNEL), its parameters (LSM_FUSED_PARAMS) and MASK (LSM_FUSED_MASK) -- gammatone_spikes_body.h
-// for gammatone_spikes_kernel(const FusedArgs a), mask.hip for gammatone_spikes_masked_kernel(a, const lsm_fe::MaskArgs m).
-// One text, two kernels -- and not one device function called by two kernels: behind a call, even a forced-inline one, the
+// for gammatone_spikes_kernel(const FusedArgs a), mask.hip for gammatone_spikes_masked_kernel(a, const lsm_fe::MaskArgs m) --
+// and RAGGED (LSM_FUSED_RAGGED): ragged_frontend.hip for gammatone_spikes_ragged_kernel(a, const lsm_fe::RaggedArgs rg).
+// One text, three kernels -- and not one device function called by three kernels: behind a call, even a forced-inline one, the
 // compiler allocated and scheduled 32 of the unmasked kernel's 34 forms differently (profiles/spec_mask.txt), and those
 // forms are measured code.
 //
@@ -12,10 +13,18 @@
 // MASK (SPEC.md 1.13): `m` holds the batch's frequency and time mask words; a masked value becomes +0.0 in the epilogue,
 // where the zero bin's does.  A lane is a channel there, so its row bit is loaded once; the bin loop is uniform, so a
 // group's time bits are one scalar word.  With MASK = false `m` is a dead local and the code is the unmasked kernel's.
+//
+// RAGGED (SPEC.md 1.14, LSM_FUSED_RAGGED, ragged_frontend.hip): clip b has its own number of time bins, rg.clip_bins[b],
+// clamped here into 0 or 3..time_bins.  Everything that says how much of the clip there is -- the samples filtered (n_end),
+// its columns `nc`, its bins `Tb` and with them zf, jz and the row's bit count -- comes from that count, a wave-uniform scalar
+// loaded once; everything that says where the clip lies -- the audio row, the scratch, the LDS stage and the raster row --
+// keeps the launch's strides a.ncols and a.time_bins.  A clip of 0 bins filters nothing and encodes nothing, reaches every
+// barrier and writes zero rows.  With RAGGED = false `nc` is a.ncols, `Tb` is a.time_bins and the code is the twin's.
 template <int NW, bool FAST, int NCH, bool SHB0 = false, bool PAIR = false>
 __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PARAMS)
 {
     LSM_FUSED_MASK                                      // constexpr bool MASK, and `m` where it is no parameter
+    LSM_FUSED_RAGGED                                    // constexpr bool RAGGED (`rg` is a parameter where it is true)
     static_assert(!PAIR || NCH == 1, "the lane pair carries one chain per lane pair");
     constexpr int CPW = PAIR ? 32 : 64;                                   // channels of a chain group (of a wave)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -31,6 +40,16 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
     const int b = valid ? b_raw : a.n_clips - 1;
     const int g = wid - b_raw * groups;
     const int F = a.n_filters, nwin = a.nwin, hop = a.hop, ncols = a.ncols, n_samples = a.n_samples;
+    // RAGGED: the clip's bins and columns (0, or 3..time_bins bins with at least one column: whatever the array holds)
+    int tb_clip = 0, nc_clip = 0;
+    if constexpr (RAGGED) {
+        const int t = min(max(__builtin_amdgcn_readfirstlane(rg.bins[b]), 0), a.time_bins);
+        nc_clip = t - (a.time_bins - ncols);
+        tb_clip = (t >= 3 && nc_clip >= 1) ? t : 0;
+        if (rg.steps_out != nullptr && valid && g == 0 && lane == 0) rg.steps_out[b] = tb_clip * a.n_thr;
+    }
+    const int nc = RAGGED ? nc_clip : ncols;                              // columns of this clip
+    const bool run = valid && (!RAGGED || tb_clip > 0);                   // this wave filters and encodes
     const int NG = groups * NCH;                                          // chain groups per clip (padded)
     const int cl = PAIR ? (lane & 31) : lane;                             // this lane's channel within its group
     const bool owner = !PAIR || lane >= 32;                               // the lane whose output is the channel's
@@ -156,9 +175,9 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
     if (a.prio == 1) __builtin_amdgcn_s_setprio(1);
     else if (a.prio == 2) __builtin_amdgcn_s_setprio(2);
     else if (a.prio == 3) __builtin_amdgcn_s_setprio(3);
-    if (valid) {
+    if (run) {
         const int pos = nwin - (NW - 1) * hop;
-        const int n_end = (ncols - 1) * hop + nwin;
+        const int n_end = (nc - 1) * hop + nwin;
         const double dn = (double)nwin;
         if (PAIR) {
             // the head's sample 0; the tail ran on a zero input, and its state restarts at +0 (all it held were
@@ -172,7 +191,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
             const int mid = min(base + pos, n_end);
             if (PAIR) LSM_RUNP(mid, NW) else LSM_RUNF(mid, NW)
             const int c = h - (NW - 1);
-            if (n == base + pos && c >= 0 && c < ncols) {
+            if (n == base + pos && c >= 0 && c < nc) {
 #pragma unroll
                 for (int q = 0; q < NCH; ++q) {
                     const double y = sqrt(win[q][NW - 1] / dn);
@@ -233,11 +252,11 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
     lo = lo > fl ? lo : fl;                             // (NaN: fl)
     const bool flat = (hi - lo) < 1e-8;
     const double den = (hi - lo) + 1e-8;
-    const int Tb = a.time_bins, n_thr = a.n_thr;
+    const int Tb = RAGGED ? tb_clip : a.time_bins, n_thr = a.n_thr;
     const int row_bits = Tb * n_thr;
-    const double zf = (double)(ncols - 1) / (double)(Tb - 1);
+    const double zf = (double)(nc - 1) / (double)(Tb - 1);
     // the bin whose coordinate lies outside the input and is +0.0 (spikes_body.h, SPEC.md 1.2): the last one or none (-1)
-    const int jz = (ncols != Tb && (double)(Tb - 1) * zf > (double)(ncols - 1)) ? Tb - 1 : -1;
+    const int jz = (nc != Tb && (double)(Tb - 1) * zf > (double)(nc - 1)) ? Tb - 1 : -1;
     // (x - lo) / den for 2 x 100 values per channel: den is wave-uniform, so its correctly rounded reciprocal is
     // computed once and every quotient is q = x*r, q' = fma(fma(-q, den, x), r, q) -- Markstein's sequence, the
     // correctly rounded quotient (= the IEEE division spec_to_spikes_kernel performs) unless den's significand is
@@ -259,7 +278,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
     const int FBH = n_thr <= 4 ? 4 : 8;                 // bits per half field
     const int JPW = 16 / FBH;                           // bins per 32-bit word (4 or 2)
     const int NG4 = (Tb + JPW - 1) / JPW;               // groups of JPW bins
-    const int RW = (row_bits + 31) >> 5;                // words per staged raster row
+    const int RW = ((RAGGED ? a.time_bins * n_thr : row_bits) + 31) >> 5;   // words per staged raster row (the launch's stride)
     uint32_t *stage = stage_all + (size_t)wave * (NCH * CPW) * RW;
     const size_t cs = (size_t)NG * CPW;                 // doubles between two columns of the scratch
     // MASK: this lane's row bits (a channel past the last filter has none: its word may not exist) and the clip's time words
@@ -308,7 +327,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
                 const int f = ZOOM ? (int)fc : j;
                 w0[u] = 1.0 - (cc - fc);
                 w1[u] = 1.0 - w0[u];
-                two[u] = f + 1 <= ncols - 1;
+                two[u] = f + 1 <= nc - 1;
                 const int f1 = two[u] ? f + 1 : f;
 #pragma unroll
                 for (int q = 0; q < NCH; ++q) {
@@ -380,12 +399,12 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
             for (int q = 0; q < NCH; ++q) if (owner) stage[(q * CPW + cl) * RW + wout] = (uint32_t)acc[q];
         }
     };
-    {
+    if (!RAGGED || Tb > 0) {                            // (a clip of 0 bins has no bin to encode; wave-uniform, no barrier inside)
         using T = std::true_type;
         using F = std::false_type;
         using N4 = std::integral_constant<int, 4>;
         using N8 = std::integral_constant<int, MAX_THR>;
-        const bool zoom = ncols != Tb;
+        const bool zoom = nc != Tb;
         if (n_thr <= 4) {
             if (fastdiv) { if (zoom) pass_a(T{}, N4{}, T{}); else pass_a(T{}, N4{}, F{}); }
             else         { if (zoom) pass_a(F{}, N4{}, T{}); else pass_a(F{}, N4{}, F{}); }
@@ -400,7 +419,9 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
         const int R = a.redundancy;
         const int fbase = g * NCH * CPW;
         const int rows_out = min(NCH * CPW, F - fbase) * R;
-        const int row_bytes = row_bits;
+        // RAGGED: a row keeps the launch's length; the clip owns its first row_bits bytes, the rest is written as 0 (the stage
+        // holds nothing of the clip past them)
+        const int row_bytes = RAGGED ? a.time_bins * n_thr : row_bits;
         uint8_t *dst = a.raster + ((size_t)b * F + fbase) * R * row_bytes;
         if ((row_bytes & 3) == 0) {
             const int rw = row_bytes >> 2;
@@ -408,14 +429,17 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
             for (int i = lane; i < rows_out * rw; i += 64) {
                 const int c = i / rw;
                 const int p = (i - c * rw) * 4;
-                const uint32_t nib = (stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 0xFu;
+                uint32_t nib = (stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 0xFu;
+                if constexpr (RAGGED) nib &= (1u << min(max(row_bits - p, 0), 4)) - 1u;
                 d4[i] = (nib * 0x00204081u) & 0x01010101u;
             }
         } else {
             for (int i = lane; i < rows_out * row_bytes; i += 64) {
                 const int c = i / row_bytes;
                 const int p = i - c * row_bytes;
-                dst[i] = (uint8_t)((stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 1u);
+                uint32_t bit = (stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 1u;
+                if constexpr (RAGGED) bit = p < row_bits ? bit : 0u;
+                dst[i] = (uint8_t)bit;
             }
         }
     }

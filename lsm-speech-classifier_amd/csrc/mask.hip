@@ -20,10 +20,12 @@ __global__ __launch_bounds__(256) void spec_to_spikes_masked_kernel(const lsm_fe
 #define LSM_FUSED_KERNEL gammatone_spikes_masked_kernel
 #define LSM_FUSED_PARAMS const FusedArgs a, const lsm_fe::MaskArgs m
 #define LSM_FUSED_MASK constexpr bool MASK = true;
+#define LSM_FUSED_RAGGED constexpr bool RAGGED = false; const lsm_fe::RaggedArgs rg{nullptr, nullptr};
 #include "gammatone_spikes_kernel.inc"
 #undef LSM_FUSED_KERNEL
 #undef LSM_FUSED_PARAMS
 #undef LSM_FUSED_MASK
+#undef LSM_FUSED_RAGGED
 
 template <int N> using Int = std::integral_constant<int, N>;
 

@@ -28,6 +28,28 @@ struct MaskArgs {
     const uint32_t *time;   // (n_clips, ceil(time_bins / 32)) or null
 };
 
+// Per-clip lengths of a ragged batch (SPEC.md 1.14), the ragged kernels' argument beside their twins' own: DEVICE int32
+// arrays of n_clips entries that no host code reads; the kernels clamp what they find (clip_counts below, and the fused
+// kernel's own statement of it).
+struct RaggedCounts {       // the split encoder
+    const int *cols;        // dB columns of clip b
+    const int *bins;        // time bins of clip b
+};
+struct RaggedArgs {         // the fused gammatone kernel
+    const int *bins;        // time bins of clip b; its columns are bins - (time_bins - ncols)
+    int *steps_out;         // bins * n_thr per clip, or null
+};
+
+// A clip's counts as the ragged encoder uses them, whatever the arrays hold: bins 0 or 3..time_bins, columns 1..ncols; a clip
+// without a column or with fewer than 3 bins is empty (0 bins, 0 columns).
+__device__ __forceinline__ void clip_counts(const RaggedCounts &rc, int b, int ncols, int time_bins, int &nc, int &Tb)
+{
+    const int c = min(max(rc.cols[b], 0), ncols), t = min(max(rc.bins[b], 0), time_bins);
+    const bool live = c >= 1 && t >= 3;
+    nc = live ? c : 0;
+    Tb = live ? t : 0;
+}
+
 template <typename T>
 __device__ __forceinline__ T block_reduce(T v, bool is_max, T *scratch)
 {
@@ -66,27 +88,60 @@ __host__ __device__ inline size_t spikes_lds_bytes(int time_bins, int n_thr)
 //   3. the raster bytes, four per store, from the latch bits.
 // MASK (SPEC.md 1.13): a value whose row or time bin is masked becomes +0.0 where the zero bin's does, after maximum, floor,
 // minimum and resize.  The row is wave-uniform (its bit is a scalar), the 64 time bits of a piece are one 64-bit scalar.
-template <typename T, bool MASK = false>
+// RAGGED (SPEC.md 1.14): clip b has its own columns and bins (`rc`, clamped by clip_counts); a.ncols and a.time_bins are then
+// the strides of db, raster and norm_out -- and size the LDS -- while the minimum and maximum, zf, jz, the no-zoom case, the
+// flat test and a row's bit count are the clip's.  Past the clip's bins the raster rows and norm_out are written as 0.
+template <typename T, bool MASK = false, bool RAGGED = false>
 __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const int b, unsigned char *smem,
-                                                    const MaskArgs m = MaskArgs{nullptr, nullptr})
+                                                    const MaskArgs m = MaskArgs{nullptr, nullptr},
+                                                    const RaggedCounts rc = RaggedCounts{nullptr, nullptr})
 {
     T *scratch = reinterpret_cast<T *>(smem);                 // 16 entries: one per wave of up to 1024 threads
-    const int F = a.n_filters, nc = a.ncols, Tb = a.time_bins, nq = a.n_thr;
+    const int F = a.n_filters, ncs = a.ncols, Tbs = a.time_bins, nq = a.n_thr;      // ncs, Tbs: the launch's strides
+    int nc_clip = 0, tb_clip = 0;
+    if constexpr (RAGGED) clip_counts(rc, b, ncs, Tbs, nc_clip, tb_clip);
+    const int nc = RAGGED ? nc_clip : ncs, Tb = RAGGED ? tb_clip : Tbs;
     const int W = (Tb + 31) >> 5;                             // words of a bit row
     uint32_t *onb = reinterpret_cast<uint32_t *>(smem + 128); // [row in group][q][W]: above on[q]; then the latch state
     uint32_t *offb = onb + (size_t)SPK_ROWS * (nq > 0 ? nq : 1) * W;
-    const T *db = a.db + (size_t)b * F * nc;
+    const T *db = a.db + (size_t)b * F * ncs;
     const int n = F * nc;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nwv = (int)(blockDim.x >> 6);
 
+    if constexpr (RAGGED) {
+        const int rest = Tbs - Tb;                            // bins of a row the clip does not own
+        if (a.norm_out)
+            for (int i = tid; i < F * rest; i += blockDim.x) {
+                const int r = i / rest;
+                a.norm_out[((size_t)b * F + r) * Tbs + Tb + (i - r * rest)] = (T)0;
+            }
+        if (Tb == 0) {                                        // an empty clip: zero rows (uniform over the workgroup)
+            if (a.raster) {
+                const size_t nb = (size_t)F * a.redundancy * Tbs * nq;
+                for (size_t i = tid; i < nb; i += blockDim.x) a.raster[(size_t)b * nb + i] = 0;
+            }
+            return;
+        }
+    }
+
     T mx = -INFINITY, mn = INFINITY;
     int nan_seen = 0;
+    if constexpr (RAGGED) {
+        for (int i = tid; i < n; i += blockDim.x) {
+            const int r = i / nc;
+            const T v = db[(size_t)r * ncs + (i - r * nc)];
+            mx = v > mx ? v : mx;
+            mn = v < mn ? v : mn;
+            nan_seen |= v != v;
+        }
+    } else {
 #pragma unroll 8
-    for (int i = tid; i < n; i += blockDim.x) {
-        const T v = db[i];
-        mx = v > mx ? v : mx;
-        mn = v < mn ? v : mn;
-        nan_seen |= v != v;
+        for (int i = tid; i < n; i += blockDim.x) {
+            const T v = db[i];
+            mx = v > mx ? v : mx;
+            mn = v < mn ? v : mn;
+            nan_seen |= v != v;
+        }
     }
     mx = block_reduce(mx, true, scratch);
     mn = block_reduce(mn, false, scratch);
@@ -100,14 +155,15 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
     const T hi = mx;
     const bool flat = (hi - lo) < (T)1e-8;
     const T den = (hi - lo) + (T)1e-8;
-    const int row_bytes = Tb * nq;
+    const int row_bytes = Tb * nq;                            // the clip's bytes of a raster row
+    const int rbs = RAGGED ? Tbs * nq : row_bytes;            // the row's length in memory
     const double zf = (double)(nc - 1) / (double)(Tb - 1);
     // Where the last bin's coordinate (Tb-1)*zf rounds to a double ABOVE nc-1 it lies outside the input, and SciPy's constant
     // boundary mode answers cval = +0.0 for that bin, whatever the row holds (SPEC.md 1.2).  The overshoot is an ulp, so no
     // earlier bin has it: one uniform test per launch, jz = the bin that is zero (-1: none).
     const int jz = (nc != Tb && (double)(Tb - 1) * zf > (double)(nc - 1)) ? Tb - 1 : -1;
     const int C = F * a.redundancy;
-    uint8_t *dst = a.raster ? a.raster + (size_t)b * C * row_bytes : nullptr;
+    uint8_t *dst = a.raster ? a.raster + (size_t)b * C * rbs : nullptr;
     const uint32_t *fmc = nullptr, *tmc = nullptr;            // this clip's mask words
     if constexpr (MASK) {
         fmc = m.freq ? m.freq + (size_t)b * ((F + 31) >> 5) : nullptr;
@@ -127,7 +183,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
                 const int pc = min(p0 + e * nwv, npiece - 1);     // (a piece past the end repeats the last one; nothing of it is kept)
                 const int rl = pc / nh, j = (pc - rl * nh) * 64 + lane;
                 const int jc = j < Tb ? j : Tb - 1;               // (lanes past the row recompute its last bin, likewise)
-                const T *row = db + (size_t)(r0 + rl) * nc;
+                const T *row = db + (size_t)(r0 + rl) * ncs;
                 if (nc == Tb) {
                     x0[e] = row[jc]; x1[e] = x0[e]; w0[e] = 1.0; w1[e] = 0.0; two[e] = false;
                 } else {
@@ -172,7 +228,7 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
                     if (tmc) tb = (unsigned long long)tmc[w] | (w + 1 < W ? (unsigned long long)tmc[w + 1] << 32 : 0ull);
                     val = (rowm || ((tb >> lane) & 1ull)) ? (T)0 : val;
                 }
-                if (a.norm_out && valid) a.norm_out[((size_t)b * F + r0 + rl) * Tb + j] = val;
+                if (a.norm_out && valid) a.norm_out[((size_t)b * F + r0 + rl) * Tbs + j] = val;
 #pragma unroll
                 for (int q = 0; q < MAX_THR; ++q) {
                     if (q < nq) {
@@ -217,8 +273,9 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
         // ---- 3. raster bytes of the group's rows (create_pure_redundancy: output row c reads filter row c / redundancy) ----
         if (dst) {
             const int c0 = r0 * a.redundancy, nrow = rows * a.redundancy;
-            if ((row_bytes & 3) == 0) {
-                const int rw = row_bytes / 4;
+            // (RAGGED: a row is rbs bytes long, the clip's latches fill its first row_bytes, the rest is 0)
+            if ((rbs & 3) == 0) {
+                const int rw = rbs / 4;
                 uint32_t *d4 = reinterpret_cast<uint32_t *>(dst) + (size_t)c0 * rw;
                 for (int i = tid; i < nrow * rw; i += blockDim.x) {
                     const int c = i / rw;
@@ -227,18 +284,20 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
                     uint32_t v = 0u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
+                        if (RAGGED && p + e >= row_bytes) break;
                         const int j = (p + e) / nq, q = (p + e) - j * nq;           // raster byte p + e = time bin j, threshold q
                         v |= ((o[q * W + (j >> 5)] >> (j & 31)) & 1u) << (8 * e);
                     }
                     d4[i] = v;
                 }
             } else {
-                uint8_t *d1 = dst + (size_t)c0 * row_bytes;
-                for (int i = tid; i < nrow * row_bytes; i += blockDim.x) {
-                    const int c = i / row_bytes;
-                    const int p = i - c * row_bytes;
+                uint8_t *d1 = dst + (size_t)c0 * rbs;
+                for (int i = tid; i < nrow * rbs; i += blockDim.x) {
+                    const int c = i / rbs;
+                    const int p = i - c * rbs;
                     const int j = p / nq, q = p - j * nq;
-                    d1[i] = (uint8_t)((onb[((size_t)(c / a.redundancy) * nq + q) * W + (j >> 5)] >> (j & 31)) & 1u);
+                    d1[i] = (RAGGED && p >= row_bytes) ? (uint8_t)0
+                            : (uint8_t)((onb[((size_t)(c / a.redundancy) * nq + q) * W + (j >> 5)] >> (j & 31)) & 1u);
                 }
             }
         }

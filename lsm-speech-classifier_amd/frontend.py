@@ -339,6 +339,124 @@ class SpikeFrontEnd:
                            "lsm_gammatone_spikes_masked_f64")
         return raster
 
+    # ---- ragged batches (SPEC.md §1.14, include/lsm_hip_ragged.h) ---------------------------------------------------------
+    def _device_bins(self, bins, n_clips: int) -> torch.Tensor:
+        """``bins`` of a ragged batch as the int32 device tensor the kernels read: host values checked
+        (`checked_ragged_bins`), a device tensor taken as it is -- never read back, the kernels clamp it."""
+        host = checked_ragged_bins(bins, n_clips, self.time_bins)
+        if host is None:
+            return bins.to(self.device).contiguous()
+        return torch.from_numpy(host).to(self.device)
+
+    def _clamped_bins(self, bins_dev: torch.Tensor) -> torch.Tensor:
+        """The kernels' clamp of a bin count (0, or 3 .. time_bins), as device arithmetic: what the split routes derive their
+        column and frame counts from, so that the launches of one batch agree whatever the tensor holds."""
+        t = bins_dev.clamp(0, self.time_bins)
+        return torch.where(t < 3, torch.zeros_like(t), t)
+
+    def spikes_from_db_ragged(self, db: torch.Tensor, cols: torch.Tensor, bins: torch.Tensor, want_norm: bool = False,
+                              want_raster: bool = True, raster_out: torch.Tensor | None = None):
+        """`spikes_from_db` for a ragged batch (`lsm_spec_to_spikes_ragged_*`): ``db`` (B, F, ncols) holds clip b's dB values
+        in its first ``cols[b]`` columns, ``bins[b]`` is its number of time bins (int32 device tensors).  Returns (raster
+        (B, C, n_steps), normalised spectrogram (B, F, time_bins) or None); both are zeros past a clip's bins."""
+        B = db.shape[0]
+        f64 = db.dtype == torch.float64
+        on, off = threshold_tables(self.thresholds, self.gap, np.float64 if f64 else np.float32)
+        if db.device != indexed_device(self.device):
+            raise ValueError(f"spectrogram on {db.device}, front end on {self.device}")
+        for name, t in (("cols", cols), ("bins", bins)):
+            if (not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != (B,) or t.device != db.device
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 ({B},) tensor on {db.device}")
+        db = db.contiguous()
+        with torch.cuda.device(self.device):
+            raster = raster_out if raster_out is not None else (
+                torch.empty((B, self.n_channels, self.n_steps), dtype=torch.uint8, device=self.device) if want_raster else None)
+            norm = (torch.empty((B, self.n_filters, self.time_bins), dtype=db.dtype, device=self.device)
+                    if want_norm else None)
+            fn = self.lib.lsm_spec_to_spikes_ragged_f64 if f64 else self.lib.lsm_spec_to_spikes_ragged_f32
+            _lib.check(fn(_dev(db), B, self.n_filters, db.shape[2], self.time_bins, _dev(cols), _dev(bins),
+                          1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on), self.redundancy,
+                          _dev(raster) if raster is not None else None, _dev(norm) if want_norm else None, self._stream()),
+                       "lsm_spec_to_spikes_ragged")
+        return raster, norm
+
+    def encode_ragged(self, audio, bins, fused: bool | None = None, low_latency: bool = False,
+                      raster_out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                      share_lds: bool = False):
+        """Clips of different lengths in the launches a batch of equal clips takes (SPEC.md §1.14).  ``audio``
+        (B, n_samples): clip b is the first ``160 * bins[b]`` samples of its row, and what lies behind them influences
+        nothing.  ``bins``: B host integers, each 0 or 3 .. time_bins (checked), or an int32 device tensor (not read: the
+        kernels clamp it).  Returns ``(raster, steps)``: the uint8 raster (B, C, n_steps) -- clip b's rows hold, in their
+        first ``bins[b] * n_thr`` bytes, what ``SpikeFrontEnd(n_filters, filterbank, n_samples=160 * bins[b],
+        time_bins=bins[b])`` encodes for the clip alone, and zeros behind them -- and ``steps``, the int32 device tensor
+        ``bins * n_thr`` that ``SNN.run_batch(lengths=...)`` takes, made on the device without a host round trip.
+        Needs a front end with ``n_samples == 160 * time_bins`` (`ragged_refusal`).  Gammatone: one launch
+        (`lsm_gammatone_spikes_ragged_f64`; ``low_latency``, ``share_lds``, ``raster_out`` and ``workspace`` as `encode`
+        takes them), or with ``fused=False`` `lsm_gammatone_spec_f64` on the padded rows and the ragged encoder: the same
+        bytes.  Mel: always the split route -- the rows are zeroed from each clip's end on into a staging tensor, then
+        `lsm_mel_power_f32`, `lsm_power_to_db_ragged_f32` and the ragged encoder.  Masks are not offered here."""
+        why = ragged_refusal(self.n_samples, self.time_bins)
+        if why:
+            raise ValueError(why)
+        audio = self._audio(audio)
+        B = audio.shape[0]
+        if fused is None:
+            fused = self.filterbank == "gammatone" and self.will_fuse()
+        if fused and self.filterbank == "mel":
+            raise ValueError("the mel branch has no one-launch ragged kernel: encode_ragged takes its split route (fused=False)")
+        if not fused and workspace is not None:
+            raise ValueError("workspace belongs to the fused launch; this call takes the split route")
+        shape = (B, self.n_channels, self.n_steps)
+        if raster_out is not None and (raster_out.dtype != torch.uint8 or tuple(raster_out.shape) != shape
+                                       or not raster_out.is_contiguous() or raster_out.device != self.device):
+            raise ValueError(f"raster_out must be a contiguous uint8 {shape} tensor on {self.device}")
+        n_thr = len(self.thresholds)
+        with torch.cuda.device(self.device):
+            bins_dev = self._device_bins(bins, B)
+            raster = raster_out if raster_out is not None else torch.empty(shape, dtype=torch.uint8, device=self.device)
+            if fused:
+                on, off = threshold_tables(self.thresholds, self.gap, np.float64)
+                steps = torch.empty((B,), dtype=torch.int32, device=self.device)
+                ws_bytes = int(self.lib.lsm_gammatone_spikes_workspace(B, self.n_filters, self.ncols))
+                if workspace is not None:
+                    if (workspace.dtype != torch.float64 or workspace.numel() * 8 < ws_bytes or not workspace.is_contiguous()
+                            or workspace.device != self.device):
+                        raise ValueError(f"workspace must be a contiguous float64 tensor of >= {ws_bytes // 8} elements on "
+                                         f"{self.device}")
+                    ws = workspace
+                else:
+                    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
+                _lib.check(self.lib.lsm_gammatone_spikes_ragged_f64(
+                    _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop, self.ncols,
+                    self.time_bins, _dev(bins_dev), _host(on), _host(off), len(on), self.redundancy, _dev(raster), _dev(steps),
+                    _dev(ws), ws_bytes, self.coef_flags, (1 if low_latency else 0) | (2 if share_lds else 0), self._stream()),
+                    "lsm_gammatone_spikes_ragged_f64")
+                return raster, steps
+            t = self._clamped_bins(bins_dev)
+            steps = (t * n_thr).to(torch.int32)
+            if self.filterbank == "gammatone":
+                # the filter is causal: the padded row's columns below a clip's count are the clip's own
+                cols = torch.where(t > 0, t - (self.time_bins - self.ncols), torch.zeros_like(t)).to(torch.int32)
+                db = torch.empty((B, self.n_filters, self.ncols), dtype=torch.float64, device=self.device)
+                _lib.check(self.lib.lsm_gammatone_spec_f64(
+                    _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop, self.ncols, None,
+                    _dev(db), self.coef_flags, self._stream()), "lsm_gammatone_spec_f64")
+            else:
+                # frames are independent and centred with zero padding: with zeros from a clip's end on, the padded row's
+                # frames up to the clip's last are the clip's own
+                live = torch.arange(self.n_samples, device=self.device)[None, :] < (t * RAGGED_HOP)[:, None]
+                staged = torch.where(live, audio, torch.zeros((), dtype=audio.dtype, device=self.device))
+                cols = torch.where(t > 0, t + 1, torch.zeros_like(t)).to(torch.int32)
+                power = self._mel.power(staged)
+                db = torch.empty_like(power)
+                from . import mel as _mel
+                _lib.check(self.lib.lsm_power_to_db_ragged_f32(
+                    _dev(power), B, self.n_filters, int(power.shape[2]), _dev(cols), C.c_float(_mel.AMIN),
+                    C.c_float(_mel.TOP_DB), _dev(db), self._stream()), "lsm_power_to_db_ragged_f32")
+            self.spikes_from_db_ragged(db, cols.contiguous(), t.to(torch.int32).contiguous(), raster_out=raster)
+        return raster, steps
+
 
     def db_range(self, audio):
         """Calibration range for `GammatoneStream` from a batch of calibration clips (B, n_samples): ``(lo, hi)`` Python
@@ -364,6 +482,66 @@ class SpikeFrontEnd:
             db = 10.0 * torch.log10(torch.clamp(torch.stack([S.min(), S.max()]), min=_mel.AMIN))
         lo, hi = (float(v) for v in db.cpu())
         return max(lo, hi - _mel.TOP_DB), hi
+
+
+# ---- ragged batches: host side (SPEC.md §1.14) -------------------------------------------------------------------------
+RAGGED_HOP = 160            # samples per time bin of a ragged clip: the reference's 100 bins per second (= STREAM_HOP)
+RAGGED_MIN_BINS = 3         # gtgram on 160 * T samples has T - 2 columns: a clip needs one
+
+
+def ragged_refusal(n_samples: int, time_bins: int) -> str | None:
+    """Why a front end of this shape cannot take ragged batches, or None: its rows must hold ``time_bins`` bins of 160
+    samples, so that a clip of T bins is the front end of ``(160 * T, T)`` whatever T is."""
+    if int(time_bins) < RAGGED_MIN_BINS:
+        return f"ragged batches need time_bins >= {RAGGED_MIN_BINS}, this front end has {time_bins}"
+    if int(n_samples) != RAGGED_HOP * int(time_bins):
+        return (f"ragged batches take {RAGGED_HOP} samples per time bin: a front end of {time_bins} bins needs n_samples = "
+                f"{RAGGED_HOP * int(time_bins)}, this one has {n_samples} (hops other than {RAGGED_HOP} are not built)")
+    return None
+
+
+def checked_ragged_bins(bins, n_clips: int, time_bins: int):
+    """The ``bins`` of a ragged batch: host integers -> an int32 array, each 0 or RAGGED_MIN_BINS .. time_bins, refused
+    otherwise with the offenders named; an int32 tensor of ``n_clips`` values on a GPU -> None (its values are never read
+    back: the kernels clamp them)."""
+    if isinstance(bins, torch.Tensor):
+        if bins.dtype != torch.int32 or tuple(bins.shape) != (n_clips,):
+            raise ValueError(f"bins must hold {n_clips} int32 values, got {bins.dtype} {tuple(bins.shape)}")
+        if bins.is_cuda:
+            return None
+        bins = bins.numpy()
+    arr = np.asarray(bins)
+    if arr.shape != (n_clips,) or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"bins must be {n_clips} integers, got {arr.dtype} {arr.shape}")
+    arr = arr.astype(np.int64)
+    bad = np.nonzero(((arr != 0) & (arr < RAGGED_MIN_BINS)) | (arr < 0) | (arr > time_bins))[0]
+    if len(bad):
+        raise ValueError(f"bins {arr[bad].tolist()} of clips {bad.tolist()}: a clip has 0 or {RAGGED_MIN_BINS} .. {time_bins} "
+                         f"time bins")
+    return arr.astype(np.int32)
+
+
+def pack_utterances(utterances, max_bins: int):
+    """Utterances of any length as one ragged batch: a list of n 1-D arrays -> ``(audio (n, 160 * max_bins) float32, bins
+    (n,) int32)`` in the input order.  Utterance r is zero-padded up to a whole bin, ``bins[r] = ceil(len / 160)``, and lies
+    at the start of row r; the rest of the row is zeros.  Refused, with the index of the offender: anything that is not
+    1-D, an utterance of fewer than 3 bins (321 samples at least) and one of more than ``max_bins``.  NumPy only."""
+    max_bins = int(max_bins)
+    if max_bins < RAGGED_MIN_BINS:
+        raise ValueError(f"max_bins = {max_bins}: a clip has at least {RAGGED_MIN_BINS} time bins")
+    audio = np.zeros((len(utterances), RAGGED_HOP * max_bins), dtype=np.float32)
+    bins = np.zeros(len(utterances), dtype=np.int32)
+    for r, u in enumerate(utterances):
+        a = np.asarray(u)
+        if a.ndim != 1:
+            raise ValueError(f"utterance {r} must be a 1-D array, got shape {tuple(a.shape)}")
+        t = -(-a.shape[0] // RAGGED_HOP)
+        if t < RAGGED_MIN_BINS or t > max_bins:
+            raise ValueError(f"utterance {r} has {a.shape[0]} samples = {t} time bins of {RAGGED_HOP}, outside "
+                             f"[{RAGGED_MIN_BINS}, {max_bins}]")
+        audio[r, :a.shape[0]] = a
+        bins[r] = t
+    return audio, bins
 
 
 # ---- streamed gammatone front end (SPEC.md §1.6, include/lsm_hip_audio.h) ----------------------------------------------

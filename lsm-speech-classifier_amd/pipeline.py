@@ -571,6 +571,38 @@ def features_from_recordings(recordings, fe, net, feature_keys):
         return feats
 
 
+def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024):
+    """Utterances of different lengths, each one clip: ``utterances``, a list of n 1-D float32 arrays of 321 to
+    ``fe.n_samples`` samples, -> (n, n_feat) float32 device tensor in the input order.  Row r holds the features of utterance
+    r taken alone: its own ``ceil(len / 160)`` time bins through the front end of that length (its normalisation range is the
+    utterance's, SPEC.md §1.14) and its own ``bins * n_thr`` reservoir steps (§4c) -- no padding takes part in either.
+    Batches of ``batch`` utterances, longest first (the waves of a launch finish with their clips, so clips of like length
+    share a launch); within a batch the ragged front end (`SpikeFrontEnd.encode_ragged`) hands its raster and its device step
+    counts to the ragged reservoir launch on the same stream, with no host synchronisation between them.  Where
+    ``fe.n_steps`` exceeds the longest launch the reservoir's plan accepts, the reservoir runs in chunks
+    (``SNN.run_chunked(lengths=...)``, host lengths)."""
+    from .frontend import pack_utterances
+    from .snn import _select_keys
+    audio, bins = pack_utterances(utterances, fe.time_bins)
+    n = len(bins)
+    keys, _ = _select_keys(feature_keys)
+    batch = max(1, int(batch))
+    with torch.cuda.device(net.device):
+        feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
+        order = np.argsort(-bins.astype(np.int64), kind="stable")
+        n_thr = len(fe.thresholds)
+        for lo in range(0, n, batch):
+            idx = order[lo:lo + batch]
+            x = torch.from_numpy(audio[idx]).to(net.device)
+            raster, steps = fe.encode_ragged(x, bins[idx])
+            if fe.n_steps > net.max_steps(len(idx)):
+                rows = net.run_chunked(raster, feature_keys, lengths=bins[idx].astype(np.int64) * n_thr)[0]
+            else:
+                rows = net.run_batch(raster, feature_keys, lengths=steps)[0]
+            feats[torch.from_numpy(idx).to(net.device)] = rows
+        return feats
+
+
 def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps: int, window_segments: int,
                                      hop_segments: int = 1):
     """Features of sliding windows over a recording: ``audio`` (n, W * fe.n_samples) float32 -> (n, Wn, n_feat) float32

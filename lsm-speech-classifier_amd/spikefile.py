@@ -19,6 +19,7 @@ import numpy as np
 
 PACKED_KEY = "X_spikes_packed"
 DENSE_KEY = "X_spikes"
+STEPS_KEY = "n_steps"
 
 
 def pack_host(x: np.ndarray) -> np.ndarray:
@@ -33,10 +34,20 @@ def unpack_host(p: np.ndarray, time_steps: int) -> np.ndarray:
     return np.unpackbits(p, axis=-1, count=time_steps, bitorder="little")
 
 
-def save(filename, X_spikes=None, y_labels=None, *, packed=None, time_steps=None) -> None:
+def save(filename, X_spikes=None, y_labels=None, *, packed=None, time_steps=None, n_steps=None) -> None:
     """Write File 1.  Give ``X_spikes`` (n, C, T) for the reference schema, or ``packed`` +
-    ``time_steps`` for the packed one."""
+    ``time_steps`` for the packed one.  ``n_steps`` (reference schema only): the steps of every clip of a variable-length
+    dataset (SPEC.md 1.14), written as the extra key ``n_steps`` (n,) int32; T is then the rows' stride."""
     y = np.asarray(y_labels, dtype=np.int32)
+    if n_steps is not None:
+        if packed is not None:
+            raise ValueError("n_steps goes with the reference schema (X_spikes), not the packed one")
+        X = np.ascontiguousarray(X_spikes, dtype=np.uint8)
+        steps = np.asarray(n_steps, dtype=np.int32)
+        if X.ndim != 3 or len(X) != len(y) or steps.shape != (len(y),) or (steps < 0).any() or (steps > X.shape[2]).any():
+            raise ValueError("X_spikes must be (n, C, T) with one label and one step count in [0, T] per clip")
+        np.savez_compressed(filename, **{DENSE_KEY: X}, y_labels=y, **{STEPS_KEY: steps})
+        return
     if packed is not None:
         if time_steps is None:
             raise ValueError("the packed schema needs time_steps")
@@ -59,6 +70,12 @@ def load_packed(filename):
             return data[PACKED_KEY], int(data["time_steps"]), y
         X = data[DENSE_KEY]
         return pack_host(X), int(X.shape[-1]), y
+
+
+def load_steps(filename):
+    """The ``n_steps`` (n,) int32 of a variable-length File 1 (SPEC.md 1.14), or None for a file of equal clips."""
+    with np.load(filename) as data:
+        return data[STEPS_KEY].astype(np.int32) if STEPS_KEY in data.files else None
 
 
 def load(filename):

@@ -67,6 +67,11 @@ def _mask_args(a):
     return out if _augment_args(a) or _reverb_args(a) or _speed_args(a) else out + ["--augment-seed", str(a.augment_seed)]
 
 
+def _variable_length_args(a):
+    """Nothing without --variable-length."""
+    return ["--variable-length", "--max-seconds", str(a.max_seconds)] if a.variable_length else []
+
+
 def _reservoir_args(a):
     out = []
     for flag, v in (("--num-neurons", a.num_neurons), ("--num-output-neurons", a.num_output_neurons),
@@ -80,7 +85,7 @@ STAGES = (
     ("Step 1: Creating Spike Train Dataset",
      lambda a: ["create_dataset.py", "--n-filters", str(a.n_filters), "--filterbank", a.filterbank]
      + _corpus_args(a) + (["--packed"] if a.packed else []) + _augment_args(a) + _reverb_args(a)
-     + _speed_args(a) + _mask_args(a)),
+     + _speed_args(a) + _mask_args(a) + _variable_length_args(a)),
     ("Step 2: Extracting LSM Features",
      lambda a: ["extract_lsm_features.py", "--feature-set", a.feature_set, "--multiplier", str(a.multiplier)]
      + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])),
@@ -130,7 +135,8 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     packed, num_neurons, num_output_neurons, small_world_k, seed, readout, nproc, time_segments, and the corruption flags
     noise_dir, snr_db, time_shift_ms, level_db, augment_seed, the reverberation flags rir_dir, rir_prob, rir_max_ms and the
     speed flags speed_factors, speed_prob and the mask flags freq_masks, freq_mask_width, time_masks, time_mask_width,
-    mask_prob: applied to stage 1 and to the in-memory route)."""
+    mask_prob: applied to stage 1 and to the in-memory route; variable_length, max_seconds: stage 1 keeps every clip at its
+    own length, SPEC.md 1.14, and stage 2 finds the lengths in File 1)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
@@ -138,11 +144,13 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
                               readout=None, nproc=1, time_segments=1, noise_dir=None, snr_db=None, time_shift_ms=0.0,
                               level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0,
                               speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
-                              time_mask_width=0, mask_prob=1.0)
+                              time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
     vars(args).update(extra)
+    if args.variable_length and (in_memory or args.nproc > 1):
+        raise SystemExit("--variable-length goes through File 1 in one process: it combines with neither --in-memory nor --nproc")
     print("--- Running Pipeline ---")
     if in_memory:
         print("\n--- Steps 1+2: audio -> LSM features on the GPU (no dataset file) ---", flush=True)
@@ -221,6 +229,10 @@ if __name__ == "__main__":
     ap.add_argument("--time-masks", type=int, default=0, help="Time spans zeroed per clip inside the encoder (stage 1).")
     ap.add_argument("--time-mask-width", type=int, default=0, help="Largest width of a time span, in time bins (stage 1).")
     ap.add_argument("--mask-prob", type=float, default=1.0, help="Share of the clips that are masked (stage 1).")
+    ap.add_argument("--variable-length", action="store_true",
+                    help="Keep every clip at its own length instead of padding it to one second (stage 1; stage 2 reads the "
+                         "lengths from File 1).")
+    ap.add_argument("--max-seconds", type=float, default=1.0, help="With --variable-length: trim clips at this length (stage 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
@@ -231,4 +243,5 @@ if __name__ == "__main__":
                  time_shift_ms=a.time_shift_ms, level_db=a.level_db, augment_seed=a.augment_seed,
                  rir_dir=a.rir_dir, rir_prob=a.rir_prob, rir_max_ms=a.rir_max_ms, speed_factors=a.speed_factors,
                  speed_prob=a.speed_prob, freq_masks=a.freq_masks, freq_mask_width=a.freq_mask_width,
-                 time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob)
+                 time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob,
+                 variable_length=a.variable_length, max_seconds=a.max_seconds)
