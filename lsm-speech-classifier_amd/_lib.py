@@ -181,6 +181,15 @@ RAGGED_SIGS = {
 RAGGED_SYMBOLS = tuple(RAGGED_SIGS)
 
 
+# include/lsm_hip_step.h: a whole step -- lane-pair gammatone front end and dense-row reservoir -- in one launch
+STEP_SIGS = {
+    "lsm_step_fused_supported": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "lsm_step_fused_f64": (c_int, [c_void, c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void,
+                                   c_int, c_int, c_void, C.c_long, c_int, c_void, c_int, c_void, c_void, c_void]),
+}
+STEP_SYMBOLS = tuple(STEP_SIGS)
+
+
 class LsmHipError(RuntimeError):
     pass
 
@@ -230,7 +239,7 @@ def load():
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
-                              + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items())):
+                              + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

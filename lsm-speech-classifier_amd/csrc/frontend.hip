@@ -419,7 +419,7 @@ static int hw_queues()
     return v > 0 ? v : 4;
 }
 
-static bool fused_plan(int n_filters, int n_clips, int launch_flags, FusedPlan *p)
+static bool fused_plan(int n_filters, int n_clips, int launch_flags, FusedPlan *p, bool step = false)
 {
     // The lane pair for 2..256 filters, whatever the low-latency flag says, where queues are scarce: at 128 filters a clip
     // is 4 waves of 0.4 times the two-chain wave's time, so one 256-clip launch covers all 1024 SIMDs and the pipeline
@@ -432,6 +432,8 @@ static bool fused_plan(int n_filters, int n_clips, int launch_flags, FusedPlan *
     const DevInfo di = dev_info();
     bool pair = n_filters <= 32 * GT_MAX_WPB && hw_queues() <= 4 &&
                 (di.cus <= 0 || (long)n_clips * ((n_filters + 127) / 128) < 4L * di.cus);
+    // (the fused step launch, step_fused.hip, is written for the lane pair and takes it wherever the pair's text can run)
+    if (step) pair = n_filters <= 32 * GT_MAX_WPB;
     // otherwise two chains per lane above 64 filters (fewest CU-cycles per clip), unless the caller asks for the
     // low-latency layout: one chain per lane = twice the waves, each half as long (1.47 against 2.43 ms for 256 clips x
     // 128 filters on an idle GPU, for 12 % more CU time)
@@ -472,7 +474,7 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
                             int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
                             int coef_flags, int launch_flags, const uint32_t *freq_mask, const uint32_t *time_mask,
                             void *stream, bool ragged = false, const int32_t *clip_bins = nullptr,
-                            int32_t *clip_steps_out = nullptr)
+                            int32_t *clip_steps_out = nullptr, lsm_fe::StepFront *step = nullptr)
 {
     LSM_REQUIRE((launch_flags & ~3) == 0, "launch_flags: only bit 0 (low-latency layout) and bit 1 (no LDS reservation) are defined");
     LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && n_samples >= 1, "bad shape");
@@ -483,7 +485,7 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
     LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
     LSM_REQUIRE(thr_on && thr_off, "null threshold table");
     if (n_clips == 0) return LSM_OK;
-    LSM_REQUIRE(audio && coefs && raster && workspace, "gammatone_spikes: null buffer");
+    LSM_REQUIRE(audio && coefs && (raster || step) && workspace, "gammatone_spikes: null buffer");
     LSM_REQUIRE(workspace_bytes >= lsm_gammatone_spikes_workspace(n_clips, n_filters, ncols),
                 "workspace of %ld bytes, need %ld (lsm_gammatone_spikes_workspace)", workspace_bytes,
                 lsm_gammatone_spikes_workspace(n_clips, n_filters, ncols));
@@ -492,7 +494,7 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
     LSM_REQUIRE((row_bytes & 3) != 0 || ((uintptr_t)raster & 3u) == 0,
                 "the raster must be 4-byte aligned when a row is a multiple of 4 bytes");
     FusedPlan pl;
-    if (!fused_plan(n_filters, n_clips, launch_flags, &pl)) {
+    if (!fused_plan(n_filters, n_clips, launch_flags, &pl, step != nullptr)) {
         lsm_set_error("gammatone_spikes: %d filters need more than %d waves per clip; use the split entry points",
                       n_filters, GT_MAX_WPB);
         return LSM_ERR_UNSUPPORTED;
@@ -526,6 +528,12 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
                                                            // wave-uniform in the lane pair
     const int nw = (nwin + hop - 1) / hop;
     if (const int rc = check_masks(freq_mask, time_mask)) return rc;
+    if (step) {                                         // the fused step launch (step_fused.hip): checked and planned, not launched
+        step->l = lsm_fe::FusedLaunch{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
+        static_assert(sizeof(step->args) == sizeof(FusedArgs), "StepFront carries a FusedArgs");
+        memcpy(step->args, &a, sizeof(FusedArgs));
+        return LSM_OK;
+    }
     if (freq_mask || time_mask) {                       // SPEC.md 1.13
         const lsm_fe::FusedLaunch l{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
         lsm_fe::launch_gammatone_spikes_masked(l, &a, lsm_fe::MaskArgs{freq_mask, time_mask}, stream);
@@ -578,6 +586,16 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
 {
     return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
                             redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, nullptr, nullptr, stream);
+}
+
+// step_fused.hip: lsm_gammatone_spikes_f64's refusals, plan and arguments for the front-end half of a fused step (no raster)
+int lsm_fe::step_front_args(const float *audio, int n_clips, int n_samples, const double *coefs, int n_filters, int nwin,
+                            int hop, int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr,
+                            int redundancy, void *workspace, long workspace_bytes, int coef_flags, StepFront *out)
+{
+    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                            redundancy, nullptr, workspace, workspace_bytes, coef_flags, 0, nullptr, nullptr, nullptr, false,
+                            nullptr, nullptr, out);
 }
 
 LSM_API int lsm_gammatone_spikes_masked_f64(const float *audio, int n_clips, int n_samples,

@@ -75,11 +75,15 @@ __device__ __forceinline__ double uniform_f64(double v)
 
 // The unmasked kernel: the text of gammatone_spikes_kernel.inc with MASK = false
 #define LSM_FUSED_KERNEL gammatone_spikes_kernel
+#define LSM_FUSED_QUALIFIERS __global__ __launch_bounds__(GT_MAX_WPB * 64)
+#define LSM_FUSED_TAIL_INC "gammatone_spikes_raster_out.inc"
 #define LSM_FUSED_PARAMS const FusedArgs a
 #define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
 #define LSM_FUSED_RAGGED constexpr bool RAGGED = false; const lsm_fe::RaggedArgs rg{nullptr, nullptr};
 #include "gammatone_spikes_kernel.inc"
 #undef LSM_FUSED_KERNEL
+#undef LSM_FUSED_QUALIFIERS
+#undef LSM_FUSED_TAIL_INC
 #undef LSM_FUSED_PARAMS
 #undef LSM_FUSED_MASK
 #undef LSM_FUSED_RAGGED
@@ -101,6 +105,16 @@ struct FusedLaunch {
 void launch_gammatone_spikes_masked(const FusedLaunch &l, const void *fused_args, const MaskArgs &m, void *stream);
 template <typename T>
 void launch_spec_to_spikes_masked(const SpikeArgs<T> &a, const MaskArgs &m, int threads, size_t lds, void *stream);
+
+// The front-end half of a fused step launch (step_fused.hip, include/lsm_hip_step.h): what lsm_gammatone_spikes_f64 would
+// launch for these arguments, after the same refusals -- the FusedArgs as bytes, for the reason above.  frontend.hip.
+struct StepFront {
+    FusedLaunch l;
+    alignas(8) unsigned char args[sizeof(FusedArgs)];
+};
+int step_front_args(const float *audio, int n_clips, int n_samples, const double *coefs, int n_filters, int nwin, int hop,
+                    int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr, int redundancy,
+                    void *workspace, long workspace_bytes, int coef_flags, StepFront *out);
 
 // The ragged twins (SPEC.md 1.14), defined in ragged_frontend.hip, likewise a translation unit of its own
 void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args, const RaggedArgs &rg, void *stream);

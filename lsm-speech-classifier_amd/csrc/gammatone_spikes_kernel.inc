@@ -2,6 +2,10 @@
 // kernel's name (LSM_FUSED_KERNEL), its parameters (LSM_FUSED_PARAMS) and MASK (LSM_FUSED_MASK) -- gammatone_spikes_body.h
 // for gammatone_spikes_kernel(const FusedArgs a), mask.hip for gammatone_spikes_masked_kernel(a, const lsm_fe::MaskArgs m) --
 // and RAGGED (LSM_FUSED_RAGGED): ragged_frontend.hip for gammatone_spikes_ragged_kernel(a, const lsm_fe::RaggedArgs rg).
+// The function's qualifiers are the includer's too (LSM_FUSED_QUALIFIERS: for these three `__global__
+// __launch_bounds__(GT_MAX_WPB * 64)`), and so is what follows the staged rows, a file the includer names
+// (LSM_FUSED_TAIL_INC): the three write the uint8 raster (gammatone_spikes_raster_out.inc); step_fused.hip hands the staged
+// bits to the reservoir's time loop in the same workgroup instead (step_fused_tail.inc) and writes no raster.
 // One text, three kernels -- and not one device function called by three kernels: behind a call, even a forced-inline one, the
 // compiler allocated and scheduled 32 of the unmasked kernel's 34 forms differently (profiles/spec_mask.txt), and those
 // forms are measured code.
@@ -21,7 +25,7 @@
 // keeps the launch's strides a.ncols and a.time_bins.  A clip of 0 bins filters nothing and encodes nothing, reaches every
 // barrier and writes zero rows.  With RAGGED = false `nc` is a.ncols, `Tb` is a.time_bins and the code is the twin's.
 template <int NW, bool FAST, int NCH, bool SHB0 = false, bool PAIR = false>
-__global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PARAMS)
+LSM_FUSED_QUALIFIERS void LSM_FUSED_KERNEL(LSM_FUSED_PARAMS)
 {
     LSM_FUSED_MASK                                      // constexpr bool MASK, and `m` where it is no parameter
     LSM_FUSED_RAGGED                                    // constexpr bool RAGGED (`rg` is a parameter where it is true)
@@ -414,33 +418,5 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void LSM_FUSED_KERNEL(LSM_FUSED_PA
         }
     }
     __syncthreads();                                    // the wave's own staged rows (and a uniform barrier count)
-    if (valid) {
-        // create_pure_redundancy: output row c reads filter row c / redundancy
-        const int R = a.redundancy;
-        const int fbase = g * NCH * CPW;
-        const int rows_out = min(NCH * CPW, F - fbase) * R;
-        // RAGGED: a row keeps the launch's length; the clip owns its first row_bits bytes, the rest is written as 0 (the stage
-        // holds nothing of the clip past them)
-        const int row_bytes = RAGGED ? a.time_bins * n_thr : row_bits;
-        uint8_t *dst = a.raster + ((size_t)b * F + fbase) * R * row_bytes;
-        if ((row_bytes & 3) == 0) {
-            const int rw = row_bytes >> 2;
-            uint32_t *d4 = reinterpret_cast<uint32_t *>(dst);
-            for (int i = lane; i < rows_out * rw; i += 64) {
-                const int c = i / rw;
-                const int p = (i - c * rw) * 4;
-                uint32_t nib = (stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 0xFu;
-                if constexpr (RAGGED) nib &= (1u << min(max(row_bits - p, 0), 4)) - 1u;
-                d4[i] = (nib * 0x00204081u) & 0x01010101u;
-            }
-        } else {
-            for (int i = lane; i < rows_out * row_bytes; i += 64) {
-                const int c = i / row_bytes;
-                const int p = i - c * row_bytes;
-                uint32_t bit = (stage[(c / R) * RW + (p >> 5)] >> (p & 31)) & 1u;
-                if constexpr (RAGGED) bit = p < row_bits ? bit : 0u;
-                dst[i] = (uint8_t)bit;
-            }
-        }
-    }
+#include LSM_FUSED_TAIL_INC
 }

@@ -19,11 +19,15 @@ __global__ __launch_bounds__(256) void spec_to_spikes_ragged_kernel(const lsm_fe
 
 // gammatone_spikes_ragged_kernel(const FusedArgs a, const lsm_fe::RaggedArgs rg): the fused kernel's text with RAGGED = true
 #define LSM_FUSED_KERNEL gammatone_spikes_ragged_kernel
+#define LSM_FUSED_QUALIFIERS __global__ __launch_bounds__(GT_MAX_WPB * 64)
+#define LSM_FUSED_TAIL_INC "gammatone_spikes_raster_out.inc"
 #define LSM_FUSED_PARAMS const FusedArgs a, const lsm_fe::RaggedArgs rg
 #define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
 #define LSM_FUSED_RAGGED constexpr bool RAGGED = true;
 #include "gammatone_spikes_kernel.inc"
 #undef LSM_FUSED_KERNEL
+#undef LSM_FUSED_QUALIFIERS
+#undef LSM_FUSED_TAIL_INC
 #undef LSM_FUSED_PARAMS
 #undef LSM_FUSED_MASK
 #undef LSM_FUSED_RAGGED

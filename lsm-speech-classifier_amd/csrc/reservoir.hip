@@ -1308,6 +1308,46 @@ static int run_dense(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
     return launch(dfn, a, r, v.wpc, lds);
 }
 
+// The fused step launch (step_fused.hip, include/lsm_hip_step.h) runs the dense-row time loop behind the front end of the same
+// clip: what run_dense would launch for a step inside the pipeline (waves_per_clip = -1, no spike matrix, trace, state or
+// order), as its arguments.  The step kernel has the <SL, 4, 3, true> forms only: any other plan is LSM_ERR_UNSUPPORTED.
+// `probe`: the shape alone is asked about (lsm_step_fused_supported), no buffer is looked at.
+int lsm_lif::step_dense_args(const lsm_reservoir *h, int n_clips, int n_steps, const int32_t *key_ids, int n_keys,
+                             float *features, int32_t *stats, bool probe, DenseArgs *out, int *sl_out, size_t *lds_out)
+{
+    LSM_REQUIRE(h != nullptr, "lsm_step_fused: null reservoir handle");
+    LSM_REQUIRE(n_clips >= 1 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
+    RunArgs r;
+    r.n_clips = n_clips; r.n_steps = n_steps; r.waves_per_clip = -1;
+    if (!probe) {
+        LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+        for (int k = 0; k < n_keys; ++k) LSM_REQUIRE(key_ids[k] >= 0 && key_ids[k] < 8, "key id %d out of range", key_ids[k]);
+        LSM_REQUIRE(features != nullptr, "null features_out");
+        int dev_now = -1;
+        LSM_CHECK_HIP(hipGetDevice(&dev_now));
+        LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d", h->device,
+                    dev_now);
+        r.key_ids = key_ids; r.n_keys = n_keys; r.features = features; r.stats = stats;
+    }
+    RunPlan plan;
+    if (const int rc = make_plan(h, n_clips, n_steps, r.waves_per_clip, &plan)) return rc;
+    const Variant *v = plan.kernel == KERNEL_DENSE ? plan.v : nullptr;
+    if (!v || v->wpc != 4 || !(v->sl == 1 || v->sl == 2 || v->sl == 4) || !v->inmask || !v->incol || h->C > 128 ||
+        input_words(h) != 4 || h->refractory != lsm_lif::DENSE_REFM_REFRACTORY) {
+        lsm_set_error("lsm_step_fused: the reservoir's launch for this shape is not the dense-row kernel with 4 waves per clip, "
+                      "coloured input masks over 4 row words and the 2-step refractory masks");
+        return LSM_ERR_UNSUPPORTED;
+    }
+    lsm_lif::DenseArgs a;
+    set_common_args(&a, h, r);
+    a.EinW = v->einw; a.ld = h->ld;
+    a.wt = h->wt.get(); a.leak = v->leak.get(); a.oslot = v->oslot.get(); a.in_ent = v->in_ent.get();
+    a.inmask = v->inmask.get();
+    a.inperm = h->inperm.get();
+    *out = a; *sl_out = v->sl; *lds_out = dense_lds_bytes(h, *v, n_steps);
+    return LSM_OK;
+}
+
 static int run_sparse(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
 {
     lif_fn_t fn = pick_kernel(v.sl, v.wpc, lif_inreg(v), lif_seg_in_lds(h, v, r.n_steps), r.stateful());

@@ -1,0 +1,129 @@
+// One launch per step (include/lsm_hip_step.h): the lane-pair gammatone front end of a clip and the dense-row
+// LIF time loop on that clip in ONE workgroup of 4 waves.  The kernel is two existing texts back to back --
+// gammatone_spikes_kernel.inc in its PAIR form up to the staged raster rows, then (step_fused_tail.inc) a hand-off of the
+// staged bits into the reservoir's input bit rows and lif_dense_kernel.inc in its <SL, 4, 3, true> form -- so every float
+// operation and its order are those of lsm_gammatone_spikes_f64 followed by lsm_reservoir_run.  What the step no longer does:
+// write the uint8 raster (13 MB per 256 clips x 128 channels x 400 steps), read it back, re-pack it with LDS atomics, and tie two
+// launches of two streams with an event.  With 4 hardware queues or fewer the pipeline (pipeline.HotPath) takes this launch.
+// The entry point's refusals and the arguments of the two halves are frontend.hip's and reservoir.hip's (step_front_args,
+// step_dense_args); the translation unit is its own so that the existing kernels keep their machine code.
+#include "lsm_common.h"
+#include "gammatone_spikes_body.h"
+#include "lif_dense.h"
+#include <cstring>
+
+namespace {
+
+// step_fused_kernel_sl<SL>(const FusedArgs a, const lsm_lif::DenseArgs d): one text per neuron slots per lane (N <= 256 SL,
+// 4 waves).  A workgroup is one clip: 256 threads, and no more than 128 vector registers so that four launches share a SIMD.
+#define LSM_FUSED_QUALIFIERS __global__ __launch_bounds__(256, 4)
+#define LSM_FUSED_PARAMS const FusedArgs a, const lsm_lif::DenseArgs d
+#define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
+#define LSM_FUSED_RAGGED constexpr bool RAGGED = false; const lsm_fe::RaggedArgs rg{nullptr, nullptr};
+#define LSM_FUSED_TAIL_INC "step_fused_tail.inc"
+
+#define LSM_FUSED_KERNEL step_fused_kernel_sl1
+#define LSM_STEP_SL 1
+#include "gammatone_spikes_kernel.inc"
+#undef LSM_FUSED_KERNEL
+#undef LSM_STEP_SL
+
+#define LSM_FUSED_KERNEL step_fused_kernel_sl2
+#define LSM_STEP_SL 2
+#include "gammatone_spikes_kernel.inc"
+#undef LSM_FUSED_KERNEL
+#undef LSM_STEP_SL
+
+#define LSM_FUSED_KERNEL step_fused_kernel_sl4
+#define LSM_STEP_SL 4
+#include "gammatone_spikes_kernel.inc"
+#undef LSM_FUSED_KERNEL
+#undef LSM_STEP_SL
+
+#undef LSM_FUSED_QUALIFIERS
+#undef LSM_FUSED_PARAMS
+#undef LSM_FUSED_MASK
+#undef LSM_FUSED_RAGGED
+#undef LSM_FUSED_TAIL_INC
+
+typedef void (*step_fn_t)(const FusedArgs, const lsm_lif::DenseArgs);
+
+// The forms built: 3 live windows (2 * hop < nwin <= 3 * hop: the front end's 25 ms window on its 10 ms hop), the fast
+// coefficient path, with and without the shared b0.
+step_fn_t pick_step(int sl, bool shb0)
+{
+    switch (sl) {
+    case 1: return shb0 ? step_fused_kernel_sl1<3, true, 1, true, true> : step_fused_kernel_sl1<3, true, 1, false, true>;
+    case 2: return shb0 ? step_fused_kernel_sl2<3, true, 1, true, true> : step_fused_kernel_sl2<3, true, 1, false, true>;
+    case 4: return shb0 ? step_fused_kernel_sl4<3, true, 1, true, true> : step_fused_kernel_sl4<3, true, 1, false, true>;
+    default: return nullptr;
+    }
+}
+
+// What the shape alone decides about the front-end half (the launch checks the rest): lane pair of exactly 4 waves per clip,
+// one raster row per filter, the forms above.
+bool front_shape_served(int n_filters, int nwin, int hop, int redundancy, int coef_flags)
+{
+    return n_filters > 96 && n_filters <= 128 && redundancy == 1 && hop >= 1 && nwin >= 1 && (nwin + hop - 1) / hop == 3 &&
+           (coef_flags & 3) == 3;
+}
+
+}  // namespace
+
+#define LSM_API extern "C" __attribute__((visibility("default")))
+
+LSM_API int lsm_step_fused_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
+                                     int n_thr, int redundancy, int coef_flags)
+{
+    LSM_REQUIRE(h != nullptr, "lsm_step_fused_supported: null reservoir handle");
+    LSM_REQUIRE(n_clips >= 1 && n_filters >= 1 && time_bins >= 1 && n_thr >= 1 && redundancy >= 1, "bad shape");
+    if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags)) return 0;
+    if ((long)time_bins * n_thr > 65535) return 0;
+    lsm_lif::DenseArgs d;
+    int sl = 0;
+    size_t lds = 0;
+    if (lsm_lif::step_dense_args(h, n_clips, time_bins * n_thr, nullptr, 0, nullptr, nullptr, true, &d, &sl, &lds) != LSM_OK)
+        return 0;
+    if (d.C != n_filters * redundancy) return 0;
+    const size_t RW = ((size_t)time_bins * n_thr + 31) / 32;
+    return 2 * GT_MAX_WPB * sizeof(double) + 4 * 32 * RW * 4 + lds + 128 <= 160 * 1024 ? 1 : 0;
+}
+
+LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
+                               int n_filters, int nwin, int hop, int ncols, int time_bins, const double *thr_on,
+                               const double *thr_off, int n_thr, int redundancy, void *workspace, long workspace_bytes,
+                               int coef_flags, const int32_t *key_ids, int n_keys, float *features_out, int32_t *stats_out,
+                               void *stream)
+{
+    LSM_REQUIRE(h != nullptr, "lsm_step_fused_f64: null reservoir handle");
+    LSM_REQUIRE(n_clips >= 0, "bad shape");
+    if (n_clips == 0) return LSM_OK;
+    lsm_fe::StepFront fr;
+    if (const int rc = lsm_fe::step_front_args(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on,
+                                               thr_off, n_thr, redundancy, workspace, workspace_bytes, coef_flags, &fr))
+        return rc;
+    FusedArgs a;
+    memcpy(&a, fr.args, sizeof a);
+    const int T = time_bins * n_thr;
+    lsm_lif::DenseArgs d;
+    int sl = 0;
+    size_t lif_lds = 0;
+    if (const int rc = lsm_lif::step_dense_args(h, n_clips, T, key_ids, n_keys, features_out, stats_out, false, &d, &sl, &lif_lds))
+        return rc;
+    step_fn_t fn = pick_step(sl, fr.l.shb0);
+    if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags) || !fr.l.pair || fr.l.nch != 1 || !fr.l.fast ||
+        fr.l.nw != 3 || a.groups != 4 || fr.l.block != 256 || fr.l.grid != (unsigned)n_clips || d.C != n_filters * redundancy ||
+        d.CW != 4 || d.T != T || fn == nullptr) {
+        lsm_set_error("lsm_step_fused_f64: shape not served (%d filters, redundancy %d, nwin %d, hop %d, coef_flags %d, %d input "
+                      "channels): make the two launches", n_filters, redundancy, nwin, hop, coef_flags, d.C);
+        return LSM_ERR_UNSUPPORTED;
+    }
+    // the front end's image (exchange doubles and the staged rows: fr.l.lds, a multiple of 16), the reservoir's behind it, and
+    // the 128 bytes of the inverse channel permutation behind the input bit rows
+    const size_t lds = fr.l.lds + lif_lds + 128;
+    LSM_REQUIRE((fr.l.lds & 15) == 0 && lds <= 160 * 1024, "the step's LDS image of %zu bytes does not fit a CU", lds);
+    if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+    hipLaunchKernelGGL(fn, dim3(fr.l.grid), dim3(fr.l.block), lds, (hipStream_t)stream, a, d);
+    LSM_CHECK_HIP(hipGetLastError());
+    return LSM_OK;
+}

@@ -8,6 +8,8 @@ LIF reservoir -> features, all on the GPU -- two launches since round 3, the fus
 work of a step is ordered on its own stream, the float64 filterbank of step s+1 runs beside the
 latency-bound reservoir kernel of step s and refills the CUs that clips finishing early leave idle.
 Every step still does all its work; per-step latency grows, throughput rises.
+Where HIP has at most 4 hardware queues a plain full step of a served shape is ONE launch (`step_fused`,
+include/lsm_hip_step.h): front end and reservoir of a clip in one workgroup, rotating over hw_queues - 1 streams.
 
 `HotPath` owns what used to live in bench.py: the stream rotation, the layout hint for the reservoir
 kernel (a launch that shares the chip with other kernels prefers fewer, fatter waves than a lone one:
@@ -34,6 +36,62 @@ RASTER_DEPTH = 4                     # raster buffers per front-end stream (two-
 # 20-step bursts (profiles/r04_tail_steps.txt)
 TAIL_STEPS = 2
 STAGES = ("full", "frontend", "reservoir")
+# With this many hardware queues or fewer a full step is ONE launch where the library has it (include/lsm_hip_step.h,
+# `step_fused`): the pipeline's 11 streams share the queues, and a reservoir launch that waits at the head of a
+# queue for its front end's event holds back the front ends queued behind it (profiles/step_fused_premise.txt).
+FUSED_STEP_MAX_HW_QUEUES = 4
+
+
+def step_fused_supported(fe, net, n_clips: int) -> bool:
+    """Whether `step_fused` serves batches of `n_clips` clips of this front end and reservoir (`lsm_step_fused_supported`):
+    a gammatone front end of 97..128 filters without redundancy, and a reservoir whose pipeline launch is the dense-row
+    kernel with 4 waves per clip and coloured input masks.  Anything else takes the two launches."""
+    if getattr(fe, "filterbank", None) != "gammatone" or not fe.will_fuse() or int(n_clips) < 1:
+        return False
+    from . import _lib
+    rc = int(_lib.load().lsm_step_fused_supported(net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop, fe.time_bins,
+                                                  len(fe.thresholds), fe.redundancy, fe.coef_flags))
+    if rc < 0:
+        _lib.check(rc, "lsm_step_fused_supported")
+    return rc == 1
+
+
+def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=None, workspace=None):
+    """One step in ONE launch on the current stream (`lsm_step_fused_f64`): audio (B, n_samples) float32 on the device ->
+    feature rows (B, n_keys * N_out) float32, bit for bit ``net.run_batch(fe.encode(audio), feature_keys)[0]``; no raster is
+    written.  `stats_out` / `features_out`: as `SNN.run_batch`'s; `workspace`: as `SpikeFrontEnd.encode`'s (from
+    `fe.new_workspace(B)`).  A shape the launch does not serve (`step_fused_supported`) raises: the caller makes the two
+    launches."""
+    from . import _lib
+    from .frontend import threshold_tables
+    from .snn import _check_stats_out, _dev, _host, _select_keys
+    audio = fe._audio(audio)
+    B = int(audio.shape[0])
+    keys, key_ids = _select_keys(feature_keys)
+    shape = (B, len(keys) * net.num_output_neurons)
+    if features_out is not None:
+        if (features_out.dtype != torch.float32 or tuple(features_out.shape) != shape or not features_out.is_contiguous()
+                or features_out.device != audio.device):
+            raise ValueError(f"features_out must be a contiguous float32 {shape} tensor on {audio.device}")
+        feats = features_out
+    _check_stats_out(stats_out, B, audio.device)
+    on, off = threshold_tables(fe.thresholds, fe.gap, np.float64)
+    with torch.cuda.device(fe.device):
+        if features_out is None:
+            feats = torch.empty(shape, dtype=torch.float32, device=fe.device)
+        ws_bytes = int(fe.lib.lsm_gammatone_spikes_workspace(B, fe.n_filters, fe.ncols))
+        if workspace is not None:
+            if (workspace.dtype != torch.float64 or workspace.numel() * 8 < ws_bytes or not workspace.is_contiguous()
+                    or workspace.device != fe.device):
+                raise ValueError(f"workspace must be a contiguous float64 tensor of >= {ws_bytes // 8} elements on {fe.device}")
+            ws = workspace
+        else:
+            ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=fe.device)
+        _lib.check(fe.lib.lsm_step_fused_f64(
+            net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
+            _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids), len(keys),
+            _dev(feats), _dev(stats_out), fe._stream()), "lsm_step_fused_f64")
+    return feats
 
 
 def configure_hardware_queues(n: int = DEFAULT_HW_QUEUES) -> int:
@@ -87,7 +145,9 @@ class HotPath:
     `reverb` = a `frontend.Reverberator`: a step submitted with `reverb=` (a `frontend.ReverbPlan` of its clips) is convolved
     with its rooms on the device (SPEC.md §1.11) ahead of the mixer; without it nothing more is launched.
     `speed` = a `frontend.SpeedPerturber`: a step submitted with `speed=` (a `frontend.SpeedPlan` of its clips) is played at
-    its clips' speeds on the device (SPEC.md §1.12) ahead of the reverberator: speed, reverb, mixer, front end."""
+    its clips' speeds on the device (SPEC.md §1.12) ahead of the reverberator: speed, reverb, mixer, front end.
+    With at most FUSED_STEP_MAX_HW_QUEUES hardware queues a full step without any of these, of a shape `step_fused_supported`
+    accepts, is one launch (`_submit_fused`); `time_reservoir`'s event pair then brackets that launch, front end included."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
@@ -140,6 +200,17 @@ class HotPath:
         # the steps enqueued ahead and a burst allocates inside the timed path.  Throughput is the same either way
         # (profiles/r03_pipeline_buffer_pool.txt); the rings make the steady path free of allocator calls.
         self._rasters = {}                  # (front-end slot, batch size) -> RasterRing
+        # One launch per step where queues are scarce (FUSED_STEP_MAX_HW_QUEUES): a full step without mixer, reverb, speed,
+        # mask or time segments, of a shape the library serves, rotates over min(hw_queues - 1, streams) of the reservoir
+        # streams and makes one launch there -- no front-end stream, no event, no raster.  One queue is left to the stream the
+        # caller submits from: with as many rotation streams as queues one of them shares its queue with that stream, and
+        # at 4 queues the step took 1.03 ms over 4 streams against 0.84 over 3 (and 0.96 over 2;
+        # profiles/step_fused_ab.txt).  With more queues nothing changes.
+        self.fused_step = (self.n_streams > 1 and self.hw_queues <= FUSED_STEP_MAX_HW_QUEUES and self.time_segments == 1
+                           and mixer is None and reverb is None and speed is None)
+        self.n_fused_streams = max(1, min(self.hw_queues - 1, self.n_streams))
+        self._fused_ok = {}                 # batch size -> step_fused_supported
+        self._fused_ws = {}                 # (rotation slot, batch size) -> the launch's front-end scratch
         self._in_flight = []                # one event per submitted step, on the stream its last launch went to
         self._step = 0
         self.reservoir_events = []          # (start, end) HIP event pairs, one per submitted step (time_reservoir)
@@ -228,6 +299,8 @@ class HotPath:
             self._in_flight.pop(0).synchronize()
         if self.n_streams == 1:
             topology = self._submit_serial
+        elif stage == "full" and mask is None and self._takes_fused_step(audio):
+            topology = self._submit_fused
         elif self.n_fe_streams and stage != "reservoir":
             topology = self._submit_two_stages
         else:
@@ -299,6 +372,37 @@ class HotPath:
                 if ring is not None:
                     ring.release(st)
                 return feats, st
+
+    def _takes_fused_step(self, audio) -> bool:
+        """Whether a plain full step over `audio` is the one-launch step (decided once per batch size)."""
+        if not self.fused_step:
+            return False
+        n = int(len(audio))
+        ok = self._fused_ok.get(n)
+        if ok is None:
+            ok = self._fused_ok[n] = step_fused_supported(self.fe, self.net, n)
+        return ok
+
+    def _submit_fused(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None, mask=None):
+        """The whole step as one launch (`step_fused`) on stream (step number) % n_fused_streams.  With `time_reservoir` the
+        event pair brackets that launch: front end and reservoir of the step together."""
+        slot = (self._step - 1) % self.n_fused_streams
+        st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            self._wait_for_input(st, cur, audio, after)
+            x = self._to_device(audio, slot)
+            key = (slot, int(x.shape[0]))
+            ws = self._fused_ws.get(key)
+            if ws is None:
+                ws = self._fused_ws[key] = self.fe.new_workspace(key[1])
+            if self.time_reservoir:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            feats = step_fused(self.fe, self.net, x, self.feature_keys, stats_out=stats_out, features_out=out, workspace=ws)
+            if self.time_reservoir:
+                e1.record()
+                self.reservoir_events.append((e0, e1))
+            return feats, st
 
     def _low_latency(self, tail: bool) -> bool:
         """Whether this step's fused gammatone front end goes out in the low-latency layout: on a tail step, and when it
