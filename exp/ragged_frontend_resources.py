@@ -4,7 +4,11 @@ csrc/frontend.hip, csrc/mask.hip and csrc/mel.hip of a checkout of the parent co
 csrc/ragged_frontend.hip of this tree, compiled for the device with the build's flags and
 `-Rpass-analysis=kernel-resource-usage -S`: every existing kernel's compiler-reported registers, spills, scratch, occupancy
 and LDS parent against this tree, its instruction lines likewise (labels renumbered, comments and debug directives dropped),
-and the same figures of every new form beside the twin it shares its text with."""
+and the same figures of every new form beside the twin it shares its text with.
+
+`--units frontend,mask,ragged_frontend,step_fused,mel`: the comparison alone, for units that both trees have (the compiler
+part of profiles/frontend_launch_request.txt): a kernel symbol that only one tree has, a differing resource report and
+differing instruction lines each give a DIFFERS line."""
 import argparse
 import collections
 import os
@@ -22,7 +26,11 @@ from lsm_speech_classifier_amd import build  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--parent-tree", required=True, help="a checkout of the parent commit")
 ap.add_argument("--out", default=None, help="also write the lines to this file")
+ap.add_argument("--units", default=None, help="comma-separated csrc units that exist in both trees: compare just these, parent "
+                                              "against this tree (kernel symbols, resource reports, instruction lines)")
 args = ap.parse_args()
+UNITS = args.units.split(",") if args.units else ["frontend", "mask", "mel"]
+NEW_UNITS = [] if args.units else ["ragged_frontend"]
 FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
           "LDS Size [bytes/block]")
 
@@ -83,13 +91,12 @@ def row(r):
 lines = ["hipcc " + " ".join(build.CFLAGS) + " --cuda-device-only -S -Rpass-analysis=kernel-resource-usage csrc/<unit>.hip",
          "columns: " + " | ".join(FIELDS)]
 with tempfile.TemporaryDirectory() as tmp:
-    jobs = [(args.parent_tree, u, tmp) for u in ("frontend", "mask", "mel")] + \
-           [(ROOT, u, tmp) for u in ("frontend", "mask", "mel", "ragged_frontend")]
-    with ThreadPoolExecutor(max_workers=7) as ex:
+    jobs = [(args.parent_tree, u, tmp) for u in UNITS] + [(ROOT, u, tmp) for u in UNITS + NEW_UNITS]
+    with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
         done = list(ex.map(compile_unit, jobs))
     res = {(("parent" if t != ROOT else "this"), u): (remarks(err), bodies(out)) for (t, u, _), (out, err) in zip(jobs, done)}
 twins = {}
-for unit in ("frontend", "mask", "mel"):
+for unit in UNITS:
     (pr, pb), (nr, nb) = res[("parent", unit)], res[("this", unit)]
     same_r = [k for k in pr if nr.get(k) == pr[k]]
     same_b = [k for k in pb if nb.get(k) == pb[k]]
@@ -99,6 +106,14 @@ for unit in ("frontend", "mask", "mel"):
     for k in pr:
         if k not in same_r or (k in pb and k not in same_b):
             lines.append(f"  DIFFERS: {k}: {pr[k]} -> {nr.get(k)}")
+    for k in pb:
+        if k not in pr and k not in same_b:
+            lines.append(f"  DIFFERS: {k}: instruction lines")
+    for k in dict.fromkeys(list(nr) + list(nb)):
+        if k not in pr and k not in pb:
+            lines.append(f"  DIFFERS: {k}: not in the parent")
+    if args.units:
+        continue
     if unit == "frontend":
         twins = nr
         for k, r in nr.items():
@@ -107,8 +122,9 @@ for unit in ("frontend", "mask", "mel"):
     if unit == "mask":
         for k, r in nr.items():
             lines.append(f"  {short(k):64s} {row(r)}")
-rr, _ = res[("this", "ragged_frontend")]
-lines.append(f"csrc/ragged_frontend.hip: {len(rr)} kernels (new); each beside its twin of csrc/frontend.hip in brackets")
+rr = res[("this", "ragged_frontend")][0] if NEW_UNITS else {}
+if NEW_UNITS:
+    lines.append(f"csrc/ragged_frontend.hip: {len(rr)} kernels (new); each beside its twin of csrc/frontend.hip in brackets")
 for k, r in rr.items():
     t = k.replace("30gammatone_spikes_ragged_kernel", "23gammatone_spikes_kernel").replace(
         "28spec_to_spikes_ragged_kernel", "21spec_to_spikes_kernel")

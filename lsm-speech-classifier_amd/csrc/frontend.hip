@@ -203,44 +203,64 @@ int check_ragged(const void *counts_a, const void *counts_b, int time_bins, long
     return LSM_OK;
 }
 
-// `ragged`: the launch of lsm_spec_to_spikes_ragged_* (SPEC.md 1.14), ncols and time_bins the strides, clip_cols / clip_bins
-// the DEVICE counts
+// Which launch an export of the two spike encoders asks for: the export's own choice, never inferred from pointers -- but a
+// masked export given two null masks makes exactly the plain launch (include/lsm_hip_mask.h).
+enum class FrontForm { Plain, Masked, Ragged, Step };
+
+// One launch of spec_to_spikes: every lsm_spec_to_spikes_* export fills the members by name (split_request, then its form's),
+// launch_spec_to_spikes refuses in one order and launches.  A member that is not the form's is never read.
 template <typename T>
-int launch_spec_to_spikes(const T *db, int n_clips, int n_filters, int ncols, int time_bins,
-                          int apply_floor, const T *thr_on, const T *thr_off, int n_thr,
-                          int redundancy, uint8_t *raster, T *norm_out, void *stream,
-                          const uint32_t *freq_mask = nullptr, const uint32_t *time_mask = nullptr,
-                          bool ragged = false, const int32_t *clip_cols = nullptr, const int32_t *clip_bins = nullptr)
+struct SplitRequest {
+    FrontForm form = FrontForm::Plain;
+    const T *db = nullptr, *thr_on = nullptr, *thr_off = nullptr;
+    int n_clips = 0, n_filters = 0, ncols = 0, time_bins = 0, apply_floor = 0, n_thr = 0, redundancy = 0;
+    uint8_t *raster = nullptr;
+    T *norm_out = nullptr;
+    void *stream = nullptr;
+    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
+    const int32_t *clip_cols = nullptr, *clip_bins = nullptr;      // Ragged (1.14): DEVICE counts; ncols, time_bins the strides
+};
+
+template <typename T>           // what all six exports are given
+SplitRequest<T> split_request(const T *db, int n_clips, int n_filters, int ncols, int time_bins, int apply_floor,
+                              const T *thr_on, const T *thr_off, int n_thr, int redundancy, uint8_t *raster, T *norm_out,
+                              void *stream)
 {
-    LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && ncols >= 2 && time_bins >= 2, "bad shape");
-    LSM_REQUIRE(db != nullptr || n_clips == 0, "spec_to_spikes: null input");
-    LSM_REQUIRE(n_thr >= 0 && n_thr <= MAX_THR, "n_thr=%d outside [0, %d]", n_thr, MAX_THR);
-    LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
-    LSM_REQUIRE(n_thr == 0 || (thr_on && thr_off), "null threshold table");
-    LSM_REQUIRE(raster == nullptr || n_thr >= 1, "a raster needs at least one threshold");
-    if (n_clips == 0) return LSM_OK;
+    SplitRequest<T> r;
+    r.db = db; r.n_clips = n_clips; r.n_filters = n_filters; r.ncols = ncols; r.time_bins = time_bins;
+    r.apply_floor = apply_floor; r.thr_on = thr_on; r.thr_off = thr_off; r.n_thr = n_thr; r.redundancy = redundancy;
+    r.raster = raster; r.norm_out = norm_out; r.stream = stream;
+    return r;
+}
+
+template <typename T>
+int launch_spec_to_spikes(const SplitRequest<T> &r)
+{
+    LSM_REQUIRE(r.n_clips >= 0 && r.n_filters >= 1 && r.ncols >= 2 && r.time_bins >= 2, "bad shape");
+    LSM_REQUIRE(r.db != nullptr || r.n_clips == 0, "spec_to_spikes: null input");
+    LSM_REQUIRE(r.n_thr >= 0 && r.n_thr <= MAX_THR, "n_thr=%d outside [0, %d]", r.n_thr, MAX_THR);
+    LSM_REQUIRE(r.redundancy >= 1, "redundancy must be >= 1");
+    LSM_REQUIRE(r.n_thr == 0 || (r.thr_on && r.thr_off), "null threshold table");
+    LSM_REQUIRE(r.raster == nullptr || r.n_thr >= 1, "a raster needs at least one threshold");
+    if (r.n_clips == 0) return LSM_OK;
     SpikeArgs<T> a;
-    a.db = db; a.n_clips = n_clips; a.n_filters = n_filters; a.ncols = ncols;
-    a.time_bins = time_bins; a.apply_floor = apply_floor; a.n_thr = n_thr;
-    a.redundancy = redundancy; a.raster = raster; a.norm_out = norm_out;
-    fill_thresholds<T>(a.on, a.off, thr_on, thr_off, n_thr, (T)0, (T)0);
-    const size_t lds = lsm_fe::spikes_lds_bytes(time_bins, n_thr);
+    a.db = r.db; a.n_clips = r.n_clips; a.n_filters = r.n_filters; a.ncols = r.ncols;
+    a.time_bins = r.time_bins; a.apply_floor = r.apply_floor; a.n_thr = r.n_thr;
+    a.redundancy = r.redundancy; a.raster = r.raster; a.norm_out = r.norm_out;
+    fill_thresholds<T>(a.on, a.off, r.thr_on, r.thr_off, r.n_thr, (T)0, (T)0);
+    const size_t lds = lsm_fe::spikes_lds_bytes(r.time_bins, r.n_thr);
     LSM_REQUIRE(lds <= 160 * 1024, "latch bit rows of %zu bytes (time_bins x thresholds) exceed one CU's LDS", lds);
-    if (const int rc = check_masks(freq_mask, time_mask)) return rc;
-    if (freq_mask || time_mask) {                       // SPEC.md 1.13; without a mask the launch below is the twin's
-        lsm_fe::launch_spec_to_spikes_masked<T>(a, lsm_fe::MaskArgs{freq_mask, time_mask}, SPK_THREADS, lds, stream);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
+    if (r.form == FrontForm::Masked && (r.freq_mask || r.time_mask)) {     // without a mask the launch is the plain one
+        if (const int rc = check_masks(r.freq_mask, r.time_mask)) return rc;
+        lsm_fe::launch_spec_to_spikes_masked<T>(a, lsm_fe::MaskArgs{r.freq_mask, r.time_mask}, SPK_THREADS, lds, r.stream);
+    } else if (r.form == FrontForm::Ragged) {
+        if (const int rc = check_ragged(r.clip_cols, r.clip_bins, r.time_bins, 0, 0)) return rc;
+        lsm_fe::launch_spec_to_spikes_ragged<T>(a, lsm_fe::RaggedCounts{r.clip_cols, r.clip_bins}, SPK_THREADS, lds, r.stream);
+    } else {
+        auto fn = spec_to_spikes_kernel<T>;
+        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+        hipLaunchKernelGGL(fn, dim3(r.n_clips), dim3(SPK_THREADS), lds, (hipStream_t)r.stream, a);
     }
-    if (ragged) {                                       // SPEC.md 1.14
-        if (const int rc = check_ragged(clip_cols, clip_bins, time_bins, 0, 0)) return rc;
-        lsm_fe::launch_spec_to_spikes_ragged<T>(a, lsm_fe::RaggedCounts{clip_cols, clip_bins}, SPK_THREADS, lds, stream);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
-    }
-    auto fn = spec_to_spikes_kernel<T>;
-    if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
-    hipLaunchKernelGGL(fn, dim3(n_clips), dim3(SPK_THREADS), lds, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
@@ -333,9 +353,6 @@ static DevInfo dev_info()
 
 #define LSM_API extern "C" __attribute__((visibility("default")))
 
-// tags that pick a kernel instantiation (as pass_a does on the device)
-template <int N> using Int = std::integral_constant<int, N>;
-
 // SPEC.md 1.1: one channel would take NumPy's pairwise window sums in the reference; these kernels sum element by element
 static const char NEED_TWO_FILTERS[] =
     "the gammatone filterbank needs n_filters >= 2 (one channel: NumPy's pairwise window sums, SPEC.md 1.1)";
@@ -385,21 +402,16 @@ LSM_API int lsm_gammatone_spec_f64(const float *audio, int n_clips, int n_sample
     const dim3 grid((unsigned)n_wgs), block((unsigned)(64 * wpb));
     const bool fast = (coef_flags & 3) == 3;       // both properties verified by the host
     const int nw = (nwin + hop - 1) / hop;
-    auto launch = [&](auto nw_c, auto fast_c) {
-        constexpr bool FAST = decltype(fast_c)::value;
-        auto fn = gammatone_kernel<decltype(nw_c)::value, FAST, FAST>;
+    auto launch = [&](auto fn) {
         if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
         hipLaunchKernelGGL(fn, grid, block, (size_t)lds, (hipStream_t)stream, audio, n_clips, n_samples, coefs,
                            n_filters, nwin, hop, ncols, spec_out, db_out);
     };
-    auto launch_nw = [&](auto nw_c) {
-        if (fast) launch(nw_c, std::true_type{}); else launch(nw_c, std::false_type{});
-    };
     switch (nw) {
-    case 1: launch_nw(Int<1>{}); break;
-    case 2: launch_nw(Int<2>{}); break;
-    case 3: launch_nw(Int<3>{}); break;
-    default: launch_nw(Int<4>{}); break;
+    case 1: launch(fast ? gammatone_kernel<1, true, true> : gammatone_kernel<1, false, false>); break;
+    case 2: launch(fast ? gammatone_kernel<2, true, true> : gammatone_kernel<2, false, false>); break;
+    case 3: launch(fast ? gammatone_kernel<3, true, true> : gammatone_kernel<3, false, false>); break;
+    default: launch(fast ? gammatone_kernel<4, true, true> : gammatone_kernel<4, false, false>); break;
     }
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
@@ -466,51 +478,77 @@ LSM_API long lsm_gammatone_spikes_workspace(int n_clips, int n_filters, int ncol
     return (long)n_clips * ncols * (((n_filters + 127) / 128) * 2) * 64 * (long)sizeof(double);
 }
 
-// lsm_gammatone_spikes_f64 and its masked twin (include/lsm_hip_mask.h): the same refusals, plan and launch geometry; with a
-// mask the kernel is the masked instantiation (mask.hip), without one exactly the unmasked launch.
-static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
-                            const double *coefs, int n_filters, int nwin, int hop, int ncols,
-                            int time_bins, const double *thr_on, const double *thr_off, int n_thr,
-                            int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
-                            int coef_flags, int launch_flags, const uint32_t *freq_mask, const uint32_t *time_mask,
-                            void *stream, bool ragged = false, const int32_t *clip_bins = nullptr,
-                            int32_t *clip_steps_out = nullptr, lsm_fe::StepFront *step = nullptr)
+// One launch of the fused front end: lsm_gammatone_spikes_f64, its masked and ragged twins and step_front_args fill the members
+// by name (front_request, then their own), plan_front and gammatone_spikes read them; never one that is not the form's.
+struct FrontRequest {
+    FrontForm form = FrontForm::Plain;
+    const float *audio = nullptr;
+    const double *coefs = nullptr, *thr_on = nullptr, *thr_off = nullptr;
+    int n_clips = 0, n_samples = 0, n_filters = 0, nwin = 0, hop = 0, ncols = 0, time_bins = 0, n_thr = 0, redundancy = 0;
+    void *workspace = nullptr;
+    long workspace_bytes = 0;
+    int coef_flags = 0, launch_flags = 0;   // (a step's front half has no launch_flags, raster or stream: they stay 0)
+    uint8_t *raster = nullptr;              // (n_clips, n_filters * redundancy, time_bins * n_thr)
+    void *stream = nullptr;
+    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
+    const int32_t *clip_bins = nullptr;     // Ragged (1.14): DEVICE counts in and out; ncols, time_bins and n_samples the strides
+    int32_t *clip_steps_out = nullptr;
+    lsm_fe::StepFront *step = nullptr;      // Step (step_fused.hip): checked and planned into it, not launched
+};
+
+// what all five callers are given
+static FrontRequest front_request(const float *audio, int n_clips, int n_samples, const double *coefs, int n_filters, int nwin,
+                                  int hop, int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr,
+                                  int redundancy, void *workspace, long workspace_bytes, int coef_flags)
 {
-    LSM_REQUIRE((launch_flags & ~3) == 0, "launch_flags: only bit 0 (low-latency layout) and bit 1 (no LDS reservation) are defined");
-    LSM_REQUIRE(n_clips >= 0 && n_filters >= 1 && n_samples >= 1, "bad shape");
-    LSM_REQUIRE(n_filters >= 2, "%s", NEED_TWO_FILTERS);
-    LSM_REQUIRE(nwin >= 1 && hop >= 1 && ncols >= 2 && time_bins >= 2, "bad window");
-    if (const int rc = check_windows(n_samples, nwin, hop, ncols)) return rc;
-    LSM_REQUIRE(n_thr >= 1 && n_thr <= MAX_THR, "n_thr=%d outside [1, %d]", n_thr, MAX_THR);
-    LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
-    LSM_REQUIRE(thr_on && thr_off, "null threshold table");
-    if (n_clips == 0) return LSM_OK;
-    LSM_REQUIRE(audio && coefs && (raster || step) && workspace, "gammatone_spikes: null buffer");
-    LSM_REQUIRE(workspace_bytes >= lsm_gammatone_spikes_workspace(n_clips, n_filters, ncols),
-                "workspace of %ld bytes, need %ld (lsm_gammatone_spikes_workspace)", workspace_bytes,
-                lsm_gammatone_spikes_workspace(n_clips, n_filters, ncols));
-    LSM_REQUIRE(((uintptr_t)workspace & 7u) == 0, "workspace must be 8-byte aligned");
-    const int row_bytes = time_bins * n_thr;
-    LSM_REQUIRE((row_bytes & 3) != 0 || ((uintptr_t)raster & 3u) == 0,
+    FrontRequest r;
+    r.audio = audio; r.n_clips = n_clips; r.n_samples = n_samples; r.coefs = coefs; r.n_filters = n_filters; r.nwin = nwin;
+    r.hop = hop; r.ncols = ncols; r.time_bins = time_bins; r.thr_on = thr_on; r.thr_off = thr_off; r.n_thr = n_thr;
+    r.redundancy = redundancy; r.workspace = workspace; r.workspace_bytes = workspace_bytes; r.coef_flags = coef_flags;
+    return r;
+}
+
+// What a launch refuses, in the order that decides which reason a caller with two bad arguments reads (the form's own last),
+// the plan, the kernel's arguments and the launch geometry.  An empty batch is accepted before its buffers are: l->grid = 0.
+static int plan_front(const FrontRequest &r, FusedArgs *args, lsm_fe::FusedLaunch *l)
+{
+    const bool step = r.form == FrontForm::Step;
+    l->grid = 0;
+    LSM_REQUIRE((r.launch_flags & ~3) == 0, "launch_flags: only bit 0 (low-latency layout) and bit 1 (no LDS reservation) are defined");
+    LSM_REQUIRE(r.n_clips >= 0 && r.n_filters >= 1 && r.n_samples >= 1, "bad shape");
+    LSM_REQUIRE(r.n_filters >= 2, "%s", NEED_TWO_FILTERS);
+    LSM_REQUIRE(r.nwin >= 1 && r.hop >= 1 && r.ncols >= 2 && r.time_bins >= 2, "bad window");
+    if (const int rc = check_windows(r.n_samples, r.nwin, r.hop, r.ncols)) return rc;
+    LSM_REQUIRE(r.n_thr >= 1 && r.n_thr <= MAX_THR, "n_thr=%d outside [1, %d]", r.n_thr, MAX_THR);
+    LSM_REQUIRE(r.redundancy >= 1, "redundancy must be >= 1");
+    LSM_REQUIRE(r.thr_on && r.thr_off, "null threshold table");
+    if (r.n_clips == 0) return LSM_OK;
+    LSM_REQUIRE(r.audio && r.coefs && (r.raster || step) && r.workspace, "gammatone_spikes: null buffer");
+    LSM_REQUIRE(r.workspace_bytes >= lsm_gammatone_spikes_workspace(r.n_clips, r.n_filters, r.ncols),
+                "workspace of %ld bytes, need %ld (lsm_gammatone_spikes_workspace)", r.workspace_bytes,
+                lsm_gammatone_spikes_workspace(r.n_clips, r.n_filters, r.ncols));
+    LSM_REQUIRE(((uintptr_t)r.workspace & 7u) == 0, "workspace must be 8-byte aligned");
+    const int row_bytes = r.time_bins * r.n_thr;
+    LSM_REQUIRE((row_bytes & 3) != 0 || ((uintptr_t)r.raster & 3u) == 0,
                 "the raster must be 4-byte aligned when a row is a multiple of 4 bytes");
     FusedPlan pl;
-    if (!fused_plan(n_filters, n_clips, launch_flags, &pl, step != nullptr)) {
+    if (!fused_plan(r.n_filters, r.n_clips, r.launch_flags, &pl, step)) {
         lsm_set_error("gammatone_spikes: %d filters need more than %d waves per clip; use the split entry points",
-                      n_filters, GT_MAX_WPB);
+                      r.n_filters, GT_MAX_WPB);
         return LSM_ERR_UNSUPPORTED;
     }
-    FusedArgs a;
-    a.audio = audio; a.coefs = coefs; a.ws = static_cast<double *>(workspace); a.raster = raster;
-    a.n_clips = n_clips; a.n_samples = n_samples; a.n_filters = n_filters; a.nwin = nwin; a.hop = hop;
-    a.ncols = ncols; a.time_bins = time_bins; a.n_thr = n_thr; a.redundancy = redundancy; a.groups = pl.groups;
+    FusedArgs &a = *args;
+    a.audio = r.audio; a.coefs = r.coefs; a.ws = static_cast<double *>(r.workspace); a.raster = r.raster;
+    a.n_clips = r.n_clips; a.n_samples = r.n_samples; a.n_filters = r.n_filters; a.nwin = r.nwin; a.hop = r.hop;
+    a.ncols = r.ncols; a.time_bins = r.time_bins; a.n_thr = r.n_thr; a.redundancy = r.redundancy; a.groups = pl.groups;
     a.prio = 0;
     // unused table entries never fire: nothing is > +inf or < -inf (the kernel compares 4 or 8 thresholds)
-    fill_thresholds<double>(a.on, a.off, thr_on, thr_off, n_thr, INFINITY, -INFINITY);
-    const long n_waves = (long)pl.groups * n_clips;
+    fill_thresholds<double>(a.on, a.off, r.thr_on, r.thr_off, r.n_thr, INFINITY, -INFINITY);
+    const long n_waves = (long)pl.groups * r.n_clips;
     const long n_wgs = (n_waves + pl.wpb - 1) / pl.wpb;
     LSM_REQUIRE(n_wgs <= 0x7fffffffL, "too many clips for one launch");
     // per lane row: the raster bits of the channel (time_bins * n_thr bits), staged for the coalesced write-out
-    const int RW = (time_bins * n_thr + 31) / 32;
+    const int RW = (r.time_bins * r.n_thr + 31) / 32;
     long lds = 2 * GT_MAX_WPB * (long)sizeof(double) + (long)pl.wpb * pl.nch * (pl.pair ? 32 : 64) * RW * 4;
     LSM_REQUIRE(lds <= 160 * 1024, "raster stage of %ld bytes exceeds one CU's LDS", lds);
     // CU-exclusive placement of small launches (cu_exclusive_lds), with two exceptions.
@@ -521,59 +559,46 @@ static int gammatone_spikes(const float *audio, int n_clips, int n_samples,
     // next step's launch off the CUs until this one has left (cfg2, 4 hardware queues, medians of 3 runs: 1.10 -> 1.00
     // ms/step at 20 steps, 1.11 -> 0.98 at 200; 12 queues, one run each: 1.03 -> 1.00 and 0.98 -> 0.86;
     // profiles/r06_lane_pair_placement.txt)
-    if (!pl.pair && !(launch_flags & 2)) lds = cu_exclusive_lds(n_wgs, lds);
-    const dim3 grid((unsigned)n_wgs), block((unsigned)(64 * pl.wpb));
-    const bool fast = (coef_flags & 3) == 3;
-    const bool shb0 = fast && (coef_flags & 4) != 0;       // one b0 for every channel: shared between the two chains,
+    if (!pl.pair && !(r.launch_flags & 2)) lds = cu_exclusive_lds(n_wgs, lds);
+    const bool fast = (r.coef_flags & 3) == 3;
+    const bool shb0 = fast && (r.coef_flags & 4) != 0;     // one b0 for every channel: shared between the two chains,
                                                            // wave-uniform in the lane pair
-    const int nw = (nwin + hop - 1) / hop;
-    if (const int rc = check_masks(freq_mask, time_mask)) return rc;
-    if (step) {                                         // the fused step launch (step_fused.hip): checked and planned, not launched
-        step->l = lsm_fe::FusedLaunch{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
-        static_assert(sizeof(step->args) == sizeof(FusedArgs), "StepFront carries a FusedArgs");
-        memcpy(step->args, &a, sizeof(FusedArgs));
+    const int nw = (r.nwin + r.hop - 1) / r.hop;
+    *l = lsm_fe::FusedLaunch{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, (unsigned)n_wgs, (unsigned)(64 * pl.wpb), (size_t)lds};
+    // the forms' own refusals, behind the twin's
+    if (const int rc = r.form == FrontForm::Masked ? check_masks(r.freq_mask, r.time_mask) : LSM_OK) return rc;
+    if (r.form == FrontForm::Ragged) {
+        if (const int rc = check_ragged(r.clip_bins, r.clip_bins, r.time_bins, r.n_samples, r.hop)) return rc;
+        LSM_REQUIRE(((uintptr_t)r.clip_steps_out & 3u) == 0, "ragged: clip_steps_out must be 4-byte aligned");
+    }
+    return LSM_OK;
+}
+
+// this unit's kernel for the form table (gammatone_spikes_body.h, launch_fused_form)
+struct PlainFamily {
+    template <int NW, bool FAST, int NCH, bool SHB0, bool PAIR>
+    static auto kernel() { return gammatone_spikes_kernel<NW, FAST, NCH, SHB0, PAIR>; }
+};
+
+// Every caller ends here with the request it filled: checked and planned, then the form's launch, or a step's plan handed over.
+static int gammatone_spikes(const FrontRequest &r)
+{
+    FusedArgs a;
+    lsm_fe::FusedLaunch l;
+    const int rc = plan_front(r, &a, &l);
+    if (rc != LSM_OK || l.grid == 0) return rc;         // refused, or an empty batch
+    if (r.form == FrontForm::Step) {
+        r.step->l = l;
+        static_assert(sizeof(r.step->args) == sizeof(FusedArgs), "StepFront carries a FusedArgs");
+        memcpy(r.step->args, &a, sizeof(FusedArgs));
         return LSM_OK;
     }
-    if (freq_mask || time_mask) {                       // SPEC.md 1.13
-        const lsm_fe::FusedLaunch l{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
-        lsm_fe::launch_gammatone_spikes_masked(l, &a, lsm_fe::MaskArgs{freq_mask, time_mask}, stream);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
-    }
-    if (ragged) {                                       // SPEC.md 1.14: ncols and time_bins are strides, n_samples the row's
-        if (const int rc = check_ragged(clip_bins, clip_bins, time_bins, n_samples, hop)) return rc;
-        LSM_REQUIRE(((uintptr_t)clip_steps_out & 3u) == 0, "ragged: clip_steps_out must be 4-byte aligned");
-        const lsm_fe::FusedLaunch l{nw > 4 ? 4 : nw, pl.nch, fast, shb0, pl.pair, grid.x, block.x, (size_t)lds};
-        lsm_fe::launch_gammatone_spikes_ragged(l, &a, lsm_fe::RaggedArgs{clip_bins, clip_steps_out}, stream);
-        LSM_CHECK_HIP(hipGetLastError());
-        return LSM_OK;
-    }
-    auto launch = [&](auto nw_c, auto fast_c, auto nch_c, auto shb0_c, auto pair_c) {
-        auto fn = gammatone_spikes_kernel<decltype(nw_c)::value, decltype(fast_c)::value, decltype(nch_c)::value,
-                                          decltype(shb0_c)::value, decltype(pair_c)::value>;
-        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
-        hipLaunchKernelGGL(fn, grid, block, (size_t)lds, (hipStream_t)stream, a);
-    };
-    // the eight forms of a kernel: the shared b0 exists on the fast path only, and not with one chain per lane
-    auto launch_nw = [&](auto nw_c) {
-        using T = std::true_type;
-        using F = std::false_type;
-        if (fast) {
-            if (pl.pair) { if (shb0) launch(nw_c, T{}, Int<1>{}, T{}, T{}); else launch(nw_c, T{}, Int<1>{}, F{}, T{}); }
-            else if (pl.nch == 2) { if (shb0) launch(nw_c, T{}, Int<2>{}, T{}, F{}); else launch(nw_c, T{}, Int<2>{}, F{}, F{}); }
-            else launch(nw_c, T{}, Int<1>{}, F{}, F{});
-        } else {
-            if (pl.pair) launch(nw_c, F{}, Int<1>{}, F{}, T{});
-            else if (pl.nch == 2) launch(nw_c, F{}, Int<2>{}, F{}, F{});
-            else launch(nw_c, F{}, Int<1>{}, F{}, F{});
-        }
-    };
-    switch (nw) {
-    case 1: launch_nw(Int<1>{}); break;
-    case 2: launch_nw(Int<2>{}); break;
-    case 3: launch_nw(Int<3>{}); break;
-    default: launch_nw(Int<4>{}); break;
-    }
+    if (r.form == FrontForm::Masked && (r.freq_mask || r.time_mask))       // without a mask exactly the plain launch
+        lsm_fe::launch_gammatone_spikes_masked(l, &a, lsm_fe::MaskArgs{r.freq_mask, r.time_mask}, r.stream);
+    else if (r.form == FrontForm::Ragged)
+        lsm_fe::launch_gammatone_spikes_ragged(l, &a, lsm_fe::RaggedArgs{r.clip_bins, r.clip_steps_out}, r.stream);
+    else
+        launch_fused_form<PlainFamily>(l, r.stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
 }
@@ -584,8 +609,10 @@ LSM_API int lsm_gammatone_spikes_f64(const float *audio, int n_clips, int n_samp
                                      int redundancy, uint8_t *raster, void *workspace, long workspace_bytes,
                                      int coef_flags, int launch_flags, void *stream)
 {
-    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
-                            redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, nullptr, nullptr, stream);
+    FrontRequest r = front_request(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off,
+                                   n_thr, redundancy, workspace, workspace_bytes, coef_flags);
+    r.raster = raster; r.launch_flags = launch_flags; r.stream = stream;
+    return gammatone_spikes(r);
 }
 
 // step_fused.hip: lsm_gammatone_spikes_f64's refusals, plan and arguments for the front-end half of a fused step (no raster)
@@ -593,9 +620,10 @@ int lsm_fe::step_front_args(const float *audio, int n_clips, int n_samples, cons
                             int hop, int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr,
                             int redundancy, void *workspace, long workspace_bytes, int coef_flags, StepFront *out)
 {
-    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
-                            redundancy, nullptr, workspace, workspace_bytes, coef_flags, 0, nullptr, nullptr, nullptr, false,
-                            nullptr, nullptr, out);
+    FrontRequest r = front_request(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off,
+                                   n_thr, redundancy, workspace, workspace_bytes, coef_flags);
+    r.form = FrontForm::Step; r.step = out;
+    return gammatone_spikes(r);
 }
 
 LSM_API int lsm_gammatone_spikes_masked_f64(const float *audio, int n_clips, int n_samples,
@@ -605,9 +633,11 @@ LSM_API int lsm_gammatone_spikes_masked_f64(const float *audio, int n_clips, int
                                             int coef_flags, int launch_flags, const uint32_t *freq_mask,
                                             const uint32_t *time_mask, void *stream)
 {
-    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
-                            redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, freq_mask, time_mask,
-                            stream);
+    FrontRequest r = front_request(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off,
+                                   n_thr, redundancy, workspace, workspace_bytes, coef_flags);
+    r.raster = raster; r.launch_flags = launch_flags; r.stream = stream;
+    r.form = FrontForm::Masked; r.freq_mask = freq_mask; r.time_mask = time_mask;
+    return gammatone_spikes(r);
 }
 
 // include/lsm_hip_ragged.h (SPEC.md 1.14): the twins' parameters with per-clip DEVICE counts; kernels in ragged_frontend.hip
@@ -618,9 +648,11 @@ LSM_API int lsm_gammatone_spikes_ragged_f64(const float *audio, int n_clips, int
                                             int32_t *clip_steps_out, void *workspace, long workspace_bytes,
                                             int coef_flags, int launch_flags, void *stream)
 {
-    return gammatone_spikes(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
-                            redundancy, raster, workspace, workspace_bytes, coef_flags, launch_flags, nullptr, nullptr, stream,
-                            true, clip_bins, clip_steps_out);
+    FrontRequest r = front_request(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off,
+                                   n_thr, redundancy, workspace, workspace_bytes, coef_flags);
+    r.raster = raster; r.launch_flags = launch_flags; r.stream = stream;
+    r.form = FrontForm::Ragged; r.clip_bins = clip_bins; r.clip_steps_out = clip_steps_out;
+    return gammatone_spikes(r);
 }
 
 LSM_API int lsm_spec_to_spikes_ragged_f64(const double *db, int n_clips, int n_filters, int ncols, int time_bins,
@@ -628,8 +660,10 @@ LSM_API int lsm_spec_to_spikes_ragged_f64(const double *db, int n_clips, int n_f
                                           const double *thr_on, const double *thr_off, int n_thr, int redundancy,
                                           uint8_t *raster, double *norm_out, void *stream)
 {
-    return launch_spec_to_spikes<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
-                                         redundancy, raster, norm_out, stream, nullptr, nullptr, true, clip_cols, clip_bins);
+    SplitRequest<double> r = split_request<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                                   redundancy, raster, norm_out, stream);
+    r.form = FrontForm::Ragged; r.clip_cols = clip_cols; r.clip_bins = clip_bins;
+    return launch_spec_to_spikes(r);
 }
 
 LSM_API int lsm_spec_to_spikes_ragged_f32(const float *db, int n_clips, int n_filters, int ncols, int time_bins,
@@ -637,8 +671,10 @@ LSM_API int lsm_spec_to_spikes_ragged_f32(const float *db, int n_clips, int n_fi
                                           const float *thr_on, const float *thr_off, int n_thr, int redundancy,
                                           uint8_t *raster, float *norm_out, void *stream)
 {
-    return launch_spec_to_spikes<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
-                                        redundancy, raster, norm_out, stream, nullptr, nullptr, true, clip_cols, clip_bins);
+    SplitRequest<float> r = split_request<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                                 redundancy, raster, norm_out, stream);
+    r.form = FrontForm::Ragged; r.clip_cols = clip_cols; r.clip_bins = clip_bins;
+    return launch_spec_to_spikes(r);
 }
 
 LSM_API int lsm_spec_to_spikes_masked_f64(const double *db, int n_clips, int n_filters, int ncols,
@@ -647,8 +683,10 @@ LSM_API int lsm_spec_to_spikes_masked_f64(const double *db, int n_clips, int n_f
                                           uint8_t *raster, double *norm_out, const uint32_t *freq_mask,
                                           const uint32_t *time_mask, void *stream)
 {
-    return launch_spec_to_spikes<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor,
-                                         thr_on, thr_off, n_thr, redundancy, raster, norm_out, stream, freq_mask, time_mask);
+    SplitRequest<double> r = split_request<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                                   redundancy, raster, norm_out, stream);
+    r.form = FrontForm::Masked; r.freq_mask = freq_mask; r.time_mask = time_mask;
+    return launch_spec_to_spikes(r);
 }
 
 LSM_API int lsm_spec_to_spikes_masked_f32(const float *db, int n_clips, int n_filters, int ncols,
@@ -657,8 +695,10 @@ LSM_API int lsm_spec_to_spikes_masked_f32(const float *db, int n_clips, int n_fi
                                           uint8_t *raster, float *norm_out, const uint32_t *freq_mask,
                                           const uint32_t *time_mask, void *stream)
 {
-    return launch_spec_to_spikes<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor,
-                                        thr_on, thr_off, n_thr, redundancy, raster, norm_out, stream, freq_mask, time_mask);
+    SplitRequest<float> r = split_request<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                                 redundancy, raster, norm_out, stream);
+    r.form = FrontForm::Masked; r.freq_mask = freq_mask; r.time_mask = time_mask;
+    return launch_spec_to_spikes(r);
 }
 
 LSM_API int lsm_spec_to_spikes_f64(const double *db, int n_clips, int n_filters, int ncols,
@@ -666,8 +706,8 @@ LSM_API int lsm_spec_to_spikes_f64(const double *db, int n_clips, int n_filters,
                                    const double *thr_off, int n_thr, int redundancy,
                                    uint8_t *raster, double *norm_out, void *stream)
 {
-    return launch_spec_to_spikes<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor,
-                                         thr_on, thr_off, n_thr, redundancy, raster, norm_out, stream);
+    return launch_spec_to_spikes(split_request<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off,
+                                                       n_thr, redundancy, raster, norm_out, stream));
 }
 
 LSM_API int lsm_spec_to_spikes_f32(const float *db, int n_clips, int n_filters, int ncols,
@@ -675,8 +715,8 @@ LSM_API int lsm_spec_to_spikes_f32(const float *db, int n_clips, int n_filters, 
                                    const float *thr_off, int n_thr, int redundancy,
                                    uint8_t *raster, float *norm_out, void *stream)
 {
-    return launch_spec_to_spikes<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor,
-                                        thr_on, thr_off, n_thr, redundancy, raster, norm_out, stream);
+    return launch_spec_to_spikes(split_request<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off,
+                                                      n_thr, redundancy, raster, norm_out, stream));
 }
 
 LSM_API int lsm_encode_hysteresis_f64(const double *spec, int n_rows, int n_bins,

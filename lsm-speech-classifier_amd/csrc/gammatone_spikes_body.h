@@ -1,5 +1,6 @@
 // gammatone_spikes_body.h -- the fused gammatone front end (filterbank -> dB -> normalise -> resize -> hysteresis encoder ->
-// raster in ONE launch): its argument type, its helpers and the kernel that frontend.hip launches.  The kernel's text is
+// raster in ONE launch): its argument type, its helpers, the kernel that frontend.hip launches and the one table that picks a
+// form of it for every unit that instantiates its text (launch_fused_form, at the end).  The kernel's text is
 // gammatone_spikes_kernel.inc; the masked kernel (mask.hip, SPEC.md 1.13) is the same text with MASK = true, in a
 // translation unit of its own, compiled beside frontend.hip.
 // Everything here sits in an unnamed namespace, as it did inside frontend.hip: the kernels' symbols carry that
@@ -100,8 +101,9 @@ struct FusedLaunch {
     size_t lds;
 };
 
-// The masked twins of the launches in frontend.hip, defined in mask.hip (their kernels are a translation unit of their own).
-// `fused_args`: a FusedArgs -- the type lives in each unit's unnamed namespace, so it crosses between them as bytes.
+// The masked launches, defined in mask.hip (their kernels are a translation unit of their own); frontend.hip calls them once
+// its one check (plan_front, launch_spec_to_spikes) has passed.  `fused_args`: a FusedArgs -- the type lives in each unit's
+// unnamed namespace, so it crosses between units as bytes: here, at the ragged launch below and in StepFront, nowhere else.
 void launch_gammatone_spikes_masked(const FusedLaunch &l, const void *fused_args, const MaskArgs &m, void *stream);
 template <typename T>
 void launch_spec_to_spikes_masked(const SpikeArgs<T> &a, const MaskArgs &m, int threads, size_t lds, void *stream);
@@ -116,9 +118,49 @@ int step_front_args(const float *audio, int n_clips, int n_samples, const double
                     int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr, int redundancy,
                     void *workspace, long workspace_bytes, int coef_flags, StepFront *out);
 
-// The ragged twins (SPEC.md 1.14), defined in ragged_frontend.hip, likewise a translation unit of its own
+// The ragged launches (SPEC.md 1.14), defined in ragged_frontend.hip, likewise a translation unit of its own
 void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args, const RaggedArgs &rg, void *stream);
 template <typename T>
 void launch_spec_to_spikes_ragged(const SpikeArgs<T> &a, const RaggedCounts &rc, int threads, size_t lds, void *stream);
 
 }  // namespace lsm_fe
+
+namespace {
+
+// The form table of the fused kernel, once for every translation unit that instantiates its text.  `Family` names the unit's
+// kernel: a struct whose `template <int NW, bool FAST, int NCH, bool SHB0, bool PAIR> static auto kernel()` returns it;
+// `args` are the kernel's arguments (the FusedArgs, then the family's own: none, MaskArgs or RaggedArgs).
+template <typename Family, typename... Args>
+void launch_fused_form(const lsm_fe::FusedLaunch &l, void *stream, const Args &...args)
+{
+    using T = std::true_type;
+    using F = std::false_type;
+    using One = std::integral_constant<int, 1>;
+    using Two = std::integral_constant<int, 2>;
+    auto launch = [&](auto nw_c, auto fast_c, auto nch_c, auto shb0_c, auto pair_c) {
+        auto fn = Family::template kernel<decltype(nw_c)::value, decltype(fast_c)::value, decltype(nch_c)::value,
+                                          decltype(shb0_c)::value, decltype(pair_c)::value>();
+        if (l.lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+        hipLaunchKernelGGL(fn, dim3(l.grid), dim3(l.block), l.lds, (hipStream_t)stream, args...);
+    };
+    // the eight forms of a kernel: the shared b0 exists on the fast path only, and not with one chain per lane
+    auto launch_nw = [&](auto nw_c) {
+        if (l.fast) {
+            if (l.pair) { if (l.shb0) launch(nw_c, T{}, One{}, T{}, T{}); else launch(nw_c, T{}, One{}, F{}, T{}); }
+            else if (l.nch == 2) { if (l.shb0) launch(nw_c, T{}, Two{}, T{}, F{}); else launch(nw_c, T{}, Two{}, F{}, F{}); }
+            else launch(nw_c, T{}, One{}, F{}, F{});
+        } else {
+            if (l.pair) launch(nw_c, F{}, One{}, F{}, T{});
+            else if (l.nch == 2) launch(nw_c, F{}, Two{}, F{}, F{});
+            else launch(nw_c, F{}, One{}, F{}, F{});
+        }
+    };
+    switch (l.nw) {
+    case 1: launch_nw(std::integral_constant<int, 1>{}); break;
+    case 2: launch_nw(std::integral_constant<int, 2>{}); break;
+    case 3: launch_nw(std::integral_constant<int, 3>{}); break;
+    default: launch_nw(std::integral_constant<int, 4>{}); break;
+    }
+}
+
+}  // namespace

@@ -1,8 +1,9 @@
 // Clips of different lengths in one front-end launch (SPEC.md 1.14, include/lsm_hip_ragged.h).  The kernels here are the
 // RAGGED = true forms of the code that frontend.hip runs with RAGGED = false (spikes_body.h's device function,
 // gammatone_spikes_kernel.inc's kernel text), in a translation unit of their own like the masked forms (mask.hip), and the
-// ragged power_to_db, which has no twin to share text with.  The entry points of the two spike encoders, their refusals and
-// the launch geometry are frontend.hip's: it calls the two launch functions below once everything is checked.
+// ragged power_to_db, which has no twin to share text with.  The entry points of the two spike encoders fill a launch request
+// in frontend.hip, which alone refuses, plans and builds the arguments, then calls the two launch functions below; the fused
+// kernel's form is picked by the one table (launch_fused_form, gammatone_spikes_body.h).
 //
 // Every per-clip count is read on the device, by the kernel that uses it, and clamped there: the host never sees one.
 #include "lsm_common.h"
@@ -32,7 +33,11 @@ __global__ __launch_bounds__(256) void spec_to_spikes_ragged_kernel(const lsm_fe
 #undef LSM_FUSED_MASK
 #undef LSM_FUSED_RAGGED
 
-template <int N> using Int = std::integral_constant<int, N>;
+// this unit's kernel for the form table (gammatone_spikes_body.h, launch_fused_form)
+struct RaggedFamily {
+    template <int NW, bool FAST, int NCH, bool SHB0, bool PAIR>
+    static auto kernel() { return gammatone_spikes_ragged_kernel<NW, FAST, NCH, SHB0, PAIR>; }
+};
 
 // librosa.power_to_db(S, ref=np.max) of clip b's first nf frames (mel.hip's power_to_db_body on rows of a stride): the
 // reference maximum and the NaN rule over those frames only, columns past them written as 0.  One 256-thread workgroup.
@@ -83,33 +88,7 @@ template void launch_spec_to_spikes_ragged<float>(const SpikeArgs<float> &, cons
 
 void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args, const RaggedArgs &rg, void *stream)
 {
-    const FusedArgs &a = *static_cast<const FusedArgs *>(fused_args);
-    auto launch = [&](auto nw_c, auto fast_c, auto nch_c, auto shb0_c, auto pair_c) {
-        auto fn = gammatone_spikes_ragged_kernel<decltype(nw_c)::value, decltype(fast_c)::value, decltype(nch_c)::value,
-                                                 decltype(shb0_c)::value, decltype(pair_c)::value>;
-        if (l.lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
-        hipLaunchKernelGGL(fn, dim3(l.grid), dim3(l.block), l.lds, (hipStream_t)stream, a, rg);
-    };
-    // the eight forms of a kernel, as in lsm_gammatone_spikes_f64
-    auto launch_nw = [&](auto nw_c) {
-        using T = std::true_type;
-        using F = std::false_type;
-        if (l.fast) {
-            if (l.pair) { if (l.shb0) launch(nw_c, T{}, Int<1>{}, T{}, T{}); else launch(nw_c, T{}, Int<1>{}, F{}, T{}); }
-            else if (l.nch == 2) { if (l.shb0) launch(nw_c, T{}, Int<2>{}, T{}, F{}); else launch(nw_c, T{}, Int<2>{}, F{}, F{}); }
-            else launch(nw_c, T{}, Int<1>{}, F{}, F{});
-        } else {
-            if (l.pair) launch(nw_c, F{}, Int<1>{}, F{}, T{});
-            else if (l.nch == 2) launch(nw_c, F{}, Int<2>{}, F{}, F{});
-            else launch(nw_c, F{}, Int<1>{}, F{}, F{});
-        }
-    };
-    switch (l.nw) {
-    case 1: launch_nw(Int<1>{}); break;
-    case 2: launch_nw(Int<2>{}); break;
-    case 3: launch_nw(Int<3>{}); break;
-    default: launch_nw(Int<4>{}); break;
-    }
+    launch_fused_form<RaggedFamily>(l, stream, *static_cast<const FusedArgs *>(fused_args), rg);
 }
 
 }  // namespace lsm_fe

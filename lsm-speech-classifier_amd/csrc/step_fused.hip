@@ -6,6 +6,7 @@
 // write the uint8 raster (13 MB per 256 clips x 128 channels x 400 steps), read it back, re-pack it with LDS atomics, and tie two
 // launches of two streams with an event.  With 4 hardware queues or fewer the pipeline (pipeline.HotPath) takes this launch.
 // The entry point's refusals and the arguments of the two halves are frontend.hip's and reservoir.hip's (step_front_args,
+// which fills the front end's launch request in its Step form and gets the plan back instead of a launch, and
 // step_dense_args); the translation unit is its own so that the existing kernels keep their machine code.
 #include "lsm_common.h"
 #include "gammatone_spikes_body.h"
@@ -49,7 +50,8 @@ namespace {
 typedef void (*step_fn_t)(const FusedArgs, const lsm_lif::DenseArgs);
 
 // The forms built: 3 live windows (2 * hop < nwin <= 3 * hop: the front end's 25 ms window on its 10 ms hop), the fast
-// coefficient path, with and without the shared b0.
+// coefficient path, with and without the shared b0.  Not the shared form table (launch_fused_form): these are three kernel
+// texts, one per SL, in two forms each, and the table would instantiate all eight forms of every one.
 step_fn_t pick_step(int sl, bool shb0)
 {
     switch (sl) {

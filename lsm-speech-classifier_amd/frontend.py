@@ -218,6 +218,32 @@ class SpikeFrontEnd:
             return self._mel.new_workspace(n_clips)
         return torch.empty((self.workspace_elems(n_clips),), dtype=torch.float64, device=self.device)
 
+    def _raster_for(self, n_clips: int, raster_out) -> torch.Tensor:
+        """The uint8 raster (n_clips, C, n_steps) of a launch: the caller's ``raster_out``, checked, or a new one."""
+        shape = (n_clips, self.n_channels, self.n_steps)
+        if raster_out is None:
+            return torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if (raster_out.dtype != torch.uint8 or tuple(raster_out.shape) != shape or not raster_out.is_contiguous()
+                or raster_out.device != self.device):
+            raise ValueError(f"raster_out must be a contiguous uint8 {shape} tensor on {self.device}")
+        return raster_out
+
+    def _workspace_for(self, n_clips: int, workspace):
+        """The scratch of a fused gammatone launch of ``n_clips`` clips and the bytes the launch needs of it: the caller's
+        ``workspace``, checked, or a new one."""
+        ws_bytes = int(self.lib.lsm_gammatone_spikes_workspace(n_clips, self.n_filters, self.ncols))
+        if workspace is None:
+            return torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device), ws_bytes
+        if (workspace.dtype != torch.float64 or workspace.numel() * 8 < ws_bytes or not workspace.is_contiguous()
+                or workspace.device != self.device):
+            raise ValueError(f"workspace must be a contiguous float64 tensor of >= {ws_bytes // 8} elements on {self.device}")
+        return workspace, ws_bytes
+
+    @staticmethod
+    def _launch_flags(low_latency: bool, share_lds: bool) -> int:
+        """`lsm_gammatone_spikes_f64`'s launch_flags: bit 0 the low-latency layout, bit 1 no LDS reservation."""
+        return (1 if low_latency else 0) | (2 if share_lds else 0)
+
     def _audio(self, audio) -> torch.Tensor:
         audio = as_float32(audio).to(self.device)
         if audio.dim() == 1:
@@ -312,25 +338,11 @@ class SpikeFrontEnd:
                 return self._mel.spikes(audio, on32, off32, self.time_bins, self.redundancy, raster_out, workspace, masks)
         on, off = threshold_tables(self.thresholds, self.gap, np.float64)
         with torch.cuda.device(self.device):
-            shape = (B, self.n_channels, self.n_steps)
-            if raster_out is not None:
-                if (raster_out.dtype != torch.uint8 or tuple(raster_out.shape) != shape or not raster_out.is_contiguous()
-                        or raster_out.device != self.device):
-                    raise ValueError(f"raster_out must be a contiguous uint8 {shape} tensor on {self.device}")
-                raster = raster_out
-            else:
-                raster = torch.empty(shape, dtype=torch.uint8, device=self.device)
-            ws_bytes = int(self.lib.lsm_gammatone_spikes_workspace(B, self.n_filters, self.ncols))
-            if workspace is not None:
-                if (workspace.dtype != torch.float64 or workspace.numel() * 8 < ws_bytes or not workspace.is_contiguous()
-                        or workspace.device != self.device):
-                    raise ValueError(f"workspace must be a contiguous float64 tensor of >= {ws_bytes // 8} elements on {self.device}")
-                ws = workspace
-            else:
-                ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
+            raster = self._raster_for(B, raster_out)
+            ws, ws_bytes = self._workspace_for(B, workspace)
             args = (_dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
                     self.ncols, self.time_bins, _host(on), _host(off), len(on), self.redundancy, _dev(raster),
-                    _dev(ws), ws_bytes, self.coef_flags, (1 if low_latency else 0) | (2 if share_lds else 0))
+                    _dev(ws), ws_bytes, self.coef_flags, self._launch_flags(low_latency, share_lds))
             if mask is None:
                 _lib.check(self.lib.lsm_gammatone_spikes_f64(*args, self._stream()), "lsm_gammatone_spikes_f64")
             else:
@@ -407,30 +419,18 @@ class SpikeFrontEnd:
             raise ValueError("the mel branch has no one-launch ragged kernel: encode_ragged takes its split route (fused=False)")
         if not fused and workspace is not None:
             raise ValueError("workspace belongs to the fused launch; this call takes the split route")
-        shape = (B, self.n_channels, self.n_steps)
-        if raster_out is not None and (raster_out.dtype != torch.uint8 or tuple(raster_out.shape) != shape
-                                       or not raster_out.is_contiguous() or raster_out.device != self.device):
-            raise ValueError(f"raster_out must be a contiguous uint8 {shape} tensor on {self.device}")
+        raster = self._raster_for(B, raster_out)        # (refused before the bins are looked at, the workspace after them)
         n_thr = len(self.thresholds)
         with torch.cuda.device(self.device):
             bins_dev = self._device_bins(bins, B)
-            raster = raster_out if raster_out is not None else torch.empty(shape, dtype=torch.uint8, device=self.device)
             if fused:
                 on, off = threshold_tables(self.thresholds, self.gap, np.float64)
                 steps = torch.empty((B,), dtype=torch.int32, device=self.device)
-                ws_bytes = int(self.lib.lsm_gammatone_spikes_workspace(B, self.n_filters, self.ncols))
-                if workspace is not None:
-                    if (workspace.dtype != torch.float64 or workspace.numel() * 8 < ws_bytes or not workspace.is_contiguous()
-                            or workspace.device != self.device):
-                        raise ValueError(f"workspace must be a contiguous float64 tensor of >= {ws_bytes // 8} elements on "
-                                         f"{self.device}")
-                    ws = workspace
-                else:
-                    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=self.device)
+                ws, ws_bytes = self._workspace_for(B, workspace)
                 _lib.check(self.lib.lsm_gammatone_spikes_ragged_f64(
                     _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop, self.ncols,
                     self.time_bins, _dev(bins_dev), _host(on), _host(off), len(on), self.redundancy, _dev(raster), _dev(steps),
-                    _dev(ws), ws_bytes, self.coef_flags, (1 if low_latency else 0) | (2 if share_lds else 0), self._stream()),
+                    _dev(ws), ws_bytes, self.coef_flags, self._launch_flags(low_latency, share_lds), self._stream()),
                     "lsm_gammatone_spikes_ragged_f64")
                 return raster, steps
             t = self._clamped_bins(bins_dev)

@@ -79,14 +79,7 @@ def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=N
     with torch.cuda.device(fe.device):
         if features_out is None:
             feats = torch.empty(shape, dtype=torch.float32, device=fe.device)
-        ws_bytes = int(fe.lib.lsm_gammatone_spikes_workspace(B, fe.n_filters, fe.ncols))
-        if workspace is not None:
-            if (workspace.dtype != torch.float64 or workspace.numel() * 8 < ws_bytes or not workspace.is_contiguous()
-                    or workspace.device != fe.device):
-                raise ValueError(f"workspace must be a contiguous float64 tensor of >= {ws_bytes // 8} elements on {fe.device}")
-            ws = workspace
-        else:
-            ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=fe.device)
+        ws, ws_bytes = fe._workspace_for(B, workspace)
         _lib.check(fe.lib.lsm_step_fused_f64(
             net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
             _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids), len(keys),

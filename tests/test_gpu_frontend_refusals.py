@@ -2,7 +2,8 @@
 with the message of the check that csrc/frontend.hip reaches first, word for word.  The order is part of the ABI's
 behaviour -- it decides which reason a caller reads -- and the two entry points do not share it: the split one accepts an
 empty batch before it looks at buffers and windows, the fused one after every argument check (threshold tables included)
-and before the buffers.  Shapes of 2 filters x 16 samples; every call is refused or empty, so nothing is launched and the
+and before the buffers.  The fused one's masked and ragged twins refuse what it refuses, in its order and words, and their own
+arguments after that.  Shapes of 2 filters x 16 samples; every call is refused or empty, so nothing is launched and the
 host arrays passed as buffers are never read."""
 import numpy as np
 import pytest
@@ -45,6 +46,21 @@ SPIKES_BOTH_BAD = [
     (dict(workspace_bytes=8, workspace="+4"), b"workspace of 8 bytes, need 4096 (lsm_gammatone_spikes_workspace)"),
     (dict(workspace="+4", raster="+1"), b"workspace must be 8-byte aligned"),
 ]
+# The masked and the ragged twin (include/lsm_hip_mask.h, lsm_hip_ragged.h): "the twin's refusals first, in the twin's order"
+# is the whole table above, word for word; then each form's own refusal loses to the last of the twin's, and stands alone.
+MASKED_PARAMS = SPIKES_PARAMS[:-1] + ["freq_mask", "time_mask", "stream"]
+RAGGED_PARAMS = ("audio n_clips n_samples coefs n_filters nwin hop ncols time_bins clip_bins thr_on thr_off n_thr redundancy "
+                 "raster clip_steps_out workspace workspace_bytes coef_flags launch_flags stream").split()
+MASKED_OWN = [
+    (dict(freq_mask="+1", workspace="+4"), b"workspace must be 8-byte aligned"),
+    (dict(time_mask="+2"), b"freq_mask and time_mask must be 4-byte aligned"),
+]
+RAGGED_OWN = [
+    (dict(clip_bins="+1", workspace="+4"), b"workspace must be 8-byte aligned"),
+    (dict(clip_bins=None, time_bins=2, ncols=2), b"ragged: null per-clip count array"),
+    (dict(clip_bins="+1", clip_steps_out="+2"), b"ragged: per-clip count arrays must be 4-byte aligned"),
+    (dict(clip_steps_out="+2"), b"ragged: clip_steps_out must be 4-byte aligned"),
+]
 
 
 def test_the_first_refusal_wins_in_both_gammatone_entry_points():
@@ -61,7 +77,14 @@ def test_the_first_refusal_wins_in_both_gammatone_entry_points():
     raster = np.full((n_clips, n_filters, time_bins * n_thr + 8), 0xAB, dtype=np.uint8)
     workspace = np.full(need // 8 + 1, np.nan)
     assert workspace.ctypes.data % 8 == 0 and raster.ctypes.data % 4 == 0 and (time_bins * n_thr) % 4 == 0
-    good = dict(audio=audio.ctypes.data, n_clips=n_clips, n_samples=n_samples, coefs=coefs.ctypes.data,
+    # the twins' own arrays (device arrays in a launch; here never read): mask words, bin counts in, step counts out
+    masks = np.full(4, 0xABABABAB, dtype=np.uint32)
+    counts = np.full(4, 0x2B2B2B2B, dtype=np.int32)
+    assert masks.ctypes.data % 4 == 0 and counts.ctypes.data % 4 == 0
+    assert time_bins >= 3 and n_samples >= hop * time_bins            # the ragged preconditions hold for the good call
+    twins_own = dict(freq_mask=masks.ctypes.data, time_mask=masks.ctypes.data + 8, clip_bins=counts.ctypes.data,
+                     clip_steps_out=counts.ctypes.data + 8)
+    good = dict(**twins_own,audio=audio.ctypes.data, n_clips=n_clips, n_samples=n_samples, coefs=coefs.ctypes.data,
                 n_filters=n_filters, nwin=nwin, hop=hop, ncols=ncols, time_bins=time_bins, thr_on=thr_on.ctypes.data,
                 thr_off=thr_off.ctypes.data, n_thr=n_thr, redundancy=1, spec_out=spec_out.ctypes.data,
                 db_out=db_out.ctypes.data, raster=raster.ctypes.data, workspace=workspace.ctypes.data,
@@ -74,7 +97,9 @@ def test_the_first_refusal_wins_in_both_gammatone_entry_points():
         return getattr(lib, export)(*[values[name] for name in params])
 
     for export, params, table in (("lsm_gammatone_spec_f64", SPEC_PARAMS, SPEC_BOTH_BAD),
-                                  ("lsm_gammatone_spikes_f64", SPIKES_PARAMS, SPIKES_BOTH_BAD)):
+                                  ("lsm_gammatone_spikes_f64", SPIKES_PARAMS, SPIKES_BOTH_BAD),
+                                  ("lsm_gammatone_spikes_masked_f64", MASKED_PARAMS, SPIKES_BOTH_BAD + MASKED_OWN),
+                                  ("lsm_gammatone_spikes_ragged_f64", RAGGED_PARAMS, SPIKES_BOTH_BAD + RAGGED_OWN)):
         for bad, message in table:
             rc = call(export, params, bad)
             assert rc == LSM_ERR_ARG and lib.lsm_last_error() == message, (export, bad, rc, lib.lsm_last_error())
@@ -87,6 +112,11 @@ def test_the_first_refusal_wins_in_both_gammatone_entry_points():
     assert call("lsm_gammatone_spikes_f64", SPIKES_PARAMS, empty) == LSM_OK, lib.lsm_last_error()
     assert call("lsm_gammatone_spikes_f64", SPIKES_PARAMS, {**empty, "thr_on": None, "thr_off": None}) == LSM_ERR_ARG
     assert lib.lsm_last_error() == b"null threshold table"
+    # the twins likewise, with null buffers and with null mask and count arrays as well
+    for export, params in (("lsm_gammatone_spikes_masked_f64", MASKED_PARAMS), ("lsm_gammatone_spikes_ragged_f64", RAGGED_PARAMS)):
+        assert call(export, params, empty) == LSM_OK, (export, lib.lsm_last_error())
+        own = {k: None for k in twins_own if k in params}
+        assert call(export, params, {**empty, **own}) == LSM_OK, (export, lib.lsm_last_error())
     # ... and before the windows by the split entry point, after them by the fused one
     assert call("lsm_gammatone_spec_f64", SPEC_PARAMS, dict(n_clips=0, nwin=17)) == LSM_OK, lib.lsm_last_error()
     assert call("lsm_gammatone_spikes_f64", SPIKES_PARAMS, dict(n_clips=0, nwin=17)) == LSM_ERR_ARG
@@ -94,3 +124,4 @@ def test_the_first_refusal_wins_in_both_gammatone_entry_points():
 
     # nothing was launched: no buffer was written
     assert np.isnan(spec_out).all() and np.isnan(db_out).all() and np.isnan(workspace).all() and (raster == 0xAB).all()
+    assert (masks == 0xABABABAB).all() and (counts == 0x2B2B2B2B).all()
