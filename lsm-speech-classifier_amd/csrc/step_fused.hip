@@ -70,6 +70,15 @@ bool front_shape_served(int n_filters, int nwin, int hop, int redundancy, int co
            (coef_flags & 3) == 3;
 }
 
+// The step's LDS image: the front end's exchange doubles and staged rows (4 waves of 32 rows of RW words), the reservoir's
+// image behind them, and the 128 bytes of the inverse channel permutation behind the input bit rows.
+size_t step_lds_bytes(long T, size_t lif_lds)
+{
+    const size_t RW = ((size_t)T + 31) / 32;
+    return 2 * GT_MAX_WPB * sizeof(double) + 4 * 32 * RW * 4 + lif_lds + 128;
+}
+constexpr size_t STEP_LDS_MAX = 160 * 1024;
+
 }  // namespace
 
 #define LSM_API extern "C" __attribute__((visibility("default")))
@@ -87,8 +96,7 @@ LSM_API int lsm_step_fused_supported(const lsm_reservoir *h, int n_clips, int n_
     if (lsm_lif::step_dense_args(h, n_clips, time_bins * n_thr, nullptr, 0, nullptr, nullptr, true, &d, &sl, &lds) != LSM_OK)
         return 0;
     if (d.C != n_filters * redundancy) return 0;
-    const size_t RW = ((size_t)time_bins * n_thr + 31) / 32;
-    return 2 * GT_MAX_WPB * sizeof(double) + 4 * 32 * RW * 4 + lds + 128 <= 160 * 1024 ? 1 : 0;
+    return step_lds_bytes((long)time_bins * n_thr, lds) <= STEP_LDS_MAX ? 1 : 0;
 }
 
 LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
@@ -100,6 +108,19 @@ LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n
     LSM_REQUIRE(h != nullptr, "lsm_step_fused_f64: null reservoir handle");
     LSM_REQUIRE(n_clips >= 0, "bad shape");
     if (n_clips == 0) return LSM_OK;
+    // A step of more steps than the reservoir's records hold, or whose LDS image cannot fit a CU whatever the reservoir (every
+    // reservoir image holds the step's 4 input words, 16 bytes a step), is a shape lsm_step_fused_supported answers with 0:
+    // refused as such here, ahead of the two halves, which call the same sizes bad arguments (the front end its stage alone,
+    // the reservoir n_steps and an image of its own past 160 KB).  What passes leaves both halves room; the whole image is
+    // looked at below.
+    if (time_bins >= 1 && n_thr >= 1) {
+        const long steps = (long)time_bins * n_thr;
+        if (steps > 65535 || step_lds_bytes(steps, 16 * (size_t)steps) > STEP_LDS_MAX) {
+            lsm_set_error("lsm_step_fused_f64: shape not served (%d bins x %d thresholds = %ld steps: at most 65535, and an LDS "
+                          "image of at most %zu bytes): make the two launches", time_bins, n_thr, steps, STEP_LDS_MAX);
+            return LSM_ERR_UNSUPPORTED;
+        }
+    }
     lsm_fe::StepFront fr;
     if (const int rc = lsm_fe::step_front_args(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on,
                                                thr_off, n_thr, redundancy, workspace, workspace_bytes, coef_flags, &fr))
@@ -120,10 +141,14 @@ LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n
                       "channels): make the two launches", n_filters, redundancy, nwin, hop, coef_flags, d.C);
         return LSM_ERR_UNSUPPORTED;
     }
-    // the front end's image (exchange doubles and the staged rows: fr.l.lds, a multiple of 16), the reservoir's behind it, and
-    // the 128 bytes of the inverse channel permutation behind the input bit rows
-    const size_t lds = fr.l.lds + lif_lds + 128;
-    LSM_REQUIRE((fr.l.lds & 15) == 0 && lds <= 160 * 1024, "the step's LDS image of %zu bytes does not fit a CU", lds);
+    // the front end's image (fr.l.lds, a multiple of 16) is step_lds_bytes' first two terms
+    const size_t lds = step_lds_bytes(T, lif_lds);
+    LSM_REQUIRE((fr.l.lds & 15) == 0 && fr.l.lds + lif_lds + 128 == lds, "the step's LDS image is not %zu bytes", lds);
+    if (lds > STEP_LDS_MAX) {
+        lsm_set_error("lsm_step_fused_f64: shape not served (%d steps: an LDS image of %zu bytes, at most %zu): make the two "
+                      "launches", T, lds, STEP_LDS_MAX);
+        return LSM_ERR_UNSUPPORTED;
+    }
     if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
     hipLaunchKernelGGL(fn, dim3(fr.l.grid), dim3(fr.l.block), lds, (hipStream_t)stream, a, d);
     LSM_CHECK_HIP(hipGetLastError());
