@@ -187,6 +187,12 @@ STEP_SIGS = {
     "lsm_step_fused_f64": (c_int, [c_void, c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void,
                                    c_int, c_int, c_void, C.c_long, c_int, c_void, c_int, c_void, c_void, c_void]),
 }
+# the forms of the step: the query with `form` last, the masked step with freq_mask, time_mask before the stream, the ragged
+# step with the DEVICE clip_bins after time_bins
+STEP_SIGS["lsm_step_fused_form_supported"] = (c_int, STEP_SIGS["lsm_step_fused_supported"][1] + [c_int])
+STEP_SIGS["lsm_step_fused_masked_f64"] = (c_int, STEP_SIGS["lsm_step_fused_f64"][1][:-1] + [c_void, c_void, c_void])
+STEP_SIGS["lsm_step_fused_ragged_f64"] = (c_int, STEP_SIGS["lsm_step_fused_f64"][1][:10] + [c_void]
+                                          + STEP_SIGS["lsm_step_fused_f64"][1][10:])
 STEP_SYMBOLS = tuple(STEP_SIGS)
 
 

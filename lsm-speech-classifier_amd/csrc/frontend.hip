@@ -626,6 +626,18 @@ int lsm_fe::step_front_args(const float *audio, int n_clips, int n_samples, cons
     return gammatone_spikes(r);
 }
 
+// step_fused.hip: the masked and the ragged step's own refusals are the masked and the ragged front end's, made there behind
+// the reservoir's (a ragged step has one count array and no clip_steps_out)
+int lsm_fe::step_check_masks(const uint32_t *freq_mask, const uint32_t *time_mask)
+{
+    return check_masks(freq_mask, time_mask);
+}
+
+int lsm_fe::step_check_ragged(const int32_t *clip_bins, int time_bins, long n_samples, long hop)
+{
+    return check_ragged(clip_bins, clip_bins, time_bins, n_samples, hop);
+}
+
 LSM_API int lsm_gammatone_spikes_masked_f64(const float *audio, int n_clips, int n_samples,
                                             const double *coefs, int n_filters, int nwin, int hop, int ncols,
                                             int time_bins, const double *thr_on, const double *thr_off, int n_thr,

@@ -117,6 +117,10 @@ struct StepFront {
 int step_front_args(const float *audio, int n_clips, int n_samples, const double *coefs, int n_filters, int nwin, int hop,
                     int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr, int redundancy,
                     void *workspace, long workspace_bytes, int coef_flags, StepFront *out);
+// the own refusals of the masked and of the ragged step (lsm_step_fused_masked_f64, lsm_step_fused_ragged_f64): those of the
+// masked and of the ragged front end, in their order and words.  frontend.hip.
+int step_check_masks(const uint32_t *freq_mask, const uint32_t *time_mask);
+int step_check_ragged(const int32_t *clip_bins, int time_bins, long n_samples, long hop);
 
 // The ragged launches (SPEC.md 1.14), defined in ragged_frontend.hip, likewise a translation unit of its own
 void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args, const RaggedArgs &rg, void *stream);

@@ -74,18 +74,24 @@ struct DenseArgs {
 // ST: the launch continues from a saved state and / or saves its own (lif_common.h); prologue and epilogue only.  REFM: the
 // state's countdown 2 / 1 is the lane mask h2 / h1.
 // The body is lif_dense_kernel.inc: one text for this kernel and for the fused step kernel (step_fused.hip), which runs it
-// behind the front end of the same clip.  The three macros name what differs between the two: where the LDS image lies and
-// where the input bit rows come from; here they expand to the tokens the body held before it was shared.
+// behind the front end of the same clip.  The five macros name what differs between the two: where the LDS image lies, where
+// the input bit rows come from, and how many steps the clip runs and its features count; here they expand to the tokens the
+// body held before it was shared.
 template <int SL, int WPC, int INMODE, bool REFM, bool ST = false>
 __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
 {
 #define LSM_DENSE_LDS_DECL extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #define LSM_DENSE_LDS smem
 #define LSM_DENSE_INPUT_BITS_INC "lif_dense_pack_raster.inc"
+#define LSM_DENSE_CLIP_STEPS \
+    !ST ? T : SCALE_LATE ? clip_step_count_unscaled(a.st, b, T) : clip_step_count(a.st, b, T, offsetof(DenseArgs, st))
+#define LSM_DENSE_FEATURE_STEPS ST ? Tb + a.st.t0 : T
 #include "lif_dense_kernel.inc"
 #undef LSM_DENSE_LDS_DECL
 #undef LSM_DENSE_LDS
 #undef LSM_DENSE_INPUT_BITS_INC
+#undef LSM_DENSE_CLIP_STEPS
+#undef LSM_DENSE_FEATURE_STEPS
 }
 
 typedef void (*dense_fn_t)(const DenseArgs);

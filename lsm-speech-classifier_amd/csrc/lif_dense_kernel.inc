@@ -6,7 +6,11 @@
 //                        at (lif_dense.h: the dynamic LDS itself, `smem`);
 //   LSM_DENSE_INPUT_BITS_INC   the file that fills the input bit rows bits[t * CW + q] once `icnt`, `wcnt` and `feat` are
 //                        zeroed: lif_dense_pack_raster.inc zeroes `bits` and packs the clip's uint8 raster into it with LDS
-//                        atomics; step_fused_bits.inc writes every word of every row from the front end's staged bits.
+//                        atomics; step_fused_bits.inc writes every word of every row from the front end's staged bits;
+//   LSM_DENSE_CLIP_STEPS, LSM_DENSE_FEATURE_STEPS   the steps the workgroup's clip runs (`Tb`) and the T of its features
+//                        (`Tf`), as expressions: lif_dense.h's are the launch's T or, in the ST forms, the state block's count
+//                        and t0 + Tb; the fused step's tail gives a ragged clip its own count for both (SPEC.md §4c with
+//                        t0 = 0) without a state block.  T stays the row stride and the size of the LDS image.
     constexpr bool INREG = INMODE == 1;
     constexpr bool INMASK = INMODE >= 2;
     constexpr bool INCOL = INMODE == 3;
@@ -33,7 +37,7 @@
     // ST: the steps this clip runs (SPEC.md §4c), workgroup-uniform; T stays the row stride of the raster, the spike matrix
     // and the trace, and the size of the LDS image.  A clip of no steps hands its state on and is left as it is.
     constexpr bool SCALE_LATE = INMODE == 1;        // which form of the step count (lif_common.h on the two forms)
-    int Tb = !ST ? T : SCALE_LATE ? clip_step_count_unscaled(a.st, b, T) : clip_step_count(a.st, b, T, offsetof(DenseArgs, st));
+    int Tb = LSM_DENSE_CLIP_STEPS;
     if constexpr (ST) {
         if (Tb == 0) {
             state_pass_through<NT>(b, tid, offsetof(DenseArgs, st));
@@ -412,7 +416,7 @@
         if (a.st.seg > 0 && a.st.t0 != STREAM_T0) segment_fold<NT>(a.st, b, Tb, feat, a.n_out, a.burst_isi_max, tid);
         state_finish<NT>(sin, sout, scratch, feat, NP, a.n_out, (uint32_t)a.st.t0, a.burst_isi_max, tid);
     }
-    const int Tf = ST ? Tb + a.st.t0 : T;           // the features are those of [0, t0 + Tb)
+    const int Tf = LSM_DENSE_FEATURE_STEPS;         // lif_dense.h: the features are those of [0, t0 + Tb)
     if (a.stats) write_stats(a.stats, b, &wcnt[32], &wcnt[33], hf, tot_spk, lane, tid);
     const int nf = a.n_keys * a.n_out;
     for (int idx = tid; idx < nf; idx += NT) {

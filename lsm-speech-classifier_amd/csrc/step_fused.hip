@@ -11,6 +11,7 @@
 #include "lsm_common.h"
 #include "gammatone_spikes_body.h"
 #include "lif_dense.h"
+#include "step_fused_forms.h"
 #include <cstring>
 
 namespace {
@@ -79,16 +80,25 @@ size_t step_lds_bytes(long T, size_t lif_lds)
 }
 constexpr size_t STEP_LDS_MAX = 160 * 1024;
 
-}  // namespace
+// The three families of the step (include/lsm_hip_step.h): the plain kernels above, the masked ones (step_fused_masked.hip)
+// and the ragged ones (step_fused_ragged.hip).  A batch is ragged or masked, never both, as on the front-end entry points.
+enum StepForm { STEP_PLAIN = 0, STEP_MASKED = 1, STEP_RAGGED = 2 };
+constexpr int RAGGED_HOP = 160;         // the one hop the ragged front end is offered for (include/lsm_hip_ragged.h)
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
-LSM_API int lsm_step_fused_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
-                                     int n_thr, int redundancy, int coef_flags)
+// What a form asks of the shape beyond the plain step: the ragged step the hop on which a clip of T bins is the front end of
+// (160 T samples, T bins).  The LDS image is step_lds_bytes for every form.
+bool form_shape_served(int form, int hop)
 {
-    LSM_REQUIRE(h != nullptr, "lsm_step_fused_supported: null reservoir handle");
+    return form != STEP_RAGGED || hop == RAGGED_HOP;
+}
+
+int step_supported(const char *what, const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
+                   int n_thr, int redundancy, int coef_flags, int form)
+{
+    LSM_REQUIRE(h != nullptr, "%s: null reservoir handle", what);
     LSM_REQUIRE(n_clips >= 1 && n_filters >= 1 && time_bins >= 1 && n_thr >= 1 && redundancy >= 1, "bad shape");
-    if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags)) return 0;
+    LSM_REQUIRE(form >= STEP_PLAIN && form <= STEP_RAGGED, "%s: form %d is none of 0 (plain), 1 (masked), 2 (ragged)", what, form);
+    if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags) || !form_shape_served(form, hop)) return 0;
     if ((long)time_bins * n_thr > 65535) return 0;
     lsm_lif::DenseArgs d;
     int sl = 0;
@@ -99,13 +109,23 @@ LSM_API int lsm_step_fused_supported(const lsm_reservoir *h, int n_clips, int n_
     return step_lds_bytes((long)time_bins * n_thr, lds) <= STEP_LDS_MAX ? 1 : 0;
 }
 
-LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
-                               int n_filters, int nwin, int hop, int ncols, int time_bins, const double *thr_on,
-                               const double *thr_off, int n_thr, int redundancy, void *workspace, long workspace_bytes,
-                               int coef_flags, const int32_t *key_ids, int n_keys, float *features_out, int32_t *stats_out,
-                               void *stream)
+// One step launch: the three entry points fill `form` and their own pointers (a member that is not the form's is never read).
+// Refusals: the front end's, the reservoir's, the form's own (the masks' alignment; the ragged counts and strides), then the
+// shapes the launch does not serve.
+struct StepOwn {
+    int form = STEP_PLAIN;
+    const char *what = "lsm_step_fused_f64";
+    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
+    const int32_t *clip_bins = nullptr;                             // Ragged (1.14): DEVICE counts, clamped in the kernel
+};
+
+int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
+                int n_filters, int nwin, int hop, int ncols, int time_bins, const double *thr_on, const double *thr_off,
+                int n_thr, int redundancy, void *workspace, long workspace_bytes, int coef_flags, const int32_t *key_ids,
+                int n_keys, float *features_out, int32_t *stats_out, void *stream)
 {
-    LSM_REQUIRE(h != nullptr, "lsm_step_fused_f64: null reservoir handle");
+    const char *const what = own.what;
+    LSM_REQUIRE(h != nullptr, "%s: null reservoir handle", what);
     LSM_REQUIRE(n_clips >= 0, "bad shape");
     if (n_clips == 0) return LSM_OK;
     // A step of more steps than the reservoir's records hold, or whose LDS image cannot fit a CU whatever the reservoir (every
@@ -116,8 +136,8 @@ LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n
     if (time_bins >= 1 && n_thr >= 1) {
         const long steps = (long)time_bins * n_thr;
         if (steps > 65535 || step_lds_bytes(steps, 16 * (size_t)steps) > STEP_LDS_MAX) {
-            lsm_set_error("lsm_step_fused_f64: shape not served (%d bins x %d thresholds = %ld steps: at most 65535, and an LDS "
-                          "image of at most %zu bytes): make the two launches", time_bins, n_thr, steps, STEP_LDS_MAX);
+            lsm_set_error("%s: shape not served (%d bins x %d thresholds = %ld steps: at most 65535, and an LDS "
+                          "image of at most %zu bytes): make the two launches", what, time_bins, n_thr, steps, STEP_LDS_MAX);
             return LSM_ERR_UNSUPPORTED;
         }
     }
@@ -133,24 +153,101 @@ LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n
     size_t lif_lds = 0;
     if (const int rc = lsm_lif::step_dense_args(h, n_clips, T, key_ids, n_keys, features_out, stats_out, false, &d, &sl, &lif_lds))
         return rc;
+    // the form's own refusals, behind the two halves'
+    if (own.form == STEP_MASKED) {
+        if (const int rc = lsm_fe::step_check_masks(own.freq_mask, own.time_mask)) return rc;
+    } else if (own.form == STEP_RAGGED) {
+        if (const int rc = lsm_fe::step_check_ragged(own.clip_bins, time_bins, n_samples, hop)) return rc;
+    }
+    // a masked step without a mask is the plain launch (SPEC.md 1.13: the unmasked bytes)
+    const int form = (own.form == STEP_MASKED && !own.freq_mask && !own.time_mask) ? (int)STEP_PLAIN : own.form;
     step_fn_t fn = pick_step(sl, fr.l.shb0);
     if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags) || !fr.l.pair || fr.l.nch != 1 || !fr.l.fast ||
         fr.l.nw != 3 || a.groups != 4 || fr.l.block != 256 || fr.l.grid != (unsigned)n_clips || d.C != n_filters * redundancy ||
         d.CW != 4 || d.T != T || fn == nullptr) {
-        lsm_set_error("lsm_step_fused_f64: shape not served (%d filters, redundancy %d, nwin %d, hop %d, coef_flags %d, %d input "
-                      "channels): make the two launches", n_filters, redundancy, nwin, hop, coef_flags, d.C);
+        lsm_set_error("%s: shape not served (%d filters, redundancy %d, nwin %d, hop %d, coef_flags %d, %d input "
+                      "channels): make the two launches", what, n_filters, redundancy, nwin, hop, coef_flags, d.C);
+        return LSM_ERR_UNSUPPORTED;
+    }
+    // ragged: a clip of t bins has t - (time_bins - ncols) columns; on hop 160 with the 2 columns a 25 ms window costs, that
+    // is the front end of (160 t samples, t bins) for every t (include/lsm_hip_ragged.h)
+    if (own.form == STEP_RAGGED && (!form_shape_served(own.form, hop) || ncols != time_bins - 2)) {
+        lsm_set_error("%s: shape not served (hop %d, %d columns for %d bins: a ragged step needs hop %d and time_bins - 2 "
+                      "columns): make the two launches", what, hop, ncols, time_bins, RAGGED_HOP);
         return LSM_ERR_UNSUPPORTED;
     }
     // the front end's image (fr.l.lds, a multiple of 16) is step_lds_bytes' first two terms
     const size_t lds = step_lds_bytes(T, lif_lds);
     LSM_REQUIRE((fr.l.lds & 15) == 0 && fr.l.lds + lif_lds + 128 == lds, "the step's LDS image is not %zu bytes", lds);
     if (lds > STEP_LDS_MAX) {
-        lsm_set_error("lsm_step_fused_f64: shape not served (%d steps: an LDS image of %zu bytes, at most %zu): make the two "
-                      "launches", T, lds, STEP_LDS_MAX);
+        lsm_set_error("%s: shape not served (%d steps: an LDS image of %zu bytes, at most %zu): make the two "
+                      "launches", what, T, lds, STEP_LDS_MAX);
         return LSM_ERR_UNSUPPORTED;
     }
-    if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
-    hipLaunchKernelGGL(fn, dim3(fr.l.grid), dim3(fr.l.block), lds, (hipStream_t)stream, a, d);
+    if (form == STEP_PLAIN) {
+        if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
+        hipLaunchKernelGGL(fn, dim3(fr.l.grid), dim3(fr.l.block), lds, (hipStream_t)stream, a, d);
+    } else {
+        // (pick_step has said that this sl has a kernel: the families build the same three)
+        const lsm_step::StepLaunch l{sl, fr.l.shb0, fr.l.grid, fr.l.block, lds};
+        const bool ok = form == STEP_MASKED
+                            ? lsm_step::launch_step_masked(l, &a, d, lsm_fe::MaskArgs{own.freq_mask, own.time_mask}, stream)
+                            : lsm_step::launch_step_ragged(l, &a, d, lsm_fe::RaggedArgs{own.clip_bins, nullptr}, stream);
+        LSM_REQUIRE(ok, "%s: no kernel for %d slots per lane", what, sl);
+    }
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
+}
+
+}  // namespace
+
+#define LSM_API extern "C" __attribute__((visibility("default")))
+
+LSM_API int lsm_step_fused_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
+                                     int n_thr, int redundancy, int coef_flags)
+{
+    return step_supported("lsm_step_fused_supported", h, n_clips, n_filters, nwin, hop, time_bins, n_thr, redundancy, coef_flags,
+                          STEP_PLAIN);
+}
+
+LSM_API int lsm_step_fused_form_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
+                                          int n_thr, int redundancy, int coef_flags, int form)
+{
+    return step_supported("lsm_step_fused_form_supported", h, n_clips, n_filters, nwin, hop, time_bins, n_thr, redundancy,
+                          coef_flags, form);
+}
+
+LSM_API int lsm_step_fused_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
+                               int n_filters, int nwin, int hop, int ncols, int time_bins, const double *thr_on,
+                               const double *thr_off, int n_thr, int redundancy, void *workspace, long workspace_bytes,
+                               int coef_flags, const int32_t *key_ids, int n_keys, float *features_out, int32_t *stats_out,
+                               void *stream)
+{
+    return step_launch(StepOwn{}, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off,
+                       n_thr, redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
+}
+
+LSM_API int lsm_step_fused_masked_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples,
+                                      const double *coefs, int n_filters, int nwin, int hop, int ncols, int time_bins,
+                                      const double *thr_on, const double *thr_off, int n_thr, int redundancy, void *workspace,
+                                      long workspace_bytes, int coef_flags, const int32_t *key_ids, int n_keys,
+                                      float *features_out, int32_t *stats_out, const uint32_t *freq_mask,
+                                      const uint32_t *time_mask, void *stream)
+{
+    StepOwn own;
+    own.form = STEP_MASKED; own.what = "lsm_step_fused_masked_f64"; own.freq_mask = freq_mask; own.time_mask = time_mask;
+    return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                       redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
+}
+
+LSM_API int lsm_step_fused_ragged_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples,
+                                      const double *coefs, int n_filters, int nwin, int hop, int ncols, int time_bins,
+                                      const int32_t *clip_bins, const double *thr_on, const double *thr_off, int n_thr,
+                                      int redundancy, void *workspace, long workspace_bytes, int coef_flags,
+                                      const int32_t *key_ids, int n_keys, float *features_out, int32_t *stats_out, void *stream)
+{
+    StepOwn own;
+    own.form = STEP_RAGGED; own.what = "lsm_step_fused_ragged_f64"; own.clip_bins = clip_bins;
+    return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                       redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
 }

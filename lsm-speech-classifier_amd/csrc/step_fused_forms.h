@@ -1,0 +1,28 @@
+// step_fused_forms.h -- the masked and the ragged forms of the one-launch step (include/lsm_hip_step.h), each
+// family in a translation unit of its own (step_fused_masked.hip, step_fused_ragged.hip) so that the units compile in
+// parallel and step_fused.hip keeps its objects.  step_fused.hip alone refuses, plans and builds the arguments; it then calls
+// one of the two launch functions below.  `fused_args`: the front half's FusedArgs as bytes (the type lives in each unit's
+// unnamed namespace: gammatone_spikes_body.h, StepFront).
+#pragma once
+#include "lsm_common.h"
+#include "spikes_body.h"
+#include "lif_dense.h"
+
+namespace lsm_step {
+
+// which kernel text (neuron slots per lane: 1, 2 or 4), which of its two forms (the shared first-section gain), and the
+// launch geometry: one workgroup of 256 threads per clip, `lds` bytes of dynamic LDS
+struct StepLaunch {
+    int sl;
+    bool shb0;
+    unsigned grid, block;
+    size_t lds;
+};
+
+// false: no such form (sl is none of 1, 2, 4); nothing was launched
+bool launch_step_masked(const StepLaunch &l, const void *fused_args, const lsm_lif::DenseArgs &d, const lsm_fe::MaskArgs &m,
+                        void *stream);
+bool launch_step_ragged(const StepLaunch &l, const void *fused_args, const lsm_lif::DenseArgs &d, const lsm_fe::RaggedArgs &rg,
+                        void *stream);
+
+}  // namespace lsm_step

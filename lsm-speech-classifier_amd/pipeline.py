@@ -42,29 +42,39 @@ STAGES = ("full", "frontend", "reservoir")
 FUSED_STEP_MAX_HW_QUEUES = 4
 
 
-def step_fused_supported(fe, net, n_clips: int) -> bool:
+STEP_FORMS = {"plain": 0, "masked": 1, "ragged": 2}       # lsm_step_fused_form_supported's `form`
+
+
+def step_fused_supported(fe, net, n_clips: int, form: str = "plain") -> bool:
     """Whether `step_fused` serves batches of `n_clips` clips of this front end and reservoir (`lsm_step_fused_supported`):
     a gammatone front end of 97..128 filters without redundancy, and a reservoir whose pipeline launch is the dense-row
-    kernel with 4 waves per clip and coloured input masks.  Anything else takes the two launches."""
+    kernel with 4 waves per clip and coloured input masks.  Anything else takes the two launches.  `form`: "plain";
+    "masked" (`step_fused(mask=...)`: wherever the plain step is served); "ragged" (`step_fused_ragged`: additionally a front
+    end that takes ragged batches, `frontend.ragged_refusal`) -- `lsm_step_fused_form_supported`."""
+    if form not in STEP_FORMS:
+        raise ValueError(f"form must be one of {tuple(STEP_FORMS)}, got {form!r}")
     if getattr(fe, "filterbank", None) != "gammatone" or not fe.will_fuse() or int(n_clips) < 1:
         return False
     from . import _lib
-    rc = int(_lib.load().lsm_step_fused_supported(net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop, fe.time_bins,
-                                                  len(fe.thresholds), fe.redundancy, fe.coef_flags))
+    if form == "plain":
+        rc = int(_lib.load().lsm_step_fused_supported(net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop, fe.time_bins,
+                                                      len(fe.thresholds), fe.redundancy, fe.coef_flags))
+    else:
+        from .frontend import ragged_refusal
+        if form == "ragged" and (ragged_refusal(fe.n_samples, fe.time_bins) or fe.ncols != fe.time_bins - 2):
+            return False
+        rc = int(_lib.load().lsm_step_fused_form_supported(net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop,
+                                                           fe.time_bins, len(fe.thresholds), fe.redundancy, fe.coef_flags,
+                                                           STEP_FORMS[form]))
     if rc < 0:
         _lib.check(rc, "lsm_step_fused_supported")
     return rc == 1
 
 
-def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=None, workspace=None):
-    """One step in ONE launch on the current stream (`lsm_step_fused_f64`): audio (B, n_samples) float32 on the device ->
-    feature rows (B, n_keys * N_out) float32, bit for bit ``net.run_batch(fe.encode(audio), feature_keys)[0]``; no raster is
-    written.  `stats_out` / `features_out`: as `SNN.run_batch`'s; `workspace`: as `SpikeFrontEnd.encode`'s (from
-    `fe.new_workspace(B)`).  A shape the launch does not serve (`step_fused_supported`) raises: the caller makes the two
-    launches."""
-    from . import _lib
-    from .frontend import threshold_tables
-    from .snn import _check_stats_out, _dev, _host, _select_keys
+def _step_outputs(fe, net, audio, feature_keys, stats_out, features_out):
+    """What the step launches share: the checked batch, its key ids and the feature rows they write (`features_out` or None:
+    the caller allocates inside its device context)."""
+    from .snn import _check_stats_out, _select_keys
     audio = fe._audio(audio)
     B = int(audio.shape[0])
     keys, key_ids = _select_keys(feature_keys)
@@ -73,17 +83,64 @@ def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=N
         if (features_out.dtype != torch.float32 or tuple(features_out.shape) != shape or not features_out.is_contiguous()
                 or features_out.device != audio.device):
             raise ValueError(f"features_out must be a contiguous float32 {shape} tensor on {audio.device}")
-        feats = features_out
     _check_stats_out(stats_out, B, audio.device)
+    return audio, B, keys, key_ids, shape
+
+
+def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=None, workspace=None, mask=None):
+    """One step in ONE launch on the current stream (`lsm_step_fused_f64`): audio (B, n_samples) float32 on the device ->
+    feature rows (B, n_keys * N_out) float32, bit for bit ``net.run_batch(fe.encode(audio), feature_keys)[0]``; no raster is
+    written.  `stats_out` / `features_out`: as `SNN.run_batch`'s; `workspace`: as `SpikeFrontEnd.encode`'s (from
+    `fe.new_workspace(B)`).  `mask`: a `frontend.MaskPlan` of the batch's clips (SPEC.md §1.13), checked (`checked_mask`) and
+    uploaded on the current stream as `encode(mask=...)` does: the launch is `lsm_step_fused_masked_f64` and the rows are those
+    of ``net.run_batch(fe.encode(audio, mask=mask), feature_keys)[0]``; None makes exactly the unmasked call.  A shape the
+    launch does not serve (`step_fused_supported`) raises: the caller makes the two launches."""
+    from . import _lib
+    from .frontend import checked_mask, threshold_tables, upload_mask
+    from .snn import _dev, _host
+    if mask is not None:
+        checked_mask(mask, 1 if getattr(audio, "ndim", 2) == 1 else len(audio), fe.n_filters, fe.time_bins)
+    audio, B, keys, key_ids, shape = _step_outputs(fe, net, audio, feature_keys, stats_out, features_out)
     on, off = threshold_tables(fe.thresholds, fe.gap, np.float64)
     with torch.cuda.device(fe.device):
-        if features_out is None:
-            feats = torch.empty(shape, dtype=torch.float32, device=fe.device)
+        feats = features_out if features_out is not None else torch.empty(shape, dtype=torch.float32, device=fe.device)
         ws, ws_bytes = fe._workspace_for(B, workspace)
-        _lib.check(fe.lib.lsm_step_fused_f64(
+        args = (net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
+                _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids), len(keys),
+                _dev(feats), _dev(stats_out))
+        if mask is None:
+            _lib.check(fe.lib.lsm_step_fused_f64(*args, fe._stream()), "lsm_step_fused_f64")
+        else:
+            fm, tm = upload_mask(mask, B, fe.n_filters, fe.time_bins, fe.device)
+            _lib.check(fe.lib.lsm_step_fused_masked_f64(*args, _dev(fm), _dev(tm), fe._stream()), "lsm_step_fused_masked_f64")
+    return feats
+
+
+def step_fused_ragged(fe, net, audio, bins, feature_keys=None, stats_out=None, features_out=None, workspace=None):
+    """One step on clips of different lengths in ONE launch on the current stream (`lsm_step_fused_ragged_f64`): clip b is the
+    first ``160 * bins[b]`` samples of its row and runs ``bins[b] * n_thr`` reservoir steps; its feature row is, bit for bit,
+    that of ``raster, steps = fe.encode_ragged(audio, bins)`` followed by ``net.run_batch(raster, feature_keys,
+    lengths=steps)[0]``.  `bins`: B host integers, each 0 or 3 .. time_bins (checked), or an int32 device tensor (not read:
+    the kernel clamps it), as `encode_ragged` takes them.  A clip of 0 bins leaves its row of `features_out` and of
+    `stats_out` as it was (a row of a tensor allocated here is then uninitialised).  The other parameters are `step_fused`'s;
+    masks are not offered.  Needs `step_fused_supported(fe, net, B, form="ragged")`."""
+    from . import _lib
+    from .frontend import checked_ragged_bins, ragged_refusal, threshold_tables
+    from .snn import _dev, _host
+    why = ragged_refusal(fe.n_samples, fe.time_bins)
+    if why:
+        raise ValueError(why)
+    checked_ragged_bins(bins, 1 if getattr(audio, "ndim", 2) == 1 else len(audio), fe.time_bins)     # before any device work
+    audio, B, keys, key_ids, shape = _step_outputs(fe, net, audio, feature_keys, stats_out, features_out)
+    on, off = threshold_tables(fe.thresholds, fe.gap, np.float64)
+    with torch.cuda.device(fe.device):
+        bins_dev = fe._device_bins(bins, B)
+        feats = features_out if features_out is not None else torch.empty(shape, dtype=torch.float32, device=fe.device)
+        ws, ws_bytes = fe._workspace_for(B, workspace)
+        _lib.check(fe.lib.lsm_step_fused_ragged_f64(
             net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
-            _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids), len(keys),
-            _dev(feats), _dev(stats_out), fe._stream()), "lsm_step_fused_f64")
+            _dev(bins_dev), _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids),
+            len(keys), _dev(feats), _dev(stats_out), fe._stream()), "lsm_step_fused_ragged_f64")
     return feats
 
 
@@ -140,11 +197,15 @@ class HotPath:
     `speed` = a `frontend.SpeedPerturber`: a step submitted with `speed=` (a `frontend.SpeedPlan` of its clips) is played at
     its clips' speeds on the device (SPEC.md §1.12) ahead of the reverberator: speed, reverb, mixer, front end.
     With at most FUSED_STEP_MAX_HW_QUEUES hardware queues a full step without any of these, of a shape `step_fused_supported`
-    accepts, is one launch (`_submit_fused`); `time_reservoir`'s event pair then brackets that launch, front end included."""
+    accepts, is one launch (`_submit_fused`); `time_reservoir`'s event pair then brackets that launch, front end included.
+    `fused_forms` = True: there a masked step is one launch too (`lsm_step_fused_masked_f64`), and a step with speed, reverb or
+    mixer runs its augmentation launches on the fused rotation stream and then the one launch; the rows are byte for byte
+    those of the default routes.  Off by default (profiles/step_fused_forms.txt)."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
-                 fe_streams: int | None = None, time_segments: int = 1, mixer=None, reverb=None, speed=None):
+                 fe_streams: int | None = None, time_segments: int = 1, mixer=None, reverb=None, speed=None,
+                 fused_forms: bool = False):
         if indexed_device(fe.device) != indexed_device(net.device):
             raise ValueError(f"front end on {fe.device}, reservoir on {net.device}")
         if mixer is not None and indexed_device(mixer.device) != indexed_device(fe.device):
@@ -199,8 +260,13 @@ class HotPath:
         # caller submits from: with as many rotation streams as queues one of them shares its queue with that stream, and
         # at 4 queues the step took 1.03 ms over 4 streams against 0.84 over 3 (and 0.96 over 2;
         # profiles/step_fused_ab.txt).  With more queues nothing changes.
+        # `fused_forms` (off unless asked for; cfg2, 4 queues: a masked step 1.00 -> 0.82 ms, mixer + mask 1.29 -> 0.95 ms,
+        # profiles/step_fused_forms.txt, which also says why it is not the default yet): a masked step takes the masked launch
+        # (`step_fused(mask=...)`), and a pipeline with a mixer, a reverberator or a speed perturber keeps the fused step and runs
+        # a step's augmentation chain on the fused rotation stream in front of it.  The rows are those of the two launches.
+        self.fused_forms = bool(fused_forms)
         self.fused_step = (self.n_streams > 1 and self.hw_queues <= FUSED_STEP_MAX_HW_QUEUES and self.time_segments == 1
-                           and mixer is None and reverb is None and speed is None)
+                           and (self.fused_forms or (mixer is None and reverb is None and speed is None)))
         self.n_fused_streams = max(1, min(self.hw_queues - 1, self.n_streams))
         self._fused_ok = {}                 # batch size -> step_fused_supported
         self._fused_ws = {}                 # (rotation slot, batch size) -> the launch's front-end scratch
@@ -292,7 +358,7 @@ class HotPath:
             self._in_flight.pop(0).synchronize()
         if self.n_streams == 1:
             topology = self._submit_serial
-        elif stage == "full" and mask is None and self._takes_fused_step(audio):
+        elif stage == "full" and (mask is None or self.fused_forms) and self._takes_fused_step(audio, mask is not None):
             topology = self._submit_fused
         elif self.n_fe_streams and stage != "reservoir":
             topology = self._submit_two_stages
@@ -366,14 +432,14 @@ class HotPath:
                     ring.release(st)
                 return feats, st
 
-    def _takes_fused_step(self, audio) -> bool:
-        """Whether a plain full step over `audio` is the one-launch step (decided once per batch size)."""
+    def _takes_fused_step(self, audio, masked: bool = False) -> bool:
+        """Whether a full step over `audio` is the one-launch step (decided once per batch size and form)."""
         if not self.fused_step:
             return False
-        n = int(len(audio))
-        ok = self._fused_ok.get(n)
+        key = (int(len(audio)), "masked") if masked else int(len(audio))
+        ok = self._fused_ok.get(key)
         if ok is None:
-            ok = self._fused_ok[n] = step_fused_supported(self.fe, self.net, n)
+            ok = self._fused_ok[key] = step_fused_supported(self.fe, self.net, int(len(audio)), "masked" if masked else "plain")
         return ok
 
     def _submit_fused(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None, mask=None):
@@ -383,7 +449,7 @@ class HotPath:
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             self._wait_for_input(st, cur, audio, after)
-            x = self._to_device(audio, slot)
+            x = self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
             key = (slot, int(x.shape[0]))
             ws = self._fused_ws.get(key)
             if ws is None:
@@ -391,7 +457,9 @@ class HotPath:
             if self.time_reservoir:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            feats = step_fused(self.fe, self.net, x, self.feature_keys, stats_out=stats_out, features_out=out, workspace=ws)
+            extra = {} if mask is None else {"mask": mask}      # a step without a mask is launched as it always was
+            feats = step_fused(self.fe, self.net, x, self.feature_keys, stats_out=stats_out, features_out=out, workspace=ws,
+                               **extra)
             if self.time_reservoir:
                 e1.record()
                 self.reservoir_events.append((e0, e1))
@@ -668,7 +736,7 @@ def features_from_recordings(recordings, fe, net, feature_keys):
         return feats
 
 
-def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024):
+def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024, fused: bool = False):
     """Utterances of different lengths, each one clip: ``utterances``, a list of n 1-D float32 arrays of 321 to
     ``fe.n_samples`` samples, -> (n, n_feat) float32 device tensor in the input order.  Row r holds the features of utterance
     r taken alone: its own ``ceil(len / 160)`` time bins through the front end of that length (its normalisation range is the
@@ -677,7 +745,9 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     share a launch); within a batch the ragged front end (`SpikeFrontEnd.encode_ragged`) hands its raster and its device step
     counts to the ragged reservoir launch on the same stream, with no host synchronisation between them.  Where
     ``fe.n_steps`` exceeds the longest launch the reservoir's plan accepts, the reservoir runs in chunks
-    (``SNN.run_chunked(lengths=...)``, host lengths)."""
+    (``SNN.run_chunked(lengths=...)``, host lengths).  ``fused`` = True: a batch whose shape the ragged one-launch step
+    serves (`step_fused_supported(..., form="ragged")`) is that one launch (`step_fused_ragged`) -- no raster, no step counts
+    in memory, the same rows; every other batch takes the two launches.  Off by default (profiles/step_fused_forms.txt)."""
     from .frontend import pack_utterances
     from .snn import _select_keys
     audio, bins = pack_utterances(utterances, fe.time_bins)
@@ -691,6 +761,11 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
         for lo in range(0, n, batch):
             idx = order[lo:lo + batch]
             x = torch.from_numpy(audio[idx]).to(net.device)
+            if fused and step_fused_supported(fe, net, len(idx), "ragged"):
+                rows = torch.zeros((len(idx), feats.shape[1]), dtype=torch.float32, device=net.device)
+                step_fused_ragged(fe, net, x, bins[idx], feature_keys, features_out=rows)
+                feats[torch.from_numpy(idx).to(net.device)] = rows
+                continue
             raster, steps = fe.encode_ragged(x, bins[idx])
             if fe.n_steps > net.max_steps(len(idx)):
                 rows = net.run_chunked(raster, feature_keys, lengths=bins[idx].astype(np.int64) * n_thr)[0]
