@@ -449,36 +449,29 @@ def create_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=
                                    thresholds=SPIKE_THRESHOLDS, gap=HYSTERESIS_GAP,
                                    time_bins=TIME_BINS, n_samples=int(SAMPLE_RATE * DURATION))
     from lsm_speech_classifier_amd import spikefile
-    mixer = plan = None
+    from lsm_speech_classifier_amd.augment import AugmentChain, StepPlans
+    stages, plans = {}, {}
     if augment:
-        bank, plan = corruption(augment, n_listed)
-        plan = plan.take(lo + np.asarray(kept, dtype=np.int64))
-        mixer = _frontend().NoiseMixer(bank, device=dev)
-    reverberator = rooms = None
+        bank, plans["mix"] = corruption(augment, n_listed)
+        stages["mixer"] = _frontend().NoiseMixer(bank, device=dev)
     if reverb:
-        rir, rir_lengths, rooms = reverberation(reverb, n_listed)
-        rooms = rooms.take(lo + np.asarray(kept, dtype=np.int64))
-        reverberator = _frontend().Reverberator(rir, rir_lengths, device=dev)
-    perturber = paces = None
+        rir, rir_lengths, plans["reverb"] = reverberation(reverb, n_listed)
+        stages["reverb"] = _frontend().Reverberator(rir, rir_lengths, device=dev)
     if speed:
-        factors, paces = speeds(speed, n_listed)
-        paces = paces.take(lo + np.asarray(kept, dtype=np.int64))
-        perturber = _frontend().SpeedPerturber(factors, device=dev)
-    veils = None
+        factors, plans["speed"] = speeds(speed, n_listed)
+        stages["speed"] = _frontend().SpeedPerturber(factors, device=dev)
     if mask:
-        veils = masks(mask, n_listed, fe).take(lo + np.asarray(kept, dtype=np.int64))
+        plans["mask"] = masks(mask, n_listed, fe)
+    chain, plans = AugmentChain(**stages), StepPlans(**plans)
+    if planned:
+        plans = plans.take(lo + np.asarray(kept, dtype=np.int64))
     parts, n_spikes = [], 0
     for a in range(0, len(clips), ENCODE_BATCH):
         batch = clips[a:a + ENCODE_BATCH]
         if not torch.is_tensor(batch):
             batch = np.stack(batch)
-        if perturber is not None:
-            batch = perturber.perturb(batch, paces.part(a, a + ENCODE_BATCH).choice)
-        if reverberator is not None:
-            batch = reverberator.reverb(batch, rooms.part(a, a + ENCODE_BATCH).rows)
-        if mixer is not None:
-            batch = mixer.mix(batch, *plan.part(a, a + ENCODE_BATCH))
-        raster = fe.encode(batch) if veils is None else fe.encode(batch, mask=veils.part(a, a + ENCODE_BATCH))
+        step = plans.part(a, a + ENCODE_BATCH)
+        raster = fe.encode(chain.apply(batch, step), **step.mask_keyword())
         n_spikes += int(raster.count_nonzero())
         part = _frontend().pack_raster(raster) if packed else raster
         parts.append(part if world > 1 else part.cpu().numpy())

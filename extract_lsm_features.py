@@ -275,6 +275,7 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
+    from lsm_speech_classifier_amd.augment import AugmentChain, StepPlans
     from lsm_speech_classifier_amd.snn import SNN
 
     if readout not in (None, "sklearn", "torch-ridge", "torch-logistic"):
@@ -293,26 +294,19 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     dev = lsm_dist.local_device() if world > 1 else None
     fe = frontend.SpikeFrontEnd(n_filters, filterbank, device=dev)
     check_time_segments(fe.n_steps, time_segments)                  # refused with the reason before any work is done
-    mixer = plan = None
+    stages, plans = {}, {}
     if corrupt is not None:
-        mixer, plan = frontend.NoiseMixer(corrupt[0], device=dev), corrupt[1]
-    rv = rooms = None
+        stages["mixer"], plans["mix"] = frontend.NoiseMixer(corrupt[0], device=dev), corrupt[1]
     if reverb is not None:
-        rv, rooms = frontend.Reverberator(reverb[0], reverb[1], device=dev), reverb[2]
-    sp = paces = None
+        stages["reverb"], plans["reverb"] = frontend.Reverberator(reverb[0], reverb[1], device=dev), reverb[2]
     if speed is not None:
-        sp, paces = frontend.SpeedPerturber(speed[0], device=dev), speed[1]
-    veils = None
+        stages["speed"], plans["speed"] = frontend.SpeedPerturber(speed[0], device=dev), speed[1]
     if mask:
-        veils = frontend.mask_plan(len(audio), fe.n_filters, fe.time_bins, **mask)
-    head_audio = audio[idx_train[:500]]
-    if sp is not None:
-        head_audio = sp.perturb(head_audio, paces.take(idx_train[:500]).choice)
-    if rv is not None:
-        head_audio = rv.reverb(head_audio, rooms.take(idx_train[:500]).rows)
-    if mixer is not None:
-        head_audio = mixer.mix(head_audio, *plan.take(idx_train[:500]))
-    head = fe.encode(head_audio, **({} if veils is None else {"mask": veils.take(idx_train[:500])})).cpu().numpy()                      # what w_critico and the diagnostics look at
+        plans["mask"] = frontend.mask_plan(len(audio), fe.n_filters, fe.time_bins, **mask)
+    chain, plans = AugmentChain(**stages), StepPlans(**plans)
+    head_plans = plans.take(idx_train[:500])
+    # what w_critico and the diagnostics look at
+    head = fe.encode(chain.apply(audio[idx_train[:500]], head_plans), **head_plans.mask_keyword()).cpu().numpy()
     params = _simulation_params(head[0], leak_variance_divisor, num_neurons, num_output_neurons, small_world_k, seed)
     with _rank0_only(rank):
         optimal_weight = calculate_theoretical_w_critico(params, head) * multiplier
@@ -332,12 +326,11 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     def split_features(idx):
         """(len(idx), n_feat) float32 rows in dataset order, STILL ON THE DEVICE (every rank holds all of them)."""
         lo, hi = lsm_dist.shard_range(len(idx), rank, world)
+        shard = plans.take(idx[lo:hi])
         local = pipeline.features_from_audio(audio[idx[lo:hi]], fe, lsm, keys, batch=batch, device_out=True,
                                              time_segments=time_segments,
-                                             corrupt=(mixer, plan.take(idx[lo:hi])) if mixer is not None else None,
-                                             reverb=(rv, rooms.take(idx[lo:hi])) if rv is not None else None,
-                                             speed=(sp, paces.take(idx[lo:hi])) if sp is not None else None,
-                                             **({} if veils is None else {"mask": veils.take(idx[lo:hi])}))
+                                             corrupt=(chain.mixer, shard.mix), reverb=(chain.reverb, shard.reverb),
+                                             speed=(chain.speed, shard.speed), mask=shard.mask)
         return lsm_dist.gather_rows(local, len(idx))
 
     X_train_dev = split_features(idx_train)

@@ -1130,6 +1130,18 @@ class ResampleStream(_ResampleBase):
         return out, new * self.up
 
 
+# ---- per-clip plans (`MixPlan`, `ReverbPlan`, `SpeedPlan`, `MaskPlan`): host arrays of one length, one entry per clip -----------
+def _plan_part(plan, lo: int, hi: int):
+    """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
+    return type(plan)(*(a[lo:hi] for a in plan))
+
+
+def _plan_take(plan, idx):
+    """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
+    idx = np.asarray(idx, dtype=np.int64)
+    return type(plan)(*(a[idx] for a in plan))
+
+
 # ---- noise mixer (SPEC.md §1.10, include/lsm_hip_mix.h) -----------------------------------------------------------------
 MIX_MAX_SAMPLES = 1 << 24
 
@@ -1143,13 +1155,7 @@ class MixPlan(NamedTuple):
     shift: np.ndarray
     scale: np.ndarray
 
-    def part(self, lo: int, hi: int) -> "MixPlan":
-        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
-        return MixPlan(*(a[lo:hi] for a in self))
-
-    def take(self, idx) -> "MixPlan":
-        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
-        return MixPlan(*(a[np.asarray(idx, dtype=np.int64)] for a in self))
+    part, take = _plan_part, _plan_take
 
 
 def _range_draw(value, u: np.ndarray, name: str) -> np.ndarray:
@@ -1396,13 +1402,7 @@ class ReverbPlan(NamedTuple):
     """Per-clip rows of a bank of room impulse responses (`reverb_plan`): ``rows`` int32 on the host, -1 = a dry clip."""
     rows: np.ndarray
 
-    def part(self, lo: int, hi: int) -> "ReverbPlan":
-        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
-        return ReverbPlan(self.rows[lo:hi])
-
-    def take(self, idx) -> "ReverbPlan":
-        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
-        return ReverbPlan(self.rows[np.asarray(idx, dtype=np.int64)])
+    part, take = _plan_part, _plan_take
 
 
 def reverb_plan(n_clips: int, n_rir_rows: int, prob: float = 1.0, seed: int = 42) -> ReverbPlan:
@@ -1595,13 +1595,7 @@ class SpeedPlan(NamedTuple):
     -1 = an unperturbed clip."""
     choice: np.ndarray
 
-    def part(self, lo: int, hi: int) -> "SpeedPlan":
-        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
-        return SpeedPlan(self.choice[lo:hi])
-
-    def take(self, idx) -> "SpeedPlan":
-        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
-        return SpeedPlan(self.choice[np.asarray(idx, dtype=np.int64)])
+    part, take = _plan_part, _plan_take
 
 
 def speed_plan(n_clips: int, n_factors: int, prob: float = 1.0, seed: int = 42) -> SpeedPlan:
@@ -1734,14 +1728,7 @@ class MaskPlan(NamedTuple):
     freq: np.ndarray
     time: np.ndarray
 
-    def part(self, lo: int, hi: int) -> "MaskPlan":
-        """The plan of clips ``lo .. hi - 1``: a batch's or a shard's slice of the whole listing's plan."""
-        return MaskPlan(self.freq[lo:hi], self.time[lo:hi])
-
-    def take(self, idx) -> "MaskPlan":
-        """The plan of the clips ``idx`` names, in that order (a split of the listing)."""
-        idx = np.asarray(idx, dtype=np.int64)
-        return MaskPlan(self.freq[idx], self.time[idx])
+    part, take = _plan_part, _plan_take
 
 
 def mask_plan(n_clips: int, n_filters: int, time_bins: int, freq_masks: int = 0, freq_width: int = 0, time_masks: int = 0,

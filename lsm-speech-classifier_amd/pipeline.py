@@ -17,9 +17,13 @@ kernel (a launch that shares the chip with other kernels prefers fewer, fatter w
 """
 from __future__ import annotations
 
+import contextlib
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
+from .augment import AugmentChain, StepPlans
 from .frontend import as_float32, checked_counts, checked_mask, checked_pcm, checked_slots, indexed_device
 
 DEFAULT_STREAMS = 6
@@ -184,18 +188,35 @@ class RasterRing:
         self.free[bi].record(reader_stream)
 
 
+def _get_or_make(cache: dict, key, make):
+    """``cache[key]``, made by ``make()`` on first use: the buffers a stream slot of the pipeline owns."""
+    got = cache.get(key)
+    if got is None:
+        got = cache[key] = make()
+    return got
+
+
+class _Step(NamedTuple):
+    """One `HotPath.submit`, as the topologies take it: `submit`'s arguments, its four plans packed and checked."""
+    audio: object
+    stats_out: object
+    after: object
+    out: object
+    stage: str
+    tail: bool
+    plans: StepPlans
+
+
 class HotPath:
     """fe: frontend.SpikeFrontEnd, net: snn.SNN (same device).  `streams` = reservoir streams (1 = serial:
     everything on the current stream); `fe_streams` = front-end streams of their own (0 = rotation: a step keeps to
     one of the `streams`; None = DEFAULT_FE_STREAMS).  `time_segments` = K > 1: a step's reservoir launch is the segmented
     one (`SNN.run_segments`, K segments of T // K steps, SPEC.md §4b) and a clip's row is its K segment rows side by side
     (segment-major, then key-major: K times the columns); 1 = the whole-clip row, the calls of a pipeline without it.
-    `mixer` = a `frontend.NoiseMixer`: a step submitted with `mix=` (a `frontend.MixPlan` of its clips) is corrupted on the
-    device before its front end (SPEC.md §1.10); without `mix` a step launches what it launches without a mixer.
-    `reverb` = a `frontend.Reverberator`: a step submitted with `reverb=` (a `frontend.ReverbPlan` of its clips) is convolved
-    with its rooms on the device (SPEC.md §1.11) ahead of the mixer; without it nothing more is launched.
-    `speed` = a `frontend.SpeedPerturber`: a step submitted with `speed=` (a `frontend.SpeedPlan` of its clips) is played at
-    its clips' speeds on the device (SPEC.md §1.12) ahead of the reverberator: speed, reverb, mixer, front end.
+    `speed`, `reverb`, `mixer` = a `frontend.SpeedPerturber`, `Reverberator`, `NoiseMixer`, the stages of the pipeline's
+    `augment.AugmentChain`: a step submitted with `speed=`, `reverb=` or `mix=` (a `frontend.SpeedPlan`, `ReverbPlan`, `MixPlan`
+    of its clips) is played at its clips' speeds (SPEC.md §1.12), then convolved with their room responses (§1.11), then
+    corrupted (§1.10) on the device before its front end; a step without a plan launches what it launches without the stage.
     With at most FUSED_STEP_MAX_HW_QUEUES hardware queues a full step without any of these, of a shape `step_fused_supported`
     accepts, is one launch (`_submit_fused`); `time_reservoir`'s event pair then brackets that launch, front end included.
     `fused_forms` = True: there a masked step is one launch too (`lsm_step_fused_masked_f64`), and a step with speed, reverb or
@@ -208,18 +229,8 @@ class HotPath:
                  fused_forms: bool = False):
         if indexed_device(fe.device) != indexed_device(net.device):
             raise ValueError(f"front end on {fe.device}, reservoir on {net.device}")
-        if mixer is not None and indexed_device(mixer.device) != indexed_device(fe.device):
-            raise ValueError(f"mixer on {mixer.device}, front end on {fe.device}")
-        self.mixer = mixer                  # frontend.NoiseMixer or None: submit(mix=...) corrupts a step's clips with it
-        self._mixed = {}                    # (rotation slot, batch shape) -> the mix launch's output buffer
-        if reverb is not None and indexed_device(reverb.device) != indexed_device(fe.device):
-            raise ValueError(f"reverberator on {reverb.device}, front end on {fe.device}")
-        self.reverb = reverb                # frontend.Reverberator or None: submit(reverb=...) convolves a step's clips with it
-        self._reverbed = {}                 # (rotation slot, batch shape) -> the reverb launch's output buffer
-        if speed is not None and indexed_device(speed.device) != indexed_device(fe.device):
-            raise ValueError(f"speed perturber on {speed.device}, front end on {fe.device}")
-        self.speed = speed                  # frontend.SpeedPerturber or None: submit(speed=...) plays a step's clips through it
-        self._sped = {}                     # (rotation slot, batch shape) -> the speed launch's output buffer
+        self.chain = AugmentChain(speed, reverb, mixer)    # the stages a step's plans (`submit`) run through, in its order
+        self.chain.check_device(fe.device)
         if fe.n_channels != net.n_channels:
             raise ValueError(f"front end has {fe.n_channels} channels, reservoir expects {net.n_channels}")
         self.fe, self.net = fe, net
@@ -268,39 +279,47 @@ class HotPath:
         self.fused_step = (self.n_streams > 1 and self.hw_queues <= FUSED_STEP_MAX_HW_QUEUES and self.time_segments == 1
                            and (self.fused_forms or (mixer is None and reverb is None and speed is None)))
         self.n_fused_streams = max(1, min(self.hw_queues - 1, self.n_streams))
-        self._fused_ok = {}                 # batch size -> step_fused_supported
-        self._fused_ws = {}                 # (rotation slot, batch size) -> the launch's front-end scratch
+        self._fused_ok = {}                 # (batch size, form) -> step_fused_supported
+        # what a slot owns beside its raster ring (`_owned`): ("h2d" / "speed" / "reverb" / "mix", slot, batch shape) -> the
+        # upload's / that launch's output buffer, ("workspace", slot, batch size) -> the fused step's front-end scratch
+        self._buffers = {}
         self._in_flight = []                # one event per submitted step, on the stream its last launch went to
         self._step = 0
         self.reservoir_events = []          # (start, end) HIP event pairs, one per submitted step (time_reservoir)
-        self._h2d = {}
 
     # ---- one step ---------------------------------------------------------------------------
-    def _one(self, x, stats_out, out, stage, tail=False, mask=None):
-        rasters = x if stage == "reservoir" else self.fe.encode(x, **({} if mask is None else {"mask": mask}))
+    @contextlib.contextmanager
+    def _timed(self):
+        """With `time_reservoir`: an event pair on the current stream around the launches made inside."""
+        if not self.time_reservoir:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        self.reservoir_events.append((e0, e1))
+
+    def _one(self, x, step, stage=None):
+        """The launches of `step` (or only those of `stage`) over `x` on the current stream."""
+        stage = stage or step.stage
+        rasters = x if stage == "reservoir" else self.fe.encode(x, **step.plans.mask_keyword())
         if stage == "frontend":
             return rasters
-        if self.time_reservoir:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
         # a tail step's reservoir launch meets a draining GPU: the layout of a lone launch (more, thinner waves) when the
         # choice is the library's (profiles/r04_tail_steps.txt)
-        wpc = 0 if (tail and self.waves_per_clip == -1) else self.waves_per_clip
-        if self.time_segments > 1:
-            K, B = self.time_segments, int(rasters.shape[0])
-            feats = self.net.run_segments(rasters, int(rasters.shape[2]) // K, self.feature_keys, waves_per_clip=wpc,
-                                          stats_out=stats_out,
-                                          features_out=out.view(B, K, -1) if out is not None else None).view(B, -1)
-        else:
-            feats, _, _ = self.net.run_batch(rasters, self.feature_keys, waves_per_clip=wpc,
-                                             stats_out=stats_out, features_out=out)
-        if self.time_reservoir:
-            e1.record()
-            self.reservoir_events.append((e0, e1))
-        return feats
+        wpc = 0 if (step.tail and self.waves_per_clip == -1) else self.waves_per_clip
+        with self._timed():
+            if self.time_segments > 1:
+                K, B = self.time_segments, int(rasters.shape[0])
+                return self.net.run_segments(rasters, int(rasters.shape[2]) // K, self.feature_keys, waves_per_clip=wpc,
+                                             stats_out=step.stats_out,
+                                             features_out=step.out.view(B, K, -1) if step.out is not None else None).view(B, -1)
+            return self.net.run_batch(rasters, self.feature_keys, waves_per_clip=wpc, stats_out=step.stats_out,
+                                      features_out=step.out)[0]
 
-    def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
-               reverb=None, speed=None, mask=None):
+    def submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False,
+               mix=None, reverb=None, speed=None, mask=None):
         """Issue one step on the next stream of the rotation.  `audio`: (B, n_samples) float32 -- device tensor,
         or pinned/pageable host tensor / NumPy array, uploaded on the step's own stream.  Returns (features
         (B, n_keys*N_out) device tensor, stream it is produced on); the caller waits (`stream.synchronize()`,
@@ -318,53 +337,46 @@ class HotPath:
         with one chain per lane (twice the waves, each half as long), the reservoir launch as a lone launch would be laid
         out.  At the end of a burst the last front end otherwise runs alone on a quarter of the chip for ~2 ms while the
         rest drains (profiles/r04_tail_steps.txt); inside a long run the normal layouts use fewer CU-cycles.
-        `mix`: a `frontend.MixPlan` of this step's B clips (needs the pipeline's `mixer`): one more launch on the stream
-        that runs the step's front end, between the upload and `encode`, into a buffer the rotation slot owns; no host
+        `speed`, `reverb`, `mix`: a `frontend.SpeedPlan` / `ReverbPlan` / `MixPlan` of this step's B clips (each needs the
+        pipeline's stage of that kind): one more launch each (`AugmentChain.apply`: speed, reverberation, mixer) on the stream
+        that runs the step's front end, between the upload and `encode`, each into a buffer the stream slot owns; no host
         synchronisation.
-        `reverb`: a `frontend.ReverbPlan` of this step's B clips (needs the pipeline's `reverb`): one more launch on the same
-        stream ahead of the mixer's, into a buffer the rotation slot owns.
-        `speed`: a `frontend.SpeedPlan` of this step's B clips (needs the pipeline's `speed`): one more launch on the same
-        stream ahead of the reverberator's, into a buffer the rotation slot owns.
         `mask`: a `frontend.MaskPlan` of this step's B clips (SPEC.md §1.13): the step's front end is the masked entry point
         -- the mask acts inside the encoder, behind every corruption of the audio -- and still writes into the pipeline's
         raster rings; the words are uploaded on the front end's stream, no host synchronisation.  A step without it launches
         what it always did.
         Back-pressure: when `max_ahead` earlier steps have not finished, submit() first waits for the oldest."""
-        if mix is not None and (self.mixer is None or stage == "reservoir"):
-            raise ValueError("submit(mix=...) needs a HotPath built with a mixer and a step that has a front end")
-        if reverb is not None and (self.reverb is None or stage == "reservoir"):
-            raise ValueError("submit(reverb=...) needs a HotPath built with a reverberator and a step that has a front end")
-        if speed is not None and (self.speed is None or stage == "reservoir"):
-            raise ValueError("submit(speed=...) needs a HotPath built with a speed perturber and a step that has a front end")
+        step = _Step(audio, stats_out, after, out, stage, tail, StepPlans(speed, reverb, mix, mask))
+        self.chain.refuse(step.plans, front_end=stage != "reservoir")
         if mask is not None:
             if stage == "reservoir":
                 raise ValueError("submit(mask=...) needs a step that has a front end")
             checked_mask(mask, len(audio), self.fe.n_filters, self.fe.time_bins)
-        res, st = self._submit(audio, stats_out, after, out, stage, tail, mix, reverb, speed, mask)
-        if st is not None and self.n_streams > 1:
-            ev = torch.cuda.Event()
-            ev.record(st)
-            self._in_flight.append(ev)
-        return res, st
-
-    def _submit(self, audio, stats_out=None, after=None, out=None, stage: str = "full", tail: bool = False, mix=None,
-                reverb=None, speed=None, mask=None):
-        """submit() without the in-flight bookkeeping."""
         if stage not in STAGES:
             raise ValueError(f"stage must be one of {STAGES}, got {stage!r}")
         slot = self._step % self.n_streams
         self._step += 1
         while len(self._in_flight) >= self.max_ahead:
             self._in_flight.pop(0).synchronize()
+        res, st = self._submit(slot, step)
+        if st is not None and self.n_streams > 1:
+            ev = torch.cuda.Event()
+            ev.record(st)
+            self._in_flight.append(ev)
+        return res, st
+
+    def _submit(self, slot, step):
+        """The step on the topology that serves it."""
+        masked = step.plans.mask is not None
         if self.n_streams == 1:
             topology = self._submit_serial
-        elif stage == "full" and (mask is None or self.fused_forms) and self._takes_fused_step(audio, mask is not None):
+        elif step.stage == "full" and (not masked or self.fused_forms) and self._takes_fused_step(step.audio, masked):
             topology = self._submit_fused
-        elif self.n_fe_streams and stage != "reservoir":
+        elif self.n_fe_streams and step.stage != "reservoir":
             topology = self._submit_two_stages
         else:
             topology = self._submit_rotation
-        return topology(slot, audio, stats_out, after, out, stage, tail, mix, reverb, speed, mask)
+        return topology(slot, step)
 
     def _wait_for_input(self, stream, cur, audio, after) -> None:
         """The ordering of a device input (`submit`): `stream` waits for `after`, or for what `cur` has issued so far."""
@@ -373,51 +385,43 @@ class HotPath:
         elif torch.is_tensor(audio) and audio.device == self.device:
             stream.wait_stream(cur)
 
-    def _submit_serial(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None,
-                       mask=None):
+    def _submit_serial(self, slot, step):
         """Everything on the current stream."""
         cur = torch.cuda.current_stream(self.device)
-        if after is not None:
-            cur.wait_event(after)
+        if step.after is not None:
+            cur.wait_event(step.after)
         with torch.cuda.device(self.device):
-            x = audio if stage == "reservoir" else self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
-            return self._one(x, stats_out, out, stage, tail, mask), cur
+            return self._one(self._input(step, slot), step), cur
 
-    def _submit_rotation(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None,
-                         mask=None):
+    def _submit_rotation(self, slot, step):
         """The step keeps to reservoir stream `slot`: its front end, then its reservoir launch."""
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
-            self._wait_for_input(st, cur, audio, after)
-            x = audio if stage == "reservoir" else self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
-            return self._one(x, stats_out, out, stage, tail, mask), st
+            self._wait_for_input(st, cur, step.audio, step.after)
+            return self._one(self._input(step, slot), step), st
 
-    def _submit_two_stages(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None,
-                           mask=None):
+    def _submit_two_stages(self, slot, step):
         """The front end on the next front-end stream, the reservoir launch on reservoir stream `slot` behind an event."""
         fslot = (self._step - 1) % self.n_fe_streams
         st, fst, cur = self.streams[slot], self.fe_streams[fslot], torch.cuda.current_stream(self.device)
+        stage = step.stage
         with torch.cuda.device(self.device):
             with torch.cuda.stream(fst):
-                self._wait_for_input(fst, cur, audio, after)
-                low_latency = self._low_latency(tail)
-                x = self._augmented(self._to_device(audio, ("fe", fslot)), speed, reverb, mix, ("fe", fslot))
+                self._wait_for_input(fst, cur, step.audio, step.after)
+                low_latency = self._low_latency(step.tail)
+                x = self._input(step, ("fe", fslot))
                 # the front end's own decision (mel branch, > 1024 filters and LSM_FRONTEND_SPLIT=1 take the split
                 # route, which allocates its raster on the front-end stream): only the fused launch of a full step
                 # writes into the pipeline's rings, everything else goes through record_stream below (ADVICE r3)
                 ring, owned = None, {}
                 if stage == "full" and self.fe.will_fuse():
-                    key = (fslot, int(x.shape[0]))
-                    ring = self._rasters.get(key)
-                    if ring is None:
-                        ring = self._rasters[key] = RasterRing(self.fe, key[1], self.device)
+                    ring = _get_or_make(self._rasters, (fslot, int(x.shape[0])),
+                                        lambda: RasterRing(self.fe, int(x.shape[0]), self.device))
                     owned = dict(raster_out=ring.acquire(fst), workspace=ring.workspace)
                 # `share_lds` stays off: beside the ring-row kernel at 4000 neurons (64 KB of LDS per clip, two per CU)
                 # the whole path runs 6.37-6.40 ms per step without the front end's LDS reservation against 6.26-6.28
                 # with it (profiles/r04_cfg4_frontend_lds_placement.txt)
-                if mask is not None:
-                    owned["mask"] = mask
-                rasters = self.fe.encode(x, low_latency=low_latency, **owned)
+                rasters = self.fe.encode(x, low_latency=low_latency, **owned, **step.plans.mask_keyword())
                 done = torch.cuda.Event()
                 done.record(fst)
                 self._fe_done.append(done)
@@ -427,43 +431,30 @@ class HotPath:
                 rasters.record_stream(st)      # allocated on the front-end stream, read on the reservoir stream
             with torch.cuda.stream(st):
                 st.wait_event(done)
-                feats = self._one(rasters, stats_out, out, "reservoir", tail)
+                feats = self._one(rasters, step, "reservoir")
                 if ring is not None:
                     ring.release(st)
                 return feats, st
 
     def _takes_fused_step(self, audio, masked: bool = False) -> bool:
         """Whether a full step over `audio` is the one-launch step (decided once per batch size and form)."""
-        if not self.fused_step:
-            return False
-        key = (int(len(audio)), "masked") if masked else int(len(audio))
-        ok = self._fused_ok.get(key)
-        if ok is None:
-            ok = self._fused_ok[key] = step_fused_supported(self.fe, self.net, int(len(audio)), "masked" if masked else "plain")
-        return ok
+        form = "masked" if masked else "plain"
+        return self.fused_step and _get_or_make(self._fused_ok, (int(len(audio)), form),
+                                                lambda: step_fused_supported(self.fe, self.net, int(len(audio)), form))
 
-    def _submit_fused(self, slot, audio, stats_out, after, out, stage, tail, mix=None, reverb=None, speed=None, mask=None):
+    def _submit_fused(self, slot, step):
         """The whole step as one launch (`step_fused`) on stream (step number) % n_fused_streams.  With `time_reservoir` the
         event pair brackets that launch: front end and reservoir of the step together."""
         slot = (self._step - 1) % self.n_fused_streams
         st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device), torch.cuda.stream(st):
-            self._wait_for_input(st, cur, audio, after)
-            x = self._augmented(self._to_device(audio, slot), speed, reverb, mix, slot)
-            key = (slot, int(x.shape[0]))
-            ws = self._fused_ws.get(key)
-            if ws is None:
-                ws = self._fused_ws[key] = self.fe.new_workspace(key[1])
-            if self.time_reservoir:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            extra = {} if mask is None else {"mask": mask}      # a step without a mask is launched as it always was
-            feats = step_fused(self.fe, self.net, x, self.feature_keys, stats_out=stats_out, features_out=out, workspace=ws,
-                               **extra)
-            if self.time_reservoir:
-                e1.record()
-                self.reservoir_events.append((e0, e1))
-            return feats, st
+            self._wait_for_input(st, cur, step.audio, step.after)
+            x = self._input(step, slot)
+            B = int(x.shape[0])
+            ws = _get_or_make(self._buffers, ("workspace", slot, B), lambda: self.fe.new_workspace(B))
+            with self._timed():
+                return step_fused(self.fe, self.net, x, self.feature_keys, stats_out=step.stats_out, features_out=step.out,
+                                  workspace=ws, **step.plans.mask_keyword()), st
 
     def _low_latency(self, tail: bool) -> bool:
         """Whether this step's fused gammatone front end goes out in the low-latency layout: on a tail step, and when it
@@ -474,52 +465,24 @@ class HotPath:
         self._fe_done = [ev for ev in self._fe_done[-8:] if not ev.query()]
         return self.fe.filterbank == "gammatone" and self.fe.will_fuse() and (tail or not self._fe_done)
 
-    def _to_device(self, audio, slot):
+    def _owned(self, kind: str, slot, shape) -> torch.Tensor:
+        """The float32 buffer of `shape` that stream slot `slot` owns for its uploads ("h2d") or for the output of one of its
+        augmentation launches ("speed", "reverb", "mix"); made on first use, on the current stream."""
+        return _get_or_make(self._buffers, (kind, slot, tuple(shape)),
+                            lambda: torch.empty(tuple(shape), dtype=torch.float32, device=self.device))
+
+    def _input(self, step, slot):
+        """What the step's first launch reads, on the current stream: a raster batch as it is; audio uploaded when it lies
+        on the host (an asynchronous copy), then through the augmentation chain for the plans the step has."""
+        audio = step.audio
+        if step.stage == "reservoir":
+            return audio
         if isinstance(audio, np.ndarray):
             audio = as_float32(audio)
-        if audio.device == self.device:
-            return audio
-        # host batch: asynchronous copy on the step's stream into this rotation slot's own buffer
-        buf = self._h2d.get((slot, tuple(audio.shape)))
-        if buf is None:
-            buf = self._h2d[(slot, tuple(audio.shape))] = torch.empty(audio.shape, dtype=torch.float32,
-                                                                      device=self.device)
-        buf.copy_(audio, non_blocking=True)
-        return buf
-
-    def _mix(self, x, mix, slot):
-        """The step's clips corrupted by `mix` on the current stream (the one that runs its front end), or `x` itself."""
-        if mix is None:
-            return x
-        key = (slot, tuple(x.shape))
-        buf = self._mixed.get(key)
-        if buf is None:
-            buf = self._mixed[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
-        return self.mixer.mix(x, mix.snr_db, mix.rows, mix.offsets, mix.shift, mix.scale, out=buf)
-
-    def _reverb(self, x, plan, slot):
-        """The step's clips convolved with the rooms of `plan` on the current stream (ahead of `_mix`), or `x` itself."""
-        if plan is None:
-            return x
-        key = (slot, tuple(x.shape))
-        buf = self._reverbed.get(key)
-        if buf is None:
-            buf = self._reverbed[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
-        return self.reverb.reverb(x, plan.rows, out=buf)
-
-    def _speed(self, x, plan, slot):
-        """The step's clips played at the speeds of `plan` on the current stream (ahead of `_reverb`), or `x` itself."""
-        if plan is None:
-            return x
-        key = (slot, tuple(x.shape))
-        buf = self._sped.get(key)
-        if buf is None:
-            buf = self._sped[key] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
-        return self.speed.perturb(x, plan.choice, out=buf)
-
-    def _augmented(self, x, speed, reverb, mix, slot):
-        """The augmentation chain in front of the front end, in the recipe's order: speed, reverberation, mixer."""
-        return self._mix(self._reverb(self._speed(x, speed, slot), reverb, slot), mix, slot)
+        if audio.device != self.device:
+            host, audio = audio, self._owned("h2d", slot, audio.shape)
+            audio.copy_(host, non_blocking=True)
+        return self.chain.apply(audio, step.plans, lambda stage, shape: self._owned(stage, slot, shape))
 
     def prime(self, audio, stage: str = "full", min_ms: float = 0.0):
         """One untimed step on EVERY stream of the pipeline, then a synchronisation: each stream's first use
@@ -577,24 +540,28 @@ class HotPath:
         is an iterable of (B_i, n_samples) arrays/tensors (host or device); `mixes`, when given, an iterable of one
         `frontend.MixPlan` per batch (`submit(mix=...)`); `reverbs` likewise one `frontend.ReverbPlan` per batch, `speeds` one
         `frontend.SpeedPlan` per batch, `masks` one `frontend.MaskPlan` per batch (`submit(mask=...)`)."""
+        its = [None if plans is None else iter(plans) for plans in (speeds, reverbs, mixes, masks)]
+
+        def each_batch():
+            while True:             # a list, not a generator expression: `next` runs here, once per batch
+                yield StepPlans(*[None if it is None else next(it) for it in its])
+
+        return self._run(audio_batches, each_batch(), out)
+
+    def _run(self, audio_batches, plans, out=None) -> torch.Tensor:
+        """`run` with one iterator of `StepPlans`, asked for one per batch as the batches come."""
         self.fork_from_current()
         # The last TAIL_STEPS batches are submitted in the low-latency layouts: that needs a look-ahead of TAIL_STEPS
         # batches, not the whole list -- a lazily produced stream of (pinned or device) batches is consumed as it comes and
         # never held in full (ADVICE r4).
         from collections import deque
-        parts, ahead, it = [], deque(), iter(audio_batches)
-        plans = iter(mixes) if mixes is not None else None
-        rooms = iter(reverbs) if reverbs is not None else None
-        paces = iter(speeds) if speeds is not None else None
-        veils = iter(masks) if masks is not None else None
+        parts, ahead = [], deque()
 
-        def step(a0, m0, r0, s0, k0, tail):
-            extra = {} if k0 is None else {"mask": k0}        # a step without a mask is submitted as it always was
-            return self.submit(a0, tail=tail, mix=m0, reverb=r0, speed=s0, **extra)[0]
+        def step(audio, p, tail):
+            return self.submit(audio, tail=tail, mix=p.mix, reverb=p.reverb, speed=p.speed, **p.mask_keyword())[0]
 
-        for a in it:
-            ahead.append((a, next(plans) if plans is not None else None, next(rooms) if rooms is not None else None,
-                          next(paces) if paces is not None else None, next(veils) if veils is not None else None))
+        for a in audio_batches:
+            ahead.append((a, next(plans)))
             if len(ahead) > TAIL_STEPS:
                 parts.append(step(*ahead.popleft(), False))
         while ahead:
@@ -617,23 +584,14 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     (n, n_feat) float32 on the host (or, `device_out`, still on the GPU for a gather), batches of `batch` clips
     through the overlapped pipeline (pinned staging, uploads on the steps' streams).  n = 0 (an empty shard)
     gives an empty (0, n_feat) block.  `time_segments` = K > 1: K segment rows per clip side by side (`HotPath`), n_feat is
-    K times as wide.  `corrupt` = ``(frontend.NoiseMixer, frontend.MixPlan of the n clips)``: every batch is corrupted on
-    the device with its slice of the plan before its front end (SPEC.md §1.10).  `reverb` = ``(frontend.Reverberator,
-    frontend.ReverbPlan of the n clips)``: every batch is convolved with its rooms ahead of that (SPEC.md §1.11).  `speed` =
-    ``(frontend.SpeedPerturber, frontend.SpeedPlan of the n clips)``: every batch is played at its clips' speeds ahead of
-    both (SPEC.md §1.12).  `mask` = a ``frontend.MaskPlan`` of the n clips: every batch's front end masks its slice of the
-    plan inside the encoder (SPEC.md §1.13)."""
-    if mask is not None and not (len(mask.freq) == len(mask.time) == len(audio)):
-        raise ValueError(f"the mask plan covers {len(mask.freq)} / {len(mask.time)} clips, audio has {len(audio)}")
-    sp, paces = speed if speed is not None else (None, None)
-    if paces is not None and len(paces.choice) != len(audio):
-        raise ValueError(f"the speed plan covers {len(paces.choice)} clips, audio has {len(audio)}")
-    rv, rooms = reverb if reverb is not None else (None, None)
-    if rooms is not None and len(rooms.rows) != len(audio):
-        raise ValueError(f"the reverb plan covers {len(rooms.rows)} clips, audio has {len(audio)}")
-    mixer, plan = corrupt if corrupt is not None else (None, None)
-    if plan is not None and len(plan.rows) != len(audio):
-        raise ValueError(f"the plan covers {len(plan.rows)} clips, audio has {len(audio)}")
+    K times as wide.  `speed` = ``(frontend.SpeedPerturber, frontend.SpeedPlan of the n clips)``, `reverb` =
+    ``(frontend.Reverberator, frontend.ReverbPlan of the n clips)``, `corrupt` = ``(frontend.NoiseMixer, frontend.MixPlan of the
+    n clips)``: every batch goes through these stages on the device, in this order (`augment.AugmentChain`; SPEC.md §1.12,
+    §1.11, §1.10), with its slice of each plan, before its front end.  `mask` = a ``frontend.MaskPlan`` of the n clips: every
+    batch's front end masks its slice of the plan inside the encoder (SPEC.md §1.13)."""
+    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
+    plans = StepPlans(speeds, reverbs, mixes, mask)
+    plans.check_covers(len(audio))
     hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer, reverb=rv, speed=sp)
     pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
     if len(pinned):
@@ -642,12 +600,8 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
         except RuntimeError:
             pass
     with torch.cuda.device(hp.device):
-        feats = hp.run((pinned[lo:lo + batch] for lo in range(0, len(pinned), batch)),
-                       mixes=(plan.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if plan is not None else None,
-                       reverbs=(rooms.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if rooms is not None else None,
-                       speeds=(paces.part(lo, lo + batch) for lo in range(0, len(pinned), batch)) if paces is not None else None,
-                       **({} if mask is None else
-                          {"masks": (mask.part(lo, lo + batch) for lo in range(0, len(pinned), batch))}))
+        starts = range(0, len(pinned), batch)
+        feats = hp._run((pinned[lo:lo + batch] for lo in starts), (plans.part(lo, lo + batch) for lo in starts))
     return feats if device_out else feats.cpu().numpy()
 
 
@@ -964,15 +918,14 @@ class AudioStreamBank:
             if resampler.unit_blocks * resampler.up != resampler.unit_hops * int(gt_stream.hop):
                 raise ValueError(f"a unit of the resampler is {resampler.unit_blocks * resampler.up} samples, not "
                                  f"{resampler.unit_hops} hops of the front end's {gt_stream.hop}")
-        if mixer is not None and int(mixer.n_streams) != int(gt_stream.n_streams):
-            raise ValueError(f"the mixer serves {mixer.n_streams} streams, the front end {gt_stream.n_streams}")
-        if reverb is not None and int(reverb.n_streams) != int(gt_stream.n_streams):
-            raise ValueError(f"the reverberator serves {reverb.n_streams} streams, the front end {gt_stream.n_streams}")
+        for name, stage in (("mixer", mixer), ("reverberator", reverb)):
+            if stage is not None and int(stage.n_streams) != int(gt_stream.n_streams):
+                raise ValueError(f"the {name} serves {stage.n_streams} streams, the front end {gt_stream.n_streams}")
         if net.n_channels != gt_stream.n_channels:
             raise ValueError(f"the front end has {gt_stream.n_channels} channels, the reservoir {net.n_channels}")
-        self.reverb = reverb                # frontend.ReverbStream or None: behind the resampler, in front of the mixer
         self.gt, self.net, self.S, self.n_thr, self.resampler = gt_stream, net, S, n_thr, resampler
-        self.mixer = mixer                  # frontend.MixStream or None: behind the resampler, in front of the front end
+        # behind the resampler, in front of the front end, in this order: frontend.ReverbStream, frontend.MixStream
+        self.stages = [stage for stage in (reverb, mixer) if stage is not None]
         self.n_streams = int(gt_stream.n_streams)
         self.bank = StreamBank(net, self.n_streams, S, window_segments, hop_segments, feature_keys)
         # time-major: an item is one raster step, (C,)
@@ -987,12 +940,8 @@ class AudioStreamBank:
         """The streams in ``slots`` have ended and new ones take their places: both halves and the pending columns."""
         if self.resampler is not None:
             self.resampler.reset(slots)
-        if self.reverb is not None:
-            self.reverb.reset(slots)
-        if self.mixer is not None:
-            self.mixer.reset(slots)
-        self.gt.reset(slots)
-        self.bank.reset(slots)
+        for stage in (*self.stages, self.gt, self.bank):
+            stage.reset(slots)
         self.pending.reset(checked_slots(slots, self.n_streams))
 
     def push(self, audio, hops=None):
@@ -1004,10 +953,8 @@ class AudioStreamBank:
         S = self.S
         if self.resampler is not None:
             audio, hops = self._resampled(audio, hops)
-        if self.reverb is not None:
-            audio = self._mixed(audio, hops, self.reverb)
-        if self.mixer is not None:
-            audio = self._mixed(audio, hops)
+        for stage in self.stages:
+            audio = self._through(stage, audio, hops)
         raster, cols = self.gt.push(audio, hops)
         dev = self.net.device
         with torch.cuda.device(dev):
@@ -1018,16 +965,14 @@ class AudioStreamBank:
             joined = run[:, :int(segs.max()) * S].transpose(1, 2).contiguous()
         return self.bank.push(joined, segs)
 
-
-    def _mixed(self, audio, hops, stage=None):
-        """The first ``hops[b]`` hops of every row through the mixer (or ``stage``, the reverberator); the rows keep their
-        length."""
+    def _through(self, stage, audio, hops):
+        """The first ``hops[b]`` hops of every row through ``stage`` (the reverberator, the mixer); the rows keep their length."""
         hop = int(self.gt.hop)
         audio = as_float32(audio)
         if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % hop or audio.shape[1] < hop:
             raise ValueError(f"audio must be ({self.n_streams}, H * {hop}) with H >= 1, got {tuple(audio.shape)}")
         new = checked_counts(hops, self.n_streams, int(audio.shape[1]) // hop, "hops")
-        return (stage or self.mixer).push(audio, None if hops is None else new * hop)[0]
+        return stage.push(audio, None if hops is None else new * hop)[0]
 
     def _resampled(self, audio, units):
         """A push at the resampler's input rate -> ``(samples, hops)`` as the front end takes them."""
