@@ -14,7 +14,8 @@
  *       1) with 3 live windows (2 * hop < nwin <= 3 * hop); a reservoir whose launch inside a pipeline (waves_per_clip = -1) is
  *       the dense-row kernel with 4 waves per clip, 1, 2 or 4 neuron slots per lane, coloured input masks and a refractory
  *       period of 2; time_bins * n_thr steps that fit the reservoir's plan.  The entry points have no spike matrix, membrane
- *       trace, state or segments: a step that needs one of them takes the two launches.
+ *       trace, state or segments: a step that needs a spike matrix or a trace takes the two launches, one that carries
+ *       state or closes time segments has entry points of its own (lsm_hip_step_state.h).
  *   lsm_step_fused_form_supported   the same question for one form of the step: `form` 0 the plain step (the answer of
  *       lsm_step_fused_supported), 1 the masked step (served wherever the plain one is), 2 the ragged step, which
  *       additionally needs hop == 160 (the one hop the ragged front end is offered for, lsm_hip_ragged.h).  The LDS bound is

@@ -195,6 +195,18 @@ STEP_SIGS["lsm_step_fused_ragged_f64"] = (c_int, STEP_SIGS["lsm_step_fused_f64"]
                                           + STEP_SIGS["lsm_step_fused_f64"][1][10:])
 STEP_SYMBOLS = tuple(STEP_SIGS)
 
+# include/lsm_hip_step_state.h (SPEC.md §4f): the step with carried state and time segments -- a query of its own, the plain
+# step with first_step, state_in, state_out in front of key_ids, and that list with segment_steps, records_out,
+# segment_rows_out in front of the stream
+STEP_STATE_SIGS = {
+    "lsm_step_fused_state_supported": (c_int, list(STEP_SIGS["lsm_step_fused_supported"][1])),
+    "lsm_step_fused_from_f64": (c_int, STEP_SIGS["lsm_step_fused_f64"][1][:17] + [c_int, c_void, c_void]
+                                + STEP_SIGS["lsm_step_fused_f64"][1][17:]),
+}
+STEP_STATE_SIGS["lsm_step_fused_segments_f64"] = (c_int, STEP_STATE_SIGS["lsm_step_fused_from_f64"][1][:-1]
+                                                  + [c_int, c_void, c_void, c_void])
+STEP_STATE_SYMBOLS = tuple(STEP_STATE_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -245,7 +257,8 @@ def load():
     for name, (res, args) in (list(_SIGS.items()) + list(STREAM_SIGS.items()) + list(AUDIO_SIGS.items())
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
-                              + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())):
+                              + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
+                              + list(STEP_STATE_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -74,7 +74,7 @@ struct DenseArgs {
 // ST: the launch continues from a saved state and / or saves its own (lif_common.h); prologue and epilogue only.  REFM: the
 // state's countdown 2 / 1 is the lane mask h2 / h1.
 // The body is lif_dense_kernel.inc: one text for this kernel and for the fused step kernel (step_fused.hip), which runs it
-// behind the front end of the same clip.  The five macros name what differs between the two: where the LDS image lies, where
+// behind the front end of the same clip.  The six macros name what differs between the two: where the LDS image lies, where
 // the input bit rows come from, and how many steps the clip runs and its features count; here they expand to the tokens the
 // body held before it was shared.
 template <int SL, int WPC, int INMODE, bool REFM, bool ST = false>
@@ -84,21 +84,36 @@ __global__ __launch_bounds__(WPC * 64) void lif_dense_kernel(const DenseArgs a)
 #define LSM_DENSE_LDS smem
 #define LSM_DENSE_INPUT_BITS_INC "lif_dense_pack_raster.inc"
 #define LSM_DENSE_CLIP_STEPS \
-    !ST ? T : SCALE_LATE ? clip_step_count_unscaled(a.st, b, T) : clip_step_count(a.st, b, T, offsetof(DenseArgs, st))
+    !ST ? T : SCALE_LATE ? clip_step_count_unscaled(a.st, b, T) : clip_step_count(a.st, b, T, LSM_DENSE_ST_OFFSET)
 #define LSM_DENSE_FEATURE_STEPS ST ? Tb + a.st.t0 : T
+#define LSM_DENSE_ST_OFFSET offsetof(DenseArgs, st)
 #include "lif_dense_kernel.inc"
 #undef LSM_DENSE_LDS_DECL
 #undef LSM_DENSE_LDS
 #undef LSM_DENSE_INPUT_BITS_INC
 #undef LSM_DENSE_CLIP_STEPS
 #undef LSM_DENSE_FEATURE_STEPS
+#undef LSM_DENSE_ST_OFFSET
 }
 
 typedef void (*dense_fn_t)(const DenseArgs);
 
-// reservoir.hip, for step_fused.hip: the arguments, slots per lane and LDS bytes of the dense launch of one pipeline step
+// What a state step (include/lsm_hip_step_state.h) adds to the dense launch of a pipeline step: lsm_reservoir_run_from's
+// first_step and state blocks and, `segmented`, lsm_reservoir_run_segments' segment_steps and records.
+struct StepState {
+    int first_step = 0;
+    const void *state_in = nullptr;
+    void *state_out = nullptr;
+    bool segmented = false;
+    int segment_steps = 0;
+    void *records = nullptr;
+};
+
+// reservoir.hip, for step_fused.hip: the arguments, slots per lane and LDS bytes of the dense launch of one pipeline step.
+// `state`: the step continues from / saves a state or closes segment records -- the refusals are then those of
+// lsm_reservoir_run_from / _run_segments (n_keys may be 0), and DenseArgs::st is filled as those entry points fill it.
 int step_dense_args(const ::lsm_reservoir *h, int n_clips, int n_steps, const int32_t *key_ids, int n_keys, float *features,
-                    int32_t *stats, bool probe, DenseArgs *out, int *sl_out, size_t *lds_out);
+                    int32_t *stats, bool probe, DenseArgs *out, int *sl_out, size_t *lds_out, const StepState *state = nullptr);
 
 // REFM needs 2 x 2 scalar registers per slot: offered up to 4 slots per lane (the layouts of N <= 4096 with >= 4
 // waves, i.e. every reservoir the dense rows serve by default); fatter layouts keep the countdown in vector registers.

@@ -11,6 +11,9 @@
 //                        (`Tf`), as expressions: lif_dense.h's are the launch's T or, in the ST forms, the state block's count
 //                        and t0 + Tb; the fused step's tail gives a ragged clip its own count for both (SPEC.md §4c with
 //                        t0 = 0) without a state block.  T stays the row stride and the size of the LDS image.
+//   LSM_DENSE_ST_OFFSET  ST forms: the byte offset of the launch's StateArgs (`a.st`) in the kernel-argument segment, which
+//                        the zero-step exit reads it from (state_pass_through, clip_step_count): offsetof(DenseArgs, st) where
+//                        the argument struct is the kernel's only parameter, behind FusedArgs in the fused step's state forms.
     constexpr bool INREG = INMODE == 1;
     constexpr bool INMASK = INMODE >= 2;
     constexpr bool INCOL = INMODE == 3;
@@ -40,7 +43,7 @@
     int Tb = LSM_DENSE_CLIP_STEPS;
     if constexpr (ST) {
         if (Tb == 0) {
-            state_pass_through<NT>(b, tid, offsetof(DenseArgs, st));
+            state_pass_through<NT>(b, tid, LSM_DENSE_ST_OFFSET);
             return;
         }
         if constexpr (SCALE_LATE) Tb = stream_step_scale(a.st, Tb, T);

@@ -1313,16 +1313,39 @@ static int run_dense(const lsm_reservoir *h, const Variant &v, const RunArgs &r)
 // order), as its arguments.  The step kernel has the <SL, 4, 3, true> forms only: any other plan is LSM_ERR_UNSUPPORTED.
 // `probe`: the shape alone is asked about (lsm_step_fused_supported), no buffer is looked at.
 int lsm_lif::step_dense_args(const lsm_reservoir *h, int n_clips, int n_steps, const int32_t *key_ids, int n_keys,
-                             float *features, int32_t *stats, bool probe, DenseArgs *out, int *sl_out, size_t *lds_out)
+                             float *features, int32_t *stats, bool probe, DenseArgs *out, int *sl_out, size_t *lds_out,
+                             const StepState *state)
 {
     LSM_REQUIRE(h != nullptr, "lsm_step_fused: null reservoir handle");
     LSM_REQUIRE(n_clips >= 1 && n_steps >= 1 && n_steps <= 65535, "bad n_clips/n_steps");
     RunArgs r;
     r.n_clips = n_clips; r.n_steps = n_steps; r.waves_per_clip = -1;
     if (!probe) {
-        LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+        if (state) {
+            // check_run's refusals of a segmented launch and of a continuation, in its order and words
+            if (state->segmented) {
+                LSM_REQUIRE(state->segment_steps >= 1, "segment_steps=%d must be >= 1", state->segment_steps);
+                LSM_REQUIRE(n_steps % state->segment_steps == 0, "n_steps=%d is not a multiple of segment_steps=%d", n_steps,
+                            state->segment_steps);
+                LSM_REQUIRE(state->records != nullptr, "null records_out");
+                LSM_REQUIRE((reinterpret_cast<uintptr_t>(state->records) & 15) == 0, "records_out must be 16-byte aligned");
+                r.segmented = true; r.segment_steps = state->segment_steps; r.records = state->records;
+            }
+            LSM_REQUIRE(state->first_step >= 0, "first_step=%d must be >= 0", state->first_step);
+            LSM_REQUIRE((long)state->first_step + n_steps <= 65535, "first_step + n_steps = %ld exceeds 65535 (the feature "
+                        "records hold spike times in 16 bits)", (long)state->first_step + n_steps);
+            LSM_REQUIRE(state->first_step == 0 || state->state_in != nullptr, "first_step=%d needs state_in (a run from reset "
+                        "starts at 0)", state->first_step);
+            LSM_REQUIRE((reinterpret_cast<uintptr_t>(state->state_in) & 15) == 0 &&
+                        (reinterpret_cast<uintptr_t>(state->state_out) & 15) == 0, "state_in / state_out must be 16-byte aligned");
+            LSM_REQUIRE(n_keys >= 0 && n_keys <= 8 && (n_keys == 0 || key_ids), "n_keys must be in [0, 8]");
+            LSM_REQUIRE(n_keys == 0 || features, "null features_out with n_keys=%d", n_keys);
+            r.from = true; r.state_in = state->state_in; r.state_out = state->state_out; r.first_step = state->first_step;
+        } else {
+            LSM_REQUIRE(n_keys >= 1 && n_keys <= 8 && key_ids, "n_keys must be in [1, 8]");
+        }
         for (int k = 0; k < n_keys; ++k) LSM_REQUIRE(key_ids[k] >= 0 && key_ids[k] < 8, "key id %d out of range", key_ids[k]);
-        LSM_REQUIRE(features != nullptr, "null features_out");
+        LSM_REQUIRE(features != nullptr || state, "null features_out");
         int dev_now = -1;
         LSM_CHECK_HIP(hipGetDevice(&dev_now));
         LSM_REQUIRE(dev_now == h->device, "reservoir handle lives on device %d but the current device is %d", h->device,

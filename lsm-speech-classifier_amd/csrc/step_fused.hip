@@ -22,6 +22,7 @@ namespace {
 #define LSM_FUSED_PARAMS const FusedArgs a, const lsm_lif::DenseArgs d
 #define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
 #define LSM_FUSED_RAGGED constexpr bool RAGGED = false; const lsm_fe::RaggedArgs rg{nullptr, nullptr};
+#define LSM_FUSED_STATE constexpr bool ST = false; const lsm_step::StateRows sx{nullptr};
 #define LSM_FUSED_TAIL_INC "step_fused_tail.inc"
 
 #define LSM_FUSED_KERNEL step_fused_kernel_sl1
@@ -46,6 +47,7 @@ namespace {
 #undef LSM_FUSED_PARAMS
 #undef LSM_FUSED_MASK
 #undef LSM_FUSED_RAGGED
+#undef LSM_FUSED_STATE
 #undef LSM_FUSED_TAIL_INC
 
 typedef void (*step_fn_t)(const FusedArgs, const lsm_lif::DenseArgs);
@@ -82,7 +84,9 @@ constexpr size_t STEP_LDS_MAX = 160 * 1024;
 
 // The three families of the step (include/lsm_hip_step.h): the plain kernels above, the masked ones (step_fused_masked.hip)
 // and the ragged ones (step_fused_ragged.hip).  A batch is ragged or masked, never both, as on the front-end entry points.
-enum StepForm { STEP_PLAIN = 0, STEP_MASKED = 1, STEP_RAGGED = 2 };
+// STEP_STATE (include/lsm_hip_step_state.h, step_fused_state.hip) is no `form` of lsm_step_fused_form_supported: its entry
+// points and its query are their own, its served set is the plain step's.
+enum StepForm { STEP_PLAIN = 0, STEP_MASKED = 1, STEP_RAGGED = 2, STEP_STATE = 3 };
 constexpr int RAGGED_HOP = 160;         // the one hop the ragged front end is offered for (include/lsm_hip_ragged.h)
 
 // What a form asks of the shape beyond the plain step: the ragged step the hop on which a clip of T bins is the front end of
@@ -109,14 +113,16 @@ int step_supported(const char *what, const lsm_reservoir *h, int n_clips, int n_
     return step_lds_bytes((long)time_bins * n_thr, lds) <= STEP_LDS_MAX ? 1 : 0;
 }
 
-// One step launch: the three entry points fill `form` and their own pointers (a member that is not the form's is never read).
-// Refusals: the front end's, the reservoir's, the form's own (the masks' alignment; the ragged counts and strides), then the
-// shapes the launch does not serve.
+// One step launch: the five entry points fill `form` and their own members (a member that is not the form's is never read).
+// Refusals: the front end's, the reservoir's (a state step: lsm_reservoir_run_from's / _run_segments'), the form's own (the
+// masks' alignment; the ragged counts and strides; the segment rows), then the shapes the launch does not serve.
 struct StepOwn {
     int form = STEP_PLAIN;
     const char *what = "lsm_step_fused_f64";
     const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
     const int32_t *clip_bins = nullptr;                             // Ragged (1.14): DEVICE counts, clamped in the kernel
+    lsm_lif::StepState state;                                       // State (4f): continuation and segment records
+    float *segment_rows = nullptr;                                  //   the clip's tumbling feature rows, or null
 };
 
 int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
@@ -125,6 +131,8 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
                 int n_keys, float *features_out, int32_t *stats_out, void *stream)
 {
     const char *const what = own.what;
+    // what the caller of an unserved shape does instead: a state step's alternative may be three launches (the segment fold)
+    const char *const instead = own.form == STEP_STATE ? "make the separate launches" : "make the two launches";
     LSM_REQUIRE(h != nullptr, "%s: null reservoir handle", what);
     LSM_REQUIRE(n_clips >= 0, "bad shape");
     if (n_clips == 0) return LSM_OK;
@@ -137,7 +145,7 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
         const long steps = (long)time_bins * n_thr;
         if (steps > 65535 || step_lds_bytes(steps, 16 * (size_t)steps) > STEP_LDS_MAX) {
             lsm_set_error("%s: shape not served (%d bins x %d thresholds = %ld steps: at most 65535, and an LDS "
-                          "image of at most %zu bytes): make the two launches", what, time_bins, n_thr, steps, STEP_LDS_MAX);
+                          "image of at most %zu bytes): %s", what, time_bins, n_thr, steps, STEP_LDS_MAX, instead);
             return LSM_ERR_UNSUPPORTED;
         }
     }
@@ -151,22 +159,28 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
     lsm_lif::DenseArgs d;
     int sl = 0;
     size_t lif_lds = 0;
-    if (const int rc = lsm_lif::step_dense_args(h, n_clips, T, key_ids, n_keys, features_out, stats_out, false, &d, &sl, &lif_lds))
+    if (const int rc = lsm_lif::step_dense_args(h, n_clips, T, key_ids, n_keys, features_out, stats_out, false, &d, &sl, &lif_lds,
+                                                own.form == STEP_STATE ? &own.state : nullptr))
         return rc;
     // the form's own refusals, behind the two halves'
     if (own.form == STEP_MASKED) {
         if (const int rc = lsm_fe::step_check_masks(own.freq_mask, own.time_mask)) return rc;
     } else if (own.form == STEP_RAGGED) {
         if (const int rc = lsm_fe::step_check_ragged(own.clip_bins, time_bins, n_samples, hop)) return rc;
+    } else if (own.form == STEP_STATE) {
+        LSM_REQUIRE((reinterpret_cast<uintptr_t>(own.segment_rows) & 3) == 0, "segment_rows_out must be 4-byte aligned");
+        LSM_REQUIRE(own.segment_rows == nullptr || n_keys >= 1, "segment_rows_out with n_keys=0: a row needs feature keys");
     }
-    // a masked step without a mask is the plain launch (SPEC.md 1.13: the unmasked bytes)
-    const int form = (own.form == STEP_MASKED && !own.freq_mask && !own.time_mask) ? (int)STEP_PLAIN : own.form;
+    // a masked step without a mask is the plain launch (SPEC.md 1.13: the unmasked bytes), and so is a state step from reset
+    // that saves no state and closes no records (SPEC.md 4f)
+    const bool stateless = own.form == STEP_STATE && !own.state.state_in && !own.state.state_out && !own.state.segmented;
+    const int form = ((own.form == STEP_MASKED && !own.freq_mask && !own.time_mask) || stateless) ? (int)STEP_PLAIN : own.form;
     step_fn_t fn = pick_step(sl, fr.l.shb0);
     if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags) || !fr.l.pair || fr.l.nch != 1 || !fr.l.fast ||
         fr.l.nw != 3 || a.groups != 4 || fr.l.block != 256 || fr.l.grid != (unsigned)n_clips || d.C != n_filters * redundancy ||
         d.CW != 4 || d.T != T || fn == nullptr) {
         lsm_set_error("%s: shape not served (%d filters, redundancy %d, nwin %d, hop %d, coef_flags %d, %d input "
-                      "channels): make the two launches", what, n_filters, redundancy, nwin, hop, coef_flags, d.C);
+                      "channels): %s", what, n_filters, redundancy, nwin, hop, coef_flags, d.C, instead);
         return LSM_ERR_UNSUPPORTED;
     }
     // ragged: a clip of t bins has t - (time_bins - ncols) columns; on hop 160 with the 2 columns a 25 ms window costs, that
@@ -180,8 +194,8 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
     const size_t lds = step_lds_bytes(T, lif_lds);
     LSM_REQUIRE((fr.l.lds & 15) == 0 && fr.l.lds + lif_lds + 128 == lds, "the step's LDS image is not %zu bytes", lds);
     if (lds > STEP_LDS_MAX) {
-        lsm_set_error("%s: shape not served (%d steps: an LDS image of %zu bytes, at most %zu): make the two "
-                      "launches", what, T, lds, STEP_LDS_MAX);
+        lsm_set_error("%s: shape not served (%d steps: an LDS image of %zu bytes, at most %zu): %s", what, T, lds,
+                      STEP_LDS_MAX, instead);
         return LSM_ERR_UNSUPPORTED;
     }
     if (form == STEP_PLAIN) {
@@ -192,7 +206,9 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
         const lsm_step::StepLaunch l{sl, fr.l.shb0, fr.l.grid, fr.l.block, lds};
         const bool ok = form == STEP_MASKED
                             ? lsm_step::launch_step_masked(l, &a, d, lsm_fe::MaskArgs{own.freq_mask, own.time_mask}, stream)
-                            : lsm_step::launch_step_ragged(l, &a, d, lsm_fe::RaggedArgs{own.clip_bins, nullptr}, stream);
+                        : form == STEP_RAGGED
+                            ? lsm_step::launch_step_ragged(l, &a, d, lsm_fe::RaggedArgs{own.clip_bins, nullptr}, stream)
+                            : lsm_step::launch_step_state(l, &a, d, lsm_step::StateRows{own.segment_rows}, stream);
         LSM_REQUIRE(ok, "%s: no kernel for %d slots per lane", what, sl);
     }
     LSM_CHECK_HIP(hipGetLastError());
@@ -248,6 +264,44 @@ LSM_API int lsm_step_fused_ragged_f64(const lsm_reservoir *h, const float *audio
 {
     StepOwn own;
     own.form = STEP_RAGGED; own.what = "lsm_step_fused_ragged_f64"; own.clip_bins = clip_bins;
+    return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                       redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
+}
+
+LSM_API int lsm_step_fused_state_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
+                                           int n_thr, int redundancy, int coef_flags)
+{
+    // the plain step's served set and LDS bound: the ST form adds no byte to the image (its scratch is the idle count array)
+    return step_supported("lsm_step_fused_state_supported", h, n_clips, n_filters, nwin, hop, time_bins, n_thr, redundancy,
+                          coef_flags, STEP_PLAIN);
+}
+
+LSM_API int lsm_step_fused_from_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples, const double *coefs,
+                                    int n_filters, int nwin, int hop, int ncols, int time_bins, const double *thr_on,
+                                    const double *thr_off, int n_thr, int redundancy, void *workspace, long workspace_bytes,
+                                    int coef_flags, int first_step, const void *state_in, void *state_out,
+                                    const int32_t *key_ids, int n_keys, float *features_out, int32_t *stats_out, void *stream)
+{
+    StepOwn own;
+    own.form = STEP_STATE; own.what = "lsm_step_fused_from_f64";
+    own.state.first_step = first_step; own.state.state_in = state_in; own.state.state_out = state_out;
+    return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                       redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
+}
+
+LSM_API int lsm_step_fused_segments_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples,
+                                        const double *coefs, int n_filters, int nwin, int hop, int ncols, int time_bins,
+                                        const double *thr_on, const double *thr_off, int n_thr, int redundancy, void *workspace,
+                                        long workspace_bytes, int coef_flags, int first_step, const void *state_in,
+                                        void *state_out, const int32_t *key_ids, int n_keys, float *features_out,
+                                        int32_t *stats_out, int segment_steps, void *records_out, float *segment_rows_out,
+                                        void *stream)
+{
+    StepOwn own;
+    own.form = STEP_STATE; own.what = "lsm_step_fused_segments_f64";
+    own.state.first_step = first_step; own.state.state_in = state_in; own.state.state_out = state_out;
+    own.state.segmented = true; own.state.segment_steps = segment_steps; own.state.records = records_out;
+    own.segment_rows = segment_rows_out;
     return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
                        redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
 }

@@ -13,4 +13,5 @@
 #define LSM_STEP_FAMILY_LAUNCH launch_step_masked
 #define LSM_FUSED_MASK constexpr bool MASK = true;
 #define LSM_FUSED_RAGGED constexpr bool RAGGED = false; const lsm_fe::RaggedArgs rg{nullptr, nullptr};
+#define LSM_FUSED_STATE constexpr bool ST = false; const lsm_step::StateRows sx{nullptr};
 #include "step_fused_family.inc"

@@ -14,4 +14,5 @@
 #define LSM_STEP_FAMILY_LAUNCH launch_step_ragged
 #define LSM_FUSED_MASK constexpr bool MASK = false; const lsm_fe::MaskArgs m{nullptr, nullptr};
 #define LSM_FUSED_RAGGED constexpr bool RAGGED = true;
+#define LSM_FUSED_STATE constexpr bool ST = false; const lsm_step::StateRows sx{nullptr};
 #include "step_fused_family.inc"

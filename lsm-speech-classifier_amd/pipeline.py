@@ -148,6 +148,93 @@ def step_fused_ragged(fe, net, audio, bins, feature_keys=None, stats_out=None, f
     return feats
 
 
+def step_fused_state_supported(fe, net, n_clips: int) -> bool:
+    """Whether `step_fused_from` and `step_fused_segments` serve batches of `n_clips` clips of this front end and reservoir
+    (`lsm_step_fused_state_supported`): the shapes of the plain `step_fused`."""
+    if getattr(fe, "filterbank", None) != "gammatone" or not fe.will_fuse() or int(n_clips) < 1:
+        return False
+    from . import _lib
+    rc = int(_lib.load().lsm_step_fused_state_supported(net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop, fe.time_bins,
+                                                        len(fe.thresholds), fe.redundancy, fe.coef_flags))
+    if rc < 0:
+        _lib.check(rc, "lsm_step_fused_state_supported")
+    return rc == 1
+
+
+def _front_args(fe, net, audio, B, workspace):
+    """The front-end half of a state step's argument list (up to and including coef_flags); inside the device context."""
+    from .frontend import threshold_tables
+    from .snn import _dev, _host
+    on, off = threshold_tables(fe.thresholds, fe.gap, np.float64)
+    ws, ws_bytes = fe._workspace_for(B, workspace)
+    return (net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
+            _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags), (on, off, ws)
+
+
+def step_fused_from(fe, net, audio, feature_keys=None, state=None, state_out=None, stats_out=None, features_out=None,
+                    workspace=None):
+    """One step that continues a run, in ONE launch on the current stream (`lsm_step_fused_from_f64`, SPEC.md §4f): bit for
+    bit ``net.run_batch(fe.encode(audio), feature_keys, state=state, state_out=state_out)[0]`` -- the feature rows of the whole
+    run so far, `stats_out` its totals, the state advanced by ``fe.n_steps`` steps in place (or written to `state_out`) -- and
+    no raster is written.  Without `state` it is `step_fused`.  The other parameters are `step_fused`'s; masks and ragged
+    batches are not offered.  Needs `step_fused_state_supported(fe, net, B)`."""
+    from . import _lib
+    from .snn import _dev, _host
+    n = 1 if getattr(audio, "ndim", 2) == 1 else len(audio)
+    first_step, src, dst = net._continuation(state, state_out, n)        # before any device work
+    audio, B, keys, key_ids, shape = _step_outputs(fe, net, audio, feature_keys, stats_out, features_out)
+    with torch.cuda.device(fe.device):
+        feats = features_out if features_out is not None else torch.empty(shape, dtype=torch.float32, device=fe.device)
+        front, keep = _front_args(fe, net, audio, B, workspace)
+        _lib.check(fe.lib.lsm_step_fused_from_f64(*front, int(first_step), _dev(src), _dev(dst), _host(key_ids), len(keys),
+                                                  _dev(feats), _dev(stats_out), fe._stream()), "lsm_step_fused_from_f64")
+    if state is not None:
+        (state_out or state).steps_done = state.steps_done + fe.n_steps
+    return feats
+
+
+def step_fused_segments(fe, net, audio, segment_steps: int, feature_keys=None, state=None, state_out=None,
+                        want_records: bool = False, stats_out=None, rows_out=None, workspace=None):
+    """One step with its features per time segment, in ONE launch on the current stream (`lsm_step_fused_segments_f64`,
+    SPEC.md §4f).  Returns the rows float32 (B, G, n_keys * N_out), G = ``fe.n_steps // segment_steps``, bit for bit
+    ``net.run_segments(fe.encode(audio), segment_steps, feature_keys, state=state, state_out=state_out)``: the workgroup of a
+    clip closes its segment records and writes the clip's rows itself; with `want_records` also the (B, G, N_out, 4) int32
+    records of ``net.run_segment_records``.  `rows_out`: a contiguous float32 (B, G, n_keys * N_out) tensor to write into.
+    `state` / `state_out` / `stats_out` / `workspace`: as `step_fused_from`'s.  Needs `step_fused_state_supported`."""
+    from . import _lib
+    from .snn import _check_stats_out, _dev, _host, _select_keys
+    S, T = int(segment_steps), int(fe.n_steps)
+    if S < 1 or T < 1 or T % S != 0:
+        raise _lib.LsmHipError(f"segment_steps = {S} must be >= 1 and divide the clip's {T} steps")
+    n = 1 if getattr(audio, "ndim", 2) == 1 else len(audio)
+    first_step, src, dst = net._continuation(state, state_out, n)        # before any device work
+    audio = fe._audio(audio)
+    B, G = int(audio.shape[0]), T // S
+    keys, key_ids = _select_keys(feature_keys)
+    shape = (B, G, len(keys) * net.num_output_neurons)
+    if rows_out is not None:
+        if (rows_out.dtype != torch.float32 or tuple(rows_out.shape) != shape or not rows_out.is_contiguous()
+                or rows_out.device != audio.device):
+            raise ValueError(f"rows_out must be a contiguous float32 {shape} tensor on {audio.device}")
+    _check_stats_out(stats_out, B, audio.device)
+    with torch.cuda.device(fe.device):
+        rows = rows_out if rows_out is not None else torch.empty(shape, dtype=torch.float32, device=fe.device)
+        # the records are the kernel's own working set (it folds and reads them back): always a buffer, returned when asked for
+        records = torch.empty((B, G, net.num_output_neurons, 4), dtype=torch.int32, device=fe.device)
+        front, keep = _front_args(fe, net, audio, B, workspace)
+        # (cumulative features are not asked for: features_out NULL is the library's "no cumulative rows" only with n_keys 0,
+        #  so the keys go with a scratch row buffer of their own); without keys (`feature_keys=()`: the records alone) the
+        #  launch has neither cumulative rows nor segment rows
+        cumulative = torch.empty((B, shape[2]), dtype=torch.float32, device=fe.device) if keys else None
+        _lib.check(fe.lib.lsm_step_fused_segments_f64(*front, int(first_step), _dev(src), _dev(dst),
+                                                      _host(key_ids) if keys else None, len(keys), _dev(cumulative),
+                                                      _dev(stats_out), S, _dev(records), _dev(rows) if keys else None,
+                                                      fe._stream()), "lsm_step_fused_segments_f64")
+    if state is not None:
+        (state_out or state).steps_done = state.steps_done + T
+    return (rows, records) if want_records else rows
+
+
 def configure_hardware_queues(n: int = DEFAULT_HW_QUEUES) -> int:
     """The HIP runtime multiplexes streams onto 4 hardware queues by default, and kernels of streams that
     share a queue serialise: with 4 queues three streams are the optimum, with 8-12 six streams overlap
@@ -221,7 +308,10 @@ class HotPath:
     accepts, is one launch (`_submit_fused`); `time_reservoir`'s event pair then brackets that launch, front end included.
     `fused_forms` = True: there a masked step is one launch too (`lsm_step_fused_masked_f64`), and a step with speed, reverb or
     mixer runs its augmentation launches on the fused rotation stream and then the one launch; the rows are byte for byte
-    those of the default routes.  Off by default (profiles/step_fused_forms.txt)."""
+    those of the default routes.  Off by default (profiles/step_fused_forms.txt).  With `time_segments` = K > 1 and
+    `fused_forms` = True a full step without mixer, reverb, speed or mask, of a shape `step_fused_state_supported` accepts, is
+    one launch as well (`step_fused_segments`: the kernel writes the step's K rows itself) instead of front end, segmented
+    reservoir launch and fold (profiles/step_fused_state.txt)."""
 
     def __init__(self, fe, net, feature_keys=None, streams: int = DEFAULT_STREAMS,
                  waves_per_clip: int | None = None, time_reservoir: bool = False,
@@ -278,6 +368,10 @@ class HotPath:
         self.fused_forms = bool(fused_forms)
         self.fused_step = (self.n_streams > 1 and self.hw_queues <= FUSED_STEP_MAX_HW_QUEUES and self.time_segments == 1
                            and (self.fused_forms or (mixer is None and reverb is None and speed is None)))
+        # `fused_forms` with time segments: the step's K rows from one launch (`_submit_fused_segments`); `fused_step` stays
+        # what it says about the whole-clip step
+        self.fused_segments = (self.n_streams > 1 and self.hw_queues <= FUSED_STEP_MAX_HW_QUEUES and self.time_segments > 1
+                               and self.fused_forms and mixer is None and reverb is None and speed is None)
         self.n_fused_streams = max(1, min(self.hw_queues - 1, self.n_streams))
         self._fused_ok = {}                 # (batch size, form) -> step_fused_supported
         # what a slot owns beside its raster ring (`_owned`): ("h2d" / "speed" / "reverb" / "mix", slot, batch shape) -> the
@@ -372,6 +466,8 @@ class HotPath:
             topology = self._submit_serial
         elif step.stage == "full" and (not masked or self.fused_forms) and self._takes_fused_step(step.audio, masked):
             topology = self._submit_fused
+        elif step.stage == "full" and not masked and self._takes_fused_segments(step.audio):
+            topology = self._submit_fused_segments
         elif self.n_fe_streams and step.stage != "reservoir":
             topology = self._submit_two_stages
         else:
@@ -455,6 +551,26 @@ class HotPath:
             with self._timed():
                 return step_fused(self.fe, self.net, x, self.feature_keys, stats_out=step.stats_out, features_out=step.out,
                                   workspace=ws, **step.plans.mask_keyword()), st
+
+    def _takes_fused_segments(self, audio) -> bool:
+        """Whether a full step over `audio` is the one-launch segmented step (decided once per batch size)."""
+        return self.fused_segments and _get_or_make(self._fused_ok, (int(len(audio)), "segments"),
+                                                    lambda: step_fused_state_supported(self.fe, self.net, int(len(audio))))
+
+    def _submit_fused_segments(self, slot, step):
+        """The whole step with its `time_segments` rows as one launch (`step_fused_segments`), on the fused rotation."""
+        slot = (self._step - 1) % self.n_fused_streams
+        st, cur = self.streams[slot], torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            self._wait_for_input(st, cur, step.audio, step.after)
+            x = self._input(step, slot)
+            B, K = int(x.shape[0]), self.time_segments
+            ws = _get_or_make(self._buffers, ("workspace", slot, B), lambda: self.fe.new_workspace(B))
+            with self._timed():
+                return step_fused_segments(self.fe, self.net, x, self.fe.n_steps // K, self.feature_keys,
+                                           stats_out=step.stats_out,
+                                           rows_out=step.out.view(B, K, -1) if step.out is not None else None,
+                                           workspace=ws).view(B, -1), st
 
     def _low_latency(self, tail: bool) -> bool:
         """Whether this step's fused gammatone front end goes out in the low-latency layout: on a tail step, and when it
@@ -652,15 +768,28 @@ def _scatter_recording_windows(arrays, windows, fe, net):
     return rasters
 
 
-def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = True):
+def _audio_window(x, w: int, fe):
+    """Window w of every recording of the device audio (n, W * n_samples) as a contiguous (n, n_samples) batch."""
+    ns = int(fe.n_samples)
+    return x[:, w * ns:(w + 1) * ns].contiguous()
+
+
+def features_from_long_audio(audio, fe, net, feature_keys, carry_state: bool = True, fused: bool = False):
     """A recording taken window by window: ``audio`` (n, W * fe.n_samples) float32 -> (n, W, n_feat) float32 device
     tensor.  The front end runs on the n * W windows as independent clips (its normalisation is per clip, as the
     reference's); the reservoir then takes window after window and, with ``carry_state``, keeps its membrane, refractory
     and spike state between them (``SNN.run_batch(state=...)``): row w holds the features of steps [0, (w + 1) * T) of
     the recording, what one run over the concatenated rasters gives.  ``carry_state=False``: every window from
-    ``reset()``, W independent ``run_batch`` calls."""
+    ``reset()``, W independent ``run_batch`` calls.  ``fused`` = True: where `step_fused_state_supported` serves the shape,
+    window w is ONE launch over its audio (`step_fused_from`) with the state carried -- W launches, no raster tensor, the same
+    rows; another shape takes the route above.  Off by default (profiles/step_fused_state.txt)."""
     audio, n, W = _audio_windows(audio, fe)
     with torch.cuda.device(net.device):
+        if fused and step_fused_state_supported(fe, net, n):
+            x = audio.to(net.device)
+            state = net.new_state(n) if carry_state else None
+            return torch.stack([step_fused_from(fe, net, _audio_window(x, w, fe), feature_keys, state=state)
+                                for w in range(W)], dim=1)
         rasters = _encode_audio_windows(audio, n, W, fe, net)
         state = net.new_state(n) if carry_state else None
         rows = [net.run_batch(rasters[:, w].contiguous(), feature_keys, state=state)[0] for w in range(W)]
@@ -730,20 +859,28 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
 
 
 def sliding_features_from_long_audio(audio, fe, net, feature_keys, segment_steps: int, window_segments: int,
-                                     hop_segments: int = 1):
+                                     hop_segments: int = 1, fused: bool = False):
     """Features of sliding windows over a recording: ``audio`` (n, W * fe.n_samples) float32 -> (n, Wn, n_feat) float32
     device tensor.  The front end runs on the n * W audio windows as independent clips, as in
     ``features_from_long_audio``; the reservoir takes them one after the other with its state carried, one segmented
     launch per audio window (``segment_steps`` divides ``fe.n_steps``), and the records of all launches, concatenated, go
     through one ``lsm_segment_features`` call: row w is the feature row of steps
     ``[w * hop_segments * segment_steps, (w * hop_segments + window_segments) * segment_steps)`` of the recording's one
-    uncut run -- windows may straddle the audio windows."""
+    uncut run -- windows may straddle the audio windows.  ``fused`` = True: where `step_fused_state_supported` serves the
+    shape, audio window w is ONE launch (`step_fused_segments`) with the state carried and no raster tensor; the records are
+    concatenated and folded once, as above.  Off by default (profiles/step_fused_state.txt)."""
     audio, n, W = _audio_windows(audio, fe)
     S = int(segment_steps)
     if S < 1 or fe.n_steps % S:
         raise ValueError(f"segment_steps = {segment_steps} must be >= 1 and divide the front end's {fe.n_steps} steps")
     net.segment_windows(W * (fe.n_steps // S), window_segments, hop_segments)     # refuse before anything is launched
     with torch.cuda.device(net.device):
+        if fused and step_fused_state_supported(fe, net, n):
+            x = audio.to(net.device)
+            state = net.new_state(n)
+            records = torch.cat([step_fused_segments(fe, net, _audio_window(x, w, fe), S, (), state=state, want_records=True)[1]
+                                 for w in range(W)], dim=1)
+            return net.segment_features(records, S, feature_keys, window_segments, hop_segments)
         rasters = _encode_audio_windows(audio, n, W, fe, net)
         state = net.new_state(n)
         records = torch.cat([net.run_segment_records(rasters[:, w].contiguous(), S, state=state)[0] for w in range(W)],
