@@ -351,12 +351,14 @@ def _synthetic_utterances(commands, per_class: int, max_bins: int):
 
 def create_variable_length_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
-                                   output_file: str = OUTPUT_FILE, max_seconds: float = DURATION):
+                                   output_file: str = OUTPUT_FILE, max_seconds: float = DURATION, trim=None):
     """File 1 with every clip at its own length (`--variable-length`, SPEC.md 1.14): the wav files are not padded to one
     second, only trimmed at ``max_seconds``, and go through the ragged front end (`SpikeFrontEnd.encode_ragged`) in batches,
     longest first.  ``X_spikes`` keeps its schema at the stride ``100 * max_seconds * n_thr`` steps -- clip r's rows hold its
     ``n_steps[r]`` steps and zeros behind them -- and the file gains the key ``n_steps`` (n,) int32, which
-    extract_lsm_features.py hands to the reservoir as the clips' lengths.  One process, no augmentation chain."""
+    extract_lsm_features.py hands to the reservoir as the clips' lengths.  One process, no augmentation chain.  ``trim``
+    (`trim_from_args`): every clip is first cut to its speech on the GPU (`frontend.SilenceTrimmer`, SPEC.md 1.15), so the
+    rows hold the trimmed clips and ``n_steps`` their lengths."""
     from lsm_speech_classifier_amd import spikefile
     commands = list(COMMANDS if commands is None else commands)
     root = Path(DATASET_ROOT if dataset_root is None else dataset_root)
@@ -379,6 +381,18 @@ def create_variable_length_dataset(n_filters: int, filterbank: str, commands=Non
                           gap=HYSTERESIS_GAP, time_bins=max_bins, n_samples=max_bins * fr.RAGGED_HOP)
     audio, bins = fr.pack_utterances(clips, max_bins)
     X = np.zeros((len(clips), fe.n_channels, fe.n_steps), dtype=np.uint8)
+    if trim:
+        import torch
+        trimmer = fr.SilenceTrimmer(device=fe.device, **trim)
+        rows = torch.empty((len(clips), fe.n_samples), dtype=torch.float32, device=fe.device)
+        kept = torch.empty((len(clips),), dtype=torch.int32, device=fe.device)
+        for a in range(0, len(clips), ENCODE_BATCH):
+            _, part, _ = trimmer.trim(audio[a:a + ENCODE_BATCH], bins[a:a + ENCODE_BATCH].astype(np.int64) * fr.RAGGED_HOP,
+                                      time_bins=max_bins, out=rows[a:a + ENCODE_BATCH])
+            kept[a:a + ENCODE_BATCH] = part
+        audio, bins = rows, kept.cpu().numpy()          # the one read-back: the order below and n_steps need host values
+        print(f"  Trimmed at {trim['top_db']:g} dB: {int(bins.min())} / {float(bins.mean()):.1f} / {int(bins.max())} time bins "
+              f"(min / mean / max)")
     order = np.argsort(-bins.astype(np.int64), kind="stable")
     for a in range(0, len(order), ENCODE_BATCH):
         idx = order[a:a + ENCODE_BATCH]
@@ -633,6 +647,34 @@ def add_variable_length_flags(ap):
                          "gains the key n_steps.")
     ap.add_argument("--max-seconds", type=float, default=DURATION,
                     help=f"With --variable-length: trim clips at this many seconds (default {DURATION:g}); sets the row stride.")
+    ap.add_argument("--trim-silence", type=float, default=None, metavar="DB",
+                    help="With --variable-length: cut every clip on the GPU to the 10 ms bins within DB decibels of its loudest "
+                         "one; File 1's n_steps are the trimmed lengths.")
+    ap.add_argument("--trim-pad-ms", type=float, default=DEFAULT_TRIM_PAD_MS,
+                    help=f"With --trim-silence: keep this much around the speech, in whole bins (default {DEFAULT_TRIM_PAD_MS:g}).")
+    ap.add_argument("--trim-min-ms", type=float, default=DEFAULT_TRIM_MIN_MS,
+                    help=f"With --trim-silence: the shortest a trimmed clip gets, in whole bins (default {DEFAULT_TRIM_MIN_MS:g}).")
+
+
+DEFAULT_TRIM_PAD_MS = 30.0
+DEFAULT_TRIM_MIN_MS = 30.0       # three time bins: the shortest clip the ragged front end takes
+
+
+def trim_from_args(a):
+    """None without --trim-silence, else what create_variable_length_dataset(trim=...) takes: top_db, pad_bins, min_bins."""
+    if getattr(a, "trim_silence", None) is None:
+        return None
+    if not a.variable_length:
+        raise SystemExit("--trim-silence needs --variable-length: a trimmed clip has a length of its own")
+    if not (np.isfinite(a.trim_silence) and a.trim_silence > 0):
+        raise SystemExit("--trim-silence must be a number of dB above 0")
+    if not a.trim_pad_ms >= 0:
+        raise SystemExit("--trim-pad-ms must be >= 0")
+    ms_per_bin = 1000.0 / BINS_PER_SECOND
+    min_bins = int(round(a.trim_min_ms / ms_per_bin))
+    if not 3 <= min_bins <= max_bins_of(a.max_seconds):
+        raise SystemExit(f"--trim-min-ms {a.trim_min_ms:g}: a trimmed clip has 3 to {max_bins_of(a.max_seconds)} time bins of 10 ms")
+    return dict(top_db=float(a.trim_silence), pad_bins=int(round(a.trim_pad_ms / ms_per_bin)), min_bins=min_bins)
 
 
 def check_variable_length_args(a):
@@ -674,11 +716,12 @@ if __name__ == "__main__":
     add_mask_flags(ap)
     add_variable_length_flags(ap)
     a = ap.parse_args()
+    trim = trim_from_args(a)
     if a.variable_length:
         check_variable_length_args(a)
         create_variable_length_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                                        dataset_root=a.dataset_root, max_per_class=a.max_per_class,
-                                       synthetic_per_class=a.synthetic_per_class, max_seconds=a.max_seconds)
+                                       synthetic_per_class=a.synthetic_per_class, max_seconds=a.max_seconds, trim=trim)
         raise SystemExit(0)
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,

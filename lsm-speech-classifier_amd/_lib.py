@@ -207,6 +207,14 @@ STEP_STATE_SIGS["lsm_step_fused_segments_f64"] = (c_int, STEP_STATE_SIGS["lsm_st
                                                   + [c_int, c_void, c_void, c_void])
 STEP_STATE_SYMBOLS = tuple(STEP_STATE_SIGS)
 
+# include/lsm_hip_trim.h (SPEC.md §1.15): silence trimming in front of the ragged front end
+TRIM_SIGS = {
+    "lsm_trim_lds_bytes": (c_int, [c_int]),
+    "lsm_trim_silence_f32": (c_int, [c_void, c_int, c_int, c_int, c_void, c_double, c_int, c_int, c_void, c_int, c_void,
+                                     c_void, c_void, c_void]),
+}
+TRIM_SYMBOLS = tuple(TRIM_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -258,7 +266,7 @@ def load():
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
                               + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
-                              + list(STEP_STATE_SIGS.items())):
+                              + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

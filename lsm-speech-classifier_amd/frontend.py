@@ -1698,6 +1698,98 @@ class SpeedPerturber:
         return out
 
 
+# ---- silence trimming in front of the ragged front end (SPEC.md §1.15, include/lsm_hip_trim.h) ---------------------------
+TRIM_MAX_BINS = 4096        # time_bins of a trim launch: 3 .. 4096
+
+
+def trim_ratio(top_db) -> float:
+    """The activity threshold of `lsm_trim_silence_f32` as a share of a clip's loudest bin: ``10 ** (-top_db / 10)`` for a
+    bin ``top_db`` dB (> 0, finite) under the loudest, 0.0 for None: only bins of exact zeros count as silence."""
+    if top_db is None:
+        return 0.0
+    top_db = float(top_db)
+    if not (np.isfinite(top_db) and top_db > 0.0):
+        raise ValueError(f"top_db must be a finite number of dB above 0, or None, got {top_db!r}")
+    return 10.0 ** (-top_db / 10.0)
+
+
+class SilenceTrimmer:
+    """Clips cut to their speech on the device (`lsm_trim_silence_f32`, SPEC.md §1.15): per clip the energies of its
+    160-sample bins, the span of the bins louder than ``ratio`` times the loudest, ``pad_bins`` bins kept on either side
+    and at least ``min_bins`` (>= 3) bins in all; the span's samples move to the start of the clip's row.  ``top_db``: the
+    threshold in dB under the loudest bin (`trim_ratio`); None trims digital silence only."""
+
+    def __init__(self, top_db=30.0, pad_bins: int = 3, min_bins: int = 3, device=None):
+        self.top_db = top_db
+        self.ratio = trim_ratio(top_db)
+        self.pad_bins, self.min_bins = int(pad_bins), int(min_bins)
+        if self.pad_bins < 0:
+            raise ValueError(f"pad_bins must be >= 0, got {pad_bins}")
+        if not RAGGED_MIN_BINS <= self.min_bins <= TRIM_MAX_BINS:
+            raise ValueError(f"min_bins must lie in [{RAGGED_MIN_BINS}, {TRIM_MAX_BINS}], got {min_bins}")
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+
+    def _lengths(self, lengths, n: int, n_samples: int):
+        """``lengths`` as the int32 device tensor the kernel reads, or None: host integers checked against the row, a device
+        tensor taken as it is -- never read back, the kernel clamps it."""
+        if lengths is None:
+            return None
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
+                raise ValueError(f"lengths must hold {n} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
+            return lengths.to(self.device).contiguous()
+        arr = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+        if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"lengths must be {n} integers, got {arr.dtype} {arr.shape}")
+        bad = np.nonzero((arr < 0) | (arr > n_samples))[0]
+        if len(bad):
+            raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {n_samples}]")
+        return torch.from_numpy(arr.astype(np.int32)).to(self.device, non_blocking=True)
+
+    def trim(self, audio, lengths=None, time_bins: int | None = None, out: torch.Tensor | None = None,
+             want_energy: bool = False):
+        """``audio`` (n, L) float32, NumPy or tensor -> ``(audio_out, bins, first[, energy])``, device tensors produced on
+        the current stream with no host synchronisation.  ``lengths``: the clips' valid samples, n host integers in
+        [0, L] (checked) or an int32 device tensor (not read: the kernel clamps it); None: L everywhere.  ``time_bins``
+        (3 .. 4096): the bins of a row, ceil(L / 160) by default.  ``audio_out`` float32 (n, 160 * time_bins) -- or ``out``,
+        a caller-owned contiguous float32 (n, >= 160 * time_bins) tensor on the device, never ``audio`` -- holds clip b's
+        span at the start of row b and +0.0 behind; ``bins`` and ``first`` int32 (n,): the span's bins, which
+        `SpikeFrontEnd.encode_ragged`, `pipeline.step_fused_ragged` and `SNN.run_batch(lengths=...)` take unread, and its
+        first bin in the clip; ``energy`` float64 (n, time_bins): the bin energies, +0.0 behind a clip's last bin."""
+        audio = as_float32(audio)
+        if audio.ndim != 2 or audio.shape[1] < 1:
+            raise ValueError(f"audio must be (n, L >= 1), got {tuple(audio.shape)}")
+        n, L = (int(v) for v in audio.shape)
+        time_bins = -(-L // RAGGED_HOP) if time_bins is None else int(time_bins)
+        if not RAGGED_MIN_BINS <= time_bins <= TRIM_MAX_BINS:
+            raise ValueError(f"time_bins = {time_bins} outside [{RAGGED_MIN_BINS}, {TRIM_MAX_BINS}]")
+        if self.min_bins > time_bins:
+            raise ValueError(f"min_bins = {self.min_bins} exceeds the row's {time_bins} time bins")
+        if out is not None:
+            if not torch.is_tensor(out) or out.dtype != torch.float32 or out.ndim != 2 or out.shape[0] != n \
+                    or out.shape[1] < RAGGED_HOP * time_bins or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"out must be a contiguous float32 ({n}, >= {RAGGED_HOP * time_bins}) tensor on {self.device}")
+            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
+                raise ValueError("out must not be audio: a clip moves towards the start of its row")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device).contiguous()
+            counts = self._lengths(lengths, n, L)
+            if out is None:
+                out = torch.empty((n, RAGGED_HOP * time_bins), dtype=torch.float32, device=self.device)
+            bins = torch.empty((n,), dtype=torch.int32, device=self.device)
+            first = torch.empty((n,), dtype=torch.int32, device=self.device)
+            energy = torch.empty((n, time_bins), dtype=torch.float64, device=self.device) if want_energy else None
+            if n:
+                _lib.check(self.lib.lsm_trim_silence_f32(
+                    _dev(audio), n, L, time_bins, _dev(counts) if counts is not None else None, C.c_double(self.ratio),
+                    self.pad_bins, self.min_bins, _dev(out), int(out.shape[1]), _dev(first), _dev(bins),
+                    _dev(energy) if want_energy else None, torch.cuda.current_stream(self.device).cuda_stream),
+                    "lsm_trim_silence_f32")
+        return (out, bins, first, energy) if want_energy else (out, bins, first)
+
+
 # ---- SpecAugment-style masks inside the spike encoders (SPEC.md §1.13, include/lsm_hip_mask.h) ---------------------------
 
 def mask_words(starts, widths, n_bits: int) -> np.ndarray:

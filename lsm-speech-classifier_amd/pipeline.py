@@ -819,7 +819,22 @@ def features_from_recordings(recordings, fe, net, feature_keys):
         return feats
 
 
-def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024, fused: bool = False):
+def _trimmed_listing(trim, audio: np.ndarray, bins: np.ndarray, fe, device, batch: int):
+    """A packed listing (`frontend.pack_utterances`) through ``trim`` in batches of ``batch`` rows: -> ``(the trimmed rows, a
+    float32 (n, 160 * time_bins) DEVICE tensor, their bins as host int32)``.  Launches only, then one read-back of the bins."""
+    from .frontend import RAGGED_HOP
+    n = len(bins)
+    rows = torch.empty((n, RAGGED_HOP * fe.time_bins), dtype=torch.float32, device=device)
+    kept = torch.empty((n,), dtype=torch.int32, device=device)
+    for lo in range(0, n, batch):
+        hi = min(n, lo + batch)
+        _, part, _ = trim.trim(torch.from_numpy(audio[lo:hi]).to(device), bins[lo:hi].astype(np.int64) * RAGGED_HOP,
+                               time_bins=fe.time_bins, out=rows[lo:hi])
+        kept[lo:hi] = part
+    return rows, kept.cpu().numpy()
+
+
+def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024, fused: bool = False, trim=None):
     """Utterances of different lengths, each one clip: ``utterances``, a list of n 1-D float32 arrays of 321 to
     ``fe.n_samples`` samples, -> (n, n_feat) float32 device tensor in the input order.  Row r holds the features of utterance
     r taken alone: its own ``ceil(len / 160)`` time bins through the front end of that length (its normalisation range is the
@@ -830,7 +845,11 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     ``fe.n_steps`` exceeds the longest launch the reservoir's plan accepts, the reservoir runs in chunks
     (``SNN.run_chunked(lengths=...)``, host lengths).  ``fused`` = True: a batch whose shape the ragged one-launch step
     serves (`step_fused_supported(..., form="ragged")`) is that one launch (`step_fused_ragged`) -- no raster, no step counts
-    in memory, the same rows; every other batch takes the two launches.  Off by default (profiles/step_fused_forms.txt)."""
+    in memory, the same rows; every other batch takes the two launches.  Off by default (profiles/step_fused_forms.txt).
+    ``trim`` (a `frontend.SilenceTrimmer`): every utterance is first cut to its speech on the device (SPEC.md §1.15) and row r
+    holds the features of that slice taken alone.  The packed listing is uploaded and trimmed in batches of ``batch``,
+    launches only; the trimmed bin counts are then read back ONCE, for the longest-first order and the host lengths the
+    batches take, and the batches run as above on the trimmed rows, gathered on the device.  None: nothing changes."""
     from .frontend import pack_utterances
     from .snn import _select_keys
     audio, bins = pack_utterances(utterances, fe.time_bins)
@@ -838,12 +857,14 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     keys, _ = _select_keys(feature_keys)
     batch = max(1, int(batch))
     with torch.cuda.device(net.device):
+        if trim is not None:
+            audio, bins = _trimmed_listing(trim, audio, bins, fe, net.device, batch)
         feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
         order = np.argsort(-bins.astype(np.int64), kind="stable")
         n_thr = len(fe.thresholds)
         for lo in range(0, n, batch):
             idx = order[lo:lo + batch]
-            x = torch.from_numpy(audio[idx]).to(net.device)
+            x = audio[torch.from_numpy(idx).to(net.device)] if torch.is_tensor(audio) else torch.from_numpy(audio[idx]).to(net.device)
             if fused and step_fused_supported(fe, net, len(idx), "ragged"):
                 rows = torch.zeros((len(idx), feats.shape[1]), dtype=torch.float32, device=net.device)
                 step_fused_ragged(fe, net, x, bins[idx], feature_keys, features_out=rows)

@@ -20,10 +20,11 @@ def white_noise(n_clips: int, seed: int = 1234, n_samples: int = CLIP_SAMPLES) -
     return (rng.standard_normal((n_clips, n_samples)) * 0.1).astype(np.float32)
 
 
-def class_chirps(labels, seed: int = 1234, n_samples: int = CLIP_SAMPLES) -> np.ndarray:
+def class_chirps(labels, seed: int = 1234, n_samples: int = CLIP_SAMPLES, noise: float = 0.04) -> np.ndarray:
     """One speech-like clip per entry of ``labels``: a harmonic source (pitch glide) shaped by
     three formant resonances whose start/end frequencies, onset and duration are fixed by the
-    class; the clip index jitters them a little and adds 0.04-sigma background noise."""
+    class; the clip index jitters them a little and adds ``noise``-sigma background noise (0.04: about 10 dB under the
+    loudest 10 ms bin; 0.001 gives the quiet surroundings a silence trimmer can cut, SPEC.md §1.15)."""
     labels = np.asarray(labels, dtype=np.int64)
     t = np.arange(n_samples) / SAMPLE_RATE
     out = np.empty((len(labels), n_samples), dtype=np.float32)
@@ -50,7 +51,7 @@ def class_chirps(labels, seed: int = 1234, n_samples: int = CLIP_SAMPLES) -> np.
         gain *= hf < 0.45 * SAMPLE_RATE
         x = (gain * np.sin(harm * phase[None, :])).sum(axis=0) * env
         x *= 0.5 / max(1e-9, np.abs(x).max())
-        x += 0.04 * srng.standard_normal(n_samples)
+        x += noise * srng.standard_normal(n_samples)
         out[n] = x.astype(np.float32)
     return out
 

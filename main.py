@@ -68,8 +68,13 @@ def _mask_args(a):
 
 
 def _variable_length_args(a):
-    """Nothing without --variable-length."""
-    return ["--variable-length", "--max-seconds", str(a.max_seconds)] if a.variable_length else []
+    """Nothing without --variable-length; the trim flags go along with --trim-silence."""
+    if not a.variable_length:
+        return []
+    out = ["--variable-length", "--max-seconds", str(a.max_seconds)]
+    if a.trim_silence is not None:
+        out += ["--trim-silence", str(a.trim_silence), "--trim-pad-ms", str(a.trim_pad_ms), "--trim-min-ms", str(a.trim_min_ms)]
+    return out
 
 
 def _reservoir_args(a):
@@ -136,7 +141,8 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     noise_dir, snr_db, time_shift_ms, level_db, augment_seed, the reverberation flags rir_dir, rir_prob, rir_max_ms and the
     speed flags speed_factors, speed_prob and the mask flags freq_masks, freq_mask_width, time_masks, time_mask_width,
     mask_prob: applied to stage 1 and to the in-memory route; variable_length, max_seconds: stage 1 keeps every clip at its
-    own length, SPEC.md 1.14, and stage 2 finds the lengths in File 1)."""
+    own length, SPEC.md 1.14, and stage 2 finds the lengths in File 1; trim_silence, trim_pad_ms, trim_min_ms: stage 1 first
+    cuts every such clip to its speech on the GPU, SPEC.md 1.15)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
@@ -144,11 +150,14 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
                               readout=None, nproc=1, time_segments=1, noise_dir=None, snr_db=None, time_shift_ms=0.0,
                               level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0,
                               speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
-                              time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0)
+                              time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0,
+                              trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
     vars(args).update(extra)
+    if args.trim_silence is not None and not args.variable_length:
+        raise SystemExit("--trim-silence needs --variable-length: a trimmed clip has a length of its own")
     if args.variable_length and (in_memory or args.nproc > 1):
         raise SystemExit("--variable-length goes through File 1 in one process: it combines with neither --in-memory nor --nproc")
     print("--- Running Pipeline ---")
@@ -233,6 +242,10 @@ if __name__ == "__main__":
                     help="Keep every clip at its own length instead of padding it to one second (stage 1; stage 2 reads the "
                          "lengths from File 1).")
     ap.add_argument("--max-seconds", type=float, default=1.0, help="With --variable-length: trim clips at this length (stage 1).")
+    ap.add_argument("--trim-silence", type=float, default=None, metavar="DB",
+                    help="With --variable-length: cut every clip on the GPU to the bins within DB decibels of its loudest (stage 1).")
+    ap.add_argument("--trim-pad-ms", type=float, default=30.0, help="With --trim-silence: kept around the speech (stage 1).")
+    ap.add_argument("--trim-min-ms", type=float, default=30.0, help="With --trim-silence: shortest trimmed clip (stage 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
@@ -244,4 +257,5 @@ if __name__ == "__main__":
                  rir_dir=a.rir_dir, rir_prob=a.rir_prob, rir_max_ms=a.rir_max_ms, speed_factors=a.speed_factors,
                  speed_prob=a.speed_prob, freq_masks=a.freq_masks, freq_mask_width=a.freq_mask_width,
                  time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob,
-                 variable_length=a.variable_length, max_seconds=a.max_seconds)
+                 variable_length=a.variable_length, max_seconds=a.max_seconds, trim_silence=a.trim_silence,
+                 trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms)
