@@ -351,14 +351,18 @@ def _synthetic_utterances(commands, per_class: int, max_bins: int):
 
 def create_variable_length_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
-                                   output_file: str = OUTPUT_FILE, max_seconds: float = DURATION, trim=None):
+                                   output_file: str = OUTPUT_FILE, max_seconds: float = DURATION, trim=None, augment=None,
+                                   reverb=None, mask=None):
     """File 1 with every clip at its own length (`--variable-length`, SPEC.md 1.14): the wav files are not padded to one
     second, only trimmed at ``max_seconds``, and go through the ragged front end (`SpikeFrontEnd.encode_ragged`) in batches,
     longest first.  ``X_spikes`` keeps its schema at the stride ``100 * max_seconds * n_thr`` steps -- clip r's rows hold its
     ``n_steps[r]`` steps and zeros behind them -- and the file gains the key ``n_steps`` (n,) int32, which
-    extract_lsm_features.py hands to the reservoir as the clips' lengths.  One process, no augmentation chain.  ``trim``
+    extract_lsm_features.py hands to the reservoir as the clips' lengths.  One process.  ``trim``
     (`trim_from_args`): every clip is first cut to its speech on the GPU (`frontend.SilenceTrimmer`, SPEC.md 1.15), so the
-    rows hold the trimmed clips and ``n_steps`` their lengths."""
+    rows hold the trimmed clips and ``n_steps`` their lengths.  ``reverb`` (`reverb_from_args`), ``augment``
+    (`augment_from_args`) and ``mask`` (`mask_from_args`): behind the trim every clip is reverberated, mixed with noise and
+    masked inside the encoder at its OWN length (SPEC.md 1.16; `AugmentChain.apply_ragged`, `frontend.mask_plan_ragged`), from
+    plans drawn for the whole listing in listing order; speed perturbation is not offered here."""
     from lsm_speech_classifier_amd import spikefile
     commands = list(COMMANDS if commands is None else commands)
     root = Path(DATASET_ROOT if dataset_root is None else dataset_root)
@@ -393,10 +397,26 @@ def create_variable_length_dataset(n_filters: int, filterbank: str, commands=Non
         audio, bins = rows, kept.cpu().numpy()          # the one read-back: the order below and n_steps need host values
         print(f"  Trimmed at {trim['top_db']:g} dB: {int(bins.min())} / {float(bins.mean()):.1f} / {int(bins.max())} time bins "
               f"(min / mean / max)")
+    from lsm_speech_classifier_amd.augment import AugmentChain, StepPlans
+    plans, stages = {}, {}
+    if augment:
+        bank, plans["mix"] = corruption(augment, len(clips))
+        stages["mixer"] = fr.NoiseMixer(bank, device=fe.device)
+    if reverb:
+        rir, rir_lengths, plans["reverb"] = reverberation(reverb, len(clips))
+        stages["reverb"] = fr.Reverberator(rir, rir_lengths, device=fe.device)
+    if mask:
+        try:
+            plans["mask"] = fr.mask_plan_ragged(bins, fe.n_filters, fe.time_bins, **mask)
+        except ValueError as e:
+            raise SystemExit(f"mask flags: {e}")
+    chain, plans = AugmentChain(**stages), StepPlans(**plans)
     order = np.argsort(-bins.astype(np.int64), kind="stable")
     for a in range(0, len(order), ENCODE_BATCH):
         idx = order[a:a + ENCODE_BATCH]
-        raster, _ = fe.encode_ragged(audio[idx], bins[idx])
+        step = plans.take(idx)
+        x = chain.apply_ragged(audio[idx], bins[idx].astype(np.int64) * fr.RAGGED_HOP, step)
+        raster, _ = fe.encode_ragged(x, bins[idx], **step.mask_keyword())
         X[idx] = raster.cpu().numpy()
     n_steps = (bins.astype(np.int64) * len(SPIKE_THRESHOLDS)).astype(np.int32)
     print("\nDataset created successfully.")
@@ -654,6 +674,9 @@ def add_variable_length_flags(ap):
                     help=f"With --trim-silence: keep this much around the speech, in whole bins (default {DEFAULT_TRIM_PAD_MS:g}).")
     ap.add_argument("--trim-min-ms", type=float, default=DEFAULT_TRIM_MIN_MS,
                     help=f"With --trim-silence: the shortest a trimmed clip gets, in whole bins (default {DEFAULT_TRIM_MIN_MS:g}).")
+    ap.add_argument("--augment-variable-length", action="store_true",
+                    help="With --variable-length: let the corruption flags, --rir-dir and the mask flags through -- every clip is "
+                         "reverberated, mixed and masked at its own (trimmed) length (SPEC.md 1.16).")
 
 
 DEFAULT_TRIM_PAD_MS = 30.0
@@ -678,12 +701,14 @@ def trim_from_args(a):
 
 
 def check_variable_length_args(a):
-    """--variable-length is a route of its own: refuse the flags it does not take instead of ignoring them."""
+    """--variable-length is a route of its own: refuse the flags it does not take instead of ignoring them.  Only with
+    --augment-variable-length does it take the corruption flags, --rir-dir and the mask flags (SPEC.md 1.16)."""
     max_bins_of(a.max_seconds)
+    refused = not getattr(a, "augment_variable_length", False)      # the three flag groups of the augmentation chain
     taken = [flag for flag, on in (("--packed", getattr(a, "packed", False)), ("--resample device", getattr(a, "resample", "host") == "device"),
-                                   ("the corruption flags", augment_from_args(a) is not None),
-                                   ("--rir-dir", reverb_from_args(a) is not None), ("--speed-factors", a.speed_factors is not None),
-                                   ("the mask flags", mask_from_args(a) is not None)) if on]
+                                   ("the corruption flags", refused and augment_from_args(a) is not None),
+                                   ("--rir-dir", refused and reverb_from_args(a) is not None), ("--speed-factors", a.speed_factors is not None),
+                                   ("the mask flags", refused and mask_from_args(a) is not None)) if on]
     if taken:
         raise SystemExit(f"--variable-length does not combine with {', '.join(taken)}")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -721,7 +746,9 @@ if __name__ == "__main__":
         check_variable_length_args(a)
         create_variable_length_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                                        dataset_root=a.dataset_root, max_per_class=a.max_per_class,
-                                       synthetic_per_class=a.synthetic_per_class, max_seconds=a.max_seconds, trim=trim)
+                                       synthetic_per_class=a.synthetic_per_class, max_seconds=a.max_seconds, trim=trim,
+                                       **({"augment": augment_from_args(a), "reverb": reverb_from_args(a),
+                                           "mask": mask_from_args(a)} if a.augment_variable_length else {}))
         raise SystemExit(0)
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,

@@ -215,6 +215,23 @@ TRIM_SIGS = {
 }
 TRIM_SYMBOLS = tuple(TRIM_SIGS)
 
+# include/lsm_hip_ragged_augment.h (SPEC.md §1.16): the mixer and the masks on ragged launches -- lsm_mix_f32's list with the
+# DEVICE clip_samples behind n_samples, each ragged encoder's (and the ragged step's) with freq_mask, time_mask before the stream
+def _ragged_masked(sig):
+    res, args = sig
+    return res, args[:-1] + [c_void, c_void] + args[-1:]
+
+
+RAGGED_AUGMENT_SIGS = {
+    "lsm_mix_ragged_f32": (c_int, MIX_SIGS["lsm_mix_f32"][1][:3] + [c_void] + MIX_SIGS["lsm_mix_f32"][1][3:]),
+    "lsm_gammatone_spikes_ragged_masked_f64": _ragged_masked(RAGGED_SIGS["lsm_gammatone_spikes_ragged_f64"]),
+    "lsm_spec_to_spikes_ragged_masked_f64": _ragged_masked(RAGGED_SIGS["lsm_spec_to_spikes_ragged_f64"]),
+    "lsm_spec_to_spikes_ragged_masked_f32": _ragged_masked(RAGGED_SIGS["lsm_spec_to_spikes_ragged_f32"]),
+    "lsm_step_fused_ragged_masked_supported": (c_int, list(STEP_SIGS["lsm_step_fused_supported"][1])),
+    "lsm_step_fused_ragged_masked_f64": _ragged_masked(STEP_SIGS["lsm_step_fused_ragged_f64"]),
+}
+RAGGED_AUGMENT_SYMBOLS = tuple(RAGGED_AUGMENT_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -266,7 +283,7 @@ def load():
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
                               + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
-                              + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items())):
+                              + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items()) + list(RAGGED_AUGMENT_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -79,3 +79,19 @@ class AugmentChain:
             m = plans.mix
             x = self.mixer.mix(x, m.snr_db, m.rows, m.offsets, m.shift, m.scale, out=out("mix"))
         return x
+
+    def apply_ragged(self, x, lengths, plans: StepPlans):
+        """`apply` for a ragged batch (SPEC.md §1.16): ``x`` (B, n_samples) rows at one stride, clip b their first
+        ``lengths[b]`` samples.  Reverberation runs at the row stride -- it is causal, so a clip's own samples are those of
+        the clip alone, and its tail behind the clip is ignored by what follows -- then the ragged mixer takes every clip at
+        its own length.  Speed perturbation changes a clip's length and is not offered.  Without a plan nothing is launched
+        and ``x`` comes back as it is."""
+        self.refuse(plans)
+        if plans.speed is not None:
+            raise ValueError("speed perturbation is not offered on ragged batches: a speed factor changes a clip's bin count")
+        if plans.reverb is not None:
+            x = self.reverb.reverb(x, plans.reverb.rows)
+        if plans.mix is not None:
+            m = plans.mix
+            x = self.mixer.mix_ragged(x, lengths, m.snr_db, m.rows, m.offsets, m.shift, m.scale)
+        return x

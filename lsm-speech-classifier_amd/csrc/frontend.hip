@@ -217,11 +217,11 @@ struct SplitRequest {
     uint8_t *raster = nullptr;
     T *norm_out = nullptr;
     void *stream = nullptr;
-    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
+    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13), and Ragged with masks (1.16)
     const int32_t *clip_cols = nullptr, *clip_bins = nullptr;      // Ragged (1.14): DEVICE counts; ncols, time_bins the strides
 };
 
-template <typename T>           // what all six exports are given
+template <typename T>           // what all eight exports are given
 SplitRequest<T> split_request(const T *db, int n_clips, int n_filters, int ncols, int time_bins, int apply_floor,
                               const T *thr_on, const T *thr_off, int n_thr, int redundancy, uint8_t *raster, T *norm_out,
                               void *stream)
@@ -255,7 +255,15 @@ int launch_spec_to_spikes(const SplitRequest<T> &r)
         lsm_fe::launch_spec_to_spikes_masked<T>(a, lsm_fe::MaskArgs{r.freq_mask, r.time_mask}, SPK_THREADS, lds, r.stream);
     } else if (r.form == FrontForm::Ragged) {
         if (const int rc = check_ragged(r.clip_cols, r.clip_bins, r.time_bins, 0, 0)) return rc;
-        lsm_fe::launch_spec_to_spikes_ragged<T>(a, lsm_fe::RaggedCounts{r.clip_cols, r.clip_bins}, SPK_THREADS, lds, r.stream);
+        // the masked ragged exports' own refusal behind the ragged twin's (include/lsm_hip_ragged_augment.h; the ragged
+        // exports leave both masks null); without a mask exactly the ragged launch
+        if (const int rc = check_masks(r.freq_mask, r.time_mask)) return rc;
+        const lsm_fe::RaggedCounts counts{r.clip_cols, r.clip_bins};
+        if (r.freq_mask || r.time_mask)
+            lsm_fe::launch_spec_to_spikes_ragged_masked<T>(a, counts, lsm_fe::MaskArgs{r.freq_mask, r.time_mask}, SPK_THREADS, lds,
+                                                           r.stream);
+        else
+            lsm_fe::launch_spec_to_spikes_ragged<T>(a, counts, SPK_THREADS, lds, r.stream);
     } else {
         auto fn = spec_to_spikes_kernel<T>;
         if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(fn));
@@ -490,13 +498,13 @@ struct FrontRequest {
     int coef_flags = 0, launch_flags = 0;   // (a step's front half has no launch_flags, raster or stream: they stay 0)
     uint8_t *raster = nullptr;              // (n_clips, n_filters * redundancy, time_bins * n_thr)
     void *stream = nullptr;
-    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
+    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13), and Ragged with masks (1.16)
     const int32_t *clip_bins = nullptr;     // Ragged (1.14): DEVICE counts in and out; ncols, time_bins and n_samples the strides
     int32_t *clip_steps_out = nullptr;
     lsm_fe::StepFront *step = nullptr;      // Step (step_fused.hip): checked and planned into it, not launched
 };
 
-// what all five callers are given
+// what all six callers are given
 static FrontRequest front_request(const float *audio, int n_clips, int n_samples, const double *coefs, int n_filters, int nwin,
                                   int hop, int ncols, int time_bins, const double *thr_on, const double *thr_off, int n_thr,
                                   int redundancy, void *workspace, long workspace_bytes, int coef_flags)
@@ -570,6 +578,7 @@ static int plan_front(const FrontRequest &r, FusedArgs *args, lsm_fe::FusedLaunc
     if (r.form == FrontForm::Ragged) {
         if (const int rc = check_ragged(r.clip_bins, r.clip_bins, r.time_bins, r.n_samples, r.hop)) return rc;
         LSM_REQUIRE(((uintptr_t)r.clip_steps_out & 3u) == 0, "ragged: clip_steps_out must be 4-byte aligned");
+        if (const int rc = check_masks(r.freq_mask, r.time_mask)) return rc;    // (the ragged export leaves both null)
     }
     return LSM_OK;
 }
@@ -595,7 +604,10 @@ static int gammatone_spikes(const FrontRequest &r)
     }
     if (r.form == FrontForm::Masked && (r.freq_mask || r.time_mask))       // without a mask exactly the plain launch
         lsm_fe::launch_gammatone_spikes_masked(l, &a, lsm_fe::MaskArgs{r.freq_mask, r.time_mask}, r.stream);
-    else if (r.form == FrontForm::Ragged)
+    else if (r.form == FrontForm::Ragged && (r.freq_mask || r.time_mask))
+        lsm_fe::launch_gammatone_spikes_ragged_masked(l, &a, lsm_fe::RaggedArgs{r.clip_bins, r.clip_steps_out},
+                                                      lsm_fe::MaskArgs{r.freq_mask, r.time_mask}, r.stream);
+    else if (r.form == FrontForm::Ragged)                                  // without a mask exactly the ragged launch
         lsm_fe::launch_gammatone_spikes_ragged(l, &a, lsm_fe::RaggedArgs{r.clip_bins, r.clip_steps_out}, r.stream);
     else
         launch_fused_form<PlainFamily>(l, r.stream, a);
@@ -665,6 +677,50 @@ LSM_API int lsm_gammatone_spikes_ragged_f64(const float *audio, int n_clips, int
     r.raster = raster; r.launch_flags = launch_flags; r.stream = stream;
     r.form = FrontForm::Ragged; r.clip_bins = clip_bins; r.clip_steps_out = clip_steps_out;
     return gammatone_spikes(r);
+}
+
+// include/lsm_hip_ragged_augment.h (SPEC.md 1.16): the ragged twins' parameters with freq_mask, time_mask before the stream;
+// kernels in ragged_masked_frontend.hip
+LSM_API int lsm_gammatone_spikes_ragged_masked_f64(const float *audio, int n_clips, int n_samples,
+                                                   const double *coefs, int n_filters, int nwin, int hop, int ncols,
+                                                   int time_bins, const int32_t *clip_bins, const double *thr_on,
+                                                   const double *thr_off, int n_thr, int redundancy, uint8_t *raster,
+                                                   int32_t *clip_steps_out, void *workspace, long workspace_bytes,
+                                                   int coef_flags, int launch_flags, const uint32_t *freq_mask,
+                                                   const uint32_t *time_mask, void *stream)
+{
+    FrontRequest r = front_request(audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off,
+                                   n_thr, redundancy, workspace, workspace_bytes, coef_flags);
+    r.raster = raster; r.launch_flags = launch_flags; r.stream = stream;
+    r.form = FrontForm::Ragged; r.clip_bins = clip_bins; r.clip_steps_out = clip_steps_out;
+    r.freq_mask = freq_mask; r.time_mask = time_mask;
+    return gammatone_spikes(r);
+}
+
+LSM_API int lsm_spec_to_spikes_ragged_masked_f64(const double *db, int n_clips, int n_filters, int ncols, int time_bins,
+                                                 const int32_t *clip_cols, const int32_t *clip_bins, int apply_floor,
+                                                 const double *thr_on, const double *thr_off, int n_thr, int redundancy,
+                                                 uint8_t *raster, double *norm_out, const uint32_t *freq_mask,
+                                                 const uint32_t *time_mask, void *stream)
+{
+    SplitRequest<double> r = split_request<double>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                                   redundancy, raster, norm_out, stream);
+    r.form = FrontForm::Ragged; r.clip_cols = clip_cols; r.clip_bins = clip_bins;
+    r.freq_mask = freq_mask; r.time_mask = time_mask;
+    return launch_spec_to_spikes(r);
+}
+
+LSM_API int lsm_spec_to_spikes_ragged_masked_f32(const float *db, int n_clips, int n_filters, int ncols, int time_bins,
+                                                 const int32_t *clip_cols, const int32_t *clip_bins, int apply_floor,
+                                                 const float *thr_on, const float *thr_off, int n_thr, int redundancy,
+                                                 uint8_t *raster, float *norm_out, const uint32_t *freq_mask,
+                                                 const uint32_t *time_mask, void *stream)
+{
+    SplitRequest<float> r = split_request<float>(db, n_clips, n_filters, ncols, time_bins, apply_floor, thr_on, thr_off, n_thr,
+                                                 redundancy, raster, norm_out, stream);
+    r.form = FrontForm::Ragged; r.clip_cols = clip_cols; r.clip_bins = clip_bins;
+    r.freq_mask = freq_mask; r.time_mask = time_mask;
+    return launch_spec_to_spikes(r);
 }
 
 LSM_API int lsm_spec_to_spikes_ragged_f64(const double *db, int n_clips, int n_filters, int ncols, int time_bins,

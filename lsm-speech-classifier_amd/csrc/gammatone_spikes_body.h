@@ -127,6 +127,13 @@ void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args
 template <typename T>
 void launch_spec_to_spikes_ragged(const SpikeArgs<T> &a, const RaggedCounts &rc, int threads, size_t lds, void *stream);
 
+// The masked ragged launches (SPEC.md 1.16), defined in ragged_masked_frontend.hip, likewise
+void launch_gammatone_spikes_ragged_masked(const FusedLaunch &l, const void *fused_args, const RaggedArgs &rg, const MaskArgs &m,
+                                           void *stream);
+template <typename T>
+void launch_spec_to_spikes_ragged_masked(const SpikeArgs<T> &a, const RaggedCounts &rc, const MaskArgs &m, int threads, size_t lds,
+                                         void *stream);
+
 }  // namespace lsm_fe
 
 namespace {

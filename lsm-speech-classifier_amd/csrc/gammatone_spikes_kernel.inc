@@ -1,7 +1,8 @@
 // gammatone_spikes_kernel.inc -- the text of the fused gammatone kernel, included once per form: the includer defines the
 // kernel's name (LSM_FUSED_KERNEL), its parameters (LSM_FUSED_PARAMS) and MASK (LSM_FUSED_MASK) -- gammatone_spikes_body.h
 // for gammatone_spikes_kernel(const FusedArgs a), mask.hip for gammatone_spikes_masked_kernel(a, const lsm_fe::MaskArgs m) --
-// and RAGGED (LSM_FUSED_RAGGED): ragged_frontend.hip for gammatone_spikes_ragged_kernel(a, const lsm_fe::RaggedArgs rg).
+// and RAGGED (LSM_FUSED_RAGGED): ragged_frontend.hip for gammatone_spikes_ragged_kernel(a, const lsm_fe::RaggedArgs rg), and
+// ragged_masked_frontend.hip for gammatone_spikes_ragged_masked_kernel(a, rg, m) with both on (SPEC.md 1.16).
 // The function's qualifiers are the includer's too (LSM_FUSED_QUALIFIERS: for these three `__global__
 // __launch_bounds__(GT_MAX_WPB * 64)`), and so is what follows the staged rows, a file the includer names
 // (LSM_FUSED_TAIL_INC): the three write the uint8 raster (gammatone_spikes_raster_out.inc); step_fused.hip hands the staged
@@ -295,7 +296,9 @@ LSM_FUSED_QUALIFIERS void LSM_FUSED_KERNEL(LSM_FUSED_PARAMS)
             chm[q] = m.freq != nullptr && live[q] &&
                      ((m.freq[(size_t)b * ((F + 31) >> 5) + (chl >> 5)] >> (chl & 31)) & 1u) != 0u;
         }
-        tmc = m.time ? m.time + (size_t)b * ((Tb + 31) >> 5) : nullptr;     // wave-uniform
+        // wave-uniform; the mask rows keep the launch's stride (RAGGED: a group's word index stays below ceil(Tb / 32), and
+        // the bits at or behind Tb belong to bins that the latch loop skips)
+        tmc = m.time ? m.time + (size_t)b * (((RAGGED ? a.time_bins : Tb) + 31) >> 5) : nullptr;
     }
     // straight-line variants (fast division or not, <= 4 thresholds or not, resize or not): one uniform choice
     // per wave instead of uniform branches inside the loop, which would keep the compiler from batching the loads

@@ -2,6 +2,8 @@
 // of the front ends.  Three kernels over the shared pieces of mix_body.h, one workgroup of 256 threads per row each:
 //   mix_power_kernel    the row power P of float32 rows;
 //   mix_kernel          the batch form: one pass takes Px and Pv, the tree joins both side by side, then the mixing pass;
+//                       and its RAGGED form on rows of a stride whose clips have their own lengths (SPEC §1.16), which
+//                       then fills the rest of the row with zeros;
 //   mix_stream_kernel   the streamed form: the mixing pass alone, from a caller's gain and a per-stream noise position.
 //
 // Layout.  Thread l owns the partial sum p[l] of SPEC §1.10, so a wave reads 256 contiguous bytes per step of the power
@@ -25,7 +27,8 @@ struct MixArgs {
     const double *ratio, *gain;         // (rows): batch / streamed
     double *gain_out, *power_out;       // (rows), (rows, 2), or null
     int n, M, L;
-};
+    const int32_t *clip_samples;        // (rows): the ragged batch form's lengths, n is then the rows' stride (last: the
+};                                      // members above keep their offsets)
 
 __device__ __forceinline__ int clamped(const int32_t *values, int b, int lo, int hi, int absent)
 {
@@ -45,12 +48,17 @@ __global__ __launch_bounds__(THREADS) void mix_power_kernel(const float *x, int 
     if (threadIdx.x == 0) power_out[blockIdx.x] = p[0][0];
 }
 
+// RAGGED (SPEC §1.16): a.n is the rows' stride and clip b has n = clamp(clip_samples[b], 0, a.n) samples -- everything that
+// says how much of the row is the clip takes n, where the row lies takes the stride.  Samples of the row from n on are never
+// read (shifted_sample clamps its index below n; with n = 0 neither the loop nor the store calls it) and are written as +0.0.
+template <bool RAGGED>
 __global__ __launch_bounds__(THREADS) void mix_kernel(const MixArgs a)
 {
     __shared__ double p[2][THREADS];
-    const int b = blockIdx.x, l = threadIdx.x, n = a.n;
+    const int b = blockIdx.x, l = threadIdx.x, stride = a.n;
+    const int n = RAGGED ? clamped(a.clip_samples, b, 0, stride, 0) : stride;
     const uint32_t L = (uint32_t)a.L;
-    const float *row = a.audio + (size_t)b * n;
+    const float *row = a.audio + (size_t)b * stride;
     const int s = clamped(a.shift, b, -n, n, 0);
     const double sc = a.scale ? (double)a.scale[b] : 1.0;
     const float *nrow = a.noise + (size_t)clamped(a.noise_row, b, 0, a.M - 1, 0) * L;
@@ -81,7 +89,8 @@ __global__ __launch_bounds__(THREADS) void mix_kernel(const MixArgs a)
         }
     }
 
-    store_row(a.out + (size_t)b * n, n,
+    float *orow = a.out + (size_t)b * stride;
+    store_row(orow, n,
               [&](const int i) {
                   const double v = noisy ? (double)nrow[noise_index(o, (uint32_t)i, L)] : 0.0;
                   return mixed_sample(shifted_sample(row, n, s, sc, i), noisy, g, v);
@@ -96,6 +105,8 @@ __global__ __launch_bounds__(THREADS) void mix_kernel(const MixArgs a)
                       j = noise_next(j, L);
                   }
               });
+    // the fill has a head of its own: out + n has whatever alignment the stride and n leave it
+    if constexpr (RAGGED) fill_row(orow + n, stride - n);
 }
 
 __global__ __launch_bounds__(THREADS) void mix_stream_kernel(const MixArgs a)
@@ -167,9 +178,11 @@ LSM_API int lsm_mix_power_f32(const float *x, int n_rows, int n_samples, double 
     return LSM_OK;
 }
 
-LSM_API int lsm_mix_f32(const float *audio, int n_clips, int n_samples, const float *noise, int n_noise_rows, int noise_len,
-                        const int32_t *noise_row, const int32_t *noise_offset, const int32_t *shift, const float *scale,
-                        const double *ratio, float *out, double *gain_out, double *power_out, void *stream)
+// The batch form's two entry points: lsm_mix_f32's refusals in their order, then the ragged form's own
+static int mix_batch(bool ragged, const float *audio, int n_clips, int n_samples, const int32_t *clip_samples, const float *noise,
+                     int n_noise_rows, int noise_len, const int32_t *noise_row, const int32_t *noise_offset,
+                     const int32_t *shift, const float *scale, const double *ratio, float *out, double *gain_out,
+                     double *power_out, void *stream)
 {
     int rc = check_shape("n_samples", n_samples, n_clips);
     if (rc == LSM_OK) rc = check_bank(n_noise_rows, noise_len);
@@ -187,14 +200,36 @@ LSM_API int lsm_mix_f32(const float *audio, int n_clips, int n_samples, const fl
     if (n_clips == 0) return LSM_OK;
     LSM_REQUIRE(audio && noise && ratio && out, "mix: null buffer (audio, noise, ratio and out are required)");
     LSM_REQUIRE(out != audio, "out must not be audio: a shift reads across what it would write");
+    if (ragged) {
+        LSM_REQUIRE(clip_samples != nullptr, "mix ragged: null clip_samples");
+        MIX_ALIGNED(clip_samples, 4);
+    }
     MixArgs a{};
     a.audio = audio; a.noise = noise; a.out = out;
     a.noise_row = noise_row; a.noise_offset = noise_offset; a.shift = shift; a.scale = scale; a.ratio = ratio;
-    a.gain_out = gain_out; a.power_out = power_out;
+    a.gain_out = gain_out; a.power_out = power_out; a.clip_samples = clip_samples;
     a.n = n_samples; a.M = n_noise_rows; a.L = noise_len;
-    hipLaunchKernelGGL(mix_kernel, dim3(n_clips), dim3(THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ragged ? mix_kernel<true> : mix_kernel<false>, dim3(n_clips), dim3(THREADS), 0, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     return LSM_OK;
+}
+
+LSM_API int lsm_mix_f32(const float *audio, int n_clips, int n_samples, const float *noise, int n_noise_rows, int noise_len,
+                        const int32_t *noise_row, const int32_t *noise_offset, const int32_t *shift, const float *scale,
+                        const double *ratio, float *out, double *gain_out, double *power_out, void *stream)
+{
+    return mix_batch(false, audio, n_clips, n_samples, nullptr, noise, n_noise_rows, noise_len, noise_row, noise_offset, shift,
+                     scale, ratio, out, gain_out, power_out, stream);
+}
+
+// include/lsm_hip_ragged_augment.h (SPEC.md §1.16): lsm_mix_f32 on rows of n_samples whose clips have clip_samples[b] samples
+LSM_API int lsm_mix_ragged_f32(const float *audio, int n_clips, int n_samples, const int32_t *clip_samples, const float *noise,
+                               int n_noise_rows, int noise_len, const int32_t *noise_row, const int32_t *noise_offset,
+                               const int32_t *shift, const float *scale, const double *ratio, float *out, double *gain_out,
+                               double *power_out, void *stream)
+{
+    return mix_batch(true, audio, n_clips, n_samples, clip_samples, noise, n_noise_rows, noise_len, noise_row, noise_offset,
+                     shift, scale, ratio, out, gain_out, power_out, stream);
 }
 
 LSM_API int lsm_mix_stream_f32(const float *audio, int n_streams, int n_cols, const float *noise, int n_noise_rows,

@@ -74,4 +74,10 @@ __device__ __forceinline__ void store_row(float *out, int n, One y, Four y4)
     if (i < n) out[i] = y(i);
 }
 
+// out[i] = +0.0 for i in [0, n): store_row's head, 16-byte stores and tail on a row that starts anywhere (n may be 0)
+__device__ __forceinline__ void fill_row(float *out, int n)
+{
+    store_row(out, n, [](const int) { return 0.0f; }, [](const int, float4 &y) { y = make_float4(0.0f, 0.0f, 0.0f, 0.0f); });
+}
+
 }  // namespace lsm_mix

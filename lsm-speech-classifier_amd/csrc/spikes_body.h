@@ -167,7 +167,9 @@ __device__ __forceinline__ void spec_to_spikes_body(const SpikeArgs<T> &a, const
     const uint32_t *fmc = nullptr, *tmc = nullptr;            // this clip's mask words
     if constexpr (MASK) {
         fmc = m.freq ? m.freq + (size_t)b * ((F + 31) >> 5) : nullptr;
-        tmc = m.time ? m.time + (size_t)b * W : nullptr;
+        // (RAGGED: the mask rows keep the launch's stride; the clip reads the first W words of its row, and the bits at or
+        // behind Tb meet lanes that are not `valid`)
+        tmc = m.time ? m.time + (size_t)b * (RAGGED ? (Tbs + 31) >> 5 : W) : nullptr;
     }
 
     for (int r0 = 0; r0 < F; r0 += SPK_ROWS) {

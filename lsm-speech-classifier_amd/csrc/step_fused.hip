@@ -83,10 +83,12 @@ size_t step_lds_bytes(long T, size_t lif_lds)
 constexpr size_t STEP_LDS_MAX = 160 * 1024;
 
 // The three families of the step (include/lsm_hip_step.h): the plain kernels above, the masked ones (step_fused_masked.hip)
-// and the ragged ones (step_fused_ragged.hip).  A batch is ragged or masked, never both, as on the front-end entry points.
+// and the ragged ones (step_fused_ragged.hip).  A batch that is both takes a fourth family (step_fused_ragged_masked.hip).
 // STEP_STATE (include/lsm_hip_step_state.h, step_fused_state.hip) is no `form` of lsm_step_fused_form_supported: its entry
 // points and its query are their own, its served set is the plain step's.
-enum StepForm { STEP_PLAIN = 0, STEP_MASKED = 1, STEP_RAGGED = 2, STEP_STATE = 3 };
+// STEP_RAGGED_MASKED (include/lsm_hip_ragged_augment.h, step_fused_ragged_masked.hip) is none either: its query is its own,
+// its served set is the ragged step's.
+enum StepForm { STEP_PLAIN = 0, STEP_MASKED = 1, STEP_RAGGED = 2, STEP_STATE = 3, STEP_RAGGED_MASKED = 4 };
 constexpr int RAGGED_HOP = 160;         // the one hop the ragged front end is offered for (include/lsm_hip_ragged.h)
 
 // What a form asks of the shape beyond the plain step: the ragged step the hop on which a clip of T bins is the front end of
@@ -113,14 +115,14 @@ int step_supported(const char *what, const lsm_reservoir *h, int n_clips, int n_
     return step_lds_bytes((long)time_bins * n_thr, lds) <= STEP_LDS_MAX ? 1 : 0;
 }
 
-// One step launch: the five entry points fill `form` and their own members (a member that is not the form's is never read).
+// One step launch: the six entry points fill `form` and their own members (a member that is not the form's is never read).
 // Refusals: the front end's, the reservoir's (a state step: lsm_reservoir_run_from's / _run_segments'), the form's own (the
 // masks' alignment; the ragged counts and strides; the segment rows), then the shapes the launch does not serve.
 struct StepOwn {
     int form = STEP_PLAIN;
     const char *what = "lsm_step_fused_f64";
-    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13)
-    const int32_t *clip_bins = nullptr;                             // Ragged (1.14): DEVICE counts, clamped in the kernel
+    const uint32_t *freq_mask = nullptr, *time_mask = nullptr;     // Masked (SPEC.md 1.13), Ragged masked (1.16)
+    const int32_t *clip_bins = nullptr;                             // Ragged (1.14), Ragged masked: DEVICE counts, clamped in the kernel
     lsm_lif::StepState state;                                       // State (4f): continuation and segment records
     float *segment_rows = nullptr;                                  //   the clip's tumbling feature rows, or null
 };
@@ -165,8 +167,9 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
     // the form's own refusals, behind the two halves'
     if (own.form == STEP_MASKED) {
         if (const int rc = lsm_fe::step_check_masks(own.freq_mask, own.time_mask)) return rc;
-    } else if (own.form == STEP_RAGGED) {
+    } else if (own.form == STEP_RAGGED || own.form == STEP_RAGGED_MASKED) {
         if (const int rc = lsm_fe::step_check_ragged(own.clip_bins, time_bins, n_samples, hop)) return rc;
+        if (const int rc = lsm_fe::step_check_masks(own.freq_mask, own.time_mask)) return rc;      // (a ragged step: both null)
     } else if (own.form == STEP_STATE) {
         LSM_REQUIRE((reinterpret_cast<uintptr_t>(own.segment_rows) & 3) == 0, "segment_rows_out must be 4-byte aligned");
         LSM_REQUIRE(own.segment_rows == nullptr || n_keys >= 1, "segment_rows_out with n_keys=0: a row needs feature keys");
@@ -174,7 +177,11 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
     // a masked step without a mask is the plain launch (SPEC.md 1.13: the unmasked bytes), and so is a state step from reset
     // that saves no state and closes no records (SPEC.md 4f)
     const bool stateless = own.form == STEP_STATE && !own.state.state_in && !own.state.state_out && !own.state.segmented;
-    const int form = ((own.form == STEP_MASKED && !own.freq_mask && !own.time_mask) || stateless) ? (int)STEP_PLAIN : own.form;
+    // a masked ragged step without a mask is the ragged launch
+    const bool maskless = !own.freq_mask && !own.time_mask;
+    const int form = ((own.form == STEP_MASKED && maskless) || stateless) ? (int)STEP_PLAIN
+                     : (own.form == STEP_RAGGED_MASKED && maskless)      ? (int)STEP_RAGGED
+                                                                         : own.form;
     step_fn_t fn = pick_step(sl, fr.l.shb0);
     if (!front_shape_served(n_filters, nwin, hop, redundancy, coef_flags) || !fr.l.pair || fr.l.nch != 1 || !fr.l.fast ||
         fr.l.nw != 3 || a.groups != 4 || fr.l.block != 256 || fr.l.grid != (unsigned)n_clips || d.C != n_filters * redundancy ||
@@ -185,7 +192,8 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
     }
     // ragged: a clip of t bins has t - (time_bins - ncols) columns; on hop 160 with the 2 columns a 25 ms window costs, that
     // is the front end of (160 t samples, t bins) for every t (include/lsm_hip_ragged.h)
-    if (own.form == STEP_RAGGED && (!form_shape_served(own.form, hop) || ncols != time_bins - 2)) {
+    const bool ragged = own.form == STEP_RAGGED || own.form == STEP_RAGGED_MASKED;
+    if (ragged && (!form_shape_served(STEP_RAGGED, hop) || ncols != time_bins - 2)) {
         lsm_set_error("%s: shape not served (hop %d, %d columns for %d bins: a ragged step needs hop %d and time_bins - 2 "
                       "columns): make the two launches", what, hop, ncols, time_bins, RAGGED_HOP);
         return LSM_ERR_UNSUPPORTED;
@@ -208,6 +216,12 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
                             ? lsm_step::launch_step_masked(l, &a, d, lsm_fe::MaskArgs{own.freq_mask, own.time_mask}, stream)
                         : form == STEP_RAGGED
                             ? lsm_step::launch_step_ragged(l, &a, d, lsm_fe::RaggedArgs{own.clip_bins, nullptr}, stream)
+                        : form == STEP_RAGGED_MASKED
+                            ? lsm_step::launch_step_ragged_masked(
+                                  l, &a, d,
+                                  lsm_step::RaggedMaskArgs{lsm_fe::RaggedArgs{own.clip_bins, nullptr},
+                                                           lsm_fe::MaskArgs{own.freq_mask, own.time_mask}},
+                                  stream)
                             : lsm_step::launch_step_state(l, &a, d, lsm_step::StateRows{own.segment_rows}, stream);
         LSM_REQUIRE(ok, "%s: no kernel for %d slots per lane", what, sl);
     }
@@ -264,6 +278,29 @@ LSM_API int lsm_step_fused_ragged_f64(const lsm_reservoir *h, const float *audio
 {
     StepOwn own;
     own.form = STEP_RAGGED; own.what = "lsm_step_fused_ragged_f64"; own.clip_bins = clip_bins;
+    return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
+                       redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
+}
+
+// include/lsm_hip_ragged_augment.h (SPEC.md 1.16): the ragged step with the masked step's words
+LSM_API int lsm_step_fused_ragged_masked_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop,
+                                                   int time_bins, int n_thr, int redundancy, int coef_flags)
+{
+    // the ragged step's served set and LDS bound: the masks add no byte to the image
+    return step_supported("lsm_step_fused_ragged_masked_supported", h, n_clips, n_filters, nwin, hop, time_bins, n_thr,
+                          redundancy, coef_flags, STEP_RAGGED);
+}
+
+LSM_API int lsm_step_fused_ragged_masked_f64(const lsm_reservoir *h, const float *audio, int n_clips, int n_samples,
+                                             const double *coefs, int n_filters, int nwin, int hop, int ncols, int time_bins,
+                                             const int32_t *clip_bins, const double *thr_on, const double *thr_off, int n_thr,
+                                             int redundancy, void *workspace, long workspace_bytes, int coef_flags,
+                                             const int32_t *key_ids, int n_keys, float *features_out, int32_t *stats_out,
+                                             const uint32_t *freq_mask, const uint32_t *time_mask, void *stream)
+{
+    StepOwn own;
+    own.form = STEP_RAGGED_MASKED; own.what = "lsm_step_fused_ragged_masked_f64"; own.clip_bins = clip_bins;
+    own.freq_mask = freq_mask; own.time_mask = time_mask;
     return step_launch(own, h, audio, n_clips, n_samples, coefs, n_filters, nwin, hop, ncols, time_bins, thr_on, thr_off, n_thr,
                        redundancy, workspace, workspace_bytes, coef_flags, key_ids, n_keys, features_out, stats_out, stream);
 }

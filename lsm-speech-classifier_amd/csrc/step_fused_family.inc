@@ -1,10 +1,10 @@
 // step_fused_family.inc -- one family of the one-launch step's kernels beside the plain one of step_fused.hip: the three kernel
 // texts (1, 2 and 4 neuron slots per lane) in the two forms the step serves (3 live windows, the fast coefficient path, the
 // lane pair; with and without the shared b0), and the function that launches one of them.  The includer
-// (step_fused_masked.hip, step_fused_ragged.hip, step_fused_state.hip) says
+// (step_fused_masked.hip, step_fused_ragged.hip, step_fused_ragged_masked.hip, step_fused_state.hip) says
 //   LSM_STEP_FAMILY_KERNEL(sl)   the kernels' names;
 //   LSM_STEP_FAMILY_ARG          the type of the family's own kernel argument, behind FusedArgs and DenseArgs;
-//   LSM_STEP_FAMILY_ARG_NAME     its name in the kernel text (`m`, `rg` or `sx`);
+//   LSM_STEP_FAMILY_ARG_NAME     its name in the kernel text (`m`, `rg`, `sx`, or `rm`, which carries both `rg` and `m`);
 //   LSM_FUSED_MASK, LSM_FUSED_RAGGED   as gammatone_spikes_kernel.inc reads them;
 //   LSM_FUSED_STATE                    as step_fused_tail.inc reads it (constexpr bool ST, and `sx` where it is no parameter);
 //   LSM_STEP_FAMILY_LAUNCH       the name of the launch function (step_fused_forms.h).

@@ -25,11 +25,20 @@ struct StateRows {
     float *segment_rows;       // (n_clips, T / seg, n_keys * n_out) or null; a segmented launch only
 };
 
+// The masked ragged family's own kernel argument (step_fused_ragged_masked.hip): the ragged step's counts and the masked
+// step's words, one argument because a family has one
+struct RaggedMaskArgs {
+    lsm_fe::RaggedArgs rg;
+    lsm_fe::MaskArgs m;
+};
+
 // false: no such form (sl is none of 1, 2, 4); nothing was launched
 bool launch_step_masked(const StepLaunch &l, const void *fused_args, const lsm_lif::DenseArgs &d, const lsm_fe::MaskArgs &m,
                         void *stream);
 bool launch_step_ragged(const StepLaunch &l, const void *fused_args, const lsm_lif::DenseArgs &d, const lsm_fe::RaggedArgs &rg,
                         void *stream);
+bool launch_step_ragged_masked(const StepLaunch &l, const void *fused_args, const lsm_lif::DenseArgs &d, const RaggedMaskArgs &rm,
+                               void *stream);
 bool launch_step_state(const StepLaunch &l, const void *fused_args, const lsm_lif::DenseArgs &d, const StateRows &sx,
                        void *stream);
 

@@ -367,10 +367,12 @@ class SpikeFrontEnd:
         return torch.where(t < 3, torch.zeros_like(t), t)
 
     def spikes_from_db_ragged(self, db: torch.Tensor, cols: torch.Tensor, bins: torch.Tensor, want_norm: bool = False,
-                              want_raster: bool = True, raster_out: torch.Tensor | None = None):
+                              want_raster: bool = True, raster_out: torch.Tensor | None = None, mask=None):
         """`spikes_from_db` for a ragged batch (`lsm_spec_to_spikes_ragged_*`): ``db`` (B, F, ncols) holds clip b's dB values
         in its first ``cols[b]`` columns, ``bins[b]`` is its number of time bins (int32 device tensors).  Returns (raster
-        (B, C, n_steps), normalised spectrogram (B, F, time_bins) or None); both are zeros past a clip's bins."""
+        (B, C, n_steps), normalised spectrogram (B, F, time_bins) or None); both are zeros past a clip's bins.  ``mask``: a
+        `MaskPlan` whose time bits name the bins of each clip's own length (SPEC.md §1.16, `mask_plan_ragged`): the masked
+        ragged entry point; None makes exactly the unmasked call."""
         B = db.shape[0]
         f64 = db.dtype == torch.float64
         on, off = threshold_tables(self.thresholds, self.gap, np.float64 if f64 else np.float32)
@@ -386,16 +388,21 @@ class SpikeFrontEnd:
                 torch.empty((B, self.n_channels, self.n_steps), dtype=torch.uint8, device=self.device) if want_raster else None)
             norm = (torch.empty((B, self.n_filters, self.time_bins), dtype=db.dtype, device=self.device)
                     if want_norm else None)
-            fn = self.lib.lsm_spec_to_spikes_ragged_f64 if f64 else self.lib.lsm_spec_to_spikes_ragged_f32
-            _lib.check(fn(_dev(db), B, self.n_filters, db.shape[2], self.time_bins, _dev(cols), _dev(bins),
-                          1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on), self.redundancy,
-                          _dev(raster) if raster is not None else None, _dev(norm) if want_norm else None, self._stream()),
-                       "lsm_spec_to_spikes_ragged")
+            args = (_dev(db), B, self.n_filters, db.shape[2], self.time_bins, _dev(cols), _dev(bins),
+                    1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on), self.redundancy,
+                    _dev(raster) if raster is not None else None, _dev(norm) if want_norm else None)
+            if mask is None:
+                fn = self.lib.lsm_spec_to_spikes_ragged_f64 if f64 else self.lib.lsm_spec_to_spikes_ragged_f32
+                _lib.check(fn(*args, self._stream()), "lsm_spec_to_spikes_ragged")
+            else:
+                fm, tm = upload_mask(mask, B, self.n_filters, self.time_bins, self.device)
+                fn = self.lib.lsm_spec_to_spikes_ragged_masked_f64 if f64 else self.lib.lsm_spec_to_spikes_ragged_masked_f32
+                _lib.check(fn(*args, _dev(fm), _dev(tm), self._stream()), "lsm_spec_to_spikes_ragged_masked")
         return raster, norm
 
     def encode_ragged(self, audio, bins, fused: bool | None = None, low_latency: bool = False,
                       raster_out: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
-                      share_lds: bool = False):
+                      share_lds: bool = False, mask=None):
         """Clips of different lengths in the launches a batch of equal clips takes (SPEC.md §1.14).  ``audio``
         (B, n_samples): clip b is the first ``160 * bins[b]`` samples of its row, and what lies behind them influences
         nothing.  ``bins``: B host integers, each 0 or 3 .. time_bins (checked), or an int32 device tensor (not read: the
@@ -407,12 +414,17 @@ class SpikeFrontEnd:
         (`lsm_gammatone_spikes_ragged_f64`; ``low_latency``, ``share_lds``, ``raster_out`` and ``workspace`` as `encode`
         takes them), or with ``fused=False`` `lsm_gammatone_spec_f64` on the padded rows and the ragged encoder: the same
         bytes.  Mel: always the split route -- the rows are zeroed from each clip's end on into a staging tensor, then
-        `lsm_mel_power_f32`, `lsm_power_to_db_ragged_f32` and the ragged encoder.  Masks are not offered here."""
+        `lsm_mel_power_f32`, `lsm_power_to_db_ragged_f32` and the ragged encoder.  ``mask``: a `MaskPlan` of the batch's clips
+        at the launch's strides whose time bit j names bin j of clip b's own bins (SPEC.md §1.16, `mask_plan_ragged`), applied
+        inside the encoder of whichever route is taken (include/lsm_hip_ragged_augment.h); None makes exactly the unmasked
+        calls."""
         why = ragged_refusal(self.n_samples, self.time_bins)
         if why:
             raise ValueError(why)
         audio = self._audio(audio)
         B = audio.shape[0]
+        if mask is not None:
+            checked_mask(mask, B, self.n_filters, self.time_bins)
         if fused is None:
             fused = self.filterbank == "gammatone" and self.will_fuse()
         if fused and self.filterbank == "mel":
@@ -427,11 +439,16 @@ class SpikeFrontEnd:
                 on, off = threshold_tables(self.thresholds, self.gap, np.float64)
                 steps = torch.empty((B,), dtype=torch.int32, device=self.device)
                 ws, ws_bytes = self._workspace_for(B, workspace)
-                _lib.check(self.lib.lsm_gammatone_spikes_ragged_f64(
-                    _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop, self.ncols,
-                    self.time_bins, _dev(bins_dev), _host(on), _host(off), len(on), self.redundancy, _dev(raster), _dev(steps),
-                    _dev(ws), ws_bytes, self.coef_flags, self._launch_flags(low_latency, share_lds), self._stream()),
-                    "lsm_gammatone_spikes_ragged_f64")
+                args = (_dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop, self.ncols,
+                        self.time_bins, _dev(bins_dev), _host(on), _host(off), len(on), self.redundancy, _dev(raster),
+                        _dev(steps), _dev(ws), ws_bytes, self.coef_flags, self._launch_flags(low_latency, share_lds))
+                if mask is None:
+                    _lib.check(self.lib.lsm_gammatone_spikes_ragged_f64(*args, self._stream()),
+                               "lsm_gammatone_spikes_ragged_f64")
+                else:
+                    fm, tm = upload_mask(mask, B, self.n_filters, self.time_bins, self.device)
+                    _lib.check(self.lib.lsm_gammatone_spikes_ragged_masked_f64(*args, _dev(fm), _dev(tm), self._stream()),
+                               "lsm_gammatone_spikes_ragged_masked_f64")
                 return raster, steps
             t = self._clamped_bins(bins_dev)
             steps = (t * n_thr).to(torch.int32)
@@ -454,7 +471,7 @@ class SpikeFrontEnd:
                 _lib.check(self.lib.lsm_power_to_db_ragged_f32(
                     _dev(power), B, self.n_filters, int(power.shape[2]), _dev(cols), C.c_float(_mel.AMIN),
                     C.c_float(_mel.TOP_DB), _dev(db), self._stream()), "lsm_power_to_db_ragged_f32")
-            self.spikes_from_db_ragged(db, cols.contiguous(), t.to(torch.int32).contiguous(), raster_out=raster)
+            self.spikes_from_db_ragged(db, cols.contiguous(), t.to(torch.int32).contiguous(), raster_out=raster, mask=mask)
         return raster, steps
 
 
@@ -1298,6 +1315,24 @@ class NoiseMixer:
         filled, clamped to the clip) and ``scale``; None is 0, 0, 0 and 1.  ``out``: a caller-owned contiguous float32
         (n, L) tensor on the device, never ``audio``.  ``want_gain``: returns ``(out, gain (n), powers (n, 2))``, float64 on
         the device -- g and {Px, Pv} of SPEC.md §1.10."""
+        return self._mix(audio, None, snr_db, rows, offsets, shift, scale, out, want_gain)
+
+    def mix_ragged(self, x, lengths, snr_db, rows, offsets, shift, scale, out=None):
+        """`mix` on rows of a stride whose clips have their own lengths (SPEC.md §1.16, `lsm_mix_ragged_f32`): ``x`` (n, L)
+        float32, clip b is the first ``lengths[b]`` samples of its row -- an int32 device tensor (never read back) or a host
+        sequence; the kernel clamps a length into [0, L] and the shift to the clip's own length, so a `mix_plan` drawn for the
+        listing is taken as it is.  The SNR is that of the clip alone; what lies behind a clip influences nothing and comes
+        back as +0.0.  Returns the float32 (n, L) tensor on the device (``out`` where given)."""
+        n = len(x)
+        if torch.is_tensor(lengths):
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
+                raise ValueError(f"lengths must be an int32 ({n},) tensor or {n} host integers")
+        else:
+            lengths = torch.from_numpy(_per_clip(np.asarray(lengths), n, np.int32, "lengths"))
+        return self._mix(x, lengths, snr_db, rows, offsets, shift, scale, out, False)
+
+    def _mix(self, audio, lengths, snr_db, rows, offsets, shift, scale, out, want_gain):
+        """`mix` (``lengths`` None: `lsm_mix_f32`) and `mix_ragged` (an int32 tensor: `lsm_mix_ragged_f32`)."""
         audio, ratio, rows, offsets, shift, scale = mix_arguments(audio, snr_db, rows, offsets, shift, scale, out)
         n, L = (int(v) for v in audio.shape)
         if out is not None and out.device != self.device:
@@ -1309,11 +1344,15 @@ class NoiseMixer:
             gain = torch.empty(n, dtype=torch.float64, device=self.device) if want_gain else None
             powers = torch.empty((n, 2), dtype=torch.float64, device=self.device) if want_gain else None
             args = [self._up(a) for a in (rows, offsets, shift, scale, ratio)]
-            _lib.check(self.lib.lsm_mix_f32(
-                _dev(audio), n, L, _dev(self.noise), self.n_rows, self.noise_len,
-                *(_dev(a) if a is not None else None for a in args), _dev(out),
-                _dev(gain) if want_gain else None, _dev(powers) if want_gain else None,
-                torch.cuda.current_stream(self.device).cuda_stream), "lsm_mix_f32")
+            if lengths is None:
+                fn, name, head = self.lib.lsm_mix_f32, "lsm_mix_f32", [_dev(audio), n, L]
+            else:
+                lengths = lengths.to(self.device, non_blocking=True).contiguous()
+                fn, name, head = self.lib.lsm_mix_ragged_f32, "lsm_mix_ragged_f32", [_dev(audio), n, L, _dev(lengths)]
+            _lib.check(fn(*head, _dev(self.noise), self.n_rows, self.noise_len,
+                          *(_dev(a) if a is not None else None for a in args), _dev(out),
+                          _dev(gain) if want_gain else None, _dev(powers) if want_gain else None,
+                          torch.cuda.current_stream(self.device).cuda_stream), name)
         return (out, gain, powers) if want_gain else out
 
 
@@ -1832,6 +1871,25 @@ def mask_plan(n_clips: int, n_filters: int, time_bins: int, freq_masks: int = 0,
     ``randint(0, time_width + 1, (n, time_masks))``, and (4) the time positions, ``floor(random_sample((n, time_masks)) *
     (time_bins - width + 1))``; (5) ``u = random_sample(n)``: a clip with ``u >= prob`` gets no mask.  Band ``k`` of a clip
     covers ``[position, position + width)``."""
+    return _drawn_masks(n_clips, n_filters, time_bins, None, freq_masks, freq_width, time_masks, time_width, prob, seed)
+
+
+def mask_plan_ragged(bins, n_filters: int, time_bins: int, freq_masks: int = 0, freq_width: int = 0, time_masks: int = 0,
+                     time_width: int = 0, prob: float = 1.0, seed: int = 42) -> MaskPlan:
+    """`mask_plan` for a listing whose clip b has ``bins[b]`` of the launch's ``time_bins`` bins (SPEC.md §1.16): the same
+    generator, the same five draws in the same order, the words at the launch's strides.  Only the time bands differ: a
+    band of drawn width ``w`` covers ``w_eff = min(w, T_b)`` bins from ``floor(u * (T_b - w_eff + 1))``, so every band lies
+    inside the clip's own bins; a clip of 0 bins gets no time bits.  With every ``bins[b] == time_bins`` the plan is
+    `mask_plan`'s, word for word."""
+    bins = np.asarray(bins)
+    if bins.ndim != 1 or bins.dtype.kind not in "iu" or (bins < 0).any() or (bins > int(time_bins)).any():
+        raise ValueError(f"bins must be a 1-D integer array with every entry in [0, {time_bins}]")
+    return _drawn_masks(len(bins), n_filters, time_bins, bins.astype(np.int64), freq_masks, freq_width, time_masks, time_width,
+                        prob, seed)
+
+
+def _drawn_masks(n_clips, n_filters, time_bins, bins, freq_masks, freq_width, time_masks, time_width, prob, seed) -> MaskPlan:
+    """`mask_plan` (``bins`` None) and `mask_plan_ragged`: one copy of the refusals and the draws."""
     n, F, Tb, p = int(n_clips), int(n_filters), int(time_bins), float(prob)
     nf, wf, nt, wt = int(freq_masks), int(freq_width), int(time_masks), int(time_width)
     if n < 0 or F < 1 or Tb < 1 or nf < 0 or nt < 0 or wf < 0 or wt < 0 or not 0.0 <= p <= 1.0:
@@ -1844,7 +1902,10 @@ def mask_plan(n_clips: int, n_filters: int, time_bins: int, freq_masks: int = 0,
     f_w = rs.randint(0, wf + 1, size=(n, nf)).astype(np.int64)
     f_p = np.floor(rs.random_sample((n, nf)) * (F - f_w + 1)).astype(np.int64)
     t_w = rs.randint(0, wt + 1, size=(n, nt)).astype(np.int64)
-    t_p = np.floor(rs.random_sample((n, nt)) * (Tb - t_w + 1)).astype(np.int64)
+    t_u = rs.random_sample((n, nt))
+    if bins is not None:
+        t_w = np.minimum(t_w, bins[:, None])
+    t_p = np.floor(t_u * ((Tb if bins is None else bins[:, None]) - t_w + 1)).astype(np.int64)
     u = rs.random_sample(n)
     freq, time = mask_words(f_p, f_w, F), mask_words(t_p, t_w, Tb)
     freq[u >= p] = 0

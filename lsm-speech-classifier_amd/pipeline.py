@@ -54,8 +54,9 @@ def step_fused_supported(fe, net, n_clips: int, form: str = "plain") -> bool:
     a gammatone front end of 97..128 filters without redundancy, and a reservoir whose pipeline launch is the dense-row
     kernel with 4 waves per clip and coloured input masks.  Anything else takes the two launches.  `form`: "plain";
     "masked" (`step_fused(mask=...)`: wherever the plain step is served); "ragged" (`step_fused_ragged`: additionally a front
-    end that takes ragged batches, `frontend.ragged_refusal`) -- `lsm_step_fused_form_supported`."""
-    if form not in STEP_FORMS:
+    end that takes ragged batches, `frontend.ragged_refusal`) -- `lsm_step_fused_form_supported`; "ragged-masked"
+    (`step_fused_ragged(mask=...)`: wherever the ragged step is served) -- `lsm_step_fused_ragged_masked_supported`."""
+    if form not in STEP_FORMS and form != "ragged-masked":
         raise ValueError(f"form must be one of {tuple(STEP_FORMS)}, got {form!r}")
     if getattr(fe, "filterbank", None) != "gammatone" or not fe.will_fuse() or int(n_clips) < 1:
         return False
@@ -65,8 +66,15 @@ def step_fused_supported(fe, net, n_clips: int, form: str = "plain") -> bool:
                                                       len(fe.thresholds), fe.redundancy, fe.coef_flags))
     else:
         from .frontend import ragged_refusal
-        if form == "ragged" and (ragged_refusal(fe.n_samples, fe.time_bins) or fe.ncols != fe.time_bins - 2):
+        if form != "masked" and (ragged_refusal(fe.n_samples, fe.time_bins) or fe.ncols != fe.time_bins - 2):
             return False
+        if form == "ragged-masked":
+            rc = int(_lib.load().lsm_step_fused_ragged_masked_supported(
+                net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop, fe.time_bins, len(fe.thresholds), fe.redundancy,
+                fe.coef_flags))
+            if rc < 0:
+                _lib.check(rc, "lsm_step_fused_ragged_masked_supported")
+            return rc == 1
         rc = int(_lib.load().lsm_step_fused_form_supported(net._handle, int(n_clips), fe.n_filters, fe.nwin, fe.hop,
                                                            fe.time_bins, len(fe.thresholds), fe.redundancy, fe.coef_flags,
                                                            STEP_FORMS[form]))
@@ -120,20 +128,25 @@ def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=N
     return feats
 
 
-def step_fused_ragged(fe, net, audio, bins, feature_keys=None, stats_out=None, features_out=None, workspace=None):
+def step_fused_ragged(fe, net, audio, bins, feature_keys=None, stats_out=None, features_out=None, workspace=None, mask=None):
     """One step on clips of different lengths in ONE launch on the current stream (`lsm_step_fused_ragged_f64`): clip b is the
     first ``160 * bins[b]`` samples of its row and runs ``bins[b] * n_thr`` reservoir steps; its feature row is, bit for bit,
     that of ``raster, steps = fe.encode_ragged(audio, bins)`` followed by ``net.run_batch(raster, feature_keys,
     lengths=steps)[0]``.  `bins`: B host integers, each 0 or 3 .. time_bins (checked), or an int32 device tensor (not read:
     the kernel clamps it), as `encode_ragged` takes them.  A clip of 0 bins leaves its row of `features_out` and of
-    `stats_out` as it was (a row of a tensor allocated here is then uninitialised).  The other parameters are `step_fused`'s;
-    masks are not offered.  Needs `step_fused_supported(fe, net, B, form="ragged")`."""
+    `stats_out` as it was (a row of a tensor allocated here is then uninitialised).  The other parameters are `step_fused`'s.
+    `mask`: a `frontend.MaskPlan` at the launch's strides whose time bits name the bins of each clip's own length (SPEC.md
+    §1.16, `frontend.mask_plan_ragged`): the launch is `lsm_step_fused_ragged_masked_f64` and the rows are those of
+    ``fe.encode_ragged(audio, bins, mask=mask)`` followed by the ragged run; None makes exactly the unmasked call.  Needs
+    `step_fused_supported(fe, net, B, form="ragged")` (with a mask: ``form="ragged-masked"``)."""
     from . import _lib
-    from .frontend import checked_ragged_bins, ragged_refusal, threshold_tables
+    from .frontend import checked_mask, checked_ragged_bins, ragged_refusal, threshold_tables, upload_mask
     from .snn import _dev, _host
     why = ragged_refusal(fe.n_samples, fe.time_bins)
     if why:
         raise ValueError(why)
+    if mask is not None:
+        checked_mask(mask, 1 if getattr(audio, "ndim", 2) == 1 else len(audio), fe.n_filters, fe.time_bins)
     checked_ragged_bins(bins, 1 if getattr(audio, "ndim", 2) == 1 else len(audio), fe.time_bins)     # before any device work
     audio, B, keys, key_ids, shape = _step_outputs(fe, net, audio, feature_keys, stats_out, features_out)
     on, off = threshold_tables(fe.thresholds, fe.gap, np.float64)
@@ -141,10 +154,15 @@ def step_fused_ragged(fe, net, audio, bins, feature_keys=None, stats_out=None, f
         bins_dev = fe._device_bins(bins, B)
         feats = features_out if features_out is not None else torch.empty(shape, dtype=torch.float32, device=fe.device)
         ws, ws_bytes = fe._workspace_for(B, workspace)
-        _lib.check(fe.lib.lsm_step_fused_ragged_f64(
-            net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
-            _dev(bins_dev), _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids),
-            len(keys), _dev(feats), _dev(stats_out), fe._stream()), "lsm_step_fused_ragged_f64")
+        args = (net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
+                _dev(bins_dev), _host(on), _host(off), len(on), fe.redundancy, _dev(ws), ws_bytes, fe.coef_flags, _host(key_ids),
+                len(keys), _dev(feats), _dev(stats_out))
+        if mask is None:
+            _lib.check(fe.lib.lsm_step_fused_ragged_f64(*args, fe._stream()), "lsm_step_fused_ragged_f64")
+        else:
+            fm, tm = upload_mask(mask, B, fe.n_filters, fe.time_bins, fe.device)
+            _lib.check(fe.lib.lsm_step_fused_ragged_masked_f64(*args, _dev(fm), _dev(tm), fe._stream()),
+                       "lsm_step_fused_ragged_masked_f64")
     return feats
 
 
@@ -834,7 +852,8 @@ def _trimmed_listing(trim, audio: np.ndarray, bins: np.ndarray, fe, device, batc
     return rows, kept.cpu().numpy()
 
 
-def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024, fused: bool = False, trim=None):
+def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024, fused: bool = False, trim=None,
+                             corrupt=None, reverb=None, mask=None):
     """Utterances of different lengths, each one clip: ``utterances``, a list of n 1-D float32 arrays of 321 to
     ``fe.n_samples`` samples, -> (n, n_feat) float32 device tensor in the input order.  Row r holds the features of utterance
     r taken alone: its own ``ceil(len / 160)`` time bins through the front end of that length (its normalisation range is the
@@ -849,9 +868,19 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     ``trim`` (a `frontend.SilenceTrimmer`): every utterance is first cut to its speech on the device (SPEC.md §1.15) and row r
     holds the features of that slice taken alone.  The packed listing is uploaded and trimmed in batches of ``batch``,
     launches only; the trimmed bin counts are then read back ONCE, for the longest-first order and the host lengths the
-    batches take, and the batches run as above on the trimmed rows, gathered on the device.  None: nothing changes."""
-    from .frontend import pack_utterances
+    batches take, and the batches run as above on the trimmed rows, gathered on the device.  None: nothing changes.
+    ``reverb`` = ``(frontend.Reverberator, frontend.ReverbPlan of the n utterances)``, ``corrupt`` = ``(frontend.NoiseMixer,
+    frontend.MixPlan of the n utterances)``, as `features_from_audio` takes them, and ``mask`` = a `frontend.MaskPlan` of the n
+    utterances (`frontend.mask_plan_ragged`) or a callable ``bins -> MaskPlan``, called once with the (trimmed) host bins: the
+    plans are in listing order and every batch takes its longest-first slice of each.  Per batch, on the one stream
+    (SPEC.md §1.16): the trim above, reverberation at the row stride (causal: a clip's own samples are the clip-alone
+    ones, its tail is ignored), the ragged mixer at the clip's (trimmed) length -- the SNR is taken against the speech, and
+    the noise does not decide the trim -- then the ragged front end with the mask.  Row r is the row of that chain on
+    utterance r alone.  With ``fused`` a masked batch takes `step_fused_ragged(mask=...)` where
+    `step_fused_supported(..., form="ragged-masked")` says so.  All three None: nothing changes."""
+    from .frontend import RAGGED_HOP, pack_utterances
     from .snn import _select_keys
+    (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (reverb, corrupt))
     audio, bins = pack_utterances(utterances, fe.time_bins)
     n = len(bins)
     keys, _ = _select_keys(feature_keys)
@@ -859,18 +888,23 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     with torch.cuda.device(net.device):
         if trim is not None:
             audio, bins = _trimmed_listing(trim, audio, bins, fe, net.device, batch)
+        plans = StepPlans(None, reverbs, mixes, mask(bins) if callable(mask) else mask)
+        plans.check_covers(n)
+        chain = AugmentChain(reverb=rv, mixer=mixer)
         feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
         order = np.argsort(-bins.astype(np.int64), kind="stable")
         n_thr = len(fe.thresholds)
         for lo in range(0, n, batch):
             idx = order[lo:lo + batch]
             x = audio[torch.from_numpy(idx).to(net.device)] if torch.is_tensor(audio) else torch.from_numpy(audio[idx]).to(net.device)
-            if fused and step_fused_supported(fe, net, len(idx), "ragged"):
+            p = plans.take(idx)
+            x = chain.apply_ragged(x, bins[idx].astype(np.int64) * RAGGED_HOP, p)
+            if fused and step_fused_supported(fe, net, len(idx), "ragged" if p.mask is None else "ragged-masked"):
                 rows = torch.zeros((len(idx), feats.shape[1]), dtype=torch.float32, device=net.device)
-                step_fused_ragged(fe, net, x, bins[idx], feature_keys, features_out=rows)
+                step_fused_ragged(fe, net, x, bins[idx], feature_keys, features_out=rows, **p.mask_keyword())
                 feats[torch.from_numpy(idx).to(net.device)] = rows
                 continue
-            raster, steps = fe.encode_ragged(x, bins[idx])
+            raster, steps = fe.encode_ragged(x, bins[idx], **p.mask_keyword())
             if fe.n_steps > net.max_steps(len(idx)):
                 rows = net.run_chunked(raster, feature_keys, lengths=bins[idx].astype(np.int64) * n_thr)[0]
             else:

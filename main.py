@@ -68,10 +68,12 @@ def _mask_args(a):
 
 
 def _variable_length_args(a):
-    """Nothing without --variable-length; the trim flags go along with --trim-silence."""
+    """Nothing without --variable-length; the trim flags go along with --trim-silence, --augment-variable-length where given."""
     if not a.variable_length:
         return []
     out = ["--variable-length", "--max-seconds", str(a.max_seconds)]
+    if getattr(a, "augment_variable_length", False):
+        out += ["--augment-variable-length"]
     if a.trim_silence is not None:
         out += ["--trim-silence", str(a.trim_silence), "--trim-pad-ms", str(a.trim_pad_ms), "--trim-min-ms", str(a.trim_min_ms)]
     return out
@@ -142,7 +144,8 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     speed flags speed_factors, speed_prob and the mask flags freq_masks, freq_mask_width, time_masks, time_mask_width,
     mask_prob: applied to stage 1 and to the in-memory route; variable_length, max_seconds: stage 1 keeps every clip at its
     own length, SPEC.md 1.14, and stage 2 finds the lengths in File 1; trim_silence, trim_pad_ms, trim_min_ms: stage 1 first
-    cuts every such clip to its speech on the GPU, SPEC.md 1.15)."""
+    cuts every such clip to its speech on the GPU, SPEC.md 1.15; augment_variable_length: stage 1 lets the corruption, the
+    reverberation and the mask flags through on such clips, SPEC.md 1.16)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
@@ -151,7 +154,7 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
                               level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0,
                               speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
                               time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0,
-                              trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0)
+                              trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0, augment_variable_length=False)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -246,6 +249,8 @@ if __name__ == "__main__":
                     help="With --variable-length: cut every clip on the GPU to the bins within DB decibels of its loudest (stage 1).")
     ap.add_argument("--trim-pad-ms", type=float, default=30.0, help="With --trim-silence: kept around the speech (stage 1).")
     ap.add_argument("--trim-min-ms", type=float, default=30.0, help="With --trim-silence: shortest trimmed clip (stage 1).")
+    ap.add_argument("--augment-variable-length", action="store_true",
+                    help="With --variable-length: let the corruption flags, --rir-dir and the mask flags through (stage 1).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
@@ -258,4 +263,4 @@ if __name__ == "__main__":
                  speed_prob=a.speed_prob, freq_masks=a.freq_masks, freq_mask_width=a.freq_mask_width,
                  time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob,
                  variable_length=a.variable_length, max_seconds=a.max_seconds, trim_silence=a.trim_silence,
-                 trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms)
+                 trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms, augment_variable_length=a.augment_variable_length)
