@@ -1,0 +1,142 @@
+"""Label new audio with a saved model: ``python classify.py --model PATH FILE.wav ...``
+
+The model file (``main.py --save-model``, ``lsm_speech_classifier_amd.readout.LinearModel``) holds the scaler, the readout
+and every parameter the front end and the reservoir were built from; nothing else is configured here.  By default every
+file is decoded like create_dataset.py decodes it (mono, 16 kHz, one clip of the model's length), goes front end ->
+reservoir -> ``DeviceReadout.score_rows`` on the GPU, and one line is printed per file: name, class name, top-two logit
+margin.  With ``--stream`` every file is one open-ended stream at its own length: it is pushed in chunks through
+``AudioStreamBank.push_scores`` (sliding windows of ``--window-ms`` every ``--hop-ms``), the window labels go through
+``pipeline.debounce`` and the events are printed.  There is no CPU fallback.
+"""
+import argparse
+from pathlib import Path
+
+import numpy as np
+
+
+def class_name(model, label: int) -> str:
+    if label < 0:
+        return "(not a number)"
+    return model.class_names[label] if model.class_names else f"class_{int(model.classes[label])}"
+
+
+def top_two_margin(logits: np.ndarray) -> float:
+    """Largest minus second-largest logit of one row (inf for a single class, nan when a logit is NaN)."""
+    if np.isnan(logits).any():
+        return float("nan")
+    top = np.sort(logits)
+    return float(top[-1] - top[-2]) if len(top) > 1 else float("inf")
+
+
+def window_plan(window_ms: float, hop_ms: float, n_thr: int, segment_steps=None):
+    """``(segment_steps, window_segments, hop_segments)`` for windows of ``window_ms`` every ``hop_ms``: a time bin is 10 ms
+    and ``n_thr`` raster steps; a segment is one hop unless ``segment_steps`` says otherwise, and the window is whole hops."""
+    if hop_ms < 10 or window_ms < hop_ms:
+        raise SystemExit("--hop-ms must be >= 10 (one time bin) and --window-ms >= --hop-ms")
+    hop_bins = int(round(hop_ms / 10.0))
+    S = int(segment_steps) if segment_steps else hop_bins * n_thr
+    window_segments = max(1, int(round(window_ms / 10.0)) * n_thr // S)
+    hop_segments = max(1, hop_bins * n_thr // S)
+    if window_segments * S > 65535:
+        raise SystemExit(f"--window-ms {window_ms}: a window may hold at most 65535 raster steps")
+    return S, window_segments, min(hop_segments, window_segments)
+
+
+def classify_clips(model, files, batch: int = 256):
+    """One line per file: the clip route."""
+    import create_dataset as cd
+    from lsm_speech_classifier_amd import pipeline, readout
+    fe, net = pipeline.pipeline_from_params(model.params)
+    ro = readout.DeviceReadout(model, net.device)
+    clips, names = [], []
+    for f in files:
+        data = cd.load_audio_file(Path(f))
+        if data is None:
+            continue
+        clip = np.zeros(fe.n_samples, dtype=np.float32)
+        clip[:min(len(data), fe.n_samples)] = data[:fe.n_samples]
+        clips.append(clip)
+        names.append(str(f))
+    if not clips:
+        return []
+    rows = pipeline.features_from_audio(np.stack(clips), fe, net, model.feature_keys, batch=batch, device_out=True)
+    logits, labels = ro.score_rows(rows)
+    logits, labels = logits.cpu().numpy(), labels.cpu().numpy()
+    out = []
+    for name, lg, lab in zip(names, logits, labels):
+        out.append((name, class_name(model, int(lab)), top_two_margin(lg)))
+        print(f"{name}\t{out[-1][1]}\t{out[-1][2]:.6g}")
+    return out
+
+
+def classify_streams(model, files, window_ms: float, hop_ms: float, hold: int, background: int, chunk_ms: float = 500.0):
+    """The stream route: every file one stream, events ``(file, time of the window's end in ms, class name)``."""
+    import create_dataset as cd
+    import torch
+    from lsm_speech_classifier_amd import frontend, pipeline, readout
+    fe, net = pipeline.pipeline_from_params(model.params)
+    ro = readout.DeviceReadout(model, net.device)
+    n_thr = len(fe.thresholds)
+    S, K, H = window_plan(window_ms, hop_ms, n_thr)
+    hop = frontend.STREAM_HOP
+    out = []
+    for f in files:
+        rate, data = cd._decode_wav(Path(f))
+        if rate != cd.SAMPLE_RATE:
+            from math import gcd
+            from scipy.signal import resample_poly
+            g = gcd(int(rate), cd.SAMPLE_RATE)
+            data = resample_poly(data, cd.SAMPLE_RATE // g, int(rate) // g).astype(np.float32)
+        n_hops = len(data) // hop
+        if n_hops < 1:
+            continue
+        audio = np.ascontiguousarray(data[:n_hops * hop], dtype=np.float32)[None, :]
+        # the streamed front ends normalise by a fixed range: calibrated on the file's own whole clips
+        whole = -(-audio.shape[1] // fe.n_samples) * fe.n_samples
+        calib = np.zeros(whole, dtype=np.float32)
+        calib[:audio.shape[1]] = audio[0]
+        calib = calib.reshape(-1, fe.n_samples)
+        if fe.filterbank == "gammatone":
+            front = frontend.GammatoneStream(fe.n_filters, 1, fe.db_range(calib), thresholds=fe.thresholds, gap=fe.gap,
+                                             redundancy=fe.redundancy, device=fe.device)
+        else:
+            front = frontend.MelStream(fe.n_filters, 1, fe.mel_db_range(calib), thresholds=fe.thresholds, gap=fe.gap,
+                                       redundancy=fe.redundancy, device=fe.device)
+        bank = pipeline.AudioStreamBank(front, net, S, K, H, model.feature_keys, readout=ro)
+        chunk = max(1, int(round(chunk_ms / 10.0))) * hop
+        state = None
+        for at in range(0, audio.shape[1], chunk):
+            _, labels, counts = bank.push_scores(audio[:, at:at + chunk])
+            events, state = pipeline.debounce(labels.cpu().numpy(), counts, state, hold, background)
+            for _, w, lab in events:
+                # window w ends after (w * H + K) segments of S steps; a step is 10 / n_thr ms (plus the front end's latency)
+                t_ms = (w * H + K) * S * 10.0 / n_thr
+                out.append((str(f), t_ms, class_name(model, lab)))
+                print(f"{f}\t{t_ms:.0f} ms\t{out[-1][2]}")
+        torch.cuda.synchronize()
+    return out
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Label wav files with a saved model (main.py --save-model).")
+    ap.add_argument("--model", type=str, required=True, help="Model file written by main.py --save-model.")
+    ap.add_argument("files", nargs="+", help="PCM wav files.")
+    ap.add_argument("--stream", action="store_true",
+                    help="Treat every file as an open-ended stream: sliding windows, debounced events.")
+    ap.add_argument("--window-ms", type=float, default=1000.0, help="With --stream: window length (default 1000).")
+    ap.add_argument("--hop-ms", type=float, default=100.0, help="With --stream: a window every this many ms (default 100).")
+    ap.add_argument("--hold", type=int, default=3,
+                    help="With --stream: a label fires after winning this many consecutive windows (default 3).")
+    ap.add_argument("--background", type=int, default=-1,
+                    help="With --stream: label index that never fires (default: none).")
+    return ap
+
+
+if __name__ == "__main__":
+    a = build_parser().parse_args()
+    from lsm_speech_classifier_amd import readout
+    model = readout.LinearModel.load(a.model)
+    if a.stream:
+        classify_streams(model, a.files, a.window_ms, a.hop_ms, a.hold, a.background)
+    else:
+        classify_clips(model, a.files)

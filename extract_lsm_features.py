@@ -238,7 +238,7 @@ def run_network_diagnostics(lsm, X_sample_batch):
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
                     num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
-                    time_segments=1, corrupt=None, reverb=None, speed=None, mask=None):
+                    time_segments=1, corrupt=None, reverb=None, speed=None, mask=None, model_out=None):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -271,7 +271,10 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     the GPU (SPEC.md 1.12), ahead of `reverb`.
 
     `mask` = what `create_dataset.mask_from_args` returns: frequency bands and time spans of every clip's normalised spectrogram
-    are zeroed inside the spike encoder (SPEC.md 1.13), by a plan drawn for all n clips in listing order."""
+    are zeroed inside the spike encoder (SPEC.md 1.13), by a plan drawn for all n clips in listing order.
+
+    `model_out` = a path: the model file of `readout.LinearModel` (SPEC.md 6) -- with a PyTorch `readout` the whole file at
+    once, otherwise its front half (scaler and parameters), which train_classifier.py --model-out completes."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
@@ -294,6 +297,7 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     dev = lsm_dist.local_device() if world > 1 else None
     fe = frontend.SpikeFrontEnd(n_filters, filterbank, device=dev)
     check_time_segments(fe.n_steps, time_segments)                  # refused with the reason before any work is done
+    check_model_out(model_out, time_segments)
     stages, plans = {}, {}
     if corrupt is not None:
         stages["mixer"], plans["mix"] = frontend.NoiseMixer(corrupt[0], device=dev), corrupt[1]
@@ -338,9 +342,14 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     lsm_dist.finish()
     if rank != 0:
         return
+    model = None
+    if model_out:
+        model = dict(path=model_out, feature_keys=keys, n_out=lsm.num_output_neurons,
+                     params=pipeline.model_params(fe, params, feature_set=feature_set, multiplier=float(multiplier),
+                                                  time_segments=1))
     if on_device:
         return _device_readout(X_train_dev, X_test_dev, y_train, y_test, readout, feature_set,
-                               leak_variance_divisor, class_names)
+                               leak_variance_divisor, class_names, model)
     X_train_feat, X_test_feat = X_train_dev.cpu().numpy(), X_test_dev.cpu().numpy()
     scaler = StandardScaler()
     X_train_scaled = scaler.fit_transform(X_train_feat)
@@ -349,10 +358,28 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
                         X_test_features=X_test_scaled, y_test=y_test, feature_set=feature_set,
                         leak_variance_divisor=leak_variance_divisor)
     print(f"Extraction complete. Features saved to '{FEATURE_FILE}'")
+    if model:
+        write_model_front(scaler, **model)
+
+
+def check_model_out(model_out, time_segments) -> None:
+    """``--model-out`` saves a model of one SPEC.md 4 row per clip: with K > 1 time segments a row is K rows side by side,
+    which the readout launches (SPEC.md 6) do not score."""
+    if model_out and int(time_segments) != 1:
+        raise ValueError("--model-out needs --time-segments 1: the saved model scores one feature row per clip or window")
+
+
+def write_model_front(scaler, path, feature_keys, n_out, params) -> None:
+    """The front half of the model file (`readout.LinearModel`): the scaler's mean and scale, the feature keys and every
+    parameter the front end and the reservoir were built from.  train_classifier.py --model-out adds the readout."""
+    from lsm_speech_classifier_amd import readout as ro
+    ro.save_model_file(path, dict(mean=scaler.mean_, scale=scaler.scale_, feature_keys=feature_keys, n_out=n_out,
+                                  params=params))
+    print(f"Model front half (scaler, parameters) saved to '{path}'")
 
 
 def _device_readout(X_train_dev, X_test_dev, y_train, y_test, readout, feature_set, leak_variance_divisor,
-                    class_names=None):
+                    class_names=None, model_file=None):
     """extract_lsm_features.py:199-212 + train_classifier.py:36-52 of the reference without the host round trip:
     scaler, readout and predictions run on the tensors' device; File 2 gets the scaled arrays (one copy each)."""
     import torch
@@ -371,15 +398,25 @@ def _device_readout(X_train_dev, X_test_dev, y_train, y_test, readout, feature_s
                         X_test_features=Xte.cpu().numpy(), y_test=y_test, feature_set=feature_set,
                         leak_variance_divisor=leak_variance_divisor)
     print(f"Extraction complete. Features saved to '{FEATURE_FILE}'")
+    if model_file:                                        # the whole model file at once: scaler, readout, parameters
+        ro.LinearModel.from_fitted(scaler, model, model_file["feature_keys"], model_file["n_out"],
+                                   tc.names_of_classes(model.classes_.cpu().numpy(), class_names),
+                                   model_file["params"]).save(model_file["path"])
+        print(f"Model saved to '{model_file['path']}'")
     return tc.report_results(y_train, y_test, y_pred, class_names)
 
 
 def main(feature_set: str, multiplier: float, leak_variance_divisor: float = None, *, num_neurons=None,
-         num_output_neurons=None, small_world_k=None, seed=None, time_segments=None):
+         num_output_neurons=None, small_world_k=None, seed=None, time_segments=None, model_out=None, front_end=None):
     """The reference's three arguments; the keyword-only ones expose the module constants the reference
     hard-codes (NUM_NEURONS, NUM_OUTPUT_NEURONS, SMALL_WORLD_K, the NumPy seed), None = the reference's value.
-    `time_segments` = K > 1: features per time segment, K times the columns (None or 1 = the reference's whole-clip rows)."""
+    `time_segments` = K > 1: features per time segment, K times the columns (None or 1 = the reference's whole-clip rows).
+    `model_out` = a path: the front half of the model file (`write_model_front`); File 1 does not say which front end wrote
+    it, so `front_end` = ``(filterbank, n_filters)`` is needed with it."""
     time_segments = 1 if time_segments is None else int(time_segments)
+    check_model_out(model_out, time_segments)
+    if model_out and front_end is None:
+        raise ValueError("--model-out needs --filterbank and --n-filters: File 1 does not say which front end wrote it")
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist
@@ -443,6 +480,25 @@ def main(feature_set: str, multiplier: float, leak_variance_divisor: float = Non
                         X_test_features=X_test_scaled, y_test=y_test, feature_set=feature_set,
                         leak_variance_divisor=leak_variance_divisor)
     print(f"Extraction complete. Features saved to '{FEATURE_FILE}'")
+    if model_out:
+        from lsm_speech_classifier_amd import frontend, pipeline
+        fe = frontend.SpikeFrontEnd(int(front_end[1]), front_end[0])
+        clip = np.asarray(X_train[0])
+        if fe.n_channels != clip.shape[0] or (steps_train is None and fe.n_steps != clip.shape[1]):
+            raise ValueError(f"the dataset's clips are {clip.shape}, a {front_end[0]} front end of {front_end[1]} filters "
+                             f"gives ({fe.n_channels}, {fe.n_steps})")
+        write_model_front(scaler, model_out, keys, lsm.num_output_neurons,
+                          pipeline.model_params(fe, params, feature_set=feature_set, multiplier=float(multiplier),
+                                                time_segments=1))
+
+
+def add_model_flags(ap):
+    ap.add_argument("--model-out", type=str, default=None,
+                    help="Write the front half of a model file here: scaler, feature keys and every parameter of the front "
+                         "end and the reservoir (train_classifier.py --model-out adds the readout; classify.py reads it).")
+    ap.add_argument("--filterbank", type=str, default=None, choices=["mel", "gammatone"],
+                    help="With --model-out: the filterbank the dataset file was written with.")
+    ap.add_argument("--n-filters", type=int, default=None, help="With --model-out: its number of filters.")
 
 
 def add_reservoir_flags(ap):
@@ -469,7 +525,11 @@ if __name__ == "__main__":
     ap.add_argument("--leak-variance-divisor", type=float, default=None)
     add_reservoir_flags(ap)
     add_time_segments_flag(ap)
+    add_model_flags(ap)
     a = ap.parse_args()
+    if a.model_out and (a.filterbank is None or a.n_filters is None):
+        ap.error("--model-out needs --filterbank and --n-filters: the dataset file does not say which front end wrote it")
     main(feature_set=a.feature_set, multiplier=a.multiplier, leak_variance_divisor=a.leak_variance_divisor,
          num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons, small_world_k=a.small_world_k,
-         seed=a.seed, time_segments=a.time_segments)
+         seed=a.seed, time_segments=a.time_segments, model_out=a.model_out,
+         front_end=(a.filterbank, a.n_filters) if a.model_out else None)

@@ -232,6 +232,16 @@ RAGGED_AUGMENT_SIGS = {
 }
 RAGGED_AUGMENT_SYMBOLS = tuple(RAGGED_AUGMENT_SIGS)
 
+# include/lsm_hip_readout.h (SPEC.md §6): scaler and linear readout over feature rows and over the windows of segment records
+_MODEL = [c_void, c_void, c_void, c_void]           # mean, scale, coef, intercept
+READOUT_SIGS = {
+    "lsm_readout_supported": (c_int, [c_int, c_int, c_int]),
+    "lsm_readout_rows_f32": (c_int, _MODEL + [c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void]),
+    "lsm_readout_windows": (c_int, [c_void] + _MODEL + [c_void, c_int, c_int, c_void, c_int, c_int, c_int, c_void, c_int,
+                                                        c_int, c_void, c_void, c_void]),
+}
+READOUT_SYMBOLS = tuple(READOUT_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -283,7 +293,8 @@ def load():
                               + list(MEL_STREAM_SIGS.items()) + list(RESAMPLE_SIGS.items()) + list(ADAPTIVE_SIGS.items())
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
                               + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
-                              + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items()) + list(RAGGED_AUGMENT_SIGS.items())):
+                              + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items()) + list(RAGGED_AUGMENT_SIGS.items())
+                              + list(READOUT_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

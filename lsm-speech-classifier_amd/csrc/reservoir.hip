@@ -6,6 +6,7 @@
 #include "lif_dense.h"
 #include "lif_ring.h"
 #include "lif_pair.h"
+#include "reservoir_facts.h"
 
 #include <algorithm>
 #include <climits>
@@ -122,6 +123,9 @@ struct lsm_reservoir {
 };
 
 static size_t ring_lds_bytes(const lsm_reservoir *h, const RingVariant &v, int T);
+
+// reservoir_facts.h: for readout.hip, whose window launch folds this reservoir's records
+ReservoirRecordFacts reservoir_record_facts(const lsm_reservoir *h) { return {h->n_out, h->burst_isi_max, h->device}; }
 
 static bool has_ring(const lsm_reservoir *h)
 {

@@ -972,6 +972,77 @@ def stream_window_plan(seen, new, window_segments: int, hop_segments: int = 1):
     return n_windows, keep
 
 
+def model_params(fe, sim_params, **more) -> dict:
+    """Every parameter the front end ``fe`` (``frontend.SpikeFrontEnd``) and a reservoir of ``sim_params``
+    (``reservoir.SimulationParams``, with the weight actually used in ``mean_weight``) were built from, as the plain dict a
+    ``readout.LinearModel`` carries in its file; ``more``: what the caller adds (feature_set, multiplier, time_segments)."""
+    p = dict(filterbank=fe.filterbank, n_filters=fe.n_filters, redundancy=fe.redundancy,
+             thresholds=[float(t) for t in fe.thresholds], gap=fe.gap, time_bins=fe.time_bins, n_samples=fe.n_samples,
+             n_channels=fe.n_channels)
+    for name in ("num_neurons", "num_output_neurons", "mean_weight", "weight_variance", "membrane_threshold",
+                 "leak_coefficient", "refractory_period", "small_world_graph_p", "small_world_graph_k", "seed"):
+        p[name] = getattr(sim_params, name)
+    lvd = sim_params.leak_variance_divisor
+    p["leak_variance_divisor"] = None if lvd is None else float(lvd)
+    p.update(more)
+    return p
+
+
+def pipeline_from_params(params: dict, device=None):
+    """``(fe, net)`` rebuilt from ``model_params``' dict: the same front end and, the wiring being a function of the
+    parameters and the seed alone (SPEC.md §2), the same reservoir -- their feature rows equal the training run's byte for
+    byte."""
+    from . import frontend
+    from .snn import SNN, SimulationParams
+    fe = frontend.SpikeFrontEnd(params["n_filters"], params["filterbank"], device=device, redundancy=params["redundancy"],
+                                thresholds=params["thresholds"], gap=params["gap"], time_bins=params["time_bins"],
+                                n_samples=params["n_samples"])
+    sim = SimulationParams(**{name: params[name] for name in (
+        "num_neurons", "mean_weight", "num_output_neurons", "membrane_threshold", "leak_coefficient", "refractory_period",
+        "small_world_graph_p", "small_world_graph_k", "leak_variance_divisor", "weight_variance", "seed")})
+    return fe, SNN(sim, n_channels=params["n_channels"], device=fe.device)
+
+
+def _checked_readout(readout, net, feature_keys):
+    """A bank's ``readout`` (``readout.DeviceReadout`` or None) scores the rows the bank would return: same keys, same
+    output neurons, same device."""
+    if readout is None:
+        return None
+    from .snn import _select_keys
+    m = readout.model
+    if (list(m.feature_keys) != list(_select_keys(feature_keys)[0]) or m.n_out != net.num_output_neurons
+            or readout.device != net.device):
+        raise ValueError(f"the readout was fitted on {m.feature_keys} x {m.n_out} output neurons on {readout.device}; the bank "
+                         f"returns {_select_keys(feature_keys)[0]} x {net.num_output_neurons} on {net.device}")
+    return readout
+
+
+def debounce(labels, counts, state, hold: int, background: int):
+    """Events from the labels of consecutive pushes, host integers only.  ``labels`` (n_streams, W) and ``counts``
+    (n_streams) as ``push_scores`` returns them (arrays on the host); ``state``: the dict a previous call returned, or None
+    at the streams' start.  Stream b emits ``(b, window index, label)`` at the window in which the same label -- neither
+    ``background`` nor -1 -- has won ``hold`` consecutive windows, counted across pushes, and nothing more until its label
+    changes.  Window indices count from the stream's start.  Returns ``(events, state)``."""
+    labels, counts = np.asarray(labels), np.asarray(counts)
+    n = int(counts.shape[0])
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError(f"hold = {hold} must be >= 1")
+    if state is None:
+        state = dict(last=np.zeros(n, dtype=np.int64), run=np.zeros(n, dtype=np.int64), seen=np.zeros(n, dtype=np.int64))
+    last, run, seen = state["last"].copy(), state["run"].copy(), state["seen"].copy()
+    events = []
+    for b in range(n):
+        for j in range(int(counts[b])):
+            lab = int(labels[b, j])
+            run[b] = run[b] + 1 if (run[b] > 0 and lab == last[b]) else 1
+            last[b] = lab
+            if run[b] == hold and lab != background and lab != -1:
+                events.append((b, int(seen[b]), lab))
+            seen[b] += 1
+    return events, dict(last=last, run=run, seen=seen)
+
+
 class CarryBuffer:
     """What ``n_streams`` streams carry from one push to the next: per stream up to ``cap`` trailing items (records, raster
     steps -- tensors of shape ``item``) in ``kept`` (n_streams, cap, *item), left-aligned and zero-padded, and how many of
@@ -1020,8 +1091,9 @@ class StreamBank:
     the segments seen; a stream has no length limit."""
 
     def __init__(self, net, n_streams: int, segment_steps: int, window_segments: int, hop_segments: int = 1,
-                 feature_keys=None):
+                 feature_keys=None, readout=None):
         self.net = net
+        self.readout = _checked_readout(readout, net, feature_keys)      # readout.DeviceReadout or None: push_scores
         self.n_streams = int(n_streams)
         self.S, self.K, self.H = int(segment_steps), int(window_segments), int(hop_segments)
         if self.n_streams < 1 or self.S < 1:
@@ -1052,6 +1124,32 @@ class StreamBank:
         (n_streams, W, n_feat) on the device and ``counts`` (int64, host) -- ``rows[b, j]`` for ``j < counts[b]`` are the
         windows of stream b this push completed, in order; rows past a count are zeros.  A push longer than the longest
         launch the plan accepts is cut at segment boundaries."""
+        from .snn import _select_keys
+        n_feat = len(_select_keys(self.feature_keys)[0]) * self.net.num_output_neurons
+        return self._push(rasters, segments,
+                          lambda joined, have: self.net.segment_features(joined, self.S, self.feature_keys, self.K, self.H,
+                                                                         segments=have),
+                          lambda: torch.zeros((self.n_streams, 0, n_feat), dtype=torch.float32, device=self.net.device))
+
+    def push_scores(self, rasters, segments):
+        """``push`` that scores the windows it completes instead of returning their rows (SPEC.md §6): returns
+        ``(logits, labels, counts)`` -- float64 (n_streams, W, n_classes), int32 (n_streams, W) and ``push``'s ``counts``;
+        ``logits[b, j]``, ``labels[b, j]`` for ``j < counts[b]`` are what ``readout.score_rows`` gives on ``push``'s
+        ``rows[b, j]``, byte for byte, from one launch that writes no feature row; past a count, zeros and -1."""
+        if self.readout is None:
+            raise ValueError("push_scores needs a readout: StreamBank(..., readout=readout.DeviceReadout(model, device))")
+        ro = self.readout
+        out = self._push(rasters, segments,
+                         lambda joined, have: ro.score_windows(self.net, joined, self.S, self.K, self.H, segments=have),
+                         lambda: (torch.zeros((self.n_streams, 0, ro.model.n_classes), dtype=torch.float64,
+                                              device=self.net.device),
+                                  torch.zeros((self.n_streams, 0), dtype=torch.int32, device=self.net.device)))
+        (logits, labels), counts = out
+        return logits, labels, counts
+
+    def _push(self, rasters, segments, windows_of, nothing):
+        """One push: ``windows_of(joined, have)`` is what the caller wants of every stream's joined records (feature rows,
+        scores), ``nothing()`` the same for a push that delivers no segment.  Returns ``(that, counts)``."""
         net, S, K, H = self.net, self.S, self.K, self.H
         if isinstance(rasters, np.ndarray):
             rasters = torch.from_numpy(np.ascontiguousarray(rasters, dtype=np.uint8))
@@ -1060,10 +1158,9 @@ class StreamBank:
         Gp = int(rasters.shape[2]) // S
         new = net._host_segments(np.asarray(segments), self.n_streams, Gp)
         counts, keep = stream_window_plan(self.seen, new, K, H)
-        from .snn import _select_keys, ragged_chunks
-        n_feat = len(_select_keys(self.feature_keys)[0]) * net.num_output_neurons
+        from .snn import ragged_chunks
         if Gp == 0 or int(new.max()) == 0:
-            return torch.zeros((self.n_streams, 0, n_feat), dtype=torch.float32, device=net.device), counts
+            return nothing(), counts
         chunk = net._max_steps_cached(self.n_streams) // S * S
         if chunk < 1:
             raise ValueError(f"segment_steps = {S} exceeds the longest launch the plan accepts for {self.n_streams} streams")
@@ -1075,7 +1172,7 @@ class StreamBank:
                 fresh[:, t0 // S:(t0 + n) // S] = rec
             # per stream: its kept records, then the new ones, contiguous from column 0 (the start of its next window)
             joined, have = self.tail.join(fresh, new)
-            rows = net.segment_features(joined, S, self.feature_keys, K, H, segments=have)
+            rows = windows_of(joined, have)
             self.tail.keep(joined, have, keep)
         self.seen += new
         return rows, counts
@@ -1092,7 +1189,7 @@ class AudioStreamBank:
     stream's room first (SPEC.md §1.11): behind the resampler, in front of the mixer."""
 
     def __init__(self, gt_stream, net, segment_steps: int, window_segments: int, hop_segments: int = 1, feature_keys=None,
-                 resampler=None, mixer=None, reverb=None):
+                 resampler=None, mixer=None, reverb=None, readout=None):
         # the refusals come before anything touches a device
         streamed = getattr(gt_stream, "filterbank", None) == "gammatone" or getattr(gt_stream, "streamed", None) is True
         if not streamed or not hasattr(gt_stream, "push"):
@@ -1120,6 +1217,8 @@ class AudioStreamBank:
         self.stages = [stage for stage in (reverb, mixer) if stage is not None]
         self.n_streams = int(gt_stream.n_streams)
         self.bank = StreamBank(net, self.n_streams, S, window_segments, hop_segments, feature_keys)
+        if readout is not None:
+            self.bank.readout = _checked_readout(readout, net, feature_keys)
         # time-major: an item is one raster step, (C,)
         self.pending = CarryBuffer(self.n_streams, S - n_thr, (gt_stream.n_channels,), torch.uint8, net.device)
 
@@ -1142,6 +1241,17 @@ class AudioStreamBank:
         With a ``resampler`` (``frontend.ResampleStream``): ``audio`` (n_streams, U * unit_in) float32 or int16 at the
         resampler's input rate and ``hops`` per-stream UNIT counts in [0, U] (None: U everywhere); stream b's first
         ``hops[b] * unit_in`` samples are resampled and reach the front end as ``hops[b] * unit_hops`` hops."""
+        return self.bank.push(*self._whole_segments(audio, hops))
+
+    def push_scores(self, audio, hops=None):
+        """``push`` with ``StreamBank.push_scores`` behind the front end: ``(logits, labels, counts)`` of the windows this
+        push completed."""
+        if getattr(self.bank, "readout", None) is None:
+            raise ValueError("push_scores needs a readout: AudioStreamBank(..., readout=readout.DeviceReadout(model, device))")
+        return self.bank.push_scores(*self._whole_segments(audio, hops))
+
+    def _whole_segments(self, audio, hops):
+        """A push through the front end: ``(rasters, segments)`` as ``StreamBank.push`` takes them."""
         S = self.S
         if self.resampler is not None:
             audio, hops = self._resampled(audio, hops)
@@ -1155,7 +1265,7 @@ class AudioStreamBank:
             segs = total // S
             self.pending.keep(run, total, total - segs * S)
             joined = run[:, :int(segs.max()) * S].transpose(1, 2).contiguous()
-        return self.bank.push(joined, segs)
+        return joined, segs
 
     def _through(self, stage, audio, hops):
         """The first ``hops[b]`` hops of every row through ``stage`` (the reverberator, the mixer); the rows keep their length."""

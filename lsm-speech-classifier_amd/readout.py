@@ -103,3 +103,204 @@ class LogisticReadout:
 
     def predict(self, X: torch.Tensor) -> torch.Tensor:
         return self.classes_[self.decision_function(X).argmax(dim=1)]
+
+
+# ---- a saved model and its scores on the device (SPEC.md §6, include/lsm_hip_readout.h) ----------------------------------
+MAX_CLASSES = 64
+
+
+def _f64(a) -> "np.ndarray":
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+class LinearModel:
+    """What turns a §4 feature row into a label: the scaler's ``mean`` / ``scale`` (D), the readout's ``coef`` (C, D) and
+    ``intercept`` (C), all float64; ``classes`` (C) int64, the values ``class_of`` maps labels to, and optional
+    ``class_names``; ``feature_keys`` and ``n_out`` with ``D = len(feature_keys) * n_out`` in §4's key-major order; and
+    ``params``, a plain dict of the parameters the front end and the reservoir were built from (numbers, strings, flat lists).
+    The refusals of SPEC.md §6 are made here: the device checks no model value."""
+
+    def __init__(self, mean, scale, coef, intercept, classes, feature_keys, n_out: int, class_names=None, params=None):
+        import numpy as np
+        self.mean, self.scale, self.coef, self.intercept = _f64(mean), _f64(scale), _f64(coef), _f64(intercept)
+        self.classes = np.ascontiguousarray(np.asarray(classes.cpu() if isinstance(classes, torch.Tensor) else classes,
+                                                       dtype=np.int64))
+        self.feature_keys = [str(k) for k in feature_keys]
+        self.n_out = int(n_out)
+        self.class_names = None if class_names is None else [str(n) for n in class_names]
+        self.params = dict(params or {})
+        D = len(self.feature_keys) * self.n_out
+        C = self.coef.shape[0] if self.coef.ndim == 2 else -1
+        if not 1 <= len(self.feature_keys) <= 8 or self.n_out < 1:
+            raise ValueError(f"a model needs 1 to 8 feature keys and n_out >= 1, got {len(self.feature_keys)} and {self.n_out}")
+        if not 1 <= C <= MAX_CLASSES:
+            raise ValueError(f"coef must be (C, D) with 1 <= C <= {MAX_CLASSES}, got shape {self.coef.shape}")
+        if (self.mean.shape != (D,) or self.scale.shape != (D,) or self.coef.shape != (C, D) or self.intercept.shape != (C,)
+                or self.classes.shape != (C,) or (self.class_names is not None and len(self.class_names) != C)):
+            raise ValueError(f"mismatched shapes: D = {len(self.feature_keys)} keys x {self.n_out} = {D}, C = {C}, but mean "
+                             f"{self.mean.shape}, scale {self.scale.shape}, coef {self.coef.shape}, intercept "
+                             f"{self.intercept.shape}, classes {self.classes.shape}")
+        for name in ("mean", "scale", "coef", "intercept"):
+            if not np.isfinite(getattr(self, name)).all():
+                raise ValueError(f"{name} has a non-finite entry")
+        if not (self.scale > 0).all():
+            raise ValueError("scale must be > 0 everywhere")
+
+    @property
+    def n_classes(self) -> int:
+        return int(self.coef.shape[0])
+
+    @property
+    def n_keys(self) -> int:
+        return len(self.feature_keys)
+
+    @classmethod
+    def from_fitted(cls, scaler, clf, feature_keys, n_out: int, class_names=None, params=None):
+        """From a fitted scaler and classifier: this module's ``StandardScaler`` / ``RidgeReadout`` / ``LogisticReadout`` or
+        scikit-learn's objects (``mean_``, ``scale_``, ``coef_``, ``intercept_``, ``classes_``).  scikit-learn's single-row
+        binary form becomes two rows -- row 0 all zeros with intercept 0, row 1 the fitted row --, so that the label is 1
+        exactly where its ``decision_function`` is > 0 and a tie gives class 0."""
+        import numpy as np
+        coef, intercept = _f64(clf.coef_), _f64(clf.intercept_).reshape(-1)
+        if coef.ndim == 1:
+            coef = coef[None, :]
+        classes = clf.classes_
+        if coef.shape[0] == 1 and len(classes) == 2:
+            coef = np.concatenate([np.zeros_like(coef), coef], axis=0)
+            intercept = np.concatenate([np.zeros(1), intercept])
+        return cls(scaler.mean_, scaler.scale_, coef, intercept, classes, feature_keys, n_out, class_names, params)
+
+    def save(self, path) -> None:
+        save_model_file(path, dict(mean=self.mean, scale=self.scale, coef=self.coef, intercept=self.intercept,
+                                   classes=self.classes, class_names=self.class_names, feature_keys=self.feature_keys,
+                                   n_out=self.n_out, params=self.params))
+
+    @classmethod
+    def load(cls, path):
+        f = load_model_file(path)
+        if "coef" not in f:
+            raise ValueError(f"{path} holds the front half of a model only (scaler and parameters): no readout was saved")
+        return cls(f["mean"], f["scale"], f["coef"], f["intercept"], f["classes"], f["feature_keys"], f["n_out"],
+                   f.get("class_names"), f["params"])
+
+
+def save_model_file(path, fields: dict) -> None:
+    """An ``.npz`` of arrays and short strings only (nothing pickled): the arrays as they are, the string lists as unicode
+    arrays, ``params`` as one JSON string."""
+    import json
+    import numpy as np
+    out = {}
+    for name in ("mean", "scale", "coef", "intercept"):
+        if fields.get(name) is not None:
+            out[name] = _f64(fields[name])
+    if fields.get("classes") is not None:
+        out["classes"] = np.asarray(fields["classes"], dtype=np.int64)
+    if fields.get("class_names") is not None:
+        out["class_names"] = np.array([str(n) for n in fields["class_names"]], dtype=np.str_)
+    out["feature_keys"] = np.array([str(k) for k in fields["feature_keys"]], dtype=np.str_)
+    out["n_out"] = np.int64(fields["n_out"])
+    out["params_json"] = np.array(json.dumps(fields.get("params") or {}, sort_keys=True))
+    with open(path, "wb") as fh:                 # a file object: np.savez appends no suffix to the caller's path
+        np.savez(fh, **out)
+
+
+def load_model_file(path) -> dict:
+    """The fields ``save_model_file`` wrote, read with ``allow_pickle=False``."""
+    import json
+    import numpy as np
+    with np.load(path, allow_pickle=False) as z:
+        f = {name: z[name] for name in z.files}
+    f["feature_keys"] = [str(k) for k in f["feature_keys"]]
+    f["n_out"] = int(f["n_out"])
+    f["params"] = json.loads(str(f.pop("params_json")))
+    if "class_names" in f:
+        f["class_names"] = [str(n) for n in f["class_names"]]
+    return f
+
+
+class DeviceReadout:
+    """``model`` uploaded once to ``device``; scores on the device through ``lsm_readout_rows_f32`` and
+    ``lsm_readout_windows``.  There is no host fallback."""
+
+    def __init__(self, model: LinearModel, device=None):
+        from . import _lib
+        self._lib = _lib
+        self.lib = _lib.load()
+        _lib.require_gpu()
+        self.model = model
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if not self.lib.lsm_readout_supported(model.n_keys, model.n_out, model.n_classes):
+            raise _lib.LsmHipError(f"no readout launch for {model.n_keys} keys x {model.n_out} output neurons, "
+                                   f"{model.n_classes} classes")
+        up = lambda a: torch.from_numpy(a).to(self.device).contiguous()     # noqa: E731
+        self.mean, self.scale, self.coef, self.intercept = up(model.mean), up(model.scale), up(model.coef), up(model.intercept)
+        self.classes = up(model.classes)
+
+    def _model_args(self):
+        import ctypes as C
+        return [C.c_void_p(t.data_ptr()) for t in (self.mean, self.scale, self.coef, self.intercept)]
+
+    def score_rows(self, features):
+        """``features`` float32 (..., D) on the device -> ``(logits, labels)``: float64 (..., C) and int32 (...)."""
+        import ctypes as C
+        m = self.model
+        D = m.n_keys * m.n_out
+        if features.dtype != torch.float32 or features.dim() < 1 or features.shape[-1] != D or features.device != self.device:
+            raise ValueError(f"features must be float32 (..., {D}) on {self.device}, got {features.dtype} "
+                             f"{tuple(features.shape)} on {features.device}")
+        lead = tuple(features.shape[:-1])
+        flat = features.reshape(-1, D).contiguous()
+        n = int(flat.shape[0])
+        logits = torch.zeros((n, m.n_classes), dtype=torch.float64, device=self.device)
+        labels = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self._lib.check(self.lib.lsm_readout_rows_f32(
+                *self._model_args(), C.c_void_p(flat.data_ptr()), n, m.n_keys, m.n_out, m.n_classes,
+                C.c_void_p(logits.data_ptr()), C.c_void_p(labels.data_ptr()), stream), "lsm_readout_rows_f32")
+        return logits.reshape(lead + (m.n_classes,)), labels.reshape(lead)
+
+    def score_windows(self, net, records, segment_steps: int, window_segments: int = 1, hop_segments: int = 1, segments=None):
+        """``SNN.segment_features(records, ..., segments=...)`` followed by ``score_rows``, in one launch that writes no
+        feature row: ``(logits, labels)``, float64 (B, W, C) and int32 (B, W).  Rows past a clip's windows are zeros and -1."""
+        import ctypes as C
+        from .snn import _select_keys
+        m = self.model
+        if net.num_output_neurons != m.n_out or net.device != self.device:
+            raise ValueError(f"the model was fitted on {m.n_out} output neurons, the reservoir has {net.num_output_neurons} "
+                             f"(devices {self.device}, {net.device})")
+        if (records.dtype != torch.int32 or records.dim() != 4 or tuple(records.shape[2:]) != (m.n_out, 4)
+                or records.device != self.device):
+            raise ValueError(f"records must be an int32 (B, G, {m.n_out}, 4) tensor on {self.device}")
+        keys, key_ids = _select_keys(m.feature_keys)
+        if keys != m.feature_keys:
+            raise ValueError(f"the model's feature keys {m.feature_keys} are not all feature keys of the reservoir")
+        records = records.contiguous()
+        B, G = int(records.shape[0]), int(records.shape[1])
+        W = net.segment_windows(G, window_segments, hop_segments)
+        host_segments = net._host_segments(segments, B, G) if segments is not None else None
+        logits = torch.zeros((B, W, m.n_classes), dtype=torch.float64, device=self.device)
+        labels = torch.full((B, W), -1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            counts = net._device_counts(segments, host_segments) if segments is not None else None
+            self._lib.check(self.lib.lsm_readout_windows(
+                net._handle, *self._model_args(), C.c_void_p(records.data_ptr()), B, G,
+                C.c_void_p(counts.data_ptr()) if counts is not None else None, int(segment_steps), int(window_segments),
+                int(hop_segments), C.c_void_p(key_ids.ctypes.data), len(keys), m.n_classes,
+                C.c_void_p(logits.data_ptr()), C.c_void_p(labels.data_ptr()), stream), "lsm_readout_windows")
+        return logits, labels
+
+    def class_of(self, labels):
+        """``classes[label]`` for labels >= 0 and -1 for -1: a tensor on the labels' device, or an array for an array."""
+        import numpy as np
+        if isinstance(labels, torch.Tensor):
+            classes = self.classes.to(labels.device)
+            return torch.where(labels >= 0, classes[labels.clamp(min=0).long()], torch.full_like(labels, -1, dtype=torch.int64))
+        labels = np.asarray(labels)
+        return np.where(labels >= 0, self.model.classes[np.clip(labels, 0, None)], -1)

@@ -95,11 +95,13 @@ STAGES = (
      + _speed_args(a) + _mask_args(a) + _variable_length_args(a)),
     ("Step 2: Extracting LSM Features",
      lambda a: ["extract_lsm_features.py", "--feature-set", a.feature_set, "--multiplier", str(a.multiplier)]
-     + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])),
+     + _reservoir_args(a) + (["--time-segments", str(a.time_segments)] if a.time_segments != 1 else [])
+     + (["--model-out", a.save_model, "--filterbank", a.filterbank, "--n-filters", str(a.n_filters)] if a.save_model else [])),
     ("Step 3: Training and Evaluating Classifier",
      lambda a: ["train_classifier.py"] + (["--readout", a.readout] if a.readout else [])
      + (["--commands", a.commands] if a.commands else [])
-     + (["--commands-file", a.commands_file] if a.commands_file else [])),
+     + (["--commands-file", a.commands_file] if a.commands_file else [])
+     + (["--model-out", a.save_model] if a.save_model else [])),
 )
 
 IN_MEMORY = """import argparse, sys, create_dataset as cd, extract_lsm_features as ex
@@ -117,7 +119,8 @@ ex.main_from_audio(audio, labels, a.n_filters, a.filterbank, a.feature_set, a.mu
                    num_neurons=a.num_neurons, num_output_neurons=a.num_output_neurons,
                    small_world_k=a.small_world_k, seed=a.seed, readout=a.device_readout,
                    class_names=cd.commands_from_args(a), time_segments=a.time_segments, corrupt=corrupt, reverb=reverb,
-                   speed=speed, **({{}} if cd.mask_from_args(a) is None else {{"mask": cd.mask_from_args(a)}}))
+                   speed=speed, **({{}} if cd.mask_from_args(a) is None else {{"mask": cd.mask_from_args(a)}}),
+                   **({{"model_out": a.save_model}} if a.save_model else {{}}))
 """
 
 
@@ -145,7 +148,9 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     mask_prob: applied to stage 1 and to the in-memory route; variable_length, max_seconds: stage 1 keeps every clip at its
     own length, SPEC.md 1.14, and stage 2 finds the lengths in File 1; trim_silence, trim_pad_ms, trim_min_ms: stage 1 first
     cuts every such clip to its speech on the GPU, SPEC.md 1.15; augment_variable_length: stage 1 lets the corruption, the
-    reverberation and the mask flags through on such clips, SPEC.md 1.16)."""
+    reverberation and the mask flags through on such clips, SPEC.md 1.16; save_model: a path -- stage 2 writes the front half
+    of the model file there and stage 3 adds its readout, or the in-memory route with a PyTorch readout writes it whole,
+    SPEC.md 6; classify.py labels new audio with it)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
@@ -154,7 +159,8 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
                               level_db=None, augment_seed=42, rir_dir=None, rir_prob=1.0, rir_max_ms=500.0,
                               speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
                               time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0,
-                              trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0, augment_variable_length=False)
+                              trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0, augment_variable_length=False,
+                              save_model=None)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -251,6 +257,9 @@ if __name__ == "__main__":
     ap.add_argument("--trim-min-ms", type=float, default=30.0, help="With --trim-silence: shortest trimmed clip (stage 1).")
     ap.add_argument("--augment-variable-length", action="store_true",
                     help="With --variable-length: let the corruption flags, --rir-dir and the mask flags through (stage 1).")
+    ap.add_argument("--save-model", type=str, default=None, metavar="PATH",
+                    help="Save the trained model (scaler, readout, front-end and reservoir parameters) for classify.py "
+                         "(stages 2 and 3).")
     a = ap.parse_args()
     run_pipeline(n_filters=a.n_filters, filterbank=a.filterbank, feature_set=a.feature_set,
                  multiplier=a.multiplier, in_memory=a.in_memory, commands=a.commands, commands_file=a.commands_file,
@@ -263,4 +272,5 @@ if __name__ == "__main__":
                  speed_prob=a.speed_prob, freq_masks=a.freq_masks, freq_mask_width=a.freq_mask_width,
                  time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob,
                  variable_length=a.variable_length, max_seconds=a.max_seconds, trim_silence=a.trim_silence,
-                 trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms, augment_variable_length=a.augment_variable_length)
+                 trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms, augment_variable_length=a.augment_variable_length,
+                 save_model=a.save_model)

@@ -66,15 +66,38 @@ def report_results(y_train, y_test, y_pred, class_names=None):
     return accuracy
 
 
-def train_and_evaluate_classifier(readout=None, class_names=None):
+def names_of_classes(classes, class_names=None):
+    """The report's name of every class value in ``classes`` (the dataset's label indices)."""
+    class_names = list(CLASS_NAMES if class_names is None else class_names)
+    return [class_names[int(i)] if 0 <= int(i) < len(class_names) else f"class_{int(i)}" for i in classes]
+
+
+def complete_model(path, clf, class_names=None) -> None:
+    """Add the fitted readout ``clf`` to the front half extract_lsm_features.py --model-out wrote at ``path`` and write the
+    whole model back (`lsm_speech_classifier_amd.readout.LinearModel`, which makes its refusals here)."""
+    from types import SimpleNamespace
+    from lsm_speech_classifier_amd import readout as ro
+    front = ro.load_model_file(path)
+    fitted = getattr(clf, "model", clf)                     # the PyTorch readout inside its adapter
+    classes = np.asarray(fitted.classes_.cpu() if hasattr(fitted.classes_, "cpu") else fitted.classes_)
+    ro.LinearModel.from_fitted(SimpleNamespace(mean_=front["mean"], scale_=front["scale"]), fitted, front["feature_keys"],
+                               front["n_out"], names_of_classes(classes, class_names), front["params"]).save(path)
+    print(f"Model saved to '{path}'")
+
+
+def train_and_evaluate_classifier(readout=None, class_names=None, model_out=None):
     """The reference's function (no arguments there).  `readout`: one of READOUTS (default: LSM_READOUT, else the
     reference's scikit-learn logistic regression); `class_names`: report names when the dataset was built with
-    another class list than the reference's 12 words (train_classifier.py:8-20 hard-codes them)."""
+    another class list than the reference's 12 words (train_classifier.py:8-20 hard-codes them); `model_out`: the model
+    file whose front half extract_lsm_features.py --model-out wrote, completed with the readout fitted here."""
     readout = readout or os.environ.get("LSM_READOUT", "sklearn")
     if readout not in READOUTS:
         raise ValueError(f"readout must be one of {READOUTS}, got {readout!r}")
     if not Path(FEATURE_FILE).exists():
         print("Error: Dataset file not found. Please run 'extract_lsm_features.py' first.")
+        return
+    if model_out and not Path(model_out).exists():
+        print(f"Error: Model file not found at '{model_out}'. Please run 'extract_lsm_features.py --model-out' first.")
         return
     with np.load(FEATURE_FILE, allow_pickle=True) as data:
         X_train, y_train = data['X_train_features'], data['y_train']
@@ -89,6 +112,8 @@ def train_and_evaluate_classifier(readout=None, class_names=None):
 
     print("Evaluating performance on the test set...")
     y_pred = clf.predict(X_test)
+    if model_out:
+        complete_model(model_out, clf, class_names)
     return report_results(y_train, y_test, y_pred, class_names)
 
 
@@ -99,6 +124,8 @@ if __name__ == "__main__":
                     help="default: LSM_READOUT, else scikit-learn logistic regression (the reference's readout)")
     ap.add_argument("--commands", type=str, default=None, help="Comma-separated class names for the report.")
     ap.add_argument("--commands-file", type=str, default=None, help="File with one class name per line.")
+    ap.add_argument("--model-out", type=str, default=None,
+                    help="Model file whose front half extract_lsm_features.py --model-out wrote: the readout is added to it.")
     a = ap.parse_args()
     names = None
     if a.commands_file:
@@ -106,4 +133,4 @@ if __name__ == "__main__":
             names = [ln.strip() for ln in fh if ln.strip() and not ln.lstrip().startswith("#")]
     elif a.commands:
         names = [w.strip() for w in a.commands.split(",") if w.strip()]
-    train_and_evaluate_classifier(readout=a.readout, class_names=names)
+    train_and_evaluate_classifier(readout=a.readout, class_names=names, model_out=a.model_out)
