@@ -202,11 +202,29 @@ def load_noise_bank(noise_dir, seed: int = 42) -> np.ndarray:
 def corruption(augment, n_listed: int):
     """``augment`` (`augment_from_args`) -> ``(noise bank, frontend.MixPlan of all n_listed clips in listing order)``."""
     bank = load_noise_bank(augment["noise_dir"], augment["seed"])
+    return bank, _mix_plan(augment, bank, n_listed, augment["seed"])
+
+
+def _mix_plan(augment, bank, n_listed: int, seed: int):
     snr = augment["snr_db"] if augment["noise_dir"] is not None else np.inf
-    plan = _frontend().mix_plan(n_listed, bank.shape[0], bank.shape[1], DEFAULT_SNR_DB if snr is None else snr,
+    return _frontend().mix_plan(n_listed, bank.shape[0], bank.shape[1], DEFAULT_SNR_DB if snr is None else snr,
                                 max_shift=int(round(augment["time_shift_ms"] * SAMPLE_RATE / 1000.0)),
-                                level_db=augment["level_db"], seed=augment["seed"])
-    return bank, plan
+                                level_db=augment["level_db"], seed=seed)
+
+
+def epoch_plans(epoch: int, n_listed: int, augment=None, corrupt=None, room=None, reverb=None, pace=None):
+    """The plans of a later pass over the same n_listed clips (`extract_lsm_features.main_from_audio(epochs=...)`): what
+    `corruption`, `reverberation` and `speeds` draw with --augment-seed + ``epoch``, for the banks already loaded -- ``corrupt``
+    and ``reverb`` are those functions' results for epoch 0, ``augment``, ``room`` and ``pace`` the flags they were made from.
+    A dict with "mix", "reverb" and "speed" for the stages in use."""
+    out = {}
+    if augment:
+        out["mix"] = _mix_plan(augment, corrupt[0], n_listed, augment["seed"] + int(epoch))
+    if room:
+        out["reverb"] = _frontend().reverb_plan(n_listed, reverb[0].shape[0], prob=room["prob"], seed=room["seed"] + int(epoch))
+    if pace:
+        out["speed"] = _frontend().speed_plan(n_listed, len(pace["factors"]), prob=pace["prob"], seed=pace["seed"] + int(epoch))
+    return out
 
 
 # ---- reverberation on the device (SPEC.md 1.11): --rir-dir, --rir-prob, --rir-max-ms; the seed is --augment-seed -----------

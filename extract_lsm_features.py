@@ -238,7 +238,8 @@ def run_network_diagnostics(lsm, X_sample_batch):
 def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set: str, multiplier: float,
                     leak_variance_divisor: float = None, batch: int = 1024, *, num_neurons=None,
                     num_output_neurons=None, small_world_k=None, seed=None, readout=None, class_names=None,
-                    time_segments=1, corrupt=None, reverb=None, speed=None, mask=None, model_out=None):
+                    time_segments=1, corrupt=None, reverb=None, speed=None, mask=None, model_out=None, epochs=1,
+                    ridge_alpha=1.0, epoch_plans=None):
     """Stages 1 + 2 without File 1: audio (n, 16000) float32 + labels -> File 2, the same arrays main() writes
     after create_dataset() (tests/test_gpu_hotpath.py compares them).  The split, w_critico (first <= 500
     training clips), the reservoir and the diagnostics follow main() line by line; the features come from
@@ -274,15 +275,25 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     are zeroed inside the spike encoder (SPEC.md 1.13), by a plan drawn for all n clips in listing order.
 
     `model_out` = a path: the model file of `readout.LinearModel` (SPEC.md 6) -- with a PyTorch `readout` the whole file at
-    once, otherwise its front half (scaler and parameters), which train_classifier.py --model-out completes."""
+    once, otherwise its front half (scaler and parameters), which train_classifier.py --model-out completes.
+
+    `readout` = "stream-ridge" (SPEC.md 7): no training row is kept or gathered.  The training split runs `epochs` times
+    through `pipeline.fit_from_audio` into one `readout.RidgeStatistics` per rank (merged in rank order under a launcher:
+    the result is that world size's, not one process's); `ridge_alpha` is the readout's penalty.  Epoch 0 uses the plans given,
+    so one epoch sees exactly the rows "torch-ridge" sees; epoch e >= 1 uses ``epoch_plans(e)`` -- a dict with the `mix`,
+    `reverb` and `speed` plans of all n clips drawn with the augmentation seed + e (`create_dataset.epoch_plans`) -- and the
+    mask plan drawn with ``mask["seed"] + e``.  The test split is scored by `readout.DeviceReadout`; File 2 is not written,
+    because no training rows exist."""
     from sklearn.model_selection import train_test_split
     from sklearn.preprocessing import StandardScaler
     from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline
     from lsm_speech_classifier_amd.augment import AugmentChain, StepPlans
     from lsm_speech_classifier_amd.snn import SNN
 
-    if readout not in (None, "sklearn", "torch-ridge", "torch-logistic"):
-        raise ValueError(f"readout must be None, 'sklearn', 'torch-ridge' or 'torch-logistic', got {readout!r}")
+    if readout not in (None, "sklearn", "torch-ridge", "torch-logistic", "stream-ridge"):
+        raise ValueError(f"readout must be None, 'sklearn', 'torch-ridge', 'torch-logistic' or 'stream-ridge', got {readout!r}")
+    check_stream_ridge(readout, epochs, time_segments, corrupt is not None or reverb is not None or speed is not None,
+                       epoch_plans)
     on_device = readout in ("torch-ridge", "torch-logistic")
     rank, _, world = lsm_dist.init()
     audio = np.ascontiguousarray(audio, dtype=np.float32)
@@ -337,6 +348,16 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
                                              speed=(chain.speed, shard.speed), mask=shard.mask)
         return lsm_dist.gather_rows(local, len(idx))
 
+    if readout == "stream-ridge":
+        stats = _stream_statistics(audio, labels, idx_train, y_train, fe, lsm, keys, chain, plans, mask, batch, int(epochs),
+                                   epoch_plans, rank, world)
+        X_test_dev = split_features(idx_test)
+        lsm_dist.finish()
+        if rank != 0:
+            return
+        return _stream_readout(stats, X_test_dev, y_train, y_test, float(ridge_alpha), class_names, model_out,
+                               pipeline.model_params(fe, params, feature_set=feature_set, multiplier=float(multiplier),
+                                                     time_segments=1))
     X_train_dev = split_features(idx_train)
     X_test_dev = split_features(idx_test)
     lsm_dist.finish()
@@ -360,6 +381,64 @@ def main_from_audio(audio, labels, n_filters: int, filterbank: str, feature_set:
     print(f"Extraction complete. Features saved to '{FEATURE_FILE}'")
     if model:
         write_model_front(scaler, **model)
+
+
+def check_stream_ridge(readout, epochs, time_segments, augmented: bool, epoch_plans) -> None:
+    """The refusals of the "stream-ridge" route, made before any work is done."""
+    if readout != "stream-ridge":
+        if int(epochs) != 1:
+            raise ValueError("epochs needs readout='stream-ridge': the other readouts keep every training row once")
+        return
+    if int(epochs) < 1:
+        raise ValueError(f"epochs={epochs} must be >= 1")
+    if int(time_segments) != 1:
+        raise ValueError("readout='stream-ridge' needs time_segments = 1: the statistics hold one feature row per clip")
+    if int(epochs) > 1 and augmented and epoch_plans is None:
+        raise ValueError("epochs > 1 with a corruption, reverberation or speed plan needs epoch_plans: the plans of the later "
+                         "epochs (create_dataset.epoch_plans)")
+
+
+def _stream_statistics(audio, labels, idx_train, y_train, fe, lsm, keys, chain, plans, mask, batch, epochs, epoch_plans,
+                       rank, world):
+    """The training split, `epochs` times, into this rank's `RidgeStatistics`; then every rank's merged in rank order."""
+    from lsm_speech_classifier_amd import dist as lsm_dist, frontend, pipeline, readout as ro
+    from lsm_speech_classifier_amd.augment import StepPlans
+    n_classes = int(labels.max()) + 1
+    if labels.min() < 0 or n_classes > ro.MAX_CLASSES:
+        raise ValueError(f"readout='stream-ridge' takes labels in [0, {ro.MAX_CLASSES}), got {int(labels.min())} to "
+                         f"{int(labels.max())}")
+    stats = ro.RidgeStatistics(keys, lsm.num_output_neurons, n_classes, device=lsm.device)
+    lo, hi = lsm_dist.shard_range(len(idx_train), rank, world)
+    for e in range(epochs):
+        drawn = plans
+        if e:
+            later = dict(epoch_plans(e)) if epoch_plans is not None else {}
+            drawn = StepPlans(later.get("speed"), later.get("reverb"), later.get("mix"),
+                              frontend.mask_plan(len(audio), fe.n_filters, fe.time_bins, **dict(mask, seed=int(mask["seed"]) + e))
+                              if mask else None)
+            for name in ("speed", "reverb", "mix"):
+                if (getattr(plans, name) is None) != (getattr(drawn, name) is None):
+                    raise ValueError(f"epoch_plans({e}) must hold a {name!r} plan exactly when epoch 0 has one")
+        shard = drawn.take(idx_train[lo:hi])
+        pipeline.fit_from_audio(audio[idx_train[lo:hi]], y_train[lo:hi], fe, lsm, keys, stats, batch=batch,
+                                corrupt=(chain.mixer, shard.mix), reverb=(chain.reverb, shard.reverb),
+                                speed=(chain.speed, shard.speed), mask=shard.mask)
+    return lsm_dist.merge_statistics(stats)
+
+
+def _stream_readout(stats, X_test_dev, y_train, y_test, alpha, class_names, model_out, params):
+    """The readout solved from the statistics, the test split scored on the device, the usual report."""
+    import train_classifier as tc
+    from lsm_speech_classifier_amd import readout as ro
+    print(f"Solving the ridge readout from the statistics of {stats.rows} training rows on the device...")
+    model = stats.to_model(alpha, tc.names_of_classes(range(stats.n_classes), class_names), params)
+    scorer = ro.DeviceReadout(model, device=X_test_dev.device)
+    y_pred = scorer.class_of(scorer.score_rows(X_test_dev)[1]).cpu().numpy()
+    print(f"'{FEATURE_FILE}' is not written on this route: no training rows exist")
+    if model_out:
+        model.save(model_out)
+        print(f"Model saved to '{model_out}'")
+    return tc.report_results(y_train, y_test, y_pred, class_names)
 
 
 def check_model_out(model_out, time_segments) -> None:

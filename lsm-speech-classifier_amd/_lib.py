@@ -242,6 +242,14 @@ READOUT_SIGS = {
 }
 READOUT_SYMBOLS = tuple(READOUT_SIGS)
 
+# include/lsm_hip_fit.h (SPEC.md §7): the statistics of a standard scaler and a ridge readout, updated from a step's rows
+FIT_SIGS = {
+    "lsm_fit_supported": (c_int, [c_int, c_int, c_int]),
+    "lsm_fit_accumulate_f32": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void, c_void, c_void,
+                                       c_void]),
+}
+FIT_SYMBOLS = tuple(FIT_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -294,7 +302,7 @@ def load():
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
                               + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
                               + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items()) + list(RAGGED_AUGMENT_SIGS.items())
-                              + list(READOUT_SIGS.items())):
+                              + list(READOUT_SIGS.items()) + list(FIT_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

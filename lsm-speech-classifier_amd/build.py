@@ -9,7 +9,7 @@ import subprocess
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
-SOURCES = ["lsm_api.hip", "frontend.hip", "mask.hip", "frontend_stream.hip", "mel.hip", "mel_stream.hip", "resample.hip", "adaptive_stream.hip", "mix.hip", "reverb.hip", "speed.hip", "trim.hip", "ragged_frontend.hip", "ragged_masked_frontend.hip", "step_fused.hip", "step_fused_masked.hip", "step_fused_ragged.hip", "step_fused_ragged_masked.hip", "step_fused_state.hip", "readout.hip", "reservoir.hip", "lif_variant_00.hip", "lif_variant_01.hip",
+SOURCES = ["lsm_api.hip", "frontend.hip", "mask.hip", "frontend_stream.hip", "mel.hip", "mel_stream.hip", "resample.hip", "adaptive_stream.hip", "mix.hip", "reverb.hip", "speed.hip", "trim.hip", "ragged_frontend.hip", "ragged_masked_frontend.hip", "step_fused.hip", "step_fused_masked.hip", "step_fused_ragged.hip", "step_fused_ragged_masked.hip", "step_fused_state.hip", "readout.hip", "fit.hip", "reservoir.hip", "lif_variant_00.hip", "lif_variant_01.hip",
            "lif_variant_10.hip", "lif_variant_11.hip", "lif_dense_0.hip", "lif_dense_1.hip", "lif_dense_2.hip", "lif_dense_3.hip",
            "lif_ring_1.hip", "lif_ring_2.hip", "lif_ring_3.hip", "lif_ring_4.hip",
            "lif_pair_1.hip", "lif_pair_2.hip", "lif_pair_3.hip", "lif_pair_4.hip",
@@ -25,6 +25,7 @@ STEP_STATE_HEADERS = ["lsm_hip_step_state.h"]   # include/: the fused step with 
 TRIM_HEADERS = ["lsm_hip_trim.h"]       # include/: silence trimming in front of the ragged front end (SPEC.md 1.15), hashed likewise
 RAGGED_AUGMENT_HEADERS = ["lsm_hip_ragged_augment.h"]   # include/: mixer and masks on ragged launches (SPEC.md 1.16), hashed likewise
 READOUT_HEADERS = ["lsm_hip_readout.h"]     # include/: scaler and linear readout on the device (SPEC.md 6), hashed likewise
+FIT_HEADERS = ["lsm_hip_fit.h"]             # include/: the streaming ridge fit's statistics (SPEC.md 7), hashed likewise
 LIB_NAME = "liblsm_hip.so"
 # -ffp-contract=off: the kernels must round every float operation exactly like the CPU oracle.
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
@@ -60,7 +61,7 @@ def source_id(include_dir: str | None = None) -> str:
     include_dir = include_dir or os.path.join(ROOT, "include")
     files = sorted(os.path.join(PKG_DIR, "csrc", f) for f in SOURCES + HEADERS) + [os.path.join(include_dir, f)
                                                                                   for f in PUBLIC_HEADERS + MASK_HEADERS + RAGGED_HEADERS + STEP_HEADERS
-                                                                                  + STEP_STATE_HEADERS + TRIM_HEADERS + RAGGED_AUGMENT_HEADERS + READOUT_HEADERS]
+                                                                                  + STEP_STATE_HEADERS + TRIM_HEADERS + RAGGED_AUGMENT_HEADERS + READOUT_HEADERS + FIT_HEADERS]
     for path in files:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:

@@ -119,6 +119,27 @@ def gather_varrows(local: torch.Tensor) -> torch.Tensor:
     return torch.cat([out[r * per: r * per + counts[r]] for r in range(world)])
 
 
+def merge_statistics(stats):
+    """Every rank's `readout.RidgeStatistics` merged in rank order, on every rank: the result starts from rank 0's and takes
+    rank 1's, rank 2's, ... through `RidgeStatistics.merge` (SPEC.md §7), so all ranks hold the same bytes -- those of this
+    world size, not those of one process over all rows.  One broadcast per rank and field: beside the result only one
+    rank's copy of a field is held at a time.  ``stats`` itself is left as it is; a single process gets it back."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return stats
+    from .readout import RidgeStatistics
+    merged = None
+    for src in range(dist.get_world_size()):
+        fields = [t.clone() for t in stats._fields()]
+        for t in fields:
+            dist.broadcast(t, src)
+        theirs = RidgeStatistics.__new__(RidgeStatistics)
+        theirs.feature_keys, theirs.n_out, theirs.n_classes, theirs.device = (stats.feature_keys, stats.n_out, stats.n_classes,
+                                                                              stats.device)
+        theirs.gram, theirs.class_sums, theirs.class_counts, theirs.col_min, theirs.col_max = fields
+        merged = theirs if merged is None else merged.merge(theirs)
+    return merged
+
+
 def broadcast_float(value: float, src: int = 0, device=None) -> float:
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return value

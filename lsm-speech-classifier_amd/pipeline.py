@@ -739,6 +739,66 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     return feats if device_out else feats.cpu().numpy()
 
 
+FIT_ROW_BUFFERS = 4                  # row buffers a `fit_from_audio` run hands round between its steps and their pushes
+
+
+def fit_from_audio(audio: np.ndarray, labels, fe, net, feature_keys, stats, batch: int = 1024,
+                   streams: int = DEFAULT_STREAMS, corrupt=None, reverb=None, speed=None, mask=None) -> int:
+    """`features_from_audio` with a sink: every step's rows go into ``stats`` (a `readout.RidgeStatistics` on the pipeline's
+    device; SPEC.md §7) instead of being kept.  ``labels`` int32 (n): a clip whose label lies outside the statistics' classes
+    is skipped by the push.  A step writes its rows into one of `FIT_ROW_BUFFERS` buffers (`HotPath.submit(out=...)`); the
+    push runs on one stream of its own behind the step's event -- so the pushes are ordered among themselves --, and an
+    event of the push releases the buffer to the step that takes it next.  No row outlives its push and the host waits for
+    nothing per step (but for `HotPath`'s back-pressure); the call returns, after one synchronisation, the number of clips
+    it has run.  The augmentation arguments are `features_from_audio`'s."""
+    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
+    plans = StepPlans(speeds, reverbs, mixes, mask)
+    plans.check_covers(len(audio))
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if labels.shape != (len(audio),):
+        raise ValueError(f"labels must hold one value per clip, got {labels.shape} for {len(audio)} clips")
+    hp = HotPath(fe, net, feature_keys, streams=streams, mixer=mixer, reverb=rv, speed=sp)
+    if indexed_device(stats.device) != hp.device:
+        raise ValueError(f"statistics on {stats.device}, pipeline on {hp.device}")
+    n_keys = len(feature_keys) if feature_keys is not None else 8
+    if n_keys * net.num_output_neurons != stats.D or n_keys != len(stats.feature_keys):
+        raise ValueError(f"the statistics hold rows of {len(stats.feature_keys)} keys x {stats.n_out}, the pipeline gives "
+                         f"{n_keys} keys x {net.num_output_neurons}")
+    pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    if len(pinned):
+        try:
+            pinned = pinned.pin_memory()
+        except RuntimeError:
+            pass
+    starts = list(range(0, len(pinned), batch))
+    with torch.cuda.device(hp.device):
+        cur = torch.cuda.current_stream(hp.device)
+        y = torch.from_numpy(labels).to(hp.device)
+        rows = [torch.empty((batch, stats.D), dtype=torch.float32, device=hp.device)
+                for _ in range(min(FIT_ROW_BUFFERS, len(starts)))]
+        released = [None] * len(rows)
+        pusher = torch.cuda.Stream(device=hp.device)
+        pusher.wait_stream(cur)                  # the labels, the buffers and whatever filled `stats` before this call
+        hp.fork_from_current()
+        for s, lo in enumerate(starts):
+            part, at = plans.part(lo, lo + batch), s % len(rows)
+            n = min(batch, len(pinned) - lo)
+            feats, st = hp.submit(pinned[lo:lo + n], out=rows[at][:n], after=released[at], tail=s >= len(starts) - TAIL_STEPS,
+                                  mix=part.mix, reverb=part.reverb, speed=part.speed, **part.mask_keyword())
+            if feats.data_ptr() != rows[at].data_ptr():
+                raise RuntimeError("the step did not write its rows into the buffer it was given")
+            done = torch.cuda.Event()
+            done.record(st)
+            pusher.wait_event(done)
+            with torch.cuda.stream(pusher):
+                stats.push(feats, y[lo:lo + n])
+            released[at] = torch.cuda.Event()
+            released[at].record(pusher)
+        hp.synchronize()
+        pusher.synchronize()
+    return len(pinned)
+
+
 def _audio_windows(audio, fe):
     """``audio`` (n, W * fe.n_samples) float32, tensor or NumPy (copied), checked: ``(audio tensor, n, W)``."""
     audio = as_float32(audio)

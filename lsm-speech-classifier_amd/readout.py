@@ -10,6 +10,8 @@ arrays (tests/test_readout.py): identical predictions for ridge, >= 99 % agreeme
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 
@@ -304,3 +306,188 @@ class DeviceReadout:
             return torch.where(labels >= 0, classes[labels.clamp(min=0).long()], torch.full_like(labels, -1, dtype=torch.int64))
         labels = np.asarray(labels)
         return np.where(labels >= 0, self.model.classes[np.clip(labels, 0, None)], -1)
+
+
+# ---- training from statistics (SPEC.md §7, include/lsm_hip_fit.h) ----------------------------------------------------------
+class RidgeSolution(NamedTuple):
+    """What `RidgeStatistics.solve` returns, float64 on the statistics' device: the scaler's ``mean`` / ``scale`` (D), the
+    readout's ``coef`` (C, D) and ``intercept`` (C) for the C classes that have rows, and those classes (int64)."""
+    mean: torch.Tensor
+    scale: torch.Tensor
+    coef: torch.Tensor
+    intercept: torch.Tensor
+    classes: torch.Tensor
+
+
+class RidgeStatistics:
+    """What a `StandardScaler` and a `RidgeReadout` are functions of, in constant size: ``gram`` (D, D) float64, the lower
+    triangle of X^T X (entries above the diagonal are never read); ``class_sums`` (C, D) float64; ``class_counts`` (C) int64;
+    ``col_min`` / ``col_max`` (D) float32 -- all on one device.  `push` adds feature rows on the GPU (`lsm_fit_accumulate_f32`;
+    there is no host fallback), `merge` adds another object's statistics, `save` / `load` keep them in a file, and `solve`
+    gives the scaler and the readout that fitting on all pushed rows would give."""
+
+    def __init__(self, feature_keys, n_out: int, n_classes: int, device=None):
+        self.feature_keys = [str(k) for k in feature_keys]
+        self.n_out, self.n_classes = int(n_out), int(n_classes)
+        if not 1 <= len(self.feature_keys) <= 8 or self.n_out < 1 or not 1 <= self.n_classes <= MAX_CLASSES:
+            raise ValueError(f"statistics need 1 to 8 feature keys, n_out >= 1 and 1 to {MAX_CLASSES} classes, got "
+                             f"{len(self.feature_keys)}, {self.n_out} and {self.n_classes}")
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        D, C = self.D, self.n_classes
+        self.gram = torch.zeros((D, D), dtype=torch.float64, device=self.device)
+        self.class_sums = torch.zeros((C, D), dtype=torch.float64, device=self.device)
+        self.class_counts = torch.zeros((C,), dtype=torch.int64, device=self.device)
+        self.col_min = torch.full((D,), float("inf"), dtype=torch.float32, device=self.device)
+        self.col_max = torch.full((D,), float("-inf"), dtype=torch.float32, device=self.device)
+
+    @property
+    def D(self) -> int:
+        return len(self.feature_keys) * self.n_out
+
+    @property
+    def rows(self) -> int:
+        """How many rows the statistics hold (a host read of the counts)."""
+        return int(self.class_counts.sum().item())
+
+    def _fields(self):
+        return self.gram, self.class_sums, self.class_counts, self.col_min, self.col_max
+
+    @classmethod
+    def from_arrays(cls, gram, class_sums, class_counts, col_min, col_max, feature_keys, n_out: int, device="cpu"):
+        """From given statistics (arrays or tensors), on any device, the CPU included."""
+        import numpy as np
+        class_counts = np.asarray(class_counts.cpu() if isinstance(class_counts, torch.Tensor) else class_counts)
+        self = cls(feature_keys, n_out, int(class_counts.shape[0]) if class_counts.ndim == 1 else -1, device)
+        given = (_f64(gram), _f64(class_sums), np.ascontiguousarray(class_counts, dtype=np.int64),
+                 np.ascontiguousarray(_np(col_min), dtype=np.float32), np.ascontiguousarray(_np(col_max), dtype=np.float32))
+        for mine, theirs, name in zip(self._fields(), given, ("gram", "class_sums", "class_counts", "col_min", "col_max")):
+            if tuple(mine.shape) != theirs.shape:
+                raise ValueError(f"{name} must have shape {tuple(mine.shape)}, got {theirs.shape}")
+            mine.copy_(torch.from_numpy(theirs))
+        return self
+
+    def push(self, features, labels) -> None:
+        """Add the rows ``features`` float32 (n, D) with ``labels`` int32 (n), both on this object's GPU, on the current
+        stream; a row whose label lies outside [0, n_classes) is skipped.  Pushes on one object must be stream-ordered by the
+        caller."""
+        import ctypes as C
+        from . import _lib
+        lib = _lib.load()
+        _lib.require_gpu()
+        if self.device.type != "cuda":
+            raise _lib.LsmHipError(f"push runs on the GPU: these statistics live on {self.device} (there is no host fallback)")
+        n = int(features.shape[0]) if features.dim() == 2 else -1
+        if (features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] != self.D
+                or features.device != self.device or not features.is_contiguous()):
+            raise ValueError(f"features must be contiguous float32 (n, {self.D}) on {self.device}, got {features.dtype} "
+                             f"{tuple(features.shape)} on {features.device}")
+        if (labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or labels.device != self.device
+                or not labels.is_contiguous()):
+            raise ValueError(f"labels must be contiguous int32 ({n},) on {self.device}, got {labels.dtype} "
+                             f"{tuple(labels.shape)} on {labels.device}")
+        if not lib.lsm_fit_supported(len(self.feature_keys), self.n_out, self.n_classes):
+            raise _lib.LsmHipError(f"no fit launch for {len(self.feature_keys)} keys x {self.n_out} output neurons, "
+                                   f"{self.n_classes} classes")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(lib.lsm_fit_accumulate_f32(
+                C.c_void_p(features.data_ptr()), C.c_void_p(labels.data_ptr()), n, len(self.feature_keys), self.n_out,
+                self.n_classes, *[C.c_void_p(t.data_ptr()) for t in self._fields()], stream), "lsm_fit_accumulate_f32")
+
+    def merge(self, other: "RidgeStatistics") -> "RidgeStatistics":
+        """Add ``other``'s statistics to these, in this order: gram, sums and counts by element-wise addition, then the
+        minimum and the maximum of the ranges.  Defined to the bit, and in its last bits not what one run of pushes over both
+        objects' rows leaves (SPEC.md §7)."""
+        if (other.feature_keys, other.n_out, other.n_classes) != (self.feature_keys, self.n_out, self.n_classes):
+            raise ValueError(f"statistics of {other.feature_keys} x {other.n_out}, {other.n_classes} classes do not merge into "
+                             f"those of {self.feature_keys} x {self.n_out}, {self.n_classes} classes")
+        theirs = [t.to(self.device) for t in other._fields()]
+        self.gram += theirs[0]
+        self.class_sums += theirs[1]
+        self.class_counts += theirs[2]
+        torch.minimum(self.col_min, theirs[3], out=self.col_min)
+        torch.maximum(self.col_max, theirs[4], out=self.col_max)
+        return self
+
+    def packed_gram(self) -> "np.ndarray":
+        """The lower triangle row by row, D * (D + 1) / 2 float64 values on the host."""
+        import numpy as np
+        g = self.gram.cpu().numpy()
+        return np.concatenate([g[i, :i + 1] for i in range(self.D)])
+
+    def save(self, path) -> None:
+        """An ``.npz`` of arrays and short strings only (nothing pickled), the Gram as its packed lower triangle."""
+        import numpy as np
+        counts = self.class_counts.cpu().numpy()
+        with open(path, "wb") as fh:
+            np.savez(fh, gram_tril=self.packed_gram(), class_sums=self.class_sums.cpu().numpy(), class_counts=counts,
+                     col_min=self.col_min.cpu().numpy(), col_max=self.col_max.cpu().numpy(),
+                     feature_keys=np.array(self.feature_keys, dtype=np.str_), n_out=np.int64(self.n_out),
+                     n_classes=np.int64(self.n_classes), rows=np.int64(counts.sum()))
+
+    @classmethod
+    def load(cls, path, device="cpu"):
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            f = {name: z[name] for name in z.files}
+        keys, n_out, C = [str(k) for k in f["feature_keys"]], int(f["n_out"]), int(f["n_classes"])
+        D = len(keys) * n_out
+        if f["gram_tril"].shape != (D * (D + 1) // 2,) or f["class_counts"].shape != (C,) \
+                or int(f["rows"]) != int(f["class_counts"].sum()):
+            raise ValueError(f"{path}: not the statistics of {len(keys)} keys x {n_out}, {C} classes, {int(f['rows'])} rows")
+        gram = np.zeros((D, D), dtype=np.float64)
+        at = 0
+        for i in range(D):
+            gram[i, :i + 1] = f["gram_tril"][at:at + i + 1]
+            at += i + 1
+        return cls.from_arrays(gram, f["class_sums"], f["class_counts"], f["col_min"], f["col_max"], keys, n_out, device)
+
+    def solve(self, alpha: float = 1.0) -> RidgeSolution:
+        """`StandardScaler` + `RidgeReadout(alpha)` on the pushed rows, from the statistics alone (float64, on this object's
+        device).  n = the counts' sum, mean = the class sums' sum / n.  A column whose range is one value is constant: its
+        mean is that value, its scale 1, and it leaves the system (coefficient 0) -- exactly, where a variance from moments
+        could only guess.  Otherwise var = max(G_ii / n - mean^2, 0) with the scaler's rounding-noise rule, and
+        (diag(1/s) (G - n mean mean^T) diag(1/s) + alpha I) w_c = diag(1/s) (2 S_c - sum x - mean (2 n_c - n)), intercept
+        (2 n_c - n) / n, one row per class that has rows."""
+        counts = self.class_counts.to(torch.float64)
+        n = counts.sum()
+        if int(self.class_counts.sum().item()) == 0:
+            raise ValueError("no rows have been pushed: nothing to solve")
+        total = self.class_sums.sum(dim=0)
+        lower = torch.tril(self.gram)
+        G = lower + torch.tril(self.gram, -1).T
+        constant = self.col_min == self.col_max
+        mean = torch.where(constant, self.col_min.to(torch.float64), total / n)
+        var = (G.diagonal() / n - mean * mean).clamp(min=0.0)
+        eps = torch.finfo(torch.float64).eps
+        noise = var <= n * eps * mean.abs() ** 2 * 10
+        scale = torch.where((var > 0) & ~noise & ~constant, var.sqrt(), torch.ones_like(var))
+        classes = torch.nonzero(self.class_counts > 0).reshape(-1)
+        keep = torch.nonzero(~constant).reshape(-1)
+        mk, sk = mean[keep], scale[keep]
+        A = (G[keep][:, keep] - n * mk[:, None] * mk[None, :]) / sk[:, None] / sk[None, :]
+        A.diagonal().add_(float(alpha))
+        nc = counts[classes]
+        rhs = (2.0 * self.class_sums[classes][:, keep] - total[keep] - mk[None, :] * (2.0 * nc - n)[:, None]) / sk[None, :]
+        coef = torch.zeros((len(classes), self.D), dtype=torch.float64, device=self.device)
+        if len(keep):
+            coef[:, keep] = torch.linalg.solve(A, rhs.T).T
+        return RidgeSolution(mean, scale, coef, (2.0 * nc - n) / n, classes)
+
+    def to_model(self, alpha: float = 1.0, class_names=None, params=None) -> LinearModel:
+        """The `LinearModel` of `solve(alpha)`; ``class_names``: one name per class of the statistics (all n_classes), of which
+        the classes that have rows keep theirs."""
+        s = self.solve(alpha)
+        classes = s.classes.cpu().numpy()
+        if class_names is not None:
+            if len(class_names) != self.n_classes:
+                raise ValueError(f"class_names must name all {self.n_classes} classes, got {len(class_names)}")
+            class_names = [class_names[int(c)] for c in classes]
+        return LinearModel(s.mean, s.scale, s.coef, s.intercept, classes, self.feature_keys, self.n_out, class_names, params)
+
+
+def _np(a):
+    import numpy as np
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)

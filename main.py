@@ -122,6 +122,14 @@ ex.main_from_audio(audio, labels, a.n_filters, a.filterbank, a.feature_set, a.mu
                    speed=speed, **({{}} if cd.mask_from_args(a) is None else {{"mask": cd.mask_from_args(a)}}),
                    **({{"model_out": a.save_model}} if a.save_model else {{}}))
 """
+# --readout stream-ridge: the same call with the passes over the training split, the penalty and the plans of the later passes
+_LAST = """                   **({{"model_out": a.save_model}} if a.save_model else {{}}))
+"""
+IN_MEMORY_STREAM_RIDGE = IN_MEMORY[:-len(_LAST)] + """                   **({{"model_out": a.save_model}} if a.save_model else {{}}),
+                   epochs=a.augment_epochs, ridge_alpha=a.ridge_alpha,
+                   epoch_plans=lambda e: cd.epoch_plans(e, len(audio), augment, corrupt, room, reverb, pace))
+"""
+assert IN_MEMORY.endswith(_LAST)
 
 
 def _launch(script_args, nproc: int):
@@ -150,7 +158,8 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     cuts every such clip to its speech on the GPU, SPEC.md 1.15; augment_variable_length: stage 1 lets the corruption, the
     reverberation and the mask flags through on such clips, SPEC.md 1.16; save_model: a path -- stage 2 writes the front half
     of the model file there and stage 3 adds its readout, or the in-memory route with a PyTorch readout writes it whole,
-    SPEC.md 6; classify.py labels new audio with it)."""
+    SPEC.md 6; classify.py labels new audio with it; readout="stream-ridge" with augment_epochs, ridge_alpha: the in-memory
+    route trains a ridge readout from statistics updated on the GPU, SPEC.md 7, and keeps no training row)."""
     args = argparse.Namespace(n_filters=n_filters, filterbank=filterbank, feature_set=feature_set,
                               multiplier=multiplier, commands=None, commands_file=None, dataset_root=None,
                               max_per_class=None, synthetic_per_class=int(os.environ.get("LSM_SYNTHETIC_PER_CLASS", "0")),
@@ -160,11 +169,27 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
                               speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
                               time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0,
                               trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0, augment_variable_length=False,
-                              save_model=None)
+                              save_model=None, augment_epochs=None, ridge_alpha=None)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
     vars(args).update(extra)
+    streamed = args.readout == "stream-ridge"
+    if streamed and not in_memory:
+        raise SystemExit("--readout stream-ridge needs --in-memory: the statistics are updated as the feature rows leave the "
+                         "reservoir, and the file route keeps every row in File 2")
+    if not streamed and (args.augment_epochs is not None or args.ridge_alpha is not None):
+        raise SystemExit("--augment-epochs and --ridge-alpha need --readout stream-ridge: the other readouts keep every "
+                         "training row once and fix their own penalty")
+    if streamed:
+        args.augment_epochs = 1 if args.augment_epochs is None else int(args.augment_epochs)
+        args.ridge_alpha = 1.0 if args.ridge_alpha is None else float(args.ridge_alpha)
+        if args.augment_epochs < 1:
+            raise SystemExit(f"--augment-epochs {args.augment_epochs}: must be >= 1")
+        if args.time_segments != 1:
+            raise SystemExit("--readout stream-ridge needs --time-segments 1: the statistics hold one feature row per clip")
+    else:
+        del args.augment_epochs, args.ridge_alpha          # without the new flags every command is what it was
     if args.trim_silence is not None and not args.variable_length:
         raise SystemExit("--trim-silence needs --variable-length: a trimmed clip has a length of its own")
     if args.variable_length and (in_memory or args.nproc > 1):
@@ -175,9 +200,9 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
         ns = {k: v for k, v in vars(args).items() if k not in ("readout", "nproc", "packed")}
         # a PyTorch readout on the in-memory route runs where the features already are: scaler, readout and
         # predictions on the GPU, no File 2 reload; File 2 is still written
-        device_readout = args.readout if args.readout in ("torch-ridge", "torch-logistic") else None
+        device_readout = args.readout if args.readout in ("torch-ridge", "torch-logistic", "stream-ridge") else None
         ns["device_readout"] = device_readout
-        code = f"import sys; sys.path.insert(0, {HERE!r})\n" + IN_MEMORY.format(ns=ns)
+        code = f"import sys; sys.path.insert(0, {HERE!r})\n" + (IN_MEMORY_STREAM_RIDGE if streamed else IN_MEMORY).format(ns=ns)
         if args.nproc > 1:            # torch.distributed.run needs a file to start
             import tempfile
             with tempfile.NamedTemporaryFile("w", suffix="_lsm_in_memory.py", delete=False) as fh:
@@ -222,8 +247,14 @@ if __name__ == "__main__":
     ap.add_argument("--num-output-neurons", type=int, default=None, help="Read-out neurons (stage 2; default 400).")
     ap.add_argument("--small-world-k", type=int, default=None, help="Ring neighbours (stage 2; default int(0.2 N)).")
     ap.add_argument("--seed", type=int, default=None, help="Reservoir wiring seed (stage 2; default 42).")
-    ap.add_argument("--readout", type=str, default=None, choices=["sklearn", "torch-ridge", "torch-logistic"],
-                    help="Readout of stage 3 (default: scikit-learn logistic regression, or LSM_READOUT).")
+    ap.add_argument("--readout", type=str, default=None, choices=["sklearn", "torch-ridge", "torch-logistic", "stream-ridge"],
+                    help="Readout of stage 3 (default: scikit-learn logistic regression, or LSM_READOUT).  stream-ridge "
+                         "(with --in-memory): a ridge readout trained from statistics updated on the GPU, no training row kept.")
+    ap.add_argument("--augment-epochs", type=int, default=None, metavar="E",
+                    help="With --readout stream-ridge: run the training split E times, epoch e with the augmentation plans "
+                         "of --augment-seed + e (default 1).")
+    ap.add_argument("--ridge-alpha", type=float, default=None, metavar="A",
+                    help="With --readout stream-ridge: the ridge penalty (default 1.0).")
     ap.add_argument("--nproc", type=int, default=int(os.environ.get("LSM_NPROC", "1")),
                     help="Ranks (one per GPU) for stages 1 and 2.")
     ap.add_argument("--time-segments", type=int, default=1,
@@ -273,4 +304,4 @@ if __name__ == "__main__":
                  time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob,
                  variable_length=a.variable_length, max_seconds=a.max_seconds, trim_silence=a.trim_silence,
                  trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms, augment_variable_length=a.augment_variable_length,
-                 save_model=a.save_model)
+                 save_model=a.save_model, augment_epochs=a.augment_epochs, ridge_alpha=a.ridge_alpha)
