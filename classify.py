@@ -6,7 +6,9 @@ file is decoded like create_dataset.py decodes it (mono, 16 kHz, one clip of the
 reservoir -> ``DeviceReadout.score_rows`` on the GPU, and one line is printed per file: name, class name, top-two logit
 margin.  With ``--stream`` every file is one open-ended stream at its own length: it is pushed in chunks through
 ``AudioStreamBank.push_scores`` (sliding windows of ``--window-ms`` every ``--hop-ms``), the window labels go through
-``pipeline.debounce`` and the events are printed.  There is no CPU fallback.
+``pipeline.debounce`` and the events are printed.  With ``--stream --endpoint`` the stream is cut into utterances on the device
+instead (``UtteranceBank.push_scores``, SPEC.md 1.17) -- the form a model trained with ``--variable-length --trim-silence`` was
+fitted on -- and one line is printed per utterance: start and end time, then the label.  There is no CPU fallback.
 """
 import argparse
 from pathlib import Path
@@ -117,6 +119,76 @@ def classify_streams(model, files, window_ms: float, hop_ms: float, hold: int, b
     return out
 
 
+def endpoint_from_args(a, max_bins: int) -> dict:
+    """The ``frontend.EndpointStream`` keywords the ``--endpoint-*`` flags ask for; a time bin is 10 ms."""
+    pad, hang, span = (int(round(v / 10.0)) for v in (a.endpoint_pad_ms, a.endpoint_hang_ms, a.endpoint_min_ms))
+    if a.endpoint_top_db is not None and not (np.isfinite(a.endpoint_top_db) and a.endpoint_top_db > 0):
+        raise SystemExit("--endpoint-top-db must be a finite number of dB above 0")
+    if not 0 <= pad < max_bins:
+        raise SystemExit(f"--endpoint-pad-ms must lie in [0, {10 * max_bins}) for this model's clips of {max_bins} time bins")
+    if not max(pad, 1) <= hang <= 1024:
+        raise SystemExit("--endpoint-hang-ms must be at least --endpoint-pad-ms and 10, and at most 10240")
+    if not 3 <= span <= max_bins:
+        raise SystemExit(f"--endpoint-min-ms must lie in [30, {10 * max_bins}]")
+    return dict(top_db=a.endpoint_top_db, floor_db=a.endpoint_floor_db, pad_bins=pad, hang_bins=hang, min_span_bins=span,
+                max_bins=int(max_bins))
+
+
+def classify_utterances(model, files, endpoint: dict, chunk_ms: float = 500.0):
+    """The endpointed stream route: every file one stream cut into utterances on the device, ``(file, start ms, end ms, class
+    name)`` per utterance."""
+    import create_dataset as cd
+    import torch
+    from lsm_speech_classifier_amd import frontend, pipeline, readout
+    fe, net = pipeline.pipeline_from_params(model.params)
+    why = frontend.ragged_refusal(fe.n_samples, fe.time_bins)
+    if why:
+        raise SystemExit(f"--endpoint needs a model whose front end takes ragged batches: {why}")
+    ro = readout.DeviceReadout(model, net.device)
+    hop = frontend.RAGGED_HOP
+    out = []
+    for f in files:
+        rate, data = cd._decode_wav(Path(f))
+        if rate != cd.SAMPLE_RATE:
+            from math import gcd
+            from scipy.signal import resample_poly
+            g = gcd(int(rate), cd.SAMPLE_RATE)
+            data = resample_poly(data, cd.SAMPLE_RATE // g, int(rate) // g).astype(np.float32)
+        n_hops = -(-len(data) // hop)
+        if n_hops < 1:
+            continue
+        audio = np.zeros((1, n_hops * hop), dtype=np.float32)
+        audio[0, :len(data)] = data
+        bank = pipeline.UtteranceBank(frontend.EndpointStream(1, device=net.device, **endpoint), fe, net, model.feature_keys,
+                                      readout=ro)
+        chunk = max(1, int(round(chunk_ms / 10.0)))
+        for at in range(0, n_hops, chunk):
+            h = min(chunk, n_hops - at)
+            block = np.zeros((1, chunk * hop), dtype=np.float32)
+            block[0, :h * hop] = audio[0, at * hop:(at + h) * hop]
+            _, labels, bins, first, _ = bank.push_scores(block, [h], [1 if at + chunk >= n_hops else 0])
+            labels, bins, first = labels.cpu().numpy(), bins.cpu().numpy(), first.cpu().numpy()
+            for u in np.nonzero(bins)[0]:
+                out.append((str(f), 10.0 * int(first[u]), 10.0 * int(first[u] + bins[u]), class_name(model, int(labels[u]))))
+                print(f"{f}\t{out[-1][1]:.0f} ms\t{out[-1][2]:.0f} ms\t{out[-1][3]}")
+        torch.cuda.synchronize()
+    return out
+
+
+def add_endpoint_flags(ap) -> None:
+    ap.add_argument("--endpoint", action="store_true",
+                    help="With --stream: cut every stream into utterances on the device and label each one.")
+    ap.add_argument("--endpoint-top-db", type=float, default=30.0,
+                    help="With --endpoint: a bin is speech above this many dB under the loudest of the last second (default 30).")
+    ap.add_argument("--endpoint-floor-db", type=float, default=-60.0,
+                    help="With --endpoint: ... and above this level relative to full scale (default -60).")
+    ap.add_argument("--endpoint-pad-ms", type=float, default=30.0, help="With --endpoint: kept around an utterance (default 30).")
+    ap.add_argument("--endpoint-hang-ms", type=float, default=200.0,
+                    help="With --endpoint: silence that closes an utterance (default 200).")
+    ap.add_argument("--endpoint-min-ms", type=float, default=30.0,
+                    help="With --endpoint: a shorter burst is dropped as a click (default 30).")
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="Label wav files with a saved model (main.py --save-model).")
     ap.add_argument("--model", type=str, required=True, help="Model file written by main.py --save-model.")
@@ -129,6 +201,7 @@ def build_parser():
                     help="With --stream: a label fires after winning this many consecutive windows (default 3).")
     ap.add_argument("--background", type=int, default=-1,
                     help="With --stream: label index that never fires (default: none).")
+    add_endpoint_flags(ap)
     return ap
 
 
@@ -136,7 +209,11 @@ if __name__ == "__main__":
     a = build_parser().parse_args()
     from lsm_speech_classifier_amd import readout
     model = readout.LinearModel.load(a.model)
-    if a.stream:
+    if a.endpoint and not a.stream:
+        raise SystemExit("--endpoint needs --stream")
+    if a.endpoint:
+        classify_utterances(model, a.files, endpoint_from_args(a, int(model.params["time_bins"])))
+    elif a.stream:
         classify_streams(model, a.files, a.window_ms, a.hop_ms, a.hold, a.background)
     else:
         classify_clips(model, a.files)

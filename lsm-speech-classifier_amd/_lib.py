@@ -250,6 +250,16 @@ FIT_SIGS = {
 }
 FIT_SYMBOLS = tuple(FIT_SIGS)
 
+# include/lsm_hip_endpoint.h (SPEC.md §1.17): stream endpointing -- utterances cut from audio streams into ragged slots
+ENDPOINT_SIGS = {
+    "lsm_endpoint_state_bytes": (C.c_long, [c_int, c_int]),
+    "lsm_endpoint_max_utterances": (c_int, [c_int, c_int, c_int]),
+    "lsm_endpoint_stream_f32": (c_int, [c_void, c_int, c_int, c_void, c_void, c_double, c_double, c_int, c_int, c_int, c_int,
+                                        c_int, c_void, c_void, c_int, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
+                                        c_void]),
+}
+ENDPOINT_SYMBOLS = tuple(ENDPOINT_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -302,7 +312,7 @@ def load():
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
                               + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
                               + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items()) + list(RAGGED_AUGMENT_SIGS.items())
-                              + list(READOUT_SIGS.items()) + list(FIT_SIGS.items())):
+                              + list(READOUT_SIGS.items()) + list(FIT_SIGS.items()) + list(ENDPOINT_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -15,17 +15,18 @@
 //              destination allow and by words otherwise.  Samples move as words, so -0.0 and NaN payloads stay.
 // Every index is formed from clamped counts: 0 <= len_b <= n_samples, NB_b <= time_bins, first + bins <= NB_b.
 #include "lsm_common.h"
+#include "bin_energy.h"
 #include "trim_body.h"
 #include <cmath>
 
 namespace {
 
 using namespace lsm_trim;
+using lsm_energy::PITCH;                    // the tile and the pinned sum: bin_energy.h, shared with endpoint.hip
+using lsm_energy::TILE_BINS;
+using lsm_energy::TILE_WORDS;
 
 constexpr int THREADS = 256;
-constexpr int TILE_BINS = 64;               // one wave sums a tile
-constexpr int PITCH = HOP + 1;              // words per staged bin: odd mod 64
-constexpr int TILE_WORDS = TILE_BINS * PITCH;
 
 struct TrimArgs {
     const float *audio;                     // (n_clips, n_samples)
@@ -59,22 +60,9 @@ __global__ __launch_bounds__(THREADS) void trim_kernel(const TrimArgs a)
     // ---- energies ------------------------------------------------------------------------------------------------------
     for (int j0 = 0; j0 < nb; j0 += TILE_BINS) {
         const int nbt = min(TILE_BINS, nb - j0);
-        const int base = HOP * j0;
-        for (int k = tid; k < HOP * nbt; k += THREADS) {
-            const int at = base + k;                                // < 160 * nb; read only below len <= n_samples
-            tile[(k / HOP) * PITCH + k % HOP] = at < len ? in[at] : 0.0f;
-        }
+        lsm_energy::stage_bins<THREADS>(in, len, j0, nbt, tile, tid);   // < 160 * nb; read only below len <= n_samples
         __syncthreads();
-        if (tid < nbt) {
-            const float *row = tile + tid * PITCH;
-            double acc = 0.0;
-#pragma unroll 16
-            for (int i = 0; i < HOP; ++i) {
-                const double x = (double)row[i];
-                acc += x * x;
-            }
-            energy[j0 + tid] = acc;
-        }
+        if (tid < nbt) energy[j0 + tid] = lsm_energy::row_energy(tile + tid * PITCH);
         __syncthreads();
     }
     if (nb == 0) __syncthreads();                                   // the scalars above, where no tile ran

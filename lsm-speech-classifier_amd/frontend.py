@@ -1829,6 +1829,165 @@ class SilenceTrimmer:
         return (out, bins, first, energy) if want_energy else (out, bins, first)
 
 
+# ---- stream endpointing in front of the ragged launches (SPEC.md §1.17, include/lsm_hip_endpoint.h) ----------------------
+ENDPOINT_MAX_HOPS = 4096        # hops of one push
+ENDPOINT_MAX_WINDOW = 1024      # window_bins and hang_bins: up to 1024
+ENDPOINT_MAX_BINS = 4096        # max_bins: 3 .. 4096
+ENDPOINT_CUT, ENDPOINT_FLUSHED = 1, 2       # bits of an utterance's flags
+
+
+def endpoint_floor(floor_db) -> float:
+    """The absolute activity floor of `lsm_endpoint_stream_f32` as a bin energy: ``160 * 10 ** (floor_db / 10)``, the energy of
+    a bin of 160 samples at ``floor_db`` dB relative to full scale (finite), 0.0 for None: no floor."""
+    if floor_db is None:
+        return 0.0
+    floor_db = float(floor_db)
+    if not np.isfinite(floor_db):
+        raise ValueError(f"floor_db must be a finite number of dB, or None, got {floor_db!r}")
+    return RAGGED_HOP * 10.0 ** (floor_db / 10.0)
+
+
+def endpoint_max_utterances(n_hops: int, pad_bins: int, hang_bins: int, max_bins: int) -> int:
+    """The slots per stream no push of ``n_hops`` hops can exceed: ``2 + (n_hops - 1) / d``, d the fewest bins between the
+    closes of two kept utterances -- ``min(hang_bins + 1, max_bins)``, `lsm_endpoint_max_utterances`' divisor, and where
+    ``max_bins >= hang_bins + 3`` also ``max(max_bins - pad_bins, max_bins + pad_bins - hang_bins)``: a forced cut behind a
+    close by silence starts ``hang_bins - pad_bins`` bins before that close (SPEC.md §1.17).  Host integers only."""
+    H, P, G, M = int(n_hops), int(pad_bins), int(hang_bins), int(max_bins)
+    d = min(G + 1, M)
+    if G + 3 <= M:
+        d = min(d, max(M - P, M + P - G))
+    return 2 + (H - 1) // d
+
+
+class Utterances(NamedTuple):
+    """What one `EndpointStream.push` emitted, device tensors: ``audio`` float32 (n_streams * max_utts, 160 * max_bins), slot
+    ``b * max_utts + u`` holding stream b's u-th utterance of the push at its start and +0.0 behind; ``bins`` int32
+    (n_streams * max_utts,): its bins, 0 for an empty slot; ``first`` int64 and ``flags`` int32 of the same shape: its first
+    bin on the stream's timeline and `ENDPOINT_CUT` / `ENDPOINT_FLUSHED` (empty slots: unspecified); ``count`` int32
+    (n_streams,): the emitted slots per stream."""
+    audio: torch.Tensor
+    bins: torch.Tensor
+    first: torch.Tensor
+    flags: torch.Tensor
+    count: torch.Tensor
+
+
+class EndpointStream:
+    """``n_streams`` open-ended audio streams cut into utterances on the device (`lsm_endpoint_stream_f32`, SPEC.md §1.17).
+    A bin of 160 samples is active when its energy exceeds ``top_db`` dB under the loudest of the last ``window_bins`` bins and
+    ``floor_db`` dB relative to full scale; an utterance opens ``pad_bins`` bins before an active bin, closes ``pad_bins`` bins
+    behind the last active one once ``hang_bins`` quiet bins have followed it, is cut at ``max_bins`` bins, and is dropped as
+    a click when its active span has fewer than ``min_span_bins`` bins.  Every ``push`` advances each stream by the whole hops
+    it delivers from the state the bank holds; a stream cut into pushes at any hop boundaries emits, byte for byte, the
+    utterances of its uncut run.  The slots of a push are a ragged batch: `SpikeFrontEnd.encode_ragged`,
+    `pipeline.step_fused_ragged` and `SNN.run_batch(lengths=...)` take ``audio`` and ``bins`` unread."""
+
+    def __init__(self, n_streams: int, top_db=30.0, floor_db=-60.0, window_bins: int = 100, pad_bins: int = 3,
+                 hang_bins: int = 20, min_span_bins: int = 3, max_bins: int = 100, device=None):
+        self.n_streams = int(n_streams)
+        self.top_db, self.floor_db = top_db, floor_db
+        self.ratio, self.floor = trim_ratio(top_db), endpoint_floor(floor_db)
+        self._window_bins, self.pad_bins, self.hang_bins = int(window_bins), int(pad_bins), int(hang_bins)
+        self.min_span_bins, self._max_bins = int(min_span_bins), int(max_bins)
+        W, P, G, A, M = self.window_bins, self.pad_bins, self.hang_bins, self.min_span_bins, self.max_bins
+        if self.n_streams < 1:
+            raise ValueError(f"EndpointStream needs n_streams >= 1, got {n_streams}")
+        if not 1 <= W <= ENDPOINT_MAX_WINDOW:
+            raise ValueError(f"window_bins must lie in [1, {ENDPOINT_MAX_WINDOW}], got {window_bins}")
+        if not RAGGED_MIN_BINS <= M <= ENDPOINT_MAX_BINS:
+            raise ValueError(f"max_bins must lie in [{RAGGED_MIN_BINS}, {ENDPOINT_MAX_BINS}], got {max_bins}")
+        if not 0 <= P < M:
+            raise ValueError(f"pad_bins must lie in [0, max_bins = {M}), got {pad_bins}")
+        if not max(P, 1) <= G <= ENDPOINT_MAX_WINDOW:
+            raise ValueError(f"hang_bins must lie in [max(pad_bins, 1) = {max(P, 1)}, {ENDPOINT_MAX_WINDOW}], got {hang_bins}")
+        if not RAGGED_MIN_BINS <= A <= M:
+            raise ValueError(f"min_span_bins must lie in [{RAGGED_MIN_BINS}, max_bins = {M}], got {min_span_bins}")
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = indexed_device(device)
+        self.state_bytes = int(self.lib.lsm_endpoint_state_bytes(W, M))
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self._outputs = {}                                              # per n_hops: the slot buffers of a push
+
+    # a state block means what it says only under the window_bins and max_bins it was made with: read-only
+    @property
+    def window_bins(self) -> int:
+        return self._window_bins
+
+    @property
+    def max_bins(self) -> int:
+        return self._max_bins
+
+    @property
+    def params(self) -> dict:
+        """The rule's parameters: what a second `EndpointStream` needs to cut the same utterances."""
+        return dict(top_db=self.top_db, floor_db=self.floor_db, window_bins=self.window_bins, pad_bins=self.pad_bins,
+                    hang_bins=self.hang_bins, min_span_bins=self.min_span_bins, max_bins=self.max_bins)
+
+    def max_utterances(self, n_hops: int) -> int:
+        """Slots per stream of a push of ``n_hops`` hops (`endpoint_max_utterances`; never below the library's figure)."""
+        return max(endpoint_max_utterances(n_hops, self.pad_bins, self.hang_bins, self.max_bins),
+                   int(self.lib.lsm_endpoint_max_utterances(int(n_hops), self.hang_bins, self.max_bins)))
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: their state blocks back to zeros."""
+        slots = checked_slots(slots, self.n_streams)
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+
+    def _counts(self, values, n_hops: int, what: str):
+        """``hops`` / ``finish`` as the int32 device tensor the kernel reads, or None: host integers checked, a device tensor
+        taken as it is -- never read back, the kernel clamps it."""
+        if values is None:
+            return None
+        n = self.n_streams
+        if torch.is_tensor(values) and values.is_cuda:
+            if values.dtype != torch.int32 or tuple(values.shape) != (n,):
+                raise ValueError(f"{what} must hold {n} int32 values, got {values.dtype} {tuple(values.shape)}")
+            return values.to(self.device).contiguous()
+        arr = np.asarray(values.numpy() if torch.is_tensor(values) else values)
+        if arr.dtype == np.bool_:
+            arr = arr.astype(np.int64)
+        if arr.shape != (n,) or arr.dtype.kind not in "iu" or (arr < 0).any() or (arr > n_hops).any():
+            raise ValueError(f"{what} must be {n} integers in [0, {n_hops}], got {values!r}")
+        return torch.from_numpy(arr.astype(np.int32)).to(self.device, non_blocking=True)
+
+    def push(self, audio, hops=None, finish=None) -> Utterances:
+        """``audio`` (n_streams, H * 160) float32, NumPy or tensor, 1 <= H <= 4096: stream b's new samples are the first
+        ``hops[b] * 160`` of its row.  ``hops``: n_streams host integers in [0, H] (checked) or an int32 device tensor (not
+        read: the kernel clamps it); None: H everywhere.  ``finish``: n_streams flags, host or device, non-zero where the stream
+        ends behind this push's hops -- an open utterance is flushed and the stream starts afresh; None: no stream ends.
+        Returns `Utterances`, device tensors produced on the current stream with NO host synchronisation.  The buffers belong
+        to the bank, one set per H: the next push of the same H overwrites them."""
+        audio = as_float32(audio)
+        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % RAGGED_HOP or audio.shape[1] < RAGGED_HOP \
+                or audio.shape[1] > ENDPOINT_MAX_HOPS * RAGGED_HOP:
+            raise ValueError(f"audio must be ({self.n_streams}, H * {RAGGED_HOP}) with 1 <= H <= {ENDPOINT_MAX_HOPS}, got "
+                             f"{tuple(audio.shape)}")
+        H = int(audio.shape[1]) // RAGGED_HOP
+        n, M = self.n_streams, self.max_bins
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device).contiguous()
+            counts = self._counts(hops, H, "hops")
+            ends = self._counts(finish, 1, "finish")
+            out = self._outputs.get(H)
+            if out is None:
+                U = self.max_utterances(H)
+                out = self._outputs[H] = Utterances(
+                    torch.zeros((n * U, RAGGED_HOP * M), dtype=torch.float32, device=self.device),
+                    torch.zeros((n * U,), dtype=torch.int32, device=self.device),
+                    torch.zeros((n * U,), dtype=torch.int64, device=self.device),
+                    torch.zeros((n * U,), dtype=torch.int32, device=self.device),
+                    torch.zeros((n,), dtype=torch.int32, device=self.device))
+            U = int(out.bins.shape[0]) // n
+            _lib.check(self.lib.lsm_endpoint_stream_f32(
+                _dev(audio), n, H, _dev(counts) if counts is not None else None, _dev(ends) if ends is not None else None,
+                C.c_double(self.ratio), C.c_double(self.floor), self.window_bins, self.pad_bins, self.hang_bins,
+                self.min_span_bins, M, _dev(self.state), _dev(self.state), U, _dev(out.audio), _dev(out.bins), _dev(out.first),
+                _dev(out.flags), _dev(out.count), None, None, torch.cuda.current_stream(self.device).cuda_stream),
+                "lsm_endpoint_stream_f32")
+        return out
+
+
 # ---- SpecAugment-style masks inside the spike encoders (SPEC.md §1.13, include/lsm_hip_mask.h) ---------------------------
 
 def mask_words(starts, widths, n_bits: int) -> np.ndarray:

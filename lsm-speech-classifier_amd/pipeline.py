@@ -1329,20 +1329,186 @@ class AudioStreamBank:
 
     def _through(self, stage, audio, hops):
         """The first ``hops[b]`` hops of every row through ``stage`` (the reverberator, the mixer); the rows keep their length."""
-        hop = int(self.gt.hop)
-        audio = as_float32(audio)
-        if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % hop or audio.shape[1] < hop:
-            raise ValueError(f"audio must be ({self.n_streams}, H * {hop}) with H >= 1, got {tuple(audio.shape)}")
-        new = checked_counts(hops, self.n_streams, int(audio.shape[1]) // hop, "hops")
-        return stage.push(audio, None if hops is None else new * hop)[0]
+        return _stage_through(stage, audio, hops, self.n_streams, int(self.gt.hop))
 
     def _resampled(self, audio, units):
         """A push at the resampler's input rate -> ``(samples, hops)`` as the front end takes them."""
-        rs = self.resampler
-        audio, _ = checked_pcm(audio, self.n_streams, rs.unit_in)
-        units = checked_counts(units, self.n_streams, int(audio.shape[1]) // rs.unit_in, "units")
-        samples, _ = rs.push(audio, units * rs.unit_blocks)
-        return samples, units * rs.unit_hops
+        return _stream_resampled(self.resampler, audio, units, self.n_streams)
+
+
+def _stage_through(stage, audio, hops, n_streams: int, hop: int):
+    """The first ``hops[b]`` hops of every row of a bank's push through ``stage`` (``frontend.ReverbStream``,
+    ``frontend.MixStream``); the rows keep their length.  One copy for `AudioStreamBank` and `UtteranceBank`."""
+    audio = as_float32(audio)
+    if audio.dim() != 2 or audio.shape[0] != n_streams or audio.shape[1] % hop or audio.shape[1] < hop:
+        raise ValueError(f"audio must be ({n_streams}, H * {hop}) with H >= 1, got {tuple(audio.shape)}")
+    new = checked_counts(hops, n_streams, int(audio.shape[1]) // hop, "hops")
+    return stage.push(audio, None if hops is None else new * hop)[0]
+
+
+def _stream_resampled(rs, audio, units, n_streams: int):
+    """A bank's push at the input rate of its ``frontend.ResampleStream`` -> ``(samples, hops)`` as the stages behind it take
+    them.  One copy for `AudioStreamBank` and `UtteranceBank`."""
+    audio, _ = checked_pcm(audio, n_streams, rs.unit_in)
+    units = checked_counts(units, n_streams, int(audio.shape[1]) // rs.unit_in, "units")
+    samples, _ = rs.push(audio, units * rs.unit_blocks)
+    return samples, units * rs.unit_hops
+
+
+class UtteranceBank:
+    """Audio streams in, utterance feature rows (or labels) out, with no host round trip in between (SPEC.md §1.17):
+    ``endpoint`` (``frontend.EndpointStream``) cuts every push into utterances, whose slots -- a ragged batch of
+    ``n_streams * max_utts`` clips, most of them empty -- go through the ragged route unread: the one-launch step
+    (`step_fused_ragged`) where `step_fused_supported(..., form="ragged")` holds, else `SpikeFrontEnd.encode_ragged` and
+    ``SNN.run_batch(lengths=...)``.  An utterance's row is, bit for bit, that of `features_from_utterances` on its samples taken
+    alone.  ``fe``: a `SpikeFrontEnd` whose rows are the endpoint's slots (``n_samples == 160 * max_bins``, ``time_bins ==
+    max_bins``).  ``fused``: None takes the one-launch step where it is served, False never, True refuses a shape it does not
+    serve.  ``resampler``, ``reverb`` and ``mixer`` are `AudioStreamBank`'s optional stages, in its order, in front of the
+    endpoint detector; with any of them ``hops`` are host integers."""
+
+    def __init__(self, endpoint, fe, net, feature_keys=None, readout=None, resampler=None, reverb=None, mixer=None, fused=None):
+        from .frontend import RAGGED_HOP, ragged_refusal
+        if not hasattr(endpoint, "max_utterances") or not hasattr(endpoint, "push"):
+            raise ValueError("UtteranceBank needs a frontend.EndpointStream")
+        M = int(endpoint.max_bins)
+        why = ragged_refusal(fe.n_samples, fe.time_bins)
+        if why is None and int(fe.time_bins) != M:
+            why = (f"the endpoint detector emits rows of max_bins = {M} bins: the front end needs n_samples = {RAGGED_HOP * M} "
+                   f"and time_bins = {M}, this one has {fe.n_samples} and {fe.time_bins}")
+        if why:
+            raise ValueError(why)
+        n = int(endpoint.n_streams)
+        if resampler is not None:
+            if int(resampler.n_streams) != n:
+                raise ValueError(f"the resampler serves {resampler.n_streams} streams, the endpoint detector {n}")
+            if resampler.unit_blocks * resampler.up != resampler.unit_hops * RAGGED_HOP:
+                raise ValueError(f"a unit of the resampler is {resampler.unit_blocks * resampler.up} samples, not "
+                                 f"{resampler.unit_hops} hops of {RAGGED_HOP}")
+        for name, stage in (("mixer", mixer), ("reverberator", reverb)):
+            if stage is not None and int(stage.n_streams) != n:
+                raise ValueError(f"the {name} serves {stage.n_streams} streams, the endpoint detector {n}")
+        if net.n_channels != fe.n_channels:
+            raise ValueError(f"the front end has {fe.n_channels} channels, the reservoir {net.n_channels}")
+        if indexed_device(endpoint.device) != indexed_device(net.device) or indexed_device(fe.device) != indexed_device(net.device):
+            raise ValueError(f"endpoint detector on {endpoint.device}, front end on {fe.device}, reservoir on {net.device}")
+        self.endpoint, self.fe, self.net, self.feature_keys, self.fused = endpoint, fe, net, feature_keys, fused
+        self.readout = _checked_readout(readout, net, feature_keys)
+        self.resampler = resampler
+        self.stages = [stage for stage in (reverb, mixer) if stage is not None]
+        self.n_streams = n
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: every stage's state back to zero."""
+        if self.resampler is not None:
+            self.resampler.reset(slots)
+        for stage in (*self.stages, self.endpoint):
+            stage.reset(slots)
+
+    def cut(self, audio, hops=None, finish=None):
+        """A push through the optional stages and the endpoint detector: ``frontend.Utterances``."""
+        if self.resampler is not None:
+            audio, hops = _stream_resampled(self.resampler, audio, hops, self.n_streams)
+        for stage in self.stages:
+            audio = _stage_through(stage, audio, hops, self.n_streams, 160)
+        return self.endpoint.push(audio, hops, finish)
+
+    def _takes_fused(self, n_clips: int) -> bool:
+        if self.fused is False:
+            return False
+        served = step_fused_supported(self.fe, self.net, n_clips, "ragged")
+        if self.fused and not served:
+            raise ValueError(f"fused=True: the one-launch ragged step does not serve {n_clips} clips of this front end and reservoir")
+        return served
+
+    def _run(self, audio, bins):
+        """A ragged batch through the route the bank takes: float32 (n, n_feat)."""
+        from .snn import _select_keys
+        fe, net = self.fe, self.net
+        n = int(audio.shape[0])
+        if self._takes_fused(n):
+            rows = torch.zeros((n, len(_select_keys(self.feature_keys)[0]) * net.num_output_neurons), dtype=torch.float32,
+                               device=net.device)
+            step_fused_ragged(fe, net, audio, bins, self.feature_keys, features_out=rows)
+            return rows
+        if fe.n_steps > net.max_steps(n):
+            raise ValueError(f"{n} slots of {fe.n_steps} steps exceed the longest launch the reservoir's plan accepts "
+                             f"({net.max_steps(n)} steps): fewer streams, or a smaller max_bins")
+        raster, steps = fe.encode_ragged(audio, bins)
+        return net.run_batch(raster, self.feature_keys, lengths=steps)[0]
+
+    def _rows(self, utt, compact: bool):
+        with torch.cuda.device(self.net.device):
+            if not compact:
+                return self._run(utt.audio, utt.bins)
+            from .snn import _select_keys
+            bins = utt.bins.cpu().numpy()                               # the one read-back of a compact push
+            idx = np.nonzero(bins)[0]
+            rows = torch.zeros((len(bins), len(_select_keys(self.feature_keys)[0]) * self.net.num_output_neurons),
+                               dtype=torch.float32, device=self.net.device)
+            if len(idx):
+                where = torch.from_numpy(idx).to(self.net.device)
+                rows[where] = self._run(utt.audio[where], bins[idx])
+            return rows
+
+    def push(self, audio, hops=None, finish=None, compact: bool = False):
+        """``audio``, ``hops`` and ``finish`` as ``frontend.EndpointStream.push`` takes them (with a ``resampler``: PCM at its
+        input rate and per-stream UNIT counts, as `AudioStreamBank.push`).  Returns ``(rows, bins, first, flags)``, device
+        tensors over the push's ``n_streams * max_utts`` slots, slot ``b * max_utts + u`` stream b's u-th utterance: ``rows``
+        float32 (slots, n_feat), ``bins`` int32 -- 0 for an empty slot, whose row is unspecified --, ``first`` int64 and
+        ``flags`` int32.  Nothing is read on the host: ``bins`` goes to the ragged launches as the endpoint kernel wrote it.
+        ``compact`` = True reads ``bins`` back once and runs only the emitted slots (rows of empty slots: zeros): the same
+        bytes for the emitted ones."""
+        utt = self.cut(audio, hops, finish)
+        return self._rows(utt, compact), utt.bins, utt.first, utt.flags
+
+    def push_scores(self, audio, hops=None, finish=None, compact: bool = False):
+        """``push`` with ``readout.score_rows`` behind it: ``(logits, labels, bins, first, flags)`` -- float64 (slots,
+        n_classes) and int32 (slots,); logits and labels of empty slots are unspecified."""
+        if self.readout is None:
+            raise ValueError("push_scores needs a readout: UtteranceBank(..., readout=readout.DeviceReadout(model, device))")
+        utt = self.cut(audio, hops, finish)
+        logits, labels = self.readout.score_rows(self._rows(utt, compact))
+        return logits, labels, utt.bins, utt.first, utt.flags
+
+
+def utterances_from_recordings(recordings, endpoint_params=None, chunk_hops: int = 100, device=None):
+    """Whole recordings cut into utterances: ``recordings``, a list of n 1-D float32 arrays (zero-padded to whole bins of 160
+    samples), go through one ``frontend.EndpointStream(n, **endpoint_params)`` in pushes of ``chunk_hops`` hops, each
+    recording with ``finish`` at its end.  Returns ``(utterances, table)``: a list of 1-D float32 host arrays and an int64
+    array (len, 4) of ``(recording, first_bin, bins, flags)`` per utterance, ordered by recording, then by time -- what
+    `features_from_utterances` takes.  One read-back per push."""
+    from .frontend import RAGGED_HOP, EndpointStream
+    arrays = [np.ascontiguousarray(np.asarray(r, dtype=np.float32)) for r in recordings]
+    for r, a in enumerate(arrays):
+        if a.ndim != 1:
+            raise ValueError(f"recording {r} must be a 1-D array, got shape {tuple(a.shape)}")
+    n, H = len(arrays), int(chunk_hops)
+    if n < 1 or H < 1:
+        raise ValueError(f"utterances_from_recordings needs at least one recording and chunk_hops >= 1, got {n}, {chunk_hops}")
+    ep = EndpointStream(n, device=device, **(endpoint_params or {}))
+    U = ep.max_utterances(H)
+    nb = np.array([-(-len(a) // RAGGED_HOP) for a in arrays], dtype=np.int64)
+    found = [[] for _ in range(n)]
+    for lo in range(0, max(int(nb.max()), 1), H):
+        block = np.zeros((n, H * RAGGED_HOP), dtype=np.float32)
+        for r, a in enumerate(arrays):
+            part = a[lo * RAGGED_HOP:(lo + H) * RAGGED_HOP]
+            block[r, :len(part)] = part
+        hops = np.clip(nb - lo, 0, H)
+        ends = ((nb > lo) | (lo == 0)) & (nb <= lo + H)                 # the push that holds the recording's last bin
+        utt = ep.push(block, hops, ends.astype(np.int64))
+        count, bins = utt.count.cpu().numpy(), utt.bins.cpu().numpy().reshape(n, U)
+        if not count.any():
+            continue
+        audio, first, flags = utt.audio.cpu().numpy().reshape(n, U, -1), utt.first.cpu().numpy().reshape(n, U), \
+            utt.flags.cpu().numpy().reshape(n, U)
+        for r in range(n):
+            for u in range(int(count[r])):
+                found[r].append((audio[r, u, :RAGGED_HOP * int(bins[r, u])].copy(), (r, int(first[r, u]), int(bins[r, u]),
+                                                                                     int(flags[r, u]))))
+    utterances = [x for per in found for x, _ in per]
+    table = np.array([row for per in found for _, row in per], dtype=np.int64).reshape(-1, 4)
+    return utterances, table
 
 
 def sliding_features_from_recordings(recordings, fe, net, feature_keys, segment_steps: int, window_segments: int,
