@@ -16,17 +16,13 @@ SOURCES = ["lsm_api.hip", "frontend.hip", "mask.hip", "frontend_stream.hip", "me
            "lif_pair_wide_1.hip", "lif_pair_wide_2.hip", "lif_pair_wide_3.hip", "lif_pair_wide_4.hip"]
 HEADERS = ["lsm_common.h", "lif_common.h", "lif_kernel.h", "lif_dense.h", "lif_ring.h", "lif_pair.h", "spikes_body.h",
            "gammatone_body.h", "gammatone_spikes_body.h", "gammatone_spikes_kernel.inc", "gammatone_spikes_raster_out.inc", "step_fused_tail.inc", "step_fused_bits.inc", "step_fused_family.inc", "step_fused_forms.h",
-           "lif_dense_kernel.inc", "lif_dense_pack_raster.inc", "mel_spikes_kernel.inc", "mel_body.h", "resample_body.h", "mix_body.h", "reverb_body.h", "trim_body.h", "bin_energy.h", "endpoint_body.h", "reservoir_facts.h"]
+           "lif_dense_kernel.inc", "lif_dense_pack_raster.inc", "mel_spikes_kernel.inc", "mel_body.h", "resample_body.h", "mix_body.h", "reverb_body.h", "trim_body.h", "bin_energy.h", "endpoint_body.h", "reservoir_facts.h", "stream_state.h"]
 PUBLIC_HEADERS = ["lsm_hip.h", "lsm_hip_streams.h", "lsm_hip_audio.h", "lsm_hip_mel_stream.h", "lsm_hip_resample.h", "lsm_hip_adaptive.h", "lsm_hip_mix.h", "lsm_hip_reverb.h", "lsm_hip_speed.h"]        # include/: the C ABI
-MASK_HEADERS = ["lsm_hip_mask.h"]       # include/: the masked encoders (SPEC.md 1.13), hashed like the nine above
-RAGGED_HEADERS = ["lsm_hip_ragged.h"]   # include/: the ragged front end (SPEC.md 1.14), hashed likewise
-STEP_HEADERS = ["lsm_hip_step.h"]       # include/: the fused step launch, hashed likewise
-STEP_STATE_HEADERS = ["lsm_hip_step_state.h"]   # include/: the fused step with state and segments (SPEC.md 4f), hashed likewise
-TRIM_HEADERS = ["lsm_hip_trim.h"]       # include/: silence trimming in front of the ragged front end (SPEC.md 1.15), hashed likewise
-RAGGED_AUGMENT_HEADERS = ["lsm_hip_ragged_augment.h"]   # include/: mixer and masks on ragged launches (SPEC.md 1.16), hashed likewise
-READOUT_HEADERS = ["lsm_hip_readout.h"]     # include/: scaler and linear readout on the device (SPEC.md 6), hashed likewise
-FIT_HEADERS = ["lsm_hip_fit.h"]             # include/: the streaming ridge fit's statistics (SPEC.md 7), hashed likewise
-ENDPOINT_HEADERS = ["lsm_hip_endpoint.h"]   # include/: stream endpointing in front of the ragged launches (SPEC.md 1.17), hashed likewise
+# include/: the headers of the later parts of the C ABI, hashed like the nine above -- masked encoders (SPEC.md 1.13), ragged
+# front end (1.14), fused step with state and segments (SPEC.md 4f), silence trimming (1.15), ragged
+# augmentation (1.16), device readout (6), streaming ridge fit (7), stream endpointing (1.17)
+ABI_HEADERS = ["lsm_hip_mask.h", "lsm_hip_ragged.h", "lsm_hip_step.h", "lsm_hip_step_state.h", "lsm_hip_trim.h",
+               "lsm_hip_ragged_augment.h", "lsm_hip_readout.h", "lsm_hip_fit.h", "lsm_hip_endpoint.h"]
 LIB_NAME = "liblsm_hip.so"
 # -ffp-contract=off: the kernels must round every float operation exactly like the CPU oracle.
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
@@ -61,8 +57,7 @@ def source_id(include_dir: str | None = None) -> str:
     h = hashlib.sha256()
     include_dir = include_dir or os.path.join(ROOT, "include")
     files = sorted(os.path.join(PKG_DIR, "csrc", f) for f in SOURCES + HEADERS) + [os.path.join(include_dir, f)
-                                                                                  for f in PUBLIC_HEADERS + MASK_HEADERS + RAGGED_HEADERS + STEP_HEADERS
-                                                                                  + STEP_STATE_HEADERS + TRIM_HEADERS + RAGGED_AUGMENT_HEADERS + READOUT_HEADERS + FIT_HEADERS + ENDPOINT_HEADERS]
+                                                                                  for f in PUBLIC_HEADERS + ABI_HEADERS]
     for path in files:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:

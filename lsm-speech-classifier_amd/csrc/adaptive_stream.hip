@@ -14,12 +14,15 @@
 //      wave-uniform); lane c holds column c's bits and stores them, a word per column where n_thr = 4;
 //   4. the last min(L - 1, columns so far) extrema move to the front of `ext` for the next chunk, and at the end into the state.
 // LDS: 2 * (L - 1 + 64) + 2 * ADP_WAVES * 64 values of T and a latch word per filter -- nothing that grows with H.
-#include "lsm_common.h"
+// state_in, state_out and stream_cols follow DESIGN.md "The state block" (stream_state.h).
+#include "spikes_body.h"
+#include "stream_state.h"
 #include <math.h>
 
 namespace {
 
-constexpr int MAX_THR = 8;
+using lsm_fe::MAX_THR;
+using namespace lsm_state;
 constexpr int ADP_WAVES = 4;                // waves per workgroup: one per SIMD of its CU
 constexpr int ADP_THREADS = ADP_WAVES * 64;
 constexpr int ADP_CHUNK = 64;               // columns per chunk: a lane each
@@ -39,7 +42,7 @@ __host__ __device__ inline size_t state_used_bytes(int n_filters, int window, in
 }
 __host__ __device__ inline size_t state_block_bytes(int n_filters, int window, int elem)
 {
-    return (state_used_bytes(n_filters, window, elem) + 15) & ~(size_t)15;
+    return state_round16(state_used_bytes(n_filters, window, elem));
 }
 inline size_t lds_bytes(int n_filters, int window, int elem)
 {
@@ -89,19 +92,14 @@ __global__ __launch_bounds__(ADP_THREADS) void adaptive_encode_kernel(const Adap
     T *pmax = pmin + ADP_WAVES * ADP_CHUNK;
     uint32_t *latch = reinterpret_cast<uint32_t *>(pmax + ADP_WAVES * ADP_CHUNK);   // [F]
 
-    int hb = a.stream_cols ? a.stream_cols[b] : H;              // workgroup-uniform
-    hb = __builtin_amdgcn_readfirstlane(min(max(hb, 0), H));
+    const int hb = __builtin_amdgcn_readfirstlane(stream_count(a.stream_cols, b, H));   // workgroup-uniform
     const size_t block = state_block_bytes(F, L, (int)sizeof(T));
+    // (the block's pointers formed here and not by state_block: the compiler keeps its register use only this way)
     const unsigned char *sin = a.state_in ? a.state_in + (size_t)b * block : nullptr;
     unsigned char *sout = a.state_out ? a.state_out + (size_t)b * block : nullptr;
-    const bool copy = sout != nullptr && sout != sin;
+    const StateBlock blk{sin, sout, sout != nullptr && sout != sin};
     if (hb == 0) {
-        // an idle stream: its block travels as it is (out of place), or stays (in place)
-        if (copy) {
-            const uint32_t *win = reinterpret_cast<const uint32_t *>(sin);
-            uint32_t *wout = reinterpret_cast<uint32_t *>(sout);
-            for (size_t i = tid; i < block / 4; i += ADP_THREADS) wout[i] = win ? win[i] : 0u;
-        }
+        carry_idle_block<ADP_THREADS>(blk, block, tid);
         return;
     }
 
@@ -177,8 +175,7 @@ __global__ __launch_bounds__(ADP_THREADS) void adaptive_encode_kernel(const Adap
                 const int f = f0 + e * ADP_WAVES;
                 if (f >= F) break;                                  // wave-uniform
                 const T v = vs[e];
-                const T vf = v < fl ? fl : v;                       // a NaN stays a NaN and compares false with every threshold
-                const T val = flat ? (T)0 : (vf - lo) / den;
+                const T val = flat ? (T)0 : lsm_fe::floored_value(v, fl, lo, den);
                 const uint32_t act = latch[f];                      // wave-uniform
                 uint32_t next = 0u, mine = 0u;
 #pragma unroll
@@ -212,30 +209,18 @@ __global__ __launch_bounds__(ADP_THREADS) void adaptive_encode_kernel(const Adap
                     }
                 }
                 if (lane == 0) latch[f] = next;                     // read again by this wave only, in the next chunk
-                if (valid) {
-                    // redundancy: output row f * R + r repeats the filter's row (SPEC.md §1.4)
-                    uint8_t *rrow = dst + (size_t)f * R * row_bytes + (size_t)col * nq;
-                    if (nq == 4) {
-                        const uint32_t word = (mine * 0x00204081u) & 0x01010101u;
-                        for (int r = 0; r < R; ++r) *reinterpret_cast<uint32_t *>(rrow + (size_t)r * row_bytes) = word;
-                    } else {
-                        for (int r = 0; r < R; ++r)
-                            for (int q = 0; q < nq; ++q) rrow[(size_t)r * row_bytes + q] = (uint8_t)((mine >> q) & 1u);
-                    }
-                }
+                // (the rows taken at the lane's column, so that the column's offset is formed once for the R rows)
+                if (valid) lsm_fe::store_column(dst + (size_t)f * R * row_bytes + (size_t)col * nq, row_bytes, 0, nq, R, mine);
             }
         }
-        // ---- 4. the last min(L - 1, cnt + n) entries move to the front: new[j] = old[j + shift], chunks of ADP_THREADS in
-        //      ascending order, each read whole before it is stored (a chunk reads at or above what it and the ones before it store) ----
+        // ---- 4. the last min(L - 1, cnt + n) entries move to the front: new[j] = old[j + shift], minimum and maximum as a pair
+        //      (stream_state.h; here the entries past `keep` are in `ext` as well) ----
         const int keep = min(L - 1, cnt + n), shift = cnt + n - keep;
         if (shift > 0) {
-            for (int base = 0; base < keep; base += ADP_THREADS) {
-                const int j = base + tid;
-                T mn_j = (T)0, mx_j = (T)0;
-                if (j < keep) { mn_j = emin[j + shift]; mx_j = emax[j + shift]; }
-                __syncthreads();
-                if (j < keep) { emin[j] = mn_j; emax[j] = mx_j; }
-            }
+            struct Ext { T mn, mx; };
+            const auto at = [&](const int i) { return Ext{emin[i], emax[i]}; };
+            shift_history<ADP_THREADS>(keep, shift, tid, at, [&](const int i) { return at(keep + i); },
+                                       [&](const int j, const Ext &e) { emin[j] = e.mn; emax[j] = e.mx; });
         }
         cnt = keep;
         __syncthreads();                                        // `ext`, the partial extrema and the latches are the next chunk's
@@ -252,10 +237,7 @@ __global__ __launch_bounds__(ADP_THREADS) void adaptive_encode_kernel(const Adap
         }
         for (int i = tid; i < F; i += ADP_THREADS) dlat[i] = latch[i];
         if (tid == 0) dlat[F] = (uint32_t)cnt;
-        if (copy) {
-            const size_t used = state_used_bytes(F, L, (int)sizeof(T));
-            if (used + tid < block) sout[used + tid] = sin ? sin[used + tid] : (unsigned char)0;
-        }
+        carry_padding<unsigned char>(blk, state_used_bytes(F, L, (int)sizeof(T)), block, tid);
     }
 }
 
@@ -273,13 +255,13 @@ int adaptive_encode(const T *db, int n_streams, int n_cols, int n_filters, const
     LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
     LSM_REQUIRE(thr_on && thr_off, "null threshold table");
     LSM_REQUIRE(raster_out != nullptr, "raster_out is required");
-    LSM_REQUIRE(((uintptr_t)raster_out & 3u) == 0, "raster_out is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)stream_cols & 3u) == 0, "stream_cols is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)db & (sizeof(T) - 1)) == 0, "db is misaligned: it must be %d-byte aligned", (int)sizeof(T));
-    LSM_REQUIRE(((uintptr_t)lo_out & (sizeof(T) - 1)) == 0, "lo_out is misaligned: it must be %d-byte aligned", (int)sizeof(T));
-    LSM_REQUIRE(((uintptr_t)hi_out & (sizeof(T) - 1)) == 0, "hi_out is misaligned: it must be %d-byte aligned", (int)sizeof(T));
-    LSM_REQUIRE(((uintptr_t)state_in & 15u) == 0, "state_in is misaligned: it must be 16-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_out & 15u) == 0, "state_out is misaligned: it must be 16-byte aligned");
+    LSM_REQUIRE_ALIGNED(raster_out, 4);
+    LSM_REQUIRE_ALIGNED(stream_cols, 4);
+    LSM_REQUIRE_ALIGNED(db, sizeof(T));
+    LSM_REQUIRE_ALIGNED(lo_out, sizeof(T));
+    LSM_REQUIRE_ALIGNED(hi_out, sizeof(T));
+    LSM_REQUIRE_ALIGNED(state_in, 16);
+    LSM_REQUIRE_ALIGNED(state_out, 16);
     if (n_streams == 0) return LSM_OK;
     LSM_REQUIRE(db != nullptr, "adaptive_encode: null db");
     AdaptiveArgs<T> a;
@@ -288,11 +270,7 @@ int adaptive_encode(const T *db, int n_streams, int n_cols, int n_filters, const
     a.state_out = static_cast<unsigned char *>(state_out);
     a.raster = raster_out; a.lo_out = lo_out; a.hi_out = hi_out;
     a.n_cols = n_cols; a.n_filters = n_filters; a.window = window_cols; a.n_thr = n_thr; a.redundancy = redundancy;
-    // unused table entries never fire: nothing is > +inf or < -inf
-    for (int q = 0; q < MAX_THR; ++q) {
-        a.on[q] = q < n_thr ? thr_on[q] : (T)INFINITY;
-        a.off[q] = q < n_thr ? thr_off[q] : (T)-INFINITY;
-    }
+    lsm_fe::fill_thresholds<T>(a.on, a.off, thr_on, thr_off, n_thr);
     const size_t lds = lds_bytes(n_filters, window_cols, (int)sizeof(T));
     if (lds > 64 * 1024) lsm_allow_big_lds(reinterpret_cast<const void *>(adaptive_encode_kernel<T>));
     hipLaunchKernelGGL(adaptive_encode_kernel<T>, dim3((unsigned)n_streams), dim3(ADP_THREADS), lds, (hipStream_t)stream, a);
@@ -301,8 +279,6 @@ int adaptive_encode(const T *db, int n_streams, int n_cols, int n_filters, const
 }
 
 }  // namespace
-
-#define LSM_API extern "C" __attribute__((visibility("default")))
 
 LSM_API long lsm_adaptive_state_bytes(int n_filters, int window_cols, int elem_bytes)
 {

@@ -16,9 +16,11 @@
 //              behind it: state_out may be state_in.
 // Every index is formed from clamped values: 0 <= h_b <= n_hops, -M < first bin of an utterance, its last bin < h_b, at most
 // M bins, slot < max_utts; ring slots are residues mod M and mod W - 1.
+// state_in and state_out follow DESIGN.md "The state block"; the block is whole 16-byte pieces and an idle stream's travels as such.
 #include "lsm_common.h"
 #include "bin_energy.h"
 #include "endpoint_body.h"
+#include "stream_state.h"
 #include <cmath>
 
 namespace {
@@ -95,15 +97,16 @@ __global__ __launch_bounds__(THREADS) void endpoint_kernel(const EndpointArgs a)
     const int M = a.M;
     const int h = clamp_hops(a.stream_hops ? a.stream_hops[b] : a.n_hops, a.n_hops);
     const bool fin = a.finish && a.finish[b] != 0;
-    const unsigned char *st_in = a.state_in ? a.state_in + b * (size_t)a.state_bytes : nullptr;
-    unsigned char *st_out = a.state_out ? a.state_out + b * (size_t)a.state_bytes : nullptr;
+    const lsm_state::StateBlock blk = lsm_state::state_block(a.state_in, a.state_out, b, (size_t)a.state_bytes);
+    const unsigned char *st_in = blk.sin;
+    unsigned char *st_out = blk.sout;
     int32_t *bins_out = a.utt_bins + b * (size_t)a.max_utts;
 
     // ---- a stream that delivers nothing and does not end: no utterance, the block as it is -----------------------------------
     if (h == 0 && !fin) {
         for (int u = tid; u < a.max_utts; u += THREADS) bins_out[u] = 0;
         if (tid == 0 && a.utt_count) a.utt_count[b] = 0;
-        if (st_out && st_out != st_in) {
+        if (blk.copy) {               // DESIGN.md "The state block"; the block is whole 16-byte pieces
             const int quads = (int)(a.state_bytes / 16);
             for (int q = tid; q < quads; q += THREADS)
                 reinterpret_cast<uint4 *>(st_out)[q] = st_in ? reinterpret_cast<const uint4 *>(st_in)[q] : make_uint4(0u, 0u, 0u, 0u);
@@ -254,8 +257,6 @@ __global__ __launch_bounds__(THREADS) void endpoint_kernel(const EndpointArgs a)
 }
 
 }  // namespace
-
-#define LSM_API extern "C" __attribute__((visibility("default")))
 
 LSM_API long lsm_endpoint_state_bytes(int window_bins, int max_bins)
 {

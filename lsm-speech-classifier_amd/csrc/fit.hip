@@ -190,8 +190,6 @@ bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API int lsm_fit_supported(int n_keys, int n_out, int n_classes)
 {
     return n_keys >= 1 && n_keys <= 8 && n_out >= 1 && (long)n_keys * n_out <= MAX_D && n_classes >= 1

@@ -131,6 +131,7 @@ __global__ __launch_bounds__(GT_MAX_WPB * 64) void gammatone_kernel(
 // for the serial part (time_bins x n_thr latch updates).
 // ---------------------------------------------------------------------------------------------
 using lsm_fe::MAX_THR;
+using lsm_fe::fill_thresholds;
 using lsm_fe::SpikeArgs;
 
 // Threads of a spec_to_spikes_kernel workgroup (one clip).  Alone on the GPU sixteen waves are faster than four (21.5 against
@@ -172,16 +173,6 @@ __global__ __launch_bounds__(64) void encode_kernel(const T *__restrict__ spec, 
                 o[j * n_thr + q] = active[q] ? 1 : 0;
             }
         }
-    }
-}
-
-// The kernels' threshold tables from the caller's n_thr entries; the entries beyond them take the pad values.
-template <typename T>
-void fill_thresholds(T (&on)[MAX_THR], T (&off)[MAX_THR], const T *thr_on, const T *thr_off, int n_thr, T pad_on, T pad_off)
-{
-    for (int q = 0; q < MAX_THR; ++q) {
-        on[q] = q < n_thr ? thr_on[q] : pad_on;
-        off[q] = q < n_thr ? thr_off[q] : pad_off;
     }
 }
 
@@ -358,8 +349,6 @@ static DevInfo dev_info()
     });
     return tab[dev];
 }
-
-#define LSM_API extern "C" __attribute__((visibility("default")))
 
 // SPEC.md 1.1: one channel would take NumPy's pairwise window sums in the reference; these kernels sum element by element
 static const char NEED_TWO_FILTERS[] =
@@ -551,7 +540,7 @@ static int plan_front(const FrontRequest &r, FusedArgs *args, lsm_fe::FusedLaunc
     a.ncols = r.ncols; a.time_bins = r.time_bins; a.n_thr = r.n_thr; a.redundancy = r.redundancy; a.groups = pl.groups;
     a.prio = 0;
     // unused table entries never fire: nothing is > +inf or < -inf (the kernel compares 4 or 8 thresholds)
-    fill_thresholds<double>(a.on, a.off, r.thr_on, r.thr_off, r.n_thr, INFINITY, -INFINITY);
+    fill_thresholds<double>(a.on, a.off, r.thr_on, r.thr_off, r.n_thr);
     const long n_waves = (long)pl.groups * r.n_clips;
     const long n_wgs = (n_waves + pl.wpb - 1) / pl.wpb;
     LSM_REQUIRE(n_wgs <= 0x7fffffffL, "too many clips for one launch");

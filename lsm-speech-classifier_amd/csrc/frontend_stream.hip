@@ -4,15 +4,18 @@
 // boundary and the latches travel in the state block, the normalisation range is fixed for the stream's life, and there is
 // one time bin per column (no resize).  Every float operation of the filter and the window sums is the one of
 // gammatone_kernel (frontend.hip) in its order (gammatone_body.h); compiled with -ffp-contract=off.
+// state_in, state_out and stream_hops follow DESIGN.md "The state block" (stream_state.h).
 #include "lsm_common.h"
 #include "gammatone_body.h"
 #include "spikes_body.h"
+#include "stream_state.h"
 #include <cmath>
 #include <type_traits>
 
 namespace {
 
 using lsm_fe::MAX_THR;
+using namespace lsm_state;
 constexpr int NWIN_MAX = 4;             // windows live at any sample, at most (nwin <= NWIN_MAX * hop)
 constexpr int GTS_WPB = 4;              // waves per workgroup: one per SIMD of its CU
 
@@ -28,7 +31,7 @@ __host__ __device__ inline size_t state_used_bytes(int n_filters, int nw)
 }
 __host__ __device__ inline size_t state_block_bytes(int n_filters, int nw)
 {
-    return (state_used_bytes(n_filters, nw) + 15) & ~(size_t)15;
+    return state_round16(state_used_bytes(n_filters, nw));
 }
 
 struct StreamArgs {
@@ -61,18 +64,15 @@ __global__ __launch_bounds__(GTS_WPB * 64) void gammatone_stream_kernel(const fl
     const int chl = (wid - b * groups) * 64 + (int)(threadIdx.x & 63);
     const bool live = chl < F;
     const int ch = live ? chl : F - 1;
-    int hb = a.stream_hops ? a.stream_hops[b] : H;      // wave-uniform
-    hb = __builtin_amdgcn_readfirstlane(min(max(hb, 0), H));
+    const int hb = __builtin_amdgcn_readfirstlane(stream_count(a.stream_hops, b, H));     // wave-uniform
 
     constexpr int ND = 8 + NW - 1;                      // doubles per channel in the state block
     const size_t block = state_block_bytes(F, NW), used = state_used_bytes(F, NW);
-    const unsigned char *sin = a.state_in ? a.state_in + (size_t)b * block : nullptr;
-    unsigned char *sout = a.state_out ? a.state_out + (size_t)b * block : nullptr;
-    const bool copy = sout != nullptr && sout != sin;   // out of place: the padding and an idle stream's block travel too
-    if (copy && wid == b * groups) {
-        const int lane = (int)(threadIdx.x & 63);
-        if (used + lane < block) sout[used + lane] = sin ? sin[used + lane] : (unsigned char)0;
-    }
+    const StateBlock blk = state_block(a.state_in, a.state_out, b, block);
+    const unsigned char *sin = blk.sin;
+    unsigned char *sout = blk.sout;
+    // out of place: the padding (the stream's first wave) and an idle stream's block (every lane its channel, below) travel
+    if (wid == b * groups) carry_padding<unsigned char>(blk, used, block, (int)(threadIdx.x & 63));
 
     double st[ND];
     uint32_t act = 0u, cnt = 0u;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(GTS_WPB * 64) void gammatone_stream_kernel(const fl
         cnt = __builtin_amdgcn_readfirstlane(su[F + ch]);       // every channel of a stream has seen the same hops
     }
     if (hb == 0) {
-        if (copy && live) {
+        if (blk.copy && live) {
             double *dd = reinterpret_cast<double *>(sout);
 #pragma unroll
             for (int k = 0; k < ND; ++k) dd[(size_t)k * F + ch] = st[k];
@@ -161,28 +161,18 @@ __global__ __launch_bounds__(GTS_WPB * 64) void gammatone_stream_kernel(const fl
             const double y = sqrt(win[NW - 1] / dn);
             const double v = 20 * log10(y + 1e-9);
             // a NaN stays a NaN through the floor and compares false with every threshold: the latches keep their state
-            const double vf = v < fl ? fl : v;
-            const double val = (vf - lo) / den;
+            const double val = lsm_fe::floored_value(v, fl, lo, den);
             uint32_t S = 0u, Rr = 0u;
 #pragma unroll
             for (int t = 0; t < MAX_THR; ++t) {
                 S |= (val > a.on[t] ? 1u : 0u) << t;
                 Rr |= (val < a.off[t] ? 1u : 0u) << t;
             }
-            act = ((S & ~act) | (act & ~Rr)) & tmask;   // both from the latch before the update (SPEC.md §1.3)
+            act = lsm_fe::latch_step(act, S, Rr, tmask);
             if (live) {
                 if (a.spec_out) a.spec_out[obase + col] = y;
                 if (a.db_out) a.db_out[obase + col] = v;
-                // redundancy: output row ch * R + r repeats the channel's row (SPEC.md §1.4)
-                if (n_thr == 4) {
-                    const uint32_t word = (act * 0x00204081u) & 0x01010101u;
-                    for (int r = 0; r < R; ++r)
-                        *reinterpret_cast<uint32_t *>(rrow + (size_t)r * row_bytes + (size_t)col * 4) = word;
-                } else {
-                    for (int r = 0; r < R; ++r)
-                        for (int t = 0; t < n_thr; ++t)
-                            rrow[(size_t)r * row_bytes + (size_t)col * n_thr + t] = (uint8_t)((act >> t) & 1u);
-                }
+                lsm_fe::store_column(rrow, row_bytes, col, n_thr, R, act);
             }
             ++col;
         } else {
@@ -213,8 +203,6 @@ bool windows_ok(int nwin, int hop) { return hop >= 1 && nwin >= hop && (long)nwi
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API long lsm_gammatone_stream_state_bytes(int n_filters, int nwin, int hop)
 {
     if (n_filters < 2 || !windows_ok(nwin, hop)) return 0;
@@ -242,14 +230,14 @@ LSM_API int lsm_gammatone_stream_f64(const float *audio, int n_streams, int n_ho
     LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
     LSM_REQUIRE(thr_on && thr_off, "null threshold table");
     LSM_REQUIRE(raster_out != nullptr, "raster_out is required");
-    LSM_REQUIRE(((uintptr_t)raster_out & 3u) == 0, "raster_out is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)audio & 3u) == 0, "audio is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)coefs & 7u) == 0, "coefs is misaligned: it must be 8-byte aligned");
-    LSM_REQUIRE(((uintptr_t)stream_hops & 3u) == 0, "stream_hops is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_in & 15u) == 0, "state_in is misaligned: it must be 16-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_out & 15u) == 0, "state_out is misaligned: it must be 16-byte aligned");
-    LSM_REQUIRE(((uintptr_t)spec_out & 7u) == 0, "spec_out is misaligned: it must be 8-byte aligned");
-    LSM_REQUIRE(((uintptr_t)db_out & 7u) == 0, "db_out is misaligned: it must be 8-byte aligned");
+    LSM_REQUIRE_ALIGNED(raster_out, 4);
+    LSM_REQUIRE_ALIGNED(audio, 4);
+    LSM_REQUIRE_ALIGNED(coefs, 8);
+    LSM_REQUIRE_ALIGNED(stream_hops, 4);
+    LSM_REQUIRE_ALIGNED(state_in, 16);
+    LSM_REQUIRE_ALIGNED(state_out, 16);
+    LSM_REQUIRE_ALIGNED(spec_out, 8);
+    LSM_REQUIRE_ALIGNED(db_out, 8);
     if (n_streams == 0) return LSM_OK;
     LSM_REQUIRE(audio && coefs, "gammatone_stream: null input");
     StreamArgs a;
@@ -259,11 +247,7 @@ LSM_API int lsm_gammatone_stream_f64(const float *audio, int n_streams, int n_ho
     a.raster = raster_out; a.spec_out = spec_out; a.db_out = db_out;
     a.n_streams = n_streams; a.n_hops = n_hops; a.n_filters = n_filters; a.nwin = nwin; a.hop = hop;
     a.n_thr = n_thr; a.redundancy = redundancy; a.db_lo = db_lo; a.db_hi = db_hi;
-    // unused table entries never fire: nothing is > +inf or < -inf
-    for (int q = 0; q < MAX_THR; ++q) {
-        a.on[q] = q < n_thr ? thr_on[q] : INFINITY;
-        a.off[q] = q < n_thr ? thr_off[q] : -INFINITY;
-    }
+    lsm_fe::fill_thresholds<double>(a.on, a.off, thr_on, thr_off, n_thr);
     const long n_wgs = ((long)((n_filters + 63) / 64) * n_streams + GTS_WPB - 1) / GTS_WPB;
     LSM_REQUIRE(n_wgs <= 0x7fffffffL, "too many streams for one launch");
     const dim3 grid((unsigned)n_wgs), block((unsigned)(64 * GTS_WPB));

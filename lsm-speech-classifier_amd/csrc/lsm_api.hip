@@ -28,8 +28,6 @@ void lsm_allow_big_lds(const void *kernel_fn)
         (void)hipGetLastError();        // the launch that follows reports the failure
 }
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 // major*10000 + minor*100 + patch of the package's __version__: build.py passes it (and the identity of the sources the
 // library is built from) on this file's command line, so there is ONE place where the number is written; _lib.load()
 // refuses a library whose version or build id is not the tree's.

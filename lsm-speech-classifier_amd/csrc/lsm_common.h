@@ -6,6 +6,9 @@
 
 #define LSM_WAVE 64
 
+// An entry point of the C ABI (the library is built with -fvisibility=hidden).
+#define LSM_API extern "C" __attribute__((visibility("default")))
+
 // Error codes of the C ABI (include/lsm_hip.h).
 #define LSM_OK 0
 #define LSM_ERR_ARG -1
@@ -37,3 +40,7 @@ void lsm_allow_big_lds(const void *kernel_fn);
             return LSM_ERR_ARG;                                                     \
         }                                                                           \
     } while (0)
+
+// A null pointer passes: whether a buffer is required is its entry point's own refusal.
+#define LSM_REQUIRE_ALIGNED(ptr, bytes) \
+    LSM_REQUIRE(((uintptr_t)(ptr) & ((bytes) - 1u)) == 0, #ptr " is misaligned: it must be %d-byte aligned", (int)(bytes))

@@ -127,8 +127,6 @@ constexpr size_t MEL_SPIKES_LDS = 4 * sizeof(double2) * ZPAD + 32;
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API int lsm_mel_power_f32(const float *audio, int n_clips, int n_samples, int n_fft, int hop,
                               int n_frames, const double *window_dev, const double *twiddle_dev,
                               const float *basis_dev, const int32_t *lo_dev, const int32_t *hi_dev,

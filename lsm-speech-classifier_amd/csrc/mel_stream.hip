@@ -6,7 +6,7 @@
 //
 // Two kernels enqueued by one call, in stream order (chosen for simplicity over mel_spikes_kernel's "last workgroup to
 // arrive finishes": no arrival counters to zero, no agent-scope fences, and the kernel boundary is what orders every read of
-// the history before its in-place shift):
+// the history before its in-place shift, DESIGN.md "The state block"):
 //   1. mel_stream_frames_kernel   grid (H, n_streams), one wave per (new frame, stream): the frame transform of mel_body.h on
 //                                 [history | new audio], power values to the workspace;
 //   2. mel_stream_finish_kernel   one workgroup per stream: dB, normalise, latches over this push's frames in order, raster
@@ -15,12 +15,14 @@
 #include "lsm_common.h"
 #include "mel_body.h"
 #include "spikes_body.h"
+#include "stream_state.h"
 #include <cmath>
 
 namespace {
 
 using namespace lsm_mel;
 using lsm_fe::MAX_THR;
+using namespace lsm_state;
 
 constexpr int HOP_MIN = NFFT / 16, HOP_MAX = NFFT / 2;
 constexpr int FIN_THREADS = 256;
@@ -43,7 +45,7 @@ __host__ __device__ inline size_t state_used_bytes(int n_mels, int hop)
 }
 __host__ __device__ inline size_t state_block_bytes(int n_mels, int hop)
 {
-    return (state_used_bytes(n_mels, hop) + 15) & ~(size_t)15;
+    return state_round16(state_used_bytes(n_mels, hop));
 }
 
 struct MelStreamArgs {
@@ -69,8 +71,7 @@ __device__ __forceinline__ StreamPlan stream_plan(const MelStreamArgs &a, const 
 {
     const int H = a.n_hops, Lg = latency_hops(a.hop);
     StreamPlan p;
-    p.hb = a.stream_hops ? a.stream_hops[b] : H;
-    p.hb = min(max(p.hb, 0), H);
+    p.hb = stream_count(a.stream_hops, b, H);
     p.cnt = 0;
     if (a.state_in) {
         const uint32_t *su = reinterpret_cast<const uint32_t *>(a.state_in + (size_t)b * state_block_bytes(a.tab.n_mels, a.hop));
@@ -120,18 +121,16 @@ __global__ __launch_bounds__(FIN_THREADS) void mel_stream_finish_kernel(const Me
     const StreamPlan p = stream_plan(a, b);
     const int H = a.n_hops, hop = a.hop, F = a.tab.n_mels, Hs = history_samples(hop), Lg = latency_hops(hop);
     const size_t block = state_block_bytes(F, hop);
-    const unsigned char *sin = a.state_in ? a.state_in + (size_t)b * block : nullptr;
-    unsigned char *sout = a.state_out ? a.state_out + (size_t)b * block : nullptr;
-    const bool copy = sout != nullptr && sout != sin;
+    const StateBlock blk = state_block(a.state_in, a.state_out, b, block);
+    const unsigned char *sin = blk.sin;
+    unsigned char *sout = blk.sout;
     if (p.hb == 0) {
-        // an idle stream: its block travels as it is (out of place), or stays (in place)
-        if (copy)
-            for (size_t i = tid; i < block / 4; i += FIN_THREADS)
-                reinterpret_cast<uint32_t *>(sout)[i] = sin ? reinterpret_cast<const uint32_t *>(sin)[i] : 0u;
+        carry_idle_block<FIN_THREADS>(blk, block, tid);
         return;
     }
     // the new history: the last Hs samples of [history | this push's h_b * hop samples], read into registers by every
-    // thread BEFORE any of them is stored (state_out may be state_in, and a short push shifts within the block)
+    // thread BEFORE any of them is stored (state_out may be state_in, and a short push shifts within the block); the
+    // latch loop lies between, so this is not stream_state.h's chunked shift
     const float *hist = reinterpret_cast<const float *>(sin);
     const float *__restrict__ row = a.audio + (size_t)b * H * hop;
     const int adv = p.hb * hop;                 // <= H * hop <= 2^31 - 1
@@ -173,8 +172,7 @@ __global__ __launch_bounds__(FIN_THREADS) void mel_stream_finish_kernel(const Me
                 // np.maximum propagates a NaN, fmaxf drops it
                 const float v = 10.0f * log10f(S != S ? S : fmaxf(1e-10f, S));
                 // a NaN stays a NaN through the floor and compares false with every threshold: the latches keep their state
-                const float vf = v < fl ? fl : v;
-                const float val = (vf - lo) / den;
+                const float val = lsm_fe::floored_value(v, fl, lo, den);
                 uint32_t up = 0u, dn = 0u;
 #pragma unroll
                 for (int t = 0; t < MAX_THR; ++t) {
@@ -191,17 +189,8 @@ __global__ __launch_bounds__(FIN_THREADS) void mel_stream_finish_kernel(const Me
                 const int nc = min(FIN_TILE, p.cols - c0);
                 for (int j = 0; j < nc; ++j) {
                     const uint32_t up = upb[tid][j], dn = dnb[tid][j];
-                    act = ((up & ~act) | (act & ~dn)) & tmask;      // both from the latch before the update (SPEC.md §1.3)
-                    // redundancy: output row m * R + r repeats the filter's row (SPEC.md §1.4)
-                    if (n_thr == 4) {
-                        const uint32_t word = (act * 0x00204081u) & 0x01010101u;
-                        for (int r = 0; r < R; ++r)
-                            *reinterpret_cast<uint32_t *>(rrow + (size_t)r * row_bytes + (size_t)(c0 + j) * 4) = word;
-                    } else {
-                        for (int r = 0; r < R; ++r)
-                            for (int t = 0; t < n_thr; ++t)
-                                rrow[(size_t)r * row_bytes + (size_t)(c0 + j) * n_thr + t] = (uint8_t)((act >> t) & 1u);
-                    }
+                    act = lsm_fe::latch_step(act, up, dn, tmask);
+                    lsm_fe::store_column(rrow, row_bytes, c0 + j, n_thr, R, act);
                 }
             }
             __syncthreads();                    // the tile's bits are free for the next one
@@ -216,19 +205,14 @@ __global__ __launch_bounds__(FIN_THREADS) void mel_stream_finish_kernel(const Me
             const int j = tid + FIN_THREADS * k;
             if (j < Hs) hout[j] = keep[k];
         }
-        const size_t used = state_used_bytes(F, hop);
         if (tid == 0) reinterpret_cast<uint32_t *>(sout)[Hs + F] = (uint32_t)min(p.cnt + p.hb, Lg - 1);
-        // out of place: the padding travels too
-        if (copy && used / 4 + tid < block / 4)
-            reinterpret_cast<uint32_t *>(sout)[used / 4 + tid] = sin ? reinterpret_cast<const uint32_t *>(sin)[used / 4 + tid] : 0u;
+        carry_padding<uint32_t>(blk, state_used_bytes(F, hop) / 4, block, tid);
     }
 }
 
 bool shape_ok(int n_mels, int n_fft, int hop) { return n_mels >= 1 && n_fft == NFFT && hop >= HOP_MIN && hop <= HOP_MAX; }
 
 }  // namespace
-
-#define LSM_API extern "C" __attribute__((visibility("default")))
 
 LSM_API long lsm_mel_stream_state_bytes(int n_mels, int n_fft, int hop)
 {
@@ -265,18 +249,18 @@ LSM_API int lsm_mel_stream_f32(const float *audio, int n_streams, int n_hops, in
     LSM_REQUIRE(redundancy >= 1, "redundancy must be >= 1");
     LSM_REQUIRE(thr_on && thr_off, "null threshold table");
     LSM_REQUIRE(raster_out != nullptr, "raster_out is required");
-    LSM_REQUIRE(((uintptr_t)raster_out & 3u) == 0, "raster_out is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)audio & 3u) == 0, "audio is misaligned: it must be 4-byte aligned");
+    LSM_REQUIRE_ALIGNED(raster_out, 4);
+    LSM_REQUIRE_ALIGNED(audio, 4);
     LSM_REQUIRE((((uintptr_t)window_dev | (uintptr_t)twiddle_dev) & 15u) == 0,
                 "the window and twiddle tables are misaligned: they must be 16-byte aligned");
     LSM_REQUIRE((((uintptr_t)basis_dev | (uintptr_t)lo_dev | (uintptr_t)hi_dev) & 3u) == 0,
                 "the basis, lo and hi tables are misaligned: they must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)stream_hops & 3u) == 0, "stream_hops is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_in & 15u) == 0, "state_in is misaligned: it must be 16-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_out & 15u) == 0, "state_out is misaligned: it must be 16-byte aligned");
-    LSM_REQUIRE(((uintptr_t)power_out & 3u) == 0, "power_out is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)db_out & 3u) == 0, "db_out is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)workspace & 15u) == 0, "workspace is misaligned: it must be 16-byte aligned");
+    LSM_REQUIRE_ALIGNED(stream_hops, 4);
+    LSM_REQUIRE_ALIGNED(state_in, 16);
+    LSM_REQUIRE_ALIGNED(state_out, 16);
+    LSM_REQUIRE_ALIGNED(power_out, 4);
+    LSM_REQUIRE_ALIGNED(db_out, 4);
+    LSM_REQUIRE_ALIGNED(workspace, 16);
     const long need = lsm_mel_stream_workspace(n_streams, n_mels, n_hops);
     LSM_REQUIRE(workspace_bytes >= need, "workspace of %ld bytes, need %ld (lsm_mel_stream_workspace)", workspace_bytes, need);
     if (n_streams == 0) return LSM_OK;
@@ -291,11 +275,7 @@ LSM_API int lsm_mel_stream_f32(const float *audio, int n_streams, int n_hops, in
     a.raster = raster_out; a.power_ws = static_cast<float *>(workspace); a.power_out = power_out; a.db_out = db_out;
     a.n_streams = n_streams; a.n_hops = n_hops; a.hop = hop; a.n_thr = n_thr; a.redundancy = redundancy;
     a.db_lo = lo32; a.db_hi = hi32;
-    // unused table entries never fire: nothing is > +inf or < -inf
-    for (int q = 0; q < MAX_THR; ++q) {
-        a.on[q] = q < n_thr ? thr_on[q] : INFINITY;
-        a.off[q] = q < n_thr ? thr_off[q] : -INFINITY;
-    }
+    lsm_fe::fill_thresholds<float>(a.on, a.off, thr_on, thr_off, n_thr);
     hipLaunchKernelGGL(mel_stream_frames_kernel, dim3(n_hops, n_streams), dim3(64), 0, (hipStream_t)stream, a);
     LSM_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(mel_stream_finish_kernel, dim3(n_streams), dim3(FIN_THREADS), 0, (hipStream_t)stream, a);

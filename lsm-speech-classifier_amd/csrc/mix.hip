@@ -12,10 +12,12 @@
 // clip has just been pulled through.  The stores are 16 bytes wide behind a head of up to three samples (store_row); the
 // loads stay scalar, because a shift and a noise offset put them at any 4-byte address.
 #include "mix_body.h"
+#include "stream_state.h"
 
 namespace {
 
 using namespace lsm_mix;
+using lsm_state::clamped_at;
 
 struct MixArgs {
     const float *audio;                 // (rows, n)
@@ -29,11 +31,6 @@ struct MixArgs {
     int n, M, L;
     const int32_t *clip_samples;        // (rows): the ragged batch form's lengths, n is then the rows' stride (last: the
 };                                      // members above keep their offsets)
-
-__device__ __forceinline__ int clamped(const int32_t *values, int b, int lo, int hi, int absent)
-{
-    return min(max(values ? values[b] : absent, lo), hi);
-}
 
 __global__ __launch_bounds__(THREADS) void mix_power_kernel(const float *x, int n, double *power_out)
 {
@@ -56,12 +53,12 @@ __global__ __launch_bounds__(THREADS) void mix_kernel(const MixArgs a)
 {
     __shared__ double p[2][THREADS];
     const int b = blockIdx.x, l = threadIdx.x, stride = a.n;
-    const int n = RAGGED ? clamped(a.clip_samples, b, 0, stride, 0) : stride;
+    const int n = RAGGED ? clamped_at(a.clip_samples, b, 0, stride, 0) : stride;
     const uint32_t L = (uint32_t)a.L;
     const float *row = a.audio + (size_t)b * stride;
-    const int s = clamped(a.shift, b, -n, n, 0);
+    const int s = clamped_at(a.shift, b, -n, n, 0);
     const double sc = a.scale ? (double)a.scale[b] : 1.0;
-    const float *nrow = a.noise + (size_t)clamped(a.noise_row, b, 0, a.M - 1, 0) * L;
+    const float *nrow = a.noise + (size_t)clamped_at(a.noise_row, b, 0, a.M - 1, 0) * L;
     const uint32_t o = mod_nonneg(a.noise_offset ? a.noise_offset[b] : 0, a.L);
     const double q = a.ratio[b];
 
@@ -113,7 +110,7 @@ __global__ __launch_bounds__(THREADS) void mix_stream_kernel(const MixArgs a)
 {
     const int b = blockIdx.x, H = a.n;
     const uint32_t L = (uint32_t)a.L;
-    const int c = clamped(a.count, b, 0, H, H);
+    const int c = lsm_state::stream_count(a.count, b, H);
     const uint32_t pos = mod_nonneg(a.pos_in ? a.pos_in[b] : 0, a.L);
     __syncthreads();                    // pos_out may be pos_in: every thread has read the position before thread 0 writes it
     if (threadIdx.x == 0 && a.pos_out) a.pos_out[b] = (int32_t)noise_index(pos, (uint32_t)c, L);
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(THREADS) void mix_stream_kernel(const MixArgs a)
     const double sc = a.scale ? (double)a.scale[b] : 1.0;
     const double g = a.gain[b];
     const bool noisy = !(g == 0.0);
-    const float *nrow = a.noise + (size_t)clamped(a.noise_row, b, 0, a.M - 1, 0) * L;
+    const float *nrow = a.noise + (size_t)clamped_at(a.noise_row, b, 0, a.M - 1, 0) * L;
 
     store_row(a.out + (size_t)b * H, c,
               [&](const int i) {
@@ -158,19 +155,14 @@ int check_bank(int n_noise_rows, int noise_len)
     return LSM_OK;
 }
 
-#define MIX_ALIGNED(ptr, bytes) \
-    LSM_REQUIRE(((uintptr_t)(ptr) & ((bytes) - 1u)) == 0, #ptr " is misaligned: it must be %d-byte aligned", (int)(bytes))
-
 }  // namespace
-
-#define LSM_API extern "C" __attribute__((visibility("default")))
 
 LSM_API int lsm_mix_power_f32(const float *x, int n_rows, int n_samples, double *power_out, void *stream)
 {
     const int rc = check_shape("n_samples", n_samples, n_rows);
     if (rc != LSM_OK) return rc;
-    MIX_ALIGNED(x, 4);
-    MIX_ALIGNED(power_out, 8);
+    LSM_REQUIRE_ALIGNED(x, 4);
+    LSM_REQUIRE_ALIGNED(power_out, 8);
     if (n_rows == 0) return LSM_OK;
     LSM_REQUIRE(x && power_out, "mix power: null buffer");
     hipLaunchKernelGGL(mix_power_kernel, dim3(n_rows), dim3(THREADS), 0, (hipStream_t)stream, x, n_samples, power_out);
@@ -187,22 +179,22 @@ static int mix_batch(bool ragged, const float *audio, int n_clips, int n_samples
     int rc = check_shape("n_samples", n_samples, n_clips);
     if (rc == LSM_OK) rc = check_bank(n_noise_rows, noise_len);
     if (rc != LSM_OK) return rc;
-    MIX_ALIGNED(audio, 4);
-    MIX_ALIGNED(noise, 4);
-    MIX_ALIGNED(out, 4);
-    MIX_ALIGNED(noise_row, 4);
-    MIX_ALIGNED(noise_offset, 4);
-    MIX_ALIGNED(shift, 4);
-    MIX_ALIGNED(scale, 4);
-    MIX_ALIGNED(ratio, 8);
-    MIX_ALIGNED(gain_out, 8);
-    MIX_ALIGNED(power_out, 8);
+    LSM_REQUIRE_ALIGNED(audio, 4);
+    LSM_REQUIRE_ALIGNED(noise, 4);
+    LSM_REQUIRE_ALIGNED(out, 4);
+    LSM_REQUIRE_ALIGNED(noise_row, 4);
+    LSM_REQUIRE_ALIGNED(noise_offset, 4);
+    LSM_REQUIRE_ALIGNED(shift, 4);
+    LSM_REQUIRE_ALIGNED(scale, 4);
+    LSM_REQUIRE_ALIGNED(ratio, 8);
+    LSM_REQUIRE_ALIGNED(gain_out, 8);
+    LSM_REQUIRE_ALIGNED(power_out, 8);
     if (n_clips == 0) return LSM_OK;
     LSM_REQUIRE(audio && noise && ratio && out, "mix: null buffer (audio, noise, ratio and out are required)");
     LSM_REQUIRE(out != audio, "out must not be audio: a shift reads across what it would write");
     if (ragged) {
         LSM_REQUIRE(clip_samples != nullptr, "mix ragged: null clip_samples");
-        MIX_ALIGNED(clip_samples, 4);
+        LSM_REQUIRE_ALIGNED(clip_samples, 4);
     }
     MixArgs a{};
     a.audio = audio; a.noise = noise; a.out = out;
@@ -239,15 +231,15 @@ LSM_API int lsm_mix_stream_f32(const float *audio, int n_streams, int n_cols, co
     int rc = check_shape("n_cols", n_cols, n_streams);
     if (rc == LSM_OK) rc = check_bank(n_noise_rows, noise_len);
     if (rc != LSM_OK) return rc;
-    MIX_ALIGNED(audio, 4);
-    MIX_ALIGNED(noise, 4);
-    MIX_ALIGNED(out, 4);
-    MIX_ALIGNED(count, 4);
-    MIX_ALIGNED(gain, 8);
-    MIX_ALIGNED(scale, 4);
-    MIX_ALIGNED(noise_row, 4);
-    MIX_ALIGNED(pos_in, 4);
-    MIX_ALIGNED(pos_out, 4);
+    LSM_REQUIRE_ALIGNED(audio, 4);
+    LSM_REQUIRE_ALIGNED(noise, 4);
+    LSM_REQUIRE_ALIGNED(out, 4);
+    LSM_REQUIRE_ALIGNED(count, 4);
+    LSM_REQUIRE_ALIGNED(gain, 8);
+    LSM_REQUIRE_ALIGNED(scale, 4);
+    LSM_REQUIRE_ALIGNED(noise_row, 4);
+    LSM_REQUIRE_ALIGNED(pos_in, 4);
+    LSM_REQUIRE_ALIGNED(pos_out, 4);
     if (n_streams == 0) return LSM_OK;
     LSM_REQUIRE(audio && noise && gain && out, "mix stream: null buffer (audio, noise, gain and out are required)");
     MixArgs a{};

@@ -93,8 +93,6 @@ void launch_gammatone_spikes_ragged(const FusedLaunch &l, const void *fused_args
 
 }  // namespace lsm_fe
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API int lsm_power_to_db_ragged_f32(const float *power, int n_clips, int n_mels, int n_frames, const int32_t *clip_frames,
                                        float amin, float top_db, float *db_out, void *stream)
 {

@@ -148,8 +148,6 @@ bool aligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API int lsm_readout_supported(int n_keys, int n_out, int n_classes)
 {
     return n_keys >= 1 && n_keys <= 8 && n_out >= 1 && n_out <= 8192 && n_classes >= 1 && n_classes <= 64 ? 1 : 0;

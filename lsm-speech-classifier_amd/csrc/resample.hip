@@ -3,7 +3,7 @@
 //   batch     resample_kernel          grid (tiles, n_clips): y[m] = z[m + delay], scipy's centred alignment, zeros outside a clip;
 //   streamed  resample_stream_kernel   grid (tiles, n_streams): z itself on [history | new blocks], then
 //             resample_state_kernel    one workgroup per stream: the last Hs samples become the new history.
-// The kernel boundary orders every read of the old history before its in-place shift (as in mel_stream.hip).
+// The kernel boundary orders every read of the old history before its in-place shift (DESIGN.md "The state block").
 //
 // Layout.  A workgroup of 512 threads makes a tile of 2048 consecutive outputs of one row, thread t the outputs
 // t, t + 512, ...: neighbouring lanes read inputs down/up samples apart (2.76 at 44.1 kHz), a wave some 700 contiguous bytes per
@@ -12,11 +12,13 @@
 // 44.1 kHz (74 KB), 640 of 21 at 11.025 kHz (105 KB), one row at 48 kHz; loading it costs 8 * K bytes from L2 per 2048
 // outputs, under 3 % of what the tap loop reads.  A table over 160 KB is refused (LSM_ERR_UNSUPPORTED).
 #include "resample_body.h"
+#include "stream_state.h"
 #include <numeric>
 
 namespace {
 
 using namespace lsm_resample;
+using namespace lsm_state;
 
 struct ResampleArgs {
     const void *audio;                  // batch (n_clips, n_in); streamed (n_streams, G * down); float32 or int16
@@ -33,13 +35,7 @@ struct ResampleArgs {
 __host__ __device__ inline size_t state_block_bytes(int n_taps, int up)
 {
     const size_t used = (size_t)history_samples(n_taps, up) * 4;
-    return used ? (used + 15) & ~(size_t)15 : 16;
-}
-
-__device__ __forceinline__ int stream_blocks_of(const ResampleArgs &a, int b)
-{
-    const int kb = a.stream_blocks ? a.stream_blocks[b] : a.n_blocks;
-    return min(max(kb, 0), a.n_blocks);
+    return used ? state_round16(used) : 16;
 }
 
 __global__ __launch_bounds__(THREADS) void resample_kernel(const ResampleArgs a)
@@ -67,7 +63,7 @@ __global__ __launch_bounds__(THREADS) void resample_stream_kernel(const Resample
 {
     extern __shared__ double tab[];
     const int b = blockIdx.y, fmt = a.fmt;
-    const long long n = (long long)stream_blocks_of(a, b) * a.up;               // outputs of this stream: <= G * up < 2^31
+    const long long n = (long long)stream_count(a.stream_blocks, b, a.n_blocks) * a.up;               // outputs of this stream: <= G * up < 2^31
     if ((long long)blockIdx.x * TILE >= n) return;                              // workgroup-uniform
     load_table(tab, a.taps, a.n_taps, a.up);
     const int Hs = history_samples(a.n_taps, a.up);
@@ -99,39 +95,23 @@ __global__ __launch_bounds__(THREADS) void resample_state_kernel(const ResampleA
     const int b = blockIdx.x, tid = threadIdx.x, fmt = a.fmt;
     const int Hs = history_samples(a.n_taps, a.up);
     const size_t block = state_block_bytes(a.n_taps, a.up);
+    // launched only where there is a state_out: its block is formed without the null test of state_block
     const unsigned char *sin = a.state_in ? a.state_in + (size_t)b * block : nullptr;
     unsigned char *sout = a.state_out + (size_t)b * block;
-    const bool copy = sout != sin;
-    const int kb = stream_blocks_of(a, b);
-    const uint32_t *win = reinterpret_cast<const uint32_t *>(sin);
-    uint32_t *wout = reinterpret_cast<uint32_t *>(sout);
+    const StateBlock blk{sin, sout, sout != sin};
+    const int kb = stream_count(a.stream_blocks, b, a.n_blocks);
     if (kb == 0) {
-        // an idle stream: its block travels as it is (out of place), or stays (in place)
-        if (copy)
-            for (size_t i = tid; i < block / 4; i += THREADS) wout[i] = win ? win[i] : 0u;
+        carry_idle_block<THREADS>(blk, block, tid);
         return;
     }
-    const float *hist = reinterpret_cast<const float *>(sin);
-    float *hout = reinterpret_cast<float *>(sout);
+    const float *hist = reinterpret_cast<const float *>(blk.sin);
+    float *hout = reinterpret_cast<float *>(blk.sout);
     const size_t row = (size_t)b * a.n_blocks * a.down;
-    const long long adv = (long long)kb * a.down;                               // >= 1
-    // Chunks of THREADS samples in ascending order, each read whole before it is stored: new[j] = old[j + adv], so a chunk
-    // reads at or above its own indices and strictly above every chunk stored before it -- a push shorter than the history
-    // shifts within the block, and state_out may be state_in.
-    for (int base = 0; base < Hs; base += THREADS) {
-        const int j = base + tid;
-        float v = 0.0f;
-        if (j < Hs) {
-            const long long src = j + adv;
-            if (src >= Hs) v = pcm_f32(a.audio, row + (size_t)(src - Hs), fmt);
-            else if (hist) v = hist[src];
-        }
-        __syncthreads();
-        if (j < Hs) hout[j] = v;
-    }
-    // out of place: the padding travels too
-    if (copy)
-        for (size_t i = (size_t)Hs + tid; i < block / 4; i += THREADS) wout[i] = win ? win[i] : 0u;
+    shift_history<THREADS>(Hs, (long long)kb * a.down, tid,
+                           [&](const long long j) { return hist ? hist[j] : 0.0f; },
+                           [&](const long long i) { return pcm_f32(a.audio, row + (size_t)i, fmt); },
+                           [&](const int j, const float v) { hout[j] = v; });
+    carry_words<THREADS>(blk, (size_t)Hs, block, tid);            // out of place: the padding travels too
 }
 
 // what both entry points ask of the design; LSM_OK, or the code with the message set
@@ -143,9 +123,8 @@ int check_design(const void *audio, int sample_format, const double *taps_dev, i
     LSM_REQUIRE(std::gcd(up, down) == 1, "up=%d and down=%d share the factor %d: reduce them", up, down, std::gcd(up, down));
     LSM_REQUIRE(n_taps >= 1, "n_taps=%d must be >= 1", n_taps);
     LSM_REQUIRE(audio && taps_dev, "resample: null buffer");
-    LSM_REQUIRE(((uintptr_t)audio & (sample_format ? 1u : 3u)) == 0, "audio is misaligned: it must be %d-byte aligned",
-                sample_format ? 2 : 4);
-    LSM_REQUIRE(((uintptr_t)taps_dev & 7u) == 0, "taps_dev is misaligned: it must be 8-byte aligned");
+    LSM_REQUIRE_ALIGNED(audio, sample_format ? 2 : 4);
+    LSM_REQUIRE_ALIGNED(taps_dev, 8);
     if (table_bytes(n_taps, up) > LDS_MAX) {
         lsm_set_error("the tap table of n_taps=%d, up=%d takes %ld bytes laid out by phase, over the %ld of a CU's LDS",
                       n_taps, up, table_bytes(n_taps, up), LDS_MAX);
@@ -165,8 +144,6 @@ void launch_tiles(Kernel kernel, long long outputs_per_row, int rows, const Resa
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API long lsm_resample_state_bytes(int n_taps, int up)
 {
     if (n_taps < 1 || up < 1) return 0;
@@ -183,7 +160,7 @@ LSM_API int lsm_resample_f32(const void *audio, int sample_format, int n_clips, 
     LSM_REQUIRE(delay >= 0 && (long long)delay * down < n_taps,
                 "delay=%d does not fit the table: delay * down must lie in [0, n_taps = %d)", delay, n_taps);
     LSM_REQUIRE(out != nullptr, "out is required");
-    LSM_REQUIRE(((uintptr_t)out & 3u) == 0, "out is misaligned: it must be 4-byte aligned");
+    LSM_REQUIRE_ALIGNED(out, 4);
     ResampleArgs a{};
     a.audio = audio; a.taps = taps_dev; a.out = out;
     a.fmt = sample_format; a.n_taps = n_taps; a.up = up; a.down = down;
@@ -204,10 +181,10 @@ LSM_API int lsm_resample_stream_f32(const void *audio, int sample_format, int n_
     LSM_REQUIRE((long long)n_blocks * down <= 0x7fffffffLL && (long long)n_blocks * up <= 0x7fffffffLL,
                 "n_blocks * down and n_blocks * up must not exceed 2^31 - 1 samples per row");
     LSM_REQUIRE(out != nullptr, "out is required");
-    LSM_REQUIRE(((uintptr_t)out & 3u) == 0, "out is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)stream_blocks & 3u) == 0, "stream_blocks is misaligned: it must be 4-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_in & 15u) == 0, "state_in is misaligned: it must be 16-byte aligned");
-    LSM_REQUIRE(((uintptr_t)state_out & 15u) == 0, "state_out is misaligned: it must be 16-byte aligned");
+    LSM_REQUIRE_ALIGNED(out, 4);
+    LSM_REQUIRE_ALIGNED(stream_blocks, 4);
+    LSM_REQUIRE_ALIGNED(state_in, 16);
+    LSM_REQUIRE_ALIGNED(state_out, 16);
     ResampleArgs a{};
     a.audio = audio; a.taps = taps_dev; a.out = out;
     a.stream_blocks = stream_blocks;

@@ -3,7 +3,7 @@
 //   batch     reverb_kernel          grid (tiles, n_clips): y[i] = sum over k < len of h[k] * x[i - k], zeros outside the clip;
 //   streamed  reverb_stream_kernel   grid (tiles, n_streams): the same on [history | new samples], then
 //             reverb_state_kernel    one workgroup per stream: the last K - 1 samples become the new history.
-// The kernel boundary orders every read of the old history before its in-place shift (as in resample.hip).
+// The kernel boundary orders every read of the old history before its in-place shift (DESIGN.md "The state block").
 //
 // A workgroup of 256 lanes makes 2048 consecutive outputs of one row, a lane 8 of them from a sliding register window; the
 // input tile and the taps of a chunk are staged in LDS as float64 (33 KB, four workgroups per CU).  A dry row copies.
@@ -12,6 +12,7 @@
 namespace {
 
 using namespace lsm_reverb;
+using namespace lsm_state;
 
 struct ReverbArgs {
     const float *audio;                 // batch (n_clips, n_in); streamed (n_streams, n_cols)
@@ -25,17 +26,12 @@ struct ReverbArgs {
     int n_in, n_out, M, K;
 };
 
-__device__ __forceinline__ int clamped(const int32_t *values, int b, int lo, int hi, int absent)
-{
-    return min(max(values ? values[b] : absent, lo), hi);
-}
-
 // the row of stream or clip b (negative: dry) and its length
 __device__ __forceinline__ int row_of(const ReverbArgs &a, int b, int &len)
 {
     const int raw = a.rir_row ? a.rir_row[b] : 0;
     const int r = min(max(raw, 0), a.M - 1);
-    len = clamped(a.rir_len, r, 1, a.K, a.K);
+    len = clamped_at(a.rir_len, r, 1, a.K, a.K);
     return raw < 0 ? -1 : r;
 }
 
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(THREADS) void reverb_stream_kernel(const ReverbArgs
     __shared__ Tile lds;
     const int b = blockIdx.y, t = threadIdx.x, H = a.n_in, Hs = a.K - 1;
     const long long o0 = (long long)blockIdx.x * TILE;
-    const long long c = clamped(a.count, b, 0, H, H);
+    const long long c = stream_count(a.count, b, H);
     if (o0 >= c) return;                                                        // workgroup-uniform
     const float *__restrict__ x = a.audio + (size_t)b * H;
     float *__restrict__ out = a.out + (size_t)b * H;
@@ -118,36 +114,24 @@ __global__ __launch_bounds__(THREADS) void reverb_state_kernel(const ReverbArgs 
 {
     const int b = blockIdx.x, tid = threadIdx.x, H = a.n_in, Hs = a.K - 1;
     const size_t block = state_block_bytes(a.K);
+    // launched only where there is a state_out: its block is formed without the null test of state_block
     const unsigned char *sin = a.state_in ? a.state_in + (size_t)b * block : nullptr;
     unsigned char *sout = a.state_out + (size_t)b * block;
-    const bool copy = sout != sin;
-    const int c = clamped(a.count, b, 0, H, H);
-    const uint32_t *win = reinterpret_cast<const uint32_t *>(sin);
-    uint32_t *wout = reinterpret_cast<uint32_t *>(sout);
+    const StateBlock blk{sin, sout, sout != sin};
+    const int c = stream_count(a.count, b, H);
     if (c == 0) {
-        // an idle stream: its block travels as it is (out of place), or stays (in place)
-        if (copy)
-            for (size_t i = tid; i < block / 4; i += THREADS) wout[i] = win ? win[i] : 0u;
+        carry_idle_block<THREADS>(blk, block, tid);
         return;
     }
+    // samples move as words, so -0.0 and NaN payloads stay
+    const uint32_t *win = reinterpret_cast<const uint32_t *>(blk.sin);
+    uint32_t *wout = reinterpret_cast<uint32_t *>(blk.sout);
     const uint32_t *x = reinterpret_cast<const uint32_t *>(a.audio + (size_t)b * H);
-    // Chunks of THREADS samples in ascending order, each read whole before it is stored: new[j] = old[j + c], so a chunk
-    // reads at or above its own indices and strictly above every chunk stored before it -- a push shorter than the history
-    // shifts within the block, and state_out may be state_in.
-    for (int base = 0; base < Hs; base += THREADS) {
-        const int j = base + tid;
-        uint32_t v = 0u;
-        if (j < Hs) {
-            const long long src = (long long)j + c;
-            if (src >= Hs) v = x[src - Hs];
-            else if (win) v = win[src];
-        }
-        __syncthreads();
-        if (j < Hs) wout[j] = v;
-    }
-    // out of place: the padding travels too
-    if (copy)
-        for (size_t i = (size_t)Hs + tid; i < block / 4; i += THREADS) wout[i] = win ? win[i] : 0u;
+    shift_history<THREADS>(Hs, c, tid,
+                           [&](const long long j) { return win ? win[j] : 0u; },
+                           [&](const long long i) { return x[i]; },
+                           [&](const int j, const uint32_t v) { wout[j] = v; });
+    carry_words<THREADS>(blk, (size_t)Hs, block, tid);            // out of place: the padding travels too
 }
 
 // what both entry points ask of the bank and of a row's shape; LSM_OK, or the code with the message set
@@ -160,12 +144,7 @@ int check_bank(const char *what, int n, int n_rows, int n_rir_rows, int n_taps)
     return LSM_OK;
 }
 
-#define REVERB_ALIGNED(ptr, bytes) \
-    LSM_REQUIRE(((uintptr_t)(ptr) & ((bytes) - 1u)) == 0, #ptr " is misaligned: it must be %d-byte aligned", (int)(bytes))
-
 }  // namespace
-
-#define LSM_API extern "C" __attribute__((visibility("default")))
 
 LSM_API long lsm_reverb_state_bytes(int n_taps)
 {
@@ -179,11 +158,11 @@ LSM_API int lsm_reverb_f32(const float *audio, int n_clips, int n_in, const floa
     const int rc = check_bank("n_in", n_in, n_clips, n_rir_rows, n_taps);
     if (rc != LSM_OK) return rc;
     LSM_REQUIRE(n_out >= 1, "n_out=%d must be >= 1", n_out);
-    REVERB_ALIGNED(audio, 4);
-    REVERB_ALIGNED(rir, 4);
-    REVERB_ALIGNED(out, 4);
-    REVERB_ALIGNED(rir_len, 4);
-    REVERB_ALIGNED(rir_row, 4);
+    LSM_REQUIRE_ALIGNED(audio, 4);
+    LSM_REQUIRE_ALIGNED(rir, 4);
+    LSM_REQUIRE_ALIGNED(out, 4);
+    LSM_REQUIRE_ALIGNED(rir_len, 4);
+    LSM_REQUIRE_ALIGNED(rir_row, 4);
     if (n_clips == 0) return LSM_OK;
     LSM_REQUIRE(audio && rir && out, "reverb: null buffer (audio, rir and out are required)");
     LSM_REQUIRE(out != audio, "out must not be audio: an output reads the samples in front of it");
@@ -202,14 +181,14 @@ LSM_API int lsm_reverb_stream_f32(const float *audio, int n_streams, int n_cols,
 {
     const int rc = check_bank("n_cols", n_cols, n_streams, n_rir_rows, n_taps);
     if (rc != LSM_OK) return rc;
-    REVERB_ALIGNED(audio, 4);
-    REVERB_ALIGNED(rir, 4);
-    REVERB_ALIGNED(out, 4);
-    REVERB_ALIGNED(rir_len, 4);
-    REVERB_ALIGNED(rir_row, 4);
-    REVERB_ALIGNED(count, 4);
-    REVERB_ALIGNED(state_in, 16);
-    REVERB_ALIGNED(state_out, 16);
+    LSM_REQUIRE_ALIGNED(audio, 4);
+    LSM_REQUIRE_ALIGNED(rir, 4);
+    LSM_REQUIRE_ALIGNED(out, 4);
+    LSM_REQUIRE_ALIGNED(rir_len, 4);
+    LSM_REQUIRE_ALIGNED(rir_row, 4);
+    LSM_REQUIRE_ALIGNED(count, 4);
+    LSM_REQUIRE_ALIGNED(state_in, 16);
+    LSM_REQUIRE_ALIGNED(state_out, 16);
     if (n_streams == 0) return LSM_OK;
     LSM_REQUIRE(audio && rir && out, "reverb stream: null buffer (audio, rir and out are required)");
     LSM_REQUIRE(out != audio, "out must not be audio: an output reads the samples in front of it");

@@ -13,7 +13,7 @@
 // every window slot, where a flat layout would put lanes R samples apart on the same banks.  The chunk's taps are staged
 // as float64 as well; every lane reads the same tap, which the LDS broadcasts.  LDS use is fixed, whatever K.
 #pragma once
-#include "lsm_common.h"
+#include "stream_state.h"
 
 namespace lsm_reverb {
 
@@ -38,7 +38,7 @@ struct Tile {
 __host__ __device__ inline size_t state_block_bytes(int n_taps)
 {
     const size_t used = (size_t)(n_taps - 1) * 4;
-    return used ? (used + 15) & ~(size_t)15 : 16;
+    return used ? lsm_state::state_round16(used) : 16;
 }
 
 // R taps of one lane: tp[e] against the window g[0 .. 2R - 2] = S[R * row + 0 ..], whose lower R values are `lo` (row `row`)

@@ -98,8 +98,6 @@ const char *design_fault(const int32_t *d)
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API long lsm_speed_lds_bytes(const int32_t *designs, int n_designs)
 {
     if (!designs || n_designs < 1 || n_designs > MAX_DESIGNS) return 0;
@@ -130,14 +128,13 @@ LSM_API int lsm_speed_f32(const void *audio, int sample_format, int n_clips, int
                     n_taps_total);
     }
     LSM_REQUIRE(audio && taps_dev, "speed: null buffer");
-    LSM_REQUIRE(((uintptr_t)audio & (sample_format ? 1u : 3u)) == 0, "audio is misaligned: it must be %d-byte aligned",
-                sample_format ? 2 : 4);
-    LSM_REQUIRE(((uintptr_t)taps_dev & 7u) == 0, "taps_dev is misaligned: it must be 8-byte aligned");
-    LSM_REQUIRE(((uintptr_t)design_row & 3u) == 0, "design_row is misaligned: it must be 4-byte aligned");
+    LSM_REQUIRE_ALIGNED(audio, sample_format ? 2 : 4);
+    LSM_REQUIRE_ALIGNED(taps_dev, 8);
+    LSM_REQUIRE_ALIGNED(design_row, 4);
     LSM_REQUIRE(n_clips >= 1 && n_clips <= 65535, "n_clips=%d outside [1, 65535] (grid.y)", n_clips);
     LSM_REQUIRE(n_in >= 1 && n_out >= 1, "n_in=%d and n_out=%d must be >= 1", n_in, n_out);
     LSM_REQUIRE(out != nullptr, "out is required");
-    LSM_REQUIRE(((uintptr_t)out & 3u) == 0, "out is misaligned: it must be 4-byte aligned");
+    LSM_REQUIRE_ALIGNED(out, 4);
     LSM_REQUIRE(out != audio, "out must not be audio: an output reads the samples around it");
     SpeedArgs a{};
     size_t lds = 0;

@@ -50,6 +50,52 @@ __device__ __forceinline__ void clip_counts(const RaggedCounts &rc, int b, int n
     Tb = live ? t : 0;
 }
 
+// ---- the column tail of the streamed encoders: one dB value of a column -> normalised value -> latch -> raster bytes ----
+
+// The launch functions' threshold tables: entries from n_thr on hold the pads.  The default pads never fire -- nothing is
+// > +inf or < -inf -- so a kernel may compare all MAX_THR entries.
+template <typename T>
+void fill_thresholds(T (&on)[MAX_THR], T (&off)[MAX_THR], const T *thr_on, const T *thr_off, int n_thr, T pad_on = (T)INFINITY,
+                     T pad_off = (T)-INFINITY)
+{
+    for (int q = 0; q < MAX_THR; ++q) {
+        on[q] = q < n_thr ? thr_on[q] : pad_on;
+        off[q] = q < n_thr ? thr_off[q] : pad_off;
+    }
+}
+
+// A dB value floored at `fl` and normalised to the range [lo, lo + den).  A NaN stays a NaN through the floor and compares
+// false with every threshold: the latches keep their state.
+template <typename T>
+__device__ __forceinline__ T floored_value(T v, T fl, T lo, T den)
+{
+    const T vf = v < fl ? fl : v;
+    return (vf - lo) / den;
+}
+
+// (The MAX_THR-wide compare of a value with the launch's tables stays written out in the two kernels that have it: handed to
+// a function, the tables' kernel-argument loads are grouped differently and the kernels need more scalar registers.)
+
+// rising and falling are both taken from the latch before the update (SPEC.md §1.3)
+__device__ __forceinline__ uint32_t latch_step(uint32_t act, uint32_t up, uint32_t dn, uint32_t tmask)
+{
+    return ((up & ~act) | (act & ~dn)) & tmask;
+}
+
+// Column `col` of one filter's raster rows, threshold t's byte from bit t of `bits`: a word where n_thr = 4 (the multiply
+// spreads bits 0..3 over the word's four bytes), bytes otherwise.  Redundancy: the filter's R output rows, `rrow` the
+// first, repeat it (SPEC.md §1.4).
+__device__ __forceinline__ void store_column(uint8_t *rrow, size_t row_bytes, int col, int n_thr, int R, uint32_t bits)
+{
+    if (n_thr == 4) {
+        const uint32_t word = (bits * 0x00204081u) & 0x01010101u;
+        for (int r = 0; r < R; ++r) *reinterpret_cast<uint32_t *>(rrow + (size_t)r * row_bytes + (size_t)col * 4) = word;
+    } else {
+        for (int r = 0; r < R; ++r)
+            for (int t = 0; t < n_thr; ++t) rrow[(size_t)r * row_bytes + (size_t)col * n_thr + t] = (uint8_t)((bits >> t) & 1u);
+    }
+}
+
 template <typename T>
 __device__ __forceinline__ T block_reduce(T v, bool is_max, T *scratch)
 {

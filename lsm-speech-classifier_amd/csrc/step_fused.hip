@@ -231,8 +231,6 @@ int step_launch(const StepOwn &own, const lsm_reservoir *h, const float *audio, 
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API int lsm_step_fused_supported(const lsm_reservoir *h, int n_clips, int n_filters, int nwin, int hop, int time_bins,
                                      int n_thr, int redundancy, int coef_flags)
 {

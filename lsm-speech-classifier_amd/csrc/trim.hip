@@ -126,8 +126,6 @@ __global__ __launch_bounds__(THREADS) void trim_kernel(const TrimArgs a)
 
 }  // namespace
 
-#define LSM_API extern "C" __attribute__((visibility("default")))
-
 LSM_API int lsm_trim_lds_bytes(int time_bins)
 {
     if (time_bins < MIN_BINS || time_bins > MAX_BINS) return LSM_ERR_ARG;

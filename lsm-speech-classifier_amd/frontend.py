@@ -590,9 +590,47 @@ def stream_column_plan(seen_hops, new_hops, nwin: int = STREAM_NWIN, hop: int = 
     return int(cols) if np.ndim(seen_hops) == 0 and np.ndim(new_hops) == 0 else cols
 
 
-class _AudioStreamBase:
-    """What the streamed front ends share: ``n_streams`` state blocks on the device, the hops each stream has seen, and the
-    checks of a push's arguments.  A subclass sets n_filters, n_streams, hop, redundancy, on, device, state and seen."""
+class _StreamPush:
+    """What a push of any bank of streams needs: the check of a caller-owned output and the upload of its counts.  A
+    subclass sets n_streams and device.  (`MixStream`, whose whole state is a noise position per stream, stops here.)"""
+
+    def _owned(self, t, shape, dtype, name, word=None):
+        """A caller-owned output checked, or zeros where the caller gave none (``word``: the dtype as the refusal says it)."""
+        if t is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() \
+                or t.device != self.device:
+            raise ValueError(f"{name} must be a contiguous {word or dtype} {shape} tensor on {self.device}")
+        return t
+
+    def _count_array(self, given, new):
+        """A push's per-stream counts for the kernel: None where the caller gave none (every stream takes the whole row),
+        or the checked counts ``new`` as int32 on the device."""
+        return None if given is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+
+
+class _StreamBank(_StreamPush):
+    """A bank with ``n_streams`` state blocks on the device (DESIGN.md "The state block"; all zeros are a stream's start).
+    A subclass sets n_streams and device before it asks for the state."""
+
+    def _new_state(self, state_bytes) -> None:
+        self.state_bytes = int(state_bytes)
+        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+
+    def _reset_state(self, slots) -> np.ndarray:
+        """The state blocks of ``slots`` back to zeros; returns the checked slots for what else a subclass clears."""
+        slots = checked_slots(slots, self.n_streams)
+        self.state[torch.from_numpy(slots).to(self.device)] = 0
+        return slots
+
+    def reset(self, slots) -> None:
+        """The streams in ``slots`` have ended and new ones take their places: their state blocks back to zeros."""
+        self._reset_state(slots)
+
+
+class _AudioStreamBase(_StreamBank):
+    """What the streamed front ends share beyond `_StreamBank`: the hops each stream has seen and the checks of a push's
+    arguments.  A subclass sets n_filters, n_streams, hop, redundancy, on, device, state and seen."""
 
     @property
     def n_thr(self) -> int:
@@ -604,16 +642,7 @@ class _AudioStreamBase:
 
     def reset(self, slots) -> None:
         """The streams in ``slots`` have ended and new ones take their places: state block and hop count back to zero."""
-        slots = checked_slots(slots, self.n_streams)
-        self.state[torch.from_numpy(slots).to(self.device)] = 0
-        self.seen[slots] = 0
-
-    def _out(self, t, shape, dtype, name):
-        if t is None:
-            return torch.zeros(shape, dtype=dtype, device=self.device)
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
-            raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on {self.device}")
-        return t
+        self.seen[self._reset_state(slots)] = 0
 
     def _pushed(self, audio, hops):
         """A push's arguments checked: (audio on the device, H, the new hops per stream as int64)."""
@@ -661,8 +690,7 @@ class GammatoneStream(_AudioStreamBase):
         tab = gammatone_filter_table(SAMPLE_RATE, self.n_filters, GT_F_MIN)
         self.coefs = torch.from_numpy(tab).to(self.device)
         self.coef_flags = coef_flags(tab)
-        self.state_bytes = int(self.lib.lsm_gammatone_stream_state_bytes(self.n_filters, self.nwin, self.hop))
-        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self._new_state(self.lib.lsm_gammatone_stream_state_bytes(self.n_filters, self.nwin, self.hop))
         self.seen = np.zeros(self.n_streams, dtype=np.int64)            # hops since the stream's start
 
     def push(self, audio, hops=None, want_db: bool = False, want_spec: bool = False, raster_out=None, db_out=None,
@@ -676,11 +704,11 @@ class GammatoneStream(_AudioStreamBase):
         audio, H, new = self._pushed(audio, hops)
         cols = stream_column_plan(self.seen, new, self.nwin, self.hop)
         with torch.cuda.device(self.device):
-            raster = self._out(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
+            raster = self._owned(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
             shape = (self.n_streams, self.n_filters, H)
-            db = self._out(db_out, shape, torch.float64, "db_out") if (want_db or db_out is not None) else None
-            spec = self._out(spec_out, shape, torch.float64, "spec_out") if (want_spec or spec_out is not None) else None
-            counts = None if hops is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            db = self._owned(db_out, shape, torch.float64, "db_out") if (want_db or db_out is not None) else None
+            spec = self._owned(spec_out, shape, torch.float64, "spec_out") if (want_spec or spec_out is not None) else None
+            counts = self._count_array(hops, new)
             _lib.check(self.lib.lsm_gammatone_stream_f64(
                 _dev(audio), self.n_streams, H, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
                 _dev(counts) if counts is not None else None, self.db_lo, self.db_hi, _host(self.on), _host(self.off),
@@ -756,8 +784,7 @@ class MelStream(_AudioStreamBase):
         self.device = indexed_device(device)
         from . import mel as _mel
         self.window, self.twiddle, self.basis, self.lo, self.hi = _mel.device_tables(self.n_filters, self.device)
-        self.state_bytes = int(self.lib.lsm_mel_stream_state_bytes(self.n_filters, MEL_N_FFT, self.hop))
-        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self._new_state(self.lib.lsm_mel_stream_state_bytes(self.n_filters, MEL_N_FFT, self.hop))
         self.seen = np.zeros(self.n_streams, dtype=np.int64)            # hops since the stream's start
         self._ws = None                                                 # scratch of the launches, grown on demand
 
@@ -773,11 +800,11 @@ class MelStream(_AudioStreamBase):
         audio, H, new = self._pushed(audio, hops)
         cols = mel_stream_frame_plan(self.seen, new, self.hop)
         with torch.cuda.device(self.device):
-            raster = self._out(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
+            raster = self._owned(raster_out, (self.n_streams, self.n_channels, H * self.n_thr), torch.uint8, "raster_out")
             shape = (self.n_streams, self.n_filters, H)
-            db = self._out(db_out, shape, torch.float32, "db_out") if (want_db or db_out is not None) else None
-            power = self._out(power_out, shape, torch.float32, "power_out") if (want_power or power_out is not None) else None
-            counts = None if hops is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            db = self._owned(db_out, shape, torch.float32, "db_out") if (want_db or db_out is not None) else None
+            power = self._owned(power_out, shape, torch.float32, "power_out") if (want_power or power_out is not None) else None
+            counts = self._count_array(hops, new)
             need = int(self.lib.lsm_mel_stream_workspace(self.n_streams, self.n_filters, H))
             if self._ws is None or self._ws.numel() < need:
                 # launches of one bank run in order on the current stream and may share the scratch; the caching allocator
@@ -802,7 +829,7 @@ ADAPTIVE_MAX_WINDOW = 4096
 _ADAPTIVE_DTYPES = {torch.float64: np.float64, torch.float32: np.float32}
 
 
-class AdaptiveEncoder:
+class AdaptiveEncoder(_StreamBank):
     """The spike encoder with a sliding normalisation range (`lsm_adaptive_encode_f64` / `_f32`, SPEC.md §1.9): dB columns
     of ``n_streams`` streams in, raster columns out.  Column c is normalised with the minimum and maximum of the stream's
     columns ``max(0, c - window_cols + 1) .. c`` after the 80 dB floor -- the reference's per-clip rule made causal -- and
@@ -836,10 +863,10 @@ class AdaptiveEncoder:
         self.device = indexed_device(device)
         self._encode = self.lib.lsm_adaptive_encode_f64 if self.dtype == torch.float64 else self.lib.lsm_adaptive_encode_f32
         elem = 8 if self.dtype == torch.float64 else 4
-        self.state_bytes = int(self.lib.lsm_adaptive_state_bytes(self.n_filters, self.window_cols, elem))
-        if self.state_bytes < 1:
+        state_bytes = int(self.lib.lsm_adaptive_state_bytes(self.n_filters, self.window_cols, elem))
+        if state_bytes < 1:
             raise ValueError(f"the encoder refuses n_filters = {n_filters} with window_cols = {window_cols}")
-        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self._new_state(state_bytes)
 
     @property
     def n_thr(self) -> int:
@@ -848,11 +875,6 @@ class AdaptiveEncoder:
     @property
     def n_channels(self) -> int:
         return self.n_filters * self.redundancy
-
-    def reset(self, slots) -> None:
-        """The streams in ``slots`` have ended and new ones take their places: no carried columns, latches off."""
-        slots = checked_slots(slots, self.n_streams)
-        self.state[torch.from_numpy(slots).to(self.device)] = 0
 
     def push_db(self, db, cols=None, raster_out=None, want_range: bool = False):
         """``db`` (n_streams, n_filters, H) of the encoder's dtype: stream b's new columns are the first ``cols[b]`` of its
@@ -869,17 +891,14 @@ class AdaptiveEncoder:
         H = int(db.shape[2])
         new = checked_counts(cols, self.n_streams, H, "cols")
         shape = (self.n_streams, self.n_channels, H * self.n_thr)
-        if raster_out is not None and (raster_out.dtype != torch.uint8 or tuple(raster_out.shape) != shape
-                                       or not raster_out.is_contiguous() or raster_out.device != self.device):
-            raise ValueError(f"raster_out must be a contiguous uint8 {shape} tensor on {self.device}")
         with torch.cuda.device(self.device):
+            raster = self._owned(raster_out, shape, torch.uint8, "raster_out", "uint8")
             db = db.to(self.device).contiguous()
-            raster = torch.zeros(shape, dtype=torch.uint8, device=self.device) if raster_out is None else raster_out
             lo = hi = None
             if want_range:
                 lo = torch.zeros((self.n_streams, H), dtype=self.dtype, device=self.device)
                 hi = torch.zeros((self.n_streams, H), dtype=self.dtype, device=self.device)
-            counts = None if cols is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            counts = self._count_array(cols, new)
             _lib.check(self._encode(
                 _dev(db), self.n_streams, H, self.n_filters, _dev(counts) if counts is not None else None, self.window_cols,
                 _host(self.on), _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state),
@@ -1097,7 +1116,7 @@ class Resampler(_ResampleBase):
         return out
 
 
-class ResampleStream(_ResampleBase):
+class ResampleStream(_ResampleBase, _StreamBank):
     """``n_streams`` open-ended PCM streams from ``rate_in`` to ``rate_out`` (`lsm_resample_stream_f32`, SPEC.md §1.8): every
     ``push`` advances each stream by the whole blocks of ``down`` input samples it delivers -- any number, 0 included -- from
     the history the bank holds (the stream's last ``history`` samples) and returns ``up`` samples per block: the next samples
@@ -1111,13 +1130,7 @@ class ResampleStream(_ResampleBase):
             raise ValueError(f"ResampleStream needs n_streams in [1, {Resampler.MAX_ROWS}], got {n_streams}")
         super().__init__(rate_in, rate_out, device)
         self.unit_blocks, self.unit_in, self.unit_hops = resample_units(self.up, self.down)
-        self.state_bytes = int(self.lib.lsm_resample_state_bytes(len(self.taps), self.up))
-        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
-
-    def reset(self, slots) -> None:
-        """The streams in ``slots`` have ended and new ones take their places: their history back to zeros."""
-        slots = checked_slots(slots, self.n_streams)
-        self.state[torch.from_numpy(slots).to(self.device)] = 0
+        self._new_state(self.lib.lsm_resample_state_bytes(len(self.taps), self.up))
 
     def push(self, audio, blocks=None, out: torch.Tensor | None = None):
         """``audio`` (n_streams, G * down) float32 or int16: stream b's new samples are the first ``blocks[b] * down`` of its
@@ -1127,19 +1140,14 @@ class ResampleStream(_ResampleBase):
         audio, fmt = checked_pcm(audio, self.n_streams, self.down)
         G = int(audio.shape[1]) // self.down
         new = checked_counts(blocks, self.n_streams, G)
-        shape = (self.n_streams, G * self.up)
-        if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous()
-                                or out.device != self.device):
-            raise ValueError(f"out must be a contiguous float32 {shape} tensor on {self.device}")
         with torch.cuda.device(self.device):
+            out = self._owned(out, (self.n_streams, G * self.up), torch.float32, "out", "float32")
             audio = audio.to(self.device)
-            if out is None:
-                out = torch.zeros(shape, dtype=torch.float32, device=self.device)
             if self.identity:
                 live = torch.from_numpy(np.arange(G)[None, :] < new[:, None]).to(self.device)
                 out[live] = self._as_float(audio)[live]
                 return out, new * self.up
-            counts = None if blocks is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            counts = self._count_array(blocks, new)
             _lib.check(self.lib.lsm_resample_stream_f32(
                 _dev(audio), fmt, self.n_streams, G, _dev(self.taps_dev), len(self.taps), self.up, self.down,
                 _dev(counts) if counts is not None else None, _dev(self.state), _dev(self.state), _dev(out),
@@ -1356,7 +1364,7 @@ class NoiseMixer:
         return (out, gain, powers) if want_gain else out
 
 
-class MixStream:
+class MixStream(_StreamPush):
     """``n_streams`` open-ended streams through the mixer's streamed form (`lsm_mix_stream_f32`): every `push` scales each
     stream's new samples and adds the next samples of its noise row, from the position the bank holds -- a stream's whole
     state.  A stream cut into pushes anywhere gives, byte for byte, the samples of its uncut run.  A stream has no clip to
@@ -1413,9 +1421,8 @@ class MixStream:
             raise ValueError(f"audio must be ({self.n_streams}, H) with 1 <= H <= {MIX_MAX_SAMPLES}, got {tuple(audio.shape)}")
         H = int(audio.shape[1])
         new = checked_counts(counts, self.n_streams, H, "counts")
-        if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (self.n_streams, H)
-                                or not out.is_contiguous() or out.device != self.device):
-            raise ValueError(f"out must be a contiguous float32 {(self.n_streams, H)} tensor on {self.device}")
+        if out is not None:
+            self._owned(out, (self.n_streams, H), torch.float32, "out", "float32")
         mixer = self.mixer
         with torch.cuda.device(self.device):
             if out is None:                                     # a copy of the rows, mixed in place
@@ -1423,7 +1430,7 @@ class MixStream:
                 audio = out
             else:
                 audio = audio.to(self.device)
-            cnt = None if counts is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            cnt = self._count_array(counts, new)
             _lib.check(mixer.lib.lsm_mix_stream_f32(
                 _dev(audio), self.n_streams, H, _dev(mixer.noise), mixer.n_rows, mixer.noise_len,
                 _dev(cnt) if cnt is not None else None, _dev(self.gain), _dev(self.scale), _dev(self.rows),
@@ -1539,7 +1546,7 @@ class Reverberator:
         return out
 
 
-class ReverbStream:
+class ReverbStream(_StreamBank):
     """``n_streams`` open-ended streams through the reverberator's streamed form (`lsm_reverb_stream_f32`): every `push`
     convolves each stream's new samples -- any number, 0 included -- behind the history the bank holds, the stream's last
     K - 1 input samples.  A stream cut into pushes anywhere gives, byte for byte, the samples of its uncut run.  Until `set`,
@@ -1550,8 +1557,7 @@ class ReverbStream:
         self.reverberator, self.n_streams, self.device = reverberator, int(n_streams), reverberator.device
         if self.n_streams < 1 or self.n_streams > REVERB_MAX_ROWS:
             raise ValueError(f"ReverbStream needs n_streams in [1, {REVERB_MAX_ROWS}], got {n_streams}")
-        self.state_bytes = int(reverberator.lib.lsm_reverb_state_bytes(reverberator.n_taps))
-        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self._new_state(reverberator.lib.lsm_reverb_state_bytes(reverberator.n_taps))
         self.rows = torch.zeros(self.n_streams, dtype=torch.int32, device=self.device)
 
     def set(self, slots, rows) -> None:
@@ -1562,11 +1568,6 @@ class ReverbStream:
             raise ValueError(f"rows {rows.tolist()} outside the bank's {self.reverberator.n_rows} rows")
         self.rows[torch.from_numpy(slots).to(self.device)] = torch.from_numpy(rows).to(self.device)
 
-    def reset(self, slots) -> None:
-        """The streams in ``slots`` have ended and new ones take their places: their histories back to zeros."""
-        slots = checked_slots(slots, self.n_streams)
-        self.state[torch.from_numpy(slots).to(self.device)] = 0
-
     def push(self, audio, counts=None, out: torch.Tensor | None = None):
         """``audio`` (n_streams, H) float32: stream b's new samples are the first ``counts[b]`` of its row; ``counts``:
         n_streams host integers in [0, H], or None for H everywhere.  Returns ``(out, counts)``: float32 (n_streams, H) on
@@ -1575,18 +1576,14 @@ class ReverbStream:
         audio = _reverb_audio(audio, self.n_streams)
         H = int(audio.shape[1])
         new = checked_counts(counts, self.n_streams, H, "counts")
-        if out is not None:
-            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (self.n_streams, H) \
-                    or not out.is_contiguous() or out.device != self.device:
-                raise ValueError(f"out must be a contiguous float32 {(self.n_streams, H)} tensor on {self.device}")
-            if out is audio or out.data_ptr() == audio.data_ptr():
-                raise ValueError("out must not be audio: an output reads the samples in front of it")
         rv = self.reverberator
         with torch.cuda.device(self.device):
+            given = out is not None
+            out = self._owned(out, (self.n_streams, H), torch.float32, "out", "float32")
+            if given and (out is audio or out.data_ptr() == audio.data_ptr()):
+                raise ValueError("out must not be audio: an output reads the samples in front of it")
             audio = audio.to(self.device)
-            if out is None:
-                out = torch.zeros((self.n_streams, H), dtype=torch.float32, device=self.device)
-            cnt = None if counts is None else torch.from_numpy(new.astype(np.int32)).to(self.device)
+            cnt = self._count_array(counts, new)
             _lib.check(rv.lib.lsm_reverb_stream_f32(
                 _dev(audio), self.n_streams, H, _dev(rv.rir), rv.n_rows, rv.n_taps,
                 _dev(rv.lengths_dev) if rv.lengths_dev is not None else None, _dev(self.rows),
@@ -1872,7 +1869,7 @@ class Utterances(NamedTuple):
     count: torch.Tensor
 
 
-class EndpointStream:
+class EndpointStream(_StreamBank):
     """``n_streams`` open-ended audio streams cut into utterances on the device (`lsm_endpoint_stream_f32`, SPEC.md §1.17).
     A bin of 160 samples is active when its energy exceeds ``top_db`` dB under the loudest of the last ``window_bins`` bins and
     ``floor_db`` dB relative to full scale; an utterance opens ``pad_bins`` bins before an active bin, closes ``pad_bins`` bins
@@ -1905,8 +1902,7 @@ class EndpointStream:
         _lib.require_gpu()
         self.lib = _lib.load()
         self.device = indexed_device(device)
-        self.state_bytes = int(self.lib.lsm_endpoint_state_bytes(W, M))
-        self.state = torch.zeros((self.n_streams, self.state_bytes), dtype=torch.uint8, device=self.device)
+        self._new_state(self.lib.lsm_endpoint_state_bytes(W, M))
         self._outputs = {}                                              # per n_hops: the slot buffers of a push
 
     # a state block means what it says only under the window_bins and max_bins it was made with: read-only
@@ -1928,11 +1924,6 @@ class EndpointStream:
         """Slots per stream of a push of ``n_hops`` hops (`endpoint_max_utterances`; never below the library's figure)."""
         return max(endpoint_max_utterances(n_hops, self.pad_bins, self.hang_bins, self.max_bins),
                    int(self.lib.lsm_endpoint_max_utterances(int(n_hops), self.hang_bins, self.max_bins)))
-
-    def reset(self, slots) -> None:
-        """The streams in ``slots`` have ended and new ones take their places: their state blocks back to zeros."""
-        slots = checked_slots(slots, self.n_streams)
-        self.state[torch.from_numpy(slots).to(self.device)] = 0
 
     def _counts(self, values, n_hops: int, what: str):
         """``hops`` / ``finish`` as the int32 device tensor the kernel reads, or None: host integers checked, a device tensor

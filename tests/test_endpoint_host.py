@@ -366,7 +366,7 @@ def test_header_binding_and_library_carry_the_three_names():
     blob = open(build.lib_path(), "rb").read()
     for name in NEW:
         assert hasattr(lib, name) and name.encode() + b"\0" in blob, name
-    assert build.ENDPOINT_HEADERS == ["lsm_hip_endpoint.h"] and "endpoint.hip" in build.SOURCES
+    assert "lsm_hip_endpoint.h" in build.ABI_HEADERS and "endpoint.hip" in build.SOURCES
     assert {"endpoint_body.h", "bin_energy.h", "trim_body.h"} <= set(build.HEADERS)
     assert len(build.PUBLIC_HEADERS) == 9 and "lsm_hip_endpoint.h" not in build.PUBLIC_HEADERS
     with pytest.raises(OSError):                                    # the header is hashed into the build id

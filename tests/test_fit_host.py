@@ -51,8 +51,8 @@ def test_header_binding_and_library_carry_the_two_names(tmp_path):
     blob = open(build.lib_path(), "rb").read()
     for name in NEW:
         assert hasattr(lib, name) and name.encode() + b"\0" in blob, name
-    assert "fit.hip" in build.SOURCES and build.FIT_HEADERS == ["lsm_hip_fit.h"]
-    assert build.READOUT_HEADERS == ["lsm_hip_readout.h"] and len(build.PUBLIC_HEADERS) == 9
+    assert "fit.hip" in build.SOURCES and "lsm_hip_fit.h" in build.ABI_HEADERS
+    assert "lsm_hip_readout.h" in build.ABI_HEADERS and len(build.PUBLIC_HEADERS) == 9
     # the header is hashed into the build id: another text of it, another id
     inc = tmp_path / "include"
     shutil.copytree(os.path.join(ROOT, "include"), inc)

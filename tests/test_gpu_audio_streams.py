@@ -378,6 +378,69 @@ def test_refusals_launch_nothing(torch_cuda):
     assert gs.seen.tolist() == [0, 0] and not gs.state.any()
 
 
+@pytest.mark.parametrize("n_filters", [3, 65])     # 3: 264 bytes in use + 8 of padding; 65: a second wave group with dead lanes
+def test_separate_state_buffers(torch_cuda, n_filters):
+    """`lsm_gammatone_stream_f64` with state_out != state_in, with no state_in and with no state_out, against its own
+    in-place run: two pushes of H = 2 hops of which the streams deliver [2, 0, 1] (stream 1 is idle), nwin = 10 over
+    hop = 4 (three live windows).  `GammatoneStream` only ever passes state_out = state_in."""
+    torch = torch_cuda
+    from lsm_speech_classifier_amd import _lib, frontend
+    lib = _lib.load()
+    F, n, H, nwin, hop, R, PAD = n_filters, 3, 2, 10, 4, 2, 0x5A
+    used = (10 * 8 + 8) * F                                     # 8 filter + 2 window doubles, latch and hop count per channel
+    block = lib.lsm_gammatone_stream_state_bytes(F, nwin, hop)
+    assert block == (used + 15) // 16 * 16 and block - used == 8
+    tab = frontend.gammatone_filter_table(16000, F, 50)
+    coefs, flags = torch.from_numpy(tab).cuda(), frontend.coef_flags(tab)
+    on, off = frontend.threshold_tables(THR, GAP, np.float64)
+    rng = np.random.RandomState(77 + F)
+    pushes = [torch.from_numpy((rng.standard_normal((n, H * hop)) * 0.3).astype(np.float32)).cuda() for _ in range(2)]
+    hops = torch.tensor([2, 0, 1], dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def push(audio, s_in, s_out):
+        raster = torch.full((n, F * R, H * 4), FILL, dtype=torch.uint8, device="cuda")
+        db = torch.full((n, F, H), -7.0, dtype=torch.float64, device="cuda")
+        spec = torch.full((n, F, H), -7.0, dtype=torch.float64, device="cuda")
+        _lib.check(lib.lsm_gammatone_stream_f64(
+            C.c_void_p(audio.data_ptr()), n, H, C.c_void_p(coefs.data_ptr()), F, nwin, hop, C.c_void_p(hops.data_ptr()),
+            -40.0, -8.0, C.c_void_p(on.ctypes.data), C.c_void_p(off.ctypes.data), 4, R,
+            C.c_void_p(s_in.data_ptr()) if s_in is not None else None,
+            C.c_void_p(s_out.data_ptr()) if s_out is not None else None, C.c_void_p(raster.data_ptr()),
+            C.c_void_p(spec.data_ptr()), C.c_void_p(db.data_ptr()), flags, stream), "lsm_gammatone_stream_f64")
+        torch.cuda.synchronize()
+        return raster, db, spec
+
+    def same(a, b):
+        return all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip(a, b))
+
+    start = torch.zeros((n, block), dtype=torch.uint8, device="cuda")
+    start[:, used:] = PAD
+    # the in-place run
+    st = start.clone()
+    out1 = push(pushes[0], st, st)
+    st1 = st.clone()
+    out2 = push(pushes[1], st, st)
+    assert bool((out2[2][0] > 0).all()) and bool((out2[0][1:] == FILL).all())      # stream 0's fourth hop closes columns
+    assert torch.equal(st1[1], start[1]) and torch.equal(st[1], start[1]) and not torch.equal(st1[0], start[0])
+    # (a) - (d) out of place, state_out pre-filled
+    s0, s1, s2 = start.clone(), torch.full_like(start, 0x3C), torch.full_like(start, 0x3C)
+    assert same(push(pushes[0], s0, s1), out1), "out of place: other outputs than in place"
+    assert torch.equal(s1[:, :used], st1[:, :used]), "out of place: other state bytes than in place"
+    assert torch.equal(s0, start), "state_in was written"
+    assert torch.equal(s1[1], start[1]), "the idle stream's block did not arrive as it was"
+    assert bool((s1[[0, 2], used:] == PAD).all()), "the padding of the active streams did not travel"
+    assert same(push(pushes[1], s1, s2), out2) and torch.equal(s2, st), "second push out of place"
+    assert torch.equal(s1[:, :used], st1[:, :used]), "state_in was written"
+    # (e) no state_in: a block of zeros
+    zeros, s3, s4 = torch.zeros_like(start), torch.full_like(start, 0x3C), torch.full_like(start, 0x3C)
+    assert same(push(pushes[0], None, s3), push(pushes[0], zeros, s4)) and torch.equal(s3, s4)
+    assert not s3[1].any() and torch.equal(s3[:, :used], st1[:, :used])
+    # (f) no state_out: the same raster, no state written
+    assert same(push(pushes[1], s1, None), out2) and torch.equal(s1[:, :used], st1[:, :used])
+    assert bool((s1[[0, 2], used:] == PAD).all())
+
+
 def test_db_range_is_the_split_paths_floored_range(torch_cuda, oracle_c):
     from lsm_speech_classifier_amd import frontend, synth
     from oracle import ref_numpy

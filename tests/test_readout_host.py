@@ -255,7 +255,7 @@ def test_header_binding_and_library_carry_the_three_names(tmp_path):
     blob = open(build.lib_path(), "rb").read()
     for name in NEW:
         assert hasattr(lib, name) and name.encode() + b"\0" in blob, name
-    assert "readout.hip" in build.SOURCES and build.READOUT_HEADERS == ["lsm_hip_readout.h"]
+    assert "readout.hip" in build.SOURCES and "lsm_hip_readout.h" in build.ABI_HEADERS
     assert "reservoir_facts.h" in build.HEADERS and len(build.PUBLIC_HEADERS) == 9
     # the header is hashed into the build id: another text of it, another id
     inc = tmp_path / "include"

@@ -61,7 +61,7 @@ def test_header_binding_and_library_carry_the_three_names():
 def test_the_build_covers_the_new_unit_and_header():
     from lsm_speech_classifier_amd import build
     assert "step_fused_state.hip" in build.SOURCES
-    assert "lsm_hip_step_state.h" in build.STEP_STATE_HEADERS
+    assert "lsm_hip_step_state.h" in build.ABI_HEADERS
     before = build.source_id()
     path = os.path.join(ROOT, "include", "lsm_hip_step_state.h")
     assert os.path.exists(path)
