@@ -370,7 +370,7 @@ def _synthetic_utterances(commands, per_class: int, max_bins: int):
 def create_variable_length_dataset(n_filters: int, filterbank: str, commands=None, dataset_root=None,
                                    max_per_class: int = MAX_SAMPLES_PER_CLASS, synthetic_per_class: int = 0,
                                    output_file: str = OUTPUT_FILE, max_seconds: float = DURATION, trim=None, augment=None,
-                                   reverb=None, mask=None):
+                                   reverb=None, mask=None, speed=None):
     """File 1 with every clip at its own length (`--variable-length`, SPEC.md 1.14): the wav files are not padded to one
     second, only trimmed at ``max_seconds``, and go through the ragged front end (`SpikeFrontEnd.encode_ragged`) in batches,
     longest first.  ``X_spikes`` keeps its schema at the stride ``100 * max_seconds * n_thr`` steps -- clip r's rows hold its
@@ -380,7 +380,10 @@ def create_variable_length_dataset(n_filters: int, filterbank: str, commands=Non
     rows hold the trimmed clips and ``n_steps`` their lengths.  ``reverb`` (`reverb_from_args`), ``augment``
     (`augment_from_args`) and ``mask`` (`mask_from_args`): behind the trim every clip is reverberated, mixed with noise and
     masked inside the encoder at its OWN length (SPEC.md 1.16; `AugmentChain.apply_ragged`, `frontend.mask_plan_ragged`), from
-    plans drawn for the whole listing in listing order; speed perturbation is not offered here."""
+    plans drawn for the whole listing in listing order.  ``speed`` (`speed_from_args`): ahead of the trim every clip is played
+    at a speed drawn from a list of factors, as the clip alone (SPEC.md 1.18; `AugmentChain.speed_ragged`), from
+    `speeds` for the whole listing in listing order; the rows hold the perturbed (then trimmed) clips and ``n_steps`` their
+    lengths, a slowed clip cut at ``max_seconds``."""
     from lsm_speech_classifier_amd import spikefile
     commands = list(COMMANDS if commands is None else commands)
     root = Path(DATASET_ROOT if dataset_root is None else dataset_root)
@@ -403,19 +406,40 @@ def create_variable_length_dataset(n_filters: int, filterbank: str, commands=Non
                           gap=HYSTERESIS_GAP, time_bins=max_bins, n_samples=max_bins * fr.RAGGED_HOP)
     audio, bins = fr.pack_utterances(clips, max_bins)
     X = np.zeros((len(clips), fe.n_channels, fe.n_steps), dtype=np.uint8)
+    from lsm_speech_classifier_amd.augment import AugmentChain, StepPlans
+    samples = None
+    if speed:
+        import torch
+        factors, paces = speeds(speed, len(clips))
+        pace = AugmentChain(speed=fr.SpeedPerturber(factors, device=fe.device))
+        lengths = bins.astype(np.int64) * fr.RAGGED_HOP
+        new_bins = -(-fr.speed_ragged_lengths(lengths, paces.choice, pace.speed, fe.n_samples) // fr.RAGGED_HOP)
+        if (new_bins < fr.RAGGED_MIN_BINS).any():
+            r = int(np.nonzero(new_bins < fr.RAGGED_MIN_BINS)[0][0])
+            raise SystemExit(f"--speed-factors: clip {r} of the listing has {int(bins[r])} time bins and {int(new_bins[r])} at "
+                             f"speed {factors[int(paces.choice[r])]}: a clip needs {fr.RAGGED_MIN_BINS}")
+        rows = torch.empty((len(clips), fe.n_samples), dtype=torch.float32, device=fe.device)
+        samples = torch.empty((len(clips),), dtype=torch.int32, device=fe.device)
+        for a in range(0, len(clips), ENCODE_BATCH):
+            _, part, _ = pace.speed_ragged(audio[a:a + ENCODE_BATCH], lengths[a:a + ENCODE_BATCH],
+                                           StepPlans(speed=paces.part(a, a + ENCODE_BATCH)), time_bins=max_bins,
+                                           out=rows[a:a + ENCODE_BATCH])
+            samples[a:a + ENCODE_BATCH] = part
+        audio, bins = rows, new_bins.astype(np.int32)   # the host bins from the formula: nothing is read back
+        print(f"  Speeds {','.join(map(str, factors))}: {int(bins.min())} / {float(bins.mean()):.1f} / {int(bins.max())} time bins "
+              f"(min / mean / max)")
     if trim:
         import torch
         trimmer = fr.SilenceTrimmer(device=fe.device, **trim)
         rows = torch.empty((len(clips), fe.n_samples), dtype=torch.float32, device=fe.device)
         kept = torch.empty((len(clips),), dtype=torch.int32, device=fe.device)
         for a in range(0, len(clips), ENCODE_BATCH):
-            _, part, _ = trimmer.trim(audio[a:a + ENCODE_BATCH], bins[a:a + ENCODE_BATCH].astype(np.int64) * fr.RAGGED_HOP,
-                                      time_bins=max_bins, out=rows[a:a + ENCODE_BATCH])
+            given = bins[a:a + ENCODE_BATCH].astype(np.int64) * fr.RAGGED_HOP if samples is None else samples[a:a + ENCODE_BATCH]
+            _, part, _ = trimmer.trim(audio[a:a + ENCODE_BATCH], given, time_bins=max_bins, out=rows[a:a + ENCODE_BATCH])
             kept[a:a + ENCODE_BATCH] = part
         audio, bins = rows, kept.cpu().numpy()          # the one read-back: the order below and n_steps need host values
         print(f"  Trimmed at {trim['top_db']:g} dB: {int(bins.min())} / {float(bins.mean()):.1f} / {int(bins.max())} time bins "
               f"(min / mean / max)")
-    from lsm_speech_classifier_amd.augment import AugmentChain, StepPlans
     plans, stages = {}, {}
     if augment:
         bank, plans["mix"] = corruption(augment, len(clips))
@@ -695,6 +719,10 @@ def add_variable_length_flags(ap):
     ap.add_argument("--augment-variable-length", action="store_true",
                     help="With --variable-length: let the corruption flags, --rir-dir and the mask flags through -- every clip is "
                          "reverberated, mixed and masked at its own (trimmed) length (SPEC.md 1.16).")
+    ap.add_argument("--speed-variable-length", action="store_true",
+                    help="With --variable-length --augment-variable-length: let --speed-factors / --speed-prob through -- every "
+                         "clip is first played at its speed, alone, and File 1's n_steps are the perturbed (then trimmed) "
+                         "lengths (SPEC.md 1.18).")
 
 
 DEFAULT_TRIM_PAD_MS = 30.0
@@ -720,12 +748,14 @@ def trim_from_args(a):
 
 def check_variable_length_args(a):
     """--variable-length is a route of its own: refuse the flags it does not take instead of ignoring them.  Only with
-    --augment-variable-length does it take the corruption flags, --rir-dir and the mask flags (SPEC.md 1.16)."""
+    --augment-variable-length does it take the corruption flags, --rir-dir and the mask flags (SPEC.md 1.16), and only with
+    --speed-variable-length beside that flag the speed flags (SPEC.md 1.18)."""
     max_bins_of(a.max_seconds)
     refused = not getattr(a, "augment_variable_length", False)      # the three flag groups of the augmentation chain
+    no_speed = refused or not getattr(a, "speed_variable_length", False)
     taken = [flag for flag, on in (("--packed", getattr(a, "packed", False)), ("--resample device", getattr(a, "resample", "host") == "device"),
                                    ("the corruption flags", refused and augment_from_args(a) is not None),
-                                   ("--rir-dir", refused and reverb_from_args(a) is not None), ("--speed-factors", a.speed_factors is not None),
+                                   ("--rir-dir", refused and reverb_from_args(a) is not None), ("--speed-factors", no_speed and a.speed_factors is not None),
                                    ("the mask flags", refused and mask_from_args(a) is not None)) if on]
     if taken:
         raise SystemExit(f"--variable-length does not combine with {', '.join(taken)}")
@@ -766,7 +796,9 @@ if __name__ == "__main__":
                                        dataset_root=a.dataset_root, max_per_class=a.max_per_class,
                                        synthetic_per_class=a.synthetic_per_class, max_seconds=a.max_seconds, trim=trim,
                                        **({"augment": augment_from_args(a), "reverb": reverb_from_args(a),
-                                           "mask": mask_from_args(a)} if a.augment_variable_length else {}))
+                                           "mask": mask_from_args(a)} if a.augment_variable_length else {}),
+                                       **({"speed": speed_from_args(a)}
+                                          if a.augment_variable_length and a.speed_variable_length else {}))
         raise SystemExit(0)
     create_dataset(n_filters=a.n_filters, filterbank=a.filterbank, commands=commands_from_args(a),
                    dataset_root=a.dataset_root, max_per_class=a.max_per_class,

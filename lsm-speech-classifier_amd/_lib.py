@@ -260,6 +260,15 @@ ENDPOINT_SIGS = {
 }
 ENDPOINT_SYMBOLS = tuple(ENDPOINT_SIGS)
 
+# include/lsm_hip_ragged_speed.h (SPEC.md §1.18): speed perturbation on ragged batches -- lsm_speed_f32's list with the DEVICE
+# clip_samples behind n_in and clip_samples_out, clip_bins_out, time_bins in front of the stream; the length formula, host only
+RAGGED_SPEED_SIGS = {
+    "lsm_speed_ragged_length": (c_int, [c_int, c_int, c_int, c_int]),
+    "lsm_speed_ragged_f32": (c_int, SPEED_SIGS["lsm_speed_f32"][1][:4] + [c_void] + SPEED_SIGS["lsm_speed_f32"][1][4:-1]
+                             + [c_void, c_void, c_int] + SPEED_SIGS["lsm_speed_f32"][1][-1:]),
+}
+RAGGED_SPEED_SYMBOLS = tuple(RAGGED_SPEED_SIGS)
+
 
 class LsmHipError(RuntimeError):
     pass
@@ -312,7 +321,8 @@ def load():
                               + list(MIX_SIGS.items()) + list(REVERB_SIGS.items()) + list(SPEED_SIGS.items())
                               + list(MASK_SIGS.items()) + list(RAGGED_SIGS.items()) + list(STEP_SIGS.items())
                               + list(STEP_STATE_SIGS.items()) + list(TRIM_SIGS.items()) + list(RAGGED_AUGMENT_SIGS.items())
-                              + list(READOUT_SIGS.items()) + list(FIT_SIGS.items()) + list(ENDPOINT_SIGS.items())):
+                              + list(READOUT_SIGS.items()) + list(FIT_SIGS.items()) + list(ENDPOINT_SIGS.items())
+                              + list(RAGGED_SPEED_SIGS.items())):
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = res
         fn.argtypes = args

@@ -80,12 +80,25 @@ class AugmentChain:
             x = self.mixer.mix(x, m.snr_db, m.rows, m.offsets, m.shift, m.scale, out=out("mix"))
         return x
 
+    def speed_ragged(self, x, lengths, plans: StepPlans, time_bins: int | None = None, out=None):
+        """The recipe's first stage on a ragged batch (SPEC.md §1.18), ahead of `apply_ragged`: ``x`` (B, n_samples) rows
+        at one stride, clip b their first ``lengths[b]`` samples, played at the speeds of ``plans.speed`` -> ``(x, samples,
+        bins)`` as `frontend.SpeedPerturber.perturb_ragged` returns them: rows of the same stride, every clip at its new
+        length with +0.0 behind, and the new lengths in samples and in time bins as int32 device tensors (``time_bins``:
+        the bins of a row, n_samples // 160 by default; ``out``: a caller-owned output buffer of ``x``'s shape).  A stage
+        of its own because it changes the lengths that every later stage takes; `apply_ragged` then runs with ``plans``
+        less its speed plan.  Without a speed plan nothing is launched and ``(x, None, None)`` comes back."""
+        self.refuse(plans)
+        if plans.speed is None:
+            return x, None, None
+        return self.speed.perturb_ragged(x, lengths, plans.speed.choice, time_bins=time_bins, out=out)
+
     def apply_ragged(self, x, lengths, plans: StepPlans):
         """`apply` for a ragged batch (SPEC.md §1.16): ``x`` (B, n_samples) rows at one stride, clip b their first
         ``lengths[b]`` samples.  Reverberation runs at the row stride -- it is causal, so a clip's own samples are those of
         the clip alone, and its tail behind the clip is ignored by what follows -- then the ragged mixer takes every clip at
-        its own length.  Speed perturbation changes a clip's length and is not offered.  Without a plan nothing is launched
-        and ``x`` comes back as it is."""
+        its own length.  Speed perturbation changes a clip's length and is not offered here: it is `speed_ragged`, ahead of
+        this call.  Without a plan nothing is launched and ``x`` comes back as it is."""
         self.refuse(plans)
         if plans.speed is not None:
             raise ValueError("speed perturbation is not offered on ragged batches: a speed factor changes a clip's bin count")

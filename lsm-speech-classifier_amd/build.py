@@ -23,6 +23,8 @@ PUBLIC_HEADERS = ["lsm_hip.h", "lsm_hip_streams.h", "lsm_hip_audio.h", "lsm_hip_
 # augmentation (1.16), device readout (6), streaming ridge fit (7), stream endpointing (1.17)
 ABI_HEADERS = ["lsm_hip_mask.h", "lsm_hip_ragged.h", "lsm_hip_step.h", "lsm_hip_step_state.h", "lsm_hip_trim.h",
                "lsm_hip_ragged_augment.h", "lsm_hip_readout.h", "lsm_hip_fit.h", "lsm_hip_endpoint.h"]
+# include/: speed perturbation on ragged batches (SPEC.md 1.18), hashed like the lists above, which keep their sizes
+RAGGED_SPEED_HEADERS = ["lsm_hip_ragged_speed.h"]
 LIB_NAME = "liblsm_hip.so"
 # -ffp-contract=off: the kernels must round every float operation exactly like the CPU oracle.
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
@@ -57,7 +59,8 @@ def source_id(include_dir: str | None = None) -> str:
     h = hashlib.sha256()
     include_dir = include_dir or os.path.join(ROOT, "include")
     files = sorted(os.path.join(PKG_DIR, "csrc", f) for f in SOURCES + HEADERS) + [os.path.join(include_dir, f)
-                                                                                  for f in PUBLIC_HEADERS + ABI_HEADERS]
+                                                                                  for f in PUBLIC_HEADERS + ABI_HEADERS
+                                                                                  + RAGGED_SPEED_HEADERS]
     for path in files:
         h.update(os.path.basename(path).encode() + b"\0")
         with open(path, "rb") as f:

@@ -24,6 +24,13 @@ __host__ __device__ inline int row_stride(int n_taps, int up) { return phase_tap
 __host__ __device__ inline long table_bytes(int n_taps, int up) { return (long)up * row_stride(n_taps, up) * 8; }
 // Hs = (K - 1) / up input samples of history: the reach of the longest row behind i0
 __host__ __device__ inline int history_samples(int n_taps, int up) { return (n_taps - 1) / up; }
+// Samples of a clip of n (>= 0) on a design (up, down) in a row of n_out (SPEC.md §1.18): min(ceil(n * up / down), n_out).
+// One copy for the ragged speed kernel and for the host export that tells Python the same integer.
+__host__ __device__ inline int ragged_length(int n, int up, int down, int n_out)
+{
+    const long long whole = ((long long)n * up + down - 1) / down;
+    return whole < n_out ? (int)whole : n_out;
+}
 
 // hp (n_taps doubles, global memory, natural order) -> tab[k % up][k / up], by the whole workgroup; ends with a barrier
 __device__ __forceinline__ void load_table(double *tab, const double *__restrict__ taps, int n_taps, int up)

@@ -1733,6 +1733,87 @@ class SpeedPerturber:
                     stream), "lsm_speed_f32")
         return out
 
+    def perturb_ragged(self, audio, lengths, choice=None, n_out: int | None = None, time_bins: int | None = None,
+                       out: torch.Tensor | None = None):
+        """`perturb` on rows of one stride whose clips have their own lengths (`lsm_speed_ragged_f32`, SPEC.md §1.18):
+        ``audio`` (n, L) float32 or int16, clip b its first ``lengths[b]`` samples -- n host integers in [0, L] (checked) or
+        an int32 device tensor (not read: the kernel clamps it).  -> ``(rows, samples, bins)``, device tensors produced on
+        the current stream with no host synchronisation: ``rows`` float32 (n, n_out) -- ``out`` where given -- holds clip b
+        played at ``factors[choice[b]]`` as the clip alone, ``samples[b]`` = min(ceil(lengths[b] * up / down), n_out) samples
+        of it (`speed_ragged_lengths` gives the same integers on the host) and +0.0 behind: no ring-out tail, and a slowed
+        clip that outgrows the row is cut; ``samples`` and ``bins`` = min(ceil(samples / 160), time_bins) are int32 (n,),
+        what `NoiseMixer.mix_ragged`, `SilenceTrimmer.trim` and `SpikeFrontEnd.encode_ragged`, `pipeline.step_fused_ragged`,
+        `SNN.run_batch(lengths=...)` take unread.  ``n_out`` defaults to L, ``time_bins`` (>= 3, with
+        160 * time_bins <= n_out) to n_out // 160."""
+        audio, fmt = checked_pcm(audio)
+        n, L = (int(v) for v in audio.shape)
+        n_out = L if n_out is None else int(n_out)
+        if n_out < 1:
+            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        time_bins = n_out // RAGGED_HOP if time_bins is None else int(time_bins)
+        if time_bins < RAGGED_MIN_BINS or RAGGED_HOP * time_bins > n_out:
+            raise ValueError(f"time_bins = {time_bins}: a row of n_out = {n_out} samples holds {RAGGED_MIN_BINS} .. "
+                             f"{n_out // RAGGED_HOP} time bins of {RAGGED_HOP}")
+        rows = self.rows_of(choice, n)
+        if torch.is_tensor(lengths) and lengths.is_cuda:
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
+                raise ValueError(f"lengths must hold {n} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
+        else:
+            arr = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+            if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
+                raise ValueError(f"lengths must be {n} integers, got {arr.dtype} {arr.shape}")
+            bad = np.nonzero((arr < 0) | (arr > L))[0]
+            if len(bad):
+                raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {L}]")
+            lengths = torch.from_numpy(arr.astype(np.int32))
+        if out is not None:
+            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) \
+                    or not out.is_contiguous() or out.device != self.device:
+                raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
+            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
+                raise ValueError("out must not be audio: an output reads the samples around it")
+        with torch.cuda.device(self.device):
+            audio = audio.to(self.device)
+            lengths = lengths.to(self.device, non_blocking=True).contiguous()
+            if out is None:
+                out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
+            samples = torch.empty((n,), dtype=torch.int32, device=self.device)
+            bins = torch.empty((n,), dtype=torch.int32, device=self.device)
+            rows_dev = None if rows is None else torch.from_numpy(rows).to(self.device, non_blocking=True)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            for r0 in range(0, n, SPEED_MAX_ROWS):
+                k = min(SPEED_MAX_ROWS, n - r0)
+                _lib.check(self.lib.lsm_speed_ragged_f32(
+                    _dev(audio[r0:]), fmt, k, L, _dev(lengths[r0:]), _dev(self.taps_dev), self.n_taps_total,
+                    _host(self.designs), len(self.designs), _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out,
+                    _dev(out[r0:]), _dev(samples[r0:]), _dev(bins[r0:]), time_bins, stream), "lsm_speed_ragged_f32")
+        return out, samples, bins
+
+
+def speed_ragged_lengths(lengths, choice, perturber, n_out: int) -> np.ndarray:
+    """The sample counts `SpeedPerturber.perturb_ragged` writes, computed on the host (`lsm_speed_ragged_length`, the one
+    function the kernel calls): ``lengths`` n host integers (below 0 counts as 0), ``choice`` as `SpeedPerturber.rows_of`
+    takes it, ``perturber`` the `SpeedPerturber` (only its designs are read), ``n_out`` the samples of an output row ->
+    int64 (n,): min(ceil(lengths * up / down), n_out), up = down = 1 for an unperturbed clip."""
+    arr = np.asarray(lengths)
+    if arr.ndim != 1 or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"lengths must be a 1-D sequence of integers, got {arr.dtype} {arr.shape}")
+    if len(arr) and (arr.max() > np.iinfo(np.int32).max or arr.min() < np.iinfo(np.int32).min):
+        raise ValueError("lengths must fit int32")
+    n_out = int(n_out)
+    if not 0 <= n_out <= np.iinfo(np.int32).max:
+        raise ValueError(f"n_out must lie in [0, 2^31), got {n_out}")
+    rows = perturber.rows_of(choice, len(arr))
+    rows = np.zeros(len(arr), dtype=np.int32) if rows is None else rows
+    lib = _lib.load()
+    new = np.empty(len(arr), dtype=np.int64)
+    for b, (n_b, r) in enumerate(zip(arr.tolist(), rows.tolist())):
+        up, down = (1, 1) if r < 0 else (int(v) for v in perturber.designs[min(r, len(perturber.designs) - 1), :2])
+        new[b] = lib.lsm_speed_ragged_length(int(n_b), up, down, n_out)
+        if new[b] < 0:
+            _lib.check(int(new[b]), "lsm_speed_ragged_length")
+    return new
+
 
 # ---- silence trimming in front of the ragged front end (SPEC.md §1.15, include/lsm_hip_trim.h) ---------------------------
 TRIM_MAX_BINS = 4096        # time_bins of a trim launch: 3 .. 4096

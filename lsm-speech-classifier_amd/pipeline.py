@@ -897,23 +897,50 @@ def features_from_recordings(recordings, fe, net, feature_keys):
         return feats
 
 
-def _trimmed_listing(trim, audio: np.ndarray, bins: np.ndarray, fe, device, batch: int):
+def _trimmed_listing(trim, audio, bins: np.ndarray, fe, device, batch: int, lengths=None):
     """A packed listing (`frontend.pack_utterances`) through ``trim`` in batches of ``batch`` rows: -> ``(the trimmed rows, a
-    float32 (n, 160 * time_bins) DEVICE tensor, their bins as host int32)``.  Launches only, then one read-back of the bins."""
+    float32 (n, 160 * time_bins) DEVICE tensor, their bins as host int32)``.  Launches only, then one read-back of the bins.
+    ``audio`` may be a device tensor (the perturbed listing) and ``lengths`` the int32 device tensor of its clips' samples;
+    None: 160 * bins from the host."""
     from .frontend import RAGGED_HOP
     n = len(bins)
     rows = torch.empty((n, RAGGED_HOP * fe.time_bins), dtype=torch.float32, device=device)
     kept = torch.empty((n,), dtype=torch.int32, device=device)
     for lo in range(0, n, batch):
         hi = min(n, lo + batch)
-        _, part, _ = trim.trim(torch.from_numpy(audio[lo:hi]).to(device), bins[lo:hi].astype(np.int64) * RAGGED_HOP,
+        x = audio[lo:hi] if torch.is_tensor(audio) else torch.from_numpy(audio[lo:hi]).to(device)
+        _, part, _ = trim.trim(x, bins[lo:hi].astype(np.int64) * RAGGED_HOP if lengths is None else lengths[lo:hi],
                                time_bins=fe.time_bins, out=rows[lo:hi])
         kept[lo:hi] = part
     return rows, kept.cpu().numpy()
 
 
+def _perturbed_listing(chain, speeds, audio: np.ndarray, bins: np.ndarray, fe, device, batch: int):
+    """A packed listing through the speed stage (`AugmentChain.speed_ragged`, SPEC.md §1.18) in batches of ``batch`` rows, every
+    utterance at ``160 * bins`` samples: -> ``(the perturbed rows, a float32 (n, 160 * time_bins) DEVICE tensor, their samples
+    as an int32 DEVICE tensor, their bins as host int32)``.  Launches only: the host bins come from the length formula
+    (`frontend.speed_ragged_lengths`), which also refuses, before any launch, an utterance that a speed leaves under 3 bins."""
+    from .frontend import RAGGED_HOP, RAGGED_MIN_BINS, speed_ragged_lengths
+    n, n_out = len(bins), RAGGED_HOP * fe.time_bins
+    lengths = bins.astype(np.int64) * RAGGED_HOP
+    new_bins = -(-speed_ragged_lengths(lengths, speeds.choice, chain.speed, n_out) // RAGGED_HOP)
+    short = np.nonzero(new_bins < RAGGED_MIN_BINS)[0]
+    if len(short):
+        r = int(short[0])
+        raise ValueError(f"utterance {r} has {int(bins[r])} time bins and {int(new_bins[r])} at its speed "
+                         f"(choice {int(speeds.choice[r])}): a clip needs {RAGGED_MIN_BINS}")
+    rows = torch.empty((n, n_out), dtype=torch.float32, device=device)
+    samples = torch.empty((n,), dtype=torch.int32, device=device)
+    for lo in range(0, n, batch):
+        hi = min(n, lo + batch)
+        _, part, _ = chain.speed_ragged(torch.from_numpy(audio[lo:hi]).to(device), lengths[lo:hi],
+                                        StepPlans(speed=speeds.part(lo, hi)), time_bins=fe.time_bins, out=rows[lo:hi])
+        samples[lo:hi] = part
+    return rows, samples, new_bins.astype(np.int32)
+
+
 def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 1024, fused: bool = False, trim=None,
-                             corrupt=None, reverb=None, mask=None):
+                             corrupt=None, reverb=None, mask=None, speed=None):
     """Utterances of different lengths, each one clip: ``utterances``, a list of n 1-D float32 arrays of 321 to
     ``fe.n_samples`` samples, -> (n, n_feat) float32 device tensor in the input order.  Row r holds the features of utterance
     r taken alone: its own ``ceil(len / 160)`` time bins through the front end of that length (its normalisation range is the
@@ -937,20 +964,36 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     ones, its tail is ignored), the ragged mixer at the clip's (trimmed) length -- the SNR is taken against the speech, and
     the noise does not decide the trim -- then the ragged front end with the mask.  Row r is the row of that chain on
     utterance r alone.  With ``fused`` a masked batch takes `step_fused_ragged(mask=...)` where
-    `step_fused_supported(..., form="ragged-masked")` says so.  All three None: nothing changes."""
+    `step_fused_supported(..., form="ragged-masked")` says so.  All three None: nothing changes.
+    ``speed`` = ``(frontend.SpeedPerturber, frontend.SpeedPlan of the n utterances)``: every utterance is first played at its
+    speed, as the clip alone (SPEC.md §1.18) -- the recipe's first stage, because everything behind it sees the recording as
+    played: speed, trim, reverberation, ragged mixer, ragged front end with the mask.  The packed listing is perturbed in
+    batches of ``batch`` at ``160 * bins`` samples per utterance, launches only; an utterance's new bins,
+    ``ceil(min(ceil(160 * bins * up / down), fe.n_samples) / 160)`` -- a slowed utterance is cut at the row -- are known on the
+    host from the formula (`frontend.speed_ragged_lengths`), so the longest-first order costs no read-back, and an utterance
+    that its speed leaves under 3 bins is refused with its index before anything is launched.  With ``trim`` the trimmer takes
+    the device lengths the speed launch wrote, and the one read-back of the trimmed bins stays the only one.  ``mask`` as a
+    callable is called with the final bins; a ready `MaskPlan` drawn for the bins before the speed stage has its time bands
+    placed against those old lengths (bits at or behind a clip's new end are ignored, §1.16).  Row r is the row of the whole
+    chain on utterance r alone.  None: not one launch changes."""
     from .frontend import RAGGED_HOP, pack_utterances
     from .snn import _select_keys
-    (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (reverb, corrupt))
+    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
     audio, bins = pack_utterances(utterances, fe.time_bins)
     n = len(bins)
     keys, _ = _select_keys(feature_keys)
     batch = max(1, int(batch))
+    chain = AugmentChain(speed=sp, reverb=rv, mixer=mixer)
     with torch.cuda.device(net.device):
+        samples = None
+        if speeds is not None:
+            chain.refuse(StepPlans(speed=speeds))
+            StepPlans(speed=speeds).check_covers(n)
+            audio, samples, bins = _perturbed_listing(chain, speeds, audio, bins, fe, net.device, batch)
         if trim is not None:
-            audio, bins = _trimmed_listing(trim, audio, bins, fe, net.device, batch)
+            audio, bins = _trimmed_listing(trim, audio, bins, fe, net.device, batch, samples)
         plans = StepPlans(None, reverbs, mixes, mask(bins) if callable(mask) else mask)
         plans.check_covers(n)
-        chain = AugmentChain(reverb=rv, mixer=mixer)
         feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
         order = np.argsort(-bins.astype(np.int64), kind="stable")
         n_thr = len(fe.thresholds)

@@ -68,12 +68,15 @@ def _mask_args(a):
 
 
 def _variable_length_args(a):
-    """Nothing without --variable-length; the trim flags go along with --trim-silence, --augment-variable-length where given."""
+    """Nothing without --variable-length; the trim flags go along with --trim-silence, --augment-variable-length and
+    --speed-variable-length where given."""
     if not a.variable_length:
         return []
     out = ["--variable-length", "--max-seconds", str(a.max_seconds)]
     if getattr(a, "augment_variable_length", False):
         out += ["--augment-variable-length"]
+    if getattr(a, "speed_variable_length", False):
+        out += ["--speed-variable-length"]
     if a.trim_silence is not None:
         out += ["--trim-silence", str(a.trim_silence), "--trim-pad-ms", str(a.trim_pad_ms), "--trim-min-ms", str(a.trim_min_ms)]
     return out
@@ -156,7 +159,8 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     mask_prob: applied to stage 1 and to the in-memory route; variable_length, max_seconds: stage 1 keeps every clip at its
     own length, SPEC.md 1.14, and stage 2 finds the lengths in File 1; trim_silence, trim_pad_ms, trim_min_ms: stage 1 first
     cuts every such clip to its speech on the GPU, SPEC.md 1.15; augment_variable_length: stage 1 lets the corruption, the
-    reverberation and the mask flags through on such clips, SPEC.md 1.16; save_model: a path -- stage 2 writes the front half
+    reverberation and the mask flags through on such clips, SPEC.md 1.16; speed_variable_length: beside it, stage 1 lets the
+    speed flags through on such clips, SPEC.md 1.18; save_model: a path -- stage 2 writes the front half
     of the model file there and stage 3 adds its readout, or the in-memory route with a PyTorch readout writes it whole,
     SPEC.md 6; classify.py labels new audio with it; readout="stream-ridge" with augment_epochs, ridge_alpha: the in-memory
     route trains a ridge readout from statistics updated on the GPU, SPEC.md 7, and keeps no training row)."""
@@ -169,7 +173,7 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
                               speed_factors=None, speed_prob=1.0, freq_masks=0, freq_mask_width=0, time_masks=0,
                               time_mask_width=0, mask_prob=1.0, variable_length=False, max_seconds=1.0,
                               trim_silence=None, trim_pad_ms=30.0, trim_min_ms=30.0, augment_variable_length=False,
-                              save_model=None, augment_epochs=None, ridge_alpha=None)
+                              speed_variable_length=False, save_model=None, augment_epochs=None, ridge_alpha=None)
     unknown = set(extra) - set(vars(args))
     if unknown:
         raise TypeError(f"run_pipeline: unknown arguments {sorted(unknown)}")
@@ -197,7 +201,7 @@ def run_pipeline(n_filters: int, filterbank: str, feature_set: str, multiplier: 
     print("--- Running Pipeline ---")
     if in_memory:
         print("\n--- Steps 1+2: audio -> LSM features on the GPU (no dataset file) ---", flush=True)
-        ns = {k: v for k, v in vars(args).items() if k not in ("readout", "nproc", "packed")}
+        ns = {k: v for k, v in vars(args).items() if k not in ("readout", "nproc", "packed", "speed_variable_length")}
         # a PyTorch readout on the in-memory route runs where the features already are: scaler, readout and
         # predictions on the GPU, no File 2 reload; File 2 is still written
         device_readout = args.readout if args.readout in ("torch-ridge", "torch-logistic", "stream-ridge") else None
@@ -288,6 +292,8 @@ if __name__ == "__main__":
     ap.add_argument("--trim-min-ms", type=float, default=30.0, help="With --trim-silence: shortest trimmed clip (stage 1).")
     ap.add_argument("--augment-variable-length", action="store_true",
                     help="With --variable-length: let the corruption flags, --rir-dir and the mask flags through (stage 1).")
+    ap.add_argument("--speed-variable-length", action="store_true",
+                    help="With --variable-length --augment-variable-length: let the speed flags through (stage 1).")
     ap.add_argument("--save-model", type=str, default=None, metavar="PATH",
                     help="Save the trained model (scaler, readout, front-end and reservoir parameters) for classify.py "
                          "(stages 2 and 3).")
@@ -304,4 +310,4 @@ if __name__ == "__main__":
                  time_masks=a.time_masks, time_mask_width=a.time_mask_width, mask_prob=a.mask_prob,
                  variable_length=a.variable_length, max_seconds=a.max_seconds, trim_silence=a.trim_silence,
                  trim_pad_ms=a.trim_pad_ms, trim_min_ms=a.trim_min_ms, augment_variable_length=a.augment_variable_length,
-                 save_model=a.save_model, augment_epochs=a.augment_epochs, ridge_alpha=a.ridge_alpha)
+                 speed_variable_length=a.speed_variable_length, save_model=a.save_model, augment_epochs=a.augment_epochs, ridge_alpha=a.ridge_alpha)
