@@ -107,12 +107,21 @@ def _stream(device=None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def _dev(t: torch.Tensor) -> C.c_void_p:
-    return C.c_void_p(t.data_ptr())
+def _dev(t, row: int = 0):
+    """The pointer a kernel gets for tensor ``t`` from its row ``row`` on; None (an argument the call leaves out) stays None.
+    The package's one definition, with `_host`."""
+    if t is None:
+        return None
+    return C.c_void_p((t[row:] if row else t).data_ptr())
 
 
 def _host(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
+
+
+def _up(a, device):
+    """A per-clip host array as a tensor on ``device``, copied on the current stream without waiting; None stays None."""
+    return None if a is None else torch.from_numpy(a).to(device, non_blocking=True)
 
 
 def indexed_device(device=None) -> torch.device:
@@ -120,6 +129,70 @@ def indexed_device(device=None) -> torch.device:
     and means whatever device is current when it is used."""
     d = torch.device(device if device is not None else "cuda")
     return d if d.index is not None or d.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
+
+
+# ---- what a stage's host side is made of (DESIGN.md §1, "What a batch stage's host side does") ----------------------------
+def _open(device=None):
+    """How a stage's constructor opens, once its own arguments are checked: ``(lib, device)`` -- a GPU required first, then
+    the library loaded, then the device pinned with its index NOW: later calls may come under another current device."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    return lib, indexed_device(device)
+
+
+def checked_out(out, shape, device=None, audio=None, reason=None, *, at_least: bool = False, name: str = "out",
+                dtype=torch.float32, word=None):
+    """A caller-owned output checked and returned: a contiguous ``dtype`` tensor (the refusal says "float32" for torch.float32;
+    ``word``: another spelling, which some stream outputs have always had) of ``shape`` -- with ``at_least`` of ``shape[0]``
+    rows of ``shape[1]`` columns or more -- on ``device`` (None: any device, for a check made before a device is touched).
+    ``reason``: why the stage cannot write over its input -- ``out`` is then refused where it is ``audio`` or starts where
+    ``audio`` starts; None: the stage may.  Host code only."""
+    shape = tuple(shape)
+    if at_least:
+        fits = torch.is_tensor(out) and out.ndim == 2 and out.shape[0] == shape[0] and out.shape[1] >= shape[1]
+    else:
+        fits = torch.is_tensor(out) and tuple(out.shape) == shape
+    if not fits or out.dtype != dtype or not out.is_contiguous() or (device is not None and out.device != device):
+        want = f"({shape[0]}, >= {shape[1]})" if at_least else f"{shape}"
+        word = word or str(dtype).replace("torch.", "")
+        raise ValueError(f"{name} must be a contiguous {word} {want} tensor" + ("" if device is None else f" on {device}"))
+    if reason is not None and (out is audio or (shape[0] and out.data_ptr() == audio.data_ptr())):
+        raise ValueError(f"{name} must not be audio: {reason}")
+    return out
+
+
+def checked_lengths(lengths, n: int, limit: int, device):
+    """The valid samples of ``n`` clips as the int32 tensor on ``device`` that a kernel reads.  A device tensor is taken as it
+    is -- int32 (n,), never read back: the kernel clamps it.  Host integers (a sequence, an array, a CPU tensor) are checked
+    against ``[0, limit]`` with the offenders named and uploaded without waiting.  ``device`` None: checked only, for a caller
+    that uploads later (host integers come back as a CPU tensor).  (`NoiseMixer.mix_ragged` keeps a conversion of its own.)"""
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
+            raise ValueError(f"lengths must hold {n} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
+        return lengths if device is None else lengths.to(device).contiguous()
+    arr = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+    if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"lengths must be {n} integers, got {arr.dtype} {arr.shape}")
+    bad = np.nonzero((arr < 0) | (arr > limit))[0]
+    if len(bad):
+        raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {limit}]")
+    host = torch.from_numpy(arr.astype(np.int32))
+    return host if device is None else host.to(device, non_blocking=True)
+
+
+def checked_n_out(n_out, default: int) -> int:
+    """The samples of an output row: ``n_out``, or ``default`` for None; at least 1."""
+    n_out = int(default) if n_out is None else int(n_out)
+    if n_out < 1:
+        raise ValueError(f"n_out must be >= 1, got {n_out}")
+    return n_out
+
+
+def row_chunks(n: int, limit: int):
+    """``(r0, k)`` of the launches a batch of ``n`` rows is cut into, ``limit`` rows at the most each: rows ``r0 .. r0 + k - 1``,
+    in order, none empty (a launch's row count is a grid dimension)."""
+    for r0 in range(0, n, limit):
+        yield r0, min(limit, n - r0)
 
 
 def as_float32(audio) -> torch.Tensor:
@@ -154,9 +227,7 @@ class SpikeFrontEnd:
             raise ValueError("the gammatone branch needs n_filters >= 2: with a single channel the reference's window sums "
                              "take NumPy's pairwise order, which the GPU filterbank does not restate (SPEC.md 1.1); use "
                              "--filterbank mel for one filter")
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)        # pin the device NOW: later calls may come under another current device
+        self.lib, self.device = _open(device)
         self.n_filters = int(n_filters)
         self.filterbank = filterbank
         self.redundancy = int(redundancy)
@@ -188,7 +259,7 @@ class SpikeFrontEnd:
 
     def _stream(self) -> int:
         """The current stream of THIS front end's device (not of whatever device is current)."""
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return _stream(self.device)
 
     def workspace_elems(self, n_clips: int) -> int:
         """float64 elements of the fused launch's scratch for a batch of `n_clips` (0 for the mel branch)."""
@@ -264,9 +335,8 @@ class SpikeFrontEnd:
             db = torch.empty((B, self.n_filters, self.ncols), dtype=torch.float64, device=self.device)
             spec = torch.empty_like(db) if want_spec else None
             _lib.check(self.lib.lsm_gammatone_spec_f64(
-                _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
-                self.ncols, _dev(spec) if want_spec else None, _dev(db), self.coef_flags, self._stream()),
-                "lsm_gammatone_spec_f64")
+                _dev(audio), B, self.n_samples, _dev(self.coefs), self.n_filters, self.nwin, self.hop, self.ncols, _dev(spec),
+                _dev(db), self.coef_flags, self._stream()), "lsm_gammatone_spec_f64")
         return db, spec
 
     def spikes_from_db(self, db: torch.Tensor, want_norm: bool = False, want_raster: bool = True, mask=None):
@@ -287,7 +357,7 @@ class SpikeFrontEnd:
                     if want_norm else None)
             args = (_dev(db), B, self.n_filters, db.shape[2], self.time_bins,
                     1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on),
-                    self.redundancy, _dev(raster) if want_raster else None, _dev(norm) if want_norm else None)
+                    self.redundancy, _dev(raster), _dev(norm))
             if mask is None:
                 fn = self.lib.lsm_spec_to_spikes_f64 if f64 else self.lib.lsm_spec_to_spikes_f32
                 _lib.check(fn(*args, self._stream()), "lsm_spec_to_spikes")
@@ -390,7 +460,7 @@ class SpikeFrontEnd:
                     if want_norm else None)
             args = (_dev(db), B, self.n_filters, db.shape[2], self.time_bins, _dev(cols), _dev(bins),
                     1 if self.filterbank == "gammatone" else 0, _host(on), _host(off), len(on), self.redundancy,
-                    _dev(raster) if raster is not None else None, _dev(norm) if want_norm else None)
+                    _dev(raster), _dev(norm))
             if mask is None:
                 fn = self.lib.lsm_spec_to_spikes_ragged_f64 if f64 else self.lib.lsm_spec_to_spikes_ragged_f32
                 _lib.check(fn(*args, self._stream()), "lsm_spec_to_spikes_ragged")
@@ -594,14 +664,12 @@ class _StreamPush:
     """What a push of any bank of streams needs: the check of a caller-owned output and the upload of its counts.  A
     subclass sets n_streams and device.  (`MixStream`, whose whole state is a noise position per stream, stops here.)"""
 
-    def _owned(self, t, shape, dtype, name, word=None):
-        """A caller-owned output checked, or zeros where the caller gave none (``word``: the dtype as the refusal says it)."""
+    def _owned(self, t, shape, dtype, name, word=None, audio=None, reason=None):
+        """A caller-owned output checked (`checked_out`), or zeros where the caller gave none.  (``word``: the dtype as the
+        refusal says it; the front-end streams, which give none, have always said "torch.uint8".)"""
         if t is None:
             return torch.zeros(shape, dtype=dtype, device=self.device)
-        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() \
-                or t.device != self.device:
-            raise ValueError(f"{name} must be a contiguous {word or dtype} {shape} tensor on {self.device}")
-        return t
+        return checked_out(t, shape, self.device, audio, reason, name=name, dtype=dtype, word=word or str(dtype))
 
     def _count_array(self, given, new):
         """A push's per-stream counts for the kernel: None where the caller gave none (every stream takes the whole row),
@@ -650,14 +718,7 @@ class _AudioStreamBase(_StreamBank):
         if audio.dim() != 2 or audio.shape[0] != self.n_streams or audio.shape[1] % self.hop or audio.shape[1] < self.hop:
             raise ValueError(f"audio must be ({self.n_streams}, H * {self.hop}) with H >= 1, got {tuple(audio.shape)}")
         H = int(audio.shape[1]) // self.hop
-        if hops is None:
-            new = np.full(self.n_streams, H, dtype=np.int64)
-        else:
-            new = np.asarray(hops)
-            if new.shape != (self.n_streams,) or new.dtype.kind not in "iu" or (new < 0).any() or (new > H).any():
-                raise ValueError(f"hops must be {self.n_streams} integers in [0, {H}], got {hops!r}")
-            new = new.astype(np.int64)
-        return audio, H, new
+        return audio, H, checked_counts(hops, self.n_streams, H, "hops")
 
 
 class GammatoneStream(_AudioStreamBase):
@@ -684,9 +745,7 @@ class GammatoneStream(_AudioStreamBase):
         self.thresholds = list(SPIKE_THRESHOLDS if thresholds is None else thresholds)
         self.gap = float(gap)
         self.on, self.off = threshold_tables(self.thresholds, self.gap, np.float64)
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         tab = gammatone_filter_table(SAMPLE_RATE, self.n_filters, GT_F_MIN)
         self.coefs = torch.from_numpy(tab).to(self.device)
         self.coef_flags = coef_flags(tab)
@@ -710,11 +769,9 @@ class GammatoneStream(_AudioStreamBase):
             spec = self._owned(spec_out, shape, torch.float64, "spec_out") if (want_spec or spec_out is not None) else None
             counts = self._count_array(hops, new)
             _lib.check(self.lib.lsm_gammatone_stream_f64(
-                _dev(audio), self.n_streams, H, _dev(self.coefs), self.n_filters, self.nwin, self.hop,
-                _dev(counts) if counts is not None else None, self.db_lo, self.db_hi, _host(self.on), _host(self.off),
-                self.n_thr, self.redundancy, _dev(self.state), _dev(self.state), _dev(raster),
-                _dev(spec) if spec is not None else None, _dev(db) if db is not None else None, self.coef_flags,
-                torch.cuda.current_stream(self.device).cuda_stream), "lsm_gammatone_stream_f64")
+                _dev(audio), self.n_streams, H, _dev(self.coefs), self.n_filters, self.nwin, self.hop, _dev(counts), self.db_lo,
+                self.db_hi, _host(self.on), _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state),
+                _dev(raster), _dev(spec), _dev(db), self.coef_flags, _stream(self.device)), "lsm_gammatone_stream_f64")
         self.seen += new
         if db is not None or spec is not None:
             return raster, cols, db, spec
@@ -779,9 +836,7 @@ class MelStream(_AudioStreamBase):
         self.thresholds = list(SPIKE_THRESHOLDS if thresholds is None else thresholds)
         self.gap = float(gap)
         self.on, self.off = threshold_tables(self.thresholds, self.gap, np.float32)
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         from . import mel as _mel
         self.window, self.twiddle, self.basis, self.lo, self.hi = _mel.device_tables(self.n_filters, self.device)
         self._new_state(self.lib.lsm_mel_stream_state_bytes(self.n_filters, MEL_N_FFT, self.hop))
@@ -812,11 +867,9 @@ class MelStream(_AudioStreamBase):
                 self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
             _lib.check(self.lib.lsm_mel_stream_f32(
                 _dev(audio), self.n_streams, H, MEL_N_FFT, self.hop, _dev(self.window), _dev(self.twiddle), _dev(self.basis),
-                _dev(self.lo), _dev(self.hi), self.n_filters, _dev(counts) if counts is not None else None, self.db_lo,
-                self.db_hi, _host(self.on), _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state),
-                _dev(raster), _dev(power) if power is not None else None, _dev(db) if db is not None else None,
-                _dev(self._ws), int(self._ws.numel()), torch.cuda.current_stream(self.device).cuda_stream),
-                "lsm_mel_stream_f32")
+                _dev(self.lo), _dev(self.hi), self.n_filters, _dev(counts), self.db_lo, self.db_hi, _host(self.on),
+                _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state), _dev(raster), _dev(power),
+                _dev(db), _dev(self._ws), int(self._ws.numel()), _stream(self.device)), "lsm_mel_stream_f32")
         self.seen += new
         if db is not None or power is not None:
             return raster, cols, db, power
@@ -858,9 +911,7 @@ class AdaptiveEncoder(_StreamBank):
         self.thresholds = list(SPIKE_THRESHOLDS if thresholds is None else thresholds)
         self.gap = float(gap)
         self.on, self.off = threshold_tables(self.thresholds, self.gap, _ADAPTIVE_DTYPES[self.dtype])
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         self._encode = self.lib.lsm_adaptive_encode_f64 if self.dtype == torch.float64 else self.lib.lsm_adaptive_encode_f32
         elem = 8 if self.dtype == torch.float64 else 4
         state_bytes = int(self.lib.lsm_adaptive_state_bytes(self.n_filters, self.window_cols, elem))
@@ -900,10 +951,9 @@ class AdaptiveEncoder(_StreamBank):
                 hi = torch.zeros((self.n_streams, H), dtype=self.dtype, device=self.device)
             counts = self._count_array(cols, new)
             _lib.check(self._encode(
-                _dev(db), self.n_streams, H, self.n_filters, _dev(counts) if counts is not None else None, self.window_cols,
-                _host(self.on), _host(self.off), self.n_thr, self.redundancy, _dev(self.state), _dev(self.state),
-                _dev(raster), _dev(lo) if lo is not None else None, _dev(hi) if hi is not None else None,
-                torch.cuda.current_stream(self.device).cuda_stream), "lsm_adaptive_encode")
+                _dev(db), self.n_streams, H, self.n_filters, _dev(counts), self.window_cols, _host(self.on), _host(self.off),
+                self.n_thr, self.redundancy, _dev(self.state), _dev(self.state), _dev(raster), _dev(lo), _dev(hi),
+                _stream(self.device)), "lsm_adaptive_encode")
         return (raster, lo, hi) if want_range else raster
 
 
@@ -1064,9 +1114,7 @@ class _ResampleBase:
                  else resample_table(self.rate_in, self.rate_out))
         self.up, self.down, self.taps, self.delay, self.history, _ = table
         self.table = table
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         self.taps_dev = torch.from_numpy(self.taps).to(self.device)
 
     def _as_float(self, audio: torch.Tensor) -> torch.Tensor:
@@ -1093,12 +1141,9 @@ class Resampler(_ResampleBase):
         zeros behind the clips.  ``out``: a caller-owned contiguous float32 (n, n_out) tensor on the device."""
         audio, fmt = checked_pcm(audio)
         n, L = (int(v) for v in audio.shape)
-        n_out = self.default_length(L) if n_out is None else int(n_out)
-        if n_out < 1:
-            raise ValueError(f"n_out must be >= 1, got {n_out}")
-        if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) or not out.is_contiguous()
-                                or out.device != self.device):
-            raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
+        n_out = checked_n_out(n_out, self.default_length(L))
+        if out is not None:
+            checked_out(out, (n, n_out), self.device)
         with torch.cuda.device(self.device):
             audio = audio.to(self.device)
             if out is None:
@@ -1107,12 +1152,11 @@ class Resampler(_ResampleBase):
                 out.zero_()
                 out[:, :min(L, n_out)] = self._as_float(audio[:, :n_out])
                 return out
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            for r0 in range(0, n, self.MAX_ROWS):
-                rows = min(self.MAX_ROWS, n - r0)
+            stream = _stream(self.device)
+            for r0, k in row_chunks(n, self.MAX_ROWS):
                 _lib.check(self.lib.lsm_resample_f32(
-                    _dev(audio[r0:]), fmt, rows, L, _dev(self.taps_dev), len(self.taps), self.up, self.down, self.delay,
-                    n_out, _dev(out[r0:]), stream), "lsm_resample_f32")
+                    _dev(audio, r0), fmt, k, L, _dev(self.taps_dev), len(self.taps), self.up, self.down, self.delay, n_out,
+                    _dev(out, r0), stream), "lsm_resample_f32")
         return out
 
 
@@ -1149,9 +1193,8 @@ class ResampleStream(_ResampleBase, _StreamBank):
                 return out, new * self.up
             counts = self._count_array(blocks, new)
             _lib.check(self.lib.lsm_resample_stream_f32(
-                _dev(audio), fmt, self.n_streams, G, _dev(self.taps_dev), len(self.taps), self.up, self.down,
-                _dev(counts) if counts is not None else None, _dev(self.state), _dev(self.state), _dev(out),
-                torch.cuda.current_stream(self.device).cuda_stream), "lsm_resample_stream_f32")
+                _dev(audio), fmt, self.n_streams, G, _dev(self.taps_dev), len(self.taps), self.up, self.down, _dev(counts),
+                _dev(self.state), _dev(self.state), _dev(out), _stream(self.device)), "lsm_resample_stream_f32")
         return out, new * self.up
 
 
@@ -1270,12 +1313,8 @@ def mix_arguments(audio, snr_db, rows=None, offsets=None, shift=None, scale=None
                          f"{tuple(audio.shape) if hasattr(audio, 'shape') else type(audio).__name__}")
     audio = audio.contiguous()
     n = int(audio.shape[0])
-    if out is not None:
-        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != tuple(audio.shape) \
-                or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 {tuple(audio.shape)} tensor")
-        if out is audio or (n and out.data_ptr() == audio.data_ptr()):
-            raise ValueError("out must not be audio: a shift reads across what it would write")
+    if out is not None:                 # its device is the mixer's to check (`NoiseMixer._mix`): nothing here knows one
+        checked_out(out, audio.shape, None, audio, "a shift reads across what it would write")
     return (audio, snr_ratio(snr_db, n), _per_clip(rows, n, np.int32, "rows"), _per_clip(offsets, n, np.int32, "offsets"),
             _per_clip(shift, n, np.int32, "shift"), _per_clip(scale, n, np.float32, "scale"))
 
@@ -1287,15 +1326,10 @@ class NoiseMixer:
 
     def __init__(self, noise_bank, device=None):
         bank = checked_noise_bank(noise_bank)
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         self.noise = bank.to(self.device)
         self.n_rows, self.noise_len = (int(v) for v in bank.shape)
         self._row_power = None
-
-    def _up(self, a):
-        return None if a is None else torch.from_numpy(a).to(self.device, non_blocking=True)
 
     def power(self, x) -> torch.Tensor:
         """``x`` (R, n) float32 -> the row powers P, float64 (R,) on the device."""
@@ -1306,7 +1340,7 @@ class NoiseMixer:
             x = x.to(self.device)
             out = torch.empty(int(x.shape[0]), dtype=torch.float64, device=self.device)
             _lib.check(self.lib.lsm_mix_power_f32(_dev(x), int(x.shape[0]), int(x.shape[1]), _dev(out),
-                                                  torch.cuda.current_stream(self.device).cuda_stream), "lsm_mix_power_f32")
+                                                  _stream(self.device)), "lsm_mix_power_f32")
         return out
 
     @property
@@ -1332,6 +1366,8 @@ class NoiseMixer:
         listing is taken as it is.  The SNR is that of the clip alone; what lies behind a clip influences nothing and comes
         back as +0.0.  Returns the float32 (n, L) tensor on the device (``out`` where given)."""
         n = len(x)
+        # not `checked_lengths`: any int32 tensor goes as it is, a host sequence (or one number for every clip) has no range to
+        # keep to -- the kernel clamps it -- and both keep the words they were always refused with
         if torch.is_tensor(lengths):
             if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
                 raise ValueError(f"lengths must be an int32 ({n},) tensor or {n} host integers")
@@ -1351,16 +1387,14 @@ class NoiseMixer:
                 out = torch.empty((n, L), dtype=torch.float32, device=self.device)
             gain = torch.empty(n, dtype=torch.float64, device=self.device) if want_gain else None
             powers = torch.empty((n, 2), dtype=torch.float64, device=self.device) if want_gain else None
-            args = [self._up(a) for a in (rows, offsets, shift, scale, ratio)]
+            args = [_up(a, self.device) for a in (rows, offsets, shift, scale, ratio)]
             if lengths is None:
                 fn, name, head = self.lib.lsm_mix_f32, "lsm_mix_f32", [_dev(audio), n, L]
             else:
                 lengths = lengths.to(self.device, non_blocking=True).contiguous()
                 fn, name, head = self.lib.lsm_mix_ragged_f32, "lsm_mix_ragged_f32", [_dev(audio), n, L, _dev(lengths)]
-            _lib.check(fn(*head, _dev(self.noise), self.n_rows, self.noise_len,
-                          *(_dev(a) if a is not None else None for a in args), _dev(out),
-                          _dev(gain) if want_gain else None, _dev(powers) if want_gain else None,
-                          torch.cuda.current_stream(self.device).cuda_stream), name)
+            _lib.check(fn(*head, _dev(self.noise), self.n_rows, self.noise_len, *(_dev(a) for a in args), _dev(out), _dev(gain),
+                          _dev(powers), _stream(self.device)), name)
         return (out, gain, powers) if want_gain else out
 
 
@@ -1432,9 +1466,8 @@ class MixStream(_StreamPush):
                 audio = audio.to(self.device)
             cnt = self._count_array(counts, new)
             _lib.check(mixer.lib.lsm_mix_stream_f32(
-                _dev(audio), self.n_streams, H, _dev(mixer.noise), mixer.n_rows, mixer.noise_len,
-                _dev(cnt) if cnt is not None else None, _dev(self.gain), _dev(self.scale), _dev(self.rows),
-                _dev(self.pos), _dev(self.pos), _dev(out), torch.cuda.current_stream(self.device).cuda_stream),
+                _dev(audio), self.n_streams, H, _dev(mixer.noise), mixer.n_rows, mixer.noise_len, _dev(cnt), _dev(self.gain),
+                _dev(self.scale), _dev(self.rows), _dev(self.pos), _dev(self.pos), _dev(out), _stream(self.device)),
                 "lsm_mix_stream_f32")
         return out, new
 
@@ -1442,6 +1475,7 @@ class MixStream(_StreamPush):
 # ---- reverberation (SPEC.md §1.11, include/lsm_hip_reverb.h) ------------------------------------------------------------
 REVERB_MAX_TAPS = 16384
 REVERB_MAX_ROWS = 65535                 # rows of one launch
+_REVERB_READS = "an output reads the samples in front of it"         # why ``out`` is never ``audio`` (`checked_out`)
 
 
 class ReverbPlan(NamedTuple):
@@ -1506,9 +1540,7 @@ class Reverberator:
 
     def __init__(self, rir_bank, lengths=None, device=None):
         bank, lengths = checked_rir_bank(rir_bank, lengths)
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         self.rir = bank.to(self.device)
         self.n_rows, self.n_taps = (int(v) for v in bank.shape)
         self.lengths = lengths
@@ -1521,28 +1553,20 @@ class Reverberator:
         float32 (n, n_out) tensor on the device, never ``audio``."""
         audio = _reverb_audio(audio)
         n, L = (int(v) for v in audio.shape)
-        n_out = L if n_out is None else int(n_out)
-        if n_out < 1:
-            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        n_out = checked_n_out(n_out, L)
         rows = _per_clip(rows, n, np.int32, "rows")
         if out is not None:
-            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) \
-                    or not out.is_contiguous() or out.device != self.device:
-                raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
-            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
-                raise ValueError("out must not be audio: an output reads the samples in front of it")
+            checked_out(out, (n, n_out), self.device, audio, _REVERB_READS)
         with torch.cuda.device(self.device):
             audio = audio.to(self.device)
             if out is None:
                 out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
-            rows_dev = None if rows is None else torch.from_numpy(rows).to(self.device, non_blocking=True)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            for r0 in range(0, n, REVERB_MAX_ROWS):
-                k = min(REVERB_MAX_ROWS, n - r0)
+            rows_dev = _up(rows, self.device)
+            stream = _stream(self.device)
+            for r0, k in row_chunks(n, REVERB_MAX_ROWS):
                 _lib.check(self.lib.lsm_reverb_f32(
-                    _dev(audio[r0:]), k, L, _dev(self.rir), self.n_rows, self.n_taps,
-                    _dev(self.lengths_dev) if self.lengths_dev is not None else None,
-                    _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out, _dev(out[r0:]), stream), "lsm_reverb_f32")
+                    _dev(audio, r0), k, L, _dev(self.rir), self.n_rows, self.n_taps, _dev(self.lengths_dev),
+                    _dev(rows_dev, r0), n_out, _dev(out, r0), stream), "lsm_reverb_f32")
         return out
 
 
@@ -1578,23 +1602,19 @@ class ReverbStream(_StreamBank):
         new = checked_counts(counts, self.n_streams, H, "counts")
         rv = self.reverberator
         with torch.cuda.device(self.device):
-            given = out is not None
-            out = self._owned(out, (self.n_streams, H), torch.float32, "out", "float32")
-            if given and (out is audio or out.data_ptr() == audio.data_ptr()):
-                raise ValueError("out must not be audio: an output reads the samples in front of it")
+            out = self._owned(out, (self.n_streams, H), torch.float32, "out", "float32", audio, _REVERB_READS)
             audio = audio.to(self.device)
             cnt = self._count_array(counts, new)
             _lib.check(rv.lib.lsm_reverb_stream_f32(
-                _dev(audio), self.n_streams, H, _dev(rv.rir), rv.n_rows, rv.n_taps,
-                _dev(rv.lengths_dev) if rv.lengths_dev is not None else None, _dev(self.rows),
-                _dev(cnt) if cnt is not None else None, _dev(self.state), _dev(self.state), _dev(out),
-                torch.cuda.current_stream(self.device).cuda_stream), "lsm_reverb_stream_f32")
+                _dev(audio), self.n_streams, H, _dev(rv.rir), rv.n_rows, rv.n_taps, _dev(rv.lengths_dev), _dev(self.rows),
+                _dev(cnt), _dev(self.state), _dev(self.state), _dev(out), _stream(self.device)), "lsm_reverb_stream_f32")
         return out, new
 
 
 # ---- speed perturbation (SPEC.md §1.12, include/lsm_hip_speed.h) --------------------------------------------------------
 SPEED_MAX_DESIGNS = 16
 SPEED_MAX_ROWS = 65535                  # rows of one launch
+_SPEED_READS = "an output reads the samples around it"              # why ``out`` is never ``audio`` (`checked_out`)
 
 
 def _speed_fraction(factor) -> Fraction:
@@ -1686,9 +1706,7 @@ class SpeedPerturber:
         self.designs = np.ascontiguousarray(
             [[t.up, t.down, len(t.taps), t.delay, int(o)] for t, o in zip(self.tables, offsets)], dtype=np.int32)
         self.n_taps_total = int(offsets[-1])
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         self.taps_dev = torch.from_numpy(np.concatenate([t.taps for t in self.tables])).to(self.device)
         self.lds_bytes = int(self.lib.lsm_speed_lds_bytes(_host(self.designs), len(self.designs)))
 
@@ -1709,28 +1727,20 @@ class SpeedPerturber:
         tensor on the device, never ``audio``."""
         audio, fmt = checked_pcm(audio)
         n, L = (int(v) for v in audio.shape)
-        n_out = L if n_out is None else int(n_out)
-        if n_out < 1:
-            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        n_out = checked_n_out(n_out, L)
         rows = self.rows_of(choice, n)
         if out is not None:
-            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) \
-                    or not out.is_contiguous() or out.device != self.device:
-                raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
-            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
-                raise ValueError("out must not be audio: an output reads the samples around it")
+            checked_out(out, (n, n_out), self.device, audio, _SPEED_READS)
         with torch.cuda.device(self.device):
             audio = audio.to(self.device)
             if out is None:
                 out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
-            rows_dev = None if rows is None else torch.from_numpy(rows).to(self.device, non_blocking=True)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            for r0 in range(0, n, SPEED_MAX_ROWS):
-                k = min(SPEED_MAX_ROWS, n - r0)
+            rows_dev = _up(rows, self.device)
+            stream = _stream(self.device)
+            for r0, k in row_chunks(n, SPEED_MAX_ROWS):
                 _lib.check(self.lib.lsm_speed_f32(
-                    _dev(audio[r0:]), fmt, k, L, _dev(self.taps_dev), self.n_taps_total, _host(self.designs),
-                    len(self.designs), _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out, _dev(out[r0:]),
-                    stream), "lsm_speed_f32")
+                    _dev(audio, r0), fmt, k, L, _dev(self.taps_dev), self.n_taps_total, _host(self.designs),
+                    len(self.designs), _dev(rows_dev, r0), n_out, _dev(out, r0), stream), "lsm_speed_f32")
         return out
 
     def perturb_ragged(self, audio, lengths, choice=None, n_out: int | None = None, time_bins: int | None = None,
@@ -1747,31 +1757,15 @@ class SpeedPerturber:
         160 * time_bins <= n_out) to n_out // 160."""
         audio, fmt = checked_pcm(audio)
         n, L = (int(v) for v in audio.shape)
-        n_out = L if n_out is None else int(n_out)
-        if n_out < 1:
-            raise ValueError(f"n_out must be >= 1, got {n_out}")
+        n_out = checked_n_out(n_out, L)
         time_bins = n_out // RAGGED_HOP if time_bins is None else int(time_bins)
         if time_bins < RAGGED_MIN_BINS or RAGGED_HOP * time_bins > n_out:
             raise ValueError(f"time_bins = {time_bins}: a row of n_out = {n_out} samples holds {RAGGED_MIN_BINS} .. "
                              f"{n_out // RAGGED_HOP} time bins of {RAGGED_HOP}")
         rows = self.rows_of(choice, n)
-        if torch.is_tensor(lengths) and lengths.is_cuda:
-            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
-                raise ValueError(f"lengths must hold {n} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
-        else:
-            arr = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
-            if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
-                raise ValueError(f"lengths must be {n} integers, got {arr.dtype} {arr.shape}")
-            bad = np.nonzero((arr < 0) | (arr > L))[0]
-            if len(bad):
-                raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {L}]")
-            lengths = torch.from_numpy(arr.astype(np.int32))
+        lengths = checked_lengths(lengths, n, L, None)          # refused here, uploaded below
         if out is not None:
-            if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, n_out) \
-                    or not out.is_contiguous() or out.device != self.device:
-                raise ValueError(f"out must be a contiguous float32 {(n, n_out)} tensor on {self.device}")
-            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
-                raise ValueError("out must not be audio: an output reads the samples around it")
+            checked_out(out, (n, n_out), self.device, audio, _SPEED_READS)
         with torch.cuda.device(self.device):
             audio = audio.to(self.device)
             lengths = lengths.to(self.device, non_blocking=True).contiguous()
@@ -1779,14 +1773,13 @@ class SpeedPerturber:
                 out = torch.empty((n, n_out), dtype=torch.float32, device=self.device)
             samples = torch.empty((n,), dtype=torch.int32, device=self.device)
             bins = torch.empty((n,), dtype=torch.int32, device=self.device)
-            rows_dev = None if rows is None else torch.from_numpy(rows).to(self.device, non_blocking=True)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            for r0 in range(0, n, SPEED_MAX_ROWS):
-                k = min(SPEED_MAX_ROWS, n - r0)
+            rows_dev = _up(rows, self.device)
+            stream = _stream(self.device)
+            for r0, k in row_chunks(n, SPEED_MAX_ROWS):
                 _lib.check(self.lib.lsm_speed_ragged_f32(
-                    _dev(audio[r0:]), fmt, k, L, _dev(lengths[r0:]), _dev(self.taps_dev), self.n_taps_total,
-                    _host(self.designs), len(self.designs), _dev(rows_dev[r0:]) if rows_dev is not None else None, n_out,
-                    _dev(out[r0:]), _dev(samples[r0:]), _dev(bins[r0:]), time_bins, stream), "lsm_speed_ragged_f32")
+                    _dev(audio, r0), fmt, k, L, _dev(lengths, r0), _dev(self.taps_dev), self.n_taps_total, _host(self.designs),
+                    len(self.designs), _dev(rows_dev, r0), n_out, _dev(out, r0), _dev(samples, r0), _dev(bins, r0), time_bins,
+                    stream), "lsm_speed_ragged_f32")
         return out, samples, bins
 
 
@@ -1844,26 +1837,7 @@ class SilenceTrimmer:
             raise ValueError(f"pad_bins must be >= 0, got {pad_bins}")
         if not RAGGED_MIN_BINS <= self.min_bins <= TRIM_MAX_BINS:
             raise ValueError(f"min_bins must lie in [{RAGGED_MIN_BINS}, {TRIM_MAX_BINS}], got {min_bins}")
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
-
-    def _lengths(self, lengths, n: int, n_samples: int):
-        """``lengths`` as the int32 device tensor the kernel reads, or None: host integers checked against the row, a device
-        tensor taken as it is -- never read back, the kernel clamps it."""
-        if lengths is None:
-            return None
-        if torch.is_tensor(lengths) and lengths.is_cuda:
-            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
-                raise ValueError(f"lengths must hold {n} int32 values, got {lengths.dtype} {tuple(lengths.shape)}")
-            return lengths.to(self.device).contiguous()
-        arr = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
-        if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
-            raise ValueError(f"lengths must be {n} integers, got {arr.dtype} {arr.shape}")
-        bad = np.nonzero((arr < 0) | (arr > n_samples))[0]
-        if len(bad):
-            raise ValueError(f"lengths {arr[bad].tolist()} of clips {bad.tolist()} outside [0, {n_samples}]")
-        return torch.from_numpy(arr.astype(np.int32)).to(self.device, non_blocking=True)
+        self.lib, self.device = _open(device)
 
     def trim(self, audio, lengths=None, time_bins: int | None = None, out: torch.Tensor | None = None,
              want_energy: bool = False):
@@ -1885,14 +1859,11 @@ class SilenceTrimmer:
         if self.min_bins > time_bins:
             raise ValueError(f"min_bins = {self.min_bins} exceeds the row's {time_bins} time bins")
         if out is not None:
-            if not torch.is_tensor(out) or out.dtype != torch.float32 or out.ndim != 2 or out.shape[0] != n \
-                    or out.shape[1] < RAGGED_HOP * time_bins or not out.is_contiguous() or out.device != self.device:
-                raise ValueError(f"out must be a contiguous float32 ({n}, >= {RAGGED_HOP * time_bins}) tensor on {self.device}")
-            if out is audio or (n and out.data_ptr() == audio.data_ptr()):
-                raise ValueError("out must not be audio: a clip moves towards the start of its row")
+            checked_out(out, (n, RAGGED_HOP * time_bins), self.device, audio, "a clip moves towards the start of its row",
+                        at_least=True)                                  # a wider row is welcome: the kernel takes its stride
         with torch.cuda.device(self.device):
             audio = audio.to(self.device).contiguous()
-            counts = self._lengths(lengths, n, L)
+            counts = None if lengths is None else checked_lengths(lengths, n, L, self.device)
             if out is None:
                 out = torch.empty((n, RAGGED_HOP * time_bins), dtype=torch.float32, device=self.device)
             bins = torch.empty((n,), dtype=torch.int32, device=self.device)
@@ -1900,10 +1871,8 @@ class SilenceTrimmer:
             energy = torch.empty((n, time_bins), dtype=torch.float64, device=self.device) if want_energy else None
             if n:
                 _lib.check(self.lib.lsm_trim_silence_f32(
-                    _dev(audio), n, L, time_bins, _dev(counts) if counts is not None else None, C.c_double(self.ratio),
-                    self.pad_bins, self.min_bins, _dev(out), int(out.shape[1]), _dev(first), _dev(bins),
-                    _dev(energy) if want_energy else None, torch.cuda.current_stream(self.device).cuda_stream),
-                    "lsm_trim_silence_f32")
+                    _dev(audio), n, L, time_bins, _dev(counts), C.c_double(self.ratio), self.pad_bins, self.min_bins, _dev(out),
+                    int(out.shape[1]), _dev(first), _dev(bins), _dev(energy), _stream(self.device)), "lsm_trim_silence_f32")
         return (out, bins, first, energy) if want_energy else (out, bins, first)
 
 
@@ -1980,9 +1949,7 @@ class EndpointStream(_StreamBank):
             raise ValueError(f"hang_bins must lie in [max(pad_bins, 1) = {max(P, 1)}, {ENDPOINT_MAX_WINDOW}], got {hang_bins}")
         if not RAGGED_MIN_BINS <= A <= M:
             raise ValueError(f"min_span_bins must lie in [{RAGGED_MIN_BINS}, max_bins = {M}], got {min_span_bins}")
-        _lib.require_gpu()
-        self.lib = _lib.load()
-        self.device = indexed_device(device)
+        self.lib, self.device = _open(device)
         self._new_state(self.lib.lsm_endpoint_state_bytes(W, M))
         self._outputs = {}                                              # per n_hops: the slot buffers of a push
 
@@ -2052,10 +2019,9 @@ class EndpointStream(_StreamBank):
                     torch.zeros((n,), dtype=torch.int32, device=self.device))
             U = int(out.bins.shape[0]) // n
             _lib.check(self.lib.lsm_endpoint_stream_f32(
-                _dev(audio), n, H, _dev(counts) if counts is not None else None, _dev(ends) if ends is not None else None,
-                C.c_double(self.ratio), C.c_double(self.floor), self.window_bins, self.pad_bins, self.hang_bins,
-                self.min_span_bins, M, _dev(self.state), _dev(self.state), U, _dev(out.audio), _dev(out.bins), _dev(out.first),
-                _dev(out.flags), _dev(out.count), None, None, torch.cuda.current_stream(self.device).cuda_stream),
+                _dev(audio), n, H, _dev(counts), _dev(ends), C.c_double(self.ratio), C.c_double(self.floor), self.window_bins,
+                self.pad_bins, self.hang_bins, self.min_span_bins, M, _dev(self.state), _dev(self.state), U, _dev(out.audio),
+                _dev(out.bins), _dev(out.first), _dev(out.flags), _dev(out.count), None, None, _stream(self.device)),
                 "lsm_endpoint_stream_f32")
         return out
 

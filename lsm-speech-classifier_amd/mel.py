@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .frontend import _dev, _host        # the package's one pair of pointer helpers
 
 SAMPLE_RATE = 16000
 N_FFT = 2048
@@ -84,10 +85,9 @@ class MelSpectrogram:
     def power(self, audio: torch.Tensor) -> torch.Tensor:
         B = audio.shape[0]
         out = torch.empty((B, self.n_mels, self.n_frames), dtype=torch.float32, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
         _lib.check(self.lib.lsm_mel_power_f32(
-            p(audio), B, self.n_samples, N_FFT, self.hop, self.n_frames, p(self.window),
-            p(self.twiddle), p(self.basis), p(self.lo), p(self.hi), self.n_mels, p(out),
+            _dev(audio), B, self.n_samples, N_FFT, self.hop, self.n_frames, _dev(self.window),
+            _dev(self.twiddle), _dev(self.basis), _dev(self.lo), _dev(self.hi), self.n_mels, _dev(out),
             torch.cuda.current_stream(self.device).cuda_stream), "lsm_mel_power_f32")
         return out
 
@@ -129,17 +129,16 @@ class MelSpectrogram:
             ws = workspace
             if ws.dtype != torch.uint8 or ws.numel() < need or ws.device != raster.device or ws.data_ptr() % 256:
                 raise ValueError(f"workspace must be a zero-initialised, 256-byte aligned uint8 tensor of >= {need} bytes")
-        p = lambda t: C.c_void_p(t.data_ptr())
-        h = lambda a: C.c_void_p(a.ctypes.data)
         on = np.ascontiguousarray(on, dtype=np.float32)
         off = np.ascontiguousarray(off, dtype=np.float32)
-        args = (p(audio), B, self.n_samples, N_FFT, self.hop, self.n_frames, p(self.window), p(self.twiddle),
-                p(self.basis), p(self.lo), p(self.hi), self.n_mels, C.c_float(AMIN), C.c_float(TOP_DB), int(time_bins),
-                h(on), h(off), len(on), int(redundancy), p(raster), p(ws), int(ws.numel()))
+        args = (_dev(audio), B, self.n_samples, N_FFT, self.hop, self.n_frames, _dev(self.window), _dev(self.twiddle),
+                _dev(self.basis), _dev(self.lo), _dev(self.hi), self.n_mels, C.c_float(AMIN), C.c_float(TOP_DB), int(time_bins),
+                _host(on), _host(off), len(on), int(redundancy), _dev(raster), _dev(ws), int(ws.numel()))
         if masks is None:
             _lib.check(self.lib.lsm_mel_spikes_f32(*args, stream), "lsm_mel_spikes_f32")
         else:
-            _lib.check(self.lib.lsm_mel_spikes_masked_f32(*args, p(masks[0]), p(masks[1]), stream), "lsm_mel_spikes_masked_f32")
+            _lib.check(self.lib.lsm_mel_spikes_masked_f32(*args, _dev(masks[0]), _dev(masks[1]), stream),
+                       "lsm_mel_spikes_masked_f32")
         return raster
 
     def power_db(self, audio: torch.Tensor) -> torch.Tensor:
@@ -147,7 +146,6 @@ class MelSpectrogram:
         S = self.power(audio)
         out = torch.empty_like(S)
         _lib.check(self.lib.lsm_power_to_db_f32(
-            C.c_void_p(S.data_ptr()), S.shape[0], S.shape[1] * S.shape[2], C.c_float(AMIN),
-            C.c_float(TOP_DB), C.c_void_p(out.data_ptr()), torch.cuda.current_stream(self.device).cuda_stream),
-            "lsm_power_to_db_f32")
+            _dev(S), S.shape[0], S.shape[1] * S.shape[2], C.c_float(AMIN), C.c_float(TOP_DB), _dev(out),
+            torch.cuda.current_stream(self.device).cuda_stream), "lsm_power_to_db_f32")
         return out

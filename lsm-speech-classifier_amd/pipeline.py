@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from .augment import AugmentChain, StepPlans
-from .frontend import as_float32, checked_counts, checked_mask, checked_pcm, checked_slots, indexed_device
+from .frontend import (_dev, _host, as_float32, checked_counts, checked_mask, checked_pcm, checked_slots, indexed_device,
+                       threshold_tables, RAGGED_HOP)
 
 DEFAULT_STREAMS = 6
 # front-end streams of their own (0 = rotation: every step keeps to one stream).  Measured at 128 filters / 1000
@@ -108,8 +109,7 @@ def step_fused(fe, net, audio, feature_keys=None, stats_out=None, features_out=N
     of ``net.run_batch(fe.encode(audio, mask=mask), feature_keys)[0]``; None makes exactly the unmasked call.  A shape the
     launch does not serve (`step_fused_supported`) raises: the caller makes the two launches."""
     from . import _lib
-    from .frontend import checked_mask, threshold_tables, upload_mask
-    from .snn import _dev, _host
+    from .frontend import upload_mask
     if mask is not None:
         checked_mask(mask, 1 if getattr(audio, "ndim", 2) == 1 else len(audio), fe.n_filters, fe.time_bins)
     audio, B, keys, key_ids, shape = _step_outputs(fe, net, audio, feature_keys, stats_out, features_out)
@@ -140,8 +140,7 @@ def step_fused_ragged(fe, net, audio, bins, feature_keys=None, stats_out=None, f
     ``fe.encode_ragged(audio, bins, mask=mask)`` followed by the ragged run; None makes exactly the unmasked call.  Needs
     `step_fused_supported(fe, net, B, form="ragged")` (with a mask: ``form="ragged-masked"``)."""
     from . import _lib
-    from .frontend import checked_mask, checked_ragged_bins, ragged_refusal, threshold_tables, upload_mask
-    from .snn import _dev, _host
+    from .frontend import checked_ragged_bins, ragged_refusal, upload_mask
     why = ragged_refusal(fe.n_samples, fe.time_bins)
     if why:
         raise ValueError(why)
@@ -181,8 +180,6 @@ def step_fused_state_supported(fe, net, n_clips: int) -> bool:
 
 def _front_args(fe, net, audio, B, workspace):
     """The front-end half of a state step's argument list (up to and including coef_flags); inside the device context."""
-    from .frontend import threshold_tables
-    from .snn import _dev, _host
     on, off = threshold_tables(fe.thresholds, fe.gap, np.float64)
     ws, ws_bytes = fe._workspace_for(B, workspace)
     return (net._handle, _dev(audio), B, fe.n_samples, _dev(fe.coefs), fe.n_filters, fe.nwin, fe.hop, fe.ncols, fe.time_bins,
@@ -197,7 +194,6 @@ def step_fused_from(fe, net, audio, feature_keys=None, state=None, state_out=Non
     no raster is written.  Without `state` it is `step_fused`.  The other parameters are `step_fused`'s; masks and ragged
     batches are not offered.  Needs `step_fused_state_supported(fe, net, B)`."""
     from . import _lib
-    from .snn import _dev, _host
     n = 1 if getattr(audio, "ndim", 2) == 1 else len(audio)
     first_step, src, dst = net._continuation(state, state_out, n)        # before any device work
     audio, B, keys, key_ids, shape = _step_outputs(fe, net, audio, feature_keys, stats_out, features_out)
@@ -220,7 +216,7 @@ def step_fused_segments(fe, net, audio, segment_steps: int, feature_keys=None, s
     records of ``net.run_segment_records``.  `rows_out`: a contiguous float32 (B, G, n_keys * N_out) tensor to write into.
     `state` / `state_out` / `stats_out` / `workspace`: as `step_fused_from`'s.  Needs `step_fused_state_supported`."""
     from . import _lib
-    from .snn import _check_stats_out, _dev, _host, _select_keys
+    from .snn import _check_stats_out, _select_keys
     S, T = int(segment_steps), int(fe.n_steps)
     if S < 1 or T < 1 or T % S != 0:
         raise _lib.LsmHipError(f"segment_steps = {S} must be >= 1 and divide the clip's {T} steps")
@@ -246,7 +242,7 @@ def step_fused_segments(fe, net, audio, segment_steps: int, feature_keys=None, s
         cumulative = torch.empty((B, shape[2]), dtype=torch.float32, device=fe.device) if keys else None
         _lib.check(fe.lib.lsm_step_fused_segments_f64(*front, int(first_step), _dev(src), _dev(dst),
                                                       _host(key_ids) if keys else None, len(keys), _dev(cumulative),
-                                                      _dev(stats_out), S, _dev(records), _dev(rows) if keys else None,
+                                                      _dev(stats_out), S, _dev(records), _dev(rows if keys else None),
                                                       fe._stream()), "lsm_step_fused_segments_f64")
     if state is not None:
         (state_out or state).steps_done = state.steps_done + T
@@ -711,6 +707,24 @@ class HotPath:
         return out
 
 
+def _stages_and_plans(speed, reverb, corrupt, mask=None, n_clips: int | None = None):
+    """``speed=``, ``reverb=``, ``corrupt=`` (each None or a ``(stage, plan)`` pair) and ``mask=`` of a listing function as ``(the
+    speed=, reverb=, mixer= keywords of HotPath and AugmentChain, the listing's StepPlans)``, checked to cover ``n_clips``."""
+    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
+    plans = StepPlans(speeds, reverbs, mixes, mask)
+    if n_clips is not None:
+        plans.check_covers(n_clips)
+    return dict(speed=sp, reverb=rv, mixer=mixer), plans
+
+
+def _pinned_float32(audio) -> torch.Tensor:
+    """``audio`` as a contiguous float32 host tensor, in pinned memory where the runtime grants it."""
+    host = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
+    with contextlib.suppress(RuntimeError):
+        return host.pin_memory() if len(host) else host
+    return host
+
+
 def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1024,
                         streams: int = DEFAULT_STREAMS, device_out: bool = False, time_segments: int = 1, corrupt=None,
                         reverb=None, speed=None, mask=None):
@@ -723,16 +737,9 @@ def features_from_audio(audio: np.ndarray, fe, net, feature_keys, batch: int = 1
     n clips)``: every batch goes through these stages on the device, in this order (`augment.AugmentChain`; SPEC.md §1.12,
     §1.11, §1.10), with its slice of each plan, before its front end.  `mask` = a ``frontend.MaskPlan`` of the n clips: every
     batch's front end masks its slice of the plan inside the encoder (SPEC.md §1.13)."""
-    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
-    plans = StepPlans(speeds, reverbs, mixes, mask)
-    plans.check_covers(len(audio))
-    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, mixer=mixer, reverb=rv, speed=sp)
-    pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-    if len(pinned):
-        try:
-            pinned = pinned.pin_memory()
-        except RuntimeError:
-            pass
+    stages, plans = _stages_and_plans(speed, reverb, corrupt, mask, len(audio))
+    hp = HotPath(fe, net, feature_keys, streams=streams, time_segments=time_segments, **stages)
+    pinned = _pinned_float32(audio)
     with torch.cuda.device(hp.device):
         starts = range(0, len(pinned), batch)
         feats = hp._run((pinned[lo:lo + batch] for lo in starts), (plans.part(lo, lo + batch) for lo in starts))
@@ -751,25 +758,18 @@ def fit_from_audio(audio: np.ndarray, labels, fe, net, feature_keys, stats, batc
     event of the push releases the buffer to the step that takes it next.  No row outlives its push and the host waits for
     nothing per step (but for `HotPath`'s back-pressure); the call returns, after one synchronisation, the number of clips
     it has run.  The augmentation arguments are `features_from_audio`'s."""
-    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
-    plans = StepPlans(speeds, reverbs, mixes, mask)
-    plans.check_covers(len(audio))
+    stages, plans = _stages_and_plans(speed, reverb, corrupt, mask, len(audio))
     labels = np.ascontiguousarray(labels, dtype=np.int32)
     if labels.shape != (len(audio),):
         raise ValueError(f"labels must hold one value per clip, got {labels.shape} for {len(audio)} clips")
-    hp = HotPath(fe, net, feature_keys, streams=streams, mixer=mixer, reverb=rv, speed=sp)
+    hp = HotPath(fe, net, feature_keys, streams=streams, **stages)
     if indexed_device(stats.device) != hp.device:
         raise ValueError(f"statistics on {stats.device}, pipeline on {hp.device}")
     n_keys = len(feature_keys) if feature_keys is not None else 8
     if n_keys * net.num_output_neurons != stats.D or n_keys != len(stats.feature_keys):
         raise ValueError(f"the statistics hold rows of {len(stats.feature_keys)} keys x {stats.n_out}, the pipeline gives "
                          f"{n_keys} keys x {net.num_output_neurons}")
-    pinned = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32))
-    if len(pinned):
-        try:
-            pinned = pinned.pin_memory()
-        except RuntimeError:
-            pass
+    pinned = _pinned_float32(audio)
     starts = list(range(0, len(pinned), batch))
     with torch.cuda.device(hp.device):
         cur = torch.cuda.current_stream(hp.device)
@@ -902,7 +902,6 @@ def _trimmed_listing(trim, audio, bins: np.ndarray, fe, device, batch: int, leng
     float32 (n, 160 * time_bins) DEVICE tensor, their bins as host int32)``.  Launches only, then one read-back of the bins.
     ``audio`` may be a device tensor (the perturbed listing) and ``lengths`` the int32 device tensor of its clips' samples;
     None: 160 * bins from the host."""
-    from .frontend import RAGGED_HOP
     n = len(bins)
     rows = torch.empty((n, RAGGED_HOP * fe.time_bins), dtype=torch.float32, device=device)
     kept = torch.empty((n,), dtype=torch.int32, device=device)
@@ -920,7 +919,7 @@ def _perturbed_listing(chain, speeds, audio: np.ndarray, bins: np.ndarray, fe, d
     utterance at ``160 * bins`` samples: -> ``(the perturbed rows, a float32 (n, 160 * time_bins) DEVICE tensor, their samples
     as an int32 DEVICE tensor, their bins as host int32)``.  Launches only: the host bins come from the length formula
     (`frontend.speed_ragged_lengths`), which also refuses, before any launch, an utterance that a speed leaves under 3 bins."""
-    from .frontend import RAGGED_HOP, RAGGED_MIN_BINS, speed_ragged_lengths
+    from .frontend import RAGGED_MIN_BINS, speed_ragged_lengths
     n, n_out = len(bins), RAGGED_HOP * fe.time_bins
     lengths = bins.astype(np.int64) * RAGGED_HOP
     new_bins = -(-speed_ragged_lengths(lengths, speeds.choice, chain.speed, n_out) // RAGGED_HOP)
@@ -976,23 +975,23 @@ def features_from_utterances(utterances, fe, net, feature_keys, batch: int = 102
     callable is called with the final bins; a ready `MaskPlan` drawn for the bins before the speed stage has its time bands
     placed against those old lengths (bits at or behind a clip's new end are ignored, §1.16).  Row r is the row of the whole
     chain on utterance r alone.  None: not one launch changes."""
-    from .frontend import RAGGED_HOP, pack_utterances
+    from .frontend import pack_utterances
     from .snn import _select_keys
-    (sp, speeds), (rv, reverbs), (mixer, mixes) = ((None, None) if pair is None else pair for pair in (speed, reverb, corrupt))
+    stages, plans = _stages_and_plans(speed, reverb, corrupt)
     audio, bins = pack_utterances(utterances, fe.time_bins)
     n = len(bins)
     keys, _ = _select_keys(feature_keys)
     batch = max(1, int(batch))
-    chain = AugmentChain(speed=sp, reverb=rv, mixer=mixer)
+    chain = AugmentChain(**stages)
     with torch.cuda.device(net.device):
         samples = None
-        if speeds is not None:
-            chain.refuse(StepPlans(speed=speeds))
-            StepPlans(speed=speeds).check_covers(n)
-            audio, samples, bins = _perturbed_listing(chain, speeds, audio, bins, fe, net.device, batch)
+        if plans.speed is not None:
+            chain.refuse(StepPlans(speed=plans.speed))
+            StepPlans(speed=plans.speed).check_covers(n)
+            audio, samples, bins = _perturbed_listing(chain, plans.speed, audio, bins, fe, net.device, batch)
         if trim is not None:
             audio, bins = _trimmed_listing(trim, audio, bins, fe, net.device, batch, samples)
-        plans = StepPlans(None, reverbs, mixes, mask(bins) if callable(mask) else mask)
+        plans = plans._replace(speed=None, mask=mask(bins) if callable(mask) else mask)        # what is left, at the final bins
         plans.check_covers(n)
         feats = torch.zeros((n, len(keys) * net.num_output_neurons), dtype=torch.float32, device=net.device)
         order = np.argsort(-bins.astype(np.int64), kind="stable")
@@ -1410,7 +1409,7 @@ class UtteranceBank:
     endpoint detector; with any of them ``hops`` are host integers."""
 
     def __init__(self, endpoint, fe, net, feature_keys=None, readout=None, resampler=None, reverb=None, mixer=None, fused=None):
-        from .frontend import RAGGED_HOP, ragged_refusal
+        from .frontend import ragged_refusal
         if not hasattr(endpoint, "max_utterances") or not hasattr(endpoint, "push"):
             raise ValueError("UtteranceBank needs a frontend.EndpointStream")
         M = int(endpoint.max_bins)
@@ -1520,7 +1519,7 @@ def utterances_from_recordings(recordings, endpoint_params=None, chunk_hops: int
     recording with ``finish`` at its end.  Returns ``(utterances, table)``: a list of 1-D float32 host arrays and an int64
     array (len, 4) of ``(recording, first_bin, bins, flags)`` per utterance, ordered by recording, then by time -- what
     `features_from_utterances` takes.  One read-back per push."""
-    from .frontend import RAGGED_HOP, EndpointStream
+    from .frontend import EndpointStream
     arrays = [np.ascontiguousarray(np.asarray(r, dtype=np.float32)) for r in recordings]
     for r, a in enumerate(arrays):
         if a.ndim != 1:

@@ -244,12 +244,12 @@ class DeviceReadout:
         self.classes = up(model.classes)
 
     def _model_args(self):
-        import ctypes as C
-        return [C.c_void_p(t.data_ptr()) for t in (self.mean, self.scale, self.coef, self.intercept)]
+        from .frontend import _dev
+        return [_dev(t) for t in (self.mean, self.scale, self.coef, self.intercept)]
 
     def score_rows(self, features):
         """``features`` float32 (..., D) on the device -> ``(logits, labels)``: float64 (..., C) and int32 (...)."""
-        import ctypes as C
+        from .frontend import _dev
         m = self.model
         D = m.n_keys * m.n_out
         if features.dtype != torch.float32 or features.dim() < 1 or features.shape[-1] != D or features.device != self.device:
@@ -263,14 +263,14 @@ class DeviceReadout:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             self._lib.check(self.lib.lsm_readout_rows_f32(
-                *self._model_args(), C.c_void_p(flat.data_ptr()), n, m.n_keys, m.n_out, m.n_classes,
-                C.c_void_p(logits.data_ptr()), C.c_void_p(labels.data_ptr()), stream), "lsm_readout_rows_f32")
+                *self._model_args(), _dev(flat), n, m.n_keys, m.n_out, m.n_classes, _dev(logits), _dev(labels), stream),
+                "lsm_readout_rows_f32")
         return logits.reshape(lead + (m.n_classes,)), labels.reshape(lead)
 
     def score_windows(self, net, records, segment_steps: int, window_segments: int = 1, hop_segments: int = 1, segments=None):
         """``SNN.segment_features(records, ..., segments=...)`` followed by ``score_rows``, in one launch that writes no
         feature row: ``(logits, labels)``, float64 (B, W, C) and int32 (B, W).  Rows past a clip's windows are zeros and -1."""
-        import ctypes as C
+        from .frontend import _dev, _host
         from .snn import _select_keys
         m = self.model
         if net.num_output_neurons != m.n_out or net.device != self.device:
@@ -292,10 +292,9 @@ class DeviceReadout:
             stream = torch.cuda.current_stream(self.device).cuda_stream
             counts = net._device_counts(segments, host_segments) if segments is not None else None
             self._lib.check(self.lib.lsm_readout_windows(
-                net._handle, *self._model_args(), C.c_void_p(records.data_ptr()), B, G,
-                C.c_void_p(counts.data_ptr()) if counts is not None else None, int(segment_steps), int(window_segments),
-                int(hop_segments), C.c_void_p(key_ids.ctypes.data), len(keys), m.n_classes,
-                C.c_void_p(logits.data_ptr()), C.c_void_p(labels.data_ptr()), stream), "lsm_readout_windows")
+                net._handle, *self._model_args(), _dev(records), B, G, _dev(counts), int(segment_steps), int(window_segments),
+                int(hop_segments), _host(key_ids), len(keys), m.n_classes, _dev(logits), _dev(labels), stream),
+                "lsm_readout_windows")
         return logits, labels
 
     def class_of(self, labels):
@@ -372,8 +371,8 @@ class RidgeStatistics:
         """Add the rows ``features`` float32 (n, D) with ``labels`` int32 (n), both on this object's GPU, on the current
         stream; a row whose label lies outside [0, n_classes) is skipped.  Pushes on one object must be stream-ordered by the
         caller."""
-        import ctypes as C
         from . import _lib
+        from .frontend import _dev
         lib = _lib.load()
         _lib.require_gpu()
         if self.device.type != "cuda":
@@ -393,8 +392,8 @@ class RidgeStatistics:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(lib.lsm_fit_accumulate_f32(
-                C.c_void_p(features.data_ptr()), C.c_void_p(labels.data_ptr()), n, len(self.feature_keys), self.n_out,
-                self.n_classes, *[C.c_void_p(t.data_ptr()) for t in self._fields()], stream), "lsm_fit_accumulate_f32")
+                _dev(features), _dev(labels), n, len(self.feature_keys), self.n_out, self.n_classes,
+                *[_dev(t) for t in self._fields()], stream), "lsm_fit_accumulate_f32")
 
     def merge(self, other: "RidgeStatistics") -> "RidgeStatistics":
         """Add ``other``'s statistics to these, in this order: gram, sums and counts by element-wise addition, then the

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .frontend import _dev, _host        # the package's one pair of pointer helpers
 from .reservoir import Reservoir, SimulationParams, build_reservoir
 
 # FEATURE_SETS['all'] order (extract_lsm_features.py:20-22) = key ids of the C ABI
@@ -98,10 +99,6 @@ class ReservoirState:
         return self._bits(16 + 6 * self._np + self._np // 8)
 
 
-def _dev(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _select_keys(feature_keys):
     """``(keys, key_ids)``: the names of ``feature_keys`` that are FEATURE_KEYS, in the given order (``None``: all of them),
     and their ids in the C ABI as an int32 array."""
@@ -113,10 +110,6 @@ def _check_stats_out(stats_out, n_clips: int, device) -> None:
     if stats_out is not None and (stats_out.dtype != torch.int32 or tuple(stats_out.shape) != (n_clips, 2)
                                   or not stats_out.is_contiguous() or stats_out.device != device):
         raise ValueError(f"stats_out must be a contiguous int32 ({n_clips}, 2) tensor on {device}")
-
-
-def _host(a):
-    return C.c_void_p(a.ctypes.data)
 
 
 class SNN:
